@@ -20,14 +20,23 @@ Two ways to be N ranks:
 
 A *step* is one full pass of the hot path over this rank's shard: create the operator chain (fdb_plan_create), scan every
 resident record with the fused HIP kernel (fdb_plan_push_batches), merge (N > 1) and produce the final Arrow record
-(fdb_plan_finish). Inputs are resident in HBM before the timed region; the result of the timed path is checked against a numpy
-restatement of the query (summed over the ranks at N > 1).
+(fdb_plan_finish). Inputs are resident in HBM before the timed region; with ``--full`` the result of the timed path is checked
+against a numpy restatement of the query (summed over the ranks at N > 1).
 
-Rank 0 prints ONE JSON line: the metric, the HBM roofline of the scan kernel (hipEvent-timed on the plan's own stream over the
-timed steps), the CPU baseline (the oracle's restatement of the reference's algorithm on this box's host cores, bounded
-sample) and — at N = 1 with the default workload — ``other_configs``: the same measurement for BASELINE.json's cfg 3 and
-cfg 5, the device-side ``filter()`` compaction (``select``), the PCIe-inclusive ``fdb_plan_push`` of host records
+Rank 0 prints ONE JSON line: the metric, ``ms_per_step`` (wall time of one timed step) and the HBM roofline of the scan kernel
+(hipEvent-timed on the plan's own stream over the timed steps). A plain run does only that: set up, one first step (it pays
+the run-time compilation of the step's kernels), ``--warmup`` steps, ``--steps`` timed steps, the line.
+
+``--full`` adds everything else the benchmark measures or checks: the timed path's result against a numpy restatement of the
+query (and, at N = 1, against the oracle on the first resident record), this box's plain read kernel as the rooflines'
+``measured_read_ceiling``, the CPU baseline (the oracle's restatement of the reference's algorithm on this box's host cores,
+bounded sample) and — at N = 1 with the default workload — ``other_configs``: the same measurement for BASELINE.json's cfg 3
+and cfg 5, the device-side ``filter()`` compaction (``select``), the PCIe-inclusive ``fdb_plan_push`` of host records
 (``host_records``), Parquet row groups decoded on the device (``parquet``) and what run-time specialisation cost (``jit``).
+
+``--dump-outputs DIR`` writes the result of the last timed step (rank 0's record) as ``DIR/<column>.npy``, float64, rows in key
+order (see ``dump_outputs``), so that two builds can be compared output for output: the inputs are seeded and the same for the
+same arguments.
 """
 from __future__ import annotations
 
@@ -75,13 +84,22 @@ def parse_args(argv=None):
     ap.add_argument("--per-record-launch", action="store_true", help="one kernel launch per resident record instead of one per scan")
     ap.add_argument("--force-merge", action="store_true", help="run the RCCL merge path even with one rank (functional check on a 1-GPU box)")
     ap.add_argument("--torch-merge", action="store_true", help="merge through torch.distributed (frostdb_amd.distributed) instead of the C ABI's fdb_comm_*")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-oracle-parity", action="store_true", help="skip the oracle-vs-GPU comparison on the first resident record (checked.oracle)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the cfg 3 / cfg 5 / select / host_records / parquet lines of the default run")
-    ap.add_argument("--only-other", default="", help="comma-separated subset of other_configs to run (cfg3,cfg5,cfg5_1B,cfg5_sorted,select,host_records,parquet,…)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-oracle-parity", action="store_true", help="--full without the oracle-vs-GPU comparison on the first resident record (checked.oracle)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the cfg 3 / cfg 5 / select / host_records / parquet lines of the default run")
+    ap.add_argument("--only-other", default="", help="with --full: comma-separated subset of other_configs to run (cfg3,cfg5,cfg5_1B,cfg5_sorted,select,host_records,parquet,…)")
     ap.add_argument("--cpu-sample-seconds", type=float, default=3.0)
     ap.add_argument("--sweep", action="store_true", help="kernel geometry sweep first (tuning aid; table on stderr)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also check the result (numpy, oracle), measure the read ceiling and the CPU baseline, and (default workload, N = 1) run other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's result as DIR/<column>.npy (float64, rows in key order; a seeded sample beyond 60 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.only_other and not args.full:
+        ap.error("--only-other selects among the lines of --full")
+    return args
 
 
 def shard_rows(total: int, world: int, rank: int) -> int:
@@ -277,17 +295,18 @@ class Workload:
         sizes = [min(br, rows - i * br) for i in range(n_chunks)]
         self.n_chunks = n_chunks
         self.select_expected = []  # rows of the first records with value > SELECT_THRESHOLD (the `select` line)
+        check = args.full  # (the numpy expectation of the query: what --full checks the timed path's result against)
 
         def gen(i):
             if config == 5:
                 b = synth.cfg5_chunk(rank, i, sizes[i], n_groups=args.groups, sorted_rows=self.ordered, of_chunks=n_chunks if self.ordered else 0, wide_dicts=self.wide_dicts)
-                return b, expected_cfg5(b), None
+                return b, (expected_cfg5(b) if check else None), None
             b = synth.prometheus_chunk(rank, i, sizes[i], row_base=i * br, cfg3=(config == 3), sorted_by_path=n_chunks if self.ordered else 0)
             sel = None
             if i < keep_host:
                 v = b.column(b.schema.get_field_index("value")).to_numpy()
                 sel = int((v > SELECT_THRESHOLD).sum())
-            return b, (expected_cfg2(b) if config == 2 else expected_cfg3(b)), sel
+            return b, ((expected_cfg2(b) if config == 2 else expected_cfg3(b)) if check else None), sel
 
         if config == 5:
             synth.cfg5_chunk(rank, 0, 8, n_groups=args.groups)  # builds the per-group digit tables once, before the thread pool
@@ -296,7 +315,8 @@ class Workload:
         workers = gen_threads or max(1, min(16, n_chunks, (os.cpu_count() or 8) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))))
         with ThreadPoolExecutor(max_workers=workers) as ex:
             for i, (b, e, sel) in enumerate(ex.map(gen, range(n_chunks))):
-                self.expected = list(e) if self.expected is None else fold_expected(config, self.expected, e)
+                if e is not None:
+                    self.expected = list(e) if self.expected is None else fold_expected(config, self.expected, e)
                 if args.host_records or i < keep_host:
                     self.host_batches.append(b)
                     self.select_expected.append(sel)
@@ -365,11 +385,12 @@ class Workload:
         return {"groups_out": len(rows), "selected_rows": int(cnt.sum())}
 
 
-def run_workload(args, wl, steps, warmup, group, comm, total_rows, resident_finish=False, push_order=None):
-    """Correctness step, warm-up, then the timed region (barrier + device sync on both sides, max over ranks).
+def run_workload(args, wl, steps, warmup, group, comm, total_rows, resident_finish=False, push_order=None, keep_last=False):
+    """First step (checked with --full), warm-up, then the timed region (barrier + device sync on both sides, max over ranks).
     `push_order`: the resident records are pushed in this order instead of the table's (an ordered workload then arrives as several ordered sets).
     `resident_finish`: the step ends with fdb_plan_finish_batch (the result record stays in HBM, for a consumer on the device)
-    instead of fdb_plan_finish (Arrow record on the host)."""
+    instead of fdb_plan_finish (Arrow record on the host).
+    `keep_last`: the result's `last_out` is the record the last timed step returned (else None)."""
     import numpy as np
     from frostdb_amd import physicalplan as pp
     rank, device, world = wl.rank, wl.device, group.world
@@ -437,7 +458,7 @@ def run_workload(args, wl, steps, warmup, group, comm, total_rows, resident_fini
     first_step_ms = (time.perf_counter() - t_first) * 1e3
     jit1 = pp.jit_stats()
     checked = None
-    if not args.host_records:
+    if args.full and not args.host_records:
         expected = [group.reduce(np.asarray(e), op) for e, op in zip(wl.expected, EXPECTED_OPS[wl.config])]
         if wl.config == 5 and world > 1:  # the all-to-all merge leaves every rank with its own disjoint shard of the groups
             sums = group.reduce(np.array([float(out.column(out.schema.names.index("sum(value)")).to_numpy().sum())]), "sum")
@@ -481,12 +502,14 @@ def run_workload(args, wl, steps, warmup, group, comm, total_rows, resident_fini
     t0 = time.perf_counter()
     k_ms, k_bytes, k_launches, kernel_name, merge_ms = 0.0, 0, 0, "", 0.0
     for _ in range(steps):
-        _, st = step(timing=True)
+        last_out, st = step(timing=True)
         k_ms += st["kernel_ms"]; k_bytes += st["algorithmic_bytes"]; k_launches += st["launches"]; merge_ms += st["merge_ms"]
         kernel_name = st["kernel"]
     group.barrier()
     group.device_sync()
     elapsed = time.perf_counter() - t0
+    if not keep_last:
+        last_out = None
     elapsed = float(group.reduce(np.array([elapsed]), "max")[0])
     # every rank's own kernel figures (rank order): the scan is rank-local, so the roofline fraction is a per-GPU quantity
     # (rccl_ranks_seen: what the transport itself reports as the communicator's size — ncclCommCount for RCCL — so that a line
@@ -498,7 +521,7 @@ def run_workload(args, wl, steps, warmup, group, comm, total_rows, resident_fini
     return {"elapsed": elapsed, "k_ms": k_ms, "k_bytes": k_bytes, "k_launches": k_launches, "kernel": kernel_name, "checked": checked, "after_finish": getattr(step, "after_finish", None),
             "per_rank": per_rank, "merge_ms": max(p["merge_ms_per_step"] for p in per_rank),
             "first_step_ms": first_step_ms, "jit_compiled": jit1["compiled"] - jit0["compiled"], "jit_compile_ms": jit1["compile_ms"] - jit0["compile_ms"],
-            "jit_disk_loads": jit1["disk_loads"] - jit0["disk_loads"]}
+            "jit_disk_loads": jit1["disk_loads"] - jit0["disk_loads"], "last_out": last_out}
 
 
 def traffic_for(tag, rows, kernel_name):
@@ -548,6 +571,51 @@ def claim_stdout():
 def emit(text):
     sys.stdout.flush()
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (text + "\n").encode())
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # (the arrays' bytes: with the .npy headers under 64 MB in all)
+
+
+def dump_outputs(rec, out_dir, limit_bytes=DUMP_LIMIT_BYTES, seed=0):
+    """`rec` — the Arrow record the timed path returned — as `out_dir/<column>.npy`, one float64 array per column, plus
+    `num_rows.npy`. A hash aggregate emits its groups in no particular order, so the rows are put in key order first (string columns,
+    then the others, NULL last); a string column is written as the rank of each value among the column's distinct values (NULL: -1).
+    More than `limit_bytes` in all: a fixed, seeded sample of the ordered rows, the same rows for the same row count."""
+    import re
+
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    assert rec is not None, "--dump-outputs: this rank's timed path returned no record"
+    cols = {}
+    for name, col in zip(rec.schema.names, rec.columns):
+        if pa.types.is_dictionary(col.type):
+            col = col.dictionary_decode()
+        cols[name] = col
+    is_str = lambda t: pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)  # noqa: E731
+    names = [n for n in cols if is_str(cols[n].type)] + [n for n in cols if not is_str(cols[n].type)]
+    n = rec.num_rows
+    order = (pc.sort_indices(pa.table({n_: cols[n_] for n_ in names}), sort_keys=[(n_, "ascending") for n_ in names]).to_numpy()  # (NULLs sort last)
+             if n and names else np.arange(n))
+    keep = max(1, limit_bytes // (8 * (len(names) + 1)) - 1)
+    if n > keep:
+        order = order[np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name in names:
+        col = cols[name]
+        if is_str(col.type):
+            distinct = pc.unique(col.drop_null())
+            distinct = pc.take(distinct, pc.sort_indices(distinct))
+            arr = pc.fill_null(pc.index_in(col, value_set=distinct), -1).to_numpy(zero_copy_only=False).astype(np.float64)
+        else:
+            arr = col.to_numpy(zero_copy_only=False).astype(np.float64)  # (NULL: NaN)
+        fname = re.sub(r"[^A-Za-z0-9_.-]+", "_", name).strip("_") or "column"
+        assert fname not in files, f"--dump-outputs: two columns map to {fname}.npy"
+        files[fname] = arr[order]
+    files.setdefault("num_rows", np.array([n], dtype=np.float64))
+    for fname, arr in files.items():
+        np.save(os.path.join(out_dir, fname + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 # ---- the secondary measurements of the default N = 1 run (other_configs) --------------------------------------------------------
@@ -1041,20 +1109,23 @@ def run_rank(args, group, device, comm):
     else:
         rows, scaling, total_rows = total, "weak", total * world
     merging = world > 1 or args.force_merge
-    secondary = headline and world == 1 and not args.no_other_configs and not args.host_records
+    secondary = args.full and headline and world == 1 and not args.no_other_configs and not args.host_records
     wl = Workload(args, config, rows, rank, device, keep_host=4 if secondary else 0,
                   gen_threads=max(1, min(16, (os.cpu_count() or 8) // world)) if isinstance(group, ThreadGroup) else None)
     shard_sizes = group.gather(rows)
     assert sum(shard_sizes) == total_rows, (shard_sizes, total_rows)
-    r = run_workload(args, wl, args.steps, args.warmup, group, comm, total_rows, push_order=[int(x) for x in args.push_order.split(",") if x] or None)
+    r = run_workload(args, wl, args.steps, args.warmup, group, comm, total_rows, push_order=[int(x) for x in args.push_order.split(",") if x] or None,
+                     keep_last=bool(args.dump_outputs) and rank == 0)
     value = total_rows * args.steps / r["elapsed"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r.pop("last_out"), args.dump_outputs)
 
-    # ---- CPU baseline (rank 0, N = 1 only): the oracle's restatement on this box's host cores, bounded sample ----
+    # ---- CPU baseline (--full, rank 0, N = 1 only): the oracle's restatement on this box's host cores, bounded sample ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(wl.sample, wl.filt, wl.aggs, wl.groups, args.cpu_sample_seconds)
     ceiling = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         ceiling = pp.read_ceiling(device, 2 << 30, 5)  # plain read kernel on this box, this run
 
     tag = ("cfg1B" if rows == HEADLINE_ROWS and config == 2 else f"cfg{config}")

@@ -189,3 +189,48 @@ def test_self_launch_of_gpus_8_is_the_command_torch_distributed_run_expects(monk
     with pytest.raises(SystemExit) as e:
         b.self_launch(args)
     assert "refusing" in str(e.value)
+
+
+def test_plain_run_is_lean_and_the_rest_is_behind_full():
+    """`bench.py --gpus 1 --steps N --warmup W` times the headline and nothing else; the checks, the read ceiling, the CPU baseline
+    and other_configs run with --full only. --only-other picks among the lines of --full, so it asks for it."""
+    import pytest
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs == ""
+    assert b.parse_args(["--full", "--only-other", "select"]).full
+    with pytest.raises(SystemExit):
+        b.parse_args(["--only-other", "select"])
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_are_float64_arrays_in_key_order(tmp_path):
+    """--dump-outputs: one float64 .npy per result column, rows in key order whatever order the hash table emitted them in
+    (string keys as ranks among the column's values, NULL last as -1), so that two builds compare array for array."""
+    import pyarrow as pa
+    b = _bench()
+    rng = np.random.default_rng(3)
+    keys = [b"/api/%d" % i for i in range(50)] + [None]
+    sums = rng.random(len(keys)) * 1000.0
+    counts = rng.integers(1, 1 << 40, len(keys))
+    outs = []
+    for k, perm in enumerate((np.arange(len(keys)), rng.permutation(len(keys)))):
+        rec = pa.RecordBatch.from_arrays([pa.array([keys[i] for i in perm], pa.binary()).dictionary_encode(), pa.array(sums[perm]),
+                                          pa.array(counts[perm], pa.int64())], names=["labels.path", "sum(value)", "count(value)"])
+        d = tmp_path / str(k)
+        b.dump_outputs(rec, str(d))
+        outs.append({p.name: np.load(p) for p in d.iterdir()})
+    assert set(outs[0]) == {"labels.path.npy", "sum_value.npy", "count_value.npy", "num_rows.npy"}
+    for name in outs[0]:
+        assert outs[0][name].dtype == np.float64 and np.array_equal(outs[0][name], outs[1][name]), name
+    order = sorted(range(len(keys)), key=lambda i: (keys[i] is None, keys[i] or b""))
+    assert outs[0]["labels.path.npy"].tolist() == list(range(50)) + [-1]
+    assert np.array_equal(outs[0]["sum_value.npy"], sums[order]) and np.array_equal(outs[0]["count_value.npy"], counts[order].astype(np.float64))
+    assert outs[0]["num_rows.npy"].tolist() == [len(keys)]
+    # a result larger than the limit: a fixed, seeded sample of the ordered rows, under the limit in all
+    big = pa.RecordBatch.from_arrays([pa.array(np.arange(100_000, dtype=np.float64)[::-1])], names=["sum(value)"])
+    b.dump_outputs(big, str(tmp_path / "big"), limit_bytes=80_000)
+    b.dump_outputs(big, str(tmp_path / "big2"), limit_bytes=80_000)
+    s1, s2 = np.load(tmp_path / "big" / "sum_value.npy"), np.load(tmp_path / "big2" / "sum_value.npy")
+    assert 0 < s1.nbytes + 8 <= 80_000 and np.array_equal(s1, s2) and bool(np.all(np.diff(s1) > 0))

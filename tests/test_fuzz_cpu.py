@@ -22,14 +22,14 @@ def run_tool(args, env=None, timeout=240):
 
 
 @pytest.mark.timeout(300)
-def test_random_plan_descriptors_never_crash_explain():
-    out = run_tool([os.path.join(ROOT, "tools", "desc_fuzz.py"), "2500", "3"])
+def test_random_plan_descriptors_never_crash_explain(tmp_path):
+    out = run_tool([os.path.join(ROOT, "tools", "desc_fuzz.py"), "2500", "3"], env={"TMPDIR": str(tmp_path)})  # (where it logs the case it is on)
     assert "codes" in out
 
 
 @pytest.mark.timeout(300)
-def test_arrow_records_with_detectable_defects_come_back_as_error_codes():
-    out = run_tool([os.path.join(ROOT, "tools", "arrow_fuzz.py"), "1200", "3"])
+def test_arrow_records_with_detectable_defects_come_back_as_error_codes(tmp_path):
+    out = run_tool([os.path.join(ROOT, "tools", "arrow_fuzz.py"), "1200", "3"], env={"TMPDIR": str(tmp_path)})  # (where it logs the case it is on)
     assert "codes" in out
 
 

@@ -5,18 +5,27 @@ would catch and that five rounds of blind edits could have introduced: an import
 identifiers / struct fields the header does not declare, reference identifiers that do not exist, unbalanced syntax, and a
 Build patch that does not apply to the reference's physicalplan.go.
 """
+import hashlib
+import json
 import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "integration", "go", "gpuplan", "operator.go")
 PATCH = os.path.join(ROOT, "integration", "go", "patches", "physicalplan_operator_factory.diff")
 HEADER = os.path.join(ROOT, "include", "frostdb_amd.h")
-REF_PP = "/root/reference/query/physicalplan/physicalplan.go"
+# what is known of the reference's query/physicalplan and query/logicalplan, as data (tools/gen_go_reference_fixture.py)
+REF_FIXTURE = os.path.join(ROOT, "tests", "golden", "go_reference.json")
+PP_MARKERS = ("gpuplan", "tryFactory(FusedStage{", "flushPending()")
+
+
+def line_hash(line):
+    return hashlib.sha256(line.encode()).hexdigest()[:16]
+
+
+def reference():
+    with open(REF_FIXTURE) as f:
+        return json.load(f)
 
 
 def go_code(text):
@@ -167,33 +176,73 @@ def test_reference_identifiers_the_shim_uses_exist():
     stage_fields = set(re.findall(r"^\t(\w+)\s", re.search(r"type FusedStage struct \{(.*?)\n\}", added, flags=re.S).group(1), flags=re.M))
     for f in set(re.findall(r"\bst\.(\w+)", code)):
         assert f in stage_fields, f"FusedStage has no field {f}"
-    if not os.path.isdir("/root/reference/query"):
-        pytest.skip("reference tree not present on this host")
-
-    def defined(pkg_dir):
-        names = set()
-        for fn in os.listdir(pkg_dir):
-            if fn.endswith(".go") and not fn.endswith("_test.go"):
-                text = open(os.path.join(pkg_dir, fn)).read()
-                names |= set(re.findall(r"^(?:type|func|var|const) (\w+)", text, flags=re.M))
-                for block in re.findall(r"^(?:const|var) \((.*?)^\)", text, flags=re.M | re.S):
-                    names |= set(re.findall(r"^\t(\w+)", block, flags=re.M))
-        return names
-    pp = defined("/root/reference/query/physicalplan") | from_patch
-    lp = defined("/root/reference/query/logicalplan")
+    ref = reference()
+    pp = set(ref["physicalplan_names"]) | from_patch
+    lp = set(ref["logicalplan_names"])
+    assert {"Build", "Option", "PhysicalPlan"} <= pp and {"Expr", "Aggregation"} <= lp  # (the fixture is the packages' own surface)
     assert not (used_pp - pp), used_pp - pp
     assert not (used_lp - lp), used_lp - lp
 
 
-@pytest.mark.skipif(not (os.path.exists(REF_PP) and shutil.which("patch")), reason="needs the reference tree and patch(1)")
-def test_build_patch_applies_to_the_reference(tmp_path):
-    work = tmp_path / "physicalplan.go"
-    shutil.copy(REF_PP, work)
-    r = subprocess.run(["patch", "-p3", "--fuzz=0", str(work)], stdin=open(PATCH), capture_output=True, text=True, cwd=tmp_path)
-    assert r.returncode == 0, r.stdout + r.stderr
-    text = open(work).read()
-    code = go_code(text)
-    assert code.count("{") == code.count("}") and code.count("(") == code.count(")")
-    assert "gpuplan" not in text
+def patch_hunks(text):
+    """The hunks of a unified diff: (first old line, 1-based; [(tag, text)] with tag ' ', '-' or '+')."""
+    hunks = []
+    for line in text.split("\n"):
+        m = re.match(r"@@ -(\d+)(?:,\d+)? \+\d+(?:,\d+)? @@", line)
+        if m:
+            hunks.append((int(m.group(1)), []))
+        elif hunks and line[:1] in (" ", "-", "+"):
+            hunks[-1][1].append((line[0], line[1:]))
+    return hunks
+
+
+def apply_to_fingerprint(line_hashes, hunks):
+    """patch(1) at fuzz 0 against a file known only by its per-line hashes: every hunk's context and removed lines must match
+    consecutive lines of the file, at the hunk's own position or shifted by an offset (tried nearest first), in file order.
+    Returns the patched file as a list of ("ref", line index) / ("new", text)."""
+    out, pos, offset = [], 0, 0
+    n = len(line_hashes)
+    for start, body in hunks:
+        old = [line_hash(t) for tag, t in body if tag != "+"]
+        want = start - 1 + offset if old else start + offset
+        at = None
+        for d in range(0, n + 1):
+            for p in ((want + d, want - d) if d else (want,)):
+                if pos <= p <= n - len(old) and line_hashes[p:p + len(old)] == old:
+                    at = p
+                    break
+            if at is not None:
+                break
+        assert at is not None, f"hunk @@ -{start} does not apply to the reference's physicalplan.go"
+        offset = at - (start - 1 if old else start)
+        out += [("ref", i) for i in range(pos, at)]
+        i = at
+        for tag, t in body:
+            if tag == "+":
+                out.append(("new", t))
+            else:
+                if tag == " ":
+                    out.append(("ref", i))
+                i += 1
+        pos = i
+    out += [("ref", i) for i in range(pos, n)]
+    return out
+
+
+def test_build_patch_applies_to_the_reference():
+    ref = reference()["physicalplan_go"]
+    hunks = patch_hunks(open(PATCH).read())
+    assert len(hunks) >= 2
+    patched = apply_to_fingerprint(ref["line_sha256_16"], hunks)
+    removed = [t for _, body in hunks for tag, t in body if tag == "-"]
+    added = [t for _, body in hunks for tag, t in body if tag == "+"]
+    assert len(patched) == len(ref["line_sha256_16"]) - len(removed) + len(added)
+    # counts of the patched file = the reference's, less what the hunks remove, plus what they add
+    count = lambda lines, s: sum(ln.count(s) for ln in lines)  # noqa: E731
+    code_removed, code_added = [go_code(t) for t in removed], [go_code(t) for t in added]
+    br = {c: ref["code_brackets"][c] - count(code_removed, c) + count(code_added, c) for c in "{}()"}
+    assert br["{"] == br["}"] and br["("] == br[")"], br
+    marks = {m: ref["markers"][m] - count(removed, m) + count(added, m) for m in PP_MARKERS}
+    assert marks["gpuplan"] == 0
     # the cases Build consults the factory in
-    assert text.count("tryFactory(FusedStage{") == 2 and "flushPending()" in text
+    assert marks["tryFactory(FusedStage{"] == 2 and marks["flushPending()"] > 0

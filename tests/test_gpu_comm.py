@@ -411,7 +411,7 @@ def test_bench_two_ranks_over_the_in_process_transport_is_cfg4_sharded():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--force-local", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--force-local", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=850, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

@@ -310,7 +310,7 @@ def test_bench_gpus_2_one_process_per_rank_reports_two_ranks_inside_the_communic
     fdb_comm_init_rank) on this 1-GPU box: the ranks share the device (FDB_BENCH_TEST_SHARE_DEVICE), the control plane runs over
     gloo, the merge over the stand-in library — the line's rccl_ranks_seen must say 2 on both ranks, the merged result is checked
     inside bench.py against the numpy expectation summed over the ranks."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "40000000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "40000000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=850, cwd=ROOT, env=child_env(fake_lib, FDB_BENCH_TEST_SHARE_DEVICE="1"))
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip().startswith("{")]

@@ -16,10 +16,10 @@ PASSES = {
     "cfg5_sorted_wide": ("fdb_hash_kernel", "fdb_hash_kernel(runs, medium)", 100_000_000, "python bench.py --config 5 --cfg5-sorted --cfg5-wide-dicts --steps 5 --warmup 1 --no-cpu-baseline --no-oracle-parity"),
     "cfg5_sorted_widerec": ("fdb_hash_kernel", "fdb_hash_kernel(runs, wide)", 100_000_000, "env FDB_RUNS_WIDE=1 python bench.py --config 5 --cfg5-sorted --steps 5 --warmup 1 --no-cpu-baseline --no-oracle-parity"),
     "cfg2_sorted": ("fdb_plan_kernel", "fdb_plan_kernel", 100_000_000, "python bench.py --config 2 --cfg2-sorted --steps 10 --warmup 2 --no-cpu-baseline --no-oracle-parity"),
-    "cfg5_1B": ("fdb_hash_kernel", "fdb_hash_kernel", 1_000_000_000, "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --only-other cfg5_1B"),
+    "cfg5_1B": ("fdb_hash_kernel", "fdb_hash_kernel", 1_000_000_000, "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --full --only-other cfg5_1B"),
     # filter(): a step is several kernels — the traffic of a step is the sum of their per-launch means (each runs once per step)
     "select": (["fdb_select_kernel", "compact_multi_kernel", "zero_regions_kernel"], "fdb_select_kernel + compact_multi_kernel", 100_000_000,
-               "python bench.py --rows 100000000 --steps 5 --warmup 1 --no-cpu-baseline --only-other select --no-oracle-parity"),
+               "python bench.py --rows 100000000 --steps 5 --warmup 1 --no-cpu-baseline --full --only-other select --no-oracle-parity"),
 }
 
 

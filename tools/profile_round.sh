@@ -11,8 +11,8 @@ TAG=${1:-round6}
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/$TAG; [ -z "${ONLY_PROF:-}" ] && rm -rf $O; mkdir -p $O
 if [ -z "${ONLY_PROF:-}" ]; then  # (ONLY_PROF=1: the rocprofv3 passes alone, into the same directory; with ONLY_PASS=<name>: that pass alone)
-timeout 600 python bench.py --steps 20 --warmup 3 > $O/bench_default_line.json 2> $O/bench_default.err; echo "bench rc=$?"
-timeout 300 python bench.py --gpus 2 --force-local --steps 10 --warmup 2 > $O/cfg4_force_local_line.json 2> $O/cfg4_force_local.err; echo "force-local rc=$?"
+timeout 600 python bench.py --steps 20 --warmup 3 --full > $O/bench_default_line.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 300 python bench.py --gpus 2 --force-local --steps 10 --warmup 2 --full > $O/cfg4_force_local_line.json 2> $O/cfg4_force_local.err; echo "force-local rc=$?"
 fi
 prof() { # name "command" [fetch] [write]
   local name=$1; shift
@@ -34,11 +34,11 @@ prof cfg5_sorted "python bench.py --config 5 --cfg5-sorted --steps 5 --warmup 1 
 prof cfg5_sorted_sets "python bench.py --config 5 --cfg5-sorted --push-order 2,0,3,1 --steps 5 --warmup 1 --no-cpu-baseline --no-oracle-parity"
 prof cfg5_sorted_wide "python bench.py --config 5 --cfg5-sorted --cfg5-wide-dicts --steps 5 --warmup 1 --no-cpu-baseline --no-oracle-parity" fetch write
 prof cfg5_sorted_widerec "env FDB_RUNS_WIDE=1 python bench.py --config 5 --cfg5-sorted --steps 5 --warmup 1 --no-cpu-baseline --no-oracle-parity" fetch write
-prof select "python bench.py --rows 100000000 --steps 5 --warmup 1 --no-cpu-baseline --only-other select --no-oracle-parity" fetch write
+prof select "python bench.py --rows 100000000 --steps 5 --warmup 1 --no-cpu-baseline --full --only-other select --no-oracle-parity" fetch write
 prof cfg2_sorted "python bench.py --config 2 --cfg2-sorted --steps 10 --warmup 2 --no-cpu-baseline --no-oracle-parity" fetch write
-prof cfg5_merge "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --only-other cfg5_merge"
-prof cfg5_1B "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --only-other cfg5_1B" fetch write
-prof parquet "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --only-other parquet"
+prof cfg5_merge "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --full --only-other cfg5_merge"
+prof cfg5_1B "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --full --only-other cfg5_1B" fetch write
+prof parquet "python bench.py --rows 100000000 --steps 3 --warmup 1 --no-cpu-baseline --no-oracle-parity --full --only-other parquet"
 prof cfg5_exchange "python bench.py --gpus 2 --force-local --config 5 --steps 3 --warmup 1 --no-cpu-baseline"
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*agent_info.csv" -delete; find $O -name "*counter_collection.csv" -size +20M -delete; du -sh $O
 [ -n "${ONLY_PROF:-}" ] && exit 0
