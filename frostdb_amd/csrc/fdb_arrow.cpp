@@ -203,9 +203,7 @@ std::shared_ptr<HostDict> read_dictionary(const HostColView& col) {
   struct Recent { uint64_t hash = 0; std::shared_ptr<std::shared_ptr<HostDict>> holder; std::vector<int32_t> raw_off; };
   static thread_local Recent recent[16];
   static thread_local unsigned recent_next = 0;
-  static const bool l1 = std::getenv("FDB_NO_DICT_L1") == nullptr;
-  static const bool l1_fast = l1 && std::getenv("FDB_NO_DICT_L1_FAST") == nullptr;  // (A/B aid)
-  if (l1_fast && !wide && n > 0)
+  if (!wide && n > 0)
     for (unsigned k = 0; k < 16; k++) {
       const Recent& r = recent[(recent_next + 15 - k) % 16];  // (most recent first)
       if (!r.holder || r.raw_off.size() != (size_t)n + 1) continue;
@@ -246,14 +244,13 @@ std::shared_ptr<HostDict> read_dictionary(const HostColView& col) {
   // a reference to them: the mutex and, worse, the reference count of the ONE shared object bounced between N cores, ≈ 1.7 µs per record
   // whatever N (0.60 G rows/s at 8 chains, 0.63 at 32: round 4). A hit here touches neither: the returned pointer ALIASES the interned
   // object (same address: "same dictionary?" stays a pointer compare everywhere) but counts its references in a control block that
-  // belongs to this thread's cache entry, which in turn holds the interned object alive. ($FDB_NO_DICT_L1: A/B aid)
-  if (l1)
-    for (Recent& r : recent)
-      if (r.holder && r.hash == h && same_content(**r.holder)) return std::shared_ptr<HostDict>(r.holder, r.holder->get());
+  // belongs to this thread's cache entry, which in turn holds the interned object alive.
+  for (Recent& r : recent)
+    if (r.holder && r.hash == h && same_content(**r.holder)) return std::shared_ptr<HostDict>(r.holder, r.holder->get());
   auto remember = [&](const std::shared_ptr<HostDict>& d) -> std::shared_ptr<HostDict> {
     // (bounded: an entry keeps its dictionary alive for the thread's lifetime, so only small ones are cached — ≤ 16 × 256 KiB per pushing
     // thread; with a bigger dictionary the pass over its bytes dwarfs the mutex and the reference count this cache exists to avoid)
-    if (!l1 || span + n * 4 > (int64_t)(256 << 10)) return d;
+    if (span + n * 4 > (int64_t)(256 << 10)) return d;
     Recent& r = recent[recent_next++ % 16];
     r.hash = h;
     r.holder = std::make_shared<std::shared_ptr<HostDict>>(d);

@@ -513,8 +513,7 @@ int fdb_plan_stream(fdb_plan* plan, void** stream_out) {
 int fdb_plan_set_tuning(fdb_plan* plan, int32_t rows_per_thread, int32_t grid_blocks) {
   if (!plan) return FDB_ERR_INVALID;
   if (rows_per_thread == 0 || rows_per_thread == 4 || rows_per_thread == 8) plan->plan.rows_per_thread = rows_per_thread;
-  plan->plan.grid_override = grid_blocks & 0xFFFFF;
-  plan->plan.ablate = (grid_blocks >> 20) & 0xF;  // bench --ablate rides in the high bits (tuning aid only)
+  plan->plan.grid_override = grid_blocks & 0xFFFFF;  // (bits 20-23 are reserved)
   plan->plan.use_partials = ((grid_blocks >> 24) & 1) == 0;
   plan->plan.sub_tiles = (grid_blocks >> 25) & 7;
   return FDB_OK;

@@ -484,10 +484,10 @@ bool Plan::comm_allreduce(Comm& comm) {
   // Small tables (cfg 2 / 3 / 4: 1 025 slots × a few arrays): ONE all-gather of the packed table and a local fold in rank order, which
   // also writes the host copy — one collective on the step's critical path instead of one all-reduce per array, and float64 sums that
   // are bit-identical on every rank and in every run whatever order the ranks arrived in (what fdb_plan_set_deterministic
-  // promises for the scan now holds across GPUs too). Bigger tables keep the all-reduce. ($FDB_MERGE_ALLREDUCE: A/B aid)
+  // promises for the scan now holds across GPUs too). Bigger tables keep the all-reduce.
   const int n_arrays = num_state_arrays();
   const size_t packed_bytes = (size_t)n_arrays * (size_t)n_slots_ * 8;
-  if (packed_bytes * (size_t)comm.size <= ((size_t)32 << 20) && std::getenv("FDB_MERGE_ALLREDUCE") == nullptr) {
+  if (packed_bytes * (size_t)comm.size <= ((size_t)32 << 20)) {
     unsigned long long* d_packed = (unsigned long long*)ctx_->dev_alloc(packed_bytes + 256);
     unsigned long long* d_all = (unsigned long long*)ctx_->dev_alloc(packed_bytes * (size_t)comm.size + 256);
     scratch_.push_back(d_packed); scratch_.push_back(d_all);

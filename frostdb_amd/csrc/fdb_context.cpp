@@ -391,9 +391,8 @@ void* Context::stage(const void* host, size_t payload) {
 
 void Context::flush_staging() {
   if (stage_sent_ >= stage_off_) return;
-  static const bool skip_known = std::getenv("FDB_NO_STAGE_SKIP") == nullptr;  // (A/B aid)
   const size_t a = stage_sent_, b = stage_off_;
-  if (skip_known && b <= shadow_valid_ && std::memcmp(stage_h_ + a, stage_shadow_.data() + a, b - a) == 0) {
+  if (b <= shadow_valid_ && std::memcmp(stage_h_ + a, stage_shadow_.data() + a, b - a) == 0) {
     stage_sent_ = b;  // the device ring already holds exactly these bytes (shipped by an earlier flush on this stream)
     return;
   }

@@ -203,7 +203,6 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
     FdbScanArgs& a = h.base;
     a.need_count = 0;  // the row count of an entry is only read back for COUNT aggregations (occupancy is "fingerprint ≠ 0")
     for (size_t j = 0; j < aggs_.size(); j++) if (aggs_[j].func == FDB_AGG_COUNT && !final_stage_) a.need_count = 1;
-    a.ablate = ablate;
     // columns read by computed aggregate inputs / keys go into base.l8 (the hash scan has no other use for the slot pools)
     bool has_expr = a.n_expr > 0;
     a.n_c4 = a.n_c8 = a.n_l4 = a.n_l8 = 0;
@@ -241,9 +240,8 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
       if (gr.kind == 0) {
         // the record's dictionary IS the plan's value list of the column, in order (the usual case: the parts of a table share their
         // dictionaries, and the plan interned the first one it saw entry by entry): key id = index + 1 — no table to ship or to read.
-        // ($FDB_NO_IDENTITY_LUT: A/B aid)
         const std::vector<uint32_t>& L = *gr.lut;
-        bool identity = !L.empty() && L.front() == 1u && L.back() == (uint32_t)L.size() && !knobs_.no_identity_lut;
+        bool identity = !L.empty() && L.front() == 1u && L.back() == (uint32_t)L.size();
         for (size_t i = 0; identity && i < L.size(); i++) identity = L[i] == (uint32_t)i + 1u;
         C.lut_len = (uint32_t)L.size();
         if (identity) lut_identity[g] = 1; else lut_off[g] = R.blob.add(L.data(), L.size() * 4);
@@ -288,7 +286,6 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
     const size_t run_lds = runs ? (size_t)4 * FDB_RUN_WAVE_LDS : 0;
     if (sub_tiles != 4 && a.lds_lut_bytes <= FDB_LDS_BUDGET) {
       JitHashShape shape = jit_hash_shape(h, hcols.data());
-      shape.ablate = runs ? 0 : ablate & 3;
       JitDeferScope defer(!runs && a.n_expr == 0);  // ($FDB_JIT_ASYNC=1: the probing scan can be interpreted while its kernel is built; a run store cannot)
       jit_fn = jit_hash_get(shape);
       if (jit_fn != nullptr)
@@ -350,8 +347,7 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
       }
       if (room < min_chunk) {
         uint64_t expected = 0;
-        static const bool no_estimate = std::getenv("FDB_HASH_NO_ESTIMATE") != nullptr;  // (tuning / debugging aid)
-        if (!no_estimate && !h_bound_stale_ && h_rows_seen_ >= (uint64_t)(1 << 20) && h_groups_bound_ > 0) {
+        if (!h_bound_stale_ && h_rows_seen_ >= (uint64_t)(1 << 20) && h_groups_bound_ > 0) {
           expected = estimate_final_groups(h_groups_bound_, h_rows_seen_, h_rows_seen_ + rows_left_total);
           expected += expected / 4;  // head-room for the estimate's error
           const uint64_t bytes_per_slot = (uint64_t)h_entry_words_ * 8 + (uint64_t)h_key_words_ * 4;
@@ -363,8 +359,6 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
         hash_reserve(want_chunk, expected);
         room = room_now();
       }
-      static const char* cap_env = std::getenv("FDB_HASH_MAX_CHUNK");  // (tuning / debugging aid)
-      if (cap_env != nullptr && std::atoll(cap_env) > 0) room = std::min<uint64_t>(room, (uint64_t)std::atoll(cap_env));
       // chunk boundaries inside a record stay on tile boundaries (1 024 rows): the kernels address 4-row lane groups with 16-byte
       // loads and read validity bitmaps bytewise from the chunk's first row
       if (room < left_here) room &= ~(uint64_t)1023;
@@ -631,8 +625,6 @@ int64_t Plan::finish_columns_hash(std::vector<OutColumn>* out, DeviceBatch* resi
       FdbPresentArgs pa;
       std::memset(&pa, 0, sizeof(pa));
       pa.dense_keys = a.dense_keys; pa.n_rows = n; pa.key_words = h_key_words_; pa.n_cand = (int)cand.size();
-      static const bool no_set = std::getenv("FDB_PRESENT_NO_SET") != nullptr;
-      pa.no_wave_set = no_set ? 1 : 0;
       size_t bm_words = 0, remap_words = 0;
       for (size_t k = 0; k < cand.size(); k++) {
         const size_t len = gcols_[cand[k]].values.size();
@@ -1249,8 +1241,7 @@ void Plan::merge_hash(Plan& src) {
 // column of ≤ 254 distinct values, there are at most FDB_RUN_TUPLE_BYTES of them and the record carries all of them in the plan's
 // order; otherwise the wide one (the table's own key tuple: any cardinality, int64 and computed keys, absent columns).
 bool Plan::runs_wanted(const DeviceBatch* const* bs, const std::vector<Resolved>& Rs, const std::vector<int>& live) const {
-  static const bool off = std::getenv("FDB_NO_RUNS") != nullptr;  // (A/B and test aid: ordered plans take the hash table + sort)
-  if (off || !ordered_ || !jit_possible() || aggs_.size() != 1 || aggs_[0].role != 0) return false;
+  if (!ordered_ || !jit_possible() || aggs_.size() != 1 || aggs_[0].role != 0) return false;
   if (gcols_.empty() || gcols_.size() > FDB_MAX_HASH_GCOLS) return false;
   if (runs_.size() + live.size() > FDB_MAX_RUN_SEGMENTS) return false;
   // Small key spaces stay with the dense table: a table that fits LDS is the fastest scan there is (one launch for every record, no run

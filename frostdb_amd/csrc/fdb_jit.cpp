@@ -46,15 +46,6 @@ const char* kKernelsHeader =
 #include "fdb_kernels_h.inc"
     ;
 
-// Wide run records are written from RE-LOADED columns (the lanes that end a run): the first pass then has to leave the columns in the
-// L2 — with non-temporal loads the second pass went back to HBM (30.8 % of the roofline; 37.9 % with plain loads,
-// profiles/round6_wide_records_temporal_loads.txt; $FDB_RUNS_WIDE_NT=1 restores the non-temporal ones). The hash-table kernel's inserting
-// lanes re-load too, but there plain loads cost 3 % (they compete with the table's entries for the L2): it keeps the non-temporal ones.
-bool temporal_loads(int runs) {
-  const char* nt = std::getenv("FDB_RUNS_WIDE_NT");
-  return runs == 2 && !(nt != nullptr && std::atoi(nt) != 0);
-}
-
 const char* kPreamble = R"HIP(
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -751,9 +742,6 @@ struct Gen {
     const int BLK = kSelectBlock;
     size_t per_wave = 0;
     const std::vector<Fused> fz = fused(&per_wave);
-    // ($FDB_SELECT_ABLATE, tuning aid — results are WRONG: 1 = no look-back (every share at offset 0), 2 = staged values are not written out, 3 = nothing is staged either)
-    const int ablate = std::getenv("FDB_SELECT_ABLATE") ? std::atoi(std::getenv("FDB_SELECT_ABLATE")) : 0;
-    const int w_sleep = std::getenv("FDB_SELECT_SLEEP") ? std::atoi(std::getenv("FDB_SELECT_SLEEP")) : 4, s_sleep = std::getenv("FDB_SELECT_SCAN_SLEEP") ? std::atoi(std::getenv("FDB_SELECT_SCAN_SLEEP")) : 4;  // (tuning aids)
     o << "#include \"fdb_kernels.h\"\n" << kPreamble;
     // what one step (4 rows per lane) of the filter columns looks like in registers: filled by `load`, consumed by `pred` — apart, so that
     // the NEXT share's loads are in flight while the workgroup waits for the current share's place
@@ -849,7 +837,7 @@ struct Gen {
     o << "      if (pos == p_end) {  // the record is complete: its row count, and the next record starts from nothing\n";
     o << "        if (lane == 0u) *sa.sparts[p].total = running;\n        running = 0; p++;\n        if (p < n_parts) p_end = parts[p].tile_end;\n      }\n";
     o << "      if (pos == pos0) {\n        if (++spins > (1u << 22)) { if (lane == 0u) sa.ctl[1] = 1ull; break; }  // (never seen; a stuck launch must not hang the device)\n";
-    o << "        __builtin_amdgcn_s_sleep(" << s_sleep << ");\n      } else spins = 0;\n    }\n    return;\n  }\n";
+    o << "        __builtin_amdgcn_s_sleep(4);\n      } else spins = 0;\n    }\n    return;\n  }\n";
     // thread 0 always holds the ticket after the next one
     o << "  long long next_ticket = 0;\n  if (tid == 0) { s_ticket[0] = (long long)(atomicAdd(sa.ctl, 1ull) - sa.ticket_base); next_ticket = s_ticket[0] < total_tiles ? (long long)(atomicAdd(sa.ctl, 1ull) - sa.ticket_base) : s_ticket[0]; }\n";
     o << "  __syncthreads();\n  long long st = s_ticket[0];\n  if (st >= total_tiles) return;\n";
@@ -865,7 +853,7 @@ struct Gen {
     o << "        sel[u] = pred(raw[u]) & (left >= 4 ? 0xFu : left > 0 ? ((1u << (int)left) - 1u) : 0u);\n      }\n";
     o << "#pragma unroll\n      for (int u = 0; u < 4; u++) {\n        uint32_t w = sel[u];\n";
     o << "        const unsigned long long b0 = __ballot(w & 1u), b1 = __ballot(w & 2u), b2 = __ballot(w & 4u), b3 = __ballot(w & 8u);\n";
-    if (!fz.empty() && ablate != 3) {
+    if (!fz.empty()) {
       // rows keep their order: lane L's four rows sit behind every selected row of the lanes below it
       o << "        const uint32_t p0 = cnt + lanes_below(b0) + lanes_below(b1) + lanes_below(b2) + lanes_below(b3);\n";
       o << "        const uint32_t p1 = p0 + (w & 1u), p2 = p1 + ((w >> 1) & 1u), p3 = p2 + ((w >> 2) & 1u);\n";
@@ -905,18 +893,16 @@ struct Gen {
     o << "    }\n";
     // 4. the share's place, from the scanner
     o << "    if (wave == 0u) {\n      unsigned long long excl = 0;\n";
-    if (ablate != 1) {
-      o << "      uint32_t spins = 0;\n      for (;;) {\n        const unsigned long long v = __hip_atomic_load(place + c_st * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n";
-      o << "        if ((v >> 40) == (unsigned long long)sa.epoch) { excl = v & VAL; break; }\n";
-      o << "        if (++spins > (1u << 22)) { if (lane == 0u) sa.ctl[1] = 1ull; break; }  // (never seen)\n";
-      o << "        __builtin_amdgcn_s_sleep(" << w_sleep << ");\n      }\n";
-    }
+    o << "      uint32_t spins = 0;\n      for (;;) {\n        const unsigned long long v = __hip_atomic_load(place + c_st * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n";
+    o << "        if ((v >> 40) == (unsigned long long)sa.epoch) { excl = v & VAL; break; }\n";
+    o << "        if (++spins > (1u << 22)) { if (lane == 0u) sa.ctl[1] = 1ull; break; }  // (never seen)\n";
+    o << "        __builtin_amdgcn_s_sleep(4);\n      }\n";
     o << "      if (lane == 0u) s_base = excl;\n    }\n    __syncthreads();\n";
     // 5. every wave writes its staged values to their place
     o << "    if (c_active) {\n      unsigned long long excl = s_base;\n";
     o << "      for (uint32_t w2 = 0; w2 < wave; w2++) excl += s_cnt[it & 1u][w2];\n";
     o << "      if (lane == 0u && (c_unit & 1) == 0) offsets[c_out_tile + (c_unit >> 1)] = (uint32_t)excl;\n";
-    if (!fz.empty() && ablate < 2) {
+    if (!fz.empty()) {
       for (size_t k = 0; k < fz.size(); k++) {
         if (fz[k].wide) {
           o << "      { unsigned long long* d = reinterpret_cast<unsigned long long*>(c_D_" << k << ") + excl;\n";
@@ -960,14 +946,14 @@ struct HashGen {
     // written by the lanes that end a run from re-loaded columns — fdb_kernels.h FdbRunsOut)
     // 3 = medium records: like 1 with TWO bytes per key id (≤ 65 534 distinct values per column; 16 more registers per row)
     const bool narrow = s.runs == 1, wide = s.runs == 2, medium = s.runs == 3;
-    if (temporal_loads(s.runs)) o << "#define FDB_LD_TEMPORAL 1\n";
+    // Wide run records are written from RE-LOADED columns (the lanes that end a run): the first pass then has to leave the columns in
+    // the L2 — with non-temporal loads the second pass went back to HBM (30.8 % of the roofline; 37.9 % with plain loads,
+    // profiles/round6_wide_records_temporal_loads.txt). The hash-table kernel's inserting lanes re-load too, but there plain loads
+    // cost 3 % (they compete with the table's entries for the L2): it keeps the non-temporal ones.
+    if (wide) o << "#define FDB_LD_TEMPORAL 1\n";
     o << "#define FDB_DEVICE_HELPERS 1\n#include \"fdb_kernels.h\"\n" << kPreamble << kHashPreamble;
     // The runs kernel wants ≈149 VGPRs = 3 waves per SIMD, which is also what its LDS stage (4 × 12 KiB per workgroup) lets a CU hold.
-    // ($FDB_RUNS_WAVES_PER_EU: tuning aid — caps the registers so that that many waves fit a SIMD; 0 / unset = no cap)
-    const int waves_cap = s.runs && std::getenv("FDB_RUNS_WAVES_PER_EU") ? std::atoi(std::getenv("FDB_RUNS_WAVES_PER_EU")) : 0;
-    o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") ";
-    if (waves_cap > 0) o << "__attribute__((amdgpu_waves_per_eu(" << waves_cap << ", " << waves_cap << "))) ";
-    o << "void fdb_hash_kernel(const FdbHashArgs h) {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_hash_kernel(const FdbHashArgs h) {\n";
     o << "  extern __shared__ __align__(16) unsigned char smem[];\n  __shared__ unsigned int s_new;\n";
     if (s.runs) o << "  __shared__ unsigned int s_runs[16];  // per wave: first run of its open chunk, runs used in it, first of those still waiting in LDS\n  if (threadIdx.x < 16) s_runs[threadIdx.x] = (threadIdx.x & 3u) == 0u ? 0u : " << FDB_RUN_CHUNK << "u;\n";
     o << "  const FdbScanArgs& a = h.base;\n  // descriptors are read through the constant address space: scalar loads, no vector registers\n  const __attribute__((address_space(4))) FdbHashCol* hc = (const __attribute__((address_space(4))) FdbHashCol*)h.hcols;\n  const uint32_t tid = threadIdx.x;\n  if (tid == 0) s_new = 0;\n";
@@ -1103,101 +1089,95 @@ struct HashGen {
       o << "    }\n";
     }
     for (int k = 0; k < 4; k++) o << "    fp_final(h1_" << k << ", h2_" << k << ");\n";
-    if (s.ablate & 1) o << "    if ((h1_0 ^ h2_0 ^ h1_1 ^ h2_1 ^ h1_2 ^ h2_2 ^ h1_3 ^ h2_3) == 0x1234567ull) h.table[0] = vm_0 ^ vm_1 ^ vm_2 ^ vm_3;\n    continue;\n";  // tuning aid
     // Run combining: a lane owns 4 CONSECUTIVE rows, and scans of tables sorted by their label columns (FrostDB's sorting columns)
     // bring rows of one group next to each other. Rows of the lane with the same fingerprint as the row before them are folded
     // into it — count and every aggregate — and only the LAST row of such a run goes to the table: one probe + one set of atomics
     // per run instead of per row. Costs a few compares on unsorted input.
-    const bool combine = !(s.ablate & 2) || s.runs != 0;
-    const int runs_ablate = s.runs && std::getenv("FDB_RUNS_ABLATE") ? std::atoi(std::getenv("FDB_RUNS_ABLATE")) : 0;  // (tuning aid: 1 no stores, 2 no folding across lanes; results are wrong)
-    if (combine) {
-      for (int k = 0; k < 4; k++) o << "    unsigned long long cnt_" << k << " = 1ull;\n";
+    for (int k = 0; k < 4; k++) o << "    unsigned long long cnt_" << k << " = 1ull;\n";
+    for (size_t j = 0; j < s.aggs.size(); j++) {
+      const JitAgg& A = s.aggs[j];
+      if (A.func == FDB_AGG_COUNT) continue;
+      for (int k = 0; k < 4; k++) {
+        const std::string r = "g" + std::to_string(j);
+        std::string raw = "(((" + r + "_m >> " + std::to_string(k) + ") & 1u) ? " + comp8(r, k) + " : a.aggs[" + std::to_string(j) + "].null_value)";
+        if (A.expr != 0) {
+          auto col = [&](int ni) -> std::string { if (s.exprs[(size_t)ni].kind == 7) return "((PM" + std::to_string(s.exprs[(size_t)ni].slot) + " >> " + std::to_string(k) + ") & 1u)"; return comp8("x" + std::to_string(s.exprs[(size_t)ni].slot), k); };
+          auto colvalid = [&](int ni) { return "((x" + std::to_string(s.exprs[(size_t)ni].slot) + "_m >> " + std::to_string(k) + ") & 1u)"; };
+          raw = "(" + expr_valid(s.exprs, A.expr - 1, col, colvalid) + " ? " + expr_bits(s.exprs, A.expr - 1, expr_value(s.exprs, A.expr - 1, col, colvalid)) + " : 0ull)";
+        }
+        const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k);
+        if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) o << "    double " << v << " = __longlong_as_double((long long)" << raw << ");\n";
+        else if (A.func == FDB_AGG_SUM) o << "    unsigned long long " << v << " = " << raw << ";\n";
+        else o << "    long long " << v << " = " << (A.type == FDB_T_F64 ? ("f64_minmax_key(__longlong_as_double((long long)" + raw + "), " + (A.func == FDB_AGG_MIN ? "true" : "false") + ")") : ("(long long)" + raw)) << ";\n";
+      }
+    }
+    for (int k = 1; k < 4; k++) {
+      o << "    if (((sel >> " << (k - 1) << ") & 3u) == 3u && h1_" << (k - 1) << " == h1_" << k << " && h2_" << (k - 1) << " == h2_" << k << ") {\n";
+      o << "      cnt_" << k << " += cnt_" << (k - 1) << ";\n";
       for (size_t j = 0; j < s.aggs.size(); j++) {
         const JitAgg& A = s.aggs[j];
         if (A.func == FDB_AGG_COUNT) continue;
-        for (int k = 0; k < 4; k++) {
-          const std::string r = "g" + std::to_string(j);
-          std::string raw = "(((" + r + "_m >> " + std::to_string(k) + ") & 1u) ? " + comp8(r, k) + " : a.aggs[" + std::to_string(j) + "].null_value)";
-          if (A.expr != 0) {
-            auto col = [&](int ni) -> std::string { if (s.exprs[(size_t)ni].kind == 7) return "((PM" + std::to_string(s.exprs[(size_t)ni].slot) + " >> " + std::to_string(k) + ") & 1u)"; return comp8("x" + std::to_string(s.exprs[(size_t)ni].slot), k); };
-            auto colvalid = [&](int ni) { return "((x" + std::to_string(s.exprs[(size_t)ni].slot) + "_m >> " + std::to_string(k) + ") & 1u)"; };
-            raw = "(" + expr_valid(s.exprs, A.expr - 1, col, colvalid) + " ? " + expr_bits(s.exprs, A.expr - 1, expr_value(s.exprs, A.expr - 1, col, colvalid)) + " : 0ull)";
-          }
-          const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k);
-          if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) o << "    double " << v << " = __longlong_as_double((long long)" << raw << ");\n";
-          else if (A.func == FDB_AGG_SUM) o << "    unsigned long long " << v << " = " << raw << ";\n";
-          else o << "    long long " << v << " = " << (A.type == FDB_T_F64 ? ("f64_minmax_key(__longlong_as_double((long long)" + raw + "), " + (A.func == FDB_AGG_MIN ? "true" : "false") + ")") : ("(long long)" + raw)) << ";\n";
-        }
+        const std::string a = "v" + std::to_string(j) + "_" + std::to_string(k - 1), b = "v" + std::to_string(j) + "_" + std::to_string(k);
+        if (A.func == FDB_AGG_SUM) o << "      " << b << " += " << a << ";\n";
+        else if (A.func == FDB_AGG_MIN) o << "      " << b << " = " << a << " < " << b << " ? " << a << " : " << b << ";\n";
+        else o << "      " << b << " = " << a << " > " << b << " ? " << a << " : " << b << ";\n";
       }
-      for (int k = 1; k < 4; k++) {
-        o << "    if (((sel >> " << (k - 1) << ") & 3u) == 3u && h1_" << (k - 1) << " == h1_" << k << " && h2_" << (k - 1) << " == h2_" << k << ") {\n";
-        o << "      cnt_" << k << " += cnt_" << (k - 1) << ";\n";
-        for (size_t j = 0; j < s.aggs.size(); j++) {
-          const JitAgg& A = s.aggs[j];
-          if (A.func == FDB_AGG_COUNT) continue;
-          const std::string a = "v" + std::to_string(j) + "_" + std::to_string(k - 1), b = "v" + std::to_string(j) + "_" + std::to_string(k);
-          if (A.func == FDB_AGG_SUM) o << "      " << b << " += " << a << ";\n";
-          else if (A.func == FDB_AGG_MIN) o << "      " << b << " = " << a << " < " << b << " ? " << a << " : " << b << ";\n";
-          else o << "      " << b << " = " << a << " > " << b << " ? " << a << " : " << b << ";\n";
-        }
-        o << "      sel &= ~" << (1u << (k - 1)) << "u;\n    }\n";
-      }
-      // The same across the lanes of the wave (its 256 rows are consecutive): a run that continues in the next lane hands its
-      // folded partial on instead of touching the table, and the lane where the run ends applies the total — one probe + one set of
-      // atomics per run and wave. Kogge-Stone scan over lanes of (fingerprint of the lane's trailing run, its partial, "the run
-      // covers every row of the span"); a lane without selected rows ends every run (less folding, never a wrong one). Equal keys
-      // that are not adjacent are simply two runs. Costs ≈50 cross-lane moves per 256 rows when nothing folds.
-      auto pick = [&](const std::string& base, const char* idx) {
-        return "(" + std::string(idx) + " == 0 ? " + base + "_0 : " + idx + " == 1 ? " + base + "_1 : " + idx + " == 2 ? " + base + "_2 : " + base + "_3)";
-      };
-      // (lanes that left the tile early — rows past the end, nothing selected by the filter — do not take part: what a shuffle
-      // reads from them is not data, so their bits in `act` gate every value that comes from another lane)
-      if (runs_ablate & 2) o << "    if (false)\n";
-      o << "    {\n      const int wl = (int)(tid & 63u);\n      const bool has = sel != 0u;\n      const unsigned long long act = __ballot(1);\n";
-      o << "      const int kf = has ? __builtin_ctz(sel) : 0, kl = has ? 31 - __builtin_clz(sel) : 0;\n";
-      o << "      const unsigned long long fa = " << pick("h1", "kf") << ", fb = " << pick("h2", "kf") << ";\n";
-      o << "      const unsigned long long ta = " << pick("h1", "kl") << ", tb = " << pick("h2", "kl") << ";\n";
-      o << "      unsigned long long t_cnt = " << pick("cnt", "kl") << ";\n";
-      std::vector<size_t> folded;  // aggregates that carry a value
-      for (size_t j = 0; j < s.aggs.size(); j++) if (s.aggs[j].func != FDB_AGG_COUNT) folded.push_back(j);
-      auto vtype = [&](size_t j) { const JitAgg& A = s.aggs[j]; return A.func == FDB_AGG_SUM ? (A.type == FDB_T_F64 ? "double" : "unsigned long long") : "long long"; };
-      for (size_t j : folded) o << "      " << vtype(j) << " t_v" << j << " = " << pick("v" + std::to_string(j), "kl") << ";\n";
-      o << "      int t_flags = has ? (2 | ((sel & (sel - 1u)) == 0u ? 1 : 0)) : 0;  // bit 1: the span ends in a run; bit 0: that run covers the whole span\n";
-      for (int off = 1; off < 64; off <<= 1) {
-        o << "      {\n        const unsigned long long pa = __shfl_up(ta, " << off << ", 64), pb = __shfl_up(tb, " << off << ", 64), pc = __shfl_up(t_cnt, " << off << ", 64);\n";
-        for (size_t j : folded) o << "        const " << vtype(j) << " pv" << j << " = __shfl_up(t_v" << j << ", " << off << ", 64);\n";
-        o << "        const int pf_raw = __shfl_up(t_flags, " << off << ", 64);\n        const int pf = (wl >= " << off << " && ((act >> (wl - " << off << ")) & 1ull)) ? pf_raw : 0;\n";
-        o << "        if (wl >= " << off << " && (t_flags & 3) == 3) {\n";
-        o << "          if ((pf & 2) && pa == ta && pb == tb) {\n            t_cnt += pc;\n";
-        for (size_t j : folded) {
-          const JitAgg& A = s.aggs[j];
-          const std::string t = "t_v" + std::to_string(j), pv = "pv" + std::to_string(j);
-          if (A.func == FDB_AGG_SUM) o << "            " << t << " += " << pv << ";\n";
-          else if (A.func == FDB_AGG_MIN) o << "            " << t << " = " << pv << " < " << t << " ? " << pv << " : " << t << ";\n";
-          else o << "            " << t << " = " << pv << " > " << t << " ? " << pv << " : " << t << ";\n";
-        }
-        o << "            t_flags = 2 | (pf & 1);\n          } else {\n            t_flags = 2;\n          }\n        }\n      }\n";
-      }
-      // what the lanes before this one hand over (the inclusive result of lane - 1), and whether the next lane takes over
-      o << "      const unsigned long long xa = __shfl_up(ta, 1, 64), xb = __shfl_up(tb, 1, 64), xc = __shfl_up(t_cnt, 1, 64);\n";
-      for (size_t j : folded) o << "      const " << vtype(j) << " xv" << j << " = __shfl_up(t_v" << j << ", 1, 64);\n";
-      o << "      const int xf_raw = __shfl_up(t_flags, 1, 64);\n      const int xf = (wl > 0 && ((act >> (wl - 1)) & 1ull)) ? xf_raw : 0;\n";
-      o << "      const unsigned long long na = __shfl_down(fa, 1, 64), nb = __shfl_down(fb, 1, 64);\n      const int nh_raw = __shfl_down((int)has, 1, 64);\n      const int nh = (wl < 63 && ((act >> (wl + 1)) & 1ull)) ? nh_raw : 0;\n";
-      o << "      if (has && wl > 0 && (xf & 2) && xa == fa && xb == fb) {\n";
-      for (int k = 0; k < 4; k++) {
-        o << "        if (kf == " << k << ") {\n          cnt_" << k << " += xc;\n";
-        for (size_t j : folded) {
-          const JitAgg& A = s.aggs[j];
-          const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k), xv = "xv" + std::to_string(j);
-          if (A.func == FDB_AGG_SUM) o << "          " << v << " += " << xv << ";\n";
-          else if (A.func == FDB_AGG_MIN) o << "          " << v << " = " << xv << " < " << v << " ? " << xv << " : " << v << ";\n";
-          else o << "          " << v << " = " << xv << " > " << v << " ? " << xv << " : " << v << ";\n";
-        }
-        o << "        }\n";
-      }
-      o << "      }\n";
-      o << "      if (has && wl < 63 && nh && na == ta && nb == tb) sel &= ~(1u << kl);\n    }\n";
+      o << "      sel &= ~" << (1u << (k - 1)) << "u;\n    }\n";
     }
+    // The same across the lanes of the wave (its 256 rows are consecutive): a run that continues in the next lane hands its
+    // folded partial on instead of touching the table, and the lane where the run ends applies the total — one probe + one set of
+    // atomics per run and wave. Kogge-Stone scan over lanes of (fingerprint of the lane's trailing run, its partial, "the run
+    // covers every row of the span"); a lane without selected rows ends every run (less folding, never a wrong one). Equal keys
+    // that are not adjacent are simply two runs. Costs ≈50 cross-lane moves per 256 rows when nothing folds.
+    auto pick = [&](const std::string& base, const char* idx) {
+      return "(" + std::string(idx) + " == 0 ? " + base + "_0 : " + idx + " == 1 ? " + base + "_1 : " + idx + " == 2 ? " + base + "_2 : " + base + "_3)";
+    };
+    // (lanes that left the tile early — rows past the end, nothing selected by the filter — do not take part: what a shuffle
+    // reads from them is not data, so their bits in `act` gate every value that comes from another lane)
+    o << "    {\n      const int wl = (int)(tid & 63u);\n      const bool has = sel != 0u;\n      const unsigned long long act = __ballot(1);\n";
+    o << "      const int kf = has ? __builtin_ctz(sel) : 0, kl = has ? 31 - __builtin_clz(sel) : 0;\n";
+    o << "      const unsigned long long fa = " << pick("h1", "kf") << ", fb = " << pick("h2", "kf") << ";\n";
+    o << "      const unsigned long long ta = " << pick("h1", "kl") << ", tb = " << pick("h2", "kl") << ";\n";
+    o << "      unsigned long long t_cnt = " << pick("cnt", "kl") << ";\n";
+    std::vector<size_t> folded;  // aggregates that carry a value
+    for (size_t j = 0; j < s.aggs.size(); j++) if (s.aggs[j].func != FDB_AGG_COUNT) folded.push_back(j);
+    auto vtype = [&](size_t j) { const JitAgg& A = s.aggs[j]; return A.func == FDB_AGG_SUM ? (A.type == FDB_T_F64 ? "double" : "unsigned long long") : "long long"; };
+    for (size_t j : folded) o << "      " << vtype(j) << " t_v" << j << " = " << pick("v" + std::to_string(j), "kl") << ";\n";
+    o << "      int t_flags = has ? (2 | ((sel & (sel - 1u)) == 0u ? 1 : 0)) : 0;  // bit 1: the span ends in a run; bit 0: that run covers the whole span\n";
+    for (int off = 1; off < 64; off <<= 1) {
+      o << "      {\n        const unsigned long long pa = __shfl_up(ta, " << off << ", 64), pb = __shfl_up(tb, " << off << ", 64), pc = __shfl_up(t_cnt, " << off << ", 64);\n";
+      for (size_t j : folded) o << "        const " << vtype(j) << " pv" << j << " = __shfl_up(t_v" << j << ", " << off << ", 64);\n";
+      o << "        const int pf_raw = __shfl_up(t_flags, " << off << ", 64);\n        const int pf = (wl >= " << off << " && ((act >> (wl - " << off << ")) & 1ull)) ? pf_raw : 0;\n";
+      o << "        if (wl >= " << off << " && (t_flags & 3) == 3) {\n";
+      o << "          if ((pf & 2) && pa == ta && pb == tb) {\n            t_cnt += pc;\n";
+      for (size_t j : folded) {
+        const JitAgg& A = s.aggs[j];
+        const std::string t = "t_v" + std::to_string(j), pv = "pv" + std::to_string(j);
+        if (A.func == FDB_AGG_SUM) o << "            " << t << " += " << pv << ";\n";
+        else if (A.func == FDB_AGG_MIN) o << "            " << t << " = " << pv << " < " << t << " ? " << pv << " : " << t << ";\n";
+        else o << "            " << t << " = " << pv << " > " << t << " ? " << pv << " : " << t << ";\n";
+      }
+      o << "            t_flags = 2 | (pf & 1);\n          } else {\n            t_flags = 2;\n          }\n        }\n      }\n";
+    }
+    // what the lanes before this one hand over (the inclusive result of lane - 1), and whether the next lane takes over
+    o << "      const unsigned long long xa = __shfl_up(ta, 1, 64), xb = __shfl_up(tb, 1, 64), xc = __shfl_up(t_cnt, 1, 64);\n";
+    for (size_t j : folded) o << "      const " << vtype(j) << " xv" << j << " = __shfl_up(t_v" << j << ", 1, 64);\n";
+    o << "      const int xf_raw = __shfl_up(t_flags, 1, 64);\n      const int xf = (wl > 0 && ((act >> (wl - 1)) & 1ull)) ? xf_raw : 0;\n";
+    o << "      const unsigned long long na = __shfl_down(fa, 1, 64), nb = __shfl_down(fb, 1, 64);\n      const int nh_raw = __shfl_down((int)has, 1, 64);\n      const int nh = (wl < 63 && ((act >> (wl + 1)) & 1ull)) ? nh_raw : 0;\n";
+    o << "      if (has && wl > 0 && (xf & 2) && xa == fa && xb == fb) {\n";
+    for (int k = 0; k < 4; k++) {
+      o << "        if (kf == " << k << ") {\n          cnt_" << k << " += xc;\n";
+      for (size_t j : folded) {
+        const JitAgg& A = s.aggs[j];
+        const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k), xv = "xv" + std::to_string(j);
+        if (A.func == FDB_AGG_SUM) o << "          " << v << " += " << xv << ";\n";
+        else if (A.func == FDB_AGG_MIN) o << "          " << v << " = " << xv << " < " << v << " ? " << xv << " : " << v << ";\n";
+        else o << "          " << v << " = " << xv << " > " << v << " ? " << xv << " : " << v << ";\n";
+      }
+      o << "        }\n";
+    }
+    o << "      }\n";
+    o << "      if (has && wl < 63 && nh && na == ta && nb == tb) sel &= ~(1u << kl);\n    }\n";
     std::vector<int> cword(s.cols.size());
     { int w = 4; for (size_t c = 0; c < s.cols.size(); c++) { cword[c] = w; w += s.cols[c].kind == 0 ? 1 : 2; } }
     // (`for_runs`: the wide run records of an ordered plan take the same road — the "inserting" rows are the ones that end a run, the
@@ -1354,7 +1334,7 @@ struct HashGen {
       o << "    {\n      const unsigned long long act2 = __ballot(1);\n      const int wl2 = (int)(tid & 63u), wv = (int)(tid >> 6), first2 = __builtin_ctzll(act2);\n";
       o << "      const unsigned long long b0 = __ballot((sel & 1u) != 0u), b1 = __ballot((sel & 2u) != 0u), b2 = __ballot((sel & 4u) != 0u), b3 = __ballot((sel & 8u) != 0u);\n";
       o << "      const uint32_t n_w = (uint32_t)(__popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3));\n";
-      o << "      if (n_w != 0u" << ((runs_ablate & 1) ? " && h.row_begin == 12345" : "") << ") {\n        const unsigned long long lt = (1ull << wl2) - 1ull;\n";
+      o << "      if (n_w != 0u) {\n        const unsigned long long lt = (1ull << wl2) - 1ull;\n";
       o << "        const uint32_t before = (uint32_t)(__popcll(b0 & lt) + __popcll(b1 & lt) + __popcll(b2 & lt) + __popcll(b3 & lt));\n";
       // The wave's runs wait in its LDS stage (FDB_RUN_STAGE of them) and leave as one contiguous copy when the stage is full or the
       // chunk changes: a store per tile made the next tile's loads wait for its acknowledgement.
@@ -1401,10 +1381,10 @@ struct HashGen {
       o << "      if (c_" << k << " != 0ull && !(p_" << k << " == h1_" << k << " && q_" << k << " == h2_" << k << ")) { bool ins; slot_" << k << " = hash_find_or_insert(h.table, h.mask, ew, h1_" << k << ", h2_" << k
         << ", ins); if (ins) ins_mask |= " << (1 << k) << "u; }\n";
       o << "      unsigned long long* e = h.table + slot_" << k << " * (uint64_t)ew;\n";
-      if (!(s.ablate & 2) && s.need_count) o << "      atomicAdd(e + 2, cnt_" << k << ");\n";
+      if (s.need_count) o << "      atomicAdd(e + 2, cnt_" << k << ");\n";
       for (size_t j = 0; j < s.aggs.size(); j++) {
         const JitAgg& A = s.aggs[j];
-        if (A.func == FDB_AGG_COUNT || (s.ablate & 2)) continue;
+        if (A.func == FDB_AGG_COUNT) continue;
         const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k);
         const std::string acc = "(e + " + std::to_string(3 + j) + ")";
         if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) o << "      atomicAdd(reinterpret_cast<double*>" << acc << ", " << v << ");\n";
@@ -1665,7 +1645,7 @@ hipFunction_t get_kernel(const std::string& key, const char* kernel_name, F make
 std::string jit_select_source(const JitShape& shape) { return Gen(shape).select_source(); }
 size_t jit_select_stage_bytes(const JitShape& shape) { size_t n = 0; (void)Gen(shape).fused(&n); return n; }
 hipFunction_t jit_select_kernel_get(const JitShape& shape) {
-  return get_kernel("select|" + shape.key() + "|f" + std::to_string(shape.fuse4) + "," + std::to_string(shape.fuse8) + (std::getenv("FDB_SELECT_ABLATE") ? std::string("|a") + std::getenv("FDB_SELECT_ABLATE") : std::string()) + (std::getenv("FDB_SELECT_SLEEP") ? std::string("|s") + std::getenv("FDB_SELECT_SLEEP") : std::string()) + (std::getenv("FDB_SELECT_SCAN_SLEEP") ? std::string("|S") + std::getenv("FDB_SELECT_SCAN_SLEEP") : std::string()), "fdb_select_kernel", [&] { return jit_select_source(shape); });
+  return get_kernel("select|" + shape.key() + "|f" + std::to_string(shape.fuse4) + "," + std::to_string(shape.fuse8), "fdb_select_kernel", [&] { return jit_select_source(shape); });
 }
 hipError_t jit_select_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_parts, int64_t total_super_tiles, const FdbScanArgs& common, int grid, size_t lds_bytes,
                              uint32_t* masks, uint32_t* offsets, const FdbSelectArgs& sel, hipStream_t stream) {
@@ -1702,9 +1682,7 @@ hipFunction_t jit_get(const JitShape& shape) {
 
 std::string JitHashShape::key() const {
   std::ostringstream k;
-  k << "a" << ablate << "c" << need_count << (runs == 1 ? "R" : runs == 2 ? "W" : runs == 3 ? "M" : "") << (runs && std::getenv("FDB_RUNS_WAVES_PER_EU") ? std::getenv("FDB_RUNS_WAVES_PER_EU") : "")
-    << (runs && std::getenv("FDB_RUNS_ABLATE") ? std::string("x") + std::getenv("FDB_RUNS_ABLATE") : std::string())
-    << (temporal_loads(runs) ? "t" : "") << "|";
+  k << "c" << need_count << (runs == 1 ? "R" : runs == 2 ? "W" : runs == 3 ? "M" : "") << "|";
   for (const JitHashCol& C : cols) k << C.kind << (C.has_validity ? 'n' : '-') << (C.lut_identity ? 'i' : C.lut_in_lds ? 'l' : 'g') << (C.kind == 2 ? std::to_string(C.expr_root) : std::string());
   k << '|';
   for (size_t l = 0; l < leaves.size(); l++) {

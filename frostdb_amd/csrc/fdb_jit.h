@@ -63,7 +63,6 @@ struct JitHashShape {
   std::vector<JitExprNode> exprs;  // column nodes read base.l8[slot]
   int n_expr_cols = 0;
   bool need_count = true;  // some aggregation is COUNT: otherwise the per-entry row count is never read (occupancy = fingerprint ≠ 0) and its atomic is skipped
-  int ablate = 0;  // tuning aid (tools/cfg5_ablate.py): 1 = stream + fingerprint only, 2 = no count / aggregate atomics
   // Table-free OrderedAggregate (FdbHashArgs.runs): no probe, no insert — every wave emits the runs of equal keys among its 256 rows
   // (key ids, row count, folded aggregate) and notes them in the launch's directory. Exactly one aggregation. 1: narrow records —
   // dictionary columns with ≤ 255 values, at most FDB_RUN_TUPLE_BYTES of them, ids packed one byte each while the fingerprint is

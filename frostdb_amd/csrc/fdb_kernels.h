@@ -132,7 +132,6 @@ struct FdbScanArgs {
   FdbColSlot c8[FDB_ARG_C8];
   unsigned long long* partials;  // LDS mode: per-workgroup partial tables [grid][1 + n_aggs][n_slots], written with plain
                                  // coalesced stores and folded by fdb_launch_reduce_partials (nullptr: flush with atomics)
-  int32_t ablate;           // tuning aid (bench --ablate): 1 skip occupancy, 2 skip aggregate atomics, 4 skip group LUTs, 8 skip filter
   int32_t lut_class;        // records with the same class carry byte-identical LUT sets at the same LDS offsets
   uint8_t code[FDB_MAX_CODE];
   uint32_t ops_after[FDB_MAX_LEAVES];  // slot kernel: the AND/OR ops that follow leaf l in postfix order: [3:0] count, then 2 bits
@@ -336,7 +335,6 @@ struct FdbHashColumnsArgs {
 // present[rank] = id − 1 (the dictionary index the host widens to), counts[k] = number of present ids.
 struct FdbPresentArgs {
   const uint32_t* dense_keys; uint64_t n_rows; int32_t key_words, n_cand;
-  int32_t no_wave_set;        // A/B aid ($FDB_PRESENT_NO_SET): ask the global bitmap for every (column, id) instead of the wave's LDS set first
   uint32_t* bitmaps;          // zeroed by the caller
   uint32_t* remap;            // [Σ (dict_len[k] + 1)] at remap_off[k]
   uint32_t* present;          // same offsets
@@ -548,8 +546,6 @@ hipError_t fdb_launch_scan_slots(const FdbScanArgs* d_parts, int n_parts, const 
                                  size_t lds_bytes, int two_phase, int mode, hipStream_t stream);
 // Rows per tile and resident workgroups per CU (occupancy query on the instance that will run) of the slot kernel.
 int fdb_slot_geometry(int two_phase, int mode, int lds_acc, size_t lds_bytes, int device, int* tile_rows, int* blocks_per_cu);
-int fdb_slot_kernel_block(void);      // threads per workgroup of the slot kernel
-hipError_t fdb_launch_fill_u64(unsigned long long* dst, unsigned long long value, int64_t n, hipStream_t stream);
 // v[i] ← bits of the float64 whose order-preserving integer key (fdb_f64_to_ordered) v[i] holds, in place.
 hipError_t fdb_launch_ordered_to_f64(unsigned long long* v, int64_t n, hipStream_t stream);
 // base[a * n + i] = idents[a] for a < n_arrays (≤ 1 + FDB_MAX_AGGS), i < n: the whole partial table in one launch.

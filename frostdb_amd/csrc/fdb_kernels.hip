@@ -261,22 +261,16 @@ __global__ __launch_bounds__(FDB_BLOCK, 8) void scan_dense_kernel(const FdbScanA
     if (row0 < a.n_rows) {
       const int64_t left = a.n_rows - row0;
       const uint32_t in_range = left >= R ? FULL : ((1u << (int)left) - 1u);
-      sel = ((a.ablate & 8) ? FULL : eval_filter<R>(a, row0, smem)) & in_range;
+      sel = eval_filter<R>(a, row0, smem) & in_range;
     }
     if (__ballot(sel != 0) == 0ull) continue;  // whole wave filtered out: skip the group/value columns
     if (row0 >= a.n_rows) continue;            // (lanes past the end hold sel == 0; keep their loads in bounds)
 
     uint32_t gid[R];
-    if (a.ablate & 4) {
-#pragma unroll
-      for (int r = 0; r < R; r++) gid[r] = 0;
-    } else {
-      group_slots<R>(a, row0, smem, gid);
-    }
+    group_slots<R>(a, row0, smem, gid);
 
     // occupancy / COUNT
-    if (a.ablate & 1) {
-    } else if (LDS) {
+    if (LDS) {
       if (a.need_count) {
 #pragma unroll
         for (int r = 0; r < R; r++) if ((sel >> r) & 1u) atomicAdd(&l_cnt[gid[r]], 1u);
@@ -301,12 +295,7 @@ __global__ __launch_bounds__(FDB_BLOCK, 8) void scan_dense_kernel(const FdbScanA
 #pragma unroll
       for (int r = 0; r < R; r++) if (!((valid >> r) & 1u)) raw[r] = A.null_value;
       unsigned long long* acc = LDS ? (l_acc + (size_t)j * n_slots) : A.acc;
-      if (a.ablate & 2) {
-        unsigned long long x = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) x ^= raw[r];
-        if (x == 0x123456789abcdefull) acc[0] = x;
-      } else if (A.func == AGG_SUM) {
+      if (A.func == AGG_SUM) {
         if (A.type == FDB_T_F64) {
 #pragma unroll
           for (int r = 0; r < R; r++)
@@ -819,7 +808,7 @@ __global__ __launch_bounds__(FDB_HASH_BLOCK) void scan_hash_kernel(const FdbHash
         if (kind[u] == 0) {
           uint32_t id = 0;
           if (valid) id = lutg[u] == nullptr ? idx[u] + 1u : lds[u] != FDB_NO_LDS ? reinterpret_cast<const uint32_t*>(smem + lds[u])[idx[u]] : as_global(lutg[u])[idx[u]];  // (no table: key id = index + 1)
-          if (!(a.ablate & 4)) kstage[word[u] * FDB_HASH_BLOCK + tid] = id;
+          kstage[word[u] * FDB_HASH_BLOCK + tid] = id;
           fp_add32(h1, h2, k1[u], k2[u], id);  // id 0 (NULL) contributes nothing
           if (id != 0) vmask |= 1ull << gi[u];
         } else {
@@ -833,7 +822,6 @@ __global__ __launch_bounds__(FDB_HASH_BLOCK) void scan_hash_kernel(const FdbHash
       }
     }
     fp_final(h1, h2);
-    if (a.ablate & 1) { if ((h1 ^ h2) == 0x1234567ull) h.table[0] = vmask; continue; }  // tuning aid: stream + fingerprint only
     bool inserted;
     const uint64_t slot = hash_find_or_insert(h.table, h.mask, ew, h1, h2, inserted);
     if (inserted) {
@@ -843,7 +831,6 @@ __global__ __launch_bounds__(FDB_HASH_BLOCK) void scan_hash_kernel(const FdbHash
       atomicAdd(&s_new, 1u);
     }
     unsigned long long* e = h.table + slot * (uint64_t)ew;
-    if (a.ablate & 2) continue;  // tuning aid: probe only
     atomicAdd(e + 2, 1ull);
     for (int j = 0; j < a.n_aggs; j++) {
       const FdbAgg& A = a.aggs[j];
@@ -1276,10 +1263,6 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ 
 }
 
 // (hash_merge / hash_partition: fdb_merge.hip)
-
-__global__ void fill_u64_kernel(unsigned long long* dst, unsigned long long value, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = value;
-}
 
 struct FillIdents { unsigned long long v[1 + FDB_MAX_AGGS]; };
 __global__ void fill_state_kernel(unsigned long long* base, int64_t n, int n_arrays, FillIdents idents) {
@@ -2064,7 +2047,6 @@ int fdb_scan_default_grid(int device) {
   return 2 * g_cu_count[device];
 }
 
-int fdb_slot_kernel_block(void) { return SLOT_BLOCK; }
 int fdb_scan_grid(const FdbScanArgs& args, int grid_blocks, int rows_per_thread) {
   const int64_t tile_rows = rows_per_thread == 0 ? (int64_t)SLOT_BLOCK * 4 : (int64_t)FDB_BLOCK * rows_per_thread;
   const int64_t n_tiles = (args.n_rows + tile_rows - 1) / tile_rows;
@@ -2174,14 +2156,6 @@ hipError_t fdb_launch_ordered_to_f64(unsigned long long* v, int64_t n, hipStream
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(ordered_to_f64_kernel, dim3(blocks), dim3(256), 0, stream, v, n);
-  return hipGetLastError();
-}
-
-hipError_t fdb_launch_fill_u64(unsigned long long* dst, unsigned long long value, int64_t n, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(fill_u64_kernel, dim3(blocks), dim3(256), 0, stream, dst, value, n);
   return hipGetLastError();
 }
 

@@ -189,8 +189,7 @@ class HostTable {
     const size_t cap = cap_ == 0 ? 256 : cap_ * 2;
     T* q = nullptr;
     bool pin = false;
-    static const bool no_pinned = std::getenv("FDB_PARQUET_NO_PINNED") != nullptr;  // (measurement aid, as for the image)
-    if (cap * sizeof(T) > ((size_t)32 << 10) && !no_pinned) {
+    if (cap * sizeof(T) > ((size_t)32 << 10)) {
       // (a pooled block is ≥ 2 MiB: the table's next doublings stay inside it)
       try { q = (T*)pinned_pool_alloc(std::max(cap * sizeof(T), (size_t)2 << 20)); pin = true; } catch (const Error&) { (void)hipGetLastError(); q = nullptr; }
     }
@@ -545,8 +544,7 @@ struct Image {
   void allocate(size_t bytes) {
     release();
     cap = bytes; used = 0;
-    static const bool no_pinned = std::getenv("FDB_PARQUET_NO_PINNED") != nullptr;  // (measurement aid)
-    try { if (no_pinned) throw Error(FDB_ERR_DEVICE, "off"); p = (uint8_t*)pinned_pool_alloc(bytes); pinned = true; }
+    try { p = (uint8_t*)pinned_pool_alloc(bytes); pinned = true; }
     catch (const Error&) { (void)hipGetLastError(); p = (uint8_t*)std::malloc(std::max<size_t>(bytes, 1)); pinned = false; if (p == nullptr) throw Error(FDB_ERR_OOM, "parquet: out of host memory"); }
   }
   bool empty() const { return used == 0; }
@@ -608,7 +606,7 @@ void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* out, st
     if (prefix > (size_t)h.compressed || prefix > (size_t)h.uncompressed) throw Error(FDB_ERR_INVALID, "parquet: levels run past the page");
     const bool packed = c.codec != CODEC_NONE && (h.type != PQ_DATA_PAGE_V2 || h.v2_compressed);
     const size_t comp_body = (size_t)h.compressed - prefix, plain_body = (size_t)h.uncompressed - prefix;
-    static const size_t device_min = std::getenv("FDB_PARQUET_DEVICE_MIN_BYTES") ? (size_t)std::atoll(std::getenv("FDB_PARQUET_DEVICE_MIN_BYTES")) : ((size_t)32 << 10);  // (tuning aid; 256 KiB until round 6: with every row group of a call on the host threads at once, inflating 1 000 literal pages of 48 KB per row group there was the host part's largest item — 3.2 ms against 1.3)
+    constexpr size_t device_min = (size_t)32 << 10;  // (256 KiB until round 6: with every row group of a call on the host threads at once, inflating 1 000 literal pages of 48 KB per row group there was the host part's largest item — 3.2 ms against 1.3)
     const bool on_device = device_inflate && packed && c.codec == CODEC_SNAPPY && is_fixed8 && h.encoding == ENC_PLAIN && plain_body >= device_min &&
                            comp_body * 10 >= plain_body * 9 && plain_body < ((size_t)1 << 31) && snappy_device_ok(raw + prefix, comp_body);
     pages.push_back(Pg{raw, (size_t)h.compressed, prefix, (size_t)h.uncompressed, packed, on_device, on_device && h.type == PQ_DATA_PAGE && c.optional != 0});
@@ -967,7 +965,7 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
   if (any_rows && hipSetDevice(device) == hipSuccess) {
     try { ctx = Context::acquire(device); } catch (...) { ctx = nullptr; }
     if (ctx != nullptr) {
-      copy_stream = std::getenv("FDB_PQ_EARLY_ON_MAIN") != nullptr ? ctx->stream : ctx->aux_stream(0);  // ($FDB_PQ_EARLY_ON_MAIN: A/B aid)
+      copy_stream = ctx->aux_stream(0);
       for (int32_t g = 0; g < n_groups; g++) {
         Group& R = G[(size_t)g];
         if (R.n_rows <= 0) continue;

@@ -617,9 +617,8 @@ void Plan::state_idents(unsigned long long* idents) const {
 
 unsigned long long* Plan::mirror_target() {
   constexpr size_t kMaxMirror = (size_t)256 << 10;
-  static const bool off = std::getenv("FDB_NO_HOST_MIRROR") != nullptr;  // (A/B aid)
   const size_t bytes = (size_t)slots_alloc_ * 8 * (1 + aggs_.size());
-  if (off || d_state_ == nullptr || bytes == 0 || bytes > kMaxMirror) return nullptr;
+  if (d_state_ == nullptr || bytes == 0 || bytes > kMaxMirror) return nullptr;
   if (h_mirror_ != nullptr && mirror_bytes_ != bytes) {
     // a fold kernel of an earlier push may still be writing the old mirror: it goes back to the process-wide pinned pool only
     // once the stream is idle (rare: the table was re-laid-out between two pushes)
@@ -1083,12 +1082,11 @@ constexpr size_t kFlushBytes = (size_t)96 << 20;
 constexpr size_t kFlushRecords = 1024;
 }  // namespace
 
-bool Plan::jit_possible() const { return sub_tiles != 4 && ablate == 0 && !knobs_.no_jit; }
+bool Plan::jit_possible() const { return sub_tiles != 4 && !knobs_.no_jit; }
 
 Plan::Knobs::Knobs() {
   no_jit = std::getenv("FDB_NO_JIT") != nullptr;
   runs_always = std::getenv("FDB_RUNS_ALWAYS") != nullptr;
-  no_identity_lut = std::getenv("FDB_NO_IDENTITY_LUT") != nullptr;
   runs_no_sort = std::getenv("FDB_RUNS_NO_SORT") != nullptr;
   no_uniform_fold = std::getenv("FDB_NO_UNIFORM_FOLD") != nullptr;
   no_present_ids = std::getenv("FDB_NO_PRESENT_IDS") != nullptr;  // (A/B aid: Finish ships dictionary indices at the dictionary's width)
@@ -1130,8 +1128,8 @@ void Plan::push(const ArrowArray* array, const ArrowSchema* schema) {
   // small record: copy now (through pinned staging — the source is not touched after this call), scan later
   const RecordSink sink = [this](size_t bytes, void** dev, unsigned char** pinned) { slab_reserve(bytes, dev, pinned); };
   std::unique_ptr<DeviceBatch> b = import_batch(view, device_, &want, stream_, ctx_, /*via_ring=*/true, &sink);
-  static const size_t ship_bytes = std::getenv("FDB_SLAB_SHIP_MB") ? (size_t)std::atoll(std::getenv("FDB_SLAB_SHIP_MB")) << 20 : (size_t)2 << 20;  // (tuning aid; 2 … 32 MiB measured within noise of each other, 2 MiB keeps the device busy earliest)
-  if (slab_.used - slab_.shipped >= ship_bytes) slab_ship();
+  constexpr size_t kShipBytes = (size_t)2 << 20;  // (2 … 32 MiB measured within noise of each other, 2 MiB keeps the device busy earliest)
+  if (slab_.used - slab_.shipped >= kShipBytes) slab_ship();
   lap(tp, prof_push_[1]);
   {
     // errors the record would raise surface here, at its own Callback, not at some later launch
@@ -1513,7 +1511,6 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     a.cnt = d_cnt_;
     a.n_slots = n_slots_;
     a.need_count = 0;
-    a.ablate = ablate;
     for (size_t j = 0; j < aggs_.size(); j++) if (a.aggs[j].func == FDB_AGG_COUNT) a.need_count = 1;
     a.lut_class = lut_class[(size_t)i];
     // LDS plan: [LUT copies][cnt u32 × n_slots][acc u64 × n_slots × n_aggs]
@@ -1604,7 +1601,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     }
     // A kernel specialised for this plan shape (fdb_jit.cpp), when every record of the launch has the same shape;
     // otherwise (or when hiprtc is unavailable) the interpreting slot kernel.
-    if (sub_tiles != 4 && ablate == 0 && lds_bytes <= 150 * 1024) {  // (gfx950: up to 160 KiB of LDS per workgroup)
+    if (sub_tiles != 4 && lds_bytes <= 150 * 1024) {  // (gfx950: up to 160 KiB of LDS per workgroup)
       JitShape shape;
       bool same = true, first = true;
       const FdbScanArgs& args0 = Rs[(size_t)live[0]].args;
@@ -2678,8 +2675,6 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::filter_batches_impl(const Device
     int waves = row_bytes > 0 ? (131072 / (64 * 4 * 4)) / row_bytes : 8;
     waves = std::max(8, std::min(28, waves));
     per_cu = std::max(1, std::min(jit_blocks_per_cu(one_pass ? select_fn : flags_fn, first_block, first_lds), waves / (first_block / 64)));
-    static const int env_per_cu = std::getenv("FDB_FLAGS_BLOCKS_PER_CU") ? std::atoi(std::getenv("FDB_FLAGS_BLOCKS_PER_CU")) : 0;  // (tuning aid)
-    if (env_per_cu > 0) per_cu = env_per_cu;
   }
   int64_t grid = (int64_t)(fdb_scan_default_grid(device_) / 2) * per_cu;
   if (grid_override > 0) grid = grid_override;
@@ -2923,8 +2918,7 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::filter_batches_impl(const Device
       // the waves that finish late — measured 8 % faster than exactly-resident; handing tiles out dynamically, one ticket per tile or per
       // 8 tiles on a per-column counter, was slower: 2.5 ms and 1.08 ms against 0.90), at least one wave per column, never more waves
       // than a column has tiles
-      static const int env_per_cu = std::getenv("FDB_COMPACT_BLOCKS_PER_CU") ? std::atoi(std::getenv("FDB_COMPACT_BLOCKS_PER_CU")) : 0;  // (tuning aid)
-      const int64_t budget = (int64_t)(fdb_scan_default_grid(device_) / 2) * (env_per_cu > 0 ? env_per_cu : (fdb_compact_multi_blocks_per_cu(any_nullable) * 3 + 1) / 2) * 4;
+      const int64_t budget = (int64_t)(fdb_scan_default_grid(device_) / 2) * ((fdb_compact_multi_blocks_per_cu(any_nullable) * 3 + 1) / 2) * 4;
       int64_t weight_sum = 0;
       for (size_t r = 0; r < n_rest; r++) weight_sum += cols[r].width;
       std::vector<int32_t> wave_begin(n_rest + 1, 0);

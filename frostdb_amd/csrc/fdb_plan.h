@@ -282,7 +282,6 @@ class Plan {
   double stat_merge_ms = 0;      // device time of cross-GPU merges (hipEvent pairs around the collectives of comm_allreduce / comm_exchange)
   int rows_per_thread = 0;  // 0: slot (load-hoisting) kernel; 4 / 8: sequential kernel
   int grid_override = 0;
-  int ablate = 0;
   int sub_tiles = 0;  // kernel variant mode: 0 default, 1: 512 thr, 2: 256 thr, 3: 1024 thr, 4: interpreting kernel only (no plan specialisation)
   const char* last_kernel() const { return last_kernel_; }
   bool deterministic = false;  // fdb_plan_set_deterministic: wave-private LDS tables, fixed-order folds; scans that cannot have them are refused
@@ -355,7 +354,7 @@ class Plan {
   // A/B and test switches of the environment, read ONCE per plan (at create): getenv on the per-record path costs a scan of the environment
   // and is not safe against a concurrent setenv. A test sets them before it creates its plan.
   struct Knobs {
-    bool no_jit, runs_always, no_identity_lut, runs_no_sort, no_uniform_fold, no_present_ids;
+    bool no_jit, runs_always, runs_no_sort, no_uniform_fold, no_present_ids;
     char runs_wide;             // 0 unset, '1' wide records every launch, 'm' medium where narrow would do
     long long ordered_sort_min; // groups from which an ordered Finish out of the table sorts on the device
     long long present_ids_min_bytes;  // index bytes a Finish must stand to save before it ranks the ids present ($FDB_PRESENT_IDS_MIN_BYTES), 32 MiB

@@ -1,5 +1,5 @@
-"""Where cfg 5's hash scan spends its time (tuning aid): kernel time per launch with parts of the kernel compiled out,
-and the phases of Finish. usage: cfg5_ablate.py [rows] [groups]"""
+"""Where cfg 5's hash scan spends its time (tuning aid): kernel time per launch of the specialised and the interpreting kernel,
+over a few grid sizes and on a second pass that inserts nothing, and the phases of Finish. usage: cfg5_ablate.py [rows] [groups]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from concurrent.futures import ThreadPoolExecutor
@@ -14,16 +14,15 @@ with ThreadPoolExecutor(8) as ex:
     batches = list(ex.map(lambda i: synth.cfg5_chunk(0, i, min(chunk, rows - i * chunk), n_groups=groups), range((rows + chunk - 1) // chunk)))
 resident = [pp.ResidentBatch(b) for b in batches]
 aggs, G = [Sum(Col("value"))], [DynCol("labels")]
-modes = [(0, "specialised kernel (fdb_hash_kernel)"), (2, "specialised: probe only (no count/sum atomics)"), (1, "specialised: stream + fingerprint only"),
-         (4 << 5, "interpreting kernel, full"), ((4 << 5) | 2, "interpreting: probe only (no count/sum atomics)"), ((4 << 5) | 1, "interpreting: stream + fingerprint only")]
+# set_tuning's second argument: bits 0-19 grid override, bits 25-27 variant mode (4 = interpreting kernels only)
+modes = [(0, "specialised kernel (fdb_hash_kernel)"), (4 << 25, "interpreting kernel")]
 for g in (512, 1024, 2048, 4096):
-    modes.append(((g << 8) | 1, f"specialised: stream + fingerprint only, grid {g}"))
-for ablate, what in modes:
+    modes.append((g, f"specialised kernel, grid {g}"))
+for mode, what in modes:
     for it in range(2):
         plan = pp.HashAggregatePlan(None, aggs, G)
         plan.set_timing(True)
-        # low 4 bits: ablate; bits 5-7: variant mode (4 = interpreting kernels only); bits 8+: grid override
-        plan.set_tuning(0, ((ablate & 15) << 20) | (((ablate >> 5) & 7) << 25) | (ablate >> 8))
+        plan.set_tuning(0, mode)
         t0 = time.perf_counter()
         plan.CallbackResident(resident)
         t1 = time.perf_counter()
@@ -31,22 +30,19 @@ for ablate, what in modes:
         t2 = time.perf_counter()
         st = plan.stats()
         kern = plan.last_kernel()
-        if ablate == 0:
-            out = plan.Finish()
+        out = plan.Finish()
         t3 = time.perf_counter()
         plan.Close()
     print(f"{kern:18s} {what:50s} kernel {st['kernel_ms'] / st['launches']:.3f} ms/launch x {st['launches']}  {st['algorithmic_bytes'] / st['kernel_ms'] / 1e6:8.1f} GB/s  "
           f"push {1e3 * (t1 - t0):.1f} ms  finish {1e3 * (t3 - t2):.1f} ms  groups {n}", flush=True)
 # steady state: a second pass over the same rows finds every group (no inserts, no key-store writes)
-for mode, what in [(0, "specialised"), (2 << 20, "specialised, probe only"), (1 << 20, "specialised, stream only"), (4 << 25, "interpreting")]:
+for mode, what in [(0, "specialised"), (4 << 25, "interpreting")]:
     plan = pp.HashAggregatePlan(None, aggs, G)
     plan.set_timing(True)
     plan.set_tuning(0, mode)
-    plan.set_tuning(0, mode & ~(15 << 20))  # first pass always builds the table
     plan.CallbackResident(resident)
     plan.num_groups()
     st0 = plan.stats()
-    plan.set_tuning(0, mode)
     plan.CallbackResident(resident)
     plan.num_groups()
     st1 = plan.stats()

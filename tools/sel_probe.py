@@ -1,5 +1,5 @@
-"""Tuning aid: times fdb_plan_filter_batches (value > 500 over 4 × 25 M resident rows) without checking results — for kernel
-variants that deliberately break them (FDB_COMPACT_BLOCKS_PER_CU). Prints kernel ms per pass (hipEvents) and wall ms."""
+"""Tuning aid: times fdb_plan_filter_batches (value > 500 over 4 × 25 M resident rows) without checking results. Prints kernel ms
+per pass (hipEvents) and wall ms."""
 import os, sys, time
 sys.path.insert(0, os.environ.get("FDB_PKG_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # (FDB_PKG_ROOT: A/B against another build of the package)
 import torch
