@@ -132,6 +132,28 @@ int fdb_selftest_widen(const void* src, int32_t width, uint32_t* dst, int64_t n)
   });
 }
 
+int fdb_selftest_exact_sum(const double* x, int64_t n, double* out) {
+  return guard(nullptr, [&] {
+    if (n < 0 || out == nullptr || (n > 0 && x == nullptr)) throw fdb::Error(FDB_ERR_INVALID, "exact sum: n >= 0 and non-null buffers");
+    // the host twin of the device path: the same digit split into the same limbs, the same normalize and rounding (fdb_kernels.h);
+    // the adds run as the scan would between two normalizes
+    long long limbs[FDB_EXACT_LIMBS] = {0};
+    unsigned long long flags = 0;
+    int64_t since = 0;
+    for (int64_t i = 0; i < n; i++) {
+      unsigned long long bits;
+      std::memcpy(&bits, x + i, 8);
+      int k; long long d0, d1, d2;
+      const unsigned long long f = fdb_exact_split(bits, &k, &d0, &d1, &d2);
+      if (f != 0ull) { flags |= f; continue; }
+      limbs[k] += d0; limbs[k + 1] += d1; limbs[k + 2] += d2;
+      if (++since == ((int64_t)1 << 30)) { fdb_exact_normalize(limbs); since = 0; }
+    }
+    const unsigned long long r = fdb_exact_round(limbs, flags);
+    std::memcpy(out, &r, 8);
+  });
+}
+
 int fdb_arrow_roundtrip(struct ArrowArray* batch, struct ArrowSchema* schema, struct ArrowArray* out, struct ArrowSchema* out_schema) {
   return guard(nullptr, [&] {
     if (out == nullptr || out_schema == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null output");
@@ -253,7 +275,7 @@ int fdb_plan_merge(fdb_plan* dst, fdb_plan* src) {
 
 int fdb_plan_group_schema(fdb_plan* plan, struct ArrowArray* out, struct ArrowSchema* out_schema) {
   if (!plan || !out || !out_schema) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); plan->plan.group_schema(out, out_schema); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_group_schema"); plan->plan.settle(); plan->plan.group_schema(out, out_schema); });
 }
 
 int fdb_plan_seed_groups(fdb_plan* plan, struct ArrowArray* schema_record, struct ArrowSchema* schema) {
@@ -263,7 +285,7 @@ int fdb_plan_seed_groups(fdb_plan* plan, struct ArrowArray* schema_record, struc
 
 int fdb_plan_hash_export(fdb_plan* src, fdb_plan* layout, int32_t n_parts, void** dev_rows, int64_t* counts, int32_t* row_words32) {
   if (!src || !layout || !dev_rows || !counts || !row_words32) return FDB_ERR_INVALID;
-  return guard(src, [&] { single_table_only(src); single_table_only(layout); src->plan.settle(); layout->plan.settle(); src->plan.hash_export(layout->plan, n_parts, dev_rows, counts, row_words32); });
+  return guard(src, [&] { single_table_only(src); single_table_only(layout); src->plan.refuse_exact("fdb_plan_hash_export"); layout->plan.refuse_exact("fdb_plan_hash_export"); src->plan.settle(); layout->plan.settle(); src->plan.hash_export(layout->plan, n_parts, dev_rows, counts, row_words32); });
 }
 
 int fdb_plan_hash_import(fdb_plan* plan, const void* dev_rows, int64_t n_rows) {
@@ -359,32 +381,32 @@ int fdb_plan_partial_state(fdb_plan* plan, int32_t agg, void* dst, int64_t capac
 
 int fdb_plan_state_signature(fdb_plan* plan, uint64_t* signature, int64_t* n_slots) {
   if (!plan) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); *signature = plan->plan.state_signature(n_slots); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_state_signature"); plan->plan.settle(); *signature = plan->plan.state_signature(n_slots); });
 }
 
 int fdb_plan_state_pointers(fdb_plan* plan, void** base, int64_t* array_stride, int64_t* n_slots) {
   if (!plan) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); plan->plan.state_pointers(base, array_stride, n_slots); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_state_pointers"); plan->plan.settle(); plan->plan.state_pointers(base, array_stride, n_slots); });
 }
 
 int fdb_plan_state_read(fdb_plan* plan, int32_t array, void* dst, int64_t capacity_bytes) {
   if (!plan) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); plan->plan.state_read(array, dst, capacity_bytes); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_state_read"); plan->plan.settle(); plan->plan.state_read(array, dst, capacity_bytes); });
 }
 
 int fdb_plan_state_write(fdb_plan* plan, int32_t array, const void* src, int64_t bytes) {
   if (!plan) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); plan->plan.state_write(array, src, bytes); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_state_write"); plan->plan.settle(); plan->plan.state_write(array, src, bytes); });
 }
 
 int fdb_plan_state_arrays(fdb_plan* plan, int32_t* n_arrays) {
   if (!plan || !n_arrays) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); *n_arrays = plan->plan.num_state_arrays(); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_state_arrays"); *n_arrays = plan->plan.num_state_arrays(); });
 }
 
 int fdb_plan_state_array_op(fdb_plan* plan, int32_t array, int32_t* op) {
   if (!plan || !op) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); *op = plan->plan.state_array_op(array); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_state_array_op"); plan->plan.settle(); *op = plan->plan.state_array_op(array); });
 }
 
 int fdb_plan_agg_type(fdb_plan* plan, int32_t agg, char* format_out) {
@@ -525,6 +547,16 @@ int fdb_plan_set_deterministic(fdb_plan* plan, int32_t enabled) {
   return FDB_OK;
 }
 
+int fdb_plan_set_exact_sums(fdb_plan* plan, int32_t enabled) {
+  if (!plan) return FDB_ERR_INVALID;
+  return guard(plan, [&] {
+    if (plan->plan.started() || (plan->dyn && plan->dyn->started()))
+      throw fdb::Error(FDB_ERR_STATE, "exact sums can only be switched before the plan's first push, merge or seed");
+    plan->plan.set_exact_sums(enabled != 0);
+    if (plan->dyn) plan->dyn->exact = enabled != 0;  // (every member plan, made on first sight of its column, inherits it)
+  });
+}
+
 const char* fdb_plan_last_kernel(fdb_plan* plan) {
   if (!plan) return "";
   (void)guard(plan, [&] { plan->plan.settle(); });
@@ -580,6 +612,7 @@ int fdb_plan_allreduce(fdb_plan* plan, fdb_comm* comm, int32_t* aligned) {
   return guard(plan, [&] {
     if (comm == nullptr || !comm->c || aligned == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     single_table_only(plan);
+    plan->plan.refuse_exact("fdb_plan_allreduce (exact sums across GPUs are not supported yet)");
     *aligned = plan->plan.comm_allreduce(*comm->c) ? 1 : 0;
   });
 }
@@ -589,6 +622,7 @@ int fdb_plan_exchange(fdb_plan* plan, fdb_comm* comm, fdb_plan** shard) {
   return guard(plan, [&] {
     if (comm == nullptr || !comm->c || shard == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     single_table_only(plan);
+    plan->plan.refuse_exact("fdb_plan_exchange (exact sums across GPUs are not supported yet)");
     *shard = nullptr;
     std::unique_ptr<fdb_plan> s(new fdb_plan(plan->plan));
     plan->plan.comm_exchange(*comm->c, s->plan);

@@ -163,6 +163,7 @@ DynamicAggs::Child* DynamicAggs::child_for(const std::string& field, int32_t fun
   std::vector<fdb_aggregation> aggs{a};
   const fdb_plan_desc v = desc_.view(aggs, /*final_stage=*/false);
   c->plan = std::make_unique<Plan>(&v, device_);
+  if (exact) c->plan->set_exact_sums(true);
   children_.push_back(std::move(c));
   return children_.back().get();
 }
@@ -235,6 +236,7 @@ int64_t DynamicAggs::num_groups(Plan& main) {
 void DynamicAggs::merge_from(Plan& main, DynamicAggs& src, Plan& src_main) {
   if (src.desc_.dynamic_aggs.size() != desc_.dynamic_aggs.size() || src.main_active() != main_active())
     throw Error(FDB_ERR_INVALID, "plans have different aggregations");
+  if (src.exact != exact) throw Error(FDB_ERR_INVALID, "an exact-sum plan merges only with exact-sum plans");
   settle(main);
   src.settle(src_main);
   if (main_active()) main.merge_from(src_main);

@@ -66,6 +66,8 @@ class DynamicAggs {
   void settle(Plan& main);
   // Draw: like HashAggregate.Draw (aggregate.go:226-243) only the aggregations that exist so far are listed — the static ones.
   const char* draw(Plan& main);
+  bool exact = false;                                          // fdb_plan_set_exact_sums: passed to every member plan
+  bool started() const { return !children_.empty(); }
 
  private:
   struct Child {

@@ -47,10 +47,11 @@ void Plan::hash_layout() {
     for (size_t j = 0; j < aggs_.size(); j++)
       idents[j] = aggs_[j].func == FDB_AGG_MIN ? (unsigned long long)FDB_I64_MAX : aggs_[j].func == FDB_AGG_MAX ? (unsigned long long)FDB_I64_MIN : 0ull;
     hip_check(fdb_launch_hash_init(nt, h_capacity_, ew, (int)aggs_.size(), idents, stream_), "hash init");
-    hip_check(fdb_launch_hash_rehash(h_table_, h_keys_, h_capacity_, h_key_words_, h_key_used_, nt, nk, h_capacity_ - 1, ew, kw, stream_), "hash rehash");
+    unsigned long long* nl = exact_limbs_alloc(h_capacity_);
+    hip_check(fdb_launch_hash_rehash(h_table_, h_keys_, h_capacity_, h_key_words_, h_key_used_, nt, nk, h_capacity_ - 1, ew, kw, stream_, d_limbs_, nl, n_exact_), "hash rehash");
     hip_check(hipStreamSynchronize(stream_), "sync(rehash)");
-    ctx_->dev_free(h_table_); ctx_->dev_free(h_keys_);
-    h_table_ = nt; h_keys_ = nk; h_key_words_ = kw;
+    ctx_->dev_free(h_table_); ctx_->dev_free(h_keys_); ctx_->dev_free(d_limbs_);
+    h_table_ = nt; h_keys_ = nk; h_key_words_ = kw; d_limbs_ = nl;
   }
   h_key_used_ = used;
 }
@@ -77,16 +78,63 @@ void Plan::hash_reserve(uint64_t extra, uint64_t expected_groups) {
   for (size_t j = 0; j < aggs_.size(); j++)
     idents[j] = aggs_[j].func == FDB_AGG_MIN ? (unsigned long long)FDB_I64_MAX : aggs_[j].func == FDB_AGG_MAX ? (unsigned long long)FDB_I64_MIN : 0ull;
   hip_check(fdb_launch_hash_init(nt, need, ew, (int)aggs_.size(), idents, stream_), "hash init");
+  unsigned long long* nl = exact_limbs_alloc(need);  // (exact SUMs: the limb rows beside the table, moved by the rehash)
   if (h_table_ != nullptr) {
-    hip_check(fdb_launch_hash_rehash(h_table_, h_keys_, h_capacity_, kw, h_key_used_, nt, nk, need - 1, ew, kw, stream_), "hash rehash");
+    hip_check(fdb_launch_hash_rehash(h_table_, h_keys_, h_capacity_, kw, h_key_used_, nt, nk, need - 1, ew, kw, stream_, d_limbs_, nl, n_exact_), "hash rehash");
     hip_check(hipStreamSynchronize(stream_), "sync(rehash)");
-    ctx_->dev_free(h_table_); ctx_->dev_free(h_keys_);
+    ctx_->dev_free(h_table_); ctx_->dev_free(h_keys_); ctx_->dev_free(d_limbs_);
   }
   if (h_count_dev_ == nullptr) {
     h_count_dev_ = (unsigned long long*)ctx_->dev_alloc(256);
     hip_check(hipMemsetAsync(h_count_dev_, 0, 256, stream_), "hipMemsetAsync(counter)");
   }
-  h_table_ = nt; h_keys_ = nk; h_capacity_ = need;
+  h_table_ = nt; h_keys_ = nk; h_capacity_ = need; d_limbs_ = nl;
+}
+
+// ---- exact float64 SUMs (fdb_plan_set_exact_sums) -----------------------------------------------------------------------------------
+void Plan::set_exact_sums(bool on) {
+  if (started_) throw Error(FDB_ERR_STATE, "exact sums can only be switched before the plan's first push, merge or seed");
+  exact_ = on;
+  n_exact_ = 0;
+  if (on) for (const AggState& A : aggs_) if (A.func == FDB_AGG_SUM) n_exact_++;
+  // an exact plan lives in the hash table from its first row on (never the dense, register or LDS variants, never a run store)
+  mode_ = on ? TableMode::HASH : TableMode::DENSE;
+  draw_.clear();
+}
+
+void Plan::refuse_exact(const char* what) const {
+  if (exact_) throw Error(FDB_ERR_UNSUPPORTED, std::string(what) + ": not available for a plan with exact sums (its accumulators are limb rows, not float64 words)");
+}
+
+int Plan::exact_q(size_t j) const {
+  if (!exact_ || aggs_[j].func != FDB_AGG_SUM) return -1;
+  int q = 0;
+  for (size_t i = 0; i < j; i++) if (aggs_[i].func == FDB_AGG_SUM) q++;
+  return q;
+}
+
+bool Plan::exact_f64(size_t j) const { return exact_q(j) >= 0 && aggs_[j].type == FDB_T_F64; }
+
+unsigned long long* Plan::exact_limbs_alloc(uint64_t capacity) {
+  if (n_exact_ == 0) return nullptr;
+  const size_t bytes = (size_t)n_exact_ * (size_t)capacity * FDB_EXACT_WORDS * 8;
+  unsigned long long* p = (unsigned long long*)ctx_->dev_alloc(bytes);
+  hip_check(hipMemsetAsync(p, 0, bytes, stream_), "hipMemsetAsync(limbs)");
+  return p;
+}
+
+void Plan::exact_normalize_now() {
+  if (n_exact_ != 0 && h_table_ != nullptr)
+    hip_check(fdb_launch_exact_normalize(d_limbs_, h_table_, h_capacity_, h_entry_words_, n_exact_, stream_), "exact normalize");
+  exact_adds_ = 0;
+}
+
+void Plan::exact_finalize() {
+  if (n_exact_ == 0 || h_table_ == nullptr) return;
+  FdbExactWords w;
+  for (int q = 0; q < FDB_MAX_AGGS; q++) w.w[q] = -1;
+  for (size_t j = 0; j < aggs_.size(); j++) if (exact_f64(j)) w.w[exact_q(j)] = 3 + (int)j;
+  hip_check(fdb_launch_exact_finalize(d_limbs_, h_table_, h_capacity_, h_entry_words_, n_exact_, w, stream_), "exact finalize");
 }
 
 // Groups the scan will end with, estimated from what it has seen: `d` distinct groups after `n` rows. Under a uniform draw from G
@@ -129,6 +177,7 @@ void Plan::hash_merge_args(FdbHashMergeArgs* m, const std::vector<FdbHashCol>& c
   for (size_t j = 0; j < aggs_.size(); j++) {
     const int32_t f = aggs_[j].func;
     m->funcs[j] = f == FDB_AGG_COUNT ? (final_stage_ ? 1 : 0) : f == FDB_AGG_SUM ? (aggs_[j].type == FDB_T_F64 ? 2 : 1) : f == FDB_AGG_MIN ? 3 : 4;
+    if (exact_q(j) >= 0 && aggs_[j].type != FDB_T_I64) m->funcs[j] = 0;  // exact SUM: the limb rows merge (an integer SUM keeps its word)
   }
   // how much of an incoming tuple the columns reach, and whether it already has our layout
   int reach = 2;
@@ -269,10 +318,13 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
       if (bytes <= 8192 && lds_off + bytes <= 60 * 1024) { hcols[g].lut_lds = (uint32_t)lds_off; lds_off = align_up_sz(lds_off + bytes, 16); }
     }
     a.lds_lut_bytes = (uint32_t)align_up_sz(lds_off, 16);
-    h.hcols = (const FdbHashCol*)upload(hcols.data(), std::max<size_t>(hcols.size(), 1) * sizeof(FdbHashCol));
+    static const FdbHashCol kNoHashCol = {};  // (no group columns: one group; the kernels read no descriptor)
+    h.hcols = (const FdbHashCol*)(hcols.empty() ? upload(&kNoHashCol, sizeof(FdbHashCol)) : upload(hcols.data(), hcols.size() * sizeof(FdbHashCol)));
     h.n_hcols = (int)hcols.size();
     h.key_words = h_key_words_;
     h.entry_words = h_entry_words_;
+    // exact SUMs: FdbAgg.acc = the aggregation's limb rows (set per launch below: the table may grow); nullptr for every other one
+    for (int j = 0; j < a.n_aggs; j++) a.aggs[j].acc = exact_f64((size_t)j) ? (unsigned long long*)(uintptr_t)1 : nullptr;
     const int grid = fdb_scan_default_grid(device_) * 4;  // 256-thread workgroups, 8 per CU
     // The run-time specialised kernel for this record's shape (fdb_jit.cpp), or the interpreting scan_hash_kernel
     hipFunction_t jit_fn = nullptr;
@@ -350,19 +402,29 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
         if (!h_bound_stale_ && h_rows_seen_ >= (uint64_t)(1 << 20) && h_groups_bound_ > 0) {
           expected = estimate_final_groups(h_groups_bound_, h_rows_seen_, h_rows_seen_ + rows_left_total);
           expected += expected / 4;  // head-room for the estimate's error
-          const uint64_t bytes_per_slot = (uint64_t)h_entry_words_ * 8 + (uint64_t)h_key_words_ * 4;
+          const uint64_t bytes_per_slot = (uint64_t)h_entry_words_ * 8 + (uint64_t)h_key_words_ * 4 + (uint64_t)n_exact_ * FDB_EXACT_WORDS * 8;
           if (next_pow2(2 * (expected + (uint64_t)kChunkRows)) * bytes_per_slot > ((uint64_t)64 << 30)) expected = 0;  // (beyond a sane budget: grow step by step)
         }
         // room for a decent next chunk on top of the expected groups: 1/8 of what is left, 4 M … 32 M rows
         const uint64_t want_chunk = expected == 0 ? min_chunk
-                                                  : std::min<uint64_t>(left_here, std::max<uint64_t>((uint64_t)kChunkRows, std::min<uint64_t>(rows_left_total / 8, (uint64_t)32 << 20)));
+                                                  : std::min<uint64_t>(left_here, std::max<uint64_t>((uint64_t)kChunkRows, std::min<uint64_t>(rows_left_total / 8, n_exact_ != 0 ? (uint64_t)kChunkRows : (uint64_t)32 << 20)));
+        // (exact SUMs: every slot of head-room costs its 576-byte limb rows, so the chunks stay small)
         hash_reserve(want_chunk, expected);
         room = room_now();
       }
       // chunk boundaries inside a record stay on tile boundaries (1 024 rows): the kernels address 4-row lane groups with 16-byte
       // loads and read validity bitmaps bytewise from the chunk's first row
       if (room < left_here) room &= ~(uint64_t)1023;
-      const int64_t r1 = r0 + (int64_t)std::min<uint64_t>(left_here, room);
+      int64_t r1 = r0 + (int64_t)std::min<uint64_t>(left_here, room);
+      if (n_exact_ != 0) {  // a limb takes one digit per row: normalize before the adds since the last one could pass the limit
+        const uint64_t lim = (uint64_t)knobs_.exact_normalize_rows;
+        if ((uint64_t)(r1 - r0) > lim - std::min(lim, exact_adds_) && lim - std::min(lim, exact_adds_) < 1024) exact_normalize_now();
+        const uint64_t allow = lim - std::min(lim, exact_adds_);
+        if ((uint64_t)(r1 - r0) > allow) r1 = r0 + (int64_t)(allow & ~(uint64_t)1023);
+        exact_adds_ += (uint64_t)(r1 - r0);
+        for (int j = 0; j < a.n_aggs; j++)
+          if (exact_f64((size_t)j)) h.base.aggs[j].acc = d_limbs_ + (uint64_t)exact_q((size_t)j) * h_capacity_ * FDB_EXACT_WORDS;
+      }
       if (std::getenv("FDB_PROFILE")) std::fprintf(stderr, "[fdb] hash chunk rows [%lld, %lld) capacity %llu bound %llu seen %llu\n", (long long)r0, (long long)r1,
                                                   (unsigned long long)h_capacity_, (unsigned long long)h_groups_bound_, (unsigned long long)h_rows_seen_);
       h.table = h_table_; h.keys = h_keys_; h.n_groups = h_count_dev_; h.mask = h_capacity_ - 1;
@@ -401,6 +463,7 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
 void Plan::fetch_compact_hash(CompactState* cs) {
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (h_table_ == nullptr) { sync(); return; }
+  exact_finalize();
   const uint64_t n = hash_groups();
   cs->n = (int64_t)n;
   if (n == 0) { sync(); return; }
@@ -482,6 +545,7 @@ int host_threads_for(size_t elements) {
 // (uint32 indices), into an arena the batch owns; nothing crosses PCIe but the per-column NULL counts.
 int64_t Plan::finish_columns_hash(std::vector<OutColumn>* out, DeviceBatch* resident, const RunsView* runs) {
   hip_check(hipSetDevice(device_), "hipSetDevice");
+  if (runs == nullptr) exact_finalize();  // (exact SUMs: the rounded sums into the accumulator words; the rest of Finish is unchanged)
   PhaseTimer pt;
   // (`runs`: the groups come from an ordered plan's run store instead of the table — pass 1 below is runs_expand, everything
   // after it — the column pass, transport widths, slices, widening, the resident form — is shared)
@@ -943,6 +1007,8 @@ void Plan::group_schema(ArrowArray* out, ArrowSchema* out_schema) {
 }
 
 void Plan::seed_groups(const ArrowArray* array, const ArrowSchema* schema) {
+  refuse_exact("fdb_plan_seed_groups");
+  started_ = true;
   runs_to_table();
   HostRecordView view;
   view_record(array, schema, &view);
@@ -1066,6 +1132,8 @@ void Plan::hash_export(Plan& layout, int n_parts, void** dev_rows, int64_t* coun
 }
 
 void Plan::hash_import(const void* dev_rows, int64_t n_rows, bool unique_rows) {
+  refuse_exact("fdb_plan_hash_import");
+  started_ = true;
   runs_to_table();
   if (n_rows <= 0) return;
   hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -1152,6 +1220,12 @@ void Plan::merge_hash_tables(Plan& src) {
   m.src_table = src.h_table_; m.src_keys = src.h_keys_; m.src_capacity = src.h_capacity_;
   m.src_key_words = src.h_key_words_; m.src_entry_words = src.h_entry_words_;
   m.unique_source = 1;
+  if (n_exact_ != 0) {
+    // a destination limb becomes the sum of two: normalize both sides first when the adds behind them could pass the limit
+    if (exact_adds_ + src.exact_adds_ + 1 > (uint64_t)knobs_.exact_normalize_rows) { exact_normalize_now(); src.exact_normalize_now(); }
+    m.exact_src = src.d_limbs_; m.exact_dst = d_limbs_; m.n_exact = n_exact_;
+    exact_adds_ += src.exact_adds_ + 1;
+  }
   // the source's stream may still be writing its table
   src.sync();
   hip_check(fdb_launch_hash_merge(m, device_, stream_), "hash merge (table)");

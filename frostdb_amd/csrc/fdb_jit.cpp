@@ -972,7 +972,16 @@ struct HashGen {
     for (size_t i = 0; i < s.exprs.size(); i++) if (s.exprs[i].kind == 1) o << "  const long long K_elit" << i << " = a.expr[" << i << "].lit; (void)K_elit" << i << ";\n";
     o << "  const int ew = h.entry_words;\n  const long long n_tiles = (h.row_end - h.row_begin + " << TILE - 1 << ") / " << TILE << ";\n";
     o << "  const uint32_t lane_shb = (tid & 1u) * 4u;\n";
+    // exact SUMs: the row work sits in a do { } while (0) — a `continue` leaves it — so that every lane of the wave meets again at the
+    // limb adds after it (fdb_exact_add_wave combines across lanes); x_slot / x_sel / xv* carry the tile's slots, rows and values there
+    auto exact_agg = [&](size_t j) { return s.exact && s.aggs[j].func == FDB_AGG_SUM && s.aggs[j].type == FDB_T_F64; };
     o << "  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {\n";
+    if (s.exact) {
+      o << "    uint64_t x_slot0 = 0, x_slot1 = 0, x_slot2 = 0, x_slot3 = 0;\n    uint32_t x_sel = 0u;\n";
+      for (size_t j = 0; j < s.aggs.size(); j++)
+        if (exact_agg(j)) o << "    unsigned long long xv" << j << "_0 = 0, xv" << j << "_1 = 0, xv" << j << "_2 = 0, xv" << j << "_3 = 0;\n";
+      o << "    do {\n";
+    }
     o << "    const long long r0 = h.row_begin + tile * " << TILE << "LL;\n    const long long left = h.row_end - r0 - (long long)tid * 4;\n    if (left <= 0) continue;\n";
     o << "    const size_t o4 = (size_t)r0 * 4, o8 = (size_t)r0 * 8, ob = (size_t)(r0 >> 3);\n";
     // The lane offsets are made opaque per tile: otherwise the compiler pre-computes one 64-bit (column base + lane offset)
@@ -1106,12 +1115,13 @@ struct HashGen {
           raw = "(" + expr_valid(s.exprs, A.expr - 1, col, colvalid) + " ? " + expr_bits(s.exprs, A.expr - 1, expr_value(s.exprs, A.expr - 1, col, colvalid)) + " : 0ull)";
         }
         const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k);
-        if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) o << "    double " << v << " = __longlong_as_double((long long)" << raw << ");\n";
+        if (exact_agg(j)) o << "    xv" << j << "_" << k << " = " << raw << ";\n";
+        else if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) o << "    double " << v << " = __longlong_as_double((long long)" << raw << ");\n";
         else if (A.func == FDB_AGG_SUM) o << "    unsigned long long " << v << " = " << raw << ";\n";
         else o << "    long long " << v << " = " << (A.type == FDB_T_F64 ? ("f64_minmax_key(__longlong_as_double((long long)" + raw + "), " + (A.func == FDB_AGG_MIN ? "true" : "false") + ")") : ("(long long)" + raw)) << ";\n";
       }
     }
-    for (int k = 1; k < 4; k++) {
+    for (int k = 1; k < 4 && !s.exact; k++) {
       o << "    if (((sel >> " << (k - 1) << ") & 3u) == 3u && h1_" << (k - 1) << " == h1_" << k << " && h2_" << (k - 1) << " == h2_" << k << ") {\n";
       o << "      cnt_" << k << " += cnt_" << (k - 1) << ";\n";
       for (size_t j = 0; j < s.aggs.size(); j++) {
@@ -1134,6 +1144,7 @@ struct HashGen {
     };
     // (lanes that left the tile early — rows past the end, nothing selected by the filter — do not take part: what a shuffle
     // reads from them is not data, so their bits in `act` gate every value that comes from another lane)
+    if (!s.exact) {  // (exact SUMs: no folding — every selected row goes to the table; the limb adds combine lanes instead)
     o << "    {\n      const int wl = (int)(tid & 63u);\n      const bool has = sel != 0u;\n      const unsigned long long act = __ballot(1);\n";
     o << "      const int kf = has ? __builtin_ctz(sel) : 0, kl = has ? 31 - __builtin_clz(sel) : 0;\n";
     o << "      const unsigned long long fa = " << pick("h1", "kf") << ", fb = " << pick("h2", "kf") << ";\n";
@@ -1178,6 +1189,7 @@ struct HashGen {
     }
     o << "      }\n";
     o << "      if (has && wl < 63 && nh && na == ta && nb == tb) sel &= ~(1u << kl);\n    }\n";
+    }
     std::vector<int> cword(s.cols.size());
     { int w = 4; for (size_t c = 0; c < s.cols.size(); c++) { cword[c] = w; w += s.cols[c].kind == 0 ? 1 : 2; } }
     // (`for_runs`: the wide run records of an ordered plan take the same road — the "inserting" rows are the ones that end a run, the
@@ -1384,7 +1396,7 @@ struct HashGen {
       if (s.need_count) o << "      atomicAdd(e + 2, cnt_" << k << ");\n";
       for (size_t j = 0; j < s.aggs.size(); j++) {
         const JitAgg& A = s.aggs[j];
-        if (A.func == FDB_AGG_COUNT) continue;
+        if (A.func == FDB_AGG_COUNT || exact_agg(j)) continue;
         const std::string v = "v" + std::to_string(j) + "_" + std::to_string(k);
         const std::string acc = "(e + " + std::to_string(3 + j) + ")";
         if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) o << "      atomicAdd(reinterpret_cast<double*>" << acc << ", " << v << ");\n";
@@ -1401,6 +1413,16 @@ struct HashGen {
     // constant 4 + Σ widths before it, tuples are 16-byte aligned, and an aligned quad of dictionary columns is ONE 16-byte store —
     // every store of a scattered tuple is its own write request, and with 34 four-byte stores those were most of an insert's cost.
     emit_tuple_stores(false);
+    if (s.exact) {
+      o << "    x_slot0 = slot_0; x_slot1 = slot_1; x_slot2 = slot_2; x_slot3 = slot_3; x_sel = sel;\n";
+      o << "    } while (0);\n";
+      for (size_t j = 0; j < s.aggs.size(); j++) {
+        if (!exact_agg(j)) continue;
+        o << "    {\n      unsigned long long* XL = a.aggs[" << j << "].acc;\n";
+        for (int k = 0; k < 4; k++) o << "      fdb_exact_add_wave(XL, x_slot" << k << ", xv" << j << "_" << k << ", ((x_sel >> " << k << ") & 1u) != 0u);\n";
+        o << "    }\n";
+      }
+    }
     o << "  }\n";
     if (wide || medium) {
       o << "  {  // the runs that still wait in the waves' stages\n    const int wv = (int)(tid >> 6), wl2 = (int)(tid & 63u);\n    __builtin_amdgcn_wave_barrier();\n";
@@ -1682,7 +1704,7 @@ hipFunction_t jit_get(const JitShape& shape) {
 
 std::string JitHashShape::key() const {
   std::ostringstream k;
-  k << "c" << need_count << (runs == 1 ? "R" : runs == 2 ? "W" : runs == 3 ? "M" : "") << "|";
+  k << "c" << need_count << (runs == 1 ? "R" : runs == 2 ? "W" : runs == 3 ? "M" : "") << (exact ? "X" : "") << "|";
   for (const JitHashCol& C : cols) k << C.kind << (C.has_validity ? 'n' : '-') << (C.lut_identity ? 'i' : C.lut_in_lds ? 'l' : 'g') << (C.kind == 2 ? std::to_string(C.expr_root) : std::string());
   k << '|';
   for (size_t l = 0; l < leaves.size(); l++) {
@@ -1718,6 +1740,7 @@ JitHashShape jit_hash_shape(const FdbHashArgs& h, const FdbHashCol* hcols) {
   for (int j = 0; j < a.n_aggs; j++) {
     s.aggs.push_back({a.aggs[j].func, a.aggs[j].type, -1, a.aggs[j].expr});
     s.agg_validity.push_back(a.aggs[j].validity != nullptr);
+    if (a.aggs[j].func == FDB_AGG_SUM && a.aggs[j].type == FDB_T_F64 && a.aggs[j].acc != nullptr) s.exact = true;
   }
   return s;
 }

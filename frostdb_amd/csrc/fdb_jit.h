@@ -69,6 +69,9 @@ struct JitHashShape {
   // computed; 2: wide records — the table's own key tuple (any cardinality, int64 / computed keys, absent columns), written by the lanes
   // that end a run from re-loaded columns.
   int runs = 0;
+  // Exact float64 SUMs (fdb_plan_set_exact_sums; FdbAgg.acc of such an aggregation = its limb rows): no folding of rows before the
+  // table (a float add would round), each row's value goes into the limbs through fdb_exact_add_wave after the tile's probes.
+  bool exact = false;
   std::string key() const;
 };
 // `hcols` = host copy of args.hcols.

@@ -231,6 +231,112 @@ struct FdbHashArgs {
   int32_t canonical;        // 1: hcols[c].word == 4 + Σ widths of the columns before c and every column of the table is present
 };
 
+// ---- exact float64 sums (fdb_plan_set_exact_sums) ------------------------------------------------------------------------------
+// A group's exact SUM is a fixed-point integer in 66 signed 64-bit LIMBS: limb j weighs 2^(32 j − 1074), so limb 0 is the smallest
+// subnormal and limbs 63 … 65 reach past DBL_MAX. A finite x = ±m · 2^e (m < 2^53, e ≥ −1074) with p = e + 1074 adds the 85-bit value
+// m << (p & 31) as three 32-bit digits to limbs p >> 5 … (p >> 5) + 2 (subtracts them for a negative x). Integer adds are associative,
+// so the limbs — and the one rounding at the end — do not depend on the order of the adds. A digit is < 2^32, so a limb takes 2^31 adds
+// before it could overflow; NORMALIZE carries the limbs back into [0, 2^32) (the top one signed) without changing the value. Word 66 of
+// a row is the flag word (NaN / +Inf / −Inf seen); a row is padded to 72 words = 576 bytes, a multiple of the 64-byte line.
+#define FDB_EXACT_LIMBS 66
+#define FDB_EXACT_FLAGS 66            // word of the flag bits in a row
+#define FDB_EXACT_WORDS 72            // row stride in 64-bit words
+#define FDB_EXACT_F_NAN 1ull
+#define FDB_EXACT_F_PINF 2ull
+#define FDB_EXACT_F_NINF 4ull
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+#define FDB_HD __host__ __device__
+#else
+#define FDB_HD
+#endif
+// Splits the float64 `bits` into (first limb, three signed digits). Returns 0 for a finite value (±0 gives three zero digits), else
+// its flag bit.
+FDB_HD inline unsigned long long fdb_exact_split(unsigned long long bits, int* limb, long long* d0, long long* d1, long long* d2) {
+  const unsigned exp = (unsigned)(bits >> 52) & 0x7FFu;
+  const unsigned long long frac = bits & 0xFFFFFFFFFFFFFull;
+  const bool neg = (bits >> 63) != 0ull;
+  *limb = 0; *d0 = 0; *d1 = 0; *d2 = 0;
+  if (exp == 0x7FFu) return frac != 0ull ? FDB_EXACT_F_NAN : neg ? FDB_EXACT_F_NINF : FDB_EXACT_F_PINF;
+  const unsigned long long m = exp == 0u ? frac : (frac | (1ull << 52));
+  const unsigned p = exp == 0u ? 0u : exp - 1u;  // e + 1074 (a subnormal has e = −1074)
+  const unsigned s = p & 31u;
+  const unsigned long long lo = m << s, hi = s == 0u ? 0ull : m >> (64u - s);
+  const long long sg = neg ? -1 : 1;
+  *limb = (int)(p >> 5);
+  *d0 = sg * (long long)(lo & 0xFFFFFFFFull);
+  *d1 = sg * (long long)(lo >> 32);
+  *d2 = sg * (long long)hi;
+  return 0ull;
+}
+// Carries limbs [0, FDB_EXACT_LIMBS) into [0, 2^32), the top limb signed. The value is unchanged.
+FDB_HD inline void fdb_exact_normalize(long long* l) {
+  long long c = 0;
+  for (int j = 0; j < FDB_EXACT_LIMBS - 1; j++) {
+    const long long v = l[j] + c;
+    l[j] = v & 0xFFFFFFFFll;
+    c = v >> 32;  // (arithmetic shift: floor division by 2^32)
+  }
+  l[FDB_EXACT_LIMBS - 1] += c;
+}
+// The exact sum of a row of limbs + flags, rounded once to nearest, ties to even (normalizes `l` in place). Zero is +0.0.
+FDB_HD inline unsigned long long fdb_exact_round(long long* l, unsigned long long flags) {
+  if ((flags & FDB_EXACT_F_NAN) != 0ull || (flags & (FDB_EXACT_F_PINF | FDB_EXACT_F_NINF)) == (FDB_EXACT_F_PINF | FDB_EXACT_F_NINF)) return 0x7FF8000000000000ull;
+  if (flags & FDB_EXACT_F_PINF) return 0x7FF0000000000000ull;
+  if (flags & FDB_EXACT_F_NINF) return 0xFFF0000000000000ull;
+  fdb_exact_normalize(l);
+  const bool neg = l[FDB_EXACT_LIMBS - 1] < 0;
+  // magnitude as 32-bit digits D[0 … 66]: negate across the limbs if needed, then split the top limb (< 2^63) in two
+  unsigned long long borrow = 0, top = 0;
+  unsigned long long hi_digit[2] = {0, 0};
+  // (streamed from the top: the first three nonzero digits make a 96-bit window, everything below it is the sticky bit)
+  unsigned long long win_hi = 0, win_lo = 0;  // window = win_hi · 2^64 + win_lo, < 2^96
+  int n_win = 0, low_digit = 0;
+  bool sticky = false;
+  if (neg) {  // two's complement over the digits: magnitude = −value
+    for (int j = 0; j < FDB_EXACT_LIMBS - 1; j++) {
+      const long long t = -l[j] - (long long)borrow;
+      l[j] = t & 0xFFFFFFFFll;
+      borrow = t < 0 ? 1ull : 0ull;
+    }
+    top = (unsigned long long)(-l[FDB_EXACT_LIMBS - 1] - (long long)borrow);
+  } else {
+    top = (unsigned long long)l[FDB_EXACT_LIMBS - 1];
+  }
+  hi_digit[0] = top & 0xFFFFFFFFull; hi_digit[1] = top >> 32;
+  for (int j = FDB_EXACT_LIMBS; j >= 0; j--) {  // digits 0 … 66: limbs 0 … 64, then the top limb's two halves
+    const unsigned long long d = j >= FDB_EXACT_LIMBS - 1 ? hi_digit[j - (FDB_EXACT_LIMBS - 1)] : (unsigned long long)l[j];
+    if (n_win == 0 && d == 0ull) continue;
+    if (n_win < 3) {
+      win_hi = (win_hi << 32) | (win_lo >> 32);
+      win_lo = (win_lo << 32) | d;
+      n_win++;
+      low_digit = j;
+    } else if (d != 0ull) {
+      sticky = true;
+    }
+  }
+  if (n_win == 0) return 0ull;
+  while (n_win < 3) { win_hi = (win_hi << 32) | (win_lo >> 32); win_lo <<= 32; n_win++; low_digit--; }  // (low_digit may go negative: zeros below limb 0)
+  // msb of the window (bit 95 … 64 is in win_hi, which holds the first nonzero digit)
+  const int lz = __builtin_clzll(win_hi) - 32;              // leading zeros within the 96-bit window
+  const unsigned long long sig = lz == 0 ? ((win_hi << 32) | (win_lo >> 32)) : ((win_hi << (32 + lz)) | (win_lo >> (32 - lz)));  // top 64 bits, msb set
+  if ((win_lo << (32 + lz)) != 0ull) sticky = true;          // window bits below those 64
+  const long long e_msb = 32ll * low_digit + 95 - lz - 1074;  // binary exponent of the msb
+  int shift = 11;                                             // bits of `sig` below a double's 53
+  if (e_msb < -1022) shift = (int)(-1011 - e_msb);            // subnormal result: its lsb is 2^-1074 (e_msb ≥ −1074 ⇒ shift ≤ 63)
+  unsigned long long q = sig >> shift;
+  const unsigned long long rem = sig & ((1ull << shift) - 1ull), half = 1ull << (shift - 1);
+  if (rem > half || (rem == half && (sticky || (q & 1ull)))) q++;
+  unsigned long long out;
+  if (e_msb < -1022) out = q;  // (a subnormal that rounds up to 2^52 is the smallest normal: the bits say so)
+  else {
+    if (e_msb > 1023) return neg ? 0xFFF0000000000000ull : 0x7FF0000000000000ull;
+    out = ((unsigned long long)(e_msb + 1022) << 52) + q;  // q carries the hidden bit (a carry to 2^53 bumps the exponent)
+    if (out >= 0x7FF0000000000000ull) out = 0x7FF0000000000000ull;
+  }
+  return out | (neg ? 0x8000000000000000ull : 0ull);
+}
+
 // ---- device helpers of the hash path (shared by fdb_kernels.hip and the kernels fdb_jit.cpp generates) ---------------
 #ifdef FDB_DEVICE_HELPERS  // defined by translation units that hold device code
 __device__ __forceinline__ unsigned long long fmix64(unsigned long long k) {
@@ -279,6 +385,48 @@ __device__ __forceinline__ uint64_t hash_find_or_insert(unsigned long long* tabl
   }
 }
 
+// Exact SUM: adds the float64 `bits` of every `active` lane into limb row `slot` of `rows` (FDB_EXACT_WORDS words per slot) with
+// no-return 64-bit integer atomics. The WHOLE wave calls it, converged (the cross-lane sums read every lane). Lanes whose (slot, first
+// limb) agree add their digits in registers first — integer adds, so this is exact too — and the group's leader issues ONE set of
+// atomics: a query with tens of groups would otherwise serialise a wave's 64 rows on a few addresses (guideline 12). The combining
+// stops at the first lane that shares its (slot, limb) with nobody: the wave's rows then are mostly distinct groups (cfg 5) and the
+// lanes still pending add their own digits.
+__device__ __forceinline__ void fdb_exact_add_wave(unsigned long long* rows, uint64_t slot, unsigned long long bits, bool active) {
+  int k; long long d0, d1, d2;
+  const unsigned long long fl = fdb_exact_split(bits, &k, &d0, &d1, &d2);
+  unsigned long long* row = rows + slot * (uint64_t)FDB_EXACT_WORDS;
+  if (active && fl != 0ull) atomicOr(row + FDB_EXACT_FLAGS, fl);
+  bool mine = active && fl == 0ull && (d0 | d1 | d2) != 0;
+  unsigned long long pending = __ballot(mine);
+  while (pending != 0ull) {
+    const int leader = __ffsll((long long)pending) - 1;
+    const unsigned long long ls = __shfl((unsigned long long)slot, leader, 64);
+    const int lk = __shfl(k, leader, 64);
+    const bool in = mine && (unsigned long long)slot == ls && k == lk;
+    const unsigned long long grp = __ballot(in);
+    if (grp == (1ull << leader)) break;  // a singleton: stop combining (the leader is still `mine` and adds below)
+    long long s0 = in ? d0 : 0, s1 = in ? d1 : 0, s2 = in ? d2 : 0;
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) {
+      s0 += __shfl_xor(s0, sh, 64); s1 += __shfl_xor(s1, sh, 64); s2 += __shfl_xor(s2, sh, 64);
+    }
+    if ((int)(threadIdx.x & 63u) == leader) {
+      unsigned long long* r = row + k;
+      if (s0 != 0) atomicAdd(r, (unsigned long long)s0);
+      if (s1 != 0) atomicAdd(r + 1, (unsigned long long)s1);
+      if (s2 != 0) atomicAdd(r + 2, (unsigned long long)s2);
+    }
+    mine = mine && !in;
+    pending &= ~grp;
+  }
+  if (mine) {
+    unsigned long long* r = row + k;
+    if (d0 != 0) atomicAdd(r, (unsigned long long)d0);
+    if (d1 != 0) atomicAdd(r + 1, (unsigned long long)d1);
+    if (d2 != 0) atomicAdd(r + 2, (unsigned long long)d2);
+  }
+}
+
 #endif  // FDB_DEVICE_HELPERS
 
 #define FDB_HASH_BLOCK 256
@@ -291,9 +439,16 @@ hipError_t fdb_launch_hash_init(unsigned long long* table, uint64_t capacity, in
 // each key tuple (valid mask + columns, without the tail padding of its stride `old_key_words`) are copied word for word into the
 // (possibly wider) new key store, the other words zeroed. The key store itself needs NO initialisation: a
 // tuple is only ever read where the entry is occupied, and every insert writes all of its words.
+// Exact SUMs: `n_exact` limb arrays (old_limbs / new_limbs: [n_exact][capacity][FDB_EXACT_WORDS], the new ones zeroed) move with the entries.
 hipError_t fdb_launch_hash_rehash(const unsigned long long* old_table, const uint32_t* old_keys, uint64_t old_capacity, int old_key_words, int old_used_words,
                                   unsigned long long* new_table, uint32_t* new_keys, uint64_t new_mask, int entry_words, int new_key_words,
-                                  hipStream_t stream);
+                                  hipStream_t stream, const unsigned long long* old_limbs = nullptr, unsigned long long* new_limbs = nullptr, int n_exact = 0);
+// Exact SUMs of a hash table (limbs: [n_exact][capacity][FDB_EXACT_WORDS]): normalize carries every occupied slot's limbs back into
+// [0, 2^32) (value unchanged); finalize writes each occupied slot's correctly rounded sum into entry word acc_word.w[q].
+struct FdbExactWords { int32_t w[FDB_MAX_AGGS]; };
+hipError_t fdb_launch_exact_normalize(unsigned long long* limbs, const unsigned long long* table, uint64_t capacity, int entry_words, int n_exact, hipStream_t stream);
+hipError_t fdb_launch_exact_finalize(const unsigned long long* limbs, unsigned long long* table, uint64_t capacity, int entry_words, int n_exact,
+                                     const FdbExactWords& acc_word, hipStream_t stream);
 // First output row of every 64-slot chunk of the table (bases[(capacity + 63) / 64], exclusive prefix sums of the occupied
 // entries per chunk) and *n_out = occupied entries: what makes the two compactions below deterministic — SLOT ORDER, no atomics.
 hipError_t fdb_launch_hash_chunk_bases(const unsigned long long* table, uint64_t capacity, int entry_words, uint32_t* bases, uint32_t* block_sums,
@@ -366,6 +521,9 @@ struct FdbHashMergeArgs {
   int32_t same_layout;    // every destination column sits at the same word of the incoming tuple, none is absent: translated in place
   int32_t unique_source;  // every incoming group occurs once (a table, rows exported from ONE table): a new slot takes plain stores
   int32_t funcs[FDB_MAX_AGGS];
+  // exact SUMs (table source only): the source's limb rows [n_exact][src_capacity][FDB_EXACT_WORDS] are added into ours
+  // [n_exact][mask + 1][FDB_EXACT_WORDS]; their funcs[j] are 0 (the accumulator word is not touched)
+  const unsigned long long* exact_src; unsigned long long* exact_dst; int32_t n_exact;
 };
 hipError_t fdb_launch_hash_merge(const FdbHashMergeArgs& args, int device, hipStream_t stream);
 

@@ -773,6 +773,11 @@ __global__ __launch_bounds__(FDB_HASH_BLOCK) void scan_hash_kernel(const FdbHash
   const int64_t n_tiles = (h.row_end - h.row_begin + FDB_HASH_BLOCK - 1) / FDB_HASH_BLOCK;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t row = h.row_begin + tile * FDB_HASH_BLOCK + tid;
+    // (the row's work sits in a do { } while (0): a `continue` leaves it, and every lane of the wave meets again at the exact sums
+    // below, whose cross-lane combining needs them all)
+    uint64_t x_slot = 0;
+    bool x_sel = false;
+    do {
     if (row >= h.row_end) continue;
     if (a.n_code != 0 && (eval_filter<R>(a, row, smem) & 1u) == 0u) continue;
 
@@ -832,9 +837,11 @@ __global__ __launch_bounds__(FDB_HASH_BLOCK) void scan_hash_kernel(const FdbHash
     }
     unsigned long long* e = h.table + slot * (uint64_t)ew;
     atomicAdd(e + 2, 1ull);
+    x_slot = slot; x_sel = true;
     for (int j = 0; j < a.n_aggs; j++) {
       const FdbAgg& A = a.aggs[j];
       if (A.func == AGG_COUNT) continue;
+      if (A.acc != nullptr) continue;  // exact SUM (A.acc = its limb rows): below
       const bool valid = A.validity == nullptr || load_valid<R>(A.validity, row) != 0u;
       unsigned long long raw[R];
       load_u64<R>(reinterpret_cast<const unsigned long long*>(A.values) + row, raw);
@@ -848,6 +855,20 @@ __global__ __launch_bounds__(FDB_HASH_BLOCK) void scan_hash_kernel(const FdbHash
         if (A.func == AGG_MIN) atomicMin(reinterpret_cast<long long*>(acc), key);
         else atomicMax(reinterpret_cast<long long*>(acc), key);
       }
+    }
+    } while (0);
+    // exact SUMs (fdb_plan_set_exact_sums): the value goes into the slot's limb row, the whole wave together
+    for (int j = 0; j < a.n_aggs; j++) {
+      const FdbAgg& A = a.aggs[j];
+      if (A.acc == nullptr || A.func != AGG_SUM) continue;
+      unsigned long long x = 0;
+      if (x_sel) {
+        const bool valid = A.validity == nullptr || load_valid<R>(A.validity, row) != 0u;
+        unsigned long long raw[R];
+        load_u64<R>(reinterpret_cast<const unsigned long long*>(A.values) + row, raw);
+        x = valid ? raw[0] : A.null_value;
+      }
+      fdb_exact_add_wave(A.acc, x_slot, x, x_sel);
     }
   }
   __syncthreads();
@@ -863,7 +884,8 @@ __global__ void hash_init_kernel(unsigned long long* table, uint64_t total_words
 }
 
 __global__ void hash_rehash_kernel(const unsigned long long* old_table, const uint32_t* old_keys, uint64_t old_capacity, int okw, int oused,
-                                   unsigned long long* new_table, uint32_t* new_keys, uint64_t new_mask, int ew, int kw) {
+                                   unsigned long long* new_table, uint32_t* new_keys, uint64_t new_mask, int ew, int kw,
+                                   const unsigned long long* old_limbs, unsigned long long* new_limbs, int n_exact) {
   // A lane claims the new slot of "its" old entry (CAS on the fingerprint, linear probing) and copies the entry's words; the KEY
   // TUPLES — tens of words each — are then copied by the whole wave, one tuple at a time with lane w on word w: coalesced reads and
   // writes instead of every lane walking its own 136 bytes (3.4 M entries of cfg 5: 2.9 ms → a fraction of that).
@@ -893,7 +915,46 @@ __global__ void hash_rehash_kernel(const unsigned long long* old_table, const ui
       const uint64_t src = wave_first + (uint64_t)src_lane;
       const uint64_t dst = (uint64_t)__shfl((unsigned long long)slot, src_lane, 64);
       for (int w = lane; w < kw; w += 64) new_keys[dst * (uint64_t)kw + w] = w < oused ? old_keys[src * (uint64_t)okw + w] : 0u;  // columns added since: NULL (the old tuple's tail padding is not a column)
+      // exact SUMs: the entry's limb rows move with it (the new rows are zeroed by the caller)
+      for (int q = 0; q < n_exact; q++) {
+        const unsigned long long* os = old_limbs + ((uint64_t)q * old_capacity + src) * FDB_EXACT_WORDS;
+        unsigned long long* ns = new_limbs + ((uint64_t)q * (new_mask + 1) + dst) * FDB_EXACT_WORDS;
+        for (int w = lane; w <= FDB_EXACT_FLAGS; w += 64) ns[w] = os[w];
+      }
     }
+  }
+}
+
+// ---- exact SUMs: normalize and round the limb rows of the occupied slots ------------------------------------------------------------
+// One thread per (slot, exact aggregation); the row's 66 limbs live in registers (every loop over them is unrolled).
+__global__ __launch_bounds__(256) void exact_normalize_kernel(unsigned long long* limbs, const unsigned long long* table, uint64_t capacity, int ew, int n_exact) {
+  const uint64_t total = capacity * (uint64_t)n_exact;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t slot = i % capacity;
+    if (table[slot * (uint64_t)ew] == 0ull) continue;
+    long long* r = reinterpret_cast<long long*>(limbs + i * FDB_EXACT_WORDS);
+    long long l[FDB_EXACT_LIMBS];
+#pragma unroll
+    for (int j = 0; j < FDB_EXACT_LIMBS; j++) l[j] = r[j];
+    fdb_exact_normalize(l);
+#pragma unroll
+    for (int j = 0; j < FDB_EXACT_LIMBS; j++) r[j] = l[j];
+  }
+}
+// Writes each occupied slot's correctly rounded sum into its accumulator word (entry word acc_word[q]): what Finish, the compaction and
+// the merges of a plan's read-out then take as an ordinary float64 SUM.
+__global__ __launch_bounds__(256) void exact_finalize_kernel(const unsigned long long* limbs, unsigned long long* table, uint64_t capacity, int ew, int n_exact,
+                                                             FdbExactWords acc_word) {
+  const uint64_t total = capacity * (uint64_t)n_exact;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t slot = i % capacity;
+    const int q = (int)(i / capacity);
+    if (acc_word.w[q] < 0 || table[slot * (uint64_t)ew] == 0ull) continue;  // (w < 0: an integer SUM's unused array)
+    const long long* r = reinterpret_cast<const long long*>(limbs + i * FDB_EXACT_WORDS);
+    long long l[FDB_EXACT_LIMBS];
+#pragma unroll
+    for (int j = 0; j < FDB_EXACT_LIMBS; j++) l[j] = r[j];
+    table[slot * (uint64_t)ew + acc_word.w[q]] = fdb_exact_round(l, (unsigned long long)r[FDB_EXACT_FLAGS]);
   }
 }
 
@@ -2513,9 +2574,22 @@ hipError_t fdb_launch_hash_init(unsigned long long* table, uint64_t capacity, in
 
 hipError_t fdb_launch_hash_rehash(const unsigned long long* old_table, const uint32_t* old_keys, uint64_t old_capacity, int old_key_words, int old_used_words,
                                   unsigned long long* new_table, uint32_t* new_keys, uint64_t new_mask, int entry_words, int new_key_words,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, const unsigned long long* old_limbs, unsigned long long* new_limbs, int n_exact) {
   hipLaunchKernelGGL(hash_rehash_kernel, dim3(4096), dim3(256), 0, stream, old_table, old_keys, old_capacity, old_key_words, old_used_words, new_table, new_keys,
-                     new_mask, entry_words, new_key_words);
+                     new_mask, entry_words, new_key_words, old_limbs, new_limbs, n_exact);
+  return hipGetLastError();
+}
+
+hipError_t fdb_launch_exact_normalize(unsigned long long* limbs, const unsigned long long* table, uint64_t capacity, int entry_words, int n_exact, hipStream_t stream) {
+  if (capacity == 0 || n_exact == 0) return hipSuccess;
+  hipLaunchKernelGGL(exact_normalize_kernel, dim3(4096), dim3(256), 0, stream, limbs, table, capacity, entry_words, n_exact);
+  return hipGetLastError();
+}
+
+hipError_t fdb_launch_exact_finalize(const unsigned long long* limbs, unsigned long long* table, uint64_t capacity, int entry_words, int n_exact,
+                                     const FdbExactWords& acc_word, hipStream_t stream) {
+  if (capacity == 0 || n_exact == 0) return hipSuccess;
+  hipLaunchKernelGGL(exact_finalize_kernel, dim3(4096), dim3(256), 0, stream, limbs, table, capacity, entry_words, n_exact, acc_word);
   return hipGetLastError();
 }
 

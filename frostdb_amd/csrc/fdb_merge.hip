@@ -224,6 +224,24 @@ __global__ __launch_bounds__(256) void hash_merge_wave_kernel(const FdbHashMerge
         }
       }
     }
+    // exact SUMs: the source's limb rows are added into the destination slot's, one tuple at a time, lane w on limb w (the limbs a
+    // sum does not reach are zero and cost no atomic)
+    if (TABLE_SRC && m.n_exact != 0) {
+      const unsigned long long my_src = active ? T.queue[lane] : 0ull;
+      for (int t = 0; t < n_act; t++) {
+        const uint64_t ss = __shfl(my_src, t, 64), ds = __shfl((unsigned long long)slot, t, 64);
+        for (int q = 0; q < m.n_exact; q++) {
+          const unsigned long long* sr = m.exact_src + ((uint64_t)q * m.src_capacity + ss) * FDB_EXACT_WORDS;
+          unsigned long long* dr = m.exact_dst + ((uint64_t)q * (m.mask + 1) + ds) * FDB_EXACT_WORDS;
+          for (int w = lane; w <= FDB_EXACT_FLAGS; w += 64) {
+            const unsigned long long v = as_global(sr)[w];
+            if (v == 0ull) continue;
+            if (w == FDB_EXACT_FLAGS) atomicOr(dr + w, v);
+            else atomicAdd(dr + w, v);
+          }
+        }
+      }
+    }
     wave_sync();
   };
 

@@ -470,6 +470,7 @@ Plan::~Plan() {
   ctx_->dev_free(d_state_);
   ctx_->dev_free(h_table_);
   ctx_->dev_free(h_keys_);
+  ctx_->dev_free(d_limbs_);
   ctx_->dev_free(h_count_dev_);
   for (RunSegment& r : runs_) ctx_->dev_free(r.block);
   for (RecordSlab& sl : inflight_slabs_) { ctx_->dev_free(sl.d); ctx_->host_free(sl.h); }
@@ -704,7 +705,7 @@ const char* Plan::draw() {
       for (size_t i = 0; i < matchers_.size(); i++) s += (i ? "," : "") + matchers_[i].name;
       s += ")";
     }
-    draw_ = s + " [gfx950]";
+    draw_ = s + (exact_ ? " [gfx950, exact float64 sums]" : " [gfx950]");
   }
   return draw_.c_str();
 }
@@ -1100,11 +1101,15 @@ Plan::Knobs::Knobs() {
   max_key_bytes = mk != nullptr ? std::max<long long>(1, std::atoll(mk)) : 0x7FFFFFFFll;
   const char* fs = std::getenv("FDB_FINISH_SLICE_SHIFT");
   finish_slice_shift = fs != nullptr ? std::max(6, std::min(20, std::atoi(fs))) : 20;
+  // (a limb holds < 2^32 after a normalize and takes one digit < 2^32 per add: 2^31 − 1 adds keep it below 2^63)
+  const char* en = std::getenv("FDB_TEST_EXACT_NORMALIZE_ROWS");
+  exact_normalize_rows = en != nullptr ? std::max<long long>(1024, std::min<long long>(std::atoll(en), (1ll << 31) - (1ll << 24))) : (1ll << 31) - (1ll << 24);
 }
 
 void Plan::push(const ArrowArray* array, const ArrowSchema* schema) {
   if (finished_) throw Error(FDB_ERR_STATE, "push after finish");
   if (aggs_.empty() && matchers_.empty()) throw Error(FDB_ERR_STATE, "filter-only plan: use fdb_plan_filter / fdb_plan_select");
+  started_ = true;
   // ($FDB_PROFILE_PUSH: tuning aid — where a small record's Callback goes, summed per plan and printed by the destructor)
   static const bool prof = std::getenv("FDB_PROFILE_PUSH") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1396,6 +1401,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
   if (aggs_.empty() && matchers_.empty()) throw Error(FDB_ERR_STATE, "filter-only plan: use fdb_plan_filter / fdb_plan_select");
   for (int i = 0; i < n; i++)
     if (bs[i]->device != device_) throw Error(FDB_ERR_INVALID, "batch lives on a different device than the plan");
+  started_ = true;
   hip_check(hipSetDevice(device_), "hipSetDevice");
   for (int i = 0; i < n; i++) bs[i]->note_reader(stream_);
   mirror_valid_ = false;
@@ -1411,7 +1417,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
 
   // reproducible float sums (fdb_plan_set_deterministic) exist on the dense path of the specialised kernel only
   bool fixed_order = false;
-  if (deterministic) for (const AggState& A : aggs_) if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) fixed_order = true;
+  if (deterministic && !exact_) for (const AggState& A : aggs_) if (A.func == FDB_AGG_SUM && A.type == FDB_T_F64) fixed_order = true;  // (exact sums win)
   // OrderedAggregate without a table: nothing accumulated yet (or already collecting runs) and the records fit the run kernel
   // (not under fixed_order: groups that a wave or record boundary cuts into several runs are folded with atomics at Finish — such a
   // scan goes on to the dense kernel, or to the explicit refusal below)
@@ -2170,6 +2176,8 @@ void Plan::merge_from(Plan& src) {
   if (&src == this) throw Error(FDB_ERR_INVALID, "cannot merge a plan into itself");
   if (src.device_ != device_) throw Error(FDB_ERR_INVALID, "merge across devices goes through frostdb_amd.distributed (RCCL)");
   if (src.aggs_.size() != aggs_.size()) throw Error(FDB_ERR_INVALID, "plans have different aggregations");
+  if (src.exact_ != exact_) throw Error(FDB_ERR_INVALID, "an exact-sum plan merges only with exact-sum plans");
+  started_ = src.started_ = true;
   for (size_t j = 0; j < aggs_.size(); j++) {
     if (src.aggs_[j].func != aggs_[j].func || src.aggs_[j].column != aggs_[j].column) throw Error(FDB_ERR_INVALID, "plans have different aggregations");
     if (aggs_[j].type == FDB_T_NONE) aggs_[j].type = src.aggs_[j].type;

@@ -286,11 +286,29 @@ class Plan {
   const char* last_kernel() const { return last_kernel_; }
   bool deterministic = false;  // fdb_plan_set_deterministic: wave-private LDS tables, fixed-order folds; scans that cannot have them are refused
   bool use_partials = true;  // LDS mode: flush workgroup tables with plain stores + a fold kernel instead of atomics
+  // fdb_plan_set_exact_sums: every float64 SUM is the correctly rounded exact sum (limb rows beside the hash table, fdb_kernels.h
+  // "exact float64 sums"). Only before the plan's first push / merge / seed; the plan lives in the hash table from then on.
+  void set_exact_sums(bool on);
+  bool exact_sums() const { return exact_; }
+  bool started() const { return started_; }
+  void refuse_exact(const char* what) const;  // FDB_ERR_UNSUPPORTED for an exact plan: `what` hands out or moves raw accumulator state
   struct Resolved;  // per-batch kernel arguments (fdb_plan.cpp)
   void sync();      // waits for the plan's stream; timing events are read, scratch and consumed records go back to their caches
 
  private:
   const char* last_kernel_ = "";  // name of the scan kernel of the latest push
+  bool started_ = false;          // a push, merge or seed happened (fdb_plan_set_exact_sums is refused from then on)
+  bool exact_ = false;
+  // exact SUMs: one limb array per SUM aggregation ([n_exact_][h_capacity_][FDB_EXACT_WORDS]; an integer SUM's stays unused), zeroed
+  // with the table and moved by its rehashes; exact_q(j) = the array of aggregation j, -1 = none
+  unsigned long long* d_limbs_ = nullptr;
+  int n_exact_ = 0;
+  int exact_q(size_t j) const;
+  bool exact_f64(size_t j) const;   // aggregation j is a float64 SUM of an exact plan
+  uint64_t exact_adds_ = 0;         // upper bound of the adds any limb took since the last normalize
+  void exact_finalize();            // rounded sums into the entries' accumulator words (before every read-out)
+  void exact_normalize_now();
+  unsigned long long* exact_limbs_alloc(uint64_t capacity);  // zeroed limb arrays for a table of `capacity` slots (nullptr: no exact SUM)
   bool references(const std::string& column) const;
   TruthCache truth_cache_;
   std::vector<Projection> projs_;
@@ -360,6 +378,7 @@ class Plan {
     long long present_ids_min_bytes;  // index bytes a Finish must stand to save before it ranks the ids present ($FDB_PRESENT_IDS_MIN_BYTES), 32 MiB
     long long max_key_bytes;    // bytes one plain string / binary key column of ONE output record may hold ($FDB_TEST_MAX_KEY_BYTES; math.MaxInt32 like optbuilders.go:221-224)
     int finish_slice_shift;     // log2 of the rows per Finish slice ($FDB_FINISH_SLICE_SHIFT: tests reach several slices with a small result), 20
+    long long exact_normalize_rows;  // adds a limb may take between two normalizes ($FDB_TEST_EXACT_NORMALIZE_ROWS: tests reach the normalize with few rows), 2^31 − 2^24
     Knobs();
   } knobs_;
   int64_t fresh_groups_ = -1;   // hash_groups() as just fetched by ordered_finish_on_device(), for the finish_columns_hash that follows at once

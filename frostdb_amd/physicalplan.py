@@ -91,6 +91,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_plan_stream.argtypes = [vp, P(vp)]
     L.fdb_plan_set_tuning.argtypes = [vp, i32, i32]
     L.fdb_plan_set_deterministic.argtypes = [vp, i32]
+    L.fdb_plan_set_exact_sums.argtypes = [vp, i32]
+    L.fdb_selftest_exact_sum.argtypes = [vp, i64, vp]
     L.fdb_snappy_decode_pages.argtypes = [vp, i64, vp, i32, vp, i64, ctypes.c_int, vp, P(ctypes.c_double)]
     L.fdb_plan_state_arrays.argtypes = [vp, P(i32)]
     L.fdb_plan_state_array_op.argtypes = [vp, i32, P(i32)]
@@ -188,6 +190,18 @@ def arrow_roundtrip(record: pa.RecordBatch) -> pa.RecordBatch:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
     return import_batch(arr, sch)
+
+
+def selftest_exact_sum(values) -> float:
+    """The correctly rounded exact sum of `values` (float64), computed on the host by the code the exact-sum kernels run
+    (fdb_selftest_exact_sum; no device)."""
+    xs = [float(v) for v in values]
+    x = (ctypes.c_double * max(1, len(xs)))(*xs)
+    out = ctypes.c_double()
+    rc = lib().fdb_selftest_exact_sum(x, len(xs), ctypes.byref(out))
+    if rc != FDB_OK:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    return out.value
 
 
 def live_allocations() -> dict:
@@ -640,6 +654,11 @@ class HashAggregatePlan:
     def set_deterministic(self, enabled: bool = True) -> None:
         """Reproducible float64 sums (fdb_plan_set_deterministic): the same pushes give the same bits on every run."""
         self._check(lib().fdb_plan_set_deterministic(self.handle, 1 if enabled else 0))
+
+    def set_exact_sums(self, enabled: bool = True) -> None:
+        """Exact float64 sums (fdb_plan_set_exact_sums): every float64 SUM is the correctly rounded exact sum of the group's values,
+        whatever the row order, record split or merge order. Only before the first push / merge; FdbError(FDB_ERR_STATE) after."""
+        self._check(lib().fdb_plan_set_exact_sums(self.handle, 1 if enabled else 0))
 
     def last_kernel(self) -> str:
         """Name of the scan kernel the latest push launched (``fdb_plan_kernel`` = run-time specialised)."""

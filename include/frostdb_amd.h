@@ -516,6 +516,22 @@ FDB_API int fdb_plan_set_tuning(fdb_plan* plan, int32_t rows_per_thread, int32_t
  * of big dense tables and the exchange of hash tables are not covered. An ordered plan (fdb_plan_desc.ordered) with this flag does
  * not collect runs (their Finish folds cut groups with atomics): it keeps the dense kernel. */
 FDB_API int fdb_plan_set_deterministic(fdb_plan* plan, int32_t enabled);
+/* Exact float64 sums. With `enabled`, every SUM over a float64 input — AVG (lowered to SUM + COUNT), computed inputs such as
+ * sum(value * 2.5), final-stage plans and the member plans of a dynamic aggregation included — returns the EXACT sum of the group's
+ * values, rounded once to nearest, ties to even: the same bits under any permutation of the rows, any split into records, any mix of
+ * push / push_many / push_batch(es) / queued small records and any order of fdb_plan_merge calls, and the bits of
+ * float(sum(Fraction(v) for v in values)). A zero sum is +0.0, NULL rows contribute 0; NaN, or both +Inf and −Inf, give NaN, one
+ * infinity gives that infinity, a finite sum beyond the double range rounds to ±Inf. Each such SUM keeps 66 64-bit integer limbs per
+ * group beside the hash table (576 bytes with its flag word and padding); the plan always scans into the hash table. COUNT, MIN, MAX,
+ * UNIQUE, AND and integer SUMs are unchanged, as are the output schema and column names. Valid only before the plan's first push,
+ * merge or seed (FDB_ERR_STATE afterwards). It wins over fdb_plan_set_deterministic: nothing is refused for its shape. Merging an
+ * exact plan with a non-exact one is FDB_ERR_INVALID. Entry points that hand out or move raw accumulator state — fdb_plan_state_*,
+ * fdb_plan_hash_export / _import, fdb_plan_group_schema / _seed_groups, fdb_plan_allreduce, fdb_plan_exchange — answer
+ * FDB_ERR_UNSUPPORTED for an exact plan; fdb_plan_partial_keys / _partial_state hand out the rounded sums. */
+FDB_API int fdb_plan_set_exact_sums(fdb_plan* plan, int32_t enabled);
+/* Host-only self-check of the exact summation (no device): out[0] = the correctly rounded exact sum of x[0 … n), computed by the same
+ * digit split, normalize and rounding code the device kernels run. */
+FDB_API int fdb_selftest_exact_sum(const double* x, int64_t n, double* out);
 /* Name of the scan kernel the latest push launched ("fdb_plan_kernel" = the run-time specialised kernel,
  * "scan_slots_kernel" / "scan_dense_kernel" = the interpreting kernels, "scan_hash_kernel" = the hash-table path);
  * "" before the first push. The string is static. */

@@ -72,6 +72,7 @@ type factoryConfig struct {
 	device         int
 	accountResults bool
 	deterministic  bool
+	exactSums      bool
 }
 
 // AccountResults makes every emitted record a copy built from the engine's memory.Allocator (FusedStage.Pool), so that
@@ -81,6 +82,10 @@ func AccountResults() FactoryOption { return func(c *factoryConfig) { c.accountR
 
 // Deterministic asks every operator for float64 sums that are bit-identical from run to run (fdb_plan_set_deterministic).
 func Deterministic() FactoryOption { return func(c *factoryConfig) { c.deterministic = true } }
+
+// ExactSums asks every operator for float64 sums that are the correctly rounded exact sum of each group's values: the same bits
+// whatever the row order, record split or merge order (fdb_plan_set_exact_sums).
+func ExactSums() FactoryOption { return func(c *factoryConfig) { c.exactSums = true } }
 
 // Factory is what the user hands to physicalplan.WithOperatorFactory: Build calls the returned func once per chain for every
 // [Filter] [Projection] Aggregation|Distinct stage. A stage this library does not cover is declined with ErrOperatorNotFused and Build
@@ -113,6 +118,11 @@ func Factory(device int, opts ...FactoryOption) physicalplan.OperatorFactory {
 		}
 		if cfg.deterministic {
 			op.SetDeterministic(true)
+		}
+		if cfg.exactSums {
+			if err := op.SetExactSums(true); err != nil {
+				return nil, fmt.Errorf("gpuplan: %v: %w", err, physicalplan.ErrOperatorNotFused)
+			}
 		}
 		return op, nil
 	}
@@ -382,6 +392,19 @@ func (o *Operator) SetDeterministic(on bool) {
 		v = 1
 	}
 	C.fdb_plan_set_deterministic(o.plan, v)
+}
+
+// SetExactSums asks for float64 sums that are the correctly rounded exact sum of each group's values (fdb_plan_set_exact_sums;
+// before the first Callback, an error afterwards).
+func (o *Operator) SetExactSums(on bool) error {
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	if rc := C.fdb_plan_set_exact_sums(o.plan, v); rc != C.FDB_OK {
+		return errors.New(C.GoString(C.fdb_plan_last_error(o.plan)))
+	}
+	return nil
 }
 
 // Finish ≙ HashAggregate.Finish: emit the partial record(s) downstream, then propagate Finish (aggregate.go:527-541). The library emits
