@@ -290,7 +290,7 @@ int fdb_plan_hash_export(fdb_plan* src, fdb_plan* layout, int32_t n_parts, void*
 
 int fdb_plan_hash_import(fdb_plan* plan, const void* dev_rows, int64_t n_rows) {
   if (!plan || (n_rows > 0 && !dev_rows)) return FDB_ERR_INVALID;
-  return guard(plan, [&] { single_table_only(plan); plan->plan.settle(); plan->plan.hash_import(dev_rows, n_rows); });
+  return guard(plan, [&] { single_table_only(plan); plan->plan.refuse_exact("fdb_plan_hash_import"); plan->plan.settle(); plan->plan.hash_import(dev_rows, n_rows); });
 }
 
 int fdb_plan_filter(fdb_plan* plan, struct ArrowArray* batch, struct ArrowSchema* schema, struct ArrowArray* out,
@@ -612,7 +612,6 @@ int fdb_plan_allreduce(fdb_plan* plan, fdb_comm* comm, int32_t* aligned) {
   return guard(plan, [&] {
     if (comm == nullptr || !comm->c || aligned == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     single_table_only(plan);
-    plan->plan.refuse_exact("fdb_plan_allreduce (exact sums across GPUs are not supported yet)");
     *aligned = plan->plan.comm_allreduce(*comm->c) ? 1 : 0;
   });
 }
@@ -622,7 +621,6 @@ int fdb_plan_exchange(fdb_plan* plan, fdb_comm* comm, fdb_plan** shard) {
   return guard(plan, [&] {
     if (comm == nullptr || !comm->c || shard == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     single_table_only(plan);
-    plan->plan.refuse_exact("fdb_plan_exchange (exact sums across GPUs are not supported yet)");
     *shard = nullptr;
     std::unique_ptr<fdb_plan> s(new fdb_plan(plan->plan));
     plan->plan.comm_exchange(*comm->c, s->plan);

@@ -601,6 +601,7 @@ void Plan::comm_exchange(Comm& comm, Plan& shard) {
     }
     put_u32(&blob, (uint32_t)mine.agg_types.size());
     for (int32_t t : mine.agg_types) put_u32(&blob, (uint32_t)t);
+    put_u32(&blob, exact_ ? 1u : 0u);  // (fdb_plan_set_exact_sums: the packed rows carry limb payloads; every rank must agree)
   } catch (...) { local = std::current_exception(); blob.clear(); }
   const std::vector<std::vector<uint8_t>> all = comm.all_gather_host(blob);
   if (local) std::rethrow_exception(local);
@@ -608,6 +609,7 @@ void Plan::comm_exchange(Comm& comm, Plan& shard) {
     if (b.empty()) throw Error(FDB_ERR_STATE, "exchange abandoned: another rank failed before the collective");
   GroupSchema uni;
   uni.agg_types.assign(aggs_.size(), FDB_T_NONE);
+  bool exact_mismatch = false;
   std::vector<std::unordered_map<std::string, uint32_t>> seen;
   for (const std::vector<uint8_t>& b : all) {
     Reader r{b};
@@ -638,18 +640,27 @@ void Plan::comm_exchange(Comm& comm, Plan& shard) {
       if (uni.agg_types[j] != FDB_T_NONE && uni.agg_types[j] != t) throw Error(FDB_ERR_INVALID, "aggregation types differ between ranks");
       uni.agg_types[j] = t;
     }
+    if ((r.u32() != 0u) != exact_) exact_mismatch = true;
   }
+  // (every rank read the same messages: all of them leave here, before the exchange's device collectives)
+  if (exact_mismatch) throw Error(FDB_ERR_INVALID, "exchange: exact sums (fdb_plan_set_exact_sums) are on for some ranks and off for others");
   // 2. re-key + partition on the device
   void* rows = nullptr;
   int64_t counts[FDB_MAX_PARTS] = {0};
   int32_t rw = 0;
   std::vector<uint8_t> cb((size_t)comm.size * 8 + 4);
   try {
+    if (exact_) shard.set_exact_sums(true);  // (the shard is a fresh clone: its limb arrays come with the table adopt_schema makes)
     shard.adopt_schema(uni);
     for (size_t j = 0; j < aggs_.size(); j++) if (aggs_[j].type == FDB_T_NONE) aggs_[j].type = uni.agg_types[j];
     pt.mark("exchange: schema");
     hash_export(shard, comm.size, &rows, counts, &rw);  // synchronised: the rows are complete
     pt.mark("exchange: export");
+    if (pt.on) {
+      long long n = 0;
+      for (int p = 0; p < comm.size; p++) n += counts[p];
+      std::fprintf(stderr, "[fdb] exchange rows %lld x %d bytes\n", n, rw * 4);
+    }
     std::memcpy(cb.data(), &rw, 4);
     std::memcpy(cb.data() + 4, counts, (size_t)comm.size * 8);
   } catch (...) { local = std::current_exception(); cb.clear(); }  // (a message of the wrong size: every rank refuses it below)

@@ -1054,10 +1054,12 @@ void Plan::hash_export(Plan& layout, int n_parts, void** dev_rows, int64_t* coun
   if (n_parts < 1 || n_parts > FDB_MAX_PARTS) throw Error(FDB_ERR_INVALID, "partition count out of range");
   if (layout.device_ != device_) throw Error(FDB_ERR_INVALID, "layout plan lives on another device");
   if (layout.aggs_.size() != aggs_.size()) throw Error(FDB_ERR_INVALID, "plans have different aggregations");
+  if (layout.exact_ != exact_) throw Error(FDB_ERR_INVALID, "an exact-sum plan exports only into the layout of an exact-sum plan");
   hip_check(hipSetDevice(device_), "hipSetDevice");
   if (mode_ == TableMode::DENSE) switch_to_hash();
   hash_layout();
   hash_reserve(0);
+  exact_normalize_now();  // (exact SUMs: every shipped digit below 2^32, the top limb signed — what the payload format holds)
   if (&layout != this && layout.mode_ == TableMode::DENSE) layout.switch_to_hash();  // (before its column set changes: the dense slot decoding needs the old one)
   // the layout plan adopts our columns / dictionary values (a no-op when it was seeded with the global schema)
   std::vector<FdbHashCol> cols(std::max<size_t>(gcols_.size(), 1));
@@ -1093,13 +1095,17 @@ void Plan::hash_export(Plan& layout, int n_parts, void** dev_rows, int64_t* coun
   const int dkw = layout.h_key_words_;
   const int n_vals = (int)(1 + aggs_.size());
   const int rw = fdb_packed_row_words(dkw, n_vals);
-  *row_words32 = rw;
+  // exact SUMs: the float64 SUMs' limb rows travel behind the values (an integer SUM's word is its exact sum already)
+  int n_ship = 0, ship_arr[FDB_MAX_AGGS] = {0};
+  for (size_t j = 0; j < aggs_.size(); j++) if (exact_f64(j)) ship_arr[n_ship++] = exact_q(j);
+  const int out_rw = fdb_packed_row_words_exact(dkw, n_vals, n_ship);
+  *row_words32 = out_rw;
   const uint64_t n = hash_groups();
   for (int p = 0; p < n_parts; p++) counts[p] = 0;
   *dev_rows = nullptr;
   if (n == 0) return;
   unsigned long long* d_counts = (unsigned long long*)ctx_->dev_alloc(FDB_MAX_PARTS * 8);
-  uint32_t* d_rows = (uint32_t*)ctx_->dev_alloc((size_t)n * rw * 4);
+  uint32_t* d_rows = (uint32_t*)ctx_->dev_alloc((size_t)n * out_rw * 4);
   scratch_.push_back(d_counts); scratch_.push_back(d_rows);
   FdbHashPartArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1108,6 +1114,8 @@ void Plan::hash_export(Plan& layout, int n_parts, void** dev_rows, int64_t* coun
   a.out = d_rows; a.counts = d_counts;
   a.n_cols = (int)gcols_.size(); a.entry_words = h_entry_words_; a.key_words = h_key_words_; a.dst_key_words = dkw; a.row_words32 = rw;
   a.n_vals = n_vals; a.n_parts = n_parts;
+  a.out_words32 = out_rw; a.n_exact_ship = n_ship; a.exact_limbs = d_limbs_;
+  for (int i = 0; i < n_ship; i++) a.exact_arr[i] = ship_arr[i];
   a.in_words = std::min((h_key_used_ + 3) & ~3, h_key_words_);
   bool same = dkw >= a.in_words && layout.gcols_.size() == gcols_.size();  // (a layout column we do not have would keep what our tuple holds at its word)
   for (size_t sc = 0; sc < gcols_.size(); sc++) if (cols[sc].src_word != cols[sc].word) same = false;
@@ -1132,7 +1140,6 @@ void Plan::hash_export(Plan& layout, int n_parts, void** dev_rows, int64_t* coun
 }
 
 void Plan::hash_import(const void* dev_rows, int64_t n_rows, bool unique_rows) {
-  refuse_exact("fdb_plan_hash_import");
   started_ = true;
   runs_to_table();
   if (n_rows <= 0) return;
@@ -1144,7 +1151,9 @@ void Plan::hash_import(const void* dev_rows, int64_t n_rows, bool unique_rows) {
   hash_reserve((uint64_t)n_rows);
   if (pt.on) { hip_check(hipStreamSynchronize(stream_), "sync"); pt.mark("import: reserve"); }
   const int kw = h_key_words_, n_vals = (int)(1 + aggs_.size());
-  const int rw = fdb_packed_row_words(kw, n_vals);
+  int n_ship = 0, ship_arr[FDB_MAX_AGGS] = {0};  // (exact SUMs: the payloads behind the values, as hash_export writes them)
+  for (size_t j = 0; j < aggs_.size(); j++) if (exact_f64(j)) ship_arr[n_ship++] = exact_q(j);
+  const int rw = fdb_packed_row_words_exact(kw, n_vals, n_ship);
   std::vector<FdbHashCol> cols(std::max<size_t>(gcols_.size(), 1));
   for (size_t c = 0; c < gcols_.size(); c++) {
     FdbHashCol& C = cols[c];
@@ -1159,7 +1168,24 @@ void Plan::hash_import(const void* dev_rows, int64_t n_rows, bool unique_rows) {
   m.n = n_rows;
   m.in_key_words = rw; m.in_entry_words = rw / 2;
   m.unique_source = unique_rows ? 1 : 0;  // (rows of several ranks in one call: a group comes once per rank that saw it)
-  hip_check(fdb_launch_hash_merge(m, device_, stream_), "hash merge");
+  if (n_ship == 0) {
+    hip_check(fdb_launch_hash_merge(m, device_, stream_), "hash merge");
+  } else {
+    // exact SUMs: every payload digit is < 2^32, so each imported row counts as one add against the normalize budget — the limbs are
+    // carried first when the rows could pass it. Rows that may repeat a group go in launches of at most the budget's rows.
+    m.n_exact_row = n_ship; m.exact_row_word0 = fdb_packed_row_words(kw, n_vals); m.exact_dst = d_limbs_;
+    for (int i = 0; i < n_ship; i++) m.exact_row_arr[i] = ship_arr[i];
+    const uint64_t lim = (uint64_t)knobs_.exact_normalize_rows;
+    for (int64_t r0 = 0; r0 < n_rows;) {
+      const int64_t r1 = unique_rows ? n_rows : std::min<int64_t>(n_rows, r0 + (int64_t)lim);
+      if (exact_adds_ + (uint64_t)(r1 - r0) > lim) exact_normalize_now();
+      exact_adds_ += (uint64_t)(r1 - r0);
+      FdbHashMergeArgs mc = m;
+      mc.in_keys = m.in_keys + r0 * (int64_t)rw; mc.entries = m.entries + r0 * (int64_t)(rw / 2); mc.n = r1 - r0;
+      hip_check(fdb_launch_hash_merge(mc, device_, stream_), "hash merge (exact)");
+      r0 = r1;
+    }
+  }
   hip_check(hipStreamSynchronize(stream_), "sync(hash import)");  // the caller may free `dev_rows` when this returns
   pt.mark("import: merge kernel");
   state_dirty_ = true;

@@ -524,6 +524,10 @@ struct FdbHashMergeArgs {
   // exact SUMs (table source only): the source's limb rows [n_exact][src_capacity][FDB_EXACT_WORDS] are added into ours
   // [n_exact][mask + 1][FDB_EXACT_WORDS]; their funcs[j] are 0 (the accumulator word is not touched)
   const unsigned long long* exact_src; unsigned long long* exact_dst; int32_t n_exact;
+  // exact SUMs (packed rows only): each incoming row carries n_exact_row payloads (FDB_EXACT_PACKED_WORDS words each, back to back
+  // from word exact_row_word0 of the row); payload i is added into our limb array exact_row_arr[i] of exact_dst
+  int32_t n_exact_row, exact_row_word0;
+  int32_t exact_row_arr[FDB_MAX_AGGS];
 };
 hipError_t fdb_launch_hash_merge(const FdbHashMergeArgs& args, int device, hipStream_t stream);
 
@@ -619,6 +623,14 @@ hipError_t fdb_launch_fill_u64(unsigned long long* p, int64_t n, unsigned long l
 // rows per partition.
 #define FDB_MAX_PARTS 64
 static inline int fdb_packed_row_words(int dst_key_words, int n_vals) { return (dst_key_words + 2 * n_vals + 3) & ~3; }  // (dst_key_words is a multiple of 4: values are 8-byte aligned, rows 16-byte)
+// Exact SUMs on the wire (the exchange of fdb_plan_exchange): a row of an exact plan carries, behind its values, one payload per float64
+// SUM — its limb row after a normalize, as FDB_EXACT_PACKED_WORDS 32-bit words: digits 0 … 64 (limbs 0 … 64, each in [0, 2^32)), the
+// top limb (int64: low word, high word) and the flag word (low, high). 276 bytes instead of the 576-byte row of the table. The payloads
+// lie back to back from word fdb_packed_row_words(…) on; the row is padded to 16 bytes.
+#define FDB_EXACT_PACKED_WORDS 69
+static inline int fdb_packed_row_words_exact(int dst_key_words, int n_vals, int n_exact_f64) {
+  return (fdb_packed_row_words(dst_key_words, n_vals) + FDB_EXACT_PACKED_WORDS * n_exact_f64 + 3) & ~3;
+}
 struct FdbHashPartArgs {
   const unsigned long long* table; const uint32_t* keys; uint64_t capacity;
   const FdbHashCol* cols;       // device array [n_cols]
@@ -629,6 +641,11 @@ struct FdbHashPartArgs {
   int32_t in_words;     // words of a source tuple that the columns reach (0: the whole stride)
   int32_t same_layout;  // source and destination tuples have one layout
   int32_t same_ids;     // … and every column keeps its key ids and its index: the fingerprint stored in the table IS the destination's (the counting pass reads entries only)
+  // exact SUMs: rows are out_words32 words apart (row_words32 + the payloads; 0 = row_words32); payload i (from word row_words32 on)
+  // is limb array exact_arr[i] of exact_limbs ([…][capacity][FDB_EXACT_WORDS], normalized)
+  int32_t out_words32, n_exact_ship;
+  int32_t exact_arr[FDB_MAX_AGGS];
+  const unsigned long long* exact_limbs;
 };
 size_t fdb_hash_partition_scratch_bytes(int device, const FdbHashPartArgs& args);
 hipError_t fdb_launch_hash_partition(const FdbHashPartArgs& args, int device, void* scratch, hipStream_t stream);

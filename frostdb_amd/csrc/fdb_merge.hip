@@ -242,6 +242,29 @@ __global__ __launch_bounds__(256) void hash_merge_wave_kernel(const FdbHashMerge
         }
       }
     }
+    // exact SUMs of packed rows (the exchange's import): payload i of a row is added into the destination slot's limb row
+    // exact_row_arr[i]. Lane ↦ (tuple, limb) over the tuples' rows laid end to end, so a wave reads and writes whole runs of adjacent
+    // words. Rows of ONE table (unique_source) touch a slot at most once per launch: a plain read-modify-write, no atomics. Zero digits
+    // are skipped (a sum reaches a few limbs only).
+    if (!TABLE_SRC && m.n_exact_row != 0) {
+      const int per_row = m.n_exact_row * (FDB_EXACT_FLAGS + 1), total = n_act * per_row;
+      for (int base = 0; base < total; base += 64) {  // (wave-uniform bound: every lane takes part in the shuffle)
+        const int it = base + lane;
+        const int t = it < total ? it / per_row : 0;
+        const uint64_t ds = (uint64_t)__shfl((unsigned long long)slot, t, 64);
+        if (it >= total) continue;
+        const int r = it - t * per_row, i = r / (FDB_EXACT_FLAGS + 1), k = r - i * (FDB_EXACT_FLAGS + 1);
+        const uint32_t* pw = m.in_keys + (row0 + t) * (int64_t)m.in_key_words + m.exact_row_word0 + i * FDB_EXACT_PACKED_WORDS;
+        // k < 65: digit k; k = 65: the top limb (words 65, 66); k = 66 = FDB_EXACT_FLAGS: the flag word (words 67, 68)
+        const unsigned long long v = k < FDB_EXACT_LIMBS - 1 ? (unsigned long long)as_global(pw)[k]
+                                                             : (unsigned long long)as_global(pw)[2 * k - 65] | ((unsigned long long)as_global(pw)[2 * k - 64] << 32);
+        if (v == 0ull) continue;
+        unsigned long long* dw = m.exact_dst + ((uint64_t)m.exact_row_arr[i] * (m.mask + 1) + ds) * FDB_EXACT_WORDS + k;
+        if (m.unique_source) *dw = k == FDB_EXACT_FLAGS ? (*dw | v) : *dw + v;
+        else if (k == FDB_EXACT_FLAGS) atomicOr(dw, v);
+        else atomicAdd(dw, v);
+      }
+    }
     wave_sync();
   };
 
@@ -268,6 +291,7 @@ __global__ __launch_bounds__(256) void hash_partition_wave_kernel(const FdbHashP
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, n_wv = blockDim.x >> 6;
   const int row_words = p.row_words32, dkw = p.dst_key_words;
+  const int out_words = p.out_words32 > 0 ? p.out_words32 : row_words;  // (stride of the packed rows: exact SUMs' payloads follow the tile's words)
   const WaveTiles T = wave_tiles(smem, wv, in_words, row_words, alias, FDB_PART_EXTRA);
   // [n_parts] next row of this wave in every partition: counts from 0 (PASS 0), positions from the wave's bases (PASS 1)
   unsigned long long* my_pos = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(T.queue) + wave_lds_bytes(in_words, row_words, alias));
@@ -314,7 +338,29 @@ __global__ __launch_bounds__(256) void hash_partition_wave_kernel(const FdbHashP
       for (int q = lane; q < total; q += 64) {
         const int t = q / RQ, j = q - t * RQ;
         const uint32_t* s = T.out + (size_t)(j * 4) * 64 + t;
-        *reinterpret_cast<u32x4*>(p.out + T.ins_slot[t] * (uint64_t)row_words + j * 4) = u32x4{s[0], s[64], s[128], s[192]};
+        *reinterpret_cast<u32x4*>(p.out + T.ins_slot[t] * (uint64_t)out_words + j * 4) = u32x4{s[0], s[64], s[128], s[192]};
+      }
+      // exact SUMs: the normalized limb rows follow as 32-bit words (fdb_kernels.h, FDB_EXACT_PACKED_WORDS), straight from the limb
+      // arrays — lane ↦ 16-byte quad of the payloads laid end to end: four adjacent limbs in, one 16-byte store out
+      if (p.n_exact_ship != 0) {
+        const int PQ = (out_words - row_words) >> 2, ptotal = n_act * PQ;
+        for (int q = lane; q < ptotal; q += 64) {
+          const int t = q / PQ, j = q - t * PQ;
+          const uint64_t src = T.queue[t];
+          uint32_t v[4];
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            const int w = j * 4 + u, i = w / FDB_EXACT_PACKED_WORDS, k = w - i * FDB_EXACT_PACKED_WORDS;
+            v[u] = 0u;
+            if (i < p.n_exact_ship) {
+              const unsigned long long* lr = p.exact_limbs + ((uint64_t)p.exact_arr[i] * p.capacity + src) * FDB_EXACT_WORDS;
+              // words 0 … 64: digits; 65 / 66: the top limb (row word 65) low / high; 67 / 68: the flag word (row word 66) low / high
+              const unsigned long long x = as_global(lr)[k < FDB_EXACT_LIMBS - 1 ? k : k < FDB_EXACT_LIMBS + 1 ? FDB_EXACT_LIMBS - 1 : FDB_EXACT_FLAGS];
+              v[u] = (k == FDB_EXACT_LIMBS || k == FDB_EXACT_LIMBS + 2) ? (uint32_t)(x >> 32) : (uint32_t)x;
+            }
+          }
+          *reinterpret_cast<u32x4*>(p.out + T.ins_slot[t] * (uint64_t)out_words + row_words + j * 4) = u32x4{v[0], v[1], v[2], v[3]};
+        }
       }
     }
     wave_sync();
@@ -384,6 +430,8 @@ hipError_t fdb_launch_hash_merge(const FdbHashMergeArgs& args, int device, hipSt
   const int64_t batches = table_src ? (int64_t)((args.src_capacity + 63) / 64) / 16 + 1 : (args.n + 63) / 64;
   const Geometry g = geometry(device, wave_lds_bytes(in_words, args.key_words, alias), batches);
   if (g.lds > ((size_t)150 << 10) || args.key_words % 4 != 0) return hipErrorInvalidValue;
+  if (args.n_exact_row != 0 && (table_src || args.exact_dst == nullptr || args.exact_row_word0 + FDB_EXACT_PACKED_WORDS * args.n_exact_row > args.in_key_words))
+    return hipErrorInvalidValue;
   if (g.lds > ((size_t)48 << 10)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_merge_wave_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 << 10);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&hash_merge_wave_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 << 10);
@@ -415,7 +463,9 @@ hipError_t fdb_launch_hash_partition(const FdbHashPartArgs& a, int device, void*
   if (a.capacity == 0) return hipSuccess;
   FdbHashPartArgs args = a;
   const PartPlan pp = part_plan(device, args);
-  if (args.row_words32 % 4 != 0 || ((uintptr_t)args.out & 15u) != 0 || pp.g.lds > ((size_t)150 << 10)) return hipErrorInvalidValue;
+  if (args.row_words32 % 4 != 0 || args.out_words32 % 4 != 0 || (args.out_words32 > 0 && args.out_words32 < args.row_words32 + FDB_EXACT_PACKED_WORDS * args.n_exact_ship) ||
+      (args.n_exact_ship != 0 && args.exact_limbs == nullptr) || ((uintptr_t)args.out & 15u) != 0 || pp.g.lds > ((size_t)150 << 10))
+    return hipErrorInvalidValue;
   const int64_t n_waves = (int64_t)pp.g.blocks * pp.g.waves;
   args.wave_bases = reinterpret_cast<unsigned long long*>(scratch);
   args.wave_counts = reinterpret_cast<uint32_t*>(args.wave_bases + n_waves * args.n_parts);

@@ -15,6 +15,10 @@ High-cardinality tables (cfg 5: millions of groups) take `merge_plan_alltoall` i
 rank's table, and a ring all-reduce / all-gather would be bound by ONE xGMI link. Groups are hash-partitioned by their
 128-bit fingerprint; each rank ships 1/N-th of its table straight to the owner of each partition (`all_to_all_single`:
 7 point-to-point xGMI links busy at once), owners merge on the device, and the result stays sharded.
+
+Not for plans with exact sums (``set_exact_sums``): this path moves raw accumulator state through entry points that refuse
+such plans (``fdb_plan_hash_export`` / ``_import``, ``fdb_plan_state_*``, ``fdb_plan_group_schema``). Exact plans merge across
+GPUs through ``frostdb_amd.comm`` (``Comm.merge`` / ``merge_alltoall``: ``fdb_plan_exchange`` carries their limbs).
 """
 from __future__ import annotations
 

@@ -403,13 +403,18 @@ FDB_API void fdb_comm_destroy(fdb_comm* comm);
  * MIN / MAX live as order-preserving int64 keys). The layout check is one tiny MAX all-reduce issued on the communicator's own
  * stream, so it overlaps the scan kernel. *aligned = 1: every rank now holds the
  * merged table (call fdb_plan_finish on the rank that emits; the others just close). *aligned = 0: layouts differ (or the plan
- * is in hash mode) — nothing was changed, use fdb_plan_exchange. Collective: every rank of `comm` must call it. */
+ * is in hash mode — always so for a plan with exact sums, fdb_plan_set_exact_sums) — nothing was changed, use fdb_plan_exchange.
+ * Collective: every rank of `comm` must call it. */
 FDB_API int fdb_plan_allreduce(fdb_plan* plan, fdb_comm* comm, int32_t* aligned);
 /* General merge (any table mode, any key sets; cfg 5): ranks agree on one group schema (all-gather of column names + distinct key
  * values, union in rank order), every table is re-keyed and hash-partitioned on the device (fdb_plan_hash_export), partitions
  * travel point-to-point to their owners (grouped send / recv: all 7 xGMI links of a GPU busy at once; slices of ≤ 128 MiB per
  * peer), owners merge on the device. The result STAYS SHARDED: *shard is a new plan of the same descriptor holding this rank's
- * share of the final groups (fingerprint % n_ranks == rank) — fdb_plan_finish + fdb_plan_close it. Collective. */
+ * share of the final groups (fingerprint % n_ranks == rank) — fdb_plan_finish + fdb_plan_close it. Collective.
+ * Exact sums (fdb_plan_set_exact_sums): every group's float64 SUMs travel as their normalized limb rows (276 bytes each behind the
+ * packed row) and the owner adds them into its own, so a shard's sums are the correctly rounded exact sums of ALL ranks' rows — the
+ * same bits for 1 or N ranks, any split of the rows between them and any rank order. Every rank must agree on the flag: if some
+ * ranks are exact and others not, every rank answers FDB_ERR_INVALID (before any data moves). */
 FDB_API int fdb_plan_exchange(fdb_plan* plan, fdb_comm* comm, fdb_plan** shard);
 
 /* Device memory owned by the library right now (≙ the reference's leak-checked allocator, memory.CheckedAllocator.AssertSize(0),
@@ -525,9 +530,10 @@ FDB_API int fdb_plan_set_deterministic(fdb_plan* plan, int32_t enabled);
  * group beside the hash table (576 bytes with its flag word and padding); the plan always scans into the hash table. COUNT, MIN, MAX,
  * UNIQUE, AND and integer SUMs are unchanged, as are the output schema and column names. Valid only before the plan's first push,
  * merge or seed (FDB_ERR_STATE afterwards). It wins over fdb_plan_set_deterministic: nothing is refused for its shape. Merging an
- * exact plan with a non-exact one is FDB_ERR_INVALID. Entry points that hand out or move raw accumulator state — fdb_plan_state_*,
- * fdb_plan_hash_export / _import, fdb_plan_group_schema / _seed_groups, fdb_plan_allreduce, fdb_plan_exchange — answer
- * FDB_ERR_UNSUPPORTED for an exact plan; fdb_plan_partial_keys / _partial_state hand out the rounded sums. */
+ * exact plan with a non-exact one is FDB_ERR_INVALID. Across GPUs, fdb_plan_exchange carries the limbs (exact shards, see there) and
+ * fdb_plan_allreduce answers *aligned = 0. Entry points that hand out or move raw accumulator state — fdb_plan_state_*,
+ * fdb_plan_hash_export / _import, fdb_plan_group_schema / _seed_groups — answer FDB_ERR_UNSUPPORTED for an exact plan;
+ * fdb_plan_partial_keys / _partial_state hand out the rounded sums. */
 FDB_API int fdb_plan_set_exact_sums(fdb_plan* plan, int32_t enabled);
 /* Host-only self-check of the exact summation (no device): out[0] = the correctly rounded exact sum of x[0 … n), computed by the same
  * digit split, normalize and rounding code the device kernels run. */

@@ -84,7 +84,8 @@ func AccountResults() FactoryOption { return func(c *factoryConfig) { c.accountR
 func Deterministic() FactoryOption { return func(c *factoryConfig) { c.deterministic = true } }
 
 // ExactSums asks every operator for float64 sums that are the correctly rounded exact sum of each group's values: the same bits
-// whatever the row order, record split or merge order (fdb_plan_set_exact_sums).
+// whatever the row order, record split or merge order (fdb_plan_set_exact_sums) — across GPUs too: MergeAcrossDevices then always
+// takes the exchange, which carries the sums' limbs, and the shards' bits do not depend on the number of GPUs or the split of rows.
 func ExactSums() FactoryOption { return func(c *factoryConfig) { c.exactSums = true } }
 
 // Factory is what the user hands to physicalplan.WithOperatorFactory: Build calls the returned func once per chain for every
@@ -600,7 +601,9 @@ func NewComms(devices []int) (Comms, error) {
 // MergeAcrossDevices is ≙ Synchronizer + HashAggregate(final=true) for chains on different GPUs: every chain's goroutine calls it
 // with its own endpoint (the calls are collective). With equal table layouts — parts of one table — the per-GPU tables are
 // all-reduced in place over xGMI and the chain on comms[0] emits the final record; otherwise the tables are hash-partitioned,
-// exchanged, merged, and EVERY chain emits its shard of the groups (OutputPlan's callback takes several records).
+// exchanged, merged, and EVERY chain emits its shard of the groups (OutputPlan's callback takes several records). Operators with
+// ExactSums never have aligned layouts (they live in the hash table): they take the exchange, and their shards' float64 sums are
+// exact. Every chain must agree on ExactSums, or every chain gets an error.
 func (o *Operator) MergeAcrossDevices(ctx context.Context, comm *C.fdb_comm) error {
 	// (no ctx.Err() shortcut here: the merge is collective — a rank that stayed out would leave its peers waiting inside RCCL;
 	// a cancelled query still takes part and drops its result afterwards)
