@@ -479,8 +479,6 @@ bool Plan::comm_allreduce(Comm& comm) {
     if (op == 0) continue;  // COUNT is served by the row-count array
     reds.push_back(Comm::Red{d_state_ + (size_t)a * slots_alloc_, (size_t)n_slots_, op});
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
   // Small tables (cfg 2 / 3 / 4: 1 025 slots × a few arrays): ONE all-gather of the packed table and a local fold in rank order, which
   // also writes the host copy — one collective on the step's critical path instead of one all-reduce per array, and float64 sums that
   // are bit-identical on every rank and in every run whatever order the ranks arrived in (what fdb_plan_set_deterministic
@@ -488,22 +486,23 @@ bool Plan::comm_allreduce(Comm& comm) {
   const int n_arrays = num_state_arrays();
   const size_t packed_bytes = (size_t)n_arrays * (size_t)n_slots_ * 8;
   if (packed_bytes * (size_t)comm.size <= ((size_t)32 << 20)) {
-    unsigned long long* d_packed = (unsigned long long*)ctx_->dev_alloc(packed_bytes + 256);
-    unsigned long long* d_all = (unsigned long long*)ctx_->dev_alloc(packed_bytes * (size_t)comm.size + 256);
-    scratch_.push_back(d_packed); scratch_.push_back(d_all);
-    int32_t ops[1 + FDB_MAX_AGGS] = {0};
-    for (int32_t a = 0; a < n_arrays; a++) ops[a] = state_array_op(a);
-    hip_check(fdb_launch_state_pack(d_state_, d_packed, n_slots_, slots_alloc_, n_arrays, stream_), "state pack");
-    comm.all_gather(d_packed, d_all, packed_bytes, stream_);
-    unsigned long long* host_out = mirror_target();
-    hip_check(fdb_launch_state_fold_ranks(d_all, comm.size, n_slots_, n_arrays, ops, d_state_, slots_alloc_, host_out, stream_), "state fold (rank order)");
-    if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); merge_events_.emplace_back(e0, e1); }
+    unsigned long long* host_out = nullptr;
+    timed([&] {
+      unsigned long long* d_packed = (unsigned long long*)ctx_->dev_alloc(packed_bytes + 256);
+      unsigned long long* d_all = (unsigned long long*)ctx_->dev_alloc(packed_bytes * (size_t)comm.size + 256);
+      scratch_.push_back(d_packed); scratch_.push_back(d_all);
+      int32_t ops[1 + FDB_MAX_AGGS] = {0};
+      for (int32_t a = 0; a < n_arrays; a++) ops[a] = state_array_op(a);
+      hip_check(fdb_launch_state_pack(d_state_, d_packed, n_slots_, slots_alloc_, n_arrays, stream_), "state pack");
+      comm.all_gather(d_packed, d_all, packed_bytes, stream_);
+      host_out = mirror_target();
+      hip_check(fdb_launch_state_fold_ranks(d_all, comm.size, n_slots_, n_arrays, ops, d_state_, slots_alloc_, host_out, stream_), "state fold (rank order)");
+    }, /*merge=*/true);
     state_dirty_ = true;
     mirror_valid_ = host_out != nullptr;
     return true;
   }
-  comm.all_reduce(reds, stream_);  // ordered after the scan and the fold kernel; Finish / Close wait for this stream
-  if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); merge_events_.emplace_back(e0, e1); }
+  timed([&] { comm.all_reduce(reds, stream_); }, /*merge=*/true);  // ordered after the scan and the fold kernel; Finish / Close wait for this stream
   state_dirty_ = true;
   // the merged table goes to the host copy from a kernel on the same stream (Finish then waits once and reads it; a device→host
   // copy command behind the collective was 15 µs)
@@ -684,10 +683,7 @@ void Plan::comm_exchange(Comm& comm, Plan& shard) {
   // 4. partitions travel to their owners, owners merge on the device
   unsigned long long* recv = nullptr;
   if (recv_rows > 0) { recv = (unsigned long long*)shard.ctx_->dev_alloc((size_t)recv_rows * rw * 4); shard.scratch_.push_back(recv); }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
-  comm.all_to_all((const unsigned long long*)rows, recv, words, stream_);
-  if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); merge_events_.emplace_back(e0, e1); }
+  timed([&] { comm.all_to_all((const unsigned long long*)rows, recv, words, stream_); }, /*merge=*/true);
   sync();  // the rows have arrived (and this plan's timing events / scratch are settled)
   pt.mark("exchange: all-to-all");
   // The owners merge what they received RANK BY RANK (the regions of `recv` are in rank order): every launch holds a group at most once, and

@@ -303,21 +303,14 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
     { int w = 4; for (size_t g = 0; g < hcols.size() && canonical; g++) { canonical = hcols[g].word == w; w += hcols[g].kind == 0 ? 1 : 2; } }
     h.canonical = canonical ? 1 : 0;
     unsigned char* d_blob = R.blob.bytes.empty() ? nullptr : (unsigned char*)upload(R.blob.bytes.data(), R.blob.bytes.size());
-    size_t lds_off = 0;
-    for (const PendingLut& p : R.luts) {  // predicate LUTs (kind 0 only: dense group LUTs were never added in this mode)
-      const bool in_lds = p.len_bytes <= 16384 && lds_off + p.len_bytes <= 32768;
-      uint32_t lds = FDB_NO_LDS;
-      if (in_lds) { lds = (uint32_t)lds_off; lds_off = align_up_sz(lds_off + p.len_bytes, 16); }
-      a.leaves[p.index].lut = d_blob + p.blob_off;
-      a.leaves[p.index].lut_lds = lds;
-    }
+    size_t lds_off = place_luts(R.luts, d_blob, 0, &a);  // predicate LUTs (kind 0 only: dense group LUTs were never added in this mode)
     for (size_t g = 0; g < hcols.size(); g++) {
       if (hcols[g].kind != 0 || lut_identity[g]) continue;  // (identity: lut stays nullptr)
       const size_t bytes = (size_t)hcols[g].lut_len * 4;
       hcols[g].lut = (const uint32_t*)(d_blob + lut_off[g]);
-      if (bytes <= 8192 && lds_off + bytes <= 60 * 1024) { hcols[g].lut_lds = (uint32_t)lds_off; lds_off = align_up_sz(lds_off + bytes, 16); }
+      if (bytes <= 8192 && lds_off + bytes <= 60 * 1024) { hcols[g].lut_lds = (uint32_t)lds_off; lds_off = align_up(lds_off + bytes, 16); }
     }
-    a.lds_lut_bytes = (uint32_t)align_up_sz(lds_off, 16);
+    a.lds_lut_bytes = (uint32_t)align_up(lds_off, 16);
     static const FdbHashCol kNoHashCol = {};  // (no group columns: one group; the kernels read no descriptor)
     h.hcols = (const FdbHashCol*)(hcols.empty() ? upload(&kNoHashCol, sizeof(FdbHashCol)) : upload(hcols.data(), hcols.size() * sizeof(FdbHashCol)));
     h.n_hcols = (int)hcols.size();
@@ -362,8 +355,8 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
       const int64_t n_chunks = b.rows / (FDB_RUN_CHUNK - 256) + launch_grid * 4 + 2;  // a wave abandons < 256 slots when it changes chunks and keeps one chunk open
       seg.capacity = n_chunks * FDB_RUN_CHUNK;
       seg.run_words = h.runs.run_words;
-      const size_t tuples_bytes = align_up_sz((size_t)seg.capacity * (seg.run_words == 0 ? (size_t)FDB_RUN_BYTES : seg.run_words == FDB_RUN_MEDIUM_WORDS ? (size_t)FDB_RUN_MEDIUM_BYTES : (size_t)seg.run_words * 4), 256);
-      const size_t dir_bytes = align_up_sz((size_t)seg.n_entries * 8, 256);
+      const size_t tuples_bytes = align_up((size_t)seg.capacity * (seg.run_words == 0 ? (size_t)FDB_RUN_BYTES : seg.run_words == FDB_RUN_MEDIUM_WORDS ? (size_t)FDB_RUN_MEDIUM_BYTES : (size_t)seg.run_words * 4), 256);
+      const size_t dir_bytes = align_up((size_t)seg.n_entries * 8, 256);
       seg.block = ctx_->dev_alloc(tuples_bytes + dir_bytes + 256);
       unsigned char* base = (unsigned char*)seg.block;
       seg.tuples = base;
@@ -373,11 +366,8 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
       h.runs.tuples = seg.tuples; h.runs.dir = seg.dir; h.runs.chunk_cursor = seg.cursor;
       h.table = nullptr; h.keys = nullptr; h.n_groups = nullptr; h.mask = 0;
       h.row_begin = 0; h.row_end = b.rows;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
-      hip_check(jit_hash_launch(jit_fn, h, (int)launch_grid, a.lds_lut_bytes + run_lds, stream_), "run scan launch");
+      timed([&] { hip_check(jit_hash_launch(jit_fn, h, (int)launch_grid, a.lds_lut_bytes + run_lds, stream_), "run scan launch"); });
       last_kernel_ = seg.run_words == 0 ? "fdb_hash_kernel(runs)" : seg.run_words == FDB_RUN_MEDIUM_WORDS ? "fdb_hash_kernel(runs, medium)" : "fdb_hash_kernel(runs, wide)";
-      if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); pending_events_.emplace_back(e0, e1); }
       state_dirty_ = true;
       stat_launches += 1;
       stat_bytes += R.bytes;
@@ -429,19 +419,18 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
                                                   (unsigned long long)h_capacity_, (unsigned long long)h_groups_bound_, (unsigned long long)h_rows_seen_);
       h.table = h_table_; h.keys = h_keys_; h.n_groups = h_count_dev_; h.mask = h_capacity_ - 1;
       h.row_begin = r0; h.row_end = r1;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
       if (jit_fn == nullptr && has_expr)
         throw Error(FDB_ERR_UNSUPPORTED, "computed (projected) columns need the run-time specialised kernel (hiprtc unavailable or disabled)");
-      if (jit_fn != nullptr) {
-        const int64_t n_tiles = (r1 - r0 + 1023) / 1024;
-        hip_check(jit_hash_launch(jit_fn, h, (int)std::min<int64_t>(jit_grid, n_tiles), a.lds_lut_bytes, stream_), "hash scan launch");
-        last_kernel_ = "fdb_hash_kernel";
-      } else {
-        hip_check(fdb_launch_scan_hash(h, grid, a.lds_lut_bytes, stream_), "hash scan launch");
-        last_kernel_ = "scan_hash_kernel";
-      }
-      if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); pending_events_.emplace_back(e0, e1); }
+      timed([&] {
+        if (jit_fn != nullptr) {
+          const int64_t n_tiles = (r1 - r0 + 1023) / 1024;
+          hip_check(jit_hash_launch(jit_fn, h, (int)std::min<int64_t>(jit_grid, n_tiles), a.lds_lut_bytes, stream_), "hash scan launch");
+          last_kernel_ = "fdb_hash_kernel";
+        } else {
+          hip_check(fdb_launch_scan_hash(h, grid, a.lds_lut_bytes, stream_), "hash scan launch");
+          last_kernel_ = "scan_hash_kernel";
+        }
+      });
       if (std::getenv("FDB_PROFILE_CHUNKS")) {  // tuning aid: per-launch time (serialises the scan)
         const auto t0 = std::chrono::steady_clock::now();
         hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
@@ -575,7 +564,7 @@ int64_t Plan::finish_columns_hash(std::vector<OutColumn>* out, DeviceBatch* resi
   // column back to back]; row masks on the side.
   std::vector<size_t> off_key(n_cols), off_bits(n_cols), off_val(n_vals), off_narrow(n_cols, 0);
   size_t total = 0;
-  auto place = [&](size_t bytes) { const size_t o = total; total = align_up_sz(total + bytes, 256); return o; };
+  auto place = [&](size_t bytes) { const size_t o = total; total = align_up(total + bytes, 256); return o; };
   for (size_t c = 0; c < n_cols; c++) if (narrow[c]) off_key[c] = place(np * 4);
   const size_t direct_begin = total;
   for (size_t c = 0; c < n_cols; c++) if (!narrow[c]) off_key[c] = place(np * (size_t)width[c]);
@@ -586,7 +575,7 @@ int64_t Plan::finish_columns_hash(std::vector<OutColumn>* out, DeviceBatch* resi
   // are on the host, so the bitmaps go LAST and are copied one by one)
   bool counts_wanted = false;
   for (const AggState& A : aggs_) if (A.func == FDB_AGG_COUNT && !final_stage_) counts_wanted = true;
-  const size_t direct_copy_bytes = (counts_wanted ? total + align_up_sz(np * 8, 256) : total) - direct_begin;
+  const size_t direct_copy_bytes = (counts_wanted ? total + align_up(np * 8, 256) : total) - direct_begin;
   off_val[0] = place(np * 8);
   const size_t bitmap_bytes = np / 8 + 64;
   for (size_t c = 0; c < n_cols; c++) off_bits[c] = place(bitmap_bytes);
@@ -1652,7 +1641,7 @@ bool Plan::merge_runs(Plan& src) {
   seg.n_entries = (v.n_runs + 255) / 256;
   seg.capacity = v.n_runs;
   seg.run_words = out_rw;
-  const size_t tuples_bytes = align_up_sz((size_t)v.n_runs * rec_bytes, 256), dir_bytes = align_up_sz((size_t)seg.n_entries * 8, 256);
+  const size_t tuples_bytes = align_up((size_t)v.n_runs * rec_bytes, 256), dir_bytes = align_up((size_t)seg.n_entries * 8, 256);
   seg.block = ctx_->dev_alloc(tuples_bytes + dir_bytes + 256);
   seg.tuples = (unsigned char*)seg.block;
   seg.dir = (uint32_t*)(seg.tuples + tuples_bytes); seg.cursor = (uint32_t*)(seg.tuples + tuples_bytes + dir_bytes);

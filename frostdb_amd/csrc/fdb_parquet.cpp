@@ -832,9 +832,6 @@ void parse_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* outp) 
   if (is_bytes) out.dict = make_dictionary(std::move(dict_values), c.utf8 ? "u" : "z");
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-constexpr size_t kTailPad = 256;
-
 std::atomic<int64_t> g_pq_calls{0}, g_pq_host_us{0}, g_pq_device_us{0}, g_pq_file_bytes{0}, g_pq_out_bytes{0};
 
 }  // namespace

@@ -31,11 +31,6 @@ void hip_check(hipError_t e, const char* what) {
   if (e != hipSuccess) throw Error(e == hipErrorOutOfMemory ? FDB_ERR_OOM : FDB_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-constexpr size_t kTailPad = 256;  // bytes readable past every column so tail lanes may over-read
-}
 void copy_stream(void* dst, const void* src, size_t n);                          // fdb_widen.cc: streaming-store copies into the pinned slab
 uint32_t copy_stream_max_u32(uint32_t* dst, const uint32_t* src, size_t n);
 namespace {
@@ -58,16 +53,16 @@ const char* agg_name(int32_t f) {  // logicalplan/expr.go:731-750
   return "unknown";
 }
 
-bool is_leaf_op(int32_t op) {
-  return (op >= FDB_OP_EQ && op <= FDB_OP_REGEX_NOT_MATCH) || op == FDB_OP_CONTAINS || op == FDB_OP_NOT_CONTAINS;
-}
-
 bool match_group(const GroupMatcher& m, const std::string& field) {  // logicalplan/expr.go:353-355, :564-566
   if (m.dynamic) return field.size() > m.name.size() && field.compare(0, m.name.size(), m.name) == 0 && field[m.name.size()] == '.';
   return field == m.name;
 }
 
 }  // namespace
+
+bool is_leaf_op(int32_t op) {
+  return (op >= FDB_OP_EQ && op <= FDB_OP_REGEX_NOT_MATCH) || op == FDB_OP_CONTAINS || op == FDB_OP_NOT_CONTAINS;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // DeviceBatch
@@ -532,7 +527,6 @@ int Plan::resolve_projection(const Projection& p, const DeviceBatch& b, Resolved
       FdbLeaf& L = a.leaves[li];
       std::memset(&L, 0, sizeof(L));
       L.lut_lds = FDB_NO_LDS; L.slot = -1;
-      R->luts.reserve(64);
       R->cur_node = -1 - (int)(base + k);  // (truth tables are cached per (node, dictionary): projection nodes get ids of their own)
       resolve_leaf(fe, b, R, &a.leaves[li]);
       e.kind = 7; e.slot = li; e.left = e.right = -1; e.type = FDB_T_BOOL;
@@ -873,7 +867,6 @@ static void emit_filter(const std::vector<ExprNode>& nodes, int idx, const Devic
   std::memset(&L, 0, sizeof(L));
   L.lut_lds = FDB_NO_LDS;
   L.slot = -1;
-  R->luts.reserve(64);
   const int li = a.n_leaves;
   a.leaves[li] = L;
   // resolve (may append a LUT that refers to leaf index li)
@@ -1204,17 +1197,21 @@ void Plan::push_batch(const DeviceBatch& b) {
   push_batches(&p, 1);
 }
 
+void Plan::resolve_predicate(const DeviceBatch& b, int root, Resolved* R) {
+  std::memset(&R->args, 0, sizeof(R->args));
+  R->args.n_rows = b.rows;
+  R->truths = &truth_cache_;
+  R->count_selected = [this, &b](int n) { return count_subtree(b, n); };
+  int max_depth = 0;
+  if (root >= 0) emit_filter(filter_, root, b, R, 0, &max_depth);
+}
+
 // Resolves one record against the plan (per-dictionary-entry work only): predicate program + LUTs, group columns
 // + key-id LUTs (may assign new key ids), aggregated columns. Nothing is launched.
 void Plan::resolve_batch(const DeviceBatch& b, Resolved* Rp, std::vector<int>* batch_gcols) {
   Resolved& R = *Rp;
-  std::memset(&R.args, 0, sizeof(R.args));
+  resolve_predicate(b, filter_root_, &R);
   FdbScanArgs& a = R.args;
-  a.n_rows = b.rows;
-  int max_depth = 0;
-  R.truths = &truth_cache_;
-  R.count_selected = [this, &b](int n) { return count_subtree(b, n); };
-  if (filter_root_ >= 0) emit_filter(filter_, filter_root_, b, &R, 0, &max_depth);
 
   // group columns: every field matched by a matcher, in the record's field order (aggregate.go:286-303)
   for (size_t ci = 0; ci < b.cols.size(); ci++) {
@@ -1332,7 +1329,7 @@ void Plan::resolve_batch(const DeviceBatch& b, Resolved* Rp, std::vector<int>* b
 // total, all in c4/c8), 2 for the two-phase layout (filter columns in c4/c8, group-by / aggregate columns in l4/l8).
 // `relaxed`: only the limits of the argument block apply (the run-time specialised kernel has no register-resident plan);
 // *interp_ok then tells whether the interpreting slot kernel could run this record too.
-static int assign_slots(const DeviceBatch& b, Plan::Resolved& R, int first_layout = 1, bool relaxed = false, bool* interp_ok = nullptr) {
+int assign_slots(const DeviceBatch& b, Plan::Resolved& R, int first_layout, bool relaxed, bool* interp_ok) {
   FdbScanArgs& a = R.args;
   // static limits of the slot kernel's register-resident plan
   bool strict = !(a.n_leaves > 6 || a.n_gcols > 2 || a.n_aggs > 6 || a.n_expr > 0);
@@ -1475,32 +1472,17 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
   std::vector<size_t> blob_base((size_t)n, 0);
   std::vector<int> lut_class((size_t)n, 0);
   {
-    // records whose LUT sets are byte-identical (the usual case: parts of one table share dictionaries) share one
-    // device copy and one class id, so the kernel re-stages LUTs in LDS only when the class changes
-    std::vector<int> reps;
+    std::vector<int> reps;  // (same_lut_set: one device copy and one class per LUT set)
     for (int i : live) {
       const Resolved& R = Rs[(size_t)i];
       int found = -1;
-      for (int r : reps) {
-        const Resolved& Q = Rs[(size_t)r];
-        if (Q.blob.bytes == R.blob.bytes && Q.luts.size() == R.luts.size()) {
-          bool same = true;
-          for (size_t k = 0; k < R.luts.size() && same; k++)
-            same = Q.luts[k].kind == R.luts[k].kind && Q.luts[k].index == R.luts[k].index && Q.luts[k].blob_off == R.luts[k].blob_off &&
-                   Q.luts[k].len_bytes == R.luts[k].len_bytes;
-          if (same) { found = r; break; }
-        }
-      }
+      for (int r : reps) if (same_lut_set(Rs[(size_t)r], R)) { found = r; break; }
       if (found >= 0) { blob_base[(size_t)i] = blob_base[(size_t)found]; lut_class[(size_t)i] = lut_class[(size_t)found]; }
       else { blob_base[(size_t)i] = blob.add(R.blob.bytes.data(), R.blob.bytes.size()); lut_class[(size_t)i] = (int)reps.size(); reps.push_back(i); }
     }
   }
   // the LUT blob and the argument blocks below go to the device with ONE copy command, issued right before the launch
-  struct StageScope {
-    Context* c;
-    explicit StageScope(Context* ctx) : c(ctx) { c->defer_staging(true); }
-    ~StageScope() { try { c->defer_staging(false); } catch (...) {} }
-  } stage_scope(ctx_);
+  StageScope stage_scope(ctx_);
   unsigned char* d_blob = blob.bytes.empty() ? nullptr : (unsigned char*)upload(blob.bytes.data(), blob.bytes.size());
 
   const size_t acc_bytes = align_up((size_t)n_slots_ * 4, 16) + (size_t)n_slots_ * 8 * aggs_.size();
@@ -1520,16 +1502,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     for (size_t j = 0; j < aggs_.size(); j++) if (a.aggs[j].func == FDB_AGG_COUNT) a.need_count = 1;
     a.lut_class = lut_class[(size_t)i];
     // LDS plan: [LUT copies][cnt u32 × n_slots][acc u64 × n_slots × n_aggs]
-    size_t lds_off = 0;
-    for (const PendingLut& p : R.luts) {
-      const bool in_lds = p.len_bytes <= 16384 && lds_off + p.len_bytes <= 32768;
-      uint32_t lds = FDB_NO_LDS;
-      if (in_lds) { lds = (uint32_t)lds_off; lds_off = align_up(lds_off + p.len_bytes, 16); }
-      unsigned char* at = d_blob + blob_base[(size_t)i] + p.blob_off;
-      if (p.kind == 0) { a.leaves[p.index].lut = at; a.leaves[p.index].lut_lds = lds; }
-      else { a.gcols[p.index].lut = (const uint32_t*)at; a.gcols[p.index].lut_lds = lds; }
-    }
-    lut_lds_max = std::max(lut_lds_max, align_up(lds_off, 16));
+    lut_lds_max = std::max(lut_lds_max, place_luts(R.luts, d_blob + blob_base[(size_t)i], 0, &a));
     if (slots_ok) {
       bool strict = true;
       const int layout = assign_slots(*bs[i], R, 1, jit_possible, &strict);
@@ -1572,18 +1545,6 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
       funcs[1 + j] = f == FDB_AGG_COUNT ? 0 : f == FDB_AGG_SUM ? (ty == FDB_T_F64 ? 2 : 1) : f == FDB_AGG_MIN ? 3 : 4;
     }
   }
-  auto timed_launch = [&](const std::function<void()>& launch) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) {
-      e0 = ctx_->get_event(); e1 = ctx_->get_event();
-      hip_check(hipEventRecord(e0, stream_), "hipEventRecord");
-    }
-    launch();
-    if (timing) {
-      hip_check(hipEventRecord(e1, stream_), "hipEventRecord");
-      pending_events_.emplace_back(e0, e1);
-    }
-  };
   auto alloc_partials = [&](int grid) -> unsigned long long* {
     if (!lds_acc || !use_partials || grid <= 0) return nullptr;
     void* p = ctx_->dev_alloc((size_t)grid * (1 + aggs_.size()) * n_slots_ * 8);
@@ -1703,7 +1664,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     ctx_->flush_staging();
     pt.mark("parts upload");
     trace("after upload");
-    timed_launch([&] {
+    timed([&] {
       if (jit_fn != nullptr) hip_check(jit_launch(jit_fn, d_parts, (int)parts.size(), total_tiles, parts[0], grid, jit_block, lds_bytes, stream_), "scan launch");
       else hip_check(fdb_launch_scan_slots(d_parts, (int)parts.size(), parts[0], total_tiles, grid, lds_bytes, two_phase, sub, stream_), "scan launch");
     });
@@ -1729,7 +1690,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
       a.n_c4 = a.n_c8 = 0;
       const int grid = fdb_scan_grid(a, base_grid, rpt);
       a.partials = alloc_partials(grid);
-      timed_launch([&] { hip_check(fdb_launch_scan_dense(a, grid, lds_bytes, rpt, stream_), "scan launch"); });
+      timed([&] { hip_check(fdb_launch_scan_dense(a, grid, lds_bytes, rpt, stream_), "scan launch"); });
       last_kernel_ = "scan_dense_kernel";
       mirror_valid_ = false;  // (a launch that flushes with atomics leaves the host copy behind)
       if (a.partials != nullptr) {
@@ -2255,789 +2216,6 @@ void Plan::merge_from(Plan& src) {
   }
   state_dirty_ = true;
   sync();
-}
-
-namespace {
-struct DevBuf {  // scratch from the context's caching allocator; the plan's stream orders every reuse
-  Context* ctx;
-  void* p = nullptr;
-  DevBuf(Context* c, size_t bytes) : ctx(c), p(c->dev_alloc(bytes)) {}
-  ~DevBuf() { ctx->dev_free(p); }
-  DevBuf(const DevBuf&) = delete;
-};
-}  // namespace
-
-// ---- selection / filter-only -------------------------------------------------------------------------------------
-// ≙ filter() (filter.go:276-323): the reference turns the predicate's bitmap into index ranges, slices every column per range
-// and concatenates the slices. Here ONE kernel pass evaluates the predicate, gives every selected row its output position
-// (decoupled look-back over per-tile totals) and writes the compacted columns — see fdb_launch_compact.
-// Rows of `b` the filter sub-tree rooted at `node` selects (one launch of the interpreting flags kernel + a wait): only used where
-// the reference's lazy AND decides whether an error exists at all (emit_filter).
-int64_t Plan::count_subtree(const DeviceBatch& b, int node) {
-  if (b.rows == 0) return 0;
-  hip_check(hipSetDevice(device_), "hipSetDevice");
-  slab_ship();  // (a small pushed record may still sit in the pinned slab: its bytes go first)
-  Resolved R;
-  std::memset(&R.args, 0, sizeof(R.args));
-  R.args.n_rows = b.rows;
-  int max_depth = 0;
-  R.truths = &truth_cache_;
-  R.count_selected = [this, &b](int n) { return count_subtree(b, n); };
-  emit_filter(filter_, node, b, &R, 0, &max_depth);
-  FdbScanArgs& a = R.args;
-  size_t lds_off = 0;
-  unsigned char* d_blob = R.blob.bytes.empty() ? nullptr : (unsigned char*)upload(R.blob.bytes.data(), R.blob.bytes.size());
-  for (const PendingLut& p : R.luts) {
-    const bool in_lds = p.len_bytes <= 16384 && lds_off + p.len_bytes <= 32768;
-    uint32_t lds = FDB_NO_LDS;
-    if (in_lds) { lds = (uint32_t)lds_off; lds_off = align_up(lds_off + p.len_bytes, 16); }
-    a.leaves[p.index].lut = d_blob + p.blob_off;
-    a.leaves[p.index].lut_lds = lds;
-  }
-  a.lds_lut_bytes = (uint32_t)align_up(lds_off, 16);
-  ctx_->flush_staging();
-  b.note_reader(stream_);
-  uint8_t* masks = nullptr;
-  uint32_t* offs = nullptr;
-  return run_flags(a, &masks, &offs);
-}
-
-void Plan::resolve_filter_only(const DeviceBatch& b, Resolved* Rp) {
-  Resolved& R = *Rp;
-  std::memset(&R.args, 0, sizeof(R.args));
-  R.args.n_rows = b.rows;
-  int max_depth = 0;
-  R.truths = &truth_cache_;
-  R.count_selected = [this, &b](int n) { return count_subtree(b, n); };
-  emit_filter(filter_, filter_root_, b, &R, 0, &max_depth);
-  FdbScanArgs& a = R.args;
-  size_t lds_off = 0;
-  unsigned char* d_blob = R.blob.bytes.empty() ? nullptr : (unsigned char*)upload(R.blob.bytes.data(), R.blob.bytes.size());
-  for (const PendingLut& p : R.luts) {
-    const bool in_lds = p.len_bytes <= 16384 && lds_off + p.len_bytes <= 32768;
-    uint32_t lds = FDB_NO_LDS;
-    if (in_lds) { lds = (uint32_t)lds_off; lds_off = align_up(lds_off + p.len_bytes, 16); }
-    a.leaves[p.index].lut = d_blob + p.blob_off;
-    a.leaves[p.index].lut_lds = lds;
-  }
-  a.lds_lut_bytes = (uint32_t)align_up(lds_off, 16);
-}
-
-// Steps 1 + 2 of filter(): selection bitmap and per-tile output offsets on the device (scratch of this plan until its next
-// sync()), number of selected rows on the host.
-int64_t Plan::run_flags(const FdbScanArgs& a, uint8_t** d_masks, uint32_t** d_offsets) {
-  const int64_t n_tiles = (a.n_rows + FDB_COMPACT_TILE - 1) / FDB_COMPACT_TILE;
-  uint8_t* masks = (uint8_t*)ctx_->dev_alloc((size_t)n_tiles * (FDB_COMPACT_TILE / 8) + 64);
-  uint32_t* offs = (uint32_t*)ctx_->dev_alloc((size_t)(n_tiles + 4 + n_tiles / 1024 + 8) * 4 + 64);  // (+ the scan's per-1024 sums)
-  unsigned long long* d_total = (unsigned long long*)ctx_->dev_alloc(64);
-  scratch_.push_back(masks); scratch_.push_back(offs); scratch_.push_back(d_total);
-  hip_check(hipMemsetAsync(offs, 0, (size_t)(n_tiles + 4) * 4, stream_), "hipMemsetAsync(tile counts)");
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
-  hip_check(fdb_launch_filter_flags(a, masks, offs, device_, stream_), "filter flags launch");
-  hip_check(fdb_launch_exclusive_scan(offs, n_tiles, offs + n_tiles + 4, d_total, stream_), "tile offsets launch");
-  if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); pending_events_.emplace_back(e0, e1); }
-  unsigned long long total = 0;
-  hip_check(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(total)");
-  hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-  *d_masks = masks; *d_offsets = offs;
-  stat_launches += 1;
-  return (int64_t)total;
-}
-
-int64_t Plan::select_batch(const DeviceBatch& in, uint32_t* d_indices, int64_t capacity) {
-  if (filter_root_ < 0) throw Error(FDB_ERR_STATE, "plan has no filter");
-  if (in.device != device_) throw Error(FDB_ERR_INVALID, "batch lives on a different device than the plan");
-  if (capacity < in.rows) throw Error(FDB_ERR_INVALID, "indices capacity smaller than the record");
-  hip_check(hipSetDevice(device_), "hipSetDevice");
-  if (in.rows == 0) return 0;
-  Resolved R;
-  resolve_filter_only(in, &R);
-  uint8_t* masks = nullptr;
-  uint32_t* offs = nullptr;
-  const int64_t n = run_flags(R.args, &masks, &offs);
-  if (n > 0) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
-    hip_check(fdb_launch_compact_col(0, nullptr, nullptr, d_indices, nullptr, masks, offs, in.rows, nullptr, device_, stream_), "compact launch");
-    if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); pending_events_.emplace_back(e0, e1); }
-  }
-  last_kernel_ = "compact_col_kernel";
-  sync();
-  stat_bytes += R.bytes + n * 4;
-  stat_rows += in.rows;
-  return n;
-}
-
-std::unique_ptr<DeviceBatch> Plan::filter_batch(const DeviceBatch& in, int64_t* n_selected) {
-  const DeviceBatch* p = &in;
-  std::vector<std::unique_ptr<DeviceBatch>> out = filter_batches(&p, 1, n_selected);  // (falls back to filter_batch_interp by itself)
-  return std::move(out[0]);
-}
-
-// The per-record path: interpreting flags kernel, one compaction launch per column (what runs when the predicate cannot be
-// specialised at run time, and the parity reference of the generated kernels).
-std::unique_ptr<DeviceBatch> Plan::filter_batch_interp(const DeviceBatch& in, int64_t* n_selected) {
-  if (filter_root_ < 0) throw Error(FDB_ERR_STATE, "plan has no filter");
-  if (in.device != device_) throw Error(FDB_ERR_INVALID, "batch lives on a different device than the plan");
-  if (in.cols.size() > 128) throw Error(FDB_ERR_UNSUPPORTED, "filter output: more than 128 columns");
-  hip_check(hipSetDevice(device_), "hipSetDevice");
-  std::unique_ptr<DeviceBatch> out(new DeviceBatch());
-  out->device = device_;
-  // an error below must not hand `out`'s arena (or `in`, which the caller may release) back to the pool with kernels still queued
-  struct DrainOnUnwind {
-    hipStream_t s; int n = std::uncaught_exceptions();
-    ~DrainOnUnwind() { if (std::uncaught_exceptions() > n) (void)hipStreamSynchronize(s); }
-  } drain{stream_};
-  for (const DevColumn& c : in.cols) {
-    if (c.d_values == nullptr && in.rows > 0)
-      throw Error(FDB_ERR_UNSUPPORTED, "filter output: column type " + c.format + " (" + c.name + ") is not supported on the device path");
-    DevColumn d;
-    d.name = c.name; d.format = c.format; d.kind = c.kind; d.dict = c.dict;
-    out->cols.push_back(std::move(d));
-  }
-  *n_selected = 0;
-  if (in.rows == 0) return out;
-  Resolved R;
-  resolve_filter_only(in, &R);
-  uint8_t* masks = nullptr;
-  uint32_t* offs = nullptr;
-  const int64_t total = run_flags(R.args, &masks, &offs);  // (one host round trip: the output is allocated at its exact size)
-  *n_selected = total;
-  out->rows = total;
-  stat_bytes += R.bytes;
-  stat_rows += in.rows;
-  if (total == 0) { sync(); return out; }
-  const uint64_t cap = (uint64_t)total;
-  struct Piece { size_t val_off, bit_off; };
-  std::vector<Piece> pieces(in.cols.size());
-  size_t total_bytes = 0;
-  for (size_t k = 0; k < in.cols.size(); k++) {
-    const DevColumn& c = in.cols[k];
-    const size_t w = c.kind == ColKind::DICT ? 4 : 8;
-    pieces[k].val_off = total_bytes;
-    total_bytes += align_up(cap * w + kTailPad, 256);
-    pieces[k].bit_off = total_bytes;
-    if (c.d_validity != nullptr) total_bytes += align_up((cap + 7) / 8 + kTailPad, 256);
-  }
-  out->arena = device_pool_alloc(device_, std::max<size_t>(total_bytes, 256));
-  out->arena_bytes = std::max<size_t>(total_bytes, 256);
-  unsigned long long* d_nulls = (unsigned long long*)ctx_->dev_alloc(128 * 64 * 8);  // 64 partial counts per column
-  scratch_.push_back(d_nulls);
-  hip_check(hipMemsetAsync(d_nulls, 0, in.cols.size() * 64 * 8, stream_), "hipMemsetAsync(null counts)");
-  struct OutCol { void* dst; uint8_t* dst_valid; int width; };
-  std::vector<OutCol> cols(in.cols.size());
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
-  for (size_t k = 0; k < in.cols.size(); k++) {  // one streaming pass per column (fdb_launch_compact_col)
-    const DevColumn& c = in.cols[k];
-    OutCol& C = cols[k];
-    C.dst = (unsigned char*)out->arena + pieces[k].val_off;
-    C.width = c.kind == ColKind::DICT ? 4 : 8;
-    C.dst_valid = nullptr;
-    if (c.d_validity != nullptr) {  // the output bitmap is OR-ed into: zero it first
-      C.dst_valid = (uint8_t*)out->arena + pieces[k].bit_off;
-      hip_check(hipMemsetAsync(C.dst_valid, 0, align_up((cap + 7) / 8 + kTailPad, 256), stream_), "hipMemsetAsync(validity)");
-    }
-    hip_check(fdb_launch_compact_col(C.width, c.d_values, c.d_validity, C.dst, C.dst_valid, masks, offs, in.rows, d_nulls + k * 64, device_, stream_), "compact launch");
-  }
-  if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); pending_events_.emplace_back(e0, e1); }
-  last_kernel_ = "compact_col_kernel";
-  std::vector<unsigned long long> h_parts(cols.size() * 64), h_nulls(cols.size(), 0);
-  hip_check(hipMemcpyAsync(h_parts.data(), d_nulls, cols.size() * 64 * 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(null counts)");
-  hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-  for (size_t k = 0; k < cols.size(); k++) for (int i = 0; i < 64; i++) h_nulls[k] += h_parts[k * 64 + (size_t)i];
-  for (size_t k = 0; k < in.cols.size(); k++) {
-    const DevColumn& c = in.cols[k];
-    DevColumn& d = out->cols[k];
-    d.length = total;
-    d.null_count = (int64_t)h_nulls[k];
-    d.d_values = cols[k].dst;
-    d.value_bytes = c.kind == ColKind::BOOL ? (total + 7) / 8 : total * cols[k].width;
-    if (c.d_validity != nullptr && d.null_count > 0) {
-      d.d_validity = cols[k].dst_valid;
-      d.validity_bytes = (total + 7) / 8;
-    }
-    out->payload_bytes += d.value_bytes + d.validity_bytes;
-    // algorithmic bytes of the compaction: every selected value read once and written once, validity likewise
-    stat_bytes += 2 * (total * cols[k].width) + (c.d_validity != nullptr ? 2 * ((total + 7) / 8) : 0);
-  }
-  sync();
-  return out;
-}
-
-// ≙ PredicateFilter.Callback for every record of a scan at once (filter.go:255-323). Four launches whatever the number of records
-// (five above ≈130 M rows): selection bitmap + per-tile counts by a kernel generated for the predicate (fdb_flags_kernel) →
-// prefix sums (sel_scan_kernel) → [host: the records' row counts, outputs allocated at their exact sizes] → zero the output
-// bitmaps → every column of every record compacted (compact_multi_kernel). Two host round trips in total. Falls back to the
-// per-record path (interpreting flags kernel, one compaction launch per column) when the predicate cannot be specialised.
-// The one-pass select kernel's workers and its scanner wait for each other with BOUNDED polls (2^22 of them, ≈ 1–2 s): on a GPU shared
-// with long kernels of other processes, or with a queue that is preempted or debugged, a valid filter() can run into the bound. That is
-// not the caller's error: the batch is filtered again through the three-launch path (flags → prefix sums → compaction), which waits for
-// nothing on the device. ($FDB_TEST_SELECT_STALL: pretends the bound was hit — the test of this road)
-std::vector<std::unique_ptr<DeviceBatch>> Plan::filter_batches(const DeviceBatch* const* in, int n, int64_t* n_selected) {
-  try {
-    return filter_batches_impl(in, n, n_selected, /*force_two_pass=*/false);
-  } catch (const SelectStall&) {
-    return filter_batches_impl(in, n, n_selected, /*force_two_pass=*/true);
-  }
-}
-
-std::vector<std::unique_ptr<DeviceBatch>> Plan::filter_batches_impl(const DeviceBatch* const* in, int n, int64_t* n_selected, bool force_two_pass) {
-  if (filter_root_ < 0) throw Error(FDB_ERR_STATE, "plan has no filter");
-  std::vector<std::unique_ptr<DeviceBatch>> out;
-  auto per_record = [&]() {
-    out.clear();
-    for (int i = 0; i < n; i++) out.push_back(filter_batch_interp(*in[i], &n_selected[i]));
-    return std::move(out);
-  };
-  std::vector<int> live;
-  for (int i = 0; i < n; i++) {
-    if (in[i]->device != device_) throw Error(FDB_ERR_INVALID, "batch lives on a different device than the plan");
-    if (in[i]->cols.size() > 128) throw Error(FDB_ERR_UNSUPPORTED, "filter output: more than 128 columns");
-    if (in[i]->rows > 0) live.push_back(i);
-  }
-  // one column layout for the whole launch (parts of one table); anything else takes the per-record path
-  bool multi = jit_possible() && !live.empty() && !in[live[0]]->cols.empty();
-  for (size_t k = 1; k < live.size() && multi; k++) {
-    const DeviceBatch& a = *in[live[0]];
-    const DeviceBatch& b = *in[live[k]];
-    multi = a.cols.size() == b.cols.size();
-    for (size_t c = 0; c < a.cols.size() && multi; c++) multi = a.cols[c].kind == b.cols[c].kind && a.cols[c].name == b.cols[c].name;
-  }
-  if (!multi) return per_record();
-  hip_check(hipSetDevice(device_), "hipSetDevice");
-  for (int i : live) in[i]->note_reader(stream_);
-  struct DrainOnUnwind {
-    hipStream_t s; int n = std::uncaught_exceptions();
-    ~DrainOnUnwind() { if (std::uncaught_exceptions() > n) (void)hipStreamSynchronize(s); }
-  };
-  for (int i = 0; i < n; i++) {
-    std::unique_ptr<DeviceBatch> o(new DeviceBatch());
-    o->device = device_;
-    for (const DevColumn& c : in[i]->cols) {
-      if (c.d_values == nullptr && in[i]->rows > 0)
-        throw Error(FDB_ERR_UNSUPPORTED, "filter output: column type " + c.format + " (" + c.name + ") is not supported on the device path");
-      DevColumn d;
-      d.name = c.name; d.format = c.format; d.kind = c.kind; d.dict = c.dict;
-      o->cols.push_back(std::move(d));
-    }
-    out.push_back(std::move(o));
-    n_selected[i] = 0;
-  }
-  DrainOnUnwind drain{stream_};  // (declared after `out`: an error waits for the queued kernels before the arenas go back to the pool)
-
-  // ---- predicate of every record: program + LUTs; records with byte-identical LUT sets share one device copy and one class ----
-  const size_t nl = live.size();
-  std::vector<Resolved> Rs(nl);
-  std::vector<int> lut_class(nl, 0);
-  std::vector<size_t> blob_base(nl, 0);
-  Blob blob;
-  {
-    std::vector<size_t> reps;
-    for (size_t k = 0; k < nl; k++) {
-      Resolved& R = Rs[k];
-      std::memset(&R.args, 0, sizeof(R.args));
-      R.args.n_rows = in[live[k]]->rows;
-      int max_depth = 0;
-      R.truths = &truth_cache_;
-      R.count_selected = [this, rec = in[live[k]]](int n) { return count_subtree(*rec, n); };
-      emit_filter(filter_, filter_root_, *in[live[k]], &R, 0, &max_depth);
-      size_t found = reps.size();
-      for (size_t r = 0; r < reps.size(); r++) {
-        const Resolved& Q = Rs[reps[r]];
-        if (Q.blob.bytes == R.blob.bytes && Q.luts.size() == R.luts.size()) { found = r; break; }
-      }
-      if (found < reps.size()) { lut_class[k] = (int)found; blob_base[k] = blob_base[reps[found]]; }
-      else { lut_class[k] = (int)reps.size(); blob_base[k] = blob.add(R.blob.bytes.data(), R.blob.bytes.size()); reps.push_back(k); }
-    }
-  }
-  struct StageScope {
-    Context* c;
-    explicit StageScope(Context* ctx) : c(ctx) { c->defer_staging(true); }
-    ~StageScope() { try { c->defer_staging(false); } catch (...) {} }
-  };
-  size_t lut_lds_max = 0;
-  JitShape shape;
-  int row_bytes = 0;
-  const FdbScanArgs* d_parts = nullptr;
-  const FdbCompactRec* d_recs = nullptr;
-  std::vector<FdbScanArgs> parts;
-  std::vector<FdbCompactRec> recs;
-  int64_t total_tiles = 0, total_super = 0;
-  bool fallback = false;
-  {
-    StageScope stage_scope(ctx_);
-    unsigned char* d_blob = blob.bytes.empty() ? nullptr : (unsigned char*)upload(blob.bytes.data(), blob.bytes.size());
-    for (size_t k = 0; k < nl; k++) {
-      Resolved& R = Rs[k];
-      FdbScanArgs& a = R.args;
-      size_t lds_off = 0;
-      for (const PendingLut& p : R.luts) {
-        const bool in_lds = p.len_bytes <= 16384 && lds_off + p.len_bytes <= 32768;
-        uint32_t lds = FDB_NO_LDS;
-        if (in_lds) { lds = (uint32_t)lds_off; lds_off = align_up(lds_off + p.len_bytes, 16); }
-        a.leaves[p.index].lut = d_blob + blob_base[k] + p.blob_off;
-        a.leaves[p.index].lut_lds = lds;
-      }
-      lut_lds_max = std::max(lut_lds_max, align_up(lds_off, 16));
-      a.lut_class = lut_class[k];
-      // every filter column in the early pools (the flags kernel has no late phase)
-      // (no `return per_record()` in here: the scope's destructor — which ends the deferral and ships what was staged — runs only
-      // AFTER a return expression has been evaluated, and the per-record path stages LUTs of its own)
-      if (assign_slots(*in[live[k]], R, 2, /*relaxed=*/true) == 0) { fallback = true; break; }
-      if (k == 0) shape = jit_shape(a, true, 512);
-      else if (!jit_shape_merge_args(&shape, Rs[0].args, a, true)) { fallback = true; break; }  // records of different predicate shapes (schema drift)
-      // the flags kernel counts in workgroup shares of four tiles (all of one record), the other kernels in tiles
-      const int64_t rec_tiles = (a.n_rows + FDB_COMPACT_TILE - 1) / FDB_COMPACT_TILE;
-      a.out_tile_base = total_tiles;
-      a.tile_begin = total_super;
-      total_super += (rec_tiles + 3) / 4;
-      a.tile_end = total_super;
-      recs.push_back(FdbCompactRec{total_tiles, a.n_rows});
-      total_tiles += rec_tiles;
-    }
-    for (size_t k = 0; k < nl && !fallback; k++) { Rs[k].args.lds_lut_bytes = (uint32_t)lut_lds_max; parts.push_back(Rs[k].args); }
-    for (int k = 0; k < shape.n_c4; k++) row_bytes += shape.c4[k].has_values ? 4 : 0;
-    for (int k = 0; k < shape.n_c8; k++) row_bytes += shape.c8[k].has_values ? 8 : 0;
-    if (!fallback) {
-      d_parts = (const FdbScanArgs*)upload(parts.data(), parts.size() * sizeof(FdbScanArgs));
-      d_recs = (const FdbCompactRec*)upload(recs.data(), recs.size() * sizeof(FdbCompactRec));
-    }
-  }
-  if (fallback) return per_record();
-  const size_t n_cols = in[live[0]]->cols.size();
-
-  // ---- which kernel: one pass over the filter columns (fdb_select_kernel), or bitmap → prefix sums → compaction ----------------------
-  // One pass: the wave that evaluates a tile also places it (look-back) and writes the compacted values of the filter columns it has
-  // in registers — columns WITHOUT a validity bitmap in any record, ≤ 8 bytes per row together (their tile is staged in LDS), whose
-  // slot reads the record's own column (a remapped or widened copy is not the column). Their outputs must exist before the row
-  // count does: worst-case sized pool blocks (extra_arenas), repacked into the exact arena when less than 40 % of them is used.
-  const bool two_pass_env = force_two_pass || std::getenv("FDB_SELECT_TWO_PASS") != nullptr;  // (A/B, tests, fall-back: the three-launch prefix sum; read per call)
-  struct FusedCol { bool wide; int slot; int col; };
-  std::vector<FusedCol> fused;
-  std::vector<int> fused_of(n_cols, -1);  // column → index in `fused`
-  if (!two_pass_env) {
-    int budget = 8;
-    auto try_slot = [&](bool wide, int slot) {
-      const JitSlot& js = wide ? shape.c8[slot] : shape.c4[slot];
-      const int w = wide ? 8 : 4;
-      if (!js.has_values || js.has_validity != 0 || w > budget || (int)fused.size() >= FDB_SELECT_MAX_FUSED) return;
-      int col = -1;
-      for (size_t k = 0; k < nl; k++) {
-        const DeviceBatch& b = *in[live[k]];
-        const void* v = wide ? Rs[k].args.c8[slot].values : Rs[k].args.c4[slot].values;
-        int found = -1;
-        for (size_t c = 0; c < n_cols; c++) if (b.cols[c].d_values == v && v != nullptr) { found = (int)c; break; }
-        if (found < 0 || (k > 0 && found != col)) return;
-        const DevColumn& dc = b.cols[(size_t)found];
-        if (dc.d_validity != nullptr || dc.kind == ColKind::BOOL || (dc.kind == ColKind::DICT) != !wide) return;
-        col = found;
-      }
-      if (col < 0 || fused_of[(size_t)col] >= 0) return;
-      fused_of[(size_t)col] = (int)fused.size();
-      fused.push_back(FusedCol{wide, slot, col});
-      budget -= w;
-    };
-    for (int i = 0; i < shape.n_c8; i++) try_slot(true, i);
-    for (int i = 0; i < shape.n_c4; i++) try_slot(false, i);
-    // (the kernel numbers its outputs 8-byte slots first, then 4-byte slots, in slot order — the order they were tried in)
-    for (const FusedCol& f : fused) { if (f.wide) shape.fuse8 |= 1 << f.slot; else shape.fuse4 |= 1 << f.slot; }
-  }
-  // When it pays (MI355X, 100 M rows, 4 columns): `value > x` 0.86 → 0.79 ms of kernels; with a second, unfused filter column the
-  // kernel needs 145 registers (one workgroup per CU) and loses what the saved read gains (0.84 → 0.86), cfg 3's three dictionary
-  // leaves 0.94 → 1.00. So: every filter column the predicate reads values of is fused, and they are the full 8 bytes per row.
-  // ($FDB_SELECT_ONE_PASS: whenever the kernel can be built — tests, A/B)
-  bool one_pass_wanted = !two_pass_env;
-  if (one_pass_wanted && std::getenv("FDB_SELECT_ONE_PASS") == nullptr) {
-    int fused_bytes = 0, value_slots = 0;
-    for (const FusedCol& f : fused) fused_bytes += f.wide ? 8 : 4;
-    for (int i = 0; i < shape.n_c8; i++) value_slots += shape.c8[i].has_values ? 1 : 0;
-    for (int i = 0; i < shape.n_c4; i++) value_slots += shape.c4[i].has_values ? 1 : 0;
-    one_pass_wanted = fused_bytes == 8 && value_slots == (int)fused.size();
-  }
-  if (!one_pass_wanted) { fused.clear(); std::fill(fused_of.begin(), fused_of.end(), -1); shape.fuse4 = shape.fuse8 = 0; }
-  hipFunction_t select_fn = one_pass_wanted ? jit_select_kernel_get(shape) : nullptr;
-  hipFunction_t flags_fn = select_fn == nullptr ? jit_flags_get(shape) : nullptr;
-  if (select_fn == nullptr) { fused.clear(); std::fill(fused_of.begin(), fused_of.end(), -1); }
-  if (select_fn == nullptr && flags_fn == nullptr) return per_record();
-  const bool one_pass = select_fn != nullptr;
-
-  // ---- selection bitmap, tile offsets, row counts -----------------------------------------------------------------------------
-  uint32_t* d_masks = (uint32_t*)ctx_->dev_alloc((size_t)total_tiles * (FDB_COMPACT_TILE / 8) + 256);
-  uint32_t* d_offsets = (uint32_t*)ctx_->dev_alloc((size_t)total_tiles * 4 + 256);
-  scratch_.push_back(d_masks); scratch_.push_back(d_offsets);
-  auto timed = [&](const std::function<void()>& f) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
-    f();
-    if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); pending_events_.emplace_back(e0, e1); }
-  };
-  const size_t stage_off = align_up(lut_lds_max, 16);
-  const int first_block = one_pass ? jit_select_block() : 256;
-  const size_t first_lds = one_pass ? stage_off + (size_t)(first_block / 64) * jit_select_stage_bytes(shape) : lut_lds_max;
-  int per_cu = 1;
-  {
-    // a wave keeps 4 steps × 64 lanes × 4 rows of every filter column in flight: ≈128 KB per CU (twice jit_select's figure: the
-    // waves also spend time on words, counts and stores)
-    int waves = row_bytes > 0 ? (131072 / (64 * 4 * 4)) / row_bytes : 8;
-    waves = std::max(8, std::min(28, waves));
-    per_cu = std::max(1, std::min(jit_blocks_per_cu(one_pass ? select_fn : flags_fn, first_block, first_lds), waves / (first_block / 64)));
-  }
-  int64_t grid = (int64_t)(fdb_scan_default_grid(device_) / 2) * per_cu;
-  if (grid_override > 0) grid = grid_override;
-  if (grid > total_super) grid = total_super;
-  unsigned long long* h_base = (unsigned long long*)ctx_->host_alloc((nl + 1 + FDB_SELECT_CTL_WORDS) * 8);
-  struct HostFree { Context* c; void* p; ~HostFree() { c->host_free(p); } } hf{ctx_, h_base};
-  std::vector<int64_t> totals(nl, 0);
-  int launches = 0;
-  const unsigned long long* d_rec_base_arg = nullptr;  // (one pass: the offsets are relative to their record already)
-  std::vector<char> pre_nullable(n_cols, 0);         // one pass: what the select launch zeroed on its way in (below)
-  std::vector<void*> pre_bits(nl, nullptr);
-  std::vector<size_t> pre_bits_bytes(nl, 0);
-  unsigned long long* pre_nulls = nullptr;
-  size_t pre_nulls_words = 0;
-  if (one_pass) {
-    // outputs of the fused columns: one worst-case block per record, owned by the result from here on
-    std::vector<FdbSelectPart> sparts(nl);
-    uint32_t epoch = 0;
-    unsigned long long ticket_base = 0, arrival_base = 0;
-    const size_t status_words = align_up((size_t)total_super, 16);
-    unsigned long long* d_ctl = ctx_->select_ctl(align_up(nl, 16) + status_words + 16 * (size_t)total_super, &epoch, &ticket_base, &arrival_base);
-    for (size_t k = 0; k < nl; k++) {
-      const DeviceBatch& src = *in[live[k]];
-      DeviceBatch& o = *out[(size_t)live[k]];
-      std::memset(&sparts[k], 0, sizeof(FdbSelectPart));
-      sparts[k].total = d_ctl + FDB_SELECT_CTL_WORDS + k;
-      if (fused.empty()) continue;
-      size_t bytes = 0;
-      std::vector<size_t> off(fused.size());
-      for (size_t f = 0; f < fused.size(); f++) { off[f] = bytes; bytes += align_up((size_t)src.rows * (fused[f].wide ? 8 : 4) + kTailPad, 256); }
-      void* block = device_pool_alloc(device_, bytes);
-      o.extra_arenas.push_back(block);
-      o.arena_bytes += bytes;
-      for (size_t f = 0; f < fused.size(); f++) sparts[k].dst[f] = (unsigned char*)block + off[f];
-    }
-    // The other columns' validity bitmaps and NULL counters — what the compaction launch ORs / adds into — are zeroed by THIS launch on
-    // its way in (FdbSelectArgs::zero) instead of by a launch of their own between the two: they must exist before the row counts do,
-    // so a record's bitmaps get a worst-case block of their own (rows / 8 bytes per nullable column; the values still go into an arena
-    // of the exact size).
-    for (size_t k = 0; k < nl; k++)
-      for (size_t c = 0; c < n_cols; c++) if (in[live[k]]->cols[c].d_validity != nullptr) pre_nullable[c] = 1;
-    size_t n_rest_pre = 0;
-    bool any_nullable_pre = false;
-    for (size_t c = 0; c < n_cols; c++) if (fused_of[c] < 0) { n_rest_pre++; any_nullable_pre = any_nullable_pre || pre_nullable[c]; }
-    std::vector<unsigned long long> zero_tab;
-    if (any_nullable_pre) {
-      for (size_t k = 0; k < nl; k++) {
-        const DeviceBatch& src = *in[live[k]];
-        DeviceBatch& o = *out[(size_t)live[k]];
-        size_t bytes = 0;
-        for (size_t c = 0; c < n_cols; c++) if (pre_nullable[c]) bytes += align_up((size_t)(src.rows + 7) / 8 + kTailPad, 256);
-        void* block = device_pool_alloc(device_, std::max<size_t>(bytes, 256));
-        pre_bits[k] = block;
-        pre_bits_bytes[k] = std::max<size_t>(bytes, 256);
-        // (in FRONT of the fused columns' block: that one stays extra_arenas.back())
-        o.extra_arenas.insert(o.extra_arenas.begin(), block);
-        o.arena_bytes += pre_bits_bytes[k];
-        zero_tab.push_back((unsigned long long)(uintptr_t)block);
-        zero_tab.push_back((unsigned long long)pre_bits_bytes[k]);
-      }
-      pre_nulls_words = nl * std::max<size_t>(n_rest_pre, 1) * 64;
-      pre_nulls = (unsigned long long*)ctx_->dev_alloc(align_up(pre_nulls_words * 8, 256));
-      scratch_.push_back(pre_nulls);
-      zero_tab.push_back((unsigned long long)(uintptr_t)pre_nulls);
-      zero_tab.push_back((unsigned long long)align_up(pre_nulls_words * 8, 256));
-    }
-    FdbSelectArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.ctl = d_ctl;
-    sa.ticket_base = ticket_base;
-    sa.epoch = epoch;
-    sa.stage_off = (uint32_t)stage_off;
-    sa.arrival_base = arrival_base;
-    sa.status_off = (uint32_t)(FDB_SELECT_CTL_WORDS + align_up(nl, 16));
-    sa.place_off = (uint32_t)(sa.status_off + status_words);
-    {
-      StageScope stage_scope(ctx_);
-      sa.sparts = (const FdbSelectPart*)upload(sparts.data(), sparts.size() * sizeof(FdbSelectPart));
-      if (!zero_tab.empty()) { sa.zero = (const unsigned long long*)upload(zero_tab.data(), zero_tab.size() * 8); sa.n_zero = (int32_t)(zero_tab.size() / 2); }
-    }
-    timed([&] { hip_check(jit_select_launch(select_fn, d_parts, (int)parts.size(), total_super, parts[0], (int)grid + 1, first_lds, d_masks, d_offsets, sa, stream_), "select launch"); });
-    // (one workgroup more than workers: the scanner; every worker draws exactly one ticket past the end)
-    ctx_->select_ctl_drawn((unsigned long long)total_super + (unsigned long long)grid, (unsigned long long)grid + 1);
-    launches = 1;
-    hip_check(hipMemcpyAsync(h_base, d_ctl + 1, (FDB_SELECT_CTL_WORDS - 1 + nl) * 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(row counts)");
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");  // (first host round trip: the other columns' outputs are allocated at their exact sizes)
-    if (h_base[0] != 0ull || std::getenv("FDB_TEST_SELECT_STALL") != nullptr) {  // a wait ran into its bound: nothing of this attempt is kept
-      ctx_->select_ctl_reset();
-      hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-      throw SelectStall();
-    }
-    for (size_t k = 0; k < nl; k++) totals[k] = (int64_t)h_base[FDB_SELECT_CTL_WORDS - 1 + k];
-  } else {
-    const int64_t n_blocks = (total_tiles + 1023) / 1024;
-    const size_t counts_bytes = align_up((size_t)n_blocks * 8 + (size_t)total_tiles * 4, 256);
-    unsigned char* d_counts = (unsigned char*)ctx_->dev_alloc(counts_bytes);
-    unsigned long long* d_rec_base = (unsigned long long*)ctx_->dev_alloc((nl + 1) * 8 + 64);
-    scratch_.push_back(d_counts); scratch_.push_back(d_rec_base);
-    unsigned long long* d_block_sums = (unsigned long long*)d_counts;
-    uint32_t* d_tile_counts = (uint32_t*)(d_counts + (size_t)n_blocks * 8);
-    const bool two_level = n_blocks > 64;  // (below that every scan workgroup adds up the counts in front of its block itself)
-    timed([&] {
-      hip_check(jit_flags_launch(flags_fn, d_parts, (int)parts.size(), total_super, parts[0], (int)grid, lut_lds_max, d_masks, d_tile_counts, stream_), "flags launch");
-      if (two_level) hip_check(fdb_launch_sel_block_sums(d_tile_counts, total_tiles, d_block_sums, stream_), "block sums launch");
-      hip_check(fdb_launch_sel_scan(d_tile_counts, two_level ? d_block_sums : nullptr, total_tiles, d_offsets, d_recs, (int)nl, d_rec_base, stream_), "prefix sums launch");
-    });
-    launches = two_level ? 3 : 2;
-    hip_check(hipMemcpyAsync(h_base, d_rec_base, (nl + 1) * 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(row counts)");
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");  // (first host round trip: outputs are allocated at their exact sizes)
-    for (size_t k = 0; k < nl; k++) totals[k] = (int64_t)(h_base[k + 1] - h_base[k]);
-    d_rec_base_arg = d_rec_base;  // (offsets are global here: compact_multi_kernel subtracts the record's base)
-  }
-
-  // ---- outputs: [values of every column | validity bitmaps of every column] per record --------------------------------------
-  // (`rest`: the columns compact_multi_kernel writes — all of them, minus what the one-pass kernel has written already)
-  std::vector<int> rest;
-  for (size_t c = 0; c < n_cols; c++) if (fused_of[c] < 0) rest.push_back((int)c);
-  const size_t n_rest = rest.size();
-  std::vector<FdbCompactCol> cols(nl * std::max<size_t>(n_rest, 1));
-  std::vector<FdbZeroRegion> regions;
-  int64_t max_region = 0, any_selected = 0;
-  // a column is compacted as nullable if ANY record of the launch has a bitmap for it (the kernel is specialised per column, not
-  // per record); the records that have none read an all-ones bitmap
-  std::vector<char> nullable(n_cols, 0);
-  int64_t ones_rows = 0;
-  for (size_t k = 0; k < nl; k++)
-    for (size_t c = 0; c < n_cols; c++) if (in[live[k]]->cols[c].d_validity != nullptr) nullable[c] = 1;
-  for (size_t k = 0; k < nl; k++)
-    for (size_t c = 0; c < n_cols; c++) if (nullable[c] && in[live[k]]->cols[c].d_validity == nullptr) ones_rows = std::max(ones_rows, in[live[k]]->rows);
-  uint8_t* d_ones = nullptr;
-  if (ones_rows > 0) {
-    const size_t ones_bytes = align_up((size_t)(ones_rows + 7) / 8 + kTailPad, 256);
-    d_ones = (uint8_t*)ctx_->dev_alloc(ones_bytes);
-    scratch_.push_back(d_ones);
-    hip_check(hipMemsetAsync(d_ones, 0xFF, ones_bytes, stream_), "hipMemsetAsync(all-valid bitmap)");
-  }
-  struct Placed { void* values = nullptr; uint8_t* valid = nullptr; };
-  std::vector<Placed> placed(nl * n_cols);
-  // worst-case blocks whose contents moved into the exact arena (or of records nothing was selected from): back to the pool once the
-  // repacking copies have read them — after the wait below, or, when an error unwinds from here on, after a wait of its own
-  struct PoolFree {
-    int dev; hipStream_t s; std::vector<void*> v; int n = std::uncaught_exceptions();
-    ~PoolFree() {
-      if (!v.empty() && std::uncaught_exceptions() > n) (void)hipStreamSynchronize(s);
-      for (void* p : v) device_pool_free(dev, p);
-    }
-  } pool_free{device_, stream_, {}};
-  std::vector<void*>& repacked = pool_free.v;
-  for (size_t k = 0; k < nl; k++) {
-    const DeviceBatch& src = *in[live[k]];
-    DeviceBatch& o = *out[(size_t)live[k]];
-    const int64_t total = totals[k];
-    if (total < 0 || total > src.rows) throw Error(FDB_ERR_DEVICE, "internal: selection counts out of range");
-    n_selected[live[k]] = total;
-    o.rows = total;
-    any_selected += total;
-    stat_bytes += Rs[k].bytes;
-    stat_rows += src.rows;
-    // the fused columns stay where the kernel put them unless most of the block is unused
-    const bool repack = !fused.empty() && total > 0 && (double)total < 0.4 * (double)src.rows;
-    size_t bytes = 0, bits_at = 0;
-    std::vector<size_t> val_off(n_cols, 0), bit_off(n_cols, 0);
-    for (size_t c = 0; c < n_cols; c++) {
-      if (fused_of[c] >= 0 && !repack) continue;
-      val_off[c] = bytes;
-      bytes += align_up((size_t)total * (src.cols[c].kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
-    }
-    bits_at = bytes;
-    uint8_t* const bits_block = (uint8_t*)pre_bits[k];  // (one pass with nullable columns: zeroed by the select launch, worst-case sized)
-    if (bits_block != nullptr) {
-      size_t at = 0;
-      for (size_t c = 0; c < n_cols; c++) if (nullable[c]) { bit_off[c] = at; at += align_up((size_t)(src.rows + 7) / 8 + kTailPad, 256); }
-    } else {
-      for (size_t c = 0; c < n_cols; c++)
-        if (nullable[c]) { bit_off[c] = bytes; bytes += align_up(((size_t)total + 7) / 8 + kTailPad, 256); }
-    }
-    if (total > 0 && bytes > 0) {
-      o.arena = device_pool_alloc(device_, std::max<size_t>(bytes, 256));
-      o.arena_bytes += std::max<size_t>(bytes, 256);
-      if (bytes > bits_at) { regions.push_back(FdbZeroRegion{(unsigned char*)o.arena + bits_at, (int64_t)(bytes - bits_at)}); max_region = std::max<int64_t>(max_region, (int64_t)(bytes - bits_at)); }
-    }
-    if (bits_block != nullptr && total == 0) {  // nothing selected: the record's result has no buffers at all
-      o.extra_arenas.erase(o.extra_arenas.begin());
-      o.arena_bytes -= pre_bits_bytes[k];
-      repacked.push_back(bits_block);
-    }
-    if (!fused.empty() && (total == 0 || repack)) {  // the worst-case block is not part of the result
-      void* block = o.extra_arenas.back();
-      o.extra_arenas.pop_back();
-      size_t worst = 0;
-      for (size_t f = 0; f < fused.size(); f++) {
-        const int w = fused[f].wide ? 8 : 4;
-        if (repack) hip_check(hipMemcpyAsync((unsigned char*)o.arena + val_off[(size_t)fused[f].col], (unsigned char*)block + worst, (size_t)total * w, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(repack)");
-        worst += align_up((size_t)src.rows * w + kTailPad, 256);
-      }
-      o.arena_bytes -= worst;
-      repacked.push_back(block);
-    }
-    for (size_t c = 0; c < n_cols; c++) {
-      Placed& P = placed[k * n_cols + c];
-      if (fused_of[c] >= 0 && !repack) {
-        // (fused columns sit in the block in `fused` order)
-        size_t at = 0;
-        for (int f = 0; f < fused_of[c]; f++) at += align_up((size_t)src.rows * (fused[(size_t)f].wide ? 8 : 4) + kTailPad, 256);
-        P.values = total > 0 ? (unsigned char*)o.extra_arenas.back() + at : nullptr;
-      } else {
-        P.values = total > 0 ? (unsigned char*)o.arena + val_off[c] : nullptr;
-      }
-      P.valid = total > 0 && nullable[c] ? (bits_block != nullptr ? bits_block : (uint8_t*)o.arena) + bit_off[c] : nullptr;
-    }
-    for (size_t r = 0; r < n_rest; r++) {
-      const size_t c = (size_t)rest[r];
-      FdbCompactCol& C = cols[k * n_rest + r];
-      C.src = src.cols[c].d_values;
-      C.width = src.cols[c].kind == ColKind::DICT ? 4 : 8;
-      C.nullable = nullable[c];
-      C.src_valid = nullable[c] ? (src.cols[c].d_validity != nullptr ? src.cols[c].d_validity : d_ones) : nullptr;
-      C.dst = placed[k * n_cols + c].values;
-      C.dst_valid = placed[k * n_cols + c].valid;
-    }
-  }
-  std::vector<unsigned long long> h_nulls(nl * std::max<size_t>(n_rest, 1) * 64, 0);
-  int any_nullable = 0;
-  for (size_t r = 0; r < n_rest; r++) any_nullable |= nullable[(size_t)rest[r]] ? 1 : 0;
-  {
-    if (any_selected > 0 && n_rest > 0) {
-      // NULL counts and validity bitmaps exist only when some column has a bitmap: without one there is nothing to zero, count or copy back
-      unsigned long long* d_nulls = nullptr;
-      if (any_nullable && pre_nulls != nullptr && pre_nulls_words >= h_nulls.size()) {
-        d_nulls = pre_nulls;  // (zeroed by the select launch)
-      } else if (any_nullable) {
-        d_nulls = (unsigned long long*)ctx_->dev_alloc(h_nulls.size() * 8);
-        scratch_.push_back(d_nulls);
-        regions.push_back(FdbZeroRegion{d_nulls, (int64_t)(h_nulls.size() * 8)});
-        max_region = std::max<int64_t>(max_region, (int64_t)(h_nulls.size() * 8));
-      }
-      const FdbCompactCol* d_cols = (const FdbCompactCol*)upload(cols.data(), cols.size() * sizeof(FdbCompactCol));
-      const FdbZeroRegion* d_regions = regions.empty() ? nullptr : (const FdbZeroRegion*)upload(regions.data(), regions.size() * sizeof(FdbZeroRegion));
-      // waves are dealt to the columns in proportion to their bytes per row (a wave stays on its column for the whole launch):
-      // 1.5 × the workgroups of 4 waves that are resident at once (a wave's share of tiles is fixed at launch: smaller shares even out
-      // the waves that finish late — measured 8 % faster than exactly-resident; handing tiles out dynamically, one ticket per tile or per
-      // 8 tiles on a per-column counter, was slower: 2.5 ms and 1.08 ms against 0.90), at least one wave per column, never more waves
-      // than a column has tiles
-      const int64_t budget = (int64_t)(fdb_scan_default_grid(device_) / 2) * ((fdb_compact_multi_blocks_per_cu(any_nullable) * 3 + 1) / 2) * 4;
-      int64_t weight_sum = 0;
-      for (size_t r = 0; r < n_rest; r++) weight_sum += cols[r].width;
-      std::vector<int32_t> wave_begin(n_rest + 1, 0);
-      for (size_t r = 0; r < n_rest; r++) {
-        int64_t share = std::max<int64_t>(1, budget * cols[r].width / std::max<int64_t>(weight_sum, 1));
-        share = std::min<int64_t>(share, total_tiles);
-        wave_begin[r + 1] = wave_begin[r] + (int32_t)share;
-      }
-      const int32_t* d_wave_begin = (const int32_t*)upload(wave_begin.data(), wave_begin.size() * 4);
-      timed([&] {
-        if (!regions.empty()) hip_check(fdb_launch_zero_regions(d_regions, (int)regions.size(), max_region, stream_), "zero launch");
-        hip_check(fdb_launch_compact_multi(d_recs, (int)nl, d_cols, (int)n_rest, any_nullable, d_wave_begin, wave_begin[n_rest], d_masks, d_offsets, d_rec_base_arg, total_tiles, d_nulls, stream_),
-                  "compact launch");
-      });
-      launches += regions.empty() ? 1 : 2;
-      if (any_nullable) hip_check(hipMemcpyAsync(h_nulls.data(), d_nulls, h_nulls.size() * 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(null counts)");
-    }
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    for (void* p : repacked) device_pool_free(device_, p);
-    repacked.clear();
-  }
-  last_kernel_ = one_pass ? (n_rest > 0 ? "fdb_select_kernel + compact_multi_kernel" : "fdb_select_kernel") : "fdb_flags_kernel + compact_multi_kernel";
-  stat_launches += launches;
-  for (size_t k = 0; k < nl; k++) {
-    const DeviceBatch& src = *in[live[k]];
-    DeviceBatch& o = *out[(size_t)live[k]];
-    const int64_t total = o.rows;
-    for (size_t c = 0; c < n_cols; c++) {
-      const Placed& P = placed[k * n_cols + c];
-      const int width = src.cols[c].kind == ColKind::DICT ? 4 : 8;
-      DevColumn& d = o.cols[c];
-      d.length = total;
-      unsigned long long nulls = 0;
-      size_t r = 0;
-      for (; r < n_rest; r++) if ((size_t)rest[r] == c) break;
-      if (r < n_rest) for (int q = 0; q < 64; q++) nulls += h_nulls[(k * n_rest + r) * 64 + (size_t)q];
-      d.null_count = (int64_t)nulls;
-      d.d_values = P.values;
-      d.value_bytes = src.cols[c].kind == ColKind::BOOL ? (total + 7) / 8 : total * width;
-      if (P.valid != nullptr && d.null_count > 0) { d.d_validity = P.valid; d.validity_bytes = (total + 7) / 8; }
-      o.payload_bytes += d.value_bytes + d.validity_bytes;
-      // algorithmic bytes of the compaction: every selected value read once and written once, validity likewise
-      stat_bytes += 2 * (total * width) + (src.cols[c].d_validity != nullptr ? 2 * ((total + 7) / 8) : 0);
-    }
-  }
-  sync();
-  return out;
-}
-
-// The record of a resident batch as Arrow in host memory (one device→host copy per buffer).
-void export_batch(const DeviceBatch& b, ArrowArray* out, ArrowSchema* out_schema) {
-  hip_check(hipSetDevice(b.device), "hipSetDevice");
-  const int64_t n = b.rows;
-  std::vector<OutColumn> cols;
-  for (const DevColumn& c : b.cols) {
-    if (c.d_values == nullptr && n > 0)
-      throw Error(FDB_ERR_UNSUPPORTED, "export: column type " + c.format + " (" + c.name + ") is not held on the device");
-    OutColumn o;
-    o.name = c.name;
-    o.length = n;
-    const int w = c.kind == ColKind::DICT ? 4 : 8;
-    o.format = c.kind == ColKind::DICT ? "I" : c.format;
-    o.values.resize((size_t)n * w);
-    if (n > 0) hip_check(hipMemcpy(o.values.data(), c.d_values, (size_t)n * w, hipMemcpyDeviceToHost), "hipMemcpy(export values)");
-    if (c.d_validity != nullptr && n > 0) {
-      o.validity.assign((size_t)((n + 63) / 64) * 8, 0);
-      hip_check(hipMemcpy(o.validity.data(), c.d_validity, (size_t)(n + 7) / 8, hipMemcpyDeviceToHost), "hipMemcpy(export validity)");
-      o.null_count = count_nulls(o.validity.data(), 0, n);
-    }
-    if (c.kind == ColKind::DICT && c.dict && c.dict->plain) {  // a plain string / binary column leaves as one
-      const std::vector<uint8_t> idx_bytes = std::move(o.values);
-      set_plain_strings(&o, (const uint32_t*)idx_bytes.data(), o.validity.empty() ? nullptr : o.validity.data(), n, c.dict->values, c.dict->value_format);
-    } else if (c.kind == ColKind::DICT) {
-      if (!c.dict) throw Error(FDB_ERR_INVALID, "export: dictionary column without its dictionary: " + c.name);
-      set_dictionary(&o, c.dict->values, c.dict->value_format);
-    } else if (c.kind == ColKind::BOOL) {  // held as int64 1 / 2, Arrow wants bits
-      std::vector<uint8_t> bits((size_t)(n + 7) / 8 + 8, 0);
-      for (int64_t i = 0; i < n; i++) { int64_t v; std::memcpy(&v, o.values.data() + (size_t)i * 8, 8); if (v >= 2) bits[(size_t)(i >> 3)] |= (uint8_t)(1u << (i & 7)); }
-      o.values = std::move(bits);
-    }
-    cols.push_back(std::move(o));
-  }
-  export_record(std::move(cols), n, out, out_schema);
-}
-
-void Plan::select(const ArrowArray* array, const ArrowSchema* schema, uint32_t* indices, int64_t capacity, int64_t* n_selected) {
-  if (filter_root_ < 0) throw Error(FDB_ERR_STATE, "plan has no filter");
-  HostRecordView view;
-  view_record(array, schema, &view);
-  if (capacity < view.rows) throw Error(FDB_ERR_INVALID, "indices capacity smaller than the record");
-  std::function<bool(const std::string&)> want = [this](const std::string& n) {
-    for (const ExprNode& e : filter_) if (is_leaf_op(e.op) && e.column == n) return true;
-    return false;
-  };
-  std::unique_ptr<DeviceBatch> b = import_batch(view, device_, &want, stream_);
-  *n_selected = 0;
-  if (b->rows == 0) return;
-  DevBuf d_idx(ctx_, (size_t)b->rows * 4);
-  const int64_t n = select_batch(*b, (uint32_t*)d_idx.p, b->rows);
-  *n_selected = n;
-  if (n) hip_check(hipMemcpy(indices, d_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost), "hipMemcpy(indices)");
-}
-
-void Plan::filter(const ArrowArray* array, const ArrowSchema* schema, ArrowArray* out, ArrowSchema* out_schema, int64_t* n_selected) {
-  if (filter_root_ < 0) throw Error(FDB_ERR_STATE, "plan has no filter");
-  HostRecordView view;
-  view_record(array, schema, &view);
-  std::unique_ptr<DeviceBatch> b = import_batch(view, device_, nullptr, stream_);
-  std::unique_ptr<DeviceBatch> f = filter_batch(*b, n_selected);
-  if (*n_selected == 0) return;  // filter.go:264-266
-  export_batch(*f, out, out_schema);
 }
 
 }  // namespace fdb

@@ -236,12 +236,9 @@ class Plan {
   // The same for a record resident in HBM, results staying in HBM: the compacted record as a new resident batch / the
   // selection vector in a DEVICE buffer of `capacity` ≥ rows entries.
   std::unique_ptr<DeviceBatch> filter_batch(const DeviceBatch& in, int64_t* n_selected);
-  // The same for every record of a scan at once: one launch sequence, two host round trips in total (sizes, NULL counts).
-  std::unique_ptr<DeviceBatch> filter_batch_interp(const DeviceBatch& in, int64_t* n_selected);
-  std::vector<std::unique_ptr<DeviceBatch>> filter_batches(const DeviceBatch* const* in, int n, int64_t* n_selected);
-  struct SelectStall {};  // the one-pass select kernel ran into its poll bound: filter_batches retries through the three-launch path
-  std::vector<std::unique_ptr<DeviceBatch>> filter_batches_impl(const DeviceBatch* const* in, int n, int64_t* n_selected, bool force_two_pass);
   int64_t select_batch(const DeviceBatch& in, uint32_t* d_indices, int64_t capacity);
+  // The same for every record of a scan at once: one launch sequence, two host round trips in total (sizes, NULL counts).
+  std::vector<std::unique_ptr<DeviceBatch>> filter_batches(const DeviceBatch* const* in, int n, int64_t* n_selected);
   const char* draw();                                                  // ≙ Draw
   int64_t num_groups();
   void partial_keys(ArrowArray* out, ArrowSchema* out_schema);
@@ -316,9 +313,19 @@ class Plan {
   // Appends the nodes of `p` to R->args.expr (columns resolved against `b`, types checked); returns the root's index.
   int resolve_projection(const Projection& p, const DeviceBatch& b, Resolved* R);
   void resolve_batch(const DeviceBatch& b, Resolved* R, std::vector<int>* batch_gcols);
-  void resolve_filter_only(const DeviceBatch& b, Resolved* R);  // predicate program + LUTs (staged), nothing else
+  void resolve_predicate(const DeviceBatch& b, int root, Resolved* R);    // fresh arguments + the program of the filter sub-tree at `root` (-1: none)
+  // selection / filter-only (fdb_filter.cpp)
+  void resolve_filter_only(const DeviceBatch& b, int root, Resolved* R);  // predicate program + LUTs (staged), nothing else
   int64_t count_subtree(const DeviceBatch& b, int node);        // rows of `b` selected by the filter sub-tree rooted at `node` (lazy AND)
   int64_t run_flags(const FdbScanArgs& a, uint8_t** d_masks, uint32_t** d_offsets);  // selection bitmap + tile offsets; returns the number selected
+  // The per-record path of filter_batches: interpreting flags kernel, one compaction launch per column.
+  std::unique_ptr<DeviceBatch> filter_batch_interp(const DeviceBatch& in, int64_t* n_selected);
+  struct SelectStall {};  // the one-pass select kernel ran into its poll bound: filter_batches retries through the three-launch path
+  struct FilterRun;       // launch state of filter_batches_impl
+  std::vector<std::unique_ptr<DeviceBatch>> filter_batches_impl(const DeviceBatch* const* in, int n, int64_t* n_selected, bool force_two_pass);
+  // `launch` between two timing events on the plan's stream when `timing` is on; the next sync adds their interval to stat_ms
+  // (`merge`: to stat_merge_ms). Defined in fdb_plan_internal.h.
+  template <class F> void timed(F&& launch, bool merge = false);
   void ensure_layout(const std::vector<uint32_t>& new_caps);
   void collect_timing();
   void fetch_state(std::vector<unsigned long long>* cnt, std::vector<std::vector<unsigned long long>>* acc);

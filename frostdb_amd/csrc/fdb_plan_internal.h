@@ -1,4 +1,4 @@
-// fdb_plan_internal.h — per-record resolution state shared by fdb_plan.cpp and fdb_hash.cpp (not part of any API).
+// fdb_plan_internal.h — per-record resolution state shared by fdb_plan.cpp, fdb_filter.cpp and fdb_hash.cpp (not part of any API).
 #pragma once
 
 #include <algorithm>
@@ -6,15 +6,20 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <memory>
 #include <vector>
 
+#include "fdb_context.h"
 #include "fdb_plan.h"
 
 namespace fdb {
 
-inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr size_t kTailPad = 256;  // bytes readable past every column so tail lanes may over-read
+
+bool is_leaf_op(int32_t op);  // a comparison / regex / contains leaf of a filter expression
 
 struct PhaseTimer {  // FDB_PROFILE=1: per-phase host microseconds on stderr (tuning aid)
   bool on;
@@ -31,7 +36,7 @@ struct PhaseTimer {  // FDB_PROFILE=1: per-phase host microseconds on stderr (tu
 struct Blob {  // LUTs of one batch, shipped with one copy
   std::vector<uint8_t> bytes;
   size_t add(const void* p, size_t n) {
-    const size_t off = align_up_sz(bytes.size(), 16);
+    const size_t off = align_up(bytes.size(), 16);
     bytes.resize(off + std::max<size_t>(n, 1), 0);
     if (n) std::memcpy(bytes.data() + off, p, n);
     return off;
@@ -39,6 +44,43 @@ struct Blob {  // LUTs of one batch, shipped with one copy
 };
 
 struct PendingLut { int kind; int index; size_t blob_off; size_t len_bytes; };  // kind 0: leaf, 1: group col
+
+// LDS plan of a record's LUTs, from `lds_off` on: a LUT of at most 16 KiB is copied into LDS while the LUTs placed there stay within
+// 32 KiB (16-byte aligned), the others are read from global memory (FDB_NO_LDS). `d_blob`: the device copy of the record's blob.
+// Sets lut / lut_lds of the leaves (kind 0) and dense group columns (kind 1); returns the aligned end of the LDS region.
+inline size_t place_luts(const std::vector<PendingLut>& luts, unsigned char* d_blob, size_t lds_off, FdbScanArgs* a) {
+  for (const PendingLut& p : luts) {
+    const bool in_lds = p.len_bytes <= 16384 && lds_off + p.len_bytes <= 32768;
+    uint32_t lds = FDB_NO_LDS;
+    if (in_lds) { lds = (uint32_t)lds_off; lds_off = align_up(lds_off + p.len_bytes, 16); }
+    unsigned char* at = d_blob + p.blob_off;
+    if (p.kind == 0) { a->leaves[p.index].lut = at; a->leaves[p.index].lut_lds = lds; }
+    else { a->gcols[p.index].lut = (const uint32_t*)at; a->gcols[p.index].lut_lds = lds; }
+  }
+  return align_up(lds_off, 16);
+}
+
+// Several tables that feed ONE launch are staged between construction and destruction and shipped with one copy command.
+struct StageScope {
+  Context* c;
+  explicit StageScope(Context* ctx) : c(ctx) { c->defer_staging(true); }
+  ~StageScope() { try { c->defer_staging(false); } catch (...) {} }
+};
+
+// Declared after the results it guards: an error that unwinds past it waits for the stream, so their arenas (and inputs the caller
+// may release) go back to the pool only once no queued kernel uses them.
+struct DrainOnUnwind {
+  hipStream_t s; int n = std::uncaught_exceptions();
+  ~DrainOnUnwind() { if (std::uncaught_exceptions() > n) (void)hipStreamSynchronize(s); }
+};
+
+template <class F>
+void Plan::timed(F&& launch, bool merge) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (timing) { e0 = ctx_->get_event(); e1 = ctx_->get_event(); hip_check(hipEventRecord(e0, stream_), "hipEventRecord"); }
+  launch();
+  if (timing) { hip_check(hipEventRecord(e1, stream_), "hipEventRecord"); (merge ? merge_events_ : pending_events_).emplace_back(e0, e1); }
+}
 
 
 struct GroupRes {
@@ -78,6 +120,20 @@ struct Plan::Resolved {
     if (!(c & 2)) { c |= 2; bytes += b.cols[(size_t)ci].validity_bytes; }
   }
 };
+
+// Records whose LUT sets are byte-identical (the usual case: parts of one table share dictionaries) share one device copy and one
+// class id, so a kernel re-stages LUTs in LDS only when the class changes.
+inline bool same_lut_set(const Plan::Resolved& q, const Plan::Resolved& r) {
+  if (q.blob.bytes != r.blob.bytes || q.luts.size() != r.luts.size()) return false;
+  for (size_t k = 0; k < r.luts.size(); k++)
+    if (q.luts[k].kind != r.luts[k].kind || q.luts[k].index != r.luts[k].index || q.luts[k].blob_off != r.luts[k].blob_off ||
+        q.luts[k].len_bytes != r.luts[k].len_bytes)
+      return false;
+  return true;
+}
+
+// Column slots of the load-hoisting kernel for a record (fdb_plan.cpp); 0 when they do not fit.
+int assign_slots(const DeviceBatch& b, Plan::Resolved& R, int first_layout = 1, bool relaxed = false, bool* interp_ok = nullptr);
 
 
 }  // namespace fdb
