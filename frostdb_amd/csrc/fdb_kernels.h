@@ -795,7 +795,12 @@ struct FdbPqRun {
   uint32_t kind;        // 0 RLE, 1 bit-packed
 };
 // A data page with PLAIN fixed-width values: value ranks [rank_start, next page's rank_start) live at byte_off + 8·(rank − rank_start).
+// In the page table of a dictionary-encoded INT64 / DOUBLE chunk (fdb_launch_pq_decode_dict8) byte_off == FDB_PQ_DICT_PAGE says "these
+// ranks are dictionary indices, look them up through idx_runs[]"; neighbouring pages of that kind share one entry.
 struct FdbPqPlainPage { int64_t rank_start; int64_t byte_off; };
+#define FDB_PQ_DICT_PAGE ((int64_t)-1)
+// Entries of a numeric dictionary the decode kernel keeps in LDS (above it the lookups read the dictionary page in global memory).
+#define FDB_PQ_DICT_LDS_ENTRIES 4096
 // DELTA_BINARY_PACKED (INT64): a page's values are first + prefix sums of (min_delta of the block + bit-packed delta). The host
 // reads the page / block headers only; a miniblock = `vpm` deltas packed at one bit width.
 struct FdbPqDeltaMini { uint64_t bit_off; uint64_t min_delta; uint32_t width; uint32_t _pad; };  // bit_off: of its first delta, in the chunk
@@ -820,6 +825,13 @@ struct FdbSnappyPage { uint64_t src_off; uint64_t dst_off; uint32_t src_len; uin
 hipError_t fdb_launch_snappy_decode(const uint8_t* src, const FdbSnappyPage* pages, int32_t n_pages, uint8_t* dst, uint32_t* status, hipStream_t stream);
 hipError_t fdb_launch_pq_delta(const uint8_t* chunk, const FdbPqDeltaPage* pages, int32_t n_pages, const FdbPqDeltaMini* minis, unsigned long long* dense,
                                hipStream_t stream);
+// Dictionary-encoded INT64 / DOUBLE chunks in one pass: out[r] = dictionary[index of row r] — or the PLAIN value of row r where pages[]
+// says the row's page is PLAIN (a writer's fallback inside the chunk) —, 0 for NULL rows; validity / prefix as for fdb_launch_pq_decode.
+// The dictionary is the n_dict 8-byte values at chunk + dict_off (any byte alignment); n_values = the chunk's non-NULL values. An index
+// ≥ n_dict (or a rank ≥ n_values) writes 0 and sets *flag |= 1: no LDS or global read depends on an unchecked index.
+hipError_t fdb_launch_pq_decode_dict8(const uint8_t* chunk, const uint32_t* validity, const uint32_t* prefix, const FdbPqPlainPage* pages, int32_t n_pages,
+                                      const FdbPqRun* idx_runs, int32_t n_idx_runs, uint64_t dict_off, uint32_t n_dict, int64_t n_values, int64_t n_rows,
+                                      unsigned long long* out, uint32_t* flag, hipStream_t stream);
 // validity[w] = the 32 definition levels (max level 1) of rows 32w … 32w+31, counts[w] = popcount; rows ≥ n_rows are 0.
 hipError_t fdb_launch_pq_validity(const uint8_t* chunk, const FdbPqRun* def_runs, int32_t n_runs, int64_t n_rows, uint32_t* validity, uint32_t* counts,
                                   hipStream_t stream);

@@ -1527,6 +1527,100 @@ __global__ void pq_decode_kernel(const uint8_t* __restrict__ chunk, const uint32
   }
 }
 
+// Dictionary-encoded INT64 / DOUBLE chunks, one pass: index → value without a 4-byte intermediate. A persistent grid takes tiles of
+// 1 024 rows grid-stride; a lane owns 4 consecutive rows (they share one validity word, and their values leave as two 16-byte stores).
+// It finds the page and the index run of its first non-NULL row by binary search and walks forward for the other three; the index
+// windows (or PLAIN values, where the writer fell back inside the chunk) of all four rows are requested before any is consumed, and
+// so are the four dictionary loads of the global-memory variant.
+// LDS_DICT: the workgroup copies the dictionary into LDS once (pq_load64: the page sits at any byte offset). The threshold is
+// FDB_PQ_DICT_LDS_ENTRIES = 4 096 entries = 32 KiB: with that, 4 workgroups of 256 lanes — the 16 waves per CU the launch asks for,
+// which 128 VGPRs per lane allow — still fit in a CU's 160 KiB, and a few thousand entries cover the columns this encoding is chosen
+// for (status codes, periods, bucket bounds, rounded values). Above it the lookups read the dictionary page in global memory, which is
+// hot in the L2 for any dictionary a writer's 1 MiB dictionary-page limit allows.
+// Every index is compared with n_dict BEFORE it addresses anything: a bad one writes 0 and raises *flag (as does a rank beyond the
+// chunk's values, which damaged definition levels could produce).
+template <bool LDS_DICT>
+__global__ __launch_bounds__(256) void pq_decode_dict8_kernel(const uint8_t* __restrict__ chunk, const uint32_t* __restrict__ validity, const uint32_t* __restrict__ prefix,
+                                                              const FdbPqPlainPage* __restrict__ pages, int n_pages, const FdbPqRun* __restrict__ runs, int n_runs,
+                                                              uint64_t dict_off, uint32_t n_dict, int64_t n_values, int64_t n_rows,
+                                                              unsigned long long* __restrict__ out, uint32_t* flag) {
+  extern __shared__ unsigned long long pq_dict_lds[];
+  if (LDS_DICT) {
+    for (uint32_t i = threadIdx.x; i < n_dict; i += blockDim.x) pq_dict_lds[i] = pq_load64(chunk, dict_off + (uint64_t)i * 8u);
+    __syncthreads();
+  }
+  bool bad = false;
+  const int64_t n_tiles = (n_rows + 1023) / 1024;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t r0 = tile * 1024 + (int64_t)threadIdx.x * 4;
+    if (r0 >= n_rows) continue;
+    const int n_here = n_rows - r0 < 4 ? (int)(n_rows - r0) : 4;
+    uint32_t nib = (1u << n_here) - 1u;  // which of the 4 rows hold a value
+    int64_t rank0 = r0;
+    if (validity != nullptr) {  // (r0 is a multiple of 4: the 4 rows' bits sit in one word; bits of rows ≥ n_rows are 0)
+      const uint32_t word = validity[r0 >> 5], b = (uint32_t)(r0 & 31);
+      nib &= word >> b;
+      rank0 = (int64_t)prefix[r0 >> 5] + (int64_t)__popc(word & ((1u << b) - 1u));
+    }
+    // step 1: where each row's value or index is — and its load, issued
+    unsigned long long w[4];   // PLAIN: the value; bit-packed index: the 64-bit window that holds it; RLE index: the index
+    uint32_t sh[4], mask[4];   // index rows: idx = (w >> sh) & mask
+    bool is_idx[4];
+    if (nib != 0u) {
+      int pg = 0;
+      { int lo = 0, hi = n_pages - 1; while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (pages[mid].rank_start <= rank0) lo = mid; else hi = mid - 1; } pg = lo; }
+      int64_t pg_end = pg + 1 < n_pages ? pages[pg + 1].rank_start : n_values;
+      FdbPqPlainPage P = pages[pg];
+      int ri = -1;
+      int64_t run_end = 0;
+      FdbPqRun R{};
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        w[u] = 0; sh[u] = 0; mask[u] = 0; is_idx[u] = false;
+        if (!((nib >> u) & 1u)) continue;
+        const int64_t rank = rank0 + (int64_t)__popc(nib & ((1u << u) - 1u));
+        if (rank >= n_values) { bad = true; continue; }
+        while (rank >= pg_end) { pg++; P = pages[pg]; pg_end = pg + 1 < n_pages ? pages[pg + 1].rank_start : n_values; }  // (rank < n_values: ends at the last page at the latest)
+        if (P.byte_off != FDB_PQ_DICT_PAGE) { w[u] = pq_load64(chunk, (uint64_t)P.byte_off + (uint64_t)(rank - P.rank_start) * 8u); continue; }
+        if (ri < 0) { ri = pq_find_run(runs, n_runs, rank); R = runs[ri]; run_end = ri + 1 < n_runs ? runs[ri + 1].start : n_values; }
+        while (rank >= run_end) { ri++; R = runs[ri]; run_end = ri + 1 < n_runs ? runs[ri + 1].start : n_values; }
+        is_idx[u] = true;
+        if (R.kind == 0u) { w[u] = R.payload; mask[u] = 0xFFFFFFFFu; }
+        else {
+          const uint64_t bit = R.payload + (uint64_t)(rank - R.start) * R.bit_width;
+          w[u] = pq_load64(chunk, bit >> 3);
+          sh[u] = (uint32_t)(bit & 7u);
+          mask[u] = R.bit_width >= 32u ? 0xFFFFFFFFu : (1u << R.bit_width) - 1u;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; u++) { w[u] = 0; sh[u] = 0; mask[u] = 0; is_idx[u] = false; }
+    }
+    // step 2: indices checked, dictionary values requested (LDS or global), then consumed
+    unsigned long long v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      v[u] = w[u];
+      if (is_idx[u]) {
+        const uint32_t idx = (uint32_t)(w[u] >> sh[u]) & mask[u];
+        v[u] = 0;
+        if (idx >= n_dict) bad = true;
+        else v[u] = LDS_DICT ? pq_dict_lds[idx] : pq_load64(chunk, dict_off + (uint64_t)idx * 8u);
+      }
+    }
+    if (n_here == 4) {
+      ulonglong2* o = reinterpret_cast<ulonglong2*>(out + r0);  // (columns start 256-byte aligned, r0 is a multiple of 4)
+      o[0] = make_ulonglong2(v[0], v[1]);
+      o[1] = make_ulonglong2(v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; u++) if (u < n_here) out[r0 + u] = v[u];
+    }
+  }
+  if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
 // One workgroup per page (grid-stride), 1 024 values per step: 4 consecutive values per thread.
 __global__ __launch_bounds__(256) void pq_delta_kernel(const uint8_t* __restrict__ chunk, const FdbPqDeltaPage* __restrict__ pages, int n_pages,
                                                        const FdbPqDeltaMini* __restrict__ minis, unsigned long long* __restrict__ dense) {
@@ -2433,6 +2527,22 @@ hipError_t fdb_launch_pq_decode(int kind, const uint8_t* chunk, const uint32_t* 
   if (kind == 0) hipLaunchKernelGGL(pq_decode_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, stream, chunk, validity, prefix, pages, n_pages, idx_runs, n_idx_runs, n_rows, out);
   else if (kind == 2) hipLaunchKernelGGL(pq_decode_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, chunk, validity, prefix, pages, n_pages, idx_runs, n_idx_runs, n_rows, out);
   else hipLaunchKernelGGL(pq_decode_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, chunk, validity, prefix, pages, n_pages, idx_runs, n_idx_runs, n_rows, out);
+  return hipGetLastError();
+}
+
+hipError_t fdb_launch_pq_decode_dict8(const uint8_t* chunk, const uint32_t* validity, const uint32_t* prefix, const FdbPqPlainPage* pages, int32_t n_pages,
+                                      const FdbPqRun* idx_runs, int32_t n_idx_runs, uint64_t dict_off, uint32_t n_dict, int64_t n_values, int64_t n_rows,
+                                      unsigned long long* out, uint32_t* flag, hipStream_t stream) {
+  if (n_rows == 0) return hipSuccess;
+  if (n_pages <= 0) return hipErrorInvalidValue;
+  int64_t blocks = (n_rows + 1023) / 1024;
+  if (blocks > 1024) blocks = 1024;  // persistent: 4 workgroups on each of 256 CUs
+  if (n_dict <= (uint32_t)FDB_PQ_DICT_LDS_ENTRIES)
+    hipLaunchKernelGGL(pq_decode_dict8_kernel<true>, dim3((unsigned)blocks), dim3(256), (size_t)n_dict * 8, stream, chunk, validity, prefix, pages, n_pages, idx_runs, n_idx_runs,
+                       dict_off, n_dict, n_values, n_rows, out, flag);
+  else
+    hipLaunchKernelGGL(pq_decode_dict8_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, chunk, validity, prefix, pages, n_pages, idx_runs, n_idx_runs,
+                       dict_off, n_dict, n_values, n_rows, out, flag);
   return hipGetLastError();
 }
 

@@ -10,11 +10,14 @@
 //
 // Covered (what pqarrow/convert/convert.go:28-102 maps to Arrow — UTF8 / BYTE_ARRAY, Int(64) signed and unsigned, BOOLEAN, DOUBLE — in the
 // encodings and codecs a FrostDB schema can ask for, schema.proto:54-86): BOOLEAN PLAIN / RLE; INT64 PLAIN / DELTA_BINARY_PACKED; DOUBLE PLAIN;
-// BYTE_ARRAY dictionary-encoded, PLAIN, DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY; UNCOMPRESSED, SNAPPY, GZIP, BROTLI, ZSTD, LZ4(_RAW).
-// Repeated (list) columns are refused. First slice, as it was built (what FrostDB's default layouts produce, dynparquet/schema.go:508-560): flat schemas; INT64 / DOUBLE columns with
-// PLAIN data pages; BYTE_ARRAY columns with a PLAIN dictionary page + RLE_DICTIONARY data pages (→ dictionary<uint32, binary>,
-// pqarrow/convert/convert.go:64-70); required or optional (max definition level 1); data pages V1 and V2; INT64 also DELTA_BINARY_PACKED (the reference's default for struct-tag schemas, internal/records/record_builder.go:146-148); pages UNCOMPRESSED, or SNAPPY / GZIP / ZSTD / LZ4_RAW (inflated on the host while the page headers are walked).
-// Anything else (DELTA_* encodings, compressed pages, dictionary fallback to PLAIN, nested columns) is FDB_ERR_UNSUPPORTED.
+// INT64 / DOUBLE dictionary-encoded (ENCODING_RLE_DICTIONARY applies to a column of any type, dynparquet/schema.go:531-560, and stock
+// writers choose it by default): the dictionary page's values stay in the chunk's bytes and the device resolves the indices
+// (pq_decode_dict8_kernel), PLAIN pages behind them — the writer's fallback inside a chunk — included;
+// BYTE_ARRAY dictionary-encoded, PLAIN (also as a fallback inside a dictionary-encoded chunk), DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY;
+// required or optional (max definition level 1); data pages V1 and V2; UNCOMPRESSED, SNAPPY, GZIP, BROTLI, ZSTD, LZ4(_RAW), inflated
+// on the host while the page headers are walked (SNAPPY pages of literals on the device).
+// FDB_ERR_UNSUPPORTED: repeated (list) and nested columns, INT32 / FLOAT and the other physical types, DELTA_BINARY_PACKED pages mixed
+// with other encodings in one chunk, a dictionary page on a BOOLEAN chunk.
 #include <dlfcn.h>
 #include <zlib.h>
 
@@ -557,7 +560,12 @@ struct ParsedChunk {
   std::shared_ptr<HostDict> dict;          // BYTE_ARRAY columns
   HostTable<FdbPqRun> def_runs;            // optional columns: one entry per run, row-numbered
   HostTable<FdbPqRun> idx_runs;            // dictionary-encoded columns: rank-numbered
-  std::vector<FdbPqPlainPage> plain_pages; // PLAIN fixed-width columns
+  std::vector<FdbPqPlainPage> plain_pages; // PLAIN fixed-width columns; with dict8_pages also the dictionary-index pages (FDB_PQ_DICT_PAGE)
+  // INT64 / DOUBLE columns with a dictionary page: its values stay where they are — in the chunk, or in the image when the chunk is
+  // compressed — and the device looks them up (pq_decode_dict8_kernel); dict8_off is relative to what goes to HBM
+  bool dict8_pages = false;                // some data page holds dictionary indices
+  uint64_t dict8_off = 0;
+  uint32_t dict8_n = 0;
   std::vector<FdbPqDeltaPage> delta_pages; // DELTA_BINARY_PACKED INT64 columns
   HostTable<FdbPqDeltaMini> delta_minis;
   int64_t non_null = 0;
@@ -593,11 +601,20 @@ void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* out, st
   // ($FDB_PARQUET_HOST_INFLATE: every page on the host, as before round 4)
   static const bool device_inflate = std::getenv("FDB_PARQUET_HOST_INFLATE") == nullptr;
   std::vector<Pg> pages;
+  bool dict_seen = false;
   while (w.p < w.end && values < n_rows) {
     const PageHeader h = read_page_header(w);
     if (h.compressed < 0 || h.uncompressed < 0 || (size_t)(w.end - w.p) < (size_t)h.compressed) throw Error(FDB_ERR_INVALID, "parquet: page runs past the end of the column chunk");
     const uint8_t* raw = w.p;
     w.p += (size_t)h.compressed;
+    if (h.type == PQ_DICTIONARY_PAGE && is_fixed8 && c.codec != CODEC_NONE) {
+      // a numeric dictionary is looked up on the device: its page is inflated into the image, in page order, like a data page (host inflate)
+      if (dict_seen) throw Error(FDB_ERR_INVALID, "parquet: two dictionary pages in one column chunk");
+      dict_seen = true;
+      pages.push_back(Pg{raw, (size_t)h.compressed, 0, (size_t)h.uncompressed, true, false, false});
+      need += (size_t)h.uncompressed + 8;
+      continue;
+    }
     if (h.type != PQ_DATA_PAGE && h.type != PQ_DATA_PAGE_V2) continue;
     // (a damaged header must not size the image: no page holds more values than the row group has rows)
     if (h.num_values < 0 || values + h.num_values > n_rows) throw Error(FDB_ERR_INVALID, "parquet: pages hold more values than the row group has rows");
@@ -673,9 +690,23 @@ void parse_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* outp) 
     const uint8_t* raw = t.p;  // the page's bytes in the file
     t.p += (size_t)h.compressed;
     if (h.type == PQ_DICTIONARY_PAGE) {
-      if (!is_bytes) throw Error(FDB_ERR_UNSUPPORTED, "parquet: dictionary-encoded numeric columns are not supported on the device path");
+      if (is_bool) throw Error(FDB_ERR_UNSUPPORTED, "parquet: dictionary-encoded numeric columns are not supported on the device path");
       if (h.encoding != ENC_PLAIN && h.encoding != ENC_PLAIN_DICTIONARY) throw Error(FDB_ERR_UNSUPPORTED, "parquet: dictionary page encoding");
       if (have_dict) throw Error(FDB_ERR_INVALID, "parquet: two dictionary pages in one column chunk");
+      if (is_fixed8) {
+        // 8-byte values: not copied here — where they are (in the chunk, or in the image where plan_chunk had the page inflated) and how many
+        size_t off = (size_t)(raw - c.data), len = (size_t)h.compressed;
+        if (use_image) {
+          off = image_at; len = (size_t)h.uncompressed;
+          image_at += len + 8;
+          if (image_at > out.image.cap) throw Error(FDB_ERR_INVALID, "parquet: dictionary page truncated");
+        }
+        if (h.num_values < 0 || (size_t)h.num_values > len / 8) throw Error(FDB_ERR_INVALID, "parquet: dictionary page truncated");
+        out.dict8_off = (uint64_t)off;
+        out.dict8_n = (uint32_t)h.num_values;
+        have_dict = true;
+        continue;
+      }
       std::vector<uint8_t> dict_tmp;
       const uint8_t* body = raw;
       size_t body_len = (size_t)h.compressed;
@@ -768,8 +799,23 @@ void parse_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* outp) 
           if (out.delta_minis.size() > 0x7FFFFFF0u) throw Error(FDB_ERR_UNSUPPORTED, "parquet: too many DELTA_BINARY_PACKED miniblocks");
           out.delta_pages.push_back(P);
         }
+      } else if (h.encoding == ENC_RLE_DICTIONARY || h.encoding == ENC_PLAIN_DICTIONARY) {
+        // indices into the chunk's dictionary page: run headers here, the lookups on the device. The page table says which ranks are
+        // indices and which are PLAIN values (a writer that gives up on its dictionary goes on with PLAIN pages in the same chunk).
+        if (!have_dict) throw Error(FDB_ERR_INVALID, "parquet: dictionary-encoded page without a dictionary page");
+        if (!out.delta_pages.empty()) throw Error(FDB_ERR_UNSUPPORTED, "parquet: PLAIN and DELTA_BINARY_PACKED pages in one column chunk");
+        if (page_non_null > 0) {
+          if (vlen < 1) throw Error(FDB_ERR_INVALID, "parquet: dictionary-index page without a bit width");
+          const int bw = base[voff];
+          if (bw > 32) throw Error(FDB_ERR_INVALID, "parquet: dictionary index bit width > 32");
+          out.max_index_bits = std::max<uint32_t>(out.max_index_bits, (uint32_t)bw);
+          if (bw == 0) out.idx_runs.push_back(FdbPqRun{rank_done, 0ull, 0u, 0u});  // every index is 0
+          else scan_runs(base, voff + 1, vlen - 1, bw, page_non_null, rank_done, &out.idx_runs, nullptr);
+        }
+        out.dict8_pages = true;
+        if (out.plain_pages.empty() || out.plain_pages.back().byte_off != FDB_PQ_DICT_PAGE) out.plain_pages.push_back(FdbPqPlainPage{rank_done, FDB_PQ_DICT_PAGE});
       } else {
-        if (h.encoding != ENC_PLAIN) throw Error(FDB_ERR_UNSUPPORTED, "parquet: INT64 pages must be PLAIN or DELTA_BINARY_PACKED, DOUBLE pages PLAIN");
+        if (h.encoding != ENC_PLAIN) throw Error(FDB_ERR_UNSUPPORTED, "parquet: INT64 pages must be PLAIN, (PLAIN_ / RLE_)DICTIONARY or DELTA_BINARY_PACKED, DOUBLE pages PLAIN or (PLAIN_ / RLE_)DICTIONARY");
         if (!out.delta_pages.empty()) throw Error(FDB_ERR_UNSUPPORTED, "parquet: PLAIN and DELTA_BINARY_PACKED pages in one column chunk");
         if ((size_t)page_non_null * 8 > vlen) throw Error(FDB_ERR_INVALID, "parquet: PLAIN page shorter than its values");
         out.plain_pages.push_back(FdbPqPlainPage{rank_done, (int64_t)voff});
@@ -1208,6 +1254,21 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
             const FdbPqPlainPage* d_one = (const FdbPqPlainPage*)to_device(&kWhole, sizeof(kWhole));
             fence();
             hip_check(fdb_launch_pq_decode(0, (const uint8_t*)dense, d_valid, d_prefix, d_one, 1, nullptr, 0, n_rows, d_out, stream), "parquet decode");
+          }
+        } else if (P.dict8_pages) {
+          // dictionary indices (and the PLAIN pages of a fallback) → 8-byte values in one pass; every index is checked against the
+          // dictionary's length there, the verdict comes back in the call's flag words like a BYTE_ARRAY column's
+          if (!c.optional && P.non_null != n_rows) throw Error(FDB_ERR_INVALID, "parquet: required column with fewer values than rows");
+          if (P.non_null == 0) hip_check(hipMemsetAsync(d_out, 0, (size_t)n_rows * 8, stream), "hipMemsetAsync");
+          else {
+            if (P.idx_runs.size() > 0x7FFFFFF0u || P.plain_pages.size() > 0x7FFFFFF0u) throw Error(FDB_ERR_UNSUPPORTED, "parquet: too many runs in a column chunk");
+            const FdbPqPlainPage* d_pages = (const FdbPqPlainPage*)to_device(P.plain_pages.data(), P.plain_pages.size() * sizeof(FdbPqPlainPage));
+            const FdbPqRun* d_idx = (const FdbPqRun*)to_device(P.idx_runs.data(), P.idx_runs.size() * sizeof(FdbPqRun), P.idx_runs.pinned());
+            R.flag_at[(size_t)i] = n_flags;
+            fence();
+            hip_check(fdb_launch_pq_decode_dict8(d_chunk, d_valid, d_prefix, d_pages, (int32_t)P.plain_pages.size(), d_idx, (int32_t)P.idx_runs.size(), P.dict8_off, P.dict8_n,
+                                                 P.non_null, n_rows, (unsigned long long*)d_out, d_flags + n_flags, stream), "parquet dictionary decode");
+            n_flags++;
           }
         } else {
           const FdbPqPlainPage* d_pages = (const FdbPqPlainPage*)to_device(P.plain_pages.data(), P.plain_pages.size() * sizeof(FdbPqPlainPage));

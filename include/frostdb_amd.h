@@ -440,7 +440,10 @@ FDB_API int fdb_batch_export(const fdb_batch* batch, struct ArrowArray* out, str
  * page and the headers of RLE / bit-packed runs; definition levels → validity bitmaps, value ranks and the per-row dictionary
  * indices / values are computed in HBM. Covered — the types pqarrow/convert/convert.go:28-102 maps to Arrow, in the encodings and
  * codecs a FrostDB schema can ask for (schema.proto:54-86): flat schemas; BOOLEAN (PLAIN, RLE → bool); INT64 (PLAIN,
- * DELTA_BINARY_PACKED → int64, or uint64 for the logical type Int(64, unsigned)); DOUBLE (PLAIN); BYTE_ARRAY with a dictionary page +
+ * DELTA_BINARY_PACKED → int64, or uint64 for the logical type Int(64, unsigned)); DOUBLE (PLAIN); INT64 / DOUBLE also with a
+ * dictionary page + RLE_DICTIONARY / PLAIN_DICTIONARY data pages, PLAIN pages behind them included (a writer's dictionary fallback
+ * inside a chunk) — the dictionary is resolved on the device, the column is 8 bytes per row like any other, and an index beyond the
+ * dictionary is FDB_ERR_INVALID; BYTE_ARRAY with a dictionary page +
  * RLE_DICTIONARY data pages and / or PLAIN, DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY data pages (their values are dictionary-encoded
  * on the host) (→ dictionary<uint32, binary>, convert.go:64-70; utf8 = 1 → dictionary<uint32, utf8>); required or optional; data
  * pages V1 / V2; codecs as listed at `codec`. Repeated (list) columns and everything else: FDB_ERR_UNSUPPORTED (the caller falls

@@ -50,6 +50,9 @@ variants = [dict(), dict(compression="SNAPPY"), dict(compression="GZIP"), dict(c
             dict(use_dictionary=["labels.a", "labels.b"], column_encoding={"ts": "DELTA_BINARY_PACKED", "opt": "DELTA_BINARY_PACKED"}),
             dict(use_dictionary=False), dict(use_dictionary=False, compression="SNAPPY", data_page_version="2.0"),
             dict(data_page_version="2.0", compression="ZSTD"), dict(compression="BROTLI"),
+            # dictionary-encoded INT64 / DOUBLE chunks (every stock writer's default): the dictionary page stays in the chunk / image for the
+            # device; a small dictionary limit makes the writer fall back to PLAIN pages inside the chunk
+            dict(use_dictionary=True), dict(use_dictionary=True, dictionary_pagesize_limit=1024), dict(use_dictionary=True, compression="SNAPPY", data_page_version="2.0"),
             dict(use_dictionary=False, column_encoding={"labels.a": "DELTA_BYTE_ARRAY", "labels.b": "DELTA_LENGTH_BYTE_ARRAY", "ts": "DELTA_BINARY_PACKED"}),
             dict(use_dictionary=False, column_encoding={"labels.a": "DELTA_LENGTH_BYTE_ARRAY", "labels.b": "DELTA_BYTE_ARRAY"}, compression="SNAPPY", data_page_version="2.0")]
 # pages of literals, big enough for the device's Snappy decoder (fdb_parquet.cpp plan_chunk: ≥ 256 KiB, compressed ≥ 0.9 × plain): the

@@ -15,25 +15,74 @@ rows, rg_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 20_000_000, 5_000_000
 rec = synth.prometheus_chunk(0, 0, rows)
 t = pa.Table.from_batches([rec])
 t = t.set_column(0, "labels.code", t.column(0).cast(pa.binary())).set_column(1, "labels.path", t.column(1).cast(pa.binary()))
-variant = os.environ.get("PQ_VARIANT", "plain")  # "plain": UNCOMPRESSED, PLAIN int64; "delta_snappy": timestamp DELTA_BINARY_PACKED, pages SNAPPY
+variant = os.environ.get("PQ_VARIANT", "plain")  # "plain": UNCOMPRESSED, PLAIN int64; "delta_snappy": timestamp DELTA_BINARY_PACKED, pages SNAPPY; "numeric_dict": below
 kw = {}
 if variant == "delta_snappy":
     kw = dict(compression="SNAPPY", column_encoding={"timestamp": "DELTA_BINARY_PACKED"}, use_dictionary=["labels.code", "labels.path"])
-data = write_parquet(t, row_group_size=rg_rows, data_page_size=1 << 20, **kw)
-n_rg = pq.ParquetFile(io.BytesIO(data)).metadata.num_row_groups
-groups = [row_group_chunks(data, g) for g in range(n_rg)]
-# the file's bytes in PINNED host memory (what a host that reads parts for the GPU would read into); chunks are (address, length)
 import torch
-pinned = torch.empty(len(data), dtype=torch.uint8, pin_memory=True)
-pinned.numpy()[:] = np.frombuffer(data, dtype=np.uint8)
-def _pin(ch):
-    out = []
-    for nm, ty, opt, u8, b, cd in ch:
-        off = data.find(b[:64]) if len(b) >= 64 else data.find(b)
-        assert data[off:off + len(b)] == b
-        out.append((nm, ty, opt, u8, (pinned.data_ptr() + off, len(b)), cd))
-    return out
-groups = [(_pin(ch), n) for ch, n in groups]
+def pinned_groups(data):
+    """the file's bytes in PINNED host memory (what a host that reads parts for the GPU would read into); chunks are (address, length)"""
+    groups = [row_group_chunks(data, g) for g in range(pq.ParquetFile(io.BytesIO(data)).metadata.num_row_groups)]
+    pinned = torch.empty(len(data), dtype=torch.uint8, pin_memory=True)
+    pinned.numpy()[:] = np.frombuffer(data, dtype=np.uint8)
+    def _pin(ch):
+        out = []
+        for nm, ty, opt, u8, b, cd in ch:
+            off = data.find(b[:64]) if len(b) >= 64 else data.find(b)
+            if data[off:off + len(b)] != b:  # (a prefix that also occurs earlier, e.g. equal dictionary pages: search for the whole chunk)
+                off = data.find(b)
+            assert data[off:off + len(b)] == b
+            out.append((nm, ty, opt, u8, (pinned.data_ptr() + off, len(b)), cd))
+        return out
+    return [(_pin(ch), n) for ch, n in groups], pinned
+
+if variant == "numeric_dict":
+    # Dictionary-encoded numeric columns against their PLAIN twins: `value` rounded to one decimal (a few thousand distinct values) and
+    # an int64 `status` of ≈ 50 values, the same table written twice. One process, the two files decoded alternately (boxes differ by
+    # several per cent, so the A/B is inside one call), median of $PQ_PASSES (default 31) passes each; a pass = file bytes → resident
+    # batches (one fdb_batches_from_parquet call) → released. One JSON line per file and one with the ratio.
+    rng = np.random.default_rng(1)
+    status = pa.array((100 + rng.integers(0, 50, rows) * 10).astype(np.int64))
+    t = t.set_column(t.schema.get_field_index("value"), "value", pa.array(np.round(t.column("value").to_numpy(), 1))).append_column("status", status)
+    passes = int(os.environ.get("PQ_PASSES", "31"))
+    files = {"numeric_dict": write_parquet(t, row_group_size=rg_rows, data_page_size=1 << 20, use_dictionary=True),
+             "numeric_plain": write_parquet(t, row_group_size=rg_rows, data_page_size=1 << 20)}
+    md = pq.ParquetFile(io.BytesIO(files["numeric_dict"])).metadata.row_group(0)
+    assert all(md.column(j).has_dictionary_page for j in range(md.num_columns) if md.column(j).path_in_schema in ("value", "status"))
+    loaded = {k: pinned_groups(v) for k, v in files.items()}
+    def decode(k):
+        keep = pp.ResidentBatch.from_parquet_many(loaded[k][0])
+        for b in keep: b.close()
+    # the two files decode to the same columns
+    for g in range(len(loaded["numeric_dict"][0])):
+        a, b = (pp.ResidentBatch.from_parquet(*loaded[k][0][g]) for k in ("numeric_dict", "numeric_plain"))
+        ta, tb = a.to_arrow(), b.to_arrow()
+        for nm in ("value", "status", "timestamp"):
+            assert ta.column(nm).equals(tb.column(nm)), nm
+        a.close(); b.close()
+    times = {k: [] for k in files}
+    stats = {k: {"host_ms": 0.0, "device_ms": 0.0} for k in files}
+    for k in files: decode(k); decode(k)  # warm-up
+    for _ in range(passes):
+        for k in files:
+            s0 = pp.parquet_stats(); t0 = time.perf_counter(); decode(k); dt = time.perf_counter() - t0; s1 = pp.parquet_stats()
+            times[k].append(dt)
+            for f in stats[k]: stats[k][f] += s1[f] - s0[f]
+    out = {}
+    for k in files:
+        ts = sorted(times[k]); med = ts[len(ts) // 2]
+        out[k] = {"variant": k, "rows": rows, "row_groups": len(loaded[k][0]), "parquet_bytes": len(files[k]), "passes": passes, "median_s_per_pass": med, "min_s": ts[0],
+                  "p90_s": ts[int(len(ts) * 0.9)], "rows_per_s": rows / med, "parquet_GB_per_s": len(files[k]) / med / 1e9,
+                  "host_ms_per_pass": stats[k]["host_ms"] / passes, "device_ms_per_pass": stats[k]["device_ms"] / passes}
+        print(json.dumps(out[k]))
+    print(json.dumps({"metric": "decode time, dictionary-encoded numeric file / PLAIN numeric file (medians, alternating passes in one process)",
+                      "ratio": out["numeric_dict"]["median_s_per_pass"] / out["numeric_plain"]["median_s_per_pass"],
+                      "bytes_ratio": len(files["numeric_dict"]) / len(files["numeric_plain"])}))
+    sys.exit(0)
+
+data = write_parquet(t, row_group_size=rg_rows, data_page_size=1 << 20, **kw)
+groups, pinned = pinned_groups(data)
+n_rg = len(groups)
 q = (Col("labels.code") == "200", [Sum(Col("value"))], [Col("labels.path")])
 
 def run_device():
