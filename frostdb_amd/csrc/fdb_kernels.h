@@ -823,6 +823,18 @@ struct FdbPqDeltaPage {
 // input, 3 output overrun, 4 bad offset, 5 output short of the announced length, 6 a copy from further back than the ring holds). fdb_batch_from_parquet inflates pages of literals with it; match-heavy pages stay on the host threads.
 struct FdbSnappyPage { uint64_t src_off; uint64_t dst_off; uint32_t src_len; uint32_t dst_len; };
 hipError_t fdb_launch_snappy_decode(const uint8_t* src, const FdbSnappyPage* pages, int32_t n_pages, uint8_t* dst, uint32_t* status, hipStream_t stream);
+// LZ4 block format (lz4_Block_format.md: no frame, no length preamble — a page's output length comes from its table entry) → bytes, on
+// the device, in the shape of the Snappy decoder above: one wave per page, tokens parsed out of an LDS window of the stream, all 64
+// lanes moving a sequence's literals and its match, the same 64 KiB output ring leaving for HBM in 16 KiB segments. What differs is the
+// format: a sequence = token (literal length << 4 | match length − 4), either length extended by bytes that add up to and including the
+// first one ≠ 255, the literals, a 2-byte offset; the last sequence ends behind its literals. A page of literals is ONE sequence with
+// ≈ 4 100 extension bytes per MiB: they are consumed 64 at a time (a ballot over `byte != 255`), not in a lane-serial loop. Matches
+// have no upper length: they are copied 64 bytes at a time, byte i of a chunk from the byte `offset` before it (i mod offset for a
+// pattern shorter than the chunk). status[page] as above, without 1: 2 truncated input, 3 output overrun, 4 bad offset (0, or before the
+// page's first byte), 5 output short of the announced length, 6 a match from further back than the ring holds (offset > 65 472: legal
+// LZ4 — offsets go up to 65 535 —, fdb_parquet.cpp leaves such pages to the host).
+typedef FdbSnappyPage FdbLz4Page;
+hipError_t fdb_launch_lz4_decode(const uint8_t* src, const FdbLz4Page* pages, int32_t n_pages, uint8_t* dst, uint32_t* status, hipStream_t stream);
 hipError_t fdb_launch_pq_delta(const uint8_t* chunk, const FdbPqDeltaPage* pages, int32_t n_pages, const FdbPqDeltaMini* minis, unsigned long long* dense,
                                hipStream_t stream);
 // Dictionary-encoded INT64 / DOUBLE chunks in one pass: out[r] = dictionary[index of row r] — or the PLAIN value of row r where pages[]

@@ -15,7 +15,8 @@
 // (pq_decode_dict8_kernel), PLAIN pages behind them — the writer's fallback inside a chunk — included;
 // BYTE_ARRAY dictionary-encoded, PLAIN (also as a fallback inside a dictionary-encoded chunk), DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY;
 // required or optional (max definition level 1); data pages V1 and V2; UNCOMPRESSED, SNAPPY, GZIP, BROTLI, ZSTD, LZ4(_RAW), inflated
-// on the host while the page headers are walked (SNAPPY pages of literals on the device).
+// on the host while the page headers are walked (SNAPPY and LZ4_RAW pages of literals on the device: snappy_decode_kernel, lz4_decode_kernel).
+// LZ4 pages do not depend on liblz4: where dlopen does not find it, the built-in block decoder below (lz4_raw) inflates them.
 // FDB_ERR_UNSUPPORTED: repeated (list) and nested columns, INT32 / FLOAT and the other physical types, DELTA_BINARY_PACKED pages mixed
 // with other encodings in one chunk, a dictionary page on a BOOLEAN chunk.
 #include <dlfcn.h>
@@ -380,12 +381,93 @@ bool snappy_device_ok(const uint8_t* src, size_t n) {
   return true;
 }
 
+// The LZ4 block format (lz4_Block_format.md), built in: a sequence = token (literal length << 4 | match length − 4), either length
+// extended by bytes that add up to and including the first one ≠ 255, the literals, a 2-byte little-endian offset (1 … 65 535); the
+// last sequence ends behind its literals. No frame and no length preamble: `cap` is the page's announced size. Decodes until `want`
+// bytes exist (want < cap: a prefix, nothing is written at or behind dst + want) or, with want == cap, the whole block, which must
+// then fill dst exactly. Accepts what LZ4_decompress_safe accepts (and blocks that end in a match, which that one refuses).
+// Returns 0, or what failed first, in lz4_decode_kernel's codes and order: 2 truncated input, 3 output overrun, 4 bad offset, 5 output short.
+uint32_t lz4_block(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t want) {
+  if (want > cap) return 3;
+  const bool whole = want == cap;
+  size_t ip = 0, op = 0;
+  auto extend = [&](size_t* len) {
+    uint8_t b;
+    do { if (ip >= n) return false; b = src[ip++]; *len += b; } while (b == 255);
+    return true;
+  };
+  while (ip < n) {
+    const uint8_t token = src[ip++];
+    size_t ll = token >> 4, ml = token & 15;
+    if (ll == 15 && !extend(&ll)) return 2;
+    if (ll > n - ip) return 2;
+    if (ll > cap - op) return 3;
+    if (op < want) std::memcpy(dst + op, src + ip, std::min(ll, want - op));
+    ip += ll; op += ll;
+    if (!whole && op >= want) return 0;
+    if (ip == n) break;
+    if (n - ip < 2) return 2;
+    const size_t off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8);
+    ip += 2;
+    if (ml == 15 && !extend(&ml)) return 2;
+    ml += 4;
+    if (off == 0 || off > op) return 4;
+    if (ml > cap - op) return 3;
+    const size_t m = op < want ? std::min(ml, want - op) : 0;
+    if (off >= m) std::memcpy(dst + op, dst + op - off, m);  // disjoint
+    else if (off >= 8) { for (size_t i = 0; i < m; i += 8) std::memcpy(dst + op + i, dst + op - off + i, std::min<size_t>(8, m - i)); }  // a pattern of ≥ 8 bytes: 8 at a time
+    else for (size_t i = 0; i < m; i++) dst[op + i] = dst[op - off + i];  // short pattern repeated: byte by byte
+    op += ml;
+    if (!whole && op >= want) return 0;
+  }
+  return (whole ? op == cap : op >= want) ? 0u : 5u;
+}
+bool lz4_raw(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) { return lz4_block(src, n, dst, cap, cap) == 0; }
+// The first `want` bytes of an LZ4 page (the definition levels at the head of a V1 page whose values are inflated on the device).
+bool lz4_prefix(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t want) { return lz4_block(src, n, dst, cap, want) == 0; }
+
+// May the device's decoder take this LZ4 page? Like snappy_device_ok: the token walk only, "no" for a match from further back than the
+// ring keeps (offset > 65 472, the Snappy kernel's bound: the two share ring and segment sizes; LZ4 offsets go up to 65 535, so such
+// pages are legal and the host inflates them) and for a malformed stream (the host's inflate then reports it).
+bool lz4_device_ok(const uint8_t* src, size_t n) {
+  size_t ip = 0;
+  auto extend = [&](size_t* len) {
+    uint8_t b;
+    do { if (ip >= n) return false; b = src[ip++]; *len += b; } while (b == 255);
+    return true;
+  };
+  while (ip < n) {
+    const uint8_t token = src[ip++];
+    size_t ll = token >> 4, ml = token & 15;
+    if (ll == 15 && !extend(&ll)) return false;
+    if (ll > n - ip) return false;
+    ip += ll;
+    if (ip == n) break;
+    if (n - ip < 2) return false;
+    const size_t off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8);
+    ip += 2;
+    if (ml == 15 && !extend(&ml)) return false;
+    if (off == 0 || off > 65472) return false;
+  }
+  return true;
+}
+
 typedef int (*lz4_fn)(const char*, char*, int, int);
 typedef size_t (*zstd_fn)(void*, size_t, const void*, size_t);
 typedef unsigned (*zstd_err_fn)(size_t);
+// liblz4's decoder where the host has it ($FDB_PARQUET_BUILTIN_LZ4: as if it had not), lz4_raw above where it has not
 lz4_fn lz4_decompress() {
-  static lz4_fn f = [] { void* h = dlopen("liblz4.so.1", RTLD_NOW | RTLD_LOCAL); return h ? (lz4_fn)dlsym(h, "LZ4_decompress_safe") : (lz4_fn) nullptr; }();
+  static lz4_fn f = [] {
+    if (std::getenv("FDB_PARQUET_BUILTIN_LZ4") != nullptr) return (lz4_fn) nullptr;
+    void* h = dlopen("liblz4.so.1", RTLD_NOW | RTLD_LOCAL);
+    return h ? (lz4_fn)dlsym(h, "LZ4_decompress_safe") : (lz4_fn) nullptr;
+  }();
   return f;
+}
+bool lz4_inflate(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
+  lz4_fn f = lz4_decompress();
+  if (f != nullptr && n <= (size_t)INT32_MAX && cap <= (size_t)INT32_MAX) return f((const char*)src, (char*)dst, (int)n, (int)cap) == (int)cap;
+  return lz4_raw(src, n, dst, cap);
 }
 std::pair<zstd_fn, zstd_err_fn> zstd_decompress() {
   static std::pair<zstd_fn, zstd_err_fn> f = [] {
@@ -434,16 +516,14 @@ void inflate_page(int codec, const uint8_t* src, size_t n, uint8_t* dst, size_t 
       return;
     }
     case CODEC_LZ4_RAW: case CODEC_LZ4_HADOOP: {
-      lz4_fn f = lz4_decompress();
-      if (f == nullptr) throw Error(FDB_ERR_UNSUPPORTED, "parquet: LZ4 pages need liblz4.so.1 on this host");
-      if (f((const char*)src, (char*)dst, (int)n, (int)cap) == (int)cap) return;
+      if (lz4_inflate(src, n, dst, cap)) return;
       // the deprecated "LZ4" codec may carry Hadoop's framing: [uncompressed size BE32][compressed size BE32][block] …
       size_t ip = 0, op = 0;
       while (ip + 8 <= n && op < cap) {
         const size_t ul = ((size_t)src[ip] << 24) | ((size_t)src[ip + 1] << 16) | ((size_t)src[ip + 2] << 8) | src[ip + 3];
         const size_t cl = ((size_t)src[ip + 4] << 24) | ((size_t)src[ip + 5] << 16) | ((size_t)src[ip + 6] << 8) | src[ip + 7];
         ip += 8;
-        if (ip + cl > n || op + ul > cap || f((const char*)src + ip, (char*)dst + op, (int)cl, (int)ul) != (int)ul) break;
+        if (ip + cl > n || op + ul > cap || !lz4_inflate(src + ip, cl, dst + op, ul)) break;
         ip += cl; op += ul;
       }
       if (op != cap) throw Error(FDB_ERR_INVALID, "parquet: corrupt LZ4 page");
@@ -570,7 +650,7 @@ struct ParsedChunk {
   HostTable<FdbPqDeltaMini> delta_minis;
   int64_t non_null = 0;
   uint32_t max_index_bits = 0;
-  // Pages inflated on the DEVICE (snappy_decode_kernel): SNAPPY pages of PLAIN fixed-width values whose compressed size says they are
+  // Pages inflated on the DEVICE (snappy_decode_kernel / lz4_decode_kernel): SNAPPY or LZ4_RAW pages of PLAIN fixed-width values whose compressed size says they are
   // literals — inflating those on the host is a copy of the whole page into the image that the device can do at memory speed, while
   // match-heavy pages (levels, indices, deltas) are byte-serial work the host's threads are better at. Their place in the
   // image stays empty on the host (but for a V1 page's definition levels, which the host needs): the image is shipped in `host_spans`.
@@ -587,7 +667,7 @@ struct InflateJob { int codec; const uint8_t* raw; size_t comp, prefix, body_len
 // BYTE_ARRAY data pages that are not dictionary-encoded (their values are dictionary-encoded HERE, one hash probe per value like the
 // reference's own BinaryDictionaryBuilder.Append, pqarrow/writer/writer.go:391-405, and the indices are appended to the image as a
 // 32-bit-wide bit-packed run, which is all the device needs) — sizes it, and lists the inflate jobs of its data pages.
-void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* out, std::vector<InflateJob>* jobs) {
+void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, bool device_inflate, ParsedChunk* out, std::vector<InflateJob>* jobs) {
   if (c.data == nullptr || c.n_bytes <= 0) throw Error(FDB_ERR_INVALID, std::string("parquet: empty column chunk for ") + (c.name ? c.name : "?"));
   if (c.optional != 0 && c.optional != 1) throw Error(FDB_ERR_UNSUPPORTED, "parquet: nested / repeated columns are not supported (max definition level > 1)");
   const bool is_bytes = c.physical_type == PT_BYTE_ARRAY, is_fixed8 = c.physical_type == PT_INT64 || c.physical_type == PT_DOUBLE, is_bool = c.physical_type == PT_BOOLEAN;
@@ -598,8 +678,6 @@ void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* out, st
   size_t need = 0, extra = 0;
   int64_t values = 0;
   struct Pg { const uint8_t* raw; size_t comp, prefix, body_len; bool packed; bool device; bool v1_levels; };
-  // ($FDB_PARQUET_HOST_INFLATE: every page on the host, as before round 4)
-  static const bool device_inflate = std::getenv("FDB_PARQUET_HOST_INFLATE") == nullptr;
   std::vector<Pg> pages;
   bool dict_seen = false;
   while (w.p < w.end && values < n_rows) {
@@ -624,8 +702,11 @@ void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* out, st
     const bool packed = c.codec != CODEC_NONE && (h.type != PQ_DATA_PAGE_V2 || h.v2_compressed);
     const size_t comp_body = (size_t)h.compressed - prefix, plain_body = (size_t)h.uncompressed - prefix;
     constexpr size_t device_min = (size_t)32 << 10;  // (256 KiB until round 6: with every row group of a call on the host threads at once, inflating 1 000 literal pages of 48 KB per row group there was the host part's largest item — 3.2 ms against 1.3)
-    const bool on_device = device_inflate && packed && c.codec == CODEC_SNAPPY && is_fixed8 && h.encoding == ENC_PLAIN && plain_body >= device_min &&
-                           comp_body * 10 >= plain_body * 9 && plain_body < ((size_t)1 << 31) && snappy_device_ok(raw + prefix, comp_body);
+    // (LZ4_RAW pages pass the same gate: a page of literals is the same copy in either format, and the thresholds are about that copy.
+    // The Hadoop-framed codec 5 stays on the host: its pages may hold several blocks)
+    const bool on_device = device_inflate && packed && (c.codec == CODEC_SNAPPY || c.codec == CODEC_LZ4_RAW) && is_fixed8 && h.encoding == ENC_PLAIN &&
+                           plain_body >= device_min && comp_body * 10 >= plain_body * 9 && plain_body < ((size_t)1 << 31) &&
+                           (c.codec == CODEC_SNAPPY ? snappy_device_ok(raw + prefix, comp_body) : lz4_device_ok(raw + prefix, comp_body));
     pages.push_back(Pg{raw, (size_t)h.compressed, prefix, (size_t)h.uncompressed, packed, on_device, on_device && h.type == PQ_DATA_PAGE && c.optional != 0});
     need += (size_t)h.uncompressed + 8;  // (+8: keeps every 64-bit window of the device's readers inside the image)
     if (is_bytes && h.encoding != ENC_RLE_DICTIONARY && h.encoding != ENC_PLAIN_DICTIONARY) { use_image = true; extra += (size_t)h.num_values * 4 + 16; }
@@ -639,10 +720,13 @@ void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* out, st
     if (g.device) {
       if (g.v1_levels) {  // <4-byte length> <RLE levels> at the head of the inflated body: the host reads them, the device inflates them again with the values
         uint32_t dl = 0;
-        if (g.body_len < 4 || !snappy_prefix(g.raw, g.comp, dst, g.body_len, 4)) throw Error(FDB_ERR_INVALID, "parquet: corrupt Snappy page");
+        const bool lz4 = c.codec == CODEC_LZ4_RAW;
+        const char* corrupt = lz4 ? "parquet: corrupt LZ4 page" : "parquet: corrupt Snappy page";
+        auto head = [&](size_t want) { return lz4 ? lz4_prefix(g.raw, g.comp, dst, g.body_len, want) : snappy_prefix(g.raw, g.comp, dst, g.body_len, want); };
+        if (g.body_len < 4 || !head(4)) throw Error(FDB_ERR_INVALID, corrupt);
         std::memcpy(&dl, dst, 4);
         if ((size_t)dl + 4 > g.body_len) throw Error(FDB_ERR_INVALID, "parquet: definition levels run past the page");
-        if (!snappy_prefix(g.raw, g.comp, dst, g.body_len, (size_t)dl + 4)) throw Error(FDB_ERR_INVALID, "parquet: corrupt Snappy page");
+        if (!head((size_t)dl + 4)) throw Error(FDB_ERR_INVALID, corrupt);
       }
       out->dev_pages.push_back(ParsedChunk::DevPage{(size_t)(g.raw - c.data) + g.prefix, g.comp - g.prefix, at + g.prefix, g.body_len - g.prefix});
       if (g.prefix > 0) out->host_spans.emplace_back(at, at + g.prefix);
@@ -879,6 +963,7 @@ void parse_chunk(const fdb_parquet_chunk& c, int64_t n_rows, ParsedChunk* outp) 
 }
 
 std::atomic<int64_t> g_pq_calls{0}, g_pq_host_us{0}, g_pq_device_us{0}, g_pq_file_bytes{0}, g_pq_out_bytes{0};
+std::atomic<int64_t> g_pq_dev_pages[8], g_pq_dev_bytes[8];  // per CompressionCodec: pages the device inflated, and their output bytes
 
 }  // namespace
 
@@ -888,6 +973,14 @@ void parquet_stats(int64_t* calls, double* host_ms, double* device_ms, int64_t* 
   if (device_ms) *device_ms = (double)g_pq_device_us.load() / 1000.0;
   if (file_bytes) *file_bytes = g_pq_file_bytes.load();
   if (out_bytes) *out_bytes = g_pq_out_bytes.load();
+}
+
+uint32_t lz4_block_host(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) { return lz4_block(src, n, dst, cap, cap); }
+
+void parquet_device_pages(int codec, int64_t* pages, int64_t* bytes) {
+  if (codec < 0 || codec >= 8) throw Error(FDB_ERR_INVALID, "parquet: no such compression codec");
+  if (pages) *pages = g_pq_dev_pages[codec].load();
+  if (bytes) *bytes = g_pq_dev_bytes[codec].load();
 }
 
 // Row groups → resident batches, ONE call: the page headers of every chunk of every row group are walked first (host threads), the
@@ -980,6 +1073,9 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
     }
   } fs{&ctx, &copy_stream, &image_stream, &scratch, &pinned};
   static const bool prof = std::getenv("FDB_PROFILE_PARQUET") != nullptr;  // (tuning aid: the host part's phases on stderr)
+  // ($FDB_PARQUET_HOST_INFLATE: every page on the host, as before round 4; read per call, on the calling thread, so that one process can
+  // compare the two paths)
+  const bool device_inflate = std::getenv("FDB_PARQUET_HOST_INFLATE") == nullptr;
 
   // ---- (1) page headers of every chunk (host-only: malformed / unsupported chunks are refused before any device call; the first
   // failure in row-group and column order is reported) ---------------------------------------------------------------------------
@@ -991,7 +1087,7 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
   auto plan_one = [&](size_t k) {
     Group& R = G[(size_t)chunk_at[k].first];
     const size_t i = (size_t)chunk_at[k].second;
-    plan_chunk(R.chunks[i], R.n_rows, &R.parsed[i], &R.jobs[i]);
+    plan_chunk(R.chunks[i], R.n_rows, device_inflate, &R.parsed[i], &R.jobs[i]);
   };
   const bool threads = chunk_bytes >= ((size_t)1 << 20) && all_chunks > 1;
   if (threads && n_groups > 1) HostPool::get().parallel_for(all_chunks, plan_one);
@@ -1093,7 +1189,7 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
   // ---- (4) device part, chunk by chunk in the order the parses complete: a row group's 40 MB of PLAIN values (parsed in 50 µs) must not
   // wait for the 1–2 ms run-header walk of the dictionary column next to it before it may cross PCIe ----------------------------------
   hipStream_t stream = nullptr;
-  std::list<std::vector<FdbSnappyPage>> snappy_tables;                                       // device-inflated pages: per chunk, the launch's page table …
+  std::list<std::vector<FdbSnappyPage>> snappy_tables;                                       // device-inflated pages (SNAPPY or LZ4_RAW: the chunk's codec says which): per chunk, the launch's page table …
   std::list<std::tuple<const uint32_t*, size_t, int32_t, int32_t>> snappy_status;            // … and where its verdicts land (pinned host copy, pages, row group, chunk)
   uint32_t* d_flags = nullptr;
   uint32_t* h_flags = nullptr;
@@ -1198,7 +1294,8 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
         uint32_t* d_status = (uint32_t*)ctx->dev_alloc(T.size() * 4 + 16);
         scratch.push_back(d_status);
         fence();
-        hip_check(fdb_launch_snappy_decode(d_raw, d_table, (int32_t)T.size(), d_chunk, d_status, stream), "snappy decode");
+        if (c.codec == CODEC_LZ4_RAW) hip_check(fdb_launch_lz4_decode(d_raw, d_table, (int32_t)T.size(), d_chunk, d_status, stream), "lz4 decode");
+        else hip_check(fdb_launch_snappy_decode(d_raw, d_table, (int32_t)T.size(), d_chunk, d_status, stream), "snappy decode");
         uint32_t* h_status = (uint32_t*)pinned.take(T.size() * 4);
         std::memset(h_status, 0xFF, T.size() * 4);  // (a verdict that never arrives is not "ok")
         snappy_status.emplace_back(h_status, T.size(), g, i);
@@ -1342,9 +1439,13 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
   for (const auto& st : snappy_status)
     for (size_t q = 0; q < std::get<1>(st); q++)
       if (std::get<0>(st)[q] != 0) {
-        const char* nm = G[(size_t)std::get<2>(st)].chunks[std::get<3>(st)].name;
-        throw Error(FDB_ERR_INVALID, std::string("parquet: corrupt Snappy page in column ") + (nm ? nm : "?"));
+        const fdb_parquet_chunk& bad = G[(size_t)std::get<2>(st)].chunks[std::get<3>(st)];
+        throw Error(FDB_ERR_INVALID, std::string(bad.codec == CODEC_LZ4_RAW ? "parquet: corrupt LZ4 page in column " : "parquet: corrupt Snappy page in column ") + (bad.name ? bad.name : "?"));
       }
+  int64_t dev_pages[2] = {0, 0}, dev_bytes[2] = {0, 0};  // [0] SNAPPY, [1] LZ4_RAW: the two codecs plan_chunk sends to the device
+  for (const Group& R : G)
+    for (int32_t i = 0; i < R.n_chunks; i++)
+      for (const ParsedChunk::DevPage& q : R.parsed[(size_t)i].dev_pages) { dev_pages[R.chunks[i].codec == CODEC_LZ4_RAW]++; dev_bytes[R.chunks[i].codec == CODEC_LZ4_RAW] += (int64_t)q.len; }
 
   std::vector<std::unique_ptr<DeviceBatch>> out;
   int64_t fb = 0, ob = 0;
@@ -1392,6 +1493,9 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
     g_pq_device_us += std::chrono::duration_cast<std::chrono::microseconds>(t_end - t_host1).count();
     g_pq_file_bytes += fb;
     g_pq_out_bytes += ob;
+    // (fdb_parquet_device_pages: counted here, behind everything that can throw — a call that fails counts nothing)
+    g_pq_dev_pages[CODEC_SNAPPY] += dev_pages[0]; g_pq_dev_bytes[CODEC_SNAPPY] += dev_bytes[0];
+    g_pq_dev_pages[CODEC_LZ4_RAW] += dev_pages[1]; g_pq_dev_bytes[CODEC_LZ4_RAW] += dev_bytes[1];
   }
   return out;
 }

@@ -94,6 +94,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_plan_set_exact_sums.argtypes = [vp, i32]
     L.fdb_selftest_exact_sum.argtypes = [vp, i64, vp]
     L.fdb_snappy_decode_pages.argtypes = [vp, i64, vp, i32, vp, i64, ctypes.c_int, vp, P(ctypes.c_double)]
+    L.fdb_lz4_decode_pages.argtypes = [vp, i64, vp, i32, vp, i64, ctypes.c_int, vp, P(ctypes.c_double)]
+    L.fdb_parquet_device_pages.argtypes = [ctypes.c_int, P(i64), P(i64)]
     L.fdb_plan_state_arrays.argtypes = [vp, P(i32)]
     L.fdb_plan_state_array_op.argtypes = [vp, i32, P(i32)]
     L.fdb_plan_group_schema.argtypes = [vp, vp, vp]
@@ -159,6 +161,17 @@ def parquet_stats() -> dict:
     c, h, d, fb, ob = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
     lib().fdb_parquet_stats(ctypes.byref(c), ctypes.byref(h), ctypes.byref(d), ctypes.byref(fb), ctypes.byref(ob))
     return {"calls": c.value, "host_ms": h.value, "device_ms": d.value, "file_bytes": fb.value, "out_bytes": ob.value}
+
+
+def parquet_device_pages(codec) -> dict:
+    """Pages of one compression codec (a CompressionCodec number or name: "SNAPPY", "LZ4_RAW") that fdb_batch_from_parquet had the
+    device inflate, accumulated over the process, and their uncompressed bytes."""
+    codec = PARQUET_CODECS[codec.upper()] if isinstance(codec, str) else int(codec)
+    n, b = ctypes.c_int64(), ctypes.c_int64()
+    rc = lib().fdb_parquet_device_pages(codec, ctypes.byref(n), ctypes.byref(b))
+    if rc != 0:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    return {"pages": n.value, "bytes": b.value}
 
 
 def read_ceiling(device: int = 0, nbytes: int = 1 << 31, reps: int = 5) -> float:
@@ -693,6 +706,16 @@ def execute(records: Sequence, filter_expr: Optional[Expr], aggs: Sequence[Aggre
 def snappy_decode_pages(pages: "list[bytes]", sizes: "list[int]", device: int = 0):
     """Snappy-compressed pages → their bytes, inflated on the device (fdb_snappy_decode_pages; tests and measurement).
     Returns (list of bytes — None for a page the decoder refused —, list of status codes, kernel milliseconds)."""
+    return _decode_pages(lib().fdb_snappy_decode_pages, pages, sizes, device)
+
+
+def lz4_decode_pages(pages: "list[bytes]", sizes: "list[int]", device: int = 0):
+    """LZ4 blocks (Parquet's LZ4_RAW pages) → their bytes, inflated on the device (fdb_lz4_decode_pages; tests and measurement);
+    device < 0: by the library's built-in host decoder, without a GPU. Returns what snappy_decode_pages returns."""
+    return _decode_pages(lib().fdb_lz4_decode_pages, pages, sizes, device)
+
+
+def _decode_pages(entry, pages, sizes, device):
     import numpy as np
     n = len(pages)
     src = b"".join(pages)
@@ -705,7 +728,7 @@ def snappy_decode_pages(pages: "list[bytes]", sizes: "list[int]", device: int = 
     status = np.zeros(max(n, 1), dtype=np.uint32)
     ms = ctypes.c_double(0.0)
     srcb = np.frombuffer(src, dtype=np.uint8) if src else np.zeros(1, dtype=np.uint8)
-    rc = lib().fdb_snappy_decode_pages(srcb.ctypes.data, len(src), table.ctypes.data, n, dst.ctypes.data, do, device, status.ctypes.data, ctypes.byref(ms))
+    rc = entry(srcb.ctypes.data, len(src), table.ctypes.data, n, dst.ctypes.data, do, device, status.ctypes.data, ctypes.byref(ms))
     if rc != FDB_OK:
         _raise(rc, (lib().fdb_last_error() or b"").decode("utf-8", "replace"))
     out, at = [], 0

@@ -485,6 +485,15 @@ FDB_API int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_
 typedef struct fdb_snappy_page { uint64_t src_off; uint64_t dst_off; uint32_t src_len; uint32_t dst_len; } fdb_snappy_page;
 FDB_API int fdb_snappy_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_snappy_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
                             int device, uint32_t* status, double* kernel_ms);
+/* The same for LZ4 blocks (Parquet's LZ4_RAW: no frame, no length preamble — dst_len is the page's uncompressed size; lz4_decode_kernel).
+ * status[i]: 0 = ok, 2 truncated input, 3 output overrun, 4 match offset 0 or before the page's first byte, 5 output shorter than
+ * announced, 6 a match from more than 65 472 bytes back (legal LZ4, offsets go up to 65 535: fdb_batch_from_parquet leaves such pages
+ * to the host). device < 0: the library's built-in HOST decoder runs over the same page table and no GPU is touched (the same
+ * status codes but 6: offsets up to 65 535 are fine there; *kernel_ms = 0) — the decoder fdb_batch_from_parquet uses for LZ4
+ * pages where liblz4 is not installed. */
+typedef fdb_snappy_page fdb_lz4_page;
+FDB_API int fdb_lz4_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_lz4_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
+                         int device, uint32_t* status, double* kernel_ms);
 
 /* ---- measurement hooks (bench.py / rocprof correlation; not needed by the Go shim) -------------- */
 /* Algorithmic bytes (values-or-indices + validity of every referenced column, once per
@@ -496,6 +505,9 @@ FDB_API int fdb_plan_stats(fdb_plan* plan, int64_t* algorithmic_bytes, double* k
  * pages, dictionary pages) and of the device part (copies, pq_* kernels, the waits), bytes of column chunks read and of columns
  * produced. */
 FDB_API int fdb_parquet_stats(int64_t* calls, double* host_ms, double* device_ms, int64_t* file_bytes, int64_t* out_bytes);
+/* Pages of compression codec `codec` (parquet.thrift CompressionCodec: 1 SNAPPY, 7 LZ4_RAW) that fdb_batch(es)_from_parquet had the
+ * DEVICE inflate, accumulated over the process, and their uncompressed bytes (calls that failed count nothing). */
+FDB_API int fdb_parquet_device_pages(int codec, int64_t* pages, int64_t* bytes);
 /* Run-time specialisation (hiprtc): kernels this process compiled, the wall time the compiler took (ms), and code objects it
  * loaded from the on-disk cache ($FDB_JIT_CACHE) instead — what the FIRST query of a shape pays on top of its scan. */
 FDB_API int fdb_jit_stats(int64_t* n_compiled, double* compile_ms, int64_t* n_disk_loads);

@@ -61,11 +61,16 @@ nb = 70_000
 t_big = pa.table({"noise": pa.array(rng.integers(-2**62, 2**62, nb), mask=rng.random(nb) < 0.1), "value": pa.array(rng.random(nb), mask=rng.random(nb) < 0.001),
                   "req": pa.array(rng.random(nb))}, schema=pa.schema([pa.field("noise", pa.int64()), pa.field("value", pa.float64()), pa.field("req", pa.float64(), nullable=False)]))
 variants += [dict(compression="SNAPPY", big=True), dict(compression="SNAPPY", data_page_version="2.0", big=True)]
+# LZ4_RAW (codec 7; pyarrow's metadata says "LZ4" for it, `raw7` below passes 7 on): small pages on the host's inflate — liblz4 or, with
+# $FDB_PARQUET_BUILTIN_LZ4, the built-in decoder —, big pages of literals through lz4_device_ok / lz4_prefix like the Snappy ones
+variants += [dict(compression="LZ4_RAW", raw7=True), dict(compression="LZ4_RAW", data_page_version="2.0", raw7=True),
+             dict(compression="LZ4_RAW", big=True, raw7=True), dict(compression="LZ4_RAW", data_page_version="2.0", big=True, raw7=True)]
 codes = {}; total = 0
 for kw in variants:
-    kw = dict(kw); big = kw.pop("big", False)
+    kw = dict(kw); big = kw.pop("big", False); raw7 = kw.pop("raw7", False)
     data = write_parquet(t_big if big else t, data_page_size=(512 << 10) if big else 2048, **kw)
     chunks, rows = row_group_chunks(data, 0)
+    if raw7: chunks = [c[:5] + ("LZ4_RAW",) for c in chunks]
     rc = call(chunks, rows); codes[rc] = codes.get(rc, 0) + 1   # unmutated: parses, then fails at the device
     for it in range(int(sys.argv[1]) if len(sys.argv) > 1 else 100):
         # one chunk at a time, so that most runs get past the other columns
@@ -90,7 +95,7 @@ for kw in variants:
                     while v >= 0x80: enc.append((v & 0x7F) | 0x80); v >>= 7
                     enc.append(v); b[k:k + len(enc)] = enc
                 else:
-                    cd = random.choice(["SNAPPY", "UNCOMPRESSED", "ZSTD", "GZIP", "LZ4"]); opt = random.choice([0, 1])
+                    cd = random.choice(["SNAPPY", "UNCOMPRESSED", "ZSTD", "GZIP", "LZ4", "LZ4_RAW"]); opt = random.choice([0, 1])
             mut.append((nm, ty, opt, u8, bytes(b), cd))
         import time as _t; _t0 = _t.time()
         n_rows = random.choice([rows, rows, rows, rows - 1, rows + 5])
@@ -103,4 +108,30 @@ for kw in variants:
         _dt = _t.time() - _t0
         if _dt > 2: print("slow call", round(_dt, 1), "s variant", kw, "victim", chunks[victim][0], "rc", rc, flush=True)
         codes[rc] = codes.get(rc, 0) + 1; total += 1
-print("variants", len(variants), "runs", total, "return codes", codes)
+# the built-in LZ4 block decoder itself (fdb_lz4_decode_pages, device = -1): mutated blocks in exact-size buffers, output sizes right and
+# wrong; every page must come back with a verdict and, where the verdict is 0 and the announced size is the true one, with the bytes
+lib.fdb_lz4_decode_pages.restype = ctypes.c_int
+lz4 = pa.Codec("lz4_raw")
+plains = [bytes(rng.integers(0, 256, 5000, dtype=np.uint8)), np.arange(3000, dtype=np.int64).tobytes(), b"abc" * 3000, b"\x00" * 70000,
+          rng.integers(0, 6, 20000).astype(np.uint32).tobytes(), b"x"]
+verdicts = {}
+for plain in plains:
+    good = lz4.compress(plain, asbytes=True)
+    for it in range(4 * (int(sys.argv[1]) if len(sys.argv) > 1 else 100)):
+        b = bytearray(good); want = len(plain)
+        r = random.random()
+        if it == 0: pass
+        elif r < 0.5:
+            for _ in range(random.randint(1, 4)): b[random.randrange(len(b))] = random.randrange(256)
+        elif r < 0.7: b = b[: random.randrange(0, len(b))]
+        elif r < 0.8: k = random.randrange(len(b)); l = random.randint(1, 300); b[k:k + l] = b"\xff" * l
+        elif r < 0.9: want = max(0, want + random.randint(-20, 20))
+        else: k = random.randrange(len(b)); b[k:k] = bytes(random.randrange(256) for _ in range(random.randint(1, 20)))
+        src = (ctypes.c_ubyte * len(b)).from_buffer_copy(bytes(b)) if len(b) else (ctypes.c_ubyte * 1)()
+        dst = (ctypes.c_ubyte * max(want, 1))()
+        table = (ctypes.c_uint64 * 3)(0, 0, len(b) | (want << 32)); st = ctypes.c_uint32(9)
+        rc = lib.fdb_lz4_decode_pages(src, ctypes.c_int64(len(b)), table, 1, dst, ctypes.c_int64(want), -1, ctypes.byref(st), None)
+        assert rc == 0 and st.value in (0, 2, 3, 4, 5), (rc, st.value)
+        if it == 0: assert st.value == 0 and bytes(dst[:want]) == plain
+        verdicts[st.value] = verdicts.get(st.value, 0) + 1
+print("variants", len(variants), "runs", total, "return codes", codes, "lz4 block verdicts", verdicts)

@@ -12,6 +12,7 @@ hipError_t fdb_launch_pq_delta(const uint8_t*, const FdbPqDeltaPage*, int32_t, c
 hipError_t fdb_launch_exclusive_scan(uint32_t*, int64_t, uint32_t*, unsigned long long*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t fdb_launch_validate_indices(const uint32_t*, const uint8_t*, int64_t, uint32_t, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 hipError_t fdb_launch_snappy_decode(const uint8_t*, const FdbSnappyPage*, int32_t, uint8_t*, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
+hipError_t fdb_launch_lz4_decode(const uint8_t*, const FdbLz4Page*, int32_t, uint8_t*, uint32_t*, hipStream_t) { return hipErrorNotSupported; }
 static thread_local std::string g_err;
 extern "C" const char* fdb_last_error(void) { return g_err.c_str(); }
 extern "C" int fdb_batch_from_parquet(const fdb_parquet_chunk* chunks, int32_t n, int64_t rows, int device, fdb_batch** out) {
@@ -23,6 +24,16 @@ extern "C" int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int
   try { auto b = fdb::batches_from_parquet(groups, n_groups, device); (void)b; return 0; }
   catch (const fdb::Error& e) { g_err = e.what(); return e.code; }
   catch (const std::exception& e) { g_err = e.what(); return FDB_ERR_INVALID; }
+}
+// fdb_lz4_decode_pages with device < 0, as fdb_capi.cpp has it: the built-in host decoder over a page table
+extern "C" int fdb_lz4_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_lz4_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes, int device, uint32_t* status, double*) {
+  if (device >= 0) return FDB_ERR_UNSUPPORTED;
+  for (int32_t i = 0; i < n_pages; i++) {
+    if (pages[i].src_off > (uint64_t)src_bytes || pages[i].src_len > (uint64_t)src_bytes - pages[i].src_off || pages[i].dst_off > (uint64_t)dst_bytes ||
+        pages[i].dst_len > (uint64_t)dst_bytes - pages[i].dst_off) return FDB_ERR_INVALID;
+    status[i] = fdb::lz4_block_host(src + pages[i].src_off, pages[i].src_len, dst + pages[i].dst_off, pages[i].dst_len);
+  }
+  return 0;
 }
 namespace fdb {
 void hip_check(hipError_t e, const char* what) {

@@ -15,7 +15,7 @@ rows, rg_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 20_000_000, 5_000_000
 rec = synth.prometheus_chunk(0, 0, rows)
 t = pa.Table.from_batches([rec])
 t = t.set_column(0, "labels.code", t.column(0).cast(pa.binary())).set_column(1, "labels.path", t.column(1).cast(pa.binary()))
-variant = os.environ.get("PQ_VARIANT", "plain")  # "plain": UNCOMPRESSED, PLAIN int64; "delta_snappy": timestamp DELTA_BINARY_PACKED, pages SNAPPY; "numeric_dict": below
+variant = os.environ.get("PQ_VARIANT", "plain")  # "plain": UNCOMPRESSED, PLAIN int64; "delta_snappy": timestamp DELTA_BINARY_PACKED, pages SNAPPY; "numeric_dict", "lz4_raw": below
 kw = {}
 if variant == "delta_snappy":
     kw = dict(compression="SNAPPY", column_encoding={"timestamp": "DELTA_BINARY_PACKED"}, use_dictionary=["labels.code", "labels.path"])
@@ -78,6 +78,49 @@ if variant == "numeric_dict":
     print(json.dumps({"metric": "decode time, dictionary-encoded numeric file / PLAIN numeric file (medians, alternating passes in one process)",
                       "ratio": out["numeric_dict"]["median_s_per_pass"] / out["numeric_plain"]["median_s_per_pass"],
                       "bytes_ratio": len(files["numeric_dict"]) / len(files["numeric_plain"])}))
+    sys.exit(0)
+
+if variant == "lz4_raw":
+    # The file with LZ4_RAW pages (codec 7 in the footer: pyarrow's metadata API says "LZ4" for 5 and 7 alike): the PLAIN float64 `value`
+    # pages are literals and are inflated on the device, the rest on the host. One process, the default and the all-host path
+    # ($FDB_PARQUET_HOST_INFLATE, read per call) decoded alternately, median and 10th / 90th percentile of $PQ_PASSES (default 15) passes
+    # each; a pass = file bytes → resident batches (one fdb_batches_from_parquet call) → released. One JSON line per path and one with the ratio.
+    from tests.lz4_cases import footer_codecs
+    passes = int(os.environ.get("PQ_PASSES", "15"))
+    data = write_parquet(t, row_group_size=rg_rows, data_page_size=1 << 20, compression="LZ4_RAW", use_dictionary=["labels.code", "labels.path"])
+    assert set(footer_codecs(data)) == {7}
+    groups, pinned = pinned_groups(data)
+    groups = [([c[:5] + ("LZ4_RAW",) for c in ch], n) for ch, n in groups]
+    def decode(host):
+        if host: os.environ["FDB_PARQUET_HOST_INFLATE"] = "1"
+        else: os.environ.pop("FDB_PARQUET_HOST_INFLATE", None)
+        keep = pp.ResidentBatch.from_parquet_many(groups)
+        for b in keep: b.close()
+    # the two paths decode to the same columns
+    tabs = []
+    for host in (False, True):
+        if host: os.environ["FDB_PARQUET_HOST_INFLATE"] = "1"
+        else: os.environ.pop("FDB_PARQUET_HOST_INFLATE", None)
+        keep = pp.ResidentBatch.from_parquet_many(groups); tabs.append([b.to_arrow() for b in keep])
+        for b in keep: b.close()
+    assert all(x.equals(y) for x, y in zip(*tabs)); del tabs
+    names = {False: "lz4_raw_device_inflate", True: "lz4_raw_host_inflate"}
+    times = {h: [] for h in names}; stats = {h: {"host_ms": 0.0, "device_ms": 0.0} for h in names}; dev_pages = {}
+    for h in names: decode(h); decode(h)  # warm-up
+    for _ in range(passes):
+        for h in names:
+            d0 = pp.parquet_device_pages(7); s0 = pp.parquet_stats(); t0 = time.perf_counter(); decode(h); dt = time.perf_counter() - t0; s1 = pp.parquet_stats()
+            times[h].append(dt); dev_pages[h] = pp.parquet_device_pages(7)["pages"] - d0["pages"]
+            for f in stats[h]: stats[h][f] += s1[f] - s0[f]
+    out = {}
+    for h, k in names.items():
+        ts = sorted(times[h]); med = ts[len(ts) // 2]
+        out[h] = {"variant": k, "rows": rows, "row_groups": len(groups), "parquet_bytes": len(data), "passes": passes, "median_s_per_pass": med, "min_s": ts[0],
+                  "p10_s": ts[int(len(ts) * 0.1)], "p90_s": ts[int(len(ts) * 0.9)], "rows_per_s": rows / med, "parquet_GB_per_s": len(data) / med / 1e9,
+                  "host_ms_per_pass": stats[h]["host_ms"] / passes, "device_ms_per_pass": stats[h]["device_ms"] / passes, "device_inflated_pages_per_pass": dev_pages[h]}
+        print(json.dumps(out[h]))
+    print(json.dumps({"metric": "decode time, LZ4_RAW pages of literals inflated on the device / every page on the host (medians, alternating passes in one process)",
+                      "ratio": out[False]["median_s_per_pass"] / out[True]["median_s_per_pass"]}))
     sys.exit(0)
 
 data = write_parquet(t, row_group_size=rg_rows, data_page_size=1 << 20, **kw)
