@@ -341,6 +341,40 @@ int fdb_plan_filter_batches(fdb_plan* plan, const fdb_batch* const* batches, int
   });
 }
 
+int fdb_plan_project_batch(fdb_plan* plan, const fdb_project_col* cols, int32_t n_cols, const fdb_batch* in, fdb_batch** out) {
+  if (!plan) return FDB_ERR_INVALID;
+  return guard(plan, [&] {
+    if (in == nullptr || !in->b || out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<fdb::DeviceBatch> r = plan->plan.project_batch(cols, n_cols, *in->b);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_plan_project_batches(fdb_plan* plan, const fdb_project_col* cols, int32_t n_cols, const fdb_batch* const* in, int32_t n, fdb_batch** out) {
+  if (!plan) return FDB_ERR_INVALID;
+  return guard(plan, [&] {
+    if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    std::vector<const fdb::DeviceBatch*> bs;
+    for (int32_t i = 0; i < n; i++) {
+      out[i] = nullptr;
+      if (in[i] == nullptr || !in[i]->b) throw fdb::Error(FDB_ERR_INVALID, "null batch");
+      bs.push_back(in[i]->b.get());
+    }
+    std::vector<std::unique_ptr<fdb::DeviceBatch>> rs = plan->plan.project_batches(cols, n_cols, bs.data(), n);
+    for (int32_t i = 0; i < n; i++) out[i] = new fdb_batch{std::move(rs[(size_t)i])};
+  });
+}
+
+int fdb_plan_project(fdb_plan* plan, const fdb_project_col* cols, int32_t n_cols, struct ArrowArray* batch, struct ArrowSchema* schema, struct ArrowArray* out,
+                     struct ArrowSchema* out_schema) {
+  if (!plan) return FDB_ERR_INVALID;
+  return guard(plan, [&] {
+    if (batch == nullptr || schema == nullptr || out == nullptr || out_schema == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    plan->plan.project(cols, n_cols, batch, schema, out, out_schema);
+  });
+}
+
 int fdb_plan_select_batch(fdb_plan* plan, const fdb_batch* batch, uint32_t* dev_indices, int64_t capacity, int64_t* n_selected) {
   if (!plan) return FDB_ERR_INVALID;
   return guard(plan, [&] {

@@ -713,6 +713,131 @@ struct Gen {
     return o.str();
   }
 
+  // ---- Projection: the computed fields of every record of a call, one launch (Plan::project_batches) ---------------------------------
+  // Record / slot / LUT handling as in fdb_plan_kernel's two-phase layout (leaves of string comparisons read c4 / c8, the expressions'
+  // columns l8); the geometry is the scan's: persistent workgroups of 256 threads over tiles of 1 024 rows, a lane owns 4 consecutive
+  // rows — two 16-byte non-temporal loads per 8-byte column, every load of the tile issued before the first is consumed, two plain
+  // 16-byte stores per output column (the consumer reads them next). No lane leaves a tile early: lanes past the end of the record
+  // re-read the rows of their wave's first lane and store nothing, so the whole wave takes part in the cross-lane steps. A field that can
+  // be NULL (a division at the root, an aliased nullable column) gets its validity from the lanes' 4-bit nibbles: three shuffles put the
+  // 32 bits of eight lanes into the first of them, which stores the word — a tile owns whole words of the bitmap, nothing is zeroed and
+  // nothing is atomic; bits past the record's last row are 0. NULLs are counted per lane across all tiles of a record and folded once per
+  // record: a butterfly per wave, four words of LDS, ONE atomic per workgroup and field.
+  std::string project_source() {
+    const int BLK = 256;
+    const size_t NO = s.proj_roots.size();
+    auto may_null = [&](size_t j) {
+      const JitExprNode& n = s.exprs[(size_t)s.proj_roots[j]];
+      return (n.kind == 0 && s.l8[n.slot].has_validity != 0) || (n.kind == 2 && n.op == FDB_OP_DIV);
+    };
+    bool any_null = false;
+    for (size_t j = 0; j < NO; j++) any_null = any_null || may_null(j);
+    o << "#include \"fdb_kernels.h\"\n" << kPreamble;
+    o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_project_kernel(const FdbScanArgs* __restrict__ parts, const int n_parts, const long long total_tiles, const FdbProjectPart* __restrict__ outs, unsigned long long* __restrict__ nulls) {\n";
+    // (no fused multiply-add: `a * b + c` rounds twice, like the reference's separate Mul and Add loops)
+    o << "#pragma clang fp contract(off)\n  extern __shared__ __align__(16) unsigned char smem[];\n";
+    if (any_null) o << "  __shared__ uint32_t s_nn[" << BLK / 64 << "][" << NO << "];\n";
+    o << "  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6; (void)lane; (void)wave;\n";
+    for (bool late : {false, true}) {
+      const int n4 = late ? s.n_l4 : s.n_c4, n8 = late ? s.n_l8 : s.n_c8;
+      for (int i = 0; i < n4; i++) o << "  const char* P_" << reg(false, late, i) << "_v = nullptr; const uint8_t* P_" << reg(false, late, i) << "_b = nullptr;\n";
+      for (int i = 0; i < n8; i++) o << "  const char* P_" << reg(true, late, i) << "_v = nullptr; const uint8_t* P_" << reg(true, late, i) << "_b = nullptr;\n";
+    }
+    for (size_t l = 0; l < s.leaves.size(); l++)
+      o << "  long long K_lit" << l << " = 0; uint32_t K_len" << l << " = 1, K_lds" << l << " = 0; int K_op" << l << " = 0; const uint8_t* K_lut" << l << " = nullptr;\n";
+    for (size_t i = 0; i < s.exprs.size(); i++) if (s.exprs[i].kind == 1) o << "  long long K_elit" << i << " = 0;\n";
+    for (size_t j = 0; j < NO; j++) {
+      o << "  unsigned char* O_v" << j << " = nullptr;\n";
+      if (may_null(j)) o << "  uint8_t* O_b" << j << " = nullptr; uint32_t N" << j << " = 0u;\n";
+    }
+    o << "  long long n_rows = 0, tile_begin = 0, tile_end = 0; int part = -1, lut_class = -1;\n";
+    std::ostringstream fl;  // NULL counts of the record the workgroup leaves (every thread of the workgroup arrives here together)
+    if (any_null) {
+      fl << "      {\n";
+      for (size_t j = 0; j < NO; j++) {
+        if (!may_null(j)) continue;
+        fl << "        { uint32_t t = N" << j << "; N" << j << " = 0u;\n#pragma unroll\n          for (int sh = 32; sh > 0; sh >>= 1) t += (uint32_t)__shfl_xor((int)t, sh, 64);\n";
+        fl << "          if (lane == 0u) s_nn[wave][" << j << "] = t; }\n";
+      }
+      fl << "        __syncthreads();\n";
+      for (size_t j = 0; j < NO; j++) {
+        if (!may_null(j)) continue;
+        fl << "        if (tid == " << j << "u) { const uint32_t t = s_nn[0][" << j << "] + s_nn[1][" << j << "] + s_nn[2][" << j << "] + s_nn[3][" << j
+           << "]; if (t != 0u) atomicAdd(nulls + (size_t)part * FDB_PROJECT_MAX_OUT + " << j << ", (unsigned long long)t); }\n";
+      }
+      fl << "        __syncthreads();\n      }\n";
+    }
+    o << "  for (long long tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {\n";
+    o << "    if (part < 0 || tile >= tile_end) {\n";
+    if (any_null) o << "      if (part >= 0)\n" << fl.str();
+    o << "      int np = part < 0 ? 0 : part;\n      while (np + 1 < n_parts && tile >= parts[np].tile_end) np++;\n      part = np;\n";
+    o << "      const FdbScanArgs& pa = parts[part];\n      n_rows = pa.n_rows; tile_begin = pa.tile_begin; tile_end = pa.tile_end;\n";
+    for (bool late : {false, true}) {
+      const int n4 = late ? s.n_l4 : s.n_c4, n8 = late ? s.n_l8 : s.n_c8;
+      const char* p4 = late ? "l4" : "c4"; const char* p8 = late ? "l8" : "c8";
+      for (int i = 0; i < n4; i++)
+        o << "      P_" << reg(false, late, i) << "_v = (const char*)pa." << p4 << "[" << i << "].values; P_" << reg(false, late, i) << "_b = pa." << p4 << "[" << i << "].validity;\n";
+      for (int i = 0; i < n8; i++)
+        o << "      P_" << reg(true, late, i) << "_v = (const char*)pa." << p8 << "[" << i << "].values; P_" << reg(true, late, i) << "_b = pa." << p8 << "[" << i << "].validity;\n";
+    }
+    for (size_t l = 0; l < s.leaves.size(); l++)
+      o << "      K_lit" << l << " = pa.leaves[" << l << "].lit; K_len" << l << " = pa.leaves[" << l << "].lut_len; K_lds" << l << " = pa.leaves[" << l << "].lut_lds; K_op" << l
+        << " = pa.leaves[" << l << "].op; K_lut" << l << " = pa.leaves[" << l << "].lut;\n";
+    for (size_t i = 0; i < s.exprs.size(); i++) if (s.exprs[i].kind == 1) o << "      K_elit" << i << " = pa.expr[" << i << "].lit;\n";
+    for (size_t j = 0; j < NO; j++) {
+      o << "      O_v" << j << " = (unsigned char*)outs[part].out[" << j << "].values;\n";
+      if (may_null(j)) o << "      O_b" << j << " = outs[part].out[" << j << "].validity;\n";
+    }
+    o << "      if (pa.lut_class != lut_class) {\n        lut_class = pa.lut_class;\n        __syncthreads();\n";
+    for (size_t l = 0; l < s.leaves.size(); l++)
+      if (s.leaves[l].kind == FDB_LEAF_DICT_LUT && s.leaves[l].lut_in_lds)
+        o << "        for (uint32_t i = tid; i < K_len" << l << "; i += " << BLK << ") smem[K_lds" << l << " + i] = as_global(K_lut" << l << ")[i];\n";
+    o << "        __syncthreads();\n      }\n    }\n";
+    o << "    const long long r0 = (tile - tile_begin) * " << BLK * 4 << "LL;\n";
+    o << "    if (n_rows - r0 - (long long)(tid & ~63u) * 4 <= 0) continue;  // (the whole wave lies past the record's end)\n";
+    o << "    const long long left = n_rows - r0 - (long long)tid * 4;\n";
+    o << "    const uint32_t ltid = left > 0 ? tid : (tid & ~63u);\n";
+    o << "    const uint32_t lane_off4 = ltid * 16u, lane_off8 = ltid * 32u, lane_offb = ltid >> 1, lane_shb = (ltid & 1u) * 4u;\n";
+    o << "    const size_t tile_off4 = (size_t)r0 * 4, tile_off8 = (size_t)r0 * 8, tile_offb = (size_t)(r0 >> 3);\n";
+    o << "    (void)lane_off4; (void)lane_off8; (void)lane_offb; (void)lane_shb; (void)tile_off4; (void)tile_off8; (void)tile_offb;\n";
+    loads(false);
+    loads(true);
+    o << "    const uint32_t live = left >= 4 ? 0xFu : left > 0 ? ((1u << (int)left) - 1u) : 0u; (void)live;\n";
+    {
+      // (rows past the record's end read as NULL: their index slots hold whatever follows the column and must not reach a truth table)
+      for (int i = 0; i < s.n_c4; i++) o << "    const u32x4 q4_" << i << " = " << reg(false, false, i) << "; const uint32_t q4_" << i << "_m = " << reg(false, false, i) << "_m & live; (void)q4_" << i << ";\n";
+      std::vector<int> seen;
+      for (const JitExprNode& e : s.exprs)
+        if (e.kind == 7 && std::find(seen.begin(), seen.end(), e.slot) == seen.end()) {
+          seen.push_back(e.slot);
+          const JitLeaf& L = s.leaves[(size_t)e.slot];
+          o << "    const uint32_t PM" << e.slot << " = " << leaf_expr_of(L, e.slot, L.wide ? reg(true, false, L.slot) : "q4_" + std::to_string(L.slot)) << "; (void)PM" << e.slot << ";\n";
+        }
+    }
+    for (size_t j = 0; j < NO; j++) {
+      const int root = s.proj_roots[j];
+      std::string valid[4];
+      for (int k = 0; k < 4; k++) {
+        const std::string comp = std::string(k < 2 ? "a" : "b") + (k % 2 == 0 ? ".x" : ".y");
+        auto col = [&](int ni) -> std::string { if (s.exprs[(size_t)ni].kind == 7) return "((PM" + std::to_string(s.exprs[(size_t)ni].slot) + " >> " + std::to_string(k) + ") & 1u)"; return reg(true, true, s.exprs[(size_t)ni].slot) + comp; };
+        auto colvalid = [&](int ni) { return "((" + reg(true, true, s.exprs[(size_t)ni].slot) + "_m >> " + std::to_string(k) + ") & 1u)"; };
+        o << "    const unsigned long long v" << j << "_" << k << " = " << expr_bits(s.exprs, root, expr_value(s.exprs, root, col, colvalid)) << ";\n";
+        valid[k] = expr_valid(s.exprs, root, col, colvalid);
+      }
+      o << "    if (left > 0) {\n      G1 u64x2* dst = (G1 u64x2*)(O_v" << j << " + tile_off8 + (size_t)tid * 32);\n";
+      o << "      u64x2 a; a.x = v" << j << "_0; a.y = v" << j << "_1; u64x2 b; b.x = v" << j << "_2; b.y = v" << j << "_3;\n      dst[0] = a; dst[1] = b;\n    }\n";
+      if (!may_null(j)) continue;
+      o << "    {\n      uint32_t w = ((" << valid[0] << ") ? 1u : 0u) | ((" << valid[1] << ") ? 2u : 0u) | ((" << valid[2] << ") ? 4u : 0u) | ((" << valid[3] << ") ? 8u : 0u);\n";
+      o << "      w &= live;\n      N" << j << " += (uint32_t)__builtin_popcount(live & ~w);\n";
+      o << "      w |= (uint32_t)__shfl_down((int)w, 1, 64) << 4;\n      w |= (uint32_t)__shfl_down((int)w, 2, 64) << 8;\n      w |= (uint32_t)__shfl_down((int)w, 4, 64) << 16;\n";
+      o << "      if ((lane & 7u) == 0u && left > 0 && O_b" << j << " != nullptr) *(G1 uint32_t*)(O_b" << j << " + tile_offb + (size_t)(tid >> 3) * 4) = w;\n    }\n";
+    }
+    o << "  }\n";
+    if (any_null) o << "  if (part >= 0)\n" << fl.str();
+    o << "}\n";
+    return o.str();
+  }
+
   // ---- filter() in one pass over the filter columns (Plan::filter_batches; FdbSelectArgs in fdb_kernels.h) ----------------------------
   // fdb_flags_kernel's row evaluation with three additions. (1) Work is handed out by a ticket counter, one ticket per workgroup share
   // of four tiles: whatever a workgroup waits for is then held by workgroups that already run, never by one the dispatcher has not
@@ -1686,6 +1811,19 @@ hipError_t jit_flags_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_
                             uint32_t* masks, uint32_t* tile_counts, hipStream_t stream) {
   long long tt = total_super_tiles;
   void* args[] = {(void*)&d_parts, (void*)&n_parts, (void*)&tt, (void*)&common, (void*)&masks, (void*)&tile_counts};
+  return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256u, 1, 1, (unsigned)lds_bytes, stream, args, nullptr);
+}
+
+std::string jit_project_source(const JitShape& shape) { return Gen(shape).project_source(); }
+hipFunction_t jit_project_get(const JitShape& shape) {
+  std::string roots;
+  for (int r : shape.proj_roots) roots += std::to_string(r) + ",";
+  return get_kernel("project|" + shape.key() + "|r" + roots, "fdb_project_kernel", [&] { return jit_project_source(shape); });
+}
+hipError_t jit_project_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_parts, int64_t total_tiles, int grid, size_t lds_bytes, const FdbProjectPart* d_outs,
+                              unsigned long long* d_nulls, hipStream_t stream) {
+  long long tt = total_tiles;
+  void* args[] = {(void*)&d_parts, (void*)&n_parts, (void*)&tt, (void*)&d_outs, (void*)&d_nulls};
   return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256u, 1, 1, (unsigned)lds_bytes, stream, args, nullptr);
 }
 

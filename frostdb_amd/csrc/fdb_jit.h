@@ -48,6 +48,8 @@ struct JitShape {
   bool uniform_fold = true;  // ($FDB_NO_UNIFORM_FOLD, A/B aid: a plan reads it at create, Plan::Knobs)
   // fdb_select_kernel only (not part of key()): early slots whose values the kernel compacts itself, bit i = slot i of c4 / c8
   int fuse4 = 0, fuse8 = 0;
+  // fdb_project_kernel only (not part of key()): root node of every computed field, in output order
+  std::vector<int> proj_roots;
   std::string key(bool with_validity = true) const;
 };
 
@@ -110,6 +112,14 @@ size_t jit_select_stage_bytes(const JitShape& shape);
 int jit_select_block();  // threads per workgroup (8 waves, half a tile each)
 hipError_t jit_select_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_parts, int64_t total_super_tiles, const FdbScanArgs& common, int grid, size_t lds_bytes,
                              uint32_t* masks, uint32_t* offsets, const FdbSelectArgs& sel, hipStream_t stream);
+
+// Projection (Plan::project_batches; fdb_kernels.h, FdbProjectPart): every computed field of a call in one launch — 256-thread workgroups,
+// tiles of FDB_PROJECT_TILE rows counted by tile_begin / tile_end of the argument blocks, a lane owns 4 consecutive rows. shape: jit_shape of a
+// record's argument block in the two-phase layout (expression columns in l8, leaves of string comparisons in c4 / c8) + proj_roots.
+std::string jit_project_source(const JitShape& shape);
+hipFunction_t jit_project_get(const JitShape& shape);
+hipError_t jit_project_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_parts, int64_t total_tiles, int grid, size_t lds_bytes, const FdbProjectPart* d_outs,
+                              unsigned long long* d_nulls, hipStream_t stream);
 
 std::string jit_source(const JitShape& shape);
 // The compiled kernel for `shape` (cached in the process and on disk), or nullptr if specialisation is unavailable.

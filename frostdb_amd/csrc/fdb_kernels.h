@@ -699,6 +699,18 @@ struct FdbSelectArgs {
   int32_t n_zero;
 };
 
+// Projection (fdb_project_kernel, generated per expression shape in fdb_jit.cpp; Plan::project_batches): the computed fields of one
+// record. The expressions are the record's FdbScanArgs.expr (roots are part of the kernel's shape), their columns sit in the l8 slots,
+// the leaves of string / dictionary comparisons in c4 / c8. Tiles are FDB_PROJECT_TILE rows: a 256-thread workgroup, a lane owns 4
+// consecutive rows, so a tile owns whole bytes (whole 32-bit words) of every bitmap it writes.
+#define FDB_PROJECT_MAX_OUT 16
+#define FDB_PROJECT_TILE 1024
+struct FdbProjectOut {
+  void* values;       // [rows] 8-byte values: int64 / uint64 / float64 bits, a bool as int64 1 (false) / 2 (true) like a stored bool column
+  uint8_t* validity;  // bitmap, whole words written by the kernel (nothing to zero); nullptr: the field cannot be NULL in this record
+};
+struct FdbProjectPart { FdbProjectOut out[FDB_PROJECT_MAX_OUT]; };  // NULL counts: nulls[record × FDB_PROJECT_MAX_OUT + field], zeroed by the caller
+
 #ifndef FDB_DEVICE_ONLY
 // ---- launch wrappers (fdb_kernels.hip) ---------------------------------------------------------------
 // All launches are asynchronous on `stream`.

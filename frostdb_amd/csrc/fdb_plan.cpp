@@ -536,7 +536,7 @@ int Plan::resolve_projection(const Projection& p, const DeviceBatch& b, Resolved
       const DevColumn& c = b.cols[(size_t)ci];
       e.type = c.kind == ColKind::I64 ? FDB_T_I64 : c.kind == ColKind::F64 ? FDB_T_F64 : c.kind == ColKind::U64 ? FDB_T_U64 : FDB_T_NONE;  // (Int32 columns do not exist on this path)
       if (e.type == FDB_T_NONE) throw Error(FDB_ERR_UNSUPPORTED, "projection " + p.name + ": unsupported type of column " + n.column);  // project.go:157-159
-      if (c.d_values == nullptr) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);
+      if (c.d_values == nullptr && b.rows > 0) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);  // (a zero-row record — a filter that selected nothing — has no buffers)
       R->count(b, ci);
       R->expr_col[base + (int)k] = ci;
     } else if (n.kind == 1) {
@@ -909,7 +909,7 @@ static void resolve_leaf(const ExprNode& e, const DeviceBatch& b, Plan::Resolved
     // Binary arrays (regexpfilter.go:48-54, binaryscalarexpr.go:87-89, :234-270 — a NULL literal searches for ""), and
     // = != < <= > >= go to Arrow's compare kernels (binaryscalarexpr.go:116, :119-152): bytewise order, a NULL scalar
     // yields NULL for every row ⇒ no row, a non-string scalar has no kernel.
-    if (c.d_values == nullptr) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);
+    if (c.d_values == nullptr && b.rows > 0) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);  // (a zero-row record — a filter that selected nothing — has no buffers)
     if (!is_regex && !is_contains) {
       if (!(e.op >= FDB_OP_EQ && e.op <= FDB_OP_GT_EQ)) throw Error(FDB_ERR_UNSUPPORTED, "unsupported binary operation");
       if (!e.lit.valid()) { set_const(false); return; }
@@ -920,7 +920,7 @@ static void resolve_leaf(const ExprNode& e, const DeviceBatch& b, Plan::Resolved
     return;
   }
   if (c.kind == ColKind::DICT) {
-    if (c.d_values == nullptr) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);
+    if (c.d_values == nullptr && b.rows > 0) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);  // (a zero-row record — a filter that selected nothing — has no buffers)
     if (is_regex && c.dict->utf8())  // regexpfilter.go:55-61: only *array.Binary dictionaries
       throw Error(FDB_ERR_UNSUPPORTED, "ArrayScalarRegexMatch: unsupported dictionary type: *array.String");
     if (!is_regex && !is_contains && e.op != FDB_OP_EQ && e.op != FDB_OP_NOT_EQ)
@@ -945,7 +945,7 @@ static void resolve_leaf(const ExprNode& e, const DeviceBatch& b, Plan::Resolved
   if (!(e.op >= FDB_OP_EQ && e.op <= FDB_OP_GT_EQ)) throw Error(FDB_ERR_UNSUPPORTED, "unsupported binary operation");
   if (c.kind != ColKind::I64 && c.kind != ColKind::U64 && c.kind != ColKind::F64 && c.kind != ColKind::BOOL)
     throw Error(FDB_ERR_UNSUPPORTED, "unsupported binary operation: compare on column type " + c.format + " (" + c.name + ")");
-  if (c.d_values == nullptr) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);
+  if (c.d_values == nullptr && b.rows > 0) throw Error(FDB_ERR_INVALID, "column not staged: " + c.name);  // (a zero-row record — a filter that selected nothing — has no buffers)
   if (!e.lit.valid()) { set_const(false); return; }  // compare with a NULL scalar yields NULL for every row (binaryscalarexpr.go:143-146)
   R->count(b, ci);
   L->values = c.d_values;

@@ -243,6 +243,12 @@ class Plan {
   int64_t select_batch(const DeviceBatch& in, uint32_t* d_indices, int64_t capacity);
   // The same for every record of a scan at once: one launch sequence, two host round trips in total (sizes, NULL counts).
   std::vector<std::unique_ptr<DeviceBatch>> filter_batches(const DeviceBatch* const* in, int n, int64_t* n_selected);
+  // ≙ Projection.Callback (project.go:906-943; fdb_project.cpp): the fields `cols` select or compute — computed ones are this plan's
+  // projections, by name — as a new resident batch of the input's row count; `project_batches`: every record of a scan, ONE launch for
+  // all computed fields, all or nothing; `project`: host record in, host record out. The plan's aggregate state is not touched.
+  std::unique_ptr<DeviceBatch> project_batch(const fdb_project_col* cols, int n_cols, const DeviceBatch& in);
+  std::vector<std::unique_ptr<DeviceBatch>> project_batches(const fdb_project_col* cols, int n_cols, const DeviceBatch* const* in, int n);
+  void project(const fdb_project_col* cols, int n_cols, const ArrowArray* array, const ArrowSchema* schema, ArrowArray* out, ArrowSchema* out_schema);
   const char* draw();                                                  // ≙ Draw
   int64_t num_groups();
   void partial_keys(ArrowArray* out, ArrowSchema* out_schema);

@@ -260,6 +260,11 @@ class IfExpr(Expr):
         return self.name
 
 
+def expr_name(e) -> str:
+    """Expr.Name(): the output field of a projected expression (a bare literal is named by its value, expr.go:620-622)."""
+    return e.name if hasattr(e, "name") else str(e)
+
+
 def Convert(e, to: str = "float64") -> ConvertExpr:
     return ConvertExpr(e, to)
 
@@ -390,8 +395,10 @@ class PlanDescHolder:
 
 
 def to_desc(filter_expr: Optional[Expr], aggs: Sequence[AggregationFunction], groups: Sequence[Column],
-            final_stage: bool = False, regex=None, ordered: bool = False) -> PlanDescHolder:
-    """`regex`: a `regex_matcher(...)` object — the host application's regular-expression engine (fdb_plan_desc.regex_match)."""
+            final_stage: bool = False, regex=None, ordered: bool = False, projections: Sequence[Any] = ()) -> PlanDescHolder:
+    """`regex`: a `regex_matcher(...)` object — the host application's regular-expression engine (fdb_plan_desc.regex_match).
+    `projections`: the computed expressions of a Projection operator (physicalplan.Projection): each becomes a projection of the
+    descriptor under its Name() / alias, whatever its form (a literal or an aliased column too)."""
     keep: List[Any] = []
     nodes: List[CExpr] = []
 
@@ -518,17 +525,18 @@ def to_desc(filter_expr: Optional[Expr], aggs: Sequence[AggregationFunction], gr
             raise TypeError(f"unsupported expression in projection: {e}")
         return len(nodes) - 1
 
-    for e in [a.expr for a in aggs] + list(groups):
+    for e in [a.expr for a in aggs] + list(groups) + list(projections):
         inner = e.expr if isinstance(e, AliasExpr) else e
         computed = isinstance(inner, (ConvertExpr, IsNullExpr, IfExpr)) or (
             isinstance(inner, BinaryExpr) and (inner.op in _ARITH or OP_EQ <= inner.op <= OP_GT_EQ or inner.op in (OP_AND, OP_OR)))
-        if not computed or e.name in seen:
+        computed = computed or any(e is p for p in projections)
+        if not computed or expr_name(e) in seen:
             continue
-        seen.add(e.name)
+        seen.add(expr_name(e))
         nodes: List[CProjNode] = []
         root = flatten(inner, nodes)
         arr = (CProjNode * len(nodes))(*nodes)
-        nm = e.name.encode()
+        nm = expr_name(e).encode()
         keep += [arr, nm]
         projs.append(CProjection(name=nm, nodes=ctypes.cast(arr, ctypes.POINTER(CProjNode)), n_nodes=len(nodes), root=root))
     if projs:

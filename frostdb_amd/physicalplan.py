@@ -11,12 +11,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Callable, List, Optional, Sequence
+from typing import Any, Callable, List, Optional, Sequence
 
 import pyarrow as pa
 
 from .arrow_c import ArrowArray, ArrowSchema, ExportedBatch, import_batch
-from .logicalplan import AggregationFunction, Column, Expr, to_desc
+from .logicalplan import AggregationFunction, Column, Expr, expr_name, to_desc
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfrostdb_amd.so")
@@ -132,6 +132,9 @@ def lib() -> ctypes.CDLL:
     L.fdb_plan_filter_batches.argtypes = [vp, P(vp), i32, P(vp), P(i64)]
     L.fdb_plan_select_batch.argtypes = [vp, vp, vp, i64, P(i64)]
     L.fdb_batch_export.argtypes = [vp, vp, vp]
+    L.fdb_plan_project_batch.argtypes = [vp, vp, i32, vp, P(vp)]
+    L.fdb_plan_project_batches.argtypes = [vp, vp, i32, P(vp), i32, P(vp)]
+    L.fdb_plan_project.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.fdb_batch_from_parquet.argtypes = [vp, i32, i64, ctypes.c_int, P(vp)]
     L.fdb_batches_from_parquet.argtypes = [vp, i32, ctypes.c_int, P(vp)]
     _lib = L
@@ -683,6 +686,92 @@ class HashAggregatePlan:
         mm = ctypes.c_double()
         lib().fdb_plan_merge_ms(self.handle, ctypes.byref(mm))
         return {"algorithmic_bytes": b.value, "kernel_ms": ms.value, "launches": n.value, "rows": r.value, "merge_ms": mm.value}
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
+
+class ProjectCol(ctypes.Structure):
+    """fdb_project_col: one item of a Projection's output list."""
+    _fields_ = [("kind", ctypes.c_int32), ("_pad", ctypes.c_int32), ("name", ctypes.c_char_p)]
+
+
+PROJECT_COLUMN, PROJECT_DYNAMIC, PROJECT_COMPUTED, PROJECT_ALL = 0, 1, 2, 3
+
+
+class Projection:
+    """≙ physicalplan.Projection (project.go:906-943) on one GPU: `exprs` is the output list — ``Col(x)`` passes the first field of that
+    name through (a record without it contributes nothing), ``DynCol(x)`` every field under ``x.``, anything else is computed on the
+    device under its Name() / alias. With `filter_expr` the same plan also answers FilterResident (``PredicateFilter → Projection``)."""
+
+    def __init__(self, exprs: Sequence[Any], filter_expr: Optional[Expr] = None, device: int = 0):
+        self.exprs = list(exprs)
+        computed = [e for e in self.exprs if not isinstance(e, Column)]
+        self._desc = to_desc(filter_expr, [], [], projections=computed)
+        self._names = []
+        items = (ProjectCol * max(1, len(self.exprs)))()
+        for i, e in enumerate(self.exprs):
+            nm = expr_name(e).encode()
+            self._names.append(nm)
+            items[i].kind = (PROJECT_DYNAMIC if e.dynamic else PROJECT_COLUMN) if isinstance(e, Column) else PROJECT_COMPUTED
+            items[i].name = nm
+        self._items, self._n_items = items, len(self.exprs)
+        out = ctypes.c_void_p()
+        rc = lib().fdb_plan_create(ctypes.addressof(self._desc.desc), device, ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        self.handle = out.value
+        self.device = device
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            _raise(rc, lib().fdb_plan_last_error(self.handle).decode("utf-8", "replace"))
+
+    def Callback(self, record: pa.RecordBatch) -> pa.RecordBatch:
+        """Host record in, host record out (fdb_plan_project)."""
+        arr, sch = ArrowArray(), ArrowSchema()
+        with ExportedBatch(record) as ex:
+            self._check(lib().fdb_plan_project(self.handle, self._items, self._n_items, ctypes.addressof(ex.array), ctypes.addressof(ex.schema),
+                                               ctypes.addressof(arr), ctypes.addressof(sch)))
+        return import_batch(arr, sch)
+
+    def ProjectResident(self, rb: "ResidentBatch") -> "ResidentBatch":
+        out = ctypes.c_void_p()
+        self._check(lib().fdb_plan_project_batch(self.handle, self._items, self._n_items, rb.handle, ctypes.byref(out)))
+        return ResidentBatch(None, device=self.device, _handle=out.value)
+
+    def ProjectResidentMany(self, rbs: Sequence["ResidentBatch"]) -> List["ResidentBatch"]:
+        """Every record of a scan: one launch for all computed fields (fdb_plan_project_batches)."""
+        n = len(rbs)
+        arr = (ctypes.c_void_p * max(1, n))(*[r.handle for r in rbs])
+        outs = (ctypes.c_void_p * max(1, n))()
+        self._check(lib().fdb_plan_project_batches(self.handle, self._items, self._n_items, arr, n, outs))
+        return [ResidentBatch(None, device=self.device, _handle=outs[i]) for i in range(n)]
+
+    def FilterResident(self, rb: "ResidentBatch") -> "ResidentBatch":
+        """The plan's PredicateFilter on a resident record (fdb_plan_filter_batch); feed the result to ProjectResident."""
+        out, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(lib().fdb_plan_filter_batch(self.handle, rb.handle, ctypes.byref(out), ctypes.byref(n)))
+        return ResidentBatch(None, device=self.device, _handle=out.value)
+
+    def set_timing(self, enabled: bool) -> None:
+        lib().fdb_plan_set_timing(self.handle, 1 if enabled else 0)
+
+    def stats(self) -> dict:
+        b, ms, n, r = ctypes.c_int64(), ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
+        lib().fdb_plan_stats(self.handle, ctypes.byref(b), ctypes.byref(ms), ctypes.byref(n), ctypes.byref(r))
+        return {"algorithmic_bytes": b.value, "kernel_ms": ms.value, "launches": n.value, "rows": r.value}
+
+    def last_kernel(self) -> str:
+        return (lib().fdb_plan_last_kernel(self.handle) or b"").decode()
+
+    def Close(self) -> None:
+        if getattr(self, "handle", None):
+            lib().fdb_plan_close(self.handle)
+            self.handle = None
 
     def __del__(self):
         try:

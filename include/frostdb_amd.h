@@ -309,6 +309,49 @@ FDB_API int fdb_plan_finish_batch(fdb_plan* plan, fdb_batch** out, int64_t* n_ro
  * nothing: on an error no output batch is returned. */
 FDB_API int fdb_plan_filter_batches(fdb_plan* plan, const fdb_batch* const* batches, int32_t n, fdb_batch** out, int64_t* n_selected);
 FDB_API int fdb_plan_select_batch(fdb_plan* plan, const fdb_batch* batch, uint32_t* dev_indices, int64_t capacity, int64_t* n_selected);
+
+/* ---- Projection as an operator of its own (≙ Projection.Callback / Project, physicalplan/project.go:906-943) ----------------------
+ * `TableScan → PredicateFilter → Projection` and the `sum(x) / convert(count(x), float64) as avg(x)` the planner puts behind a final
+ * aggregate (logicalplan/builder.go:205-238). The COMPUTED expressions are the plan's projections[] (a plan with n_aggs == 0,
+ * n_groups == 0 and n_projections > 0 is valid; any plan that has projections may be used — the calls do not touch its aggregate
+ * state, like fdb_plan_filter*; a filter-only plan's fdb_plan_push keeps answering FDB_ERR_STATE); the output list is passed per call.
+ * Output record: fields in `cols` order, each item expanded to 0 … n fields; as many rows as the input; a call that produces no
+ * field at all gives a zero-column, zero-row record; a zero-row input gives zero-row columns of the right types. The result is an
+ * ordinary resident batch (fdb_batch_export, fdb_plan_push_batch(es), fdb_plan_filter_batch, fdb_batch_release) whose lifetime does not
+ * depend on the input's. Pass-through columns keep type, dictionary, values and NULLs bit for bit (device-to-device copies).
+ * Computed fields (semantics as at fdb_proj_node): arithmetic has the type of its left operand (int64 / uint64 / float64); + - *
+ * use the RAW slots and are always valid; / is NULL where the divisor is 0 (float64: == 0, so -0.0 too), else Go's quotient
+ * (truncation toward zero, MinInt64 / -1 wraps); only the OUTERMOST operation's validity survives (an inner NULL reads back as raw 0);
+ * comparison / AND / OR / isnull give a bool column without NULLs (a NULL operand compares false); convert gives float64, always
+ * valid; if gives int64, always valid; a projection whose root is an int64 / uint64 / float64 literal is a constant column of the
+ * record's length (literalProjection, :716-728); a projection whose root is a column is that column under the projection's name
+ * (aliasProjection, :40-56: int64 / uint64 / float64). A division column without a NULL is emitted without a validity bitmap.
+ * Errors: a column missing inside an expression FDB_ERR_NOT_FOUND, mixed operand types FDB_ERR_INVALID, unsupported node / column
+ * types FDB_ERR_UNSUPPORTED, a kind 2 item that names no projection of the plan FDB_ERR_INVALID. Computed items need the run-time
+ * generated kernel: without hiprtc (or under FDB_NO_JIT) a call with one answers FDB_ERR_UNSUPPORTED; pass-through-only calls work.
+ * A computed bool field is held like every resident bool column — one int64 per row, 1 = false / 2 = true (what fdb_batch_import
+ * makes of an Arrow bool column) — not as a bitmap; fdb_batch_export turns it into Arrow's bit-packed form.
+ * At most 16 computed fields per call. Not carried over: boolExprProjection's shortcut for a result column that the table scan
+ * pre-computed (:411-432) — no scan on this path produces one. */
+typedef struct fdb_project_col {
+  int32_t kind;      /* 0 column   — plainProjection (project.go:481-491): the FIRST field named exactly `name`; a record
+                                     without it contributes NOTHING (no error)
+                        1 dynamic  — dynamicProjection (:742-755): every field whose name starts with name + ".", in the
+                                     record's field order; may be none
+                        2 computed — desc.projections[] entry whose name is `name`; the output field carries that name
+                                     (BinaryExpr.Name() or the alias, aliasProjection :40-56)
+                        3 all      — allProjection: every field of the record; `name` ignored */
+  int32_t _pad;
+  const char* name;
+} fdb_project_col;
+FDB_API int fdb_plan_project_batch(fdb_plan* plan, const fdb_project_col* cols, int32_t n_cols, const fdb_batch* in, fdb_batch** out);
+/* `n` resident records (≙ every record of a scan), ONE launch for every computed field of all of them. All or nothing: on an error no
+ * output batch is returned. The records must agree in the types of the columns the expressions read. */
+FDB_API int fdb_plan_project_batches(fdb_plan* plan, const fdb_project_col* cols, int32_t n_cols, const fdb_batch* const* in, int32_t n, fdb_batch** out);
+/* Host record in, host record out: the referenced and passed-through columns are staged (`batch` is only borrowed), projected on
+ * the device and exported. */
+FDB_API int fdb_plan_project(fdb_plan* plan, const fdb_project_col* cols, int32_t n_cols, struct ArrowArray* batch, struct ArrowSchema* schema,
+                             struct ArrowArray* out, struct ArrowSchema* out_schema);
 /* ≙ PhysicalPlan.Draw: "PredicateFilter (…) - HashAggregate (sum(value) by labels.path)". Owned by the plan. */
 FDB_API const char* fdb_plan_draw(fdb_plan* plan);
 /* The same string for a descriptor, without creating a plan or touching a device (≙ `explain`: the operator strings of

@@ -7,7 +7,9 @@
 //       -I frostdb_amd/csrc --cuda-device-only -Rpass-analysis=kernel-resource-usage -c /tmp/k.hip -o /tmp/k.o
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "frostdb_amd.h"
 #include "fdb_kernels.h"
@@ -29,6 +31,56 @@ int main(int argc, char** argv) {
     if (argc > 2) { s.n_c4 = 0; s.leaves = {a}; s.code = {0}; }  // `value > T` alone (bench.py's select line)
     if (select) { s.fuse8 = 1; if (argc > 3) s.fuse4 = 1; }  // the one-pass kernel: `value` (and the dictionary column) compacted by the predicate's own wave
     std::fputs((select ? fdb::jit_select_source(s) : fdb::jit_flags_source(s)).c_str(), stdout);
+    return 0;
+  }
+  if (argc > 2 && std::string(argv[1]) == "project") {
+    // the Projection kernel (fdb_project_kernel) of one or more expressions, written in postfix, tokens separated by ',', expressions by ';':
+    //   c<t><slot>[n]  column of type i (int64) / u (uint64) / f (float64) in 8-byte slot <slot>, n: with a validity bitmap
+    //   l<t>           literal of that type          + - * /   arithmetic (type of the left operand)
+    //   q1 … q6        comparison (fdb_op EQ … GT_EQ)          and / or   over two booleans
+    //   cv  nu  if     convert(int64 → float64) / isnull(column) / if(cond, then, else) — operands pushed in that order
+    //   db<slot>[n]    a dictionary column (4-byte slot) compared with a string literal: truth table in a 64-bit word
+    //   dl<slot>[n]    … truth table in LDS          u8<slot>  a uint64 column (early 8-byte slot) compared as a filter leaf does
+    //   e.g.  project 'ci0,ci1,*'    project 'ci0n,ci1n,/,ci2,+;ci0n,cv,cf3,*'    project 'db0n,ci0,li,q5,and'
+    fdb::JitShape s;
+    s.block = 256; s.two_phase = true; s.lds_acc = false;
+    const std::string spec = argv[2];
+    std::vector<int> st;
+    auto push = [&](fdb::JitExprNode n) { s.exprs.push_back(n); st.push_back((int)s.exprs.size() - 1); };
+    auto pop = [&]() { if (st.empty()) { std::fprintf(stderr, "jit_dump: malformed expression\n"); std::exit(2); } const int v = st.back(); st.pop_back(); return v; };
+    auto type_of = [](char t) { return t == 'i' ? FDB_T_I64 : t == 'u' ? FDB_T_U64 : FDB_T_F64; };
+    size_t at = 0;
+    while (at <= spec.size()) {
+      size_t end = spec.find_first_of(",;", at);
+      if (end == std::string::npos) end = spec.size();
+      const std::string t = spec.substr(at, end - at);
+      const bool nullable = !t.empty() && t.back() == 'n' && t != "and";
+      if (t.size() >= 3 && t[0] == 'c' && (t[1] == 'i' || t[1] == 'u' || t[1] == 'f')) {
+        const int slot = t[2] - '0';
+        s.n_l8 = std::max(s.n_l8, slot + 1); s.l8[slot].has_values = true; if (nullable) s.l8[slot].has_validity = 1;
+        push({0, 0, -1, -1, slot, type_of(t[1])});
+      } else if (t.size() == 2 && t[0] == 'l') push({1, 0, -1, -1, -1, type_of(t[1])});
+      else if (t == "+" || t == "-" || t == "*" || t == "/") {
+        const int r = pop(), l = pop();
+        push({2, t == "+" ? FDB_OP_ADD : t == "-" ? FDB_OP_SUB : t == "*" ? FDB_OP_MUL : FDB_OP_DIV, l, r, -1, s.exprs[(size_t)l].type});
+      } else if (t.size() == 2 && t[0] == 'q') { const int r = pop(), l = pop(); push({3, t[1] - '0', l, r, -1, FDB_T_BOOL}); }
+      else if (t == "and" || t == "or") { const int r = pop(), l = pop(); push({3, t == "and" ? FDB_OP_AND : FDB_OP_OR, l, r, -1, FDB_T_BOOL}); }
+      else if (t == "cv") { const int l = pop(); push({4, 0, l, -1, -1, FDB_T_F64}); }
+      else if (t == "nu") { const int l = pop(); push({5, 0, l, -1, -1, FDB_T_BOOL}); }
+      else if (t == "if") { const int e = pop(), th = pop(), c = pop(); push({6, c, th, e, -1, FDB_T_I64}); }
+      else if (t.size() >= 3 && (t.substr(0, 2) == "db" || t.substr(0, 2) == "dl" || t.substr(0, 2) == "u8")) {
+        const int slot = t[2] - '0';
+        fdb::JitLeaf L;
+        L.slot = slot;
+        if (t[0] == 'u') { L.kind = FDB_LEAF_CMP_U64; L.wide = 1; L.op = 5; s.n_c8 = std::max(s.n_c8, slot + 1); s.c8[slot].has_values = true; if (nullable) s.c8[slot].has_validity = 1; }
+        else { L.kind = t[1] == 'b' ? FDB_LEAF_DICT_BITS : FDB_LEAF_DICT_LUT; L.lut_in_lds = t[1] == 'l'; s.n_c4 = std::max(s.n_c4, slot + 1); s.c4[slot].has_values = true; if (nullable) s.c4[slot].has_validity = 1; }
+        s.leaves.push_back(L);
+        push({7, 0, -1, -1, (int)s.leaves.size() - 1, FDB_T_BOOL});
+      } else if (!t.empty()) { std::fprintf(stderr, "jit_dump: unknown token %s\n", t.c_str()); return 2; }
+      if (end == spec.size() || spec[end] == ';') { s.proj_roots.push_back(pop()); st.clear(); }
+      at = end + 1;
+    }
+    std::fputs(fdb::jit_project_source(s).c_str(), stdout);
     return 0;
   }
   if (argc > 1 && std::string(argv[1]) == "plan") {
