@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "fdb_codec.h"
 #include "fdb_comm.h"
 #include "fdb_context.h"
 #include "fdb_dynamic.h"
@@ -479,31 +480,30 @@ int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_grou
   });
 }
 
-int fdb_snappy_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_snappy_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
-                            int device, uint32_t* status, double* kernel_ms) {
-  static_assert(sizeof(fdb_snappy_page) == sizeof(FdbSnappyPage), "fdb_snappy_page mirrors FdbSnappyPage");
+// fdb_snappy_decode_pages / fdb_lz4_decode_pages: `codec` is parquet.thrift's number, `what` the prefix of the error texts
+static int decode_pages(int codec, const char* what, const uint8_t* src, int64_t src_bytes, const FdbCodecPage* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
+                        int device, uint32_t* status, double* kernel_ms) {
   return guard(nullptr, [&] {
-    if (n_pages < 0 || src_bytes < 0 || dst_bytes < 0 || (n_pages > 0 && (pages == nullptr || status == nullptr))) throw fdb::Error(FDB_ERR_INVALID, "snappy: bad arguments");
-    for (int32_t i = 0; i < n_pages; i++)  // every page stays inside the buffers (the kernel checks a page against its own lengths only)
-      if (pages[i].src_off > (uint64_t)src_bytes || pages[i].src_len > (uint64_t)src_bytes - pages[i].src_off || pages[i].dst_off > (uint64_t)dst_bytes ||
-          pages[i].dst_len > (uint64_t)dst_bytes - pages[i].dst_off)
-        throw fdb::Error(FDB_ERR_INVALID, "snappy: page " + std::to_string(i) + " lies outside the buffers");
+    if (n_pages < 0 || src_bytes < 0 || dst_bytes < 0 || (n_pages > 0 && (pages == nullptr || status == nullptr))) throw fdb::Error(FDB_ERR_INVALID, std::string(what) + ": bad arguments");
+    const int32_t outside = fdb::check_page_table(pages, n_pages, src_bytes, dst_bytes);
+    if (outside >= 0) throw fdb::Error(FDB_ERR_INVALID, std::string(what) + ": page " + std::to_string(outside) + " lies outside the buffers");
     if (kernel_ms) *kernel_ms = 0.0;
     if (n_pages == 0) return;
+    if (device < 0) { fdb::decode_pages_host(codec, src, pages, n_pages, dst, status); return; }  // the host decoder over the same table: no GPU is touched (the kernel's status codes; never 6)
     fdb::hip_check(hipSetDevice(device), "hipSetDevice");
     struct Dev { void* p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } d_src, d_dst, d_pages, d_status;
     struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
     const size_t pad = 64;  // (the kernel's 16-byte moves never start past a page's last byte, but may end up to 15 bytes behind it)
     fdb::hip_check(hipMalloc(&d_src.p, (size_t)src_bytes + pad), "hipMalloc");
     fdb::hip_check(hipMalloc(&d_dst.p, (size_t)dst_bytes + pad), "hipMalloc");
-    fdb::hip_check(hipMalloc(&d_pages.p, (size_t)n_pages * sizeof(FdbSnappyPage)), "hipMalloc");
+    fdb::hip_check(hipMalloc(&d_pages.p, (size_t)n_pages * sizeof(FdbCodecPage)), "hipMalloc");
     fdb::hip_check(hipMalloc(&d_status.p, (size_t)n_pages * 4), "hipMalloc");
     fdb::hip_check(hipMemcpy(d_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice), "hipMemcpy");
-    fdb::hip_check(hipMemcpy(d_pages.p, pages, (size_t)n_pages * sizeof(FdbSnappyPage), hipMemcpyHostToDevice), "hipMemcpy");
+    fdb::hip_check(hipMemcpy(d_pages.p, pages, (size_t)n_pages * sizeof(FdbCodecPage), hipMemcpyHostToDevice), "hipMemcpy");
     fdb::hip_check(hipEventCreate(&e0.e), "hipEventCreate");
     fdb::hip_check(hipEventCreate(&e1.e), "hipEventCreate");
     fdb::hip_check(hipEventRecord(e0.e, nullptr), "hipEventRecord");
-    fdb::hip_check(fdb_launch_snappy_decode((const uint8_t*)d_src.p, (const FdbSnappyPage*)d_pages.p, n_pages, (uint8_t*)d_dst.p, (uint32_t*)d_status.p, nullptr), "snappy launch");
+    fdb::hip_check(fdb_launch_page_decode(codec, (const uint8_t*)d_src.p, (const FdbCodecPage*)d_pages.p, n_pages, (uint8_t*)d_dst.p, (uint32_t*)d_status.p, nullptr), (std::string(what) + " launch").c_str());
     fdb::hip_check(hipEventRecord(e1.e, nullptr), "hipEventRecord");
     fdb::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     float ms = 0.f;
@@ -513,45 +513,16 @@ int fdb_snappy_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_sna
     if (dst_bytes > 0) fdb::hip_check(hipMemcpy(dst, d_dst.p, (size_t)dst_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
   });
 }
+static_assert(sizeof(fdb_snappy_page) == sizeof(FdbCodecPage), "fdb_snappy_page (and fdb_lz4_page, the same type) mirrors FdbCodecPage");
+
+int fdb_snappy_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_snappy_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
+                            int device, uint32_t* status, double* kernel_ms) {
+  return decode_pages(FDB_CODEC_SNAPPY, "snappy", src, src_bytes, reinterpret_cast<const FdbCodecPage*>(pages), n_pages, dst, dst_bytes, device, status, kernel_ms);
+}
 
 int fdb_lz4_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_lz4_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
                          int device, uint32_t* status, double* kernel_ms) {
-  static_assert(sizeof(fdb_lz4_page) == sizeof(FdbLz4Page), "fdb_lz4_page mirrors FdbLz4Page");
-  return guard(nullptr, [&] {
-    if (n_pages < 0 || src_bytes < 0 || dst_bytes < 0 || (n_pages > 0 && (pages == nullptr || status == nullptr))) throw fdb::Error(FDB_ERR_INVALID, "lz4: bad arguments");
-    for (int32_t i = 0; i < n_pages; i++)  // every page stays inside the buffers (the decoders check a page against its own lengths only)
-      if (pages[i].src_off > (uint64_t)src_bytes || pages[i].src_len > (uint64_t)src_bytes - pages[i].src_off || pages[i].dst_off > (uint64_t)dst_bytes ||
-          pages[i].dst_len > (uint64_t)dst_bytes - pages[i].dst_off)
-        throw fdb::Error(FDB_ERR_INVALID, "lz4: page " + std::to_string(i) + " lies outside the buffers");
-    if (kernel_ms) *kernel_ms = 0.0;
-    if (n_pages == 0) return;
-    if (device < 0) {  // the built-in host decoder over the same table: no GPU is touched (the kernel's status codes; never 6)
-      for (int32_t i = 0; i < n_pages; i++)
-        status[i] = fdb::lz4_block_host(src + pages[i].src_off, pages[i].src_len, dst + pages[i].dst_off, pages[i].dst_len);
-      return;
-    }
-    fdb::hip_check(hipSetDevice(device), "hipSetDevice");
-    struct Dev { void* p = nullptr; ~Dev() { if (p) (void)hipFree(p); } } d_src, d_dst, d_pages, d_status;
-    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
-    const size_t pad = 64;  // (the kernel's 16-byte moves never start past a page's last byte, but may end up to 15 bytes behind it)
-    fdb::hip_check(hipMalloc(&d_src.p, (size_t)src_bytes + pad), "hipMalloc");
-    fdb::hip_check(hipMalloc(&d_dst.p, (size_t)dst_bytes + pad), "hipMalloc");
-    fdb::hip_check(hipMalloc(&d_pages.p, (size_t)n_pages * sizeof(FdbLz4Page)), "hipMalloc");
-    fdb::hip_check(hipMalloc(&d_status.p, (size_t)n_pages * 4), "hipMalloc");
-    fdb::hip_check(hipMemcpy(d_src.p, src, (size_t)src_bytes, hipMemcpyHostToDevice), "hipMemcpy");
-    fdb::hip_check(hipMemcpy(d_pages.p, pages, (size_t)n_pages * sizeof(FdbLz4Page), hipMemcpyHostToDevice), "hipMemcpy");
-    fdb::hip_check(hipEventCreate(&e0.e), "hipEventCreate");
-    fdb::hip_check(hipEventCreate(&e1.e), "hipEventCreate");
-    fdb::hip_check(hipEventRecord(e0.e, nullptr), "hipEventRecord");
-    fdb::hip_check(fdb_launch_lz4_decode((const uint8_t*)d_src.p, (const FdbLz4Page*)d_pages.p, n_pages, (uint8_t*)d_dst.p, (uint32_t*)d_status.p, nullptr), "lz4 launch");
-    fdb::hip_check(hipEventRecord(e1.e, nullptr), "hipEventRecord");
-    fdb::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    float ms = 0.f;
-    fdb::hip_check(hipEventElapsedTime(&ms, e0.e, e1.e), "hipEventElapsedTime");
-    if (kernel_ms) *kernel_ms = (double)ms;
-    fdb::hip_check(hipMemcpy(status, d_status.p, (size_t)n_pages * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (dst_bytes > 0) fdb::hip_check(hipMemcpy(dst, d_dst.p, (size_t)dst_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-  });
+  return decode_pages(FDB_CODEC_LZ4_RAW, "lz4", src, src_bytes, reinterpret_cast<const FdbCodecPage*>(pages), n_pages, dst, dst_bytes, device, status, kernel_ms);
 }
 
 int64_t fdb_batch_num_rows(const fdb_batch* batch) { return batch ? batch->b->rows : 0; }

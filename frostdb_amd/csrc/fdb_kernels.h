@@ -825,30 +825,31 @@ struct FdbPqDeltaPage {
 };
 // dense[rank] = value for every non-NULL value of the column (one workgroup per page: unpack, add min_delta, block-wide inclusive
 // scan with the running total of the page carried from tile to tile; int64 arithmetic wraps like the reference's decoder).
-// Snappy block format (format_description.txt) → bytes, on the device: one wave per page. Elements are byte-serial inside a page
-// (every tag says where the next one starts and copies refer to output already produced), pages are independent: the wave parses the
-// tags out of an LDS window of the compressed stream — every lane the same bytes, LDS latency instead of a global round trip per
-// element — and all 64 lanes move the bytes of the element: literals from the stream, copies from the page's own output (a copy's
-// source lies wholly before its destination, byte i of an overlapping pattern comes from source byte i mod offset: no lane waits for
-// another). The page's most recent 64 KiB of output live in an LDS ring (what copies read and write: LDS latency per element instead
-// of a trip to HBM) and leave for HBM in 16 KiB segments. status[page]: 0 = ok, else what failed first (1 length preamble, 2 truncated
-// input, 3 output overrun, 4 bad offset, 5 output short of the announced length, 6 a copy from further back than the ring holds). fdb_batch_from_parquet inflates pages of literals with it; match-heavy pages stay on the host threads.
-struct FdbSnappyPage { uint64_t src_off; uint64_t dst_off; uint32_t src_len; uint32_t dst_len; };
-hipError_t fdb_launch_snappy_decode(const uint8_t* src, const FdbSnappyPage* pages, int32_t n_pages, uint8_t* dst, uint32_t* status, hipStream_t stream);
-// LZ4 block format (lz4_Block_format.md: no frame, no length preamble — a page's output length comes from its table entry) → bytes, on
-// the device, in the shape of the Snappy decoder above: one wave per page, tokens parsed out of an LDS window of the stream, all 64
-// lanes moving a sequence's literals and its match, the same 64 KiB output ring leaving for HBM in 16 KiB segments. What differs is the
-// format: a sequence = token (literal length << 4 | match length − 4), either length extended by bytes that add up to and including the
-// first one ≠ 255, the literals, a 2-byte offset; the last sequence ends behind its literals. A page of literals is ONE sequence with
-// ≈ 4 100 extension bytes per MiB: they are consumed 64 at a time (a ballot over `byte != 255`), not in a lane-serial loop. Matches
-// have no upper length: they are copied 64 bytes at a time, byte i of a chunk from the byte `offset` before it (i mod offset for a
-// pattern shorter than the chunk). status[page] as above, without 1: 2 truncated input, 3 output overrun, 4 bad offset (0, or before the
-// page's first byte), 5 output short of the announced length, 6 a match from further back than the ring holds (offset > 65 472: legal
-// LZ4 — offsets go up to 65 535 —, fdb_parquet.cpp leaves such pages to the host).
-typedef FdbSnappyPage FdbLz4Page;
-hipError_t fdb_launch_lz4_decode(const uint8_t* src, const FdbLz4Page* pages, int32_t n_pages, uint8_t* dst, uint32_t* status, hipStream_t stream);
 hipError_t fdb_launch_pq_delta(const uint8_t* chunk, const FdbPqDeltaPage* pages, int32_t n_pages, const FdbPqDeltaMini* minis, unsigned long long* dense,
                                hipStream_t stream);
+// Compressed pages → bytes, on the device (fdb_codec.hip): one wave per page. Elements are byte-serial inside a page (every tag or token
+// says where the next one starts and copies refer to output already produced), pages are independent: the wave parses the elements out
+// of an LDS window of the compressed stream — every lane the same bytes, LDS latency instead of a global round trip per element — and all
+// 64 lanes move the bytes of the element: literals from the stream, copies from the page's own output (a copy's source lies wholly
+// before its destination, byte i of an overlapping pattern comes from source byte i mod offset: no lane waits for another). The page's
+// most recent 64 KiB of output live in an LDS ring (what copies read and write: LDS latency per element instead of a trip to HBM) and
+// leave for HBM in 16 KiB segments. status[page]: 0 = ok, else what failed first (1 length preamble, 2 truncated input, 3 output
+// overrun, 4 bad offset: 0, or before the page's first byte, 5 output short of the announced length, 6 a copy from further back than
+// the ring holds: offset > FDB_PAGE_RING_REACH — legal in both formats, fdb_parquet.cpp leaves such pages to the host).
+// fdb_batch_from_parquet inflates pages of literals with it; match-heavy pages stay on the host threads.
+// snappy_decode_kernel — the Snappy block format (format_description.txt): a varint preamble with the uncompressed length, then literals
+// (length in the tag or in 1 … 4 bytes behind it) and copies of ≤ 64 bytes with a 1-, 2- or 4-byte offset.
+// lz4_decode_kernel — the LZ4 block format (lz4_Block_format.md: no frame, no length preamble — a page's output length comes from its
+// table entry, so status is never 1): a sequence = token (literal length << 4 | match length − 4), either length extended by bytes that
+// add up to and including the first one ≠ 255, the literals, a 2-byte offset (up to 65 535); the last sequence ends behind its literals. A
+// page of literals is ONE sequence with ≈ 4 100 extension bytes per MiB: they are consumed 64 at a time (a ballot over `byte != 255`),
+// not in a lane-serial loop. Matches have no upper length: they are copied 64 bytes at a time.
+#define FDB_PAGE_RING_REACH 65472u  // the ring's 64 KiB less the 64 bytes a wave writes at a time: the furthest back a copy may reach on the device
+#define FDB_CODEC_SNAPPY 1          // parquet.thrift CompressionCodec
+#define FDB_CODEC_LZ4_RAW 7
+struct FdbCodecPage { uint64_t src_off; uint64_t dst_off; uint32_t src_len; uint32_t dst_len; };  // compressed bytes [src_off, + src_len) of src → bytes [dst_off, + dst_len) of dst
+// codec: FDB_CODEC_SNAPPY or FDB_CODEC_LZ4_RAW (anything else: hipErrorInvalidValue)
+hipError_t fdb_launch_page_decode(int codec, const uint8_t* src, const FdbCodecPage* pages, int32_t n_pages, uint8_t* dst, uint32_t* status, hipStream_t stream);
 // Dictionary-encoded INT64 / DOUBLE chunks in one pass: out[r] = dictionary[index of row r] — or the PLAIN value of row r where pages[]
 // says the row's page is PLAIN (a writer's fallback inside the chunk) —, 0 for NULL rows; validity / prefix as for fdb_launch_pq_decode.
 // The dictionary is the n_dict 8-byte values at chunk + dict_off (any byte alignment); n_values = the chunk's non-NULL values. An index

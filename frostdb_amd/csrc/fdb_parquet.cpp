@@ -16,7 +16,7 @@
 // BYTE_ARRAY dictionary-encoded, PLAIN (also as a fallback inside a dictionary-encoded chunk), DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY;
 // required or optional (max definition level 1); data pages V1 and V2; UNCOMPRESSED, SNAPPY, GZIP, BROTLI, ZSTD, LZ4(_RAW), inflated
 // on the host while the page headers are walked (SNAPPY and LZ4_RAW pages of literals on the device: snappy_decode_kernel, lz4_decode_kernel).
-// LZ4 pages do not depend on liblz4: where dlopen does not find it, the built-in block decoder below (lz4_raw) inflates them.
+// LZ4 pages do not depend on liblz4: where dlopen does not find it, the built-in block decoder (fdb_codec.cpp lz4_raw) inflates them.
 // FDB_ERR_UNSUPPORTED: repeated (list) and nested columns, INT32 / FLOAT and the other physical types, DELTA_BINARY_PACKED pages mixed
 // with other encodings in one chunk, a dictionary page on a BOOLEAN chunk.
 #include <dlfcn.h>
@@ -40,6 +40,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "fdb_codec.h"
 #include "fdb_hostpool.h"
 #include "fdb_context.h"
 #include "fdb_kernels.h"
@@ -266,196 +267,14 @@ void scan_runs(const uint8_t* chunk, size_t off, size_t len, int bw, int64_t n_v
 // file's bytes. Codec numbers are parquet.thrift's CompressionCodec.
 enum { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_GZIP = 2, CODEC_BROTLI = 4, CODEC_LZ4_HADOOP = 5, CODEC_ZSTD = 6, CODEC_LZ4_RAW = 7 };
 
-bool snappy_raw(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {  // the Snappy block format (format_description.txt)
-  size_t ip = 0, op = 0;
-  uint64_t len = 0;
-  for (int shift = 0;; shift += 7) {  // preamble: uncompressed length as a varint
-    if (ip >= n || shift > 35) return false;
-    const uint8_t b = src[ip++];
-    len |= (uint64_t)(b & 0x7F) << shift;
-    if (!(b & 0x80)) break;
-  }
-  if (len != cap) return false;
-  while (ip < n) {
-    const uint8_t tag = src[ip++];
-    if ((tag & 3) == 0) {  // literal
-      size_t l = (size_t)(tag >> 2) + 1;
-      if (l > 60) {
-        const size_t extra = l - 60;
-        if (ip + extra > n) return false;
-        l = 0;
-        for (size_t i = 0; i < extra; i++) l |= (size_t)src[ip + i] << (8 * i);
-        l += 1;
-        ip += extra;
-      }
-      if (ip + l > n || op + l > cap) return false;
-      std::memcpy(dst + op, src + ip, l);
-      ip += l; op += l;
-      continue;
-    }
-    size_t l, off;
-    if ((tag & 3) == 1) { if (ip + 1 > n) return false; l = 4 + ((tag >> 2) & 7); off = ((size_t)(tag >> 5) << 8) | src[ip]; ip += 1; }
-    else if ((tag & 3) == 2) { if (ip + 2 > n) return false; l = (size_t)(tag >> 2) + 1; off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8); ip += 2; }
-    else { if (ip + 4 > n) return false; l = (size_t)(tag >> 2) + 1; off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8) | ((size_t)src[ip + 2] << 16) | ((size_t)src[ip + 3] << 24); ip += 4; }
-    if (off == 0 || off > op || op + l > cap) return false;
-    if (off >= l) std::memcpy(dst + op, dst + op - off, l);  // disjoint
-    else if (off >= 8) { for (size_t i = 0; i < l; i += 8) std::memcpy(dst + op + i, dst + op - off + i, std::min<size_t>(8, l - i)); }  // a pattern of ≥ 8 bytes: 8 at a time
-    else for (size_t i = 0; i < l; i++) dst[op + i] = dst[op - off + i];  // short pattern repeated: byte by byte
-    op += l;
-  }
-  return op == cap;
-}
-
-// The first `want` bytes of a Snappy page (the definition levels at the head of a V1 page whose values are inflated on the device):
-// the same walk, stopped as soon as `want` bytes exist. `cap` = the page's announced uncompressed size.
-bool snappy_prefix(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t want) {
-  size_t ip = 0, op = 0;
-  uint64_t len = 0;
-  for (int shift = 0;; shift += 7) {
-    if (ip >= n || shift > 35) return false;
-    const uint8_t b = src[ip++];
-    len |= (uint64_t)(b & 0x7F) << shift;
-    if (!(b & 0x80)) break;
-  }
-  if (len != cap || want > cap) return false;
-  while (ip < n && op < want) {
-    const uint8_t tag = src[ip++];
-    if ((tag & 3) == 0) {
-      size_t l = (size_t)(tag >> 2) + 1;
-      if (l > 60) {
-        const size_t extra = l - 60;
-        if (ip + extra > n) return false;
-        l = 0;
-        for (size_t i = 0; i < extra; i++) l |= (size_t)src[ip + i] << (8 * i);
-        l += 1;
-        ip += extra;
-      }
-      if (ip + l > n || op + l > cap) return false;
-      std::memcpy(dst + op, src + ip, std::min(l, want - op));
-      ip += l; op += l;
-      continue;
-    }
-    size_t l, off;
-    if ((tag & 3) == 1) { if (ip + 1 > n) return false; l = 4 + ((tag >> 2) & 7); off = ((size_t)(tag >> 5) << 8) | src[ip]; ip += 1; }
-    else if ((tag & 3) == 2) { if (ip + 2 > n) return false; l = (size_t)(tag >> 2) + 1; off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8); ip += 2; }
-    else { if (ip + 4 > n) return false; l = (size_t)(tag >> 2) + 1; off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8) | ((size_t)src[ip + 2] << 16) | ((size_t)src[ip + 3] << 24); ip += 4; }
-    if (off == 0 || off > op || op + l > cap) return false;
-    for (size_t i = 0; i < l && op + i < want; i++) dst[op + i] = dst[op - off + i];
-    op += l;
-  }
-  return op >= want;
-}
-
-// May the device's decoder take this Snappy page? It keeps the page's last 64 KiB of output in an LDS ring, so a copy that reaches
-// further back than that (offset > 65 472: legal Snappy — a 4-byte-offset element, or a block longer than 64 KiB as klauspost/compress
-// writes them for parquet-go, go.mod) is beyond it. Walks the element tags only (literals are skipped, nothing is copied): a page of
-// literals has a handful of them. A malformed stream also answers "no": the host's inflate then reports it.
-bool snappy_device_ok(const uint8_t* src, size_t n) {
-  size_t ip = 0;
-  for (int shift = 0;; shift += 7) {
-    if (ip >= n || shift > 35) return false;
-    if (!(src[ip++] & 0x80)) break;
-  }
-  while (ip < n) {
-    const uint8_t tag = src[ip++];
-    if ((tag & 3) == 0) {
-      size_t l = (size_t)(tag >> 2) + 1;
-      if (l > 60) {
-        const size_t extra = l - 60;
-        if (ip + extra > n) return false;
-        l = 0;
-        for (size_t i = 0; i < extra; i++) l |= (size_t)src[ip + i] << (8 * i);
-        l += 1;
-        ip += extra;
-      }
-      if (l > n - ip) return false;
-      ip += l;
-      continue;
-    }
-    size_t off;
-    if ((tag & 3) == 1) { if (ip + 1 > n) return false; off = ((size_t)(tag >> 5) << 8) | src[ip]; ip += 1; }
-    else if ((tag & 3) == 2) { if (ip + 2 > n) return false; off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8); ip += 2; }
-    else { if (ip + 4 > n) return false; off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8) | ((size_t)src[ip + 2] << 16) | ((size_t)src[ip + 3] << 24); ip += 4; }
-    if (off > 65472) return false;
-  }
-  return true;
-}
-
-// The LZ4 block format (lz4_Block_format.md), built in: a sequence = token (literal length << 4 | match length − 4), either length
-// extended by bytes that add up to and including the first one ≠ 255, the literals, a 2-byte little-endian offset (1 … 65 535); the
-// last sequence ends behind its literals. No frame and no length preamble: `cap` is the page's announced size. Decodes until `want`
-// bytes exist (want < cap: a prefix, nothing is written at or behind dst + want) or, with want == cap, the whole block, which must
-// then fill dst exactly. Accepts what LZ4_decompress_safe accepts (and blocks that end in a match, which that one refuses).
-// Returns 0, or what failed first, in lz4_decode_kernel's codes and order: 2 truncated input, 3 output overrun, 4 bad offset, 5 output short.
-uint32_t lz4_block(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t want) {
-  if (want > cap) return 3;
-  const bool whole = want == cap;
-  size_t ip = 0, op = 0;
-  auto extend = [&](size_t* len) {
-    uint8_t b;
-    do { if (ip >= n) return false; b = src[ip++]; *len += b; } while (b == 255);
-    return true;
-  };
-  while (ip < n) {
-    const uint8_t token = src[ip++];
-    size_t ll = token >> 4, ml = token & 15;
-    if (ll == 15 && !extend(&ll)) return 2;
-    if (ll > n - ip) return 2;
-    if (ll > cap - op) return 3;
-    if (op < want) std::memcpy(dst + op, src + ip, std::min(ll, want - op));
-    ip += ll; op += ll;
-    if (!whole && op >= want) return 0;
-    if (ip == n) break;
-    if (n - ip < 2) return 2;
-    const size_t off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8);
-    ip += 2;
-    if (ml == 15 && !extend(&ml)) return 2;
-    ml += 4;
-    if (off == 0 || off > op) return 4;
-    if (ml > cap - op) return 3;
-    const size_t m = op < want ? std::min(ml, want - op) : 0;
-    if (off >= m) std::memcpy(dst + op, dst + op - off, m);  // disjoint
-    else if (off >= 8) { for (size_t i = 0; i < m; i += 8) std::memcpy(dst + op + i, dst + op - off + i, std::min<size_t>(8, m - i)); }  // a pattern of ≥ 8 bytes: 8 at a time
-    else for (size_t i = 0; i < m; i++) dst[op + i] = dst[op - off + i];  // short pattern repeated: byte by byte
-    op += ml;
-    if (!whole && op >= want) return 0;
-  }
-  return (whole ? op == cap : op >= want) ? 0u : 5u;
-}
-bool lz4_raw(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) { return lz4_block(src, n, dst, cap, cap) == 0; }
-// The first `want` bytes of an LZ4 page (the definition levels at the head of a V1 page whose values are inflated on the device).
-bool lz4_prefix(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t want) { return lz4_block(src, n, dst, cap, want) == 0; }
-
-// May the device's decoder take this LZ4 page? Like snappy_device_ok: the token walk only, "no" for a match from further back than the
-// ring keeps (offset > 65 472, the Snappy kernel's bound: the two share ring and segment sizes; LZ4 offsets go up to 65 535, so such
-// pages are legal and the host inflates them) and for a malformed stream (the host's inflate then reports it).
-bool lz4_device_ok(const uint8_t* src, size_t n) {
-  size_t ip = 0;
-  auto extend = [&](size_t* len) {
-    uint8_t b;
-    do { if (ip >= n) return false; b = src[ip++]; *len += b; } while (b == 255);
-    return true;
-  };
-  while (ip < n) {
-    const uint8_t token = src[ip++];
-    size_t ll = token >> 4, ml = token & 15;
-    if (ll == 15 && !extend(&ll)) return false;
-    if (ll > n - ip) return false;
-    ip += ll;
-    if (ip == n) break;
-    if (n - ip < 2) return false;
-    const size_t off = (size_t)src[ip] | ((size_t)src[ip + 1] << 8);
-    ip += 2;
-    if (ml == 15 && !extend(&ml)) return false;
-    if (off == 0 || off > 65472) return false;
-  }
-  return true;
-}
+static_assert(CODEC_SNAPPY == FDB_CODEC_SNAPPY && CODEC_LZ4_RAW == FDB_CODEC_LZ4_RAW, "fdb_launch_page_decode takes the chunk's codec as it is");
+// what every refusal of a damaged Snappy / LZ4 page starts with
+std::string corrupt_page(int codec) { return codec == CODEC_SNAPPY ? "parquet: corrupt Snappy page" : "parquet: corrupt LZ4 page"; }
 
 typedef int (*lz4_fn)(const char*, char*, int, int);
 typedef size_t (*zstd_fn)(void*, size_t, const void*, size_t);
 typedef unsigned (*zstd_err_fn)(size_t);
-// liblz4's decoder where the host has it ($FDB_PARQUET_BUILTIN_LZ4: as if it had not), lz4_raw above where it has not
+// liblz4's decoder where the host has it ($FDB_PARQUET_BUILTIN_LZ4: as if it had not), lz4_raw (fdb_codec.cpp) where it has not
 lz4_fn lz4_decompress() {
   static lz4_fn f = [] {
     if (std::getenv("FDB_PARQUET_BUILTIN_LZ4") != nullptr) return (lz4_fn) nullptr;
@@ -488,7 +307,7 @@ void inflate_page(int codec, const uint8_t* src, size_t n, uint8_t* dst, size_t 
   if (cap == 0) return;
   switch (codec) {
     case CODEC_SNAPPY:
-      if (!snappy_raw(src, n, dst, cap)) throw Error(FDB_ERR_INVALID, "parquet: corrupt Snappy page");
+      if (!snappy_raw(src, n, dst, cap)) throw Error(FDB_ERR_INVALID, corrupt_page(codec));
       return;
     case CODEC_GZIP: {
       z_stream z;
@@ -526,7 +345,7 @@ void inflate_page(int codec, const uint8_t* src, size_t n, uint8_t* dst, size_t 
         if (ip + cl > n || op + ul > cap || !lz4_inflate(src + ip, cl, dst + op, ul)) break;
         ip += cl; op += ul;
       }
-      if (op != cap) throw Error(FDB_ERR_INVALID, "parquet: corrupt LZ4 page");
+      if (op != cap) throw Error(FDB_ERR_INVALID, corrupt_page(codec));
       return;
     }
     default:
@@ -720,13 +539,11 @@ void plan_chunk(const fdb_parquet_chunk& c, int64_t n_rows, bool device_inflate,
     if (g.device) {
       if (g.v1_levels) {  // <4-byte length> <RLE levels> at the head of the inflated body: the host reads them, the device inflates them again with the values
         uint32_t dl = 0;
-        const bool lz4 = c.codec == CODEC_LZ4_RAW;
-        const char* corrupt = lz4 ? "parquet: corrupt LZ4 page" : "parquet: corrupt Snappy page";
-        auto head = [&](size_t want) { return lz4 ? lz4_prefix(g.raw, g.comp, dst, g.body_len, want) : snappy_prefix(g.raw, g.comp, dst, g.body_len, want); };
-        if (g.body_len < 4 || !head(4)) throw Error(FDB_ERR_INVALID, corrupt);
+        auto head = [&](size_t want) { return c.codec == CODEC_LZ4_RAW ? lz4_prefix(g.raw, g.comp, dst, g.body_len, want) : snappy_prefix(g.raw, g.comp, dst, g.body_len, want); };
+        if (g.body_len < 4 || !head(4)) throw Error(FDB_ERR_INVALID, corrupt_page(c.codec));
         std::memcpy(&dl, dst, 4);
         if ((size_t)dl + 4 > g.body_len) throw Error(FDB_ERR_INVALID, "parquet: definition levels run past the page");
-        if (!head((size_t)dl + 4)) throw Error(FDB_ERR_INVALID, corrupt);
+        if (!head((size_t)dl + 4)) throw Error(FDB_ERR_INVALID, corrupt_page(c.codec));
       }
       out->dev_pages.push_back(ParsedChunk::DevPage{(size_t)(g.raw - c.data) + g.prefix, g.comp - g.prefix, at + g.prefix, g.body_len - g.prefix});
       if (g.prefix > 0) out->host_spans.emplace_back(at, at + g.prefix);
@@ -975,7 +792,6 @@ void parquet_stats(int64_t* calls, double* host_ms, double* device_ms, int64_t* 
   if (out_bytes) *out_bytes = g_pq_out_bytes.load();
 }
 
-uint32_t lz4_block_host(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) { return lz4_block(src, n, dst, cap, cap); }
 
 void parquet_device_pages(int codec, int64_t* pages, int64_t* bytes) {
   if (codec < 0 || codec >= 8) throw Error(FDB_ERR_INVALID, "parquet: no such compression codec");
@@ -1189,8 +1005,8 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
   // ---- (4) device part, chunk by chunk in the order the parses complete: a row group's 40 MB of PLAIN values (parsed in 50 µs) must not
   // wait for the 1–2 ms run-header walk of the dictionary column next to it before it may cross PCIe ----------------------------------
   hipStream_t stream = nullptr;
-  std::list<std::vector<FdbSnappyPage>> snappy_tables;                                       // device-inflated pages (SNAPPY or LZ4_RAW: the chunk's codec says which): per chunk, the launch's page table …
-  std::list<std::tuple<const uint32_t*, size_t, int32_t, int32_t>> snappy_status;            // … and where its verdicts land (pinned host copy, pages, row group, chunk)
+  std::list<std::vector<FdbCodecPage>> codec_tables;                                       // device-inflated pages (SNAPPY or LZ4_RAW: the chunk's codec says which): per chunk, the launch's page table …
+  std::list<std::tuple<const uint32_t*, size_t, int32_t, int32_t>> codec_status;            // … and where its verdicts land (pinned host copy, pages, row group, chunk)
   uint32_t* d_flags = nullptr;
   uint32_t* h_flags = nullptr;
   int32_t n_flags = 0;
@@ -1286,20 +1102,19 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
         uint8_t* d_raw = (uint8_t*)ctx->dev_alloc(hi - lo + 64);
         scratch.push_back(d_raw);
         h2d(d_raw, c.data + lo, hi - lo, "hipMemcpyAsync(compressed pages)");
-        std::vector<FdbSnappyPage> table;
-        for (const ParsedChunk::DevPage& q : P.dev_pages) table.push_back(FdbSnappyPage{(uint64_t)(q.raw_off - lo), (uint64_t)q.at, (uint32_t)q.comp, (uint32_t)q.len});
-        snappy_tables.push_back(std::move(table));  // (kept alive until the copy below has read it)
-        const std::vector<FdbSnappyPage>& T = snappy_tables.back();
-        const FdbSnappyPage* d_table = (const FdbSnappyPage*)to_device(T.data(), T.size() * sizeof(FdbSnappyPage));
+        std::vector<FdbCodecPage> table;
+        for (const ParsedChunk::DevPage& q : P.dev_pages) table.push_back(FdbCodecPage{(uint64_t)(q.raw_off - lo), (uint64_t)q.at, (uint32_t)q.comp, (uint32_t)q.len});
+        codec_tables.push_back(std::move(table));  // (kept alive until the copy below has read it)
+        const std::vector<FdbCodecPage>& T = codec_tables.back();
+        const FdbCodecPage* d_table = (const FdbCodecPage*)to_device(T.data(), T.size() * sizeof(FdbCodecPage));
         uint32_t* d_status = (uint32_t*)ctx->dev_alloc(T.size() * 4 + 16);
         scratch.push_back(d_status);
         fence();
-        if (c.codec == CODEC_LZ4_RAW) hip_check(fdb_launch_lz4_decode(d_raw, d_table, (int32_t)T.size(), d_chunk, d_status, stream), "lz4 decode");
-        else hip_check(fdb_launch_snappy_decode(d_raw, d_table, (int32_t)T.size(), d_chunk, d_status, stream), "snappy decode");
+        hip_check(fdb_launch_page_decode(c.codec, d_raw, d_table, (int32_t)T.size(), d_chunk, d_status, stream), c.codec == CODEC_LZ4_RAW ? "lz4 decode" : "snappy decode");
         uint32_t* h_status = (uint32_t*)pinned.take(T.size() * 4);
         std::memset(h_status, 0xFF, T.size() * 4);  // (a verdict that never arrives is not "ok")
-        snappy_status.emplace_back(h_status, T.size(), g, i);
-        hip_check(hipMemcpyAsync(h_status, d_status, T.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(snappy status)");
+        codec_status.emplace_back(h_status, T.size(), g, i);
+        hip_check(hipMemcpyAsync(h_status, d_status, T.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(codec status)");
       }
       uint32_t* d_valid = nullptr;
       uint32_t* d_prefix = nullptr;
@@ -1436,11 +1251,11 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
     if (n_flags > 0) hip_check(hipMemcpyAsync(h_flags, d_flags, (size_t)n_flags * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(index checks)");
     hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(parquet decode)");
   }
-  for (const auto& st : snappy_status)
+  for (const auto& st : codec_status)
     for (size_t q = 0; q < std::get<1>(st); q++)
       if (std::get<0>(st)[q] != 0) {
         const fdb_parquet_chunk& bad = G[(size_t)std::get<2>(st)].chunks[std::get<3>(st)];
-        throw Error(FDB_ERR_INVALID, std::string(bad.codec == CODEC_LZ4_RAW ? "parquet: corrupt LZ4 page in column " : "parquet: corrupt Snappy page in column ") + (bad.name ? bad.name : "?"));
+        throw Error(FDB_ERR_INVALID, corrupt_page(bad.codec) + " in column " + (bad.name ? bad.name : "?"));
       }
   int64_t dev_pages[2] = {0, 0}, dev_bytes[2] = {0, 0};  // [0] SNAPPY, [1] LZ4_RAW: the two codecs plan_chunk sends to the device
   for (const Group& R : G)

@@ -82,9 +82,6 @@ std::unique_ptr<DeviceBatch> batch_from_parquet(const fdb_parquet_chunk* chunks,
 std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_groups, int device);
 void parquet_stats(int64_t* calls, double* host_ms, double* device_ms, int64_t* file_bytes, int64_t* out_bytes);
 void parquet_device_pages(int codec, int64_t* pages, int64_t* bytes);  // pages / output bytes the device inflated, per CompressionCodec
-// the built-in LZ4 block decoder of fdb_parquet.cpp (host): dst[0, cap) = the block src[0, n); 0, or lz4_decode_kernel's code for what
-// failed first (2 truncated input, 3 output overrun, 4 bad offset, 5 output short of cap)
-uint32_t lz4_block_host(const uint8_t* src, size_t n, uint8_t* dst, size_t cap);
 // The record of a resident batch as Arrow in host memory.
 void export_batch(const DeviceBatch& b, ArrowArray* out, ArrowSchema* out_schema);
 

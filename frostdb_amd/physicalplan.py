@@ -793,8 +793,8 @@ def execute(records: Sequence, filter_expr: Optional[Expr], aggs: Sequence[Aggre
 
 
 def snappy_decode_pages(pages: "list[bytes]", sizes: "list[int]", device: int = 0):
-    """Snappy-compressed pages → their bytes, inflated on the device (fdb_snappy_decode_pages; tests and measurement).
-    Returns (list of bytes — None for a page the decoder refused —, list of status codes, kernel milliseconds)."""
+    """Snappy-compressed pages → their bytes, inflated on the device (fdb_snappy_decode_pages; tests and measurement);
+    device < 0: by the library's host decoder, without a GPU (the same status codes but 6). Returns (list of bytes — None for a page the decoder refused —, list of status codes, kernel milliseconds)."""
     return _decode_pages(lib().fdb_snappy_decode_pages, pages, sizes, device)
 
 

@@ -524,7 +524,9 @@ FDB_API int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_
  * device, decoded by ONE launch, and `dst` is copied back. status[i]: 0 = ok, 1 length preamble ≠ dst_len, 2 truncated input,
  * 3 output overrun, 4 copy offset outside the output, 5 output shorter than announced, 6 a copy from more than 65 472 bytes back (the
  * format allows it, no compressor emits it: matches stay inside a 64 KiB fragment) (a page that fails leaves its part of `dst`
- * undefined; the others are unaffected). *kernel_ms (may be NULL): device time of the launch. */
+ * undefined; the others are unaffected). *kernel_ms (may be NULL): device time of the launch. device < 0: the library's HOST decoder
+ * runs over the same page table and no GPU is touched (the same status codes but 6: any offset is fine there; *kernel_ms = 0) — the
+ * decoder fdb_batch_from_parquet uses for the Snappy pages the device does not take. */
 typedef struct fdb_snappy_page { uint64_t src_off; uint64_t dst_off; uint32_t src_len; uint32_t dst_len; } fdb_snappy_page;
 FDB_API int fdb_snappy_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_snappy_page* pages, int32_t n_pages, uint8_t* dst, int64_t dst_bytes,
                             int device, uint32_t* status, double* kernel_ms);

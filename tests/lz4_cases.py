@@ -7,11 +7,11 @@ import numpy as np
 import pyarrow as pa
 import pyarrow.parquet as pq
 
-RING_REACH = 65_472  # the furthest back a match may reach on the device (fdb_kernels.hip: SNAPPY_RING - 64); LZ4 allows 65 535
+RING_REACH = 65_472  # the furthest back a match may reach on the device (fdb_kernels.h: FDB_PAGE_RING_REACH); LZ4 allows 65 535
 
 
 def payloads():
-    """The families of tests/test_gpu_snappy.py::_payloads, with a match 60 000 bytes back (inside LZ4's 64 KiB window)."""
+    """The families of tests/snappy_cases.py payloads, with a match 60 000 bytes back (inside LZ4's 64 KiB window)."""
     rng = np.random.default_rng(11)
     out = [b"", b"x", b"ab" * 3, bytes(range(60)), bytes(range(61)), bytes(rng.integers(0, 256, 59, dtype=np.uint8)), bytes(rng.integers(0, 256, 300, dtype=np.uint8)),
            bytes(rng.integers(0, 256, 70_000, dtype=np.uint8)),             # incompressible: one sequence, 274 extension bytes

@@ -1,4 +1,4 @@
-"""The library's built-in LZ4 block decoder (fdb_parquet.cpp lz4_raw, reached through fdb_lz4_decode_pages with device < 0: no GPU is
+"""The library's built-in LZ4 block decoder (fdb_codec.cpp lz4_raw, reached through fdb_lz4_decode_pages with device < 0: no GPU is
 touched), and the Parquet path's use of it where liblz4 is not installed ($FDB_PARQUET_BUILTIN_LZ4 hides it): bit-identical to pyarrow's
 lz4_raw codec on compressor output and on hand-made streams that only the format allows; damaged pages refused one by one."""
 import os

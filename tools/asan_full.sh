@@ -11,10 +11,11 @@ mkdir -p "$OUT"
 SRC="$ROOT/frostdb_amd/csrc"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 python -c "import sys; sys.path.insert(0, '$ROOT'); from frostdb_amd import build; build.build()" > /dev/null   # (writes fdb_kernels_h.inc)
-for f in fdb_arrow fdb_context fdb_plan fdb_hash fdb_jit fdb_dynamic fdb_comm fdb_parquet fdb_regex fdb_capi; do
+for f in fdb_arrow fdb_context fdb_plan fdb_hash fdb_jit fdb_dynamic fdb_comm fdb_parquet fdb_codec fdb_regex fdb_capi; do
   $HIPCC --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -munsafe-fp-atomics -fsanitize=address,undefined -fno-gpu-sanitize -x hip -c "$SRC/$f.cpp" -o "$OUT/$f.o"
 done
 $HIPCC --offload-arch=gfx950 -O1 -std=c++17 -fPIC -munsafe-fp-atomics -fno-gpu-sanitize -c "$SRC/fdb_kernels.hip" -o "$OUT/fdb_kernels.o"
+$HIPCC --offload-arch=gfx950 -O1 -std=c++17 -fPIC -fno-gpu-sanitize -c "$SRC/fdb_codec.hip" -o "$OUT/fdb_codec_hip.o"
 $HIPCC --offload-arch=gfx950 -O1 -std=c++17 -fPIC -fno-gpu-sanitize -c "$SRC/fdb_sort.hip" -o "$OUT/fdb_sort.o"
 $HIPCC --offload-arch=gfx950 -O1 -std=c++17 -fPIC -munsafe-fp-atomics -fno-gpu-sanitize -c "$SRC/fdb_merge.hip" -o "$OUT/fdb_merge.o"
 $HIPCC -O1 -g -std=c++17 -fPIC -fsanitize=address,undefined -c "$SRC/fdb_widen.cc" -o "$OUT/fdb_widen.o"

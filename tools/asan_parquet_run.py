@@ -108,30 +108,32 @@ for kw in variants:
         _dt = _t.time() - _t0
         if _dt > 2: print("slow call", round(_dt, 1), "s variant", kw, "victim", chunks[victim][0], "rc", rc, flush=True)
         codes[rc] = codes.get(rc, 0) + 1; total += 1
-# the built-in LZ4 block decoder itself (fdb_lz4_decode_pages, device = -1): mutated blocks in exact-size buffers, output sizes right and
-# wrong; every page must come back with a verdict and, where the verdict is 0 and the announced size is the true one, with the bytes
-lib.fdb_lz4_decode_pages.restype = ctypes.c_int
-lz4 = pa.Codec("lz4_raw")
+# the host block decoders themselves (fdb_lz4_decode_pages / fdb_snappy_decode_pages, device = -1): mutated blocks in exact-size buffers,
+# output sizes right and wrong; every page must come back with a verdict and, where the verdict is 0 and the announced size is the true
+# one, with the bytes
 plains = [bytes(rng.integers(0, 256, 5000, dtype=np.uint8)), np.arange(3000, dtype=np.int64).tobytes(), b"abc" * 3000, b"\x00" * 70000,
           rng.integers(0, 6, 20000).astype(np.uint32).tobytes(), b"x"]
 verdicts = {}
-for plain in plains:
-    good = lz4.compress(plain, asbytes=True)
-    for it in range(4 * (int(sys.argv[1]) if len(sys.argv) > 1 else 100)):
-        b = bytearray(good); want = len(plain)
-        r = random.random()
-        if it == 0: pass
-        elif r < 0.5:
-            for _ in range(random.randint(1, 4)): b[random.randrange(len(b))] = random.randrange(256)
-        elif r < 0.7: b = b[: random.randrange(0, len(b))]
-        elif r < 0.8: k = random.randrange(len(b)); l = random.randint(1, 300); b[k:k + l] = b"\xff" * l
-        elif r < 0.9: want = max(0, want + random.randint(-20, 20))
-        else: k = random.randrange(len(b)); b[k:k] = bytes(random.randrange(256) for _ in range(random.randint(1, 20)))
-        src = (ctypes.c_ubyte * len(b)).from_buffer_copy(bytes(b)) if len(b) else (ctypes.c_ubyte * 1)()
-        dst = (ctypes.c_ubyte * max(want, 1))()
-        table = (ctypes.c_uint64 * 3)(0, 0, len(b) | (want << 32)); st = ctypes.c_uint32(9)
-        rc = lib.fdb_lz4_decode_pages(src, ctypes.c_int64(len(b)), table, 1, dst, ctypes.c_int64(want), -1, ctypes.byref(st), None)
-        assert rc == 0 and st.value in (0, 2, 3, 4, 5), (rc, st.value)
-        if it == 0: assert st.value == 0 and bytes(dst[:want]) == plain
-        verdicts[st.value] = verdicts.get(st.value, 0) + 1
-print("variants", len(variants), "runs", total, "return codes", codes, "lz4 block verdicts", verdicts)
+for name, entry, allowed in (("lz4_raw", lib.fdb_lz4_decode_pages, (0, 2, 3, 4, 5)), ("snappy", lib.fdb_snappy_decode_pages, (0, 1, 2, 3, 4, 5))):
+    entry.restype = ctypes.c_int
+    codec = pa.Codec(name); verdicts[name] = {}
+    for plain in plains:
+        good = codec.compress(plain, asbytes=True)
+        for it in range(4 * (int(sys.argv[1]) if len(sys.argv) > 1 else 100)):
+            b = bytearray(good); want = len(plain)
+            r = random.random()
+            if it == 0: pass
+            elif r < 0.5:
+                for _ in range(random.randint(1, 4)): b[random.randrange(len(b))] = random.randrange(256)
+            elif r < 0.7: b = b[: random.randrange(0, len(b))]
+            elif r < 0.8: k = random.randrange(len(b)); l = random.randint(1, 300); b[k:k + l] = b"\xff" * l
+            elif r < 0.9: want = max(0, want + random.randint(-20, 20))
+            else: k = random.randrange(len(b)); b[k:k] = bytes(random.randrange(256) for _ in range(random.randint(1, 20)))
+            src = (ctypes.c_ubyte * len(b)).from_buffer_copy(bytes(b)) if len(b) else (ctypes.c_ubyte * 1)()
+            dst = (ctypes.c_ubyte * max(want, 1))()
+            table = (ctypes.c_uint64 * 3)(0, 0, len(b) | (want << 32)); st = ctypes.c_uint32(9)
+            rc = entry(src, ctypes.c_int64(len(b)), table, 1, dst, ctypes.c_int64(want), -1, ctypes.byref(st), None)
+            assert rc == 0 and st.value in allowed, (name, rc, st.value)
+            if it == 0: assert st.value == 0 and bytes(dst[:want]) == plain
+            verdicts[name][st.value] = verdicts[name].get(st.value, 0) + 1
+print("variants", len(variants), "runs", total, "return codes", codes, "block verdicts", verdicts)
