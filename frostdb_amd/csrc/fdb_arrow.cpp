@@ -322,6 +322,19 @@ std::shared_ptr<HostDict> encode_plain(const HostColView& col, std::vector<uint3
   return d;
 }
 
+// The dictionary of a plain string / binary column from values that did not arrive as a column (the Sampler's union of such columns):
+// `plain` set, the hash encode_plain would have given the same values. Not interned: its users key their caches by the object.
+std::shared_ptr<HostDict> make_plain_dictionary(std::vector<std::string>&& values, const std::string& value_format) {
+  std::shared_ptr<HostDict> d(new HostDict());
+  d->value_format = value_format;
+  d->plain = true;
+  DictHasher hs;
+  for (const std::string& v : values) { hs.add_len(v.size()); hs.add_bytes(v.data(), v.size()); }
+  d->hash = hs.finish() ^ 0x9E3779B97F4A7C15ull;
+  d->values = std::move(values);
+  return d;
+}
+
 const std::vector<int32_t>& HostDict::arrow_offsets() const {
   std::call_once(offsets_once_, [this] {
     arrow_offsets_.resize(values.size() + 1);

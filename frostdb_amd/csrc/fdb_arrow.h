@@ -79,6 +79,7 @@ std::shared_ptr<HostDict> make_dictionary(std::vector<std::string>&& values, con
 // (first-seen order, `plain` set) and `idx` gets one uint32 per row (0 for NULL rows) — from there on the column travels like
 // a dictionary column, and the filter / group-key code asks `dict->plain` where the reference treats the two differently.
 std::shared_ptr<HostDict> encode_plain(const HostColView& col, std::vector<uint32_t>* idx);
+std::shared_ptr<HostDict> make_plain_dictionary(std::vector<std::string>&& values, const std::string& value_format);  // … of a plain column: `plain` set, distinct values in the given order
 int64_t count_nulls(const uint8_t* validity, int64_t offset, int64_t length);
 // Copies `length` bits starting at bit `offset` of `src` to bit 0 of `dst` (dst has (length+7)/8 bytes, zero padded).
 void copy_bits(const uint8_t* src, int64_t offset, int64_t length, uint8_t* dst);

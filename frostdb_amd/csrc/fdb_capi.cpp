@@ -12,6 +12,7 @@
 #include "fdb_jit.h"
 #include "fdb_plan.h"
 #include "fdb_regex.h"
+#include "fdb_take.h"
 
 // A plan handle: one operator chain. With aggregations over a DynamicColumn (fdb_dynamic.h) `plan` is the family's main plan
 // (static aggregations / group keys) and `dyn` holds the children.
@@ -28,6 +29,7 @@ struct fdb_plan {
 };
 struct fdb_comm { std::unique_ptr<fdb::Comm> c; };
 struct fdb_batch { std::unique_ptr<fdb::DeviceBatch> b; };
+struct fdb_sampler { fdb::Sampler s; fdb_sampler(int64_t size, uint64_t seed, int device) : s(size, seed, device) {} };
 
 namespace {
 thread_local std::string g_last_error;
@@ -388,6 +390,78 @@ int fdb_batch_export(const fdb_batch* batch, struct ArrowArray* out, struct Arro
   return guard(nullptr, [&] {
     if (batch == nullptr || !batch->b || out == nullptr || out_schema == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     fdb::export_batch(*batch->b, out, out_schema);
+  });
+}
+
+int fdb_batch_take(const fdb_batch* in, const int32_t* indices, int64_t n, fdb_batch** out) {
+  return guard(nullptr, [&] {
+    if (in == nullptr || !in->b || out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<fdb::DeviceBatch> r = fdb::take_batch(*in->b, indices, n);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_batch_limit(const fdb_batch* in, uint64_t count, fdb_batch** out) {
+  return guard(nullptr, [&] {
+    if (in == nullptr || !in->b || out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<fdb::DeviceBatch> r = fdb::limit_batch(*in->b, count);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_sampler_create(int64_t size, uint64_t seed, int device, fdb_sampler** out) {
+  return guard(nullptr, [&] {
+    if (out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out = new fdb_sampler(size, seed, device);
+  });
+}
+
+int fdb_sampler_push_batch(fdb_sampler* sampler, const fdb_batch* batch) {
+  return guard(nullptr, [&] {
+    if (sampler == nullptr || batch == nullptr || !batch->b) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    sampler->s.push_batch(*batch->b);
+  });
+}
+
+int fdb_sampler_push(fdb_sampler* sampler, struct ArrowArray* batch, struct ArrowSchema* schema) {
+  return guard(nullptr, [&] {
+    if (sampler == nullptr || batch == nullptr || schema == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    sampler->s.push(batch, schema);
+  });
+}
+
+int fdb_sampler_finish_batch(fdb_sampler* sampler, fdb_batch** out, int64_t* n_rows) {
+  return guard(nullptr, [&] {
+    if (sampler == nullptr || out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<fdb::DeviceBatch> r = sampler->s.finish_batch(n_rows);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_sampler_finish(fdb_sampler* sampler, struct ArrowArray* out, struct ArrowSchema* out_schema, int64_t* n_rows) {
+  return guard(nullptr, [&] {
+    if (sampler == nullptr || out == nullptr || out_schema == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    sampler->s.finish(out, out_schema, n_rows);
+  });
+}
+
+void fdb_sampler_close(fdb_sampler* sampler) { delete sampler; }
+
+int fdb_selftest_reservoir(uint64_t seed, int64_t size, const int64_t* record_rows, int32_t n_records, int64_t* rows_out) {
+  return guard(nullptr, [&] {
+    if (size < 0 || n_records < 0 || (n_records > 0 && record_rows == nullptr)) throw fdb::Error(FDB_ERR_INVALID, "bad arguments");
+    fdb::ReservoirSelect sel(size, seed);
+    int64_t base = 0;
+    for (int32_t r = 0; r < n_records; r++) {
+      if (record_rows[r] < 0) throw fdb::Error(FDB_ERR_INVALID, "negative row count");
+      if (rows_out == nullptr && record_rows[r] > 0 && size > 0) throw fdb::Error(FDB_ERR_INVALID, "null output");
+      sel.push(record_rows[r], [&](int64_t row, int64_t slot) { rows_out[slot] = base + row; });
+      base += record_rows[r];
+    }
   });
 }
 

@@ -872,4 +872,31 @@ hipError_t fdb_launch_validate_indices(const uint32_t* idx, const uint8_t* valid
 // op 1 int64 sum, 2 float64 sum, 3 int64 min, 4 int64 max). `srcs` are device pointers of this or of peer devices; dst may be
 // one of them (each element is read from every source before it is written).
 hipError_t fdb_launch_peer_reduce(unsigned long long* dst, const void* const* srcs, int n_srcs, int64_t lo, int64_t hi, int op, hipStream_t stream);
+
+// ---- row gather / scatter (fdb_take.hip): Take, Limit and the reservoir of the Sampler -----------------------------------------------
+// One column of a gather or a scatter. Values are 4-byte dictionary indices or 8-byte words (int64 / uint64 / float64 / resident bool).
+// The host has validated every row number and slot; the only index the kernels check themselves is a dictionary index against
+// `table_len` (slots under NULL rows may hold anything).
+struct FdbTakeCol {
+  const void* src;           // the source column's values (unused when `absent`)
+  const uint8_t* src_valid;  // nullptr: every source row is valid; else a bitmap (bit offset 0), or a byte per row when `valid_bytes`
+  void* dst;
+  void* dst_valid;           // gather: the output bitmap as 64-bit words, 8-byte aligned (nullptr: the source has no NULLs, none is written);
+                             // scatter: a byte per slot
+  const uint32_t* table;     // width 4: source index → destination index (nullptr: indices are copied as they are)
+  uint32_t table_len;        // an index ≥ table_len writes 0
+  int32_t width;             // 4 or 8
+  int32_t valid_bytes;
+  int32_t absent;            // scatter: the source record lacks the field — the slot becomes NULL, its value 0
+  int32_t pad_;
+};
+#define FDB_TAKE_BLOCK 256
+#define FDB_TAKE_MAX_COLS 65535
+// Gather: for i < n, row rows[i] (rows == nullptr: row i) of every column goes to row i of its destination. A wave writes the validity
+// word of its 64 rows from one ballot (bits past n are 0; no atomics on the bitmap); nulls[c] += the NULLs among the n rows of column c
+// (zeroed by the caller, one atomic add per block that saw a NULL). One launch for all n_cols ≤ FDB_TAKE_MAX_COLS columns.
+hipError_t fdb_launch_take(const FdbTakeCol* d_cols, int n_cols, const uint32_t* d_rows, int64_t n, unsigned long long* d_nulls, hipStream_t stream);
+// Scatter: for i < m, row pairs[2i] of every column goes to slot pairs[2i + 1] of its destination, the slot's validity byte with it. The
+// slots of one launch are distinct (the host keeps the LAST pair per slot), so no two lanes write one value or one byte.
+hipError_t fdb_launch_scatter(const FdbTakeCol* d_cols, int n_cols, const uint32_t* d_pairs, int64_t m, hipStream_t stream);
 #endif  // FDB_DEVICE_ONLY

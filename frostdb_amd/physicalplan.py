@@ -137,6 +137,16 @@ def lib() -> ctypes.CDLL:
     L.fdb_plan_project.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.fdb_batch_from_parquet.argtypes = [vp, i32, i64, ctypes.c_int, P(vp)]
     L.fdb_batches_from_parquet.argtypes = [vp, i32, ctypes.c_int, P(vp)]
+    L.fdb_batch_take.argtypes = [vp, vp, i64, P(vp)]
+    L.fdb_batch_limit.argtypes = [vp, ctypes.c_uint64, P(vp)]
+    L.fdb_sampler_create.argtypes = [i64, ctypes.c_uint64, ctypes.c_int, P(vp)]
+    L.fdb_sampler_push_batch.argtypes = [vp, vp]
+    L.fdb_sampler_push.argtypes = [vp, vp, vp]
+    L.fdb_sampler_finish_batch.argtypes = [vp, P(vp), P(i64)]
+    L.fdb_sampler_finish.argtypes = [vp, vp, vp, P(i64)]
+    L.fdb_sampler_close.argtypes = [vp]
+    L.fdb_sampler_close.restype = None
+    L.fdb_selftest_reservoir.argtypes = [ctypes.c_uint64, i64, vp, i32, vp]
     _lib = L
     return L
 
@@ -218,6 +228,19 @@ def selftest_exact_sum(values) -> float:
     if rc != FDB_OK:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
     return out.value
+
+
+def selftest_reservoir(seed: int, size: int, record_rows: Sequence[int]) -> List[int]:
+    """The rows a ``ReservoirSampler(size, seed)`` ends with after records of `record_rows` rows were pushed in turn, by slot, numbered
+    across the records in push order (fdb_selftest_reservoir: the library's own selection code on the host, no device)."""
+    lens = [int(n) for n in record_rows]
+    rows = (ctypes.c_int64 * max(1, len(lens)))(*lens)
+    kept = min(int(size), sum(lens)) if size > 0 else 0
+    out = (ctypes.c_int64 * max(1, kept))()
+    rc = lib().fdb_selftest_reservoir(int(seed) & 0xFFFFFFFFFFFFFFFF, int(size), rows, len(lens), out)
+    if rc != FDB_OK:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    return [out[i] for i in range(kept)]
 
 
 def live_allocations() -> dict:
@@ -377,6 +400,20 @@ class ResidentBatch:
         if rc != 0:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return import_batch(arr, sch)
+
+    def take(self, indices) -> "ResidentBatch":
+        """≙ arrowutils.Take: row ``indices[i]`` of this record as row i of a new resident record (fdb_batch_take). int32 indices in any
+        order, duplicates allowed; one outside the record raises FdbError(FDB_ERR_INVALID)."""
+        import numpy as np
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.int64))
+        if idx.size and (idx.min() < -(1 << 31) or idx.max() >= (1 << 31)):
+            _raise(FDB_ERR_INVALID, "take: index does not fit int32")
+        idx = idx.astype(np.int32)
+        out = ctypes.c_void_p()
+        rc = lib().fdb_batch_take(self.handle, idx.ctypes.data if idx.size else None, int(idx.size), ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return ResidentBatch(None, device=self.device, _handle=out.value)
 
     @property
     def num_rows(self) -> int:
@@ -771,6 +808,90 @@ class Projection:
     def Close(self) -> None:
         if getattr(self, "handle", None):
             lib().fdb_plan_close(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
+
+class Limiter:
+    """≙ physicalplan.Limiter (limit.go): the first `count` rows of EVERY record — the reference never decrements its count, so a
+    Limiter has no state and nothing to close."""
+
+    def __init__(self, count: int, device: int = 0):
+        if count < 0:
+            count += 1 << 64  # (limit.go:36: uint64(v.Value))
+        self.count = int(count)
+        self.device = device
+
+    def CallbackResident(self, rb: "ResidentBatch") -> "ResidentBatch":
+        out = ctypes.c_void_p()
+        rc = lib().fdb_batch_limit(rb.handle, self.count, ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return ResidentBatch(None, device=rb.device, _handle=out.value)
+
+    def Callback(self, record: pa.RecordBatch) -> pa.RecordBatch:
+        """Host record in, host record out: staged, limited on the device, exported."""
+        rb = ResidentBatch(record, device=self.device)
+        try:
+            out = self.CallbackResident(rb)
+            try:
+                return out.to_arrow()
+            finally:
+                out.close()
+        finally:
+            rb.close()
+
+    def Draw(self) -> str:
+        return "Limit(%d)" % self.count
+
+
+class ReservoirSampler:
+    """≙ physicalplan.ReservoirSampler (sampler.go) on one GPU: up to `size` rows of everything pushed, chosen by Algorithm L with the
+    generator include/frostdb_amd.h documents (`seed`). The reservoir is a record in HBM; Finish always gives ONE record (the
+    reference's materialize form). Splitting `size` over the chains of a query is the caller's job."""
+
+    def __init__(self, size: int, seed: int, device: int = 0):
+        self.size = int(size)
+        self.device = device
+        out = ctypes.c_void_p()
+        rc = lib().fdb_sampler_create(self.size, int(seed) & 0xFFFFFFFFFFFFFFFF, device, ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        self.handle = out.value
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+
+    def Callback(self, record: pa.RecordBatch) -> None:
+        with ExportedBatch(record) as ex:
+            self._check(lib().fdb_sampler_push(self.handle, ctypes.addressof(ex.array), ctypes.addressof(ex.schema)))
+
+    def CallbackResident(self, rb: "ResidentBatch") -> None:
+        self._check(lib().fdb_sampler_push_batch(self.handle, rb.handle))
+
+    def Finish(self) -> pa.RecordBatch:
+        arr, sch = ArrowArray(), ArrowSchema()
+        n = ctypes.c_int64()
+        self._check(lib().fdb_sampler_finish(self.handle, ctypes.addressof(arr), ctypes.addressof(sch), ctypes.byref(n)))
+        return import_batch(arr, sch)
+
+    def FinishResident(self) -> "ResidentBatch":
+        out, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(lib().fdb_sampler_finish_batch(self.handle, ctypes.byref(out), ctypes.byref(n)))
+        return ResidentBatch(None, device=self.device, _handle=out.value)
+
+    def Draw(self) -> str:
+        return "Reservoir Sampler (%d)" % self.size
+
+    def Close(self) -> None:
+        if getattr(self, "handle", None):
+            lib().fdb_sampler_close(self.handle)
             self.handle = None
 
     def __del__(self):

@@ -603,6 +603,56 @@ FDB_API int fdb_selftest_exact_sum(const double* x, int64_t n, double* out);
  * "" before the first push. The string is static. */
 FDB_API const char* fdb_plan_last_kernel(fdb_plan* plan);
 
+
+/* ---- Take, Limit and the reservoir Sampler on resident records ------------------------------------------------------------------
+ * The two physical operators of the reference that cut a record to K rows (Limiter, limit.go; ReservoirSampler, sampler.go) and the
+ * row gather both rest on (arrowutils.Take), for records that fdb_plan_filter_batch / fdb_plan_project_batch left in HBM: nothing
+ * crosses PCIe but the row numbers. Errors of these calls are read with fdb_last_error().
+ *
+ * fdb_batch_take ≙ arrowutils.Take(ctx, r, indices): row indices[i] of `in` becomes row i of *out — any order, duplicates allowed —,
+ * a new resident batch with the same fields, types and dictionaries whose lifetime is independent of `in`'s. n == 0 gives a zero-row
+ * record of the same schema. A negative index or one ≥ the record's rows answers FDB_ERR_INVALID before anything is launched. A
+ * column without a NULL among the taken rows is emitted without a validity bitmap. */
+FDB_API int fdb_batch_take(const fdb_batch* in, const int32_t* indices, int64_t n, fdb_batch** out);
+/* ≙ Limiter.Callback (limit.go:63-98), including its quirk: `count` is applied to EVERY record and never decremented, so the call is
+ * stateless. rows ≤ count: the whole record (copied device to device: *out does not depend on `in`); count == 0: zero rows, same
+ * schema; otherwise the first `count` rows. */
+FDB_API int fdb_batch_limit(const fdb_batch* in, uint64_t count, fdb_batch** out);
+
+/* ≙ ReservoirSampler (sampler.go): keeps up to `size` rows of everything pushed, each row of the input with the same probability.
+ * Push is single-threaded per handle, like a plan. The handle holds a `size`-slot reservoir record in HBM and nothing else — a row
+ * that enters is copied into its slot before push returns and no input record is referenced afterwards —, so the reference's
+ * sizeLimit / materialize (sampler.go:228-289), which bound the bytes such references pin, have nothing to bound and are not part
+ * of this interface. Splitting K over the chains of a query (physicalplan.go:478-486) is the caller's job.
+ *
+ * Which rows are kept is Algorithm L exactly as sampler.go:128-198 runs it: the fill phase in order; then i, w and the `s.i == 0`
+ * sentinel; the pending index carried into the next record; one slot draw and one update of w per replacement. (One repair: the
+ * reference indexes the unsliced record with a row number counted from the slice its fill phase cut off; here the slice is indexed.)
+ * The draws come from splitmix64 seeded with `seed` (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; x = z ^ z >> 31), one output x per draw: a unit draw (rand.Float64) is
+ * ((x >> 11) + 0.5) * 2^-53, a slot draw (rand.Intn(size)) is (x * size) >> 64; where 1 - w rounds to 0 the skip is 1. The first draw
+ * of a sampler is the unit draw of its initial w. A push of a zero-row record is a no-op; size == 0 keeps nothing.
+ *
+ * The result is always in materialize's form (the reference emits the source records and one-row slices when it never
+ * materialised): ONE record — the fields of the records whose rows are in the reservoir, sorted by name bytewise (:244-254); a row
+ * is NULL in a field its record lacked (:264-267), dynamic columns and a field first seen after the reservoir filled included; rows
+ * in slot order. A field whose type differs between records answers FDB_ERR_UNSUPPORTED. A dictionary (or plain string / binary)
+ * field's output dictionary is the union of the contributing records' dictionaries in first-seen order, entries compared by their
+ * bytes; unreferenced entries may stay in it; binary against utf8 in one field is FDB_ERR_UNSUPPORTED. Finish with nothing kept gives
+ * a record without columns or rows, *n_rows = 0. Finish does not empty the reservoir. */
+typedef struct fdb_sampler fdb_sampler;
+FDB_API int fdb_sampler_create(int64_t size, uint64_t seed, int device, fdb_sampler** out);
+FDB_API int fdb_sampler_push_batch(fdb_sampler* sampler, const fdb_batch* batch);
+/* … a host record: staged for the call, the caller's buffers are only borrowed. */
+FDB_API int fdb_sampler_push(fdb_sampler* sampler, struct ArrowArray* batch, struct ArrowSchema* schema);
+FDB_API int fdb_sampler_finish_batch(fdb_sampler* sampler, fdb_batch** out, int64_t* n_rows);
+FDB_API int fdb_sampler_finish(fdb_sampler* sampler, struct ArrowArray* out, struct ArrowSchema* out_schema, int64_t* n_rows);
+FDB_API void fdb_sampler_close(fdb_sampler* sampler);
+/* Host-only self-check of the Sampler's selection (no device): records of record_rows[0 … n_records) rows are pushed in turn into a
+ * sampler of `size` slots seeded with `seed`; rows_out[slot] = the row the slot ends with, numbered across the records in push
+ * order. rows_out has min(size, Σ record_rows) entries. */
+FDB_API int fdb_selftest_reservoir(uint64_t seed, int64_t size, const int64_t* record_rows, int32_t n_records, int64_t* rows_out);
+
 #ifdef __cplusplus
 }
 #endif
