@@ -12,6 +12,8 @@
 #include "fdb_jit.h"
 #include "fdb_plan.h"
 #include "fdb_regex.h"
+#include "fdb_sort.h"
+#include "fdb_sortkey.h"
 #include "fdb_take.h"
 
 // A plan handle: one operator chain. With aggregations over a DynamicColumn (fdb_dynamic.h) `plan` is the family's main plan
@@ -409,6 +411,43 @@ int fdb_batch_limit(const fdb_batch* in, uint64_t count, fdb_batch** out) {
     std::unique_ptr<fdb::DeviceBatch> r = fdb::limit_batch(*in->b, count);
     *out = new fdb_batch{std::move(r)};
   });
+}
+
+int fdb_batch_sort_indices(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, int32_t* indices_out) {
+  return guard(nullptr, [&] {
+    if (in == nullptr || !in->b) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    fdb::sort_batch_indices(*in->b, cols, n_cols, indices_out);
+  });
+}
+
+int fdb_batch_sort(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, fdb_batch** out) {
+  return guard(nullptr, [&] {
+    if (in == nullptr || !in->b || out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<fdb::DeviceBatch> r = fdb::sort_batch(*in->b, cols, n_cols);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_selftest_sort_key(int32_t kind, uint32_t direction, uint64_t raw, uint64_t* key_out) {
+  return guard(nullptr, [&] {
+    if (key_out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    if (kind != FDB_SORT_I64 && kind != FDB_SORT_U64 && kind != FDB_SORT_F64) throw fdb::Error(FDB_ERR_INVALID, "sort key: kind is not int64 (1), uint64 (2) or float64 (3)");
+    if (direction > 1u) throw fdb::Error(FDB_ERR_INVALID, "sort key: direction is not 0 (ascending) or 1 (descending)");
+    *key_out = fdb_sortkey_directed(fdb_sortkey_value(kind, raw), direction == 1u ? FDB_SORT_DESC : 0u, 64);
+  });
+}
+
+int fdb_sort_bench(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, int32_t reps, int32_t warmup, double* sort_ms, double* bare_ms, int32_t* n_passes) {
+  return guard(nullptr, [&] {
+    if (in == nullptr || !in->b) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    fdb::sort_bench(*in->b, cols, n_cols, reps, warmup, sort_ms, bare_ms, n_passes);
+  });
+}
+
+const char* fdb_batch_column_name(const fdb_batch* batch, int32_t index) {
+  if (batch == nullptr || !batch->b || index < 0 || (size_t)index >= batch->b->cols.size()) return nullptr;
+  return batch->b->cols[(size_t)index].name.c_str();
 }
 
 int fdb_sampler_create(int64_t size, uint64_t seed, int device, fdb_sampler** out) {

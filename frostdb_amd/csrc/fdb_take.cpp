@@ -16,23 +16,17 @@
 
 namespace fdb {
 
-namespace {
-// A pooled context for the length of one call.
-struct CallScope {
-  Context* ctx = nullptr;
-  std::vector<void*> scratch;
-  explicit CallScope(int device) {
-    hip_check(hipSetDevice(device), "hipSetDevice");
-    ctx = Context::acquire(device);
-  }
-  ~CallScope() {
-    (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : scratch) ctx->dev_free(p);
-    ctx->reset_staging();
-    Context::release(ctx);
-  }
-  CallScope(const CallScope&) = delete;
-};
+CallScope::CallScope(int device) {
+  hip_check(hipSetDevice(device), "hipSetDevice");
+  ctx = Context::acquire(device);
+}
+
+CallScope::~CallScope() {
+  (void)hipStreamSynchronize(ctx->stream);
+  for (void* p : scratch) ctx->dev_free(p);
+  ctx->reset_staging();
+  Context::release(ctx);
+}
 
 void require_values(const DeviceBatch& in, const char* what) {
   for (const DevColumn& c : in.cols)
@@ -40,6 +34,7 @@ void require_values(const DeviceBatch& in, const char* what) {
       throw Error(FDB_ERR_UNSUPPORTED, std::string(what) + ": column type " + c.format + " (" + c.name + ") is not supported on the device path");
 }
 
+namespace {
 // The record `in` without rows: every column's name, format, kind and dictionary.
 std::unique_ptr<DeviceBatch> schema_only(const DeviceBatch& in) {
   std::unique_ptr<DeviceBatch> out(new DeviceBatch());
@@ -163,8 +158,12 @@ std::unique_ptr<DeviceBatch> take_batch(const DeviceBatch& in, const int32_t* in
   cs.scratch.push_back(d_rows);
   // (validated: every index is ≥ 0, so the int32 bits are the uint32 row numbers; the call ends synchronised, the caller's array is only read until then)
   hip_check(hipMemcpyAsync(d_rows, indices, (size_t)n * 4, hipMemcpyHostToDevice, cs.ctx->stream), "hipMemcpyAsync(take indices)");
-  in.note_reader(cs.ctx->stream);
-  return gather(cs.ctx, &cs.scratch, in.device, columns_of(in), d_rows, n);
+  return take_device_rows(in, &cs, d_rows, n);
+}
+
+std::unique_ptr<DeviceBatch> take_device_rows(const DeviceBatch& in, CallScope* cs, const uint32_t* d_rows, int64_t n) {
+  in.note_reader(cs->ctx->stream);
+  return gather(cs->ctx, &cs->scratch, in.device, columns_of(in), d_rows, n);
 }
 
 std::unique_ptr<DeviceBatch> limit_batch(const DeviceBatch& in, uint64_t count) {

@@ -147,6 +147,12 @@ def lib() -> ctypes.CDLL:
     L.fdb_sampler_close.argtypes = [vp]
     L.fdb_sampler_close.restype = None
     L.fdb_selftest_reservoir.argtypes = [ctypes.c_uint64, i64, vp, i32, vp]
+    L.fdb_batch_sort_indices.argtypes = [vp, vp, i32, vp]
+    L.fdb_batch_sort.argtypes = [vp, vp, i32, P(vp)]
+    L.fdb_selftest_sort_key.argtypes = [i32, ctypes.c_uint32, ctypes.c_uint64, P(ctypes.c_uint64)]
+    L.fdb_sort_bench.argtypes = [vp, vp, i32, i32, i32, P(ctypes.c_double), P(ctypes.c_double), P(i32)]
+    L.fdb_batch_column_name.argtypes = [vp, i32]
+    L.fdb_batch_column_name.restype = ctypes.c_char_p
     _lib = L
     return L
 
@@ -243,6 +249,19 @@ def selftest_reservoir(seed: int, size: int, record_rows: Sequence[int]) -> List
     return [out[i] for i in range(kept)]
 
 
+SORT_KIND_INT64, SORT_KIND_UINT64, SORT_KIND_FLOAT64 = 1, 2, 3
+
+
+def selftest_sort_key(kind: int, descending: bool, raw: int) -> int:
+    """The 64-bit radix-key value field the device Sort gives one non-NULL int64 / uint64 / float64 value (`raw` = its bits), in the
+    given direction (fdb_selftest_sort_key: the encoding the key kernel runs, on the host, no device)."""
+    out = ctypes.c_uint64()
+    rc = lib().fdb_selftest_sort_key(int(kind), 1 if descending else 0, int(raw) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(out))
+    if rc != FDB_OK:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    return out.value
+
+
 def live_allocations() -> dict:
     """Device blocks / bytes and pinned result blocks the library owns right now (0 once everything is closed and released)."""
     a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
@@ -298,6 +317,11 @@ def device_count() -> int:
 
 def _raise(code: int, msg: str):
     raise (UnsupportedError if code == FDB_ERR_UNSUPPORTED else FdbError)(code, msg)
+
+
+class SortCol(ctypes.Structure):
+    """fdb_sort_col ≙ arrowutils.SortingColumn: column position, direction (0 ascending / 1 descending), nulls_first."""
+    _fields_ = [("index", ctypes.c_int32), ("direction", ctypes.c_uint32), ("nulls_first", ctypes.c_uint32)]
 
 
 class ParquetChunk(ctypes.Structure):
@@ -411,6 +435,75 @@ class ResidentBatch:
         idx = idx.astype(np.int32)
         out = ctypes.c_void_p()
         rc = lib().fdb_batch_take(self.handle, idx.ctypes.data if idx.size else None, int(idx.size), ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return ResidentBatch(None, device=self.device, _handle=out.value)
+
+    @property
+    def column_names(self) -> List[str]:
+        """The names of the record's columns, in order (fdb_batch_column_name)."""
+        names, k = [], 0
+        while True:
+            nm = lib().fdb_batch_column_name(self.handle, k)
+            if nm is None:
+                return names
+            names.append(nm.decode("utf-8", "replace"))
+            k += 1
+
+    def _sort_cols(self, columns):
+        """`columns` → an fdb_sort_col array. A column is ``(name_or_index, descending=False, nulls_first=False)`` or a bare name /
+        index; a name the record lacks (or has twice) raises KeyError before the library is called. A raw descriptor —
+        ``SortCol(index, direction, nulls_first)`` — is passed through unchecked."""
+        if isinstance(columns, (str, int, SortCol)):
+            columns = [columns]
+        names = None
+        cols = []
+        for c in columns:
+            if isinstance(c, SortCol):
+                cols.append(c)
+                continue
+            c = (c,) if isinstance(c, (str, int)) else tuple(c)
+            if not 1 <= len(c) <= 3:
+                raise ValueError("a sorting column is (name_or_index, descending=False, nulls_first=False)")
+            key, descending, nulls_first = c[0], (len(c) > 1 and bool(c[1])), (len(c) > 2 and bool(c[2]))
+            if isinstance(key, str):
+                if names is None:
+                    names = self.column_names
+                if names.count(key) != 1:
+                    raise KeyError("sort: the record has %s column named %r" % ("no" if key not in names else "more than one", key))
+                key = names.index(key)
+            cols.append(SortCol(int(key), 1 if descending else 0, 1 if nulls_first else 0))
+        return (SortCol * max(1, len(cols)))(*cols), len(cols)
+
+    def sort_indices(self, columns):
+        """≙ arrowutils.SortRecord: the int32 permutation p with row p[i] of this record = row i of the sorted record
+        (fdb_batch_sort_indices). Stable. `columns`: see ``sort``."""
+        import numpy as np
+        arr, n = self._sort_cols(columns)
+        out = np.empty(max(1, self.num_rows), dtype=np.int32)
+        rc = lib().fdb_batch_sort_indices(self.handle, arr, n, out.ctypes.data)
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return out[: self.num_rows]
+
+    def sort_bench(self, columns, reps: int = 7, warmup: int = 2) -> dict:
+        """Measurement aid (fdb_sort_bench): median device ms of the sort's key kernels + radix passes, and of bare radix sorts with
+        the same pass count and bit widths."""
+        arr, n = self._sort_cols(columns)
+        a, b, k = ctypes.c_double(), ctypes.c_double(), ctypes.c_int32()
+        rc = lib().fdb_sort_bench(self.handle, arr, n, int(reps), int(warmup), ctypes.byref(a), ctypes.byref(b), ctypes.byref(k))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return {"sort_ms": a.value, "bare_sort_ms": b.value, "passes": k.value}
+
+    def sort(self, columns) -> "ResidentBatch":
+        """≙ SortRecord + Take without the indices leaving HBM: this record's rows in the order of `columns`, as a new resident record
+        (fdb_batch_sort). A column is ``(name_or_index, descending=False, nulls_first=False)`` or a bare name; compared left to right;
+        NULLs after a column's values unless nulls_first, whatever the direction; float64 as Go's cmp.Compare (NaNs equal, below -Inf);
+        strings by their bytes; rows equal on every column keep their order."""
+        arr, n = self._sort_cols(columns)
+        out = ctypes.c_void_p()
+        rc = lib().fdb_batch_sort(self.handle, arr, n, ctypes.byref(out))
         if rc != 0:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return ResidentBatch(None, device=self.device, _handle=out.value)

@@ -619,6 +619,40 @@ FDB_API int fdb_batch_take(const fdb_batch* in, const int32_t* indices, int64_t 
  * schema; otherwise the first `count` rows. */
 FDB_API int fdb_batch_limit(const fdb_batch* in, uint64_t count, fdb_batch** out);
 
+/* ---- Sort of a resident record ------------------------------------------------------------------------------------------------------
+ * ≙ arrowutils.SortRecord (pqarrow/arrowutils/sort.go:48-65) and the "sort indices, then Take" pair the reference's ordered paths use
+ * (merge_test.go:356-375), for a record that is already in HBM: nothing crosses PCIe but the column list (and, for
+ * fdb_batch_sort_indices, the indices on their way out). fdb_sort_col has the vocabulary of arrowutils.SortingColumn: `index` = the
+ * column's position in the record, `direction` 0 = Ascending / 1 = Descending (the numeric values of arrowutils.Direction),
+ * `nulls_first` != 0 = the column's NULLs before all its values, else after them — in both cases whatever the direction (:534-564).
+ * Columns are compared left to right, the first on which two rows differ decides (:517-532). Values: int64 (and what imports as int64:
+ * timestamps) signed; uint64 unsigned; float64 as Go's cmp.Compare — every NaN equals every other NaN and sorts below -Inf, -0.0
+ * equals +0.0 (NOT pyarrow's order); dictionary and plain string / binary columns by the bytes of the entry (bytes.Compare), two
+ * dictionary entries that hold the same bytes being equal. The raw slot under a NULL is never looked at.
+ * The result is STABLE: rows equal on every sorting column keep their input order. The reference's sort.Sort is not stable — any order
+ * of such rows is legal there; this one is deterministic.
+ * Errors, all answered before anything is launched: n_cols == 0 FDB_ERR_INVALID "at least one column is needed for sorting" (checked
+ * first); then a record of 0 or 1 rows gives the empty / {0} permutation without a look at the columns (:412-417); a column index
+ * outside the record, a direction other than 0 / 1, more than 2^31 - 1 rows (indices are int32): FDB_ERR_INVALID; a bool column, or a
+ * column of a type the resident record cannot hold: FDB_ERR_UNSUPPORTED "unsupported column type for sorting … for column …" (:477).
+ * Not bound by the Go shim yet. */
+typedef struct fdb_sort_col { int32_t index; uint32_t direction; uint32_t nulls_first; } fdb_sort_col;
+/* ≙ arrowutils.SortRecord: indices_out[i] (caller's buffer, one int32 per row of `in`) = the input row that is row i of the sorted record */
+FDB_API int fdb_batch_sort_indices(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, int32_t* indices_out);
+/* = SortRecord + Take without the indices leaving HBM: *out is a new resident batch, independent of `in` */
+FDB_API int fdb_batch_sort(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, fdb_batch** out);
+/* host-only: the 64-bit value field of one non-NULL value (kind = the column kinds of the header: int64 / uint64 / float64; raw = its bits) */
+FDB_API int fdb_selftest_sort_key(int32_t kind, uint32_t direction, uint64_t raw, uint64_t* key_out);
+/* Measurement aid (tools/sort_bench.py): *sort_ms = the device time (HIP events on the call's stream, median of `reps` calls after
+ * `warmup` calls) of what fdb_batch_sort_indices runs on the device before its copy-out — key kernels + radix passes —; *bare_ms = the
+ * same for bare radix sorts of (uint64 key, uint64 value) pairs with the same pass count (*n_passes) and bit widths: the yardstick. The
+ * record needs at least 2 rows. */
+FDB_API int fdb_sort_bench(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, int32_t reps, int32_t warmup, double* sort_ms, double* bare_ms,
+                           int32_t* n_passes);
+/* Name of column `index` of a resident batch (for callers that name sorting columns); NULL past the last column. The string lives as
+ * long as the batch. */
+FDB_API const char* fdb_batch_column_name(const fdb_batch* batch, int32_t index);
+
 /* ≙ ReservoirSampler (sampler.go): keeps up to `size` rows of everything pushed, each row of the input with the same probability.
  * Push is single-threaded per handle, like a plan. The handle holds a `size`-slot reservoir record in HBM and nothing else — a row
  * that enters is copied into its slot before push returns and no input record is referenced afterwards —, so the reference's
