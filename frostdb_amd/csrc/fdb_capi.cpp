@@ -10,6 +10,8 @@
 #include "fdb_context.h"
 #include "fdb_dynamic.h"
 #include "fdb_jit.h"
+#include "fdb_mergepath.h"
+#include "fdb_mergerec.h"
 #include "fdb_plan.h"
 #include "fdb_regex.h"
 #include "fdb_sort.h"
@@ -442,6 +444,47 @@ int fdb_sort_bench(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols
   return guard(nullptr, [&] {
     if (in == nullptr || !in->b) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     fdb::sort_bench(*in->b, cols, n_cols, reps, warmup, sort_ms, bare_ms, n_passes);
+  });
+}
+
+extern "C++" {
+static std::vector<const fdb::DeviceBatch*> merge_inputs(const fdb_batch* const* in, int32_t n) {
+  if (n < 0 || (n > 0 && in == nullptr)) throw fdb::Error(FDB_ERR_INVALID, "merge: bad record list");
+  std::vector<const fdb::DeviceBatch*> recs((size_t)n, nullptr);
+  for (int32_t r = 0; r < n; r++) {
+    if (in[r] == nullptr || !in[r]->b) throw fdb::Error(FDB_ERR_INVALID, "merge: record " + std::to_string(r) + " is null");
+    recs[(size_t)r] = in[r]->b.get();
+  }
+  return recs;
+}
+}
+
+int fdb_batches_merge(const fdb_batch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, uint64_t limit, fdb_batch** out) {
+  return guard(nullptr, [&] {
+    if (out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const std::vector<const fdb::DeviceBatch*> recs = merge_inputs(in, n);
+    std::unique_ptr<fdb::DeviceBatch> r = fdb::merge_batches(recs.data(), n, cols, n_cols, limit);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int32_t fdb_merge_tile_rows(int32_t words) { return words < 0 ? 0 : (int32_t)fdb_merge_tile(words); }
+
+int fdb_selftest_merge_path(const uint64_t* a, int64_t na, const uint64_t* b, int64_t nb, int32_t words, uint32_t* src_out) {
+  return guard(nullptr, [&] {
+    if (na < 0 || nb < 0 || words < 1 || words > 64 || na + nb > 0x7FFFFFFFll || (na > 0 && a == nullptr) || (nb > 0 && b == nullptr) || (na + nb > 0 && src_out == nullptr))
+      throw fdb::Error(FDB_ERR_INVALID, "merge path: bad arguments");
+    const int64_t bad = fdb_merge_path_host(a, na, b, nb, words, src_out);
+    if (bad != 0) throw fdb::Error(FDB_ERR_INVALID, "merge path: the split points of tile " + std::to_string(bad - 1) + " cross (are both runs sorted?)");
+  });
+}
+
+int fdb_merge_bench(const fdb_batch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, int32_t reps, int32_t warmup, double* merge_ms, double* gather_ms,
+                    double* round_ms, int32_t round_cap, int32_t* n_rounds, int32_t* words) {
+  return guard(nullptr, [&] {
+    const std::vector<const fdb::DeviceBatch*> recs = merge_inputs(in, n);
+    fdb::merge_bench(recs.data(), n, cols, n_cols, reps, warmup, merge_ms, gather_ms, round_ms, round_cap, n_rounds, words);
   });
 }
 

@@ -15,76 +15,18 @@
 #include "fdb_context.h"
 #include "fdb_plan_internal.h"
 #include "fdb_sortkey.h"
+#include "fdb_sortplan.h"
 #include "fdb_take.h"
 
 namespace fdb {
 
 namespace {
 
-// Dense ranks of a dictionary's entries by their bytes (equal bytes — a dictionary with unique == false — share a rank), and the number of
-// distinct entries.
-std::vector<uint32_t> dense_ranks(const HostDict& d, uint32_t* distinct) {
-  const size_t n = d.values.size();
-  if (d.unique) {  // positions among the sorted entries are dense already, and computed once per interned dictionary
-    *distinct = (uint32_t)n;
-    return d.sorted_ranks();
-  }
-  std::vector<uint32_t> order(n), rank(n);
-  for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return d.values[x] < d.values[y]; });  // (std::string: bytewise, as bytes.Compare)
-  uint32_t r = 0;
-  for (size_t k = 0; k < n; k++) {
-    if (k > 0 && d.values[order[k]] != d.values[order[k - 1]]) r++;
-    rank[order[k]] = r;
-  }
-  *distinct = n == 0 ? 0u : r + 1u;
-  return rank;
-}
-
-// The packing of the key fields into words: one SortPart per (word, column) — the column's value field, its NULL bit, or both; bits_out[w]
-// = the bits word w uses. Word 0 is the most significant.
-struct SortPart { int word; int col; int width; int shift; int null_shift; };
-struct SortColBits { int value_bits; bool has_null_bit; };
-
-std::vector<SortPart> pack_sort_fields(const std::vector<SortColBits>& cols, std::vector<int>* bits_out) {
-  // greedy, most significant column first; `top` = bits of the current word already given away, counted from its top
-  struct Piece { int word, col, width, top; bool null_bit; };
-  std::vector<Piece> pieces;
-  std::vector<int> used;
-  auto place = [&](int col, int width, bool null_bit) {
-    if (used.empty() || used.back() + width > 64) used.push_back(0);
-    pieces.push_back(Piece{(int)used.size() - 1, col, width, used.back(), null_bit});
-    used.back() += width;
-  };
-  for (size_t c = 0; c < cols.size(); c++) {
-    if (cols[c].has_null_bit) place((int)c, 1, true);
-    if (cols[c].value_bits > 0) place((int)c, cols[c].value_bits, false);
-  }
-  // a word sorts on its low used[w] bits: the first piece of a word ends at bit used[w] - 1
-  std::vector<SortPart> parts;
-  for (const Piece& p : pieces) {
-    const int low = used[(size_t)p.word] - p.top - p.width;
-    if (!parts.empty() && parts.back().word == p.word && parts.back().col == p.col) {  // the value field right under its NULL bit
-      parts.back().width = p.width; parts.back().shift = low;
-      continue;
-    }
-    parts.push_back(p.null_bit ? SortPart{p.word, p.col, 0, 0, low} : SortPart{p.word, p.col, p.width, low, -1});
-  }
-  *bits_out = used;
-  return parts;
-}
-
 struct SortPlan {
   std::vector<std::vector<FdbSortField>> words;  // [word][field], ranks = an OFFSET into `ranks` (in entries) + 1 until they are on the device
   std::vector<int> bits;
   std::vector<uint32_t> ranks;                   // the rank tables of the dictionary columns, back to back
 };
-
-int bits_for(uint64_t distinct) {  // ceil(log2(distinct))
-  int b = 0;
-  while (b < 64 && ((uint64_t)1 << b) < distinct) b++;
-  return b;
-}
 
 // Everything that can refuse the call, and the plan of the keys. rows ≥ 2.
 SortPlan plan_sort(const DeviceBatch& in, const fdb_sort_col* cols, int32_t n_cols) {

@@ -151,6 +151,11 @@ def lib() -> ctypes.CDLL:
     L.fdb_batch_sort.argtypes = [vp, vp, i32, P(vp)]
     L.fdb_selftest_sort_key.argtypes = [i32, ctypes.c_uint32, ctypes.c_uint64, P(ctypes.c_uint64)]
     L.fdb_sort_bench.argtypes = [vp, vp, i32, i32, i32, P(ctypes.c_double), P(ctypes.c_double), P(i32)]
+    L.fdb_batches_merge.argtypes = [P(vp), i32, vp, i32, ctypes.c_uint64, P(vp)]
+    L.fdb_merge_tile_rows.argtypes = [i32]
+    L.fdb_merge_tile_rows.restype = i32
+    L.fdb_selftest_merge_path.argtypes = [vp, i64, vp, i64, i32, vp]
+    L.fdb_merge_bench.argtypes = [P(vp), i32, vp, i32, i32, i32, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double), i32, P(i32), P(i32)]
     L.fdb_batch_column_name.argtypes = [vp, i32]
     L.fdb_batch_column_name.restype = ctypes.c_char_p
     _lib = L
@@ -260,6 +265,25 @@ def selftest_sort_key(kind: int, descending: bool, raw: int) -> int:
     if rc != FDB_OK:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
     return out.value
+
+
+def merge_tile_rows(words: int) -> int:
+    """The output tile (rows) of the device merge kernel for a key of `words` 64-bit words (fdb_merge_tile_rows)."""
+    return int(lib().fdb_merge_tile_rows(int(words)))
+
+
+def selftest_merge_path(a, b, words: int):
+    """The device merge's merge-path code run on the host (fdb_selftest_merge_path; no device): `a` and `b` are sorted runs of keys of
+    `words` unsigned 64-bit words each (sequences of `words`-tuples, or arrays of shape (n, words)). Returns, per output row, its
+    source: i for a[i], len(a) + j for b[j]. Ties go to `a`."""
+    import numpy as np
+    ka = np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, int(words)))
+    kb = np.ascontiguousarray(np.asarray(b, dtype=np.uint64).reshape(-1, int(words)))
+    out = np.empty(max(1, len(ka) + len(kb)), dtype=np.uint32)
+    rc = lib().fdb_selftest_merge_path(ka.ctypes.data if len(ka) else None, len(ka), kb.ctypes.data if len(kb) else None, len(kb), int(words), out.ctypes.data)
+    if rc != FDB_OK:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    return out[: len(ka) + len(kb)]
 
 
 def live_allocations() -> dict:
@@ -507,6 +531,41 @@ class ResidentBatch:
         if rc != 0:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return ResidentBatch(None, device=self.device, _handle=out.value)
+
+    @staticmethod
+    def _merge_args(records, columns):
+        records = list(records)
+        handles = (ctypes.c_void_p * max(1, len(records)))(*[r.handle for r in records])
+        if records:
+            arr, n = records[0]._sort_cols(columns)
+        else:
+            arr, n = (SortCol * 1)(), 0
+        return records, handles, arr, n
+
+    @staticmethod
+    def merge(records, columns, limit: int = 0) -> "ResidentBatch":
+        """≙ arrowutils.MergeRecords: the rows of `records` — resident records of one schema, each already ordered by `columns` (as for
+        ``sort``: names or indices, resolved against the first record) — as ONE new resident record in that order, at most `limit` rows
+        when limit > 0 (fdb_batches_merge). Stable: equal rows come out in record order, then row order. An input that is not
+        ordered raises FdbError(FDB_ERR_INVALID) naming the record and the row."""
+        records, handles, arr, n = ResidentBatch._merge_args(records, columns)
+        out = ctypes.c_void_p()
+        rc = lib().fdb_batches_merge(handles, len(records), arr, n, int(limit), ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return ResidentBatch(None, device=records[0].device, _handle=out.value)
+
+    @staticmethod
+    def merge_bench(records, columns, reps: int = 7, warmup: int = 2) -> dict:
+        """Measurement aid (fdb_merge_bench): median device ms of the merge's key kernels + order check + rounds, of its gather, and of
+        every round alone."""
+        records, handles, arr, n = ResidentBatch._merge_args(records, columns)
+        a, b, k, w = ctypes.c_double(), ctypes.c_double(), ctypes.c_int32(), ctypes.c_int32()
+        rounds = (ctypes.c_double * 32)()
+        rc = lib().fdb_merge_bench(handles, len(records), arr, n, int(reps), int(warmup), ctypes.byref(a), ctypes.byref(b), rounds, 32, ctypes.byref(k), ctypes.byref(w))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
     @property
     def num_rows(self) -> int:

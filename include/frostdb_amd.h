@@ -649,6 +649,35 @@ FDB_API int fdb_selftest_sort_key(int32_t kind, uint32_t direction, uint64_t raw
  * record needs at least 2 rows. */
 FDB_API int fdb_sort_bench(const fdb_batch* in, const fdb_sort_col* cols, int32_t n_cols, int32_t reps, int32_t warmup, double* sort_ms, double* bare_ms,
                            int32_t* n_passes);
+/* ---- MergeRecords over resident records --------------------------------------------------------------------------------------------
+ * ≙ arrowutils.MergeRecords (pqarrow/arrowutils/merge.go:23-68), what OrderedSynchronizer.mergeRecordsLocked and OrderedAggregate run
+ * where several ordered streams meet: `n` >= 1 resident records of one schema (field lists equal in length, names, order and kind), each
+ * already ordered by `cols` (the vocabulary of fdb_batch_sort), become ONE new resident record, independent of its inputs, holding all
+ * their rows in that order, cut to `limit` rows when limit > 0. Neither keys nor permutation leave HBM. The result is the STABLE sort of
+ * the concatenation in[0] ‖ in[1] ‖ … under fdb_batch_sort's comparison: rows equal on every sorting column come out in record order,
+ * inside a record in row order (container/heap promises no order of ties: this is one of the legal ones, always the same).
+ * Deviations from the reference: two rows both NULL in a column are decided by the NEXT column (cursorHeap.Less returns false at once,
+ * merge.go:91-98); float64 sorting columns are accepted (the reference panics, :169-171) and compare as Go's cmp.Compare; descending
+ * and mixed directions are supported (the reference's comment says ascending only, its TestMerge vectors say otherwise); dictionaries
+ * may differ between the inputs — entries compare by their bytes, the output column carries the union of the entries in first-seen
+ * order, and when every input shares one dictionary's content that dictionary is the output's, untranslated; the inputs' order is
+ * CHECKED on the device before any merge launch — an unordered input is FDB_ERR_INVALID naming the record and the first offending row.
+ * n == 1 is fdb_batch_limit of the record (its order is not looked at); a total of 0 rows gives a zero-row record of the schema.
+ * FDB_ERR_INVALID: n == 0, a null record, records on different devices, no sorting columns, a column index or direction out of range,
+ * differing field lists, more than 2^31 - 1 rows in total. FDB_ERR_UNSUPPORTED: a bool sorting column, a column the resident record
+ * cannot hold, a field that is utf8 in one record and binary in another. ensureSameSchema's virtual NULL columns
+ * (ordered_synchronizer.go:143-241) are not built. Not bound by the Go shim yet. */
+FDB_API int fdb_batches_merge(const fdb_batch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, uint64_t limit, fdb_batch** out);
+/* the output tile (rows) of the merge kernel for a key of `words` 64-bit words: tests track the kernel through it */
+FDB_API int32_t fdb_merge_tile_rows(int32_t words);
+/* host-only: the kernels' merge-path code (diagonal search, per-lane serial merge, tile by tile and lane by lane) over two sorted runs
+ * of `words`-word keys, row-major; src_out[o] (na + nb entries) = the source of output o: i for a[i], na + j for b[j] */
+FDB_API int fdb_selftest_merge_path(const uint64_t* a, int64_t na, const uint64_t* b, int64_t nb, int32_t words, uint32_t* src_out);
+/* Measurement aid (tools/merge_bench.py): device time between HIP events on the call's stream, medians of `reps` calls after `warmup`
+ * calls — *merge_ms: key kernels + order check (one host round trip included) + rounds; *gather_ms: the gather; round_ms[k]
+ * (k < min(*n_rounds, round_cap)): round k alone; *words: the key's words. At least two records with rows. */
+FDB_API int fdb_merge_bench(const fdb_batch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, int32_t reps, int32_t warmup, double* merge_ms,
+                            double* gather_ms, double* round_ms, int32_t round_cap, int32_t* n_rounds, int32_t* words);
 /* Name of column `index` of a resident batch (for callers that name sorting columns); NULL past the last column. The string lives as
  * long as the batch. */
 FDB_API const char* fdb_batch_column_name(const fdb_batch* batch, int32_t index);
