@@ -13,6 +13,7 @@ import pyarrow.parquet as pq
 import pytest
 
 from frostdb_amd.logicalplan import Col, Count, DynCol, Sum, UInt64
+from tests.parquet_pages import DATA_PAGE, PLAIN, page_header
 from tests.parquet_util import row_group_chunks, write_parquet
 from tests.test_gpu_parity import assert_same_result, run_oracle
 from tests.util import arrow_to_pydict
@@ -435,20 +436,6 @@ def test_literal_snappy_pages_are_inflated_on_the_device(pp, version, monkeypatc
         pass
 
 
-def _thrift_page_header_v1(n_values: int, uncompressed: int, compressed: int) -> bytes:
-    """PageHeader{1: type = DATA_PAGE, 2: uncompressed_page_size, 3: compressed_page_size, 5: DataPageHeader{1: num_values, 2: PLAIN, 3: RLE,
-    4: RLE}} in Thrift's compact protocol (field header = delta << 4 | type; i32 = zigzag varint)."""
-    def zz(v):
-        v = (v << 1) ^ (v >> 31)
-        out = bytearray()
-        while v >= 0x80:
-            out.append((v & 0x7F) | 0x80); v >>= 7
-        out.append(v)
-        return bytes(out)
-    inner = b"\x15" + zz(n_values) + b"\x15" + zz(0) + b"\x15" + zz(3) + b"\x15" + zz(3) + b"\x00"
-    return b"\x15" + zz(0) + b"\x15" + zz(uncompressed) + b"\x15" + zz(compressed) + b"\x2c" + inner + b"\x00"
-
-
 @pytest.mark.parametrize("how", ["four_byte_offset", "two_byte_offset_past_the_ring"])
 def test_snappy_pages_with_copies_from_far_back_take_the_host_path(pp, how, monkeypatch):
     """A legal Snappy page the device's decoder cannot take: a copy that reaches further back than the 64 KiB of output it keeps
@@ -481,7 +468,7 @@ def test_snappy_pages_with_copies_from_far_back_take_the_host_path(pp, how, monk
     body = varint(len(raw)) + literal(bytes(raw[:at])) + copy + literal(bytes(raw[at + 64:]))
     import pyarrow as _pa
     assert _pa.decompress(body, decompressed_size=len(raw), codec="snappy").to_pybytes() == bytes(raw)  # (the page is what the test thinks it is)
-    chunk = _thrift_page_header_v1(n, len(raw), len(body)) + body
+    chunk = page_header(DATA_PAGE, len(raw), len(body), n, PLAIN) + body
     for host in (False, True):
         if host:
             monkeypatch.setenv("FDB_PARQUET_HOST_INFLATE", "1")
