@@ -33,6 +33,7 @@ struct fdb_plan {
 };
 struct fdb_comm { std::unique_ptr<fdb::Comm> c; };
 struct fdb_batch { std::unique_ptr<fdb::DeviceBatch> b; };
+struct fdb_osync { fdb::OrderedSync s; fdb_osync(int32_t inputs, const fdb_order_col* order, int32_t n_order) : s(inputs, order, n_order) {} };
 struct fdb_sampler { fdb::Sampler s; fdb_sampler(int64_t size, uint64_t seed, int device) : s(size, seed, device) {} };
 
 namespace {
@@ -468,6 +469,79 @@ int fdb_batches_merge(const fdb_batch* const* in, int32_t n, const fdb_sort_col*
     *out = new fdb_batch{std::move(r)};
   });
 }
+
+int fdb_batches_merge_named(const fdb_batch* const* in, int32_t n, const fdb_order_col* order, int32_t n_order, uint64_t limit, fdb_batch** out) {
+  return guard(nullptr, [&] {
+    if (out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const std::vector<const fdb::DeviceBatch*> recs = merge_inputs(in, n);
+    std::unique_ptr<fdb::DeviceBatch> r = fdb::merge_batches_named(recs.data(), n, order, n_order, limit);
+    *out = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_selftest_merge_schema(const char* const* names, const int32_t* kinds, const int32_t* n_fields, int32_t n_records, const fdb_order_col* order, int32_t n_order,
+                              int32_t* out_fields, int32_t* col_map, int32_t cap, int32_t* n_out, int32_t* n_sort) {
+  return guard(nullptr, [&] {
+    if (n_records < 0 || (n_records > 0 && n_fields == nullptr) || order == nullptr || n_order <= 0 || cap < 0 || n_out == nullptr || n_sort == nullptr)
+      throw fdb::Error(FDB_ERR_INVALID, "merge schema: bad arguments");
+    std::vector<fdb::MergeOrder> exprs;
+    for (int32_t k = 0; k < n_order; k++) {
+      if (order[k].name == nullptr) throw fdb::Error(FDB_ERR_INVALID, "merge schema: order expression " + std::to_string(k) + " has no name");
+      exprs.push_back(fdb::MergeOrder{order[k].name, order[k].dynamic != 0});
+    }
+    std::vector<std::vector<fdb::MergeField>> lists((size_t)n_records);
+    std::vector<int32_t> base((size_t)n_records, 0);
+    int32_t flat = 0;
+    for (int32_t r = 0; r < n_records; r++) {
+      if (n_fields[r] < 0 || (n_fields[r] > 0 && (names == nullptr || kinds == nullptr))) throw fdb::Error(FDB_ERR_INVALID, "merge schema: bad field list");
+      base[(size_t)r] = flat;
+      for (int32_t f = 0; f < n_fields[r]; f++, flat++) {
+        if (names[flat] == nullptr) throw fdb::Error(FDB_ERR_INVALID, "merge schema: field without a name");
+        lists[(size_t)r].push_back(fdb::MergeField{names[flat], kinds[flat]});
+      }
+    }
+    const fdb::MergeSchema u = fdb::unify_merge_schema(lists, exprs);
+    *n_out = (int32_t)u.first.size();
+    *n_sort = (int32_t)u.sort_expr.size();
+    if (*n_out > cap) throw fdb::Error(FDB_ERR_INVALID, "merge schema: " + std::to_string(*n_out) + " output columns, room for " + std::to_string(cap));
+    if (*n_out > 0 && (out_fields == nullptr || (n_records > 0 && col_map == nullptr))) throw fdb::Error(FDB_ERR_INVALID, "merge schema: null output");
+    for (int32_t i = 0; i < *n_out; i++) {
+      out_fields[i] = base[(size_t)u.first[(size_t)i].record] + u.first[(size_t)i].field;
+      for (int32_t r = 0; r < n_records; r++) col_map[(size_t)r * (size_t)*n_out + (size_t)i] = u.map[(size_t)r][(size_t)i];
+    }
+  });
+}
+
+int fdb_osync_create(int32_t inputs, const fdb_order_col* order, int32_t n_order, fdb_osync** out) {
+  return guard(nullptr, [&] {
+    if (out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    *out = new fdb_osync(inputs, order, n_order);
+  });
+}
+
+int fdb_osync_push(fdb_osync* s, int32_t input, const fdb_batch* batch, fdb_batch** merged) {
+  return guard(nullptr, [&] {
+    if (s == nullptr || batch == nullptr || !batch->b || merged == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *merged = nullptr;
+    std::unique_ptr<fdb::DeviceBatch> r = s->s.push(input, batch->b.get());
+    if (r) *merged = new fdb_batch{std::move(r)};
+  });
+}
+
+int fdb_osync_finish(fdb_osync* s, int32_t input, fdb_batch** merged, int32_t* done) {
+  return guard(nullptr, [&] {
+    if (s == nullptr || merged == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *merged = nullptr;
+    bool last = false;
+    std::unique_ptr<fdb::DeviceBatch> r = s->s.finish(input, &last);
+    if (done != nullptr) *done = last ? 1 : 0;
+    if (r) *merged = new fdb_batch{std::move(r)};
+  });
+}
+
+void fdb_osync_close(fdb_osync* s) { delete s; }
 
 int32_t fdb_merge_tile_rows(int32_t words) { return words < 0 ? 0 : (int32_t)fdb_merge_tile(words); }
 

@@ -81,7 +81,10 @@ struct FdbMergeArgs {
 };
 // The gather: one FdbMergeCol per output column, one FdbMergeSrc per (column, input) at [column * n_inputs + input], one FdbMergeInput
 // per input in position order (start ascending).
-struct FdbMergeCol { void* dst; void* dst_valid; int32_t width; int32_t _pad; };
+struct FdbMergeCol { void* dst; void* dst_valid; int32_t width; int32_t lacking; };  // lacking != 0: some input lacks the column (then dst_valid is set)
+// FdbMergeSrc::values == nullptr is the ABSENT marker (≙ FDB_SORT_ABSENT of the key kernel): the input lacks the column — its rows leave
+// as NULL with value 0 and nothing of the source is read. The kernel looks at the marker only in columns whose FdbMergeCol::lacking says
+// that some input lacks them, so a column that every input has is gathered by the code that ran before the marker existed.
 struct FdbMergeSrc { const void* values; const uint8_t* validity; const uint32_t* table; uint32_t table_len; uint32_t _pad; };
 struct FdbMergeInput { uint32_t start, rows; };
 

@@ -219,7 +219,26 @@ __global__ __launch_bounds__(FDB_MERGE_BLOCK) void merge_tile_kernel_any(const F
 // ---- gather --------------------------------------------------------------------------------------------------------------------------------
 // Row i of the result = the row at position rows[i] of the concatenated inputs: blockIdx.y = column, the lane's input is the last one
 // that starts at or before its position. Modelled on take_kernel (fdb_take.hip): validity leaves as one ballot per wave, NULLs are
-// counted per column. A NULL row's dictionary index is never translated: it leaves as 0.
+// counted per column. A NULL row's dictionary index is never translated: it leaves as 0. A row of an input that lacks the column
+// (FdbMergeSrc::values == nullptr) is NULL with value 0; the marker is tested before any load from that source — and only in the columns
+// that some input lacks (FdbMergeCol::lacking, block-uniform): every other column runs the code it ran before the marker existed.
+template <bool LACKING>
+__device__ __forceinline__ bool merge_gather_row(const FdbMergeCol& c, const FdbMergeSrc& s, const bool inside, const uint64_t j, const int64_t i) {
+  const bool have = LACKING ? inside && s.values != nullptr : inside;  // (values == nullptr: the input lacks the column — NULL, value 0, no load)
+  const bool ok = have && (s.validity == nullptr || ((s.validity[j >> 3] >> (j & 7)) & 1) != 0);
+  if (c.width == 4) {
+    uint32_t v = 0u;
+    if (ok) {
+      v = ((const uint32_t*)s.values)[j];
+      if (s.table != nullptr) v = v < s.table_len ? s.table[v] : 0u;
+    }
+    ((uint32_t*)c.dst)[i] = v;
+  } else {
+    ((unsigned long long*)c.dst)[i] = have ? ((const unsigned long long*)s.values)[j] : 0ull;
+  }
+  return ok;
+}
+
 __global__ __launch_bounds__(FDB_MERGE_BLOCK) void merge_gather_kernel(const FdbMergeCol* __restrict__ cols, const FdbMergeSrc* __restrict__ srcs,
                                                                        const FdbMergeInput* __restrict__ inputs, const int n_inputs, const uint32_t* __restrict__ rows,
                                                                        const int64_t n, unsigned long long* __restrict__ nulls) {
@@ -240,17 +259,7 @@ __global__ __launch_bounds__(FDB_MERGE_BLOCK) void merge_gather_kernel(const Fdb
     const uint64_t j = (uint64_t)g - in.start;
     const bool inside = g >= in.start && j < in.rows;
     const FdbMergeSrc s = srcs[(size_t)blockIdx.y * (size_t)n_inputs + (size_t)lo];
-    ok = inside && (s.validity == nullptr || ((s.validity[j >> 3] >> (j & 7)) & 1) != 0);
-    if (c.width == 4) {
-      uint32_t v = 0u;
-      if (ok) {
-        v = ((const uint32_t*)s.values)[j];
-        if (s.table != nullptr) v = v < s.table_len ? s.table[v] : 0u;
-      }
-      ((uint32_t*)c.dst)[i] = v;
-    } else {
-      ((unsigned long long*)c.dst)[i] = inside ? ((const unsigned long long*)s.values)[j] : 0ull;
-    }
+    ok = c.lacking != 0 ? merge_gather_row<true>(c, s, inside, j, i) : merge_gather_row<false>(c, s, inside, j, i);  // (block-uniform choice)
   }
   if (c.dst_valid == nullptr) return;  // (block-uniform: no input has a NULL in this column)
   const unsigned long long valid = __ballot(ok), present = __ballot(live);

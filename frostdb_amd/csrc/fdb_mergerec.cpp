@@ -12,6 +12,9 @@
 // of the inputs is made, neither the keys nor the permutation leaves HBM. What the host does is the plan — the field layout
 // (pack_sort_fields, once for all inputs: a column gets a NULL bit if ANY input has a NULL in it, a dictionary column's width comes from
 // the union's distinct count), the dictionary unions with their translation and rank tables — and the run bookkeeping of the rounds.
+// merge_batches_named is the same plan over a unified field list (unify_merge_schema, fdb_mergerec.h) with a per-input column map: a
+// column an input lacks becomes FDB_SORT_ABSENT in that input's key fields and a null FdbMergeSrc::values in the gather — no stand-in
+// buffer exists anywhere. OrderedSync (the end of this file) calls it once per round of inputs.
 // Like Take and Sort the call borrows a pooled context, runs on its one stream and ends synchronised; all temporaries are the context's.
 #include "fdb_mergerec.h"
 
@@ -31,7 +34,9 @@ namespace {
 struct MergeJob {
   int device = 0;
   uint64_t limit = 0;
+  std::vector<const DevColumn*> schema;  // per output column: the field where the call first shows it (name, format, kind; its record may have no rows)
   std::vector<const DeviceBatch*> recs;  // the inputs that have rows, in call order
+  std::vector<std::vector<const DevColumn*>> cols;  // [input][output column]; nullptr: the input lacks the column (merge_batches_named)
   std::vector<int32_t> call_index;       // … and their places in the call (error texts)
   std::vector<int64_t> start;            // first position of each, a multiple of 4
   int64_t positions = 0;                 // end of the last one
@@ -42,44 +47,40 @@ struct MergeJob {
   int words() const { return (int)bits.size(); }
 };
 
-// Everything that can refuse the call before a launch, and the plan. `in` has n >= 1 non-null records.
-MergeJob plan_merge(const DeviceBatch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, uint64_t limit) {
-  const DeviceBatch& first = *in[0];
+void check_devices(const DeviceBatch* const* in, int32_t n) {
   for (int32_t r = 1; r < n; r++)
-    if (in[r]->device != first.device) throw Error(FDB_ERR_INVALID, "merge: record " + std::to_string(r) + " lives on a different device than record 0");
-  if (n_cols == 0) throw Error(FDB_ERR_INVALID, "merge: at least one column is needed for sorting");
-  if (n_cols < 0 || cols == nullptr) throw Error(FDB_ERR_INVALID, "merge: bad column list");
-  for (int32_t k = 0; k < n_cols; k++) {
-    if (cols[k].index < 0 || (size_t)cols[k].index >= first.cols.size())
-      throw Error(FDB_ERR_INVALID, "merge: column index " + std::to_string(cols[k].index) + " outside the record's " + std::to_string(first.cols.size()) + " columns");
-    if (cols[k].direction > 1u) throw Error(FDB_ERR_INVALID, "merge: unexpected direction value " + std::to_string(cols[k].direction) + ", only 0 (ascending) and 1 (descending) are allowed");
-  }
+    if (in[r]->device != in[0]->device) throw Error(FDB_ERR_INVALID, "merge: record " + std::to_string(r) + " lives on a different device than record 0");
+}
+
+// The plan over the unified field list `schema`: map[r][c] = where column c sits in record r (-1: the record lacks it), cols[k].index a
+// position in `schema`. Everything that is left to refuse before a launch is refused here.
+MergeJob plan_merge_columns(const DeviceBatch* const* in, int32_t n, std::vector<const DevColumn*> schema, const std::vector<std::vector<int32_t>>& map, const fdb_sort_col* cols,
+                            int32_t n_cols, uint64_t limit) {
+  const size_t C = schema.size();
   int64_t total = 0;
   for (int32_t r = 0; r < n; r++) {
-    const DeviceBatch& b = *in[r];
-    if (b.cols.size() != first.cols.size())
-      throw Error(FDB_ERR_INVALID, "merge: record " + std::to_string(r) + " has " + std::to_string(b.cols.size()) + " fields, record 0 has " + std::to_string(first.cols.size()));
-    for (size_t c = 0; c < b.cols.size(); c++)
-      if (b.cols[c].name != first.cols[c].name || b.cols[c].kind != first.cols[c].kind)
-        throw Error(FDB_ERR_INVALID, "merge: field " + std::to_string(c) + " of record " + std::to_string(r) + " (" + b.cols[c].name + ", " + b.cols[c].format + ") is not record 0's (" +
-                                         first.cols[c].name + ", " + first.cols[c].format + ")");
-    total += b.rows;
+    total += in[r]->rows;
     if (total > 0x7FFFFFFFll) throw Error(FDB_ERR_INVALID, "merge: more than 2^31 - 1 rows in total");
   }
   for (int32_t k = 0; k < n_cols; k++) {
-    const DevColumn& c = first.cols[(size_t)cols[k].index];
+    const DevColumn& c = *schema[(size_t)cols[k].index];
     if (c.kind != ColKind::I64 && c.kind != ColKind::U64 && c.kind != ColKind::F64 && c.kind != ColKind::DICT)
       throw Error(FDB_ERR_UNSUPPORTED, "unsupported column type for merging " + c.format + " for column " + c.name);
   }
   MergeJob job;
-  job.device = first.device;
+  job.device = in[0]->device;
   job.limit = limit;
+  job.schema = std::move(schema);
   for (int32_t r = 0; r < n; r++) {
     const DeviceBatch& b = *in[r];
     require_values(b, "merge");
     if (b.rows == 0) continue;
+    std::vector<const DevColumn*> at(C, nullptr);
+    for (size_t c = 0; c < C; c++)
+      if (map[(size_t)r][c] >= 0) at[c] = &b.cols[(size_t)map[(size_t)r][c]];
     for (int32_t k = 0; k < n_cols; k++) {
-      const DevColumn& c = b.cols[(size_t)cols[k].index];
+      if (at[(size_t)cols[k].index] == nullptr) continue;
+      const DevColumn& c = *at[(size_t)cols[k].index];
       if (c.d_values == nullptr || (c.kind == ColKind::DICT && !c.dict)) throw Error(FDB_ERR_UNSUPPORTED, "unsupported column type for merging " + c.format + " for column " + c.name);
       if (((uintptr_t)c.d_values & 15u) != 0) throw Error(FDB_ERR_UNSUPPORTED, "merge: the values of column " + c.name + " are not 16-byte aligned");
     }
@@ -88,62 +89,103 @@ MergeJob plan_merge(const DeviceBatch* const* in, int32_t n, const fdb_sort_col*
     job.start.push_back(job.positions);
     job.positions = (int64_t)align_up((size_t)(job.positions + b.rows), 4);
     job.recs.push_back(&b);
+    job.cols.push_back(std::move(at));
     job.call_index.push_back(r);
   }
   const size_t R = job.recs.size();
   if (R == 0) return job;
-  // the dictionaries: one plan per dictionary column; a sorting column's carries the ranks
-  std::vector<char> sorts(first.cols.size(), 0);
+  // the dictionaries: one plan per dictionary column over the inputs that have it; a sorting column's carries the ranks
+  std::vector<char> sorts(C, 0);
   for (int32_t k = 0; k < n_cols; k++) sorts[(size_t)cols[k].index] = 1;
-  job.dicts.resize(first.cols.size());
-  for (size_t c = 0; c < first.cols.size(); c++) {
-    if (first.cols[c].kind != ColKind::DICT) continue;
+  job.dicts.resize(C);
+  for (size_t c = 0; c < C; c++) {
+    if (job.schema[c]->kind != ColKind::DICT) continue;
     std::vector<std::shared_ptr<HostDict>> ds(R);
-    for (size_t r = 0; r < R; r++) ds[r] = job.recs[r]->cols[c].dict;
-    job.dicts[c] = plan_merge_dict(ds, first.cols[c].name, sorts[c] != 0);
+    bool any = false;
+    for (size_t r = 0; r < R; r++)
+      if (job.cols[r][c] != nullptr) { ds[r] = job.cols[r][c]->dict; any = true; }
+    if (any) { job.dicts[c] = plan_merge_dict(ds, job.schema[c]->name, sorts[c] != 0); continue; }
+    // only records without rows carry the column: it comes out all NULL, with such a record's dictionary
+    MergeDictPlan& p = job.dicts[c];
+    p.out = job.schema[c]->dict ? job.schema[c]->dict : make_dictionary({}, "z");
+    p.tables.assign(R, nullptr);
+    if (sorts[c] != 0) p.out_ranks = dense_ranks(*p.out, &p.distinct);
   }
-  // the key layout, once for all inputs
+  // the key layout, once for all inputs: a column has its NULL bit when some input has a NULL in it, or lacks it
   std::vector<SortColBits> col_bits((size_t)n_cols);
   for (int32_t k = 0; k < n_cols; k++) {
     const size_t c = (size_t)cols[k].index;
     bool any_null = false;
-    for (const DeviceBatch* b : job.recs) any_null = any_null || (b->cols[c].null_count != 0 && b->cols[c].d_validity != nullptr);
-    col_bits[(size_t)k] = SortColBits{first.cols[c].kind == ColKind::DICT ? bits_for(job.dicts[c].distinct) : 64, any_null};
+    for (size_t r = 0; r < R; r++) any_null = any_null || job.cols[r][c] == nullptr || (job.cols[r][c]->null_count != 0 && job.cols[r][c]->d_validity != nullptr);
+    col_bits[(size_t)k] = SortColBits{job.schema[c]->kind == ColKind::DICT ? bits_for(job.dicts[c].distinct) : 64, any_null};
   }
   const std::vector<SortPart> parts = pack_sort_fields(col_bits, &job.bits);
-  // rank tables: one per (dictionary sorting column, input) — one for all inputs where they share the dictionary
+  // rank tables: one per (dictionary sorting column, input that has it) — one for all inputs where they share the dictionary
   std::vector<std::vector<size_t>> rank_off((size_t)n_cols, std::vector<size_t>(R, 0)), rank_len = rank_off;
   for (int32_t k = 0; k < n_cols; k++) {
     const size_t c = (size_t)cols[k].index;
-    if (first.cols[c].kind != ColKind::DICT || col_bits[(size_t)k].value_bits == 0) continue;
+    if (job.schema[c]->kind != ColKind::DICT || col_bits[(size_t)k].value_bits == 0) continue;
     const MergeDictPlan& dp = job.dicts[c];
+    size_t shared_from = R;  // the input whose table a shared dictionary's other inputs reuse
     for (size_t r = 0; r < R; r++) {
-      if (dp.shared && r > 0) { rank_off[(size_t)k][r] = rank_off[(size_t)k][0]; rank_len[(size_t)k][r] = rank_len[(size_t)k][0]; continue; }
+      if (job.cols[r][c] == nullptr) continue;
+      if (dp.shared && shared_from < R) { rank_off[(size_t)k][r] = rank_off[(size_t)k][shared_from]; rank_len[(size_t)k][r] = rank_len[(size_t)k][shared_from]; continue; }
       const std::vector<uint32_t> t = dp.ranks_of(r);
       rank_off[(size_t)k][r] = job.ranks.size();
       rank_len[(size_t)k][r] = t.size();
       job.ranks.insert(job.ranks.end(), t.begin(), t.end());
+      if (dp.shared) shared_from = r;
     }
   }
   job.fields.assign(R, std::vector<std::vector<FdbSortField>>(job.bits.size()));
   for (size_t r = 0; r < R; r++)
     for (const SortPart& p : parts) {
       const fdb_sort_col& sc = cols[p.col];
-      const DevColumn& c = job.recs[r]->cols[(size_t)sc.index];
+      const DevColumn* c = job.cols[r][(size_t)sc.index];
       FdbSortField f;
       std::memset(&f, 0, sizeof(f));
-      f.values = c.d_values;
-      f.validity = col_bits[(size_t)p.col].has_null_bit && c.null_count != 0 ? c.d_validity : nullptr;  // (no NULL in THIS input: every row valid)
-      f.kind = (int32_t)c.kind;
+      f.kind = (int32_t)job.schema[(size_t)sc.index]->kind;
       f.width = p.width; f.shift = p.shift; f.null_shift = p.null_shift;
       f.flags = (sc.direction == 1u ? FDB_SORT_DESC : 0u) | (sc.nulls_first != 0u ? FDB_SORT_NULLS_FIRST : 0u);
-      if (c.kind == ColKind::DICT && p.width > 0) {
-        f.ranks = (const uint32_t*)(uintptr_t)(rank_off[(size_t)p.col][r] + 1);
-        f.rank_len = (uint32_t)std::min<size_t>(rank_len[(size_t)p.col][r], 0xFFFFFFFFu);
+      if (c == nullptr) {
+        f.flags |= FDB_SORT_ABSENT;  // (every row NULL; the kernel loads nothing for this field)
+      } else {
+        f.values = c->d_values;
+        f.validity = col_bits[(size_t)p.col].has_null_bit && c->null_count != 0 ? c->d_validity : nullptr;  // (no NULL in THIS input: every row valid)
+        if (c->kind == ColKind::DICT && p.width > 0) {
+          f.ranks = (const uint32_t*)(uintptr_t)(rank_off[(size_t)p.col][r] + 1);
+          f.rank_len = (uint32_t)std::min<size_t>(rank_len[(size_t)p.col][r], 0xFFFFFFFFu);
+        }
       }
       job.fields[r][(size_t)p.word].push_back(f);
     }
   return job;
+}
+
+// Everything that can refuse the call before a launch, and the plan. `in` has n >= 1 non-null records.
+MergeJob plan_merge(const DeviceBatch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, uint64_t limit) {
+  const DeviceBatch& first = *in[0];
+  check_devices(in, n);
+  if (n_cols == 0) throw Error(FDB_ERR_INVALID, "merge: at least one column is needed for sorting");
+  if (n_cols < 0 || cols == nullptr) throw Error(FDB_ERR_INVALID, "merge: bad column list");
+  for (int32_t k = 0; k < n_cols; k++) {
+    if (cols[k].index < 0 || (size_t)cols[k].index >= first.cols.size())
+      throw Error(FDB_ERR_INVALID, "merge: column index " + std::to_string(cols[k].index) + " outside the record's " + std::to_string(first.cols.size()) + " columns");
+    if (cols[k].direction > 1u) throw Error(FDB_ERR_INVALID, "merge: unexpected direction value " + std::to_string(cols[k].direction) + ", only 0 (ascending) and 1 (descending) are allowed");
+  }
+  for (int32_t r = 0; r < n; r++) {
+    const DeviceBatch& b = *in[r];
+    if (b.cols.size() != first.cols.size())
+      throw Error(FDB_ERR_INVALID, "merge: record " + std::to_string(r) + " has " + std::to_string(b.cols.size()) + " fields, record 0 has " + std::to_string(first.cols.size()));
+    for (size_t c = 0; c < b.cols.size(); c++)
+      if (b.cols[c].name != first.cols[c].name || b.cols[c].kind != first.cols[c].kind)
+        throw Error(FDB_ERR_INVALID, "merge: field " + std::to_string(c) + " of record " + std::to_string(r) + " (" + b.cols[c].name + ", " + b.cols[c].format + ") is not record 0's (" +
+                                         first.cols[c].name + ", " + first.cols[c].format + ")");
+  }
+  std::vector<const DevColumn*> schema;
+  std::vector<int32_t> identity;
+  for (size_t c = 0; c < first.cols.size(); c++) { schema.push_back(&first.cols[c]); identity.push_back((int32_t)c); }
+  return plan_merge_columns(in, n, std::move(schema), std::vector<std::vector<int32_t>>((size_t)n, identity), cols, n_cols, limit);
 }
 
 struct Merged { const uint32_t* perm = nullptr; int64_t n = 0; uint32_t* d_error = nullptr; };
@@ -261,12 +303,11 @@ Merged merge_on_device(MergeJob job, CallScope* cs, std::vector<hipEvent_t>* mar
 }
 
 // Row perm[i] of the concatenated inputs → row i of a new record of `n` > 0 rows: one launch, one wait (modelled on fdb_take.cpp's gather).
-// A column without a NULL in any input is emitted without a bitmap.
+// A column gets a bitmap when some input has one for it or lacks the column; one that ends without a NULL is emitted without it.
 std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, const Merged& m, hipEvent_t done) {
   Context* ctx = cs->ctx;
   hipStream_t stream = ctx->stream;
-  const DeviceBatch& first = *job.recs[0];
-  const size_t C = first.cols.size(), R = job.recs.size();
+  const size_t C = job.schema.size(), R = job.recs.size();
   const int64_t n = m.n;
   std::unique_ptr<DeviceBatch> out(new DeviceBatch());
   DrainOnUnwind drain{stream};  // (after `out`: its arena outlives the queued kernel)
@@ -277,9 +318,9 @@ std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, c
   size_t bytes = 0;
   for (size_t c = 0; c < C; c++) {
     val_off[c] = bytes;
-    bytes += align_up(rows * (first.cols[c].kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
+    bytes += align_up(rows * (job.schema[c]->kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
     bool any_validity = false;
-    for (const DeviceBatch* b : job.recs) any_validity = any_validity || b->cols[c].d_validity != nullptr;
+    for (size_t r = 0; r < R; r++) any_validity = any_validity || job.cols[r][c] == nullptr || job.cols[r][c]->d_validity != nullptr;
     if (any_validity) { bit_off[c] = bytes; bytes += align_up(bitmap_bytes + kTailPad, 256); }
   }
   if (bytes > 0) { out->arena = device_pool_alloc(job.device, bytes); out->arena_bytes = bytes; }
@@ -301,11 +342,12 @@ std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, c
         std::memset(&mc[c], 0, sizeof(FdbMergeCol));
         mc[c].dst = (unsigned char*)out->arena + val_off[c];
         mc[c].dst_valid = bit_off[c] != (size_t)-1 ? (unsigned char*)out->arena + bit_off[c] : nullptr;
-        mc[c].width = first.cols[c].kind == ColKind::DICT ? 4 : 8;
+        mc[c].width = job.schema[c]->kind == ColKind::DICT ? 4 : 8;
         for (size_t r = 0; r < R; r++) {
           FdbMergeSrc& s = ms[c * R + r];
           std::memset(&s, 0, sizeof(s));
-          const DevColumn& col = job.recs[r]->cols[c];
+          if (job.cols[r][c] == nullptr) { mc[c].lacking = 1; continue; }  // values == nullptr, the gather's ABSENT marker: its rows leave as NULL, nothing is read
+          const DevColumn& col = *job.cols[r][c];
           s.values = col.d_values;
           s.validity = col.d_validity;
           if (col.kind == ColKind::DICT && !job.dicts[c].shared && job.dicts[c].tables[r] && !job.dicts[c].tables[r]->empty()) {  // (an empty dictionary: every row NULL)
@@ -327,7 +369,7 @@ std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, c
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   if (h_error != 0) throw Error(FDB_ERR_STATE, "merge: a tile's split points crossed (the inputs passed the order check: this is a bug)");
   for (size_t c = 0; c < C; c++) {
-    const DevColumn& src = first.cols[c];
+    const DevColumn& src = *job.schema[c];
     DevColumn d;
     d.name = src.name; d.format = src.format; d.kind = src.kind;
     d.dict = src.kind == ColKind::DICT ? job.dicts[c].out : src.dict;
@@ -348,6 +390,17 @@ void check_records(const DeviceBatch* const* in, int32_t n) {
     if (in[r] == nullptr) throw Error(FDB_ERR_INVALID, "merge: record " + std::to_string(r) + " is null");
 }
 
+std::vector<MergeOrder> check_order(const fdb_order_col* order, int32_t n_order) {
+  if (order == nullptr || n_order <= 0) throw Error(FDB_ERR_INVALID, "merge: at least one order expression is needed");
+  std::vector<MergeOrder> exprs;
+  for (int32_t k = 0; k < n_order; k++) {
+    if (order[k].name == nullptr) throw Error(FDB_ERR_INVALID, "merge: order expression " + std::to_string(k) + " has no name");
+    if (order[k].direction > 1u) throw Error(FDB_ERR_INVALID, "merge: unexpected direction value " + std::to_string(order[k].direction) + ", only 0 (ascending) and 1 (descending) are allowed");
+    exprs.push_back(MergeOrder{order[k].name, order[k].dynamic != 0});
+  }
+  return exprs;
+}
+
 }  // namespace
 
 std::unique_ptr<DeviceBatch> merge_batches(const DeviceBatch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, uint64_t limit) {
@@ -359,6 +412,87 @@ std::unique_ptr<DeviceBatch> merge_batches(const DeviceBatch* const* in, int32_t
   DrainOnUnwind drain{cs.ctx->stream};
   const Merged m = merge_on_device(job, &cs, nullptr);
   return gather_merged(job, &cs, m, nullptr);
+}
+
+std::unique_ptr<DeviceBatch> merge_batches_named(const DeviceBatch* const* in, int32_t n, const fdb_order_col* order, int32_t n_order, uint64_t limit) {
+  check_records(in, n);
+  check_devices(in, n);
+  const std::vector<MergeOrder> exprs = check_order(order, n_order);
+  std::vector<std::vector<MergeField>> lists((size_t)n);
+  for (int32_t r = 0; r < n; r++)
+    for (const DevColumn& c : in[r]->cols) lists[(size_t)r].push_back(MergeField{c.name, (int32_t)c.kind});
+  const MergeSchema u = unify_merge_schema(lists, exprs);
+  std::vector<const DevColumn*> schema;
+  for (const MergeSchema::At& at : u.first) schema.push_back(&in[at.record]->cols[(size_t)at.field]);
+  std::vector<fdb_sort_col> cols;
+  if (n > 1)  // (a single record's order is not looked at: no key)
+    for (size_t k = 0; k < u.sort_expr.size(); k++) cols.push_back(fdb_sort_col{(int32_t)k, order[u.sort_expr[k]].direction, order[u.sort_expr[k]].nulls_first});
+  MergeJob job = plan_merge_columns(in, n, schema, u.map, cols.data(), (int32_t)cols.size(), limit);
+  if (job.recs.empty()) {  // no rows at all: the unified schema
+    std::unique_ptr<DeviceBatch> out(new DeviceBatch());
+    out->device = job.device;
+    for (const DevColumn* c : schema) {
+      DevColumn d;
+      d.name = c->name; d.format = c->format; d.kind = c->kind; d.dict = c->dict;
+      if (d.kind == ColKind::DICT && !d.dict) d.dict = make_dictionary({}, "z");
+      out->cols.push_back(std::move(d));
+    }
+    return out;
+  }
+  CallScope cs(job.device);
+  DrainOnUnwind drain{cs.ctx->stream};
+  const Merged m = merge_on_device(job, &cs, nullptr);
+  return gather_merged(job, &cs, m, nullptr);
+}
+
+// ---- OrderedSync -----------------------------------------------------------------------------------------------------------------------------
+OrderedSync::OrderedSync(int32_t inputs, const fdb_order_col* order, int32_t n_order) {
+  if (inputs <= 0) throw Error(FDB_ERR_INVALID, "ordered synchronizer: at least one input is needed");
+  for (const MergeOrder& o : check_order(order, n_order)) names_.push_back(o.name);
+  order_.assign(order, order + n_order);
+  for (size_t k = 0; k < order_.size(); k++) order_[k].name = names_[k].c_str();  // (names_ is not touched again)
+  parked_.assign((size_t)inputs, nullptr);
+  finished_.assign((size_t)inputs, 0);
+  running_ = inputs;
+}
+
+void OrderedSync::check_input(int32_t input) const {
+  if (input < 0 || (size_t)input >= parked_.size()) throw Error(FDB_ERR_INVALID, "ordered synchronizer: input " + std::to_string(input) + " outside the " + std::to_string(parked_.size()) + " inputs");
+}
+
+std::unique_ptr<DeviceBatch> OrderedSync::merge_round() {
+  std::vector<const DeviceBatch*> recs;
+  for (const DeviceBatch* b : parked_)
+    if (b != nullptr) recs.push_back(b);
+  std::fill(parked_.begin(), parked_.end(), nullptr);  // (whatever the merge answers: the round is over)
+  waiting_ = 0;
+  return merge_batches_named(recs.data(), (int32_t)recs.size(), order_.data(), (int32_t)order_.size(), 0);
+}
+
+std::unique_ptr<DeviceBatch> OrderedSync::push(int32_t input, const DeviceBatch* batch) {
+  if (batch == nullptr) throw Error(FDB_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(mu_);
+  check_input(input);
+  if (finished_[(size_t)input]) throw Error(FDB_ERR_STATE, "ordered synchronizer: input " + std::to_string(input) + " has finished");
+  if (parked_[(size_t)input] != nullptr) throw Error(FDB_ERR_STATE, "ordered synchronizer: input " + std::to_string(input) + " already waits in this round");
+  parked_[(size_t)input] = batch;
+  waiting_++;
+  if (waiting_ != running_) return nullptr;
+  return merge_round();  // this is the last input of the round (ordered_synchronizer.go:76-88)
+}
+
+std::unique_ptr<DeviceBatch> OrderedSync::finish(int32_t input, bool* done) {
+  std::lock_guard<std::mutex> lock(mu_);
+  if (done != nullptr) *done = false;
+  check_input(input);
+  if (running_ == 0) throw Error(FDB_ERR_STATE, "too many OrderedSynchronizer Finish calls");
+  if (finished_[(size_t)input]) throw Error(FDB_ERR_STATE, "ordered synchronizer: input " + std::to_string(input) + " has already finished");
+  if (parked_[(size_t)input] != nullptr) throw Error(FDB_ERR_STATE, "ordered synchronizer: input " + std::to_string(input) + " waits in this round and cannot finish before it is merged");
+  finished_[(size_t)input] = 1;
+  running_--;
+  if (done != nullptr) *done = running_ == 0;
+  if (running_ > 0 && running_ == waiting_) return merge_round();  // everyone else waits (:96-104)
+  return nullptr;
 }
 
 void merge_bench(const DeviceBatch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, int32_t reps, int32_t warmup, double* merge_ms, double* gather_ms,

@@ -31,6 +31,8 @@
 
 #define FDB_SORT_DESC 1u         // FdbSortField::flags
 #define FDB_SORT_NULLS_FIRST 2u
+#define FDB_SORT_ABSENT 4u       // the record has no such column (a merge of records with differing field lists): every row is NULL and
+                                 // neither values, validity nor ranks are read — they may be nullptr
 
 FDB_SORTKEY_HD uint64_t fdb_sortkey_i64(uint64_t raw) { return raw ^ (1ull << 63); }
 

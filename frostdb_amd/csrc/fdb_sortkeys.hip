@@ -6,7 +6,8 @@
 // 4-byte index column with one, and the 4 validity bits of the lane sit in one byte (the row number is a multiple of 4); through a permutation
 // the loads are gathers by nature and only the permutation itself (one 16-byte load) and the keys (two 16-byte stores) are contiguous. The
 // field descriptors are wave-uniform and read through the constant address space (scalar loads); rank tables are read from global memory,
-// where a dictionary's table stays hot in L2. A NULL row's raw slot is never used: not as a value, not as an index into a rank table.
+// where a dictionary's table stays hot in L2. A NULL row's raw slot is never used: not as a value, not as an index into a rank table. A field
+// marked FDB_SORT_ABSENT (the merge of records with differing field lists) has no column behind it: its rows are NULL and nothing is loaded.
 #include <hip/hip_runtime.h>
 
 #include "fdb_sortkey.h"
@@ -47,8 +48,12 @@ __global__ __launch_bounds__(FDB_SORT_BLOCK) void sort_keys_kernel(const FdbSort
     const FDB_GLOBAL uint32_t* ranks = (const FDB_GLOBAL uint32_t*)fields[f].ranks;
     const uint32_t rank_len = fields[f].rank_len, flags = fields[f].flags;
     const int32_t kind = fields[f].kind, width = fields[f].width, shift = fields[f].shift, null_shift = fields[f].null_shift;
+    const bool absent = (flags & FDB_SORT_ABSENT) != 0u;  // (wave-uniform) every row NULL, nothing of the column is loaded
     bool valid[FDB_SORT_ROWS];
-    if (validity == nullptr) {
+    if (absent) {
+#pragma unroll
+      for (int k = 0; k < FDB_SORT_ROWS; k++) valid[k] = false;
+    } else if (validity == nullptr) {
 #pragma unroll
       for (int k = 0; k < FDB_SORT_ROWS; k++) valid[k] = true;
     } else if (!PERM) {
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(FDB_SORT_BLOCK) void sort_keys_kernel(const FdbSort
 #pragma unroll
       for (int k = 0; k < FDB_SORT_ROWS; k++) valid[k] = live[k] && (((uint32_t)validity[row[k] >> 3] >> (uint32_t)(row[k] & 7)) & 1u) != 0u;
     }
-    if (width > 0) {  // (wave-uniform)
+    if (width > 0 && !absent) {  // (wave-uniform; an absent column's value field stays 0, as under every NULL)
       u64 v[FDB_SORT_ROWS];
       if (kind == FDB_SORT_DICT) {
         uint32_t idx[FDB_SORT_ROWS];

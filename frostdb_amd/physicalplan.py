@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 from typing import Any, Callable, List, Optional, Sequence
 
 import pyarrow as pa
@@ -152,6 +153,13 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_sort_key.argtypes = [i32, ctypes.c_uint32, ctypes.c_uint64, P(ctypes.c_uint64)]
     L.fdb_sort_bench.argtypes = [vp, vp, i32, i32, i32, P(ctypes.c_double), P(ctypes.c_double), P(i32)]
     L.fdb_batches_merge.argtypes = [P(vp), i32, vp, i32, ctypes.c_uint64, P(vp)]
+    L.fdb_batches_merge_named.argtypes = [P(vp), i32, vp, i32, ctypes.c_uint64, P(vp)]
+    L.fdb_selftest_merge_schema.argtypes = [P(ctypes.c_char_p), P(i32), P(i32), i32, vp, i32, P(i32), P(i32), i32, P(i32), P(i32)]
+    L.fdb_osync_create.argtypes = [i32, vp, i32, P(vp)]
+    L.fdb_osync_push.argtypes = [vp, i32, vp, P(vp)]
+    L.fdb_osync_finish.argtypes = [vp, i32, P(vp), P(i32)]
+    L.fdb_osync_close.argtypes = [vp]
+    L.fdb_osync_close.restype = None
     L.fdb_merge_tile_rows.argtypes = [i32]
     L.fdb_merge_tile_rows.restype = i32
     L.fdb_selftest_merge_path.argtypes = [vp, i64, vp, i64, i32, vp]
@@ -286,6 +294,28 @@ def selftest_merge_path(a, b, words: int):
     return out[: len(ka) + len(kb)]
 
 
+def selftest_merge_schema(records, order_by):
+    """The schema union and column map of ``ResidentBatch.merge_named`` run on the host (fdb_selftest_merge_schema; no device).
+    `records`: per record a list of ``(field name, column kind)``; `order_by` as for ``merge_named``. Returns ``(columns, n_sort, col_map)``:
+    per output column the ``(record, field)`` where it is first seen, how many leading columns are sorting columns, and per record the
+    position of every output column inside it (-1: the record lacks it). What the schema rules refuse raises FdbError."""
+    records = [list(r) for r in records]
+    flat = [(r, f, name, kind) for r, rec in enumerate(records) for f, (name, kind) in enumerate(rec)]
+    names = (ctypes.c_char_p * max(1, len(flat)))(*[x[2].encode("utf-8") for x in flat])
+    kinds = (ctypes.c_int32 * max(1, len(flat)))(*[int(x[3]) for x in flat])
+    counts = (ctypes.c_int32 * max(1, len(records)))(*[len(r) for r in records])
+    arr, n, _keep = _order_cols(order_by)
+    cap = max(1, len(flat))
+    out_fields = (ctypes.c_int32 * cap)()
+    col_map = (ctypes.c_int32 * (cap * max(1, len(records))))()
+    n_out, n_sort = ctypes.c_int32(), ctypes.c_int32()
+    rc = lib().fdb_selftest_merge_schema(names, kinds, counts, len(records), arr, n, out_fields, col_map, cap, ctypes.byref(n_out), ctypes.byref(n_sort))
+    if rc != 0:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    columns = [flat[out_fields[i]][:2] for i in range(n_out.value)]
+    return columns, n_sort.value, [[col_map[r * n_out.value + i] for i in range(n_out.value)] for r in range(len(records))]
+
+
 def live_allocations() -> dict:
     """Device blocks / bytes and pinned result blocks the library owns right now (0 once everything is closed and released)."""
     a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
@@ -346,6 +376,33 @@ def _raise(code: int, msg: str):
 class SortCol(ctypes.Structure):
     """fdb_sort_col ≙ arrowutils.SortingColumn: column position, direction (0 ascending / 1 descending), nulls_first."""
     _fields_ = [("index", ctypes.c_int32), ("direction", ctypes.c_uint32), ("nulls_first", ctypes.c_uint32)]
+
+
+class OrderCol(ctypes.Structure):
+    """fdb_order_col: an order-by expression by name — ``dynamic`` != 0 matches every field called ``name.<something>`` — with the
+    direction and NULL placement of every column it matches."""
+    _fields_ = [("name", ctypes.c_char_p), ("dynamic", ctypes.c_int32), ("direction", ctypes.c_uint32), ("nulls_first", ctypes.c_uint32)]
+
+
+def _order_cols(order_by):
+    """`order_by` → (fdb_order_col array, count, what keeps its strings alive). An entry is ``Col(name)`` / ``DynCol(name)``, a bare name,
+    ``(expr, descending=False, nulls_first=False)`` or a raw ``OrderCol``."""
+    if isinstance(order_by, (str, Column, OrderCol)):
+        order_by = [order_by]
+    cols, keep = [], []
+    for o in order_by:
+        if isinstance(o, OrderCol):
+            cols.append(o)
+            continue
+        o = (o,) if isinstance(o, (str, Column)) else tuple(o)
+        if not 1 <= len(o) <= 3:
+            raise ValueError("an order-by entry is (expr, descending=False, nulls_first=False)")
+        expr = Column(o[0]) if isinstance(o[0], str) else o[0]
+        if not isinstance(expr, Column):
+            raise TypeError("an order-by expression is Col(name) or DynCol(name)")
+        keep.append(expr.name.encode("utf-8"))
+        cols.append(OrderCol(keep[-1], 1 if expr.dynamic else 0, 1 if len(o) > 1 and o[1] else 0, 1 if len(o) > 2 and o[2] else 0))
+    return (OrderCol * max(1, len(cols)))(*cols), len(cols), (keep, cols)
 
 
 class ParquetChunk(ctypes.Structure):
@@ -551,6 +608,21 @@ class ResidentBatch:
         records, handles, arr, n = ResidentBatch._merge_args(records, columns)
         out = ctypes.c_void_p()
         rc = lib().fdb_batches_merge(handles, len(records), arr, n, int(limit), ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        return ResidentBatch(None, device=records[0].device, _handle=out.value)
+
+    @staticmethod
+    def merge_named(records, order_by, limit: int = 0) -> "ResidentBatch":
+        """≙ OrderedSynchronizer.ensureSameSchema + MergeRecords: ``merge`` for records whose field lists differ
+        (fdb_batches_merge_named). `order_by`: ``Col(name)`` / ``DynCol(name)`` — a dynamic expression stands for every matching column,
+        in name order — or ``(expr, descending, nulls_first)``. The result has the sorting columns first, then every other field in
+        first-seen order; a record's rows are NULL in the columns it lacks."""
+        records = list(records)
+        handles = (ctypes.c_void_p * max(1, len(records)))(*[r.handle for r in records])
+        arr, n, _keep = _order_cols(order_by)
+        out = ctypes.c_void_p()
+        rc = lib().fdb_batches_merge_named(handles, len(records), arr, n, int(limit), ctypes.byref(out))
         if rc != 0:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return ResidentBatch(None, device=records[0].device, _handle=out.value)
@@ -1045,6 +1117,64 @@ class ReservoirSampler:
         if getattr(self, "handle", None):
             lib().fdb_sampler_close(self.handle)
             self.handle = None
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
+
+class OrderedSynchronizer:
+    """≙ physicalplan.OrderedSynchronizer (ordered_synchronizer.go) over resident records, without the blocking: `inputs` chains each
+    contribute at most one record to a round; the call that completes a round — the push of the last running input, or the Finish that
+    leaves only waiting inputs — returns the round's records merged by `order_by` (``ResidentBatch.merge_named``), every other call
+    returns None. Parked records are referenced here until their round is merged. Safe to call from several threads."""
+
+    def __init__(self, inputs: int, order_by):
+        self.inputs = int(inputs)
+        self._order, n, self._keep = _order_cols(order_by)
+        self._parked = {}
+        self._device = 0
+        self._lock = threading.Lock()  # call and bookkeeping are one step (the library serialises the calls anyway: it merges under its mutex)
+        out = ctypes.c_void_p()
+        rc = lib().fdb_osync_create(self.inputs, self._order, n, ctypes.byref(out))
+        if rc != 0:
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        self.handle = out.value
+
+    def _merged(self, rc: int, out) -> Optional["ResidentBatch"]:
+        if rc != 0:  # (what a failed round parked stays referenced until the next round is merged: longer than needed, never shorter)
+            _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+        if not out.value:
+            return None
+        self._parked.clear()  # the round is merged: its records are the callers' again
+        return ResidentBatch(None, device=self._device, _handle=out.value)
+
+    def Callback(self, input: int, rb: "ResidentBatch") -> Optional["ResidentBatch"]:
+        out = ctypes.c_void_p()
+        with self._lock:
+            rc = lib().fdb_osync_push(self.handle, int(input), rb.handle, ctypes.byref(out))
+            if rc == 0 and not out.value:
+                self._parked[int(input)] = rb
+            self._device = rb.device
+            return self._merged(rc, out)
+
+    def Finish(self, input: int):
+        """→ (the merged record of the round this call completed, or None; True when the last input has finished)"""
+        out, done = ctypes.c_void_p(), ctypes.c_int32()
+        with self._lock:
+            rc = lib().fdb_osync_finish(self.handle, int(input), ctypes.byref(out), ctypes.byref(done))
+            return self._merged(rc, out), bool(done.value)
+
+    def Draw(self) -> str:
+        return "OrderedSynchronizer"
+
+    def Close(self) -> None:
+        if getattr(self, "handle", None):
+            lib().fdb_osync_close(self.handle)
+            self.handle = None
+        self._parked = {}
 
     def __del__(self):
         try:

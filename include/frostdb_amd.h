@@ -665,9 +665,67 @@ FDB_API int fdb_sort_bench(const fdb_batch* in, const fdb_sort_col* cols, int32_
  * n == 1 is fdb_batch_limit of the record (its order is not looked at); a total of 0 rows gives a zero-row record of the schema.
  * FDB_ERR_INVALID: n == 0, a null record, records on different devices, no sorting columns, a column index or direction out of range,
  * differing field lists, more than 2^31 - 1 rows in total. FDB_ERR_UNSUPPORTED: a bool sorting column, a column the resident record
- * cannot hold, a field that is utf8 in one record and binary in another. ensureSameSchema's virtual NULL columns
- * (ordered_synchronizer.go:143-241) are not built. Not bound by the Go shim yet. */
+ * cannot hold, a field that is utf8 in one record and binary in another. Records whose field lists differ (ensureSameSchema's virtual NULL
+ * columns, ordered_synchronizer.go:143-241) go through fdb_batches_merge_named below. Not bound by the Go shim yet. */
 FDB_API int fdb_batches_merge(const fdb_batch* const* in, int32_t n, const fdb_sort_col* cols, int32_t n_cols, uint64_t limit, fdb_batch** out);
+/* ---- MergeRecords over resident records whose field lists differ; OrderedSynchronizer --------------------------------------------------
+ * ≙ OrderedSynchronizer.ensureSameSchema + arrowutils.MergeRecords (query/physicalplan/ordered_synchronizer.go:143-241, :116-137): the
+ * merge of fdb_batches_merge for records that need not carry the same fields — dynamic columns (`labels.*`) differ from row group to row
+ * group. The sorting columns are NAMED: `name` / `dynamic` have the vocabulary of fdb_group_expr — dynamic == 0 matches the field
+ * called `name`, dynamic != 0 every field called `name.<something>`; direction / nulls_first as in fdb_sort_col, they apply to every
+ * column the expression matches. The unified schema is computed on the host before any launch (:155-208): for each order expression in
+ * turn, the fields that match it in ANY input (inputs without rows take part in the schema) become sorting columns, several matches in
+ * byte order of their names (dynparquet.MergeDeduplicatedDynCols is sort.Strings); an expression that matches nothing is skipped
+ * ("this field will just be considered to be null", :173-177); after the sorting columns come all remaining fields, each once. A record's
+ * rows are NULL in every column it lacks — where the reference builds a virtual NULL array per such column, here the kernels are told
+ * that the (input, column) pair is absent and nothing is allocated, filled or read for it; such a column always has its validity bitmap,
+ * and null_count is exact. Inputs that lack a sorting column sit where its NULLs sit and are ordered by the remaining columns. The output
+ * always has the unified column order, also for n == 1 (the record's columns rearranged, cut to `limit`; its order is not looked at, as
+ * in fdb_batches_merge). If no expression matches any field the key is empty and the result is the concatenation in input order, cut to
+ * `limit`: the stable sort under an empty key, one of the orders the reference may produce. A dictionary column is united over the
+ * inputs that have it ("every input shares one dictionary" means every input that has the column); one that only inputs without rows
+ * carry comes out all NULL with such an input's dictionary (an empty binary one if it has none).
+ * Deviations from the reference, besides those of fdb_batches_merge: the remaining fields come in first-seen order — input order, then
+ * field order — where the reference iterates a Go map (any order is legal there, this one is deterministic); a field is never emitted
+ * twice — with two or more order expressions the reference's leftoverCols also receives the columns that matched ANOTHER expression
+ * (:159-168) and its schema duplicates them; a field an earlier expression matched is not matched again by a later one; each expression
+ * carries its own direction and NULL placement (the reference merges ascending, NULLs last only, SortingColumn{Index: i}, :198-201).
+ * Refusals, all answered before any launch: n == 0, a null record, records on different devices, order == NULL, n_order <= 0, a null
+ * `name`, a direction above 1: FDB_ERR_INVALID; a record with two fields of one name: FDB_ERR_INVALID "found multiple fields … for name
+ * …" (:219-227); a name whose column kind differs between two inputs: FDB_ERR_INVALID naming both records; more than 2^31 - 1 rows in
+ * total: FDB_ERR_INVALID; a bool sorting column, a field that is utf8 in one record and binary in another: FDB_ERR_UNSUPPORTED, as
+ * fdb_batches_merge. An unordered input is FDB_ERR_INVALID naming the record's place in the call and the first offending row.
+ * Not bound by the Go shim yet. */
+typedef struct fdb_order_col { const char* name; int32_t dynamic; uint32_t direction; uint32_t nulls_first; } fdb_order_col;
+FDB_API int fdb_batches_merge_named(const fdb_batch* const* in, int32_t n, const fdb_order_col* order, int32_t n_order, uint64_t limit, fdb_batch** out);
+/* host-only: the schema union and the per-input column map behind fdb_batches_merge_named. names / kinds of all fields of all records
+ * back to back (n_fields[r] of record r); out_fields[i] = position, in that flat list, of the first occurrence of output column i;
+ * *n_sort = how many leading output columns are sorting columns; col_map[r * *n_out + i] = the field's position inside record r, or -1.
+ * out_fields has room for `cap` columns, col_map for n_records * cap entries; *n_out and *n_sort are set even where *n_out > cap, which
+ * writes nothing else and answers FDB_ERR_INVALID. Directions are not looked at. Refuses what the schema rules refuse: a record with two
+ * fields of one name, a name whose kind differs between two records. */
+FDB_API int fdb_selftest_merge_schema(const char* const* names, const int32_t* kinds, const int32_t* n_fields, int32_t n_records, const fdb_order_col* order,
+                                      int32_t n_order, int32_t* out_fields, int32_t* col_map, int32_t cap, int32_t* n_out, int32_t* n_sort);
+/* ≙ OrderedSynchronizer (ordered_synchronizer.go:59-137) over resident records, without the blocking — a C ABI driven from one thread
+ * cannot park its caller on a channel; a caller that wants the reference's blocking (the Go shim) keeps the channel on its side.
+ * `inputs` chains feed the synchronizer; each contributes at most one record to a ROUND. fdb_osync_push parks `batch` as input `input`'s
+ * contribution to the current round — the batch is BORROWED: the caller keeps it alive until the round it belongs to has been merged.
+ * The call that makes "inputs waiting == inputs still running" completes the round: it merges the parked records with
+ * fdb_batches_merge_named (limit 0; the records in input order, so the order of ties does not depend on who arrived first), returns
+ * the result in *merged (a new batch the caller owns) and empties the round; every other push sets *merged = NULL. fdb_osync_finish
+ * retires an input; if after it running > 0 && running == waiting this call completes the round (:96-104); *done = 1 when the last
+ * input has finished. The schema is computed anew every round, so rounds may differ in their fields. A round whose merge fails (an
+ * unordered input, say) returns that error to the completing call and is discarded; the synchronizer stays usable.
+ * FDB_ERR_STATE: a push from an input that has finished or that already waits in this round (the reference cannot get there: it
+ * blocks), a finish from an input that has finished or waits in this round, one more finish than inputs ("too many OrderedSynchronizer
+ * Finish calls"). FDB_ERR_INVALID: inputs <= 0, an order list fdb_batches_merge_named refuses, an input number outside the inputs, a
+ * null argument. Calls may come from different threads: one mutex guards the state, the merge of a round included. Closing with records
+ * parked forgets them. Errors are read with fdb_last_error() on the calling thread. Not bound by the Go shim yet. */
+typedef struct fdb_osync fdb_osync;
+FDB_API int fdb_osync_create(int32_t inputs, const fdb_order_col* order, int32_t n_order, fdb_osync** out);
+FDB_API int fdb_osync_push(fdb_osync* s, int32_t input, const fdb_batch* batch, fdb_batch** merged);
+FDB_API int fdb_osync_finish(fdb_osync* s, int32_t input, fdb_batch** merged, int32_t* done);
+FDB_API void fdb_osync_close(fdb_osync* s);
 /* the output tile (rows) of the merge kernel for a key of `words` 64-bit words: tests track the kernel through it */
 FDB_API int32_t fdb_merge_tile_rows(int32_t words);
 /* host-only: the kernels' merge-path code (diagonal search, per-lane serial merge, tile by tile and lane by lane) over two sorted runs

@@ -2,7 +2,7 @@
 # Host-only memory-safety check of the device MergeRecords' host code under AddressSanitizer + UBSan: the key layout across records
 # (frostdb_amd/csrc/fdb_sortplan.h: pack_sort_fields, bits_for, dense_ranks), the dictionary plan of a column across the inputs with its
 # union, translation and rank tables (fdb_mergerec.h: plan_merge_dict, with fdb_reservoir.h's DictUnion and fdb_arrow.cpp's dictionary
-# constructors) and the merge-path walk behind fdb_selftest_merge_path (fdb_mergepath.h: the code the kernels compile, on host arrays).
+# constructors), the schema union and per-input column map of records whose field lists differ (fdb_mergerec.h: unify_merge_schema) and the merge-path walk behind fdb_selftest_merge_path (fdb_mergepath.h: the code the kernels compile, on host arrays).
 # No GPU, no HIP, no python: a stand-alone program (tools/asan_merge_main.cpp) is compiled with g++ and run. Prints "asan merge ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -1,6 +1,6 @@
 // Stand-alone driver of the host-only half of the device MergeRecords for tools/asan_merge.sh: the key layout across records
-// (fdb_sortplan.h), the dictionary plan of a column across the inputs (fdb_mergerec.h, host-only part) and the merge-path walk of
-// fdb_selftest_merge_path (fdb_mergepath.h). No GPU, no HIP, no python. Prints "asan merge ok" and exits 0 when every check holds.
+// (fdb_sortplan.h), the dictionary plan of a column across the inputs and the schema union with its per-input column map of records
+// whose field lists differ (fdb_mergerec.h, host-only part) and the merge-path walk of fdb_selftest_merge_path (fdb_mergepath.h). No GPU, no HIP, no python. Prints "asan merge ok" and exits 0 when every check holds.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -124,9 +124,85 @@ static void merge_paths() {
   (void)fdb_merge_path_host(a.data(), (int64_t)a.size(), b.data(), (int64_t)b.size(), 1, out.data());
 }
 
+// the schema union and the column map over random field lists: dynamic and plain expressions, 0 to 6 records, empty records, and —
+// refused — duplicate names and kind conflicts
+static void schemas() {
+  const char* pool[] = {"labels.a", "labels.b", "labels.c", "labels.", "labels", "labelsx", "pprof.x", "pprof.y", "timestamp", "value", ""};
+  const size_t P = sizeof(pool) / sizeof(pool[0]);
+  uint64_t seed = 21;
+  int refused = 0, accepted = 0;
+  for (int round = 0; round < 600; round++) {
+    std::vector<std::vector<MergeField>> recs(rnd(&seed) % 7);
+    bool duplicate = false, conflict = false;
+    std::vector<int32_t> kind_of(P, 0);
+    for (auto& r : recs) {
+      const size_t n = rnd(&seed) % 9;
+      for (size_t f = 0; f < n; f++) {
+        const size_t k = rnd(&seed) % P;
+        const int32_t kind = rnd(&seed) % 16 == 0 ? 3 : (k < 8 ? 6 : 1);  // now and then another kind than the name's usual one
+        for (const MergeField& g : r) duplicate = duplicate || g.name == pool[k];
+        r.push_back(MergeField{pool[k], kind});
+      }
+    }
+    for (const auto& r : recs)
+      for (const MergeField& f : r)
+        for (size_t k = 0; k < P; k++)
+          if (f.name == pool[k]) { conflict = conflict || (kind_of[k] != 0 && kind_of[k] != f.kind); kind_of[k] = f.kind; }
+    const MergeOrder exprs[] = {{"labels", true}, {"pprof", true}, {"timestamp", false}, {"labels.a", false}, {"missing", true}, {"", false}, {"", true}};
+    std::vector<MergeOrder> order;
+    for (size_t k = 0, n = 1 + rnd(&seed) % 3; k < n; k++) order.push_back(exprs[rnd(&seed) % 7]);
+    MergeSchema u;
+    try {
+      u = unify_merge_schema(recs, order);
+    } catch (const Error& e) {
+      CHECK(e.code == FDB_ERR_INVALID && (duplicate || conflict));
+      refused++;
+      continue;
+    }
+    CHECK(!duplicate && !conflict);
+    accepted++;
+    const size_t C = u.first.size(), S = u.sort_expr.size();
+    CHECK(S <= C && u.map.size() == recs.size());
+    std::vector<std::string> names;
+    for (const MergeSchema::At& at : u.first) {
+      CHECK(at.record >= 0 && (size_t)at.record < recs.size() && at.field >= 0 && (size_t)at.field < recs[(size_t)at.record].size());
+      names.push_back(recs[(size_t)at.record][(size_t)at.field].name);
+    }
+    for (size_t c = 0; c < C; c++) {
+      for (size_t d = 0; d < c; d++) CHECK(names[d] != names[c]);  // a field is emitted once
+      for (int32_t r = 0; r < u.first[c].record; r++)              // … named by its first occurrence
+        for (const MergeField& f : recs[(size_t)r]) CHECK(f.name != names[c]);
+      bool matched = false;  // by an expression up to the column's own (sorting columns), by none at all (the rest)
+      for (size_t e = 0; e < order.size(); e++) matched = matched || merge_order_matches(order[e], names[c]);
+      CHECK(matched == (c < S));
+      if (c < S) {
+        CHECK(u.sort_expr[c] >= 0 && (size_t)u.sort_expr[c] < order.size() && merge_order_matches(order[(size_t)u.sort_expr[c]], names[c]));
+        for (int32_t e = 0; e < u.sort_expr[c]; e++) CHECK(!merge_order_matches(order[(size_t)e], names[c]));  // the first expression that matches takes it
+        if (c > 0) CHECK(u.sort_expr[c - 1] < u.sort_expr[c] || (u.sort_expr[c - 1] == u.sort_expr[c] && names[c - 1] < names[c]));  // expression order, then byte order
+      }
+    }
+    size_t distinct = 0;
+    for (size_t r = 0; r < recs.size(); r++) {
+      CHECK(u.map[r].size() == C);
+      size_t present = 0;
+      for (size_t c = 0; c < C; c++) {
+        const int32_t f = u.map[r][c];
+        CHECK(f >= -1 && f < (int32_t)recs[r].size());
+        if (f >= 0) { CHECK(recs[r][(size_t)f].name == names[c]); present++; }
+        else for (const MergeField& g : recs[r]) CHECK(g.name != names[c]);
+      }
+      CHECK(present == recs[r].size());  // every field of every record has its output column
+      distinct += present;
+    }
+    CHECK(distinct >= C || recs.empty());
+  }
+  CHECK(refused > 50 && accepted > 50);
+}
+
 int main() {
   layouts();
   dictionaries();
+  schemas();
   merge_paths();
   std::puts("asan merge ok");
   return 0;
