@@ -13,6 +13,7 @@
 #include "fdb_mergepath.h"
 #include "fdb_mergerec.h"
 #include "fdb_plan.h"
+#include "fdb_pqwrite_host.h"
 #include "fdb_regex.h"
 #include "fdb_sort.h"
 #include "fdb_sortkey.h"
@@ -696,6 +697,26 @@ int fdb_batch_from_parquet(const fdb_parquet_chunk* chunks, int32_t n_chunks, in
     std::unique_ptr<fdb_batch> b(new fdb_batch());
     b->b = fdb::batch_from_parquet(chunks, n_chunks, n_rows, device);
     *out = b.release();
+  });
+}
+
+int fdb_batch_to_parquet(const fdb_batch* batch, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes);
+  });
+}
+
+void fdb_bytes_free(uint8_t* bytes) { fdb::pqw_free_bytes(bytes); }
+
+int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::HostRecordView view;
+    fdb::view_record(batch, schema, &view);
+    fdb::selftest_parquet_write(view, options, bytes, n_bytes);
   });
 }
 

@@ -1,0 +1,549 @@
+// fdb_pqwrite.cpp — a resident record as one Parquet file (fdb_batch_to_parquet), the encoders running on the device.
+//
+// ≙ Table.writeRecordsToParquet → pqarrow.RecordsToFile → recordToRows (table.go:1436-1459, pqarrow/parquet.go:85-139, :375-400): the
+// reference builds one parquet.Value per cell on the CPU. Here the host decides a layout and writes what is small — page headers, run
+// headers, dictionary pages, the footer (a thrift compact writer of this file's own) — and the device writes every payload:
+//   1. survey (pqw_survey_kernel): per (column, page) the non-NULL rows and, of index columns, the smallest and largest index; per tile
+//      the rank of its first value. Only the per-page table comes back.
+//   2. layout (host): with it every page's size is known, so every payload's final file offset is.
+//   3. encode (pqw_encode_kernel): every payload straight to that offset in ONE image of the file body, holes where the host's bytes go.
+//   4. one device→host copy of the image into the returned buffer; the host fills the holes and appends the footer.
+// fdb_selftest_parquet_write runs the same layout and tail over a host record, the two kernels replaced by a host walk of the same
+// arithmetic (fdb_pqwrite.h) — byte-identical files, no GPU. Compiled with FDB_PQWRITE_HOST_ONLY the device half is left out
+// (tools/asan_parquet_write.sh).
+//
+// File: PAR1 | per column [dictionary page] data pages V1 | FileMetaData | length | PAR1. Flat schema, one row group, UNCOMPRESSED,
+// definition levels RLE (one RLE run when a page has no NULL or only NULLs, else one bit-packed run whose payload is the validity
+// bitmap's bytes), no repetition levels. I64 → INT64 PLAIN; U64 → INT64 PLAIN, Int(64, unsigned) (writeUint64, parquet.go:154-165);
+// F64 → DOUBLE PLAIN; BOOL → BOOLEAN PLAIN; dictionary and plain string / binary columns → BYTE_ARRAY, a PLAIN dictionary page of the
+// interned dictionary's entries in entry order + RLE_DICTIONARY pages: the width byte, then ONE bit-packed run — or one RLE run where all
+// non-NULL indices of the page are equal, as in the leading sorting columns of an ordered record. An all-NULL column with an empty
+// dictionary has no dictionary page and PLAIN pages of zero values.
+#include "fdb_pqwrite_host.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#ifndef FDB_PQWRITE_HOST_ONLY
+#include "fdb_context.h"
+#include "fdb_plan_internal.h"
+#include "fdb_take.h"
+#endif
+
+namespace fdb {
+
+namespace {
+
+// ---- thrift compact protocol, as far as parquet.thrift's structs need it ----------------------------------------------------------------
+struct Thrift {
+  enum { T_TRUE = 1, T_FALSE = 2, T_BYTE = 3, T_I32 = 5, T_I64 = 6, T_BINARY = 8, T_LIST = 9, T_STRUCT = 12 };
+  std::string out;
+  std::vector<int> stack;
+  int last = 0;
+  void varint(uint64_t v) { while (v >= 0x80) { out.push_back((char)(v | 0x80)); v >>= 7; } out.push_back((char)v); }
+  void zigzag(int64_t v) { varint(((uint64_t)v << 1) ^ (uint64_t)(v >> 63)); }
+  void field(int id, int type) {
+    const int delta = id - last;
+    if (delta > 0 && delta <= 15) out.push_back((char)((delta << 4) | type));
+    else { out.push_back((char)type); zigzag(id); }
+    last = id;
+  }
+  void i32(int id, int32_t v) { field(id, T_I32); zigzag(v); }
+  void i64(int id, int64_t v) { field(id, T_I64); zigzag(v); }
+  void boolean(int id, bool v) { field(id, v ? T_TRUE : T_FALSE); }
+  void byte(int id, int8_t v) { field(id, T_BYTE); out.push_back((char)v); }
+  void str(const std::string& s) { varint(s.size()); out += s; }
+  void string(int id, const std::string& s) { field(id, T_BINARY); str(s); }
+  void list(int id, int elem, size_t n) {
+    field(id, T_LIST);
+    if (n < 15) out.push_back((char)((n << 4) | (size_t)elem));
+    else { out.push_back((char)(0xF0 | elem)); varint(n); }
+  }
+  void open() { stack.push_back(last); last = 0; }               // a struct that is a list element (or the top)
+  void open(int id) { field(id, T_STRUCT); open(); }             // … a field
+  void close() { out.push_back(0); last = stack.back(); stack.pop_back(); }
+};
+
+enum { PT_BOOLEAN = 0, PT_INT64 = 2, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6 };
+enum { ENC_PLAIN = 0, ENC_RLE = 3, ENC_RLE_DICTIONARY = 8 };
+enum { PAGE_DATA = 0, PAGE_DICTIONARY = 2 };
+
+std::string page_header(int type, int64_t body, int64_t num_values, int encoding) {
+  Thrift t;
+  t.open();
+  t.i32(1, type);
+  t.i32(2, (int32_t)body);
+  t.i32(3, (int32_t)body);
+  if (type == PAGE_DATA) {
+    t.open(5);
+    t.i32(1, (int32_t)num_values); t.i32(2, encoding); t.i32(3, ENC_RLE); t.i32(4, ENC_RLE);
+    t.close();
+  } else {
+    t.open(7);
+    t.i32(1, (int32_t)num_values); t.i32(2, encoding);
+    t.close();
+  }
+  t.close();
+  return t.out;
+}
+
+std::string varint_bytes(uint64_t v) { Thrift t; t.varint(v); return t.out; }
+std::string le32(uint32_t v) { std::string s(4, '\0'); std::memcpy(&s[0], &v, 4); return s; }
+
+struct ChunkMeta { int64_t dict_off = -1, data_off = 0, bytes = 0, nulls = 0; };
+
+std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMeta>& chunks, int64_t rows, int64_t body_bytes) {
+  Thrift t;
+  t.open();
+  t.i32(1, 1);
+  t.list(2, Thrift::T_STRUCT, cols.size() + 1);
+  t.open(); t.i32(3, 0); t.string(4, "schema"); t.i32(5, (int32_t)cols.size()); t.close();
+  for (const PqwColumn& c : cols) {
+    t.open();
+    t.i32(1, c.physical);
+    t.i32(3, c.optional ? 1 : 0);
+    t.string(4, c.name);
+    if (c.physical == PT_BYTE_ARRAY && c.utf8) { t.i32(6, 0); t.open(10); t.open(1); t.close(); t.close(); }                            // UTF8; LogicalType.STRING
+    if (c.is_u64) { t.i32(6, 14); t.open(10); t.open(10); t.byte(1, 64); t.boolean(2, false); t.close(); t.close(); }                    // UINT_64; LogicalType.INTEGER(64, unsigned)
+    t.close();
+  }
+  t.i64(3, rows);
+  t.list(4, Thrift::T_STRUCT, 1);
+  t.open();  // RowGroup
+  t.list(1, Thrift::T_STRUCT, cols.size());
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    const ChunkMeta& m = chunks[k];
+    t.open();  // ColumnChunk
+    t.i64(2, m.dict_off >= 0 ? m.dict_off : m.data_off);
+    t.open(3);  // ColumnMetaData
+    t.i32(1, c.physical);
+    const bool dict = c.pq_kind == FDB_PQW_INDEX;
+    t.list(2, Thrift::T_I32, 1 + (c.optional ? 1 : 0) + (dict ? 1 : 0));  // (RLE: the definition levels, which a required column does not have)
+    t.zigzag(ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
+    t.list(3, Thrift::T_BINARY, 1); t.str(c.name);
+    t.i32(4, 0);  // UNCOMPRESSED
+    t.i64(5, rows);
+    t.i64(6, m.bytes);
+    t.i64(7, m.bytes);
+    t.i64(9, m.data_off);
+    if (m.dict_off >= 0) t.i64(11, m.dict_off);
+    t.open(12); t.i64(3, m.nulls); t.close();  // Statistics.null_count
+    t.close();
+    t.close();
+  }
+  t.i64(2, body_bytes - 4);
+  t.i64(3, rows);
+  t.i64(5, 4);
+  t.i64(6, body_bytes - 4);
+  t.close();
+  t.string(6, "frostdb_amd 0.1.0");
+  t.close();
+  return t.out;
+}
+
+// The PLAIN dictionary page's body: every entry as a 4-byte length and its bytes, in entry order, duplicates included.
+std::string dictionary_body(const HostDict& d) {
+  std::string s;
+  size_t total = 0;
+  for (const std::string& v : d.values) total += 4 + v.size();
+  s.reserve(total);
+  for (const std::string& v : d.values) { s += le32((uint32_t)v.size()); s += v; }
+  return s;
+}
+
+constexpr uint64_t kBytesMagic = 0x5051574259544553ull;
+struct BytesHeader { uint64_t magic, pinned; unsigned char pad[48]; };
+static_assert(sizeof(BytesHeader) == 64, "the returned bytes stay 64-byte aligned");
+
+}  // namespace
+
+uint8_t* pqw_alloc_bytes(size_t n, bool pinned) {
+  unsigned char* p = nullptr;
+#ifndef FDB_PQWRITE_HOST_ONLY
+  if (pinned) {  // (no pinned memory to be had: the copy goes into pageable memory instead, slower and right)
+    try { p = (unsigned char*)pinned_pool_alloc(n + sizeof(BytesHeader)); } catch (const Error&) { (void)hipGetLastError(); p = nullptr; }
+  }
+#else
+  pinned = false;
+#endif
+  if (p == nullptr) { pinned = false; p = (unsigned char*)std::malloc(n + sizeof(BytesHeader)); }
+  if (p == nullptr) throw std::bad_alloc();
+  BytesHeader h;
+  std::memset(&h, 0, sizeof(h));
+  h.magic = kBytesMagic; h.pinned = pinned ? 1 : 0;
+  std::memcpy(p, &h, sizeof(h));
+  return p + sizeof(BytesHeader);
+}
+
+void pqw_free_bytes(uint8_t* bytes) {
+  if (bytes == nullptr) return;
+  unsigned char* p = bytes - sizeof(BytesHeader);
+  BytesHeader h;
+  std::memcpy(&h, p, sizeof(h));
+  if (h.magic != kBytesMagic) return;  // (not ours: leave it alone rather than free a stranger's pointer)
+  std::memset(p, 0, 8);
+#ifndef FDB_PQWRITE_HOST_ONLY
+  if (h.pinned) { pinned_pool_free(p); return; }
+#endif
+  std::free(p);
+}
+
+// Everything that can refuse the record, before anything is launched.
+std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows) {
+  int64_t pr = opt != nullptr ? opt->page_rows : 0;
+  if (pr == 0) pr = 65536;
+  if (pr < 64 || pr > (1 << 24) || pr % 64 != 0)
+    throw Error(FDB_ERR_INVALID, "parquet write: page_rows must be a multiple of 64 in [64, 2^24] (0: 65536), got " + std::to_string(pr));
+  *page_rows = (int32_t)pr;
+  if (rows < 0) throw Error(FDB_ERR_INVALID, "parquet write: negative row count");
+  const int32_t n_opt = opt != nullptr ? opt->n_optional : 0;
+  if (n_opt != 0 && (n_opt != (int32_t)in.size() || opt->optional == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: `optional` has " + std::to_string(n_opt) + " entries, the record " + std::to_string(in.size()) + " columns");
+  std::vector<PqwColumn> cols;
+  for (size_t k = 0; k < in.size(); k++) {
+    const PqwInput& c = in[k];
+    PqwColumn o;
+    o.name = c.name;
+    switch (c.kind) {
+      case ColKind::I64: o.pq_kind = FDB_PQW_V64; o.physical = PT_INT64; break;
+      case ColKind::U64: o.pq_kind = FDB_PQW_V64; o.physical = PT_INT64; o.is_u64 = true; break;
+      case ColKind::F64: o.pq_kind = FDB_PQW_V64; o.physical = PT_DOUBLE; break;
+      case ColKind::BOOL: o.pq_kind = FDB_PQW_BOOL; o.physical = PT_BOOLEAN; o.width = 1; break;
+      case ColKind::DICT: o.pq_kind = FDB_PQW_INDEX; o.physical = PT_BYTE_ARRAY; break;
+      default: throw Error(FDB_ERR_UNSUPPORTED, "parquet write: column type " + c.format + " (" + c.name + ") is not one the writer knows");
+    }
+    if (c.values == nullptr && rows > 0)
+      throw Error(FDB_ERR_UNSUPPORTED, "parquet write: column type " + c.format + " (" + c.name + ") is not held on the device");
+    if (c.kind == ColKind::DICT) {
+      if (!c.dict) throw Error(FDB_ERR_INVALID, "parquet write: dictionary column without its dictionary: " + c.name);
+      const uint64_t entries = c.dict->values.size();
+      if (entries >= (1ull << 32)) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the dictionary of " + c.name + " has 2^32 entries or more");
+      uint64_t page = 0;
+      for (const std::string& v : c.dict->values) {
+        if (v.size() > 0x7FFFFFFFull) { page = 1ull << 32; break; }
+        page += 4 + v.size();
+      }
+      if (page > 0x7FFFFFFFull) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the dictionary page of " + c.name + " would pass 2^31 - 1 bytes");
+      o.dict = c.dict.get();
+      o.entries = entries;
+      o.utf8 = c.dict->utf8();
+      o.width = entries > 0 ? fdb_pqw_bits(entries - 1) : 0;
+      if (entries == 0) o.pq_kind = PQW_NO_VALUES;  // every row is NULL (checked by the survey): PLAIN pages of zero values
+    }
+    const bool nulls = c.null_count > 0;
+    const int want = n_opt != 0 ? (int)opt->optional[k] : -1;
+    if (want < -1 || want > 1) throw Error(FDB_ERR_INVALID, "parquet write: optional[" + std::to_string(k) + "] is " + std::to_string(want) + " (-1 auto, 0 required, 1 optional)");
+    if (want == 0 && nulls) throw Error(FDB_ERR_INVALID, "parquet write: column " + c.name + " is asked to be required and holds " + std::to_string(c.null_count) + " NULLs");
+    if (nulls && c.validity == nullptr) throw Error(FDB_ERR_INVALID, "parquet write: column " + c.name + " counts NULLs and has no validity bitmap");
+    o.optional = want < 0 ? (nulls || c.kind == ColKind::DICT) : want == 1;
+    o.values = c.values;
+    o.validity = nulls ? c.validity : nullptr;
+    cols.push_back(std::move(o));
+  }
+  return cols;
+}
+
+FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols) {
+  FdbPqwGeom g;
+  g.rows = rows; g.page_rows = page_rows; g.n_pages = fdb_pqw_pages(rows, page_rows); g.tiles_per_page = fdb_pqw_tiles_per_page(page_rows);
+  g.n_cols = (int32_t)n_cols; g.pad = 0;
+  return g;
+}
+
+void PqwLayout::put(uint64_t off, const std::string& s) {
+  if (s.empty()) return;
+  pieces.push_back(Piece{off, blob.size(), s.size()});
+  blob += s;
+}
+
+PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats) {
+  if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
+  PqwLayout L;
+  L.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
+  uint64_t cur = 0;
+  L.put(cur, "PAR1");
+  cur += 4;
+  std::vector<ChunkMeta> chunks(cols.size());
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    ChunkMeta& m = chunks[k];
+    const uint64_t chunk_start = cur;
+    if (c.pq_kind == FDB_PQW_INDEX) {
+      const std::string body = dictionary_body(*c.dict);
+      const std::string hdr = page_header(PAGE_DICTIONARY, (int64_t)body.size(), (int64_t)c.entries, ENC_PLAIN);
+      m.dict_off = (int64_t)cur;
+      L.put(cur, hdr); cur += hdr.size();
+      L.put(cur, body); cur += body.size();
+    }
+    m.data_off = (int64_t)cur;
+    int64_t valid = 0;
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const FdbPqwPageStat& s = stats[k * (size_t)g.n_pages + (size_t)p];
+      const uint32_t n = (uint32_t)(fdb_pqw_page_end(g, p) - fdb_pqw_page_first(g, p)), cnt = s.count;
+      if (cnt > n || (c.validity == nullptr && cnt != n)) throw Error(FDB_ERR_STATE, "parquet write: the survey counts " + std::to_string(cnt) + " values in a page of " + std::to_string(n) + " rows (" + c.name + ")");
+      if (c.pq_kind == PQW_NO_VALUES && cnt != 0) throw Error(FDB_ERR_INVALID, "parquet write: column " + c.name + " has values and an empty dictionary");
+      valid += cnt;
+      std::string pre, vpre;
+      uint64_t level_payload = 0, value_payload = 0;
+      if (c.optional) {
+        if (cnt == n || cnt == 0) {
+          const std::string run = varint_bytes((uint64_t)n << 1) + std::string(1, cnt == n ? '\1' : '\0');
+          pre = le32((uint32_t)run.size()) + run;
+        } else {
+          level_payload = fdb_pqw_level_bytes(n);
+          const std::string run = varint_bytes(((uint64_t)fdb_pqw_level_bytes(n) << 1) | 1);
+          pre = le32((uint32_t)(run.size() + level_payload)) + run;
+        }
+      }
+      int encoding = ENC_PLAIN;
+      if (c.pq_kind == FDB_PQW_V64) value_payload = (uint64_t)cnt * 8;
+      else if (c.pq_kind == FDB_PQW_BOOL) value_payload = fdb_pqw_packed_bytes(cnt, 1);
+      else if (c.pq_kind == FDB_PQW_INDEX) {
+        encoding = ENC_RLE_DICTIONARY;
+        vpre = std::string(1, (char)c.width);
+        if (cnt > 0) {
+          if (s.mn > s.mx || s.mx >= c.entries)
+            throw Error(FDB_ERR_INVALID, "parquet write: dictionary index out of range in column " + c.name + ": a valid row holds " + std::to_string(s.mx) + ", the dictionary has " + std::to_string(c.entries) + " entries");
+          if (s.mn == s.mx) {  // one RLE run: the count, the value in ⌈w/8⌉ bytes
+            vpre += varint_bytes((uint64_t)cnt << 1);
+            for (uint32_t b = 0; b < (c.width + 7) / 8; b++) vpre.push_back((char)(s.mn >> (8 * b)));
+          } else {
+            vpre += varint_bytes(((uint64_t)fdb_pqw_groups(cnt) << 1) | 1);
+            value_payload = fdb_pqw_packed_bytes(cnt, c.width);
+          }
+        }
+      }
+      const uint64_t body = pre.size() + level_payload + vpre.size() + value_payload;
+      const std::string hdr = page_header(PAGE_DATA, (int64_t)body, n, encoding);
+      FdbPqwPageOut& o = L.out[k * (size_t)g.n_pages + (size_t)p];
+      L.put(cur, hdr + pre); cur += hdr.size() + pre.size();
+      if (level_payload > 0) { o.levels_off = cur; cur += level_payload; }
+      L.put(cur, vpre); cur += vpre.size();
+      if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
+    }
+    m.bytes = (int64_t)(cur - chunk_start);
+    m.nulls = g.rows - valid;
+  }
+  L.body_bytes = cur;
+  L.footer = footer(cols, chunks, g.rows, (int64_t)cur);
+  return L;
+}
+
+void pqw_finish(const PqwLayout& L, uint8_t* file) {
+  for (const PqwLayout::Piece& p : L.pieces) std::memcpy(file + p.off, L.blob.data() + p.pos, p.len);
+  std::memcpy(file + L.body_bytes, L.footer.data(), L.footer.size());
+  const uint32_t len = (uint32_t)L.footer.size();
+  std::memcpy(file + L.body_bytes + L.footer.size(), &len, 4);
+  std::memcpy(file + L.body_bytes + L.footer.size() + 4, "PAR1", 4);
+}
+
+// ---- the host walk: what the two kernels do, tile by tile, over host arrays ---------------------------------------------------------------
+void pqw_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, std::vector<FdbPqwPageStat>* stats, std::vector<uint32_t>* tile_base) {
+  stats->assign(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0});
+  tile_base->assign(stats->size() * (size_t)g.tiles_per_page, 0);
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const size_t item = k * (size_t)g.n_pages + (size_t)p;
+      uint32_t run = 0, mn = 0xFFFFFFFFu, mx = 0;
+      for (int32_t t = 0; t < g.tiles_per_page; t++) {
+        (*tile_base)[item * (size_t)g.tiles_per_page + (size_t)t] = run;
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        if (first >= end) continue;
+        for (int wi = 0; wi < FDB_PQW_TILE_WORDS; wi++) {
+          const uint64_t w = fdb_pqw_valid_word(c.validity, first, wi, end);
+          run += (uint32_t)fdb_pqw_popc(w);
+          if (c.pq_kind != FDB_PQW_INDEX && c.pq_kind != PQW_NO_VALUES) continue;
+          for (int b = 0; b < 64; b++)
+            if ((w >> b) & 1) { const uint32_t v = ((const uint32_t*)c.values)[first + wi * 64 + b]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
+        }
+      }
+      (*stats)[item] = FdbPqwPageStat{run, mn, mx, 0};
+    }
+  }
+}
+
+void pqw_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageOut>& out, const std::vector<uint32_t>& tile_base,
+                     unsigned char* image) {
+  std::vector<uint32_t> vals(FDB_PQW_STAGE_WORDS, 0);
+  const auto or_word = [&](uint64_t k, uint32_t word) { uint32_t cur; std::memcpy(&cur, image + k * 4, 4); cur |= word; std::memcpy(image + k * 4, &cur, 4); };
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const size_t cp = k * (size_t)g.n_pages + (size_t)p;
+      const FdbPqwPageOut po = out[cp];
+      for (int32_t t = 0; t < g.tiles_per_page; t++) {
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        if (first >= end) continue;
+        if (po.levels_off == FDB_PQW_NONE && po.values_off == FDB_PQW_NONE) continue;
+        const uint32_t n = (uint32_t)(end - first);
+        uint64_t word[FDB_PQW_TILE_WORDS];
+        uint32_t before[FDB_PQW_TILE_WORDS], count = 0;
+        for (int wi = 0; wi < FDB_PQW_TILE_WORDS; wi++) { word[wi] = fdb_pqw_valid_word(c.validity, first, wi, end); before[wi] = count; count += (uint32_t)fdb_pqw_popc(word[wi]); }
+        const uint64_t base = tile_base[cp * (size_t)g.tiles_per_page + (size_t)t];
+        const bool packed = c.pq_kind != FDB_PQW_V64;
+        if (po.levels_off != FDB_PQW_NONE) {
+          const uint64_t at = po.levels_off + (uint64_t)((first - fdb_pqw_page_first(g, p)) >> 3);
+          for (uint32_t i = 0; i < fdb_pqw_level_bytes(n); i++) {
+            const unsigned char byte = (unsigned char)(word[i >> 3] >> (8 * (i & 7)));
+            if (packed) or_word((at + i) >> 2, (uint32_t)byte << (8 * (uint32_t)((at + i) & 3)));
+            else image[at + i] = byte;
+          }
+        }
+        if (po.values_off == FDB_PQW_NONE || count == 0) continue;
+        if (!packed) {
+          for (uint32_t lr = 0; lr < n; lr++) {
+            const uint64_t w = word[lr >> 6];
+            if (!((w >> (lr & 63)) & 1)) continue;
+            const uint64_t rank = base + before[lr >> 6] + (uint32_t)fdb_pqw_popc(w & ((1ull << (lr & 63)) - 1));
+            std::memcpy(image + po.values_off + rank * 8, (const unsigned char*)c.values + (size_t)(first + lr) * 8, 8);
+          }
+        } else if (c.width > 0) {
+          const uint32_t mask = c.width >= 32 ? 0xFFFFFFFFu : ((1u << c.width) - 1);
+          for (uint32_t lr = 0; lr < n; lr++) {
+            const uint64_t w = word[lr >> 6];
+            if (!((w >> (lr & 63)) & 1)) continue;
+            const uint32_t j = before[lr >> 6] + (uint32_t)fdb_pqw_popc(w & ((1ull << (lr & 63)) - 1));
+            uint32_t v;
+            if (c.pq_kind == FDB_PQW_BOOL) { int64_t b; std::memcpy(&b, (const unsigned char*)c.values + (size_t)(first + lr) * 8, 8); v = b >= 2; }
+            else v = ((const uint32_t*)c.values)[first + lr];
+            vals[fdb_pqw_slot(j)] = v & mask;
+          }
+          const uint64_t payload_bit = po.values_off * 8;
+          const uint64_t k0 = fdb_pqw_first_word(payload_bit, base, c.width), k1 = fdb_pqw_last_word(payload_bit, base, count, c.width);
+          for (uint64_t q = k0; q <= k1; q++) {
+            const uint32_t wd = fdb_pqw_assemble_word(vals.data(), base, count, payload_bit, c.width, q);
+            if (q == k0 || q == k1) or_word(q, wd);
+            else std::memcpy(image + q * 4, &wd, 4);
+          }
+        }
+      }
+    }
+  }
+}
+
+void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes) {
+  // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
+  const size_t rows = (size_t)view.rows;
+  std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
+  std::vector<std::vector<int64_t>> keep_i64(view.cols.size());
+  std::vector<std::vector<uint8_t>> keep_bits(view.cols.size());
+  std::vector<PqwInput> in;
+  for (size_t k = 0; k < view.cols.size(); k++) {
+    const HostColView& c = view.cols[k];
+    PqwInput o;
+    o.name = c.name; o.format = c.format; o.kind = c.kind; o.null_count = c.null_count;
+    if (c.kind == ColKind::I64 || c.kind == ColKind::U64 || c.kind == ColKind::F64) {
+      o.values = rows > 0 ? (const unsigned char*)c.values + (size_t)c.offset * 8 : nullptr;
+    } else if (c.kind == ColKind::BOOL) {
+      keep_i64[k].assign(rows + 1, 0);
+      const uint8_t* bits = (const uint8_t*)c.values;
+      for (size_t i = 0; i < rows; i++) keep_i64[k][i] = 1 + ((bits[(c.offset + (int64_t)i) >> 3] >> ((c.offset + (int64_t)i) & 7)) & 1);
+      o.values = keep_i64[k].data();
+    } else if (c.kind == ColKind::DICT) {
+      o.dict = read_dictionary(c);
+      keep_idx[k].assign(rows + 1, 0);
+      for (size_t i = 0; i < rows; i++) {
+        const size_t at = (size_t)c.offset + i;
+        switch (c.index_width) {
+          case 1: keep_idx[k][i] = ((const uint8_t*)c.values)[at]; break;
+          case 2: keep_idx[k][i] = ((const uint16_t*)c.values)[at]; break;
+          case 4: keep_idx[k][i] = ((const uint32_t*)c.values)[at]; break;
+          default: keep_idx[k][i] = (uint32_t)((const uint64_t*)c.values)[at]; break;
+        }
+      }
+      o.values = keep_idx[k].data();
+    } else if (c.kind == ColKind::STR) {
+      o.dict = encode_plain(c, &keep_idx[k]);
+      keep_idx[k].resize(rows + 1, 0);
+      o.kind = ColKind::DICT;
+      o.values = keep_idx[k].data();
+    }
+    if (c.null_count > 0 && c.validity != nullptr) {
+      keep_bits[k].assign((rows + 63) / 64 * 8 + 8, 0);
+      copy_bits(c.validity, c.offset, c.length, keep_bits[k].data());
+      o.validity = keep_bits[k].data();
+    }
+    in.push_back(std::move(o));
+  }
+  int32_t page_rows = 0;
+  const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows);
+  const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
+  std::vector<FdbPqwPageStat> stats;
+  std::vector<uint32_t> tile_base;
+  pqw_survey_host(cols, g, &stats, &tile_base);
+  const PqwLayout L = pqw_layout(cols, g, stats);
+  const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+  std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
+  pqw_encode_host(cols, g, L.out, tile_base, image.data());
+  uint8_t* file = pqw_alloc_bytes(file_bytes, false);
+  std::memcpy(file, image.data(), (size_t)L.body_bytes);
+  pqw_finish(L, file);
+  *bytes = file;
+  *n_bytes = (int64_t)file_bytes;
+}
+
+#ifndef FDB_PQWRITE_HOST_ONLY
+void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes) {
+  std::vector<PqwInput> in;
+  for (const DevColumn& c : b.cols) {
+    PqwInput o;
+    o.name = c.name; o.format = c.format; o.kind = c.kind; o.dict = c.dict; o.null_count = c.null_count; o.values = c.d_values; o.validity = c.d_validity;
+    in.push_back(std::move(o));
+  }
+  int32_t page_rows = 0;
+  const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows);
+  const FdbPqwGeom g = pqw_geometry(b.rows, page_rows, cols.size());
+  struct Bytes { uint8_t* p = nullptr; ~Bytes() { pqw_free_bytes(p); } } file;
+  if (b.rows == 0 || cols.empty()) {  // nothing for the device to do
+    const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}));
+    const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+    file.p = pqw_alloc_bytes(file_bytes, false);
+    pqw_finish(L, file.p);
+    *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
+    return;
+  }
+  PhaseTimer pt;  // FDB_PROFILE=1: the passes timed apart (the encode pass is then waited for on its own)
+  struct Image { int device; void* p = nullptr; ~Image() { if (p != nullptr) device_pool_free(device, p); } } image{b.device};  // (before the scope: freed after its wait)
+  CallScope cs(b.device);
+  hipStream_t stream = cs.ctx->stream;
+  DrainOnUnwind drain{stream};
+  std::vector<FdbPqwCol> kc(cols.size());
+  for (size_t k = 0; k < cols.size(); k++) {
+    std::memset(&kc[k], 0, sizeof(FdbPqwCol));
+    kc[k].values = cols[k].values; kc[k].validity = cols[k].validity; kc[k].width = (int32_t)cols[k].width;
+    kc[k].kind = cols[k].pq_kind == PQW_NO_VALUES ? FDB_PQW_INDEX : cols[k].pq_kind;
+  }
+  const size_t items = cols.size() * (size_t)g.n_pages;
+  const FdbPqwCol* d_cols = (const FdbPqwCol*)cs.ctx->stage(kc.data(), kc.size() * sizeof(FdbPqwCol));
+  FdbPqwPageStat* d_stats = (FdbPqwPageStat*)cs.alloc(items * sizeof(FdbPqwPageStat));
+  uint32_t* d_tile_base = (uint32_t*)cs.alloc(items * (size_t)g.tiles_per_page * 4);
+  std::vector<FdbPqwPageStat> stats(items);
+  b.note_reader(stream);
+  hip_check(fdb_launch_pqw_survey(d_cols, g, d_stats, d_tile_base, stream), "parquet write: survey launch");
+  hip_check(hipMemcpyAsync(stats.data(), d_stats, items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(page table)");
+  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+  pt.mark("pqwrite survey");
+  const PqwLayout L = pqw_layout(cols, g, stats);
+  const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8, image_bytes = align_up((size_t)L.body_bytes + 8, 256);
+  pt.mark("pqwrite layout");
+  image.p = device_pool_alloc(b.device, image_bytes);
+  FdbPqwPageOut* d_out = (FdbPqwPageOut*)cs.alloc(items * sizeof(FdbPqwPageOut));
+  hip_check(hipMemcpyAsync(d_out, L.out.data(), items * sizeof(FdbPqwPageOut), hipMemcpyHostToDevice, stream), "hipMemcpyAsync(page offsets)");
+  hip_check(hipMemsetAsync(image.p, 0, image_bytes, stream), "hipMemsetAsync(file image)");
+  hip_check(fdb_launch_pqw_encode(d_cols, g, d_out, d_tile_base, (unsigned char*)image.p, stream), "parquet write: encode launch");
+  if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite encode"); }
+  file.p = pqw_alloc_bytes(file_bytes, true);
+  cs.ctx->copy_out_parallel(file.p, image.p, (size_t)L.body_bytes);
+  pt.mark("pqwrite copy");
+  pqw_finish(L, file.p);
+  pt.mark("pqwrite host tail");
+  *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
+}
+#endif
+
+}  // namespace fdb

@@ -166,6 +166,10 @@ def lib() -> ctypes.CDLL:
     L.fdb_merge_bench.argtypes = [P(vp), i32, vp, i32, i32, i32, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double), i32, P(i32), P(i32)]
     L.fdb_batch_column_name.argtypes = [vp, i32]
     L.fdb_batch_column_name.restype = ctypes.c_char_p
+    L.fdb_batch_to_parquet.argtypes = [vp, vp, P(vp), P(i64)]
+    L.fdb_selftest_parquet_write.argtypes = [vp, vp, vp, P(vp), P(i64)]
+    L.fdb_bytes_free.argtypes = [vp]
+    L.fdb_bytes_free.restype = None
     _lib = L
     return L
 
@@ -314,6 +318,48 @@ def selftest_merge_schema(records, order_by):
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
     columns = [flat[out_fields[i]][:2] for i in range(n_out.value)]
     return columns, n_sort.value, [[col_map[r * n_out.value + i] for i in range(n_out.value)] for r in range(len(records))]
+
+
+class ParquetWriteOptions(ctypes.Structure):
+    """fdb_parquet_write_options."""
+    _fields_ = [("page_rows", ctypes.c_int32), ("n_optional", ctypes.c_int32), ("optional", ctypes.c_void_p)]
+
+
+def _parquet_write_options(page_rows, optional, names):
+    """`optional`: None (every column auto), a sequence with one entry per column or a dict by column name; an entry is None / -1
+    (auto), False / 0 (required) or True / 1 (optional). Returns the struct and what it points at."""
+    if optional is None:
+        flags = []
+    elif isinstance(optional, dict):
+        unknown = [n for n in optional if n not in names]
+        if unknown:
+            _raise(FDB_ERR_INVALID, "parquet write: `optional` names no column of the record: %s" % unknown[0])
+        flags = [optional.get(n) for n in names]
+    else:
+        flags = list(optional)
+        if not flags and names:  # (an empty array would read as "every column auto" on the C side)
+            _raise(FDB_ERR_INVALID, "parquet write: `optional` has 0 entries, the record %d columns" % len(names))
+    arr = (ctypes.c_int8 * max(1, len(flags)))(*[-1 if f is None else int(f) for f in flags])
+    return ParquetWriteOptions(int(page_rows), len(flags), ctypes.cast(arr, ctypes.c_void_p) if flags else None), arr
+
+
+def _take_bytes(rc, out, n) -> bytes:
+    if rc != 0:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    try:
+        return ctypes.string_at(out.value, n.value)
+    finally:
+        lib().fdb_bytes_free(out.value)
+
+
+def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None) -> bytes:
+    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional)`` writes, byte for byte, made without a device
+    (fdb_selftest_parquet_write): the same layout, headers and footer, the two kernels replaced by a host walk of the code they compile."""
+    opts, _keep = _parquet_write_options(page_rows, optional, list(record.schema.names))
+    out, n = ctypes.c_void_p(), ctypes.c_int64()
+    with ExportedBatch(record) as ex:
+        rc = lib().fdb_selftest_parquet_write(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+    return _take_bytes(rc, out, n)
 
 
 def live_allocations() -> dict:
@@ -638,6 +684,16 @@ class ResidentBatch:
         if rc != 0:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
+
+    def to_parquet(self, page_rows: int = 0, optional=None) -> bytes:
+        """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, UNCOMPRESSED, data
+        pages V1 of `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
+        sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
+        False (required; refused for a column with NULLs) or True."""
+        opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
+        out, n = ctypes.c_void_p(), ctypes.c_int64()
+        rc = lib().fdb_batch_to_parquet(self.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+        return _take_bytes(rc, out, n)
 
     @property
     def num_rows(self) -> int:

@@ -517,6 +517,50 @@ typedef struct fdb_parquet_row_group {
   int64_t n_rows;                   /* RowGroup.num_rows */
 } fdb_parquet_row_group;
 FDB_API int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_groups, int device, fdb_batch** out);
+
+/* ---- a resident batch written as a Parquet row group, encoded on the device --------------------------------------------------
+ * ≙ Table.writeRecordsToParquet → pqarrow.RecordsToFile → recordToRows (table.go:1436-1459, pqarrow/parquet.go:85-139, :375-400), the
+ * step that ends compaction, block rotation and snapshots: instead of one parquet.Value per cell built on the CPU (after an export of
+ * the record at 8 bytes per row and 4 per index), the record stays in HBM and the device writes every payload of the file — definition
+ * levels, values compacted past their NULLs, BOOLEAN bits, dictionary indices bit-packed at the dictionary's width — straight to its
+ * final file offset in one image; the host reads back one small table per page to size the file, copies the image out once, and writes
+ * page headers, dictionary pages and the footer. `batch` may come from anywhere: fdb_batch_import, fdb_batch(es)_from_parquet,
+ * fdb_plan_filter_batch(es), fdb_plan_project_batch, fdb_batch_take / _limit / _sort, fdb_batches_merge(_named), fdb_plan_finish_batch.
+ *
+ * The file: PAR1, ONE row group, FileMetaData, PAR1 — a flat schema, the batch's columns in their order under their names,
+ * UNCOMPRESSED, data pages V1 of `page_rows` rows, definition levels RLE-encoded (one RLE run where a page has no NULL or only NULLs,
+ * else one bit-packed run), no repetition levels. int64 → INT64 PLAIN; uint64 → INT64 PLAIN with the logical type Int(64, unsigned),
+ * the bits as they are (writeUint64, parquet.go:154-165); float64 → DOUBLE PLAIN, every bit kept; bool → BOOLEAN PLAIN; dictionary
+ * columns and plain string / binary columns → BYTE_ARRAY (String where the values are utf8) with one PLAIN dictionary page — the
+ * column's dictionary entry by entry, duplicates included — and RLE_DICTIONARY data pages at width bits(entries − 1): one bit-packed
+ * run per page, or one RLE run where all of a page's non-NULL indices are equal. A column that is all NULL over an empty dictionary has
+ * no dictionary page and PLAIN pages of zero values. The footer carries what a reader needs (types, encodings, sizes, page offsets)
+ * and Statistics.null_count per column; min / max statistics and sorting_columns are not written. A zero-row batch gives a valid file
+ * whose row group has zero rows. The record's own columns are the schema: a field the record lacks is not written as all-NULL, as the
+ * reference does for a schema it is handed (writeNull).
+ *
+ * Everything that can refuse the call does so before anything is launched: FDB_ERR_INVALID — page_rows not a multiple of 64 in
+ * [64, 2^24] (0 = the default, 65 536), an `optional` array of another length than the batch has columns or with an entry outside
+ * −1 … 1, "required" asked of a column that holds NULLs; FDB_ERR_UNSUPPORTED — a column type the resident record does not hold, a
+ * dictionary of 2^32 entries or more, a dictionary page past 2^31 − 1 bytes (a data page cannot pass it: 2^24 rows of 8 bytes).
+ * Two exceptions, which only the record's rows can show: a non-NULL row whose dictionary index lies past its dictionary, and a non-NULL
+ * row over an EMPTY dictionary. Both are found by the survey pass and answered FDB_ERR_INVALID after it, before the encode pass: nothing
+ * has been written by then.
+ *
+ * *bytes is host memory of the library holding *n_bytes bytes: give it back with fdb_bytes_free (NULL is a no-op). */
+typedef struct fdb_parquet_write_options {
+  int32_t page_rows;       /* rows per data page: a multiple of 64 in [64, 2^24]; 0 = 65 536 */
+  int32_t n_optional;      /* entries of `optional`: 0 (every column auto) or the batch's column count */
+  const int8_t* optional;  /* per column: −1 auto — optional iff the column holds NULLs or is a dictionary / plain string column (dynamic
+                              label columns are optional in every FrostDB schema) —, 0 required, 1 optional */
+} fdb_parquet_write_options;
+FDB_API int fdb_batch_to_parquet(const fdb_batch* batch, const fdb_parquet_write_options* options /* NULL: defaults */, uint8_t** bytes, int64_t* n_bytes);
+FDB_API void fdb_bytes_free(uint8_t* bytes);
+/* The same writer over a HOST record, the two kernels replaced by a host walk of the code they compile (fdb_pqwrite.h: page geometry,
+ * bit positions, word assembly): byte for byte the file fdb_batch_to_parquet writes for the record, and no GPU is touched — what makes
+ * the file format checkable on a CPU-only machine, as fdb_selftest_merge_path does for the merge kernels. */
+FDB_API int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes);
+
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry
  * point takes HOST buffers, for tests and measurement: `src` holds the compressed pages (pages[i] = {src_off, dst_off, src_len,

@@ -1,0 +1,178 @@
+// Stand-alone driver of the host half of the Parquet writer for tools/asan_parquet_write.sh: column checks and options (pqw_columns),
+// the survey and encode walk over host arrays (pqw_survey_host / pqw_encode_host: the arithmetic of fdb_pqwrite.h that the kernels
+// compile), layout planning with the thrift writer and the dictionary page builder (pqw_layout) and the tail (pqw_finish) — over seeded
+// random records and options, every buffer sized exactly. What the walk wrote is read back with a bit reader of this file's own. No
+// GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fdb_pqwrite_host.h"
+
+using namespace fdb;
+
+#define CHECK(cond) do { if (!(cond)) { std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); std::exit(1); } } while (0)
+
+static uint64_t rnd(uint64_t* s) {
+  uint64_t z = (*s += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+struct Column {
+  ColKind kind;
+  std::vector<uint64_t> v64;        // I64 / U64 / F64 / BOOL (1 / 2)
+  std::vector<uint32_t> idx;        // DICT
+  std::vector<uint8_t> bits;        // validity, whole words; empty: no NULLs
+  std::shared_ptr<HostDict> dict;
+  int64_t nulls = 0;
+  bool valid(int64_t r) const { return bits.empty() || ((bits[(size_t)(r >> 3)] >> (r & 7)) & 1); }
+};
+
+static uint32_t read_bits(const uint8_t* p, uint64_t bit, uint32_t w) {
+  uint32_t v = 0;
+  for (uint32_t b = 0; b < w; b++) v |= (uint32_t)((p[(bit + b) >> 3] >> ((bit + b) & 7)) & 1) << b;
+  return v;
+}
+
+static void one_record(uint64_t* seed, int round) {
+  static const int64_t row_choices[] = {0, 1, 7, 63, 64, 65, 127, 128, 129, 1000, 4095, 4096, 4097, 9000};
+  static const int32_t page_choices[] = {0, 64, 128, 4096, 8192, 65536};
+  static const uint32_t entry_choices[] = {0, 1, 2, 3, 5, 255, 256, 257, 65537};
+  const int64_t rows = row_choices[rnd(seed) % 14];
+  const int32_t page_rows = rows > 4097 ? page_choices[2 + rnd(seed) % 4] : page_choices[rnd(seed) % 6];
+  const size_t n_cols = 1 + rnd(seed) % 5;
+  std::vector<Column> cols(n_cols);
+  std::vector<PqwInput> in;
+  std::vector<int8_t> optional;
+  for (size_t k = 0; k < n_cols; k++) {
+    Column& c = cols[k];
+    static const ColKind kinds[] = {ColKind::I64, ColKind::U64, ColKind::F64, ColKind::BOOL, ColKind::DICT, ColKind::DICT};
+    c.kind = kinds[rnd(seed) % 6];
+    uint32_t entries = entry_choices[rnd(seed) % 9];
+    const int null_mode = (int)(rnd(seed) % 5);  // 0 none, 1 all, 2 random, 3 whole tiles, 4 rare
+    if (c.kind == ColKind::DICT && entries == 0 && rows > 0 && null_mode != 1) entries = 1;
+    if (null_mode != 0 && rows > 0) {
+      c.bits.assign((size_t)(rows + 63) / 64 * 8, 0);
+      for (int64_t r = 0; r < rows; r++) {
+        const bool v = null_mode == 1 ? false : null_mode == 2 ? (rnd(seed) & 1) != 0 : null_mode == 3 ? ((r / 64) % 3 != 1) : rnd(seed) % 97 != 0;
+        if (v) c.bits[(size_t)(r >> 3)] |= (uint8_t)(1u << (r & 7)); else c.nulls++;
+      }
+      for (int64_t r = rows; r < (rows + 63) / 64 * 64; r++) if (rnd(seed) & 1) c.bits[(size_t)(r >> 3)] |= (uint8_t)(1u << (r & 7));  // bits past the end are undefined
+      if (c.nulls == 0) c.bits.clear();
+    }
+    PqwInput o;
+    o.name = "c" + std::to_string(k); o.kind = c.kind; o.null_count = c.nulls;
+    if (c.kind == ColKind::DICT) {
+      std::vector<std::string> values;
+      for (uint32_t e = 0; e < entries; e++) values.push_back(e % 7 == 3 ? std::string() : "v" + std::to_string(e % 1000));
+      c.dict = (rnd(seed) & 1) ? make_dictionary(std::move(values), (rnd(seed) & 1) ? "u" : "z") : make_plain_dictionary(std::move(values), "u");
+      const bool constant = rnd(seed) % 3 == 0;
+      c.idx.resize((size_t)rows);
+      for (int64_t r = 0; r < rows; r++) c.idx[(size_t)r] = entries == 0 ? 0 : constant ? (uint32_t)((r / 64) % entries) : (uint32_t)(rnd(seed) % entries);
+      if (!constant && rows > 0 && entries > 0) c.idx[(size_t)rows - 1] = entries - 1;
+      for (int64_t r = 0; r < rows; r++) if (!c.valid(r)) c.idx[(size_t)r] = 0xFFFFFFFFu;  // a NULL row's index must never be looked at
+      o.dict = c.dict;
+      o.values = rows > 0 ? c.idx.data() : nullptr;
+    } else {
+      c.v64.resize((size_t)rows);
+      for (int64_t r = 0; r < rows; r++) c.v64[(size_t)r] = c.kind == ColKind::BOOL ? 1 + (rnd(seed) & 1) : rnd(seed);
+      o.values = rows > 0 ? c.v64.data() : nullptr;
+    }
+    o.validity = c.bits.empty() ? nullptr : c.bits.data();
+    in.push_back(std::move(o));
+    optional.push_back(c.nulls > 0 ? (int8_t)((rnd(seed) & 1) ? 1 : -1) : (int8_t)((int)(rnd(seed) % 3) - 1));
+  }
+  fdb_parquet_write_options opt;
+  opt.page_rows = page_rows;
+  const bool with_optional = (round & 1) != 0;
+  opt.n_optional = with_optional ? (int32_t)n_cols : 0;
+  opt.optional = with_optional ? optional.data() : nullptr;
+
+  int32_t pr = 0;
+  const std::vector<PqwColumn> pc = pqw_columns(in, rows, &opt, &pr);
+  CHECK(pr == (page_rows == 0 ? 65536 : page_rows) && pc.size() == n_cols);
+  const FdbPqwGeom g = pqw_geometry(rows, pr, n_cols);
+  std::vector<FdbPqwPageStat> stats;
+  std::vector<uint32_t> tile_base;
+  pqw_survey_host(pc, g, &stats, &tile_base);
+  const PqwLayout L = pqw_layout(pc, g, stats);
+  std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
+  pqw_encode_host(pc, g, L.out, tile_base, image.data());
+  const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+  uint8_t* file = pqw_alloc_bytes(file_bytes, false);
+  std::memcpy(file, image.data(), (size_t)L.body_bytes);
+  for (size_t b = (size_t)L.body_bytes; b < image.size(); b++) CHECK(image[b] == 0);  // nothing is written past the body
+  pqw_finish(L, file);
+  CHECK(std::memcmp(file, "PAR1", 4) == 0 && std::memcmp(file + file_bytes - 4, "PAR1", 4) == 0);
+  uint32_t flen;
+  std::memcpy(&flen, file + file_bytes - 8, 4);
+  CHECK(flen == L.footer.size());
+  // the host's pieces do not overlap the payloads, the payloads hold what the record holds
+  std::vector<uint8_t> owner(L.body_bytes, 0);
+  for (const PqwLayout::Piece& p : L.pieces) for (size_t b = 0; b < p.len; b++) { CHECK(p.off + b < L.body_bytes && owner[p.off + b] == 0); owner[p.off + b] = 1; }
+  for (size_t k = 0; k < n_cols; k++) {
+    const Column& c = cols[k];
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const FdbPqwPageOut po = L.out[k * (size_t)g.n_pages + (size_t)p];
+      const FdbPqwPageStat st = stats[k * (size_t)g.n_pages + (size_t)p];
+      const int64_t first = fdb_pqw_page_first(g, p), end = fdb_pqw_page_end(g, p);
+      uint32_t cnt = 0;
+      for (int64_t r = first; r < end; r++) cnt += pc[k].validity == nullptr || c.valid(r);
+      CHECK(cnt == st.count);
+      if (po.levels_off != FDB_PQW_NONE) {
+        for (uint32_t b = 0; b < fdb_pqw_level_bytes((uint32_t)(end - first)); b++) { CHECK(owner[po.levels_off + b] == 0); owner[po.levels_off + b] = 2; }
+        for (int64_t r = first; r < first + (int64_t)fdb_pqw_level_bytes((uint32_t)(end - first)) * 8; r++)
+          CHECK(read_bits(file + po.levels_off, (uint64_t)(r - first), 1) == (r < end && c.valid(r) ? 1u : 0u));
+      }
+      if (po.values_off == FDB_PQW_NONE) continue;
+      const uint32_t w = pc[k].pq_kind == FDB_PQW_V64 ? 64 : pc[k].width;
+      const uint64_t bytes = pc[k].pq_kind == FDB_PQW_V64 ? (uint64_t)cnt * 8 : fdb_pqw_packed_bytes(cnt, w);
+      for (uint64_t b = 0; b < bytes; b++) { CHECK(owner[po.values_off + b] == 0); owner[po.values_off + b] = 3; }
+      uint64_t j = 0;
+      for (int64_t r = first; r < end; r++) {
+        if (!(pc[k].validity == nullptr || c.valid(r))) continue;
+        if (pc[k].pq_kind == FDB_PQW_V64) { uint64_t v; std::memcpy(&v, file + po.values_off + j * 8, 8); CHECK(v == c.v64[(size_t)r]); }
+        else if (pc[k].pq_kind == FDB_PQW_BOOL) CHECK(read_bits(file + po.values_off, j, 1) == (c.v64[(size_t)r] >= 2 ? 1u : 0u));
+        else CHECK(read_bits(file + po.values_off, j * w, w) == c.idx[(size_t)r]);
+        j++;
+      }
+      for (uint64_t bit = j * (w == 64 ? 64 : w); bit < bytes * 8; bit++) CHECK(read_bits(file + po.values_off, bit, 1) == 0);  // padding bits zero
+    }
+  }
+  for (uint64_t b = 0; b < L.body_bytes; b++) CHECK(owner[b] != 0);  // every byte of the body belongs to somebody
+  pqw_free_bytes(file);
+}
+
+static void refusals() {
+  std::vector<PqwInput> in(1);
+  std::vector<uint64_t> v(8, 0);
+  std::vector<uint8_t> bits(8, 0x0F);
+  in[0].name = "x"; in[0].kind = ColKind::I64; in[0].values = v.data(); in[0].validity = bits.data(); in[0].null_count = 4;
+  int32_t pr = 0;
+  const auto code = [&](const fdb_parquet_write_options& o) { try { pqw_columns(in, 8, &o, &pr); } catch (const Error& e) { return e.code; } return (int)FDB_OK; };
+  const int8_t required = 0, bad = 3;
+  CHECK(code(fdb_parquet_write_options{0, 0, nullptr}) == FDB_OK && pr == 65536);
+  CHECK(code(fdb_parquet_write_options{100, 0, nullptr}) == FDB_ERR_INVALID);
+  CHECK(code(fdb_parquet_write_options{32, 0, nullptr}) == FDB_ERR_INVALID);
+  CHECK(code(fdb_parquet_write_options{(1 << 24) + 64, 0, nullptr}) == FDB_ERR_INVALID);
+  CHECK(code(fdb_parquet_write_options{64, 2, &required}) == FDB_ERR_INVALID);
+  CHECK(code(fdb_parquet_write_options{64, 1, &required}) == FDB_ERR_INVALID);
+  CHECK(code(fdb_parquet_write_options{64, 1, &bad}) == FDB_ERR_INVALID);
+  in[0].kind = ColKind::OTHER;
+  CHECK(code(fdb_parquet_write_options{64, 0, nullptr}) == FDB_ERR_UNSUPPORTED);
+  in[0].kind = ColKind::DICT;
+  CHECK(code(fdb_parquet_write_options{64, 0, nullptr}) == FDB_ERR_INVALID);  // no dictionary
+  pqw_free_bytes(nullptr);
+}
+
+int main() {
+  uint64_t seed = 11;
+  for (int round = 0; round < 400; round++) one_record(&seed, round);
+  refusals();
+  std::printf("asan parquet write ok\n");
+  return 0;
+}

@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""A resident record written as a Parquet row group on the device (ResidentBatch.to_parquet) against what a caller has to do without it (MI355X).
+
+The record has the shape of bench.py's config 2 at --rows rows (default 20 M): an int64 timestamp, a float64 value with 5 % NULLs and five
+label columns — dictionaries of 10, 50, 100, 500 and 1 000 entries, 10 % NULLs each, the first one ordered as the leading sorting column
+of a compacted part is. In ONE process, medians of --reps passes after --warmup:
+  to_parquet_ms     fdb_batch_to_parquet + fdb_bytes_free: the C call, the file in the library's (pinned) buffer
+  python_ms         ResidentBatch.to_parquet(): the same + the copy into a Python bytes object
+  survey_ms … host_tail_ms   its passes timed apart: FDB_PROFILE=1 passes of their own (the encode pass is then waited for by itself),
+                    read from the library's stderr lines; copy_ms is the one device→host copy of the file image
+  floor_ms          a bare device→host copy of as many bytes as the file has, into pinned memory: what the link allows
+  arrow_write_ms    to_arrow() followed by pyarrow.parquet.write_table with matching options (one row group, UNCOMPRESSED, data pages
+                    V1, dictionary encoding for the label columns only, no statistics): what a caller does at the parent commit;
+                    export_ms is its to_arrow() part (--baseline-reps passes, default 3)
+One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
+
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--out FILE]
+"""
+import argparse
+import io
+import json
+import os
+import re
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402,F401  (first: one ROCm stack per process, see tests/conftest.py)
+import numpy as np  # noqa: E402
+import pyarrow as pa  # noqa: E402
+import pyarrow.parquet as pq  # noqa: E402
+
+from frostdb_amd import physicalplan as pp  # noqa: E402
+
+LABELS = [10, 50, 100, 500, 1000]
+PHASES = ["survey", "layout", "encode", "copy", "host tail"]
+
+
+def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
+    rng = np.random.default_rng(seed)
+    cols = [pa.array(np.cumsum(rng.integers(0, 2000, rows, dtype=np.int64))), pa.array(rng.standard_normal(rows), mask=rng.random(rows) < 0.05)]
+    names = ["timestamp", "value"]
+    for k, entries in enumerate(LABELS):
+        idx = rng.integers(0, entries, rows).astype(np.uint32)
+        if k == 0:
+            idx = np.sort(idx)
+        values = pa.array(["label-%d-value-%04d" % (k, e) for e in range(entries)], type=pa.string())
+        cols.append(pa.DictionaryArray.from_arrays(pa.array(idx, mask=rng.random(rows) < 0.10), values))
+        names.append("labels.l%d" % k)
+    return pa.RecordBatch.from_arrays(cols, names=names)
+
+
+def median_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        times.append((time.perf_counter() - t) * 1e3)
+    return statistics.median(times), times
+
+
+def profiled_phases(rb, page_rows, reps):
+    """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
+    os.environ["FDB_PROFILE"] = "1"
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            for _ in range(reps):
+                rb.to_parquet(page_rows=page_rows)
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+            del os.environ["FDB_PROFILE"]
+        tmp.seek(0)
+        text = tmp.read().decode("utf-8", "replace")
+    out = {}
+    for phase in PHASES:
+        us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
+        out[phase] = statistics.median(us) / 1e3 if us else None
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rows", type=int, default=20_000_000)
+    ap.add_argument("--page-rows", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--baseline-reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    record = make_record(args.rows)
+    rb = pp.ResidentBatch(record)
+    del record
+    try:
+        data = rb.to_parquet(page_rows=args.page_rows)
+        file_bytes = len(data)
+        md = pq.ParquetFile(io.BytesIO(data)).metadata
+        assert md.num_rows == args.rows and md.num_row_groups == 1
+        del data
+        import ctypes
+        opts = pp.ParquetWriteOptions(args.page_rows, 0, None)
+
+        def c_call():
+            out, n = ctypes.c_void_p(), ctypes.c_int64()
+            rc = pp.lib().fdb_batch_to_parquet(rb.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+            assert rc == 0 and n.value == file_bytes, pp.lib().fdb_last_error()
+            pp.lib().fdb_bytes_free(out.value)
+        to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps)
+
+        dev = torch.empty(file_bytes, dtype=torch.uint8, device="cuda")
+        host = torch.empty(file_bytes, dtype=torch.uint8).pin_memory()
+
+        def bare_copy():
+            host.copy_(dev, non_blocking=True)
+            torch.cuda.synchronize()
+        floor_ms, _ = median_ms(bare_copy, args.reps, args.warmup)
+        del dev, host
+
+        label_names = ["labels.l%d" % k for k in range(len(LABELS))]
+        export_times, baseline_bytes = [], [0]
+
+        def arrow_write():
+            t = time.perf_counter()
+            rec = rb.to_arrow()
+            export_times.append((time.perf_counter() - t) * 1e3)
+            sink = pa.BufferOutputStream()
+            pq.write_table(pa.Table.from_batches([rec]), sink, row_group_size=max(1, rec.num_rows), compression="NONE", use_dictionary=label_names,
+                           data_page_version="1.0", write_statistics=False, data_page_size=1 << 20)
+            baseline_bytes[0] = sink.getvalue().size
+        arrow_write_ms, _ = median_ms(arrow_write, args.baseline_reps, 1)
+    finally:
+        rb.close()
+    r3 = lambda v: None if v is None else round(v, 3)  # noqa: E731
+    line = {"tool": "parquet_write_bench", "rows": args.rows, "page_rows": args.page_rows or 65536, "columns": 2 + len(LABELS), "file_bytes": file_bytes,
+            "to_parquet_ms": r3(to_parquet_ms), "to_parquet_min_ms": r3(min(to_parquet_all)), "python_ms": r3(python_ms), "to_parquet_gbs": round(file_bytes / (to_parquet_ms * 1e-3) / 1e9, 2),
+            "survey_ms": r3(phases["survey"]), "layout_ms": r3(phases["layout"]), "encode_ms": r3(phases["encode"]), "copy_ms": r3(phases["copy"]),
+            "host_tail_ms": r3(phases["host tail"]), "floor_ms": r3(floor_ms), "floor_gbs": round(file_bytes / (floor_ms * 1e-3) / 1e9, 2),
+            "arrow_write_ms": r3(arrow_write_ms), "export_ms": r3(statistics.median(export_times[1:])), "arrow_file_bytes": baseline_bytes[0],
+            "arrow_over_device": round(arrow_write_ms / to_parquet_ms, 2), "reps": args.reps, "warmup": args.warmup, "baseline_reps": args.baseline_reps,
+            "date": time.strftime("%Y-%m-%d")}
+    text = json.dumps(line)
+    print(text, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+    assert pp.live_allocations()["device_blocks"] == 0
+
+
+if __name__ == "__main__":
+    main()
