@@ -26,30 +26,14 @@ struct DevBuf {  // scratch from the context's caching allocator; the plan's str
 };
 
 // The result record of filtering `in`, without rows yet: every column's name, format, kind and dictionary.
-std::unique_ptr<DeviceBatch> filter_output(const DeviceBatch& in, int device) {
-  std::unique_ptr<DeviceBatch> out(new DeviceBatch());
-  out->device = device;
-  for (const DevColumn& c : in.cols) {
-    if (c.d_values == nullptr && in.rows > 0)
-      throw Error(FDB_ERR_UNSUPPORTED, "filter output: column type " + c.format + " (" + c.name + ") is not supported on the device path");
-    DevColumn d;
-    d.name = c.name; d.format = c.format; d.kind = c.kind; d.dict = c.dict;
-    out->cols.push_back(std::move(d));
-  }
-  return out;
+std::unique_ptr<DeviceBatch> filter_output(const DeviceBatch& in) {
+  require_values(in, "filter output");
+  return RecordBuilder::schema_of(in);
 }
 
-// Column `c` of `o`, filtered: `total` rows at `values`, the bitmap at `valid` kept only when some row is NULL. Returns the algorithmic
-// bytes of its compaction: every selected value read once and written once, validity likewise.
-int64_t finish_column(const DevColumn& c, int64_t total, int64_t nulls, void* values, uint8_t* valid, DeviceBatch* o, DevColumn* d) {
-  const int64_t width = c.kind == ColKind::DICT ? 4 : 8;
-  d->length = total;
-  d->null_count = nulls;
-  d->d_values = values;
-  d->value_bytes = c.kind == ColKind::BOOL ? (total + 7) / 8 : total * width;
-  if (valid != nullptr && nulls > 0) { d->d_validity = valid; d->validity_bytes = (total + 7) / 8; }
-  o->payload_bytes += d->value_bytes + d->validity_bytes;
-  return 2 * (total * width) + (c.d_validity != nullptr ? 2 * ((total + 7) / 8) : 0);
+// Algorithmic bytes of compacting column `c` to `total` rows: every selected value read once and written once, validity likewise.
+int64_t compaction_bytes(const DevColumn& c, int64_t total) {
+  return 2 * (total * (int64_t)value_width(c.kind)) + (c.d_validity != nullptr ? 2 * ((total + 7) / 8) : 0);
 }
 }  // namespace
 
@@ -126,63 +110,45 @@ std::unique_ptr<DeviceBatch> Plan::filter_batch(const DeviceBatch& in, int64_t* 
 // filter_batches_impl has checked the plan and the record.
 std::unique_ptr<DeviceBatch> Plan::filter_batch_interp(const DeviceBatch& in, int64_t* n_selected) {
   hip_check(hipSetDevice(device_), "hipSetDevice");
-  std::unique_ptr<DeviceBatch> out;
-  DrainOnUnwind drain{stream_};  // (after `out`: its arena, and `in`, which the caller may release, outlive the queued kernels)
-  out = filter_output(in, device_);
+  DrainOnUnwind drain{stream_};  // (`in`, which the caller may release, outlives the queued kernels)
+  require_values(in, "filter output");
   *n_selected = 0;
-  if (in.rows == 0) return out;
+  if (in.rows == 0) return RecordBuilder::schema_of(in);
   Resolved R;
   resolve_filter_only(in, filter_root_, &R);
   uint8_t* masks = nullptr;
   uint32_t* offs = nullptr;
   const int64_t total = run_flags(R.args, &masks, &offs);  // (one host round trip: the output is allocated at its exact size)
   *n_selected = total;
-  out->rows = total;
   stat_bytes += R.bytes;
   stat_rows += in.rows;
-  if (total == 0) { sync(); return out; }
-  const uint64_t cap = (uint64_t)total;
-  struct Piece { size_t val_off, bit_off; };
-  std::vector<Piece> pieces(in.cols.size());
-  size_t total_bytes = 0;
-  for (size_t k = 0; k < in.cols.size(); k++) {
-    const DevColumn& c = in.cols[k];
-    const size_t w = c.kind == ColKind::DICT ? 4 : 8;
-    pieces[k].val_off = total_bytes;
-    total_bytes += align_up(cap * w + kTailPad, 256);
-    pieces[k].bit_off = total_bytes;
-    if (c.d_validity != nullptr) total_bytes += align_up((cap + 7) / 8 + kTailPad, 256);
-  }
-  out->arena = device_pool_alloc(device_, std::max<size_t>(total_bytes, 256));
-  out->arena_bytes = std::max<size_t>(total_bytes, 256);
+  RecordBuilder out(device_, total);
+  DrainOnUnwind drain_out{stream_};  // (after `out`: its arena outlives the queued kernels)
+  for (const DevColumn& c : in.cols) out.add(c.name, c.format, c.kind, c.dict, c.d_validity != nullptr);
+  if (total == 0) { sync(); return out.finish(nullptr); }
+  out.allocate();
+  const size_t n_cols = in.cols.size();
   unsigned long long* d_nulls = (unsigned long long*)ctx_->dev_alloc(128 * 64 * 8);  // 64 partial counts per column
   scratch_.push_back(d_nulls);
-  hip_check(hipMemsetAsync(d_nulls, 0, in.cols.size() * 64 * 8, stream_), "hipMemsetAsync(null counts)");
-  struct OutCol { void* dst; uint8_t* dst_valid; int width; };
-  std::vector<OutCol> cols(in.cols.size());
+  hip_check(hipMemsetAsync(d_nulls, 0, n_cols * 64 * 8, stream_), "hipMemsetAsync(null counts)");
   timed([&] {
-    for (size_t k = 0; k < in.cols.size(); k++) {  // one streaming pass per column (fdb_launch_compact_col)
+    for (size_t k = 0; k < n_cols; k++) {  // one streaming pass per column (fdb_launch_compact_col)
       const DevColumn& c = in.cols[k];
-      OutCol& C = cols[k];
-      C.dst = (unsigned char*)out->arena + pieces[k].val_off;
-      C.width = c.kind == ColKind::DICT ? 4 : 8;
-      C.dst_valid = nullptr;
-      if (c.d_validity != nullptr) {  // the output bitmap is OR-ed into: zero it first
-        C.dst_valid = (uint8_t*)out->arena + pieces[k].bit_off;
-        hip_check(hipMemsetAsync(C.dst_valid, 0, align_up((cap + 7) / 8 + kTailPad, 256), stream_), "hipMemsetAsync(validity)");
-      }
-      hip_check(fdb_launch_compact_col(C.width, c.d_values, c.d_validity, C.dst, C.dst_valid, masks, offs, in.rows, d_nulls + k * 64, device_, stream_), "compact launch");
+      uint8_t* dst_valid = out.validity(k);
+      if (dst_valid != nullptr) hip_check(hipMemsetAsync(dst_valid, 0, out.bitmap_slot_bytes(), stream_), "hipMemsetAsync(validity)");  // the output bitmap is OR-ed into: zero it first
+      hip_check(fdb_launch_compact_col((int)value_width(c.kind), c.d_values, c.d_validity, out.values(k), dst_valid, masks, offs, in.rows, d_nulls + k * 64, device_, stream_), "compact launch");
     }
   });
   last_kernel_ = "compact_col_kernel";
-  std::vector<unsigned long long> h_parts(cols.size() * 64), h_nulls(cols.size(), 0);
-  hip_check(hipMemcpyAsync(h_parts.data(), d_nulls, cols.size() * 64 * 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(null counts)");
+  std::vector<unsigned long long> h_parts(n_cols * 64), h_nulls(n_cols, 0);
+  hip_check(hipMemcpyAsync(h_parts.data(), d_nulls, n_cols * 64 * 8, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(null counts)");
   hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-  for (size_t k = 0; k < cols.size(); k++) for (int i = 0; i < 64; i++) h_nulls[k] += h_parts[k * 64 + (size_t)i];
-  for (size_t k = 0; k < in.cols.size(); k++)
-    stat_bytes += finish_column(in.cols[k], total, (int64_t)h_nulls[k], cols[k].dst, cols[k].dst_valid, out.get(), &out->cols[k]);
+  for (size_t k = 0; k < n_cols; k++) {
+    for (int i = 0; i < 64; i++) h_nulls[k] += h_parts[k * 64 + (size_t)i];
+    stat_bytes += compaction_bytes(in.cols[k], total);
+  }
   sync();
-  return out;
+  return out.finish(h_nulls.data());
 }
 
 // ≙ PredicateFilter.Callback for every record of a scan at once (filter.go:255-323). Four launches whatever the number of records
@@ -311,7 +277,7 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::filter_batches_impl(const Device
   hip_check(hipSetDevice(device_), "hipSetDevice");
   for (int i : live) in[i]->note_reader(stream_);
   for (int i = 0; i < n; i++) {
-    out.push_back(filter_output(*in[i], device_));
+    out.push_back(filter_output(*in[i]));
     n_selected[i] = 0;
   }
   DrainOnUnwind drain{stream_};  // (declared after `out`: an error waits for the queued kernels before the arenas go back to the pool)
@@ -465,7 +431,7 @@ void Plan::FilterRun::count_rows_one_pass(int64_t grid, size_t first_lds, size_t
     if (fused.empty()) continue;
     size_t bytes = 0;
     std::vector<size_t> off(fused.size());
-    for (size_t f = 0; f < fused.size(); f++) { off[f] = bytes; bytes += align_up((size_t)src(k).rows * (fused[f].wide ? 8 : 4) + kTailPad, 256); }
+    for (size_t f = 0; f < fused.size(); f++) { off[f] = bytes; bytes += values_slot((size_t)src(k).rows, fused[f].wide ? 8 : 4); }
     void* block = device_pool_alloc(P.device_, bytes);
     o.extra_arenas.push_back(block);
     o.arena_bytes += bytes;
@@ -482,7 +448,7 @@ void Plan::FilterRun::count_rows_one_pass(int64_t grid, size_t first_lds, size_t
     for (size_t k = 0; k < nl; k++) {
       DeviceBatch& o = dst(k);
       size_t bytes = 0;
-      for (size_t c = 0; c < n_cols; c++) if (nullable[c]) bytes += align_up((size_t)(src(k).rows + 7) / 8 + kTailPad, 256);
+      for (size_t c = 0; c < n_cols; c++) if (nullable[c]) bytes += bitmap_slot((size_t)src(k).rows);
       void* block = device_pool_alloc(P.device_, std::max<size_t>(bytes, 256));
       pre_bits[k] = block;
       pre_bits_bytes[k] = std::max<size_t>(bytes, 256);
@@ -556,7 +522,7 @@ void Plan::FilterRun::lay_out(int64_t* n_selected) {
     for (size_t c = 0; c < n_cols; c++) if (nullable[c] && src(k).cols[c].d_validity == nullptr) ones_rows = std::max(ones_rows, src(k).rows);
   uint8_t* d_ones = nullptr;
   if (ones_rows > 0) {
-    const size_t ones_bytes = align_up((size_t)(ones_rows + 7) / 8 + kTailPad, 256);
+    const size_t ones_bytes = bitmap_slot((size_t)ones_rows);
     d_ones = (uint8_t*)P.ctx_->dev_alloc(ones_bytes);
     P.scratch_.push_back(d_ones);
     hip_check(hipMemsetAsync(d_ones, 0xFF, ones_bytes, P.stream_), "hipMemsetAsync(all-valid bitmap)");
@@ -584,16 +550,16 @@ void Plan::FilterRun::place_record(size_t k, const uint8_t* d_ones) {
   for (size_t c = 0; c < n_cols; c++) {
     if (fused_of[c] >= 0 && !repack) continue;
     val_off[c] = bytes;
-    bytes += align_up((size_t)total * (s.cols[c].kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
+    bytes += values_slot((size_t)total, value_width(s.cols[c].kind));
   }
   bits_at = bytes;
   uint8_t* const bits_block = (uint8_t*)pre_bits[k];  // (one pass with nullable columns: zeroed by the select launch, worst-case sized)
   if (bits_block != nullptr) {
     size_t at = 0;
-    for (size_t c = 0; c < n_cols; c++) if (nullable[c]) { bit_off[c] = at; at += align_up((size_t)(s.rows + 7) / 8 + kTailPad, 256); }
+    for (size_t c = 0; c < n_cols; c++) if (nullable[c]) { bit_off[c] = at; at += bitmap_slot((size_t)s.rows); }
   } else {
     for (size_t c = 0; c < n_cols; c++)
-      if (nullable[c]) { bit_off[c] = bytes; bytes += align_up(((size_t)total + 7) / 8 + kTailPad, 256); }
+      if (nullable[c]) { bit_off[c] = bytes; bytes += bitmap_slot((size_t)total); }
   }
   if (total > 0 && bytes > 0) {
     o.arena = device_pool_alloc(P.device_, std::max<size_t>(bytes, 256));
@@ -612,7 +578,7 @@ void Plan::FilterRun::place_record(size_t k, const uint8_t* d_ones) {
     for (size_t f = 0; f < fused.size(); f++) {
       const int w = fused[f].wide ? 8 : 4;
       if (repack) hip_check(hipMemcpyAsync((unsigned char*)o.arena + val_off[(size_t)fused[f].col], (unsigned char*)block + worst, (size_t)total * w, hipMemcpyDeviceToDevice, P.stream_), "hipMemcpyAsync(repack)");
-      worst += align_up((size_t)s.rows * w + kTailPad, 256);
+      worst += values_slot((size_t)s.rows, (size_t)w);
     }
     o.arena_bytes -= worst;
     repacked.v.push_back(block);
@@ -622,7 +588,7 @@ void Plan::FilterRun::place_record(size_t k, const uint8_t* d_ones) {
     if (fused_of[c] >= 0 && !repack) {
       // (fused columns sit in the block in `fused` order)
       size_t at = 0;
-      for (int f = 0; f < fused_of[c]; f++) at += align_up((size_t)s.rows * (fused[(size_t)f].wide ? 8 : 4) + kTailPad, 256);
+      for (int f = 0; f < fused_of[c]; f++) at += values_slot((size_t)s.rows, fused[(size_t)f].wide ? 8 : 4);
       Q.values = total > 0 ? (unsigned char*)o.extra_arenas.back() + at : nullptr;
     } else {
       Q.values = total > 0 ? (unsigned char*)o.arena + val_off[c] : nullptr;
@@ -633,7 +599,7 @@ void Plan::FilterRun::place_record(size_t k, const uint8_t* d_ones) {
     const size_t c = (size_t)rest[r];
     FdbCompactCol& C = cols[k * rest.size() + r];
     C.src = s.cols[c].d_values;
-    C.width = s.cols[c].kind == ColKind::DICT ? 4 : 8;
+    C.width = (int)value_width(s.cols[c].kind);
     C.nullable = nullable[c];
     C.src_valid = nullable[c] ? (s.cols[c].d_validity != nullptr ? s.cols[c].d_validity : d_ones) : nullptr;
     C.dst = placed[k * n_cols + c].values;
@@ -700,7 +666,8 @@ void Plan::FilterRun::describe() {
       const Placed& Q = placed[k * n_cols + c];
       unsigned long long nulls = 0;
       if (rest_of[c] >= 0) for (int q = 0; q < 64; q++) nulls += h_nulls[(k * rest.size() + (size_t)rest_of[c]) * 64 + (size_t)q];
-      P.stat_bytes += finish_column(src(k).cols[c], o.rows, (int64_t)nulls, Q.values, Q.valid, &o, &o.cols[c]);
+      finish_column(&o, c, (int64_t)nulls, Q.values, Q.valid);
+      P.stat_bytes += compaction_bytes(src(k).cols[c], o.rows);
     }
   }
 }

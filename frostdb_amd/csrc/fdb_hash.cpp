@@ -747,7 +747,7 @@ int64_t Plan::finish_columns_hash(std::vector<OutColumn>* out, DeviceBatch* resi
     for (size_t c = 0; c < n_cols; c++) {
       const GroupColState& g = gcols_[c];
       DevColumn d;
-      d.name = g.name; d.length = (int64_t)n; d.null_count = (int64_t)h_nulls[c];
+      d.name = g.name;
       if (g.kind == 0) {
         d.kind = ColKind::DICT; d.format = "I";
         std::vector<std::string> vals;
@@ -758,31 +758,23 @@ int64_t Plan::finish_columns_hash(std::vector<OutColumn>* out, DeviceBatch* resi
           pd->plain = true;
           d.dict = pd;
         }
-        d.value_bytes = (int64_t)n * 4;
       } else {
         d.kind = g.is_bool ? ColKind::BOOL : g.is_u64 ? ColKind::U64 : ColKind::I64;
         d.format = g.is_bool ? "b" : g.is_u64 ? "L" : "l";
-        d.value_bytes = g.is_bool ? (int64_t)(n + 7) / 8 : (int64_t)n * 8;
       }
-      if (n > 0) {
-        d.d_values = d_key[c];
-        if (d.null_count > 0) { d.d_validity = d_bits[c]; d.validity_bytes = (int64_t)(n + 7) / 8; }
-      }
-      resident->payload_bytes += d.value_bytes + d.validity_bytes;
       resident->cols.push_back(std::move(d));
+      finish_column(resident, c, (int64_t)h_nulls[c], n > 0 ? d_key[c] : nullptr, d_bits[c]);
     }
     for (size_t j = 0; j < aggs_.size(); j++) {
       const AggState& A = aggs_[j];
       const bool count_from_cnt = A.func == FDB_AGG_COUNT && !final_stage_;
       DevColumn d;
-      d.name = A.emit_name; d.length = (int64_t)n;
+      d.name = A.emit_name;
       const bool is_f64 = !count_from_cnt && A.type == FDB_T_F64;
       d.kind = is_f64 ? ColKind::F64 : ColKind::I64;
       d.format = is_f64 ? "g" : "l";
-      if (n > 0) d.d_values = d_vals[count_from_cnt ? 0 : 1 + j];
-      d.value_bytes = (int64_t)n * 8;
-      resident->payload_bytes += d.value_bytes;
       resident->cols.push_back(std::move(d));
+      finish_column(resident, n_cols + j, 0, n > 0 ? d_vals[count_from_cnt ? 0 : 1 + j] : nullptr, nullptr);
     }
     finished_ = true;
     return (int64_t)n;

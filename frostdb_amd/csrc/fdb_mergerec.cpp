@@ -302,28 +302,22 @@ Merged merge_on_device(MergeJob job, CallScope* cs, std::vector<hipEvent_t>* mar
   return m;
 }
 
-// Row perm[i] of the concatenated inputs → row i of a new record of `n` > 0 rows: one launch, one wait (modelled on fdb_take.cpp's gather).
+// Row perm[i] of the concatenated inputs → row i of a new record of `n` > 0 rows: one launch, one wait.
 // A column gets a bitmap when some input has one for it or lacks the column; one that ends without a NULL is emitted without it.
 std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, const Merged& m, hipEvent_t done) {
   Context* ctx = cs->ctx;
   hipStream_t stream = ctx->stream;
   const size_t C = job.schema.size(), R = job.recs.size();
   const int64_t n = m.n;
-  std::unique_ptr<DeviceBatch> out(new DeviceBatch());
+  RecordBuilder out(job.device, n);
   DrainOnUnwind drain{stream};  // (after `out`: its arena outlives the queued kernel)
-  out->device = job.device;
-  out->rows = n;
-  const size_t rows = (size_t)n, bitmap_bytes = (rows + 63) / 64 * 8;  // (the kernel writes whole 64-bit words)
-  std::vector<size_t> val_off(C, 0), bit_off(C, (size_t)-1);
-  size_t bytes = 0;
   for (size_t c = 0; c < C; c++) {
-    val_off[c] = bytes;
-    bytes += align_up(rows * (job.schema[c]->kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
+    const DevColumn& src = *job.schema[c];
     bool any_validity = false;
     for (size_t r = 0; r < R; r++) any_validity = any_validity || job.cols[r][c] == nullptr || job.cols[r][c]->d_validity != nullptr;
-    if (any_validity) { bit_off[c] = bytes; bytes += align_up(bitmap_bytes + kTailPad, 256); }
+    out.add(src.name, src.format, src.kind, src.kind == ColKind::DICT ? job.dicts[c].out : src.dict, any_validity);
   }
-  if (bytes > 0) { out->arena = device_pool_alloc(job.device, bytes); out->arena_bytes = bytes; }
+  out.allocate();
   std::vector<FdbMergeCol> mc(C);
   std::vector<FdbMergeSrc> ms(C * R);
   std::vector<FdbMergeInput> mi(R);
@@ -340,9 +334,9 @@ std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, c
       StageScope stage_scope(ctx);  // the translation tables and the descriptors leave with one copy
       for (size_t c = 0; c < C; c++) {
         std::memset(&mc[c], 0, sizeof(FdbMergeCol));
-        mc[c].dst = (unsigned char*)out->arena + val_off[c];
-        mc[c].dst_valid = bit_off[c] != (size_t)-1 ? (unsigned char*)out->arena + bit_off[c] : nullptr;
-        mc[c].width = job.schema[c]->kind == ColKind::DICT ? 4 : 8;
+        mc[c].dst = out.values(c);
+        mc[c].dst_valid = out.validity(c);
+        mc[c].width = (int32_t)value_width(job.schema[c]->kind);
         for (size_t r = 0; r < R; r++) {
           FdbMergeSrc& s = ms[c * R + r];
           std::memset(&s, 0, sizeof(s));
@@ -368,20 +362,7 @@ std::unique_ptr<DeviceBatch> gather_merged(const MergeJob& job, CallScope* cs, c
   hip_check(hipMemcpyAsync(&h_error, m.d_error, 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(merge error word)");
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   if (h_error != 0) throw Error(FDB_ERR_STATE, "merge: a tile's split points crossed (the inputs passed the order check: this is a bug)");
-  for (size_t c = 0; c < C; c++) {
-    const DevColumn& src = *job.schema[c];
-    DevColumn d;
-    d.name = src.name; d.format = src.format; d.kind = src.kind;
-    d.dict = src.kind == ColKind::DICT ? job.dicts[c].out : src.dict;
-    d.length = n;
-    d.null_count = (int64_t)h_nulls[c];
-    d.d_values = (unsigned char*)out->arena + val_off[c];
-    d.value_bytes = n * (d.kind == ColKind::DICT ? 4 : 8);
-    if (d.null_count > 0) { d.d_validity = (uint8_t*)out->arena + bit_off[c]; d.validity_bytes = (n + 7) / 8; }
-    out->payload_bytes += d.value_bytes + d.validity_bytes;
-    out->cols.push_back(std::move(d));
-  }
-  return out;
+  return out.finish(h_nulls.data());
 }
 
 void check_records(const DeviceBatch* const* in, int32_t n) {
@@ -429,15 +410,9 @@ std::unique_ptr<DeviceBatch> merge_batches_named(const DeviceBatch* const* in, i
     for (size_t k = 0; k < u.sort_expr.size(); k++) cols.push_back(fdb_sort_col{(int32_t)k, order[u.sort_expr[k]].direction, order[u.sort_expr[k]].nulls_first});
   MergeJob job = plan_merge_columns(in, n, schema, u.map, cols.data(), (int32_t)cols.size(), limit);
   if (job.recs.empty()) {  // no rows at all: the unified schema
-    std::unique_ptr<DeviceBatch> out(new DeviceBatch());
-    out->device = job.device;
-    for (const DevColumn* c : schema) {
-      DevColumn d;
-      d.name = c->name; d.format = c->format; d.kind = c->kind; d.dict = c->dict;
-      if (d.kind == ColKind::DICT && !d.dict) d.dict = make_dictionary({}, "z");
-      out->cols.push_back(std::move(d));
-    }
-    return out;
+    RecordBuilder out(job.device, 0);
+    for (const DevColumn* c : schema) out.add(c->name, c->format, c->kind, c->kind == ColKind::DICT && !c->dict ? make_dictionary({}, "z") : c->dict, false);
+    return out.finish(nullptr);
   }
   CallScope cs(job.device);
   DrainOnUnwind drain{cs.ctx->stream};

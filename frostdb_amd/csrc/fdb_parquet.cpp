@@ -810,14 +810,13 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
   if (groups == nullptr || n_groups <= 0) throw Error(FDB_ERR_INVALID, "parquet: no row groups");
   for (int32_t g = 0; g < n_groups; g++)
     if (groups[g].chunks == nullptr || groups[g].n_chunks <= 0 || groups[g].n_rows < 0) throw Error(FDB_ERR_INVALID, "parquet: no column chunks");
-  struct Piece { size_t val_off, bit_off; };
   struct Group {
     const fdb_parquet_chunk* chunks; int32_t n_chunks; int64_t n_rows;
     std::vector<ParsedChunk> parsed;
     std::vector<std::vector<InflateJob>> jobs;  // per chunk
     std::vector<uint8_t*> early;                // device copies of chunks that cross PCIe as they are, started before the host part
     std::vector<hipEvent_t> copied;             // per early-copied chunk: its copy is complete
-    std::vector<Piece> pieces;
+    RecordLayout layout;  // the slots of the row group's columns: an optional column has a bitmap slot
     std::unique_ptr<DeviceBatch> b;
     unsigned long long* h_totals = nullptr;     // per chunk, in the call's pinned block
     std::vector<unsigned long long*> d_totals;
@@ -832,7 +831,7 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
     Group& R = G[(size_t)g];
     R.chunks = groups[g].chunks; R.n_chunks = groups[g].n_chunks; R.n_rows = groups[g].n_rows;
     const size_t n = (size_t)R.n_chunks;
-    R.parsed.resize(n); R.jobs.resize(n); R.early.assign(n, nullptr); R.copied.assign(n, nullptr); R.pieces.resize(n);
+    R.parsed.resize(n); R.jobs.resize(n); R.early.assign(n, nullptr); R.copied.assign(n, nullptr);
     R.d_totals.assign(n, nullptr); R.flag_at.assign(n, -1); R.parse_us.assign(n, 0.0); R.parsed_ok.assign(n, 0);
     all_chunks += n;
   }
@@ -1025,16 +1024,8 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
       R.b.reset(new DeviceBatch());
       R.b->device = device;
       R.b->rows = R.n_rows;
-      size_t total = 0;
-      for (int32_t i = 0; i < R.n_chunks; i++) {
-        const fdb_parquet_chunk& c = R.chunks[i];
-        const size_t w = c.physical_type == 6 ? 4 : 8;
-        R.pieces[(size_t)i].val_off = total;
-        total += align_up((size_t)R.n_rows * w + kTailPad, 256);
-        R.pieces[(size_t)i].bit_off = total;
-        if (c.optional) total += align_up((size_t)((R.n_rows + 31) / 32) * 4 + kTailPad, 256);
-      }
-      if (R.n_rows > 0) { R.b->arena = device_pool_alloc(device, std::max<size_t>(total, 256)); R.b->arena_bytes = std::max<size_t>(total, 256); }
+      for (int32_t i = 0; i < R.n_chunks; i++) R.layout.add((size_t)R.n_rows, R.chunks[i].physical_type == 6 ? 4 : 8, R.chunks[i].optional != 0);
+      if (R.n_rows > 0 && R.layout.total > 0) { R.b->arena = device_pool_alloc(device, R.layout.total); R.b->arena_bytes = R.layout.total; }
     }
   };
   auto issue_chunk = [&](int32_t g, int32_t i, hipStream_t stream) {  // (`stream`: the one this chunk's kernels and tables go to)
@@ -1121,7 +1112,7 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
       if (c.optional) {
         if (P.def_runs.empty()) throw Error(FDB_ERR_INVALID, "parquet: optional column without definition levels");
         const FdbPqRun* d_runs = (const FdbPqRun*)to_device(P.def_runs.data(), P.def_runs.size() * sizeof(FdbPqRun), P.def_runs.pinned());
-        d_valid = (uint32_t*)((unsigned char*)b->arena + R.pieces[(size_t)i].bit_off);
+        d_valid = (uint32_t*)((unsigned char*)b->arena + R.layout.cols[(size_t)i].bit_off);
         d_prefix = (uint32_t*)ctx->dev_alloc((size_t)(n_words + 4 + n_words / 1024 + 8) * 4);  // (+ the scan's per-1024 sums)
         scratch.push_back(d_prefix);
         R.d_totals[(size_t)i] = (unsigned long long*)ctx->dev_alloc(64);
@@ -1130,7 +1121,7 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
         hip_check(fdb_launch_pq_validity(d_chunk, d_runs, (int32_t)P.def_runs.size(), n_rows, d_valid, d_prefix, stream), "parquet validity");
         hip_check(fdb_launch_exclusive_scan(d_prefix, n_words, d_prefix + n_words + 4, R.d_totals[(size_t)i], stream), "parquet rank scan");
       }
-      void* d_out = (unsigned char*)b->arena + R.pieces[(size_t)i].val_off;
+      void* d_out = (unsigned char*)b->arena + R.layout.cols[(size_t)i].val_off;
       if (c.physical_type == 6) {
         const FdbPqRun* d_idx = (const FdbPqRun*)to_device(P.idx_runs.data(), P.idx_runs.size() * sizeof(FdbPqRun), P.idx_runs.pinned());
         if (P.non_null > 0 && P.idx_runs.empty()) throw Error(FDB_ERR_INVALID, "parquet: values without index runs");
@@ -1278,23 +1269,20 @@ std::vector<std::unique_ptr<DeviceBatch>> batches_from_parquet(const fdb_parquet
       const ParsedChunk& P = R.parsed[(size_t)i];
       DevColumn d;
       d.name = c.name ? c.name : "";
-      d.length = n_rows;
       if (c.physical_type == 6) { d.kind = ColKind::DICT; d.format = "I"; d.dict = P.dict ? P.dict : make_dictionary({}, c.utf8 ? "u" : "z"); }
       else if (c.physical_type == PT_INT64 && c.utf8) { d.kind = ColKind::U64; d.format = "L"; }  // logical type Int(64, unsigned) (convert.go:76-82)
       else if (c.physical_type == PT_INT64) { d.kind = ColKind::I64; d.format = "l"; }
       else if (c.physical_type == PT_BOOLEAN) { d.kind = ColKind::BOOL; d.format = "b"; }
       else { d.kind = ColKind::F64; d.format = "g"; }
-      const size_t w = c.physical_type == 6 ? 4 : 8;
-      if (n_rows > 0) d.d_values = (unsigned char*)b->arena + R.pieces[(size_t)i].val_off;
-      d.value_bytes = d.kind == ColKind::BOOL ? (n_rows + 7) / 8 : n_rows * (int64_t)w;
+      int64_t nulls = 0;
       if (c.optional && n_rows > 0) {
         if ((int64_t)R.h_totals[(size_t)i] != P.non_null) throw Error(FDB_ERR_INVALID, "parquet: definition levels and value counts disagree in column " + d.name);
-        d.null_count = n_rows - P.non_null;
-        if (d.null_count > 0) { d.d_validity = (uint8_t*)b->arena + R.pieces[(size_t)i].bit_off; d.validity_bytes = (n_rows + 7) / 8; }
+        nulls = n_rows - P.non_null;
       }
       if (R.flag_at[(size_t)i] >= 0 && h_flags != nullptr && h_flags[(size_t)R.flag_at[(size_t)i]] != 0) throw Error(FDB_ERR_INVALID, "parquet: dictionary index out of range in column " + d.name);
-      b->payload_bytes += d.value_bytes + d.validity_bytes;
       b->cols.push_back(std::move(d));
+      finish_column(b, (size_t)i, nulls, n_rows > 0 ? (unsigned char*)b->arena + R.layout.cols[(size_t)i].val_off : nullptr,
+                    nulls > 0 ? (unsigned char*)b->arena + R.layout.cols[(size_t)i].bit_off : nullptr);
       fb += c.n_bytes;
     }
     ob += b->payload_bytes;

@@ -123,29 +123,18 @@ std::unique_ptr<DeviceBatch> import_batch(const HostRecordView& view, int device
   struct Report { ~Report() { if (prof && p_n.load() > 0) std::fprintf(stderr, "[fdb] import of %lld records: plan+dictionaries %.2f, reserve %.2f, copies %.2f, index check %.2f us per record\n", (long long)p_n.load(),
                                                                       p_ns[0] / 1e3 / p_n, p_ns[1] / 1e3 / p_n, p_ns[2] / 1e3 / p_n, p_ns[3] / 1e3 / p_n); } };
   static Report report;
-  // plan the arena
-  struct Piece { size_t col; bool validity; size_t off; size_t bytes; };
-  std::vector<Piece> pieces;
+  // plan the arena: the slots of the staged columns the device can hold
+  RecordLayout layout;
+  std::vector<size_t> held;  // their numbers among the record's columns, in layout order
   std::vector<std::pair<size_t, std::vector<uint32_t>>> plain_idx;  // (column, encoded indices) of plain string columns
-  size_t total = 0;
   for (size_t i = 0; i < view.cols.size(); i++) {
     const HostColView& c = view.cols[i];
     DevColumn d;
     d.name = c.name; d.format = c.format; d.kind = c.kind; d.length = c.length; d.null_count = c.null_count;
-    const bool staged = (want == nullptr || (*want)(c.name));
-    if (staged) {
-      int64_t vb = 0;
-      if (c.kind == ColKind::I64 || c.kind == ColKind::U64 || c.kind == ColKind::F64 || c.kind == ColKind::BOOL) vb = c.length * 8;  // (bool: widened to int64 1 / 2)
-      else if (c.kind == ColKind::DICT || c.kind == ColKind::STR) vb = c.length * 4;  // (plain strings: encoded below, one uint32 per row)
-      if (vb > 0 || ((c.kind == ColKind::I64 || c.kind == ColKind::U64 || c.kind == ColKind::F64 || c.kind == ColKind::DICT || c.kind == ColKind::BOOL || c.kind == ColKind::STR))) {
-        d.value_bytes = c.kind == ColKind::BOOL ? (c.length + 7) / 8 : vb;  // (algorithmic bytes: Arrow's bit-packed buffer)
-        pieces.push_back(Piece{i, false, total, (size_t)vb});
-        total += align_up((size_t)vb + kTailPad, 256);
-        if (c.null_count > 0) {
-          d.validity_bytes = (c.length + 7) / 8;
-          pieces.push_back(Piece{i, true, total, (size_t)d.validity_bytes});
-          total += align_up((size_t)d.validity_bytes + kTailPad, 256);
-        }
+    if (want == nullptr || (*want)(c.name)) {  // (present but not staged: d_values stays nullptr)
+      if (c.kind == ColKind::I64 || c.kind == ColKind::U64 || c.kind == ColKind::F64 || c.kind == ColKind::DICT || c.kind == ColKind::BOOL || c.kind == ColKind::STR) {
+        held.push_back(i);
+        layout.add((size_t)c.length, value_width(c.kind), c.null_count > 0);
       }
       if (c.kind == ColKind::DICT) d.dict = read_dictionary(c);
       if (c.kind == ColKind::STR) {  // from here on a dictionary column whose dictionary says `plain`
@@ -153,11 +142,10 @@ std::unique_ptr<DeviceBatch> import_batch(const HostRecordView& view, int device
         d.dict = encode_plain(c, &plain_idx.back().second);
         d.kind = ColKind::DICT;
       }
-    } else {
-      d.kind = c.kind;  // present but not staged: d_values stays nullptr
     }
     b->cols.push_back(std::move(d));
   }
+  const size_t total = layout.total;
   lap(0);
   unsigned char* sink_host = nullptr;
   if (total > 0) {
@@ -180,61 +168,60 @@ std::unique_ptr<DeviceBatch> import_batch(const HostRecordView& view, int device
     else if (ctx != nullptr) hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream), what);
     else hip_check(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), what);
   };
-  for (const Piece& p : pieces) {
-    const HostColView& c = view.cols[p.col];
-    DevColumn& d = b->cols[p.col];
-    unsigned char* dst = (unsigned char*)b->arena + p.off;
-    if (p.validity) {
-      d.d_validity = dst;
-      if (p.bytes == 0) continue;
+  for (size_t k = 0; k < held.size(); k++) {
+    const size_t col = held[k];
+    const HostColView& c = view.cols[col];
+    const DevColumn& d = b->cols[col];
+    unsigned char* dst = (unsigned char*)b->arena + layout.cols[k].val_off;
+    unsigned char* dst_bits = layout.cols[k].bit_off != kNoSlot ? (unsigned char*)b->arena + layout.cols[k].bit_off : nullptr;
+    finish_column(b.get(), col, c.null_count, dst, dst_bits);
+    const size_t vb = (size_t)c.length * value_width(d.kind), bb = (size_t)(c.length + 7) / 8;  // (bool: widened to int64 1 / 2; plain strings: one uint32 per row)
+    if (dst_bits != nullptr && bb > 0) {
       if ((c.offset & 7) == 0) {  // byte-aligned bitmap: copied as is (bits past `length` are never looked at)
-        h2d(dst, c.validity + (c.offset >> 3), p.bytes, "hipMemcpy(validity)");
+        h2d(dst_bits, c.validity + (c.offset >> 3), bb, "hipMemcpy(validity)");
       } else {
-        keep_bits.emplace_back(p.bytes, 0);
+        keep_bits.emplace_back(bb, 0);
         copy_bits(c.validity, c.offset, c.length, keep_bits.back().data());
-        h2d(dst, keep_bits.back().data(), p.bytes, "hipMemcpy(validity)");
-      }
-    } else {
-      d.d_values = dst;
-      if (p.bytes == 0) continue;
-      if (c.kind == ColKind::BOOL) {
-        // Arrow booleans are bit-packed; on the device a bool is an int64 holding 1 (false) or 2 (true) — the reference's own
-        // hash of a bool key (dynparquet/hashed.go:228-242; 0 is NULL), so a bool group key is an ordinary int64 key, a filter
-        // leaf an int64 compare and AND a MIN
-        keep_i64.emplace_back((size_t)c.length);
-        std::vector<int64_t>& wide = keep_i64.back();
-        const uint8_t* bits = (const uint8_t*)c.values;
-        for (int64_t i = 0; i < c.length; i++) wide[(size_t)i] = 1 + ((bits[(c.offset + i) >> 3] >> ((c.offset + i) & 7)) & 1);
-        h2d(dst, wide.data(), p.bytes, "hipMemcpy(bool values)");
-      } else if (c.kind == ColKind::STR) {
-        const std::vector<uint32_t>* enc = nullptr;
-        for (const auto& pi : plain_idx) if (pi.first == p.col) enc = &pi.second;
-        h2d(dst, enc->data(), p.bytes, "hipMemcpy(encoded strings)");
-      } else if (c.kind == ColKind::DICT && c.index_width != 4) {
-        keep_idx.emplace_back((size_t)c.length);
-        std::vector<uint32_t>& wide = keep_idx.back();
-        for (int64_t i = 0; i < c.length; i++) {
-          switch (c.index_width) {
-            case 1: wide[(size_t)i] = ((const uint8_t*)c.values)[c.offset + i]; break;
-            case 2: wide[(size_t)i] = ((const uint16_t*)c.values)[c.offset + i]; break;
-            default: wide[(size_t)i] = (uint32_t)((const uint64_t*)c.values)[c.offset + i]; break;
-          }
-        }
-        h2d(dst, wide.data(), p.bytes, "hipMemcpy(indices)");
-      } else if (ring != nullptr && c.kind == ColKind::DICT && d.dict && !d.dict->plain) {
-        // indices into the pinned piece and their maximum in ONE pass (the separate validation pass re-read what had just been written: 27 µs
-        // of a 65 536-row record's 85)
-        const uint32_t* src = (const uint32_t*)c.values + c.offset;
-        uint32_t* out = (uint32_t*)(ring + (dst - (unsigned char*)b->arena));
-        index_max[p.col] = copy_stream_max_u32(out, src, (size_t)c.length);
-        index_max_known[p.col] = 1;
-      } else {
-        const size_t w = c.kind == ColKind::DICT ? 4 : 8;
-        h2d(dst, (const unsigned char*)c.values + (size_t)c.offset * w, p.bytes, "hipMemcpy(values)");
+        h2d(dst_bits, keep_bits.back().data(), bb, "hipMemcpy(validity)");
       }
     }
+    if (vb == 0) continue;
+    if (c.kind == ColKind::BOOL) {
+      // Arrow booleans are bit-packed; on the device a bool is an int64 holding 1 (false) or 2 (true) — the reference's own
+      // hash of a bool key (dynparquet/hashed.go:228-242; 0 is NULL), so a bool group key is an ordinary int64 key, a filter
+      // leaf an int64 compare and AND a MIN
+      keep_i64.emplace_back((size_t)c.length);
+      std::vector<int64_t>& wide = keep_i64.back();
+      const uint8_t* bits = (const uint8_t*)c.values;
+      for (int64_t i = 0; i < c.length; i++) wide[(size_t)i] = 1 + ((bits[(c.offset + i) >> 3] >> ((c.offset + i) & 7)) & 1);
+      h2d(dst, wide.data(), vb, "hipMemcpy(bool values)");
+    } else if (c.kind == ColKind::STR) {
+      const std::vector<uint32_t>* enc = nullptr;
+      for (const auto& pi : plain_idx) if (pi.first == col) enc = &pi.second;
+      h2d(dst, enc->data(), vb, "hipMemcpy(encoded strings)");
+    } else if (c.kind == ColKind::DICT && c.index_width != 4) {
+      keep_idx.emplace_back((size_t)c.length);
+      std::vector<uint32_t>& wide = keep_idx.back();
+      for (int64_t i = 0; i < c.length; i++) {
+        switch (c.index_width) {
+          case 1: wide[(size_t)i] = ((const uint8_t*)c.values)[c.offset + i]; break;
+          case 2: wide[(size_t)i] = ((const uint16_t*)c.values)[c.offset + i]; break;
+          default: wide[(size_t)i] = (uint32_t)((const uint64_t*)c.values)[c.offset + i]; break;
+        }
+      }
+      h2d(dst, wide.data(), vb, "hipMemcpy(indices)");
+    } else if (ring != nullptr && c.kind == ColKind::DICT && d.dict && !d.dict->plain) {
+      // indices into the pinned piece and their maximum in ONE pass (the separate validation pass re-read what had just been written: 27 µs
+      // of a 65 536-row record's 85)
+      const uint32_t* src = (const uint32_t*)c.values + c.offset;
+      uint32_t* out = (uint32_t*)(ring + (dst - (unsigned char*)b->arena));
+      index_max[col] = copy_stream_max_u32(out, src, (size_t)c.length);
+      index_max_known[col] = 1;
+    } else {
+      const size_t w = value_width(c.kind);
+      h2d(dst, (const unsigned char*)c.values + (size_t)c.offset * w, vb, "hipMemcpy(values)");
+    }
   }
-  for (const DevColumn& d : b->cols) b->payload_bytes += d.value_bytes + d.validity_bytes;
   lap(2);
   // dictionary indices are validated before anything can scan the record (see check_indices_host)
   std::vector<size_t> dict_cols;

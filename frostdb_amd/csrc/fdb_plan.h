@@ -17,6 +17,7 @@
 #include "fdb_arrow.h"
 #include "fdb_regex.h"
 #include "fdb_kernels.h"
+#include "fdb_record.h"
 
 namespace fdb {
 
@@ -24,20 +25,6 @@ void hip_check(hipError_t e, const char* what);
 // Counts and array pointers of a plan descriptor agree (no negative count, no missing array, no projection without nodes): what every
 // reader of the descriptor — the dynamic-aggregation copy, Draw, the plan itself — may then rely on. Throws FDB_ERR_INVALID.
 void check_desc_shape(const fdb_plan_desc* d);
-
-// One column of a record resident in HBM.
-struct DevColumn {
-  std::string name;
-  std::string format;           // Arrow format of the column as received (index format for DICT)
-  ColKind kind = ColKind::OTHER;
-  int64_t length = 0;
-  int64_t null_count = 0;
-  void* d_values = nullptr;     // int64/uint64/double values or uint32 dictionary indices; nullptr for STR/OTHER/BOOL
-  uint8_t* d_validity = nullptr;  // validity bitmap at bit offset 0; nullptr ⇔ null_count == 0
-  std::shared_ptr<HostDict> dict;
-  int64_t value_bytes = 0;      // algorithmic bytes: values/indices
-  int64_t validity_bytes = 0;   // algorithmic bytes: bitmap (0 when the column has no nulls)
-};
 
 struct DeviceBatch {
   int device = 0;

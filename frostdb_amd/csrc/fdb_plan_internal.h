@@ -16,9 +16,6 @@
 
 namespace fdb {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-constexpr size_t kTailPad = 256;  // bytes readable past every column so tail lanes may over-read
-
 bool is_leaf_op(int32_t op);  // a comparison / regex / contains leaf of a filter expression
 
 struct PhaseTimer {  // FDB_PROFILE=1: per-phase host microseconds on stderr (tuning aid)
@@ -65,13 +62,6 @@ struct StageScope {
   Context* c;
   explicit StageScope(Context* ctx) : c(ctx) { c->defer_staging(true); }
   ~StageScope() { try { c->defer_staging(false); } catch (...) {} }
-};
-
-// Declared after the results it guards: an error that unwinds past it waits for the stream, so their arenas (and inputs the caller
-// may release) go back to the pool only once no queued kernel uses them.
-struct DrainOnUnwind {
-  hipStream_t s; int n = std::uncaught_exceptions();
-  ~DrainOnUnwind() { if (std::uncaught_exceptions() > n) (void)hipStreamSynchronize(s); }
 };
 
 template <class F>

@@ -28,7 +28,7 @@
 #ifndef FDB_PQWRITE_HOST_ONLY
 #include "fdb_context.h"
 #include "fdb_plan_internal.h"
-#include "fdb_take.h"
+#include "fdb_record.h"
 #endif
 
 namespace fdb {

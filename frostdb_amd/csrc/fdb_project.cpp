@@ -59,7 +59,8 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
     if (in[i]->device != device_) throw Error(FDB_ERR_INVALID, "batch lives on a different device than the plan");
   hip_check(hipSetDevice(device_), "hipSetDevice");
   std::vector<std::unique_ptr<DeviceBatch>> out;
-  DrainOnUnwind drain{stream_};  // (after `out`: its arenas, and the inputs the caller may release, outlive the queued copies and the kernel)
+  std::vector<RecordBuilder> outs;  // one per record, finished into `out` in step (3)
+  DrainOnUnwind drain{stream_};  // (after `out` and `outs`: their arenas, and the inputs the caller may release, outlive the queued copies and the kernel)
   auto find_proj = [this](const std::string& name) { return find_projection(name); };
 
   struct Rec {
@@ -67,7 +68,7 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
     std::vector<int> computed;      // indices into `fields`
     std::vector<int> roots;         // root node of each computed field (in R.args.expr)
     Resolved R;
-    std::vector<size_t> val_off, bit_off;  // per field, into the output arena (bit_off: (size_t)-1 = no bitmap)
+    int64_t rows = 0;               // of the output: a record that contributes no field contributes no row
     int part = -1;                  // index among the launch's argument blocks
   };
   std::vector<Rec> recs((size_t)n);
@@ -109,41 +110,22 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
   for (int i = 0; i < n; i++) {
     const DeviceBatch& b = *in[i];
     Rec& r = recs[(size_t)i];
-    std::unique_ptr<DeviceBatch> o(new DeviceBatch());
-    o->device = device_;
-    o->rows = r.fields.empty() ? 0 : b.rows;
-    const size_t rows = (size_t)o->rows;
-    size_t bytes = 0;
-    r.val_off.assign(r.fields.size(), 0);
-    r.bit_off.assign(r.fields.size(), (size_t)-1);
+    r.rows = r.fields.empty() ? 0 : b.rows;
+    RecordBuilder o(device_, r.rows);
     size_t k = 0;
-    for (size_t f = 0; f < r.fields.size(); f++) {
-      const Field& F = r.fields[f];
-      DevColumn d;
-      bool bitmap;
-      size_t w = 8;
+    for (const Field& F : r.fields) {
       if (F.proj == nullptr) {
         const DevColumn& c = b.cols[(size_t)F.src];
-        d.name = c.name; d.format = c.format; d.kind = c.kind; d.dict = c.dict;
-        w = c.kind == ColKind::DICT ? 4 : 8;
-        bitmap = c.d_validity != nullptr;
+        o.add(c.name, c.format, c.kind, c.dict, c.d_validity != nullptr);
       } else {
         const int32_t t = r.R.args.expr[r.roots[k]].type;
-        d.name = F.proj->name;
-        d.kind = t == FDB_T_I64 ? ColKind::I64 : t == FDB_T_U64 ? ColKind::U64 : t == FDB_T_F64 ? ColKind::F64 : ColKind::BOOL;
-        d.format = t == FDB_T_I64 ? "l" : t == FDB_T_U64 ? "L" : t == FDB_T_F64 ? "g" : "b";
-        bitmap = may_null(r, b, k);
+        o.add(F.proj->name, t == FDB_T_I64 ? "l" : t == FDB_T_U64 ? "L" : t == FDB_T_F64 ? "g" : "b",
+              t == FDB_T_I64 ? ColKind::I64 : t == FDB_T_U64 ? ColKind::U64 : t == FDB_T_F64 ? ColKind::F64 : ColKind::BOOL, nullptr, may_null(r, b, k));
         k++;
       }
-      d.length = o->rows;
-      o->cols.push_back(std::move(d));
-      if (rows == 0) continue;
-      r.val_off[f] = bytes;
-      bytes += align_up(rows * w + kTailPad, 256);
-      if (bitmap) { r.bit_off[f] = bytes; bytes += align_up((rows + 7) / 8 + kTailPad, 256); }
     }
-    if (bytes > 0) { o->arena = device_pool_alloc(device_, bytes); o->arena_bytes = bytes; }
-    out.push_back(std::move(o));
+    o.allocate();
+    outs.push_back(std::move(o));
   }
 
   // (2) pass-through fields: bit for bit, into the output's own arena (its lifetime does not depend on the input's)
@@ -152,21 +134,21 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
   for (int i = 0; i < n; i++) {
     const DeviceBatch& b = *in[i];
     Rec& r = recs[(size_t)i];
-    DeviceBatch& o = *out[(size_t)i];
-    if (o.rows == 0) continue;
+    const RecordBuilder& o = outs[(size_t)i];
+    if (r.rows == 0) continue;
     for (size_t f = 0; f < r.fields.size(); f++) {
       if (r.fields[f].proj != nullptr) continue;
       const DevColumn& c = b.cols[(size_t)r.fields[f].src];
-      const size_t vb = (size_t)o.rows * (c.kind == ColKind::DICT ? 4 : 8), bb = ((size_t)o.rows + 7) / 8;
-      hip_check(hipMemcpyAsync((unsigned char*)o.arena + r.val_off[f], c.d_values, vb, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(projected column)");
-      if (c.d_validity != nullptr) hip_check(hipMemcpyAsync((unsigned char*)o.arena + r.bit_off[f], c.d_validity, bb, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(projected validity)");
+      const size_t vb = (size_t)r.rows * value_width(c.kind), bb = ((size_t)r.rows + 7) / 8;
+      hip_check(hipMemcpyAsync(o.values(f), c.d_values, vb, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(projected column)");
+      if (c.d_validity != nullptr) hip_check(hipMemcpyAsync(o.validity(f), c.d_validity, bb, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(projected validity)");
       copied += 2 * (int64_t)(vb + (c.d_validity != nullptr ? bb : 0));
     }
   }
 
   // computed fields: one argument block per record that has rows, one launch
   std::vector<int> live;
-  for (int i = 0; i < n; i++) if (out[(size_t)i]->rows > 0 && !recs[(size_t)i].computed.empty()) live.push_back(i);
+  for (int i = 0; i < n; i++) if (recs[(size_t)i].rows > 0 && !recs[(size_t)i].computed.empty()) live.push_back(i);
   std::vector<unsigned long long> h_nulls;
   if (!live.empty()) {
     std::vector<FdbScanArgs> parts;
@@ -208,11 +190,10 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
         r.part = (int)k;
         FdbProjectPart op;
         std::memset(&op, 0, sizeof(op));
-        DeviceBatch& o = *out[(size_t)live[k]];
+        const RecordBuilder& o = outs[(size_t)live[k]];
         for (size_t c = 0; c < r.computed.size(); c++) {
-          const size_t f = (size_t)r.computed[c];
-          op.out[c].values = (unsigned char*)o.arena + r.val_off[f];
-          op.out[c].validity = r.bit_off[f] != (size_t)-1 ? (uint8_t*)o.arena + r.bit_off[f] : nullptr;
+          op.out[c].values = o.values((size_t)r.computed[c]);
+          op.out[c].validity = o.validity((size_t)r.computed[c]);
         }
         oparts.push_back(op);
       }
@@ -247,27 +228,15 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
   for (int i = 0; i < n; i++) {
     const DeviceBatch& b = *in[i];
     Rec& r = recs[(size_t)i];
-    DeviceBatch& o = *out[(size_t)i];
     if (!r.fields.empty()) { stat_rows += b.rows; stat_bytes += r.R.bytes; }
-    if (o.rows == 0) continue;
+    std::vector<unsigned long long> nulls;
     size_t k = 0;
-    for (size_t f = 0; f < r.fields.size(); f++) {
-      DevColumn& d = o.cols[f];
-      d.d_values = (unsigned char*)o.arena + r.val_off[f];
-      if (r.fields[f].proj == nullptr) {
-        const DevColumn& c = b.cols[(size_t)r.fields[f].src];
-        d.null_count = c.null_count; d.value_bytes = c.value_bytes; d.validity_bytes = c.validity_bytes;
-        if (c.d_validity != nullptr) d.d_validity = (uint8_t*)o.arena + r.bit_off[f];
-      } else {
-        const int64_t nulls = r.part >= 0 ? (int64_t)h_nulls[(size_t)r.part * FDB_PROJECT_MAX_OUT + k] : 0;
-        d.null_count = nulls;
-        d.value_bytes = d.kind == ColKind::BOOL ? (o.rows + 7) / 8 : o.rows * 8;
-        if (nulls > 0 && r.bit_off[f] != (size_t)-1) { d.d_validity = (uint8_t*)o.arena + r.bit_off[f]; d.validity_bytes = (o.rows + 7) / 8; }
-        stat_bytes += o.rows * 8 + d.validity_bytes;
-        k++;
-      }
-      o.payload_bytes += d.value_bytes + d.validity_bytes;
+    for (const Field& F : r.fields) {
+      if (F.proj == nullptr) nulls.push_back((unsigned long long)b.cols[(size_t)F.src].null_count);
+      else { nulls.push_back(r.part >= 0 ? h_nulls[(size_t)r.part * FDB_PROJECT_MAX_OUT + k] : 0); k++; }
     }
+    out.push_back(outs[(size_t)i].finish(nulls.data()));
+    for (int f : r.computed) stat_bytes += r.rows * 8 + out.back()->cols[(size_t)f].validity_bytes;
   }
   stat_bytes += copied;
   return out;

@@ -1,0 +1,132 @@
+// fdb_record.h — the layout contract of a record resident in HBM (DeviceBatch, fdb_plan.h) and the one builder of such records.
+//
+// A record is one arena of 256-byte aligned slots. Per column a value slot — uint32 dictionary indices or 8-byte values, bool widened to
+// int64 — and, only if the column may hold NULLs, a bitmap slot; every slot ends kTailPad bytes past its payload. A finished column
+// carries its bitmap iff it holds a NULL, and its value_bytes / validity_bytes are the algorithmic bytes every roofline figure counts.
+//
+// Three layers, smallest first: the slot arithmetic and finish_column are host-only (no device, no HIP: tools/asan_record.sh runs them
+// under AddressSanitizer with FDB_RECORD_HOST_ONLY defined); RecordBuilder and the plumbing of a call that builds a record need both.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "fdb_arrow.h"
+
+namespace fdb {
+
+// ---- 1. slot arithmetic ------------------------------------------------------------------------------------------------------------------
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr size_t kTailPad = 256;  // bytes readable past every column so tail lanes may over-read
+constexpr size_t kNoSlot = (size_t)-1;
+
+inline size_t value_width(ColKind kind) { return kind == ColKind::DICT || kind == ColKind::STR ? 4 : 8; }  // (a plain string column is staged as indices)
+inline size_t values_slot(size_t rows, size_t width) { return align_up(rows * width + kTailPad, 256); }
+// Whole 64-bit words, which is what the kernels write. Sizing the payload in bytes, (rows + 7) / 8, or in 32-bit words, (rows + 31) / 32 * 4,
+// gives the same slot: the word forms round the byte count up to a multiple of 4 or 8, and the next multiple of 256 at or above the
+// byte count is itself such a multiple, so the rounding never passes it.
+inline size_t bitmap_slot(size_t rows) { return align_up((rows + 63) / 64 * 8 + kTailPad, 256); }
+
+// Offsets of the slots of one record, in column order: [values | bitmap] per column.
+struct RecordLayout {
+  struct Col { size_t val_off, bit_off; };  // bit_off == kNoSlot: no bitmap slot
+  std::vector<Col> cols;
+  size_t total = 0;
+  void add(size_t rows, size_t width, bool bitmap) {
+    Col c{total, kNoSlot};
+    total += values_slot(rows, width);
+    if (bitmap) { c.bit_off = total; total += bitmap_slot(rows); }
+    cols.push_back(c);
+  }
+};
+
+// ---- 2. a finished column ----------------------------------------------------------------------------------------------------------------
+// One column of a record resident in HBM.
+struct DevColumn {
+  std::string name;
+  std::string format;           // Arrow format of the column as received (index format for DICT)
+  ColKind kind = ColKind::OTHER;
+  int64_t length = 0;
+  int64_t null_count = 0;
+  void* d_values = nullptr;     // int64/uint64/double values, bool as int64 1 / 2, uint32 indices (DICT, and STR: encoded on import); nullptr for OTHER or not staged
+  uint8_t* d_validity = nullptr;  // validity bitmap at bit offset 0; nullptr ⇔ null_count == 0
+  std::shared_ptr<HostDict> dict;
+  int64_t value_bytes = 0;      // algorithmic bytes: values/indices
+  int64_t validity_bytes = 0;   // algorithmic bytes: bitmap (0 when the column has no nulls)
+};
+
+// `d` (its kind set) holds `rows` rows at `values`, `nulls` of them NULL; `bitmap` is kept only if there is a NULL. A bool counts as
+// Arrow's bits, whatever it occupies. Returns what the column adds to its record's payload_bytes.
+inline int64_t finish_column(DevColumn* d, int64_t rows, int64_t nulls, void* values, void* bitmap) {
+  d->length = rows;
+  d->null_count = nulls;
+  d->d_values = values;
+  d->value_bytes = d->kind == ColKind::BOOL ? (rows + 7) / 8 : rows * (int64_t)value_width(d->kind);
+  if (nulls > 0 && bitmap != nullptr) { d->d_validity = (uint8_t*)bitmap; d->validity_bytes = (rows + 7) / 8; }
+  return d->value_bytes + d->validity_bytes;
+}
+
+}  // namespace fdb
+
+#ifndef FDB_RECORD_HOST_ONLY
+#include <exception>
+
+#include <hip/hip_runtime_api.h>
+
+namespace fdb {
+
+class Context;
+struct DeviceBatch;
+
+// Declared after the results it guards: an error that unwinds past it waits for the stream, so their arenas (and inputs the caller
+// may release) go back to the pool only once no queued kernel uses them.
+struct DrainOnUnwind {
+  hipStream_t s; int n = std::uncaught_exceptions();
+  ~DrainOnUnwind() { if (std::uncaught_exceptions() > n) (void)hipStreamSynchronize(s); }
+};
+
+// A pooled context for the length of one call: its stream, its staging ring, and device scratch that goes back to the context's pool
+// when the call ends (synchronised).
+struct CallScope {
+  Context* ctx = nullptr;
+  std::vector<void*> scratch;
+  explicit CallScope(int device);
+  ~CallScope();
+  CallScope(const CallScope&) = delete;
+  void* alloc(size_t bytes);
+};
+
+// FDB_ERR_UNSUPPORTED, naming `what`, if a column of `in` (rows > 0) is of a type the resident record cannot hold.
+void require_values(const DeviceBatch& in, const char* what);
+
+// finish_column for column `c` of `b` (b->rows rows), added to the record's payload_bytes.
+void finish_column(DeviceBatch* b, size_t c, int64_t nulls, void* values, void* bitmap);
+
+// ---- 3. a record of `rows` rows, column by column -----------------------------------------------------------------------------------------
+// add() every column, allocate(), point the kernels at values() / validity(), and once the NULL counts are back finish(). Declare it
+// before the DrainOnUnwind of the stream that writes the arena. Without rows nothing is laid out and finish() gives the bare schema.
+class RecordBuilder {
+ public:
+  RecordBuilder(int device, int64_t rows);
+  RecordBuilder(RecordBuilder&&) noexcept;
+  ~RecordBuilder();
+  void add(const std::string& name, const std::string& format, ColKind kind, std::shared_ptr<HostDict> dict, bool may_have_nulls);
+  void allocate();  // the arena, from the device pool (nothing when there is nothing to hold)
+  void* values(size_t c) const;
+  uint8_t* validity(size_t c) const;  // nullptr: the column has no bitmap slot
+  size_t bitmap_slot_bytes() const { return bitmap_slot((size_t)rows_); }  // (a bitmap that is OR-ed into is zeroed whole)
+  std::unique_ptr<DeviceBatch> finish(const unsigned long long* nulls);  // nulls[c]: NULLs of column c (not read without rows)
+  // `in` without rows: every column's name, format, kind and dictionary.
+  static std::unique_ptr<DeviceBatch> schema_of(const DeviceBatch& in);
+
+ private:
+  std::unique_ptr<DeviceBatch> out_;
+  RecordLayout layout_;
+  int64_t rows_;
+};
+
+}  // namespace fdb
+#endif

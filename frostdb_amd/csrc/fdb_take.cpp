@@ -16,37 +16,7 @@
 
 namespace fdb {
 
-CallScope::CallScope(int device) {
-  hip_check(hipSetDevice(device), "hipSetDevice");
-  ctx = Context::acquire(device);
-}
-
-CallScope::~CallScope() {
-  (void)hipStreamSynchronize(ctx->stream);
-  for (void* p : scratch) ctx->dev_free(p);
-  ctx->reset_staging();
-  Context::release(ctx);
-}
-
-void require_values(const DeviceBatch& in, const char* what) {
-  for (const DevColumn& c : in.cols)
-    if (c.d_values == nullptr && in.rows > 0)
-      throw Error(FDB_ERR_UNSUPPORTED, std::string(what) + ": column type " + c.format + " (" + c.name + ") is not supported on the device path");
-}
-
 namespace {
-// The record `in` without rows: every column's name, format, kind and dictionary.
-std::unique_ptr<DeviceBatch> schema_only(const DeviceBatch& in) {
-  std::unique_ptr<DeviceBatch> out(new DeviceBatch());
-  out->device = in.device;
-  for (const DevColumn& c : in.cols) {
-    DevColumn d;
-    d.name = c.name; d.format = c.format; d.kind = c.kind; d.dict = c.dict;
-    out->cols.push_back(std::move(d));
-  }
-  return out;
-}
-
 struct GatherCol {
   std::string name, format;
   ColKind kind;
@@ -61,28 +31,19 @@ struct GatherCol {
 std::unique_ptr<DeviceBatch> gather(Context* ctx, std::vector<void*>* scratch, int device, const std::vector<GatherCol>& cols, const uint32_t* d_rows, int64_t n) {
   if (cols.size() > (size_t)FDB_TAKE_MAX_COLS) throw Error(FDB_ERR_UNSUPPORTED, "take: more than " + std::to_string(FDB_TAKE_MAX_COLS) + " columns");
   hipStream_t stream = ctx->stream;
-  std::unique_ptr<DeviceBatch> out(new DeviceBatch());
+  RecordBuilder out(device, n);
   DrainOnUnwind drain{stream};  // (after `out`: its arena outlives the queued kernel)
-  out->device = device;
-  out->rows = n;
-  const size_t rows = (size_t)n, bitmap_bytes = (rows + 63) / 64 * 8;  // (the kernel writes whole 64-bit words)
-  std::vector<size_t> val_off(cols.size(), 0), bit_off(cols.size(), (size_t)-1);
-  size_t bytes = 0;
-  for (size_t k = 0; k < cols.size(); k++) {
-    val_off[k] = bytes;
-    bytes += align_up(rows * (cols[k].kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
-    if (cols[k].src_valid != nullptr) { bit_off[k] = bytes; bytes += align_up(bitmap_bytes + kTailPad, 256); }
-  }
-  if (bytes > 0) { out->arena = device_pool_alloc(device, bytes); out->arena_bytes = bytes; }
+  for (const GatherCol& c : cols) out.add(c.name, c.format, c.kind, c.dict, c.src_valid != nullptr);
+  out.allocate();
   std::vector<FdbTakeCol> tc(cols.size());
   for (size_t k = 0; k < cols.size(); k++) {
     FdbTakeCol& t = tc[k];
     std::memset(&t, 0, sizeof(t));
     t.src = cols[k].src;
     t.src_valid = cols[k].src_valid;
-    t.dst = (unsigned char*)out->arena + val_off[k];
-    t.dst_valid = bit_off[k] != (size_t)-1 ? (unsigned char*)out->arena + bit_off[k] : nullptr;
-    t.width = cols[k].kind == ColKind::DICT ? 4 : 8;
+    t.dst = out.values(k);
+    t.dst_valid = out.validity(k);
+    t.width = (int32_t)value_width(cols[k].kind);
     t.valid_bytes = cols[k].valid_bytes ? 1 : 0;
   }
   std::vector<unsigned long long> h_nulls(cols.size(), 0);
@@ -95,18 +56,7 @@ std::unique_ptr<DeviceBatch> gather(Context* ctx, std::vector<void*>* scratch, i
     hip_check(hipMemcpyAsync(h_nulls.data(), d_nulls, cols.size() * 8, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(null counts)");
   }
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  for (size_t k = 0; k < cols.size(); k++) {
-    DevColumn d;
-    d.name = cols[k].name; d.format = cols[k].format; d.kind = cols[k].kind; d.dict = cols[k].dict;
-    d.length = n;
-    d.null_count = (int64_t)h_nulls[k];
-    d.d_values = (unsigned char*)out->arena + val_off[k];
-    d.value_bytes = d.kind == ColKind::BOOL ? (n + 7) / 8 : n * (d.kind == ColKind::DICT ? 4 : 8);
-    if (d.null_count > 0) { d.d_validity = (uint8_t*)out->arena + bit_off[k]; d.validity_bytes = (n + 7) / 8; }
-    out->payload_bytes += d.value_bytes + d.validity_bytes;
-    out->cols.push_back(std::move(d));
-  }
-  return out;
+  return out.finish(h_nulls.data());
 }
 
 std::vector<GatherCol> columns_of(const DeviceBatch& in) {
@@ -119,40 +69,28 @@ std::vector<GatherCol> columns_of(const DeviceBatch& in) {
 std::unique_ptr<DeviceBatch> copy_batch(const DeviceBatch& in) {
   CallScope cs(in.device);
   hipStream_t stream = cs.ctx->stream;
-  std::unique_ptr<DeviceBatch> out = schema_only(in);
+  RecordBuilder out(in.device, in.rows);
   DrainOnUnwind drain{stream};
-  out->rows = in.rows;
-  const size_t rows = (size_t)in.rows;
-  std::vector<size_t> val_off(in.cols.size(), 0), bit_off(in.cols.size(), 0);
-  size_t bytes = 0;
-  for (size_t k = 0; k < in.cols.size(); k++) {
-    val_off[k] = bytes;
-    bytes += align_up(rows * (in.cols[k].kind == ColKind::DICT ? 4 : 8) + kTailPad, 256);
-    if (in.cols[k].d_validity != nullptr) { bit_off[k] = bytes; bytes += align_up((rows + 7) / 8 + kTailPad, 256); }
-  }
-  if (bytes > 0) { out->arena = device_pool_alloc(in.device, bytes); out->arena_bytes = bytes; }
+  for (const DevColumn& c : in.cols) out.add(c.name, c.format, c.kind, c.dict, c.d_validity != nullptr);
+  out.allocate();
   in.note_reader(stream);
+  const size_t rows = (size_t)in.rows;
+  std::vector<unsigned long long> nulls;
   for (size_t k = 0; k < in.cols.size(); k++) {
     const DevColumn& c = in.cols[k];
-    DevColumn& d = out->cols[k];
-    d.length = c.length; d.null_count = c.null_count; d.value_bytes = c.value_bytes; d.validity_bytes = c.validity_bytes;
-    d.d_values = (unsigned char*)out->arena + val_off[k];
-    hip_check(hipMemcpyAsync(d.d_values, c.d_values, rows * (c.kind == ColKind::DICT ? 4 : 8), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(limit column)");
-    if (c.d_validity != nullptr) {
-      d.d_validity = (uint8_t*)out->arena + bit_off[k];
-      hip_check(hipMemcpyAsync(d.d_validity, c.d_validity, (rows + 7) / 8, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(limit validity)");
-    }
+    nulls.push_back((unsigned long long)c.null_count);
+    hip_check(hipMemcpyAsync(out.values(k), c.d_values, rows * value_width(c.kind), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(limit column)");
+    if (c.d_validity != nullptr) hip_check(hipMemcpyAsync(out.validity(k), c.d_validity, (rows + 7) / 8, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(limit validity)");
   }
-  out->payload_bytes = in.payload_bytes;
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  return out;
+  return out.finish(nulls.data());
 }
 }  // namespace
 
 std::unique_ptr<DeviceBatch> take_batch(const DeviceBatch& in, const int32_t* indices, int64_t n) {
   check_take_indices(indices, n, in.rows);
   require_values(in, "take");
-  if (n == 0) return schema_only(in);
+  if (n == 0) return RecordBuilder::schema_of(in);
   CallScope cs(in.device);
   uint32_t* d_rows = (uint32_t*)cs.ctx->dev_alloc((size_t)n * 4);
   cs.scratch.push_back(d_rows);
@@ -168,7 +106,7 @@ std::unique_ptr<DeviceBatch> take_device_rows(const DeviceBatch& in, CallScope* 
 
 std::unique_ptr<DeviceBatch> limit_batch(const DeviceBatch& in, uint64_t count) {
   require_values(in, "limit");
-  if (in.rows == 0 || count == 0) return schema_only(in);  // limit.go:64-70
+  if (in.rows == 0 || count == 0) return RecordBuilder::schema_of(in);  // limit.go:64-70
   if ((uint64_t)in.rows <= count) return copy_batch(in);    // limit.go:72-74
   // the first `count` rows: take_kernel over the identity — a prefix copy of every column in one launch, the last validity word cut at
   // `count` and the prefix's NULLs counted on the way

@@ -7,20 +7,10 @@
 
 #include "fdb_context.h"
 #include "fdb_plan.h"
+#include "fdb_record.h"
 #include "fdb_reservoir.h"
 
 namespace fdb {
-
-// A pooled context for the length of one call: its stream, its staging ring, and device scratch that goes back to the context's pool
-// when the call ends (synchronised).
-struct CallScope {
-  Context* ctx = nullptr;
-  std::vector<void*> scratch;
-  explicit CallScope(int device);
-  ~CallScope();
-  CallScope(const CallScope&) = delete;
-  void* alloc(size_t bytes) { void* p = ctx->dev_alloc(bytes); scratch.push_back(p); return p; }
-};
 
 // ≙ arrowutils.Take(ctx, r, indices) as limit.go:88 uses it: row indices[i] of `in` becomes row i of a new resident record with the
 // same fields, types and dictionaries, whose lifetime does not depend on `in`'s. Any order, duplicates allowed; n == 0 gives a
@@ -30,8 +20,6 @@ std::unique_ptr<DeviceBatch> take_batch(const DeviceBatch& in, const int32_t* in
 // every i < n — the CALLER vouches for that, nothing is checked here —, n > 0, every column of `in` has its values. One launch on the
 // scope's stream, one wait.
 std::unique_ptr<DeviceBatch> take_device_rows(const DeviceBatch& in, CallScope* cs, const uint32_t* d_rows, int64_t n);
-// FDB_ERR_UNSUPPORTED, naming `what`, if a column of `in` (rows > 0) is of a type the resident record cannot hold.
-void require_values(const DeviceBatch& in, const char* what);
 
 // ≙ Limiter.Callback (limit.go:63-98), its quirk included: `count` applies to EVERY record and is never decremented, so the call has no
 // state. rows ≤ count: the whole record, copied device to device; count == 0: zero rows; else the first `count` rows.
@@ -66,7 +54,7 @@ class Sampler {
   void grow(int64_t slots);      // room for `slots` slots in every field
   void alloc_field(Field* f, int64_t cap);  // every slot NULL
   int field_of(const DevColumn& c);  // the field of this name (type checked), or -1
-  size_t width(const Field& f) const { return f.kind == ColKind::DICT ? 4 : 8; }
+  size_t width(const Field& f) const { return value_width(f.kind); }
 
   int device_;
   ReservoirSelect select_;
