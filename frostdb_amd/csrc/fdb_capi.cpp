@@ -708,6 +708,14 @@ int fdb_batch_to_parquet(const fdb_batch* batch, const fdb_parquet_write_options
   });
 }
 
+int fdb_batch_to_parquet_encoded(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings);
+  });
+}
+
 void fdb_bytes_free(uint8_t* bytes) { fdb::pqw_free_bytes(bytes); }
 
 int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes) {
@@ -717,6 +725,17 @@ int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSchema* sch
     fdb::HostRecordView view;
     fdb::view_record(batch, schema, &view);
     fdb::selftest_parquet_write(view, options, bytes, n_bytes);
+  });
+}
+
+int fdb_selftest_parquet_write_encoded(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
+                                       uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::HostRecordView view;
+    fdb::view_record(batch, schema, &view);
+    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings);
   });
 }
 

@@ -19,6 +19,12 @@
 // interned dictionary's entries in entry order + RLE_DICTIONARY pages: the width byte, then ONE bit-packed run — or one RLE run where all
 // non-NULL indices of the page are equal, as in the leading sorting columns of an ordered record. An all-NULL column with an empty
 // dictionary has no dictionary page and PLAIN pages of zero values.
+//
+// fdb_batch_to_parquet_encoded: an I64 / U64 column may be asked to be written DELTA_BINARY_PACKED instead (blocks of 128, 4 miniblocks; the
+// rule is spelled out in fdb_pqdelta.h). Its pages' sizes depend on the values, so between survey and layout the DELTA passes of
+// fdb_pqdelta.hip run — compaction of the columns with a bitmap, block survey, page walk — and the page sizes come back with the survey's
+// table, in the same wait; after the layout the DELTA encoder writes the pages' value bytes into the same image, beside the encode pass,
+// which for such a column writes the definition levels only. The host walk has its counterparts (pqd_survey_host / pqd_encode_host).
 #include "fdb_pqwrite_host.h"
 
 #include <algorithm>
@@ -66,7 +72,7 @@ struct Thrift {
 };
 
 enum { PT_BOOLEAN = 0, PT_INT64 = 2, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6 };
-enum { ENC_PLAIN = 0, ENC_RLE = 3, ENC_RLE_DICTIONARY = 8 };
+enum { ENC_PLAIN = 0, ENC_RLE = 3, ENC_DELTA_BINARY_PACKED = 5, ENC_RLE_DICTIONARY = 8 };
 enum { PAGE_DATA = 0, PAGE_DICTIONARY = 2 };
 
 std::string page_header(int type, int64_t body, int64_t num_values, int encoding) {
@@ -121,7 +127,7 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     t.i32(1, c.physical);
     const bool dict = c.pq_kind == FDB_PQW_INDEX;
     t.list(2, Thrift::T_I32, 1 + (c.optional ? 1 : 0) + (dict ? 1 : 0));  // (RLE: the definition levels, which a required column does not have)
-    t.zigzag(ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
+    t.zigzag(c.delta_slot >= 0 ? ENC_DELTA_BINARY_PACKED : ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
     t.list(3, Thrift::T_BINARY, 1); t.str(c.name);
     t.i32(4, 0);  // UNCOMPRESSED
     t.i64(5, rows);
@@ -191,7 +197,8 @@ void pqw_free_bytes(uint8_t* bytes) {
 }
 
 // Everything that can refuse the record, before anything is launched.
-std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows) {
+std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows, const int8_t* encodings,
+                                   int32_t n_encodings) {
   int64_t pr = opt != nullptr ? opt->page_rows : 0;
   if (pr == 0) pr = 65536;
   if (pr < 64 || pr > (1 << 24) || pr % 64 != 0)
@@ -201,6 +208,9 @@ std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows
   const int32_t n_opt = opt != nullptr ? opt->n_optional : 0;
   if (n_opt != 0 && (n_opt != (int32_t)in.size() || opt->optional == nullptr))
     throw Error(FDB_ERR_INVALID, "parquet write: `optional` has " + std::to_string(n_opt) + " entries, the record " + std::to_string(in.size()) + " columns");
+  if (n_encodings != 0 && (n_encodings != (int32_t)in.size() || encodings == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: `encodings` has " + std::to_string(n_encodings) + " entries, the record " + std::to_string(in.size()) + " columns");
+  int delta_slots = 0;
   std::vector<PqwColumn> cols;
   for (size_t k = 0; k < in.size(); k++) {
     const PqwInput& c = in[k];
@@ -216,6 +226,13 @@ std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows
     }
     if (c.values == nullptr && rows > 0)
       throw Error(FDB_ERR_UNSUPPORTED, "parquet write: column type " + c.format + " (" + c.name + ") is not held on the device");
+    const int enc = n_encodings != 0 ? (int)encodings[k] : 0;
+    if (enc < 0 || enc > 1) throw Error(FDB_ERR_INVALID, "parquet write: encodings[" + std::to_string(k) + "] is " + std::to_string(enc) + " (0 as ever, 1 DELTA_BINARY_PACKED)");
+    if (enc == 1) {
+      if (c.kind != ColKind::I64 && c.kind != ColKind::U64)
+        throw Error(FDB_ERR_UNSUPPORTED, "parquet write: DELTA_BINARY_PACKED is for int64 / uint64 columns; column " + c.name + " is " + (c.format.empty() ? std::string("another kind") : c.format));
+      o.delta_slot = delta_slots++;
+    }
     if (c.kind == ColKind::DICT) {
       if (!c.dict) throw Error(FDB_ERR_INVALID, "parquet write: dictionary column without its dictionary: " + c.name);
       const uint64_t entries = c.dict->values.size();
@@ -245,6 +262,12 @@ std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows
   return cols;
 }
 
+size_t pqw_delta_columns(const std::vector<PqwColumn>& cols) {
+  size_t n = 0;
+  for (const PqwColumn& c : cols) n += c.delta_slot >= 0;
+  return n;
+}
+
 FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols) {
   FdbPqwGeom g;
   g.rows = rows; g.page_rows = page_rows; g.n_pages = fdb_pqw_pages(rows, page_rows); g.tiles_per_page = fdb_pqw_tiles_per_page(page_rows);
@@ -258,9 +281,11 @@ void PqwLayout::put(uint64_t off, const std::string& s) {
   blob += s;
 }
 
-PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats) {
+PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes) {
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
+  if (delta_bytes.size() != pqw_delta_columns(cols) * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
   PqwLayout L;
+  L.delta_out.assign(delta_bytes.size(), FDB_PQW_NONE);
   L.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
   uint64_t cur = 0;
   L.put(cur, "PAR1");
@@ -298,7 +323,13 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
         }
       }
       int encoding = ENC_PLAIN;
-      if (c.pq_kind == FDB_PQW_V64) value_payload = (uint64_t)cnt * 8;
+      if (c.delta_slot >= 0) {
+        encoding = ENC_DELTA_BINARY_PACKED;
+        value_payload = delta_bytes[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p];
+        // (the smallest page is 80 01 04 + a count byte + a first-value byte; the first value's length is the device's to know)
+        if (value_payload < 5 || value_payload > fdb_pqd_max_page_bytes(cnt) || (cnt <= 1 && value_payload > FDB_PQD_MAX_HEADER))
+          throw Error(FDB_ERR_STATE, "parquet write: the block survey sizes a DELTA page of " + std::to_string(cnt) + " values at " + std::to_string(value_payload) + " bytes (" + c.name + ")");
+      } else if (c.pq_kind == FDB_PQW_V64) value_payload = (uint64_t)cnt * 8;
       else if (c.pq_kind == FDB_PQW_BOOL) value_payload = fdb_pqw_packed_bytes(cnt, 1);
       else if (c.pq_kind == FDB_PQW_INDEX) {
         encoding = ENC_RLE_DICTIONARY;
@@ -321,7 +352,8 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
       L.put(cur, hdr + pre); cur += hdr.size() + pre.size();
       if (level_payload > 0) { o.levels_off = cur; cur += level_payload; }
       L.put(cur, vpre); cur += vpre.size();
-      if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
+      if (c.delta_slot >= 0) { L.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
+      else if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
     }
     m.bytes = (int64_t)(cur - chunk_start);
     m.nulls = g.rows - valid;
@@ -426,7 +458,94 @@ void pqw_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
   }
 }
 
-void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes) {
+// ---- the DELTA passes over host arrays: compaction, block survey and page walk, then the encoder, block by block -------------------------
+void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& tile_base, PqdHost* d) {
+  const size_t n_d = pqw_delta_columns(cols), bpp = (size_t)fdb_pqd_blocks_per_page(g.page_rows);
+  d->dense.assign(n_d, std::vector<uint64_t>());
+  d->blocks.assign(n_d * (size_t)g.n_pages * bpp, FdbPqdBlock{0, 0, 0, 0, 0});
+  d->page_bytes.assign(n_d * (size_t)g.n_pages, 0);
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    if (c.delta_slot < 0) continue;
+    const size_t slot = (size_t)c.delta_slot;
+    if (c.validity != nullptr) {  // compaction, tile by tile: a value goes to the survey's rank of its tile + its rank inside the tile
+      std::vector<uint64_t>& dense = d->dense[slot];
+      dense.assign((size_t)g.rows, 0);
+      for (int64_t p = 0; p < g.n_pages; p++) {
+        for (int32_t t = 0; t < g.tiles_per_page; t++) {
+          int64_t first, end;
+          fdb_pqw_tile_rows(g, p, t, &first, &end);
+          if (first >= end) continue;
+          uint64_t* dst = dense.data() + fdb_pqw_page_first(g, p) + tile_base[(k * (size_t)g.n_pages + (size_t)p) * (size_t)g.tiles_per_page + (size_t)t];
+          uint32_t before = 0;
+          for (int wi = 0; wi < FDB_PQW_TILE_WORDS; wi++) {
+            const uint64_t w = fdb_pqw_valid_word(c.validity, first, wi, end);
+            for (int b = 0; b < 64; b++)
+              if ((w >> b) & 1) std::memcpy(dst + before + (uint32_t)fdb_pqw_popc(w & ((1ull << b) - 1)), (const unsigned char*)c.values + (size_t)(first + wi * 64 + b) * 8, 8);
+            before += (uint32_t)fdb_pqw_popc(w);
+          }
+        }
+      }
+    }
+    const uint64_t* values = d->values(c);
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const size_t cp = slot * (size_t)g.n_pages + (size_t)p;
+      const uint32_t count = stats[k * (size_t)g.n_pages + (size_t)p].count, deltas = fdb_pqd_deltas(count);
+      const uint64_t* v = values + fdb_pqw_page_first(g, p);
+      uint32_t run = fdb_pqd_header_len(count, count > 0 ? v[0] : 0);
+      for (uint32_t b = 0; b < fdb_pqd_blocks(deltas); b++) {
+        const uint32_t n = fdb_pqd_block_deltas(deltas, b);
+        const uint64_t at = (uint64_t)b * FDB_PQD_BLOCK;
+        int64_t mn = INT64_MAX;
+        for (uint32_t i = 0; i < n; i++) { const int64_t dl = (int64_t)fdb_pqd_delta(v, at + i); mn = dl < mn ? dl : mn; }
+        uint32_t widths = 0;
+        for (uint32_t m = 0; m < fdb_pqd_minis(n); m++) {
+          uint64_t mx = 0;
+          for (uint32_t i = m * FDB_PQD_MINI; i < n && i < (m + 1) * FDB_PQD_MINI; i++) { const uint64_t r = fdb_pqd_rel(fdb_pqd_delta(v, at + i), mn); mx = r > mx ? r : mx; }
+          widths = fdb_pqd_set_width(widths, m, fdb_pqd_bit_length(mx));
+        }
+        FdbPqdBlock& r = d->blocks[cp * bpp + b];
+        r.min = mn; r.widths = widths; r.bytes = fdb_pqd_block_bytes(mn, widths, fdb_pqd_minis(n)); r.off = run;
+        run += r.bytes;
+      }
+      d->page_bytes[cp] = run;
+    }
+  }
+}
+
+void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const PqdHost& d, const std::vector<uint64_t>& delta_out,
+                     unsigned char* image) {
+  const size_t bpp = (size_t)fdb_pqd_blocks_per_page(g.page_rows);
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    if (c.delta_slot < 0) continue;
+    const uint64_t* values = d.values(c);
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const size_t cp = (size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p;
+      const uint32_t count = stats[k * (size_t)g.n_pages + (size_t)p].count, deltas = fdb_pqd_deltas(count);
+      const uint64_t* v = values + fdb_pqw_page_first(g, p);
+      unsigned char* out = image + delta_out[cp];
+      const uint64_t first = count > 0 ? v[0] : 0;
+      for (uint32_t i = 0; i < fdb_pqd_header_len(count, first); i++) out[i] = fdb_pqd_header_byte(count, first, i);
+      for (uint32_t b = 0; b < fdb_pqd_blocks(deltas); b++) {
+        const uint32_t n = fdb_pqd_block_deltas(deltas, b);
+        const FdbPqdBlock& r = d.blocks[cp * bpp + b];
+        uint64_t rel[FDB_PQD_BLOCK];
+        for (uint32_t i = 0; i < FDB_PQD_BLOCK; i++) rel[i] = i < n ? fdb_pqd_rel(fdb_pqd_delta(v, (uint64_t)b * FDB_PQD_BLOCK + i), r.min) : 0;
+        unsigned char* q = out + r.off;
+        const uint32_t head = fdb_pqd_block_head_len(r.min);
+        for (uint32_t i = 0; i < head; i++) q[i] = fdb_pqd_block_head_byte(r.min, r.widths, i);
+        q += head;
+        for (uint32_t m = 0; m < fdb_pqd_minis(n); m++) {
+          const uint32_t w = fdb_pqd_width(r.widths, m);
+          for (uint32_t kk = 0; kk < w; kk++, q += 4) { const uint32_t word = fdb_pqd_assemble_word(rel + m * FDB_PQD_MINI, w, kk); std::memcpy(q, &word, 4); }
+        }
+      }
+    }
+  }
+}
+
+void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings) {
   // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
   const size_t rows = (size_t)view.rows;
   std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
@@ -471,15 +590,18 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     in.push_back(std::move(o));
   }
   int32_t page_rows = 0;
-  const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows);
+  const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings);
   const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
   pqw_survey_host(cols, g, &stats, &tile_base);
-  const PqwLayout L = pqw_layout(cols, g, stats);
+  PqdHost delta;
+  pqd_survey_host(cols, g, stats, tile_base, &delta);
+  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes);
   const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(cols, g, L.out, tile_base, image.data());
+  pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
   std::memcpy(file, image.data(), (size_t)L.body_bytes);
   pqw_finish(L, file);
@@ -488,7 +610,7 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
 }
 
 #ifndef FDB_PQWRITE_HOST_ONLY
-void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes) {
+void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings) {
   std::vector<PqwInput> in;
   for (const DevColumn& c : b.cols) {
     PqwInput o;
@@ -496,8 +618,9 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     in.push_back(std::move(o));
   }
   int32_t page_rows = 0;
-  const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows);
+  const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings);
   const FdbPqwGeom g = pqw_geometry(b.rows, page_rows, cols.size());
+  const size_t n_delta = pqw_delta_columns(cols);
   struct Bytes { uint8_t* p = nullptr; ~Bytes() { pqw_free_bytes(p); } } file;
   if (b.rows == 0 || cols.empty()) {  // nothing for the device to do
     const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}));
@@ -523,12 +646,40 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   FdbPqwPageStat* d_stats = (FdbPqwPageStat*)cs.alloc(items * sizeof(FdbPqwPageStat));
   uint32_t* d_tile_base = (uint32_t*)cs.alloc(items * (size_t)g.tiles_per_page * 4);
   std::vector<FdbPqwPageStat> stats(items);
+  // the DELTA columns: scratch for the dense values of those with a bitmap, the block table, the page sizes — all from the call's arena
+  const size_t d_items = n_delta * (size_t)g.n_pages;
+  std::vector<uint32_t> delta_bytes(d_items);
+  const FdbPqdCol* d_dcols = nullptr;
+  FdbPqdBlock* d_blocks = nullptr;
+  uint32_t* d_page_bytes = nullptr;
+  bool compact = false;
+  if (n_delta > 0) {
+    std::vector<FdbPqdCol> dc(n_delta);
+    for (size_t k = 0; k < cols.size(); k++) {
+      if (cols[k].delta_slot < 0) continue;
+      FdbPqdCol& o = dc[(size_t)cols[k].delta_slot];
+      std::memset(&o, 0, sizeof(FdbPqdCol));
+      o.values = (const uint64_t*)cols[k].values; o.validity = cols[k].validity; o.col = (int32_t)k;
+      o.dense = cols[k].validity != nullptr ? (uint64_t*)cs.alloc(((size_t)g.rows + 1) * 8) : (uint64_t*)const_cast<void*>(cols[k].values);  // (only ever read when it is the column)
+      compact = compact || cols[k].validity != nullptr;
+    }
+    d_dcols = (const FdbPqdCol*)cs.ctx->stage(dc.data(), dc.size() * sizeof(FdbPqdCol));
+    d_blocks = (FdbPqdBlock*)cs.alloc(d_items * (size_t)fdb_pqd_blocks_per_page(g.page_rows) * sizeof(FdbPqdBlock));
+    d_page_bytes = (uint32_t*)cs.alloc(d_items * 4);
+  }
   b.note_reader(stream);
   hip_check(fdb_launch_pqw_survey(d_cols, g, d_stats, d_tile_base, stream), "parquet write: survey launch");
   hip_check(hipMemcpyAsync(stats.data(), d_stats, items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(page table)");
+  if (n_delta > 0) {
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite survey"); }
+    if (compact) hip_check(fdb_launch_pqd_compact(d_dcols, (int32_t)n_delta, g, d_tile_base, stream), "parquet write: DELTA compaction launch");
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta compact"); }
+    hip_check(fdb_launch_pqd_survey(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_page_bytes, stream), "parquet write: DELTA block survey launch");
+    hip_check(hipMemcpyAsync(delta_bytes.data(), d_page_bytes, d_items * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(DELTA page sizes)");
+  }
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  pt.mark("pqwrite survey");
-  const PqwLayout L = pqw_layout(cols, g, stats);
+  pt.mark(n_delta > 0 ? "pqwrite delta survey" : "pqwrite survey");
+  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes);
   const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8, image_bytes = align_up((size_t)L.body_bytes + 8, 256);
   pt.mark("pqwrite layout");
   image.p = device_pool_alloc(b.device, image_bytes);
@@ -537,6 +688,12 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   hip_check(hipMemsetAsync(image.p, 0, image_bytes, stream), "hipMemsetAsync(file image)");
   hip_check(fdb_launch_pqw_encode(d_cols, g, d_out, d_tile_base, (unsigned char*)image.p, stream), "parquet write: encode launch");
   if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite encode"); }
+  if (n_delta > 0) {
+    uint64_t* d_delta_out = (uint64_t*)cs.alloc(d_items * 8);
+    hip_check(hipMemcpyAsync(d_delta_out, L.delta_out.data(), d_items * 8, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(DELTA page offsets)");
+    hip_check(fdb_launch_pqd_encode(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_delta_out, (unsigned char*)image.p, stream), "parquet write: DELTA encode launch");
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta encode"); }
+  }
   file.p = pqw_alloc_bytes(file_bytes, true);
   cs.ctx->copy_out_parallel(file.p, image.p, (size_t)L.body_bytes);
   pt.mark("pqwrite copy");

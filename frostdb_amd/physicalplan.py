@@ -168,6 +168,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_batch_column_name.restype = ctypes.c_char_p
     L.fdb_batch_to_parquet.argtypes = [vp, vp, P(vp), P(i64)]
     L.fdb_selftest_parquet_write.argtypes = [vp, vp, vp, P(vp), P(i64)]
+    L.fdb_batch_to_parquet_encoded.argtypes = [vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
+    L.fdb_selftest_parquet_write_encoded.argtypes = [vp, vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
     L.fdb_bytes_free.restype = None
     _lib = L
@@ -343,6 +345,27 @@ def _parquet_write_options(page_rows, optional, names):
     return ParquetWriteOptions(int(page_rows), len(flags), ctypes.cast(arr, ctypes.c_void_p) if flags else None), arr
 
 
+PARQUET_ENCODINGS = {None: 0, "plain": 0, "delta": 1}
+
+
+def _parquet_encodings(encodings, names):
+    """`encodings`: a sequence with one entry per column or a dict by column name; an entry is None / "plain" (as the column is
+    written without it) or "delta" (DELTA_BINARY_PACKED; int64 / uint64 columns). Returns the int8 array and its length."""
+    if isinstance(encodings, dict):
+        unknown = [n for n in encodings if n not in names]
+        if unknown:
+            _raise(FDB_ERR_INVALID, "parquet write: `encodings` names no column of the record: %s" % unknown[0])
+        wanted = [encodings.get(n) for n in names]
+    else:
+        wanted = list(encodings)
+        if not wanted and names:  # (an empty array would read as "every column as ever" on the C side)
+            _raise(FDB_ERR_INVALID, "parquet write: `encodings` has 0 entries, the record %d columns" % len(names))
+    for e in wanted:
+        if not (e is None or isinstance(e, str)) or e not in PARQUET_ENCODINGS:
+            _raise(FDB_ERR_INVALID, "parquet write: unknown encoding %r (None, 'plain' or 'delta')" % (e,))
+    return (ctypes.c_int8 * max(1, len(wanted)))(*[PARQUET_ENCODINGS[e] for e in wanted]), len(wanted)
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -352,13 +375,20 @@ def _take_bytes(rc, out, n) -> bytes:
         lib().fdb_bytes_free(out.value)
 
 
-def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None) -> bytes:
-    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional)`` writes, byte for byte, made without a device
-    (fdb_selftest_parquet_write): the same layout, headers and footer, the two kernels replaced by a host walk of the code they compile."""
-    opts, _keep = _parquet_write_options(page_rows, optional, list(record.schema.names))
+def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None) -> bytes:
+    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings)`` writes, byte for byte, made without a device
+    (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded): the same layout, headers and footer, the kernels
+    replaced by a host walk of the code they compile."""
+    names = list(record.schema.names)
+    opts, _keep = _parquet_write_options(page_rows, optional, names)
+    enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
     out, n = ctypes.c_void_p(), ctypes.c_int64()
     with ExportedBatch(record) as ex:
-        rc = lib().fdb_selftest_parquet_write(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+        if encodings is None:
+            rc = lib().fdb_selftest_parquet_write(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+        else:
+            rc = lib().fdb_selftest_parquet_write_encoded(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_enc,
+                                                          ctypes.byref(out), ctypes.byref(n))
     return _take_bytes(rc, out, n)
 
 
@@ -685,14 +715,20 @@ class ResidentBatch:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
-    def to_parquet(self, page_rows: int = 0, optional=None) -> bytes:
+    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None) -> bytes:
         """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, UNCOMPRESSED, data
         pages V1 of `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
-        False (required; refused for a column with NULLs) or True."""
+        False (required; refused for a column with NULLs) or True. `encodings`: None, a sequence per column or a dict by name of
+        None / "plain" (as without it) or "delta": an int64 / uint64 column written DELTA_BINARY_PACKED, its deltas, widths and pages
+        made on the device (fdb_batch_to_parquet_encoded) — what sorted timestamps ask for."""
         opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
         out, n = ctypes.c_void_p(), ctypes.c_int64()
-        rc = lib().fdb_batch_to_parquet(self.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+        if encodings is None:
+            rc = lib().fdb_batch_to_parquet(self.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+        else:
+            enc, n_enc = _parquet_encodings(encodings, self.column_names)
+            rc = lib().fdb_batch_to_parquet_encoded(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_enc, ctypes.byref(out), ctypes.byref(n))
         return _take_bytes(rc, out, n)
 
     @property

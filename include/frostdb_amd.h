@@ -560,6 +560,21 @@ FDB_API void fdb_bytes_free(uint8_t* bytes);
  * bit positions, word assembly): byte for byte the file fdb_batch_to_parquet writes for the record, and no GPU is touched — what makes
  * the file format checkable on a CPU-only machine, as fdb_selftest_merge_path does for the merge kernels. */
 FDB_API int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes);
+/* The same two calls with an encoding per column (≙ the `delta_binary_packed` struct tag and parquet.DeltaBinaryPacked of the reference's
+ * schemas, dynparquet/schema.go:429-430): a column asked to be DELTA_BINARY_PACKED is written in blocks of 128 deltas with 4 miniblocks
+ * of 32, per data page over the page's non-NULL values — deltas of the 64-bit patterns, wrapping; per block the signed minimum, per
+ * miniblock the bit length (0 … 64) of its largest delta − minimum; the last miniblock that holds a delta padded with zero bits,
+ * miniblocks that hold none with width byte 0 and no body; a page of one value is its header, a page of none `80 01 04 00 00` — and
+ * its chunk names DELTA_BINARY_PACKED (and RLE when optional) instead of PLAIN. Levels, null_count, optionality and page geometry are as
+ * above, and so is every other column: with n_encodings == 0 or all entries 0 the file is fdb_batch_to_parquet's, byte for byte. The
+ * deltas, widths and sizes are found on the device (fdb_pqdelta.hip: compaction of columns with NULLs, block survey, page walk) before
+ * the layout, and the pages encoded on the device after it. Refused before anything is launched: FDB_ERR_INVALID — n_encodings neither
+ * 0 nor the column count, an entry outside 0 … 1; FDB_ERR_UNSUPPORTED, naming the column — DELTA asked of a column that is not
+ * int64 / uint64 (a uint64 column is written as INT64 Int(64, unsigned), bits as they are). */
+/* encodings: per column 0 = as fdb_batch_to_parquet writes it, 1 = DELTA_BINARY_PACKED (int64 / uint64 columns);
+   n_encodings: 0 (all 0) or the batch's column count */
+FDB_API int fdb_batch_to_parquet_encoded(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_encoded(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes);
 
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry

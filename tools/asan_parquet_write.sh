@@ -1,8 +1,8 @@
 #!/bin/bash
 # Host-only memory-safety check of the Parquet writer's host half under AddressSanitizer + UBSan: options and column checks, layout
 # planning, the thrift compact writer, the dictionary page builder and the tail (frostdb_amd/csrc/fdb_pqwrite.cpp), and the host walk of
-# the survey and encode passes (fdb_pqwrite.h: the page geometry, bit positions and word assembly the kernels compile) over seeded
-# random records and options, with fdb_arrow.cpp's dictionary constructors.
+# the survey and encode passes (fdb_pqwrite.h: the page geometry, bit positions and word assembly the kernels compile) and of the
+# DELTA_BINARY_PACKED passes (fdb_pqdelta.h) over seeded random records and options, with fdb_arrow.cpp's dictionary constructors.
 # No GPU, no HIP, no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -1,8 +1,9 @@
 // Stand-alone driver of the host half of the Parquet writer for tools/asan_parquet_write.sh: column checks and options (pqw_columns),
 // the survey and encode walk over host arrays (pqw_survey_host / pqw_encode_host: the arithmetic of fdb_pqwrite.h that the kernels
 // compile), layout planning with the thrift writer and the dictionary page builder (pqw_layout) and the tail (pqw_finish) — over seeded
-// random records and options, every buffer sized exactly. What the walk wrote is read back with a bit reader of this file's own. No
-// GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
+// random records and options, every buffer sized exactly. Some int64 / uint64 columns are asked to be DELTA_BINARY_PACKED: the DELTA
+// passes' host walk (pqd_survey_host / pqd_encode_host: the arithmetic of fdb_pqdelta.h) sizes and writes their pages. What the walk
+// wrote is read back with a bit reader and a DELTA decoder of this file's own. No GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,6 +39,53 @@ static uint32_t read_bits(const uint8_t* p, uint64_t bit, uint32_t w) {
   return v;
 }
 
+static uint64_t read_varint(const uint8_t* p, size_t* at) {
+  uint64_t v = 0;
+  for (int shift = 0;; shift += 7) {
+    CHECK(shift < 70);
+    const uint8_t b = p[(*at)++];
+    v |= (uint64_t)(b & 0x7F) << (shift < 64 ? shift : 63);
+    if (b < 0x80) return v;
+  }
+}
+static int64_t unzigzag(uint64_t z) { return (int64_t)((z >> 1) ^ (0 - (z & 1))); }
+static uint64_t read_bits64(const uint8_t* p, uint64_t bit, uint32_t w) {
+  uint64_t v = 0;
+  for (uint32_t b = 0; b < w; b++) v |= (uint64_t)((p[(bit + b) >> 3] >> ((bit + b) & 7)) & 1) << b;
+  return v;
+}
+
+// A DELTA_BINARY_PACKED page of exactly `bytes` bytes decodes to `want`: blocks of 128 in 4 miniblocks, every miniblock as narrow as its
+// largest value allows, padding zero, no width and no body where no delta is.
+static void check_delta_page(const uint8_t* p, size_t bytes, const std::vector<uint64_t>& want) {
+  size_t at = 0;
+  CHECK(read_varint(p, &at) == 128);
+  CHECK(read_varint(p, &at) == 4);
+  const uint64_t count = read_varint(p, &at);
+  CHECK(count == want.size());
+  uint64_t prev = (uint64_t)unzigzag(read_varint(p, &at));
+  CHECK(prev == (count > 0 ? want[0] : 0));
+  for (uint64_t i = 1; i < count;) {
+    const uint64_t mn = (uint64_t)unzigzag(read_varint(p, &at));
+    const uint8_t* widths = p + at;
+    at += 4;
+    for (int m = 0; m < 4; m++) {
+      const uint32_t w = widths[m];
+      if (i >= count) { CHECK(w == 0); continue; }
+      CHECK(w <= 64 && at + 4 * (size_t)w <= bytes);
+      uint64_t mx = 0;
+      for (uint32_t j = 0; j < 32; j++) {
+        const uint64_t r = read_bits64(p + at, (uint64_t)j * w, w);
+        if (i < count) { prev += mn + r; CHECK(prev == want[i]); i++; mx = r > mx ? r : mx; }
+        else CHECK(r == 0);
+      }
+      CHECK(w == 0 ? mx == 0 : (mx >> (w - 1)) == 1);
+      at += 4 * (size_t)w;
+    }
+  }
+  CHECK(at == bytes);
+}
+
 static void one_record(uint64_t* seed, int round) {
   static const int64_t row_choices[] = {0, 1, 7, 63, 64, 65, 127, 128, 129, 1000, 4095, 4096, 4097, 9000};
   static const int32_t page_choices[] = {0, 64, 128, 4096, 8192, 65536};
@@ -47,7 +95,7 @@ static void one_record(uint64_t* seed, int round) {
   const size_t n_cols = 1 + rnd(seed) % 5;
   std::vector<Column> cols(n_cols);
   std::vector<PqwInput> in;
-  std::vector<int8_t> optional;
+  std::vector<int8_t> optional, encodings;
   for (size_t k = 0; k < n_cols; k++) {
     Column& c = cols[k];
     static const ColKind kinds[] = {ColKind::I64, ColKind::U64, ColKind::F64, ColKind::BOOL, ColKind::DICT, ColKind::DICT};
@@ -79,9 +127,16 @@ static void one_record(uint64_t* seed, int round) {
       o.values = rows > 0 ? c.idx.data() : nullptr;
     } else {
       c.v64.resize((size_t)rows);
-      for (int64_t r = 0; r < rows; r++) c.v64[(size_t)r] = c.kind == ColKind::BOOL ? 1 + (rnd(seed) & 1) : rnd(seed);
+      const int shape = (int)(rnd(seed) % 4);  // 0 any bits, 1 small steps, 2 constant, 3 steps of either sign around 2^63
+      uint64_t run = shape == 3 ? (1ull << 63) - 50 : rnd(seed);
+      for (int64_t r = 0; r < rows; r++) {
+        if (c.kind == ColKind::BOOL) c.v64[(size_t)r] = 1 + (rnd(seed) & 1);
+        else if (shape == 0 || c.kind == ColKind::F64) c.v64[(size_t)r] = rnd(seed);
+        else c.v64[(size_t)r] = run += shape == 1 ? rnd(seed) % 2000 : shape == 2 ? 0 : rnd(seed) % 101 - 50;
+      }
       o.values = rows > 0 ? c.v64.data() : nullptr;
     }
+    encodings.push_back((c.kind == ColKind::I64 || c.kind == ColKind::U64) && rnd(seed) % 3 != 0 ? 1 : 0);
     o.validity = c.bits.empty() ? nullptr : c.bits.data();
     in.push_back(std::move(o));
     optional.push_back(c.nulls > 0 ? (int8_t)((rnd(seed) & 1) ? 1 : -1) : (int8_t)((int)(rnd(seed) % 3) - 1));
@@ -93,15 +148,19 @@ static void one_record(uint64_t* seed, int round) {
   opt.optional = with_optional ? optional.data() : nullptr;
 
   int32_t pr = 0;
-  const std::vector<PqwColumn> pc = pqw_columns(in, rows, &opt, &pr);
+  const bool with_encodings = (round & 2) != 0 || (round & 1) == 0;  // (one round in four writes every column as ever)
+  const std::vector<PqwColumn> pc = with_encodings ? pqw_columns(in, rows, &opt, &pr, encodings.data(), (int32_t)n_cols) : pqw_columns(in, rows, &opt, &pr);
   CHECK(pr == (page_rows == 0 ? 65536 : page_rows) && pc.size() == n_cols);
   const FdbPqwGeom g = pqw_geometry(rows, pr, n_cols);
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
   pqw_survey_host(pc, g, &stats, &tile_base);
-  const PqwLayout L = pqw_layout(pc, g, stats);
+  PqdHost dh;
+  pqd_survey_host(pc, g, stats, tile_base, &dh);
+  const PqwLayout L = pqw_layout(pc, g, stats, dh.page_bytes);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(pc, g, L.out, tile_base, image.data());
+  pqd_encode_host(pc, g, stats, dh, L.delta_out, image.data());
   const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
   std::memcpy(file, image.data(), (size_t)L.body_bytes);
@@ -127,6 +186,18 @@ static void one_record(uint64_t* seed, int round) {
         for (uint32_t b = 0; b < fdb_pqw_level_bytes((uint32_t)(end - first)); b++) { CHECK(owner[po.levels_off + b] == 0); owner[po.levels_off + b] = 2; }
         for (int64_t r = first; r < first + (int64_t)fdb_pqw_level_bytes((uint32_t)(end - first)) * 8; r++)
           CHECK(read_bits(file + po.levels_off, (uint64_t)(r - first), 1) == (r < end && c.valid(r) ? 1u : 0u));
+      }
+      CHECK((pc[k].delta_slot >= 0) == (with_encodings && encodings[k] == 1));
+      if (pc[k].delta_slot >= 0) {  // the page's value bytes are the survey's count of them, and decode to the page's non-NULL values
+        CHECK(po.values_off == FDB_PQW_NONE);
+        const size_t dp = (size_t)pc[k].delta_slot * (size_t)g.n_pages + (size_t)p;
+        const uint64_t off = L.delta_out[dp], bytes = dh.page_bytes[dp];
+        for (uint64_t b = 0; b < bytes; b++) { CHECK(off + b < L.body_bytes && owner[off + b] == 0); owner[off + b] = 4; }
+        std::vector<uint64_t> want;
+        for (int64_t r = first; r < end; r++) if (pc[k].validity == nullptr || c.valid(r)) want.push_back(c.v64[(size_t)r]);
+        std::vector<uint8_t> exact(file + off, file + off + bytes);  // (sized exactly: a decoder that reads past the page is caught)
+        check_delta_page(exact.data(), exact.size(), want);
+        continue;
       }
       if (po.values_off == FDB_PQW_NONE) continue;
       const uint32_t w = pc[k].pq_kind == FDB_PQW_V64 ? 64 : pc[k].width;
@@ -162,6 +233,15 @@ static void refusals() {
   CHECK(code(fdb_parquet_write_options{64, 2, &required}) == FDB_ERR_INVALID);
   CHECK(code(fdb_parquet_write_options{64, 1, &required}) == FDB_ERR_INVALID);
   CHECK(code(fdb_parquet_write_options{64, 1, &bad}) == FDB_ERR_INVALID);
+  const fdb_parquet_write_options plain_opt{64, 0, nullptr};
+  const auto enc_code = [&](const int8_t* e, int32_t n) { try { pqw_columns(in, 8, &plain_opt, &pr, e, n); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const int8_t delta = 1, two = 2, both[2] = {1, 1};
+  CHECK(enc_code(&delta, 1) == FDB_OK && enc_code(nullptr, 0) == FDB_OK);
+  CHECK(enc_code(&two, 1) == FDB_ERR_INVALID && enc_code(both, 2) == FDB_ERR_INVALID && enc_code(nullptr, 1) == FDB_ERR_INVALID);
+  in[0].kind = ColKind::F64;
+  CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED);
+  in[0].kind = ColKind::BOOL;
+  CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED);
   in[0].kind = ColKind::OTHER;
   CHECK(code(fdb_parquet_write_options{64, 0, nullptr}) == FDB_ERR_UNSUPPORTED);
   in[0].kind = ColKind::DICT;

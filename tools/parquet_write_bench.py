@@ -12,9 +12,13 @@ of a compacted part is. In ONE process, medians of --reps passes after --warmup:
   arrow_write_ms    to_arrow() followed by pyarrow.parquet.write_table with matching options (one row group, UNCOMPRESSED, data pages
                     V1, dictionary encoding for the label columns only, no statistics): what a caller does at the parent commit;
                     export_ms is its to_arrow() part (--baseline-reps passes, default 3)
+With --delta the `timestamp` column is written DELTA_BINARY_PACKED (fdb_batch_to_parquet_encoded): the line's own figures — file_bytes,
+to_parquet_ms, the phases, among them delta_compact_ms / delta_survey_ms (block survey + page walk, with the wait for the tables) /
+delta_encode_ms — are then the DELTA call's, and the PLAIN call on the same record in the same process goes into the same line as
+plain_file_bytes, plain_to_parquet_ms, plain_to_parquet_min_ms / _max_ms (its spread over the repetitions: the yardstick) and plain_*_ms phases.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta] [--out FILE]
 """
 import argparse
 import io
@@ -37,6 +41,7 @@ from frostdb_amd import physicalplan as pp  # noqa: E402
 
 LABELS = [10, 50, 100, 500, 1000]
 PHASES = ["survey", "layout", "encode", "copy", "host tail"]
+DELTA_PHASES = ["delta compact", "delta survey", "delta encode"]
 
 
 def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
@@ -64,7 +69,7 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps):
+def profiled_phases(rb, page_rows, reps, encodings=None):
     """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
     os.environ["FDB_PROFILE"] = "1"
     sys.stderr.flush()
@@ -73,7 +78,7 @@ def profiled_phases(rb, page_rows, reps):
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -81,7 +86,7 @@ def profiled_phases(rb, page_rows, reps):
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES:
+    for phase in PHASES + DELTA_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = statistics.median(us) / 1e3 if us else None
     return out
@@ -94,28 +99,44 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--baseline-reps", type=int, default=3)
+    ap.add_argument("--delta", action="store_true", help="write `timestamp` DELTA_BINARY_PACKED; the PLAIN call goes into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     record = make_record(args.rows)
     rb = pp.ResidentBatch(record)
     del record
     try:
-        data = rb.to_parquet(page_rows=args.page_rows)
+        encodings = {"timestamp": "delta"} if args.delta else None
+        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings)
         file_bytes = len(data)
         md = pq.ParquetFile(io.BytesIO(data)).metadata
         assert md.num_rows == args.rows and md.num_row_groups == 1
+        if args.delta:
+            assert set(md.row_group(0).column(0).encodings) == {"DELTA_BINARY_PACKED"}
         del data
         import ctypes
         opts = pp.ParquetWriteOptions(args.page_rows, 0, None)
+        n_columns = len(rb.column_names)
+        enc = (ctypes.c_int8 * n_columns)(*([1] + [0] * (n_columns - 1)))
 
-        def c_call():
+        def c_call(delta=args.delta, want=file_bytes):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
-            rc = pp.lib().fdb_batch_to_parquet(rb.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
-            assert rc == 0 and n.value == file_bytes, pp.lib().fdb_last_error()
+            if delta:
+                rc = pp.lib().fdb_batch_to_parquet_encoded(rb.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_columns, ctypes.byref(out), ctypes.byref(n))
+            else:
+                rc = pp.lib().fdb_batch_to_parquet(rb.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+            assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
+        plain = {}
+        if args.delta:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+            plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
+            ms, every = median_ms(lambda: c_call(False, plain_bytes), args.reps, args.warmup)
+            ph = profiled_phases(rb, args.page_rows, args.reps)
+            plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
+            plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
-        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows), args.reps, 1)
-        phases = profiled_phases(rb, args.page_rows, args.reps)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps, encodings)
 
         dev = torch.empty(file_bytes, dtype=torch.uint8, device="cuda")
         host = torch.empty(file_bytes, dtype=torch.uint8).pin_memory()
@@ -148,6 +169,10 @@ def main():
             "arrow_write_ms": r3(arrow_write_ms), "export_ms": r3(statistics.median(export_times[1:])), "arrow_file_bytes": baseline_bytes[0],
             "arrow_over_device": round(arrow_write_ms / to_parquet_ms, 2), "reps": args.reps, "warmup": args.warmup, "baseline_reps": args.baseline_reps,
             "date": time.strftime("%Y-%m-%d")}
+    if args.delta:
+        line.update({"delta": ["timestamp"], "to_parquet_max_ms": r3(max(to_parquet_all)), "delta_compact_ms": r3(phases["delta compact"]), "delta_survey_ms": r3(phases["delta survey"]),
+                     "delta_encode_ms": r3(phases["delta encode"])})
+        line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
     if args.out:
