@@ -25,6 +25,16 @@
 // fdb_pqdelta.hip run — compaction of the columns with a bitmap, block survey, page walk — and the page sizes come back with the survey's
 // table, in the same wait; after the layout the DELTA encoder writes the pages' value bytes into the same image, beside the encode pass,
 // which for such a column writes the definition levels only. The host walk has its counterparts (pqd_survey_host / pqd_encode_host).
+//
+// fdb_batch_to_parquet_compressed: a column may be asked to be SNAPPY as well (the rule is spelled out in fdb_pqsnappy.h). Steps 1 – 3 are
+// then what they were, but the image they fill is a STAGING image in HBM, laid out as the uncompressed file; after them
+//   4. the host's few bytes inside the bodies of the pages to be compressed are uploaded and placed (a body has to be whole),
+//   5. every fragment of every such body is compressed into its slot of scratch, the sizes are summed per page, and only those come back,
+//   6. the host lays the file out again (pqw_layout with the sizes; dictionary pages it compresses itself), and ONE gather launch moves
+//      the fragments' elements and the chunks of the uncompressed columns into the final image,
+//   7. which is what is copied out; headers, block preambles, dictionary pages and the footer are the host's, as before.
+// Device memory: staging + scratch + final image, about 3 × the file body, all of it the call's and freed on every path. Without a
+// compressed column nothing of this runs: the path, its launches, allocations and copies are those of fdb_batch_to_parquet_encoded.
 #include "fdb_pqwrite_host.h"
 
 #include <algorithm>
@@ -75,12 +85,12 @@ enum { PT_BOOLEAN = 0, PT_INT64 = 2, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6 };
 enum { ENC_PLAIN = 0, ENC_RLE = 3, ENC_DELTA_BINARY_PACKED = 5, ENC_RLE_DICTIONARY = 8 };
 enum { PAGE_DATA = 0, PAGE_DICTIONARY = 2 };
 
-std::string page_header(int type, int64_t body, int64_t num_values, int encoding) {
+std::string page_header(int type, int64_t body, int64_t compressed, int64_t num_values, int encoding) {
   Thrift t;
   t.open();
   t.i32(1, type);
   t.i32(2, (int32_t)body);
-  t.i32(3, (int32_t)body);
+  t.i32(3, (int32_t)compressed);
   if (type == PAGE_DATA) {
     t.open(5);
     t.i32(1, (int32_t)num_values); t.i32(2, encoding); t.i32(3, ENC_RLE); t.i32(4, ENC_RLE);
@@ -97,7 +107,7 @@ std::string page_header(int type, int64_t body, int64_t num_values, int encoding
 std::string varint_bytes(uint64_t v) { Thrift t; t.varint(v); return t.out; }
 std::string le32(uint32_t v) { std::string s(4, '\0'); std::memcpy(&s[0], &v, 4); return s; }
 
-struct ChunkMeta { int64_t dict_off = -1, data_off = 0, bytes = 0, nulls = 0; };
+struct ChunkMeta { int64_t dict_off = -1, data_off = 0, bytes = 0, raw_bytes = 0, nulls = 0; };  // bytes: as stored; raw_bytes: the bodies uncompressed (headers in both)
 
 std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMeta>& chunks, int64_t rows, int64_t body_bytes) {
   Thrift t;
@@ -129,9 +139,9 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     t.list(2, Thrift::T_I32, 1 + (c.optional ? 1 : 0) + (dict ? 1 : 0));  // (RLE: the definition levels, which a required column does not have)
     t.zigzag(c.delta_slot >= 0 ? ENC_DELTA_BINARY_PACKED : ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
     t.list(3, Thrift::T_BINARY, 1); t.str(c.name);
-    t.i32(4, 0);  // UNCOMPRESSED
+    t.i32(4, c.codec);  // 0 UNCOMPRESSED, 1 SNAPPY
     t.i64(5, rows);
-    t.i64(6, m.bytes);
+    t.i64(6, m.raw_bytes);
     t.i64(7, m.bytes);
     t.i64(9, m.data_off);
     if (m.dict_off >= 0) t.i64(11, m.dict_off);
@@ -139,7 +149,9 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     t.close();
     t.close();
   }
-  t.i64(2, body_bytes - 4);
+  int64_t raw_bytes = 0;
+  for (const ChunkMeta& m : chunks) raw_bytes += m.raw_bytes;
+  t.i64(2, raw_bytes);  // total_byte_size: uncompressed
   t.i64(3, rows);
   t.i64(5, 4);
   t.i64(6, body_bytes - 4);
@@ -198,7 +210,7 @@ void pqw_free_bytes(uint8_t* bytes) {
 
 // Everything that can refuse the record, before anything is launched.
 std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows, const int8_t* encodings,
-                                   int32_t n_encodings) {
+                                   int32_t n_encodings, const int8_t* codecs, int32_t n_codecs) {
   int64_t pr = opt != nullptr ? opt->page_rows : 0;
   if (pr == 0) pr = 65536;
   if (pr < 64 || pr > (1 << 24) || pr % 64 != 0)
@@ -210,12 +222,17 @@ std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows
     throw Error(FDB_ERR_INVALID, "parquet write: `optional` has " + std::to_string(n_opt) + " entries, the record " + std::to_string(in.size()) + " columns");
   if (n_encodings != 0 && (n_encodings != (int32_t)in.size() || encodings == nullptr))
     throw Error(FDB_ERR_INVALID, "parquet write: `encodings` has " + std::to_string(n_encodings) + " entries, the record " + std::to_string(in.size()) + " columns");
+  if (n_codecs != 0 && (n_codecs != (int32_t)in.size() || codecs == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: `codecs` has " + std::to_string(n_codecs) + " entries, the record " + std::to_string(in.size()) + " columns");
+  for (int32_t k = 0; k < n_codecs; k++)
+    if (codecs[k] < 0 || codecs[k] > 1) throw Error(FDB_ERR_INVALID, "parquet write: codecs[" + std::to_string(k) + "] is " + std::to_string((int)codecs[k]) + " (0 UNCOMPRESSED, 1 SNAPPY)");
   int delta_slots = 0;
   std::vector<PqwColumn> cols;
   for (size_t k = 0; k < in.size(); k++) {
     const PqwInput& c = in[k];
     PqwColumn o;
     o.name = c.name;
+    o.codec = n_codecs != 0 ? (int)codecs[k] : 0;
     switch (c.kind) {
       case ColKind::I64: o.pq_kind = FDB_PQW_V64; o.physical = PT_INT64; break;
       case ColKind::U64: o.pq_kind = FDB_PQW_V64; o.physical = PT_INT64; o.is_u64 = true; break;
@@ -281,10 +298,40 @@ void PqwLayout::put(uint64_t off, const std::string& s) {
   blob += s;
 }
 
-PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes) {
+void PqwLayout::put_body(uint64_t off, const std::string& s) {
+  if (s.empty()) return;
+  body_pieces.push_back(Piece{off, body_blob.size(), s.size()});
+  body_blob += s;
+}
+
+size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols) {
+  size_t n = 0;
+  for (const PqwColumn& c : cols) n += c.codec != 0;
+  return n;
+}
+
+std::string pqs_block_host(const unsigned char* body, size_t n) {
+  std::string block = varint_bytes(n);
+  std::vector<uint32_t> table(FDB_PQS_TABLE);
+  std::vector<unsigned char> out(fdb_pqs_bound(FDB_PQS_FRAGMENT));
+  for (size_t at = 0; at < n; at += FDB_PQS_FRAGMENT) {
+    const uint32_t len = (uint32_t)std::min<size_t>(FDB_PQS_FRAGMENT, n - at);
+    block.append((const char*)out.data(), fdb_pqs_compress_fragment_host(body + at, len, table.data(), out.data()));
+  }
+  return block;
+}
+
+PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes,
+                     const std::vector<uint32_t>* page_elements) {
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
   if (delta_bytes.size() != pqw_delta_columns(cols) * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
+  if (page_elements != nullptr && page_elements->size() != pqw_compressed_columns(cols) * (size_t)g.n_pages)
+    throw Error(FDB_ERR_STATE, "parquet write: the table of compressed page sizes does not match the record");
+  const bool final_form = page_elements != nullptr;  // else: every page as it is before compression — the file of a record without codecs, the staging image of one with
+  size_t next_compressed = 0;
   PqwLayout L;
+  L.chunk_off.assign(cols.size(), 0);
+  L.chunk_len.assign(cols.size(), 0);
   L.delta_out.assign(delta_bytes.size(), FDB_PQW_NONE);
   L.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
   uint64_t cur = 0;
@@ -295,12 +342,15 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
     const PqwColumn& c = cols[k];
     ChunkMeta& m = chunks[k];
     const uint64_t chunk_start = cur;
+    const bool squeeze = final_form && c.codec != 0;  // this chunk's pages are written as Snappy blocks
     if (c.pq_kind == FDB_PQW_INDEX) {
       const std::string body = dictionary_body(*c.dict);
-      const std::string hdr = page_header(PAGE_DICTIONARY, (int64_t)body.size(), (int64_t)c.entries, ENC_PLAIN);
+      const std::string stored = squeeze ? pqs_block_host((const unsigned char*)body.data(), body.size()) : std::string();  // (host bytes already: the header's walk)
+      const std::string hdr = page_header(PAGE_DICTIONARY, (int64_t)body.size(), (int64_t)(squeeze ? stored.size() : body.size()), (int64_t)c.entries, ENC_PLAIN);
       m.dict_off = (int64_t)cur;
+      m.raw_bytes += (int64_t)(hdr.size() + body.size());
       L.put(cur, hdr); cur += hdr.size();
-      L.put(cur, body); cur += body.size();
+      L.put(cur, squeeze ? stored : body); cur += squeeze ? stored.size() : body.size();
     }
     m.data_off = (int64_t)cur;
     int64_t valid = 0;
@@ -347,16 +397,37 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
         }
       }
       const uint64_t body = pre.size() + level_payload + vpre.size() + value_payload;
-      const std::string hdr = page_header(PAGE_DATA, (int64_t)body, n, encoding);
+      if (squeeze) {  // header, the block's preamble, then the elements the compressor made of the body
+        const uint64_t elements = (*page_elements)[next_compressed++];
+        if (elements > (uint64_t)fdb_pqs_fragments(body) * fdb_pqs_bound(FDB_PQS_FRAGMENT) || (body > 0) != (elements > 0))
+          throw Error(FDB_ERR_STATE, "parquet write: the compressor sizes a page body of " + std::to_string(body) + " bytes at " + std::to_string(elements) + " (" + c.name + ")");
+        const std::string preamble = varint_bytes(body);
+        const std::string hdr = page_header(PAGE_DATA, (int64_t)body, (int64_t)(preamble.size() + elements), n, encoding);
+        m.raw_bytes += (int64_t)(hdr.size() + body);
+        L.put(cur, hdr + preamble); cur += hdr.size() + preamble.size();
+        L.pages.push_back(PqwLayout::Page{cur, body});
+        cur += elements;
+        continue;
+      }
+      const std::string hdr = page_header(PAGE_DATA, (int64_t)body, (int64_t)body, n, encoding);
+      m.raw_bytes += (int64_t)(hdr.size() + body);
       FdbPqwPageOut& o = L.out[k * (size_t)g.n_pages + (size_t)p];
-      L.put(cur, hdr + pre); cur += hdr.size() + pre.size();
+      if (c.codec == 0) { L.put(cur, hdr + pre); cur += hdr.size() + pre.size(); }
+      else {  // the staging image of a page to be compressed: the host's bytes inside the body are placed on their own, before the compressor runs
+        cur += hdr.size();
+        L.pages.push_back(PqwLayout::Page{cur, body});
+        L.put_body(cur, pre); cur += pre.size();
+      }
       if (level_payload > 0) { o.levels_off = cur; cur += level_payload; }
-      L.put(cur, vpre); cur += vpre.size();
+      if (c.codec == 0) L.put(cur, vpre); else L.put_body(cur, vpre);
+      cur += vpre.size();
       if (c.delta_slot >= 0) { L.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
       else if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
     }
     m.bytes = (int64_t)(cur - chunk_start);
     m.nulls = g.rows - valid;
+    L.chunk_off[k] = chunk_start;
+    L.chunk_len[k] = cur - chunk_start;
   }
   L.body_bytes = cur;
   L.footer = footer(cols, chunks, g.rows, (int64_t)cur);
@@ -545,7 +616,8 @@ void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
   }
 }
 
-void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings) {
+void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
+                            const int8_t* codecs, int32_t n_codecs) {
   // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
   const size_t rows = (size_t)view.rows;
   std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
@@ -590,7 +662,7 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     in.push_back(std::move(o));
   }
   int32_t page_rows = 0;
-  const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings);
+  const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
   const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
@@ -598,19 +670,45 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
   PqdHost delta;
   pqd_survey_host(cols, g, stats, tile_base, &delta);
   const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes);
-  const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(cols, g, L.out, tile_base, image.data());
   pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
+  if (pqw_compressed_columns(cols) == 0) {
+    const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+    uint8_t* file = pqw_alloc_bytes(file_bytes, false);
+    std::memcpy(file, image.data(), (size_t)L.body_bytes);
+    pqw_finish(L, file);
+    *bytes = file;
+    *n_bytes = (int64_t)file_bytes;
+    return;
+  }
+  // `image` is the staging image: the bodies made whole, every page compressed fragment by fragment, the file laid out again, the
+  // elements and the uncompressed chunks moved to where it wants them — the passes of fdb_pqsnappy.hip, walked
+  for (const PqwLayout::Piece& p : L.body_pieces) std::memcpy(image.data() + p.off, L.body_blob.data() + p.pos, p.len);
+  std::vector<uint32_t> page_elements(L.pages.size(), 0), table(FDB_PQS_TABLE);
+  std::vector<std::string> elements(L.pages.size());
+  std::vector<unsigned char> slot(fdb_pqs_slot_bytes());
+  for (size_t i = 0; i < L.pages.size(); i++) {
+    for (uint64_t at = 0; at < L.pages[i].body; at += FDB_PQS_FRAGMENT) {
+      const uint32_t len = (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, L.pages[i].body - at);
+      elements[i].append((const char*)slot.data(), fdb_pqs_compress_fragment_host(image.data() + L.pages[i].off + at, len, table.data(), slot.data()));
+    }
+    page_elements[i] = (uint32_t)elements[i].size();
+  }
+  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements);
+  const size_t file_bytes = (size_t)F.body_bytes + F.footer.size() + 8;
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
-  std::memcpy(file, image.data(), (size_t)L.body_bytes);
-  pqw_finish(L, file);
+  for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
+  for (size_t k = 0; k < cols.size(); k++)
+    if (cols[k].codec == 0) std::memcpy(file + F.chunk_off[k], image.data() + L.chunk_off[k], (size_t)L.chunk_len[k]);
+  pqw_finish(F, file);
   *bytes = file;
   *n_bytes = (int64_t)file_bytes;
 }
 
 #ifndef FDB_PQWRITE_HOST_ONLY
-void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings) {
+void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
+                      const int8_t* codecs, int32_t n_codecs) {
   std::vector<PqwInput> in;
   for (const DevColumn& c : b.cols) {
     PqwInput o;
@@ -618,12 +716,13 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     in.push_back(std::move(o));
   }
   int32_t page_rows = 0;
-  const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings);
+  const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
   const FdbPqwGeom g = pqw_geometry(b.rows, page_rows, cols.size());
-  const size_t n_delta = pqw_delta_columns(cols);
+  const size_t n_delta = pqw_delta_columns(cols), n_compressed = pqw_compressed_columns(cols);
   struct Bytes { uint8_t* p = nullptr; ~Bytes() { pqw_free_bytes(p); } } file;
-  if (b.rows == 0 || cols.empty()) {  // nothing for the device to do
-    const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}));
+  if (b.rows == 0 || cols.empty()) {  // nothing for the device to do (no data page: the dictionary pages are the host's, compressed or not)
+    const std::vector<uint32_t> no_pages;
+    const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}), {}, n_compressed > 0 ? &no_pages : nullptr);
     const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
     file.p = pqw_alloc_bytes(file_bytes, false);
     pqw_finish(L, file.p);
@@ -631,7 +730,7 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     return;
   }
   PhaseTimer pt;  // FDB_PROFILE=1: the passes timed apart (the encode pass is then waited for on its own)
-  struct Image { int device; void* p = nullptr; ~Image() { if (p != nullptr) device_pool_free(device, p); } } image{b.device};  // (before the scope: freed after its wait)
+  struct Image { int device; void* p = nullptr; ~Image() { if (p != nullptr) device_pool_free(device, p); } } image{b.device}, scratch{b.device}, final_image{b.device};  // (before the scope: freed after its wait; the last two: compressed columns only)
   CallScope cs(b.device);
   hipStream_t stream = cs.ctx->stream;
   DrainOnUnwind drain{stream};
@@ -694,12 +793,73 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     hip_check(fdb_launch_pqd_encode(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_delta_out, (unsigned char*)image.p, stream), "parquet write: DELTA encode launch");
     if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta encode"); }
   }
-  file.p = pqw_alloc_bytes(file_bytes, true);
-  cs.ctx->copy_out_parallel(file.p, image.p, (size_t)L.body_bytes);
+  if (n_compressed == 0) {
+    file.p = pqw_alloc_bytes(file_bytes, true);
+    cs.ctx->copy_out_parallel(file.p, image.p, (size_t)L.body_bytes);
+    pt.mark("pqwrite copy");
+    pqw_finish(L, file.p);
+    pt.mark("pqwrite host tail");
+    *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
+    return;
+  }
+  // `image` is the staging image. The host's bytes inside the bodies go in, every fragment is compressed into its slot of scratch, the
+  // sizes are summed per page and come back; the file is laid out again, and one gather fills the final image, which is what crosses
+  // the link.
+  const auto upload = [&](const void* host, size_t n, const char* what) {
+    void* d = cs.alloc(std::max<size_t>(n, 8));
+    if (n > 0) hip_check(hipMemcpyAsync(d, host, n, hipMemcpyHostToDevice, stream), what);
+    return d;
+  };
+  std::vector<FdbPqsRange> pieces;
+  for (const PqwLayout::Piece& p : L.body_pieces) pieces.push_back(FdbPqsRange{(uint64_t)p.pos, p.off, (uint32_t)p.len, 0});
+  std::vector<FdbPqsPage> pages;
+  std::vector<FdbPqsFrag> frags;
+  for (const PqwLayout::Page& pg : L.pages) {
+    pages.push_back(FdbPqsPage{(uint32_t)frags.size(), fdb_pqs_fragments(pg.body)});
+    for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT)
+      frags.push_back(FdbPqsFrag{pg.off + at, (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at), (uint32_t)(pages.size() - 1)});
+  }
+  if (frags.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 fragments to compress");
+  scratch.p = device_pool_alloc(b.device, std::max<size_t>(frags.size(), 1) * fdb_pqs_slot_bytes());
+  const unsigned char* d_blob = (const unsigned char*)upload(L.body_blob.data(), L.body_blob.size(), "hipMemcpyAsync(page body pieces)");
+  const FdbPqsRange* d_pieces = (const FdbPqsRange*)upload(pieces.data(), pieces.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(page body piece table)");
+  const FdbPqsFrag* d_frags = (const FdbPqsFrag*)upload(frags.data(), frags.size() * sizeof(FdbPqsFrag), "hipMemcpyAsync(fragment table)");
+  const FdbPqsPage* d_pages = (const FdbPqsPage*)upload(pages.data(), pages.size() * sizeof(FdbPqsPage), "hipMemcpyAsync(compressed page table)");
+  uint32_t* d_frag_bytes = (uint32_t*)cs.alloc(std::max<size_t>(frags.size(), 1) * 4);
+  uint32_t* d_frag_off = (uint32_t*)cs.alloc(std::max<size_t>(frags.size(), 1) * 4);
+  uint32_t* d_page_elements = (uint32_t*)cs.alloc(std::max<size_t>(pages.size(), 1) * 4);
+  std::vector<uint32_t> page_elements(pages.size(), 0);
+  hip_check(fdb_launch_pqs_place(d_pieces, (int32_t)pieces.size(), d_blob, (unsigned char*)image.p, stream), "parquet write: body piece launch");
+  hip_check(fdb_launch_pqs_compress(d_frags, (int32_t)frags.size(), (const unsigned char*)image.p, (unsigned char*)scratch.p, d_frag_bytes, stream), "parquet write: compress launch");
+  if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite compress"); }
+  hip_check(fdb_launch_pqs_scan(d_pages, (int32_t)pages.size(), d_frag_bytes, d_frag_off, d_page_elements, stream), "parquet write: compressed size scan launch");
+  if (!pages.empty()) hip_check(hipMemcpyAsync(page_elements.data(), d_page_elements, pages.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(compressed page sizes)");
+  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+  pt.mark("pqwrite scan");
+  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements);
+  const size_t out_bytes = (size_t)F.body_bytes + F.footer.size() + 8;
+  pt.mark("pqwrite final layout");
+  std::vector<uint64_t> page_dst(F.pages.size());
+  for (size_t i = 0; i < F.pages.size(); i++) page_dst[i] = F.pages[i].off;
+  std::vector<FdbPqsRange> ranges;  // the chunks of the uncompressed columns, in pieces a workgroup moves at a time
+  for (size_t k = 0; k < cols.size(); k++) {
+    if (cols[k].codec != 0) continue;
+    for (uint64_t at = 0; at < L.chunk_len[k]; at += FDB_PQS_COPY_PIECE)
+      ranges.push_back(FdbPqsRange{L.chunk_off[k] + at, F.chunk_off[k] + at, (uint32_t)std::min<uint64_t>(FDB_PQS_COPY_PIECE, L.chunk_len[k] - at), 0});
+  }
+  if (ranges.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 pieces to move");
+  const uint64_t* d_page_dst = (const uint64_t*)upload(page_dst.data(), page_dst.size() * 8, "hipMemcpyAsync(compressed page offsets)");
+  const FdbPqsRange* d_ranges = (const FdbPqsRange*)upload(ranges.data(), ranges.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(chunk piece table)");
+  final_image.p = device_pool_alloc(b.device, align_up((size_t)F.body_bytes + 8, 256));
+  hip_check(fdb_launch_pqs_gather(d_frags, (int32_t)frags.size(), d_frag_bytes, d_frag_off, d_page_dst, (const unsigned char*)scratch.p, d_ranges, (int32_t)ranges.size(),
+                                  (const unsigned char*)image.p, (unsigned char*)final_image.p, stream), "parquet write: gather launch");
+  if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite gather"); }
+  file.p = pqw_alloc_bytes(out_bytes, true);
+  cs.ctx->copy_out_parallel(file.p, final_image.p, (size_t)F.body_bytes);
   pt.mark("pqwrite copy");
-  pqw_finish(L, file.p);
+  pqw_finish(F, file.p);
   pt.mark("pqwrite host tail");
-  *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
+  *bytes = file.p; *n_bytes = (int64_t)out_bytes; file.p = nullptr;
 }
 #endif
 

@@ -9,6 +9,7 @@
 
 #include "fdb_arrow.h"
 #include "fdb_pqdelta.h"
+#include "fdb_pqsnappy.h"
 #include "fdb_pqwrite.h"
 #ifndef FDB_PQWRITE_HOST_ONLY
 #include "fdb_plan.h"
@@ -34,6 +35,7 @@ struct PqwColumn {
   int physical = 0;              // parquet Type
   bool is_u64 = false, utf8 = false, optional = false;
   int delta_slot = -1;            // >= 0: written DELTA_BINARY_PACKED, and its place among the columns that are (the tables of fdb_pqdelta.h)
+  int codec = 0;                  // parquet CompressionCodec of the chunk's pages: 0 UNCOMPRESSED, 1 SNAPPY
   uint32_t width = 0;
   uint64_t entries = 0;
   const HostDict* dict = nullptr;
@@ -52,16 +54,35 @@ struct PqwLayout {
   uint64_t body_bytes = 0;       // PAR1 + column chunks: what the image holds; the footer starts here
   std::string footer;
   void put(uint64_t off, const std::string& s);
+  // With compressed columns the file is laid out twice — as it is before compression (the staging image) and as it is written — and
+  // both layouts list the data pages of the compressed columns in the same order: in the staging layout `off` / `body` are where a
+  // page's body starts and how long it is, in the final one where the elements of its Snappy block go. `body_pieces` (of `body_blob`):
+  // the host's bytes inside those bodies, which have to be in the staging image before the compressor reads it. chunk_off / chunk_len:
+  // every column's chunk, which for an uncompressed column moves from one image to the other as it is.
+  struct Page { uint64_t off, body; };
+  std::vector<Page> pages;
+  std::string body_blob;
+  std::vector<Piece> body_pieces;
+  std::vector<uint64_t> chunk_off, chunk_len;
+  void put_body(uint64_t off, const std::string& s);
 };
 
 // Options and columns checked, every refusal made (FDB_ERR_INVALID / FDB_ERR_UNSUPPORTED): nothing has been launched yet. `encodings`:
-// per column 0 (as ever) or 1 (DELTA_BINARY_PACKED; I64 and U64 columns only), n_encodings 0 or the column count.
+// per column 0 (as ever) or 1 (DELTA_BINARY_PACKED; I64 and U64 columns only), n_encodings 0 or the column count. `codecs`: per column
+// 0 (UNCOMPRESSED) or 1 (SNAPPY), n_codecs 0 or the column count.
 std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows,
-                                   const int8_t* encodings = nullptr, int32_t n_encodings = 0);
+                                   const int8_t* encodings = nullptr, int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0);
 size_t pqw_delta_columns(const std::vector<PqwColumn>& cols);
+size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols);
+// The Snappy block of `n` bytes: the preamble and every fragment's elements, by the host walk of fdb_pqsnappy.h.
+std::string pqs_block_host(const unsigned char* body, size_t n);
 FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
 // `delta_bytes`[delta_slot × n_pages + page]: the value bytes of a DELTA page, as the block survey found them.
-PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes = {});
+// `page_elements` == nullptr: every page as it is before compression, whatever the columns' codecs — the file itself when no column has
+// one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of the elements of the
+// page's Snappy block (the preamble not counted), as the compressor found them.
+PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes = {},
+                     const std::vector<uint32_t>* page_elements = nullptr);
 // Fills the holes of `file` (body_bytes + footer + 8 bytes long, the payloads in place) and appends footer, length and magic.
 void pqw_finish(const PqwLayout& L, uint8_t* file);
 void pqw_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, std::vector<FdbPqwPageStat>* stats, std::vector<uint32_t>* tile_base);
@@ -86,9 +107,10 @@ uint8_t* pqw_alloc_bytes(size_t n, bool pinned);
 void pqw_free_bytes(uint8_t* bytes);
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr,
-                            int32_t n_encodings = 0);
+                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0);
 #ifndef FDB_PQWRITE_HOST_ONLY
-void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr, int32_t n_encodings = 0);
+void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr, int32_t n_encodings = 0,
+                      const int8_t* codecs = nullptr, int32_t n_codecs = 0);
 #endif
 
 }  // namespace fdb

@@ -170,6 +170,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_parquet_write.argtypes = [vp, vp, vp, P(vp), P(i64)]
     L.fdb_batch_to_parquet_encoded.argtypes = [vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
     L.fdb_selftest_parquet_write_encoded.argtypes = [vp, vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
+    L.fdb_batch_to_parquet_compressed.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
+    L.fdb_selftest_parquet_write_compressed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
     L.fdb_bytes_free.restype = None
     _lib = L
@@ -366,6 +368,29 @@ def _parquet_encodings(encodings, names):
     return (ctypes.c_int8 * max(1, len(wanted)))(*[PARQUET_ENCODINGS[e] for e in wanted]), len(wanted)
 
 
+PARQUET_WRITE_CODECS = {None: 0, "uncompressed": 0, "snappy": 1}
+
+
+def _parquet_codecs(compression, names):
+    """`compression`: "snappy" (every column), a sequence with one entry per column or a dict by column name; an entry is None /
+    "uncompressed" or "snappy". Returns the int8 array and its length."""
+    if isinstance(compression, str):
+        wanted = [compression] * len(names)
+    elif isinstance(compression, dict):
+        unknown = [n for n in compression if n not in names]
+        if unknown:
+            _raise(FDB_ERR_INVALID, "parquet write: `compression` names no column of the record: %s" % unknown[0])
+        wanted = [compression.get(n) for n in names]
+    else:
+        wanted = list(compression)
+        if not wanted and names:  # (an empty array would read as "every column uncompressed" on the C side)
+            _raise(FDB_ERR_INVALID, "parquet write: `codecs` has 0 entries, the record %d columns" % len(names))
+    for e in wanted:
+        if not (e is None or isinstance(e, str)) or e not in PARQUET_WRITE_CODECS:
+            _raise(FDB_ERR_INVALID, "parquet write: unknown codec %r (None, 'uncompressed' or 'snappy')" % (e,))
+    return (ctypes.c_int8 * max(1, len(wanted)))(*[PARQUET_WRITE_CODECS[e] for e in wanted]), len(wanted)
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -375,16 +400,21 @@ def _take_bytes(rc, out, n) -> bytes:
         lib().fdb_bytes_free(out.value)
 
 
-def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None) -> bytes:
-    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings)`` writes, byte for byte, made without a device
-    (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded): the same layout, headers and footer, the kernels
-    replaced by a host walk of the code they compile."""
+def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None) -> bytes:
+    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression)`` writes, byte for byte, made
+    without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
+    fdb_selftest_parquet_write_compressed): the same layout, headers and footer, the kernels replaced by a host walk of the code they
+    compile."""
     names = list(record.schema.names)
     opts, _keep = _parquet_write_options(page_rows, optional, names)
     enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
     out, n = ctypes.c_void_p(), ctypes.c_int64()
     with ExportedBatch(record) as ex:
-        if encodings is None:
+        if compression is not None:
+            codecs, n_codecs = _parquet_codecs(compression, names)
+            rc = lib().fdb_selftest_parquet_write_compressed(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
+                                                             n_enc, ctypes.cast(codecs, ctypes.c_void_p), n_codecs, ctypes.byref(out), ctypes.byref(n))
+        elif encodings is None:
             rc = lib().fdb_selftest_parquet_write(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
         else:
             rc = lib().fdb_selftest_parquet_write_encoded(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_enc,
@@ -715,16 +745,25 @@ class ResidentBatch:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
-    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None) -> bytes:
-        """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, UNCOMPRESSED, data
-        pages V1 of `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
+    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None) -> bytes:
+        """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, data pages V1 of
+        `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
         False (required; refused for a column with NULLs) or True. `encodings`: None, a sequence per column or a dict by name of
         None / "plain" (as without it) or "delta": an int64 / uint64 column written DELTA_BINARY_PACKED, its deltas, widths and pages
-        made on the device (fdb_batch_to_parquet_encoded) — what sorted timestamps ask for."""
+        made on the device (fdb_batch_to_parquet_encoded) — what sorted timestamps ask for. `compression`: None (UNCOMPRESSED),
+        "snappy" (every column), a sequence per column or a dict by name of None / "uncompressed" / "snappy": every page of such a
+        column — dictionary page and data pages — is written as a Snappy block, compressed on the device in fragments of 32 KiB
+        (fdb_batch_to_parquet_compressed), and only the compressed file crosses the link; for the length of the call the device holds
+        about three times the file body. DELTA and SNAPPY go together."""
         opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
         out, n = ctypes.c_void_p(), ctypes.c_int64()
-        if encodings is None:
+        if compression is not None:
+            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
+            codecs, n_codecs = _parquet_codecs(compression, self.column_names)
+            rc = lib().fdb_batch_to_parquet_compressed(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc, ctypes.cast(codecs, ctypes.c_void_p),
+                                                       n_codecs, ctypes.byref(out), ctypes.byref(n))
+        elif encodings is None:
             rc = lib().fdb_batch_to_parquet(self.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
         else:
             enc, n_enc = _parquet_encodings(encodings, self.column_names)

@@ -575,6 +575,30 @@ FDB_API int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSch
    n_encodings: 0 (all 0) or the batch's column count */
 FDB_API int fdb_batch_to_parquet_encoded(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_encoded(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes);
+/* The same two calls with a compression codec per column as well (≙ the `compression` of a FrostDB column's storage layout,
+ * dynparquet/schema.go:434-443, :571-580): every page of a column asked to be SNAPPY — its dictionary page and all its data pages — is
+ * written as ONE Snappy block: PageHeader.uncompressed_page_size is the body as the calls above write it (level length + levels +
+ * values, or the DELTA bytes), compressed_page_size the block, ColumnMetaData.codec is SNAPPY, total_uncompressed_size and
+ * total_compressed_size each count the page headers, and every page offset follows the compressed sizes. The block is the varint of the
+ * body's length, then the elements of the body's FRAGMENTS of 32 768 bytes (FDB_PQS_FRAGMENT) in order, each compressed on its own: no
+ * copy reaches before its fragment's first byte, so no offset passes 32 767 — within the 65 472 that fdb_snappy_decode_pages reaches back
+ * on the device — and a body of 0 bytes is the block `00`. Inside a fragment (the rule is spelled out in fdb_pqsnappy.h): windows of 64
+ * positions; a position is held against the nearest earlier position of its window, at most 16 back, with the same 4 bytes, else against the one a hash
+ * table of the positions before the window holds (the largest under each hash); the lowest position with a match wins, the match is
+ * extended to its end, literals are tagged in 1 / 2 / 3 bytes, copies cut into elements of at most 64 bytes, the 1-byte-offset form
+ * where length 4 … 11 and offset < 2 048 allow it. A page never exceeds 32 + U + U/6 bytes for a body of U. DELTA and SNAPPY go together
+ * on one column. With n_codecs == 0 or all entries 0 the file is fdb_batch_to_parquet_encoded's, byte for byte, made by the same path:
+ * no further launch, allocation or copy. Otherwise the uncompressed file body is encoded into a staging image in HBM, the host's few
+ * bytes inside the page bodies are uploaded and placed, the fragments are compressed on the device (fdb_pqsnappy.hip, one wave each)
+ * into scratch of Snappy's bound, the sizes are summed per page on the device and only those come back, in one more wait; the host lays
+ * the file out again (compressing the dictionary pages itself: they are host bytes), one gather launch moves every fragment's elements
+ * and the chunks of the uncompressed columns into the final image, and that — the smaller one — is what crosses the link. Device memory
+ * for the length of the call: staging + scratch + final image, about 3 × the file body — accepted; all of it is the call's own and
+ * freed on every path. Refused before anything is launched: FDB_ERR_INVALID — n_codecs neither 0 nor the column count, an entry outside
+ * 0 … 1; and everything the calls above refuse, unchanged. fdb_parquet_write_options keeps its layout. */
+/* codecs: per column parquet's CompressionCodec number, 0 = UNCOMPRESSED, 1 = SNAPPY; n_codecs: 0 (all 0) or the batch's column count */
+FDB_API int fdb_batch_to_parquet_compressed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_compressed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes);
 
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry

@@ -2,12 +2,14 @@
 # Host-only memory-safety check of the Parquet writer's host half under AddressSanitizer + UBSan: options and column checks, layout
 # planning, the thrift compact writer, the dictionary page builder and the tail (frostdb_amd/csrc/fdb_pqwrite.cpp), and the host walk of
 # the survey and encode passes (fdb_pqwrite.h: the page geometry, bit positions and word assembly the kernels compile) and of the
-# DELTA_BINARY_PACKED passes (fdb_pqdelta.h) over seeded random records and options, with fdb_arrow.cpp's dictionary constructors.
-# No GPU, no HIP, no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
+# DELTA_BINARY_PACKED passes (fdb_pqdelta.h) over seeded random records and options, with fdb_arrow.cpp's dictionary constructors; and the
+# SNAPPY compressor's host walk (fdb_pqsnappy.h) over the same records with codecs per column at random and over bodies around one and
+# two fragments, every page inflated again by the library's host decoder (fdb_codec.cpp).
+# No GPU, no HIP runtime (fdb_codec.h takes its types from the HIP headers), no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${TMPDIR:-/tmp}/fdb_asan_parquet_write
 mkdir -p "$OUT"
-g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DFDB_PQWRITE_HOST_ONLY -I"$ROOT/include" -I"$ROOT/frostdb_amd/csrc" \
-    "$ROOT/tools/asan_parquet_write_main.cpp" "$ROOT/frostdb_amd/csrc/fdb_pqwrite.cpp" "$ROOT/frostdb_amd/csrc/fdb_arrow.cpp" -o "$OUT/asan_parquet_write" -lpthread
+g++ -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -DFDB_PQWRITE_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I"${ROCM_PATH:-/opt/rocm}/include" -I"$ROOT/include" -I"$ROOT/frostdb_amd/csrc" \
+    "$ROOT/tools/asan_parquet_write_main.cpp" "$ROOT/frostdb_amd/csrc/fdb_pqwrite.cpp" "$ROOT/frostdb_amd/csrc/fdb_codec.cpp" "$ROOT/frostdb_amd/csrc/fdb_arrow.cpp" -o "$OUT/asan_parquet_write" -lpthread
 "$OUT/asan_parquet_write"

@@ -3,13 +3,18 @@
 // compile), layout planning with the thrift writer and the dictionary page builder (pqw_layout) and the tail (pqw_finish) — over seeded
 // random records and options, every buffer sized exactly. Some int64 / uint64 columns are asked to be DELTA_BINARY_PACKED: the DELTA
 // passes' host walk (pqd_survey_host / pqd_encode_host: the arithmetic of fdb_pqdelta.h) sizes and writes their pages. What the walk
-// wrote is read back with a bit reader and a DELTA decoder of this file's own. No GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
+// wrote is read back with a bit reader and a DELTA decoder of this file's own. Some columns, DELTA ones among them, are asked to be SNAPPY:
+// the compressor's host walk (fdb_pqsnappy.h) runs over the staging image's page bodies, the file is laid out again, and every page of
+// the final file — dictionary pages too — is inflated by the library's host decoder (fdb_codec.cpp snappy_block) into a buffer of exactly
+// the body's size and compared with the body; bodies of 0 … 2 fragments + 1 bytes of several kinds go through the same two.
+// No GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "fdb_codec.h"
 #include "fdb_pqwrite_host.h"
 
 using namespace fdb;
@@ -84,6 +89,35 @@ static void check_delta_page(const uint8_t* p, size_t bytes, const std::vector<u
     }
   }
   CHECK(at == bytes);
+}
+
+// `block` (sized exactly) inflates to `body` (into a buffer sized exactly), and stays within Snappy's bound.
+static void check_block(const std::string& block, const unsigned char* body, size_t n) {
+  std::vector<uint8_t> exact(block.begin(), block.end()), out(n);
+  CHECK(exact.size() <= 32 + n + n / 6);
+  CHECK(snappy_block(exact.data(), exact.size(), out.data(), n, n) == 0);
+  CHECK(n == 0 || std::memcmp(out.data(), body, n) == 0);
+}
+
+// Bodies around nothing, one and two fragments, of several kinds, through the block compressor and the host decoder.
+static void snappy_bodies(uint64_t* seed) {
+  static const size_t sizes[] = {0, 1, 2, 3, 4, 5, 63, 64, 65, 4096, FDB_PQS_FRAGMENT - 1, FDB_PQS_FRAGMENT, FDB_PQS_FRAGMENT + 1, 2 * FDB_PQS_FRAGMENT - 1, 2 * FDB_PQS_FRAGMENT, 2 * FDB_PQS_FRAGMENT + 1};
+  for (size_t n : sizes) {
+    for (int kind = 0; kind < 5; kind++) {  // 0 noise, 1 one byte, 2 few distinct 8-byte values, 3 runs of random periods and lengths, 4 noise with repeats from far back
+      std::vector<unsigned char> body(n);
+      uint64_t few[8];
+      for (uint64_t& f : few) f = rnd(seed);
+      for (size_t i = 0; i < n;) {
+        if (kind == 0) body[i++] = (unsigned char)rnd(seed);
+        else if (kind == 1) body[i++] = 7;
+        else if (kind == 2) { const uint64_t v = few[rnd(seed) % 8]; for (int b = 0; b < 8 && i < n; b++) body[i++] = (unsigned char)(v >> (8 * b)); }
+        else if (kind == 3) { const size_t period = 1 + rnd(seed) % 70, len = 1 + rnd(seed) % 400, at = i; for (size_t j = 0; j < len && i < n; j++, i++) body[i] = j < period ? (unsigned char)rnd(seed) : body[at + j % period]; }
+        else { const size_t len = 1 + rnd(seed) % 200, back = i > 0 ? 1 + rnd(seed) % i : 0; const bool copy = back > 0 && (rnd(seed) & 1); for (size_t j = 0; j < len && i < n; j++, i++) body[i] = copy ? body[i - back] : (unsigned char)rnd(seed); }
+      }
+      const std::vector<unsigned char> exact(body);  // (sized exactly: a walk that reads past the body is caught)
+      check_block(pqs_block_host(exact.data(), exact.size()), exact.data(), n);
+    }
+  }
 }
 
 static void one_record(uint64_t* seed, int round) {
@@ -215,6 +249,70 @@ static void one_record(uint64_t* seed, int round) {
     }
   }
   for (uint64_t b = 0; b < L.body_bytes; b++) CHECK(owner[b] != 0);  // every byte of the body belongs to somebody
+  // the same record with a codec per column at random (three rounds in four): what fdb_selftest_parquet_write_compressed does, step by step
+  std::vector<int8_t> codecs;
+  for (size_t k = 0; k < n_cols; k++) codecs.push_back((int8_t)(rnd(seed) & 1));
+  if ((round & 3) != 3) {
+    const std::vector<PqwColumn> cc = pqw_columns(in, rows, &opt, &pr, with_encodings ? encodings.data() : nullptr, with_encodings ? (int32_t)n_cols : 0, codecs.data(), (int32_t)n_cols);
+    const PqwLayout S = pqw_layout(cc, g, stats, dh.page_bytes);  // the staging layout: the payload offsets are those of the uncompressed file
+    CHECK(S.body_bytes == L.body_bytes);
+    std::vector<unsigned char> staging(image);
+    for (const PqwLayout::Piece& p : S.body_pieces) { CHECK(p.off + p.len <= S.body_bytes && p.pos + p.len <= S.body_blob.size()); std::memcpy(staging.data() + p.off, S.body_blob.data() + p.pos, p.len); }
+    CHECK(S.pages.size() == pqw_compressed_columns(cc) * (size_t)g.n_pages);
+    std::vector<uint32_t> page_elements, table(FDB_PQS_TABLE);
+    std::vector<std::string> elements;
+    for (const PqwLayout::Page& pg : S.pages) {
+      CHECK(pg.off + pg.body <= S.body_bytes);
+      CHECK(std::memcmp(staging.data() + pg.off, file + pg.off, (size_t)pg.body) == 0);  // a whole body: what the uncompressed file holds there
+      std::string e;
+      for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT) {
+        const uint32_t len = (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at);
+        const std::vector<unsigned char> frag(staging.begin() + (size_t)(pg.off + at), staging.begin() + (size_t)(pg.off + at) + len);  // (sized exactly)
+        std::vector<unsigned char> out(fdb_pqs_bound(len));
+        e.append((const char*)out.data(), fdb_pqs_compress_fragment_host(frag.data(), len, table.data(), out.data()));
+      }
+      page_elements.push_back((uint32_t)e.size());
+      elements.push_back(std::move(e));
+    }
+    const PqwLayout F = pqw_layout(cc, g, stats, dh.page_bytes, &page_elements);
+    CHECK(F.pages.size() == S.pages.size());
+    const size_t out_bytes = (size_t)F.body_bytes + F.footer.size() + 8;
+    uint8_t* out_file = pqw_alloc_bytes(out_bytes, false);
+    std::vector<uint8_t> own(F.body_bytes, 0);
+    for (const PqwLayout::Piece& p : F.pieces) for (size_t b = 0; b < p.len; b++) { CHECK(p.off + b < F.body_bytes && own[p.off + b] == 0); own[p.off + b] = 1; }
+    for (size_t i = 0; i < F.pages.size(); i++) {
+      CHECK(F.pages[i].body == S.pages[i].body && F.pages[i].off + elements[i].size() <= F.body_bytes);
+      std::memcpy(out_file + F.pages[i].off, elements[i].data(), elements[i].size());
+      for (size_t b = 0; b < elements[i].size(); b++) { CHECK(own[F.pages[i].off + b] == 0); own[F.pages[i].off + b] = 2; }
+    }
+    for (size_t k = 0; k < n_cols; k++) {
+      if (cc[k].codec != 0) continue;
+      CHECK(F.chunk_len[k] == S.chunk_len[k] && F.chunk_off[k] + F.chunk_len[k] <= F.body_bytes);
+      std::memcpy(out_file + F.chunk_off[k], staging.data() + S.chunk_off[k], (size_t)S.chunk_len[k]);
+      for (uint64_t b = 0; b < F.chunk_len[k]; b++) if (own[F.chunk_off[k] + b] == 0) own[F.chunk_off[k] + b] = 3;
+    }
+    for (uint64_t b = 0; b < F.body_bytes; b++) CHECK(own[b] != 0);
+    pqw_finish(F, out_file);
+    CHECK(std::memcmp(out_file, "PAR1", 4) == 0 && std::memcmp(out_file + out_bytes - 4, "PAR1", 4) == 0);
+    for (size_t i = 0; i < F.pages.size(); i++) {  // the preamble sits in front of the elements; the block inflates to the body
+      size_t pl = 1;
+      for (uint64_t v = F.pages[i].body; v >= 0x80; v >>= 7) pl++;
+      CHECK(F.pages[i].off >= pl);
+      check_block(std::string((const char*)out_file + F.pages[i].off - pl, pl + elements[i].size()), staging.data() + S.pages[i].off, (size_t)S.pages[i].body);
+    }
+    for (size_t k = 0; k < n_cols; k++) {  // a compressed dictionary page: the block the host walk makes of the entries
+      if (cc[k].codec == 0 || cc[k].pq_kind != FDB_PQW_INDEX) continue;
+      std::string body;
+      for (const std::string& v : cc[k].dict->values) { const uint32_t n = (uint32_t)v.size(); body.append((const char*)&n, 4); body += v; }
+      const std::string block = pqs_block_host((const unsigned char*)body.data(), body.size());
+      check_block(block, (const unsigned char*)body.data(), body.size());
+      bool found = false;
+      for (size_t at = (size_t)F.chunk_off[k]; at + block.size() <= (size_t)(F.chunk_off[k] + F.chunk_len[k]) && at < (size_t)F.chunk_off[k] + 32 && !found; at++)
+        found = std::memcmp(out_file + at, block.data(), block.size()) == 0;
+      CHECK(found);  // right behind the dictionary page's header
+    }
+    pqw_free_bytes(out_file);
+  }
   pqw_free_bytes(file);
 }
 
@@ -238,6 +336,10 @@ static void refusals() {
   const int8_t delta = 1, two = 2, both[2] = {1, 1};
   CHECK(enc_code(&delta, 1) == FDB_OK && enc_code(nullptr, 0) == FDB_OK);
   CHECK(enc_code(&two, 1) == FDB_ERR_INVALID && enc_code(both, 2) == FDB_ERR_INVALID && enc_code(nullptr, 1) == FDB_ERR_INVALID);
+  const auto codec_code = [&](const int8_t* c, int32_t n) { try { pqw_columns(in, 8, &plain_opt, &pr, nullptr, 0, c, n); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const int8_t minus = -1;
+  CHECK(codec_code(&delta, 1) == FDB_OK && codec_code(nullptr, 0) == FDB_OK);
+  CHECK(codec_code(&two, 1) == FDB_ERR_INVALID && codec_code(&minus, 1) == FDB_ERR_INVALID && codec_code(both, 2) == FDB_ERR_INVALID && codec_code(nullptr, 1) == FDB_ERR_INVALID);
   in[0].kind = ColKind::F64;
   CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED);
   in[0].kind = ColKind::BOOL;
@@ -252,6 +354,7 @@ static void refusals() {
 int main() {
   uint64_t seed = 11;
   for (int round = 0; round < 400; round++) one_record(&seed, round);
+  snappy_bodies(&seed);
   refusals();
   std::printf("asan parquet write ok\n");
   return 0;

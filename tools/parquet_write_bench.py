@@ -16,9 +16,14 @@ With --delta the `timestamp` column is written DELTA_BINARY_PACKED (fdb_batch_to
 to_parquet_ms, the phases, among them delta_compact_ms / delta_survey_ms (block survey + page walk, with the wait for the tables) /
 delta_encode_ms — are then the DELTA call's, and the PLAIN call on the same record in the same process goes into the same line as
 plain_file_bytes, plain_to_parquet_ms, plain_to_parquet_min_ms / _max_ms (its spread over the repetitions: the yardstick) and plain_*_ms phases.
+With --snappy every column is written SNAPPY and `timestamp` DELTA_BINARY_PACKED + SNAPPY (fdb_batch_to_parquet_compressed): the line's
+own figures are the SNAPPY call's — among the phases place_compress_ms (the host's body bytes placed + the compress kernel), scan_ms (the
+size scan with the wait for the page sizes), final_layout_ms and gather_ms — and the uncompressed PLAIN call on the same record in the
+same process goes into the line as with --delta, with plain_floor_ms, the bare copy of ITS file's bytes, beside floor_ms, that of the
+compressed file's.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy] [--out FILE]
 """
 import argparse
 import io
@@ -42,6 +47,7 @@ from frostdb_amd import physicalplan as pp  # noqa: E402
 LABELS = [10, 50, 100, 500, 1000]
 PHASES = ["survey", "layout", "encode", "copy", "host tail"]
 DELTA_PHASES = ["delta compact", "delta survey", "delta encode"]
+SNAPPY_PHASES = ["compress", "scan", "final layout", "gather"]
 
 
 def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
@@ -69,7 +75,7 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps, encodings=None):
+def profiled_phases(rb, page_rows, reps, encodings=None, compression=None):
     """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
     os.environ["FDB_PROFILE"] = "1"
     sys.stderr.flush()
@@ -78,7 +84,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None):
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows, encodings=encodings)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -86,7 +92,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None):
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = statistics.median(us) / 1e3 if us else None
     return out
@@ -100,52 +106,66 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--baseline-reps", type=int, default=3)
     ap.add_argument("--delta", action="store_true", help="write `timestamp` DELTA_BINARY_PACKED; the PLAIN call goes into the same line")
+    ap.add_argument("--snappy", action="store_true", help="write every column SNAPPY and `timestamp` DELTA + SNAPPY; the uncompressed PLAIN call goes into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    assert not (args.delta and args.snappy), "--delta or --snappy"
     record = make_record(args.rows)
     rb = pp.ResidentBatch(record)
     del record
     try:
-        encodings = {"timestamp": "delta"} if args.delta else None
-        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings)
+        encodings = {"timestamp": "delta"} if args.delta or args.snappy else None
+        compression = "snappy" if args.snappy else None
+        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression)
         file_bytes = len(data)
         md = pq.ParquetFile(io.BytesIO(data)).metadata
         assert md.num_rows == args.rows and md.num_row_groups == 1
-        if args.delta:
+        if args.delta or args.snappy:
             assert set(md.row_group(0).column(0).encodings) == {"DELTA_BINARY_PACKED"}
+        if args.snappy:
+            assert all(md.row_group(0).column(j).compression == "SNAPPY" for j in range(md.num_columns))
+            column_bytes = {md.row_group(0).column(j).path_in_schema: [md.row_group(0).column(j).total_compressed_size, md.row_group(0).column(j).total_uncompressed_size] for j in range(md.num_columns)}
         del data
         import ctypes
         opts = pp.ParquetWriteOptions(args.page_rows, 0, None)
         n_columns = len(rb.column_names)
         enc = (ctypes.c_int8 * n_columns)(*([1] + [0] * (n_columns - 1)))
 
-        def c_call(delta=args.delta, want=file_bytes):
+        codecs = (ctypes.c_int8 * n_columns)(*([1] * n_columns))
+
+        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
-            if delta:
+            if snappy:
+                rc = pp.lib().fdb_batch_to_parquet_compressed(rb.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_columns, ctypes.cast(codecs, ctypes.c_void_p), n_columns,
+                                                              ctypes.byref(out), ctypes.byref(n))
+            elif delta:
                 rc = pp.lib().fdb_batch_to_parquet_encoded(rb.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_columns, ctypes.byref(out), ctypes.byref(n))
             else:
                 rc = pp.lib().fdb_batch_to_parquet(rb.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
             assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
         plain = {}
-        if args.delta:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+        if args.delta or args.snappy:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
             plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
-            ms, every = median_ms(lambda: c_call(False, plain_bytes), args.reps, args.warmup)
+            ms, every = median_ms(lambda: c_call(False, plain_bytes, False), args.reps, args.warmup)
             ph = profiled_phases(rb, args.page_rows, args.reps)
             plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
             plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
-        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings), args.reps, 1)
-        phases = profiled_phases(rb, args.page_rows, args.reps, encodings)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression)
 
-        dev = torch.empty(file_bytes, dtype=torch.uint8, device="cuda")
-        host = torch.empty(file_bytes, dtype=torch.uint8).pin_memory()
+        def bare_copy_ms(n_bytes):
+            dev = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+            host = torch.empty(n_bytes, dtype=torch.uint8).pin_memory()
 
-        def bare_copy():
-            host.copy_(dev, non_blocking=True)
-            torch.cuda.synchronize()
-        floor_ms, _ = median_ms(bare_copy, args.reps, args.warmup)
-        del dev, host
+            def bare_copy():
+                host.copy_(dev, non_blocking=True)
+                torch.cuda.synchronize()
+            return median_ms(bare_copy, args.reps, args.warmup)[0]
+        floor_ms = bare_copy_ms(file_bytes)
+        if args.snappy:
+            plain["plain_floor_ms"] = bare_copy_ms(plain["plain_file_bytes"])
 
         label_names = ["labels.l%d" % k for k in range(len(LABELS))]
         export_times, baseline_bytes = [], [0]
@@ -172,6 +192,11 @@ def main():
     if args.delta:
         line.update({"delta": ["timestamp"], "to_parquet_max_ms": r3(max(to_parquet_all)), "delta_compact_ms": r3(phases["delta compact"]), "delta_survey_ms": r3(phases["delta survey"]),
                      "delta_encode_ms": r3(phases["delta encode"])})
+    if args.snappy:
+        line.update({"delta": ["timestamp"], "snappy": "all", "to_parquet_max_ms": r3(max(to_parquet_all)), "delta_compact_ms": r3(phases["delta compact"]),
+                     "delta_survey_ms": r3(phases["delta survey"]), "delta_encode_ms": r3(phases["delta encode"]), "place_compress_ms": r3(phases["compress"]), "scan_ms": r3(phases["scan"]),
+                     "final_layout_ms": r3(phases["final layout"]), "gather_ms": r3(phases["gather"]), "column_bytes": column_bytes})
+    if args.delta or args.snappy:
         line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
