@@ -35,7 +35,16 @@
 //   7. which is what is copied out; headers, block preambles, dictionary pages and the footer are the host's, as before.
 // Device memory: staging + scratch + final image, about 3 × the file body, all of it the call's and freed on every path. Without a
 // compressed column nothing of this runs: the path, its launches, allocations and copies are those of fdb_batch_to_parquet_encoded.
+//
+// fdb_batch_to_parquet_indexed: min / max statistics, the page index and sorting_columns, when asked for (the rules are spelled out in
+// include/frostdb_amd.h, the keys in fdb_pqstats.h). After the survey — before the DELTA passes — the min / max pass of fdb_pqstats.hip
+// folds an order-preserving key of every value that counts into a (column, page) table, which comes back with the survey's table in the
+// same wait. The rest is the host's, inside pqw_layout: pages folded into chunk bounds, keys mapped back (a rank to an entry), the zero
+// rule, the cut of BYTE_ARRAY bounds, the boundary order, and the thrift of Statistics, ColumnIndex, OffsetIndex, column_orders and
+// sorting_columns. The index bytes follow the body in the file (PqwLayout::tail, written by pqw_finish); the image stays the body. For a
+// compressed file the index is the final layout's. Without index options nothing of this runs.
 #include "fdb_pqwrite_host.h"
+#include "fdb_sortplan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -107,9 +116,17 @@ std::string page_header(int type, int64_t body, int64_t compressed, int64_t num_
 std::string varint_bytes(uint64_t v) { Thrift t; t.varint(v); return t.out; }
 std::string le32(uint32_t v) { std::string s(4, '\0'); std::memcpy(&s[0], &v, 4); return s; }
 
-struct ChunkMeta { int64_t dict_off = -1, data_off = 0, bytes = 0, raw_bytes = 0, nulls = 0; };  // bytes: as stored; raw_bytes: the bodies uncompressed (headers in both)
+struct PageLoc { uint64_t off, bytes; uint32_t rows, count; };  // a data page: where its header starts, header + body as stored, its rows and non-NULL rows
+struct ChunkMeta {
+  int64_t dict_off = -1, data_off = 0, bytes = 0, raw_bytes = 0, nulls = 0;  // bytes: as stored; raw_bytes: the bodies uncompressed (headers in both)
+  // with statistics only
+  std::vector<PageLoc> pages;
+  bool has_bounds = false;
+  std::string min, max;                                                     // Statistics.min_value / max_value
+  int64_t offset_index_off = -1, offset_index_len = 0, column_index_off = -1, column_index_len = 0;
+};
 
-std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMeta>& chunks, int64_t rows, int64_t body_bytes) {
+std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMeta>& chunks, int64_t rows, int64_t body_bytes, const PqxIndex* x) {
   Thrift t;
   t.open();
   t.i32(1, 1);
@@ -145,18 +162,28 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     t.i64(7, m.bytes);
     t.i64(9, m.data_off);
     if (m.dict_off >= 0) t.i64(11, m.dict_off);
-    t.open(12); t.i64(3, m.nulls); t.close();  // Statistics.null_count
+    t.open(12); t.i64(3, m.nulls); if (m.has_bounds) { t.string(5, m.max); t.string(6, m.min); } t.close();  // Statistics: null_count, max_value, min_value
     t.close();
+    if (m.offset_index_off >= 0) { t.i64(4, m.offset_index_off); t.i32(5, (int32_t)m.offset_index_len); }
+    if (m.column_index_off >= 0) { t.i64(6, m.column_index_off); t.i32(7, (int32_t)m.column_index_len); }
     t.close();
   }
   int64_t raw_bytes = 0;
   for (const ChunkMeta& m : chunks) raw_bytes += m.raw_bytes;
   t.i64(2, raw_bytes);  // total_byte_size: uncompressed
   t.i64(3, rows);
+  if (x != nullptr && !x->sorting.empty()) {
+    t.list(4, Thrift::T_STRUCT, x->sorting.size());
+    for (const fdb_parquet_sorting_column& sc : x->sorting) { t.open(); t.i32(1, sc.column); t.boolean(2, sc.descending != 0); t.boolean(3, sc.nulls_first != 0); t.close(); }
+  }
   t.i64(5, 4);
   t.i64(6, body_bytes - 4);
   t.close();
   t.string(6, "frostdb_amd 0.1.0");
+  if (x != nullptr && x->statistics > 0) {  // column_orders: TypeDefinedOrder for every column
+    t.list(7, Thrift::T_STRUCT, cols.size());
+    for (size_t k = 0; k < cols.size(); k++) { t.open(); t.open(1); t.close(); t.close(); }
+  }
   t.close();
   return t.out;
 }
@@ -169,6 +196,104 @@ std::string dictionary_body(const HostDict& d) {
   s.reserve(total);
   for (const std::string& v : d.values) { s += le32((uint32_t)v.size()); s += v; }
   return s;
+}
+
+// ---- statistics and the page index: the host's half of the min / max pass (fdb_pqstats.h) -----------------------------------------------
+std::string le64(uint64_t v) { std::string s(8, '\0'); std::memcpy(&s[0], &v, 8); return s; }
+
+// The bytes a bound is written as: the key mapped back, parquet-format's zero rule for doubles (a minimum that is zero is −0.0, a
+// maximum +0.0), an index key — a rank — as the bytes of an entry of that rank.
+std::string pqx_bound(const PqwColumn& c, const PqxIndex& x, size_t k, uint64_t key, bool is_max) {
+  const int mode = x.modes[k];
+  if (mode == FDB_PQX_INDEX) {
+    if (key >= x.entry_of_rank[k].size()) throw Error(FDB_ERR_STATE, "parquet write: the min / max pass names rank " + std::to_string(key) + " in column " + c.name);
+    return c.dict->values[x.entry_of_rank[k][(size_t)key]];
+  }
+  uint64_t bits = fdb_pqx_value(mode, key);
+  if (mode == FDB_PQX_BOOL) return std::string(1, (char)(bits != 0));
+  if (mode == FDB_PQX_F64 && (bits << 1) == 0) bits = is_max ? 0 : 0x8000000000000000ull;
+  return le64(bits);
+}
+
+std::string pqx_cut_min(const std::string& s, size_t limit) { return s.size() > limit ? s.substr(0, limit) : s; }
+std::string pqx_cut_max(const std::string& s, size_t limit) {
+  if (s.size() <= limit) return s;
+  std::string p = s.substr(0, limit);
+  while (!p.empty() && (unsigned char)p.back() == 0xFF) p.pop_back();
+  if (p.empty()) return s;  // the prefix is all 0xFF: no shorter upper bound
+  p.back() = (char)((unsigned char)p.back() + 1);
+  return p;
+}
+
+// a < b in the column's order, of two bounds as written
+bool pqx_less(int mode, const std::string& a, const std::string& b) {
+  if (mode == FDB_PQX_INDEX) return a < b;  // (std::string: bytewise unsigned, the shorter first)
+  if (mode == FDB_PQX_BOOL) return (unsigned char)a[0] < (unsigned char)b[0];
+  uint64_t va, vb, ka = 0, kb = 0;
+  std::memcpy(&va, a.data(), 8); std::memcpy(&vb, b.data(), 8);
+  fdb_pqx_key(mode, va, &ka); fdb_pqx_key(mode, vb, &kb);
+  if (mode == FDB_PQX_F64 && (va << 1) == 0 && (vb << 1) == 0) return false;  // −0.0 == +0.0
+  return ka < kb;
+}
+
+// Chunk bounds into `m`, and with statistics == 2 the column's ColumnIndex (empty: the column gets none) — from the table's slots of
+// column k and the pages the layout has listed in `m`.
+std::string pqx_column_index(const PqwColumn& c, const PqxIndex& x, size_t k, size_t n_pages, ChunkMeta* m) {
+  const int mode = x.modes[k];
+  const size_t items = x.table.size() / 2;
+  uint64_t cmn = FDB_PQX_EMPTY_MIN, cmx = FDB_PQX_EMPTY_MAX;
+  std::vector<std::string> mins(n_pages), maxs(n_pages);
+  bool sayable = true;
+  for (size_t p = 0; p < n_pages; p++) {
+    const uint64_t mn = x.table[k * n_pages + p], mx = x.table[items + k * n_pages + p];
+    const bool empty = mn > mx;
+    const uint32_t cnt = m->pages[p].count;
+    if (empty) {
+      if (cnt > 0 && mode != FDB_PQX_F64) throw Error(FDB_ERR_STATE, "parquet write: the min / max pass found no value in a page of " + std::to_string(cnt) + " (" + c.name + ")");
+      if (cnt > 0) sayable = false;  // values, and NaNs only: the ColumnIndex has no way to say it
+      continue;
+    }
+    if (cnt == 0) throw Error(FDB_ERR_STATE, "parquet write: the min / max pass found a value in a page of NULLs (" + c.name + ")");
+    cmn = mn < cmn ? mn : cmn; cmx = mx > cmx ? mx : cmx;
+    if (x.statistics == 2) {
+      mins[p] = pqx_bound(c, x, k, mn, false); maxs[p] = pqx_bound(c, x, k, mx, true);
+      if (mode == FDB_PQX_INDEX) { mins[p] = pqx_cut_min(mins[p], x.limit); maxs[p] = pqx_cut_max(maxs[p], x.limit); }
+    }
+  }
+  if (cmn <= cmx) { m->has_bounds = true; m->min = pqx_bound(c, x, k, cmn, false); m->max = pqx_bound(c, x, k, cmx, true); }
+  if (x.statistics != 2 || !sayable) return std::string();
+  bool up = true, down = true;
+  size_t prev = n_pages;
+  for (size_t p = 0; p < n_pages; p++) {
+    if (m->pages[p].count == 0) continue;
+    if (prev != n_pages) {
+      if (pqx_less(mode, mins[p], mins[prev]) || pqx_less(mode, maxs[p], maxs[prev])) up = false;
+      if (pqx_less(mode, mins[prev], mins[p]) || pqx_less(mode, maxs[prev], maxs[p])) down = false;
+    }
+    prev = p;
+  }
+  Thrift t;
+  t.open();
+  t.list(1, Thrift::T_TRUE, n_pages);
+  for (size_t p = 0; p < n_pages; p++) t.out.push_back(m->pages[p].count == 0 ? (char)Thrift::T_TRUE : (char)Thrift::T_FALSE);
+  t.list(2, Thrift::T_BINARY, n_pages);
+  for (size_t p = 0; p < n_pages; p++) t.str(mins[p]);
+  t.list(3, Thrift::T_BINARY, n_pages);
+  for (size_t p = 0; p < n_pages; p++) t.str(maxs[p]);
+  t.i32(4, up ? 1 : down ? 2 : 0);  // BoundaryOrder: UNORDERED 0, ASCENDING 1, DESCENDING 2
+  t.list(5, Thrift::T_I64, n_pages);
+  for (size_t p = 0; p < n_pages; p++) t.zigzag((int64_t)m->pages[p].rows - (int64_t)m->pages[p].count);
+  t.close();
+  return t.out;
+}
+
+std::string pqx_offset_index(const ChunkMeta& m, int32_t page_rows) {
+  Thrift t;
+  t.open();
+  t.list(1, Thrift::T_STRUCT, m.pages.size());
+  for (size_t p = 0; p < m.pages.size(); p++) { t.open(); t.i64(1, (int64_t)m.pages[p].off); t.i32(2, (int32_t)m.pages[p].bytes); t.i64(3, (int64_t)p * page_rows); t.close(); }
+  t.close();
+  return t.out;
 }
 
 constexpr uint64_t kBytesMagic = 0x5051574259544553ull;
@@ -310,6 +435,82 @@ size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols) {
   return n;
 }
 
+PqxIndex pqx_plan(const fdb_parquet_index_options* index, size_t n_cols) {
+  PqxIndex x;
+  if (index == nullptr) return x;
+  if (index->statistics < 0 || index->statistics > 2)
+    throw Error(FDB_ERR_INVALID, "parquet write: statistics is " + std::to_string(index->statistics) + " (0 none, 1 chunk bounds, 2 chunk bounds and the page index)");
+  if (index->index_size_limit < 0 || index->index_size_limit > 65536)
+    throw Error(FDB_ERR_INVALID, "parquet write: index_size_limit is " + std::to_string(index->index_size_limit) + " (0: 16, else 1 to 65536)");
+  if (index->n_sorting_columns < 0 || (index->n_sorting_columns > 0 && index->sorting_columns == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: `sorting_columns` has " + std::to_string(index->n_sorting_columns) + " entries" + (index->n_sorting_columns > 0 ? " and no array" : ""));
+  std::vector<bool> seen(n_cols, false);
+  for (int32_t i = 0; i < index->n_sorting_columns; i++) {
+    const fdb_parquet_sorting_column& sc = index->sorting_columns[i];
+    if (sc.column < 0 || (size_t)sc.column >= n_cols)
+      throw Error(FDB_ERR_INVALID, "parquet write: sorting column " + std::to_string(sc.column) + " is outside the record's " + std::to_string(n_cols) + " columns");
+    if (seen[(size_t)sc.column]) throw Error(FDB_ERR_INVALID, "parquet write: sorting column " + std::to_string(sc.column) + " is named twice");
+    seen[(size_t)sc.column] = true;
+    x.sorting.push_back(sc);
+  }
+  x.statistics = index->statistics;
+  x.limit = index->index_size_limit == 0 ? 16u : (uint32_t)index->index_size_limit;
+  return x;
+}
+
+void pqx_prepare(const std::vector<PqwColumn>& cols, PqxIndex* x) {
+  x->modes.assign(cols.size(), FDB_PQX_U64);
+  x->ranks.assign(cols.size(), std::vector<uint32_t>());
+  x->entry_of_rank.assign(cols.size(), std::vector<uint32_t>());
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    if (c.pq_kind == FDB_PQW_BOOL) x->modes[k] = FDB_PQX_BOOL;
+    else if (c.pq_kind == FDB_PQW_V64) x->modes[k] = c.physical == PT_DOUBLE ? FDB_PQX_F64 : c.is_u64 ? FDB_PQX_U64 : FDB_PQX_I64;
+    else {
+      x->modes[k] = FDB_PQX_INDEX;
+      if (c.dict == nullptr || c.entries == 0) continue;  // (all NULL over an empty dictionary: no rank, no value that counts)
+      uint32_t distinct = 0;
+      x->ranks[k] = dense_ranks(*c.dict, &distinct);
+      x->entry_of_rank[k].assign(distinct, 0);
+      for (size_t i = x->ranks[k].size(); i-- > 0;) x->entry_of_rank[k][x->ranks[k][i]] = (uint32_t)i;  // (the first entry of equal ones: the same bytes)
+    }
+  }
+}
+
+void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, PqxIndex* x) {
+  const size_t items = cols.size() * (size_t)g.n_pages;
+  x->table.assign(2 * items, FDB_PQX_EMPTY_MAX);
+  std::fill(x->table.begin(), x->table.begin() + (std::ptrdiff_t)items, FDB_PQX_EMPTY_MIN);
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    const int mode = x->modes[k];
+    const uint32_t per = mode == FDB_PQX_INDEX ? FDB_PQX_UNIT_INDEX : FDB_PQX_UNIT_V64, rank_len = (uint32_t)x->ranks[k].size();
+    for (int64_t p = g.n_pages; p-- > 0;) {
+      for (int32_t t = g.tiles_per_page; t-- > 0;) {
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        if (first >= end) continue;
+        uint64_t mn = FDB_PQX_EMPTY_MIN, mx = FDB_PQX_EMPTY_MAX, key;
+        for (uint32_t u = 0; (int64_t)u * per < end - first; u++) {
+          const uint32_t bits = fdb_pqx_unit_bits(c.validity, first, end, u, per);
+          for (uint32_t i = 0; i < per; i++) {
+            if (!((bits >> i) & 1)) continue;
+            const size_t row = (size_t)first + (size_t)u * per + i;
+            bool counts;
+            if (mode == FDB_PQX_INDEX) counts = fdb_pqx_index_key(x->ranks[k].data(), rank_len, ((const uint32_t*)c.values)[row], &key);
+            else { uint64_t v; std::memcpy(&v, (const unsigned char*)c.values + row * 8, 8); counts = fdb_pqx_key(mode, v, &key); }
+            if (counts) fdb_pqx_fold(key, &mn, &mx);
+          }
+        }
+        if (mn > mx) continue;  // (the tile issues nothing)
+        uint64_t& smn = x->table[k * (size_t)g.n_pages + (size_t)p];
+        uint64_t& smx = x->table[items + k * (size_t)g.n_pages + (size_t)p];
+        smn = mn < smn ? mn : smn; smx = mx > smx ? mx : smx;
+      }
+    }
+  }
+}
+
 std::string pqs_block_host(const unsigned char* body, size_t n) {
   std::string block = varint_bytes(n);
   std::vector<uint32_t> table(FDB_PQS_TABLE);
@@ -322,7 +523,10 @@ std::string pqs_block_host(const unsigned char* body, size_t n) {
 }
 
 PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes,
-                     const std::vector<uint32_t>* page_elements) {
+                     const std::vector<uint32_t>* page_elements, const PqxIndex* x) {
+  if (x != nullptr && !x->any()) x = nullptr;
+  const bool bounds = x != nullptr && x->statistics > 0;
+  if (bounds && (x->table.size() != 2 * stats.size() || x->modes.size() != cols.size())) throw Error(FDB_ERR_STATE, "parquet write: the min / max table does not match the record");
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
   if (delta_bytes.size() != pqw_delta_columns(cols) * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
   if (page_elements != nullptr && page_elements->size() != pqw_compressed_columns(cols) * (size_t)g.n_pages)
@@ -404,6 +608,7 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
         const std::string preamble = varint_bytes(body);
         const std::string hdr = page_header(PAGE_DATA, (int64_t)body, (int64_t)(preamble.size() + elements), n, encoding);
         m.raw_bytes += (int64_t)(hdr.size() + body);
+        if (bounds) m.pages.push_back(PageLoc{cur, hdr.size() + preamble.size() + elements, n, cnt});
         L.put(cur, hdr + preamble); cur += hdr.size() + preamble.size();
         L.pages.push_back(PqwLayout::Page{cur, body});
         cur += elements;
@@ -411,6 +616,7 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
       }
       const std::string hdr = page_header(PAGE_DATA, (int64_t)body, (int64_t)body, n, encoding);
       m.raw_bytes += (int64_t)(hdr.size() + body);
+      if (bounds) m.pages.push_back(PageLoc{cur, hdr.size() + body, n, cnt});
       FdbPqwPageOut& o = L.out[k * (size_t)g.n_pages + (size_t)p];
       if (c.codec == 0) { L.put(cur, hdr + pre); cur += hdr.size() + pre.size(); }
       else {  // the staging image of a page to be compressed: the host's bytes inside the body are placed on their own, before the compressor runs
@@ -430,16 +636,31 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
     L.chunk_len[k] = cur - chunk_start;
   }
   L.body_bytes = cur;
-  L.footer = footer(cols, chunks, g.rows, (int64_t)cur);
+  if (bounds) {  // chunk bounds; with statistics == 2 every column's ColumnIndex, then every column's OffsetIndex, after the pages
+    for (size_t k = 0; k < cols.size(); k++) {
+      const std::string ci = pqx_column_index(cols[k], *x, k, (size_t)g.n_pages, &chunks[k]);
+      if (ci.empty()) continue;
+      chunks[k].column_index_off = (int64_t)(cur + L.tail.size()); chunks[k].column_index_len = (int64_t)ci.size();
+      L.tail += ci;
+    }
+    for (size_t k = 0; k < cols.size() && x->statistics == 2; k++) {
+      const std::string oi = pqx_offset_index(chunks[k], g.page_rows);
+      chunks[k].offset_index_off = (int64_t)(cur + L.tail.size()); chunks[k].offset_index_len = (int64_t)oi.size();
+      L.tail += oi;
+    }
+  }
+  L.footer = footer(cols, chunks, g.rows, (int64_t)cur, x);
   return L;
 }
 
 void pqw_finish(const PqwLayout& L, uint8_t* file) {
   for (const PqwLayout::Piece& p : L.pieces) std::memcpy(file + p.off, L.blob.data() + p.pos, p.len);
-  std::memcpy(file + L.body_bytes, L.footer.data(), L.footer.size());
+  uint8_t* end = file + L.body_bytes;
+  if (!L.tail.empty()) { std::memcpy(end, L.tail.data(), L.tail.size()); end += L.tail.size(); }  // the page index: the host's, after the image
+  std::memcpy(end, L.footer.data(), L.footer.size());
   const uint32_t len = (uint32_t)L.footer.size();
-  std::memcpy(file + L.body_bytes + L.footer.size(), &len, 4);
-  std::memcpy(file + L.body_bytes + L.footer.size() + 4, "PAR1", 4);
+  std::memcpy(end + L.footer.size(), &len, 4);
+  std::memcpy(end + L.footer.size() + 4, "PAR1", 4);
 }
 
 // ---- the host walk: what the two kernels do, tile by tile, over host arrays ---------------------------------------------------------------
@@ -617,7 +838,7 @@ void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
 }
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                            const int8_t* codecs, int32_t n_codecs) {
+                            const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index) {
   // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
   const size_t rows = (size_t)view.rows;
   std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
@@ -663,18 +884,21 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
   }
   int32_t page_rows = 0;
   const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
+  PqxIndex x = pqx_plan(index, cols.size());
   const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
   pqw_survey_host(cols, g, &stats, &tile_base);
+  if (x.statistics > 0) { pqx_prepare(cols, &x); pqx_minmax_host(cols, g, &x); }
   PqdHost delta;
   pqd_survey_host(cols, g, stats, tile_base, &delta);
-  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes);
+  const bool squeezed = pqw_compressed_columns(cols) > 0;  // then L is the staging image's layout, and the index is the final one's
+  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes, nullptr, squeezed ? nullptr : &x);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(cols, g, L.out, tile_base, image.data());
   pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
-  if (pqw_compressed_columns(cols) == 0) {
-    const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+  if (!squeezed) {
+    const size_t file_bytes = L.file_bytes();
     uint8_t* file = pqw_alloc_bytes(file_bytes, false);
     std::memcpy(file, image.data(), (size_t)L.body_bytes);
     pqw_finish(L, file);
@@ -695,8 +919,8 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     }
     page_elements[i] = (uint32_t)elements[i].size();
   }
-  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements);
-  const size_t file_bytes = (size_t)F.body_bytes + F.footer.size() + 8;
+  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements, &x);
+  const size_t file_bytes = F.file_bytes();
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
   for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
   for (size_t k = 0; k < cols.size(); k++)
@@ -708,7 +932,7 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
 
 #ifndef FDB_PQWRITE_HOST_ONLY
 void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                      const int8_t* codecs, int32_t n_codecs) {
+                      const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index) {
   std::vector<PqwInput> in;
   for (const DevColumn& c : b.cols) {
     PqwInput o;
@@ -717,13 +941,22 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   }
   int32_t page_rows = 0;
   const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
+  PqxIndex x = pqx_plan(index, cols.size());
+  const bool bounds = x.statistics > 0;
+  if (bounds) {
+    pqx_prepare(cols, &x);
+    for (size_t k = 0; k < cols.size(); k++)
+      if (((uintptr_t)cols[k].values & 15u) != 0)  // (the pass loads 16 bytes of values at a time)
+        throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (statistics)");
+  }
   const FdbPqwGeom g = pqw_geometry(b.rows, page_rows, cols.size());
   const size_t n_delta = pqw_delta_columns(cols), n_compressed = pqw_compressed_columns(cols);
   struct Bytes { uint8_t* p = nullptr; ~Bytes() { pqw_free_bytes(p); } } file;
   if (b.rows == 0 || cols.empty()) {  // nothing for the device to do (no data page: the dictionary pages are the host's, compressed or not)
     const std::vector<uint32_t> no_pages;
-    const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}), {}, n_compressed > 0 ? &no_pages : nullptr);
-    const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+    if (bounds) x.table.assign(2 * cols.size() * (size_t)g.n_pages, 0);  // (no page: no slot)
+    const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}), {}, n_compressed > 0 ? &no_pages : nullptr, &x);
+    const size_t file_bytes = L.file_bytes();
     file.p = pqw_alloc_bytes(file_bytes, false);
     pqw_finish(L, file.p);
     *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
@@ -769,17 +1002,38 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   b.note_reader(stream);
   hip_check(fdb_launch_pqw_survey(d_cols, g, d_stats, d_tile_base, stream), "parquet write: survey launch");
   hip_check(hipMemcpyAsync(stats.data(), d_stats, items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(page table)");
-  if (n_delta > 0) {
+  if (bounds) {  // the min / max pass (fdb_pqstats.hip): beside the survey, its table back in the same wait
     if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite survey"); }
+    std::vector<FdbPqxCol> xc(cols.size());
+    for (size_t k = 0; k < cols.size(); k++) {
+      std::memset(&xc[k], 0, sizeof(FdbPqxCol));
+      xc[k].values = cols[k].values; xc[k].validity = cols[k].validity; xc[k].mode = x.modes[k];
+      const std::vector<uint32_t>& r = x.ranks[k];
+      if (r.empty()) continue;
+      uint32_t* d_ranks = (uint32_t*)cs.alloc(r.size() * 4);
+      hip_check(hipMemcpyAsync(d_ranks, r.data(), r.size() * 4, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(dictionary ranks)");  // (`x` outlives the wait)
+      xc[k].ranks = d_ranks; xc[k].rank_len = (uint32_t)r.size();
+    }
+    const FdbPqxCol* d_xcols = (const FdbPqxCol*)cs.ctx->stage(xc.data(), xc.size() * sizeof(FdbPqxCol));
+    unsigned long long* d_table = (unsigned long long*)cs.alloc(2 * items * 8);
+    hip_check(hipMemsetAsync(d_table, 0xFF, items * 8, stream), "hipMemsetAsync(min table)");
+    hip_check(hipMemsetAsync(d_table + items, 0, items * 8, stream), "hipMemsetAsync(max table)");
+    hip_check(fdb_launch_pqx_minmax(d_xcols, g, d_table, stream), "parquet write: min / max launch");
+    x.table.assign(2 * items, 0);
+    hip_check(hipMemcpyAsync(x.table.data(), d_table, 2 * items * 8, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(min / max table)");
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite stats"); }
+  }
+  if (n_delta > 0) {
+    if (pt.on && !bounds) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite survey"); }
     if (compact) hip_check(fdb_launch_pqd_compact(d_dcols, (int32_t)n_delta, g, d_tile_base, stream), "parquet write: DELTA compaction launch");
     if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta compact"); }
     hip_check(fdb_launch_pqd_survey(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_page_bytes, stream), "parquet write: DELTA block survey launch");
     hip_check(hipMemcpyAsync(delta_bytes.data(), d_page_bytes, d_items * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(DELTA page sizes)");
   }
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  pt.mark(n_delta > 0 ? "pqwrite delta survey" : "pqwrite survey");
-  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes);
-  const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8, image_bytes = align_up((size_t)L.body_bytes + 8, 256);
+  pt.mark(n_delta > 0 ? "pqwrite delta survey" : bounds && pt.on ? "pqwrite wait" : "pqwrite survey");
+  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes, nullptr, n_compressed > 0 ? nullptr : &x);
+  const size_t file_bytes = L.file_bytes(), image_bytes = align_up((size_t)L.body_bytes + 8, 256);
   pt.mark("pqwrite layout");
   image.p = device_pool_alloc(b.device, image_bytes);
   FdbPqwPageOut* d_out = (FdbPqwPageOut*)cs.alloc(items * sizeof(FdbPqwPageOut));
@@ -836,8 +1090,8 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   if (!pages.empty()) hip_check(hipMemcpyAsync(page_elements.data(), d_page_elements, pages.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(compressed page sizes)");
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   pt.mark("pqwrite scan");
-  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements);
-  const size_t out_bytes = (size_t)F.body_bytes + F.footer.size() + 8;
+  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements, &x);
+  const size_t out_bytes = F.file_bytes();
   pt.mark("pqwrite final layout");
   std::vector<uint64_t> page_dst(F.pages.size());
   for (size_t i = 0; i < F.pages.size(); i++) page_dst[i] = F.pages[i].off;

@@ -10,6 +10,7 @@
 #include "fdb_arrow.h"
 #include "fdb_pqdelta.h"
 #include "fdb_pqsnappy.h"
+#include "fdb_pqstats.h"
 #include "fdb_pqwrite.h"
 #ifndef FDB_PQWRITE_HOST_ONLY
 #include "fdb_plan.h"
@@ -65,7 +66,30 @@ struct PqwLayout {
   std::vector<Piece> body_pieces;
   std::vector<uint64_t> chunk_off, chunk_len;
   void put_body(uint64_t off, const std::string& s);
+  // The page index (statistics == 2): every column's ColumnIndex, then every column's OffsetIndex — host bytes that follow the body in
+  // the file, before the footer; empty otherwise. The image stays the body.
+  std::string tail;
+  size_t file_bytes() const { return (size_t)body_bytes + tail.size() + footer.size() + 8; }
 };
+
+// What fdb_parquet_index_options asks for, checked (pqx_plan), and what the min / max pass found (fdb_pqstats.h) — the table of the
+// kernel on the device, of pqx_minmax_host in the self-test. With it pqw_layout writes Statistics.min_value / max_value, column_orders,
+// the page index and sorting_columns; without it (nullptr) the file of the calls before.
+struct PqxIndex {
+  int statistics = 0;                                 // 0 none, 1 chunk bounds, 2 + ColumnIndex and OffsetIndex
+  uint32_t limit = 16;                                // BYTE_ARRAY bounds of the ColumnIndex are cut to this many bytes
+  std::vector<fdb_parquet_sorting_column> sorting;
+  std::vector<int> modes;                             // per column: FDB_PQX_*
+  std::vector<std::vector<uint32_t>> ranks, entry_of_rank;  // per INDEX column: the dense rank of every entry, and an entry of every rank
+  std::vector<uint64_t> table;                        // 2 × columns × pages keys: mins, then maxes
+  bool any() const { return statistics > 0 || !sorting.empty(); }
+};
+// Every refusal of the index options (FDB_ERR_INVALID): nothing has been launched yet. `index` == nullptr: nothing asked.
+PqxIndex pqx_plan(const fdb_parquet_index_options* index, size_t n_cols);
+// modes, ranks and entry_of_rank of the columns (statistics > 0).
+void pqx_prepare(const std::vector<PqwColumn>& cols, PqxIndex* x);
+// The pass over host arrays: the table set to empty, then every tile folded in — in descending order, which min and max do not mind.
+void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, PqxIndex* x);
 
 // Options and columns checked, every refusal made (FDB_ERR_INVALID / FDB_ERR_UNSUPPORTED): nothing has been launched yet. `encodings`:
 // per column 0 (as ever) or 1 (DELTA_BINARY_PACKED; I64 and U64 columns only), n_encodings 0 or the column count. `codecs`: per column
@@ -82,8 +106,8 @@ FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
 // one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of the elements of the
 // page's Snappy block (the preamble not counted), as the compressor found them.
 PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes = {},
-                     const std::vector<uint32_t>* page_elements = nullptr);
-// Fills the holes of `file` (body_bytes + footer + 8 bytes long, the payloads in place) and appends footer, length and magic.
+                     const std::vector<uint32_t>* page_elements = nullptr, const PqxIndex* index = nullptr);
+// Fills the holes of `file` (L.file_bytes() long, the payloads in place) and appends the page index, if any, footer, length and magic.
 void pqw_finish(const PqwLayout& L, uint8_t* file);
 void pqw_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, std::vector<FdbPqwPageStat>* stats, std::vector<uint32_t>* tile_base);
 // `image`: zeroed, body_bytes rounded up to whole words (+ 4).
@@ -107,10 +131,10 @@ uint8_t* pqw_alloc_bytes(size_t n, bool pinned);
 void pqw_free_bytes(uint8_t* bytes);
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr,
-                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0);
+                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr);
 #ifndef FDB_PQWRITE_HOST_ONLY
 void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr, int32_t n_encodings = 0,
-                      const int8_t* codecs = nullptr, int32_t n_codecs = 0);
+                      const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr);
 #endif
 
 }  // namespace fdb

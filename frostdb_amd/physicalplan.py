@@ -172,6 +172,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_parquet_write_encoded.argtypes = [vp, vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
     L.fdb_batch_to_parquet_compressed.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
     L.fdb_selftest_parquet_write_compressed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
+    L.fdb_batch_to_parquet_indexed.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
+    L.fdb_selftest_parquet_write_indexed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
     L.fdb_bytes_free.restype = None
     _lib = L
@@ -391,6 +393,49 @@ def _parquet_codecs(compression, names):
     return (ctypes.c_int8 * max(1, len(wanted)))(*[PARQUET_WRITE_CODECS[e] for e in wanted]), len(wanted)
 
 
+class ParquetSortingColumn(ctypes.Structure):
+    """fdb_parquet_sorting_column."""
+    _fields_ = [("column", ctypes.c_int32), ("descending", ctypes.c_int8), ("nulls_first", ctypes.c_int8), ("pad", ctypes.c_int8 * 2)]
+
+
+class ParquetIndexOptions(ctypes.Structure):
+    """fdb_parquet_index_options."""
+    _fields_ = [("statistics", ctypes.c_int32), ("index_size_limit", ctypes.c_int32), ("sorting_columns", ctypes.c_void_p), ("n_sorting_columns", ctypes.c_int32)]
+
+
+PARQUET_STATISTICS = {None: 0, "chunk": 1, "page": 2}
+
+
+def _parquet_index_options(statistics, index_size_limit, sorting_columns, names):
+    """`statistics`: None, "chunk" (Statistics.min_value / max_value per chunk) or "page" (the same + ColumnIndex and OffsetIndex).
+    `index_size_limit`: bytes a BYTE_ARRAY bound of the ColumnIndex is cut to (0 = 16). `sorting_columns`: a sequence of
+    (name or index, descending=False, nulls_first=False), written as RowGroup.sorting_columns. Returns the struct and what it points
+    at, or (None, None) when nothing is asked: the caller then calls what it called without these arguments."""
+    if statistics is None and not index_size_limit and not sorting_columns:
+        return None, None
+    if not (statistics is None or isinstance(statistics, str)) or statistics not in PARQUET_STATISTICS:
+        _raise(FDB_ERR_INVALID, "parquet write: unknown statistics %r (None, 'chunk' or 'page')" % (statistics,))
+    if isinstance(index_size_limit, bool) or not isinstance(index_size_limit, int) or not -2**31 <= index_size_limit < 2**31:
+        _raise(FDB_ERR_INVALID, "parquet write: index_size_limit is %r (0: 16, else 1 to 65536)" % (index_size_limit,))
+    wanted = []
+    for entry in (sorting_columns or ()):
+        entry = tuple(entry) if isinstance(entry, (tuple, list)) else (entry,)
+        if not 1 <= len(entry) <= 3:
+            _raise(FDB_ERR_INVALID, "parquet write: a sorting column is (name or index, descending=False, nulls_first=False), got %r" % (entry,))
+        col = entry[0]
+        if isinstance(col, str):
+            if col not in names:
+                _raise(FDB_ERR_INVALID, "parquet write: `sorting_columns` names no column of the record: %s" % col)
+            col = names.index(col)
+        elif isinstance(col, bool) or not isinstance(col, int) or not -2**31 <= col < 2**31:
+            _raise(FDB_ERR_INVALID, "parquet write: a sorting column is a name or an index, got %r" % (col,))
+        wanted.append((col, 1 if len(entry) > 1 and entry[1] else 0, 1 if len(entry) > 2 and entry[2] else 0))
+    arr = (ParquetSortingColumn * max(1, len(wanted)))()
+    for i, (col, desc, first) in enumerate(wanted):
+        arr[i].column, arr[i].descending, arr[i].nulls_first = col, desc, first
+    return ParquetIndexOptions(PARQUET_STATISTICS[statistics], index_size_limit, ctypes.cast(arr, ctypes.c_void_p) if wanted else None, len(wanted)), arr
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -400,17 +445,24 @@ def _take_bytes(rc, out, n) -> bytes:
         lib().fdb_bytes_free(out.value)
 
 
-def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None) -> bytes:
-    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression)`` writes, byte for byte, made
-    without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
-    fdb_selftest_parquet_write_compressed): the same layout, headers and footer, the kernels replaced by a host walk of the code they
+def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0,
+                           sorting_columns=None) -> bytes:
+    """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
+    made without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
+    fdb_selftest_parquet_write_compressed, with `statistics`, `index_size_limit` or `sorting_columns`
+    fdb_selftest_parquet_write_indexed): the same layout, headers and footer, the kernels replaced by a host walk of the code they
     compile."""
     names = list(record.schema.names)
     opts, _keep = _parquet_write_options(page_rows, optional, names)
     enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
+    index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
     out, n = ctypes.c_void_p(), ctypes.c_int64()
     with ExportedBatch(record) as ex:
-        if compression is not None:
+        if index is not None:
+            codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
+            rc = lib().fdb_selftest_parquet_write_indexed(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
+                                                          n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
+        elif compression is not None:
             codecs, n_codecs = _parquet_codecs(compression, names)
             rc = lib().fdb_selftest_parquet_write_compressed(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
                                                              n_enc, ctypes.cast(codecs, ctypes.c_void_p), n_codecs, ctypes.byref(out), ctypes.byref(n))
@@ -745,7 +797,7 @@ class ResidentBatch:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
-    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None) -> bytes:
+    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0, sorting_columns=None) -> bytes:
         """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, data pages V1 of
         `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
@@ -755,10 +807,21 @@ class ResidentBatch:
         "snappy" (every column), a sequence per column or a dict by name of None / "uncompressed" / "snappy": every page of such a
         column — dictionary page and data pages — is written as a Snappy block, compressed on the device in fragments of 32 KiB
         (fdb_batch_to_parquet_compressed), and only the compressed file crosses the link; for the length of the call the device holds
-        about three times the file body. DELTA and SNAPPY go together."""
+        about three times the file body. DELTA and SNAPPY go together. `statistics`: None, "chunk" — Statistics.min_value / max_value
+        per column chunk and FileMetaData.column_orders, the bounds found by one more pass on the device — or "page": the same and the
+        Parquet page index (ColumnIndex and OffsetIndex per column, between the pages and the footer), which FrostDB's own scan prunes
+        row groups with; `index_size_limit`: the bytes a string bound of the ColumnIndex is cut to (0 = 16); `sorting_columns`: a
+        sequence of (name or index, descending=False, nulls_first=False) written as RowGroup.sorting_columns — metadata only, the rows
+        are not checked (fdb_batch_to_parquet_indexed). Without these three the call is what it was."""
         opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
         out, n = ctypes.c_void_p(), ctypes.c_int64()
-        if compression is not None:
+        index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, self.column_names)
+        if index is not None:
+            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
+            codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
+            rc = lib().fdb_batch_to_parquet_indexed(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,
+                                                    ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
+        elif compression is not None:
             enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
             codecs, n_codecs = _parquet_codecs(compression, self.column_names)
             rc = lib().fdb_batch_to_parquet_compressed(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc, ctypes.cast(codecs, ctypes.c_void_p),

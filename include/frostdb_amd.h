@@ -535,7 +535,8 @@ FDB_API int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_
  * column's dictionary entry by entry, duplicates included — and RLE_DICTIONARY data pages at width bits(entries − 1): one bit-packed
  * run per page, or one RLE run where all of a page's non-NULL indices are equal. A column that is all NULL over an empty dictionary has
  * no dictionary page and PLAIN pages of zero values. The footer carries what a reader needs (types, encodings, sizes, page offsets)
- * and Statistics.null_count per column; min / max statistics and sorting_columns are not written. A zero-row batch gives a valid file
+ * and Statistics.null_count per column; min / max statistics, the page index and sorting_columns are written by
+ * fdb_batch_to_parquet_indexed (below) and by no other call. A zero-row batch gives a valid file
  * whose row group has zero rows. The record's own columns are the schema: a field the record lacks is not written as all-NULL, as the
  * reference does for a schema it is handed (writeNull).
  *
@@ -599,6 +600,53 @@ FDB_API int fdb_selftest_parquet_write_encoded(struct ArrowArray* batch, struct 
 /* codecs: per column parquet's CompressionCodec number, 0 = UNCOMPRESSED, 1 = SNAPPY; n_codecs: 0 (all 0) or the batch's column count */
 FDB_API int fdb_batch_to_parquet_compressed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_compressed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes);
+/* The same two calls with min / max statistics, the Parquet page index and RowGroup.sorting_columns as well — what FrostDB's own scan
+ * reads of a part: BinaryScalarOperation opens each chunk's ColumnIndex() for per-page NullCount, MinValue and MaxValue
+ * (query/expr/binaryscalarexpr.go:87-178), filter.go:174-178 and pqarrow/arrow.go:725-770, :935-971 do the same for all-NULL chunks,
+ * single-value chunks and Distinct, and a sorted part is known by its sorting_columns (dynparquet/schema.go:342, :837-847). All of it is
+ * written only when asked for: with index == NULL, or statistics == 0 and no sorting column, the file is
+ * fdb_batch_to_parquet_compressed's, byte for byte, made by the same path — no further launch, allocation, copy or footer field.
+ *
+ * statistics ≥ 1: FileMetaData.column_orders (field 7, one TypeDefinedOrder per column: without it readers ignore the bounds) and, per
+ * chunk, Statistics.min_value / max_value (fields 6 / 5, beside null_count; the deprecated fields 1 / 2 are not written) over the chunk's
+ * non-NULL values, exact and never cut, BYTE_ARRAY included; a column without a non-NULL, non-NaN value has neither. int64: signed order,
+ * 8 bytes little-endian; uint64: unsigned order (Int(64, unsigned)), 8 bytes; float64: numeric order, NaNs left out, 8 bytes — a minimum
+ * equal to zero is written −0.0 and a maximum equal to zero +0.0 whatever signs occurred (parquet-format's rule); bool: false < true, one
+ * byte 0 / 1; dictionary and plain string / binary columns: the entries' bytes compared as unsigned bytes, shorter first on a common
+ * prefix, over the entries that non-NULL rows REFER to — an unused entry never shows, duplicate entries are one value.
+ *
+ * statistics == 2: after the last chunk's pages and before the footer every column's ColumnIndex, then every column's OffsetIndex;
+ * each ColumnChunk names them (fields 4 … 7); RowGroup.total_compressed_size keeps counting the pages only. OffsetIndex: one
+ * PageLocation per data page (the dictionary page is not one) — the offset of the page header, header + body as stored (for a SNAPPY
+ * column: of the final layout), first_row_index = page × page_rows. ColumnIndex: null_pages, min_values, max_values, boundary_order,
+ * null_counts; a page without a non-NULL value is a null page with empty bounds; bounds as above, but a BYTE_ARRAY bound longer than
+ * index_size_limit is cut — a minimum to its prefix, a maximum to its prefix with trailing 0xFF bytes dropped and the last remaining
+ * byte incremented (a prefix of 0xFF only: the maximum stays whole); boundary_order, judged on the non-null pages' bounds as written:
+ * ASCENDING when mins and maxes are both non-decreasing (also for zero or one such page), else DESCENDING when both are non-increasing,
+ * else UNORDERED. A float64 column in which some page has values but only NaNs gets no ColumnIndex (the format cannot say it; Arrow
+ * does the same); it keeps its OffsetIndex, and its chunk bounds come from the other pages.
+ *
+ * sorting_columns: RowGroup.sorting_columns (field 4) as given — metadata only, the rows are not checked against it.
+ *
+ * The bounds are found on the device (fdb_pqstats.hip): one more pass after the survey, a workgroup per (column, page, tile) folding
+ * order-preserving 64-bit keys (fdb_pqstats.h; a dictionary column's through its dense byte-order ranks, the ranks Sort and Merge use,
+ * uploaded from the call's arena) into a (column, page) table with one atomicMin and one atomicMax per tile; the table comes back with
+ * the survey's in the wait that is there already — the call waits no more often than without statistics. The host folds pages into
+ * chunk bounds, maps the keys back, applies the zero rule and the cut, and writes the thrift; the index bytes are the host's and follow
+ * the image. The 8-byte columns must be 16-byte aligned on the device (every resident record's are).
+ *
+ * Refused before anything is launched, FDB_ERR_INVALID: statistics outside 0 … 2; index_size_limit outside 0 … 65 536;
+ * n_sorting_columns negative, or positive without the array; a sorting column outside the record's columns or named twice; and
+ * everything the calls above refuse, unchanged. fdb_parquet_write_options keeps its layout. */
+typedef struct fdb_parquet_sorting_column { int32_t column; int8_t descending; int8_t nulls_first; int8_t pad[2]; } fdb_parquet_sorting_column;
+typedef struct fdb_parquet_index_options {
+  int32_t statistics;        /* 0 none · 1 chunk Statistics.min_value / max_value · 2 the same + ColumnIndex and OffsetIndex */
+  int32_t index_size_limit;  /* BYTE_ARRAY bounds in the ColumnIndex are cut to this many bytes; 0 = 16 (dynparquet.ColumnIndexSize), else 1 … 65 536 */
+  const fdb_parquet_sorting_column* sorting_columns;  /* RowGroup.sorting_columns, in this order; metadata only, the rows are not checked */
+  int32_t n_sorting_columns;
+} fdb_parquet_index_options;
+FDB_API int fdb_batch_to_parquet_indexed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_indexed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry

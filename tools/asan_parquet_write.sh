@@ -5,6 +5,8 @@
 # DELTA_BINARY_PACKED passes (fdb_pqdelta.h) over seeded random records and options, with fdb_arrow.cpp's dictionary constructors; and the
 # SNAPPY compressor's host walk (fdb_pqsnappy.h) over the same records with codecs per column at random and over bodies around one and
 # two fragments, every page inflated again by the library's host decoder (fdb_codec.cpp).
+# Every record is also written with index options at random — statistics, a cut limit, sorting columns: the min / max pass's host walk
+# (fdb_pqstats.h), chunk bounds, ColumnIndex and OffsetIndex — and the index is read back by a small thrift reader of the program's own.
 # No GPU, no HIP runtime (fdb_codec.h takes its types from the HIP headers), no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

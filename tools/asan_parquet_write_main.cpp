@@ -7,6 +7,10 @@
 // the compressor's host walk (fdb_pqsnappy.h) runs over the staging image's page bodies, the file is laid out again, and every page of
 // the final file — dictionary pages too — is inflated by the library's host decoder (fdb_codec.cpp snappy_block) into a buffer of exactly
 // the body's size and compared with the body; bodies of 0 … 2 fragments + 1 bytes of several kinds go through the same two.
+// Every record is also written with index options at random (statistics 0 … 2, a cut limit, sorting columns): the min / max pass's host
+// walk (pqx_minmax_host: the keys of fdb_pqstats.h that the kernel compiles) fills the table, the layout writes chunk bounds, ColumnIndex
+// and OffsetIndex, and a small thrift reader of this file's own reads the index back out of a buffer sized exactly and holds every
+// page's bounds, NULL counts and location against a plain loop over the record.
 // No GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
@@ -120,6 +124,126 @@ static void snappy_bodies(uint64_t* seed) {
   }
 }
 
+// ---- the page index, read back ---------------------------------------------------------------------------------------------------------
+struct IndexReader {
+  const std::vector<uint8_t>& b;
+  size_t at = 0;
+  uint8_t byte() { CHECK(at < b.size()); return b[at++]; }
+  uint64_t varint() { uint64_t v = 0; for (int shift = 0;; shift += 7) { CHECK(shift < 70); const uint8_t x = byte(); v |= (uint64_t)(x & 0x7F) << (shift < 64 ? shift : 63); if (x < 0x80) return v; } }
+  int field(int* last) { const uint8_t h = byte(); if (h == 0) return 0; CHECK((h >> 4) != 0); *last += h >> 4; return h & 15; }  // (the writer never needs the long form here)
+  size_t list(int elem) { const uint8_t h = byte(); CHECK((h & 15) == elem); return (h >> 4) == 15 ? (size_t)varint() : (size_t)(h >> 4); }
+  std::string binary() { const size_t n = (size_t)varint(); CHECK(at + n <= b.size()); std::string v((const char*)b.data() + at, n); at += n; return v; }
+};
+struct ReadColumnIndex { std::vector<bool> null_pages; std::vector<std::string> mins, maxs; int order = -1; std::vector<int64_t> null_counts; };
+static ReadColumnIndex read_column_index(IndexReader* r) {
+  ReadColumnIndex ci;
+  int last = 0;
+  CHECK(r->field(&last) == 9 && last == 1);
+  for (size_t n = r->list(1), i = 0; i < n; i++) { const uint8_t v = r->byte(); CHECK(v == 1 || v == 2); ci.null_pages.push_back(v == 1); }
+  CHECK(r->field(&last) == 9 && last == 2);
+  for (size_t n = r->list(8), i = 0; i < n; i++) ci.mins.push_back(r->binary());
+  CHECK(r->field(&last) == 9 && last == 3);
+  for (size_t n = r->list(8), i = 0; i < n; i++) ci.maxs.push_back(r->binary());
+  CHECK(r->field(&last) == 5 && last == 4);
+  ci.order = (int)unzigzag(r->varint());
+  CHECK(r->field(&last) == 9 && last == 5);
+  for (size_t n = r->list(6), i = 0; i < n; i++) ci.null_counts.push_back(unzigzag(r->varint()));
+  CHECK(r->field(&last) == 0);
+  return ci;
+}
+struct ReadLocation { int64_t off, bytes, first_row; };
+static std::vector<ReadLocation> read_offset_index(IndexReader* r) {
+  std::vector<ReadLocation> out;
+  int last = 0;
+  CHECK(r->field(&last) == 9 && last == 1);
+  for (size_t n = r->list(12), i = 0; i < n; i++) {
+    ReadLocation l;
+    int f = 0;
+    CHECK(r->field(&f) == 6 && f == 1); l.off = unzigzag(r->varint());
+    CHECK(r->field(&f) == 5 && f == 2); l.bytes = unzigzag(r->varint());
+    CHECK(r->field(&f) == 6 && f == 3); l.first_row = unzigzag(r->varint());
+    CHECK(r->field(&f) == 0);
+    out.push_back(l);
+  }
+  CHECK(r->field(&last) == 0);
+  return out;
+}
+
+// a < b in the column's order, by a plain comparison of the values themselves (not by the keys under test)
+static bool value_less(const Column& c, int64_t a, int64_t b) {
+  if (c.kind == ColKind::DICT) return c.dict->values[c.idx[(size_t)a]] < c.dict->values[c.idx[(size_t)b]];
+  const uint64_t x = c.v64[(size_t)a], y = c.v64[(size_t)b];
+  if (c.kind == ColKind::I64) return (int64_t)x < (int64_t)y;
+  if (c.kind == ColKind::F64) { double dx, dy; std::memcpy(&dx, &x, 8); std::memcpy(&dy, &y, 8); return dx < dy || (dx == dy && (x >> 63) > (y >> 63)); }  // (−0.0 below +0.0: the zero rule decides what is written)
+  if (c.kind == ColKind::BOOL) return (x >= 2) < (y >= 2);
+  return x < y;
+}
+static bool counts(const Column& c, int64_t r) {
+  if (c.kind != ColKind::F64) return true;
+  double d;
+  std::memcpy(&d, &c.v64[(size_t)r], 8);
+  return d == d;
+}
+static std::string written(const Column& c, int64_t r, bool is_max) {
+  if (c.kind == ColKind::DICT) return c.dict->values[c.idx[(size_t)r]];
+  uint64_t v = c.v64[(size_t)r];
+  if (c.kind == ColKind::BOOL) return std::string(1, (char)(v >= 2));
+  if (c.kind == ColKind::F64 && (v << 1) == 0) v = is_max ? 0 : 1ull << 63;
+  return std::string((const char*)&v, 8);
+}
+
+// The record written with `index`: the tail holds what a loop over the record says, page by page.
+static void check_index(const std::vector<Column>& cols, const std::vector<PqwColumn>& pc, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const PqwLayout& L,
+                        const PqxIndex& x, const std::vector<uint64_t>& chunk_off, const std::vector<uint64_t>& chunk_len) {
+  if (x.statistics < 2) { CHECK(L.tail.empty()); return; }
+  const std::vector<uint8_t> exact(L.tail.begin(), L.tail.end());  // (sized exactly: a reader that runs past the index is caught)
+  IndexReader r{exact};
+  const size_t n_pages = (size_t)g.n_pages;
+  for (size_t k = 0; k < cols.size(); k++) {
+    const Column& c = cols[k];
+    std::vector<int64_t> lo(n_pages, -1), hi(n_pages, -1);
+    bool sayable = true;
+    for (size_t p = 0; p < n_pages; p++) {
+      for (int64_t row = fdb_pqw_page_first(g, (int64_t)p); row < fdb_pqw_page_end(g, (int64_t)p); row++) {
+        if (!(pc[k].validity == nullptr || c.valid(row)) || !counts(c, row)) continue;
+        if (lo[p] < 0 || value_less(c, row, lo[p])) lo[p] = row;
+        if (hi[p] < 0 || value_less(c, hi[p], row)) hi[p] = row;
+      }
+      if (lo[p] < 0 && stats[k * n_pages + p].count > 0) sayable = false;
+    }
+    if (!sayable) continue;  // a page of NaNs only: the column has no ColumnIndex
+    const ReadColumnIndex ci = read_column_index(&r);
+    CHECK(ci.null_pages.size() == n_pages && ci.mins.size() == n_pages && ci.maxs.size() == n_pages && ci.null_counts.size() == n_pages && ci.order >= 0 && ci.order <= 2);
+    for (size_t p = 0; p < n_pages; p++) {
+      const int64_t n = fdb_pqw_page_end(g, (int64_t)p) - fdb_pqw_page_first(g, (int64_t)p);
+      CHECK(ci.null_counts[p] == n - (int64_t)stats[k * n_pages + p].count && ci.null_pages[p] == (stats[k * n_pages + p].count == 0));
+      if (lo[p] < 0) { CHECK(ci.mins[p].empty() && ci.maxs[p].empty()); continue; }
+      std::string mn = written(c, lo[p], false), mx = written(c, hi[p], true);
+      if (c.kind == ColKind::DICT) {
+        if (mn.size() > x.limit) mn.resize(x.limit);
+        if (mx.size() > x.limit) {
+          std::string cut = mx.substr(0, x.limit);
+          while (!cut.empty() && (unsigned char)cut.back() == 0xFF) cut.pop_back();
+          if (!cut.empty()) { cut.back() = (char)(cut.back() + 1); mx = cut; }
+        }
+      }
+      CHECK(ci.mins[p] == mn && ci.maxs[p] == mx);
+    }
+  }
+  for (size_t k = 0; k < cols.size(); k++) {
+    const std::vector<ReadLocation> locs = read_offset_index(&r);
+    CHECK(locs.size() == n_pages);
+    uint64_t at = chunk_off[k];
+    for (size_t p = 0; p < n_pages; p++) {
+      CHECK(locs[p].first_row == (int64_t)p * g.page_rows && locs[p].bytes > 0 && (uint64_t)locs[p].off >= at);  // (a dictionary page may sit in front of the first)
+      CHECK(p == 0 || (uint64_t)locs[p].off == at);
+      at = (uint64_t)locs[p].off + (uint64_t)locs[p].bytes;
+    }
+    CHECK(n_pages == 0 || at == chunk_off[k] + chunk_len[k]);
+  }
+  CHECK(r.at == exact.size());
+}
+
 static void one_record(uint64_t* seed, int round) {
   static const int64_t row_choices[] = {0, 1, 7, 63, 64, 65, 127, 128, 129, 1000, 4095, 4096, 4097, 9000};
   static const int32_t page_choices[] = {0, 64, 128, 4096, 8192, 65536};
@@ -195,7 +319,8 @@ static void one_record(uint64_t* seed, int round) {
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(pc, g, L.out, tile_base, image.data());
   pqd_encode_host(pc, g, stats, dh, L.delta_out, image.data());
-  const size_t file_bytes = (size_t)L.body_bytes + L.footer.size() + 8;
+  const size_t file_bytes = L.file_bytes();
+  CHECK(L.tail.empty());
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
   std::memcpy(file, image.data(), (size_t)L.body_bytes);
   for (size_t b = (size_t)L.body_bytes; b < image.size(); b++) CHECK(image[b] == 0);  // nothing is written past the body
@@ -249,6 +374,25 @@ static void one_record(uint64_t* seed, int round) {
     }
   }
   for (uint64_t b = 0; b < L.body_bytes; b++) CHECK(owner[b] != 0);  // every byte of the body belongs to somebody
+  // the same record with index options at random: the body is the same, the index follows it, the footer names it
+  static const int32_t limit_choices[] = {0, 1, 3, 16, 17, 65536};
+  std::vector<fdb_parquet_sorting_column> sorting;
+  for (size_t k = 0; k < n_cols; k++) if (rnd(seed) % 3 == 0) sorting.push_back(fdb_parquet_sorting_column{(int32_t)k, (int8_t)(rnd(seed) & 1), (int8_t)(rnd(seed) & 1), {0, 0}});
+  const fdb_parquet_index_options iopt{(int32_t)(rnd(seed) % 3), limit_choices[rnd(seed) % 6], sorting.empty() ? nullptr : sorting.data(), (int32_t)sorting.size()};
+  PqxIndex x = pqx_plan(&iopt, n_cols);
+  CHECK(x.statistics == iopt.statistics && x.limit == (iopt.index_size_limit == 0 ? 16u : (uint32_t)iopt.index_size_limit) && x.sorting.size() == sorting.size());
+  if (x.statistics > 0) { pqx_prepare(pc, &x); pqx_minmax_host(pc, g, &x); }
+  {
+    const PqwLayout I = pqw_layout(pc, g, stats, dh.page_bytes, nullptr, &x);
+    CHECK(I.body_bytes == L.body_bytes && I.blob == L.blob && (x.any() || I.footer == L.footer) && (x.statistics == 2 || I.tail.empty()));
+    check_index(cols, pc, g, stats, I, x, I.chunk_off, I.chunk_len);
+    uint8_t* indexed = pqw_alloc_bytes(I.file_bytes(), false);
+    std::memcpy(indexed, image.data(), (size_t)I.body_bytes);
+    pqw_finish(I, indexed);
+    CHECK(std::memcmp(indexed, file, (size_t)L.body_bytes) == 0 && std::memcmp(indexed + I.file_bytes() - 4, "PAR1", 4) == 0);
+    CHECK(I.tail.empty() || std::memcmp(indexed + I.body_bytes, I.tail.data(), I.tail.size()) == 0);
+    pqw_free_bytes(indexed);
+  }
   // the same record with a codec per column at random (three rounds in four): what fdb_selftest_parquet_write_compressed does, step by step
   std::vector<int8_t> codecs;
   for (size_t k = 0; k < n_cols; k++) codecs.push_back((int8_t)(rnd(seed) & 1));
@@ -274,9 +418,10 @@ static void one_record(uint64_t* seed, int round) {
       page_elements.push_back((uint32_t)e.size());
       elements.push_back(std::move(e));
     }
-    const PqwLayout F = pqw_layout(cc, g, stats, dh.page_bytes, &page_elements);
+    const PqwLayout F = pqw_layout(cc, g, stats, dh.page_bytes, &page_elements, &x);  // (the index of a compressed file: of the final layout)
     CHECK(F.pages.size() == S.pages.size());
-    const size_t out_bytes = (size_t)F.body_bytes + F.footer.size() + 8;
+    check_index(cols, cc, g, stats, F, x, F.chunk_off, F.chunk_len);
+    const size_t out_bytes = F.file_bytes();
     uint8_t* out_file = pqw_alloc_bytes(out_bytes, false);
     std::vector<uint8_t> own(F.body_bytes, 0);
     for (const PqwLayout::Piece& p : F.pieces) for (size_t b = 0; b < p.len; b++) { CHECK(p.off + b < F.body_bytes && own[p.off + b] == 0); own[p.off + b] = 1; }
@@ -340,6 +485,13 @@ static void refusals() {
   const int8_t minus = -1;
   CHECK(codec_code(&delta, 1) == FDB_OK && codec_code(nullptr, 0) == FDB_OK);
   CHECK(codec_code(&two, 1) == FDB_ERR_INVALID && codec_code(&minus, 1) == FDB_ERR_INVALID && codec_code(both, 2) == FDB_ERR_INVALID && codec_code(nullptr, 1) == FDB_ERR_INVALID);
+  const auto index_code = [&](const fdb_parquet_index_options& o, size_t n) { try { pqx_plan(&o, n); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const fdb_parquet_sorting_column s0{0, 0, 0, {0, 0}}, s2{2, 1, 1, {0, 0}}, twice[2] = {s0, s0}, ok2[2] = {s2, s0};
+  CHECK(index_code(fdb_parquet_index_options{0, 0, nullptr, 0}, 1) == FDB_OK && index_code(fdb_parquet_index_options{2, 65536, ok2, 2}, 3) == FDB_OK && !pqx_plan(nullptr, 1).any());
+  CHECK(index_code(fdb_parquet_index_options{3, 0, nullptr, 0}, 1) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{-1, 0, nullptr, 0}, 1) == FDB_ERR_INVALID);
+  CHECK(index_code(fdb_parquet_index_options{1, 65537, nullptr, 0}, 1) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{0, -1, nullptr, 0}, 1) == FDB_ERR_INVALID);
+  CHECK(index_code(fdb_parquet_index_options{1, 0, &s2, 1}, 2) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{1, 0, twice, 2}, 2) == FDB_ERR_INVALID);
+  CHECK(index_code(fdb_parquet_index_options{1, 0, nullptr, 1}, 2) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{1, 0, &s0, -1}, 2) == FDB_ERR_INVALID);
   in[0].kind = ColKind::F64;
   CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED);
   in[0].kind = ColKind::BOOL;

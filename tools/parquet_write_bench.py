@@ -21,9 +21,13 @@ own figures are the SNAPPY call's — among the phases place_compress_ms (the ho
 size scan with the wait for the page sizes), final_layout_ms and gather_ms — and the uncompressed PLAIN call on the same record in the
 same process goes into the line as with --delta, with plain_floor_ms, the bare copy of ITS file's bytes, beside floor_ms, that of the
 compressed file's.
+With --stats the record is written uncompressed and PLAIN with statistics="page" (fdb_batch_to_parquet_indexed): chunk bounds, ColumnIndex
+and OffsetIndex of every column. The line's own figures are that call's — among the phases stats_ms, the min / max pass of
+fdb_pqstats.hip timed apart (rank upload, table reset, kernel, its wait), and wait_ms, what is then left of the survey's wait — and the
+call without statistics on the same record in the same process, in front of it, goes into the line as with --delta.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats] [--out FILE]
 """
 import argparse
 import io
@@ -48,6 +52,7 @@ LABELS = [10, 50, 100, 500, 1000]
 PHASES = ["survey", "layout", "encode", "copy", "host tail"]
 DELTA_PHASES = ["delta compact", "delta survey", "delta encode"]
 SNAPPY_PHASES = ["compress", "scan", "final layout", "gather"]
+STATS_PHASES = ["stats", "wait"]
 
 
 def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
@@ -75,7 +80,7 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps, encodings=None, compression=None):
+def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None):
     """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
     os.environ["FDB_PROFILE"] = "1"
     sys.stderr.flush()
@@ -84,7 +89,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None):
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -92,7 +97,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None):
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = statistics.median(us) / 1e3 if us else None
     return out
@@ -107,16 +112,18 @@ def main():
     ap.add_argument("--baseline-reps", type=int, default=3)
     ap.add_argument("--delta", action="store_true", help="write `timestamp` DELTA_BINARY_PACKED; the PLAIN call goes into the same line")
     ap.add_argument("--snappy", action="store_true", help="write every column SNAPPY and `timestamp` DELTA + SNAPPY; the uncompressed PLAIN call goes into the same line")
+    ap.add_argument("--stats", action="store_true", help="write statistics and the page index (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert not (args.delta and args.snappy), "--delta or --snappy"
+    assert args.delta + args.snappy + args.stats <= 1, "--delta, --snappy or --stats"
     record = make_record(args.rows)
     rb = pp.ResidentBatch(record)
     del record
     try:
         encodings = {"timestamp": "delta"} if args.delta or args.snappy else None
         compression = "snappy" if args.snappy else None
-        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression)
+        stats = "page" if args.stats else None
+        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats)
         file_bytes = len(data)
         md = pq.ParquetFile(io.BytesIO(data)).metadata
         assert md.num_rows == args.rows and md.num_row_groups == 1
@@ -125,6 +132,8 @@ def main():
         if args.snappy:
             assert all(md.row_group(0).column(j).compression == "SNAPPY" for j in range(md.num_columns))
             column_bytes = {md.row_group(0).column(j).path_in_schema: [md.row_group(0).column(j).total_compressed_size, md.row_group(0).column(j).total_uncompressed_size] for j in range(md.num_columns)}
+        if args.stats:
+            assert all(md.row_group(0).column(j).has_column_index and md.row_group(0).column(j).has_offset_index and md.row_group(0).column(j).statistics.has_min_max for j in range(md.num_columns))
         del data
         import ctypes
         opts = pp.ParquetWriteOptions(args.page_rows, 0, None)
@@ -133,9 +142,13 @@ def main():
 
         codecs = (ctypes.c_int8 * n_columns)(*([1] * n_columns))
 
-        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy):
+        index = pp.ParquetIndexOptions(2, 0, None, 0)
+
+        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
-            if snappy:
+            if indexed:
+                rc = pp.lib().fdb_batch_to_parquet_indexed(rb.handle, ctypes.byref(opts), None, 0, None, 0, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
+            elif snappy:
                 rc = pp.lib().fdb_batch_to_parquet_compressed(rb.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_columns, ctypes.cast(codecs, ctypes.c_void_p), n_columns,
                                                               ctypes.byref(out), ctypes.byref(n))
             elif delta:
@@ -145,15 +158,15 @@ def main():
             assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
         plain = {}
-        if args.delta or args.snappy:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+        if args.delta or args.snappy or args.stats:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
             plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
-            ms, every = median_ms(lambda: c_call(False, plain_bytes, False), args.reps, args.warmup)
+            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False), args.reps, args.warmup)
             ph = profiled_phases(rb, args.page_rows, args.reps)
             plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
             plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
-        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression), args.reps, 1)
-        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats)
 
         def bare_copy_ms(n_bytes):
             dev = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
@@ -196,7 +209,9 @@ def main():
         line.update({"delta": ["timestamp"], "snappy": "all", "to_parquet_max_ms": r3(max(to_parquet_all)), "delta_compact_ms": r3(phases["delta compact"]),
                      "delta_survey_ms": r3(phases["delta survey"]), "delta_encode_ms": r3(phases["delta encode"]), "place_compress_ms": r3(phases["compress"]), "scan_ms": r3(phases["scan"]),
                      "final_layout_ms": r3(phases["final layout"]), "gather_ms": r3(phases["gather"]), "column_bytes": column_bytes})
-    if args.delta or args.snappy:
+    if args.stats:
+        line.update({"statistics": "page", "to_parquet_max_ms": r3(max(to_parquet_all)), "stats_ms": r3(phases["stats"]), "wait_ms": r3(phases["wait"])})
+    if args.delta or args.snappy or args.stats:
         line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
