@@ -40,7 +40,11 @@ void Plan::hash_layout() {
   kw = (kw + 3) & ~3;
   const int ew = (int)((3 + aggs_.size() + 3) / 4 * 4);
   if (h_table_ == nullptr) { h_key_words_ = kw; h_key_used_ = used; h_entry_words_ = ew; return; }
-  if (kw != h_key_words_) {  // columns were added: widen the key store (same capacity, same fingerprints)
+  // columns were added: widen the key store (same capacity, same fingerprints). A column that lands on what was tail padding takes the
+  // same road although the tuples keep their width: the padding of the tuples already there is not zero (the specialised scan leaves
+  // a canonical tuple's padding unwritten, an in-place merge copies the source's), and the re-hash writes the words past the old
+  // used prefix as 0 = NULL.
+  if (kw != h_key_words_ || used > h_key_used_) {
     uint32_t* nk = (uint32_t*)ctx_->dev_alloc((size_t)h_capacity_ * kw * 4);  // (no initialisation needed, see fdb_launch_hash_rehash)
     unsigned long long* nt = (unsigned long long*)ctx_->dev_alloc((size_t)h_capacity_ * ew * 8);
     unsigned long long idents[FDB_MAX_AGGS] = {0};
