@@ -568,6 +568,11 @@ const char* fdb_batch_column_name(const fdb_batch* batch, int32_t index) {
   return batch->b->cols[(size_t)index].name.c_str();
 }
 
+const char* fdb_batch_column_format(const fdb_batch* batch, int32_t index) {
+  if (batch == nullptr || !batch->b || index < 0 || (size_t)index >= batch->b->cols.size()) return nullptr;
+  return batch->b->cols[(size_t)index].format.c_str();
+}
+
 int fdb_sampler_create(int64_t size, uint64_t seed, int device, fdb_sampler** out) {
   return guard(nullptr, [&] {
     if (out == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
@@ -776,6 +781,27 @@ int fdb_selftest_parquet_write_indexed(struct ArrowArray* batch, struct ArrowSch
     fdb::HostRecordView view;
     fdb::view_record(batch, schema, &view);
     fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index);
+  });
+}
+
+int fdb_batch_to_parquet_filtered(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
+                                  const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom);
+  });
+}
+
+int fdb_selftest_parquet_write_filtered(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
+                                        const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, uint8_t** bytes,
+                                        int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::HostRecordView view;
+    fdb::view_record(batch, schema, &view);
+    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom);
   });
 }
 

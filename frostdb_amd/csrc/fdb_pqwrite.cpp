@@ -43,6 +43,16 @@
 // rule, the cut of BYTE_ARRAY bounds, the boundary order, and the thrift of Statistics, ColumnIndex, OffsetIndex, column_orders and
 // sorting_columns. The index bytes follow the body in the file (PqwLayout::tail, written by pqw_finish); the image stays the body. For a
 // compressed file the index is the final layout's. Without index options nothing of this runs.
+//
+// fdb_batch_to_parquet_filtered: a split-block bloom filter per chosen column (the rule is spelled out in fdb_pqbloom.h and in
+// include/frostdb_amd.h). The host hashes the entries of the chosen index columns once (entry_hashes, fdb_sortplan.h). The survey's
+// table gives every filter its size (pqb_size), so the layout can place them — after the last chunk's pages, in column order, each a
+// header (a host piece) and then its bitset (PqwLayout::blooms), in front of the page index — and the insert pass of fdb_pqbloom.hip
+// runs then, on the call's stream beside the encode pass, into ONE zeroed table of bitsets from the call's arena, each 32-byte aligned
+// there (the atomics want that; a file offset is arbitrary, so the bitsets are not part of the image). They come back after the image,
+// one copy per filter straight to its offset in the returned bytes, in the wait of the image's copy: no wait is added. For a compressed
+// file the offsets are the final layout's; filters are never compressed. The host walk is pqb_insert_host. Without a chosen column
+// nothing of this runs.
 #include "fdb_pqwrite_host.h"
 #include "fdb_sortplan.h"
 
@@ -124,6 +134,7 @@ struct ChunkMeta {
   bool has_bounds = false;
   std::string min, max;                                                     // Statistics.min_value / max_value
   int64_t offset_index_off = -1, offset_index_len = 0, column_index_off = -1, column_index_len = 0;
+  int64_t bloom_off = -1, bloom_len = 0;                                    // with a bloom filter only: its header's offset, header + bitset
 };
 
 std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMeta>& chunks, int64_t rows, int64_t body_bytes, const PqxIndex* x) {
@@ -163,6 +174,7 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     t.i64(9, m.data_off);
     if (m.dict_off >= 0) t.i64(11, m.dict_off);
     t.open(12); t.i64(3, m.nulls); if (m.has_bounds) { t.string(5, m.max); t.string(6, m.min); } t.close();  // Statistics: null_count, max_value, min_value
+    if (m.bloom_off >= 0) { t.i64(14, m.bloom_off); t.i32(15, (int32_t)m.bloom_len); }  // bloom_filter_offset, bloom_filter_length
     t.close();
     if (m.offset_index_off >= 0) { t.i64(4, m.offset_index_off); t.i32(5, (int32_t)m.offset_index_len); }
     if (m.column_index_off >= 0) { t.i64(6, m.column_index_off); t.i32(7, (int32_t)m.column_index_len); }
@@ -511,6 +523,81 @@ void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, Pq
   }
 }
 
+// ---- bloom filters: the host's half of the insert pass (fdb_pqbloom.h) -------------------------------------------------------------------
+PqbPlan pqb_plan(const fdb_parquet_bloom_options* bloom, const std::vector<PqwColumn>& cols) {
+  PqbPlan b;
+  if (bloom == nullptr) return b;
+  if (bloom->n_columns != 0 && (bloom->n_columns != (int32_t)cols.size() || bloom->columns == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: the bloom filter `columns` has " + std::to_string(bloom->n_columns) + " entries, the record " + std::to_string(cols.size()) + " columns");
+  if (bloom->bits_per_value < 0 || bloom->bits_per_value > 64)
+    throw Error(FDB_ERR_INVALID, "parquet write: bloom filter bits_per_value is " + std::to_string(bloom->bits_per_value) + " (0: " + std::to_string(FDB_PQB_DEFAULT_BITS) + ", else 1 to 64)");
+  bool some = false;
+  for (int32_t k = 0; k < bloom->n_columns; k++) {
+    const int e = (int)bloom->columns[k];
+    if (e < 0 || e > 1) throw Error(FDB_ERR_INVALID, "parquet write: bloom filter columns[" + std::to_string(k) + "] is " + std::to_string(e) + " (0 none, 1 a bloom filter)");
+    if (e == 1 && cols[(size_t)k].pq_kind == FDB_PQW_BOOL) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: a bloom filter is not written for a boolean column (" + cols[(size_t)k].name + ")");
+    some = some || e == 1;
+  }
+  if (!some) return b;
+  b.on.assign(bloom->columns, bloom->columns + bloom->n_columns);
+  b.bits_per_value = fdb_pqb_bits_per_value(bloom->bits_per_value);
+  return b;
+}
+
+void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b) {
+  b->hashes.assign(cols.size(), std::vector<uint64_t>());
+  for (size_t k = 0; k < cols.size() && b->any(); k++)
+    if (b->on[k] != 0 && cols[k].pq_kind == FDB_PQW_INDEX && cols[k].dict != nullptr)
+      b->hashes[k] = entry_hashes(*cols[k].dict, [](const unsigned char* p, size_t n) { return fdb_pqb_hash(p, n); });
+}
+
+void pqb_size(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqbPlan* b) {
+  b->bytes.assign(cols.size(), 0);
+  b->table_off.assign(cols.size(), 0);
+  b->table_bytes = 0;
+  for (size_t k = 0; k < cols.size() && b->any(); k++) {
+    if (b->on[k] == 0) continue;
+    uint64_t n = 0;
+    for (int64_t p = 0; p < g.n_pages; p++) n += stats[k * (size_t)g.n_pages + (size_t)p].count;
+    if (cols[k].pq_kind == FDB_PQW_INDEX || cols[k].pq_kind == PQW_NO_VALUES) n = std::min<uint64_t>(n, cols[k].entries);
+    b->bytes[k] = fdb_pqb_bytes(n, b->bits_per_value);
+    b->table_off[k] = b->table_bytes;
+    b->table_bytes += b->bytes[k];  // (a multiple of 32)
+  }
+}
+
+void pqb_insert_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqbPlan& b, unsigned char* table) {
+  for (size_t k = 0; k < cols.size() && b.any(); k++) {
+    if (b.on[k] == 0) continue;
+    const PqwColumn& c = cols[k];
+    const bool index = c.pq_kind != FDB_PQW_V64;
+    const std::vector<uint64_t>& hashes = b.hashes[k];
+    const uint32_t per = index ? FDB_PQX_UNIT_INDEX : FDB_PQX_UNIT_V64, n_blocks = b.bytes[k] / FDB_PQB_BLOCK_BYTES;
+    unsigned char* bits = table + b.table_off[k];
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      for (int32_t t = 0; t < g.tiles_per_page; t++) {
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        for (uint32_t u = 0; (int64_t)u * per < end - first; u++) {
+          const uint32_t unit = fdb_pqx_unit_bits(c.validity, first, end, u, per);
+          for (uint32_t i = 0; i < per; i++) {
+            if (!((unit >> i) & 1)) continue;
+            const size_t row = (size_t)first + (size_t)u * per + i;
+            uint64_t h;
+            if (index) {
+              const uint32_t v = ((const uint32_t*)c.values)[row];
+              if (v >= hashes.size()) continue;  // (the survey's to refuse)
+              h = hashes[v];
+            } else { uint64_t v; std::memcpy(&v, (const unsigned char*)c.values + row * 8, 8); h = fdb_pqb_hash8(v); }
+            unsigned char* blk = bits + (size_t)fdb_pqb_block(h, n_blocks) * FDB_PQB_BLOCK_BYTES;
+            for (int q = 0; q < 4; q++) { uint64_t w; std::memcpy(&w, blk + q * 8, 8); w |= fdb_pqb_pair_mask(h, q); std::memcpy(blk + q * 8, &w, 8); }
+          }
+        }
+      }
+    }
+  }
+}
+
 std::string pqs_block_host(const unsigned char* body, size_t n) {
   std::string block = varint_bytes(n);
   std::vector<uint32_t> table(FDB_PQS_TABLE);
@@ -523,8 +610,10 @@ std::string pqs_block_host(const unsigned char* body, size_t n) {
 }
 
 PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes,
-                     const std::vector<uint32_t>* page_elements, const PqxIndex* x) {
+                     const std::vector<uint32_t>* page_elements, const PqxIndex* x, const PqbPlan* bloom) {
   if (x != nullptr && !x->any()) x = nullptr;
+  if (bloom != nullptr && !bloom->any()) bloom = nullptr;
+  if (bloom != nullptr && bloom->bytes.size() != cols.size()) throw Error(FDB_ERR_STATE, "parquet write: the bloom filter sizes do not match the record");
   const bool bounds = x != nullptr && x->statistics > 0;
   if (bounds && (x->table.size() != 2 * stats.size() || x->modes.size() != cols.size())) throw Error(FDB_ERR_STATE, "parquet write: the min / max table does not match the record");
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
@@ -636,6 +725,17 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
     L.chunk_len[k] = cur - chunk_start;
   }
   L.body_bytes = cur;
+  if (bloom != nullptr) {  // after the last chunk's pages, in column order: header, bitset, no padding
+    for (size_t k = 0; k < cols.size(); k++) {
+      if (bloom->on[k] == 0) continue;
+      unsigned char hdr[FDB_PQB_MAX_HEADER];
+      const uint32_t len = fdb_pqb_header(bloom->bytes[k], hdr);
+      chunks[k].bloom_off = (int64_t)cur; chunks[k].bloom_len = (int64_t)len + bloom->bytes[k];
+      L.put(cur, std::string((const char*)hdr, len)); cur += len;
+      L.blooms.push_back(PqwLayout::Bloom{k, cur, bloom->bytes[k]}); cur += bloom->bytes[k];
+    }
+    L.bloom_bytes = cur - L.body_bytes;
+  }
   if (bounds) {  // chunk bounds; with statistics == 2 every column's ColumnIndex, then every column's OffsetIndex, after the pages
     for (size_t k = 0; k < cols.size(); k++) {
       const std::string ci = pqx_column_index(cols[k], *x, k, (size_t)g.n_pages, &chunks[k]);
@@ -649,13 +749,13 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
       L.tail += oi;
     }
   }
-  L.footer = footer(cols, chunks, g.rows, (int64_t)cur, x);
+  L.footer = footer(cols, chunks, g.rows, (int64_t)L.body_bytes, x);
   return L;
 }
 
 void pqw_finish(const PqwLayout& L, uint8_t* file) {
   for (const PqwLayout::Piece& p : L.pieces) std::memcpy(file + p.off, L.blob.data() + p.pos, p.len);
-  uint8_t* end = file + L.body_bytes;
+  uint8_t* end = file + L.body_bytes + L.bloom_bytes;
   if (!L.tail.empty()) { std::memcpy(end, L.tail.data(), L.tail.size()); end += L.tail.size(); }  // the page index: the host's, after the image
   std::memcpy(end, L.footer.data(), L.footer.size());
   const uint32_t len = (uint32_t)L.footer.size();
@@ -838,7 +938,7 @@ void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
 }
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                            const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index) {
+                            const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom) {
   // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
   const size_t rows = (size_t)view.rows;
   std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
@@ -885,15 +985,24 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
   int32_t page_rows = 0;
   const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
   PqxIndex x = pqx_plan(index, cols.size());
+  PqbPlan bl = pqb_plan(bloom, cols);
   const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
   pqw_survey_host(cols, g, &stats, &tile_base);
+  std::vector<unsigned char> bitsets;
+  if (bl.any()) { pqb_prepare(cols, &bl); pqb_size(cols, g, stats, &bl); }
+  const auto place_bitsets = [&](const PqwLayout& at, uint8_t* file) {  // the insert pass, walked, and every bitset to its place in the file
+    if (at.blooms.empty()) return;
+    bitsets.assign((size_t)bl.table_bytes, 0);
+    pqb_insert_host(cols, g, bl, bitsets.data());
+    for (const PqwLayout::Bloom& f : at.blooms) std::memcpy(file + f.bits_off, bitsets.data() + bl.table_off[f.col], (size_t)f.bytes);
+  };
   if (x.statistics > 0) { pqx_prepare(cols, &x); pqx_minmax_host(cols, g, &x); }
   PqdHost delta;
   pqd_survey_host(cols, g, stats, tile_base, &delta);
   const bool squeezed = pqw_compressed_columns(cols) > 0;  // then L is the staging image's layout, and the index is the final one's
-  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes, nullptr, squeezed ? nullptr : &x);
+  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes, nullptr, squeezed ? nullptr : &x, squeezed ? nullptr : &bl);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(cols, g, L.out, tile_base, image.data());
   pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
@@ -901,6 +1010,7 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     const size_t file_bytes = L.file_bytes();
     uint8_t* file = pqw_alloc_bytes(file_bytes, false);
     std::memcpy(file, image.data(), (size_t)L.body_bytes);
+    place_bitsets(L, file);
     pqw_finish(L, file);
     *bytes = file;
     *n_bytes = (int64_t)file_bytes;
@@ -919,12 +1029,13 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     }
     page_elements[i] = (uint32_t)elements[i].size();
   }
-  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements, &x);
+  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements, &x, &bl);
   const size_t file_bytes = F.file_bytes();
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
   for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
   for (size_t k = 0; k < cols.size(); k++)
     if (cols[k].codec == 0) std::memcpy(file + F.chunk_off[k], image.data() + L.chunk_off[k], (size_t)L.chunk_len[k]);
+  place_bitsets(F, file);
   pqw_finish(F, file);
   *bytes = file;
   *n_bytes = (int64_t)file_bytes;
@@ -932,7 +1043,7 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
 
 #ifndef FDB_PQWRITE_HOST_ONLY
 void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                      const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index) {
+                      const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom) {
   std::vector<PqwInput> in;
   for (const DevColumn& c : b.cols) {
     PqwInput o;
@@ -949,15 +1060,25 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
       if (((uintptr_t)cols[k].values & 15u) != 0)  // (the pass loads 16 bytes of values at a time)
         throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (statistics)");
   }
+  PqbPlan bl = pqb_plan(bloom, cols);
+  if (bl.any()) {
+    pqb_prepare(cols, &bl);
+    for (size_t k = 0; k < cols.size(); k++)
+      if (bl.on[k] != 0 && ((uintptr_t)cols[k].values & 15u) != 0)  // (the pass loads 16 bytes of values at a time)
+        throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (bloom filter)");
+  }
   const FdbPqwGeom g = pqw_geometry(b.rows, page_rows, cols.size());
   const size_t n_delta = pqw_delta_columns(cols), n_compressed = pqw_compressed_columns(cols);
   struct Bytes { uint8_t* p = nullptr; ~Bytes() { pqw_free_bytes(p); } } file;
   if (b.rows == 0 || cols.empty()) {  // nothing for the device to do (no data page: the dictionary pages are the host's, compressed or not)
     const std::vector<uint32_t> no_pages;
     if (bounds) x.table.assign(2 * cols.size() * (size_t)g.n_pages, 0);  // (no page: no slot)
-    const PqwLayout L = pqw_layout(cols, g, std::vector<FdbPqwPageStat>(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0}), {}, n_compressed > 0 ? &no_pages : nullptr, &x);
+    const std::vector<FdbPqwPageStat> no_stats(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0});
+    if (bl.any()) pqb_size(cols, g, no_stats, &bl);
+    const PqwLayout L = pqw_layout(cols, g, no_stats, {}, n_compressed > 0 ? &no_pages : nullptr, &x, &bl);
     const size_t file_bytes = L.file_bytes();
     file.p = pqw_alloc_bytes(file_bytes, false);
+    for (const PqwLayout::Bloom& f : L.blooms) std::memset(file.p + f.bits_off, 0, (size_t)f.bytes);  // (no value: one zero block each)
     pqw_finish(L, file.p);
     *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
     return;
@@ -1032,9 +1153,41 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   }
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   pt.mark(n_delta > 0 ? "pqwrite delta survey" : bounds && pt.on ? "pqwrite wait" : "pqwrite survey");
-  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes, nullptr, n_compressed > 0 ? nullptr : &x);
+  if (bl.any()) pqb_size(cols, g, stats, &bl);
+  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes, nullptr, n_compressed > 0 ? nullptr : &x, n_compressed > 0 ? nullptr : &bl);
   const size_t file_bytes = L.file_bytes(), image_bytes = align_up((size_t)L.body_bytes + 8, 256);
   pt.mark("pqwrite layout");
+  // The bloom filters (fdb_pqbloom.hip): the survey's table has sized them, so their bitsets — one zeroed table of the call's arena,
+  // every bitset 32-byte aligned in it, which a file offset is not — are filled beside the encode pass, on the same stream. They come
+  // back after the image, each straight to its place behind its header (bloom_out), in the wait of the image's copy.
+  unsigned char* d_bitsets = nullptr;
+  if (bl.any()) {
+    std::vector<FdbPqbCol> bc;
+    d_bitsets = (unsigned char*)cs.alloc((size_t)bl.table_bytes);
+    for (size_t k = 0; k < cols.size(); k++) {
+      if (bl.on[k] == 0) continue;
+      FdbPqbCol o;
+      std::memset(&o, 0, sizeof(FdbPqbCol));
+      o.values = cols[k].values; o.validity = cols[k].validity; o.index = cols[k].pq_kind != FDB_PQW_V64;
+      o.bits = (unsigned long long*)(d_bitsets + bl.table_off[k]); o.n_blocks = bl.bytes[k] / FDB_PQB_BLOCK_BYTES;
+      const std::vector<uint64_t>& h = bl.hashes[k];
+      if (!h.empty()) {
+        uint64_t* d_hashes = (uint64_t*)cs.alloc(h.size() * 8);
+        hip_check(hipMemcpyAsync(d_hashes, h.data(), h.size() * 8, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(entry hashes)");  // (`bl` outlives the wait)
+        o.hashes = d_hashes; o.hash_len = (uint32_t)h.size();
+      }
+      bc.push_back(o);
+    }
+    const FdbPqbCol* d_bcols = (const FdbPqbCol*)cs.ctx->stage(bc.data(), bc.size() * sizeof(FdbPqbCol));
+    hip_check(hipMemsetAsync(d_bitsets, 0, (size_t)bl.table_bytes, stream), "hipMemsetAsync(bloom filter bitsets)");
+    hip_check(fdb_launch_pqb_insert(d_bcols, (int32_t)bc.size(), g, stream), "parquet write: bloom filter launch");
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite bloom insert"); }
+  }
+  const auto bloom_out = [&](const PqwLayout& at, uint8_t* out) {
+    for (const PqwLayout::Bloom& f : at.blooms)
+      hip_check(hipMemcpyAsync(out + f.bits_off, d_bitsets + bl.table_off[f.col], (size_t)f.bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(bloom filter bitset)");
+    if (pt.on && !at.blooms.empty()) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite bloom copy"); }
+  };
   image.p = device_pool_alloc(b.device, image_bytes);
   FdbPqwPageOut* d_out = (FdbPqwPageOut*)cs.alloc(items * sizeof(FdbPqwPageOut));
   hip_check(hipMemcpyAsync(d_out, L.out.data(), items * sizeof(FdbPqwPageOut), hipMemcpyHostToDevice, stream), "hipMemcpyAsync(page offsets)");
@@ -1049,6 +1202,7 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   }
   if (n_compressed == 0) {
     file.p = pqw_alloc_bytes(file_bytes, true);
+    bloom_out(L, file.p);
     cs.ctx->copy_out_parallel(file.p, image.p, (size_t)L.body_bytes);
     pt.mark("pqwrite copy");
     pqw_finish(L, file.p);
@@ -1090,7 +1244,7 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   if (!pages.empty()) hip_check(hipMemcpyAsync(page_elements.data(), d_page_elements, pages.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(compressed page sizes)");
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   pt.mark("pqwrite scan");
-  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements, &x);
+  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements, &x, &bl);
   const size_t out_bytes = F.file_bytes();
   pt.mark("pqwrite final layout");
   std::vector<uint64_t> page_dst(F.pages.size());
@@ -1109,6 +1263,7 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
                                   (const unsigned char*)image.p, (unsigned char*)final_image.p, stream), "parquet write: gather launch");
   if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite gather"); }
   file.p = pqw_alloc_bytes(out_bytes, true);
+  bloom_out(F, file.p);
   cs.ctx->copy_out_parallel(file.p, final_image.p, (size_t)F.body_bytes);
   pt.mark("pqwrite copy");
   pqw_finish(F, file.p);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "fdb_arrow.h"
+#include "fdb_pqbloom.h"
 #include "fdb_pqdelta.h"
 #include "fdb_pqsnappy.h"
 #include "fdb_pqstats.h"
@@ -69,8 +70,33 @@ struct PqwLayout {
   // The page index (statistics == 2): every column's ColumnIndex, then every column's OffsetIndex — host bytes that follow the body in
   // the file, before the footer; empty otherwise. The image stays the body.
   std::string tail;
-  size_t file_bytes() const { return (size_t)body_bytes + tail.size() + footer.size() + 8; }
+  // The bloom filters (fdb_pqbloom.h), in column order between the body and the page index: each a header — a piece of `blob` like any
+  // other host byte — and then its bitset, which the insert pass fills and the caller moves to `bits_off`. Empty: none was asked for.
+  struct Bloom { size_t col; uint64_t bits_off, bytes; };
+  std::vector<Bloom> blooms;
+  uint64_t bloom_bytes = 0;      // headers + bitsets
+  size_t file_bytes() const { return (size_t)body_bytes + (size_t)bloom_bytes + tail.size() + footer.size() + 8; }
 };
+
+// What fdb_parquet_bloom_options asks for, checked (pqb_plan); the entry hashes of the filtered index columns (pqb_prepare); and, once
+// the survey has counted the non-NULL rows, every filter's size and its place in the table of bitsets (pqb_size).
+struct PqbPlan {
+  std::vector<int8_t> on;                      // per column: 1 = gets a filter (empty: none does)
+  uint32_t bits_per_value = FDB_PQB_DEFAULT_BITS;
+  std::vector<std::vector<uint64_t>> hashes;   // per filtered index column: XXH64 of every entry
+  std::vector<uint32_t> bytes;                 // per column: the bitset's bytes (0: no filter)
+  std::vector<uint64_t> table_off;             // per column: where its bitset starts in the table (a multiple of 32)
+  uint64_t table_bytes = 0;
+  bool any() const { return !on.empty(); }
+};
+// Every refusal of the bloom options: FDB_ERR_INVALID — n_columns neither 0 nor the column count, an entry outside 0 … 1,
+// bits_per_value outside 0 … 64; FDB_ERR_UNSUPPORTED, naming the column — a BOOL column. Nothing has been launched yet. `bloom` ==
+// nullptr or no entry set: nothing asked (any() is false).
+PqbPlan pqb_plan(const fdb_parquet_bloom_options* bloom, const std::vector<PqwColumn>& cols);
+void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b);
+void pqb_size(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqbPlan* b);
+// The pass over host arrays: every non-NULL row's value into the column's bitset of `table` (table_bytes long, zeroed).
+void pqb_insert_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqbPlan& b, unsigned char* table);
 
 // What fdb_parquet_index_options asks for, checked (pqx_plan), and what the min / max pass found (fdb_pqstats.h) — the table of the
 // kernel on the device, of pqx_minmax_host in the self-test. With it pqw_layout writes Statistics.min_value / max_value, column_orders,
@@ -106,8 +132,9 @@ FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
 // one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of the elements of the
 // page's Snappy block (the preamble not counted), as the compressor found them.
 PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes = {},
-                     const std::vector<uint32_t>* page_elements = nullptr, const PqxIndex* index = nullptr);
-// Fills the holes of `file` (L.file_bytes() long, the payloads in place) and appends the page index, if any, footer, length and magic.
+                     const std::vector<uint32_t>* page_elements = nullptr, const PqxIndex* index = nullptr, const PqbPlan* bloom = nullptr);
+// Fills the holes of `file` (L.file_bytes() long, the payloads in place — the bitsets of L.blooms included) and appends the page index,
+// if any, footer, length and magic.
 void pqw_finish(const PqwLayout& L, uint8_t* file);
 void pqw_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, std::vector<FdbPqwPageStat>* stats, std::vector<uint32_t>* tile_base);
 // `image`: zeroed, body_bytes rounded up to whole words (+ 4).
@@ -131,10 +158,10 @@ uint8_t* pqw_alloc_bytes(size_t n, bool pinned);
 void pqw_free_bytes(uint8_t* bytes);
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr,
-                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr);
+                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr);
 #ifndef FDB_PQWRITE_HOST_ONLY
 void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr, int32_t n_encodings = 0,
-                      const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr);
+                      const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr);
 #endif
 
 }  // namespace fdb

@@ -31,6 +31,15 @@ inline std::vector<uint32_t> dense_ranks(const HostDict& d, uint32_t* distinct) 
   return rank;
 }
 
+// A hash of every entry's bytes, entry by entry — the table the Parquet writer's bloom filter pass gathers an index column's hashes
+// from (`hash`: fdb_pqb_hash of fdb_pqbloom.h; equal entries get equal hashes, an empty entry the hash of no bytes).
+template <class Hash>
+inline std::vector<uint64_t> entry_hashes(const HostDict& d, Hash hash) {
+  std::vector<uint64_t> h(d.values.size());
+  for (size_t i = 0; i < h.size(); i++) h[i] = hash((const unsigned char*)d.values[i].data(), d.values[i].size());
+  return h;
+}
+
 // The packing of the key fields into words: one SortPart per (word, column) — the column's value field, its NULL bit, or both; bits_out[w]
 // = the bits word w uses. Word 0 is the most significant.
 struct SortPart { int word; int col; int width; int shift; int null_shift; };

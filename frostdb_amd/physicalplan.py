@@ -166,6 +166,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_merge_bench.argtypes = [P(vp), i32, vp, i32, i32, i32, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double), i32, P(i32), P(i32)]
     L.fdb_batch_column_name.argtypes = [vp, i32]
     L.fdb_batch_column_name.restype = ctypes.c_char_p
+    L.fdb_batch_column_format.argtypes = [vp, i32]
+    L.fdb_batch_column_format.restype = ctypes.c_char_p
     L.fdb_batch_to_parquet.argtypes = [vp, vp, P(vp), P(i64)]
     L.fdb_selftest_parquet_write.argtypes = [vp, vp, vp, P(vp), P(i64)]
     L.fdb_batch_to_parquet_encoded.argtypes = [vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
@@ -174,6 +176,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_parquet_write_compressed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
     L.fdb_batch_to_parquet_indexed.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
     L.fdb_selftest_parquet_write_indexed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
+    L.fdb_batch_to_parquet_filtered.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, P(vp), P(i64)]
+    L.fdb_selftest_parquet_write_filtered.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
     L.fdb_bytes_free.restype = None
     _lib = L
@@ -436,6 +440,40 @@ def _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
     return ParquetIndexOptions(PARQUET_STATISTICS[statistics], index_size_limit, ctypes.cast(arr, ctypes.c_void_p) if wanted else None, len(wanted)), arr
 
 
+class ParquetBloomOptions(ctypes.Structure):
+    """fdb_parquet_bloom_options."""
+    _fields_ = [("columns", ctypes.c_void_p), ("n_columns", ctypes.c_int32), ("bits_per_value", ctypes.c_int32)]
+
+
+def _parquet_bloom_options(bloom_filters, bits_per_value, names, is_bool, sorting_columns):
+    """`bloom_filters`: None, a sequence of column names, a dict of name → bool, or "sorting": the `sorting_columns` that are not
+    boolean (`is_bool`: per column), which is what the reference's Schema.NewWriter gives a filter — with no sorting column, none.
+    `bits_per_value`: 0 (10) or 1 … 64. Returns the struct and what it points at, or (None, None) when nothing is asked: the caller
+    then calls what it called without these arguments."""
+    if bloom_filters is None and not bits_per_value:
+        return None, None
+    if isinstance(bits_per_value, bool) or not isinstance(bits_per_value, int) or not -2**31 <= bits_per_value < 2**31:
+        _raise(FDB_ERR_INVALID, "parquet write: bloom filter bits_per_value is %r (0: 10, else 1 to 64)" % (bits_per_value,))
+    wanted = [0] * len(names)
+    if isinstance(bloom_filters, str):
+        if bloom_filters != "sorting":
+            _raise(FDB_ERR_INVALID, "parquet write: `bloom_filters` is a sequence of column names, a dict of name → bool or 'sorting', got %r" % (bloom_filters,))
+        for entry in (sorting_columns or ()):
+            col = entry[0] if isinstance(entry, (tuple, list)) else entry
+            col = names.index(col) if isinstance(col, str) and col in names else col
+            if isinstance(col, int) and not isinstance(col, bool) and 0 <= col < len(names) and not is_bool[col]:  # (anything else is the index options' to refuse)
+                wanted[col] = 1
+    else:
+        chosen = [n for n, on in bloom_filters.items() if on] if isinstance(bloom_filters, dict) else list(bloom_filters or ())
+        for n in (list(bloom_filters) if isinstance(bloom_filters, dict) else chosen):
+            if not isinstance(n, str) or n not in names:
+                _raise(FDB_ERR_INVALID, "parquet write: `bloom_filters` names no column of the record: %s" % (n,))
+        for n in chosen:
+            wanted[names.index(n)] = 1
+    arr = (ctypes.c_int8 * max(1, len(wanted)))(*wanted)
+    return ParquetBloomOptions(ctypes.cast(arr, ctypes.c_void_p) if wanted else None, len(wanted), bits_per_value), arr
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -446,19 +484,25 @@ def _take_bytes(rc, out, n) -> bytes:
 
 
 def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0,
-                           sorting_columns=None) -> bytes:
+                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0) -> bytes:
     """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
     made without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
     fdb_selftest_parquet_write_compressed, with `statistics`, `index_size_limit` or `sorting_columns`
-    fdb_selftest_parquet_write_indexed): the same layout, headers and footer, the kernels replaced by a host walk of the code they
-    compile."""
+    fdb_selftest_parquet_write_indexed, with `bloom_filters` or `bloom_bits_per_value` fdb_selftest_parquet_write_filtered): the same
+    layout, headers and footer, the kernels replaced by a host walk of the code they compile."""
     names = list(record.schema.names)
     opts, _keep = _parquet_write_options(page_rows, optional, names)
     enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
     index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
+    bloom, _keep_bloom = _parquet_bloom_options(bloom_filters, bloom_bits_per_value, names, [pa.types.is_boolean(f.type) for f in record.schema], sorting_columns)
     out, n = ctypes.c_void_p(), ctypes.c_int64()
     with ExportedBatch(record) as ex:
-        if index is not None:
+        if bloom is not None:
+            codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
+            rc = lib().fdb_selftest_parquet_write_filtered(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
+                                                           n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
+                                                           ctypes.byref(bloom), ctypes.byref(out), ctypes.byref(n))
+        elif index is not None:
             codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
             rc = lib().fdb_selftest_parquet_write_indexed(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
                                                           n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
@@ -689,6 +733,17 @@ class ResidentBatch:
             names.append(nm.decode("utf-8", "replace"))
             k += 1
 
+    @property
+    def column_formats(self) -> List[str]:
+        """The Arrow format strings of the record's columns, in order (fdb_batch_column_format)."""
+        formats, k = [], 0
+        while True:
+            f = lib().fdb_batch_column_format(self.handle, k)
+            if f is None:
+                return formats
+            formats.append(f.decode("utf-8", "replace"))
+            k += 1
+
     def _sort_cols(self, columns):
         """`columns` → an fdb_sort_col array. A column is ``(name_or_index, descending=False, nulls_first=False)`` or a bare name /
         index; a name the record lacks (or has twice) raises KeyError before the library is called. A raw descriptor —
@@ -797,7 +852,8 @@ class ResidentBatch:
             _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
-    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0, sorting_columns=None) -> bytes:
+    def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0, sorting_columns=None,
+                   bloom_filters=None, bloom_bits_per_value: int = 0) -> bytes:
         """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, data pages V1 of
         `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
@@ -812,11 +868,25 @@ class ResidentBatch:
         Parquet page index (ColumnIndex and OffsetIndex per column, between the pages and the footer), which FrostDB's own scan prunes
         row groups with; `index_size_limit`: the bytes a string bound of the ColumnIndex is cut to (0 = 16); `sorting_columns`: a
         sequence of (name or index, descending=False, nulls_first=False) written as RowGroup.sorting_columns — metadata only, the rows
-        are not checked (fdb_batch_to_parquet_indexed). Without these three the call is what it was."""
+        are not checked (fdb_batch_to_parquet_indexed). Without these three the call is what it was. `bloom_filters`: None, a sequence
+        of column names, a dict of name → bool, or "sorting" — the `sorting_columns` that are not boolean, what the reference's
+        Schema.NewWriter does: each such column gets a split-block bloom filter (XXH64 of the value's PLAIN bytes) of
+        `bloom_bits_per_value` bits per non-NULL row (0 = 10; a dictionary column: per entry, when those are fewer), its bits set on the
+        device by one more pass, written after the pages and named by ColumnMetaData.bloom_filter_offset / _length — what FrostDB's
+        scan asks first for `=` (fdb_batch_to_parquet_filtered). A boolean column is refused; an unknown name is FDB_ERR_INVALID.
+        Without these two the call is what it was."""
         opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
         out, n = ctypes.c_void_p(), ctypes.c_int64()
         index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, self.column_names)
-        if index is not None:
+        bloom, _keep_bloom = (None, None) if bloom_filters is None and not bloom_bits_per_value else _parquet_bloom_options(
+            bloom_filters, bloom_bits_per_value, self.column_names, [f == "b" for f in self.column_formats], sorting_columns)
+        if bloom is not None:
+            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
+            codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
+            rc = lib().fdb_batch_to_parquet_filtered(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,
+                                                     ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
+                                                     ctypes.byref(bloom), ctypes.byref(out), ctypes.byref(n))
+        elif index is not None:
             enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
             codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
             rc = lib().fdb_batch_to_parquet_indexed(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,

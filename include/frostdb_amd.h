@@ -647,6 +647,45 @@ typedef struct fdb_parquet_index_options {
 } fdb_parquet_index_options;
 FDB_API int fdb_batch_to_parquet_indexed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_indexed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+/* The same two calls with a split-block bloom filter per column as well (parquet-format's BloomFilter.md) — the other thing FrostDB's
+ * scan reads of a part: its writer puts one, at 10 bits per value, on every sorting column that is not boolean (Schema.NewWriter,
+ * dynparquet/schema.go:1109-1143), and BinaryScalarOperation asks a chunk's BloomFilter() for `=` before it looks at the bounds
+ * (query/expr/binaryscalarexpr.go:104-118) — what prunes a label column whose values span the whole range in every part, where min /
+ * max never does. With bloom == NULL, n_columns == 0 or every entry 0 the file is fdb_batch_to_parquet_indexed's, byte for byte, made
+ * by the same path — no further launch, allocation, copy or footer field.
+ *
+ * The rule (fdb_pqbloom.h): a value's hash is XXH64, seed 0, of its PLAIN bytes — an int64 / uint64 / float64 value's 8 bytes,
+ * little-endian, the bits as they are (a NaN with its payload; −0.0 and +0.0 are two values); a dictionary or plain string / binary
+ * entry's bytes without a length prefix. Its block is ((hash >> 32) × n_blocks) >> 32, a block being 32 bytes, eight 32-bit little-endian
+ * words, and in word i it sets bit ((uint32)hash × SALT[i]) >> 27, SALT = 47b6137b 44974d91 8824ad5b a2b7289d 705495c7 2df1424b 9efc4947
+ * 5c6bfb31. Every non-NULL row's value goes in; of a dictionary column only the entries a non-NULL row REFERS to — an unused entry
+ * never answers "maybe". The bitset has 32 × max(1, ⌈⌈n × b / 8⌉ / 32⌉) bytes, at most 134 217 728 and not rounded to a power of two:
+ * b = bits_per_value (0 = 10), n = the column's non-NULL rows, of a dictionary or string column the smaller of that and its dictionary's
+ * length; a column without a non-NULL value gets one zero block. Each filter is a BloomFilterHeader — `15`, the zigzag varint of the
+ * bitset's bytes, `1c 1c 00 00 1c 1c 00 00 1c 1c 00 00 00`: BLOCK, XXHASH, UNCOMPRESSED — and then the bitset, never compressed; the
+ * filters follow the last chunk's pages in column order without padding, ColumnIndex / OffsetIndex come after them when asked for,
+ * then the footer; ColumnMetaData.bloom_filter_offset / bloom_filter_length (fields 14 / 15: the header's offset, header + bitset) name
+ * each, for a file with SNAPPY columns in the final layout; RowGroup.total_compressed_size keeps counting the pages only.
+ *
+ * The bits are set on the device (fdb_pqbloom.hip): once the survey's table has sized the filters, one more pass on the same stream, a
+ * workgroup per (filtered column, page, tile); an 8-byte value is hashed in registers, an index gathers its entry's hash from a table
+ * the host computed and uploaded from the call's arena; a value equal to the row before it is skipped, an insert reads its block and
+ * issues 64-bit atomic ORs only for the pairs of words that lack a bit. The bitsets live in one zeroed table of the call's arena, each
+ * 32-byte aligned (a file offset is not), and come back after the image, one copy per filter straight to its place in the returned
+ * bytes; the call waits no more often than without filters. The 8-byte columns must be 16-byte aligned on the device (every resident
+ * record's are).
+ *
+ * Refused before anything is launched: FDB_ERR_INVALID — n_columns neither 0 nor the column count, an entry outside 0 … 1,
+ * bits_per_value outside 0 … 64; FDB_ERR_UNSUPPORTED, naming the column — a filter asked of a bool column (the reference skips
+ * booleans too); and everything the calls above refuse, unchanged. fdb_parquet_write_options and fdb_parquet_index_options keep their
+ * layouts. */
+typedef struct fdb_parquet_bloom_options {
+  const int8_t* columns;   /* per column: 0 = none, 1 = a bloom filter */
+  int32_t n_columns;       /* 0 (no filter) or the batch's column count */
+  int32_t bits_per_value;  /* 0 = 10 (bloomFilterBitsPerValue), else 1 … 64 */
+} fdb_parquet_bloom_options;
+FDB_API int fdb_batch_to_parquet_filtered(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_filtered(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry
@@ -870,6 +909,9 @@ FDB_API int fdb_merge_bench(const fdb_batch* const* in, int32_t n, const fdb_sor
 /* Name of column `index` of a resident batch (for callers that name sorting columns); NULL past the last column. The string lives as
  * long as the batch. */
 FDB_API const char* fdb_batch_column_name(const fdb_batch* batch, int32_t index);
+/* Its Arrow format string ("l", "L", "g", "b", "u", a dictionary's index format, …), for callers that choose columns by type — the
+ * bloom filters of the sorting columns that are not boolean; NULL past the last column. The string lives as long as the batch. */
+FDB_API const char* fdb_batch_column_format(const fdb_batch* batch, int32_t index);
 
 /* ≙ ReservoirSampler (sampler.go): keeps up to `size` rows of everything pushed, each row of the input with the same probability.
  * Push is single-threaded per handle, like a plan. The handle holds a `size`-slot reservoir record in HBM and nothing else — a row

@@ -7,6 +7,9 @@
 # two fragments, every page inflated again by the library's host decoder (fdb_codec.cpp).
 # Every record is also written with index options at random — statistics, a cut limit, sorting columns: the min / max pass's host walk
 # (fdb_pqstats.h), chunk bounds, ColumnIndex and OffsetIndex — and the index is read back by a small thrift reader of the program's own.
+# … and with bloom filter options at random — columns and bits per value: the insert pass's host walk (fdb_pqbloom.h), the filters'
+# headers and bitsets between the pages and the index — and a reader of the program's own, with its own XXH64, finds every non-NULL
+# value in its column's filter and no bit that no value set.
 # No GPU, no HIP runtime (fdb_codec.h takes its types from the HIP headers), no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

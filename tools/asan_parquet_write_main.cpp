@@ -11,6 +11,10 @@
 // walk (pqx_minmax_host: the keys of fdb_pqstats.h that the kernel compiles) fills the table, the layout writes chunk bounds, ColumnIndex
 // and OffsetIndex, and a small thrift reader of this file's own reads the index back out of a buffer sized exactly and holds every
 // page's bounds, NULL counts and location against a plain loop over the record.
+// And with bloom filter options at random (columns, bits per value): the insert pass's host walk (pqb_insert_host: the hash, block and
+// bits of fdb_pqbloom.h that the kernel compiles) fills a table of bitsets sized exactly, the layout puts header and bitset of every
+// filter between the pages and the index, and a reader of this file's own — its own XXH64, block and salts — finds every non-NULL
+// value of the record in its column's filter, and no bit set that no value set.
 // No GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
@@ -167,6 +171,71 @@ static std::vector<ReadLocation> read_offset_index(IndexReader* r) {
   }
   CHECK(r->field(&last) == 0);
   return out;
+}
+
+// ---- the bloom filters, read back ---------------------------------------------------------------------------------------------------------
+static uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+// XXH64, seed 0, byte by byte from its description (not the header's under test)
+static uint64_t reader_xxh64(const std::string& s) {
+  const uint64_t P1 = 0x9E3779B185EBCA87ull, P2 = 0xC2B2AE3D27D4EB4Full, P3 = 0x165667B19E3779F9ull, P4 = 0x85EBCA77C2B2AE63ull, P5 = 0x27D4EB2F165667C5ull;
+  const auto le = [&](size_t at, int n) { uint64_t v = 0; for (int b = 0; b < n; b++) v |= (uint64_t)(unsigned char)s[at + (size_t)b] << (8 * b); return v; };
+  const auto round = [&](uint64_t acc, uint64_t in) { return rotl64(acc + in * P2, 31) * P1; };
+  size_t at = 0;
+  uint64_t h;
+  if (s.size() >= 32) {
+    uint64_t v[4] = {P1 + P2, P2, 0, 0 - P1};
+    for (; at + 32 <= s.size(); at += 32) for (int i = 0; i < 4; i++) v[i] = round(v[i], le(at + 8 * (size_t)i, 8));
+    h = rotl64(v[0], 1) + rotl64(v[1], 7) + rotl64(v[2], 12) + rotl64(v[3], 18);
+    for (int i = 0; i < 4; i++) h = (h ^ round(0, v[i])) * P1 + P4;
+  } else h = P5;
+  h += s.size();
+  for (; at + 8 <= s.size(); at += 8) h = rotl64(h ^ round(0, le(at, 8)), 27) * P1 + P4;
+  if (at + 4 <= s.size()) { h = rotl64(h ^ (le(at, 4) * P1), 23) * P2 + P3; at += 4; }
+  for (; at < s.size(); at++) h = rotl64(h ^ ((unsigned char)s[at] * P5), 11) * P1;
+  h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3;
+  return h ^ (h >> 32);
+}
+
+// The record written with filters on the columns of `b`: header and bitset of each where the layout says, every non-NULL value found,
+// every set bit accounted for.
+static void check_bloom(const std::vector<Column>& cols, const std::vector<PqwColumn>& pc, int64_t rows, const std::vector<FdbPqwPageStat>& stats, size_t n_pages, const PqwLayout& L,
+                        const PqbPlan& b, const uint8_t* file) {
+  static const uint32_t salt[8] = {0x47b6137bu, 0x44974d91u, 0x8824ad5bu, 0xa2b7289du, 0x705495c7u, 0x2df1424bu, 0x9efc4947u, 0x5c6bfb31u};
+  size_t next = 0;
+  uint64_t at = L.body_bytes;
+  for (size_t k = 0; k < cols.size(); k++) {
+    if (!b.any() || b.on[k] == 0) continue;
+    CHECK(next < L.blooms.size() && L.blooms[next].col == k);
+    const PqwLayout::Bloom& f = L.blooms[next++];
+    uint64_t n = 0;
+    for (size_t p = 0; p < n_pages; p++) n += stats[k * n_pages + p].count;
+    if (cols[k].kind == ColKind::DICT) n = std::min<uint64_t>(n, cols[k].dict->values.size());
+    const uint64_t want_bytes = std::min<uint64_t>(32 * std::max<uint64_t>(1, ((n * b.bits_per_value + 7) / 8 + 31) / 32), 128u << 20);
+    CHECK(f.bytes == want_bytes && f.bytes % 32 == 0);
+    // the header: 15, the zigzag varint of the size, the three empty unions, the stop byte — right in front of the bitset
+    size_t h = (size_t)at;
+    CHECK(file[h++] == 0x15);
+    CHECK(read_varint(file, &h) == 2 * f.bytes);
+    static const uint8_t rest[13] = {0x1c, 0x1c, 0, 0, 0x1c, 0x1c, 0, 0, 0x1c, 0x1c, 0, 0, 0};
+    CHECK(std::memcmp(file + h, rest, 13) == 0 && h + 13 == f.bits_off);
+    const std::vector<uint8_t> exact(file + f.bits_off, file + f.bits_off + f.bytes);  // (sized exactly: a reader that runs past the bitset is caught)
+    std::vector<uint8_t> expected(exact.size(), 0);
+    for (int64_t r = 0; r < rows; r++) {
+      if (!(pc[k].validity == nullptr || cols[k].valid(r))) continue;
+      const std::string plain = cols[k].kind == ColKind::DICT ? cols[k].dict->values[cols[k].idx[(size_t)r]] : std::string((const char*)&cols[k].v64[(size_t)r], 8);
+      const uint64_t hash = reader_xxh64(plain);
+      const size_t block = (size_t)(((hash >> 32) * (f.bytes / 32)) >> 32);
+      for (int i = 0; i < 8; i++) {
+        const uint32_t bit = ((uint32_t)hash * salt[i]) >> 27;
+        const size_t byte = block * 32 + (size_t)i * 4 + bit / 8;
+        CHECK((exact[byte] >> (bit % 8)) & 1);  // present
+        expected[byte] |= (uint8_t)(1u << (bit % 8));
+      }
+    }
+    CHECK(exact == expected);  // and nothing else is set
+    at = f.bits_off + f.bytes;
+  }
+  CHECK(next == L.blooms.size() && at == L.body_bytes + L.bloom_bytes);
 }
 
 // a < b in the column's order, by a plain comparison of the values themselves (not by the keys under test)
@@ -393,6 +462,35 @@ static void one_record(uint64_t* seed, int round) {
     CHECK(I.tail.empty() || std::memcmp(indexed + I.body_bytes, I.tail.data(), I.tail.size()) == 0);
     pqw_free_bytes(indexed);
   }
+  // … and with bloom filters at random as well: the body is the same, the filters follow it, the index follows them
+  static const int32_t bit_choices[] = {0, 1, 7, 10, 33, 64};
+  std::vector<int8_t> filtered;
+  for (size_t k = 0; k < n_cols; k++) filtered.push_back((int8_t)(cols[k].kind != ColKind::BOOL && rnd(seed) % 3 != 0));
+  const bool no_array = rnd(seed) % 8 == 0;
+  const fdb_parquet_bloom_options bopt{no_array ? nullptr : filtered.data(), no_array ? 0 : (int32_t)n_cols, bit_choices[rnd(seed) % 6]};
+  PqbPlan bl = pqb_plan(&bopt, pc);
+  bool some = false;
+  for (int8_t f : filtered) some = some || f != 0;
+  CHECK(bl.any() == (some && !no_array) && (!bl.any() || bl.bits_per_value == (bopt.bits_per_value == 0 ? 10u : (uint32_t)bopt.bits_per_value)));
+  if (bl.any()) { pqb_prepare(pc, &bl); pqb_size(pc, g, stats, &bl); }
+  {
+    const PqwLayout Bf = pqw_layout(pc, g, stats, dh.page_bytes, nullptr, &x, &bl);
+    CHECK(Bf.body_bytes == L.body_bytes && Bf.blooms.empty() == !bl.any() && (bl.any() || (Bf.bloom_bytes == 0 && Bf.blob == L.blob)));
+    std::vector<unsigned char> bitsets((size_t)bl.table_bytes, 0);  // (sized exactly)
+    pqb_insert_host(pc, g, bl, bitsets.data());
+    uint8_t* filtered_file = pqw_alloc_bytes(Bf.file_bytes(), false);
+    std::memcpy(filtered_file, image.data(), (size_t)Bf.body_bytes);
+    for (const PqwLayout::Bloom& f : Bf.blooms) {
+      CHECK(bl.table_off[f.col] % 32 == 0 && bl.table_off[f.col] + f.bytes <= bl.table_bytes && f.bits_off + f.bytes <= Bf.body_bytes + Bf.bloom_bytes);
+      std::memcpy(filtered_file + f.bits_off, bitsets.data() + bl.table_off[f.col], (size_t)f.bytes);
+    }
+    pqw_finish(Bf, filtered_file);
+    CHECK(std::memcmp(filtered_file, file, (size_t)L.body_bytes) == 0 && std::memcmp(filtered_file + Bf.file_bytes() - 4, "PAR1", 4) == 0);
+    CHECK(Bf.tail.empty() || std::memcmp(filtered_file + Bf.body_bytes + Bf.bloom_bytes, Bf.tail.data(), Bf.tail.size()) == 0);
+    check_bloom(cols, pc, rows, stats, (size_t)g.n_pages, Bf, bl, filtered_file);
+    check_index(cols, pc, g, stats, Bf, x, Bf.chunk_off, Bf.chunk_len);
+    pqw_free_bytes(filtered_file);
+  }
   // the same record with a codec per column at random (three rounds in four): what fdb_selftest_parquet_write_compressed does, step by step
   std::vector<int8_t> codecs;
   for (size_t k = 0; k < n_cols; k++) codecs.push_back((int8_t)(rnd(seed) & 1));
@@ -492,10 +590,18 @@ static void refusals() {
   CHECK(index_code(fdb_parquet_index_options{1, 65537, nullptr, 0}, 1) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{0, -1, nullptr, 0}, 1) == FDB_ERR_INVALID);
   CHECK(index_code(fdb_parquet_index_options{1, 0, &s2, 1}, 2) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{1, 0, twice, 2}, 2) == FDB_ERR_INVALID);
   CHECK(index_code(fdb_parquet_index_options{1, 0, nullptr, 1}, 2) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{1, 0, &s0, -1}, 2) == FDB_ERR_INVALID);
+  const auto bloom_code = [&](const fdb_parquet_bloom_options& o) { try { pqb_plan(&o, pqw_columns(in, 8, &plain_opt, &pr)); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const int8_t none = 0;
+  CHECK(bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_OK && bloom_code(fdb_parquet_bloom_options{&delta, 1, 64}) == FDB_OK && bloom_code(fdb_parquet_bloom_options{nullptr, 0, 0}) == FDB_OK);
+  CHECK(!pqb_plan(nullptr, pqw_columns(in, 8, &plain_opt, &pr)).any() && bloom_code(fdb_parquet_bloom_options{&none, 1, 1}) == FDB_OK);
+  CHECK(bloom_code(fdb_parquet_bloom_options{&two, 1, 0}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{&minus, 1, 0}) == FDB_ERR_INVALID);
+  CHECK(bloom_code(fdb_parquet_bloom_options{both, 2, 0}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{nullptr, 1, 0}) == FDB_ERR_INVALID);
+  CHECK(bloom_code(fdb_parquet_bloom_options{&delta, 1, 65}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{&none, 1, -1}) == FDB_ERR_INVALID);
   in[0].kind = ColKind::F64;
-  CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED);
+  CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED && bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_OK);
   in[0].kind = ColKind::BOOL;
   CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED);
+  CHECK(bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_ERR_UNSUPPORTED && bloom_code(fdb_parquet_bloom_options{&none, 1, 0}) == FDB_OK);
   in[0].kind = ColKind::OTHER;
   CHECK(code(fdb_parquet_write_options{64, 0, nullptr}) == FDB_ERR_UNSUPPORTED);
   in[0].kind = ColKind::DICT;

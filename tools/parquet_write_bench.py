@@ -25,9 +25,15 @@ With --stats the record is written uncompressed and PLAIN with statistics="page"
 and OffsetIndex of every column. The line's own figures are that call's — among the phases stats_ms, the min / max pass of
 fdb_pqstats.hip timed apart (rank upload, table reset, kernel, its wait), and wait_ms, what is then left of the survey's wait — and the
 call without statistics on the same record in the same process, in front of it, goes into the line as with --delta.
+With --bloom the record is written uncompressed and PLAIN with bloom filters on `timestamp` and on the label column `labels.l4`
+(fdb_batch_to_parquet_filtered): 20 M distinct values at 10 bits each — a filter of 25 MB, up to four 64-bit atomic ORs a row — beside
+1 000 entries, whose filter is found set after the first rows and costs its loads. The line's own figures are that call's — among the
+phases bloom_insert_ms, the insert pass of fdb_pqbloom.hip timed apart (entry hashes uploaded, bitsets zeroed, kernel, its wait), and
+bloom_copy_ms, the bitsets' device→host copies — with bloom_bytes, what the filters add to the file, and the call without filters on the
+same record in the same process, in front of it, goes into the line as with --delta.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats | --bloom] [--out FILE]
 """
 import argparse
 import io
@@ -53,6 +59,8 @@ PHASES = ["survey", "layout", "encode", "copy", "host tail"]
 DELTA_PHASES = ["delta compact", "delta survey", "delta encode"]
 SNAPPY_PHASES = ["compress", "scan", "final layout", "gather"]
 STATS_PHASES = ["stats", "wait"]
+BLOOM_PHASES = ["bloom insert", "bloom copy"]
+BLOOM_COLUMNS = ["timestamp", "labels.l4"]
 
 
 def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
@@ -80,7 +88,7 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None):
+def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None):
     """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
     os.environ["FDB_PROFILE"] = "1"
     sys.stderr.flush()
@@ -89,7 +97,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -97,7 +105,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES + BLOOM_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = statistics.median(us) / 1e3 if us else None
     return out
@@ -113,9 +121,10 @@ def main():
     ap.add_argument("--delta", action="store_true", help="write `timestamp` DELTA_BINARY_PACKED; the PLAIN call goes into the same line")
     ap.add_argument("--snappy", action="store_true", help="write every column SNAPPY and `timestamp` DELTA + SNAPPY; the uncompressed PLAIN call goes into the same line")
     ap.add_argument("--stats", action="store_true", help="write statistics and the page index (uncompressed, PLAIN); the call without them goes into the same line")
+    ap.add_argument("--bloom", action="store_true", help="write bloom filters on `timestamp` and `labels.l4` (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert args.delta + args.snappy + args.stats <= 1, "--delta, --snappy or --stats"
+    assert args.delta + args.snappy + args.stats + args.bloom <= 1, "--delta, --snappy, --stats or --bloom"
     record = make_record(args.rows)
     rb = pp.ResidentBatch(record)
     del record
@@ -123,7 +132,8 @@ def main():
         encodings = {"timestamp": "delta"} if args.delta or args.snappy else None
         compression = "snappy" if args.snappy else None
         stats = "page" if args.stats else None
-        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats)
+        bloom = BLOOM_COLUMNS if args.bloom else None
+        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom)
         file_bytes = len(data)
         md = pq.ParquetFile(io.BytesIO(data)).metadata
         assert md.num_rows == args.rows and md.num_row_groups == 1
@@ -134,6 +144,9 @@ def main():
             column_bytes = {md.row_group(0).column(j).path_in_schema: [md.row_group(0).column(j).total_compressed_size, md.row_group(0).column(j).total_uncompressed_size] for j in range(md.num_columns)}
         if args.stats:
             assert all(md.row_group(0).column(j).has_column_index and md.row_group(0).column(j).has_offset_index and md.row_group(0).column(j).statistics.has_min_max for j in range(md.num_columns))
+        if args.bloom:
+            filters = {md.row_group(0).column(j).path_in_schema: md.row_group(0).column(j).to_dict().get("bloom_filter_length") for j in range(md.num_columns)}
+            assert all((filters[n] is not None) == (n in BLOOM_COLUMNS) for n in filters), filters
         del data
         import ctypes
         opts = pp.ParquetWriteOptions(args.page_rows, 0, None)
@@ -143,10 +156,15 @@ def main():
         codecs = (ctypes.c_int8 * n_columns)(*([1] * n_columns))
 
         index = pp.ParquetIndexOptions(2, 0, None, 0)
+        names = rb.column_names
+        bloom_on = (ctypes.c_int8 * n_columns)(*[1 if n in BLOOM_COLUMNS else 0 for n in names])
+        bloom_opts = pp.ParquetBloomOptions(ctypes.cast(bloom_on, ctypes.c_void_p), n_columns, 0)
 
-        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats):
+        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats, filtered=args.bloom):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
-            if indexed:
+            if filtered:
+                rc = pp.lib().fdb_batch_to_parquet_filtered(rb.handle, ctypes.byref(opts), None, 0, None, 0, None, ctypes.byref(bloom_opts), ctypes.byref(out), ctypes.byref(n))
+            elif indexed:
                 rc = pp.lib().fdb_batch_to_parquet_indexed(rb.handle, ctypes.byref(opts), None, 0, None, 0, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
             elif snappy:
                 rc = pp.lib().fdb_batch_to_parquet_compressed(rb.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_columns, ctypes.cast(codecs, ctypes.c_void_p), n_columns,
@@ -158,15 +176,15 @@ def main():
             assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
         plain = {}
-        if args.delta or args.snappy or args.stats:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+        if args.delta or args.snappy or args.stats or args.bloom:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
             plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
-            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False), args.reps, args.warmup)
+            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False, False), args.reps, args.warmup)
             ph = profiled_phases(rb, args.page_rows, args.reps)
             plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
             plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
-        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats), args.reps, 1)
-        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats, bloom)
 
         def bare_copy_ms(n_bytes):
             dev = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
@@ -211,7 +229,10 @@ def main():
                      "final_layout_ms": r3(phases["final layout"]), "gather_ms": r3(phases["gather"]), "column_bytes": column_bytes})
     if args.stats:
         line.update({"statistics": "page", "to_parquet_max_ms": r3(max(to_parquet_all)), "stats_ms": r3(phases["stats"]), "wait_ms": r3(phases["wait"])})
-    if args.delta or args.snappy or args.stats:
+    if args.bloom:
+        line.update({"bloom": BLOOM_COLUMNS, "bloom_bytes": file_bytes - plain["plain_file_bytes"], "to_parquet_max_ms": r3(max(to_parquet_all)), "bloom_insert_ms": r3(phases["bloom insert"]),
+                     "bloom_copy_ms": r3(phases["bloom copy"])})
+    if args.delta or args.snappy or args.stats or args.bloom:
         line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
