@@ -805,6 +805,27 @@ int fdb_selftest_parquet_write_filtered(struct ArrowArray* batch, struct ArrowSc
   });
 }
 
+int fdb_batch_to_parquet_runs(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
+                              const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, const fdb_parquet_run_options* runs, uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom, runs);
+  });
+}
+
+int fdb_selftest_parquet_write_runs(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
+                                    const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
+                                    const fdb_parquet_run_options* runs, uint8_t** bytes, int64_t* n_bytes) {
+  return guard(nullptr, [&] {
+    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    *bytes = nullptr; *n_bytes = 0;
+    fdb::HostRecordView view;
+    fdb::view_record(batch, schema, &view);
+    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom, runs);
+  });
+}
+
 int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_groups, int device, fdb_batch** out) {
   return guard(nullptr, [&] {
     if (out == nullptr || n_groups <= 0) throw fdb::Error(FDB_ERR_INVALID, "null output");

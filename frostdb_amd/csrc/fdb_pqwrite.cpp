@@ -53,6 +53,16 @@
 // one copy per filter straight to its offset in the returned bytes, in the wait of the image's copy: no wait is added. For a compressed
 // file the offsets are the final layout's; filters are never compressed. The host walk is pqb_insert_host. Without a chosen column
 // nothing of this runs.
+//
+// fdb_batch_to_parquet_runs: RLE runs INSIDE a page's dictionary indices and definition levels, on the columns chosen (the rule is
+// spelled out in fdb_pqruns.h and in include/frostdb_amd.h) — what a record sorted by its label columns asks for. A chosen stream of a
+// page that would be ONE bit-packed run is cut into RLE and bit-packed runs instead, never longer. Its size depends on the data, so the
+// run passes of fdb_pqruns.hip sit where DELTA's do: after the survey the compaction of the indices of the chosen columns with a bitmap
+// (scratch of the call's arena) and the run survey, whose table of sizes comes back with the survey's in the same wait; pqw_layout holds
+// every size to the rule's bounds and places the stream (PqwLayout::run_out; the run headers are the device's, so the host's `pre` / `vpre`
+// shrink to the levels' length and the width byte); after the layout the run encoder writes the runs into the same image, beside the
+// encode pass, which leaves such a stream alone. A SNAPPY column's pages go through the staging image as ever. The host walk is
+// pqr_survey_host / pqr_encode_host. Without a chosen stream nothing of this runs.
 #include "fdb_pqwrite_host.h"
 #include "fdb_sortplan.h"
 
@@ -422,6 +432,95 @@ size_t pqw_delta_columns(const std::vector<PqwColumn>& cols) {
   return n;
 }
 
+size_t pqr_streams(const std::vector<PqwColumn>& cols) {
+  size_t n = 0;
+  for (const PqwColumn& c : cols) n += (size_t)(c.run_values >= 0) + (size_t)(c.run_levels >= 0);
+  return n;
+}
+
+size_t pqr_plan(const fdb_parquet_run_options* runs, std::vector<PqwColumn>* cols) {
+  if (runs == nullptr) return 0;
+  if (runs->n_columns != 0 && (runs->n_columns != (int32_t)cols->size() || runs->columns == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: the run options' `columns` has " + std::to_string(runs->n_columns) + " entries, the record " + std::to_string(cols->size()) + " columns");
+  for (int32_t k = 0; k < runs->n_columns; k++) {
+    const int e = (int)runs->columns[k];
+    if (e < 0 || e > 3) throw Error(FDB_ERR_INVALID, "parquet write: run options columns[" + std::to_string(k) + "] is " + std::to_string(e) + " (bit 0 dictionary indices, bit 1 definition levels)");
+    const PqwColumn& c = (*cols)[(size_t)k];
+    if ((e & 1) != 0 && c.pq_kind != FDB_PQW_INDEX && c.pq_kind != PQW_NO_VALUES)
+      throw Error(FDB_ERR_UNSUPPORTED, "parquet write: runs of dictionary indices are for dictionary and string / binary columns; column " + c.name + " is not one");
+  }
+  int next = 0;
+  for (int32_t k = 0; k < runs->n_columns; k++) {
+    PqwColumn& c = (*cols)[(size_t)k];
+    if ((runs->columns[k] & 1) != 0 && c.pq_kind == FDB_PQW_INDEX && c.width > 0) c.run_values = next++;
+    if ((runs->columns[k] & 2) != 0 && c.optional && c.validity != nullptr) c.run_levels = next++;
+  }
+  return (size_t)next;
+}
+
+// ---- runs inside a page: the host's half of the run passes (fdb_pqruns.h) ------------------------------------------------------------------
+std::string pqr_page_host(const uint32_t* sym, uint32_t n, uint32_t w) {
+  const uint32_t G = n / 8, tail = n % 8, GG = fdb_pqw_groups(n), T = fdb_pqr_threshold(w);
+  std::vector<uint32_t> key(G), cls(GG);
+  for (uint32_t i = 0; i < G; i++) key[i] = fdb_pqr_group_key(sym + (size_t)i * 8, 8);
+  for (uint32_t i = 0; i < G; i++) cls[i] = fdb_pqr_class(key.data(), (int32_t)i, 0, (int32_t)G, T);
+  if (tail > 0) cls[G] = fdb_pqr_tail_class(fdb_pqr_group_key(sym + (size_t)G * 8, tail), G > 0, G > 0 ? cls[G - 1] : FDB_PQR_MIXED);
+  std::string s;
+  for (uint32_t i = 0; i < GG;) {
+    uint32_t e = i + 1;
+    while (e < GG && cls[e] == cls[i]) e++;
+    const uint32_t groups = e - i, symbols = (e * 8 < n ? e * 8 : n) - i * 8;
+    const uint32_t head = cls[i] == FDB_PQR_MIXED ? fdb_pqr_packed_header(groups) : fdb_pqr_rle_header(symbols);
+    for (uint32_t b = 0; b < fdb_pqr_varint_len(head); b++) s.push_back((char)fdb_pqr_varint_byte(head, b));
+    if (cls[i] != FDB_PQR_MIXED) {
+      for (uint32_t b = 0; b < fdb_pqr_value_bytes(w); b++) s.push_back((char)(cls[i] >> (8 * b)));
+    } else {
+      for (uint32_t q = i; q < e; q++) {
+        uint32_t grp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t k = 0; k < 8 && (size_t)q * 8 + k < n; k++) grp[k] = sym[(size_t)q * 8 + k];
+        for (uint32_t b = 0; b < w; b++) s.push_back((char)fdb_pqr_group_byte(grp, w, b));
+      }
+    }
+    i = e;
+  }
+  return s;
+}
+
+void pqr_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqrHost* r) {
+  const size_t n_streams = pqr_streams(cols);
+  r->payload.assign(n_streams * (size_t)g.n_pages, std::string());
+  r->page_bytes.assign(n_streams * (size_t)g.n_pages, 0);
+  std::vector<uint32_t> sym;
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& c = cols[k];
+    for (int pass = 0; pass < 2; pass++) {
+      const bool levels = pass == 1;
+      const int slot = levels ? c.run_levels : c.run_values;
+      if (slot < 0) continue;
+      const uint32_t w = levels ? 1u : c.width, mask = w >= 32 ? 0xFFFFFFFFu : ((1u << w) - 1);
+      for (int64_t p = 0; p < g.n_pages; p++) {
+        const FdbPqwPageStat& s = stats[k * (size_t)g.n_pages + (size_t)p];
+        const int64_t first = fdb_pqw_page_first(g, p), end = fdb_pqw_page_end(g, p);
+        if (!fdb_pqr_active(levels, s.count, (uint32_t)(end - first), s.mn, s.mx)) continue;
+        sym.clear();
+        for (int64_t row = first; row < end; row++) {  // the stream's symbols: every row's validity bit, or the non-NULL rows' indices in order
+          const bool valid = c.validity == nullptr || ((c.validity[row >> 3] >> (row & 7)) & 1);
+          if (levels) sym.push_back(valid ? 1u : 0u);
+          else if (valid) sym.push_back(((const uint32_t*)c.values)[row] & mask);
+        }
+        const size_t at = (size_t)slot * (size_t)g.n_pages + (size_t)p;
+        r->payload[at] = pqr_page_host(sym.data(), (uint32_t)sym.size(), w);
+        r->page_bytes[at] = (uint32_t)r->payload[at].size();
+      }
+    }
+  }
+}
+
+void pqr_encode_host(const PqrHost& r, const std::vector<uint64_t>& run_out, unsigned char* image) {
+  for (size_t i = 0; i < r.payload.size(); i++)
+    if (run_out[i] != FDB_PQW_NONE && !r.payload[i].empty()) std::memcpy(image + run_out[i], r.payload[i].data(), r.payload[i].size());
+}
+
 FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols) {
   FdbPqwGeom g;
   g.rows = rows; g.page_rows = page_rows; g.n_pages = fdb_pqw_pages(rows, page_rows); g.tiles_per_page = fdb_pqw_tiles_per_page(page_rows);
@@ -610,7 +709,7 @@ std::string pqs_block_host(const unsigned char* body, size_t n) {
 }
 
 PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes,
-                     const std::vector<uint32_t>* page_elements, const PqxIndex* x, const PqbPlan* bloom) {
+                     const std::vector<uint32_t>* page_elements, const PqxIndex* x, const PqbPlan* bloom, const std::vector<uint32_t>* run_bytes) {
   if (x != nullptr && !x->any()) x = nullptr;
   if (bloom != nullptr && !bloom->any()) bloom = nullptr;
   if (bloom != nullptr && bloom->bytes.size() != cols.size()) throw Error(FDB_ERR_STATE, "parquet write: the bloom filter sizes do not match the record");
@@ -620,6 +719,15 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
   if (delta_bytes.size() != pqw_delta_columns(cols) * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
   if (page_elements != nullptr && page_elements->size() != pqw_compressed_columns(cols) * (size_t)g.n_pages)
     throw Error(FDB_ERR_STATE, "parquet write: the table of compressed page sizes does not match the record");
+  const size_t n_run_streams = pqr_streams(cols);
+  if ((run_bytes != nullptr ? run_bytes->size() : 0) != n_run_streams * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of run-encoded sizes does not match the record");
+  // The bytes of a page's stream cut into runs, held to the rule's bounds: no more than its one bit-packed run, no less than a run.
+  const auto run_payload = [&](const PqwColumn& c, int slot, int64_t p, uint32_t n, uint32_t w) {
+    const uint32_t bytes = (*run_bytes)[(size_t)slot * (size_t)g.n_pages + (size_t)p];
+    if (bytes > fdb_pqr_max_bytes(n, w) || bytes < fdb_pqr_min_bytes(w))
+      throw Error(FDB_ERR_STATE, "parquet write: the run survey sizes a stream of " + std::to_string(n) + " symbols of " + std::to_string(w) + " bits at " + std::to_string(bytes) + " bytes (" + c.name + ")");
+    return (uint64_t)bytes;
+  };
   const bool final_form = page_elements != nullptr;  // else: every page as it is before compression — the file of a record without codecs, the staging image of one with
   size_t next_compressed = 0;
   PqwLayout L;
@@ -627,6 +735,7 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
   L.chunk_len.assign(cols.size(), 0);
   L.delta_out.assign(delta_bytes.size(), FDB_PQW_NONE);
   L.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
+  L.run_out.assign(n_run_streams * (size_t)g.n_pages, FDB_PQW_NONE);
   uint64_t cur = 0;
   L.put(cur, "PAR1");
   cur += 4;
@@ -655,10 +764,14 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
       valid += cnt;
       std::string pre, vpre;
       uint64_t level_payload = 0, value_payload = 0;
+      const bool level_runs = c.run_levels >= 0 && fdb_pqr_active(true, cnt, n, s.mn, s.mx), value_runs = c.run_values >= 0 && fdb_pqr_active(false, cnt, n, s.mn, s.mx);
       if (c.optional) {
         if (cnt == n || cnt == 0) {
           const std::string run = varint_bytes((uint64_t)n << 1) + std::string(1, cnt == n ? '\1' : '\0');
           pre = le32((uint32_t)run.size()) + run;
+        } else if (level_runs) {  // the runs, headers and all, are the device's
+          level_payload = run_payload(c, c.run_levels, p, n, 1);
+          pre = le32((uint32_t)level_payload);
         } else {
           level_payload = fdb_pqw_level_bytes(n);
           const std::string run = varint_bytes(((uint64_t)fdb_pqw_level_bytes(n) << 1) | 1);
@@ -683,6 +796,8 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
           if (s.mn == s.mx) {  // one RLE run: the count, the value in ⌈w/8⌉ bytes
             vpre += varint_bytes((uint64_t)cnt << 1);
             for (uint32_t b = 0; b < (c.width + 7) / 8; b++) vpre.push_back((char)(s.mn >> (8 * b)));
+          } else if (value_runs) {
+            value_payload = run_payload(c, c.run_values, p, cnt, c.width);
           } else {
             vpre += varint_bytes(((uint64_t)fdb_pqw_groups(cnt) << 1) | 1);
             value_payload = fdb_pqw_packed_bytes(cnt, c.width);
@@ -713,10 +828,12 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
         L.pages.push_back(PqwLayout::Page{cur, body});
         L.put_body(cur, pre); cur += pre.size();
       }
-      if (level_payload > 0) { o.levels_off = cur; cur += level_payload; }
+      if (level_runs) { L.run_out[(size_t)c.run_levels * (size_t)g.n_pages + (size_t)p] = cur; cur += level_payload; }
+      else if (level_payload > 0) { o.levels_off = cur; cur += level_payload; }
       if (c.codec == 0) L.put(cur, vpre); else L.put_body(cur, vpre);
       cur += vpre.size();
-      if (c.delta_slot >= 0) { L.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
+      if (value_runs && c.pq_kind == FDB_PQW_INDEX) { L.run_out[(size_t)c.run_values * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }
+      else if (c.delta_slot >= 0) { L.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
       else if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
     }
     m.bytes = (int64_t)(cur - chunk_start);
@@ -938,7 +1055,8 @@ void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
 }
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                            const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom) {
+                            const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
+                            const fdb_parquet_run_options* runs) {
   // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
   const size_t rows = (size_t)view.rows;
   std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
@@ -983,9 +1101,10 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     in.push_back(std::move(o));
   }
   int32_t page_rows = 0;
-  const std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
+  std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
   PqxIndex x = pqx_plan(index, cols.size());
   PqbPlan bl = pqb_plan(bloom, cols);
+  const size_t n_runs = pqr_plan(runs, &cols);
   const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
@@ -1001,11 +1120,15 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
   if (x.statistics > 0) { pqx_prepare(cols, &x); pqx_minmax_host(cols, g, &x); }
   PqdHost delta;
   pqd_survey_host(cols, g, stats, tile_base, &delta);
+  PqrHost rn;
+  if (n_runs > 0) pqr_survey_host(cols, g, stats, &rn);
+  const std::vector<uint32_t>* run_bytes = n_runs > 0 ? &rn.page_bytes : nullptr;
   const bool squeezed = pqw_compressed_columns(cols) > 0;  // then L is the staging image's layout, and the index is the final one's
-  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes, nullptr, squeezed ? nullptr : &x, squeezed ? nullptr : &bl);
+  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes, nullptr, squeezed ? nullptr : &x, squeezed ? nullptr : &bl, run_bytes);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(cols, g, L.out, tile_base, image.data());
   pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
+  if (n_runs > 0) pqr_encode_host(rn, L.run_out, image.data());
   if (!squeezed) {
     const size_t file_bytes = L.file_bytes();
     uint8_t* file = pqw_alloc_bytes(file_bytes, false);
@@ -1029,7 +1152,7 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     }
     page_elements[i] = (uint32_t)elements[i].size();
   }
-  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements, &x, &bl);
+  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements, &x, &bl, run_bytes);
   const size_t file_bytes = F.file_bytes();
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
   for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
@@ -1043,7 +1166,8 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
 
 #ifndef FDB_PQWRITE_HOST_ONLY
 void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                      const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom) {
+                      const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
+                      const fdb_parquet_run_options* runs) {
   std::vector<PqwInput> in;
   for (const DevColumn& c : b.cols) {
     PqwInput o;
@@ -1051,8 +1175,9 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     in.push_back(std::move(o));
   }
   int32_t page_rows = 0;
-  const std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
+  std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
   PqxIndex x = pqx_plan(index, cols.size());
+  const size_t n_runs = pqr_plan(runs, &cols);
   const bool bounds = x.statistics > 0;
   if (bounds) {
     pqx_prepare(cols, &x);
@@ -1075,7 +1200,8 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     if (bounds) x.table.assign(2 * cols.size() * (size_t)g.n_pages, 0);  // (no page: no slot)
     const std::vector<FdbPqwPageStat> no_stats(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0});
     if (bl.any()) pqb_size(cols, g, no_stats, &bl);
-    const PqwLayout L = pqw_layout(cols, g, no_stats, {}, n_compressed > 0 ? &no_pages : nullptr, &x, &bl);
+    const std::vector<uint32_t> no_runs(n_runs * (size_t)g.n_pages, 0);
+    const PqwLayout L = pqw_layout(cols, g, no_stats, {}, n_compressed > 0 ? &no_pages : nullptr, &x, &bl, n_runs > 0 ? &no_runs : nullptr);
     const size_t file_bytes = L.file_bytes();
     file.p = pqw_alloc_bytes(file_bytes, false);
     for (const PqwLayout::Bloom& f : L.blooms) std::memset(file.p + f.bits_off, 0, (size_t)f.bytes);  // (no value: one zero block each)
@@ -1120,6 +1246,32 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     d_blocks = (FdbPqdBlock*)cs.alloc(d_items * (size_t)fdb_pqd_blocks_per_page(g.page_rows) * sizeof(FdbPqdBlock));
     d_page_bytes = (uint32_t*)cs.alloc(d_items * 4);
   }
+  // the streams to be cut into runs: scratch for the dense indices of the columns with a bitmap, the table of sizes — from the call's arena
+  const size_t r_items = n_runs * (size_t)g.n_pages;
+  std::vector<uint32_t> run_bytes(r_items);
+  const FdbPqrStream* d_streams = nullptr;
+  uint32_t* d_run_bytes = nullptr;
+  bool run_compact = false;
+  if (n_runs > 0) {
+    std::vector<FdbPqrStream> rs(n_runs);
+    for (size_t k = 0; k < cols.size(); k++) {
+      const PqwColumn& c = cols[k];
+      if (c.run_values >= 0) {
+        FdbPqrStream& o = rs[(size_t)c.run_values];
+        std::memset(&o, 0, sizeof(FdbPqrStream));
+        o.values = (const uint32_t*)c.values; o.validity = c.validity; o.col = (int32_t)k; o.width = (int32_t)c.width;
+        o.dense = c.validity != nullptr ? (uint32_t*)cs.alloc(((size_t)g.rows + 8) * 4) : (uint32_t*)const_cast<void*>(c.values);  // (only ever read when it is the column)
+        run_compact = run_compact || c.validity != nullptr;
+      }
+      if (c.run_levels >= 0) {
+        FdbPqrStream& o = rs[(size_t)c.run_levels];
+        std::memset(&o, 0, sizeof(FdbPqrStream));
+        o.validity = c.validity; o.col = (int32_t)k; o.width = 1; o.levels = 1;
+      }
+    }
+    d_streams = (const FdbPqrStream*)cs.ctx->stage(rs.data(), rs.size() * sizeof(FdbPqrStream));
+    d_run_bytes = (uint32_t*)cs.alloc(r_items * 4);
+  }
   b.note_reader(stream);
   hip_check(fdb_launch_pqw_survey(d_cols, g, d_stats, d_tile_base, stream), "parquet write: survey launch");
   hip_check(hipMemcpyAsync(stats.data(), d_stats, items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(page table)");
@@ -1151,10 +1303,17 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     hip_check(fdb_launch_pqd_survey(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_page_bytes, stream), "parquet write: DELTA block survey launch");
     hip_check(hipMemcpyAsync(delta_bytes.data(), d_page_bytes, d_items * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(DELTA page sizes)");
   }
+  if (n_runs > 0) {  // the run passes (fdb_pqruns.hip): beside the survey, their table back in the same wait
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark(n_delta > 0 ? "pqwrite delta survey" : bounds ? "pqwrite wait" : "pqwrite survey"); }
+    if (run_compact) hip_check(fdb_launch_pqr_compact(d_streams, (int32_t)n_runs, g, d_tile_base, stream), "parquet write: run compaction launch");
+    hip_check(fdb_launch_pqr_survey(d_streams, (int32_t)n_runs, g, d_stats, d_run_bytes, stream), "parquet write: run survey launch");
+    hip_check(hipMemcpyAsync(run_bytes.data(), d_run_bytes, r_items * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(run-encoded sizes)");
+  }
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  pt.mark(n_delta > 0 ? "pqwrite delta survey" : bounds && pt.on ? "pqwrite wait" : "pqwrite survey");
+  pt.mark(n_runs > 0 ? "pqwrite run survey" : n_delta > 0 ? "pqwrite delta survey" : bounds && pt.on ? "pqwrite wait" : "pqwrite survey");
   if (bl.any()) pqb_size(cols, g, stats, &bl);
-  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes, nullptr, n_compressed > 0 ? nullptr : &x, n_compressed > 0 ? nullptr : &bl);
+  const std::vector<uint32_t>* run_table = n_runs > 0 ? &run_bytes : nullptr;
+  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes, nullptr, n_compressed > 0 ? nullptr : &x, n_compressed > 0 ? nullptr : &bl, run_table);
   const size_t file_bytes = L.file_bytes(), image_bytes = align_up((size_t)L.body_bytes + 8, 256);
   pt.mark("pqwrite layout");
   // The bloom filters (fdb_pqbloom.hip): the survey's table has sized them, so their bitsets — one zeroed table of the call's arena,
@@ -1200,6 +1359,12 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
     hip_check(fdb_launch_pqd_encode(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_delta_out, (unsigned char*)image.p, stream), "parquet write: DELTA encode launch");
     if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta encode"); }
   }
+  if (n_runs > 0) {
+    uint64_t* d_run_out = (uint64_t*)cs.alloc(r_items * 8);
+    hip_check(hipMemcpyAsync(d_run_out, L.run_out.data(), r_items * 8, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(run-encoded page offsets)");
+    hip_check(fdb_launch_pqr_encode(d_streams, (int32_t)n_runs, g, d_stats, d_run_bytes, d_run_out, (unsigned char*)image.p, stream), "parquet write: run encode launch");
+    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite run encode"); }
+  }
   if (n_compressed == 0) {
     file.p = pqw_alloc_bytes(file_bytes, true);
     bloom_out(L, file.p);
@@ -1244,7 +1409,7 @@ void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt
   if (!pages.empty()) hip_check(hipMemcpyAsync(page_elements.data(), d_page_elements, pages.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(compressed page sizes)");
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   pt.mark("pqwrite scan");
-  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements, &x, &bl);
+  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements, &x, &bl, run_table);
   const size_t out_bytes = F.file_bytes();
   pt.mark("pqwrite final layout");
   std::vector<uint64_t> page_dst(F.pages.size());

@@ -10,6 +10,7 @@
 #include "fdb_arrow.h"
 #include "fdb_pqbloom.h"
 #include "fdb_pqdelta.h"
+#include "fdb_pqruns.h"
 #include "fdb_pqsnappy.h"
 #include "fdb_pqstats.h"
 #include "fdb_pqwrite.h"
@@ -38,6 +39,7 @@ struct PqwColumn {
   bool is_u64 = false, utf8 = false, optional = false;
   int delta_slot = -1;            // >= 0: written DELTA_BINARY_PACKED, and its place among the columns that are (the tables of fdb_pqdelta.h)
   int codec = 0;                  // parquet CompressionCodec of the chunk's pages: 0 UNCOMPRESSED, 1 SNAPPY
+  int run_values = -1, run_levels = -1;  // >= 0: the pages' indices / definition levels are cut into runs (fdb_pqruns.h), and the stream's place in the tables of that
   uint32_t width = 0;
   uint64_t entries = 0;
   const HostDict* dict = nullptr;
@@ -53,6 +55,7 @@ struct PqwLayout {
   std::vector<Piece> pieces;
   std::vector<FdbPqwPageOut> out;
   std::vector<uint64_t> delta_out;  // [delta_slot × n_pages + page]: where a DELTA page's value bytes start (its `out` says FDB_PQW_NONE for the values)
+  std::vector<uint64_t> run_out;    // [run stream × n_pages + page]: where a stream cut into runs starts (FDB_PQW_NONE: the page's is not; then `out` says where it goes)
   uint64_t body_bytes = 0;       // PAR1 + column chunks: what the image holds; the footer starts here
   std::string footer;
   void put(uint64_t off, const std::string& s);
@@ -123,6 +126,12 @@ void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, Pq
 std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows,
                                    const int8_t* encodings = nullptr, int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0);
 size_t pqw_delta_columns(const std::vector<PqwColumn>& cols);
+// What fdb_parquet_run_options asks for, checked, into the columns' run_values / run_levels; returns the streams. Every refusal:
+// FDB_ERR_INVALID — n_columns neither 0 nor the column count, an entry outside 0 … 3; FDB_ERR_UNSUPPORTED, naming the column — bit 0
+// on a column that is not an INDEX column. Nothing has been launched yet. A stream that could never hold more than one run gets no
+// place: levels of a required column or of one without a bitmap, indices of a dictionary of fewer than two entries.
+size_t pqr_plan(const fdb_parquet_run_options* runs, std::vector<PqwColumn>* cols);
+size_t pqr_streams(const std::vector<PqwColumn>& cols);
 size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols);
 // The Snappy block of `n` bytes: the preamble and every fragment's elements, by the host walk of fdb_pqsnappy.h.
 std::string pqs_block_host(const unsigned char* body, size_t n);
@@ -132,7 +141,10 @@ FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
 // one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of the elements of the
 // page's Snappy block (the preamble not counted), as the compressor found them.
 PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes = {},
-                     const std::vector<uint32_t>* page_elements = nullptr, const PqxIndex* index = nullptr, const PqbPlan* bloom = nullptr);
+                     const std::vector<uint32_t>* page_elements = nullptr, const PqxIndex* index = nullptr, const PqbPlan* bloom = nullptr,
+                     const std::vector<uint32_t>* run_bytes = nullptr);
+// (`run_bytes`[run stream × n_pages + page]: the bytes of a page's stream cut into runs, as the run survey found them — held to the
+// rule's bounds before they are trusted; looked at only where fdb_pqr_active says the rule applies.)
 // Fills the holes of `file` (L.file_bytes() long, the payloads in place — the bitsets of L.blooms included) and appends the page index,
 // if any, footer, length and magic.
 void pqw_finish(const PqwLayout& L, uint8_t* file);
@@ -153,15 +165,28 @@ void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
 void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const PqdHost& d, const std::vector<uint64_t>& delta_out,
                      unsigned char* image);
 
+// The run passes over host arrays, the rule of fdb_pqruns.h that the kernels compile: every stream's runs, page by page, kept as bytes
+// (pqr_survey_host; their lengths are the table the layout wants) and then put where the layout says (pqr_encode_host).
+struct PqrHost {
+  std::vector<std::string> payload;   // [run stream × n_pages + page]; empty where the rule does not apply
+  std::vector<uint32_t> page_bytes;
+};
+// A stream's bytes by the rule: n symbols at width w.
+std::string pqr_page_host(const uint32_t* sym, uint32_t n, uint32_t w);
+void pqr_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqrHost* r);
+void pqr_encode_host(const PqrHost& r, const std::vector<uint64_t>& run_out, unsigned char* image);
+
 // The buffer a file is returned in (fdb_bytes_free): malloc'ed, or a block of the pinned result pool when the device copies into it.
 uint8_t* pqw_alloc_bytes(size_t n, bool pinned);
 void pqw_free_bytes(uint8_t* bytes);
 
 void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr,
-                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr);
+                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr,
+                            const fdb_parquet_run_options* runs = nullptr);
 #ifndef FDB_PQWRITE_HOST_ONLY
 void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr, int32_t n_encodings = 0,
-                      const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr);
+                      const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr,
+                      const fdb_parquet_run_options* runs = nullptr);
 #endif
 
 }  // namespace fdb

@@ -178,6 +178,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_parquet_write_indexed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
     L.fdb_batch_to_parquet_filtered.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, P(vp), P(i64)]
     L.fdb_selftest_parquet_write_filtered.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, P(vp), P(i64)]
+    L.fdb_batch_to_parquet_runs.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, P(vp), P(i64)]
+    L.fdb_selftest_parquet_write_runs.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
     L.fdb_bytes_free.restype = None
     _lib = L
@@ -474,6 +476,40 @@ def _parquet_bloom_options(bloom_filters, bits_per_value, names, is_bool, sortin
     return ParquetBloomOptions(ctypes.cast(arr, ctypes.c_void_p) if wanted else None, len(wanted), bits_per_value), arr
 
 
+class ParquetRunOptions(ctypes.Structure):
+    """fdb_parquet_run_options."""
+    _fields_ = [("columns", ctypes.c_void_p), ("n_columns", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+PARQUET_RUN_STREAMS = {None: 0, False: 0, "values": 1, "levels": 2, True: 3}
+
+
+def _parquet_run_options(runs, names, is_index):
+    """`runs`: None; True — every column, its definition levels and, of a dictionary / string / binary column (`is_index`: per
+    column), its indices; a sequence of column names (both streams of each); or a dict of name → True (both) / "values" (the
+    dictionary indices) / "levels" (the definition levels) / None. Returns the struct and what it points at, or (None, None) when
+    nothing is asked: the caller then calls what it called without this argument."""
+    if runs is None or runs is False:
+        return None, None
+    if runs is True:
+        wanted = [2 | (1 if ix else 0) for ix in is_index]
+    elif isinstance(runs, str):
+        _raise(FDB_ERR_INVALID, "parquet write: `runs` is True, a sequence of column names or a dict of name → True / 'values' / 'levels', got %r" % (runs,))
+    else:
+        wanted = [0] * len(names)
+        for n in runs:
+            if not isinstance(n, str) or n not in names:
+                _raise(FDB_ERR_INVALID, "parquet write: `runs` names no column of the record: %s" % (n,))
+            e = runs[n] if isinstance(runs, dict) else True
+            if isinstance(e, (list, dict, set, tuple)) or e not in PARQUET_RUN_STREAMS or (not isinstance(e, (bool, str)) and e is not None):
+                _raise(FDB_ERR_INVALID, "parquet write: unknown run streams %r (True, 'values', 'levels' or None)" % (e,))
+            wanted[names.index(n)] = PARQUET_RUN_STREAMS[e]
+    if not any(wanted):
+        return None, None
+    arr = (ctypes.c_int8 * max(1, len(wanted)))(*wanted)
+    return ParquetRunOptions(ctypes.cast(arr, ctypes.c_void_p), len(wanted), 0), arr
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -484,20 +520,30 @@ def _take_bytes(rc, out, n) -> bytes:
 
 
 def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0,
-                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0) -> bytes:
+                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None) -> bytes:
     """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
     made without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
     fdb_selftest_parquet_write_compressed, with `statistics`, `index_size_limit` or `sorting_columns`
     fdb_selftest_parquet_write_indexed, with `bloom_filters` or `bloom_bits_per_value` fdb_selftest_parquet_write_filtered): the same
-    layout, headers and footer, the kernels replaced by a host walk of the code they compile."""
+    layout, headers and footer, the kernels replaced by a host walk of the code they compile. With `runs`
+    fdb_selftest_parquet_write_runs: the run passes walked as well."""
     names = list(record.schema.names)
     opts, _keep = _parquet_write_options(page_rows, optional, names)
     enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
     index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
     bloom, _keep_bloom = _parquet_bloom_options(bloom_filters, bloom_bits_per_value, names, [pa.types.is_boolean(f.type) for f in record.schema], sorting_columns)
+    def is_index(t):
+        t = t.value_type if pa.types.is_dictionary(t) else t
+        return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
+    run_opts, _keep_runs = _parquet_run_options(runs, names, [is_index(f.type) for f in record.schema])
     out, n = ctypes.c_void_p(), ctypes.c_int64()
     with ExportedBatch(record) as ex:
-        if bloom is not None:
+        if run_opts is not None:
+            codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
+            rc = lib().fdb_selftest_parquet_write_runs(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
+                                                       n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
+                                                       ctypes.byref(bloom) if bloom is not None else None, ctypes.byref(run_opts), ctypes.byref(out), ctypes.byref(n))
+        elif bloom is not None:
             codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
             rc = lib().fdb_selftest_parquet_write_filtered(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
                                                            n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
@@ -853,7 +899,7 @@ class ResidentBatch:
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
     def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0, sorting_columns=None,
-                   bloom_filters=None, bloom_bits_per_value: int = 0) -> bytes:
+                   bloom_filters=None, bloom_bits_per_value: int = 0, runs=None) -> bytes:
         """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, data pages V1 of
         `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
@@ -874,13 +920,25 @@ class ResidentBatch:
         `bloom_bits_per_value` bits per non-NULL row (0 = 10; a dictionary column: per entry, when those are fewer), its bits set on the
         device by one more pass, written after the pages and named by ColumnMetaData.bloom_filter_offset / _length — what FrostDB's
         scan asks first for `=` (fdb_batch_to_parquet_filtered). A boolean column is refused; an unknown name is FDB_ERR_INVALID.
-        Without these two the call is what it was."""
+        Without these two the call is what it was. `runs`: None; True — every column; a sequence of column names; or a dict of
+        name → True / "values" / "levels" / None: the pages' dictionary indices ("values") and definition levels ("levels") are cut
+        into RLE and bit-packed runs instead of one bit-packed run each (the rule: include/frostdb_amd.h) — what a record sorted by
+        its label columns asks for, where a label column is long stretches of one index and a dynamic column long stretches of NULL;
+        sized and written on the device by two more passes (fdb_batch_to_parquet_runs). No page gets longer. "values" on a column
+        that has no dictionary is refused (True skips such columns). Without it the call is what it was."""
         opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
         out, n = ctypes.c_void_p(), ctypes.c_int64()
         index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, self.column_names)
         bloom, _keep_bloom = (None, None) if bloom_filters is None and not bloom_bits_per_value else _parquet_bloom_options(
             bloom_filters, bloom_bits_per_value, self.column_names, [f == "b" for f in self.column_formats], sorting_columns)
-        if bloom is not None:
+        run_opts, _keep_runs = (None, None) if runs is None else _parquet_run_options(runs, self.column_names, [f not in ("l", "L", "g", "b") for f in self.column_formats])
+        if run_opts is not None:
+            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
+            codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
+            rc = lib().fdb_batch_to_parquet_runs(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,
+                                                 ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
+                                                 ctypes.byref(bloom) if bloom is not None else None, ctypes.byref(run_opts), ctypes.byref(out), ctypes.byref(n))
+        elif bloom is not None:
             enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
             codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
             rc = lib().fdb_batch_to_parquet_filtered(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,

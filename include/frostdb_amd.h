@@ -687,6 +687,39 @@ typedef struct fdb_parquet_bloom_options {
 FDB_API int fdb_batch_to_parquet_filtered(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_filtered(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 
+/* The same two calls with RLE runs INSIDE a page's dictionary indices and definition levels — what a record sorted by its label columns
+ * asks for: there a label column is long stretches of one index and a dynamic column long stretches of NULL and of not-NULL, which the
+ * calls above write at the column's full width unless a whole page is one value. With runs == NULL, n_columns == 0 or every entry 0 the
+ * file is fdb_batch_to_parquet_filtered's, byte for byte, made by the same path — no further launch, allocation or wait.
+ *
+ * The rule (fdb_pqruns.h). A stream is n symbols at width w >= 1: a page's definition levels (w = 1, n = the page's rows) or an INDEX
+ * column's page values (w = the column's width, n = the page's non-NULL rows, by rank). It applies only where the calls above emit ONE
+ * bit-packed run; a page that is one RLE run, a column of width 0, an empty page and V64 / BOOL / DELTA payloads stay byte for byte.
+ * G = n / 8 full groups, then n mod 8 tail symbols. A group is uniform when its 8 symbols are equal, a stretch a maximal range of
+ * consecutive uniform groups of one value, T = ⌈16 / w⌉. A stretch of at least T groups is an RLE run: varint(count << 1), the value in
+ * ⌈w / 8⌉ little-endian bytes. The tail joins the last RLE run when the stretch ending at group G − 1 is one and every tail symbol
+ * equals its value. Every maximal range of the remaining groups is a bit-packed run: varint((groups << 1) | 1), groups × w bytes,
+ * LSB first; a tail that joined nothing is one more zero-padded group at the end of the last bit-packed run, or a run of one group of
+ * its own right after an RLE run. Two RLE runs may follow each other. An RLE run replaces at least 16 packed bytes and costs at most
+ * 4 + 4 + 4 (its header, its value, the header of the bit-packed run it splits off), so no page gets longer.
+ *
+ * The sizes now depend on the data, so the passes sit where DELTA's do (fdb_pqruns.hip): after the survey a compaction of the indices
+ * of the chosen columns that have a bitmap (4 bytes a row of scratch from the call's arena) and the run survey, a workgroup per
+ * (stream, page), whose table of sizes comes back with the survey's in the wait the call already pays; after the layout the run
+ * encoder, beside the encode pass, into the same image. A SNAPPY column's pages go through the staging image as ever. Statistics, the
+ * page index, bloom filters, sorting_columns and the encodings lists are untouched; sizes and PageLocations follow the new bodies.
+ *
+ * Refused before anything is launched: FDB_ERR_INVALID — n_columns neither 0 nor the column count, an entry outside 0 … 3;
+ * FDB_ERR_UNSUPPORTED, naming the column — bit 0 on a column that is not a dictionary / string / binary column. Bit 1 on a required
+ * column is ignored. Everything the calls above refuse, unchanged; their structs keep their layouts. */
+typedef struct fdb_parquet_run_options {
+  const int8_t* columns;   /* per column: bit 0 = dictionary indices, bit 1 = definition levels */
+  int32_t n_columns;       /* 0 or the record's column count */
+  int32_t pad;
+} fdb_parquet_run_options;
+FDB_API int fdb_batch_to_parquet_runs(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_runs(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry
  * point takes HOST buffers, for tests and measurement: `src` holds the compressed pages (pages[i] = {src_off, dst_off, src_len,

@@ -10,6 +10,8 @@
 # … and with bloom filter options at random — columns and bits per value: the insert pass's host walk (fdb_pqbloom.h), the filters'
 # headers and bitsets between the pages and the index — and a reader of the program's own, with its own XXH64, finds every non-NULL
 # value in its column's filter and no bit that no value set.
+# … and with run options at random — per column the dictionary indices, the definition levels, both or none: the run passes' host walk
+# (fdb_pqruns.h), every stream cut into runs decoded by a hybrid reader of the program's own and held to "never longer than packed".
 # No GPU, no HIP runtime (fdb_codec.h takes its types from the HIP headers), no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

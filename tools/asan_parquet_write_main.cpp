@@ -15,6 +15,10 @@
 // bits of fdb_pqbloom.h that the kernel compiles) fills a table of bitsets sized exactly, the layout puts header and bitset of every
 // filter between the pages and the index, and a reader of this file's own — its own XXH64, block and salts — finds every non-NULL
 // value of the record in its column's filter, and no bit set that no value set.
+// And with run options at random (per column: dictionary indices, definition levels, both, none): the run passes' host walk
+// (pqr_survey_host / pqr_encode_host: the rule of fdb_pqruns.h that the kernels compile) sizes and writes the streams, the layout holds
+// the sizes to the rule's bounds, and a hybrid reader of this file's own decodes every run-encoded stream out of a buffer sized exactly
+// — to the page's validity bits or non-NULL indices — and holds it to "never longer than the one bit-packed run".
 // No GPU, no HIP, no python. Prints "asan parquet write ok" and exits 0 when every check holds.
 #include <cstdio>
 #include <cstdlib>
@@ -97,6 +101,35 @@ static void check_delta_page(const uint8_t* p, size_t bytes, const std::vector<u
     }
   }
   CHECK(at == bytes);
+}
+
+// A stream of the RLE / bit-packed hybrid of exactly `bytes` bytes decodes to `want` at width w: padding zero, nothing behind the last run.
+static size_t g_rle_inside = 0, g_streams = 0;  // streams read back, and those of more than one run with an RLE run among them
+static void check_hybrid(const uint8_t* p, size_t bytes, uint32_t w, const std::vector<uint32_t>& want) {
+  size_t at = 0, n = 0, runs = 0, rle = 0;
+  while (at < bytes) {
+    const uint64_t head = read_varint(p, &at);
+    runs++;
+    if (head & 1) {
+      const uint64_t groups = head >> 1;
+      CHECK(groups > 0 && at + groups * w <= bytes && n < want.size() && n + groups * 8 < want.size() + 8);
+      for (uint64_t j = 0; j < groups * 8; j++) CHECK(read_bits(p + at, j * w, w) == (n + j < want.size() ? want[n + j] : 0u));
+      n = n + groups * 8 < want.size() ? n + (size_t)groups * 8 : want.size();
+      at += (size_t)(groups * w);
+    } else {
+      const uint64_t count = head >> 1;
+      uint32_t v = 0;
+      CHECK(count >= 8 && at + (w + 7) / 8 <= bytes && n + count <= want.size());
+      for (uint32_t b = 0; b < (w + 7) / 8; b++) v |= (uint32_t)p[at + b] << (8 * b);
+      for (uint64_t j = 0; j < count; j++) CHECK(want[n + j] == v);
+      n += (size_t)count;
+      at += (w + 7) / 8;
+      rle++;
+    }
+  }
+  CHECK(at == bytes && n == want.size() && runs > 0);
+  g_streams++;
+  g_rle_inside += runs > 1 && rle > 0;
 }
 
 // `block` (sized exactly) inflates to `body` (into a buffer sized exactly), and stays within Snappy's bound.
@@ -491,6 +524,57 @@ static void one_record(uint64_t* seed, int round) {
     check_index(cols, pc, g, stats, Bf, x, Bf.chunk_off, Bf.chunk_len);
     pqw_free_bytes(filtered_file);
   }
+  // … and with run options at random: no page longer, every stream cut into runs decodes to the page's levels or indices
+  std::vector<int8_t> run_flags;
+  for (size_t k = 0; k < n_cols; k++) run_flags.push_back((int8_t)(cols[k].kind == ColKind::DICT ? rnd(seed) % 4 : (rnd(seed) & 1) * 2));
+  const fdb_parquet_run_options ropt{run_flags.data(), (int32_t)n_cols, 0};
+  std::vector<PqwColumn> rc = pc;
+  const size_t n_streams = pqr_plan(&ropt, &rc);
+  CHECK(n_streams == pqr_streams(rc) && n_streams <= 2 * n_cols);
+  if (n_streams > 0) {
+    PqrHost rh;
+    pqr_survey_host(rc, g, stats, &rh);
+    CHECK(rh.page_bytes.size() == n_streams * (size_t)g.n_pages);
+    const PqwLayout Rl = pqw_layout(rc, g, stats, dh.page_bytes, nullptr, nullptr, nullptr, &rh.page_bytes);
+    CHECK(Rl.body_bytes <= L.body_bytes && Rl.run_out.size() == rh.page_bytes.size());
+    std::vector<unsigned char> rimage(((size_t)Rl.body_bytes + 8 + 3) / 4 * 4, 0);
+    pqw_encode_host(rc, g, Rl.out, tile_base, rimage.data());
+    pqd_encode_host(rc, g, stats, dh, Rl.delta_out, rimage.data());
+    pqr_encode_host(rh, Rl.run_out, rimage.data());
+    for (size_t b = (size_t)Rl.body_bytes; b < rimage.size(); b++) CHECK(rimage[b] == 0);
+    std::vector<uint8_t> own(Rl.body_bytes, 0);
+    for (const PqwLayout::Piece& p : Rl.pieces) for (size_t b = 0; b < p.len; b++) { CHECK(p.off + b < Rl.body_bytes && own[p.off + b] == 0); own[p.off + b] = 1; }
+    for (size_t k = 0; k < n_cols; k++) {
+      for (int pass = 0; pass < 2; pass++) {
+        const bool levels = pass == 1;
+        const int slot = levels ? rc[k].run_levels : rc[k].run_values;
+        if (slot < 0) continue;
+        CHECK(levels ? (run_flags[k] & 2) != 0 && rc[k].optional : (run_flags[k] & 1) != 0 && cols[k].kind == ColKind::DICT);
+        const uint32_t w = levels ? 1 : rc[k].width;
+        for (int64_t p = 0; p < g.n_pages; p++) {
+          const size_t at = (size_t)slot * (size_t)g.n_pages + (size_t)p;
+          const FdbPqwPageStat st = stats[k * (size_t)g.n_pages + (size_t)p];
+          const int64_t first = fdb_pqw_page_first(g, p), end = fdb_pqw_page_end(g, p);
+          const bool active = fdb_pqr_active(levels, st.count, (uint32_t)(end - first), st.mn, st.mx);
+          CHECK(active == (Rl.run_out[at] != FDB_PQW_NONE) && active == (rh.page_bytes[at] != 0));
+          if (!active) continue;
+          std::vector<uint32_t> want;
+          for (int64_t r = first; r < end; r++) {
+            if (levels) want.push_back(cols[k].valid(r) ? 1u : 0u);
+            else if (cols[k].valid(r)) want.push_back(cols[k].idx[(size_t)r]);
+          }
+          const uint64_t off = Rl.run_out[at], bytes = rh.page_bytes[at];
+          size_t packed = 1;  // the one bit-packed run: its header, groups × w bytes
+          for (uint64_t v = ((uint64_t)fdb_pqw_groups((uint32_t)want.size()) << 1) | 1; v >= 0x80; v >>= 7) packed++;
+          packed += (size_t)fdb_pqw_packed_bytes((uint32_t)want.size(), w);
+          CHECK(bytes <= packed && bytes >= 2);
+          for (uint64_t b = 0; b < bytes; b++) { CHECK(off + b < Rl.body_bytes && own[off + b] == 0); own[off + b] = 5; }
+          const std::vector<uint8_t> exact(rimage.begin() + (size_t)off, rimage.begin() + (size_t)(off + bytes));  // (sized exactly: a reader that runs past the stream is caught)
+          check_hybrid(exact.data(), exact.size(), w, want);
+        }
+      }
+    }
+  }
   // the same record with a codec per column at random (three rounds in four): what fdb_selftest_parquet_write_compressed does, step by step
   std::vector<int8_t> codecs;
   for (size_t k = 0; k < n_cols; k++) codecs.push_back((int8_t)(rnd(seed) & 1));
@@ -597,6 +681,12 @@ static void refusals() {
   CHECK(bloom_code(fdb_parquet_bloom_options{&two, 1, 0}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{&minus, 1, 0}) == FDB_ERR_INVALID);
   CHECK(bloom_code(fdb_parquet_bloom_options{both, 2, 0}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{nullptr, 1, 0}) == FDB_ERR_INVALID);
   CHECK(bloom_code(fdb_parquet_bloom_options{&delta, 1, 65}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{&none, 1, -1}) == FDB_ERR_INVALID);
+  const auto run_code = [&](const fdb_parquet_run_options& o) { try { std::vector<PqwColumn> c = pqw_columns(in, 8, &plain_opt, &pr); pqr_plan(&o, &c); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const int8_t four = 4;
+  CHECK(run_code(fdb_parquet_run_options{&two, 1, 0}) == FDB_OK && run_code(fdb_parquet_run_options{&none, 1, 0}) == FDB_OK && run_code(fdb_parquet_run_options{nullptr, 0, 0}) == FDB_OK);
+  CHECK(run_code(fdb_parquet_run_options{&delta, 1, 0}) == FDB_ERR_UNSUPPORTED && run_code(fdb_parquet_run_options{&bad, 1, 0}) == FDB_ERR_UNSUPPORTED);  // bit 0 on an int64 column
+  CHECK(run_code(fdb_parquet_run_options{&four, 1, 0}) == FDB_ERR_INVALID && run_code(fdb_parquet_run_options{&minus, 1, 0}) == FDB_ERR_INVALID);
+  CHECK(run_code(fdb_parquet_run_options{both, 2, 0}) == FDB_ERR_INVALID && run_code(fdb_parquet_run_options{nullptr, 1, 0}) == FDB_ERR_INVALID);
   in[0].kind = ColKind::F64;
   CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED && bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_OK);
   in[0].kind = ColKind::BOOL;
@@ -614,6 +704,7 @@ int main() {
   for (int round = 0; round < 400; round++) one_record(&seed, round);
   snappy_bodies(&seed);
   refusals();
+  CHECK(g_streams > 100 && g_rle_inside > 20);  // the seeded records do hold stretches
   std::printf("asan parquet write ok\n");
   return 0;
 }

@@ -31,9 +31,17 @@ With --bloom the record is written uncompressed and PLAIN with bloom filters on 
 phases bloom_insert_ms, the insert pass of fdb_pqbloom.hip timed apart (entry hashes uploaded, bitsets zeroed, kernel, its wait), and
 bloom_copy_ms, the bitsets' device→host copies — with bloom_bytes, what the filters add to the file, and the call without filters on the
 same record in the same process, in front of it, goes into the line as with --delta.
+With --runs the record is first SORTED by its label columns and the timestamp with the project's own sort (ResidentBatch.sort) — what a
+compacted part is — and written uncompressed with runs=True (fdb_batch_to_parquet_runs): the dictionary indices and definition levels of
+every column cut into RLE and bit-packed runs. The line's own figures are that call's — among the phases run_survey_ms (the compaction
+of the indices by rank, the run survey and the wait for its table) and run_encode_ms — and the call without runs on the same sorted
+record in the same process goes into the line as with --delta, with plain_floor_ms, the bare copy of ITS file's bytes, beside floor_ms.
+The UNSORTED record, whose columns have no stretches and for which the run survey is pure cost, is written both ways as well:
+unsorted_file_bytes / unsorted_to_parquet_ms / unsorted_run_survey_ms / unsorted_run_encode_ms against unsorted_plain_file_bytes /
+unsorted_plain_to_parquet_ms and its _min_ms / _max_ms.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats | --bloom] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats | --bloom | --runs] [--out FILE]
 """
 import argparse
 import io
@@ -61,6 +69,7 @@ SNAPPY_PHASES = ["compress", "scan", "final layout", "gather"]
 STATS_PHASES = ["stats", "wait"]
 BLOOM_PHASES = ["bloom insert", "bloom copy"]
 BLOOM_COLUMNS = ["timestamp", "labels.l4"]
+RUN_PHASES = ["run survey", "run encode"]
 
 
 def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
@@ -88,7 +97,7 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None):
+def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None, runs=None):
     """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
     os.environ["FDB_PROFILE"] = "1"
     sys.stderr.flush()
@@ -97,7 +106,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -105,7 +114,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES + BLOOM_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = statistics.median(us) / 1e3 if us else None
     return out
@@ -122,18 +131,23 @@ def main():
     ap.add_argument("--snappy", action="store_true", help="write every column SNAPPY and `timestamp` DELTA + SNAPPY; the uncompressed PLAIN call goes into the same line")
     ap.add_argument("--stats", action="store_true", help="write statistics and the page index (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--bloom", action="store_true", help="write bloom filters on `timestamp` and `labels.l4` (uncompressed, PLAIN); the call without them goes into the same line")
+    ap.add_argument("--runs", action="store_true", help="sort the record by its label columns and write it with runs=True (uncompressed); the call without runs, and both calls on the unsorted record, go into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert args.delta + args.snappy + args.stats + args.bloom <= 1, "--delta, --snappy, --stats or --bloom"
+    assert args.delta + args.snappy + args.stats + args.bloom + args.runs <= 1, "--delta, --snappy, --stats, --bloom or --runs"
     record = make_record(args.rows)
     rb = pp.ResidentBatch(record)
     del record
+    unsorted = None
+    if args.runs:
+        unsorted, rb = rb, rb.sort([("labels.l%d" % k,) for k in range(len(LABELS))] + [("timestamp",)])
     try:
         encodings = {"timestamp": "delta"} if args.delta or args.snappy else None
         compression = "snappy" if args.snappy else None
         stats = "page" if args.stats else None
         bloom = BLOOM_COLUMNS if args.bloom else None
-        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom)
+        runs = True if args.runs else None
+        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs)
         file_bytes = len(data)
         md = pq.ParquetFile(io.BytesIO(data)).metadata
         assert md.num_rows == args.rows and md.num_row_groups == 1
@@ -144,6 +158,8 @@ def main():
             column_bytes = {md.row_group(0).column(j).path_in_schema: [md.row_group(0).column(j).total_compressed_size, md.row_group(0).column(j).total_uncompressed_size] for j in range(md.num_columns)}
         if args.stats:
             assert all(md.row_group(0).column(j).has_column_index and md.row_group(0).column(j).has_offset_index and md.row_group(0).column(j).statistics.has_min_max for j in range(md.num_columns))
+        if args.runs:
+            column_bytes = {md.row_group(0).column(j).path_in_schema: md.row_group(0).column(j).total_compressed_size for j in range(md.num_columns)}
         if args.bloom:
             filters = {md.row_group(0).column(j).path_in_schema: md.row_group(0).column(j).to_dict().get("bloom_filter_length") for j in range(md.num_columns)}
             assert all((filters[n] is not None) == (n in BLOOM_COLUMNS) for n in filters), filters
@@ -160,9 +176,15 @@ def main():
         bloom_on = (ctypes.c_int8 * n_columns)(*[1 if n in BLOOM_COLUMNS else 0 for n in names])
         bloom_opts = pp.ParquetBloomOptions(ctypes.cast(bloom_on, ctypes.c_void_p), n_columns, 0)
 
-        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats, filtered=args.bloom):
+        run_opts, _keep_runs = pp._parquet_run_options(True, names, [n.startswith("labels.") for n in names])
+
+        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats, filtered=args.bloom, run_encoded=args.runs, handle=None):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
-            if filtered:
+            if run_encoded:
+                rc = pp.lib().fdb_batch_to_parquet_runs(handle or rb.handle, ctypes.byref(opts), None, 0, None, 0, None, None, ctypes.byref(run_opts), ctypes.byref(out), ctypes.byref(n))
+            elif handle is not None:
+                rc = pp.lib().fdb_batch_to_parquet(handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+            elif filtered:
                 rc = pp.lib().fdb_batch_to_parquet_filtered(rb.handle, ctypes.byref(opts), None, 0, None, 0, None, ctypes.byref(bloom_opts), ctypes.byref(out), ctypes.byref(n))
             elif indexed:
                 rc = pp.lib().fdb_batch_to_parquet_indexed(rb.handle, ctypes.byref(opts), None, 0, None, 0, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
@@ -176,15 +198,24 @@ def main():
             assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
         plain = {}
-        if args.delta or args.snappy or args.stats or args.bloom:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+        if args.delta or args.snappy or args.stats or args.bloom or args.runs:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
             plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
-            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False, False), args.reps, args.warmup)
+            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False, False, False), args.reps, args.warmup)
             ph = profiled_phases(rb, args.page_rows, args.reps)
             plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
             plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
-        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom), args.reps, 1)
-        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats, bloom)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats, bloom, runs)
+        if args.runs:  # the record as it was before the sort: no stretches, the run passes are pure cost
+            u_bytes, u_plain_bytes = len(unsorted.to_parquet(page_rows=args.page_rows, runs=True)), len(unsorted.to_parquet(page_rows=args.page_rows))
+            u_plain_ms, u_plain_all = median_ms(lambda: c_call(False, u_plain_bytes, False, False, False, False, unsorted.handle), args.reps, args.warmup)
+            u_ms, u_all = median_ms(lambda: c_call(False, u_bytes, False, False, False, True, unsorted.handle), args.reps, args.warmup)
+            u_phases = profiled_phases(unsorted, args.page_rows, args.reps, runs=True)
+            plain.update({"unsorted_file_bytes": u_bytes, "unsorted_plain_file_bytes": u_plain_bytes, "unsorted_to_parquet_ms": u_ms, "unsorted_to_parquet_min_ms": min(u_all),
+                          "unsorted_to_parquet_max_ms": max(u_all), "unsorted_plain_to_parquet_ms": u_plain_ms, "unsorted_plain_to_parquet_min_ms": min(u_plain_all),
+                          "unsorted_plain_to_parquet_max_ms": max(u_plain_all), "unsorted_run_survey_ms": u_phases["run survey"], "unsorted_run_encode_ms": u_phases["run encode"],
+                          "unsorted_survey_ms": u_phases["survey"], "unsorted_encode_ms": u_phases["encode"], "unsorted_copy_ms": u_phases["copy"]})
 
         def bare_copy_ms(n_bytes):
             dev = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
@@ -195,7 +226,7 @@ def main():
                 torch.cuda.synchronize()
             return median_ms(bare_copy, args.reps, args.warmup)[0]
         floor_ms = bare_copy_ms(file_bytes)
-        if args.snappy:
+        if args.snappy or args.runs:
             plain["plain_floor_ms"] = bare_copy_ms(plain["plain_file_bytes"])
 
         label_names = ["labels.l%d" % k for k in range(len(LABELS))]
@@ -212,6 +243,8 @@ def main():
         arrow_write_ms, _ = median_ms(arrow_write, args.baseline_reps, 1)
     finally:
         rb.close()
+        if unsorted is not None:
+            unsorted.close()
     r3 = lambda v: None if v is None else round(v, 3)  # noqa: E731
     line = {"tool": "parquet_write_bench", "rows": args.rows, "page_rows": args.page_rows or 65536, "columns": 2 + len(LABELS), "file_bytes": file_bytes,
             "to_parquet_ms": r3(to_parquet_ms), "to_parquet_min_ms": r3(min(to_parquet_all)), "python_ms": r3(python_ms), "to_parquet_gbs": round(file_bytes / (to_parquet_ms * 1e-3) / 1e9, 2),
@@ -232,7 +265,10 @@ def main():
     if args.bloom:
         line.update({"bloom": BLOOM_COLUMNS, "bloom_bytes": file_bytes - plain["plain_file_bytes"], "to_parquet_max_ms": r3(max(to_parquet_all)), "bloom_insert_ms": r3(phases["bloom insert"]),
                      "bloom_copy_ms": r3(phases["bloom copy"])})
-    if args.delta or args.snappy or args.stats or args.bloom:
+    if args.runs:
+        line.update({"runs": "all", "sorted_by": ["labels.l%d" % k for k in range(len(LABELS))] + ["timestamp"], "to_parquet_max_ms": r3(max(to_parquet_all)),
+                     "run_survey_ms": r3(phases["run survey"]), "run_encode_ms": r3(phases["run encode"]), "column_bytes": column_bytes})
+    if args.delta or args.snappy or args.stats or args.bloom or args.runs:
         line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
