@@ -705,125 +705,84 @@ int fdb_batch_from_parquet(const fdb_parquet_chunk* chunks, int32_t n_chunks, in
   });
 }
 
-int fdb_batch_to_parquet(const fdb_batch* batch, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes) {
+// The Parquet writer's twelve entry points: each fills as much of a PqwSpec as it has arguments for and goes through one of these two.
+static int write_resident(const fdb_batch* batch, const fdb::PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes) {
   return guard(nullptr, [&] {
     if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     *bytes = nullptr; *n_bytes = 0;
-    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes);
+    fdb::batch_to_parquet(*batch->b, spec, bytes, n_bytes);
   });
 }
 
-int fdb_batch_to_parquet_encoded(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes) {
+static int write_selftest(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb::PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes) {
   return guard(nullptr, [&] {
-    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
+    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
     *bytes = nullptr; *n_bytes = 0;
-    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings);
+    fdb::HostRecordView view;
+    fdb::view_record(batch, schema, &view);
+    fdb::selftest_parquet_write(view, spec, bytes, n_bytes);
   });
+}
+
+int fdb_batch_to_parquet(const fdb_batch* batch, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes) {
+  return write_resident(batch, fdb::PqwSpec{options}, bytes, n_bytes);
+}
+
+int fdb_batch_to_parquet_encoded(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, uint8_t** bytes, int64_t* n_bytes) {
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings}, bytes, n_bytes);
 }
 
 void fdb_bytes_free(uint8_t* bytes) { fdb::pqw_free_bytes(bytes); }
 
 int fdb_selftest_parquet_write(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::HostRecordView view;
-    fdb::view_record(batch, schema, &view);
-    fdb::selftest_parquet_write(view, options, bytes, n_bytes);
-  });
+  return write_selftest(batch, schema, fdb::PqwSpec{options}, bytes, n_bytes);
 }
 
 int fdb_selftest_parquet_write_encoded(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
                                        uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::HostRecordView view;
-    fdb::view_record(batch, schema, &view);
-    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings);
-  });
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings}, bytes, n_bytes);
 }
 
 int fdb_batch_to_parquet_compressed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
                                     uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs);
-  });
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs}, bytes, n_bytes);
 }
 
 int fdb_selftest_parquet_write_compressed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
                                           const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::HostRecordView view;
-    fdb::view_record(batch, schema, &view);
-    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs);
-  });
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs}, bytes, n_bytes);
 }
 
 int fdb_batch_to_parquet_indexed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
                                  const fdb_parquet_index_options* index, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index);
-  });
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index}, bytes, n_bytes);
 }
 
 int fdb_selftest_parquet_write_indexed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
                                        const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::HostRecordView view;
-    fdb::view_record(batch, schema, &view);
-    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index);
-  });
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index}, bytes, n_bytes);
 }
 
 int fdb_batch_to_parquet_filtered(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
                                   const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom);
-  });
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom}, bytes, n_bytes);
 }
 
 int fdb_selftest_parquet_write_filtered(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
                                         const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, uint8_t** bytes,
                                         int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::HostRecordView view;
-    fdb::view_record(batch, schema, &view);
-    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom);
-  });
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom}, bytes, n_bytes);
 }
 
 int fdb_batch_to_parquet_runs(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
                               const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, const fdb_parquet_run_options* runs, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::batch_to_parquet(*batch->b, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom, runs);
-  });
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs}, bytes, n_bytes);
 }
 
 int fdb_selftest_parquet_write_runs(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
                                     const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
                                     const fdb_parquet_run_options* runs, uint8_t** bytes, int64_t* n_bytes) {
-  return guard(nullptr, [&] {
-    if (batch == nullptr || schema == nullptr || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
-    *bytes = nullptr; *n_bytes = 0;
-    fdb::HostRecordView view;
-    fdb::view_record(batch, schema, &view);
-    fdb::selftest_parquet_write(view, options, bytes, n_bytes, encodings, n_encodings, codecs, n_codecs, index, bloom, runs);
-  });
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs}, bytes, n_bytes);
 }
 
 int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_groups, int device, fdb_batch** out) {

@@ -1,68 +1,50 @@
-// fdb_pqwrite.cpp — a resident record as one Parquet file (fdb_batch_to_parquet), the encoders running on the device.
+// fdb_pqwrite.cpp — a resident record as one Parquet file (fdb_batch_to_parquet and its wider entry points), encoded on the device.
 //
 // ≙ Table.writeRecordsToParquet → pqarrow.RecordsToFile → recordToRows (table.go:1436-1459, pqarrow/parquet.go:85-139, :375-400): the
 // reference builds one parquet.Value per cell on the CPU. Here the host decides a layout and writes what is small — page headers, run
-// headers, dictionary pages, the footer (a thrift compact writer of this file's own) — and the device writes every payload:
-//   1. survey (pqw_survey_kernel): per (column, page) the non-NULL rows and, of index columns, the smallest and largest index; per tile
-//      the rank of its first value. Only the per-page table comes back.
-//   2. layout (host): with it every page's size is known, so every payload's final file offset is.
-//   3. encode (pqw_encode_kernel): every payload straight to that offset in ONE image of the file body, holes where the host's bytes go.
-//   4. one device→host copy of the image into the returned buffer; the host fills the holes and appends the footer.
-// fdb_selftest_parquet_write runs the same layout and tail over a host record, the two kernels replaced by a host walk of the same
-// arithmetic (fdb_pqwrite.h) — byte-identical files, no GPU. Compiled with FDB_PQWRITE_HOST_ONLY the device half is left out
-// (tools/asan_parquet_write.sh).
+// headers, dictionary pages, the page index, the footer (a thrift compact writer of this file's own) — and the device writes every
+// payload. Every entry point fills a PqwSpec with the arguments it has (null / 0: not asked) and runs ONE pipeline; a pass in
+// [brackets] runs only when asked for, and without it launches, allocations and copies are those of the narrower call.
+//   plan     pqw_plan: options and columns checked, every refusal made — in the parameters' order: write options and columns, index,
+//            bloom, runs — before anything is launched; the columns' modes and ranks (statistics) and the entry hashes of the filtered
+//            index columns (entry_hashes, fdb_sortplan.h) prepared. A record without rows or columns ends here, on the host.
+//   survey   pqw_survey_kernel: per (column, page) the non-NULL rows and, of index columns, the smallest and largest index; per tile
+//            the rank of its first value. Only the per-page table comes back. Behind it, their tables back in the SAME wait:
+//            [min / max] statistics and the page index (rules: include/frostdb_amd.h, keys: fdb_pqstats.h): fdb_pqstats.hip folds an
+//                        order-preserving key of every value that counts into a (column, page) table;
+//            [DELTA]     an I64 / U64 column written DELTA_BINARY_PACKED (blocks of 128, 4 miniblocks; rule: fdb_pqdelta.h): its page
+//                        sizes depend on the values, so fdb_pqdelta.hip compacts the columns with a bitmap, surveys blocks, walks pages;
+//            [runs]      RLE runs INSIDE a page's dictionary indices and definition levels (rule: fdb_pqruns.h), what a record sorted by
+//                        its label columns asks for: a chosen stream that would be ONE bit-packed run is cut into RLE and bit-packed
+//                        runs, never longer; fdb_pqruns.hip compacts the indices of the columns with a bitmap and surveys the runs.
+//   layout   pqw_layout (host): with these tables every page's size is known, so every payload's file offset is; every DELTA and run
+//            size is held to its rule's bounds first. The survey's table sizes the bloom filters (pqb_size). Pages are folded into
+//            chunk bounds, keys mapped back (a rank to an entry), the zero rule, the cut of BYTE_ARRAY bounds, the boundary order, the
+//            thrift of Statistics, ColumnIndex, OffsetIndex, column_orders and sorting_columns.
+//   encode   [bloom] first, on the same stream: a split-block filter per chosen column (rule: fdb_pqbloom.h), inserted by fdb_pqbloom.hip
+//            into ONE zeroed table of bitsets from the call's arena, each 32-byte aligned there (the atomics want that; a file offset
+//            is arbitrary, so the bitsets are not part of the image). Then pqw_encode_kernel: every payload straight to its offset in
+//            ONE image of the file body, holes where the host's bytes go. [DELTA]: the DELTA encoder writes the pages' value bytes, the
+//            encode pass such a column's levels only. [runs]: the run encoder writes the runs, headers and all (PqwLayout::run_out; the
+//            host's `pre` / `vpre` shrink to the levels' length and the width byte); the encode pass leaves such a stream alone.
+//   [SNAPPY] a column written SNAPPY (rule: fdb_pqsnappy.h): the image so far is a STAGING image in HBM, laid out as the uncompressed
+//            file. The host's few bytes inside the bodies to be compressed are placed (a body has to be whole), every fragment is
+//            compressed into its slot of scratch, the sizes are summed per page and only those come back: the second wait. The host
+//            lays the file out again (dictionary pages it compresses itself) and ONE gather launch moves the fragments' elements and
+//            the chunks of the uncompressed columns into the final image. Device memory: about 3 × the file body, the call's, freed
+//            on every path. The page index and the filters are the FINAL layout's; filters are never compressed.
+//   deliver  the bitsets, one copy per filter straight to its offset in the returned bytes, then one device→host copy of the image
+//            into the returned (pinned) buffer, in one wait; the host fills the holes, appends page index (PqwLayout::tail) and footer.
+// fdb_selftest_parquet_write runs the same plan, layout and tail over a host record, every kernel replaced by a host walk of the same
+// arithmetic (fdb_pqwrite.h, the *_host functions) — byte-identical files, no GPU. FDB_PQWRITE_HOST_ONLY leaves the device half out.
 //
-// File: PAR1 | per column [dictionary page] data pages V1 | FileMetaData | length | PAR1. Flat schema, one row group, UNCOMPRESSED,
-// definition levels RLE (one RLE run when a page has no NULL or only NULLs, else one bit-packed run whose payload is the validity
-// bitmap's bytes), no repetition levels. I64 → INT64 PLAIN; U64 → INT64 PLAIN, Int(64, unsigned) (writeUint64, parquet.go:154-165);
-// F64 → DOUBLE PLAIN; BOOL → BOOLEAN PLAIN; dictionary and plain string / binary columns → BYTE_ARRAY, a PLAIN dictionary page of the
-// interned dictionary's entries in entry order + RLE_DICTIONARY pages: the width byte, then ONE bit-packed run — or one RLE run where all
-// non-NULL indices of the page are equal, as in the leading sorting columns of an ordered record. An all-NULL column with an empty
-// dictionary has no dictionary page and PLAIN pages of zero values.
-//
-// fdb_batch_to_parquet_encoded: an I64 / U64 column may be asked to be written DELTA_BINARY_PACKED instead (blocks of 128, 4 miniblocks; the
-// rule is spelled out in fdb_pqdelta.h). Its pages' sizes depend on the values, so between survey and layout the DELTA passes of
-// fdb_pqdelta.hip run — compaction of the columns with a bitmap, block survey, page walk — and the page sizes come back with the survey's
-// table, in the same wait; after the layout the DELTA encoder writes the pages' value bytes into the same image, beside the encode pass,
-// which for such a column writes the definition levels only. The host walk has its counterparts (pqd_survey_host / pqd_encode_host).
-//
-// fdb_batch_to_parquet_compressed: a column may be asked to be SNAPPY as well (the rule is spelled out in fdb_pqsnappy.h). Steps 1 – 3 are
-// then what they were, but the image they fill is a STAGING image in HBM, laid out as the uncompressed file; after them
-//   4. the host's few bytes inside the bodies of the pages to be compressed are uploaded and placed (a body has to be whole),
-//   5. every fragment of every such body is compressed into its slot of scratch, the sizes are summed per page, and only those come back,
-//   6. the host lays the file out again (pqw_layout with the sizes; dictionary pages it compresses itself), and ONE gather launch moves
-//      the fragments' elements and the chunks of the uncompressed columns into the final image,
-//   7. which is what is copied out; headers, block preambles, dictionary pages and the footer are the host's, as before.
-// Device memory: staging + scratch + final image, about 3 × the file body, all of it the call's and freed on every path. Without a
-// compressed column nothing of this runs: the path, its launches, allocations and copies are those of fdb_batch_to_parquet_encoded.
-//
-// fdb_batch_to_parquet_indexed: min / max statistics, the page index and sorting_columns, when asked for (the rules are spelled out in
-// include/frostdb_amd.h, the keys in fdb_pqstats.h). After the survey — before the DELTA passes — the min / max pass of fdb_pqstats.hip
-// folds an order-preserving key of every value that counts into a (column, page) table, which comes back with the survey's table in the
-// same wait. The rest is the host's, inside pqw_layout: pages folded into chunk bounds, keys mapped back (a rank to an entry), the zero
-// rule, the cut of BYTE_ARRAY bounds, the boundary order, and the thrift of Statistics, ColumnIndex, OffsetIndex, column_orders and
-// sorting_columns. The index bytes follow the body in the file (PqwLayout::tail, written by pqw_finish); the image stays the body. For a
-// compressed file the index is the final layout's. Without index options nothing of this runs.
-//
-// fdb_batch_to_parquet_filtered: a split-block bloom filter per chosen column (the rule is spelled out in fdb_pqbloom.h and in
-// include/frostdb_amd.h). The host hashes the entries of the chosen index columns once (entry_hashes, fdb_sortplan.h). The survey's
-// table gives every filter its size (pqb_size), so the layout can place them — after the last chunk's pages, in column order, each a
-// header (a host piece) and then its bitset (PqwLayout::blooms), in front of the page index — and the insert pass of fdb_pqbloom.hip
-// runs then, on the call's stream beside the encode pass, into ONE zeroed table of bitsets from the call's arena, each 32-byte aligned
-// there (the atomics want that; a file offset is arbitrary, so the bitsets are not part of the image). They come back after the image,
-// one copy per filter straight to its offset in the returned bytes, in the wait of the image's copy: no wait is added. For a compressed
-// file the offsets are the final layout's; filters are never compressed. The host walk is pqb_insert_host. Without a chosen column
-// nothing of this runs.
-//
-// fdb_batch_to_parquet_runs: RLE runs INSIDE a page's dictionary indices and definition levels, on the columns chosen (the rule is
-// spelled out in fdb_pqruns.h and in include/frostdb_amd.h) — what a record sorted by its label columns asks for. A chosen stream of a
-// page that would be ONE bit-packed run is cut into RLE and bit-packed runs instead, never longer. Its size depends on the data, so the
-// run passes of fdb_pqruns.hip sit where DELTA's do: after the survey the compaction of the indices of the chosen columns with a bitmap
-// (scratch of the call's arena) and the run survey, whose table of sizes comes back with the survey's in the same wait; pqw_layout holds
-// every size to the rule's bounds and places the stream (PqwLayout::run_out; the run headers are the device's, so the host's `pre` / `vpre`
-// shrink to the levels' length and the width byte); after the layout the run encoder writes the runs into the same image, beside the
-// encode pass, which leaves such a stream alone. A SNAPPY column's pages go through the staging image as ever. The host walk is
-// pqr_survey_host / pqr_encode_host. Without a chosen stream nothing of this runs.
+// File: PAR1 | per column [dictionary page] data pages V1 | [bloom filters] | [page index] | FileMetaData | length | PAR1. Flat schema,
+// one row group, definition levels RLE (one RLE run when a page has no NULL or only NULLs, else one bit-packed run whose payload is the
+// validity bitmap's bytes), no repetition levels. I64 → INT64 PLAIN; U64 → INT64 PLAIN, Int(64, unsigned) (writeUint64,
+// parquet.go:154-165); F64 → DOUBLE PLAIN; BOOL → BOOLEAN PLAIN; dictionary and plain string / binary columns → BYTE_ARRAY, a PLAIN
+// dictionary page of the interned dictionary's entries in entry order + RLE_DICTIONARY pages: the width byte, then ONE bit-packed run —
+// or one RLE run where all non-NULL indices of the page are equal, as in the leading sorting columns of an ordered record. An all-NULL
+// column with an empty dictionary has no dictionary page and PLAIN pages of zero values.
 #include "fdb_pqwrite_host.h"
 #include "fdb_sortplan.h"
 
@@ -355,9 +337,9 @@ void pqw_free_bytes(uint8_t* bytes) {
   std::free(p);
 }
 
-// Everything that can refuse the record, before anything is launched.
-std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows, const int8_t* encodings,
-                                   int32_t n_encodings, const int8_t* codecs, int32_t n_codecs) {
+std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec, int32_t* page_rows) {
+  const fdb_parquet_write_options* opt = spec.options;
+  const int8_t *encodings = spec.encodings, *codecs = spec.codecs; const int32_t n_encodings = spec.n_encodings, n_codecs = spec.n_codecs;
   int64_t pr = opt != nullptr ? opt->page_rows : 0;
   if (pr == 0) pr = 65536;
   if (pr < 64 || pr > (1 << 24) || pr % 64 != 0)
@@ -569,7 +551,8 @@ PqxIndex pqx_plan(const fdb_parquet_index_options* index, size_t n_cols) {
   return x;
 }
 
-void pqx_prepare(const std::vector<PqwColumn>& cols, PqxIndex* x) {
+// modes, ranks and entry_of_rank of the columns (statistics > 0).
+static void pqx_prepare(const std::vector<PqwColumn>& cols, PqxIndex* x) {
   x->modes.assign(cols.size(), FDB_PQX_U64);
   x->ranks.assign(cols.size(), std::vector<uint32_t>());
   x->entry_of_rank.assign(cols.size(), std::vector<uint32_t>());
@@ -643,11 +626,25 @@ PqbPlan pqb_plan(const fdb_parquet_bloom_options* bloom, const std::vector<PqwCo
   return b;
 }
 
-void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b) {
+static void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b) {
   b->hashes.assign(cols.size(), std::vector<uint64_t>());
   for (size_t k = 0; k < cols.size() && b->any(); k++)
     if (b->on[k] != 0 && cols[k].pq_kind == FDB_PQW_INDEX && cols[k].dict != nullptr)
       b->hashes[k] = entry_hashes(*cols[k].dict, [](const unsigned char* p, size_t n) { return fdb_pqb_hash(p, n); });
+}
+
+PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec) {
+  PqwPlan P;
+  int32_t page_rows = 0;
+  P.cols = pqw_columns(in, rows, spec, &page_rows);
+  P.x = pqx_plan(spec.index, P.cols.size());
+  P.bloom = pqb_plan(spec.bloom, P.cols);
+  P.n_runs = pqr_plan(spec.runs, &P.cols);
+  if (P.x.statistics > 0) pqx_prepare(P.cols, &P.x);
+  if (P.bloom.any()) pqb_prepare(P.cols, &P.bloom);
+  P.g = pqw_geometry(rows, page_rows, P.cols.size());
+  P.n_delta = pqw_delta_columns(P.cols); P.n_compressed = pqw_compressed_columns(P.cols);
+  return P;
 }
 
 void pqb_size(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqbPlan* b) {
@@ -697,29 +694,36 @@ void pqb_insert_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
   }
 }
 
-std::string pqs_block_host(const unsigned char* body, size_t n) {
-  std::string block = varint_bytes(n);
+// The elements of every fragment of a body, by the host walk of fdb_pqsnappy.h: a Snappy block without its preamble.
+static std::string pqs_elements_host(const unsigned char* body, size_t n) {
+  std::string elements;
   std::vector<uint32_t> table(FDB_PQS_TABLE);
-  std::vector<unsigned char> out(fdb_pqs_bound(FDB_PQS_FRAGMENT));
+  std::vector<unsigned char> out(fdb_pqs_slot_bytes());
   for (size_t at = 0; at < n; at += FDB_PQS_FRAGMENT) {
     const uint32_t len = (uint32_t)std::min<size_t>(FDB_PQS_FRAGMENT, n - at);
-    block.append((const char*)out.data(), fdb_pqs_compress_fragment_host(body + at, len, table.data(), out.data()));
+    elements.append((const char*)out.data(), fdb_pqs_compress_fragment_host(body + at, len, table.data(), out.data()));
   }
-  return block;
+  return elements;
 }
+std::string pqs_block_host(const unsigned char* body, size_t n) { return varint_bytes(n) + pqs_elements_host(body, n); }
 
-PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes,
-                     const std::vector<uint32_t>* page_elements, const PqxIndex* x, const PqbPlan* bloom, const std::vector<uint32_t>* run_bytes) {
-  if (x != nullptr && !x->any()) x = nullptr;
-  if (bloom != nullptr && !bloom->any()) bloom = nullptr;
+PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) {
+  static const std::vector<uint32_t> no_table;
+  const std::vector<PqwColumn>& cols = plan.cols; const FdbPqwGeom& g = plan.g; const std::vector<FdbPqwPageStat>& stats = sizes.stats;
+  const std::vector<uint32_t>& delta_bytes = sizes.delta_bytes != nullptr ? *sizes.delta_bytes : no_table;
+  const std::vector<uint32_t>*page_elements = sizes.page_elements, *run_bytes = sizes.run_bytes;
+  const bool final_form = page_elements != nullptr;  // else: every page as it is before compression — the file of a record without codecs, the staging image of one with
+  const bool own = final_form || plan.n_compressed == 0;  // the file's own layout: a compressed file's index and filters belong to the final one
+  const PqxIndex* x = own && plan.x.any() ? &plan.x : nullptr;
+  const PqbPlan* bloom = own && plan.bloom.any() ? &plan.bloom : nullptr;
   if (bloom != nullptr && bloom->bytes.size() != cols.size()) throw Error(FDB_ERR_STATE, "parquet write: the bloom filter sizes do not match the record");
   const bool bounds = x != nullptr && x->statistics > 0;
   if (bounds && (x->table.size() != 2 * stats.size() || x->modes.size() != cols.size())) throw Error(FDB_ERR_STATE, "parquet write: the min / max table does not match the record");
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
-  if (delta_bytes.size() != pqw_delta_columns(cols) * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
-  if (page_elements != nullptr && page_elements->size() != pqw_compressed_columns(cols) * (size_t)g.n_pages)
+  if (delta_bytes.size() != plan.n_delta * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
+  if (page_elements != nullptr && page_elements->size() != plan.n_compressed * (size_t)g.n_pages)
     throw Error(FDB_ERR_STATE, "parquet write: the table of compressed page sizes does not match the record");
-  const size_t n_run_streams = pqr_streams(cols);
+  const size_t n_run_streams = plan.n_runs;
   if ((run_bytes != nullptr ? run_bytes->size() : 0) != n_run_streams * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of run-encoded sizes does not match the record");
   // The bytes of a page's stream cut into runs, held to the rule's bounds: no more than its one bit-packed run, no less than a run.
   const auto run_payload = [&](const PqwColumn& c, int slot, int64_t p, uint32_t n, uint32_t w) {
@@ -728,7 +732,6 @@ PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
       throw Error(FDB_ERR_STATE, "parquet write: the run survey sizes a stream of " + std::to_string(n) + " symbols of " + std::to_string(w) + " bits at " + std::to_string(bytes) + " bytes (" + c.name + ")");
     return (uint64_t)bytes;
   };
-  const bool final_form = page_elements != nullptr;  // else: every page as it is before compression — the file of a record without codecs, the staging image of one with
   size_t next_compressed = 0;
   PqwLayout L;
   L.chunk_off.assign(cols.size(), 0);
@@ -1054,14 +1057,13 @@ void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
   }
 }
 
-void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                            const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
-                            const fdb_parquet_run_options* runs) {
-  // the record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole words
+// ---- fdb_selftest_parquet_write: the pipeline over a host record ------------------------------------------------------------------------
+// A host record in the resident form: 8 bytes per value (a bool widened to 1 / 2), a uint32 per index, bitmaps at bit 0 in whole
+// words. `keep`: what had to be made for that, for as long as the columns are looked at.
+struct HostResident { std::vector<std::vector<uint32_t>> idx; std::vector<std::vector<int64_t>> i64; std::vector<std::vector<uint8_t>> bits; };
+static std::vector<PqwInput> resident_form(const HostRecordView& view, HostResident* keep) {
   const size_t rows = (size_t)view.rows;
-  std::vector<std::vector<uint32_t>> keep_idx(view.cols.size());
-  std::vector<std::vector<int64_t>> keep_i64(view.cols.size());
-  std::vector<std::vector<uint8_t>> keep_bits(view.cols.size());
+  keep->idx.resize(view.cols.size()); keep->i64.resize(view.cols.size()); keep->bits.resize(view.cols.size());
   std::vector<PqwInput> in;
   for (size_t k = 0; k < view.cols.size(); k++) {
     const HostColView& c = view.cols[k];
@@ -1070,370 +1072,416 @@ void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_
     if (c.kind == ColKind::I64 || c.kind == ColKind::U64 || c.kind == ColKind::F64) {
       o.values = rows > 0 ? (const unsigned char*)c.values + (size_t)c.offset * 8 : nullptr;
     } else if (c.kind == ColKind::BOOL) {
-      keep_i64[k].assign(rows + 1, 0);
+      keep->i64[k].assign(rows + 1, 0);
       const uint8_t* bits = (const uint8_t*)c.values;
-      for (size_t i = 0; i < rows; i++) keep_i64[k][i] = 1 + ((bits[(c.offset + (int64_t)i) >> 3] >> ((c.offset + (int64_t)i) & 7)) & 1);
-      o.values = keep_i64[k].data();
+      for (size_t i = 0; i < rows; i++) keep->i64[k][i] = 1 + ((bits[(c.offset + (int64_t)i) >> 3] >> ((c.offset + (int64_t)i) & 7)) & 1);
+      o.values = keep->i64[k].data();
     } else if (c.kind == ColKind::DICT) {
       o.dict = read_dictionary(c);
-      keep_idx[k].assign(rows + 1, 0);
+      keep->idx[k].assign(rows + 1, 0);
       for (size_t i = 0; i < rows; i++) {
         const size_t at = (size_t)c.offset + i;
         switch (c.index_width) {
-          case 1: keep_idx[k][i] = ((const uint8_t*)c.values)[at]; break;
-          case 2: keep_idx[k][i] = ((const uint16_t*)c.values)[at]; break;
-          case 4: keep_idx[k][i] = ((const uint32_t*)c.values)[at]; break;
-          default: keep_idx[k][i] = (uint32_t)((const uint64_t*)c.values)[at]; break;
+          case 1: keep->idx[k][i] = ((const uint8_t*)c.values)[at]; break;
+          case 2: keep->idx[k][i] = ((const uint16_t*)c.values)[at]; break;
+          case 4: keep->idx[k][i] = ((const uint32_t*)c.values)[at]; break;
+          default: keep->idx[k][i] = (uint32_t)((const uint64_t*)c.values)[at]; break;
         }
       }
-      o.values = keep_idx[k].data();
+      o.values = keep->idx[k].data();
     } else if (c.kind == ColKind::STR) {
-      o.dict = encode_plain(c, &keep_idx[k]);
-      keep_idx[k].resize(rows + 1, 0);
+      o.dict = encode_plain(c, &keep->idx[k]);
+      keep->idx[k].resize(rows + 1, 0);
       o.kind = ColKind::DICT;
-      o.values = keep_idx[k].data();
+      o.values = keep->idx[k].data();
     }
     if (c.null_count > 0 && c.validity != nullptr) {
-      keep_bits[k].assign((rows + 63) / 64 * 8 + 8, 0);
-      copy_bits(c.validity, c.offset, c.length, keep_bits[k].data());
-      o.validity = keep_bits[k].data();
+      keep->bits[k].assign((rows + 63) / 64 * 8 + 8, 0);
+      copy_bits(c.validity, c.offset, c.length, keep->bits[k].data());
+      o.validity = keep->bits[k].data();
     }
     in.push_back(std::move(o));
   }
-  int32_t page_rows = 0;
-  std::vector<PqwColumn> cols = pqw_columns(in, view.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
-  PqxIndex x = pqx_plan(index, cols.size());
-  PqbPlan bl = pqb_plan(bloom, cols);
-  const size_t n_runs = pqr_plan(runs, &cols);
-  const FdbPqwGeom g = pqw_geometry(view.rows, page_rows, cols.size());
-  std::vector<FdbPqwPageStat> stats;
-  std::vector<uint32_t> tile_base;
+  return in;
+}
+
+// The pipeline with every kernel replaced by its host walk, over columns in host memory — or over a record without rows or columns,
+// which gives the device nothing to do (no data page: the dictionary pages are the host's, compressed or not).
+static void pqw_write_host(PqwPlan& P, uint8_t** bytes, int64_t* n_bytes) {
+  const std::vector<PqwColumn>& cols = P.cols; const FdbPqwGeom& g = P.g;
+  // the survey passes
+  std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> tile_base;
   pqw_survey_host(cols, g, &stats, &tile_base);
-  std::vector<unsigned char> bitsets;
-  if (bl.any()) { pqb_prepare(cols, &bl); pqb_size(cols, g, stats, &bl); }
-  const auto place_bitsets = [&](const PqwLayout& at, uint8_t* file) {  // the insert pass, walked, and every bitset to its place in the file
-    if (at.blooms.empty()) return;
-    bitsets.assign((size_t)bl.table_bytes, 0);
-    pqb_insert_host(cols, g, bl, bitsets.data());
-    for (const PqwLayout::Bloom& f : at.blooms) std::memcpy(file + f.bits_off, bitsets.data() + bl.table_off[f.col], (size_t)f.bytes);
-  };
-  if (x.statistics > 0) { pqx_prepare(cols, &x); pqx_minmax_host(cols, g, &x); }
-  PqdHost delta;
+  if (P.bloom.any()) pqb_size(cols, g, stats, &P.bloom);
+  if (P.x.statistics > 0) pqx_minmax_host(cols, g, &P.x);
+  PqdHost delta; PqrHost rn;
   pqd_survey_host(cols, g, stats, tile_base, &delta);
-  PqrHost rn;
-  if (n_runs > 0) pqr_survey_host(cols, g, stats, &rn);
-  const std::vector<uint32_t>* run_bytes = n_runs > 0 ? &rn.page_bytes : nullptr;
-  const bool squeezed = pqw_compressed_columns(cols) > 0;  // then L is the staging image's layout, and the index is the final one's
-  const PqwLayout L = pqw_layout(cols, g, stats, delta.page_bytes, nullptr, squeezed ? nullptr : &x, squeezed ? nullptr : &bl, run_bytes);
+  if (P.n_runs > 0) pqr_survey_host(cols, g, stats, &rn);
+  PqwSizes sizes{stats, &delta.page_bytes, P.n_runs > 0 ? &rn.page_bytes : nullptr, nullptr};
+  // layout, and the encode passes
+  const PqwLayout L = pqw_layout(P, sizes);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(cols, g, L.out, tile_base, image.data());
   pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
-  if (n_runs > 0) pqr_encode_host(rn, L.run_out, image.data());
-  if (!squeezed) {
-    const size_t file_bytes = L.file_bytes();
-    uint8_t* file = pqw_alloc_bytes(file_bytes, false);
+  if (P.n_runs > 0) pqr_encode_host(rn, L.run_out, image.data());
+  // the file's body: the image, or — `image` being the staging image — what the compressor made of it, laid out again and gathered
+  PqwLayout F; uint8_t* file = nullptr;
+  if (P.n_compressed == 0) {
+    file = pqw_alloc_bytes(L.file_bytes(), false);
     std::memcpy(file, image.data(), (size_t)L.body_bytes);
-    place_bitsets(L, file);
-    pqw_finish(L, file);
-    *bytes = file;
-    *n_bytes = (int64_t)file_bytes;
-    return;
-  }
-  // `image` is the staging image: the bodies made whole, every page compressed fragment by fragment, the file laid out again, the
-  // elements and the uncompressed chunks moved to where it wants them — the passes of fdb_pqsnappy.hip, walked
-  for (const PqwLayout::Piece& p : L.body_pieces) std::memcpy(image.data() + p.off, L.body_blob.data() + p.pos, p.len);
-  std::vector<uint32_t> page_elements(L.pages.size(), 0), table(FDB_PQS_TABLE);
-  std::vector<std::string> elements(L.pages.size());
-  std::vector<unsigned char> slot(fdb_pqs_slot_bytes());
-  for (size_t i = 0; i < L.pages.size(); i++) {
-    for (uint64_t at = 0; at < L.pages[i].body; at += FDB_PQS_FRAGMENT) {
-      const uint32_t len = (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, L.pages[i].body - at);
-      elements[i].append((const char*)slot.data(), fdb_pqs_compress_fragment_host(image.data() + L.pages[i].off + at, len, table.data(), slot.data()));
+  } else {
+    for (const PqwLayout::Piece& p : L.body_pieces) std::memcpy(image.data() + p.off, L.body_blob.data() + p.pos, p.len);  // the bodies made whole
+    std::vector<std::string> elements;
+    std::vector<uint32_t> page_elements;
+    for (const PqwLayout::Page& pg : L.pages) {
+      elements.push_back(pqs_elements_host(image.data() + pg.off, (size_t)pg.body));
+      page_elements.push_back((uint32_t)elements.back().size());
     }
-    page_elements[i] = (uint32_t)elements[i].size();
+    sizes.page_elements = &page_elements;
+    F = pqw_layout(P, sizes);
+    file = pqw_alloc_bytes(F.file_bytes(), false);
+    for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
+    for (size_t k = 0; k < cols.size(); k++)
+      if (cols[k].codec == 0) std::memcpy(file + F.chunk_off[k], image.data() + L.chunk_off[k], (size_t)L.chunk_len[k]);
   }
-  const PqwLayout F = pqw_layout(cols, g, stats, delta.page_bytes, &page_elements, &x, &bl, run_bytes);
-  const size_t file_bytes = F.file_bytes();
-  uint8_t* file = pqw_alloc_bytes(file_bytes, false);
-  for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
-  for (size_t k = 0; k < cols.size(); k++)
-    if (cols[k].codec == 0) std::memcpy(file + F.chunk_off[k], image.data() + L.chunk_off[k], (size_t)L.chunk_len[k]);
-  place_bitsets(F, file);
-  pqw_finish(F, file);
-  *bytes = file;
-  *n_bytes = (int64_t)file_bytes;
+  const PqwLayout& at = P.n_compressed == 0 ? L : F;
+  if (!at.blooms.empty()) {  // the insert pass, and every bitset to its place in the file
+    std::vector<unsigned char> bitsets((size_t)P.bloom.table_bytes, 0);
+    pqb_insert_host(cols, g, P.bloom, bitsets.data());
+    for (const PqwLayout::Bloom& f : at.blooms) std::memcpy(file + f.bits_off, bitsets.data() + P.bloom.table_off[f.col], (size_t)f.bytes);
+  }
+  pqw_finish(at, file);
+  *bytes = file; *n_bytes = (int64_t)at.file_bytes();
+}
+
+void selftest_parquet_write(const HostRecordView& view, const PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes) {
+  HostResident keep;
+  const std::vector<PqwInput> in = resident_form(view, &keep);  // (owns the dictionaries the plan's columns point at)
+  PqwPlan P = pqw_plan(in, view.rows, spec);
+  pqw_write_host(P, bytes, n_bytes);
 }
 
 #ifndef FDB_PQWRITE_HOST_ONLY
-void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings, int32_t n_encodings,
-                      const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
-                      const fdb_parquet_run_options* runs) {
-  std::vector<PqwInput> in;
-  for (const DevColumn& c : b.cols) {
-    PqwInput o;
-    o.name = c.name; o.format = c.format; o.kind = c.kind; o.dict = c.dict; o.null_count = c.null_count; o.values = c.d_values; o.validity = c.d_validity;
-    in.push_back(std::move(o));
+// ---- fdb_batch_to_parquet: the pipeline on the device ------------------------------------------------------------------------------------
+struct PqwBytes { uint8_t* p = nullptr; ~PqwBytes() { pqw_free_bytes(p); } };  // the file until it is handed over
+struct PoolBlock {  // an image of the file body in HBM
+  int device; unsigned char* p = nullptr;
+  void alloc(size_t bytes) { p = (unsigned char*)device_pool_alloc(device, bytes); }
+  ~PoolBlock() { if (p != nullptr) device_pool_free(device, p); }
+};
+
+// One call's side of the device: the plan, its scope, stream and timer, its images (with a compressed column: staging image,
+// scratch, final image), the tables of the survey and of the optional passes (the call's arena) and the host tables its wait fills.
+struct PqwCall {
+  PqwPlan& P;
+  CallScope& cs;
+  hipStream_t stream;
+  PoolBlock &image, &scratch, &final_image;
+  PhaseTimer& pt;  // FDB_PROFILE=1: the passes timed apart (every pass is then waited for on its own)
+  const char* queued = nullptr;  // FDB_PROFILE: the pass queued last and not waited for yet — the name the next wait is marked with
+  size_t items = 0, d_items = 0, r_items = 0;  // columns, DELTA columns, run streams × pages
+  const FdbPqwCol* d_cols = nullptr; FdbPqwPageStat* d_stats = nullptr; uint32_t* d_tile_base = nullptr;
+  const FdbPqdCol* d_dcols = nullptr; FdbPqdBlock* d_blocks = nullptr; uint32_t* d_page_bytes = nullptr;
+  const FdbPqrStream* d_streams = nullptr; uint32_t* d_run_bytes = nullptr; unsigned char* d_bitsets = nullptr;
+  bool compact = false, run_compact = false;  // a DELTA column / a column whose indices are cut into runs has a bitmap
+  std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> delta_bytes, run_bytes;  // what the survey's wait fills
+  void wait() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
+  void timed(const char* what) { if (pt.on) { wait(); pt.mark(what); } }  // FDB_PROFILE: a pass waited for by itself
+  void settle() { timed(queued != nullptr ? queued : "pqwrite wait"); queued = nullptr; }  // … the pass queued last ("pqwrite wait": none was)
+  void* upload(const void* host, size_t n, const char* what) {  // (`host` outlives the next wait)
+    void* d = cs.alloc(std::max<size_t>(n, 8));
+    if (n > 0) hip_check(hipMemcpyAsync(d, host, n, hipMemcpyHostToDevice, stream), what);
+    return d;
   }
-  int32_t page_rows = 0;
-  std::vector<PqwColumn> cols = pqw_columns(in, b.rows, opt, &page_rows, encodings, n_encodings, codecs, n_codecs);
-  PqxIndex x = pqx_plan(index, cols.size());
-  const size_t n_runs = pqr_plan(runs, &cols);
-  const bool bounds = x.statistics > 0;
-  if (bounds) {
-    pqx_prepare(cols, &x);
-    for (size_t k = 0; k < cols.size(); k++)
-      if (((uintptr_t)cols[k].values & 15u) != 0)  // (the pass loads 16 bytes of values at a time)
-        throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (statistics)");
-  }
-  PqbPlan bl = pqb_plan(bloom, cols);
-  if (bl.any()) {
-    pqb_prepare(cols, &bl);
-    for (size_t k = 0; k < cols.size(); k++)
-      if (bl.on[k] != 0 && ((uintptr_t)cols[k].values & 15u) != 0)  // (the pass loads 16 bytes of values at a time)
-        throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (bloom filter)");
-  }
-  const FdbPqwGeom g = pqw_geometry(b.rows, page_rows, cols.size());
-  const size_t n_delta = pqw_delta_columns(cols), n_compressed = pqw_compressed_columns(cols);
-  struct Bytes { uint8_t* p = nullptr; ~Bytes() { pqw_free_bytes(p); } } file;
-  if (b.rows == 0 || cols.empty()) {  // nothing for the device to do (no data page: the dictionary pages are the host's, compressed or not)
-    const std::vector<uint32_t> no_pages;
-    if (bounds) x.table.assign(2 * cols.size() * (size_t)g.n_pages, 0);  // (no page: no slot)
-    const std::vector<FdbPqwPageStat> no_stats(cols.size() * (size_t)g.n_pages, FdbPqwPageStat{0, 0, 0, 0});
-    if (bl.any()) pqb_size(cols, g, no_stats, &bl);
-    const std::vector<uint32_t> no_runs(n_runs * (size_t)g.n_pages, 0);
-    const PqwLayout L = pqw_layout(cols, g, no_stats, {}, n_compressed > 0 ? &no_pages : nullptr, &x, &bl, n_runs > 0 ? &no_runs : nullptr);
-    const size_t file_bytes = L.file_bytes();
-    file.p = pqw_alloc_bytes(file_bytes, false);
-    for (const PqwLayout::Bloom& f : L.blooms) std::memset(file.p + f.bits_off, 0, (size_t)f.bytes);  // (no value: one zero block each)
-    pqw_finish(L, file.p);
-    *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
-    return;
-  }
-  PhaseTimer pt;  // FDB_PROFILE=1: the passes timed apart (the encode pass is then waited for on its own)
-  struct Image { int device; void* p = nullptr; ~Image() { if (p != nullptr) device_pool_free(device, p); } } image{b.device}, scratch{b.device}, final_image{b.device};  // (before the scope: freed after its wait; the last two: compressed columns only)
-  CallScope cs(b.device);
-  hipStream_t stream = cs.ctx->stream;
-  DrainOnUnwind drain{stream};
+};
+
+// The columns as the survey and encode kernels see them, the survey's two tables.
+static void pqw_tables(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
   std::vector<FdbPqwCol> kc(cols.size());
   for (size_t k = 0; k < cols.size(); k++) {
     std::memset(&kc[k], 0, sizeof(FdbPqwCol));
     kc[k].values = cols[k].values; kc[k].validity = cols[k].validity; kc[k].width = (int32_t)cols[k].width;
     kc[k].kind = cols[k].pq_kind == PQW_NO_VALUES ? FDB_PQW_INDEX : cols[k].pq_kind;
   }
-  const size_t items = cols.size() * (size_t)g.n_pages;
-  const FdbPqwCol* d_cols = (const FdbPqwCol*)cs.ctx->stage(kc.data(), kc.size() * sizeof(FdbPqwCol));
-  FdbPqwPageStat* d_stats = (FdbPqwPageStat*)cs.alloc(items * sizeof(FdbPqwPageStat));
-  uint32_t* d_tile_base = (uint32_t*)cs.alloc(items * (size_t)g.tiles_per_page * 4);
-  std::vector<FdbPqwPageStat> stats(items);
-  // the DELTA columns: scratch for the dense values of those with a bitmap, the block table, the page sizes — all from the call's arena
-  const size_t d_items = n_delta * (size_t)g.n_pages;
-  std::vector<uint32_t> delta_bytes(d_items);
-  const FdbPqdCol* d_dcols = nullptr;
-  FdbPqdBlock* d_blocks = nullptr;
-  uint32_t* d_page_bytes = nullptr;
-  bool compact = false;
-  if (n_delta > 0) {
-    std::vector<FdbPqdCol> dc(n_delta);
-    for (size_t k = 0; k < cols.size(); k++) {
-      if (cols[k].delta_slot < 0) continue;
-      FdbPqdCol& o = dc[(size_t)cols[k].delta_slot];
-      std::memset(&o, 0, sizeof(FdbPqdCol));
-      o.values = (const uint64_t*)cols[k].values; o.validity = cols[k].validity; o.col = (int32_t)k;
-      o.dense = cols[k].validity != nullptr ? (uint64_t*)cs.alloc(((size_t)g.rows + 1) * 8) : (uint64_t*)const_cast<void*>(cols[k].values);  // (only ever read when it is the column)
-      compact = compact || cols[k].validity != nullptr;
-    }
-    d_dcols = (const FdbPqdCol*)cs.ctx->stage(dc.data(), dc.size() * sizeof(FdbPqdCol));
-    d_blocks = (FdbPqdBlock*)cs.alloc(d_items * (size_t)fdb_pqd_blocks_per_page(g.page_rows) * sizeof(FdbPqdBlock));
-    d_page_bytes = (uint32_t*)cs.alloc(d_items * 4);
-  }
-  // the streams to be cut into runs: scratch for the dense indices of the columns with a bitmap, the table of sizes — from the call's arena
-  const size_t r_items = n_runs * (size_t)g.n_pages;
-  std::vector<uint32_t> run_bytes(r_items);
-  const FdbPqrStream* d_streams = nullptr;
-  uint32_t* d_run_bytes = nullptr;
-  bool run_compact = false;
-  if (n_runs > 0) {
-    std::vector<FdbPqrStream> rs(n_runs);
-    for (size_t k = 0; k < cols.size(); k++) {
-      const PqwColumn& c = cols[k];
-      if (c.run_values >= 0) {
-        FdbPqrStream& o = rs[(size_t)c.run_values];
-        std::memset(&o, 0, sizeof(FdbPqrStream));
-        o.values = (const uint32_t*)c.values; o.validity = c.validity; o.col = (int32_t)k; o.width = (int32_t)c.width;
-        o.dense = c.validity != nullptr ? (uint32_t*)cs.alloc(((size_t)g.rows + 8) * 4) : (uint32_t*)const_cast<void*>(c.values);  // (only ever read when it is the column)
-        run_compact = run_compact || c.validity != nullptr;
-      }
-      if (c.run_levels >= 0) {
-        FdbPqrStream& o = rs[(size_t)c.run_levels];
-        std::memset(&o, 0, sizeof(FdbPqrStream));
-        o.validity = c.validity; o.col = (int32_t)k; o.width = 1; o.levels = 1;
-      }
-    }
-    d_streams = (const FdbPqrStream*)cs.ctx->stage(rs.data(), rs.size() * sizeof(FdbPqrStream));
-    d_run_bytes = (uint32_t*)cs.alloc(r_items * 4);
-  }
-  b.note_reader(stream);
-  hip_check(fdb_launch_pqw_survey(d_cols, g, d_stats, d_tile_base, stream), "parquet write: survey launch");
-  hip_check(hipMemcpyAsync(stats.data(), d_stats, items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(page table)");
-  if (bounds) {  // the min / max pass (fdb_pqstats.hip): beside the survey, its table back in the same wait
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite survey"); }
-    std::vector<FdbPqxCol> xc(cols.size());
-    for (size_t k = 0; k < cols.size(); k++) {
-      std::memset(&xc[k], 0, sizeof(FdbPqxCol));
-      xc[k].values = cols[k].values; xc[k].validity = cols[k].validity; xc[k].mode = x.modes[k];
-      const std::vector<uint32_t>& r = x.ranks[k];
-      if (r.empty()) continue;
-      uint32_t* d_ranks = (uint32_t*)cs.alloc(r.size() * 4);
-      hip_check(hipMemcpyAsync(d_ranks, r.data(), r.size() * 4, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(dictionary ranks)");  // (`x` outlives the wait)
-      xc[k].ranks = d_ranks; xc[k].rank_len = (uint32_t)r.size();
-    }
-    const FdbPqxCol* d_xcols = (const FdbPqxCol*)cs.ctx->stage(xc.data(), xc.size() * sizeof(FdbPqxCol));
-    unsigned long long* d_table = (unsigned long long*)cs.alloc(2 * items * 8);
-    hip_check(hipMemsetAsync(d_table, 0xFF, items * 8, stream), "hipMemsetAsync(min table)");
-    hip_check(hipMemsetAsync(d_table + items, 0, items * 8, stream), "hipMemsetAsync(max table)");
-    hip_check(fdb_launch_pqx_minmax(d_xcols, g, d_table, stream), "parquet write: min / max launch");
-    x.table.assign(2 * items, 0);
-    hip_check(hipMemcpyAsync(x.table.data(), d_table, 2 * items * 8, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(min / max table)");
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite stats"); }
-  }
-  if (n_delta > 0) {
-    if (pt.on && !bounds) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite survey"); }
-    if (compact) hip_check(fdb_launch_pqd_compact(d_dcols, (int32_t)n_delta, g, d_tile_base, stream), "parquet write: DELTA compaction launch");
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta compact"); }
-    hip_check(fdb_launch_pqd_survey(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_page_bytes, stream), "parquet write: DELTA block survey launch");
-    hip_check(hipMemcpyAsync(delta_bytes.data(), d_page_bytes, d_items * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(DELTA page sizes)");
-  }
-  if (n_runs > 0) {  // the run passes (fdb_pqruns.hip): beside the survey, their table back in the same wait
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark(n_delta > 0 ? "pqwrite delta survey" : bounds ? "pqwrite wait" : "pqwrite survey"); }
-    if (run_compact) hip_check(fdb_launch_pqr_compact(d_streams, (int32_t)n_runs, g, d_tile_base, stream), "parquet write: run compaction launch");
-    hip_check(fdb_launch_pqr_survey(d_streams, (int32_t)n_runs, g, d_stats, d_run_bytes, stream), "parquet write: run survey launch");
-    hip_check(hipMemcpyAsync(run_bytes.data(), d_run_bytes, r_items * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(run-encoded sizes)");
-  }
-  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  pt.mark(n_runs > 0 ? "pqwrite run survey" : n_delta > 0 ? "pqwrite delta survey" : bounds && pt.on ? "pqwrite wait" : "pqwrite survey");
-  if (bl.any()) pqb_size(cols, g, stats, &bl);
-  const std::vector<uint32_t>* run_table = n_runs > 0 ? &run_bytes : nullptr;
-  const PqwLayout L = pqw_layout(cols, g, stats, delta_bytes, nullptr, n_compressed > 0 ? nullptr : &x, n_compressed > 0 ? nullptr : &bl, run_table);
-  const size_t file_bytes = L.file_bytes(), image_bytes = align_up((size_t)L.body_bytes + 8, 256);
-  pt.mark("pqwrite layout");
-  // The bloom filters (fdb_pqbloom.hip): the survey's table has sized them, so their bitsets — one zeroed table of the call's arena,
-  // every bitset 32-byte aligned in it, which a file offset is not — are filled beside the encode pass, on the same stream. They come
-  // back after the image, each straight to its place behind its header (bloom_out), in the wait of the image's copy.
-  unsigned char* d_bitsets = nullptr;
-  if (bl.any()) {
-    std::vector<FdbPqbCol> bc;
-    d_bitsets = (unsigned char*)cs.alloc((size_t)bl.table_bytes);
-    for (size_t k = 0; k < cols.size(); k++) {
-      if (bl.on[k] == 0) continue;
-      FdbPqbCol o;
-      std::memset(&o, 0, sizeof(FdbPqbCol));
-      o.values = cols[k].values; o.validity = cols[k].validity; o.index = cols[k].pq_kind != FDB_PQW_V64;
-      o.bits = (unsigned long long*)(d_bitsets + bl.table_off[k]); o.n_blocks = bl.bytes[k] / FDB_PQB_BLOCK_BYTES;
-      const std::vector<uint64_t>& h = bl.hashes[k];
-      if (!h.empty()) {
-        uint64_t* d_hashes = (uint64_t*)cs.alloc(h.size() * 8);
-        hip_check(hipMemcpyAsync(d_hashes, h.data(), h.size() * 8, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(entry hashes)");  // (`bl` outlives the wait)
-        o.hashes = d_hashes; o.hash_len = (uint32_t)h.size();
-      }
-      bc.push_back(o);
-    }
-    const FdbPqbCol* d_bcols = (const FdbPqbCol*)cs.ctx->stage(bc.data(), bc.size() * sizeof(FdbPqbCol));
-    hip_check(hipMemsetAsync(d_bitsets, 0, (size_t)bl.table_bytes, stream), "hipMemsetAsync(bloom filter bitsets)");
-    hip_check(fdb_launch_pqb_insert(d_bcols, (int32_t)bc.size(), g, stream), "parquet write: bloom filter launch");
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite bloom insert"); }
-  }
-  const auto bloom_out = [&](const PqwLayout& at, uint8_t* out) {
-    for (const PqwLayout::Bloom& f : at.blooms)
-      hip_check(hipMemcpyAsync(out + f.bits_off, d_bitsets + bl.table_off[f.col], (size_t)f.bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(bloom filter bitset)");
-    if (pt.on && !at.blooms.empty()) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite bloom copy"); }
-  };
-  image.p = device_pool_alloc(b.device, image_bytes);
-  FdbPqwPageOut* d_out = (FdbPqwPageOut*)cs.alloc(items * sizeof(FdbPqwPageOut));
-  hip_check(hipMemcpyAsync(d_out, L.out.data(), items * sizeof(FdbPqwPageOut), hipMemcpyHostToDevice, stream), "hipMemcpyAsync(page offsets)");
-  hip_check(hipMemsetAsync(image.p, 0, image_bytes, stream), "hipMemsetAsync(file image)");
-  hip_check(fdb_launch_pqw_encode(d_cols, g, d_out, d_tile_base, (unsigned char*)image.p, stream), "parquet write: encode launch");
-  if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite encode"); }
-  if (n_delta > 0) {
-    uint64_t* d_delta_out = (uint64_t*)cs.alloc(d_items * 8);
-    hip_check(hipMemcpyAsync(d_delta_out, L.delta_out.data(), d_items * 8, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(DELTA page offsets)");
-    hip_check(fdb_launch_pqd_encode(d_dcols, (int32_t)n_delta, g, d_stats, d_blocks, d_delta_out, (unsigned char*)image.p, stream), "parquet write: DELTA encode launch");
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite delta encode"); }
-  }
-  if (n_runs > 0) {
-    uint64_t* d_run_out = (uint64_t*)cs.alloc(r_items * 8);
-    hip_check(hipMemcpyAsync(d_run_out, L.run_out.data(), r_items * 8, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(run-encoded page offsets)");
-    hip_check(fdb_launch_pqr_encode(d_streams, (int32_t)n_runs, g, d_stats, d_run_bytes, d_run_out, (unsigned char*)image.p, stream), "parquet write: run encode launch");
-    if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite run encode"); }
-  }
-  if (n_compressed == 0) {
-    file.p = pqw_alloc_bytes(file_bytes, true);
-    bloom_out(L, file.p);
-    cs.ctx->copy_out_parallel(file.p, image.p, (size_t)L.body_bytes);
-    pt.mark("pqwrite copy");
-    pqw_finish(L, file.p);
-    pt.mark("pqwrite host tail");
-    *bytes = file.p; *n_bytes = (int64_t)file_bytes; file.p = nullptr;
-    return;
-  }
-  // `image` is the staging image. The host's bytes inside the bodies go in, every fragment is compressed into its slot of scratch, the
-  // sizes are summed per page and come back; the file is laid out again, and one gather fills the final image, which is what crosses
-  // the link.
-  const auto upload = [&](const void* host, size_t n, const char* what) {
-    void* d = cs.alloc(std::max<size_t>(n, 8));
-    if (n > 0) hip_check(hipMemcpyAsync(d, host, n, hipMemcpyHostToDevice, stream), what);
-    return d;
-  };
-  std::vector<FdbPqsRange> pieces;
-  for (const PqwLayout::Piece& p : L.body_pieces) pieces.push_back(FdbPqsRange{(uint64_t)p.pos, p.off, (uint32_t)p.len, 0});
-  std::vector<FdbPqsPage> pages;
-  std::vector<FdbPqsFrag> frags;
-  for (const PqwLayout::Page& pg : L.pages) {
-    pages.push_back(FdbPqsPage{(uint32_t)frags.size(), fdb_pqs_fragments(pg.body)});
-    for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT)
-      frags.push_back(FdbPqsFrag{pg.off + at, (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at), (uint32_t)(pages.size() - 1)});
-  }
-  if (frags.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 fragments to compress");
-  scratch.p = device_pool_alloc(b.device, std::max<size_t>(frags.size(), 1) * fdb_pqs_slot_bytes());
-  const unsigned char* d_blob = (const unsigned char*)upload(L.body_blob.data(), L.body_blob.size(), "hipMemcpyAsync(page body pieces)");
-  const FdbPqsRange* d_pieces = (const FdbPqsRange*)upload(pieces.data(), pieces.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(page body piece table)");
-  const FdbPqsFrag* d_frags = (const FdbPqsFrag*)upload(frags.data(), frags.size() * sizeof(FdbPqsFrag), "hipMemcpyAsync(fragment table)");
-  const FdbPqsPage* d_pages = (const FdbPqsPage*)upload(pages.data(), pages.size() * sizeof(FdbPqsPage), "hipMemcpyAsync(compressed page table)");
-  uint32_t* d_frag_bytes = (uint32_t*)cs.alloc(std::max<size_t>(frags.size(), 1) * 4);
-  uint32_t* d_frag_off = (uint32_t*)cs.alloc(std::max<size_t>(frags.size(), 1) * 4);
-  uint32_t* d_page_elements = (uint32_t*)cs.alloc(std::max<size_t>(pages.size(), 1) * 4);
-  std::vector<uint32_t> page_elements(pages.size(), 0);
-  hip_check(fdb_launch_pqs_place(d_pieces, (int32_t)pieces.size(), d_blob, (unsigned char*)image.p, stream), "parquet write: body piece launch");
-  hip_check(fdb_launch_pqs_compress(d_frags, (int32_t)frags.size(), (const unsigned char*)image.p, (unsigned char*)scratch.p, d_frag_bytes, stream), "parquet write: compress launch");
-  if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite compress"); }
-  hip_check(fdb_launch_pqs_scan(d_pages, (int32_t)pages.size(), d_frag_bytes, d_frag_off, d_page_elements, stream), "parquet write: compressed size scan launch");
-  if (!pages.empty()) hip_check(hipMemcpyAsync(page_elements.data(), d_page_elements, pages.size() * 4, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(compressed page sizes)");
-  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-  pt.mark("pqwrite scan");
-  const PqwLayout F = pqw_layout(cols, g, stats, delta_bytes, &page_elements, &x, &bl, run_table);
-  const size_t out_bytes = F.file_bytes();
-  pt.mark("pqwrite final layout");
-  std::vector<uint64_t> page_dst(F.pages.size());
-  for (size_t i = 0; i < F.pages.size(); i++) page_dst[i] = F.pages[i].off;
-  std::vector<FdbPqsRange> ranges;  // the chunks of the uncompressed columns, in pieces a workgroup moves at a time
+  c->items = cols.size() * (size_t)c->P.g.n_pages;
+  c->d_cols = (const FdbPqwCol*)c->cs.ctx->stage(kc.data(), kc.size() * sizeof(FdbPqwCol));
+  c->d_stats = (FdbPqwPageStat*)c->cs.alloc(c->items * sizeof(FdbPqwPageStat));
+  c->d_tile_base = (uint32_t*)c->cs.alloc(c->items * (size_t)c->P.g.tiles_per_page * 4);
+  c->stats.resize(c->items);
+}
+
+// The DELTA columns: scratch for the dense values of those with a bitmap, the block table, the page sizes.
+static void pqd_tables(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  const FdbPqwGeom& g = c->P.g;
+  c->d_items = c->P.n_delta * (size_t)g.n_pages;
+  c->delta_bytes.resize(c->d_items);
+  std::vector<FdbPqdCol> dc(c->P.n_delta);
   for (size_t k = 0; k < cols.size(); k++) {
+    if (cols[k].delta_slot < 0) continue;
+    FdbPqdCol& o = dc[(size_t)cols[k].delta_slot];
+    std::memset(&o, 0, sizeof(FdbPqdCol));
+    o.values = (const uint64_t*)cols[k].values; o.validity = cols[k].validity; o.col = (int32_t)k;
+    o.dense = cols[k].validity != nullptr ? (uint64_t*)c->cs.alloc(((size_t)g.rows + 1) * 8) : (uint64_t*)const_cast<void*>(cols[k].values);  // (only ever read when it is the column)
+    c->compact = c->compact || cols[k].validity != nullptr;
+  }
+  c->d_dcols = (const FdbPqdCol*)c->cs.ctx->stage(dc.data(), dc.size() * sizeof(FdbPqdCol));
+  c->d_blocks = (FdbPqdBlock*)c->cs.alloc(c->d_items * (size_t)fdb_pqd_blocks_per_page(g.page_rows) * sizeof(FdbPqdBlock));
+  c->d_page_bytes = (uint32_t*)c->cs.alloc(c->d_items * 4);
+}
+
+// The streams to be cut into runs: scratch for the dense indices of the columns with a bitmap, the table of sizes.
+static void pqr_tables(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  const FdbPqwGeom& g = c->P.g;
+  c->r_items = c->P.n_runs * (size_t)g.n_pages;
+  c->run_bytes.resize(c->r_items);
+  std::vector<FdbPqrStream> rs(c->P.n_runs);
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& col = cols[k];
+    if (col.run_values >= 0) {
+      FdbPqrStream& o = rs[(size_t)col.run_values];
+      std::memset(&o, 0, sizeof(FdbPqrStream));
+      o.values = (const uint32_t*)col.values; o.validity = col.validity; o.col = (int32_t)k; o.width = (int32_t)col.width;
+      o.dense = col.validity != nullptr ? (uint32_t*)c->cs.alloc(((size_t)g.rows + 8) * 4) : (uint32_t*)const_cast<void*>(col.values);  // (only ever read when it is the column)
+      c->run_compact = c->run_compact || col.validity != nullptr;
+    }
+    if (col.run_levels >= 0) {
+      FdbPqrStream& o = rs[(size_t)col.run_levels];
+      std::memset(&o, 0, sizeof(FdbPqrStream));
+      o.validity = col.validity; o.col = (int32_t)k; o.width = 1; o.levels = 1;
+    }
+  }
+  c->d_streams = (const FdbPqrStream*)c->cs.ctx->stage(rs.data(), rs.size() * sizeof(FdbPqrStream));
+  c->d_run_bytes = (uint32_t*)c->cs.alloc(c->r_items * 4);
+}
+
+// The min / max pass (fdb_pqstats.hip): behind the survey, its table back in the same wait.
+static void pqx_minmax_pass(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  PqxIndex& x = c->P.x;
+  c->settle();
+  std::vector<FdbPqxCol> xc(cols.size());
+  for (size_t k = 0; k < cols.size(); k++) {
+    std::memset(&xc[k], 0, sizeof(FdbPqxCol));
+    xc[k].values = cols[k].values; xc[k].validity = cols[k].validity; xc[k].mode = x.modes[k];
+    const std::vector<uint32_t>& r = x.ranks[k];
+    if (r.empty()) continue;
+    uint32_t* d_ranks = (uint32_t*)c->cs.alloc(r.size() * 4);
+    hip_check(hipMemcpyAsync(d_ranks, r.data(), r.size() * 4, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(dictionary ranks)");  // (the plan outlives the wait)
+    xc[k].ranks = d_ranks; xc[k].rank_len = (uint32_t)r.size();
+  }
+  const FdbPqxCol* d_xcols = (const FdbPqxCol*)c->cs.ctx->stage(xc.data(), xc.size() * sizeof(FdbPqxCol));
+  unsigned long long* d_table = (unsigned long long*)c->cs.alloc(2 * c->items * 8);
+  hip_check(hipMemsetAsync(d_table, 0xFF, c->items * 8, c->stream), "hipMemsetAsync(min table)");
+  hip_check(hipMemsetAsync(d_table + c->items, 0, c->items * 8, c->stream), "hipMemsetAsync(max table)");
+  hip_check(fdb_launch_pqx_minmax(d_xcols, c->P.g, d_table, c->stream), "parquet write: min / max launch");
+  x.table.assign(2 * c->items, 0);
+  hip_check(hipMemcpyAsync(x.table.data(), d_table, 2 * c->items * 8, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(min / max table)");
+  c->timed("pqwrite stats");
+}
+
+// The DELTA passes of fdb_pqdelta.hip that size the pages: compaction of the columns with a bitmap, block survey and page walk.
+static void pqd_survey_pass(PqwCall* c) {
+  const int32_t n = (int32_t)c->P.n_delta;
+  if (c->queued != nullptr) c->settle();
+  if (c->compact) hip_check(fdb_launch_pqd_compact(c->d_dcols, n, c->P.g, c->d_tile_base, c->stream), "parquet write: DELTA compaction launch");
+  c->timed("pqwrite delta compact");
+  hip_check(fdb_launch_pqd_survey(c->d_dcols, n, c->P.g, c->d_stats, c->d_blocks, c->d_page_bytes, c->stream), "parquet write: DELTA block survey launch");
+  hip_check(hipMemcpyAsync(c->delta_bytes.data(), c->d_page_bytes, c->d_items * 4, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(DELTA page sizes)");
+  c->queued = "pqwrite delta survey";
+}
+
+// The run passes of fdb_pqruns.hip that size the streams: compaction of the indices of the columns with a bitmap, the run survey.
+static void pqr_survey_pass(PqwCall* c) {
+  const int32_t n = (int32_t)c->P.n_runs;
+  c->settle();
+  if (c->run_compact) hip_check(fdb_launch_pqr_compact(c->d_streams, n, c->P.g, c->d_tile_base, c->stream), "parquet write: run compaction launch");
+  hip_check(fdb_launch_pqr_survey(c->d_streams, n, c->P.g, c->d_stats, c->d_run_bytes, c->stream), "parquet write: run survey launch");
+  hip_check(hipMemcpyAsync(c->run_bytes.data(), c->d_run_bytes, c->r_items * 4, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(run-encoded sizes)");
+  c->queued = "pqwrite run survey";
+}
+
+// The insert pass of fdb_pqbloom.hip, into one zeroed table of bitsets the survey's table has sized.
+static void pqb_insert_pass(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  const PqbPlan& bl = c->P.bloom;
+  std::vector<FdbPqbCol> bc;
+  c->d_bitsets = (unsigned char*)c->cs.alloc((size_t)bl.table_bytes);
+  for (size_t k = 0; k < cols.size(); k++) {
+    if (bl.on[k] == 0) continue;
+    FdbPqbCol o;
+    std::memset(&o, 0, sizeof(FdbPqbCol));
+    o.values = cols[k].values; o.validity = cols[k].validity; o.index = cols[k].pq_kind != FDB_PQW_V64;
+    o.bits = (unsigned long long*)(c->d_bitsets + bl.table_off[k]); o.n_blocks = bl.bytes[k] / FDB_PQB_BLOCK_BYTES;
+    const std::vector<uint64_t>& h = bl.hashes[k];
+    if (!h.empty()) {
+      uint64_t* d_hashes = (uint64_t*)c->cs.alloc(h.size() * 8);
+      hip_check(hipMemcpyAsync(d_hashes, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(entry hashes)");  // (the plan outlives the wait)
+      o.hashes = d_hashes; o.hash_len = (uint32_t)h.size();
+    }
+    bc.push_back(o);
+  }
+  const FdbPqbCol* d_bcols = (const FdbPqbCol*)c->cs.ctx->stage(bc.data(), bc.size() * sizeof(FdbPqbCol));
+  hip_check(hipMemsetAsync(c->d_bitsets, 0, (size_t)bl.table_bytes, c->stream), "hipMemsetAsync(bloom filter bitsets)");
+  hip_check(fdb_launch_pqb_insert(d_bcols, (int32_t)bc.size(), c->P.g, c->stream), "parquet write: bloom filter launch");
+  c->timed("pqwrite bloom insert");
+}
+
+// The image, zeroed, and the encode passes into it, every payload to where `L` says: the encode pass, then the DELTA and the run encoder.
+static void pqw_encode_passes(PqwCall* c, const PqwLayout& L) {
+  const FdbPqwGeom& g = c->P.g;
+  const size_t image_bytes = align_up((size_t)L.body_bytes + 8, 256);
+  c->image.alloc(image_bytes);
+  unsigned char* image = c->image.p;
+  FdbPqwPageOut* d_out = (FdbPqwPageOut*)c->cs.alloc(c->items * sizeof(FdbPqwPageOut));
+  hip_check(hipMemcpyAsync(d_out, L.out.data(), c->items * sizeof(FdbPqwPageOut), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(page offsets)");
+  hip_check(hipMemsetAsync(image, 0, image_bytes, c->stream), "hipMemsetAsync(file image)");
+  hip_check(fdb_launch_pqw_encode(c->d_cols, g, d_out, c->d_tile_base, image, c->stream), "parquet write: encode launch");
+  c->timed("pqwrite encode");
+  if (c->P.n_delta > 0) {
+    uint64_t* d_delta_out = (uint64_t*)c->cs.alloc(c->d_items * 8);
+    hip_check(hipMemcpyAsync(d_delta_out, L.delta_out.data(), c->d_items * 8, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(DELTA page offsets)");
+    hip_check(fdb_launch_pqd_encode(c->d_dcols, (int32_t)c->P.n_delta, g, c->d_stats, c->d_blocks, d_delta_out, image, c->stream), "parquet write: DELTA encode launch");
+    c->timed("pqwrite delta encode");
+  }
+  if (c->P.n_runs > 0) {
+    uint64_t* d_run_out = (uint64_t*)c->cs.alloc(c->r_items * 8);
+    hip_check(hipMemcpyAsync(d_run_out, L.run_out.data(), c->r_items * 8, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(run-encoded page offsets)");
+    hip_check(fdb_launch_pqr_encode(c->d_streams, (int32_t)c->P.n_runs, g, c->d_stats, c->d_run_bytes, d_run_out, image, c->stream), "parquet write: run encode launch");
+    c->timed("pqwrite run encode");
+  }
+}
+
+// SNAPPY (fdb_pqsnappy.hip): the host tables of the compress and gather passes — they outlive the waits of both — and their device copies.
+struct PqsTables {
+  std::vector<FdbPqsRange> pieces, ranges; std::vector<FdbPqsPage> pages; std::vector<FdbPqsFrag> frags;
+  std::vector<uint64_t> page_dst; std::vector<uint32_t> page_elements;
+  const FdbPqsFrag* d_frags = nullptr; uint32_t *d_frag_bytes = nullptr, *d_frag_off = nullptr;
+};
+
+// The staging image, laid out by `L`, compressed: the fragment and page tables of the pages it lists, the host's bytes inside their
+// bodies placed, every fragment into its slot of scratch, the sizes summed per page (t->page_elements) — the call's second wait.
+static void pqs_compress_pass(PqwCall* c, const PqwLayout& L, PqsTables* t) {
+  for (const PqwLayout::Piece& p : L.body_pieces) t->pieces.push_back(FdbPqsRange{(uint64_t)p.pos, p.off, (uint32_t)p.len, 0});
+  for (const PqwLayout::Page& pg : L.pages) {
+    t->pages.push_back(FdbPqsPage{(uint32_t)t->frags.size(), fdb_pqs_fragments(pg.body)});
+    for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT)
+      t->frags.push_back(FdbPqsFrag{pg.off + at, (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at), (uint32_t)(t->pages.size() - 1)});
+  }
+  if (t->frags.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 fragments to compress");
+  const size_t n_frags = std::max<size_t>(t->frags.size(), 1);
+  c->scratch.alloc(n_frags * fdb_pqs_slot_bytes());
+  const unsigned char* d_blob = (const unsigned char*)c->upload(L.body_blob.data(), L.body_blob.size(), "hipMemcpyAsync(page body pieces)");
+  const FdbPqsRange* d_pieces = (const FdbPqsRange*)c->upload(t->pieces.data(), t->pieces.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(page body piece table)");
+  t->d_frags = (const FdbPqsFrag*)c->upload(t->frags.data(), t->frags.size() * sizeof(FdbPqsFrag), "hipMemcpyAsync(fragment table)");
+  const FdbPqsPage* d_pages = (const FdbPqsPage*)c->upload(t->pages.data(), t->pages.size() * sizeof(FdbPqsPage), "hipMemcpyAsync(compressed page table)");
+  t->d_frag_bytes = (uint32_t*)c->cs.alloc(n_frags * 4);
+  t->d_frag_off = (uint32_t*)c->cs.alloc(n_frags * 4);
+  uint32_t* d_page_elements = (uint32_t*)c->cs.alloc(std::max<size_t>(t->pages.size(), 1) * 4);
+  t->page_elements.assign(t->pages.size(), 0);
+  hip_check(fdb_launch_pqs_place(d_pieces, (int32_t)t->pieces.size(), d_blob, c->image.p, c->stream), "parquet write: body piece launch");
+  hip_check(fdb_launch_pqs_compress(t->d_frags, (int32_t)t->frags.size(), c->image.p, c->scratch.p, t->d_frag_bytes, c->stream), "parquet write: compress launch");
+  c->timed("pqwrite compress");
+  hip_check(fdb_launch_pqs_scan(d_pages, (int32_t)t->pages.size(), t->d_frag_bytes, t->d_frag_off, d_page_elements, c->stream), "parquet write: compressed size scan launch");
+  if (!t->pages.empty()) hip_check(hipMemcpyAsync(t->page_elements.data(), d_page_elements, t->pages.size() * 4, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(compressed page sizes)");
+  c->wait();
+  c->pt.mark("pqwrite scan");
+}
+
+// ONE gather launch moves the fragments' elements and the chunks of the uncompressed columns from the staging image (`L`) to where the
+// final layout `F` wants them in the final image.
+static void pqs_gather_pass(PqwCall* c, const PqwLayout& L, const PqwLayout& F, PqsTables* t) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  std::vector<uint64_t>& page_dst = t->page_dst; std::vector<FdbPqsRange>& ranges = t->ranges;
+  page_dst.resize(F.pages.size());
+  for (size_t i = 0; i < F.pages.size(); i++) page_dst[i] = F.pages[i].off;
+  for (size_t k = 0; k < cols.size(); k++) {  // the chunks of the uncompressed columns, in pieces a workgroup moves at a time
     if (cols[k].codec != 0) continue;
     for (uint64_t at = 0; at < L.chunk_len[k]; at += FDB_PQS_COPY_PIECE)
       ranges.push_back(FdbPqsRange{L.chunk_off[k] + at, F.chunk_off[k] + at, (uint32_t)std::min<uint64_t>(FDB_PQS_COPY_PIECE, L.chunk_len[k] - at), 0});
   }
   if (ranges.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 pieces to move");
-  const uint64_t* d_page_dst = (const uint64_t*)upload(page_dst.data(), page_dst.size() * 8, "hipMemcpyAsync(compressed page offsets)");
-  const FdbPqsRange* d_ranges = (const FdbPqsRange*)upload(ranges.data(), ranges.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(chunk piece table)");
-  final_image.p = device_pool_alloc(b.device, align_up((size_t)F.body_bytes + 8, 256));
-  hip_check(fdb_launch_pqs_gather(d_frags, (int32_t)frags.size(), d_frag_bytes, d_frag_off, d_page_dst, (const unsigned char*)scratch.p, d_ranges, (int32_t)ranges.size(),
-                                  (const unsigned char*)image.p, (unsigned char*)final_image.p, stream), "parquet write: gather launch");
-  if (pt.on) { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); pt.mark("pqwrite gather"); }
-  file.p = pqw_alloc_bytes(out_bytes, true);
-  bloom_out(F, file.p);
-  cs.ctx->copy_out_parallel(file.p, final_image.p, (size_t)F.body_bytes);
-  pt.mark("pqwrite copy");
-  pqw_finish(F, file.p);
-  pt.mark("pqwrite host tail");
-  *bytes = file.p; *n_bytes = (int64_t)out_bytes; file.p = nullptr;
+  const uint64_t* d_page_dst = (const uint64_t*)c->upload(page_dst.data(), page_dst.size() * 8, "hipMemcpyAsync(compressed page offsets)");
+  const FdbPqsRange* d_ranges = (const FdbPqsRange*)c->upload(ranges.data(), ranges.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(chunk piece table)");
+  c->final_image.alloc(align_up((size_t)F.body_bytes + 8, 256));
+  hip_check(fdb_launch_pqs_gather(t->d_frags, (int32_t)t->frags.size(), t->d_frag_bytes, t->d_frag_off, d_page_dst, c->scratch.p, d_ranges, (int32_t)ranges.size(), c->image.p, c->final_image.p,
+                                  c->stream), "parquet write: gather launch");
+  c->timed("pqwrite gather");
+}
+
+// The one ending: the pinned file, every bitset straight to its place in it, the image in one parallel copy, the host's holes and tail.
+static size_t pqw_deliver(PqwCall* c, const PqwLayout& at, const void* image, PqwBytes* file) {
+  const size_t file_bytes = at.file_bytes();
+  file->p = pqw_alloc_bytes(file_bytes, true);
+  for (const PqwLayout::Bloom& f : at.blooms)
+    hip_check(hipMemcpyAsync(file->p + f.bits_off, c->d_bitsets + c->P.bloom.table_off[f.col], (size_t)f.bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(bloom filter bitset)");
+  if (!at.blooms.empty()) c->timed("pqwrite bloom copy");
+  c->cs.ctx->copy_out_parallel(file->p, image, (size_t)at.body_bytes);
+  c->pt.mark("pqwrite copy");
+  pqw_finish(at, file->p);
+  c->pt.mark("pqwrite host tail");
+  return file_bytes;
+}
+
+void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes) {
+  std::vector<PqwInput> in;
+  for (const DevColumn& c : b.cols) {
+    PqwInput o;
+    o.name = c.name; o.format = c.format; o.kind = c.kind; o.dict = c.dict; o.null_count = c.null_count; o.values = c.d_values; o.validity = c.d_validity;
+    in.push_back(std::move(o));
+  }
+  // plan: every refusal of the options, then the device's own two — the min / max and the insert pass load 16 bytes of values at a time
+  PqwPlan P = pqw_plan(in, b.rows, spec);
+  const std::vector<PqwColumn>& cols = P.cols;
+  const bool bounds = P.x.statistics > 0;
+  for (size_t k = 0; k < cols.size() && bounds; k++)
+    if (((uintptr_t)cols[k].values & 15u) != 0) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (statistics)");
+  for (size_t k = 0; k < cols.size() && P.bloom.any(); k++)
+    if (P.bloom.on[k] != 0 && ((uintptr_t)cols[k].values & 15u) != 0)
+      throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (bloom filter)");
+  if (b.rows == 0 || cols.empty()) { pqw_write_host(P, bytes, n_bytes); return; }
+  PqwBytes file;
+  PhaseTimer pt;
+  PoolBlock image{b.device}, scratch{b.device}, final_image{b.device};  // (before the scope: freed after its wait; the last two: compressed columns only)
+  CallScope cs(b.device);
+  DrainOnUnwind drain{cs.ctx->stream};
+  PqwCall c{P, cs, cs.ctx->stream, image, scratch, final_image, pt};
+  pqw_tables(&c);
+  if (P.n_delta > 0) pqd_tables(&c);
+  if (P.n_runs > 0) pqr_tables(&c);
+  // the survey passes, their tables back in ONE wait
+  b.note_reader(c.stream);
+  hip_check(fdb_launch_pqw_survey(c.d_cols, P.g, c.d_stats, c.d_tile_base, c.stream), "parquet write: survey launch");
+  hip_check(hipMemcpyAsync(c.stats.data(), c.d_stats, c.items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, c.stream), "hipMemcpyAsync(page table)");
+  c.queued = "pqwrite survey";
+  if (bounds) pqx_minmax_pass(&c);
+  if (P.n_delta > 0) pqd_survey_pass(&c);
+  if (P.n_runs > 0) pqr_survey_pass(&c);
+  c.wait();
+  pt.mark(c.queued != nullptr ? c.queued : "pqwrite wait");
+  // layout: the file's own, or — with a compressed column — the staging image's
+  if (P.bloom.any()) pqb_size(cols, P.g, c.stats, &P.bloom);
+  PqwSizes sizes{c.stats, &c.delta_bytes, P.n_runs > 0 ? &c.run_bytes : nullptr, nullptr};
+  const PqwLayout L = pqw_layout(P, sizes);
+  pt.mark("pqwrite layout");
+  // the encode passes, the filters' insert pass in front of them
+  if (P.bloom.any()) pqb_insert_pass(&c);
+  pqw_encode_passes(&c, L);
+  // with a compressed column `image` is the staging image: compress it (the second wait), lay the file out again, gather
+  const bool squeezed = P.n_compressed > 0;
+  PqwLayout F; PqsTables t;
+  if (squeezed) {
+    pqs_compress_pass(&c, L, &t);
+    sizes.page_elements = &t.page_elements;
+    F = pqw_layout(P, sizes);
+    pt.mark("pqwrite final layout");
+    pqs_gather_pass(&c, L, F, &t);
+  }
+  // deliver: what crosses the link is the file's own image
+  *n_bytes = (int64_t)pqw_deliver(&c, squeezed ? F : L, squeezed ? final_image.p : image.p, &file);
+  *bytes = file.p; file.p = nullptr;
 }
 #endif
 

@@ -81,7 +81,7 @@ struct PqwLayout {
   size_t file_bytes() const { return (size_t)body_bytes + (size_t)bloom_bytes + tail.size() + footer.size() + 8; }
 };
 
-// What fdb_parquet_bloom_options asks for, checked (pqb_plan); the entry hashes of the filtered index columns (pqb_prepare); and, once
+// What fdb_parquet_bloom_options asks for, checked (pqb_plan); the entry hashes of the filtered index columns (pqw_plan); and, once
 // the survey has counted the non-NULL rows, every filter's size and its place in the table of bitsets (pqb_size).
 struct PqbPlan {
   std::vector<int8_t> on;                      // per column: 1 = gets a filter (empty: none does)
@@ -96,14 +96,14 @@ struct PqbPlan {
 // bits_per_value outside 0 … 64; FDB_ERR_UNSUPPORTED, naming the column — a BOOL column. Nothing has been launched yet. `bloom` ==
 // nullptr or no entry set: nothing asked (any() is false).
 PqbPlan pqb_plan(const fdb_parquet_bloom_options* bloom, const std::vector<PqwColumn>& cols);
-void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b);
 void pqb_size(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqbPlan* b);
 // The pass over host arrays: every non-NULL row's value into the column's bitset of `table` (table_bytes long, zeroed).
 void pqb_insert_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqbPlan& b, unsigned char* table);
 
-// What fdb_parquet_index_options asks for, checked (pqx_plan), and what the min / max pass found (fdb_pqstats.h) — the table of the
-// kernel on the device, of pqx_minmax_host in the self-test. With it pqw_layout writes Statistics.min_value / max_value, column_orders,
-// the page index and sorting_columns; without it (nullptr) the file of the calls before.
+// What fdb_parquet_index_options asks for, checked (pqx_plan), the columns' modes and ranks when statistics > 0 (pqw_plan), and what
+// the min / max pass found (fdb_pqstats.h) — the table of the kernel on the device, of pqx_minmax_host in the self-test. With it
+// pqw_layout writes Statistics.min_value / max_value, column_orders, the page index and sorting_columns; when nothing is asked
+// (any() is false) the file of the calls before.
 struct PqxIndex {
   int statistics = 0;                                 // 0 none, 1 chunk bounds, 2 + ColumnIndex and OffsetIndex
   uint32_t limit = 16;                                // BYTE_ARRAY bounds of the ColumnIndex are cut to this many bytes
@@ -115,16 +115,23 @@ struct PqxIndex {
 };
 // Every refusal of the index options (FDB_ERR_INVALID): nothing has been launched yet. `index` == nullptr: nothing asked.
 PqxIndex pqx_plan(const fdb_parquet_index_options* index, size_t n_cols);
-// modes, ranks and entry_of_rank of the columns (statistics > 0).
-void pqx_prepare(const std::vector<PqwColumn>& cols, PqxIndex* x);
 // The pass over host arrays: the table set to empty, then every tile folded in — in descending order, which min and max do not mind.
 void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, PqxIndex* x);
 
-// Options and columns checked, every refusal made (FDB_ERR_INVALID / FDB_ERR_UNSUPPORTED): nothing has been launched yet. `encodings`:
-// per column 0 (as ever) or 1 (DELTA_BINARY_PACKED; I64 and U64 columns only), n_encodings 0 or the column count. `codecs`: per column
-// 0 (UNCOMPRESSED) or 1 (SNAPPY), n_codecs 0 or the column count.
-std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const fdb_parquet_write_options* opt, int32_t* page_rows,
-                                   const int8_t* encodings = nullptr, int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0);
+// What one call asks for beside the record: the arguments of fdb_batch_to_parquet_runs, which the narrower entry points fill in part.
+// The pointers are borrowed; null / 0: not asked. `encodings`: per column 0 (as ever) or 1 (DELTA_BINARY_PACKED; I64 and U64 columns
+// only); `codecs`: per column 0 (UNCOMPRESSED) or 1 (SNAPPY); n_encodings / n_codecs: 0 or the column count.
+struct PqwSpec {
+  const fdb_parquet_write_options* options = nullptr;
+  const int8_t* encodings = nullptr; int32_t n_encodings = 0;
+  const int8_t* codecs = nullptr; int32_t n_codecs = 0;
+  const fdb_parquet_index_options* index = nullptr;
+  const fdb_parquet_bloom_options* bloom = nullptr;
+  const fdb_parquet_run_options* runs = nullptr;
+};
+// The write options, encodings and codecs of `spec` and the columns checked, every refusal of theirs made (FDB_ERR_INVALID /
+// FDB_ERR_UNSUPPORTED): nothing has been launched yet.
+std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec, int32_t* page_rows);
 size_t pqw_delta_columns(const std::vector<PqwColumn>& cols);
 // What fdb_parquet_run_options asks for, checked, into the columns' run_values / run_levels; returns the streams. Every refusal:
 // FDB_ERR_INVALID — n_columns neither 0 nor the column count, an entry outside 0 … 3; FDB_ERR_UNSUPPORTED, naming the column — bit 0
@@ -136,15 +143,32 @@ size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols);
 // The Snappy block of `n` bytes: the preamble and every fragment's elements, by the host walk of fdb_pqsnappy.h.
 std::string pqs_block_host(const unsigned char* body, size_t n);
 FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
-// `delta_bytes`[delta_slot × n_pages + page]: the value bytes of a DELTA page, as the block survey found them.
-// `page_elements` == nullptr: every page as it is before compression, whatever the columns' codecs — the file itself when no column has
-// one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of the elements of the
-// page's Snappy block (the preamble not counted), as the compressor found them.
-PqwLayout pqw_layout(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& delta_bytes = {},
-                     const std::vector<uint32_t>* page_elements = nullptr, const PqxIndex* index = nullptr, const PqbPlan* bloom = nullptr,
-                     const std::vector<uint32_t>* run_bytes = nullptr);
-// (`run_bytes`[run stream × n_pages + page]: the bytes of a page's stream cut into runs, as the run survey found them — held to the
-// rule's bounds before they are trusted; looked at only where fdb_pqr_active says the rule applies.)
+
+// Everything a call decides before anything is launched: the columns, the geometry, the index and bloom options checked and prepared
+// (modes and ranks; entry hashes), how many columns are DELTA, how many compressed, how many streams are cut into runs. What the
+// passes find later goes into it: x.table (the min / max pass), the filters' sizes (pqb_size).
+struct PqwPlan {
+  std::vector<PqwColumn> cols;
+  FdbPqwGeom g;
+  PqxIndex x; PqbPlan bloom;
+  size_t n_delta = 0, n_compressed = 0, n_runs = 0;
+};
+// THE place that checks a call's options and makes every refusal, in the parameters' order: write options and columns (pqw_columns),
+// index (pqx_plan), bloom (pqb_plan), runs (pqr_plan). Nothing has been launched yet. `in` outlives the plan (its dictionaries).
+PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec);
+// The tables the layout is made from, borrowed (null: no such column or stream). `delta_bytes`[delta_slot × n_pages + page]: the value
+// bytes of a DELTA page, as the block survey found them. `run_bytes`[run stream × n_pages + page]: the bytes of a page's stream cut into
+// runs, as the run survey found them — held to the rule's bounds before they are trusted; looked at only where fdb_pqr_active says the
+// rule applies. `page_elements` == nullptr: every page as it is before compression, whatever the columns' codecs — the file itself
+// when no column has one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of
+// the elements of the page's Snappy block (the preamble not counted), as the compressor found them.
+struct PqwSizes {
+  const std::vector<FdbPqwPageStat>& stats;  // the survey's
+  const std::vector<uint32_t>*delta_bytes = nullptr, *run_bytes = nullptr, *page_elements = nullptr;
+};
+// The page index, sorting_columns and the bloom filters of the plan are laid out when the layout is the file's own — no compressed
+// column, or `page_elements` given: a staging image has neither.
+PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes);
 // Fills the holes of `file` (L.file_bytes() long, the payloads in place — the bitsets of L.blooms included) and appends the page index,
 // if any, footer, length and magic.
 void pqw_finish(const PqwLayout& L, uint8_t* file);
@@ -180,13 +204,9 @@ void pqr_encode_host(const PqrHost& r, const std::vector<uint64_t>& run_out, uns
 uint8_t* pqw_alloc_bytes(size_t n, bool pinned);
 void pqw_free_bytes(uint8_t* bytes);
 
-void selftest_parquet_write(const HostRecordView& view, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr,
-                            int32_t n_encodings = 0, const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr,
-                            const fdb_parquet_run_options* runs = nullptr);
+void selftest_parquet_write(const HostRecordView& view, const PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes);
 #ifndef FDB_PQWRITE_HOST_ONLY
-void batch_to_parquet(const DeviceBatch& b, const fdb_parquet_write_options* opt, uint8_t** bytes, int64_t* n_bytes, const int8_t* encodings = nullptr, int32_t n_encodings = 0,
-                      const int8_t* codecs = nullptr, int32_t n_codecs = 0, const fdb_parquet_index_options* index = nullptr, const fdb_parquet_bloom_options* bloom = nullptr,
-                      const fdb_parquet_run_options* runs = nullptr);
+void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes);
 #endif
 
 }  // namespace fdb

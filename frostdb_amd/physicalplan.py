@@ -168,18 +168,10 @@ def lib() -> ctypes.CDLL:
     L.fdb_batch_column_name.restype = ctypes.c_char_p
     L.fdb_batch_column_format.argtypes = [vp, i32]
     L.fdb_batch_column_format.restype = ctypes.c_char_p
-    L.fdb_batch_to_parquet.argtypes = [vp, vp, P(vp), P(i64)]
-    L.fdb_selftest_parquet_write.argtypes = [vp, vp, vp, P(vp), P(i64)]
-    L.fdb_batch_to_parquet_encoded.argtypes = [vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
-    L.fdb_selftest_parquet_write_encoded.argtypes = [vp, vp, vp, vp, ctypes.c_int32, P(vp), P(i64)]
-    L.fdb_batch_to_parquet_compressed.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
-    L.fdb_selftest_parquet_write_compressed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, P(vp), P(i64)]
-    L.fdb_batch_to_parquet_indexed.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
-    L.fdb_selftest_parquet_write_indexed.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, P(vp), P(i64)]
-    L.fdb_batch_to_parquet_filtered.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, P(vp), P(i64)]
-    L.fdb_selftest_parquet_write_filtered.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, P(vp), P(i64)]
-    L.fdb_batch_to_parquet_runs.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, P(vp), P(i64)]
-    L.fdb_selftest_parquet_write_runs.argtypes = [vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, P(vp), P(i64)]
+    for suffix, takes in PARQUET_WRITE_ENTRIES:
+        optional_args = [vp, i32, vp, i32, vp, vp, vp][:takes + min(takes, 2)]  # (encodings and codecs: an array and its length)
+        getattr(L, "fdb_batch_to_parquet" + suffix).argtypes = [vp, vp] + optional_args + [P(vp), P(i64)]
+        getattr(L, "fdb_selftest_parquet_write" + suffix).argtypes = [vp, vp, vp] + optional_args + [P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
     L.fdb_bytes_free.restype = None
     _lib = L
@@ -519,6 +511,31 @@ def _take_bytes(rc, out, n) -> bytes:
         lib().fdb_bytes_free(out.value)
 
 
+# The writer's entry points, narrowest first: the suffix of the name, and how many of the optional arguments — encodings, codecs, index
+# options, bloom options, run options, in this order — it takes.
+PARQUET_WRITE_ENTRIES = [("", 0), ("_encoded", 1), ("_compressed", 2), ("_indexed", 3), ("_filtered", 4), ("_runs", 5)]
+
+
+def _parquet_write(entry, head, names, is_bool, is_index, asked) -> bytes:
+    """`asked`, the options of ResidentBatch.to_parquet / selftest_parquet_write in their order, as the C structures, and the call
+    through the NARROWEST of `entry`'s entry points that carries what was asked (`head`: its arguments in front of the options)."""
+    page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs = asked
+    opts, _keep = _parquet_write_options(page_rows, optional, names)
+    enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
+    codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
+    index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
+    bloom, _keep_bloom = _parquet_bloom_options(bloom_filters, bloom_bits_per_value, names, is_bool, sorting_columns)
+    run_opts, _keep_runs = _parquet_run_options(runs, names, is_index)
+    optional_args = [(ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc), (ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs)]
+    optional_args += [(ctypes.byref(struct) if struct is not None else None,) for struct in (index, bloom, run_opts)]
+    is_asked = [encodings is not None, compression is not None, index is not None, bloom is not None, run_opts is not None]
+    need = max([i + 1 for i, on in enumerate(is_asked) if on], default=0)
+    suffix, takes = next(e for e in PARQUET_WRITE_ENTRIES if e[1] >= need)
+    out, n = ctypes.c_void_p(), ctypes.c_int64()
+    rc = getattr(lib(), entry + suffix)(*head, ctypes.byref(opts), *[a for group in optional_args[:takes] for a in group], ctypes.byref(out), ctypes.byref(n))
+    return _take_bytes(rc, out, n)
+
+
 def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0,
                            sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None) -> bytes:
     """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
@@ -527,41 +544,13 @@ def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=
     fdb_selftest_parquet_write_indexed, with `bloom_filters` or `bloom_bits_per_value` fdb_selftest_parquet_write_filtered): the same
     layout, headers and footer, the kernels replaced by a host walk of the code they compile. With `runs`
     fdb_selftest_parquet_write_runs: the run passes walked as well."""
-    names = list(record.schema.names)
-    opts, _keep = _parquet_write_options(page_rows, optional, names)
-    enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
-    index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
-    bloom, _keep_bloom = _parquet_bloom_options(bloom_filters, bloom_bits_per_value, names, [pa.types.is_boolean(f.type) for f in record.schema], sorting_columns)
     def is_index(t):
         t = t.value_type if pa.types.is_dictionary(t) else t
         return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
-    run_opts, _keep_runs = _parquet_run_options(runs, names, [is_index(f.type) for f in record.schema])
-    out, n = ctypes.c_void_p(), ctypes.c_int64()
+    asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs)
     with ExportedBatch(record) as ex:
-        if run_opts is not None:
-            codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
-            rc = lib().fdb_selftest_parquet_write_runs(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
-                                                       n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
-                                                       ctypes.byref(bloom) if bloom is not None else None, ctypes.byref(run_opts), ctypes.byref(out), ctypes.byref(n))
-        elif bloom is not None:
-            codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
-            rc = lib().fdb_selftest_parquet_write_filtered(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
-                                                           n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
-                                                           ctypes.byref(bloom), ctypes.byref(out), ctypes.byref(n))
-        elif index is not None:
-            codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
-            rc = lib().fdb_selftest_parquet_write_indexed(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
-                                                          n_enc, ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
-        elif compression is not None:
-            codecs, n_codecs = _parquet_codecs(compression, names)
-            rc = lib().fdb_selftest_parquet_write_compressed(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None,
-                                                             n_enc, ctypes.cast(codecs, ctypes.c_void_p), n_codecs, ctypes.byref(out), ctypes.byref(n))
-        elif encodings is None:
-            rc = lib().fdb_selftest_parquet_write(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
-        else:
-            rc = lib().fdb_selftest_parquet_write_encoded(ctypes.addressof(ex.array), ctypes.addressof(ex.schema), ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_enc,
-                                                          ctypes.byref(out), ctypes.byref(n))
-    return _take_bytes(rc, out, n)
+        return _parquet_write("fdb_selftest_parquet_write", [ctypes.addressof(ex.array), ctypes.addressof(ex.schema)], list(record.schema.names),
+                              [pa.types.is_boolean(f.type) for f in record.schema], [is_index(f.type) for f in record.schema], asked)
 
 
 def live_allocations() -> dict:
@@ -926,40 +915,9 @@ class ResidentBatch:
         its label columns asks for, where a label column is long stretches of one index and a dynamic column long stretches of NULL;
         sized and written on the device by two more passes (fdb_batch_to_parquet_runs). No page gets longer. "values" on a column
         that has no dictionary is refused (True skips such columns). Without it the call is what it was."""
-        opts, _keep = _parquet_write_options(page_rows, optional, self.column_names)
-        out, n = ctypes.c_void_p(), ctypes.c_int64()
-        index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, self.column_names)
-        bloom, _keep_bloom = (None, None) if bloom_filters is None and not bloom_bits_per_value else _parquet_bloom_options(
-            bloom_filters, bloom_bits_per_value, self.column_names, [f == "b" for f in self.column_formats], sorting_columns)
-        run_opts, _keep_runs = (None, None) if runs is None else _parquet_run_options(runs, self.column_names, [f not in ("l", "L", "g", "b") for f in self.column_formats])
-        if run_opts is not None:
-            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
-            codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
-            rc = lib().fdb_batch_to_parquet_runs(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,
-                                                 ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
-                                                 ctypes.byref(bloom) if bloom is not None else None, ctypes.byref(run_opts), ctypes.byref(out), ctypes.byref(n))
-        elif bloom is not None:
-            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
-            codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
-            rc = lib().fdb_batch_to_parquet_filtered(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,
-                                                     ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index) if index is not None else None,
-                                                     ctypes.byref(bloom), ctypes.byref(out), ctypes.byref(n))
-        elif index is not None:
-            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
-            codecs, n_codecs = _parquet_codecs(compression, self.column_names) if compression is not None else (None, 0)
-            rc = lib().fdb_batch_to_parquet_indexed(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc,
-                                                    ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs, ctypes.byref(index), ctypes.byref(out), ctypes.byref(n))
-        elif compression is not None:
-            enc, n_enc = _parquet_encodings(encodings, self.column_names) if encodings is not None else (None, 0)
-            codecs, n_codecs = _parquet_codecs(compression, self.column_names)
-            rc = lib().fdb_batch_to_parquet_compressed(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc, ctypes.cast(codecs, ctypes.c_void_p),
-                                                       n_codecs, ctypes.byref(out), ctypes.byref(n))
-        elif encodings is None:
-            rc = lib().fdb_batch_to_parquet(self.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
-        else:
-            enc, n_enc = _parquet_encodings(encodings, self.column_names)
-            rc = lib().fdb_batch_to_parquet_encoded(self.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_enc, ctypes.byref(out), ctypes.byref(n))
-        return _take_bytes(rc, out, n)
+        asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs)
+        return _parquet_write("fdb_batch_to_parquet", [self.handle], self.column_names, [f == "b" for f in self.column_formats],
+                              [f not in ("l", "L", "g", "b") for f in self.column_formats], asked)
 
     @property
     def num_rows(self) -> int:

@@ -14,6 +14,14 @@ ROWS = [0, 1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 1000]
 NULL_PATTERNS = ["none", "all", "alternate", "first_of_page", "last_of_page", "whole_page"]
 DICT_SIZES = [1, 2, 3, 4, 5, 255, 256, 257, 65536, 65537]  # widths 0, 1, 2, 2, 3, 8, 8, 9, 16, 17
 
+# Calls on mixed_record() that are wrong in two ways at once: (options, the code's name, a piece of the text). The writer checks its
+# options in the parameters' order — write options and columns, index, bloom, runs — so the refusal is that of the EARLIER parameter,
+# from the host walk and from the device alike.
+DOUBLY_WRONG = [
+    ({"bloom_filters": ["flag"], "runs": {"timestamp": "values"}}, "FDB_ERR_UNSUPPORTED", "a bloom filter is not written for a boolean column (flag)"),
+    ({"index_size_limit": 70000, "bloom_filters": ["timestamp"], "bloom_bits_per_value": 65}, "FDB_ERR_INVALID", "index_size_limit is 70000"),
+]
+
 
 def valid_mask(rows: int, pattern: str, page: int = PAGE) -> np.ndarray:
     """True = the row holds a value."""

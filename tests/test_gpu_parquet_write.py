@@ -241,6 +241,23 @@ def test_refusals_leave_nothing_behind_and_the_device_usable():
         rb.close()
 
 
+@pytest.mark.parametrize("kw,code,text", cases.DOUBLY_WRONG)
+def test_a_doubly_wrong_call_is_refused_as_the_host_walk_refuses_it(kw, code, text):
+    record = cases.mixed_record(64, "alternate")
+    with pytest.raises(pp.FdbError) as host:
+        pp.selftest_parquet_write(record, page_rows=cases.PAGE, **kw)
+    rb = pp.ResidentBatch(record)
+    try:
+        before = pp.live_allocations()
+        with pytest.raises(pp.FdbError) as device:
+            rb.to_parquet(page_rows=cases.PAGE, **kw)
+        assert pp.live_allocations() == before   # refused before anything was allocated or launched
+    finally:
+        rb.close()
+    assert device.value.code == host.value.code == getattr(pp, code)
+    assert str(device.value) == str(host.value) and text in str(device.value)
+
+
 def test_everything_is_released():
     gc.collect()
     before = pp.live_allocations()

@@ -199,6 +199,13 @@ def test_refusals_return_their_codes(pp):
     assert e.value.code == pp.FDB_ERR_INVALID and "out of range" in str(e.value)
 
 
+@pytest.mark.parametrize("kw,code,text", cases.DOUBLY_WRONG)
+def test_a_doubly_wrong_call_is_refused_for_the_earlier_parameter(pp, kw, code, text):
+    with pytest.raises(pp.FdbError) as e:
+        pp.selftest_parquet_write(cases.mixed_record(64, "alternate"), page_rows=cases.PAGE, **kw)
+    assert e.value.code == getattr(pp, code) and text in str(e.value), str(e.value)
+
+
 def test_entry_points_are_in_library_header_and_binding(pp):
     L = pp.lib()
     header = open(os.path.join(ROOT, "include", "frostdb_amd.h")).read()

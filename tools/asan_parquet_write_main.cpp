@@ -1,4 +1,4 @@
-// Stand-alone driver of the host half of the Parquet writer for tools/asan_parquet_write.sh: column checks and options (pqw_columns),
+// Stand-alone driver of the host half of the Parquet writer for tools/asan_parquet_write.sh: column checks and options (pqw_plan),
 // the survey and encode walk over host arrays (pqw_survey_host / pqw_encode_host: the arithmetic of fdb_pqwrite.h that the kernels
 // compile), layout planning with the thrift writer and the dictionary page builder (pqw_layout) and the tail (pqw_finish) — over seeded
 // random records and options, every buffer sized exactly. Some int64 / uint64 columns are asked to be DELTA_BINARY_PACKED: the DELTA
@@ -409,15 +409,19 @@ static void one_record(uint64_t* seed, int round) {
 
   int32_t pr = 0;
   const bool with_encodings = (round & 2) != 0 || (round & 1) == 0;  // (one round in four writes every column as ever)
-  const std::vector<PqwColumn> pc = with_encodings ? pqw_columns(in, rows, &opt, &pr, encodings.data(), (int32_t)n_cols) : pqw_columns(in, rows, &opt, &pr);
+  PqwSpec spec{&opt, with_encodings ? encodings.data() : nullptr, with_encodings ? (int32_t)n_cols : 0};
+  const std::vector<PqwColumn> pc = pqw_columns(in, rows, spec, &pr);
   CHECK(pr == (page_rows == 0 ? 65536 : page_rows) && pc.size() == n_cols);
   const FdbPqwGeom g = pqw_geometry(rows, pr, n_cols);
+  const PqwPlan plain = pqw_plan(in, rows, spec);
+  CHECK(plain.cols.size() == n_cols && plain.g.n_pages == g.n_pages && plain.g.page_rows == pr && !plain.x.any() && !plain.bloom.any() && plain.n_runs == 0 && plain.n_compressed == 0);
   std::vector<FdbPqwPageStat> stats;
   std::vector<uint32_t> tile_base;
   pqw_survey_host(pc, g, &stats, &tile_base);
   PqdHost dh;
   pqd_survey_host(pc, g, stats, tile_base, &dh);
-  const PqwLayout L = pqw_layout(pc, g, stats, dh.page_bytes);
+  const PqwSizes sizes{stats, &dh.page_bytes};
+  const PqwLayout L = pqw_layout(plain, sizes);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
   pqw_encode_host(pc, g, L.out, tile_base, image.data());
   pqd_encode_host(pc, g, stats, dh, L.delta_out, image.data());
@@ -481,11 +485,13 @@ static void one_record(uint64_t* seed, int round) {
   std::vector<fdb_parquet_sorting_column> sorting;
   for (size_t k = 0; k < n_cols; k++) if (rnd(seed) % 3 == 0) sorting.push_back(fdb_parquet_sorting_column{(int32_t)k, (int8_t)(rnd(seed) & 1), (int8_t)(rnd(seed) & 1), {0, 0}});
   const fdb_parquet_index_options iopt{(int32_t)(rnd(seed) % 3), limit_choices[rnd(seed) % 6], sorting.empty() ? nullptr : sorting.data(), (int32_t)sorting.size()};
-  PqxIndex x = pqx_plan(&iopt, n_cols);
+  spec.index = &iopt;
+  PqwPlan indexed_plan = pqw_plan(in, rows, spec);
+  PqxIndex& x = indexed_plan.x;
   CHECK(x.statistics == iopt.statistics && x.limit == (iopt.index_size_limit == 0 ? 16u : (uint32_t)iopt.index_size_limit) && x.sorting.size() == sorting.size());
-  if (x.statistics > 0) { pqx_prepare(pc, &x); pqx_minmax_host(pc, g, &x); }
+  if (x.statistics > 0) pqx_minmax_host(pc, g, &x);
   {
-    const PqwLayout I = pqw_layout(pc, g, stats, dh.page_bytes, nullptr, &x);
+    const PqwLayout I = pqw_layout(indexed_plan, sizes);
     CHECK(I.body_bytes == L.body_bytes && I.blob == L.blob && (x.any() || I.footer == L.footer) && (x.statistics == 2 || I.tail.empty()));
     check_index(cols, pc, g, stats, I, x, I.chunk_off, I.chunk_len);
     uint8_t* indexed = pqw_alloc_bytes(I.file_bytes(), false);
@@ -501,13 +507,15 @@ static void one_record(uint64_t* seed, int round) {
   for (size_t k = 0; k < n_cols; k++) filtered.push_back((int8_t)(cols[k].kind != ColKind::BOOL && rnd(seed) % 3 != 0));
   const bool no_array = rnd(seed) % 8 == 0;
   const fdb_parquet_bloom_options bopt{no_array ? nullptr : filtered.data(), no_array ? 0 : (int32_t)n_cols, bit_choices[rnd(seed) % 6]};
-  PqbPlan bl = pqb_plan(&bopt, pc);
+  spec.bloom = &bopt;
+  PqwPlan filtered_plan = pqw_plan(in, rows, spec); filtered_plan.x = x;  // (with the table the min / max walk filled)
+  PqbPlan& bl = filtered_plan.bloom;
   bool some = false;
   for (int8_t f : filtered) some = some || f != 0;
   CHECK(bl.any() == (some && !no_array) && (!bl.any() || bl.bits_per_value == (bopt.bits_per_value == 0 ? 10u : (uint32_t)bopt.bits_per_value)));
-  if (bl.any()) { pqb_prepare(pc, &bl); pqb_size(pc, g, stats, &bl); }
+  if (bl.any()) pqb_size(pc, g, stats, &bl);
   {
-    const PqwLayout Bf = pqw_layout(pc, g, stats, dh.page_bytes, nullptr, &x, &bl);
+    const PqwLayout Bf = pqw_layout(filtered_plan, sizes);
     CHECK(Bf.body_bytes == L.body_bytes && Bf.blooms.empty() == !bl.any() && (bl.any() || (Bf.bloom_bytes == 0 && Bf.blob == L.blob)));
     std::vector<unsigned char> bitsets((size_t)bl.table_bytes, 0);  // (sized exactly)
     pqb_insert_host(pc, g, bl, bitsets.data());
@@ -528,14 +536,16 @@ static void one_record(uint64_t* seed, int round) {
   std::vector<int8_t> run_flags;
   for (size_t k = 0; k < n_cols; k++) run_flags.push_back((int8_t)(cols[k].kind == ColKind::DICT ? rnd(seed) % 4 : (rnd(seed) & 1) * 2));
   const fdb_parquet_run_options ropt{run_flags.data(), (int32_t)n_cols, 0};
-  std::vector<PqwColumn> rc = pc;
-  const size_t n_streams = pqr_plan(&ropt, &rc);
+  spec.index = nullptr; spec.bloom = nullptr; spec.runs = &ropt;
+  const PqwPlan run_plan = pqw_plan(in, rows, spec); spec.runs = nullptr;
+  const std::vector<PqwColumn>& rc = run_plan.cols;
+  const size_t n_streams = run_plan.n_runs;
   CHECK(n_streams == pqr_streams(rc) && n_streams <= 2 * n_cols);
   if (n_streams > 0) {
     PqrHost rh;
     pqr_survey_host(rc, g, stats, &rh);
     CHECK(rh.page_bytes.size() == n_streams * (size_t)g.n_pages);
-    const PqwLayout Rl = pqw_layout(rc, g, stats, dh.page_bytes, nullptr, nullptr, nullptr, &rh.page_bytes);
+    const PqwLayout Rl = pqw_layout(run_plan, PqwSizes{stats, &dh.page_bytes, &rh.page_bytes});
     CHECK(Rl.body_bytes <= L.body_bytes && Rl.run_out.size() == rh.page_bytes.size());
     std::vector<unsigned char> rimage(((size_t)Rl.body_bytes + 8 + 3) / 4 * 4, 0);
     pqw_encode_host(rc, g, Rl.out, tile_base, rimage.data());
@@ -579,8 +589,10 @@ static void one_record(uint64_t* seed, int round) {
   std::vector<int8_t> codecs;
   for (size_t k = 0; k < n_cols; k++) codecs.push_back((int8_t)(rnd(seed) & 1));
   if ((round & 3) != 3) {
-    const std::vector<PqwColumn> cc = pqw_columns(in, rows, &opt, &pr, with_encodings ? encodings.data() : nullptr, with_encodings ? (int32_t)n_cols : 0, codecs.data(), (int32_t)n_cols);
-    const PqwLayout S = pqw_layout(cc, g, stats, dh.page_bytes);  // the staging layout: the payload offsets are those of the uncompressed file
+    spec.codecs = codecs.data(); spec.n_codecs = (int32_t)n_cols; spec.index = &iopt;
+    PqwPlan compressed_plan = pqw_plan(in, rows, spec); compressed_plan.x = x;
+    const std::vector<PqwColumn>& cc = compressed_plan.cols;
+    const PqwLayout S = pqw_layout(compressed_plan, sizes);  // the staging layout: the payload offsets are those of the uncompressed file
     CHECK(S.body_bytes == L.body_bytes);
     std::vector<unsigned char> staging(image);
     for (const PqwLayout::Piece& p : S.body_pieces) { CHECK(p.off + p.len <= S.body_bytes && p.pos + p.len <= S.body_blob.size()); std::memcpy(staging.data() + p.off, S.body_blob.data() + p.pos, p.len); }
@@ -600,7 +612,7 @@ static void one_record(uint64_t* seed, int round) {
       page_elements.push_back((uint32_t)e.size());
       elements.push_back(std::move(e));
     }
-    const PqwLayout F = pqw_layout(cc, g, stats, dh.page_bytes, &page_elements, &x);  // (the index of a compressed file: of the final layout)
+    const PqwLayout F = pqw_layout(compressed_plan, PqwSizes{stats, &dh.page_bytes, nullptr, &page_elements});
     CHECK(F.pages.size() == S.pages.size());
     check_index(cols, cc, g, stats, F, x, F.chunk_off, F.chunk_len);
     const size_t out_bytes = F.file_bytes();
@@ -649,7 +661,7 @@ static void refusals() {
   std::vector<uint8_t> bits(8, 0x0F);
   in[0].name = "x"; in[0].kind = ColKind::I64; in[0].values = v.data(); in[0].validity = bits.data(); in[0].null_count = 4;
   int32_t pr = 0;
-  const auto code = [&](const fdb_parquet_write_options& o) { try { pqw_columns(in, 8, &o, &pr); } catch (const Error& e) { return e.code; } return (int)FDB_OK; };
+  const auto code = [&](const fdb_parquet_write_options& o) { try { pqw_columns(in, 8, PqwSpec{&o}, &pr); } catch (const Error& e) { return e.code; } return (int)FDB_OK; };
   const int8_t required = 0, bad = 3;
   CHECK(code(fdb_parquet_write_options{0, 0, nullptr}) == FDB_OK && pr == 65536);
   CHECK(code(fdb_parquet_write_options{100, 0, nullptr}) == FDB_ERR_INVALID);
@@ -659,11 +671,11 @@ static void refusals() {
   CHECK(code(fdb_parquet_write_options{64, 1, &required}) == FDB_ERR_INVALID);
   CHECK(code(fdb_parquet_write_options{64, 1, &bad}) == FDB_ERR_INVALID);
   const fdb_parquet_write_options plain_opt{64, 0, nullptr};
-  const auto enc_code = [&](const int8_t* e, int32_t n) { try { pqw_columns(in, 8, &plain_opt, &pr, e, n); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const auto enc_code = [&](const int8_t* e, int32_t n) { try { pqw_columns(in, 8, PqwSpec{&plain_opt, e, n}, &pr); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
   const int8_t delta = 1, two = 2, both[2] = {1, 1};
   CHECK(enc_code(&delta, 1) == FDB_OK && enc_code(nullptr, 0) == FDB_OK);
   CHECK(enc_code(&two, 1) == FDB_ERR_INVALID && enc_code(both, 2) == FDB_ERR_INVALID && enc_code(nullptr, 1) == FDB_ERR_INVALID);
-  const auto codec_code = [&](const int8_t* c, int32_t n) { try { pqw_columns(in, 8, &plain_opt, &pr, nullptr, 0, c, n); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const auto codec_code = [&](const int8_t* c, int32_t n) { try { pqw_columns(in, 8, PqwSpec{&plain_opt, nullptr, 0, c, n}, &pr); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
   const int8_t minus = -1;
   CHECK(codec_code(&delta, 1) == FDB_OK && codec_code(nullptr, 0) == FDB_OK);
   CHECK(codec_code(&two, 1) == FDB_ERR_INVALID && codec_code(&minus, 1) == FDB_ERR_INVALID && codec_code(both, 2) == FDB_ERR_INVALID && codec_code(nullptr, 1) == FDB_ERR_INVALID);
@@ -674,14 +686,14 @@ static void refusals() {
   CHECK(index_code(fdb_parquet_index_options{1, 65537, nullptr, 0}, 1) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{0, -1, nullptr, 0}, 1) == FDB_ERR_INVALID);
   CHECK(index_code(fdb_parquet_index_options{1, 0, &s2, 1}, 2) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{1, 0, twice, 2}, 2) == FDB_ERR_INVALID);
   CHECK(index_code(fdb_parquet_index_options{1, 0, nullptr, 1}, 2) == FDB_ERR_INVALID && index_code(fdb_parquet_index_options{1, 0, &s0, -1}, 2) == FDB_ERR_INVALID);
-  const auto bloom_code = [&](const fdb_parquet_bloom_options& o) { try { pqb_plan(&o, pqw_columns(in, 8, &plain_opt, &pr)); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const auto bloom_code = [&](const fdb_parquet_bloom_options& o) { try { pqb_plan(&o, pqw_columns(in, 8, PqwSpec{&plain_opt}, &pr)); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
   const int8_t none = 0;
   CHECK(bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_OK && bloom_code(fdb_parquet_bloom_options{&delta, 1, 64}) == FDB_OK && bloom_code(fdb_parquet_bloom_options{nullptr, 0, 0}) == FDB_OK);
-  CHECK(!pqb_plan(nullptr, pqw_columns(in, 8, &plain_opt, &pr)).any() && bloom_code(fdb_parquet_bloom_options{&none, 1, 1}) == FDB_OK);
+  CHECK(!pqb_plan(nullptr, pqw_columns(in, 8, PqwSpec{&plain_opt}, &pr)).any() && bloom_code(fdb_parquet_bloom_options{&none, 1, 1}) == FDB_OK);
   CHECK(bloom_code(fdb_parquet_bloom_options{&two, 1, 0}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{&minus, 1, 0}) == FDB_ERR_INVALID);
   CHECK(bloom_code(fdb_parquet_bloom_options{both, 2, 0}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{nullptr, 1, 0}) == FDB_ERR_INVALID);
   CHECK(bloom_code(fdb_parquet_bloom_options{&delta, 1, 65}) == FDB_ERR_INVALID && bloom_code(fdb_parquet_bloom_options{&none, 1, -1}) == FDB_ERR_INVALID);
-  const auto run_code = [&](const fdb_parquet_run_options& o) { try { std::vector<PqwColumn> c = pqw_columns(in, 8, &plain_opt, &pr); pqr_plan(&o, &c); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  const auto run_code = [&](const fdb_parquet_run_options& o) { try { std::vector<PqwColumn> c = pqw_columns(in, 8, PqwSpec{&plain_opt}, &pr); pqr_plan(&o, &c); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
   const int8_t four = 4;
   CHECK(run_code(fdb_parquet_run_options{&two, 1, 0}) == FDB_OK && run_code(fdb_parquet_run_options{&none, 1, 0}) == FDB_OK && run_code(fdb_parquet_run_options{nullptr, 0, 0}) == FDB_OK);
   CHECK(run_code(fdb_parquet_run_options{&delta, 1, 0}) == FDB_ERR_UNSUPPORTED && run_code(fdb_parquet_run_options{&bad, 1, 0}) == FDB_ERR_UNSUPPORTED);  // bit 0 on an int64 column
