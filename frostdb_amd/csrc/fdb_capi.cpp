@@ -705,7 +705,7 @@ int fdb_batch_from_parquet(const fdb_parquet_chunk* chunks, int32_t n_chunks, in
   });
 }
 
-// The Parquet writer's twelve entry points: each fills as much of a PqwSpec as it has arguments for and goes through one of these two.
+// The Parquet writer's entry points (fdb_batch_to_parquet* and fdb_selftest_parquet_write*): each fills as much of a PqwSpec as it has arguments for and goes through one of these two.
 static int write_resident(const fdb_batch* batch, const fdb::PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes) {
   return guard(nullptr, [&] {
     if (batch == nullptr || !batch->b || bytes == nullptr || n_bytes == nullptr) throw fdb::Error(FDB_ERR_INVALID, "null argument");
@@ -783,6 +783,18 @@ int fdb_selftest_parquet_write_runs(struct ArrowArray* batch, struct ArrowSchema
                                     const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
                                     const fdb_parquet_run_options* runs, uint8_t** bytes, int64_t* n_bytes) {
   return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs}, bytes, n_bytes);
+}
+
+int fdb_batch_to_parquet_grouped(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
+                                 const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, const fdb_parquet_run_options* runs,
+                                 const fdb_parquet_group_options* groups, uint8_t** bytes, int64_t* n_bytes) {
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs, groups}, bytes, n_bytes);
+}
+
+int fdb_selftest_parquet_write_grouped(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
+                                       const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
+                                       const fdb_parquet_run_options* runs, const fdb_parquet_group_options* groups, uint8_t** bytes, int64_t* n_bytes) {
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs, groups}, bytes, n_bytes);
 }
 
 int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_groups, int device, fdb_batch** out) {

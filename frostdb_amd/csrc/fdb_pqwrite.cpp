@@ -6,7 +6,7 @@
 // payload. Every entry point fills a PqwSpec with the arguments it has (null / 0: not asked) and runs ONE pipeline; a pass in
 // [brackets] runs only when asked for, and without it launches, allocations and copies are those of the narrower call.
 //   plan     pqw_plan: options and columns checked, every refusal made — in the parameters' order: write options and columns, index,
-//            bloom, runs — before anything is launched; the columns' modes and ranks (statistics) and the entry hashes of the filtered
+//            bloom, runs, groups — before anything is launched; the columns' modes and ranks (statistics) and the entry hashes of the filtered
 //            index columns (entry_hashes, fdb_sortplan.h) prepared. A record without rows or columns ends here, on the host.
 //   survey   pqw_survey_kernel: per (column, page) the non-NULL rows and, of index columns, the smallest and largest index; per tile
 //            the rank of its first value. Only the per-page table comes back. Behind it, their tables back in the SAME wait:
@@ -17,6 +17,11 @@
 //            [runs]      RLE runs INSIDE a page's dictionary indices and definition levels (rule: fdb_pqruns.h), what a record sorted by
 //                        its label columns asks for: a chosen stream that would be ONE bit-packed run is cut into RLE and bit-packed
 //                        runs, never longer; fdb_pqruns.hip compacts the indices of the columns with a bitmap and surveys the runs.
+//            [used]      dictionaries of used entries only (fdb_parquet_group_options; rule: fdb_pqdict.h): fdb_pqdict.hip sets a bit per
+//                        referenced entry in one table of presence bitmaps. After the wait the host counts the used entries
+//                        (pqg_resolve) and a remap pass writes a re-keyed copy of every pruned index column, which IS the column for
+//                        every later pass but the bloom insert; the run passes, which need the new width, then follow it and are
+//                        waited for once more.
 //   layout   pqw_layout (host): with these tables every page's size is known, so every payload's file offset is; every DELTA and run
 //            size is held to its rule's bounds first. The survey's table sizes the bloom filters (pqb_size). Pages are folded into
 //            chunk bounds, keys mapped back (a rank to an entry), the zero rule, the cut of BYTE_ARRAY bounds, the boundary order, the
@@ -38,8 +43,11 @@
 // fdb_selftest_parquet_write runs the same plan, layout and tail over a host record, every kernel replaced by a host walk of the same
 // arithmetic (fdb_pqwrite.h, the *_host functions) — byte-identical files, no GPU. FDB_PQWRITE_HOST_ONLY leaves the device half out.
 //
-// File: PAR1 | per column [dictionary page] data pages V1 | [bloom filters] | [page index] | FileMetaData | length | PAR1. Flat schema,
-// one row group, definition levels RLE (one RLE run when a page has no NULL or only NULLs, else one bit-packed run whose payload is the
+// File: PAR1 | per row group, per column [dictionary page] data pages V1 | [bloom filters] | [page index] | FileMetaData | length | PAR1.
+// [row groups] fdb_parquet_group_options::row_group_rows = R cuts the record into groups of R rows (pqw_parts): (group, column) is a
+// VIRTUAL column — the column's buffers g · R rows in — of a record of R rows, so the call is at most two PARTS, the full groups' and a
+// shorter last group's, each a plan of its own that every pass above is launched for once, into ONE layout, image and set of waits.
+// Flat schema, one row group unless asked, definition levels RLE (one RLE run when a page has no NULL or only NULLs, else one bit-packed run whose payload is the
 // validity bitmap's bytes), no repetition levels. I64 → INT64 PLAIN; U64 → INT64 PLAIN, Int(64, unsigned) (writeUint64,
 // parquet.go:154-165); F64 → DOUBLE PLAIN; BOOL → BOOLEAN PLAIN; dictionary and plain string / binary columns → BYTE_ARRAY, a PLAIN
 // dictionary page of the interned dictionary's entries in entry order + RLE_DICTIONARY pages: the width byte, then ONE bit-packed run —
@@ -64,7 +72,7 @@ namespace {
 
 // ---- thrift compact protocol, as far as parquet.thrift's structs need it ----------------------------------------------------------------
 struct Thrift {
-  enum { T_TRUE = 1, T_FALSE = 2, T_BYTE = 3, T_I32 = 5, T_I64 = 6, T_BINARY = 8, T_LIST = 9, T_STRUCT = 12 };
+  enum { T_TRUE = 1, T_FALSE = 2, T_BYTE = 3, T_I16 = 4, T_I32 = 5, T_I64 = 6, T_BINARY = 8, T_LIST = 9, T_STRUCT = 12 };
   std::string out;
   std::vector<int> stack;
   int last = 0;
@@ -76,6 +84,7 @@ struct Thrift {
     else { out.push_back((char)type); zigzag(id); }
     last = id;
   }
+  void i16(int id, int16_t v) { field(id, T_I16); zigzag(v); }
   void i32(int id, int32_t v) { field(id, T_I32); zigzag(v); }
   void i64(int id, int64_t v) { field(id, T_I64); zigzag(v); }
   void boolean(int id, bool v) { field(id, v ? T_TRUE : T_FALSE); }
@@ -120,6 +129,8 @@ std::string le32(uint32_t v) { std::string s(4, '\0'); std::memcpy(&s[0], &v, 4)
 
 struct PageLoc { uint64_t off, bytes; uint32_t rows, count; };  // a data page: where its header starts, header + body as stored, its rows and non-NULL rows
 struct ChunkMeta {
+  const PqwColumn* col = nullptr;
+  int64_t start = 0, rows = 0;                                              // where the chunk starts; its row group's rows
   int64_t dict_off = -1, data_off = 0, bytes = 0, raw_bytes = 0, nulls = 0;  // bytes: as stored; raw_bytes: the bodies uncompressed (headers in both)
   // with statistics only
   std::vector<PageLoc> pages;
@@ -129,13 +140,15 @@ struct ChunkMeta {
   int64_t bloom_off = -1, bloom_len = 0;                                    // with a bloom filter only: its header's offset, header + bitset
 };
 
-std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMeta>& chunks, int64_t rows, int64_t body_bytes, const PqxIndex* x) {
+// `chunks`: n_groups × n_cols of them, group after group; the schema is the first group's columns'. `group_rows`: per group.
+std::string footer(const std::vector<ChunkMeta>& chunks, size_t n_cols, const std::vector<int64_t>& group_rows, int64_t rows, const PqxIndex* x, bool ordinals) {
   Thrift t;
   t.open();
   t.i32(1, 1);
-  t.list(2, Thrift::T_STRUCT, cols.size() + 1);
-  t.open(); t.i32(3, 0); t.string(4, "schema"); t.i32(5, (int32_t)cols.size()); t.close();
-  for (const PqwColumn& c : cols) {
+  t.list(2, Thrift::T_STRUCT, n_cols + 1);
+  t.open(); t.i32(3, 0); t.string(4, "schema"); t.i32(5, (int32_t)n_cols); t.close();
+  for (size_t k = 0; k < n_cols; k++) {
+    const PqwColumn& c = *chunks[k].col;
     t.open();
     t.i32(1, c.physical);
     t.i32(3, c.optional ? 1 : 0);
@@ -145,12 +158,14 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     t.close();
   }
   t.i64(3, rows);
-  t.list(4, Thrift::T_STRUCT, 1);
+  t.list(4, Thrift::T_STRUCT, group_rows.size());
+  for (size_t grp = 0; grp < group_rows.size(); grp++) {
+  const int64_t rows = group_rows[grp];  // (from here on: the group's)
   t.open();  // RowGroup
-  t.list(1, Thrift::T_STRUCT, cols.size());
-  for (size_t k = 0; k < cols.size(); k++) {
-    const PqwColumn& c = cols[k];
-    const ChunkMeta& m = chunks[k];
+  t.list(1, Thrift::T_STRUCT, n_cols);
+  for (size_t k = 0; k < n_cols; k++) {
+    const ChunkMeta& m = chunks[grp * n_cols + k];
+    const PqwColumn& c = *m.col;
     t.open();  // ColumnChunk
     t.i64(2, m.dict_off >= 0 ? m.dict_off : m.data_off);
     t.open(3);  // ColumnMetaData
@@ -172,21 +187,23 @@ std::string footer(const std::vector<PqwColumn>& cols, const std::vector<ChunkMe
     if (m.column_index_off >= 0) { t.i64(6, m.column_index_off); t.i32(7, (int32_t)m.column_index_len); }
     t.close();
   }
-  int64_t raw_bytes = 0;
-  for (const ChunkMeta& m : chunks) raw_bytes += m.raw_bytes;
+  int64_t raw_bytes = 0, stored_bytes = 0;
+  for (size_t k = 0; k < n_cols; k++) { raw_bytes += chunks[grp * n_cols + k].raw_bytes; stored_bytes += chunks[grp * n_cols + k].bytes; }
   t.i64(2, raw_bytes);  // total_byte_size: uncompressed
   t.i64(3, rows);
   if (x != nullptr && !x->sorting.empty()) {
     t.list(4, Thrift::T_STRUCT, x->sorting.size());
     for (const fdb_parquet_sorting_column& sc : x->sorting) { t.open(); t.i32(1, sc.column); t.boolean(2, sc.descending != 0); t.boolean(3, sc.nulls_first != 0); t.close(); }
   }
-  t.i64(5, 4);
-  t.i64(6, body_bytes - 4);
+  t.i64(5, n_cols > 0 ? chunks[grp * n_cols].start : 4);  // file_offset
+  t.i64(6, stored_bytes);                                // total_compressed_size
+  if (ordinals) t.i16(7, (int16_t)grp);  // (under group options only: the calls before keep their bytes)
   t.close();
+  }
   t.string(6, "frostdb_amd 0.1.0");
   if (x != nullptr && x->statistics > 0) {  // column_orders: TypeDefinedOrder for every column
-    t.list(7, Thrift::T_STRUCT, cols.size());
-    for (size_t k = 0; k < cols.size(); k++) { t.open(); t.open(1); t.close(); t.close(); }
+    t.list(7, Thrift::T_STRUCT, n_cols);
+    for (size_t k = 0; k < n_cols; k++) { t.open(); t.open(1); t.close(); t.close(); }
   }
   t.close();
   return t.out;
@@ -202,6 +219,18 @@ std::string dictionary_body(const HostDict& d) {
   return s;
 }
 
+// … of the used entries only (fdb_pqdict.h): those whose bit of `bits` is set, in entry order.
+std::string dictionary_body(const HostDict& d, const unsigned long long* bits) {
+  std::string s;
+  for (size_t i = 0; i < d.values.size(); i++)
+    if (fdb_pqg_used(bits, (uint32_t)i)) { s += le32((uint32_t)d.values[i].size()); s += d.values[i]; }
+  return s;
+}
+
+std::string index_out_of_range(const PqwColumn& c, uint32_t index, uint64_t entries) {
+  return "parquet write: dictionary index out of range in column " + c.name + ": a valid row holds " + std::to_string(index) + ", the dictionary has " + std::to_string(entries) + " entries";
+}
+
 // ---- statistics and the page index: the host's half of the min / max pass (fdb_pqstats.h) -----------------------------------------------
 std::string le64(uint64_t v) { std::string s(8, '\0'); std::memcpy(&s[0], &v, 8); return s; }
 
@@ -210,8 +239,9 @@ std::string le64(uint64_t v) { std::string s(8, '\0'); std::memcpy(&s[0], &v, 8)
 std::string pqx_bound(const PqwColumn& c, const PqxIndex& x, size_t k, uint64_t key, bool is_max) {
   const int mode = x.modes[k];
   if (mode == FDB_PQX_INDEX) {
-    if (key >= x.entry_of_rank[k].size()) throw Error(FDB_ERR_STATE, "parquet write: the min / max pass names rank " + std::to_string(key) + " in column " + c.name);
-    return c.dict->values[x.entry_of_rank[k][(size_t)key]];
+    const std::vector<uint32_t>& entry_of_rank = x.entry_of_rank[c.real];
+    if (key >= entry_of_rank.size()) throw Error(FDB_ERR_STATE, "parquet write: the min / max pass names rank " + std::to_string(key) + " in column " + c.name);
+    return c.dict->values[entry_of_rank[(size_t)key]];
   }
   uint64_t bits = fdb_pqx_value(mode, key);
   if (mode == FDB_PQX_BOOL) return std::string(1, (char)(bits != 0));
@@ -401,12 +431,16 @@ std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows
     if (want == 0 && nulls) throw Error(FDB_ERR_INVALID, "parquet write: column " + c.name + " is asked to be required and holds " + std::to_string(c.null_count) + " NULLs");
     if (nulls && c.validity == nullptr) throw Error(FDB_ERR_INVALID, "parquet write: column " + c.name + " counts NULLs and has no validity bitmap");
     o.optional = want < 0 ? (nulls || c.kind == ColKind::DICT) : want == 1;
+    o.real = k;
     o.values = c.values;
     o.validity = nulls ? c.validity : nullptr;
     cols.push_back(std::move(o));
   }
   return cols;
 }
+
+// The indices as the record holds them, whether or not the column has a re-keyed copy by now.
+static const void* pqw_raw(const PqwColumn& c) { return c.raw_values != nullptr ? c.raw_values : c.values; }
 
 size_t pqw_delta_columns(const std::vector<PqwColumn>& cols) {
   size_t n = 0;
@@ -578,7 +612,8 @@ void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, Pq
   for (size_t k = 0; k < cols.size(); k++) {
     const PqwColumn& c = cols[k];
     const int mode = x->modes[k];
-    const uint32_t per = mode == FDB_PQX_INDEX ? FDB_PQX_UNIT_INDEX : FDB_PQX_UNIT_V64, rank_len = (uint32_t)x->ranks[k].size();
+    const std::vector<uint32_t>& ranks = x->ranks[c.real];
+    const uint32_t per = mode == FDB_PQX_INDEX ? FDB_PQX_UNIT_INDEX : FDB_PQX_UNIT_V64, rank_len = (uint32_t)ranks.size();
     for (int64_t p = g.n_pages; p-- > 0;) {
       for (int32_t t = g.tiles_per_page; t-- > 0;) {
         int64_t first, end;
@@ -591,7 +626,7 @@ void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, Pq
             if (!((bits >> i) & 1)) continue;
             const size_t row = (size_t)first + (size_t)u * per + i;
             bool counts;
-            if (mode == FDB_PQX_INDEX) counts = fdb_pqx_index_key(x->ranks[k].data(), rank_len, ((const uint32_t*)c.values)[row], &key);
+            if (mode == FDB_PQX_INDEX) counts = fdb_pqx_index_key(ranks.data(), rank_len, ((const uint32_t*)pqw_raw(c))[row], &key);
             else { uint64_t v; std::memcpy(&v, (const unsigned char*)c.values + row * 8, 8); counts = fdb_pqx_key(mode, v, &key); }
             if (counts) fdb_pqx_fold(key, &mn, &mx);
           }
@@ -633,6 +668,89 @@ static void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b) {
       b->hashes[k] = entry_hashes(*cols[k].dict, [](const unsigned char* p, size_t n) { return fdb_pqb_hash(p, n); });
 }
 
+// ---- used-entry dictionaries: the host's half of the present and remap passes (fdb_pqdict.h) ---------------------------------------------
+PqgPlan pqg_plan(const fdb_parquet_group_options* groups, int64_t rows, std::vector<PqwColumn>* cols) {
+  PqgPlan d;
+  if (groups == nullptr) return d;
+  const int64_t R = groups->row_group_rows;
+  if (R < 0 || R % 64 != 0) throw Error(FDB_ERR_INVALID, "parquet write: row_group_rows must be a multiple of 64 (0: one row group), got " + std::to_string(R));
+  const int64_t n_groups = R > 0 && rows > 0 ? (rows - 1) / R + 1 : 1;
+  if (n_groups > 32767)
+    throw Error(FDB_ERR_INVALID, "parquet write: row_group_rows " + std::to_string(R) + " cuts " + std::to_string(rows) + " rows into " + std::to_string(n_groups) + " row groups, more than 32767 (RowGroup.ordinal is an i16)");
+  if (groups->dictionaries < 0 || groups->dictionaries > 1)
+    throw Error(FDB_ERR_INVALID, "parquet write: dictionaries is " + std::to_string(groups->dictionaries) + " (0 the whole dictionary, 1 the used entries only)");
+  if (groups->pad != 0) throw Error(FDB_ERR_INVALID, "parquet write: the group options' pad is " + std::to_string(groups->pad) + " (0)");
+  uint64_t words = 0;
+  for (size_t k = 0; k < cols->size() && groups->dictionaries == 1; k++) {
+    PqwColumn& c = (*cols)[k];
+    if (c.pq_kind != FDB_PQW_INDEX) continue;  // (an empty dictionary has nothing to prune)
+    c.used_slot = (int)d.cols.size();
+    PqgPlan::Col o;
+    o.col = k; o.entries = c.entries; o.word_off = words; o.words = fdb_pqg_words(c.entries);
+    d.cols.push_back(o);
+    words += o.words;
+  }
+  d.bits.assign((size_t)words, 0);
+  return d;
+}
+
+void pqg_present_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, PqgPlan* d) {
+  for (const PqgPlan::Col& o : d->cols) {
+    const PqwColumn& c = cols[o.col];
+    unsigned long long* bits = d->bits.data() + o.word_off;
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      for (int32_t t = 0; t < g.tiles_per_page; t++) {
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        for (uint32_t u = 0; (int64_t)u * FDB_PQX_UNIT_INDEX < end - first; u++) {
+          const uint32_t unit = fdb_pqx_unit_bits(c.validity, first, end, u, FDB_PQX_UNIT_INDEX);
+          for (uint32_t i = 0; i < FDB_PQX_UNIT_INDEX; i++) {
+            if (!((unit >> i) & 1)) continue;
+            const uint32_t v = ((const uint32_t*)c.values)[(size_t)first + (size_t)u * FDB_PQX_UNIT_INDEX + i];
+            if (v < o.entries) bits[v >> 6] |= fdb_pqg_bit(v);  // (at or past: the survey's to refuse)
+          }
+        }
+      }
+    }
+  }
+}
+
+void pqg_resolve(const std::vector<FdbPqwPageStat>& stats, const FdbPqwGeom& g, std::vector<PqwColumn>* cols, PqgPlan* d) {
+  d->before.assign(d->bits.size(), 0);
+  for (PqgPlan::Col& o : d->cols) {
+    PqwColumn& c = (*cols)[o.col];
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const FdbPqwPageStat& s = stats[o.col * (size_t)g.n_pages + (size_t)p];
+      if (s.count > 0 && (s.mn > s.mx || s.mx >= o.entries)) throw Error(FDB_ERR_INVALID, index_out_of_range(c, s.mx, o.entries));
+    }
+    const uint64_t spare = o.entries & 63;  // bits past the last entry: never set by a pass that works
+    if (spare != 0 && (d->bits[(size_t)(o.word_off + o.words - 1)] >> spare) != 0) throw Error(FDB_ERR_STATE, "parquet write: the present pass names an entry past the dictionary of " + c.name);
+    uint32_t used = 0;
+    for (uint64_t w = 0; w < o.words; w++) { d->before[(size_t)(o.word_off + w)] = used; used += (uint32_t)fdb_pqw_popc(d->bits[(size_t)(o.word_off + w)]); }
+    o.used = used;
+    c.entries = used;
+    c.width = used > 0 ? fdb_pqw_bits((uint64_t)used - 1) : 0;
+    if (used == 0) c.pq_kind = PQW_NO_VALUES;  // every row is NULL: the form of an empty dictionary
+  }
+}
+
+void pqg_remap_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqgPlan& d, std::vector<std::vector<uint32_t>>* out) {
+  out->assign(d.cols.size(), std::vector<uint32_t>());
+  for (size_t slot = 0; slot < d.cols.size(); slot++) {
+    const PqgPlan::Col& o = d.cols[slot];
+    const PqwColumn& c = cols[o.col];
+    const unsigned long long* bits = d.bits.data() + o.word_off;
+    const uint32_t* before = d.before.data() + o.word_off;
+    std::vector<uint32_t>& dst = (*out)[slot];
+    dst.assign((size_t)g.rows + 8, 0);
+    for (int64_t row = 0; row < g.rows; row++) {
+      if (c.validity != nullptr && !((c.validity[row >> 3] >> (row & 7)) & 1)) continue;
+      const uint32_t v = ((const uint32_t*)pqw_raw(c))[row];
+      if (v < o.entries) dst[(size_t)row] = fdb_pqg_rank(bits, before, v);
+    }
+  }
+}
+
 PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec) {
   PqwPlan P;
   int32_t page_rows = 0;
@@ -640,11 +758,53 @@ PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& s
   P.x = pqx_plan(spec.index, P.cols.size());
   P.bloom = pqb_plan(spec.bloom, P.cols);
   P.n_runs = pqr_plan(spec.runs, &P.cols);
+  P.dict = pqg_plan(spec.groups, rows, &P.cols);
+  P.grouped = spec.groups != nullptr && (spec.groups->row_group_rows != 0 || spec.groups->dictionaries != 0);
   if (P.x.statistics > 0) pqx_prepare(P.cols, &P.x);
   if (P.bloom.any()) pqb_prepare(P.cols, &P.bloom);
   P.g = pqw_geometry(rows, page_rows, P.cols.size());
   P.n_delta = pqw_delta_columns(P.cols); P.n_compressed = pqw_compressed_columns(P.cols);
+  P.n_real = P.cols.size(); P.file_rows = rows;
   return P;
+}
+
+// Groups [first, first + n) of R rows — the last of `rows` — as one plan over virtual columns: every table and slot is the part's own,
+// the ranks and entry hashes stay the record's columns' (PqwColumn::real).
+static PqwPlan pqw_part(const PqwPlan& P, const fdb_parquet_group_options* groups, int64_t first, int64_t n, int64_t R, int64_t rows) {
+  PqwPlan A;
+  A.x = P.x; A.x.modes.clear();
+  A.bloom = P.bloom; A.bloom.on.clear();
+  A.grouped = true; A.first_group = first; A.n_groups = n; A.n_real = P.n_real; A.file_rows = P.file_rows;
+  int deltas = 0, runs = 0;
+  for (int64_t gi = 0; gi < n; gi++) {
+    const size_t at = (size_t)((first + gi) * R);
+    for (size_t k = 0; k < P.cols.size(); k++) {
+      PqwColumn c = P.cols[k];
+      const bool index = c.pq_kind == FDB_PQW_INDEX || c.pq_kind == PQW_NO_VALUES;
+      if (c.values != nullptr) c.values = (const unsigned char*)c.values + at * (index ? 4 : 8);  // (R is a multiple of 64: 256-byte steps)
+      if (c.validity != nullptr) c.validity += at / 8;                                              // (… and whole validity words)
+      if (c.delta_slot >= 0) c.delta_slot = deltas++;
+      if (c.run_values >= 0) c.run_values = runs++;
+      if (c.run_levels >= 0) c.run_levels = runs++;
+      A.cols.push_back(std::move(c));
+      if (!P.x.modes.empty()) A.x.modes.push_back(P.x.modes[k]);
+      if (P.bloom.any()) A.bloom.on.push_back(P.bloom.on[k]);
+    }
+  }
+  A.dict = pqg_plan(groups, rows, &A.cols);
+  A.g = pqw_geometry(rows, P.g.page_rows, A.cols.size());
+  A.n_delta = (size_t)deltas; A.n_runs = (size_t)runs; A.n_compressed = pqw_compressed_columns(A.cols);
+  return A;
+}
+
+std::vector<PqwPlan> pqw_parts(PqwPlan&& plan, const PqwSpec& spec) {
+  std::vector<PqwPlan> parts;
+  const int64_t R = spec.groups != nullptr ? spec.groups->row_group_rows : 0, rows = plan.g.rows;
+  if (R == 0 || rows <= R) { parts.push_back(std::move(plan)); return parts; }
+  const int64_t full = rows / R, rest = rows % R;
+  parts.push_back(pqw_part(plan, spec.groups, 0, full, R, R));
+  if (rest > 0) parts.push_back(pqw_part(plan, spec.groups, full, 1, R, rest));
+  return parts;
 }
 
 void pqb_size(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, PqbPlan* b) {
@@ -667,7 +827,7 @@ void pqb_insert_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
     if (b.on[k] == 0) continue;
     const PqwColumn& c = cols[k];
     const bool index = c.pq_kind != FDB_PQW_V64;
-    const std::vector<uint64_t>& hashes = b.hashes[k];
+    const std::vector<uint64_t>& hashes = b.hashes[c.real];
     const uint32_t per = index ? FDB_PQX_UNIT_INDEX : FDB_PQX_UNIT_V64, n_blocks = b.bytes[k] / FDB_PQB_BLOCK_BYTES;
     unsigned char* bits = table + b.table_off[k];
     for (int64_t p = 0; p < g.n_pages; p++) {
@@ -681,7 +841,7 @@ void pqb_insert_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
             const size_t row = (size_t)first + (size_t)u * per + i;
             uint64_t h;
             if (index) {
-              const uint32_t v = ((const uint32_t*)c.values)[row];
+              const uint32_t v = ((const uint32_t*)pqw_raw(c))[row];
               if (v >= hashes.size()) continue;  // (the survey's to refuse)
               h = hashes[v];
             } else { uint64_t v; std::memcpy(&v, (const unsigned char*)c.values + row * 8, 8); h = fdb_pqb_hash8(v); }
@@ -707,13 +867,34 @@ static std::string pqs_elements_host(const unsigned char* body, size_t n) {
 }
 std::string pqs_block_host(const unsigned char* body, size_t n) { return varint_bytes(n) + pqs_elements_host(body, n); }
 
-PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) {
+PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) { return pqw_layout(std::vector<const PqwPlan*>{&plan}, std::vector<PqwSizes>{sizes}); }
+
+PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector<PqwSizes>& part_sizes) {
   static const std::vector<uint32_t> no_table;
+  if (parts.empty() || parts.size() != part_sizes.size()) throw Error(FDB_ERR_STATE, "parquet write: the layout's tables do not match its parts");
+  size_t n_compressed = 0, compressed_pages = 0, next_compressed = 0;
+  for (const PqwPlan* part : parts) { n_compressed += part->n_compressed; compressed_pages += part->n_compressed * (size_t)part->g.n_pages; }
+  const std::vector<uint32_t>* page_elements = part_sizes[0].page_elements;
+  const bool final_form = page_elements != nullptr;  // else: every page as it is before compression — the file of a record without codecs, the staging image of one with
+  const bool own = final_form || n_compressed == 0;  // the file's own layout: a compressed file's index and filters belong to the final one
+  if (page_elements != nullptr && page_elements->size() != compressed_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of compressed page sizes does not match the record");
+  PqwLayout L;
+  L.parts.resize(parts.size());
+  uint64_t cur = 0;
+  L.put(cur, "PAR1");
+  cur += 4;
+  std::vector<ChunkMeta> chunks;       // in file order: part after part, and in a part group after group, column after column
+  std::vector<size_t> chunk_base;      // per part: its first chunk
+  std::vector<int64_t> group_rows;
+  for (size_t pi = 0; pi < parts.size(); pi++) {
+  const PqwPlan& plan = *parts[pi]; const PqwSizes& sizes = part_sizes[pi];
+  PqwLayout::Part& LP = L.parts[pi];
+  chunk_base.push_back(chunks.size());
+  chunks.resize(chunks.size() + plan.cols.size());
+  for (int64_t gi = 0; gi < plan.n_groups; gi++) group_rows.push_back(plan.g.rows);
   const std::vector<PqwColumn>& cols = plan.cols; const FdbPqwGeom& g = plan.g; const std::vector<FdbPqwPageStat>& stats = sizes.stats;
   const std::vector<uint32_t>& delta_bytes = sizes.delta_bytes != nullptr ? *sizes.delta_bytes : no_table;
-  const std::vector<uint32_t>*page_elements = sizes.page_elements, *run_bytes = sizes.run_bytes;
-  const bool final_form = page_elements != nullptr;  // else: every page as it is before compression — the file of a record without codecs, the staging image of one with
-  const bool own = final_form || plan.n_compressed == 0;  // the file's own layout: a compressed file's index and filters belong to the final one
+  const std::vector<uint32_t>* run_bytes = sizes.run_bytes;
   const PqxIndex* x = own && plan.x.any() ? &plan.x : nullptr;
   const PqbPlan* bloom = own && plan.bloom.any() ? &plan.bloom : nullptr;
   if (bloom != nullptr && bloom->bytes.size() != cols.size()) throw Error(FDB_ERR_STATE, "parquet write: the bloom filter sizes do not match the record");
@@ -721,8 +902,6 @@ PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) {
   if (bounds && (x->table.size() != 2 * stats.size() || x->modes.size() != cols.size())) throw Error(FDB_ERR_STATE, "parquet write: the min / max table does not match the record");
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
   if (delta_bytes.size() != plan.n_delta * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
-  if (page_elements != nullptr && page_elements->size() != plan.n_compressed * (size_t)g.n_pages)
-    throw Error(FDB_ERR_STATE, "parquet write: the table of compressed page sizes does not match the record");
   const size_t n_run_streams = plan.n_runs;
   if ((run_bytes != nullptr ? run_bytes->size() : 0) != n_run_streams * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of run-encoded sizes does not match the record");
   // The bytes of a page's stream cut into runs, held to the rule's bounds: no more than its one bit-packed run, no less than a run.
@@ -732,24 +911,19 @@ PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) {
       throw Error(FDB_ERR_STATE, "parquet write: the run survey sizes a stream of " + std::to_string(n) + " symbols of " + std::to_string(w) + " bits at " + std::to_string(bytes) + " bytes (" + c.name + ")");
     return (uint64_t)bytes;
   };
-  size_t next_compressed = 0;
-  PqwLayout L;
-  L.chunk_off.assign(cols.size(), 0);
-  L.chunk_len.assign(cols.size(), 0);
-  L.delta_out.assign(delta_bytes.size(), FDB_PQW_NONE);
-  L.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
-  L.run_out.assign(n_run_streams * (size_t)g.n_pages, FDB_PQW_NONE);
-  uint64_t cur = 0;
-  L.put(cur, "PAR1");
-  cur += 4;
-  std::vector<ChunkMeta> chunks(cols.size());
+  LP.delta_out.assign(delta_bytes.size(), FDB_PQW_NONE);
+  LP.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
+  LP.run_out.assign(n_run_streams * (size_t)g.n_pages, FDB_PQW_NONE);
   for (size_t k = 0; k < cols.size(); k++) {
     const PqwColumn& c = cols[k];
-    ChunkMeta& m = chunks[k];
+    ChunkMeta& m = chunks[chunk_base[pi] + k];
     const uint64_t chunk_start = cur;
+    m.col = &c; m.start = (int64_t)chunk_start; m.rows = g.rows;
     const bool squeeze = final_form && c.codec != 0;  // this chunk's pages are written as Snappy blocks
+    const unsigned long long* used = c.used_slot >= 0 ? plan.dict.bits.data() + plan.dict.cols[(size_t)c.used_slot].word_off : nullptr;  // the chunk's presence bitmap
+    if (used != nullptr && plan.dict.before.size() != plan.dict.bits.size()) throw Error(FDB_ERR_STATE, "parquet write: the used entries of " + c.name + " have not been counted");
     if (c.pq_kind == FDB_PQW_INDEX) {
-      const std::string body = dictionary_body(*c.dict);
+      const std::string body = used != nullptr ? dictionary_body(*c.dict, used) : dictionary_body(*c.dict);
       const std::string stored = squeeze ? pqs_block_host((const unsigned char*)body.data(), body.size()) : std::string();  // (host bytes already: the header's walk)
       const std::string hdr = page_header(PAGE_DICTIONARY, (int64_t)body.size(), (int64_t)(squeeze ? stored.size() : body.size()), (int64_t)c.entries, ENC_PLAIN);
       m.dict_off = (int64_t)cur;
@@ -794,11 +968,12 @@ PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) {
         encoding = ENC_RLE_DICTIONARY;
         vpre = std::string(1, (char)c.width);
         if (cnt > 0) {
-          if (s.mn > s.mx || s.mx >= c.entries)
-            throw Error(FDB_ERR_INVALID, "parquet write: dictionary index out of range in column " + c.name + ": a valid row holds " + std::to_string(s.mx) + ", the dictionary has " + std::to_string(c.entries) + " entries");
-          if (s.mn == s.mx) {  // one RLE run: the count, the value in ⌈w/8⌉ bytes
+          if (s.mn > s.mx || (used == nullptr && s.mx >= c.entries))  // (a pruned column's range: pqg_resolve has looked)
+            throw Error(FDB_ERR_INVALID, index_out_of_range(c, s.mx, c.entries));
+          if (s.mn == s.mx) {  // one RLE run: the count, the value — of a pruned dictionary the entry's rank — in ⌈w/8⌉ bytes
+            const uint32_t value = used != nullptr ? fdb_pqg_rank(used, plan.dict.before.data() + plan.dict.cols[(size_t)c.used_slot].word_off, s.mn) : s.mn;
             vpre += varint_bytes((uint64_t)cnt << 1);
-            for (uint32_t b = 0; b < (c.width + 7) / 8; b++) vpre.push_back((char)(s.mn >> (8 * b)));
+            for (uint32_t b = 0; b < (c.width + 7) / 8; b++) vpre.push_back((char)(value >> (8 * b)));
           } else if (value_runs) {
             value_payload = run_payload(c, c.run_values, p, cnt, c.width);
           } else {
@@ -824,52 +999,65 @@ PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) {
       const std::string hdr = page_header(PAGE_DATA, (int64_t)body, (int64_t)body, n, encoding);
       m.raw_bytes += (int64_t)(hdr.size() + body);
       if (bounds) m.pages.push_back(PageLoc{cur, hdr.size() + body, n, cnt});
-      FdbPqwPageOut& o = L.out[k * (size_t)g.n_pages + (size_t)p];
+      FdbPqwPageOut& o = LP.out[k * (size_t)g.n_pages + (size_t)p];
       if (c.codec == 0) { L.put(cur, hdr + pre); cur += hdr.size() + pre.size(); }
       else {  // the staging image of a page to be compressed: the host's bytes inside the body are placed on their own, before the compressor runs
         cur += hdr.size();
         L.pages.push_back(PqwLayout::Page{cur, body});
         L.put_body(cur, pre); cur += pre.size();
       }
-      if (level_runs) { L.run_out[(size_t)c.run_levels * (size_t)g.n_pages + (size_t)p] = cur; cur += level_payload; }
+      if (level_runs) { LP.run_out[(size_t)c.run_levels * (size_t)g.n_pages + (size_t)p] = cur; cur += level_payload; }
       else if (level_payload > 0) { o.levels_off = cur; cur += level_payload; }
       if (c.codec == 0) L.put(cur, vpre); else L.put_body(cur, vpre);
       cur += vpre.size();
-      if (value_runs && c.pq_kind == FDB_PQW_INDEX) { L.run_out[(size_t)c.run_values * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }
-      else if (c.delta_slot >= 0) { L.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
+      if (value_runs && c.pq_kind == FDB_PQW_INDEX) { LP.run_out[(size_t)c.run_values * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }
+      else if (c.delta_slot >= 0) { LP.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
       else if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
     }
     m.bytes = (int64_t)(cur - chunk_start);
     m.nulls = g.rows - valid;
-    L.chunk_off[k] = chunk_start;
-    L.chunk_len[k] = cur - chunk_start;
+    L.chunk_off.push_back(chunk_start);
+    L.chunk_len.push_back(cur - chunk_start);
+    L.chunk_codec.push_back(c.codec);
+  }
   }
   L.body_bytes = cur;
-  if (bloom != nullptr) {  // after the last chunk's pages, in column order: header, bitset, no padding
-    for (size_t k = 0; k < cols.size(); k++) {
-      if (bloom->on[k] == 0) continue;
+  const PqwPlan& head = *parts[0];
+  const PqxIndex* x = own && head.x.any() ? &head.x : nullptr;
+  const bool bounds = x != nullptr && x->statistics > 0;
+  // after the last group's pages, in (group, column) order: header, bitset, no padding
+  for (size_t pi = 0; pi < parts.size() && own && head.bloom.any(); pi++) {
+    const PqbPlan& bloom = parts[pi]->bloom;
+    for (size_t k = 0; k < parts[pi]->cols.size(); k++) {
+      if (bloom.on[k] == 0) continue;
+      ChunkMeta& m = chunks[chunk_base[pi] + k];
       unsigned char hdr[FDB_PQB_MAX_HEADER];
-      const uint32_t len = fdb_pqb_header(bloom->bytes[k], hdr);
-      chunks[k].bloom_off = (int64_t)cur; chunks[k].bloom_len = (int64_t)len + bloom->bytes[k];
+      const uint32_t len = fdb_pqb_header(bloom.bytes[k], hdr);
+      m.bloom_off = (int64_t)cur; m.bloom_len = (int64_t)len + bloom.bytes[k];
       L.put(cur, std::string((const char*)hdr, len)); cur += len;
-      L.blooms.push_back(PqwLayout::Bloom{k, cur, bloom->bytes[k]}); cur += bloom->bytes[k];
+      L.blooms.push_back(PqwLayout::Bloom{pi, k, cur, bloom.bytes[k]}); cur += bloom.bytes[k];
     }
-    L.bloom_bytes = cur - L.body_bytes;
   }
-  if (bounds) {  // chunk bounds; with statistics == 2 every column's ColumnIndex, then every column's OffsetIndex, after the pages
-    for (size_t k = 0; k < cols.size(); k++) {
-      const std::string ci = pqx_column_index(cols[k], *x, k, (size_t)g.n_pages, &chunks[k]);
+  L.bloom_bytes = cur - L.body_bytes;
+  // chunk bounds; with statistics == 2 every chunk's ColumnIndex, then every chunk's OffsetIndex, after the pages and the filters
+  for (size_t pi = 0; pi < parts.size() && bounds; pi++) {
+    for (size_t k = 0; k < parts[pi]->cols.size(); k++) {
+      ChunkMeta& m = chunks[chunk_base[pi] + k];
+      const std::string ci = pqx_column_index(parts[pi]->cols[k], parts[pi]->x, k, (size_t)parts[pi]->g.n_pages, &m);
       if (ci.empty()) continue;
-      chunks[k].column_index_off = (int64_t)(cur + L.tail.size()); chunks[k].column_index_len = (int64_t)ci.size();
+      m.column_index_off = (int64_t)(cur + L.tail.size()); m.column_index_len = (int64_t)ci.size();
       L.tail += ci;
     }
-    for (size_t k = 0; k < cols.size() && x->statistics == 2; k++) {
-      const std::string oi = pqx_offset_index(chunks[k], g.page_rows);
-      chunks[k].offset_index_off = (int64_t)(cur + L.tail.size()); chunks[k].offset_index_len = (int64_t)oi.size();
+  }
+  for (size_t pi = 0; pi < parts.size() && bounds && x->statistics == 2; pi++) {
+    for (size_t k = 0; k < parts[pi]->cols.size(); k++) {
+      ChunkMeta& m = chunks[chunk_base[pi] + k];
+      const std::string oi = pqx_offset_index(m, parts[pi]->g.page_rows);
+      m.offset_index_off = (int64_t)(cur + L.tail.size()); m.offset_index_len = (int64_t)oi.size();
       L.tail += oi;
     }
   }
-  L.footer = footer(cols, chunks, g.rows, (int64_t)L.body_bytes, x);
+  L.footer = footer(chunks, head.n_real, group_rows, head.file_rows, x, head.grouped);
   return L;
 }
 
@@ -1107,26 +1295,42 @@ static std::vector<PqwInput> resident_form(const HostRecordView& view, HostResid
 
 // The pipeline with every kernel replaced by its host walk, over columns in host memory — or over a record without rows or columns,
 // which gives the device nothing to do (no data page: the dictionary pages are the host's, compressed or not).
-static void pqw_write_host(PqwPlan& P, uint8_t** bytes, int64_t* n_bytes) {
-  const std::vector<PqwColumn>& cols = P.cols; const FdbPqwGeom& g = P.g;
-  // the survey passes
-  std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> tile_base;
-  pqw_survey_host(cols, g, &stats, &tile_base);
-  if (P.bloom.any()) pqb_size(cols, g, stats, &P.bloom);
-  if (P.x.statistics > 0) pqx_minmax_host(cols, g, &P.x);
-  PqdHost delta; PqrHost rn;
-  pqd_survey_host(cols, g, stats, tile_base, &delta);
-  if (P.n_runs > 0) pqr_survey_host(cols, g, stats, &rn);
-  PqwSizes sizes{stats, &delta.page_bytes, P.n_runs > 0 ? &rn.page_bytes : nullptr, nullptr};
+struct PqwHostPart { std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> tile_base; std::vector<std::vector<uint32_t>> rekeyed; PqdHost delta; PqrHost rn; };
+static void pqw_write_host(std::vector<PqwPlan>& plans, uint8_t** bytes, int64_t* n_bytes) {
+  std::vector<PqwHostPart> host(plans.size());
+  std::vector<const PqwPlan*> parts;
+  std::vector<PqwSizes> sizes;
+  size_t n_compressed = 0;
+  for (size_t pi = 0; pi < plans.size(); pi++) {  // the survey passes
+    PqwPlan& P = plans[pi]; PqwHostPart& h = host[pi];
+    const std::vector<PqwColumn>& cols = P.cols; const FdbPqwGeom& g = P.g;
+    pqw_survey_host(cols, g, &h.stats, &h.tile_base);
+    if (P.x.statistics > 0) pqx_minmax_host(cols, g, &P.x);
+    if (P.dict.any()) {  // the present pass, the used entries counted, the remap pass: from here on a pruned column is its re-keyed copy
+      pqg_present_host(cols, g, &P.dict);
+      pqg_resolve(h.stats, g, &P.cols, &P.dict);
+      pqg_remap_host(cols, g, P.dict, &h.rekeyed);
+      for (size_t slot = 0; slot < P.dict.cols.size(); slot++) { PqwColumn& c = P.cols[P.dict.cols[slot].col]; c.raw_values = c.values; c.values = h.rekeyed[slot].data(); }
+    }
+    if (P.bloom.any()) pqb_size(cols, g, h.stats, &P.bloom);
+    pqd_survey_host(cols, g, h.stats, h.tile_base, &h.delta);
+    if (P.n_runs > 0) pqr_survey_host(cols, g, h.stats, &h.rn);
+    parts.push_back(&P);
+    sizes.push_back(PqwSizes{h.stats, &h.delta.page_bytes, P.n_runs > 0 ? &h.rn.page_bytes : nullptr, nullptr});
+    n_compressed += P.n_compressed;
+  }
   // layout, and the encode passes
-  const PqwLayout L = pqw_layout(P, sizes);
+  const PqwLayout L = pqw_layout(parts, sizes);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
-  pqw_encode_host(cols, g, L.out, tile_base, image.data());
-  pqd_encode_host(cols, g, stats, delta, L.delta_out, image.data());
-  if (P.n_runs > 0) pqr_encode_host(rn, L.run_out, image.data());
+  for (size_t pi = 0; pi < plans.size(); pi++) {
+    const PqwPlan& P = plans[pi]; const PqwHostPart& h = host[pi];
+    pqw_encode_host(P.cols, P.g, L.parts[pi].out, h.tile_base, image.data());
+    pqd_encode_host(P.cols, P.g, h.stats, h.delta, L.parts[pi].delta_out, image.data());
+    if (P.n_runs > 0) pqr_encode_host(h.rn, L.parts[pi].run_out, image.data());
+  }
   // the file's body: the image, or — `image` being the staging image — what the compressor made of it, laid out again and gathered
   PqwLayout F; uint8_t* file = nullptr;
-  if (P.n_compressed == 0) {
+  if (n_compressed == 0) {
     file = pqw_alloc_bytes(L.file_bytes(), false);
     std::memcpy(file, image.data(), (size_t)L.body_bytes);
   } else {
@@ -1137,18 +1341,22 @@ static void pqw_write_host(PqwPlan& P, uint8_t** bytes, int64_t* n_bytes) {
       elements.push_back(pqs_elements_host(image.data() + pg.off, (size_t)pg.body));
       page_elements.push_back((uint32_t)elements.back().size());
     }
-    sizes.page_elements = &page_elements;
-    F = pqw_layout(P, sizes);
+    std::vector<PqwSizes> final_sizes;
+    for (const PqwSizes& z : sizes) final_sizes.push_back(PqwSizes{z.stats, z.delta_bytes, z.run_bytes, &page_elements});
+    F = pqw_layout(parts, final_sizes);
     file = pqw_alloc_bytes(F.file_bytes(), false);
     for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
-    for (size_t k = 0; k < cols.size(); k++)
-      if (cols[k].codec == 0) std::memcpy(file + F.chunk_off[k], image.data() + L.chunk_off[k], (size_t)L.chunk_len[k]);
+    for (size_t k = 0; k < L.chunk_off.size(); k++)
+      if (L.chunk_codec[k] == 0) std::memcpy(file + F.chunk_off[k], image.data() + L.chunk_off[k], (size_t)L.chunk_len[k]);
   }
-  const PqwLayout& at = P.n_compressed == 0 ? L : F;
+  const PqwLayout& at = n_compressed == 0 ? L : F;
   if (!at.blooms.empty()) {  // the insert pass, and every bitset to its place in the file
-    std::vector<unsigned char> bitsets((size_t)P.bloom.table_bytes, 0);
-    pqb_insert_host(cols, g, P.bloom, bitsets.data());
-    for (const PqwLayout::Bloom& f : at.blooms) std::memcpy(file + f.bits_off, bitsets.data() + P.bloom.table_off[f.col], (size_t)f.bytes);
+    std::vector<std::vector<unsigned char>> bitsets;
+    for (const PqwPlan& P : plans) {
+      bitsets.emplace_back((size_t)P.bloom.table_bytes, 0);
+      pqb_insert_host(P.cols, P.g, P.bloom, bitsets.back().data());
+    }
+    for (const PqwLayout::Bloom& f : at.blooms) std::memcpy(file + f.bits_off, bitsets[f.part].data() + plans[f.part].bloom.table_off[f.col], (size_t)f.bytes);
   }
   pqw_finish(at, file);
   *bytes = file; *n_bytes = (int64_t)at.file_bytes();
@@ -1157,8 +1365,8 @@ static void pqw_write_host(PqwPlan& P, uint8_t** bytes, int64_t* n_bytes) {
 void selftest_parquet_write(const HostRecordView& view, const PqwSpec& spec, uint8_t** bytes, int64_t* n_bytes) {
   HostResident keep;
   const std::vector<PqwInput> in = resident_form(view, &keep);  // (owns the dictionaries the plan's columns point at)
-  PqwPlan P = pqw_plan(in, view.rows, spec);
-  pqw_write_host(P, bytes, n_bytes);
+  std::vector<PqwPlan> parts = pqw_parts(pqw_plan(in, view.rows, spec), spec);
+  pqw_write_host(parts, bytes, n_bytes);
 }
 
 #ifndef FDB_PQWRITE_HOST_ONLY
@@ -1170,7 +1378,11 @@ struct PoolBlock {  // an image of the file body in HBM
   ~PoolBlock() { if (p != nullptr) device_pool_free(device, p); }
 };
 
-// One call's side of the device: the plan, its scope, stream and timer, its images (with a compressed column: staging image,
+// What the parts of one call share beside scope, stream and images: the pass queued last, and the device copies of the rank and hash
+// tables, which belong to the record's columns — every group of a column reads the same one.
+struct PqwShared { const char* queued = nullptr; std::vector<const uint32_t*> d_ranks; std::vector<const uint64_t*> d_hashes; };
+
+// One part's side of the device (a call without row groups has one): the plan, its scope, stream and timer, its images (with a compressed column: staging image,
 // scratch, final image), the tables of the survey and of the optional passes (the call's arena) and the host tables its wait fills.
 struct PqwCall {
   PqwPlan& P;
@@ -1178,11 +1390,13 @@ struct PqwCall {
   hipStream_t stream;
   PoolBlock &image, &scratch, &final_image;
   PhaseTimer& pt;  // FDB_PROFILE=1: the passes timed apart (every pass is then waited for on its own)
-  const char* queued = nullptr;  // FDB_PROFILE: the pass queued last and not waited for yet — the name the next wait is marked with
+  PqwShared& shared;
+  const char*& queued;  // FDB_PROFILE: the pass queued last and not waited for yet — the name the next wait is marked with
   size_t items = 0, d_items = 0, r_items = 0;  // columns, DELTA columns, run streams × pages
   const FdbPqwCol* d_cols = nullptr; FdbPqwPageStat* d_stats = nullptr; uint32_t* d_tile_base = nullptr;
   const FdbPqdCol* d_dcols = nullptr; FdbPqdBlock* d_blocks = nullptr; uint32_t* d_page_bytes = nullptr;
   const FdbPqrStream* d_streams = nullptr; uint32_t* d_run_bytes = nullptr; unsigned char* d_bitsets = nullptr;
+  unsigned long long* d_present = nullptr;  // used-entry dictionaries: the table of presence bitmaps
   bool compact = false, run_compact = false;  // a DELTA column / a column whose indices are cut into runs has a bitmap
   std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> delta_bytes, run_bytes;  // what the survey's wait fills
   void wait() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
@@ -1196,7 +1410,7 @@ struct PqwCall {
 };
 
 // The columns as the survey and encode kernels see them, the survey's two tables.
-static void pqw_tables(PqwCall* c) {
+static void pqw_stage_cols(PqwCall* c) {
   const std::vector<PqwColumn>& cols = c->P.cols;
   std::vector<FdbPqwCol> kc(cols.size());
   for (size_t k = 0; k < cols.size(); k++) {
@@ -1204,8 +1418,13 @@ static void pqw_tables(PqwCall* c) {
     kc[k].values = cols[k].values; kc[k].validity = cols[k].validity; kc[k].width = (int32_t)cols[k].width;
     kc[k].kind = cols[k].pq_kind == PQW_NO_VALUES ? FDB_PQW_INDEX : cols[k].pq_kind;
   }
-  c->items = cols.size() * (size_t)c->P.g.n_pages;
   c->d_cols = (const FdbPqwCol*)c->cs.ctx->stage(kc.data(), kc.size() * sizeof(FdbPqwCol));
+}
+
+static void pqw_tables(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  c->items = cols.size() * (size_t)c->P.g.n_pages;
+  pqw_stage_cols(c);
   c->d_stats = (FdbPqwPageStat*)c->cs.alloc(c->items * sizeof(FdbPqwPageStat));
   c->d_tile_base = (uint32_t*)c->cs.alloc(c->items * (size_t)c->P.g.tiles_per_page * 4);
   c->stats.resize(c->items);
@@ -1266,11 +1485,15 @@ static void pqx_minmax_pass(PqwCall* c) {
   for (size_t k = 0; k < cols.size(); k++) {
     std::memset(&xc[k], 0, sizeof(FdbPqxCol));
     xc[k].values = cols[k].values; xc[k].validity = cols[k].validity; xc[k].mode = x.modes[k];
-    const std::vector<uint32_t>& r = x.ranks[k];
+    const std::vector<uint32_t>& r = x.ranks[cols[k].real];
     if (r.empty()) continue;
-    uint32_t* d_ranks = (uint32_t*)c->cs.alloc(r.size() * 4);
-    hip_check(hipMemcpyAsync(d_ranks, r.data(), r.size() * 4, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(dictionary ranks)");  // (the plan outlives the wait)
-    xc[k].ranks = d_ranks; xc[k].rank_len = (uint32_t)r.size();
+    const uint32_t*& shared_ranks = c->shared.d_ranks[cols[k].real];
+    if (shared_ranks == nullptr) {
+      uint32_t* d_ranks = (uint32_t*)c->cs.alloc(r.size() * 4);
+      hip_check(hipMemcpyAsync(d_ranks, r.data(), r.size() * 4, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(dictionary ranks)");  // (the plan outlives the wait)
+      shared_ranks = d_ranks;
+    }
+    xc[k].ranks = shared_ranks; xc[k].rank_len = (uint32_t)r.size();
   }
   const FdbPqxCol* d_xcols = (const FdbPqxCol*)c->cs.ctx->stage(xc.data(), xc.size() * sizeof(FdbPqxCol));
   unsigned long long* d_table = (unsigned long long*)c->cs.alloc(2 * c->items * 8);
@@ -1303,6 +1526,47 @@ static void pqr_survey_pass(PqwCall* c) {
   c->queued = "pqwrite run survey";
 }
 
+// The pruned columns as fdb_pqdict.hip sees them; `before` / `copies`: null for the present pass.
+static const FdbPqgCol* pqg_stage_cols(PqwCall* c, const uint32_t* d_before, const std::vector<uint32_t*>* copies) {
+  const PqgPlan& d = c->P.dict;
+  std::vector<FdbPqgCol> gc(d.cols.size());
+  for (size_t slot = 0; slot < d.cols.size(); slot++) {
+    const PqwColumn& col = c->P.cols[d.cols[slot].col];
+    std::memset(&gc[slot], 0, sizeof(FdbPqgCol));
+    gc[slot].values = (const uint32_t*)(col.raw_values != nullptr ? col.raw_values : col.values); gc[slot].validity = col.validity;
+    gc[slot].bits = c->d_present + d.cols[slot].word_off; gc[slot].entries = (uint32_t)d.cols[slot].entries;
+    if (d_before != nullptr) { gc[slot].before = d_before + d.cols[slot].word_off; gc[slot].out = (*copies)[slot]; }
+  }
+  return (const FdbPqgCol*)c->cs.ctx->stage(gc.data(), gc.size() * sizeof(FdbPqgCol));
+}
+
+// The present pass (fdb_pqdict.hip): behind the survey, into one zeroed table of presence bitmaps, back in the same wait.
+static void pqg_present_pass(PqwCall* c) {
+  PqgPlan& d = c->P.dict;
+  if (c->queued != nullptr) c->settle();
+  const size_t bytes = d.bits.size() * 8;
+  c->d_present = (unsigned long long*)c->cs.alloc(std::max<size_t>(bytes, 8));
+  hip_check(hipMemsetAsync(c->d_present, 0, std::max<size_t>(bytes, 8), c->stream), "hipMemsetAsync(presence bitmaps)");
+  hip_check(fdb_launch_pqg_present(pqg_stage_cols(c, nullptr, nullptr), (int32_t)d.cols.size(), c->P.g, c->stream), "parquet write: dictionary present launch");
+  if (bytes > 0) hip_check(hipMemcpyAsync(d.bits.data(), c->d_present, bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(presence bitmaps)");
+  c->queued = "pqwrite dict present";
+}
+
+// After the wait: the used entries counted (pqg_resolve), their counts up, the remap pass into a re-keyed copy of every pruned column —
+// which is the column from here on, for the table the encode pass reads as well.
+static void pqg_remap_pass(PqwCall* c) {
+  PqgPlan& d = c->P.dict;
+  if (c->queued != nullptr) c->settle();
+  pqg_resolve(c->stats, c->P.g, &c->P.cols, &d);
+  const uint32_t* d_before = (const uint32_t*)c->upload(d.before.data(), d.before.size() * 4, "hipMemcpyAsync(used entry counts)");  // (the plan outlives the wait)
+  std::vector<uint32_t*> copies;
+  for (size_t slot = 0; slot < d.cols.size(); slot++) copies.push_back((uint32_t*)c->cs.alloc(((size_t)c->P.g.rows + 8) * 4));
+  hip_check(fdb_launch_pqg_remap(pqg_stage_cols(c, d_before, &copies), (int32_t)d.cols.size(), c->P.g, c->stream), "parquet write: dictionary remap launch");
+  c->timed("pqwrite dict remap");
+  for (size_t slot = 0; slot < d.cols.size(); slot++) { PqwColumn& col = c->P.cols[d.cols[slot].col]; col.raw_values = col.values; col.values = copies[slot]; }
+  pqw_stage_cols(c);
+}
+
 // The insert pass of fdb_pqbloom.hip, into one zeroed table of bitsets the survey's table has sized.
 static void pqb_insert_pass(PqwCall* c) {
   const std::vector<PqwColumn>& cols = c->P.cols;
@@ -1313,13 +1577,17 @@ static void pqb_insert_pass(PqwCall* c) {
     if (bl.on[k] == 0) continue;
     FdbPqbCol o;
     std::memset(&o, 0, sizeof(FdbPqbCol));
-    o.values = cols[k].values; o.validity = cols[k].validity; o.index = cols[k].pq_kind != FDB_PQW_V64;
+    o.values = pqw_raw(cols[k]); o.validity = cols[k].validity; o.index = cols[k].pq_kind != FDB_PQW_V64;
     o.bits = (unsigned long long*)(c->d_bitsets + bl.table_off[k]); o.n_blocks = bl.bytes[k] / FDB_PQB_BLOCK_BYTES;
-    const std::vector<uint64_t>& h = bl.hashes[k];
+    const std::vector<uint64_t>& h = bl.hashes[cols[k].real];
     if (!h.empty()) {
-      uint64_t* d_hashes = (uint64_t*)c->cs.alloc(h.size() * 8);
-      hip_check(hipMemcpyAsync(d_hashes, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(entry hashes)");  // (the plan outlives the wait)
-      o.hashes = d_hashes; o.hash_len = (uint32_t)h.size();
+      const uint64_t*& shared_hashes = c->shared.d_hashes[cols[k].real];
+      if (shared_hashes == nullptr) {
+        uint64_t* d_hashes = (uint64_t*)c->cs.alloc(h.size() * 8);
+        hip_check(hipMemcpyAsync(d_hashes, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(entry hashes)");  // (the plan outlives the wait)
+        shared_hashes = d_hashes;
+      }
+      o.hashes = shared_hashes; o.hash_len = (uint32_t)h.size();
     }
     bc.push_back(o);
   }
@@ -1329,15 +1597,19 @@ static void pqb_insert_pass(PqwCall* c) {
   c->timed("pqwrite bloom insert");
 }
 
-// The image, zeroed, and the encode passes into it, every payload to where `L` says: the encode pass, then the DELTA and the run encoder.
-static void pqw_encode_passes(PqwCall* c, const PqwLayout& L) {
-  const FdbPqwGeom& g = c->P.g;
-  const size_t image_bytes = align_up((size_t)L.body_bytes + 8, 256);
+// The image, zeroed: once for the call.
+static void pqw_image(PqwCall* c, const PqwLayout& whole) {
+  const size_t image_bytes = align_up((size_t)whole.body_bytes + 8, 256);
   c->image.alloc(image_bytes);
+  hip_check(hipMemsetAsync(c->image.p, 0, image_bytes, c->stream), "hipMemsetAsync(file image)");
+}
+
+// A part's encode passes into the image, every payload to where `L` says: the encode pass, then the DELTA and the run encoder.
+static void pqw_encode_passes(PqwCall* c, const PqwLayout::Part& L) {
+  const FdbPqwGeom& g = c->P.g;
   unsigned char* image = c->image.p;
   FdbPqwPageOut* d_out = (FdbPqwPageOut*)c->cs.alloc(c->items * sizeof(FdbPqwPageOut));
   hip_check(hipMemcpyAsync(d_out, L.out.data(), c->items * sizeof(FdbPqwPageOut), hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(page offsets)");
-  hip_check(hipMemsetAsync(image, 0, image_bytes, c->stream), "hipMemsetAsync(file image)");
   hip_check(fdb_launch_pqw_encode(c->d_cols, g, d_out, c->d_tile_base, image, c->stream), "parquet write: encode launch");
   c->timed("pqwrite encode");
   if (c->P.n_delta > 0) {
@@ -1393,12 +1665,11 @@ static void pqs_compress_pass(PqwCall* c, const PqwLayout& L, PqsTables* t) {
 // ONE gather launch moves the fragments' elements and the chunks of the uncompressed columns from the staging image (`L`) to where the
 // final layout `F` wants them in the final image.
 static void pqs_gather_pass(PqwCall* c, const PqwLayout& L, const PqwLayout& F, PqsTables* t) {
-  const std::vector<PqwColumn>& cols = c->P.cols;
   std::vector<uint64_t>& page_dst = t->page_dst; std::vector<FdbPqsRange>& ranges = t->ranges;
   page_dst.resize(F.pages.size());
   for (size_t i = 0; i < F.pages.size(); i++) page_dst[i] = F.pages[i].off;
-  for (size_t k = 0; k < cols.size(); k++) {  // the chunks of the uncompressed columns, in pieces a workgroup moves at a time
-    if (cols[k].codec != 0) continue;
+  for (size_t k = 0; k < L.chunk_off.size(); k++) {  // the chunks of the uncompressed columns, in pieces a workgroup moves at a time
+    if (L.chunk_codec[k] != 0) continue;
     for (uint64_t at = 0; at < L.chunk_len[k]; at += FDB_PQS_COPY_PIECE)
       ranges.push_back(FdbPqsRange{L.chunk_off[k] + at, F.chunk_off[k] + at, (uint32_t)std::min<uint64_t>(FDB_PQS_COPY_PIECE, L.chunk_len[k] - at), 0});
   }
@@ -1412,11 +1683,12 @@ static void pqs_gather_pass(PqwCall* c, const PqwLayout& L, const PqwLayout& F, 
 }
 
 // The one ending: the pinned file, every bitset straight to its place in it, the image in one parallel copy, the host's holes and tail.
-static size_t pqw_deliver(PqwCall* c, const PqwLayout& at, const void* image, PqwBytes* file) {
+static size_t pqw_deliver(std::vector<PqwCall>& calls, const PqwLayout& at, const void* image, PqwBytes* file) {
+  PqwCall* c = &calls[0];
   const size_t file_bytes = at.file_bytes();
   file->p = pqw_alloc_bytes(file_bytes, true);
   for (const PqwLayout::Bloom& f : at.blooms)
-    hip_check(hipMemcpyAsync(file->p + f.bits_off, c->d_bitsets + c->P.bloom.table_off[f.col], (size_t)f.bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(bloom filter bitset)");
+    hip_check(hipMemcpyAsync(file->p + f.bits_off, calls[f.part].d_bitsets + calls[f.part].P.bloom.table_off[f.col], (size_t)f.bytes, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(bloom filter bitset)");
   if (!at.blooms.empty()) c->timed("pqwrite bloom copy");
   c->cs.ctx->copy_out_parallel(file->p, image, (size_t)at.body_bytes);
   c->pt.mark("pqwrite copy");
@@ -1433,54 +1705,94 @@ void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes
     in.push_back(std::move(o));
   }
   // plan: every refusal of the options, then the device's own two — the min / max and the insert pass load 16 bytes of values at a time
-  PqwPlan P = pqw_plan(in, b.rows, spec);
-  const std::vector<PqwColumn>& cols = P.cols;
-  const bool bounds = P.x.statistics > 0;
-  for (size_t k = 0; k < cols.size() && bounds; k++)
-    if (((uintptr_t)cols[k].values & 15u) != 0) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (statistics)");
-  for (size_t k = 0; k < cols.size() && P.bloom.any(); k++)
-    if (P.bloom.on[k] != 0 && ((uintptr_t)cols[k].values & 15u) != 0)
-      throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (bloom filter)");
-  if (b.rows == 0 || cols.empty()) { pqw_write_host(P, bytes, n_bytes); return; }
+  PqwPlan whole = pqw_plan(in, b.rows, spec);
+  {
+    const std::vector<PqwColumn>& cols = whole.cols;
+    for (size_t k = 0; k < cols.size() && whole.x.statistics > 0; k++)
+      if (((uintptr_t)cols[k].values & 15u) != 0) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (statistics)");
+    for (size_t k = 0; k < cols.size() && whole.bloom.any(); k++)
+      if (whole.bloom.on[k] != 0 && ((uintptr_t)cols[k].values & 15u) != 0)
+        throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[k].name + " are not 16-byte aligned (bloom filter)");
+    for (const PqgPlan::Col& o : whole.dict.cols)
+      if (((uintptr_t)cols[o.col].values & 15u) != 0) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: the values of column " + cols[o.col].name + " are not 16-byte aligned (used-entry dictionary)");
+  }
+  const size_t n_real = whole.n_real;
+  // the call's parts: one, or with several row groups the full groups' and the short last one's — every pass below is launched per part
+  std::vector<PqwPlan> plans = pqw_parts(std::move(whole), spec);
+  if (b.rows == 0 || n_real == 0) { pqw_write_host(plans, bytes, n_bytes); return; }
+  const PqwPlan& head = plans[0];
+  const bool bounds = head.x.statistics > 0, blooms = head.bloom.any();
+  const bool pruned = head.dict.any();  // the run passes then read the re-keyed copies: they follow the remap pass, and the call waits once more
+  size_t n_compressed = 0, n_runs = 0;
+  for (const PqwPlan& P : plans) { n_compressed += P.n_compressed; n_runs += P.n_runs; }
   PqwBytes file;
   PhaseTimer pt;
   PoolBlock image{b.device}, scratch{b.device}, final_image{b.device};  // (before the scope: freed after its wait; the last two: compressed columns only)
   CallScope cs(b.device);
   DrainOnUnwind drain{cs.ctx->stream};
-  PqwCall c{P, cs, cs.ctx->stream, image, scratch, final_image, pt};
-  pqw_tables(&c);
-  if (P.n_delta > 0) pqd_tables(&c);
-  if (P.n_runs > 0) pqr_tables(&c);
+  PqwShared shared;
+  shared.d_ranks.assign(n_real, nullptr); shared.d_hashes.assign(n_real, nullptr);
+  std::vector<PqwCall> calls;
+  for (PqwPlan& P : plans) calls.push_back(PqwCall{P, cs, cs.ctx->stream, image, scratch, final_image, pt, shared, shared.queued});
+  hipStream_t stream = cs.ctx->stream;
+  for (PqwCall& c : calls) {
+    pqw_tables(&c);
+    if (c.P.n_delta > 0) pqd_tables(&c);
+    if (c.P.n_runs > 0 && !pruned) pqr_tables(&c);
+  }
   // the survey passes, their tables back in ONE wait
-  b.note_reader(c.stream);
-  hip_check(fdb_launch_pqw_survey(c.d_cols, P.g, c.d_stats, c.d_tile_base, c.stream), "parquet write: survey launch");
-  hip_check(hipMemcpyAsync(c.stats.data(), c.d_stats, c.items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, c.stream), "hipMemcpyAsync(page table)");
-  c.queued = "pqwrite survey";
-  if (bounds) pqx_minmax_pass(&c);
-  if (P.n_delta > 0) pqd_survey_pass(&c);
-  if (P.n_runs > 0) pqr_survey_pass(&c);
-  c.wait();
-  pt.mark(c.queued != nullptr ? c.queued : "pqwrite wait");
+  b.note_reader(stream);
+  for (PqwCall& c : calls) {
+    if (c.queued != nullptr) c.settle();
+    hip_check(fdb_launch_pqw_survey(c.d_cols, c.P.g, c.d_stats, c.d_tile_base, c.stream), "parquet write: survey launch");
+    hip_check(hipMemcpyAsync(c.stats.data(), c.d_stats, c.items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, c.stream), "hipMemcpyAsync(page table)");
+    c.queued = "pqwrite survey";
+    if (bounds) pqx_minmax_pass(&c);
+    if (c.P.n_delta > 0) pqd_survey_pass(&c);
+    if (pruned) pqg_present_pass(&c);
+    if (c.P.n_runs > 0 && !pruned) pqr_survey_pass(&c);
+  }
+  calls[0].wait();
+  pt.mark(shared.queued != nullptr ? shared.queued : "pqwrite wait");
+  shared.queued = nullptr;
+  if (pruned) {
+    for (PqwCall& c : calls) {
+      pqg_remap_pass(&c);
+      if (c.P.n_runs > 0) { pqr_tables(&c); pqr_survey_pass(&c); }
+    }
+    if (n_runs > 0) {
+      calls[0].wait();
+      pt.mark("pqwrite run survey");
+      shared.queued = nullptr;
+    }
+  }
   // layout: the file's own, or — with a compressed column — the staging image's
-  if (P.bloom.any()) pqb_size(cols, P.g, c.stats, &P.bloom);
-  PqwSizes sizes{c.stats, &c.delta_bytes, P.n_runs > 0 ? &c.run_bytes : nullptr, nullptr};
-  const PqwLayout L = pqw_layout(P, sizes);
+  std::vector<const PqwPlan*> parts;
+  std::vector<PqwSizes> sizes;
+  for (PqwCall& c : calls) {
+    if (blooms) pqb_size(c.P.cols, c.P.g, c.stats, &c.P.bloom);
+    parts.push_back(&c.P);
+    sizes.push_back(PqwSizes{c.stats, &c.delta_bytes, c.P.n_runs > 0 ? &c.run_bytes : nullptr, nullptr});
+  }
+  const PqwLayout L = pqw_layout(parts, sizes);
   pt.mark("pqwrite layout");
   // the encode passes, the filters' insert pass in front of them
-  if (P.bloom.any()) pqb_insert_pass(&c);
-  pqw_encode_passes(&c, L);
+  for (PqwCall& c : calls) if (blooms) pqb_insert_pass(&c);
+  pqw_image(&calls[0], L);
+  for (size_t pi = 0; pi < calls.size(); pi++) pqw_encode_passes(&calls[pi], L.parts[pi]);
   // with a compressed column `image` is the staging image: compress it (the second wait), lay the file out again, gather
-  const bool squeezed = P.n_compressed > 0;
+  const bool squeezed = n_compressed > 0;
   PqwLayout F; PqsTables t;
   if (squeezed) {
-    pqs_compress_pass(&c, L, &t);
-    sizes.page_elements = &t.page_elements;
-    F = pqw_layout(P, sizes);
+    pqs_compress_pass(&calls[0], L, &t);
+    std::vector<PqwSizes> final_sizes;
+    for (const PqwSizes& z : sizes) final_sizes.push_back(PqwSizes{z.stats, z.delta_bytes, z.run_bytes, &t.page_elements});
+    F = pqw_layout(parts, final_sizes);
     pt.mark("pqwrite final layout");
-    pqs_gather_pass(&c, L, F, &t);
+    pqs_gather_pass(&calls[0], L, F, &t);
   }
   // deliver: what crosses the link is the file's own image
-  *n_bytes = (int64_t)pqw_deliver(&c, squeezed ? F : L, squeezed ? final_image.p : image.p, &file);
+  *n_bytes = (int64_t)pqw_deliver(calls, squeezed ? F : L, squeezed ? final_image.p : image.p, &file);
   *bytes = file.p; file.p = nullptr;
 }
 #endif

@@ -10,6 +10,7 @@
 #include "fdb_arrow.h"
 #include "fdb_pqbloom.h"
 #include "fdb_pqdelta.h"
+#include "fdb_pqdict.h"
 #include "fdb_pqruns.h"
 #include "fdb_pqsnappy.h"
 #include "fdb_pqstats.h"
@@ -34,6 +35,7 @@ struct PqwInput {
 
 struct PqwColumn {
   std::string name;
+  size_t real = 0;               // the record's column this one is — itself, or with several row groups the column it is one group's rows of
   int pq_kind = FDB_PQW_V64;     // FDB_PQW_V64 / _BOOL / _INDEX or PQW_NO_VALUES
   int physical = 0;              // parquet Type
   bool is_u64 = false, utf8 = false, optional = false;
@@ -42,6 +44,9 @@ struct PqwColumn {
   int run_values = -1, run_levels = -1;  // >= 0: the pages' indices / definition levels are cut into runs (fdb_pqruns.h), and the stream's place in the tables of that
   uint32_t width = 0;
   uint64_t entries = 0;
+  int used_slot = -1;             // >= 0: the chunk's dictionary keeps the used entries only (fdb_pqdict.h), and the column's place in PqgPlan. Once
+                                  // pqg_resolve has run, `entries` counts the used ones, `width` is theirs and `values` the re-keyed copy
+  const void* raw_values = nullptr;  // … and the indices as the record holds them, which the bloom pass keeps reading
   const HostDict* dict = nullptr;
   const void* values = nullptr;
   const unsigned char* validity = nullptr;  // nullptr: every row counts
@@ -53,9 +58,13 @@ struct PqwLayout {
   struct Piece { uint64_t off; size_t pos, len; };
   std::string blob;
   std::vector<Piece> pieces;
-  std::vector<FdbPqwPageOut> out;
-  std::vector<uint64_t> delta_out;  // [delta_slot × n_pages + page]: where a DELTA page's value bytes start (its `out` says FDB_PQW_NONE for the values)
-  std::vector<uint64_t> run_out;    // [run stream × n_pages + page]: where a stream cut into runs starts (FDB_PQW_NONE: the page's is not; then `out` says where it goes)
+  // Per part of the plan (PqwPlan: one, or with several row groups the full groups and the short last one), in that part's own tables:
+  struct Part {
+    std::vector<FdbPqwPageOut> out;
+    std::vector<uint64_t> delta_out;  // [delta_slot × n_pages + page]: where a DELTA page's value bytes start (its `out` says FDB_PQW_NONE for the values)
+    std::vector<uint64_t> run_out;    // [run stream × n_pages + page]: where a stream cut into runs starts (FDB_PQW_NONE: the page's is not; then `out` says where it goes)
+  };
+  std::vector<Part> parts;
   uint64_t body_bytes = 0;       // PAR1 + column chunks: what the image holds; the footer starts here
   std::string footer;
   void put(uint64_t off, const std::string& s);
@@ -69,13 +78,14 @@ struct PqwLayout {
   std::string body_blob;
   std::vector<Piece> body_pieces;
   std::vector<uint64_t> chunk_off, chunk_len;
+  std::vector<int> chunk_codec;  // (chunks in file order: group after group, column after column)
   void put_body(uint64_t off, const std::string& s);
   // The page index (statistics == 2): every column's ColumnIndex, then every column's OffsetIndex — host bytes that follow the body in
   // the file, before the footer; empty otherwise. The image stays the body.
   std::string tail;
-  // The bloom filters (fdb_pqbloom.h), in column order between the body and the page index: each a header — a piece of `blob` like any
+  // The bloom filters (fdb_pqbloom.h), in (group, column) order between the body and the page index: each a header — a piece of `blob` like any
   // other host byte — and then its bitset, which the insert pass fills and the caller moves to `bits_off`. Empty: none was asked for.
-  struct Bloom { size_t col; uint64_t bits_off, bytes; };
+  struct Bloom { size_t part, col; uint64_t bits_off, bytes; };  // `col`: the column's place in its part
   std::vector<Bloom> blooms;
   uint64_t bloom_bytes = 0;      // headers + bitsets
   size_t file_bytes() const { return (size_t)body_bytes + (size_t)bloom_bytes + tail.size() + footer.size() + 8; }
@@ -86,7 +96,7 @@ struct PqwLayout {
 struct PqbPlan {
   std::vector<int8_t> on;                      // per column: 1 = gets a filter (empty: none does)
   uint32_t bits_per_value = FDB_PQB_DEFAULT_BITS;
-  std::vector<std::vector<uint64_t>> hashes;   // per filtered index column: XXH64 of every entry
+  std::vector<std::vector<uint64_t>> hashes;   // per filtered index column of the RECORD (PqwColumn::real): XXH64 of every entry
   std::vector<uint32_t> bytes;                 // per column: the bitset's bytes (0: no filter)
   std::vector<uint64_t> table_off;             // per column: where its bitset starts in the table (a multiple of 32)
   uint64_t table_bytes = 0;
@@ -109,7 +119,7 @@ struct PqxIndex {
   uint32_t limit = 16;                                // BYTE_ARRAY bounds of the ColumnIndex are cut to this many bytes
   std::vector<fdb_parquet_sorting_column> sorting;
   std::vector<int> modes;                             // per column: FDB_PQX_*
-  std::vector<std::vector<uint32_t>> ranks, entry_of_rank;  // per INDEX column: the dense rank of every entry, and an entry of every rank
+  std::vector<std::vector<uint32_t>> ranks, entry_of_rank;  // per INDEX column of the RECORD (PqwColumn::real; all its groups share them): the dense rank of every entry, and an entry of every rank
   std::vector<uint64_t> table;                        // 2 × columns × pages keys: mins, then maxes
   bool any() const { return statistics > 0 || !sorting.empty(); }
 };
@@ -128,6 +138,7 @@ struct PqwSpec {
   const fdb_parquet_index_options* index = nullptr;
   const fdb_parquet_bloom_options* bloom = nullptr;
   const fdb_parquet_run_options* runs = nullptr;
+  const fdb_parquet_group_options* groups = nullptr;
 };
 // The write options, encodings and codecs of `spec` and the columns checked, every refusal of theirs made (FDB_ERR_INVALID /
 // FDB_ERR_UNSUPPORTED): nothing has been launched yet.
@@ -144,18 +155,47 @@ size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols);
 std::string pqs_block_host(const unsigned char* body, size_t n);
 FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
 
+// Used-entry dictionaries (fdb_parquet_group_options::dictionaries = 1; fdb_pqdict.h): the pruned columns, each with its place in ONE
+// table of presence bitmaps — the present pass's on the device, pqg_present_host's in the self-test — and, once pqg_resolve has looked
+// at the table, the used entries in front of every word and their count.
+struct PqgPlan {
+  struct Col { size_t col; uint64_t entries, word_off, words; uint32_t used = 0; };
+  std::vector<Col> cols;
+  std::vector<unsigned long long> bits;   // the table: every column's bitmap, one after the other
+  std::vector<uint32_t> before;           // per word of the table: the column's used entries in front of it
+  bool any() const { return !cols.empty(); }
+};
+// Every refusal of the group options (FDB_ERR_INVALID): nothing has been launched yet. `groups` == nullptr or all zero: nothing asked.
+// Returns the pruned columns of `cols` — the record's, or one part's virtual columns — their used_slot set.
+PqgPlan pqg_plan(const fdb_parquet_group_options* groups, int64_t rows, std::vector<PqwColumn>* cols);
+// The pass over host arrays: every non-NULL row's index into its column's bitmap of d->bits (zeroed).
+void pqg_present_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, PqgPlan* d);
+// After the wait: an index out of range refused (as the layout would), the used entries counted, d->before made; the columns' `entries`
+// and `width` become the used entries', a column without one takes the form of an empty dictionary. `values` is the caller's to swap.
+void pqg_resolve(const std::vector<FdbPqwPageStat>& stats, const FdbPqwGeom& g, std::vector<PqwColumn>* cols, PqgPlan* d);
+// The pass over host arrays: `out`[slot] = the column's re-keyed indices (rows + 8 of them).
+void pqg_remap_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqgPlan& d, std::vector<std::vector<uint32_t>>* out);
+
 // Everything a call decides before anything is launched: the columns, the geometry, the index and bloom options checked and prepared
 // (modes and ranks; entry hashes), how many columns are DELTA, how many compressed, how many streams are cut into runs. What the
 // passes find later goes into it: x.table (the min / max pass), the filters' sizes (pqb_size).
 struct PqwPlan {
   std::vector<PqwColumn> cols;
   FdbPqwGeom g;
-  PqxIndex x; PqbPlan bloom;
+  PqxIndex x; PqbPlan bloom; PqgPlan dict;
   size_t n_delta = 0, n_compressed = 0, n_runs = 0;
+  bool grouped = false;  // group options that are not all zero: a row group says its ordinal
+  // Several row groups (row_group_rows = R cuts the record): the plan is one PART of the call, over VIRTUAL columns — (group, column),
+  // group after group: the record's column with its buffers starting (first_group + group) · R rows in, a column of a record of g.rows
+  // rows to every pass. One part holds the full groups, a second the shorter last one: at most two launches of a pass, whatever G is.
+  int64_t first_group = 0, n_groups = 1, file_rows = 0;
+  size_t n_real = 0;     // the record's columns: cols.size() == n_groups × n_real
 };
 // THE place that checks a call's options and makes every refusal, in the parameters' order: write options and columns (pqw_columns),
-// index (pqx_plan), bloom (pqb_plan), runs (pqr_plan). Nothing has been launched yet. `in` outlives the plan (its dictionaries).
+// index (pqx_plan), bloom (pqb_plan), runs (pqr_plan), groups (pqg_plan). Nothing has been launched yet. `in` outlives the plan (its dictionaries).
 PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec);
+// The call's parts: the plan itself when the record is one row group, else the full groups' part and, if the last group is shorter, its.
+std::vector<PqwPlan> pqw_parts(PqwPlan&& plan, const PqwSpec& spec);
 // The tables the layout is made from, borrowed (null: no such column or stream). `delta_bytes`[delta_slot × n_pages + page]: the value
 // bytes of a DELTA page, as the block survey found them. `run_bytes`[run stream × n_pages + page]: the bytes of a page's stream cut into
 // runs, as the run survey found them — held to the rule's bounds before they are trusted; looked at only where fdb_pqr_active says the
@@ -169,6 +209,8 @@ struct PqwSizes {
 // The page index, sorting_columns and the bloom filters of the plan are laid out when the layout is the file's own — no compressed
 // column, or `page_elements` given: a staging image has neither.
 PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes);
+// … of a call in parts: `sizes`[i] are parts[i]'s tables; `page_elements`, every part's the same, lists the pages in file order.
+PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector<PqwSizes>& sizes);
 // Fills the holes of `file` (L.file_bytes() long, the payloads in place — the bitsets of L.blooms included) and appends the page index,
 // if any, footer, length and magic.
 void pqw_finish(const PqwLayout& L, uint8_t* file);

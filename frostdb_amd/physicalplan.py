@@ -169,7 +169,7 @@ def lib() -> ctypes.CDLL:
     L.fdb_batch_column_format.argtypes = [vp, i32]
     L.fdb_batch_column_format.restype = ctypes.c_char_p
     for suffix, takes in PARQUET_WRITE_ENTRIES:
-        optional_args = [vp, i32, vp, i32, vp, vp, vp][:takes + min(takes, 2)]  # (encodings and codecs: an array and its length)
+        optional_args = [vp, i32, vp, i32, vp, vp, vp, vp][:takes + min(takes, 2)]  # (encodings and codecs: an array and its length)
         getattr(L, "fdb_batch_to_parquet" + suffix).argtypes = [vp, vp] + optional_args + [P(vp), P(i64)]
         getattr(L, "fdb_selftest_parquet_write" + suffix).argtypes = [vp, vp, vp] + optional_args + [P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
@@ -502,6 +502,27 @@ def _parquet_run_options(runs, names, is_index):
     return ParquetRunOptions(ctypes.cast(arr, ctypes.c_void_p), len(wanted), 0), arr
 
 
+class ParquetGroupOptions(ctypes.Structure):
+    """fdb_parquet_group_options."""
+    _fields_ = [("row_group_rows", ctypes.c_int64), ("dictionaries", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+PARQUET_DICTIONARIES = {None: 0, "whole": 0, "used": 1}
+
+
+def _parquet_group_options(row_group_rows, dictionaries):
+    """`row_group_rows`: 0 (one row group) or the rows per row group, a multiple of 64; `dictionaries`: None / "whole" (every chunk
+    carries the column's whole dictionary) or "used" (only the entries its non-NULL rows refer to). Returns the struct, or None when
+    nothing is asked: the caller then calls what it called without these arguments."""
+    if isinstance(dictionaries, (list, dict, set, tuple)) or dictionaries not in PARQUET_DICTIONARIES or isinstance(dictionaries, bool):
+        _raise(FDB_ERR_INVALID, "parquet write: `dictionaries` is None, 'whole' or 'used', got %r" % (dictionaries,))
+    if isinstance(row_group_rows, bool) or not isinstance(row_group_rows, int) or not -2**63 <= row_group_rows < 2**63:
+        _raise(FDB_ERR_INVALID, "parquet write: row_group_rows must be a multiple of 64 (0: one row group), got %r" % (row_group_rows,))
+    if row_group_rows == 0 and PARQUET_DICTIONARIES[dictionaries] == 0:
+        return None
+    return ParquetGroupOptions(row_group_rows, PARQUET_DICTIONARIES[dictionaries], 0)
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -512,23 +533,24 @@ def _take_bytes(rc, out, n) -> bytes:
 
 
 # The writer's entry points, narrowest first: the suffix of the name, and how many of the optional arguments — encodings, codecs, index
-# options, bloom options, run options, in this order — it takes.
-PARQUET_WRITE_ENTRIES = [("", 0), ("_encoded", 1), ("_compressed", 2), ("_indexed", 3), ("_filtered", 4), ("_runs", 5)]
+# options, bloom options, run options, group options, in this order — it takes.
+PARQUET_WRITE_ENTRIES = [("", 0), ("_encoded", 1), ("_compressed", 2), ("_indexed", 3), ("_filtered", 4), ("_runs", 5), ("_grouped", 6)]
 
 
 def _parquet_write(entry, head, names, is_bool, is_index, asked) -> bytes:
     """`asked`, the options of ResidentBatch.to_parquet / selftest_parquet_write in their order, as the C structures, and the call
     through the NARROWEST of `entry`'s entry points that carries what was asked (`head`: its arguments in front of the options)."""
-    page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs = asked
+    page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries = asked
     opts, _keep = _parquet_write_options(page_rows, optional, names)
     enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
     codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
     index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
     bloom, _keep_bloom = _parquet_bloom_options(bloom_filters, bloom_bits_per_value, names, is_bool, sorting_columns)
     run_opts, _keep_runs = _parquet_run_options(runs, names, is_index)
+    group_opts = _parquet_group_options(row_group_rows, dictionaries)
     optional_args = [(ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc), (ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs)]
-    optional_args += [(ctypes.byref(struct) if struct is not None else None,) for struct in (index, bloom, run_opts)]
-    is_asked = [encodings is not None, compression is not None, index is not None, bloom is not None, run_opts is not None]
+    optional_args += [(ctypes.byref(struct) if struct is not None else None,) for struct in (index, bloom, run_opts, group_opts)]
+    is_asked = [encodings is not None, compression is not None, index is not None, bloom is not None, run_opts is not None, group_opts is not None]
     need = max([i + 1 for i, on in enumerate(is_asked) if on], default=0)
     suffix, takes = next(e for e in PARQUET_WRITE_ENTRIES if e[1] >= need)
     out, n = ctypes.c_void_p(), ctypes.c_int64()
@@ -537,17 +559,18 @@ def _parquet_write(entry, head, names, is_bool, is_index, asked) -> bytes:
 
 
 def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0,
-                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None) -> bytes:
+                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None) -> bytes:
     """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
     made without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
     fdb_selftest_parquet_write_compressed, with `statistics`, `index_size_limit` or `sorting_columns`
     fdb_selftest_parquet_write_indexed, with `bloom_filters` or `bloom_bits_per_value` fdb_selftest_parquet_write_filtered): the same
     layout, headers and footer, the kernels replaced by a host walk of the code they compile. With `runs`
-    fdb_selftest_parquet_write_runs: the run passes walked as well."""
+    fdb_selftest_parquet_write_runs: the run passes walked as well; with `row_group_rows` or `dictionaries`
+    fdb_selftest_parquet_write_grouped: the present and remap passes too."""
     def is_index(t):
         t = t.value_type if pa.types.is_dictionary(t) else t
         return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
-    asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs)
+    asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries)
     with ExportedBatch(record) as ex:
         return _parquet_write("fdb_selftest_parquet_write", [ctypes.addressof(ex.array), ctypes.addressof(ex.schema)], list(record.schema.names),
                               [pa.types.is_boolean(f.type) for f in record.schema], [is_index(f.type) for f in record.schema], asked)
@@ -888,7 +911,7 @@ class ResidentBatch:
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
     def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0, sorting_columns=None,
-                   bloom_filters=None, bloom_bits_per_value: int = 0, runs=None) -> bytes:
+                   bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None) -> bytes:
         """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, data pages V1 of
         `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
@@ -914,8 +937,15 @@ class ResidentBatch:
         into RLE and bit-packed runs instead of one bit-packed run each (the rule: include/frostdb_amd.h) — what a record sorted by
         its label columns asks for, where a label column is long stretches of one index and a dynamic column long stretches of NULL;
         sized and written on the device by two more passes (fdb_batch_to_parquet_runs). No page gets longer. "values" on a column
-        that has no dictionary is refused (True skips such columns). Without it the call is what it was."""
-        asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs)
+        that has no dictionary is refused (True skips such columns). Without it the call is what it was. `dictionaries`: None /
+        "whole" — every chunk carries the column's whole dictionary — or "used": the dictionary page of a dictionary / string column
+        holds only the entries a non-NULL row refers to, in entry order, and the indices are re-keyed to their rank among those and
+        packed at that width — what a record asks for after filter(), take, limit, a sampler or a merge over a dictionary union;
+        found and re-keyed on the device by two more passes (fdb_batch_to_parquet_grouped). `row_group_rows` (≙ WithRowGroupSize;
+        here a multiple of 64): 0 (one row group), or the rows per row group — the last one shorter —, each group with its own pages,
+        statistics, page index, bloom filters and (with "used") dictionaries; from_parquet_many reads them back in one call.
+        Without these two the call is what it was."""
+        asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries)
         return _parquet_write("fdb_batch_to_parquet", [self.handle], self.column_names, [f == "b" for f in self.column_formats],
                               [f not in ("l", "L", "g", "b") for f in self.column_formats], asked)
 

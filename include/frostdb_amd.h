@@ -720,6 +720,42 @@ typedef struct fdb_parquet_run_options {
 FDB_API int fdb_batch_to_parquet_runs(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_runs(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 
+/* … and with dictionaries of USED entries only. After filter(), take, limit, a sampler or a merge over a dictionary union a resident
+ * column refers to a fraction of its dictionary; fdb_batch_to_parquet_runs still writes every entry and packs the indices at the whole
+ * dictionary's width. With `dictionaries` = 1 the dictionary page of a dictionary / string / binary column holds the entries that at
+ * least one non-NULL row refers to, in entry order (entries of equal bytes and different indices both stay when both are used), its
+ * num_values is their count U, every index is re-keyed to its rank among them and the pages are packed at bits(U − 1). A column whose
+ * rows are all NULL takes the form of an empty dictionary: no dictionary page, PLAIN pages of zero values. Statistics, the page index
+ * and the bloom filters are over the same byte values as before; a filter's size is capped by U instead of the dictionary's length.
+ *
+ * Two more passes (fdb_pqdict.hip): behind the survey every non-NULL row's index sets a bit of the column's presence bitmap (one zeroed
+ * table of the call's arena, back in the survey's wait); the host counts the used entries in front of every 64-entry word, and a remap
+ * pass writes a re-keyed copy of the index column (4 bytes a row of the call's arena) that the encode and run passes read from then on.
+ * The run survey needs the re-keyed width, so with `runs` it follows the remap pass and the call waits once more.
+ *
+ * `row_group_rows` (≙ TableConfig.RowGroupSize, table.go:77-80; here a multiple of 64, so that a group starts on a validity word, where
+ * the reference takes any number): rows [g·R, min(rows, (g + 1)·R)) are row group g, the last one shorter; a record of 0 rows keeps its
+ * one zero-row group. A group is cut into pages of page_rows on its own (page_rows need not divide R). The file is PAR1, group after
+ * group and in a group column after column ([dictionary page] data pages), then the bloom filters, then every ColumnIndex, then every
+ * OffsetIndex — each in (group, column) order, first_row_index relative to the group — then the footer: per group what the one RowGroup
+ * of the calls above carries (chunk metadata and statistics over the group's pages only, null_count, num_rows, sizes, file_offset),
+ * sorting_columns repeated, ordinal = g (written under non-zero options only). A bloom filter is per (group, column), sized from the
+ * group's non-NULL rows and capped by the chunk's dictionary length; with `dictionaries` = 1 every group's chunk has the dictionary of
+ * its own rows. With `dictionaries` = 0 a group's chunks are byte for byte those of the file written for its rows alone. No pass is
+ * launched per group: (group, column) is a column of a record of R rows to every kernel, so a pass runs once for the full groups and
+ * once more for a shorter last one, and the call waits no more often than without groups.
+ *
+ * `groups` == NULL or all zero: fdb_batch_to_parquet_runs' path and bytes, no launch, allocation or wait more. Refused before anything
+ * is launched, after everything the calls above refuse: FDB_ERR_INVALID — row_group_rows negative or not a multiple of 64, more than
+ * 32 767 row groups, dictionaries outside 0 … 1, pad != 0. */
+typedef struct fdb_parquet_group_options {
+  int64_t row_group_rows;  /* 0: one row group; else a multiple of 64: rows per row group, the last one shorter */
+  int32_t dictionaries;    /* 0: every chunk carries the column's whole dictionary; 1: only the entries its non-NULL rows refer to */
+  int32_t pad;             /* 0 */
+} fdb_parquet_group_options;
+FDB_API int fdb_batch_to_parquet_grouped(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, const fdb_parquet_group_options* groups /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_grouped(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, const fdb_parquet_group_options* groups /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry
  * point takes HOST buffers, for tests and measurement: `src` holds the compressed pages (pages[i] = {src_off, dst_off, src_len,

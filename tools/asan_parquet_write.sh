@@ -12,6 +12,9 @@
 # value in its column's filter and no bit that no value set.
 # … and with run options at random — per column the dictionary indices, the definition levels, both or none: the run passes' host walk
 # (fdb_pqruns.h), every stream cut into runs decoded by a hybrid reader of the program's own and held to "never longer than packed".
+# … and with group options at random — a row_group_rows that leaves one row group, dictionaries of used entries only: the present and
+# remap passes' host walk (fdb_pqdict.h), every re-keyed index checked, and a dictionary reader of the program's own finds in every
+# pruned chunk exactly the used entries.
 # No GPU, no HIP runtime (fdb_codec.h takes its types from the HIP headers), no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

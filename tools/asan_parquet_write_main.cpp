@@ -295,6 +295,28 @@ static std::string written(const Column& c, int64_t r, bool is_max) {
 }
 
 // The record written with `index`: the tail holds what a loop over the record says, page by page.
+// The dictionary reader: a chunk that starts with a PLAIN dictionary page of exactly the entries `used` of the column's dictionary, in this order.
+static void check_dictionary_page(const std::vector<uint8_t>& chunk, const Column& col, const std::vector<uint32_t>& used) {
+  IndexReader r{chunk};
+  int last = 0, inner = 0;
+  CHECK(r.field(&last) == 5 && last == 1 && unzigzag(r.varint()) == 2);  // PageType DICTIONARY_PAGE
+  CHECK(r.field(&last) == 5 && last == 2); const int64_t body = unzigzag(r.varint());
+  CHECK(r.field(&last) == 5 && last == 3 && unzigzag(r.varint()) == body);
+  CHECK(r.field(&last) == 12 && last == 7);
+  CHECK(r.field(&inner) == 5 && inner == 1 && unzigzag(r.varint()) == (int64_t)used.size());
+  CHECK(r.field(&inner) == 5 && inner == 2 && unzigzag(r.varint()) == 0);  // PLAIN
+  CHECK(r.field(&inner) == 0 && r.field(&last) == 0);
+  const size_t start = r.at;
+  for (uint32_t e : used) {
+    const std::string& v = col.dict->values[e];
+    uint32_t len;
+    CHECK(r.at + 4 <= chunk.size()); std::memcpy(&len, chunk.data() + r.at, 4); r.at += 4;
+    CHECK(len == v.size() && r.at + len <= chunk.size() && std::memcmp(chunk.data() + r.at, v.data(), len) == 0);
+    r.at += len;
+  }
+  CHECK((int64_t)(r.at - start) == body);
+}
+
 static void check_index(const std::vector<Column>& cols, const std::vector<PqwColumn>& pc, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const PqwLayout& L,
                         const PqxIndex& x, const std::vector<uint64_t>& chunk_off, const std::vector<uint64_t>& chunk_len) {
   if (x.statistics < 2) { CHECK(L.tail.empty()); return; }
@@ -423,8 +445,8 @@ static void one_record(uint64_t* seed, int round) {
   const PqwSizes sizes{stats, &dh.page_bytes};
   const PqwLayout L = pqw_layout(plain, sizes);
   std::vector<unsigned char> image(((size_t)L.body_bytes + 8 + 3) / 4 * 4, 0);
-  pqw_encode_host(pc, g, L.out, tile_base, image.data());
-  pqd_encode_host(pc, g, stats, dh, L.delta_out, image.data());
+  pqw_encode_host(pc, g, L.parts[0].out, tile_base, image.data());
+  pqd_encode_host(pc, g, stats, dh, L.parts[0].delta_out, image.data());
   const size_t file_bytes = L.file_bytes();
   CHECK(L.tail.empty());
   uint8_t* file = pqw_alloc_bytes(file_bytes, false);
@@ -441,7 +463,7 @@ static void one_record(uint64_t* seed, int round) {
   for (size_t k = 0; k < n_cols; k++) {
     const Column& c = cols[k];
     for (int64_t p = 0; p < g.n_pages; p++) {
-      const FdbPqwPageOut po = L.out[k * (size_t)g.n_pages + (size_t)p];
+      const FdbPqwPageOut po = L.parts[0].out[k * (size_t)g.n_pages + (size_t)p];
       const FdbPqwPageStat st = stats[k * (size_t)g.n_pages + (size_t)p];
       const int64_t first = fdb_pqw_page_first(g, p), end = fdb_pqw_page_end(g, p);
       uint32_t cnt = 0;
@@ -456,7 +478,7 @@ static void one_record(uint64_t* seed, int round) {
       if (pc[k].delta_slot >= 0) {  // the page's value bytes are the survey's count of them, and decode to the page's non-NULL values
         CHECK(po.values_off == FDB_PQW_NONE);
         const size_t dp = (size_t)pc[k].delta_slot * (size_t)g.n_pages + (size_t)p;
-        const uint64_t off = L.delta_out[dp], bytes = dh.page_bytes[dp];
+        const uint64_t off = L.parts[0].delta_out[dp], bytes = dh.page_bytes[dp];
         for (uint64_t b = 0; b < bytes; b++) { CHECK(off + b < L.body_bytes && owner[off + b] == 0); owner[off + b] = 4; }
         std::vector<uint64_t> want;
         for (int64_t r = first; r < end; r++) if (pc[k].validity == nullptr || c.valid(r)) want.push_back(c.v64[(size_t)r]);
@@ -546,11 +568,11 @@ static void one_record(uint64_t* seed, int round) {
     pqr_survey_host(rc, g, stats, &rh);
     CHECK(rh.page_bytes.size() == n_streams * (size_t)g.n_pages);
     const PqwLayout Rl = pqw_layout(run_plan, PqwSizes{stats, &dh.page_bytes, &rh.page_bytes});
-    CHECK(Rl.body_bytes <= L.body_bytes && Rl.run_out.size() == rh.page_bytes.size());
+    CHECK(Rl.body_bytes <= L.body_bytes && Rl.parts[0].run_out.size() == rh.page_bytes.size());
     std::vector<unsigned char> rimage(((size_t)Rl.body_bytes + 8 + 3) / 4 * 4, 0);
-    pqw_encode_host(rc, g, Rl.out, tile_base, rimage.data());
-    pqd_encode_host(rc, g, stats, dh, Rl.delta_out, rimage.data());
-    pqr_encode_host(rh, Rl.run_out, rimage.data());
+    pqw_encode_host(rc, g, Rl.parts[0].out, tile_base, rimage.data());
+    pqd_encode_host(rc, g, stats, dh, Rl.parts[0].delta_out, rimage.data());
+    pqr_encode_host(rh, Rl.parts[0].run_out, rimage.data());
     for (size_t b = (size_t)Rl.body_bytes; b < rimage.size(); b++) CHECK(rimage[b] == 0);
     std::vector<uint8_t> own(Rl.body_bytes, 0);
     for (const PqwLayout::Piece& p : Rl.pieces) for (size_t b = 0; b < p.len; b++) { CHECK(p.off + b < Rl.body_bytes && own[p.off + b] == 0); own[p.off + b] = 1; }
@@ -566,14 +588,14 @@ static void one_record(uint64_t* seed, int round) {
           const FdbPqwPageStat st = stats[k * (size_t)g.n_pages + (size_t)p];
           const int64_t first = fdb_pqw_page_first(g, p), end = fdb_pqw_page_end(g, p);
           const bool active = fdb_pqr_active(levels, st.count, (uint32_t)(end - first), st.mn, st.mx);
-          CHECK(active == (Rl.run_out[at] != FDB_PQW_NONE) && active == (rh.page_bytes[at] != 0));
+          CHECK(active == (Rl.parts[0].run_out[at] != FDB_PQW_NONE) && active == (rh.page_bytes[at] != 0));
           if (!active) continue;
           std::vector<uint32_t> want;
           for (int64_t r = first; r < end; r++) {
             if (levels) want.push_back(cols[k].valid(r) ? 1u : 0u);
             else if (cols[k].valid(r)) want.push_back(cols[k].idx[(size_t)r]);
           }
-          const uint64_t off = Rl.run_out[at], bytes = rh.page_bytes[at];
+          const uint64_t off = Rl.parts[0].run_out[at], bytes = rh.page_bytes[at];
           size_t packed = 1;  // the one bit-packed run: its header, groups × w bytes
           for (uint64_t v = ((uint64_t)fdb_pqw_groups((uint32_t)want.size()) << 1) | 1; v >= 0x80; v >>= 7) packed++;
           packed += (size_t)fdb_pqw_packed_bytes((uint32_t)want.size(), w);
@@ -584,6 +606,144 @@ static void one_record(uint64_t* seed, int round) {
         }
       }
     }
+  }
+  // … and with group options at random — a row_group_rows that leaves one row group, dictionaries of used entries only — beside the run
+  // options: the present and remap walks (fdb_pqdict.h), and a dictionary reader of the program's own finds in every pruned chunk
+  // exactly the used entries, and in every page the ranks among them
+  {
+    const int64_t whole_words = (rows + 63) / 64 * 64;
+    const fdb_parquet_group_options gopt{rnd(seed) % 3 == 0 ? whole_words + 64 * (int64_t)(rnd(seed) % 3) : 0, (int32_t)(rnd(seed) % 4 != 0), 0};
+    spec.runs = (rnd(seed) & 1) ? &ropt : nullptr; spec.groups = &gopt;
+    PqwPlan used_plan = pqw_plan(in, rows, spec);
+    const bool with_runs = spec.runs != nullptr;
+    spec.runs = nullptr; spec.groups = nullptr;
+    CHECK(used_plan.grouped == (gopt.row_group_rows != 0 || gopt.dictionaries != 0) && used_plan.dict.any() == (gopt.dictionaries == 1 && !used_plan.dict.cols.empty()));
+    PqgPlan& dp = used_plan.dict;
+    std::vector<std::vector<uint32_t>> rekeyed;
+    std::vector<std::vector<uint32_t>> used_entries(n_cols);
+    if (dp.any()) {
+      pqg_present_host(used_plan.cols, g, &dp);
+      pqg_resolve(stats, g, &used_plan.cols, &dp);
+      pqg_remap_host(used_plan.cols, g, dp, &rekeyed);
+      for (size_t slot = 0; slot < dp.cols.size(); slot++) {
+        const size_t k = dp.cols[slot].col;
+        PqwColumn& uc = used_plan.cols[k];
+        CHECK(cols[k].kind == ColKind::DICT && uc.used_slot == (int)slot && rekeyed[slot].size() == (size_t)rows + 8);
+        std::vector<bool> seen(cols[k].dict->values.size(), false);
+        for (int64_t r = 0; r < rows; r++) if (cols[k].valid(r)) seen[cols[k].idx[(size_t)r]] = true;
+        std::vector<uint32_t> rank(seen.size(), 0);
+        for (size_t e = 0; e < seen.size(); e++) if (seen[e]) { rank[e] = (uint32_t)used_entries[k].size(); used_entries[k].push_back((uint32_t)e); }
+        CHECK(dp.cols[slot].used == used_entries[k].size() && uc.entries == used_entries[k].size() && uc.width == (used_entries[k].empty() ? 0 : fdb_pqw_bits(used_entries[k].size() - 1)));
+        CHECK((uc.pq_kind == PQW_NO_VALUES) == used_entries[k].empty());
+        for (int64_t r = 0; r < rows; r++) CHECK(rekeyed[slot][(size_t)r] == (cols[k].valid(r) ? rank[cols[k].idx[(size_t)r]] : 0u));
+        for (size_t r = (size_t)rows; r < rekeyed[slot].size(); r++) CHECK(rekeyed[slot][r] == 0);
+        uc.raw_values = uc.values; uc.values = rekeyed[slot].data();
+      }
+    }
+    const std::vector<PqwColumn>& uc = used_plan.cols;
+    PqrHost rh;
+    if (used_plan.n_runs > 0) pqr_survey_host(uc, g, stats, &rh);
+    CHECK(with_runs || used_plan.n_runs == 0);
+    const PqwLayout U = pqw_layout(used_plan, PqwSizes{stats, &dh.page_bytes, used_plan.n_runs > 0 ? &rh.page_bytes : nullptr});
+    CHECK(U.body_bytes <= L.body_bytes && (used_plan.grouped || with_runs || U.footer == L.footer) && (!used_plan.grouped || with_runs || dp.any() || U.footer.size() == L.footer.size() + 2));
+    std::vector<unsigned char> uimage(((size_t)U.body_bytes + 8 + 3) / 4 * 4, 0);
+    pqw_encode_host(uc, g, U.parts[0].out, tile_base, uimage.data());
+    pqd_encode_host(uc, g, stats, dh, U.parts[0].delta_out, uimage.data());
+    if (used_plan.n_runs > 0) pqr_encode_host(rh, U.parts[0].run_out, uimage.data());
+    for (size_t b = (size_t)U.body_bytes; b < uimage.size(); b++) CHECK(uimage[b] == 0);
+    uint8_t* ufile = pqw_alloc_bytes(U.file_bytes(), false);
+    std::memcpy(ufile, uimage.data(), (size_t)U.body_bytes);
+    pqw_finish(U, ufile);
+    for (const PqgPlan::Col& o : dp.cols) {  // the dictionary reader: the chunk's first page, when there is a used entry, holds exactly those
+      const size_t k = o.col;
+      const std::vector<uint8_t> chunk(ufile + U.chunk_off[k], ufile + U.chunk_off[k] + U.chunk_len[k]);  // (sized exactly)
+      if (used_entries[k].empty()) continue;  // (no dictionary page: the chunk starts with a data page — the run of CHECKs on pq_kind above)
+      check_dictionary_page(chunk, cols[k], used_entries[k]);
+      // the pages the encode pass packed: the ranks at the used entries' width
+      for (int64_t p = 0; p < g.n_pages; p++) {
+        const FdbPqwPageOut po = U.parts[0].out[k * (size_t)g.n_pages + (size_t)p];
+        if (po.values_off == FDB_PQW_NONE) continue;
+        uint64_t j = 0;
+        for (int64_t row = fdb_pqw_page_first(g, p); row < fdb_pqw_page_end(g, p); row++)
+          if (cols[k].valid(row)) { CHECK(read_bits(ufile + po.values_off, j * uc[k].width, uc[k].width) == rekeyed[(size_t)uc[k].used_slot][(size_t)row]); j++; }
+      }
+    }
+    pqw_free_bytes(ufile);
+  }
+  // … and cut into several row groups — row_group_rows a multiple of 64 below the rows, the dictionaries whole or of used entries, runs at
+  // random: the plan's parts (pqw_parts: the full groups as virtual columns, the shorter last group) walked pass by pass as the self-test
+  // walks them, into ONE layout. Every group is then read back: its chunks follow each other from where the group before ended, every
+  // chunk of a dictionary column starts with a dictionary page of exactly the entries its own rows use (or of the whole dictionary), and
+  // every plainly packed index page holds the rows' indices, re-keyed or as they are.
+  if (rows > 64) {
+    const int64_t R = 64 * (1 + (int64_t)(rnd(seed) % (uint64_t)((rows - 1) / 64)));
+    const fdb_parquet_group_options gopt{R, (int32_t)(rnd(seed) & 1), 0};
+    spec.runs = (rnd(seed) & 1) ? &ropt : nullptr; spec.groups = &gopt;
+    std::vector<PqwPlan> plans = pqw_parts(pqw_plan(in, rows, spec), spec);
+    spec.runs = nullptr; spec.groups = nullptr;
+    const int64_t n_groups = (rows + R - 1) / R;
+    CHECK(plans.size() == (rows % R == 0 ? 1u : 2u) && plans[0].n_groups == rows / R && plans[0].g.rows == R && (plans.size() == 1 || (plans[1].n_groups == 1 && plans[1].g.rows == rows % R && plans[1].first_group == rows / R)));
+    struct Walk { std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> tile_base; std::vector<std::vector<uint32_t>> rekeyed; PqdHost delta; PqrHost runs; };
+    std::vector<Walk> walks(plans.size());
+    std::vector<const PqwPlan*> parts;
+    std::vector<PqwSizes> part_sizes;
+    for (size_t pi = 0; pi < plans.size(); pi++) {
+      PqwPlan& P = plans[pi]; Walk& w = walks[pi];
+      CHECK(P.cols.size() == (size_t)P.n_groups * n_cols && P.n_real == n_cols && P.file_rows == rows && P.grouped);
+      pqw_survey_host(P.cols, P.g, &w.stats, &w.tile_base);
+      if (P.dict.any()) {
+        pqg_present_host(P.cols, P.g, &P.dict);
+        pqg_resolve(w.stats, P.g, &P.cols, &P.dict);
+        pqg_remap_host(P.cols, P.g, P.dict, &w.rekeyed);
+        for (size_t slot = 0; slot < P.dict.cols.size(); slot++) { PqwColumn& c = P.cols[P.dict.cols[slot].col]; c.raw_values = c.values; c.values = w.rekeyed[slot].data(); }
+      }
+      pqd_survey_host(P.cols, P.g, w.stats, w.tile_base, &w.delta);
+      if (P.n_runs > 0) pqr_survey_host(P.cols, P.g, w.stats, &w.runs);
+      parts.push_back(&P);
+      part_sizes.push_back(PqwSizes{w.stats, &w.delta.page_bytes, P.n_runs > 0 ? &w.runs.page_bytes : nullptr});
+    }
+    const PqwLayout Gl = pqw_layout(parts, part_sizes);
+    CHECK(Gl.parts.size() == plans.size() && Gl.chunk_off.size() == (size_t)n_groups * n_cols && Gl.chunk_len.size() == Gl.chunk_off.size());
+    std::vector<unsigned char> gimage(((size_t)Gl.body_bytes + 8 + 3) / 4 * 4, 0);
+    for (size_t pi = 0; pi < plans.size(); pi++) {
+      pqw_encode_host(plans[pi].cols, plans[pi].g, Gl.parts[pi].out, walks[pi].tile_base, gimage.data());
+      pqd_encode_host(plans[pi].cols, plans[pi].g, walks[pi].stats, walks[pi].delta, Gl.parts[pi].delta_out, gimage.data());
+      if (plans[pi].n_runs > 0) pqr_encode_host(walks[pi].runs, Gl.parts[pi].run_out, gimage.data());
+    }
+    for (size_t b = (size_t)Gl.body_bytes; b < gimage.size(); b++) CHECK(gimage[b] == 0);
+    uint8_t* gfile = pqw_alloc_bytes(Gl.file_bytes(), false);
+    std::memcpy(gfile, gimage.data(), (size_t)Gl.body_bytes);
+    pqw_finish(Gl, gfile);
+    uint64_t at = 4;
+    for (int64_t gi = 0; gi < n_groups; gi++) {
+      const size_t pi = gi < plans[0].n_groups ? 0 : 1;
+      const PqwPlan& P = plans[pi];
+      const int64_t first = gi * R, end = std::min(rows, first + R);
+      for (size_t k = 0; k < n_cols; k++) {
+        const size_t chunk_at = (size_t)gi * n_cols + k, vk = (size_t)(gi - P.first_group) * n_cols + k;
+        CHECK(Gl.chunk_off[chunk_at] == at && Gl.chunk_len[chunk_at] > 0 && at + Gl.chunk_len[chunk_at] <= Gl.body_bytes);
+        at += Gl.chunk_len[chunk_at];
+        if (cols[k].kind != ColKind::DICT) continue;
+        const PqwColumn& vc = P.cols[vk];
+        CHECK(vc.real == k);
+        std::vector<bool> seen(cols[k].dict->values.size(), gopt.dictionaries == 0);
+        for (int64_t r = first; r < end; r++) if (cols[k].valid(r)) seen[cols[k].idx[(size_t)r]] = true;
+        std::vector<uint32_t> used, rank(seen.size(), 0);
+        for (size_t e = 0; e < seen.size(); e++) if (seen[e]) { rank[e] = (uint32_t)used.size(); used.push_back((uint32_t)e); }
+        CHECK(vc.entries == used.size() && (vc.pq_kind == PQW_NO_VALUES) == used.empty() && vc.width == (used.empty() ? 0 : fdb_pqw_bits(used.size() - 1)));
+        if (used.empty()) continue;
+        check_dictionary_page(std::vector<uint8_t>(gfile + Gl.chunk_off[chunk_at], gfile + Gl.chunk_off[chunk_at] + Gl.chunk_len[chunk_at]), cols[k], used);
+        for (int64_t p = 0; p < P.g.n_pages; p++) {
+          const FdbPqwPageOut po = Gl.parts[pi].out[vk * (size_t)P.g.n_pages + (size_t)p];
+          if (po.values_off == FDB_PQW_NONE) continue;
+          uint64_t j = 0;
+          for (int64_t row = first + fdb_pqw_page_first(P.g, p); row < first + fdb_pqw_page_end(P.g, p); row++)
+            if (cols[k].valid(row)) { CHECK(read_bits(gfile + po.values_off, j * vc.width, vc.width) == rank[cols[k].idx[(size_t)row]]); j++; }
+        }
+      }
+    }
+    CHECK(at == Gl.body_bytes);
+    pqw_free_bytes(gfile);
   }
   // the same record with a codec per column at random (three rounds in four): what fdb_selftest_parquet_write_compressed does, step by step
   std::vector<int8_t> codecs;
@@ -699,6 +859,11 @@ static void refusals() {
   CHECK(run_code(fdb_parquet_run_options{&delta, 1, 0}) == FDB_ERR_UNSUPPORTED && run_code(fdb_parquet_run_options{&bad, 1, 0}) == FDB_ERR_UNSUPPORTED);  // bit 0 on an int64 column
   CHECK(run_code(fdb_parquet_run_options{&four, 1, 0}) == FDB_ERR_INVALID && run_code(fdb_parquet_run_options{&minus, 1, 0}) == FDB_ERR_INVALID);
   CHECK(run_code(fdb_parquet_run_options{both, 2, 0}) == FDB_ERR_INVALID && run_code(fdb_parquet_run_options{nullptr, 1, 0}) == FDB_ERR_INVALID);
+  const auto group_code = [&](const fdb_parquet_group_options& o, int64_t rows) { try { std::vector<PqwColumn> c = pqw_columns(in, 8, PqwSpec{&plain_opt}, &pr); pqg_plan(&o, rows, &c); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
+  CHECK(group_code(fdb_parquet_group_options{0, 0, 0}, 8) == FDB_OK && group_code(fdb_parquet_group_options{64, 1, 0}, 64) == FDB_OK && group_code(fdb_parquet_group_options{128, 0, 0}, 0) == FDB_OK);
+  CHECK(group_code(fdb_parquet_group_options{-64, 0, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{63, 0, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{64, 0, 0}, 64 * 32767 + 1) == FDB_ERR_INVALID);
+  CHECK(group_code(fdb_parquet_group_options{0, 2, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{0, -1, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{0, 1, 1}, 8) == FDB_ERR_INVALID);
+  CHECK(group_code(fdb_parquet_group_options{64, 0, 0}, 65) == FDB_OK && group_code(fdb_parquet_group_options{64, 1, 0}, 64 * 32767) == FDB_OK);  // several row groups, as many as an ordinal can say
   in[0].kind = ColKind::F64;
   CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED && bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_OK);
   in[0].kind = ColKind::BOOL;

@@ -39,9 +39,21 @@ record in the same process goes into the line as with --delta, with plain_floor_
 The UNSORTED record, whose columns have no stretches and for which the run survey is pure cost, is written both ways as well:
 unsorted_file_bytes / unsorted_to_parquet_ms / unsorted_run_survey_ms / unsorted_run_encode_ms against unsorted_plain_file_bytes /
 unsorted_plain_to_parquet_ms and its _min_ms / _max_ms.
+With --used the record is written uncompressed with dictionaries="used" (fdb_batch_to_parquet_grouped): every label column's dictionary
+page holds the used entries only and its indices are re-keyed and packed at that width. The line's own figures are that call's — among
+the phases dict_present_ms (bitmaps zeroed, the present pass of fdb_pqdict.hip, with the wait for the survey's tables and the bitmaps) and
+dict_remap_ms (counts up, the remap pass), each also as a rate over the label columns' index bytes (4 B a row and column read; the remap
+pass writes as many) against read_ceiling_gbs, the plain read kernel of the same run — and the call with the whole dictionaries on the
+same record in the same process goes into the line as with --delta, with plain_floor_ms. --fraction F (default 1: the record as it is,
+every entry used, the two passes pure cost) makes the label columns name only every ⌈1/F⌉-th entry of their dictionaries, what a filter
+on another column leaves.
+With --groups R the record is written in row groups of R rows (fdb_batch_to_parquet_grouped, row_group_rows = R; uncompressed, alone or
+with --used): ⌈rows / R⌉ row groups, every pass launched once for the full groups and once more for a shorter last one. The line's own
+figures are the grouped call's — its phases are the SUM of a call's marks, both launches — with row_groups, and the ungrouped call of the
+parent path on the same record in the same process goes into the line as with --delta, with its spread and plain_floor_ms.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats | --bloom | --runs] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats | --bloom | --runs | [--used [--fraction F]] [--groups R]] [--out FILE]
 """
 import argparse
 import io
@@ -70,14 +82,18 @@ STATS_PHASES = ["stats", "wait"]
 BLOOM_PHASES = ["bloom insert", "bloom copy"]
 BLOOM_COLUMNS = ["timestamp", "labels.l4"]
 RUN_PHASES = ["run survey", "run encode"]
+DICT_PHASES = ["dict present", "dict remap"]
 
 
-def make_record(rows: int, seed: int = 1) -> pa.RecordBatch:
+def make_record(rows: int, seed: int = 1, fraction: float = 1.0) -> pa.RecordBatch:
     rng = np.random.default_rng(seed)
     cols = [pa.array(np.cumsum(rng.integers(0, 2000, rows, dtype=np.int64))), pa.array(rng.standard_normal(rows), mask=rng.random(rows) < 0.05)]
     names = ["timestamp", "value"]
     for k, entries in enumerate(LABELS):
         idx = rng.integers(0, entries, rows).astype(np.uint32)
+        if fraction < 1.0:
+            step = int(np.ceil(1.0 / fraction))
+            idx = idx // step * step
         if k == 0:
             idx = np.sort(idx)
         values = pa.array(["label-%d-value-%04d" % (k, e) for e in range(entries)], type=pa.string())
@@ -97,8 +113,9 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None, runs=None):
-    """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms}."""
+def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None, runs=None, dictionaries=None, groups=0):
+    """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms} — with `groups`, where a call marks a pass once
+    per launch, the marks' sum per call."""
     os.environ["FDB_PROFILE"] = "1"
     sys.stderr.flush()
     saved = os.dup(2)
@@ -106,7 +123,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs, dictionaries=dictionaries, row_group_rows=groups)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -114,9 +131,9 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES + DICT_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
-        out[phase] = statistics.median(us) / 1e3 if us else None
+        out[phase] = (sum(us) / reps if groups else statistics.median(us)) / 1e3 if us else None
     return out
 
 
@@ -132,10 +149,15 @@ def main():
     ap.add_argument("--stats", action="store_true", help="write statistics and the page index (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--bloom", action="store_true", help="write bloom filters on `timestamp` and `labels.l4` (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--runs", action="store_true", help="sort the record by its label columns and write it with runs=True (uncompressed); the call without runs, and both calls on the unsorted record, go into the same line")
+    ap.add_argument("--used", action="store_true", help="write dictionaries of used entries only (uncompressed); the call with the whole dictionaries goes into the same line")
+    ap.add_argument("--fraction", type=float, default=1.0, help="with --used: the label columns name only every ceil(1/F)-th entry of their dictionaries")
+    ap.add_argument("--groups", type=int, default=0, help="write row groups of this many rows (a multiple of 64; alone or with --used); the ungrouped call goes into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert args.delta + args.snappy + args.stats + args.bloom + args.runs <= 1, "--delta, --snappy, --stats, --bloom or --runs"
-    record = make_record(args.rows)
+    assert args.delta + args.snappy + args.stats + args.bloom + args.runs + args.used <= 1, "--delta, --snappy, --stats, --bloom, --runs or --used"
+    assert 0.0 < args.fraction <= 1.0 and (args.used or args.fraction == 1.0), "--fraction goes with --used"
+    assert args.groups == 0 or (args.groups > 0 and args.groups % 64 == 0 and args.delta + args.snappy + args.stats + args.bloom + args.runs == 0), "--groups R: a multiple of 64, alone or with --used"
+    record = make_record(args.rows, fraction=args.fraction)
     rb = pp.ResidentBatch(record)
     del record
     unsorted = None
@@ -147,10 +169,12 @@ def main():
         stats = "page" if args.stats else None
         bloom = BLOOM_COLUMNS if args.bloom else None
         runs = True if args.runs else None
-        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs)
+        dictionaries = "used" if args.used else None
+        data = rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs, dictionaries=dictionaries, row_group_rows=args.groups)
         file_bytes = len(data)
         md = pq.ParquetFile(io.BytesIO(data)).metadata
-        assert md.num_rows == args.rows and md.num_row_groups == 1
+        row_groups = -(-args.rows // args.groups) if args.groups else 1
+        assert md.num_rows == args.rows and md.num_row_groups == row_groups
         if args.delta or args.snappy:
             assert set(md.row_group(0).column(0).encodings) == {"DELTA_BINARY_PACKED"}
         if args.snappy:
@@ -158,8 +182,8 @@ def main():
             column_bytes = {md.row_group(0).column(j).path_in_schema: [md.row_group(0).column(j).total_compressed_size, md.row_group(0).column(j).total_uncompressed_size] for j in range(md.num_columns)}
         if args.stats:
             assert all(md.row_group(0).column(j).has_column_index and md.row_group(0).column(j).has_offset_index and md.row_group(0).column(j).statistics.has_min_max for j in range(md.num_columns))
-        if args.runs:
-            column_bytes = {md.row_group(0).column(j).path_in_schema: md.row_group(0).column(j).total_compressed_size for j in range(md.num_columns)}
+        if args.runs or args.used or args.groups:
+            column_bytes = {md.row_group(0).column(j).path_in_schema: sum(md.row_group(g).column(j).total_compressed_size for g in range(row_groups)) for j in range(md.num_columns)}
         if args.bloom:
             filters = {md.row_group(0).column(j).path_in_schema: md.row_group(0).column(j).to_dict().get("bloom_filter_length") for j in range(md.num_columns)}
             assert all((filters[n] is not None) == (n in BLOOM_COLUMNS) for n in filters), filters
@@ -178,9 +202,13 @@ def main():
 
         run_opts, _keep_runs = pp._parquet_run_options(True, names, [n.startswith("labels.") for n in names])
 
-        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats, filtered=args.bloom, run_encoded=args.runs, handle=None):
+        group_opts = pp.ParquetGroupOptions(args.groups, 1 if args.used else 0, 0)
+
+        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats, filtered=args.bloom, run_encoded=args.runs, handle=None, used=args.used or args.groups > 0):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
-            if run_encoded:
+            if used:
+                rc = pp.lib().fdb_batch_to_parquet_grouped(rb.handle, ctypes.byref(opts), None, 0, None, 0, None, None, None, ctypes.byref(group_opts), ctypes.byref(out), ctypes.byref(n))
+            elif run_encoded:
                 rc = pp.lib().fdb_batch_to_parquet_runs(handle or rb.handle, ctypes.byref(opts), None, 0, None, 0, None, None, ctypes.byref(run_opts), ctypes.byref(out), ctypes.byref(n))
             elif handle is not None:
                 rc = pp.lib().fdb_batch_to_parquet(handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
@@ -198,19 +226,19 @@ def main():
             assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
         plain = {}
-        if args.delta or args.snappy or args.stats or args.bloom or args.runs:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+        if args.delta or args.snappy or args.stats or args.bloom or args.runs or args.used or args.groups:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
             plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
-            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False, False, False), args.reps, args.warmup)
+            ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False, False, False, None, False), args.reps, args.warmup)
             ph = profiled_phases(rb, args.page_rows, args.reps)
             plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
             plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
-        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs), args.reps, 1)
-        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats, bloom, runs)
+        python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs, dictionaries=dictionaries, row_group_rows=args.groups), args.reps, 1)
+        phases = profiled_phases(rb, args.page_rows, args.reps, encodings, compression, stats, bloom, runs, dictionaries, args.groups)
         if args.runs:  # the record as it was before the sort: no stretches, the run passes are pure cost
             u_bytes, u_plain_bytes = len(unsorted.to_parquet(page_rows=args.page_rows, runs=True)), len(unsorted.to_parquet(page_rows=args.page_rows))
-            u_plain_ms, u_plain_all = median_ms(lambda: c_call(False, u_plain_bytes, False, False, False, False, unsorted.handle), args.reps, args.warmup)
-            u_ms, u_all = median_ms(lambda: c_call(False, u_bytes, False, False, False, True, unsorted.handle), args.reps, args.warmup)
+            u_plain_ms, u_plain_all = median_ms(lambda: c_call(False, u_plain_bytes, False, False, False, False, unsorted.handle, False), args.reps, args.warmup)
+            u_ms, u_all = median_ms(lambda: c_call(False, u_bytes, False, False, False, True, unsorted.handle, False), args.reps, args.warmup)
             u_phases = profiled_phases(unsorted, args.page_rows, args.reps, runs=True)
             plain.update({"unsorted_file_bytes": u_bytes, "unsorted_plain_file_bytes": u_plain_bytes, "unsorted_to_parquet_ms": u_ms, "unsorted_to_parquet_min_ms": min(u_all),
                           "unsorted_to_parquet_max_ms": max(u_all), "unsorted_plain_to_parquet_ms": u_plain_ms, "unsorted_plain_to_parquet_min_ms": min(u_plain_all),
@@ -226,7 +254,8 @@ def main():
                 torch.cuda.synchronize()
             return median_ms(bare_copy, args.reps, args.warmup)[0]
         floor_ms = bare_copy_ms(file_bytes)
-        if args.snappy or args.runs:
+        read_ceiling = pp.read_ceiling(0, 2 << 30, 5) if args.used else None
+        if args.snappy or args.runs or args.used or args.groups:
             plain["plain_floor_ms"] = bare_copy_ms(plain["plain_file_bytes"])
 
         label_names = ["labels.l%d" % k for k in range(len(LABELS))]
@@ -268,7 +297,15 @@ def main():
     if args.runs:
         line.update({"runs": "all", "sorted_by": ["labels.l%d" % k for k in range(len(LABELS))] + ["timestamp"], "to_parquet_max_ms": r3(max(to_parquet_all)),
                      "run_survey_ms": r3(phases["run survey"]), "run_encode_ms": r3(phases["run encode"]), "column_bytes": column_bytes})
-    if args.delta or args.snappy or args.stats or args.bloom or args.runs:
+    if args.used:
+        index_bytes = 4 * args.rows * len(LABELS)
+        rate = lambda ms: None if not ms else round(index_bytes / (ms * 1e-3) / 1e9, 1)  # noqa: E731
+        line.update({"dictionaries": "used", "fraction": args.fraction, "to_parquet_max_ms": r3(max(to_parquet_all)), "dict_present_ms": r3(phases["dict present"]), "dict_remap_ms": r3(phases["dict remap"]),
+                     "index_bytes": index_bytes, "dict_present_read_gbs": rate(phases["dict present"]), "dict_remap_read_gbs": rate(phases["dict remap"]), "read_ceiling_gbs": round(read_ceiling, 1),
+                     "column_bytes": column_bytes})
+    if args.groups:
+        line.update({"row_group_rows": args.groups, "row_groups": row_groups, "to_parquet_max_ms": r3(max(to_parquet_all)), "column_bytes": column_bytes})
+    if args.delta or args.snappy or args.stats or args.bloom or args.runs or args.used or args.groups:
         line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
