@@ -855,6 +855,7 @@ int fdb_lz4_decode_pages(const uint8_t* src, int64_t src_bytes, const fdb_lz4_pa
 
 int64_t fdb_batch_num_rows(const fdb_batch* batch) { return batch ? batch->b->rows : 0; }
 int64_t fdb_batch_device_bytes(const fdb_batch* batch) { return batch ? (int64_t)batch->b->arena_bytes : 0; }
+int64_t fdb_batch_scan_cache_bytes(const fdb_batch* batch) { return batch ? batch->b->scan_cache_bytes() : 0; }
 void fdb_batch_release(fdb_batch* batch) { delete batch; }
 
 int fdb_plan_stats(fdb_plan* plan, int64_t* algorithmic_bytes, double* kernel_ms, int64_t* n_launches, int64_t* rows_scanned) {

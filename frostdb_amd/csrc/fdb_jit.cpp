@@ -49,6 +49,7 @@ const char* kKernelsHeader =
 const char* kPreamble = R"HIP(
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define G1 __attribute__((address_space(1)))
 template <typename T> __device__ __forceinline__ const G1 T* as_global(const T* p) { return (const G1 T*)p; }
 __device__ __forceinline__ long long f64_to_ordered(double d) { long long b = __double_as_longlong(d); return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL); }
@@ -66,7 +67,20 @@ __device__ __forceinline__ u32x4 ld4(const void* base, uint32_t byte_off) {
 __device__ __forceinline__ u64x2 ld8(const void* base, uint32_t byte_off) {
   return *as_global(reinterpret_cast<const u64x2*>(reinterpret_cast<const char*>(base) + byte_off));
 }
+// (narrow-index caches, fdb_record.h: a lane's four indices at 1 / 2 bytes each — one 4- / 8-byte load, contiguous across the wave)
+__device__ __forceinline__ uint32_t ld1raw(const void* base, uint32_t byte_off) {
+  return *as_global(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + byte_off));
+}
+__device__ __forceinline__ u32x2 ld2raw(const void* base, uint32_t byte_off) {
+  return *as_global(reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(base) + byte_off));
+}
 #else
+__device__ __forceinline__ uint32_t ld1raw(const void* base, uint32_t byte_off) {
+  return __builtin_nontemporal_load(as_global(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + byte_off)));
+}
+__device__ __forceinline__ u32x2 ld2raw(const void* base, uint32_t byte_off) {
+  return __builtin_nontemporal_load(as_global(reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(base) + byte_off)));
+}
 __device__ __forceinline__ u32x4 ld4(const void* base, uint32_t byte_off) {
   return __builtin_nontemporal_load(as_global(reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(base) + byte_off)));
 }
@@ -74,6 +88,17 @@ __device__ __forceinline__ u64x2 ld8(const void* base, uint32_t byte_off) {
   return __builtin_nontemporal_load(as_global(reinterpret_cast<const u64x2*>(reinterpret_cast<const char*>(base) + byte_off)));
 }
 #endif
+// … unpacked into the register form the rest of the kernel consumes
+__device__ __forceinline__ u32x4 ld1x4(const void* base, uint32_t byte_off) {
+  const uint32_t v = ld1raw(base, byte_off);
+  u32x4 r; r.x = v & 0xFFu; r.y = (v >> 8) & 0xFFu; r.z = (v >> 16) & 0xFFu; r.w = v >> 24;
+  return r;
+}
+__device__ __forceinline__ u32x4 ld2x4(const void* base, uint32_t byte_off) {
+  const u32x2 v = ld2raw(base, byte_off);
+  u32x4 r; r.x = v.x & 0xFFFFu; r.y = v.x >> 16; r.z = v.y & 0xFFFFu; r.w = v.y >> 16;
+  return r;
+}
 __device__ __forceinline__ uint32_t ldv(const uint8_t* bm, uint32_t byte_off, uint32_t shift) { return (as_global(bm)[byte_off] >> shift) & 0xFu; }
 // dictionary truth table in a 64-bit immediate: 4 rows → 4-bit mask (NULL rows look up entry `null_at`)
 __device__ __forceinline__ uint32_t leaf_bits(u32x4 idx, uint32_t valid, unsigned long long bits, uint32_t null_at) {
@@ -222,7 +247,9 @@ struct Gen {
     for (int i = 0; i < n4; i++) {
       const JitSlot& c = late ? s.l4[i] : s.c4[i];
       const std::string r = reg(false, late, i);
-      if (c.has_values) o << "    const u32x4 " << r << " = ld4(P_" << r << "_v + tile_off4, lane_off4);\n";
+      if (c.has_values && c.width == 1) o << "    const u32x4 " << r << " = ld1x4(P_" << r << "_v + tile_off1, lane_off1);\n";
+      else if (c.has_values && c.width == 2) o << "    const u32x4 " << r << " = ld2x4(P_" << r << "_v + tile_off2, lane_off2);\n";
+      else if (c.has_values) o << "    const u32x4 " << r << " = ld4(P_" << r << "_v + tile_off4, lane_off4);\n";
       mask(c, r);
     }
     for (int i = 0; i < n8; i++) {
@@ -236,10 +263,16 @@ struct Gen {
     }
   }
 
+  // fdb_plan_kernel: `live` = the lane's rows that exist. A tail lane loads up to three rows past the record's last one, and nothing
+  // says what a column's pad or a bitmap's last bits hold (a pool block keeps what its last owner wrote): without the mask such a row's
+  // "index" went into the LUT gathers, and a LUT too big for LDS is gathered from global memory — anywhere within 4 GiB behind it.
+  bool live_mask = false;
   void mask(const JitSlot& c, const std::string& r) {
-    if (c.has_validity == 1) o << "    const uint32_t " << r << "_m = ldv(P_" << r << "_b + tile_offb, lane_offb, lane_shb);\n";
-    else if (c.has_validity == 2) o << "    const uint32_t " << r << "_m = P_" << r << "_b != nullptr ? ldv(P_" << r << "_b + tile_offb, lane_offb, lane_shb) : 0xFu;\n";
-    else o << "    const uint32_t " << r << "_m = 0xFu;\n";
+    const char* all = live_mask ? "live" : "0xFu";
+    const char* cut = live_mask ? " & live" : "";
+    if (c.has_validity == 1) o << "    const uint32_t " << r << "_m = ldv(P_" << r << "_b + tile_offb, lane_offb, lane_shb)" << cut << ";\n";
+    else if (c.has_validity == 2) o << "    const uint32_t " << r << "_m = P_" << r << "_b != nullptr ? ldv(P_" << r << "_b + tile_offb, lane_offb, lane_shb)" << cut << " : " << all << ";\n";
+    else o << "    const uint32_t " << r << "_m = " << all << ";\n";
   }
 
   std::string leaf_expr(int l) { return leaf_expr_of(s.leaves[l], l, reg(s.leaves[l].wide, false, s.leaves[l].slot)); }
@@ -346,6 +379,7 @@ struct Gen {
     }
     o << "  long long n_rows = 0, tile_begin = 0, tile_end = 0; int part = -1, lut_class = -1;\n";
     o << "  const uint32_t lane_off4 = tid * 16u, lane_off8 = tid * 32u, lane_offb = tid >> 1, lane_shb = (tid & 1u) * 4u;\n";
+    o << "  const uint32_t lane_off1 = tid * 4u, lane_off2 = tid * 8u; (void)lane_off1; (void)lane_off2;\n";
     o << "  for (long long tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {\n";
     o << "    if (part < 0 || tile >= tile_end) {\n      int np = part < 0 ? 0 : part;\n      while (np + 1 < n_parts && tile >= parts[np].tile_end) np++;\n      part = np;\n";
     o << "      const FdbScanArgs& pa = parts[part];\n      n_rows = pa.n_rows; tile_begin = pa.tile_begin; tile_end = pa.tile_end;\n";
@@ -376,8 +410,11 @@ struct Gen {
     o << "    const long long r0 = (tile - tile_begin) * " << BLK * 4 << "LL;\n";
     o << "    const long long left = n_rows - r0 - (long long)tid * 4;\n    if (left <= 0) continue;\n";
     o << "    const size_t tile_off4 = (size_t)r0 * 4, tile_off8 = (size_t)r0 * 8, tile_offb = (size_t)(r0 >> 3);\n";
+    o << "    const size_t tile_off1 = (size_t)r0, tile_off2 = (size_t)r0 * 2; (void)tile_off1; (void)tile_off2;\n";
+    o << "    const uint32_t live = left >= 4 ? 0xFu : ((1u << (int)left) - 1u);\n";
+    live_mask = true;
     loads(false);
-    o << "    uint32_t sel = left >= 4 ? 0xFu : ((1u << (int)left) - 1u);\n";
+    o << "    uint32_t sel = live;\n";
     if (!s.code.empty()) o << "    sel &= " << filter_expr() << ";\n";
     {  // match bits of the leaves that boolean projections read (expression nodes of kind 7): leaves outside the filter program
       std::vector<int> seen;
@@ -1575,7 +1612,7 @@ struct HashGen {
 std::string JitShape::key(bool with_validity) const {
   std::ostringstream k;
   k << "b" << block << "l" << lds_acc << "c" << need_count << "t" << two_phase << "r" << reg_slots << "h" << cache << (wave_tables ? "w" : "") << (uniform_fold ? "u" : "") << "|";
-  auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); k << '|'; };
+  auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) { k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); if (p[i].width != 4) k << 'w' << p[i].width; } k << '|'; };
   slots(c4, n_c4); slots(c8, n_c8); slots(l4, n_l4); slots(l8, n_l8);
   for (const JitLeaf& L : leaves) k << L.kind << ',' << L.slot << ',' << L.wide << ',' << (L.kind >= FDB_LEAF_CMP_I64 && L.kind <= FDB_LEAF_CMP_I64_F64 ? L.op : 0) << ',' << L.lut_in_lds << ';';
   k << '|';
@@ -1603,6 +1640,8 @@ JitShape jit_shape(const FdbScanArgs& a, bool two_phase, int block) {
     for (int i = 0; i < n; i++) { dst[i].has_values = src[i].values != nullptr; dst[i].has_validity = src[i].validity != nullptr ? 1 : 0; }
   };
   slots(s.c4, a.c4, s.n_c4); slots(s.c8, a.c8, s.n_c8); slots(s.l4, a.l4, s.n_l4); slots(s.l8, a.l8, s.n_l8);
+  for (int i = 0; i < s.n_c4; i++) s.c4[i].width = a.w4[i] == 1 || a.w4[i] == 2 ? a.w4[i] : 4;
+  for (int i = 0; i < s.n_l4; i++) s.l4[i].width = a.wl4[i] == 1 || a.wl4[i] == 2 ? a.wl4[i] : 4;
   for (int l = 0; l < a.n_leaves; l++) {
     const FdbLeaf& L = a.leaves[l];
     s.leaves.push_back({L.kind, L.slot, L.wide, L.op, L.kind == FDB_LEAF_DICT_LUT && L.lut_lds != FDB_NO_LDS});
@@ -1632,6 +1671,7 @@ bool jit_shape_merge_args(JitShape* into, const FdbScanArgs& a, const FdbScanArg
   auto values_same = [](const FdbColSlot* x, const FdbColSlot* y, int n) { for (int i = 0; i < n; i++) if ((x[i].values != nullptr) != (y[i].values != nullptr)) return false; return true; };
   if (!values_same(a.c4, b.c4, a.n_c4) || !values_same(a.c8, b.c8, a.n_c8)) return false;
   if (two_phase && (!values_same(a.l4, b.l4, a.n_l4) || !values_same(a.l8, b.l8, a.n_l8))) return false;
+  if (std::memcmp(a.w4, b.w4, sizeof a.w4) != 0 || (two_phase && std::memcmp(a.wl4, b.wl4, sizeof a.wl4) != 0)) return false;  // (0 and 4 both mean the uint32 column: the plan writes 0)
   if (a.n_leaves != b.n_leaves || a.n_code != b.n_code || a.n_gcols != b.n_gcols || a.n_aggs != b.n_aggs || a.n_expr != b.n_expr) return false;
   for (int l = 0; l < a.n_leaves; l++) {
     const FdbLeaf& x = a.leaves[l]; const FdbLeaf& y = b.leaves[l];

@@ -12,7 +12,9 @@
 
 namespace fdb {
 
-struct JitSlot { bool has_values = false; int has_validity = 0; };  // has_validity: 0 no record has a bitmap, 1 every record, 2 some (checked per record)
+// has_validity: 0 no record has a bitmap, 1 every record, 2 some (checked per record). width (4-byte slots of fdb_plan_kernel only): bytes
+// per index behind `values` — 4: the uint32 column, 1 / 2: the records' narrow-index caches (FdbScanArgs.w4 / wl4), unpacked after the load
+struct JitSlot { bool has_values = false; int has_validity = 0; int width = 4; };
 struct JitLeaf { int kind = 0, slot = -1, wide = 0, op = 0; bool lut_in_lds = false; };
 struct JitGroup { int slot = -1; bool lut_in_lds = false; };
 struct JitAgg { int func = 0, type = 0, slot = -1; int expr = 0; };  // expr: 1 + root node of a computed input, 0 = stored column

@@ -2297,6 +2297,45 @@ hipError_t fdb_launch_stream_read(const void* src, int64_t bytes, unsigned long 
 }
 
 namespace {
+// The narrow-index cache of a resident dictionary column (fdb_record.h, ScanCache): one 16-byte store per thread = 16 / W rows, read as
+// 16-byte vectors. Whatever sits under a NULL row is truncated (the scan masks it with the validity nibble anyway); rows past the
+// last one, up to the end of the thread's vector, are written as 0, so that a tail lane of the scan finds a legal index there. The
+// last thread reads ≤ 15 rows = 60 bytes and writes ≤ 15 bytes past the payloads: inside kTailPad of either slot.
+template <int W>
+__global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, int64_t rows, int64_t n_vec) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_vec) return;
+  constexpr int PER = 16 / W;  // rows per thread
+  constexpr int NV = PER / 4;  // 16-byte vectors of uint32 indices it reads
+  const int64_t r0 = i * PER;
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int k = 0; k < NV; k++) {
+    const u32x4 v = __builtin_nontemporal_load(as_global(src + i * NV + k));
+    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int r = k * 4 + q;  // row of the thread; W bytes at byte r * W of its output
+      const uint32_t x = r0 + r < rows ? (e[q] & (W == 1 ? 0xFFu : 0xFFFFu)) : 0u;
+      w[(r * W) / 4] |= x << (8 * ((r * W) % 4));
+    }
+  }
+  u32x4 out; out.x = w[0]; out.y = w[1]; out.z = w[2]; out.w = w[3];
+  dst[i] = out;
+}
+}  // namespace
+
+hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream) {
+  if (rows <= 0) return hipSuccess;
+  if (width != 1 && width != 2) return hipErrorInvalidValue;
+  const int64_t per = 16 / width, n_vec = (rows + per - 1) / per;
+  const unsigned grid = (unsigned)((n_vec + 255) / 256);
+  if (width == 1) hipLaunchKernelGGL(narrow_indices_kernel<1>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), reinterpret_cast<u32x4*>(dst), rows, n_vec);
+  else hipLaunchKernelGGL(narrow_indices_kernel<2>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), reinterpret_cast<u32x4*>(dst), rows, n_vec);
+  return hipGetLastError();
+}
+
+namespace {
 // v[i] ← the double whose order-preserving integer key v[i] holds (the inverse of f64_to_ordered: the same involution)
 __global__ void ordered_to_f64_kernel(unsigned long long* v, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -83,6 +83,7 @@ DeviceBatch::~DeviceBatch() {
   }
   if (arena != nullptr) device_pool_free(device, arena);
   for (void* p : extra_arenas) device_pool_free(device, p);
+  for (const ScanCache::Col& c : scan_cache.cols) device_pool_free(device, c.d);  // (only resident records get one: the scans that read it were waited for above)
 }
 
 int DeviceBatch::find(const std::string& name) const {
@@ -1367,6 +1368,8 @@ int assign_slots(const DeviceBatch& b, Plan::Resolved& R, int first_layout, bool
     for (int k = 0; k < a.n_expr && ok; k++)  // the columns computed aggregate inputs read share the aggregates' pool
       if (a.expr[k].kind == 0) { a.expr[k].slot = slot_in(layout == 1 ? e8 : l8, R.expr_col[k], true); ok = a.expr[k].slot >= 0; }
     if (ok) {
+      for (int k = 0; k < a.n_c4; k++) R.c4_col[k] = e4.cols[k];
+      for (int k = 0; k < a.n_l4; k++) R.l4_col[k] = l4.cols[k];
       if (a.n_c4 > FDB_MAX_C4 || a.n_c8 > FDB_MAX_C8 || a.n_l4 > FDB_MAX_L4 || a.n_l8 > FDB_MAX_L8) strict = false;
       if (interp_ok != nullptr) *interp_ok = strict;
       return layout;
@@ -1542,6 +1545,8 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
   // ---- choose the scan kernel: run-time specialised (fdb_jit.cpp) → interpreting slot kernel → sequential kernel ----------
   int two_phase = 0, tile_rows_i = 0, per_cu = 1;
   const int sub = sub_tiles == 4 ? 0 : sub_tiles;  // kernel variant mode (0 = default, 4 = interpreting kernel only)
+  struct Narrowed { int part, k, col; bool late; const void* wide; int64_t saved; };  // a slot switched to its record's narrow-index cache
+  std::vector<Narrowed> narrowed;
   hipFunction_t jit_fn = nullptr;
   int jit_block = sub == 1 ? 512 : sub == 2 ? 256 : sub == 3 ? 1024 : 0;  // 0: picked by occupancy
   if (fixed_order) jit_block = 256;
@@ -1556,6 +1561,39 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     // A kernel specialised for this plan shape (fdb_jit.cpp), when every record of the launch has the same shape;
     // otherwise (or when hiprtc is unavailable) the interpreting slot kernel.
     if (sub_tiles != 4 && lds_bytes <= 150 * 1024) {  // (gfx950: up to 160 KiB of LDS per workgroup)
+      // Narrow index reads (fdb_record.h, ScanCache): a 4-byte slot is scanned at 1 or 2 bytes when EVERY part of the launch can hold a
+      // cache of that one width for the slot's column — built here, by the first scan that wants it; otherwise the whole launch reads
+      // the slot's uint32 columns, which every record has. Slots without values (IS NULL leaves) have nothing to narrow. The
+      // algorithmic bytes count the width that is scanned.
+      auto narrow_pool = [&](bool late) {
+        const FdbScanArgs& a0 = Rs[(size_t)live[0]].args;
+        const int n4 = late ? a0.n_l4 : a0.n_c4;
+        for (int i : live) if ((late ? Rs[(size_t)i].args.n_l4 : Rs[(size_t)i].args.n_c4) != n4) return;  // (records of different shapes: the launch is split below)
+        for (int k = 0; k < n4; k++) {
+          int w = 0;
+          for (int i : live) {
+            const Resolved& R = Rs[(size_t)i];
+            const int ci = late ? R.l4_col[k] : R.c4_col[k];
+            const int wi = (late ? R.args.l4[k] : R.args.c4[k]).values == nullptr || ci < 0 ? 4 : scan_cache_width(*bs[i], (size_t)ci);
+            w = w == 0 || w == wi ? wi : 4;
+            if (w == 4) break;
+          }
+          if (w >= 4) continue;
+          for (int i : live) {
+            Resolved& R = Rs[(size_t)i];
+            const int ci = late ? R.l4_col[k] : R.c4_col[k];
+            FdbColSlot& sl = late ? R.args.l4[k] : R.args.c4[k];
+            bool counted = false;  // (a column the filter and the group-by both read sits in two slots and counts once)
+            for (const Narrowed& nw : narrowed) if (nw.part == i && nw.col == ci) counted = true;
+            const int64_t saved = counted ? 0 : bs[i]->rows * (int64_t)(4 - w);
+            narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved});
+            sl.values = scan_cache_get(*bs[i], (size_t)ci, stream_);
+            (late ? R.args.wl4 : R.args.w4)[k] = (uint8_t)w;
+            R.bytes -= saved;
+          }
+        }
+      };
+      if (jit_possible) { narrow_pool(false); if (two_phase) narrow_pool(true); }
       JitShape shape;
       bool same = true, first = true;
       const FdbScanArgs& args0 = Rs[(size_t)live[0]].args;
@@ -1596,8 +1634,8 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
         if (jit_block != 0) { jit_fn = jit_get(shape); if (jit_fn != nullptr) per_cu = jit_blocks_per_cu(jit_fn, jit_block, lds_bytes); }
         else {
           int row_bytes = 0;
-          for (int k = 0; k < shape.n_c4; k++) row_bytes += shape.c4[k].has_values ? 4 : 0;
-          for (int k = 0; k < shape.n_l4; k++) row_bytes += shape.l4[k].has_values ? 4 : 0;
+          for (int k = 0; k < shape.n_c4; k++) row_bytes += shape.c4[k].has_values ? shape.c4[k].width : 0;
+          for (int k = 0; k < shape.n_l4; k++) row_bytes += shape.l4[k].has_values ? shape.l4[k].width : 0;
           for (int k = 0; k < shape.n_c8; k++) row_bytes += shape.c8[k].has_values ? 8 : 0;
           for (int k = 0; k < shape.n_l8; k++) row_bytes += shape.l8[k].has_values ? 8 : 0;
           jit_fn = jit_select(shape, lds_bytes, row_bytes, &jit_block, &per_cu);
@@ -1606,6 +1644,15 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     }
     // a launch only the specialised kernel could serve (more leaves / aggregates than the interpreting kernel's register-resident
     // plan holds, computed columns) falls back to the sequential kernel when specialisation is unavailable
+    if (jit_fn == nullptr) {  // the interpreting kernels read the uint32 columns
+      for (const Narrowed& nw : narrowed) {
+        Resolved& R = Rs[(size_t)nw.part];
+        (nw.late ? R.args.l4 : R.args.c4)[nw.k].values = nw.wide;
+        (nw.late ? R.args.wl4 : R.args.w4)[nw.k] = 0;
+        R.bytes += nw.saved;
+      }
+      narrowed.clear();
+    }
     if (jit_fn == nullptr && !interp_ok) slots_ok = false;
   }
   if (fixed_order && jit_fn == nullptr) throw Error(FDB_ERR_UNSUPPORTED, "deterministic float sums need the run-time specialised dense kernel (records of one shape, hiprtc available)");

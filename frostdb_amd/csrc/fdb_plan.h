@@ -44,6 +44,10 @@ struct DeviceBatch {
   ~DeviceBatch();
   // Exactly-one-field lookup like ArrayRef.ArrowArray (binaryscalarexpr.go:22-29): -1 if absent or ambiguous.
   int find(const std::string& name) const;
+  // The narrow-index cache (fdb_record.h): built lazily by dense generated scans, under scan_cache_mu; freed by the destructor.
+  mutable std::mutex scan_cache_mu;
+  mutable ScanCache scan_cache;
+  int64_t scan_cache_bytes() const { std::lock_guard<std::mutex> lk(scan_cache_mu); return scan_cache.bytes; }
 
  private:
   mutable std::mutex readers_mu_;

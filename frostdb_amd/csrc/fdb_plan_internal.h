@@ -91,6 +91,7 @@ struct Plan::Resolved {
   int gcol_col[FDB_MAX_DENSE_GCOLS];
   int agg_col[FDB_MAX_AGGS];
   int expr_col[FDB_MAX_EXPR_NODES];       // batch column behind each expression column node
+  int c4_col[FDB_ARG_C4], l4_col[FDB_ARG_L4];  // batch column behind each 4-byte slot (assign_slots)
   std::vector<GroupRes> groups;           // group-by columns of this record (plan-level index, record column, kind, key-id LUT)
   // AndExpr.Eval is lazy (filter.go:172-190): when the left side of an AND selects no row of the record the right side is not
   // evaluated — so a right side that cannot be evaluated on this record (an operator its column type does not support) only is
@@ -101,6 +102,8 @@ struct Plan::Resolved {
     for (int& v : gcol_col) v = -1;
     for (int& v : agg_col) v = -1;
     for (int& v : expr_col) v = -1;
+    for (int& v : c4_col) v = -1;
+    for (int& v : l4_col) v = -1;
   }
   // Algorithmic bytes: each referenced buffer once per row, whatever the number of references.
   void count(const DeviceBatch& b, int ci, bool values = true) {

@@ -24,6 +24,31 @@ void* CallScope::alloc(size_t bytes) {
   return p;
 }
 
+int scan_cache_width(const DeviceBatch& b, size_t c) {
+  if (b.arena_ctx != nullptr || b.arena_borrowed || b.rows < kScanCacheMinRows) return 4;
+  const DevColumn& col = b.cols[c];
+  if (col.kind != ColKind::DICT || col.dict == nullptr || col.d_values == nullptr) return 4;
+  return narrow_width(col.dict->values.size());
+}
+
+const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
+  const int width = scan_cache_width(b, c);
+  if (width >= 4) throw Error(FDB_ERR_INVALID, "internal: no narrow-index cache for column " + b.cols[c].name);
+  std::lock_guard<std::mutex> lk(b.scan_cache_mu);
+  ScanCache& sc = b.scan_cache;
+  if (sc.cols.empty()) sc.cols.resize(b.cols.size());
+  ScanCache::Col& e = sc.cols[c];
+  if (e.d != nullptr) return e.d;
+  const size_t bytes = values_slot((size_t)b.rows, (size_t)width);
+  void* d = device_pool_alloc(b.device, bytes);
+  hipError_t err = fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, d, b.rows, width, stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(stream);
+  if (err != hipSuccess) { device_pool_free(b.device, d); hip_check(err, "narrow-index cache"); }
+  e.d = d; e.width = width; e.bytes = bytes;
+  sc.bytes += (int64_t)bytes;
+  return d;
+}
+
 void require_values(const DeviceBatch& in, const char* what) {
   for (const DevColumn& c : in.cols)
     if (c.d_values == nullptr && in.rows > 0)

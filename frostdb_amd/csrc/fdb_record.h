@@ -99,6 +99,29 @@ struct CallScope {
   void* alloc(size_t bytes);
 };
 
+// ---- the narrow-index cache of a resident record -------------------------------------------------------------------------------------
+// Beside the record, never part of it: per dictionary column at most one device buffer of the column's indices at 1 byte (dictionaries
+// of ≤ 256 entries) or 2 bytes (≤ 65 536), which the dense generated scan (fdb_plan_kernel) reads instead of the uint32 column. It
+// depends on the immutable record alone, so it is built once — by the first such scan that references the column — and freed with the
+// record. The record's layout, arena_bytes (fdb_batch_device_bytes: the record's OWN columns) and every other operator are untouched by
+// it: the cache is extra memory, up to 3 bytes per row and scanned dictionary column, reported by fdb_batch_scan_cache_bytes.
+// A buffer is sized like a values slot and comes from the device pool, so fdb_live_allocations counts it.
+constexpr int64_t kScanCacheMinRows = (int64_t)1 << 20;  // below it 3 B/row and column save less than a microsecond of a scan
+// Bytes per index the cache can hold for a dictionary of `entries` entries; 4: none (the column itself).
+inline int narrow_width(size_t entries) { return entries <= 256 ? 1 : entries <= 65536 ? 2 : 4; }
+struct ScanCache {
+  struct Col { void* d = nullptr; int width = 0; size_t bytes = 0; };
+  std::vector<Col> cols;  // by column of the record; empty until the first buffer
+  int64_t bytes = 0;      // Σ values_slot(rows, width) of the buffers
+};
+// Width at which a dense generated scan may read column `c` of `b` — 1, 2, or 4 when the column gets no buffer: no dictionary column,
+// a dictionary too large, a record below kScanCacheMinRows or a transient one (a host record is scanned once). Builds nothing.
+int scan_cache_width(const DeviceBatch& b, size_t c);
+// The buffer of column `c` (scan_cache_width(b, c) < 4), built on `stream` if it is not there yet. Two plans on two threads and two
+// streams may meet the same fresh record: the record's mutex is held from the look-up to the publication, and a buffer is published
+// only after the stream that built it has been synchronised — exactly one survives and nobody reads it early.
+const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream);
+
 // FDB_ERR_UNSUPPORTED, naming `what`, if a column of `in` (rows > 0) is of a type the resident record cannot hold.
 void require_values(const DeviceBatch& in, const char* what);
 

@@ -81,6 +81,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_batch_num_rows.argtypes = [vp]
     L.fdb_batch_device_bytes.restype = i64
     L.fdb_batch_device_bytes.argtypes = [vp]
+    L.fdb_batch_scan_cache_bytes.restype = i64
+    L.fdb_batch_scan_cache_bytes.argtypes = [vp]
     L.fdb_batch_release.argtypes = [vp]
     L.fdb_batch_release.restype = None
     L.fdb_plan_stats.argtypes = [vp, P(i64), P(ctypes.c_double), P(i64), P(i64)]
@@ -956,6 +958,11 @@ class ResidentBatch:
     @property
     def device_bytes(self) -> int:
         return lib().fdb_batch_device_bytes(self.handle)
+
+    @property
+    def scan_cache_bytes(self) -> int:
+        """Bytes of the narrow-index cache dense scans keep beside the record (not part of `device_bytes`; 0 until such a scan)."""
+        return lib().fdb_batch_scan_cache_bytes(self.handle)
 
     def close(self) -> None:
         if getattr(self, "handle", None):

@@ -471,6 +471,10 @@ FDB_API int fdb_batch_import(struct ArrowArray* batch, struct ArrowSchema* schem
 FDB_API int64_t fdb_batch_num_rows(const fdb_batch* batch);
 /* Bytes this batch occupies in HBM (values/indices + validity bitmaps; dictionaries stay on the host). */
 FDB_API int64_t fdb_batch_device_bytes(const fdb_batch* batch);
+/* Bytes of the batch's narrow-index cache, which is NOT part of fdb_batch_device_bytes: the first dense generated scan that references a
+ * dictionary column of ≤ 65 536 entries in a batch of ≥ 1 Mi rows keeps the column's indices at 1 or 2 bytes beside the batch and later
+ * scans read those (up to 3 bytes per row and scanned dictionary column; freed with the batch). 0 until such a scan. */
+FDB_API int64_t fdb_batch_scan_cache_bytes(const fdb_batch* batch);
 FDB_API void fdb_batch_release(fdb_batch* batch);
 /* The record of a resident batch as Arrow in host memory (the caller owns `out` / `out_schema` and calls their release()). */
 FDB_API int fdb_batch_export(const fdb_batch* batch, struct ArrowArray* out, struct ArrowSchema* out_schema);

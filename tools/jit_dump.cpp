@@ -85,6 +85,7 @@ int main(int argc, char** argv) {
   }
   if (argc > 1 && std::string(argv[1]) == "plan") {
     // the dense scan kernel of a cfg 2-like shape (`labels.code == X` + SUM(float64) [+ MIN / COUNT] GROUP BY labels.path):
+    //   plan [variant] [narrow]   narrow: the dictionary slots read from narrow-index caches (1-byte filter column, 2-byte group column)
     //   plan [variant]   variant: lds (default) | wave (per-wave tables: fdb_plan_set_deterministic) | reg (≤ 8 slots in registers) | cache (table too big for LDS) | two (two-phase layout, 4 aggregates)
     const std::string v = argc > 2 ? argv[2] : "lds";
     fdb::JitShape s;
@@ -107,6 +108,10 @@ int main(int argc, char** argv) {
       s.n_c8 = 1; s.c8[0].has_values = true;
       s.gcols.push_back({1, true});
       s.aggs = {{FDB_AGG_SUM, FDB_T_F64, 0, 0}, {FDB_AGG_MIN, FDB_T_F64, 0, 0}};
+    }
+    if (argc > 3 && std::string(argv[3]) == "narrow") {  // narrow-index caches: the filter column read at 1 byte, the group column at 2
+      s.c4[0].width = 1;
+      (s.two_phase ? s.l4[0] : s.c4[1]).width = 2;
     }
     std::fputs(fdb::jit_source(s).c_str(), stdout);
     return 0;
