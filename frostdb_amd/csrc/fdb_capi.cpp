@@ -14,6 +14,7 @@
 #include "fdb_mergerec.h"
 #include "fdb_plan.h"
 #include "fdb_pqwrite_host.h"
+#include "fdb_record.h"
 #include "fdb_regex.h"
 #include "fdb_sort.h"
 #include "fdb_sortkey.h"
@@ -138,6 +139,27 @@ int fdb_selftest_widen(const void* src, int32_t width, uint32_t* dst, int64_t n)
       return;
     }
     fdb::widen_indices(src, width, dst, (size_t)n);
+  });
+}
+
+int fdb_selftest_scan_cache(const uint32_t* indices, int64_t rows, int32_t width, int device, uint8_t* out, int64_t out_bytes) {
+  return guard(nullptr, [&] {
+    if (indices == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || (width != 1 && width != 2) || out_bytes != (rows * width + 15) / 16 * 16)
+      throw fdb::Error(FDB_ERR_INVALID, "scan cache: 1 to 2^28 rows, width 1 or 2, out_bytes = rows * width rounded up to 16");
+    // the builder as scan_cache_get runs it: a uint32 column in a values slot, the cache in a slot of its own width
+    fdb::CallScope call(device);
+    void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
+    void* d_dst = call.alloc(fdb::values_slot((size_t)rows, (size_t)width));
+    fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), "scan cache: copy in");
+    fdb::hip_check(fdb_launch_narrow_indices((const uint32_t*)d_src, d_dst, rows, width, call.ctx->stream), "scan cache: builder");
+    fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), "scan cache: copy out");
+    fdb::hip_check(hipStreamSynchronize(call.ctx->stream), "scan cache: wait");
+    // every row where scan_cache_position says, which is also where fdb_plan_kernel looks for it
+    for (int64_t i = 0; i < rows; i++) {
+      const int64_t at = fdb::scan_cache_position(i, rows, width);
+      const uint32_t got = width == 1 ? out[at] : (uint32_t)out[2 * at] | ((uint32_t)out[2 * at + 1] << 8);
+      if (got != (indices[i] & (width == 1 ? 0xFFu : 0xFFFFu))) throw fdb::Error(FDB_ERR_INVALID, "scan cache: row " + std::to_string(i) + " is not at its position");
+    }
   });
 }
 

@@ -48,6 +48,10 @@ struct JitShape {
   // LDS tables: when the slots of a wave's selected rows agree (sorted input) the updates go to a wave-uniform address, so that the compiler
   // folds them across the lanes (fdb_jit.cpp, "Sorted input")
   bool uniform_fold = true;  // ($FDB_NO_UNIFORM_FOLD, A/B aid: a plan reads it at create, Plan::Knobs)
+  // fdb_plan_kernel, set when a slot of the launch is narrow (JitSlot::width < 4): the unit of work (FdbScanArgs tile_begin / tile_end,
+  // total_tiles) is block × 16 rows instead of block × 4 — each wave takes one block of 1 024 rows as four sub-steps of 64 lanes × 4 rows
+  // and reads the narrow slots of a full block with 16-byte loads, in the order the records' caches keep them (scan_cache_position).
+  bool quad = false;
   // fdb_select_kernel only (not part of key()): early slots whose values the kernel compacts itself, bit i = slot i of c4 / c8
   int fuse4 = 0, fuse8 = 0;
   // fdb_project_kernel only (not part of key()): root node of every computed field, in output order

@@ -134,7 +134,8 @@ struct FdbScanArgs {
                                  // coalesced stores and folded by fdb_launch_reduce_partials (nullptr: flush with atomics)
   int32_t lut_class;        // records with the same class carry byte-identical LUT sets at the same LDS offsets
   // fdb_plan_kernel only: bytes per index that c4[k] / l4[k].values holds — 0 (what every other builder of these blocks leaves) or 4: the
-  // record's own uint32 column; 1 / 2: the record's narrow-index cache (fdb_record.h, ScanCache), the same width in every part of a launch
+  // record's own uint32 column; 1 / 2: the record's narrow-index cache (fdb_record.h, ScanCache), the same width in every part of a launch.
+  // A launch with such a slot is a quad launch (fdb_jit.h, JitShape::quad): tile_begin / tile_end count units of block × 16 rows.
   uint8_t w4[FDB_ARG_C4];
   uint8_t wl4[FDB_ARG_L4];
   uint8_t code[FDB_MAX_CODE];
@@ -731,8 +732,9 @@ hipError_t fdb_launch_reduce_partials(const unsigned long long* partials, int n_
 // The slot kernel over `n_parts` records in ONE launch. `d_parts` is the device copy of the per-record argument
 // blocks (global tile ranges filled in, in units of fdb_slot_geometry's tile_rows); `common` = any of them (table
 // pointers, aggregation functions, LDS layout are identical across records). sub_tiles: 1 or 2.
-// dst[i] = (uint8 / uint16) src[i] for i < rows, zero up to the next multiple of 16 bytes (width: 1 or 2): the narrow-index cache of a
-// resident dictionary column. Both buffers are sized like a values slot (kTailPad past the payload), which the 16-byte accesses rely on.
+// dst[scan_cache_position(i, rows, width)] = (uint8 / uint16) src[i] for i < rows (fdb_record.h: the full 1 024-row blocks wave-interleaved,
+// the last, partial block in row order), zero up to the next multiple of 16 bytes (width: 1 or 2): the narrow-index cache of a resident
+// dictionary column. Both buffers are sized like a values slot (kTailPad past the payload), which the 16-byte accesses rely on.
 hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream);
 // Measurement only: reads `bytes` (multiple of 16) once with the best streaming pattern of this box.
 hipError_t fdb_launch_stream_read(const void* src, int64_t bytes, unsigned long long* out, hipStream_t stream);

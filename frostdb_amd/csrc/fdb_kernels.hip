@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "fdb_kernels.h"
+#include "fdb_record.h"
 
 namespace {
 
@@ -2298,25 +2299,33 @@ hipError_t fdb_launch_stream_read(const void* src, int64_t bytes, unsigned long 
 
 namespace {
 // The narrow-index cache of a resident dictionary column (fdb_record.h, ScanCache): one 16-byte store per thread = 16 / W rows, read as
-// 16-byte vectors. Whatever sits under a NULL row is truncated (the scan masks it with the validity nibble anyway); rows past the
-// last one, up to the end of the thread's vector, are written as 0, so that a tail lane of the scan finds a legal index there. The
-// last thread reads ≤ 15 rows = 60 bytes and writes ≤ 15 bytes past the payloads: inside kTailPad of either slot.
+// 16-byte vectors. The vectors of the record's full 1 024-row blocks are written in the wave-interleaved order fdb_plan_kernel loads them
+// in (scan_cache_position): vector l of a block (and of its half h, W = 2) holds lane l's rows 256 u + 4 l … + 3 of sub-steps u = 0 … 3
+// (W = 2: u = 2 h, 2 h + 1), gathered from 4 / 2 reads 1 KiB apart — each wave read instruction still contiguous. The vectors of the last,
+// partial block hold consecutive rows. Whatever sits under a NULL row is truncated (the scan masks it with the validity nibble anyway);
+// rows past the last one, up to the end of the thread's vector, are written as 0, so that a tail lane of the scan finds a legal index
+// there. The last thread reads ≤ 15 rows = 60 bytes and writes ≤ 15 bytes past the payloads: inside kTailPad of either slot.
 template <int W>
 __global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, int64_t rows, int64_t n_vec) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_vec) return;
   constexpr int PER = 16 / W;  // rows per thread
   constexpr int NV = PER / 4;  // 16-byte vectors of uint32 indices it reads
+  constexpr int64_t VB = fdb::kScanCacheBlock * W / 16;  // vectors it writes per block
   const int64_t r0 = i * PER;
+  const bool interleaved = r0 + PER <= rows / fdb::kScanCacheBlock * fdb::kScanCacheBlock;
+  // first source vector and the stride between the thread's source vectors: a lane's rows of consecutive sub-steps are 256 rows apart
+  const int64_t s0 = interleaved ? (i / VB) * (fdb::kScanCacheBlock / 4) + ((i % VB) / 64) * (64 * NV) + (i % 64) : i * NV;
+  const int64_t sd = interleaved ? 64 : 1;
   uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int k = 0; k < NV; k++) {
-    const u32x4 v = __builtin_nontemporal_load(as_global(src + i * NV + k));
+    const u32x4 v = __builtin_nontemporal_load(as_global(src + s0 + k * sd));
     const uint32_t e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      const int r = k * 4 + q;  // row of the thread; W bytes at byte r * W of its output
-      const uint32_t x = r0 + r < rows ? (e[q] & (W == 1 ? 0xFFu : 0xFFFFu)) : 0u;
+      const int r = k * 4 + q;  // element of the thread's vector; W bytes at byte r * W of its output
+      const uint32_t x = interleaved || r0 + r < rows ? (e[q] & (W == 1 ? 0xFFu : 0xFFFFu)) : 0u;
       w[(r * W) / 4] |= x << (8 * ((r * W) % 4));
     }
   }

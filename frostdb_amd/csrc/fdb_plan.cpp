@@ -1549,6 +1549,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
   std::vector<Narrowed> narrowed;
   hipFunction_t jit_fn = nullptr;
   int jit_block = sub == 1 ? 512 : sub == 2 ? 256 : sub == 3 ? 1024 : 0;  // 0: picked by occupancy
+  bool quad_unit = false;  // JitShape::quad: the launch counts its tiles in units of jit_block × 16 rows
   if (fixed_order) jit_block = 256;
   if (slots_ok) {
     // records that fit the single-phase layout also fit the two-phase one: re-assign them if the launch is mixed
@@ -1640,6 +1641,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
           for (int k = 0; k < shape.n_l8; k++) row_bytes += shape.l8[k].has_values ? 8 : 0;
           jit_fn = jit_select(shape, lds_bytes, row_bytes, &jit_block, &per_cu);
         }
+        quad_unit = shape.quad;
       }
     }
     // a launch only the specialised kernel could serve (more leaves / aggregates than the interpreting kernel's register-resident
@@ -1661,7 +1663,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
   if (slots_ok) {
     // ---- one launch of the slot kernel (specialised or interpreting) over every record -------------------------------------
     if (jit_fn != nullptr) {
-      tile_rows_i = jit_block * 4;
+      tile_rows_i = jit_block * (quad_unit ? 16 : 4);
     } else {
       fdb_slot_geometry(two_phase, sub, lds_acc, lds_bytes, device_, &tile_rows_i, &per_cu);
     }

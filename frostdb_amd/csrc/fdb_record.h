@@ -30,6 +30,24 @@ inline size_t values_slot(size_t rows, size_t width) { return align_up(rows * wi
 // byte count is itself such a multiple, so the rounding never passes it.
 inline size_t bitmap_slot(size_t rows) { return align_up((rows + 63) / 64 * 8 + kTailPad, 256); }
 
+// Element position of row `i` in a narrow-index cache (ScanCache, below) of `rows` rows at `width` 1 or 2 bytes per index. The cache has one
+// reader, fdb_plan_kernel, whose wave owns a block of 1 024 consecutive rows as four sub-steps of 256 rows; in sub-step u lane l owns rows
+// 256 u + 4 l … + 3. The indices of a full block sit in the order the wave's 16-byte loads want them: lane l's load at byte 16 l of the
+// block's 1 024 bytes (width 1), or its two loads at bytes 1 024 h + 16 l of the block's 2 048 (width 2), hold its rows of sub-steps
+// 0 … 3, or 2 h and 2 h + 1. The rows of the record's last, partial block stay in row order. The layout follows from the wave
+// (64 lanes × 4 rows) alone: not from a workgroup size, a query or a launch.
+#if defined(__HIPCC__)
+#define FDB_RECORD_HD __host__ __device__
+#else
+#define FDB_RECORD_HD
+#endif
+constexpr int64_t kScanCacheBlock = 1024;  // rows of a wave's block
+FDB_RECORD_HD inline int64_t scan_cache_position(int64_t i, int64_t rows, int width) {
+  if (i >= rows / kScanCacheBlock * kScanCacheBlock) return i;
+  const int64_t b = i / kScanCacheBlock, j = i % kScanCacheBlock, u = j / 256, l = (j % 256) / 4, r = j % 4;
+  return width == 1 ? kScanCacheBlock * b + 16 * l + 4 * u + r : kScanCacheBlock * b + 512 * (u / 2) + 8 * l + 4 * (u % 2) + r;
+}
+
 // Offsets of the slots of one record, in column order: [values | bitmap] per column.
 struct RecordLayout {
   struct Col { size_t val_off, bit_off; };  // bit_off == kNoSlot: no bitmap slot
@@ -105,7 +123,8 @@ struct CallScope {
 // depends on the immutable record alone, so it is built once — by the first such scan that references the column — and freed with the
 // record. The record's layout, arena_bytes (fdb_batch_device_bytes: the record's OWN columns) and every other operator are untouched by
 // it: the cache is extra memory, up to 3 bytes per row and scanned dictionary column, reported by fdb_batch_scan_cache_bytes.
-// A buffer is sized like a values slot and comes from the device pool, so fdb_live_allocations counts it.
+// A buffer is sized like a values slot and comes from the device pool, so fdb_live_allocations counts it. Its bytes are a private layout
+// (scan_cache_position, above): no other operator, and nothing outside the library, reads them.
 constexpr int64_t kScanCacheMinRows = (int64_t)1 << 20;  // below it 3 B/row and column save less than a microsecond of a scan
 // Bytes per index the cache can hold for a dictionary of `entries` entries; 4: none (the column itself).
 inline int narrow_width(size_t entries) { return entries <= 256 ? 1 : entries <= 65536 ? 2 : 4; }

@@ -244,6 +244,11 @@ FDB_API int fdb_regex_match(const char* pattern, int64_t pattern_len, const uint
  * them). `width` -12 / -14: the 2- / 4-bit road THROUGH a rank → index table (what a Finish that ships the ids present uses), with the
  * table t[r] = 3 r + 5: dst[i] = 3 src[i] + 5. No device is touched. */
 FDB_API int fdb_selftest_widen(const void* src, int32_t width, uint32_t* dst, int64_t n);
+/* Self-check of the narrow-index cache's builder (the buffers a dense generated scan reads instead of a record's uint32 dictionary
+ * indices; their bytes are a private, wave-interleaved layout): runs the builder on `device` over `rows` uint32 `indices` at `width` 1 or 2
+ * bytes and copies the buffer's first `out_bytes` = rows x width rounded up to 16 bytes to `out` — the indices in the cache's order and
+ * zeros behind the last row. FDB_ERR_INVALID also when a row is not where the library's own position formula puts it. */
+FDB_API int fdb_selftest_scan_cache(const uint32_t* indices, int64_t rows, int32_t width, int device, uint8_t* out, int64_t out_bytes);
 
 /* ---- plan life cycle (≙ physicalplan.Build for one chain, physicalplan.go:417-474) -------------- */
 /* `desc` and everything it points at (expression nodes, names, literals, patterns) is copied: the caller may free it as soon

@@ -85,7 +85,8 @@ int main(int argc, char** argv) {
   }
   if (argc > 1 && std::string(argv[1]) == "plan") {
     // the dense scan kernel of a cfg 2-like shape (`labels.code == X` + SUM(float64) [+ MIN / COUNT] GROUP BY labels.path):
-    //   plan [variant] [narrow]   narrow: the dictionary slots read from narrow-index caches (1-byte filter column, 2-byte group column)
+    //   plan [variant] [narrow [threads]]   narrow: the dictionary slots read from narrow-index caches (1-byte filter column, 2-byte group column),
+    //                                       the quad shape of such a launch; threads: per workgroup (256 / 512 / 1024)
     //   plan [variant]   variant: lds (default) | wave (per-wave tables: fdb_plan_set_deterministic) | reg (≤ 8 slots in registers) | cache (table too big for LDS) | two (two-phase layout, 4 aggregates)
     const std::string v = argc > 2 ? argv[2] : "lds";
     fdb::JitShape s;
@@ -112,7 +113,9 @@ int main(int argc, char** argv) {
     if (argc > 3 && std::string(argv[3]) == "narrow") {  // narrow-index caches: the filter column read at 1 byte, the group column at 2
       s.c4[0].width = 1;
       (s.two_phase ? s.l4[0] : s.c4[1]).width = 2;
+      s.quad = true;  // (what jit_shape sets for a launch with a narrow slot)
     }
+    if (argc > 4) s.block = std::atoi(argv[4]);  // plan <variant> narrow <threads per workgroup>
     std::fputs(fdb::jit_source(s).c_str(), stdout);
     return 0;
   }
