@@ -97,39 +97,145 @@ inline uint32_t fdb_pqs_put_copy(uint32_t len, uint32_t off, unsigned char* out,
   for (uint32_t i = 0; i < fdb_pqs_copy_elem_len(rest, off); i++) out[o++] = fdb_pqs_copy_elem_byte(rest, off, i);
   return o;
 }
+// The search, shared with the LZ4_RAW rule (fdb_pqlz4.h), which bounds it by the page body's end: positions 0 … stop − 1 may win (here
+// every position with 4 bytes left: fdb_pqs_stop(n)), a match is extended up to position `reach` (here n).
+FDB_PQW_HD uint32_t fdb_pqs_stop(uint32_t n) { return n >= 4 ? n - 3 : 0; }
+// The window at `cursor`: the lowest position with a candidate, if any.
+inline bool fdb_pqs_find_host(const unsigned char* src, uint32_t cursor, uint32_t stop, const uint32_t* table, uint32_t* win, uint32_t* cand) {
+  for (uint32_t l = 0; l < FDB_PQS_WINDOW; l++) {
+    const uint32_t p = cursor + l;
+    if (p >= stop) break;
+    const uint32_t x = fdb_pqs_load32(src + p);
+    for (uint32_t q = p; q > cursor && p - (q - 1) <= FDB_PQS_NEAR; q--)
+      if (fdb_pqs_load32(src + q - 1) == x) { *win = p; *cand = q - 1; return true; }
+    const uint32_t t = table[fdb_pqs_hash(x)];
+    if (t != 0 && fdb_pqs_load32(src + t - 1) == x) { *win = p; *cand = t - 1; return true; }
+  }
+  return false;
+}
+inline uint32_t fdb_pqs_extend_host(const unsigned char* src, uint32_t win, uint32_t cand, uint32_t reach) {
+  uint32_t len = 4;
+  while (win + len < reach && src[cand + len] == src[win + len]) len++;
+  return len;
+}
+// Every position below `cursor` that is not in the table yet is put in; returns the new `filled`.
+inline uint32_t fdb_pqs_fill_host(const unsigned char* src, uint32_t* table, uint32_t filled, uint32_t cursor, uint32_t stop) {
+  for (; filled < cursor && filled < stop; filled++) {
+    uint32_t* e = table + fdb_pqs_hash(fdb_pqs_load32(src + filled));
+    if (filled + 1 > *e) *e = filled + 1;
+  }
+  return filled;
+}
 inline uint32_t fdb_pqs_compress_fragment_host(const unsigned char* src, uint32_t n, uint32_t* table, unsigned char* out) {
   for (uint32_t i = 0; i < FDB_PQS_TABLE; i++) table[i] = 0;
+  const uint32_t stop = fdb_pqs_stop(n);
   uint32_t cursor = 0, lit = 0, filled = 0, o = 0;
-  while (cursor + 4 <= n) {
+  while (cursor < stop) {
     uint32_t win = 0, cand = 0;
-    bool found = false;
-    for (uint32_t l = 0; l < FDB_PQS_WINDOW && !found; l++) {
-      const uint32_t p = cursor + l;
-      if (p + 4 > n) break;
-      const uint32_t x = fdb_pqs_load32(src + p);
-      for (uint32_t q = p; q > cursor && p - (q - 1) <= FDB_PQS_NEAR && !found; q--)
-        if (fdb_pqs_load32(src + q - 1) == x) { found = true; win = p; cand = q - 1; }
-      if (!found) {
-        const uint32_t t = table[fdb_pqs_hash(x)];
-        if (t != 0 && fdb_pqs_load32(src + t - 1) == x) { found = true; win = p; cand = t - 1; }
-      }
-    }
-    if (found) {
-      uint32_t len = 4;
-      while (win + len < n && src[cand + len] == src[win + len]) len++;
+    if (fdb_pqs_find_host(src, cursor, stop, table, &win, &cand)) {
+      const uint32_t len = fdb_pqs_extend_host(src, win, cand, n);
       o = fdb_pqs_put_literal(src, lit, win, out, o);
       o = fdb_pqs_put_copy(len, win - cand, out, o);
       cursor = lit = win + len;
     } else {
       cursor += FDB_PQS_WINDOW;
     }
-    for (; filled < cursor && filled + 4 <= n; filled++) {
-      uint32_t* e = table + fdb_pqs_hash(fdb_pqs_load32(src + filled));
-      if (filled + 1 > *e) *e = filled + 1;
-    }
+    filled = fdb_pqs_fill_host(src, table, filled, cursor, stop);
   }
   return fdb_pqs_put_literal(src, lit, n, out, o);
 }
+
+#if defined(__HIPCC__) || defined(__HIP__)
+// ---- the search on the device: what a wave does with one window, bounded by `stop` and `reach` — the LZ4_RAW compress kernel's ---------------
+// (fdb_pqlz4.hip). pqs_compress_kernel holds the same steps inline, with stop = fdb_pqs_stop(n) and reach = n: calling these from it
+// was measured and cost its compress pass 4 % (9.96 → 10.41 ms on 268 MB of page bodies, alternated runs), so it stays as it is.
+// The lanes of one wave have written LDS and are about to read what the others wrote (or the other way round).
+__device__ __forceinline__ void fdb_pqs_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t fdb_pqs_lowest_lane(unsigned long long mask) { return mask != 0ull ? (uint32_t)__builtin_ctzll(mask) : 64u; }
+
+// `len` bytes src → dst at any alignment, by the 64 lanes of a wave (or the `threads` threads of a workgroup).
+__device__ __forceinline__ void fdb_pqs_copy_bytes(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, uint32_t len, uint32_t tid, uint32_t threads) {
+  for (uint32_t i = tid * 4; i + 4 <= len; i += threads * 4) { const uint32_t x = fdb_pqs_load32(src + i); __builtin_memcpy(dst + i, &x, 4); }
+  const uint32_t r = len & ~3u;
+  if (r + tid < len) dst[r + tid] = src[r + tid];
+}
+
+// The 4 bytes of the position 64 further, loaded while this window is searched: the next window's, if nothing matches here.
+struct FdbPqsAhead { uint32_t x = 0, at = ~0u; };
+
+// The window at `cursor` (< stop), a lane a position: each lane looks its 4 bytes up in the table (positions before the window) and, by
+// shuffles, in the FDB_PQS_NEAR lanes below it; a ballot finds the lowest lane with a candidate. True: *win and *cand are that position
+// and what it is held against. False: no position has a candidate, and the window's own positions have gone into the table with the
+// bytes the lanes hold (the caller's `filled` is cursor + FDB_PQS_WINDOW then).
+__device__ __forceinline__ bool fdb_pqs_find(const unsigned char* __restrict__ src, uint32_t cursor, uint32_t stop, uint32_t* table, uint32_t lane, FdbPqsAhead* ahead, uint32_t* win,
+                                             uint32_t* cand) {
+  const uint32_t p = cursor + lane;
+  const bool valid = p < stop;
+  uint32_t x;
+  if (ahead->at == cursor) x = ahead->x;
+  else x = valid ? fdb_pqs_load32(src + p) : 0;
+  const uint32_t t = valid ? table[fdb_pqs_hash(x)] : 0;
+  const bool t_hit = t != 0 && fdb_pqs_load32(src + t - 1) == x;  // (t − 1 < cursor: 4 bytes are left there)
+  ahead->x = p + FDB_PQS_WINDOW < stop ? fdb_pqs_load32(src + p + FDB_PQS_WINDOW) : 0;
+  ahead->at = cursor + FDB_PQS_WINDOW;
+  const unsigned long long t_mask = __ballot(t_hit);
+  unsigned long long w_mask = 0;  // the lanes with a candidate inside the window, best_d back
+  uint32_t best_d = 0, w = fdb_pqs_lowest_lane(t_mask);
+  // the lanes up to the lowest one with a candidate try every distance up to FDB_PQS_NEAR, down to the window's first position:
+  // a lane l has tried them all once d reaches l, so when d passes w no lane below w can turn up any more, and w's own nearest
+  // is found. Eight distances at a step, so that the shuffles do not wait for each other's ballot (a distance past w finds
+  // nothing below w).
+  static_assert(FDB_PQS_NEAR % 8 == 0 && FDB_PQS_NEAR < FDB_PQS_WINDOW, "the distances are tried eight at a step");
+  for (uint32_t d0 = 1; d0 <= FDB_PQS_NEAR && d0 <= w; d0 += 8) {
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++) {
+      const uint32_t d = d0 + k;  // (FDB_PQS_NEAR at the most)
+      const uint32_t y = (uint32_t)__shfl_up((int)x, d, 64);
+      if (valid && lane >= d && y == x && best_d == 0) best_d = d;
+    }
+    w_mask = __ballot(best_d != 0);
+    w = fdb_pqs_lowest_lane(w_mask | t_mask);
+  }
+  if (w < 64) {
+    const uint32_t wd = (uint32_t)__shfl((int)best_d, (int)w, 64), wt = (uint32_t)__shfl((int)t, (int)w, 64);
+    *win = cursor + w;
+    *cand = wd != 0 ? cursor + w - wd : wt - 1;
+    return true;
+  }
+  fdb_pqs_wave_sync();
+  if (valid) atomicMax(&table[fdb_pqs_hash(x)], p + 1);
+  fdb_pqs_wave_sync();
+  return false;
+}
+
+// The match of `win` against `cand`, extended 64 bytes at a compare + ballot up to position `reach`.
+__device__ __forceinline__ uint32_t fdb_pqs_extend(const unsigned char* __restrict__ src, uint32_t win, uint32_t cand, uint32_t reach, uint32_t lane) {
+  uint32_t len = 4;
+  for (;;) {
+    const uint32_t i = len + lane;
+    const bool same = win + i < reach && src[cand + i] == src[win + i];
+    const unsigned long long mask = __ballot(same);
+    if (mask != ~0ull) return len + (uint32_t)__builtin_ctzll(~mask);
+    len += 64;
+  }
+}
+
+// The positions filled … cursor − 1 go into the table: atomicMax of the position — the largest wins whatever lane comes first — and the
+// wave waits before it looks anything up.
+__device__ __forceinline__ void fdb_pqs_fill(const unsigned char* __restrict__ src, uint32_t* table, uint32_t filled, uint32_t cursor, uint32_t stop, uint32_t lane) {
+  fdb_pqs_wave_sync();  // (every lane has looked up what it wanted)
+  for (uint32_t base = filled; base < cursor; base += 64) {
+    const uint32_t q = base + lane;
+    if (q < cursor && q < stop) atomicMax(&table[fdb_pqs_hash(fdb_pqs_load32(src + q))], q + 1);
+  }
+  fdb_pqs_wave_sync();
+}
+#endif
 
 #ifndef FDB_PQWRITE_HOST_ONLY
 // Place: ranges[i].len bytes of blob[ranges[i].src_off …] → image[ranges[i].dst_off …] (the host's bytes inside the bodies of compressed pages).

@@ -38,6 +38,10 @@
 //            lays the file out again (dictionary pages it compresses itself) and ONE gather launch moves the fragments' elements and
 //            the chunks of the uncompressed columns into the final image. Device memory: about 3 × the file body, the call's, freed
 //            on every path. The page index and the filters are the FINAL layout's; filters are never compressed.
+//   [LZ4_RAW] a column written LZ4_RAW (rule: fdb_pqlz4.h) goes the same way beside the SNAPPY ones: its pages' fragments are searched by
+//            fdb_pqlz4.hip's compress kernel, which leaves per fragment the literals before its first match and behind its last as counts
+//            and the sequences between in scratch; a walk per page joins them into ONE bare block and sizes it — the sizes come back in
+//            the same wait — and a second gather launch writes the blocks. The chunks of uncompressed columns stay the first gather's.
 //   deliver  the bitsets, one copy per filter straight to its offset in the returned bytes, then one device→host copy of the image
 //            into the returned (pinned) buffer, in one wait; the host fills the holes, appends page index (PqwLayout::tail) and footer.
 // fdb_selftest_parquet_write runs the same plan, layout and tail over a host record, every kernel replaced by a host walk of the same
@@ -174,7 +178,7 @@ std::string footer(const std::vector<ChunkMeta>& chunks, size_t n_cols, const st
     t.list(2, Thrift::T_I32, 1 + (c.optional ? 1 : 0) + (dict ? 1 : 0));  // (RLE: the definition levels, which a required column does not have)
     t.zigzag(c.delta_slot >= 0 ? ENC_DELTA_BINARY_PACKED : ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
     t.list(3, Thrift::T_BINARY, 1); t.str(c.name);
-    t.i32(4, c.codec);  // 0 UNCOMPRESSED, 1 SNAPPY
+    t.i32(4, c.codec);  // 0 UNCOMPRESSED, 1 SNAPPY, 7 LZ4_RAW
     t.i64(5, rows);
     t.i64(6, m.raw_bytes);
     t.i64(7, m.bytes);
@@ -384,7 +388,8 @@ std::vector<PqwColumn> pqw_columns(const std::vector<PqwInput>& in, int64_t rows
   if (n_codecs != 0 && (n_codecs != (int32_t)in.size() || codecs == nullptr))
     throw Error(FDB_ERR_INVALID, "parquet write: `codecs` has " + std::to_string(n_codecs) + " entries, the record " + std::to_string(in.size()) + " columns");
   for (int32_t k = 0; k < n_codecs; k++)
-    if (codecs[k] < 0 || codecs[k] > 1) throw Error(FDB_ERR_INVALID, "parquet write: codecs[" + std::to_string(k) + "] is " + std::to_string((int)codecs[k]) + " (0 UNCOMPRESSED, 1 SNAPPY)");
+    if (codecs[k] != 0 && codecs[k] != PQW_SNAPPY && codecs[k] != PQW_LZ4_RAW)
+      throw Error(FDB_ERR_INVALID, "parquet write: codecs[" + std::to_string(k) + "] is " + std::to_string((int)codecs[k]) + " (0 UNCOMPRESSED, 1 SNAPPY, 7 LZ4_RAW)");
   int delta_slots = 0;
   std::vector<PqwColumn> cols;
   for (size_t k = 0; k < in.size(); k++) {
@@ -866,6 +871,13 @@ static std::string pqs_elements_host(const unsigned char* body, size_t n) {
   return elements;
 }
 std::string pqs_block_host(const unsigned char* body, size_t n) { return varint_bytes(n) + pqs_elements_host(body, n); }
+std::string pql_block_host(const unsigned char* body, size_t n) {
+  std::vector<uint32_t> table(FDB_PQS_TABLE);
+  std::vector<unsigned char> mid(fdb_pql_slot_bytes());
+  std::string block((size_t)fdb_pql_bound(n), '\0');
+  block.resize((size_t)fdb_pql_block_host(body, n, table.data(), mid.data(), (unsigned char*)&block[0]));
+  return block;
+}
 
 PqwLayout pqw_layout(const PqwPlan& plan, const PqwSizes& sizes) { return pqw_layout(std::vector<const PqwPlan*>{&plan}, std::vector<PqwSizes>{sizes}); }
 
@@ -919,12 +931,13 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
     ChunkMeta& m = chunks[chunk_base[pi] + k];
     const uint64_t chunk_start = cur;
     m.col = &c; m.start = (int64_t)chunk_start; m.rows = g.rows;
-    const bool squeeze = final_form && c.codec != 0;  // this chunk's pages are written as Snappy blocks
+    const bool squeeze = final_form && c.codec != 0;  // this chunk's pages are written as Snappy or LZ4 blocks
+    const bool lz4 = c.codec == PQW_LZ4_RAW;
     const unsigned long long* used = c.used_slot >= 0 ? plan.dict.bits.data() + plan.dict.cols[(size_t)c.used_slot].word_off : nullptr;  // the chunk's presence bitmap
     if (used != nullptr && plan.dict.before.size() != plan.dict.bits.size()) throw Error(FDB_ERR_STATE, "parquet write: the used entries of " + c.name + " have not been counted");
     if (c.pq_kind == FDB_PQW_INDEX) {
       const std::string body = used != nullptr ? dictionary_body(*c.dict, used) : dictionary_body(*c.dict);
-      const std::string stored = squeeze ? pqs_block_host((const unsigned char*)body.data(), body.size()) : std::string();  // (host bytes already: the header's walk)
+      const std::string stored = !squeeze ? std::string() : lz4 ? pql_block_host((const unsigned char*)body.data(), body.size()) : pqs_block_host((const unsigned char*)body.data(), body.size());  // (host bytes already: the header's walk)
       const std::string hdr = page_header(PAGE_DICTIONARY, (int64_t)body.size(), (int64_t)(squeeze ? stored.size() : body.size()), (int64_t)c.entries, ENC_PLAIN);
       m.dict_off = (int64_t)cur;
       m.raw_bytes += (int64_t)(hdr.size() + body.size());
@@ -983,16 +996,16 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
         }
       }
       const uint64_t body = pre.size() + level_payload + vpre.size() + value_payload;
-      if (squeeze) {  // header, the block's preamble, then the elements the compressor made of the body
+      if (squeeze) {  // header, the block's preamble (SNAPPY; an LZ4_RAW block is bare), then what the compressor made of the body
         const uint64_t elements = (*page_elements)[next_compressed++];
-        if (elements > (uint64_t)fdb_pqs_fragments(body) * fdb_pqs_bound(FDB_PQS_FRAGMENT) || (body > 0) != (elements > 0))
+        if (lz4 ? elements < 1 || elements > fdb_pql_bound(body) : elements > (uint64_t)fdb_pqs_fragments(body) * fdb_pqs_bound(FDB_PQS_FRAGMENT) || (body > 0) != (elements > 0))
           throw Error(FDB_ERR_STATE, "parquet write: the compressor sizes a page body of " + std::to_string(body) + " bytes at " + std::to_string(elements) + " (" + c.name + ")");
-        const std::string preamble = varint_bytes(body);
+        const std::string preamble = lz4 ? std::string() : varint_bytes(body);
         const std::string hdr = page_header(PAGE_DATA, (int64_t)body, (int64_t)(preamble.size() + elements), n, encoding);
         m.raw_bytes += (int64_t)(hdr.size() + body);
         if (bounds) m.pages.push_back(PageLoc{cur, hdr.size() + preamble.size() + elements, n, cnt});
         L.put(cur, hdr + preamble); cur += hdr.size() + preamble.size();
-        L.pages.push_back(PqwLayout::Page{cur, body});
+        L.pages.push_back(PqwLayout::Page{cur, body, c.codec});
         cur += elements;
         continue;
       }
@@ -1003,7 +1016,7 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
       if (c.codec == 0) { L.put(cur, hdr + pre); cur += hdr.size() + pre.size(); }
       else {  // the staging image of a page to be compressed: the host's bytes inside the body are placed on their own, before the compressor runs
         cur += hdr.size();
-        L.pages.push_back(PqwLayout::Page{cur, body});
+        L.pages.push_back(PqwLayout::Page{cur, body, c.codec});
         L.put_body(cur, pre); cur += pre.size();
       }
       if (level_runs) { LP.run_out[(size_t)c.run_levels * (size_t)g.n_pages + (size_t)p] = cur; cur += level_payload; }
@@ -1338,7 +1351,7 @@ static void pqw_write_host(std::vector<PqwPlan>& plans, uint8_t** bytes, int64_t
     std::vector<std::string> elements;
     std::vector<uint32_t> page_elements;
     for (const PqwLayout::Page& pg : L.pages) {
-      elements.push_back(pqs_elements_host(image.data() + pg.off, (size_t)pg.body));
+      elements.push_back(pg.codec == PQW_LZ4_RAW ? pql_block_host(image.data() + pg.off, (size_t)pg.body) : pqs_elements_host(image.data() + pg.off, (size_t)pg.body));
       page_elements.push_back((uint32_t)elements.back().size());
     }
     std::vector<PqwSizes> final_sizes;
@@ -1626,11 +1639,16 @@ static void pqw_encode_passes(PqwCall* c, const PqwLayout::Part& L) {
   }
 }
 
-// SNAPPY (fdb_pqsnappy.hip): the host tables of the compress and gather passes — they outlive the waits of both — and their device copies.
+// SNAPPY (fdb_pqsnappy.hip) and LZ4_RAW (fdb_pqlz4.hip): the host tables of the compress and gather passes — they outlive the waits of
+// both — and their device copies. Each codec has the pages of its columns in tables of its own; `page_elements` lists both in the
+// layout's order. Without an LZ4_RAW column its tables stay empty: nothing of it is allocated, copied or launched.
 struct PqsTables {
   std::vector<FdbPqsRange> pieces, ranges; std::vector<FdbPqsPage> pages; std::vector<FdbPqsFrag> frags;
-  std::vector<uint64_t> page_dst; std::vector<uint32_t> page_elements;
+  std::vector<uint64_t> page_dst; std::vector<uint32_t> page_elements, snappy_elements;
   const FdbPqsFrag* d_frags = nullptr; uint32_t *d_frag_bytes = nullptr, *d_frag_off = nullptr;
+  std::vector<FdbPqlPage> lz_pages; std::vector<FdbPqlFrag> lz_frags; std::vector<uint64_t> lz_page_dst; std::vector<uint32_t> lz_bytes;
+  const FdbPqlFrag* d_lz_frags = nullptr; const FdbPqlPage* d_lz_pages = nullptr; FdbPqlOut* d_lz_outs = nullptr; FdbPqlPlace *d_lz_places = nullptr, *d_lz_closes = nullptr;
+  size_t lz_scratch = 0;  // where the LZ4 fragments' slots start in the call's scratch
 };
 
 // The staging image, laid out by `L`, compressed: the fragment and page tables of the pages it lists, the host's bytes inside their
@@ -1638,13 +1656,22 @@ struct PqsTables {
 static void pqs_compress_pass(PqwCall* c, const PqwLayout& L, PqsTables* t) {
   for (const PqwLayout::Piece& p : L.body_pieces) t->pieces.push_back(FdbPqsRange{(uint64_t)p.pos, p.off, (uint32_t)p.len, 0});
   for (const PqwLayout::Page& pg : L.pages) {
+    if (pg.codec == PQW_LZ4_RAW) {
+      t->lz_pages.push_back(FdbPqlPage{pg.off + pg.body, (uint32_t)t->lz_frags.size(), fdb_pqs_fragments(pg.body)});
+      for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT) {
+        const uint32_t len = (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at);
+        t->lz_frags.push_back(FdbPqlFrag{pg.off + at, len, (uint32_t)(t->lz_pages.size() - 1), fdb_pql_stop(at, len, pg.body), fdb_pql_reach(at, len, pg.body)});
+      }
+      continue;
+    }
     t->pages.push_back(FdbPqsPage{(uint32_t)t->frags.size(), fdb_pqs_fragments(pg.body)});
     for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT)
       t->frags.push_back(FdbPqsFrag{pg.off + at, (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at), (uint32_t)(t->pages.size() - 1)});
   }
-  if (t->frags.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 fragments to compress");
+  if (t->frags.size() + t->lz_frags.size() > 0x7FFFFFFFull / 2) throw Error(FDB_ERR_UNSUPPORTED, "parquet write: more than 2^30 fragments to compress");
   const size_t n_frags = std::max<size_t>(t->frags.size(), 1);
-  c->scratch.alloc(n_frags * fdb_pqs_slot_bytes());
+  t->lz_scratch = n_frags * fdb_pqs_slot_bytes();
+  c->scratch.alloc(t->lz_scratch + t->lz_frags.size() * fdb_pql_slot_bytes());
   const unsigned char* d_blob = (const unsigned char*)c->upload(L.body_blob.data(), L.body_blob.size(), "hipMemcpyAsync(page body pieces)");
   const FdbPqsRange* d_pieces = (const FdbPqsRange*)c->upload(t->pieces.data(), t->pieces.size() * sizeof(FdbPqsRange), "hipMemcpyAsync(page body piece table)");
   t->d_frags = (const FdbPqsFrag*)c->upload(t->frags.data(), t->frags.size() * sizeof(FdbPqsFrag), "hipMemcpyAsync(fragment table)");
@@ -1652,22 +1679,38 @@ static void pqs_compress_pass(PqwCall* c, const PqwLayout& L, PqsTables* t) {
   t->d_frag_bytes = (uint32_t*)c->cs.alloc(n_frags * 4);
   t->d_frag_off = (uint32_t*)c->cs.alloc(n_frags * 4);
   uint32_t* d_page_elements = (uint32_t*)c->cs.alloc(std::max<size_t>(t->pages.size(), 1) * 4);
-  t->page_elements.assign(t->pages.size(), 0);
+  t->snappy_elements.assign(t->pages.size(), 0);
   hip_check(fdb_launch_pqs_place(d_pieces, (int32_t)t->pieces.size(), d_blob, c->image.p, c->stream), "parquet write: body piece launch");
   hip_check(fdb_launch_pqs_compress(t->d_frags, (int32_t)t->frags.size(), c->image.p, c->scratch.p, t->d_frag_bytes, c->stream), "parquet write: compress launch");
   c->timed("pqwrite compress");
   hip_check(fdb_launch_pqs_scan(d_pages, (int32_t)t->pages.size(), t->d_frag_bytes, t->d_frag_off, d_page_elements, c->stream), "parquet write: compressed size scan launch");
-  if (!t->pages.empty()) hip_check(hipMemcpyAsync(t->page_elements.data(), d_page_elements, t->pages.size() * 4, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(compressed page sizes)");
+  if (!t->pages.empty()) hip_check(hipMemcpyAsync(t->snappy_elements.data(), d_page_elements, t->pages.size() * 4, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(compressed page sizes)");
+  if (!t->lz_pages.empty()) {  // (a page without a byte has no fragment, and still a block: its closing sequence)
+    t->d_lz_frags = (const FdbPqlFrag*)c->upload(t->lz_frags.data(), t->lz_frags.size() * sizeof(FdbPqlFrag), "hipMemcpyAsync(LZ4 fragment table)");
+    t->d_lz_pages = (const FdbPqlPage*)c->upload(t->lz_pages.data(), t->lz_pages.size() * sizeof(FdbPqlPage), "hipMemcpyAsync(LZ4 page table)");
+    const size_t n_lz = std::max<size_t>(t->lz_frags.size(), 1);
+    t->d_lz_outs = (FdbPqlOut*)c->cs.alloc(n_lz * sizeof(FdbPqlOut));
+    t->d_lz_places = (FdbPqlPlace*)c->cs.alloc(n_lz * sizeof(FdbPqlPlace));
+    t->d_lz_closes = (FdbPqlPlace*)c->cs.alloc(t->lz_pages.size() * sizeof(FdbPqlPlace));
+    uint32_t* d_lz_bytes = (uint32_t*)c->cs.alloc(t->lz_pages.size() * 4);
+    t->lz_bytes.assign(t->lz_pages.size(), 0);
+    hip_check(fdb_launch_pql_compress(t->d_lz_frags, (int32_t)t->lz_frags.size(), c->image.p, c->scratch.p + t->lz_scratch, t->d_lz_outs, c->stream), "parquet write: LZ4 compress launch");
+    c->timed("pqwrite lz compress");
+    hip_check(fdb_launch_pql_scan(t->d_lz_pages, (int32_t)t->lz_pages.size(), t->d_lz_outs, t->d_lz_places, t->d_lz_closes, d_lz_bytes, c->stream), "parquet write: LZ4 size scan launch");
+    hip_check(hipMemcpyAsync(t->lz_bytes.data(), d_lz_bytes, t->lz_pages.size() * 4, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(LZ4 page sizes)");
+  }
   c->wait();
   c->pt.mark("pqwrite scan");
+  size_t next_snappy = 0, next_lz = 0;
+  for (const PqwLayout::Page& pg : L.pages) t->page_elements.push_back(pg.codec == PQW_LZ4_RAW ? t->lz_bytes[next_lz++] : t->snappy_elements[next_snappy++]);
 }
 
-// ONE gather launch moves the fragments' elements and the chunks of the uncompressed columns from the staging image (`L`) to where the
-// final layout `F` wants them in the final image.
+// ONE gather launch moves the SNAPPY fragments' elements and the chunks of the uncompressed columns from the staging image (`L`) to
+// where the final layout `F` wants them in the final image — with or without a SNAPPY column, the chunks are its ranges; a second
+// one, with an LZ4_RAW column, writes the LZ4 blocks.
 static void pqs_gather_pass(PqwCall* c, const PqwLayout& L, const PqwLayout& F, PqsTables* t) {
   std::vector<uint64_t>& page_dst = t->page_dst; std::vector<FdbPqsRange>& ranges = t->ranges;
-  page_dst.resize(F.pages.size());
-  for (size_t i = 0; i < F.pages.size(); i++) page_dst[i] = F.pages[i].off;
+  for (const PqwLayout::Page& pg : F.pages) (pg.codec == PQW_LZ4_RAW ? t->lz_page_dst : page_dst).push_back(pg.off);
   for (size_t k = 0; k < L.chunk_off.size(); k++) {  // the chunks of the uncompressed columns, in pieces a workgroup moves at a time
     if (L.chunk_codec[k] != 0) continue;
     for (uint64_t at = 0; at < L.chunk_len[k]; at += FDB_PQS_COPY_PIECE)
@@ -1680,6 +1723,12 @@ static void pqs_gather_pass(PqwCall* c, const PqwLayout& L, const PqwLayout& F, 
   hip_check(fdb_launch_pqs_gather(t->d_frags, (int32_t)t->frags.size(), t->d_frag_bytes, t->d_frag_off, d_page_dst, c->scratch.p, d_ranges, (int32_t)ranges.size(), c->image.p, c->final_image.p,
                                   c->stream), "parquet write: gather launch");
   c->timed("pqwrite gather");
+  if (t->lz_pages.empty()) return;
+  if (t->lz_page_dst.size() != t->lz_pages.size()) throw Error(FDB_ERR_STATE, "parquet write: the final layout's LZ4 pages do not match the staging image's");
+  const uint64_t* d_lz_dst = (const uint64_t*)c->upload(t->lz_page_dst.data(), t->lz_page_dst.size() * 8, "hipMemcpyAsync(LZ4 page offsets)");
+  hip_check(fdb_launch_pql_gather(t->d_lz_frags, (int32_t)t->lz_frags.size(), t->d_lz_pages, (int32_t)t->lz_pages.size(), t->d_lz_outs, t->d_lz_places, t->d_lz_closes, d_lz_dst,
+                                  c->scratch.p + t->lz_scratch, c->image.p, c->final_image.p, c->stream), "parquet write: LZ4 gather launch");
+  c->timed("pqwrite lz gather");
 }
 
 // The one ending: the pinned file, every bitset straight to its place in it, the image in one parallel copy, the host's holes and tail.

@@ -12,6 +12,7 @@
 #include "fdb_pqdelta.h"
 #include "fdb_pqdict.h"
 #include "fdb_pqruns.h"
+#include "fdb_pqlz4.h"
 #include "fdb_pqsnappy.h"
 #include "fdb_pqstats.h"
 #include "fdb_pqwrite.h"
@@ -21,6 +22,7 @@
 
 namespace fdb {
 
+constexpr int PQW_SNAPPY = 1, PQW_LZ4_RAW = 7;  // parquet.thrift CompressionCodec, the two the writer compresses with
 constexpr int PQW_NO_VALUES = -1;  // PqwColumn::pq_kind of a BYTE_ARRAY column that is all NULL and has an empty dictionary
 
 // A column as the writer is handed it: the resident form, on the device (fdb_batch_to_parquet) or in host arrays (the self-test).
@@ -40,7 +42,7 @@ struct PqwColumn {
   int physical = 0;              // parquet Type
   bool is_u64 = false, utf8 = false, optional = false;
   int delta_slot = -1;            // >= 0: written DELTA_BINARY_PACKED, and its place among the columns that are (the tables of fdb_pqdelta.h)
-  int codec = 0;                  // parquet CompressionCodec of the chunk's pages: 0 UNCOMPRESSED, 1 SNAPPY
+  int codec = 0;                  // parquet CompressionCodec of the chunk's pages: 0 UNCOMPRESSED, PQW_SNAPPY, PQW_LZ4_RAW
   int run_values = -1, run_levels = -1;  // >= 0: the pages' indices / definition levels are cut into runs (fdb_pqruns.h), and the stream's place in the tables of that
   uint32_t width = 0;
   uint64_t entries = 0;
@@ -70,10 +72,10 @@ struct PqwLayout {
   void put(uint64_t off, const std::string& s);
   // With compressed columns the file is laid out twice — as it is before compression (the staging image) and as it is written — and
   // both layouts list the data pages of the compressed columns in the same order: in the staging layout `off` / `body` are where a
-  // page's body starts and how long it is, in the final one where the elements of its Snappy block go. `body_pieces` (of `body_blob`):
+  // page's body starts and how long it is, in the final one where the elements of its Snappy block, or its LZ4 block, go. `body_pieces` (of `body_blob`):
   // the host's bytes inside those bodies, which have to be in the staging image before the compressor reads it. chunk_off / chunk_len:
   // every column's chunk, which for an uncompressed column moves from one image to the other as it is.
-  struct Page { uint64_t off, body; };
+  struct Page { uint64_t off, body; int codec; };
   std::vector<Page> pages;
   std::string body_blob;
   std::vector<Piece> body_pieces;
@@ -130,7 +132,7 @@ void pqx_minmax_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, Pq
 
 // What one call asks for beside the record: the arguments of fdb_batch_to_parquet_runs, which the narrower entry points fill in part.
 // The pointers are borrowed; null / 0: not asked. `encodings`: per column 0 (as ever) or 1 (DELTA_BINARY_PACKED; I64 and U64 columns
-// only); `codecs`: per column 0 (UNCOMPRESSED) or 1 (SNAPPY); n_encodings / n_codecs: 0 or the column count.
+// only); `codecs`: per column 0 (UNCOMPRESSED), 1 (SNAPPY) or 7 (LZ4_RAW); n_encodings / n_codecs: 0 or the column count.
 struct PqwSpec {
   const fdb_parquet_write_options* options = nullptr;
   const int8_t* encodings = nullptr; int32_t n_encodings = 0;
@@ -153,6 +155,8 @@ size_t pqr_streams(const std::vector<PqwColumn>& cols);
 size_t pqw_compressed_columns(const std::vector<PqwColumn>& cols);
 // The Snappy block of `n` bytes: the preamble and every fragment's elements, by the host walk of fdb_pqsnappy.h.
 std::string pqs_block_host(const unsigned char* body, size_t n);
+// The LZ4 block of `n` bytes, bare, by the host walk of fdb_pqlz4.h.
+std::string pql_block_host(const unsigned char* body, size_t n);
 FdbPqwGeom pqw_geometry(int64_t rows, int32_t page_rows, size_t n_cols);
 
 // Used-entry dictionaries (fdb_parquet_group_options::dictionaries = 1; fdb_pqdict.h): the pruned columns, each with its place in ONE
@@ -201,7 +205,7 @@ std::vector<PqwPlan> pqw_parts(PqwPlan&& plan, const PqwSpec& spec);
 // runs, as the run survey found them — held to the rule's bounds before they are trusted; looked at only where fdb_pqr_active says the
 // rule applies. `page_elements` == nullptr: every page as it is before compression, whatever the columns' codecs — the file itself
 // when no column has one, else the staging image. Otherwise the file as written: [compressed column × n_pages + page] = the bytes of
-// the elements of the page's Snappy block (the preamble not counted), as the compressor found them.
+// the elements of the page's Snappy block (the preamble not counted) or of its whole LZ4 block, as the compressor found them.
 struct PqwSizes {
   const std::vector<FdbPqwPageStat>& stats;  // the survey's
   const std::vector<uint32_t>*delta_bytes = nullptr, *run_bytes = nullptr, *page_elements = nullptr;

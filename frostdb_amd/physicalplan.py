@@ -371,12 +371,12 @@ def _parquet_encodings(encodings, names):
     return (ctypes.c_int8 * max(1, len(wanted)))(*[PARQUET_ENCODINGS[e] for e in wanted]), len(wanted)
 
 
-PARQUET_WRITE_CODECS = {None: 0, "uncompressed": 0, "snappy": 1}
+PARQUET_WRITE_CODECS = {None: 0, "uncompressed": 0, "snappy": 1, "lz4": 7}  # "lz4": parquet's LZ4_RAW, the bare block
 
 
 def _parquet_codecs(compression, names):
-    """`compression`: "snappy" (every column), a sequence with one entry per column or a dict by column name; an entry is None /
-    "uncompressed" or "snappy". Returns the int8 array and its length."""
+    """`compression`: "snappy" or "lz4" (every column), a sequence with one entry per column or a dict by column name; an entry is
+    None / "uncompressed", "snappy" or "lz4" (LZ4_RAW). Returns the int8 array and its length."""
     if isinstance(compression, str):
         wanted = [compression] * len(names)
     elif isinstance(compression, dict):
@@ -390,7 +390,7 @@ def _parquet_codecs(compression, names):
             _raise(FDB_ERR_INVALID, "parquet write: `codecs` has 0 entries, the record %d columns" % len(names))
     for e in wanted:
         if not (e is None or isinstance(e, str)) or e not in PARQUET_WRITE_CODECS:
-            _raise(FDB_ERR_INVALID, "parquet write: unknown codec %r (None, 'uncompressed' or 'snappy')" % (e,))
+            _raise(FDB_ERR_INVALID, "parquet write: unknown codec %r (None, 'uncompressed', 'snappy' or 'lz4')" % (e,))
     return (ctypes.c_int8 * max(1, len(wanted)))(*[PARQUET_WRITE_CODECS[e] for e in wanted]), len(wanted)
 
 
@@ -565,7 +565,7 @@ def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=
                            sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None) -> bytes:
     """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
     made without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
-    fdb_selftest_parquet_write_compressed, with `statistics`, `index_size_limit` or `sorting_columns`
+    fdb_selftest_parquet_write_compressed — "snappy" by the host walk of fdb_pqsnappy.h, "lz4" by that of fdb_pqlz4.h —, with `statistics`, `index_size_limit` or `sorting_columns`
     fdb_selftest_parquet_write_indexed, with `bloom_filters` or `bloom_bits_per_value` fdb_selftest_parquet_write_filtered): the same
     layout, headers and footer, the kernels replaced by a host walk of the code they compile. With `runs`
     fdb_selftest_parquet_write_runs: the run passes walked as well; with `row_group_rows` or `dictionaries`
@@ -924,7 +924,9 @@ class ResidentBatch:
         "snappy" (every column), a sequence per column or a dict by name of None / "uncompressed" / "snappy": every page of such a
         column — dictionary page and data pages — is written as a Snappy block, compressed on the device in fragments of 32 KiB
         (fdb_batch_to_parquet_compressed), and only the compressed file crosses the link; for the length of the call the device holds
-        about three times the file body. DELTA and SNAPPY go together. `statistics`: None, "chunk" — Statistics.min_value / max_value
+        about three times the file body. DELTA and SNAPPY go together. "lz4" in place of "snappy": the pages are LZ4_RAW blocks
+        (ColumnMetaData.codec 7, the bare block without a preamble), found by the same match search, one block per page; SNAPPY,
+        LZ4_RAW and uncompressed columns may stand side by side in one file. `statistics`: None, "chunk" — Statistics.min_value / max_value
         per column chunk and FileMetaData.column_orders, the bounds found by one more pass on the device — or "page": the same and the
         Parquet page index (ColumnIndex and OffsetIndex per column, between the pages and the footer), which FrostDB's own scan prunes
         row groups with; `index_size_limit`: the bytes a string bound of the ColumnIndex is cut to (0 = 16); `sorting_columns`: a

@@ -604,9 +604,23 @@ FDB_API int fdb_selftest_parquet_write_encoded(struct ArrowArray* batch, struct 
  * the file out again (compressing the dictionary pages itself: they are host bytes), one gather launch moves every fragment's elements
  * and the chunks of the uncompressed columns into the final image, and that — the smaller one — is what crosses the link. Device memory
  * for the length of the call: staging + scratch + final image, about 3 × the file body — accepted; all of it is the call's own and
- * freed on every path. Refused before anything is launched: FDB_ERR_INVALID — n_codecs neither 0 nor the column count, an entry outside
- * 0 … 1; and everything the calls above refuse, unchanged. fdb_parquet_write_options keeps its layout. */
-/* codecs: per column parquet's CompressionCodec number, 0 = UNCOMPRESSED, 1 = SNAPPY; n_codecs: 0 (all 0) or the batch's column count */
+ * freed on every path. Refused before anything is launched: FDB_ERR_INVALID — n_codecs neither 0 nor the column count, an entry that
+ * is none of 0, 1 and 7; and everything the calls above refuse, unchanged. fdb_parquet_write_options keeps its layout.
+ * A column asked to be LZ4_RAW (7, the COMPRESSION_LZ4_RAW of the same schema.go lines): every page of it is ONE LZ4 block, bare —
+ * parquet's LZ4_RAW has no preamble, uncompressed_page_size is the body's length U — and ColumnMetaData.codec is 7; sizes and offsets
+ * follow the compressed sizes as for SNAPPY. The matches are found exactly as above, fragment by fragment (no match reaches before its
+ * fragment's first byte: offsets stay below 32 768, inside LZ4's 65 535 and the 65 472 the device decoder reaches back), under the block
+ * format's two end conditions, which are the BODY's: a position may win only if it is at most U − 12, and a match is extended only up to
+ * body position U − 5 — liblz4 refuses a block that ends otherwise. They touch the last fragment and, when that one is shorter than 12
+ * bytes, the one before it. The sequences of all fragments in order form the block: a sequence's literals are every body byte since the
+ * previous match's end, across fragment boundaries and whole fragments without a match (a run may exceed 32 768 literals); lengths are
+ * coded as the format says (nibble 15, bytes of 255, a last byte below 255); the block ends in a sequence of literals only, and a body
+ * of 0 bytes is the one byte `00`. A page never exceeds U + U/255 + 16 bytes, LZ4_compressBound. The rule is spelled out in fdb_pqlz4.h.
+ * On the device (fdb_pqlz4.hip) a wave per fragment leaves the literals before its first match and behind its last as counts and the
+ * sequences between them in scratch; a walk per page with the pending literals as its carry places every fragment and the closing
+ * sequence and sizes the page; a gather writes the joined runs from the staging image and the scratch's middles. SNAPPY, LZ4_RAW and
+ * uncompressed columns may stand side by side; a call without an LZ4_RAW column launches, allocates and copies nothing of this. */
+/* codecs: per column parquet's CompressionCodec number, 0 = UNCOMPRESSED, 1 = SNAPPY, 7 = LZ4_RAW; n_codecs: 0 (all 0) or the batch's column count */
 FDB_API int fdb_batch_to_parquet_compressed(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_compressed(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, uint8_t** bytes, int64_t* n_bytes);
 /* The same two calls with min / max statistics, the Parquet page index and RowGroup.sorting_columns as well — what FrostDB's own scan

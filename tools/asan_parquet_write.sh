@@ -4,7 +4,8 @@
 # the survey and encode passes (fdb_pqwrite.h: the page geometry, bit positions and word assembly the kernels compile) and of the
 # DELTA_BINARY_PACKED passes (fdb_pqdelta.h) over seeded random records and options, with fdb_arrow.cpp's dictionary constructors; and the
 # SNAPPY compressor's host walk (fdb_pqsnappy.h) over the same records with codecs per column at random and over bodies around one and
-# two fragments, every page inflated again by the library's host decoder (fdb_codec.cpp).
+# two fragments, every page inflated again by the library's host decoder (fdb_codec.cpp); the codec drawn per column is UNCOMPRESSED,
+# SNAPPY or LZ4_RAW, and the LZ4_RAW compressor's host walk (fdb_pqlz4.h) runs over the same pages and bodies, inflated again by fdb::lz4_raw.
 # Every record is also written with index options at random — statistics, a cut limit, sorting columns: the min / max pass's host walk
 # (fdb_pqstats.h), chunk bounds, ColumnIndex and OffsetIndex — and the index is read back by a small thrift reader of the program's own.
 # … and with bloom filter options at random — columns and bits per value: the insert pass's host walk (fdb_pqbloom.h), the filters'

@@ -6,7 +6,10 @@
 // wrote is read back with a bit reader and a DELTA decoder of this file's own. Some columns, DELTA ones among them, are asked to be SNAPPY:
 // the compressor's host walk (fdb_pqsnappy.h) runs over the staging image's page bodies, the file is laid out again, and every page of
 // the final file — dictionary pages too — is inflated by the library's host decoder (fdb_codec.cpp snappy_block) into a buffer of exactly
-// the body's size and compared with the body; bodies of 0 … 2 fragments + 1 bytes of several kinds go through the same two.
+// the body's size and compared with the body; bodies of 0 … 2 fragments + 1 bytes of several kinds go through the same two. Others are
+// asked to be LZ4_RAW (codec 7): the host walk of fdb_pqlz4.h makes each page body one block, which fdb::lz4_raw inflates again and a
+// sequence reader of this file's own holds to the block format's end conditions; the same bodies, and more around the fragment size,
+// go through that walk too.
 // Every record is also written with index options at random (statistics 0 … 2, a cut limit, sorting columns): the min / max pass's host
 // walk (pqx_minmax_host: the keys of fdb_pqstats.h that the kernel compiles) fills the table, the layout writes chunk bounds, ColumnIndex
 // and OffsetIndex, and a small thrift reader of this file's own reads the index back out of a buffer sized exactly and holds every
@@ -140,9 +143,38 @@ static void check_block(const std::string& block, const unsigned char* body, siz
   CHECK(n == 0 || std::memcmp(out.data(), body, n) == 0);
 }
 
-// Bodies around nothing, one and two fragments, of several kinds, through the block compressor and the host decoder.
+// … an LZ4_RAW block: it inflates under fdb::lz4_raw to `body`, stays within LZ4_compressBound, and — what liblz4 insists on and the
+// library's own decoder does not — its sequences end as the format says: no match starts behind n − 12 or ends behind n − 5, the last
+// sequence has none.
+static void check_lz4_block(const std::string& block, const unsigned char* body, size_t n) {
+  std::vector<uint8_t> exact(block.begin(), block.end()), out(n);
+  CHECK(exact.size() >= 1 && exact.size() <= n + n / 255 + 16);
+  CHECK(lz4_raw(exact.data(), exact.size(), out.data(), n));
+  CHECK(n == 0 || std::memcmp(out.data(), body, n) == 0);
+  size_t at = 0, pos = 0;
+  const auto length = [&](size_t v) { if (v == 15) { uint8_t b; do { CHECK(at < exact.size()); b = exact[at++]; v += b; } while (b == 255); } return v; };
+  for (;;) {
+    CHECK(at < exact.size());
+    const uint8_t token = exact[at++];
+    const size_t lit = length(token >> 4);
+    CHECK(at + lit <= exact.size());
+    at += lit; pos += lit;
+    if (at == exact.size()) { CHECK((token & 15) == 0); break; }
+    CHECK(at + 2 <= exact.size());
+    const size_t off = exact[at] | ((size_t)exact[at + 1] << 8);
+    at += 2;
+    const size_t len = length(token & 15) + 4;
+    CHECK(off >= 1 && off <= pos % FDB_PQS_FRAGMENT && pos / FDB_PQS_FRAGMENT == (pos + len - 1) / FDB_PQS_FRAGMENT);
+    CHECK(pos + 12 <= n && pos + len + 5 <= n);
+    pos += len;
+  }
+  CHECK(pos == n);
+}
+
+// Bodies around nothing, one and two fragments, of several kinds, through the block compressors and the host decoders.
 static void snappy_bodies(uint64_t* seed) {
-  static const size_t sizes[] = {0, 1, 2, 3, 4, 5, 63, 64, 65, 4096, FDB_PQS_FRAGMENT - 1, FDB_PQS_FRAGMENT, FDB_PQS_FRAGMENT + 1, 2 * FDB_PQS_FRAGMENT - 1, 2 * FDB_PQS_FRAGMENT, 2 * FDB_PQS_FRAGMENT + 1};
+  static const size_t sizes[] = {0, 1, 2, 3, 4, 5, 11, 12, 13, 14, 17, 18, 63, 64, 65, 4096, FDB_PQS_FRAGMENT - 1, FDB_PQS_FRAGMENT, FDB_PQS_FRAGMENT + 1, FDB_PQS_FRAGMENT + 4, FDB_PQS_FRAGMENT + 5,
+                                 FDB_PQS_FRAGMENT + 11, FDB_PQS_FRAGMENT + 12, FDB_PQS_FRAGMENT + 13, 2 * FDB_PQS_FRAGMENT - 1, 2 * FDB_PQS_FRAGMENT, 2 * FDB_PQS_FRAGMENT + 1, 2 * FDB_PQS_FRAGMENT + 3};
   for (size_t n : sizes) {
     for (int kind = 0; kind < 5; kind++) {  // 0 noise, 1 one byte, 2 few distinct 8-byte values, 3 runs of random periods and lengths, 4 noise with repeats from far back
       std::vector<unsigned char> body(n);
@@ -157,6 +189,7 @@ static void snappy_bodies(uint64_t* seed) {
       }
       const std::vector<unsigned char> exact(body);  // (sized exactly: a walk that reads past the body is caught)
       check_block(pqs_block_host(exact.data(), exact.size()), exact.data(), n);
+      check_lz4_block(pql_block_host(exact.data(), exact.size()), exact.data(), n);
     }
   }
 }
@@ -747,7 +780,7 @@ static void one_record(uint64_t* seed, int round) {
   }
   // the same record with a codec per column at random (three rounds in four): what fdb_selftest_parquet_write_compressed does, step by step
   std::vector<int8_t> codecs;
-  for (size_t k = 0; k < n_cols; k++) codecs.push_back((int8_t)(rnd(seed) & 1));
+  for (size_t k = 0; k < n_cols; k++) { static const int8_t drawn[3] = {0, 1, 7}; codecs.push_back(drawn[rnd(seed) % 3]); }
   if ((round & 3) != 3) {
     spec.codecs = codecs.data(); spec.n_codecs = (int32_t)n_cols; spec.index = &iopt;
     PqwPlan compressed_plan = pqw_plan(in, rows, spec); compressed_plan.x = x;
@@ -763,7 +796,11 @@ static void one_record(uint64_t* seed, int round) {
       CHECK(pg.off + pg.body <= S.body_bytes);
       CHECK(std::memcmp(staging.data() + pg.off, file + pg.off, (size_t)pg.body) == 0);  // a whole body: what the uncompressed file holds there
       std::string e;
-      for (uint64_t at = 0; at < pg.body; at += FDB_PQS_FRAGMENT) {
+      if (pg.codec == PQW_LZ4_RAW) {  // the whole block, by the walk over a body sized exactly
+        const std::vector<unsigned char> body(staging.begin() + (size_t)pg.off, staging.begin() + (size_t)(pg.off + pg.body));
+        e = pql_block_host(body.data(), body.size());
+      }
+      for (uint64_t at = 0; at < pg.body && pg.codec != PQW_LZ4_RAW; at += FDB_PQS_FRAGMENT) {
         const uint32_t len = (uint32_t)std::min<uint64_t>(FDB_PQS_FRAGMENT, pg.body - at);
         const std::vector<unsigned char> frag(staging.begin() + (size_t)(pg.off + at), staging.begin() + (size_t)(pg.off + at) + len);  // (sized exactly)
         std::vector<unsigned char> out(fdb_pqs_bound(len));
@@ -794,6 +831,11 @@ static void one_record(uint64_t* seed, int round) {
     pqw_finish(F, out_file);
     CHECK(std::memcmp(out_file, "PAR1", 4) == 0 && std::memcmp(out_file + out_bytes - 4, "PAR1", 4) == 0);
     for (size_t i = 0; i < F.pages.size(); i++) {  // the preamble sits in front of the elements; the block inflates to the body
+      CHECK(F.pages[i].codec == S.pages[i].codec);
+      if (F.pages[i].codec == PQW_LZ4_RAW) {  // (bare: no preamble)
+        check_lz4_block(std::string((const char*)out_file + F.pages[i].off, elements[i].size()), staging.data() + S.pages[i].off, (size_t)S.pages[i].body);
+        continue;
+      }
       size_t pl = 1;
       for (uint64_t v = F.pages[i].body; v >= 0x80; v >>= 7) pl++;
       CHECK(F.pages[i].off >= pl);
@@ -803,8 +845,9 @@ static void one_record(uint64_t* seed, int round) {
       if (cc[k].codec == 0 || cc[k].pq_kind != FDB_PQW_INDEX) continue;
       std::string body;
       for (const std::string& v : cc[k].dict->values) { const uint32_t n = (uint32_t)v.size(); body.append((const char*)&n, 4); body += v; }
-      const std::string block = pqs_block_host((const unsigned char*)body.data(), body.size());
-      check_block(block, (const unsigned char*)body.data(), body.size());
+      const bool lz4 = cc[k].codec == PQW_LZ4_RAW;
+      const std::string block = lz4 ? pql_block_host((const unsigned char*)body.data(), body.size()) : pqs_block_host((const unsigned char*)body.data(), body.size());
+      if (lz4) check_lz4_block(block, (const unsigned char*)body.data(), body.size()); else check_block(block, (const unsigned char*)body.data(), body.size());
       bool found = false;
       for (size_t at = (size_t)F.chunk_off[k]; at + block.size() <= (size_t)(F.chunk_off[k] + F.chunk_len[k]) && at < (size_t)F.chunk_off[k] + 32 && !found; at++)
         found = std::memcmp(out_file + at, block.data(), block.size()) == 0;
@@ -836,8 +879,9 @@ static void refusals() {
   CHECK(enc_code(&delta, 1) == FDB_OK && enc_code(nullptr, 0) == FDB_OK);
   CHECK(enc_code(&two, 1) == FDB_ERR_INVALID && enc_code(both, 2) == FDB_ERR_INVALID && enc_code(nullptr, 1) == FDB_ERR_INVALID);
   const auto codec_code = [&](const int8_t* c, int32_t n) { try { pqw_columns(in, 8, PqwSpec{&plain_opt, nullptr, 0, c, n}, &pr); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
-  const int8_t minus = -1;
-  CHECK(codec_code(&delta, 1) == FDB_OK && codec_code(nullptr, 0) == FDB_OK);
+  const int8_t minus = -1, lz4 = 7, five = 5, six = 6, eight = 8;
+  CHECK(codec_code(&delta, 1) == FDB_OK && codec_code(nullptr, 0) == FDB_OK && codec_code(&lz4, 1) == FDB_OK);
+  CHECK(codec_code(&five, 1) == FDB_ERR_INVALID && codec_code(&six, 1) == FDB_ERR_INVALID && codec_code(&eight, 1) == FDB_ERR_INVALID);
   CHECK(codec_code(&two, 1) == FDB_ERR_INVALID && codec_code(&minus, 1) == FDB_ERR_INVALID && codec_code(both, 2) == FDB_ERR_INVALID && codec_code(nullptr, 1) == FDB_ERR_INVALID);
   const auto index_code = [&](const fdb_parquet_index_options& o, size_t n) { try { pqx_plan(&o, n); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK; };
   const fdb_parquet_sorting_column s0{0, 0, 0, {0, 0}}, s2{2, 1, 1, {0, 0}}, twice[2] = {s0, s0}, ok2[2] = {s2, s0};

@@ -21,6 +21,12 @@ own figures are the SNAPPY call's — among the phases place_compress_ms (the ho
 size scan with the wait for the page sizes), final_layout_ms and gather_ms — and the uncompressed PLAIN call on the same record in the
 same process goes into the line as with --delta, with plain_floor_ms, the bare copy of ITS file's bytes, beside floor_ms, that of the
 compressed file's.
+With --lz4 every column is written LZ4_RAW and `timestamp` DELTA_BINARY_PACKED + LZ4_RAW (codec 7 at fdb_batch_to_parquet_compressed): the
+line's own figures are the LZ4 call's — among the phases place_ms (the host's body bytes placed; the SNAPPY compress launch has nothing to
+do), lz_compress_ms (the compress kernel of fdb_pqlz4.hip), scan_ms (the walk with the carry and the wait for the page sizes),
+final_layout_ms, gather_ms (the launch that moves uncompressed chunks: none here) and lz_gather_ms — and both the --snappy call
+(snappy_file_bytes, snappy_to_parquet_ms with its spread, snappy_place_compress_ms / _scan_ms / _final_layout_ms / _gather_ms) and the
+uncompressed PLAIN call on the same record in the same process go into the same line.
 With --stats the record is written uncompressed and PLAIN with statistics="page" (fdb_batch_to_parquet_indexed): chunk bounds, ColumnIndex
 and OffsetIndex of every column. The line's own figures are that call's — among the phases stats_ms, the min / max pass of
 fdb_pqstats.hip timed apart (rank upload, table reset, kernel, its wait), and wait_ms, what is then left of the survey's wait — and the
@@ -53,7 +59,7 @@ figures are the grouped call's — its phases are the SUM of a call's marks, bot
 parent path on the same record in the same process goes into the line as with --delta, with its spread and plain_floor_ms.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --stats | --bloom | --runs | [--used [--fraction F]] [--groups R]] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --lz4 | --stats | --bloom | --runs | [--used [--fraction F]] [--groups R]] [--out FILE]
 """
 import argparse
 import io
@@ -78,6 +84,7 @@ LABELS = [10, 50, 100, 500, 1000]
 PHASES = ["survey", "layout", "encode", "copy", "host tail"]
 DELTA_PHASES = ["delta compact", "delta survey", "delta encode"]
 SNAPPY_PHASES = ["compress", "scan", "final layout", "gather"]
+LZ4_PHASES = ["lz compress", "lz gather"]
 STATS_PHASES = ["stats", "wait"]
 BLOOM_PHASES = ["bloom insert", "bloom copy"]
 BLOOM_COLUMNS = ["timestamp", "labels.l4"]
@@ -131,7 +138,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES + DICT_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + LZ4_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES + DICT_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = (sum(us) / reps if groups else statistics.median(us)) / 1e3 if us else None
     return out
@@ -146,6 +153,7 @@ def main():
     ap.add_argument("--baseline-reps", type=int, default=3)
     ap.add_argument("--delta", action="store_true", help="write `timestamp` DELTA_BINARY_PACKED; the PLAIN call goes into the same line")
     ap.add_argument("--snappy", action="store_true", help="write every column SNAPPY and `timestamp` DELTA + SNAPPY; the uncompressed PLAIN call goes into the same line")
+    ap.add_argument("--lz4", action="store_true", help="write every column LZ4_RAW and `timestamp` DELTA + LZ4_RAW; the --snappy call and the uncompressed PLAIN call go into the same line")
     ap.add_argument("--stats", action="store_true", help="write statistics and the page index (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--bloom", action="store_true", help="write bloom filters on `timestamp` and `labels.l4` (uncompressed, PLAIN); the call without them goes into the same line")
     ap.add_argument("--runs", action="store_true", help="sort the record by its label columns and write it with runs=True (uncompressed); the call without runs, and both calls on the unsorted record, go into the same line")
@@ -154,9 +162,9 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="write row groups of this many rows (a multiple of 64; alone or with --used); the ungrouped call goes into the same line")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    assert args.delta + args.snappy + args.stats + args.bloom + args.runs + args.used <= 1, "--delta, --snappy, --stats, --bloom, --runs or --used"
+    assert args.delta + args.snappy + args.lz4 + args.stats + args.bloom + args.runs + args.used <= 1, "--delta, --snappy, --lz4, --stats, --bloom, --runs or --used"
     assert 0.0 < args.fraction <= 1.0 and (args.used or args.fraction == 1.0), "--fraction goes with --used"
-    assert args.groups == 0 or (args.groups > 0 and args.groups % 64 == 0 and args.delta + args.snappy + args.stats + args.bloom + args.runs == 0), "--groups R: a multiple of 64, alone or with --used"
+    assert args.groups == 0 or (args.groups > 0 and args.groups % 64 == 0 and args.delta + args.snappy + args.lz4 + args.stats + args.bloom + args.runs == 0), "--groups R: a multiple of 64, alone or with --used"
     record = make_record(args.rows, fraction=args.fraction)
     rb = pp.ResidentBatch(record)
     del record
@@ -164,8 +172,8 @@ def main():
     if args.runs:
         unsorted, rb = rb, rb.sort([("labels.l%d" % k,) for k in range(len(LABELS))] + [("timestamp",)])
     try:
-        encodings = {"timestamp": "delta"} if args.delta or args.snappy else None
-        compression = "snappy" if args.snappy else None
+        encodings = {"timestamp": "delta"} if args.delta or args.snappy or args.lz4 else None
+        compression = "snappy" if args.snappy else "lz4" if args.lz4 else None
         stats = "page" if args.stats else None
         bloom = BLOOM_COLUMNS if args.bloom else None
         runs = True if args.runs else None
@@ -175,10 +183,10 @@ def main():
         md = pq.ParquetFile(io.BytesIO(data)).metadata
         row_groups = -(-args.rows // args.groups) if args.groups else 1
         assert md.num_rows == args.rows and md.num_row_groups == row_groups
-        if args.delta or args.snappy:
+        if args.delta or args.snappy or args.lz4:
             assert set(md.row_group(0).column(0).encodings) == {"DELTA_BINARY_PACKED"}
-        if args.snappy:
-            assert all(md.row_group(0).column(j).compression == "SNAPPY" for j in range(md.num_columns))
+        if args.snappy or args.lz4:  # (pyarrow's metadata says "LZ4" for codec 7)
+            assert all(md.row_group(0).column(j).compression == ("SNAPPY" if args.snappy else "LZ4") for j in range(md.num_columns))
             column_bytes = {md.row_group(0).column(j).path_in_schema: [md.row_group(0).column(j).total_compressed_size, md.row_group(0).column(j).total_uncompressed_size] for j in range(md.num_columns)}
         if args.stats:
             assert all(md.row_group(0).column(j).has_column_index and md.row_group(0).column(j).has_offset_index and md.row_group(0).column(j).statistics.has_min_max for j in range(md.num_columns))
@@ -193,7 +201,8 @@ def main():
         n_columns = len(rb.column_names)
         enc = (ctypes.c_int8 * n_columns)(*([1] + [0] * (n_columns - 1)))
 
-        codecs = (ctypes.c_int8 * n_columns)(*([1] * n_columns))
+        codecs = (ctypes.c_int8 * n_columns)(*([7 if args.lz4 else 1] * n_columns))
+        snappy_codecs = (ctypes.c_int8 * n_columns)(*([1] * n_columns))
 
         index = pp.ParquetIndexOptions(2, 0, None, 0)
         names = rb.column_names
@@ -204,7 +213,7 @@ def main():
 
         group_opts = pp.ParquetGroupOptions(args.groups, 1 if args.used else 0, 0)
 
-        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy, indexed=args.stats, filtered=args.bloom, run_encoded=args.runs, handle=None, used=args.used or args.groups > 0):
+        def c_call(delta=args.delta, want=file_bytes, snappy=args.snappy or args.lz4, indexed=args.stats, filtered=args.bloom, run_encoded=args.runs, handle=None, used=args.used or args.groups > 0):
             out, n = ctypes.c_void_p(), ctypes.c_int64()
             if used:
                 rc = pp.lib().fdb_batch_to_parquet_grouped(rb.handle, ctypes.byref(opts), None, 0, None, 0, None, None, None, ctypes.byref(group_opts), ctypes.byref(out), ctypes.byref(n))
@@ -226,11 +235,24 @@ def main():
             assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
             pp.lib().fdb_bytes_free(out.value)
         plain = {}
-        if args.delta or args.snappy or args.stats or args.bloom or args.runs or args.used or args.groups:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
+        if args.lz4:  # the SNAPPY call on the same record, in this process, measured the same way
+            snappy_bytes = len(rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression="snappy"))
+
+            def snappy_call():
+                out, n = ctypes.c_void_p(), ctypes.c_int64()
+                rc = pp.lib().fdb_batch_to_parquet_compressed(rb.handle, ctypes.byref(opts), ctypes.cast(enc, ctypes.c_void_p), n_columns, ctypes.cast(snappy_codecs, ctypes.c_void_p), n_columns,
+                                                              ctypes.byref(out), ctypes.byref(n))
+                assert rc == 0 and n.value == snappy_bytes, pp.lib().fdb_last_error()
+                pp.lib().fdb_bytes_free(out.value)
+            ms, every = median_ms(snappy_call, args.reps, args.warmup)
+            ph = profiled_phases(rb, args.page_rows, args.reps, encodings, "snappy")
+            plain.update({"snappy_file_bytes": snappy_bytes, "snappy_to_parquet_ms": ms, "snappy_to_parquet_min_ms": min(every), "snappy_to_parquet_max_ms": max(every),
+                          "snappy_place_compress_ms": ph["compress"], "snappy_scan_ms": ph["scan"], "snappy_final_layout_ms": ph["final layout"], "snappy_gather_ms": ph["gather"]})
+        if args.delta or args.snappy or args.lz4 or args.stats or args.bloom or args.runs or args.used or args.groups:  # the yardstick: the PLAIN call on the same record, in this process, measured the same way
             plain_bytes = len(rb.to_parquet(page_rows=args.page_rows))
             ms, every = median_ms(lambda: c_call(False, plain_bytes, False, False, False, False, None, False), args.reps, args.warmup)
             ph = profiled_phases(rb, args.page_rows, args.reps)
-            plain = {"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)}
+            plain.update({"plain_file_bytes": plain_bytes, "plain_to_parquet_ms": ms, "plain_to_parquet_min_ms": min(every), "plain_to_parquet_max_ms": max(every)})
             plain.update({"plain_%s_ms" % k.replace(" ", "_"): ph[k] for k in PHASES})
         to_parquet_ms, to_parquet_all = median_ms(c_call, args.reps, args.warmup)
         python_ms, _ = median_ms(lambda: rb.to_parquet(page_rows=args.page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs, dictionaries=dictionaries, row_group_rows=args.groups), args.reps, 1)
@@ -255,7 +277,7 @@ def main():
             return median_ms(bare_copy, args.reps, args.warmup)[0]
         floor_ms = bare_copy_ms(file_bytes)
         read_ceiling = pp.read_ceiling(0, 2 << 30, 5) if args.used else None
-        if args.snappy or args.runs or args.used or args.groups:
+        if args.snappy or args.lz4 or args.runs or args.used or args.groups:
             plain["plain_floor_ms"] = bare_copy_ms(plain["plain_file_bytes"])
 
         label_names = ["labels.l%d" % k for k in range(len(LABELS))]
@@ -289,6 +311,11 @@ def main():
         line.update({"delta": ["timestamp"], "snappy": "all", "to_parquet_max_ms": r3(max(to_parquet_all)), "delta_compact_ms": r3(phases["delta compact"]),
                      "delta_survey_ms": r3(phases["delta survey"]), "delta_encode_ms": r3(phases["delta encode"]), "place_compress_ms": r3(phases["compress"]), "scan_ms": r3(phases["scan"]),
                      "final_layout_ms": r3(phases["final layout"]), "gather_ms": r3(phases["gather"]), "column_bytes": column_bytes})
+    if args.lz4:
+        line.update({"delta": ["timestamp"], "lz4": "all", "to_parquet_max_ms": r3(max(to_parquet_all)), "delta_compact_ms": r3(phases["delta compact"]),
+                     "delta_survey_ms": r3(phases["delta survey"]), "delta_encode_ms": r3(phases["delta encode"]), "place_ms": r3(phases["compress"]), "lz_compress_ms": r3(phases["lz compress"]),
+                     "scan_ms": r3(phases["scan"]), "final_layout_ms": r3(phases["final layout"]), "gather_ms": r3(phases["gather"]), "lz_gather_ms": r3(phases["lz gather"]),
+                     "column_bytes": column_bytes})
     if args.stats:
         line.update({"statistics": "page", "to_parquet_max_ms": r3(max(to_parquet_all)), "stats_ms": r3(phases["stats"]), "wait_ms": r3(phases["wait"])})
     if args.bloom:
@@ -305,7 +332,7 @@ def main():
                      "column_bytes": column_bytes})
     if args.groups:
         line.update({"row_group_rows": args.groups, "row_groups": row_groups, "to_parquet_max_ms": r3(max(to_parquet_all)), "column_bytes": column_bytes})
-    if args.delta or args.snappy or args.stats or args.bloom or args.runs or args.used or args.groups:
+    if args.delta or args.snappy or args.lz4 or args.stats or args.bloom or args.runs or args.used or args.groups:
         line.update({k: (r3(v) if isinstance(v, float) else v) for k, v in plain.items()})
     text = json.dumps(line)
     print(text, flush=True)
