@@ -301,6 +301,23 @@ struct Gen {
       valid(s.c8[i], r);
     }
     o << "      }\n";
+    // Sub-step 0's registers are read here, in front of its filter: left to itself the optimiser sinks every load whose only uses sit
+    // behind the first `continue` (the group column's nibble, the aggregate's values) below that branch, and the wave pays a second
+    // memory round trip per block with 2 KiB in flight. An empty statement: it emits no instruction, and the wait in front of it counts
+    // sub-step 0's loads only — they are the first to leave.
+    std::string keep;
+    auto use = [&](const std::string& v) { keep += (keep.empty() ? "\"v\"(" : ", \"v\"(") + v + ")"; };
+    for (int i = 0; i < s.n_c4; i++) {
+      const std::string r = reg(false, false, i);
+      if (s.c4[i].has_values && s.c4[i].width >= 4) use("A_" + r + "[0]");
+      if (s.c4[i].has_validity != 0) use("M_" + r + "[0]");
+    }
+    for (int i = 0; i < s.n_c8; i++) {
+      const std::string r = reg(true, false, i);
+      if (s.c8[i].has_values) { use("A_" + r + "a[0]"); use("A_" + r + "b[0]"); }
+      if (s.c8[i].has_validity != 0) use("M_" + r + "[0]");
+    }
+    if (!keep.empty()) o << "      asm volatile(\"\" :: " << keep << ");\n";
   }
 
   void loads(bool late) {
@@ -2047,13 +2064,18 @@ hipError_t jit_hash_launch(hipFunction_t fn, const FdbHashArgs& args, int grid, 
 // are in flight per CU (Little's law for ≈8 TB/s × ≈2 µs over 256 CUs) — 16 waves for cfg 2 (64 B per lane and tile),
 // 8 for cfg 3 (128 B) — and gets SLOWER with more resident waves (cfg 2: 6.75 TB/s at 16 waves/CU, 6.0 at 32), so the
 // persistent grid is sized from the bytes one lane requests per tile, not from the occupancy limit.
-hipFunction_t jit_select(JitShape shape, size_t lds_bytes, int row_bytes, int* block_out, int* blocks_per_cu_out) {
+hipFunction_t jit_select(JitShape shape, size_t lds_bytes, int row_bytes, bool sorted_input, int* block_out, int* blocks_per_cu_out) {
   int waves = row_bytes > 0 ? (65536 / (64 * 4)) / row_bytes : 16;  // 64 lanes × 4 rows per lane and tile
   waves = std::max(8, std::min(32, waves));
-  // A quad shape (JitShape::quad) keeps four sub-steps in flight per wave, 16 rows per lane, and is fastest with about twice the bytes in
-  // flight in a quarter of the waves: ≈144 KB per CU in 256-thread workgroups, at least two of them (profiles/quad_scan_ab.json,
-  // "geometry": 3 per CU for the headline's 11 B per row — 2, 4 and 6 are slower —, 2 per CU for cfg 3's 20 B per row).
-  if (shape.quad) waves = std::max(8, std::min(16, row_bytes > 0 ? 144 / row_bytes : 12));
+  // A quad shape (JitShape::quad) keeps four sub-steps in flight per wave, 16 rows per lane, all of a block's early loads issued before
+  // its first branch (Gen::block_loads), and is fastest with ≈96 KB in flight per CU in 256-thread workgroups, at least two of them
+  // (profiles/block_loads_ab.json, "geometry": 2 per CU for the headline's 11 B per row — 3, 4 and 6 are slower, as are 1 024-thread
+  // workgroups —, 2 per CU for cfg 3's 20 B per row). While the optimiser still sank sub-step 0's loads below that branch a wave had
+  // 2 KiB in flight for half of a block's time, and 3 per CU were the best (profiles/quad_scan_ab.json).
+  // An ordered plan's input is sorted by its group columns: every wave takes the uniform fold, whose butterflies are a long dependent
+  // chain behind each sub-step, and wants the third workgroup to load meanwhile (cfg 2 sorted: 0.197 ms per 100 M rows at 3 per CU,
+  // 0.238 at 2).
+  if (shape.quad) waves = std::max(8, std::min(16, row_bytes > 0 ? (sorted_input ? 144 : 96) / row_bytes : 8));
   const int block = shape.quad ? 256 : waves % 8 == 0 ? 512 : 256;
   shape.block = block;
   hipFunction_t fn = jit_get(shape);

@@ -1639,7 +1639,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
           for (int k = 0; k < shape.n_l4; k++) row_bytes += shape.l4[k].has_values ? shape.l4[k].width : 0;
           for (int k = 0; k < shape.n_c8; k++) row_bytes += shape.c8[k].has_values ? 8 : 0;
           for (int k = 0; k < shape.n_l8; k++) row_bytes += shape.l8[k].has_values ? 8 : 0;
-          jit_fn = jit_select(shape, lds_bytes, row_bytes, &jit_block, &per_cu);
+          jit_fn = jit_select(shape, lds_bytes, row_bytes, ordered_, &jit_block, &per_cu);
         }
         quad_unit = shape.quad;
       }

@@ -87,6 +87,7 @@ int main(int argc, char** argv) {
     // the dense scan kernel of a cfg 2-like shape (`labels.code == X` + SUM(float64) [+ MIN / COUNT] GROUP BY labels.path):
     //   plan [variant] [narrow [threads]]   narrow: the dictionary slots read from narrow-index caches (1-byte filter column, 2-byte group column),
     //                                       the quad shape of such a launch; threads: per workgroup (256 / 512 / 1024)
+    //   plan [variant] narrow threads sum   the same with SUM(float64) as the only aggregate: the shape bench.py's headline runs
     //   plan [variant]   variant: lds (default) | wave (per-wave tables: fdb_plan_set_deterministic) | reg (≤ 8 slots in registers) | cache (table too big for LDS) | two (two-phase layout, 4 aggregates)
     const std::string v = argc > 2 ? argv[2] : "lds";
     fdb::JitShape s;
@@ -116,6 +117,7 @@ int main(int argc, char** argv) {
       s.quad = true;  // (what jit_shape sets for a launch with a narrow slot)
     }
     if (argc > 4) s.block = std::atoi(argv[4]);  // plan <variant> narrow <threads per workgroup>
+    if (argc > 5 && std::string(argv[5]) == "sum" && !s.two_phase) s.aggs.resize(1);  // plan <variant> narrow <threads> sum: SUM(float64) alone, bench.py's headline query
     std::fputs(fdb::jit_source(s).c_str(), stdout);
     return 0;
   }
