@@ -323,7 +323,7 @@ void Plan::push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, co
     // exact SUMs: FdbAgg.acc = the aggregation's limb rows (set per launch below: the table may grow); nullptr for every other one
     for (int j = 0; j < a.n_aggs; j++) a.aggs[j].acc = exact_f64((size_t)j) ? (unsigned long long*)(uintptr_t)1 : nullptr;
     const int grid = fdb_scan_default_grid(device_) * 4;  // 256-thread workgroups, 8 per CU
-    // The run-time specialised kernel for this record's shape (fdb_jit.cpp), or the interpreting scan_hash_kernel
+    // The run-time specialised kernel for this record's shape (written by fdb_jitgen.cpp, compiled and cached by fdb_jit.cpp), or the interpreting scan_hash_kernel
     hipFunction_t jit_fn = nullptr;
     int jit_grid = 0;
     if (runs) {  // (the shape is that of a runs launch; the real pointers follow below)

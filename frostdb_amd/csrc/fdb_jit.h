@@ -1,4 +1,4 @@
-// fdb_jit.h — plan-specialised scan kernels (fdb_jit.cpp).
+// fdb_jit.h — plan-specialised scan kernels (fdb_jitgen.cpp writes their source, fdb_jit.cpp compiles, caches and launches them).
 #pragma once
 #include <cstdlib>
 
@@ -46,7 +46,7 @@ struct JitShape {
   // order in which the waves' LDS atomics interleave differs from run to run, and float64 addition is not associative.
   bool wave_tables = false;
   // LDS tables: when the slots of a wave's selected rows agree (sorted input) the updates go to a wave-uniform address, so that the compiler
-  // folds them across the lanes (fdb_jit.cpp, "Sorted input")
+  // folds them across the lanes (fdb_jitgen.cpp, "Sorted input")
   bool uniform_fold = true;  // ($FDB_NO_UNIFORM_FOLD, A/B aid: a plan reads it at create, Plan::Knobs)
   // fdb_plan_kernel, set when a slot of the launch is narrow (JitSlot::width < 4): the unit of work (FdbScanArgs tile_begin / tile_end,
   // total_tiles) is block × 16 rows instead of block × 4 — each wave takes one block of 1 024 rows as four sub-steps of 64 lanes × 4 rows

@@ -1559,7 +1559,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
       for (int i : live)
         if (layouts[k++] == 1 && assign_slots(*bs[i], Rs[(size_t)i], 2, jit_possible) != 2) throw Error(FDB_ERR_INVALID, "internal: slot re-assignment failed");
     }
-    // A kernel specialised for this plan shape (fdb_jit.cpp), when every record of the launch has the same shape;
+    // A kernel specialised for this plan shape (written by fdb_jitgen.cpp, compiled and cached by fdb_jit.cpp), when every record of the launch has the same shape;
     // otherwise (or when hiprtc is unavailable) the interpreting slot kernel.
     if (sub_tiles != 4 && lds_bytes <= 150 * 1024) {  // (gfx950: up to 160 KiB of LDS per workgroup)
       // Narrow index reads (fdb_record.h, ScanCache): a 4-byte slot is scanned at 1 or 2 bytes when EVERY part of the launch can hold a

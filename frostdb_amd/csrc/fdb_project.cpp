@@ -7,7 +7,7 @@
 // convertProjection :493-556, isNullProjection :558-601, ifExprProjection :603-702, literalProjection :716-728, aliasProjection
 // :40-56), which are the plan's projections[]. Pass-through fields are copied device to device into the output's own arena; ALL
 // computed fields of ALL records of the call are evaluated by ONE launch of a kernel generated for the expressions' shape
-// (fdb_project_kernel, fdb_jit.cpp). Not carried over: boolExprProjection's shortcut for a result column a table scan pre-computed
+// (fdb_project_kernel, fdb_jitgen.cpp). Not carried over: boolExprProjection's shortcut for a result column a table scan pre-computed
 // (:411-432) — no scan on this path produces one.
 #include "fdb_plan.h"
 #include "fdb_jit.h"

@@ -1,4 +1,4 @@
-"""Cases for what feeds the hash table and what empties it — the specialised fdb_hash_kernel (fdb_jit.cpp), the interpreting
+"""Cases for what feeds the hash table and what empties it — the specialised fdb_hash_kernel (fdb_jitgen.cpp), the interpreting
 scan_hash_kernel, push_hash's chunk walk, hash_reserve → hash_rehash_kernel, and the device Finish of a table (hash_chunk_counts /
 hash_gather_rows / group_rows_to_columns / present_ids / rank_ids, the transport widths and slices of finish_columns_hash,
 hash_compact_kernel behind fetch_compact_hash) — and, beside every case, the CLAIM of which branch it takes: per push the chunk list,
@@ -77,7 +77,7 @@ def lut_places(luts, predicate_bytes=0):
 
 
 def stored_quads(kinds, words, canonical):
-    """HashGen::emit_tuple_stores (fdb_jit.cpp, "stores: aligned quads …"): inside every group of 8 columns, four dictionary columns that
+    """HashGen::emit_tuple_stores (fdb_jitgen.cpp, "stores: aligned quads …"): inside every group of 8 columns, four dictionary columns that
     start on a word divisible by 4 leave as one 16-byte store — in a canonical record only. → first column of every such quad"""
     out = []
     if not canonical:

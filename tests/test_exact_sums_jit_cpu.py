@@ -1,4 +1,4 @@
-"""The exact-sum variant of the run-time generated hash kernel (fdb_jit.cpp, JitHashShape::exact: limb adds through fdb_exact_add_wave
+"""The exact-sum variant of the run-time generated hash kernel (fdb_jitgen.cpp, JitHashShape::exact: limb adds through fdb_exact_add_wave
 after the tile's probes) compiles for gfx950 without spilling — checked here, without a GPU, with the options hiprtc gets."""
 import glob
 import os
@@ -7,14 +7,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+from tests.jit_corpus import EXACT
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SHAPES = [
-    ("exact_32_columns", ["32", "0", "exact"]),  # cfg 5's key shape, two exact SUMs (one with NULLs) and a COUNT
-    ("exact_int64_key", ["3", "1", "exact"]),    # an int64 (time bucket) key
-    ("exact_no_groups", ["0", "0", "exact"]),    # no group column: one group
-]
+SHAPES = EXACT
 
 
 def test_exact_hash_kernels_compile_for_gfx950(tmp_path):

@@ -3044,7 +3044,7 @@ def test_filter_in_one_pass_survives_the_epoch_wrap(pp, monkeypatch):
 @pytest.mark.parametrize("run_len", [1, 37, 300, 5000, 1 << 30])
 def test_dense_kernel_folds_waves_whose_rows_share_a_slot(pp, run_len, monkeypatch):
     """A table sorted by its group column: the rows of a wave fall into one slot and the specialised dense kernel folds them across the
-    lanes before ONE LDS update (fdb_jit.cpp, "Sorted input") — single-phase shapes, SUM / MIN / MAX / COUNT, float64 and int64, with a
+    lanes before ONE LDS update (fdb_jitgen.cpp, "Sorted input") — single-phase shapes, SUM / MIN / MAX / COUNT, float64 and int64, with a
     filter that empties some lanes and whole waves, NULL group keys, runs of equal keys from 1 row (nothing folds) to the whole record
     (everything folds), ragged record sizes. Equal to the oracle, and bit-identical in the integer columns to the kernel without the
     fold (FDB_NO_UNIFORM_FOLD)."""

@@ -1,5 +1,5 @@
 """The quad form of the dense scan issues every early load of a wave's 1 024-row block in front of sub-step 0's filter (Gen::block_loads,
-frostdb_amd/csrc/fdb_jit.cpp). The branches those loads used to hide behind are taken here on purpose: tables built from explicit arrays
+frostdb_amd/csrc/fdb_jitgen.cpp). The branches those loads used to hide behind are taken here on purpose: tables built from explicit arrays
 whose filter column selects nothing in chosen sub-steps of 256 rows — sub-step 0 of every fourth block, later sub-steps of the others, one
 whole block — with NULLs in the group column at a block's rows 0 to 3 and at its last row.
 

@@ -7,7 +7,7 @@ The claims are a Python RESTATEMENT of the host arithmetic and can drift from th
   Plan::hash_layout (fdb_hash.cpp:36-61), Plan::hash_reserve (:71-96), push_hash (:246-453: the key-id LUTs :293-317, `canonical`
   :306-308, the chunk walk :381-450), the transport widths of finish_columns_hash (:555-563, :709-718) and its slices (:549-553), the
   mode decision of Plan::push_batches (fdb_plan.cpp:1418-1427), resolve_batch's column order (:1203-1237) and the quads of
-  HashGen::emit_tuple_stores (fdb_jit.cpp). Whoever changes how those shape a push or a Finish changes hash_scan_cases.py with them."""
+  HashGen::emit_tuple_stores (fdb_jitgen.cpp). Whoever changes how those shape a push or a Finish changes hash_scan_cases.py with them."""
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -15,6 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 import pytest
 
 from tests import hash_scan_cases as S
+from tests.jit_corpus import HASH_CASES
 from tests.test_jit_sources_cpu import HIPCC, ROOT, jit_dump  # noqa: F401  (the fixture that builds tools/jit_dump.cpp)
 
 
@@ -252,14 +253,14 @@ def test_the_numpy_reference_equals_the_oracle(family):
 # jit_dump's arguments: N dictionary columns with validity (the first 8 LUTs in LDS), SUM(float64) + COUNT; "1": the last column an int64 key;
 # "exact": exact sums. That covers the column counts of the `columns` family; a filter, the seven reducers of `rows` / `runs`, uint64 / bool /
 # computed keys and columns without validity cannot be expressed and are compiled on the device only.
-HASH_SHAPES = [[str(n)] for n in (9, 12, 16, 17, 31, 32, 33, 63, 64)] + [[str(n + 1), "1"] for n in (0, 1, 2, 3, 7, 8, 31, 32, 63)] + [["2", "1", "exact"]]
+HASH_SHAPES = HASH_CASES  # (tests/jit_corpus.py)
 
 
 def test_hash_kernels_of_the_cases_column_counts_compile_without_scratch(jit_dump):  # noqa: F811
     exe, out = jit_dump
 
-    def one(args):
-        name = "hash_scan_" + "_".join(args)
+    def one(shape):
+        name, args = shape
         src = subprocess.run([exe] + args, check=True, capture_output=True, text=True).stdout
         assert "void fdb_hash_kernel(" in src, name
         path = str(out / (name + ".hip"))

@@ -6,13 +6,10 @@ import subprocess
 
 import pytest
 
+from tests.jit_corpus import NARROW
 from tests.test_jit_sources_cpu import HIPCC, ROOT, jit_dump  # noqa: F401  (the fixture builds tools/jit_dump.cpp)
 
-SHAPES = [
-    ("narrow_lds", ["plan", "lds", "narrow"]),
-    ("narrow_two_phase", ["plan", "two", "narrow"]),
-    ("narrow_wave_tables", ["plan", "wave", "narrow"]),
-]
+SHAPES = NARROW
 
 
 @pytest.mark.parametrize("name,args", SHAPES, ids=[s[0] for s in SHAPES])

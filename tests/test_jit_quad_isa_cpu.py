@@ -18,11 +18,11 @@ import subprocess
 
 import pytest
 
+from tests.jit_corpus import QUAD_ISA
 from tests.test_jit_sources_cpu import HIPCC, ROOT, jit_dump  # noqa: F401  (the fixture builds tools/jit_dump.cpp)
-from tests.test_jit_quad_sources_cpu import SHAPES as QUAD_SHAPES
 
 # (name, jit_dump arguments, two_phase)
-SHAPES = [(n, a, a[1] == "two") for n, a, _ in QUAD_SHAPES] + [("quad_lds_256_sum", ["plan", "lds", "narrow", "256", "sum"], False)]
+SHAPES = [(n, a, a[1] == "two") for n, a in QUAD_ISA]
 
 KEEP_ALIVE = re.compile(r'^ *asm volatile\("" :: "v"\(.*\);\n', re.M)
 

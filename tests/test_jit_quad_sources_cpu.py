@@ -10,15 +10,11 @@ import subprocess
 
 import pytest
 
+from tests.jit_corpus import QUAD
 from tests.test_jit_sources_cpu import HIPCC, ROOT, jit_dump  # noqa: F401  (the fixture builds tools/jit_dump.cpp)
 
-SHAPES = [
-    ("quad_lds", ["plan", "lds", "narrow"], 512),
-    ("quad_two_phase", ["plan", "two", "narrow"], 512),
-    ("quad_wave_tables", ["plan", "wave", "narrow"], 256),
-    ("quad_lds_512", ["plan", "lds", "narrow", "512"], 512),
-    ("quad_lds_256", ["plan", "lds", "narrow", "256"], 256),
-]
+# (name, jit_dump arguments, threads per workgroup: what the tool gives the variant, or the fourth argument)
+SHAPES = [(name, args, int(args[3]) if len(args) > 3 else 256 if args[1] == "wave" else 512) for name, args in QUAD]
 
 
 @pytest.mark.parametrize("name,args,block", SHAPES, ids=[s[0] for s in SHAPES])

@@ -1,32 +1,19 @@
 """The run-time generated kernels compile for gfx950 — checked here, without a GPU: on the GPU box hiprtc compiles them at the first query
 of a shape, and a source that does not compile would silently put that shape on the interpreting kernels (or fail the one-pass filter,
 the run kernel, the deterministic mode, which have no interpreting twin). tools/jit_dump.cpp prints the source the generators in
-fdb_jit.cpp produce for representative shapes; hipcc compiles each for the device only (the same options hiprtc gets)."""
+fdb_jitgen.cpp produce for representative shapes; hipcc compiles each for the device only (the same options hiprtc gets)."""
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+from tests.jit_corpus import SOURCES, kernel_of
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SHAPES = [
-    ("plan_lds", ["plan", "lds"], "fdb_plan_kernel"),
-    ("plan_wave_tables", ["plan", "wave"], "fdb_plan_kernel"),       # fdb_plan_set_deterministic
-    ("plan_reg_slots", ["plan", "reg"], "fdb_plan_kernel"),
-    ("plan_cache", ["plan", "cache"], "fdb_plan_kernel"),
-    ("plan_two_phase", ["plan", "two"], "fdb_plan_kernel"),
-    ("flags", ["flags"], "fdb_flags_kernel"),
-    ("select_value", ["select", "1"], "fdb_select_kernel"),          # filter() in one pass: one 8-byte column fused
-    ("select_value_and_dict", ["select"], "fdb_select_kernel"),      # … next to an unfused dictionary leaf with a LUT in LDS
-    ("hash_32_columns", ["32"], "fdb_hash_kernel"),                  # cfg 5
-    ("hash_int64_key", ["8", "1"], "fdb_hash_kernel"),
-    ("runs_32_columns", ["32", "2"], "fdb_hash_kernel"),             # the table-free OrderedAggregate's run kernel
-    ("runs_wide_32_columns", ["32", "3"], "fdb_hash_kernel"),        # … writing wide records (any cardinality: tuples from re-loaded columns)
-    ("runs_wide_int64_key", ["3", "4"], "fdb_hash_kernel"),          # … with an int64 key column
-    ("runs_medium_32_columns", ["32", "5"], "fdb_hash_kernel"),      # … writing medium records (two bytes per key id, ids kept in registers)
-]
+SHAPES = [(name, args, kernel_of(args)) for name, args in SOURCES]
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""The Projection operator without a GPU: the C ABI's new struct and symbols, and the kernels fdb_jit.cpp generates for the expression
+"""The Projection operator without a GPU: the C ABI's new struct and symbols, and the kernels fdb_jitgen.cpp generates for the expression
 sets of tests/test_gpu_project.py's differential test — compiled offline for gfx950 the way test_jit_sources_cpu.py does it for the
 other generated kernels (a source that does not compile, or spills, would only show on the GPU box)."""
 import ctypes
@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-from tests.golden.projection_cases import DIFF_CASES
+from tests.jit_corpus import PROJECT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -77,20 +77,21 @@ def jit_dump(tmp_path_factory):
 def test_project_kernels_compile_for_gfx950_without_scratch(jit_dump):
     exe, out = jit_dump
 
-    def one(case):
-        src = subprocess.run([exe, "project", case["shape"]], check=True, capture_output=True, text=True).stdout
-        assert "void fdb_project_kernel(" in src, case["id"]
-        path = str(out / (case["id"] + ".hip"))
+    def one(shape):
+        name, args = shape
+        src = subprocess.run([exe] + args, check=True, capture_output=True, text=True).stdout
+        assert "void fdb_project_kernel(" in src, name
+        path = str(out / (name + ".hip"))
         with open(path, "w") as f:
             f.write(src)
         r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-DFDB_DEVICE_ONLY=1", "-include", "hip/hip_runtime.h",
                             "-I", os.path.join(ROOT, "frostdb_amd", "csrc"), "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", path + ".o"],
                            capture_output=True, text=True)
         usage = [ln.split("remark: ")[-1].replace(" [-Rpass-analysis=kernel-resource-usage]", "") for ln in r.stderr.splitlines() if "remark:" in ln and ("ScratchSize" in ln or "VGPRs:" in ln or "SGPRs:" in ln or "LDS Size" in ln or "Spill" in ln)]
-        return case["id"], r.returncode, r.stderr if r.returncode else "", usage
+        return name, r.returncode, r.stderr if r.returncode else "", usage
 
-    with ThreadPoolExecutor(max_workers=min(len(DIFF_CASES), os.cpu_count() or 4)) as ex:
-        results = list(ex.map(one, DIFF_CASES))
+    with ThreadPoolExecutor(max_workers=min(len(PROJECT), os.cpu_count() or 4)) as ex:
+        results = list(ex.map(one, PROJECT))
     failed = [(n, err[-2000:]) for n, rc, err, _ in results if rc != 0]
     assert not failed, failed
     for name, _, _, usage in results:

@@ -1,7 +1,7 @@
 // Tuning aid: what can the LOADS of the narrow dense scan reach by themselves? Streams the headline's columns — a 1-byte index column, a
 // 2-byte index column, a float64 column, two validity bitmaps: 11.25 B per row — with nothing behind the loads but an xor, in five forms:
 //   wide4   the 4-byte scan's pattern (two uint32 index columns: 16.25 B per row), a lane owns 4 rows: 16 B + 16 B + 2 × 16 B per lane
-//   direct  the narrow scan's pattern (fdb_jit.cpp, ld1x4 / ld2x4), a lane owns 4 rows: 4 B + 8 B + 2 × 16 B per lane
+//   direct  the narrow scan's pattern (fdb_jitgen.cpp, ld1x4 / ld2x4), a lane owns 4 rows: 4 B + 8 B + 2 × 16 B per lane
 //   wide16  a lane owns 16 consecutive rows: 16 B + 2 × 16 B + 8 × 16 B per lane (every index load a full 16-byte load)
 //   quad16  a wave owns a block of 1 024 rows as four sub-steps of 256 rows, in sub-step u lane l owns rows 256u + 4l … +3, and the index columns
 //           are read as if laid out for that (a wave-interleaved cache): one 16-byte load at 16l of the block's 1 024 B of the 1-byte column,
