@@ -793,9 +793,10 @@ def test_benchmark_schema_query_over_a_table_sorted_by_path(pp):
 def test_run_path_against_the_hash_path_on_random_shapes(pp, seed):
     """Differential: an ordered plan (run kernel + run-store Finish, or its fall-backs) against the plain hash aggregate sorted by key, over
     shapes that stress the run store's bookkeeping — ragged records (1 row … tens of thousands, not multiples of the 256-row wave tile or
-    the 1 024-row workgroup tile), every row its own run (a wave's LDS stage fills and flushes inside one record, chunks of 4 096 runs
-    change), one run spanning whole records, NULL keys, a filter that drops most rows, more records than run segments (the path is left
-    mid-scan), sorted and unsorted input."""
+    the 1 024-row workgroup tile), every row its own run (256 runs in every wave tile), one run spanning whole records, NULL keys, a filter
+    that drops most rows, more records than run segments (the path is left mid-scan), sorted and unsorted input. With the default grid and
+    at most 150 000 rows every wave sees ONE tile here: its LDS stage never fills and it never leaves its first chunk of 4 096 runs —
+    tests/test_gpu_run_store.py forces one and two workgroups for those edges."""
     rng = np.random.default_rng(1000 + seed)
     n_rec = int(rng.integers(1, 80 if seed % 4 == 3 else 12))
     card = [int(rng.integers(1, 200)), int(rng.integers(1, 9)), int(rng.integers(1, 4))]
