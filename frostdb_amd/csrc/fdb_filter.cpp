@@ -296,25 +296,17 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::filter_batches_impl(const Device
 // Every record's predicate: program + LUTs; records with the same LUT set (same_lut_set) share one device copy and one class. false:
 // the records cannot share one generated kernel (slots, predicate shapes) — the per-record path takes over.
 bool Plan::FilterRun::resolve() {
-  std::vector<int> lut_class(nl, 0);
-  std::vector<size_t> blob_base(nl, 0);
-  Blob blob;
-  std::vector<size_t> reps;
+  LutClasses luts;
   for (size_t k = 0; k < nl; k++) {
-    Resolved& R = Rs[k];
-    P.resolve_predicate(src(k), P.filter_root_, &R);
-    size_t found = reps.size();
-    for (size_t r = 0; r < reps.size(); r++) if (same_lut_set(Rs[reps[r]], R)) { found = r; break; }
-    if (found < reps.size()) { lut_class[k] = (int)found; blob_base[k] = blob_base[reps[found]]; }
-    else { lut_class[k] = (int)reps.size(); blob_base[k] = blob.add(R.blob.bytes.data(), R.blob.bytes.size()); reps.push_back(k); }
+    P.resolve_predicate(src(k), P.filter_root_, &Rs[k]);
+    luts.add(Rs[k]);
   }
   StageScope stage_scope(P.ctx_);
-  unsigned char* d_blob = blob.bytes.empty() ? nullptr : (unsigned char*)P.upload(blob.bytes.data(), blob.bytes.size());
+  unsigned char* d_blob = luts.blob.bytes.empty() ? nullptr : (unsigned char*)P.upload(luts.blob.bytes.data(), luts.blob.bytes.size());
   for (size_t k = 0; k < nl; k++) {
     Resolved& R = Rs[k];
     FdbScanArgs& a = R.args;
-    lut_lds_max = std::max(lut_lds_max, place_luts(R.luts, d_blob + blob_base[k], 0, &a));
-    a.lut_class = lut_class[k];
+    lut_lds_max = std::max(lut_lds_max, luts.place(k, d_blob, R));
     // every filter column in the early pools (the flags kernel has no late phase)
     if (assign_slots(src(k), R, 2, /*relaxed=*/true) == 0) return false;
     if (k == 0) shape = jit_shape(a, true, 512);
@@ -329,8 +321,7 @@ bool Plan::FilterRun::resolve() {
     total_tiles += rec_tiles;
   }
   for (size_t k = 0; k < nl; k++) { Rs[k].args.lds_lut_bytes = (uint32_t)lut_lds_max; parts.push_back(Rs[k].args); }
-  for (int k = 0; k < shape.n_c4; k++) row_bytes += shape.c4[k].has_values ? 4 : 0;
-  for (int k = 0; k < shape.n_c8; k++) row_bytes += shape.c8[k].has_values ? 8 : 0;
+  row_bytes = shape.row_bytes();  // (every 4-byte slot at 4: only a dense scan narrows; no late slots)
   d_parts = (const FdbScanArgs*)P.upload(parts.data(), parts.size() * sizeof(FdbScanArgs));
   d_recs = (const FdbCompactRec*)P.upload(recs.data(), recs.size() * sizeof(FdbCompactRec));
   return true;

@@ -57,6 +57,14 @@ struct JitShape {
   // fdb_project_kernel only (not part of key()): root node of every computed field, in output order
   std::vector<int> proj_roots;
   std::string key(bool with_validity = true) const;
+  int row_bytes() const {  // bytes of column data a scan of this shape reads per row (slots with values, 4-byte slots at their width)
+    int b = 0;
+    for (int k = 0; k < n_c4; k++) b += c4[k].has_values ? c4[k].width : 0;
+    for (int k = 0; k < n_l4; k++) b += l4[k].has_values ? l4[k].width : 0;
+    for (int k = 0; k < n_c8; k++) b += c8[k].has_values ? 8 : 0;
+    for (int k = 0; k < n_l8; k++) b += l8[k].has_values ? 8 : 0;
+    return b;
+  }
 };
 
 // Shape of a high-cardinality (hash table) scan: fdb_hash_kernel.

@@ -1434,310 +1434,7 @@ void Plan::push_batches(const DeviceBatch* const* bs, int n) {
     pt.mark("hash scan");
     return;
   }
-  for (int i : live) {  // dense path: group columns → mixed-radix digits through per-dictionary LUTs
-    Resolved& R = Rs[(size_t)i];
-    FdbScanArgs& a = R.args;
-    for (const GroupRes& gr : R.groups) {
-      FdbGroupCol& G = a.gcols[a.n_gcols];
-      const DevColumn& c = bs[i]->cols[(size_t)gr.ci];
-      G.idx = (const uint32_t*)c.d_values;
-      G.validity = c.d_validity;
-      G.lut_len = (uint32_t)gr.lut->size();
-      G.lut_lds = FDB_NO_LDS;
-      G.slot = -1;
-      R.gcol_col[a.n_gcols] = gr.ci;
-      const size_t off = R.blob.add(gr.lut->data(), gr.lut->size() * 4);
-      R.luts.push_back(PendingLut{1, a.n_gcols, off, gr.lut->size() * 4});
-      part_gcols[(size_t)i].push_back(gr.gi);
-      a.n_gcols++;
-    }
-  }
-  std::vector<uint32_t> caps;
-  for (const GroupColState& g : gcols_) caps.push_back((uint32_t)g.values.size() + 1);
-  ensure_layout(caps);
-  pt.mark("layout");
-
-  // one blob for every LUT of every record
-  Blob blob;
-  std::vector<size_t> blob_base((size_t)n, 0);
-  std::vector<int> lut_class((size_t)n, 0);
-  {
-    std::vector<int> reps;  // (same_lut_set: one device copy and one class per LUT set)
-    for (int i : live) {
-      const Resolved& R = Rs[(size_t)i];
-      int found = -1;
-      for (int r : reps) if (same_lut_set(Rs[(size_t)r], R)) { found = r; break; }
-      if (found >= 0) { blob_base[(size_t)i] = blob_base[(size_t)found]; lut_class[(size_t)i] = lut_class[(size_t)found]; }
-      else { blob_base[(size_t)i] = blob.add(R.blob.bytes.data(), R.blob.bytes.size()); lut_class[(size_t)i] = (int)reps.size(); reps.push_back(i); }
-    }
-  }
-  // the LUT blob and the argument blocks below go to the device with ONE copy command, issued right before the launch
-  StageScope stage_scope(ctx_);
-  unsigned char* d_blob = blob.bytes.empty() ? nullptr : (unsigned char*)upload(blob.bytes.data(), blob.bytes.size());
-
-  const size_t acc_bytes = align_up((size_t)n_slots_ * 4, 16) + (size_t)n_slots_ * 8 * aggs_.size();
-  size_t lut_lds_max = 0;
-  bool slots_ok = rows_per_thread == 0;
-  const bool jit_possible = this->jit_possible();
-  bool interp_ok = true;  // every record also fits the interpreting slot kernel's limits
-  std::vector<int> layouts;
-  for (int i : live) {
-    Resolved& R = Rs[(size_t)i];
-    FdbScanArgs& a = R.args;
-    for (int g = 0; g < a.n_gcols; g++) a.gcols[g].stride = gcols_[(size_t)part_gcols[(size_t)i][(size_t)g]].stride;
-    for (size_t j = 0; j < aggs_.size(); j++) a.aggs[j].acc = aggs_[j].d_acc;
-    a.cnt = d_cnt_;
-    a.n_slots = n_slots_;
-    a.need_count = 0;
-    for (size_t j = 0; j < aggs_.size(); j++) if (a.aggs[j].func == FDB_AGG_COUNT) a.need_count = 1;
-    a.lut_class = lut_class[(size_t)i];
-    // LDS plan: [LUT copies][cnt u32 × n_slots][acc u64 × n_slots × n_aggs]
-    lut_lds_max = std::max(lut_lds_max, place_luts(R.luts, d_blob + blob_base[(size_t)i], 0, &a));
-    if (slots_ok) {
-      bool strict = true;
-      const int layout = assign_slots(*bs[i], R, 1, jit_possible, &strict);
-      if (layout == 0) slots_ok = false;
-      interp_ok = interp_ok && strict;
-      layouts.push_back(layout);
-    }
-  }
-  int lds_acc = 0;
-  size_t lds_bytes = lut_lds_max;
-  int base_grid = grid_override > 0 ? grid_override : fdb_scan_default_grid(device_);
-  if (fixed_order) {
-    // a table per wave, 4 waves (256-thread workgroups); no combining cache, no interpreting or sequential kernel
-    if (!jit_possible || !slots_ok || !use_partials) throw Error(FDB_ERR_UNSUPPORTED, "deterministic float sums need the run-time specialised dense kernel");
-    if (lut_lds_max + 4 * acc_bytes > 150 * 1024) throw Error(FDB_ERR_UNSUPPORTED, "deterministic float sums: four per-wave tables of " + std::to_string(acc_bytes) + " bytes do not fit LDS");
-    lds_acc = 1; lds_bytes += 4 * acc_bytes;
-  }
-  else if (lut_lds_max + acc_bytes <= FDB_LDS_BUDGET) { lds_acc = 1; lds_bytes += acc_bytes; }
-  else if (lut_lds_max + acc_bytes <= 150 * 1024) { lds_acc = 1; lds_bytes += acc_bytes; if (grid_override <= 0) base_grid /= 2; }
-  // table too big for LDS: the specialised kernel gets a combining cache instead (JitShape::cache), ≤ 48 KiB per workgroup
-  int cache_slots = 0;
-  if (!lds_acc && jit_possible) {
-    const size_t entry = 8 + 8 * aggs_.size();
-    cache_slots = 1;
-    while ((size_t)cache_slots * 2 * entry <= 48 * 1024) cache_slots *= 2;
-    lds_bytes = lut_lds_max + (size_t)cache_slots * entry;
-  }
-  for (int i : live) {
-    Rs[(size_t)i].args.lds_lut_bytes = (uint32_t)lut_lds_max; Rs[(size_t)i].args.lds_acc = lds_acc; Rs[(size_t)i].args.cache_slots = cache_slots;
-  }
-  pt.mark("lut upload");
-
-  int32_t funcs[1 + FDB_MAX_AGGS] = {0};
-  funcs[0] = 1;
-  {
-    const FdbScanArgs& a0 = Rs[(size_t)live[0]].args;
-    for (size_t j = 0; j < aggs_.size(); j++) {
-      const int32_t f = a0.aggs[j].func;
-      const int32_t ty = aggs_[j].type;
-      funcs[1 + j] = f == FDB_AGG_COUNT ? 0 : f == FDB_AGG_SUM ? (ty == FDB_T_F64 ? 2 : 1) : f == FDB_AGG_MIN ? 3 : 4;
-    }
-  }
-  auto alloc_partials = [&](int grid) -> unsigned long long* {
-    if (!lds_acc || !use_partials || grid <= 0) return nullptr;
-    void* p = ctx_->dev_alloc((size_t)grid * (1 + aggs_.size()) * n_slots_ * 8);
-    scratch_.push_back(p);
-    return (unsigned long long*)p;
-  };
-
-  // ---- choose the scan kernel: run-time specialised (fdb_jit.cpp) → interpreting slot kernel → sequential kernel ----------
-  int two_phase = 0, tile_rows_i = 0, per_cu = 1;
-  const int sub = sub_tiles == 4 ? 0 : sub_tiles;  // kernel variant mode (0 = default, 4 = interpreting kernel only)
-  struct Narrowed { int part, k, col; bool late; const void* wide; int64_t saved; };  // a slot switched to its record's narrow-index cache
-  std::vector<Narrowed> narrowed;
-  hipFunction_t jit_fn = nullptr;
-  int jit_block = sub == 1 ? 512 : sub == 2 ? 256 : sub == 3 ? 1024 : 0;  // 0: picked by occupancy
-  bool quad_unit = false;  // JitShape::quad: the launch counts its tiles in units of jit_block × 16 rows
-  if (fixed_order) jit_block = 256;
-  if (slots_ok) {
-    // records that fit the single-phase layout also fit the two-phase one: re-assign them if the launch is mixed
-    for (int l : layouts) if (l == 2) two_phase = 1;
-    if (two_phase) {
-      size_t k = 0;
-      for (int i : live)
-        if (layouts[k++] == 1 && assign_slots(*bs[i], Rs[(size_t)i], 2, jit_possible) != 2) throw Error(FDB_ERR_INVALID, "internal: slot re-assignment failed");
-    }
-    // A kernel specialised for this plan shape (written by fdb_jitgen.cpp, compiled and cached by fdb_jit.cpp), when every record of the launch has the same shape;
-    // otherwise (or when hiprtc is unavailable) the interpreting slot kernel.
-    if (sub_tiles != 4 && lds_bytes <= 150 * 1024) {  // (gfx950: up to 160 KiB of LDS per workgroup)
-      // Narrow index reads (fdb_record.h, ScanCache): a 4-byte slot is scanned at 1 or 2 bytes when EVERY part of the launch can hold a
-      // cache of that one width for the slot's column — built here, by the first scan that wants it; otherwise the whole launch reads
-      // the slot's uint32 columns, which every record has. Slots without values (IS NULL leaves) have nothing to narrow. The
-      // algorithmic bytes count the width that is scanned.
-      auto narrow_pool = [&](bool late) {
-        const FdbScanArgs& a0 = Rs[(size_t)live[0]].args;
-        const int n4 = late ? a0.n_l4 : a0.n_c4;
-        for (int i : live) if ((late ? Rs[(size_t)i].args.n_l4 : Rs[(size_t)i].args.n_c4) != n4) return;  // (records of different shapes: the launch is split below)
-        for (int k = 0; k < n4; k++) {
-          int w = 0;
-          for (int i : live) {
-            const Resolved& R = Rs[(size_t)i];
-            const int ci = late ? R.l4_col[k] : R.c4_col[k];
-            const int wi = (late ? R.args.l4[k] : R.args.c4[k]).values == nullptr || ci < 0 ? 4 : scan_cache_width(*bs[i], (size_t)ci);
-            w = w == 0 || w == wi ? wi : 4;
-            if (w == 4) break;
-          }
-          if (w >= 4) continue;
-          for (int i : live) {
-            Resolved& R = Rs[(size_t)i];
-            const int ci = late ? R.l4_col[k] : R.c4_col[k];
-            FdbColSlot& sl = late ? R.args.l4[k] : R.args.c4[k];
-            bool counted = false;  // (a column the filter and the group-by both read sits in two slots and counts once)
-            for (const Narrowed& nw : narrowed) if (nw.part == i && nw.col == ci) counted = true;
-            const int64_t saved = counted ? 0 : bs[i]->rows * (int64_t)(4 - w);
-            narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved});
-            sl.values = scan_cache_get(*bs[i], (size_t)ci, stream_);
-            (late ? R.args.wl4 : R.args.w4)[k] = (uint8_t)w;
-            R.bytes -= saved;
-          }
-        }
-      };
-      if (jit_possible) { narrow_pool(false); if (two_phase) narrow_pool(true); }
-      JitShape shape;
-      bool same = true, first = true;
-      const FdbScanArgs& args0 = Rs[(size_t)live[0]].args;
-      for (int i : live) {
-        if (first) { shape = jit_shape(args0, two_phase != 0, jit_block ? jit_block : 256); first = false; }
-        else if (!jit_shape_merge_args(&shape, args0, Rs[(size_t)i].args, two_phase != 0)) { same = false; break; }
-      }
-      if (!same && live.size() > 1 && jit_possible) {
-        // Records of different shapes (schema drift: a filter column missing here, a predicate value absent from that part's
-        // dictionary there) cannot share one specialised kernel: the launch is split into one launch per shape, so that a
-        // few odd parts do not push the whole scan onto the interpreting kernel.
-        std::vector<std::string> keys;
-        std::vector<std::vector<const DeviceBatch*>> groups;
-        for (int i : live) {
-          const std::string k = jit_shape(Rs[(size_t)i].args, two_phase != 0, 256).key(false);
-          size_t g = 0;
-          for (; g < keys.size(); g++) if (keys[g] == k) break;
-          if (g == keys.size()) { keys.push_back(k); groups.emplace_back(); }
-          groups[g].push_back(bs[i]);
-        }
-        if (groups.size() > 1) {
-          ctx_->defer_staging(false);  // (each group stages its own tables)
-          for (auto& g : groups) push_batches(g.data(), (int)g.size());
-          return;
-        }
-      }
-      {
-        // tiny tables live in registers (JitShape::reg_slots): ≤ 8 slots and ≤ 48 accumulator registers per lane
-        int regs_per_slot = 2;
-        for (const AggState& A : aggs_) if (A.func != FDB_AGG_COUNT || final_stage_) regs_per_slot += 2;
-        if (n_slots_ >= 1 && n_slots_ <= 8 && (int)n_slots_ * regs_per_slot <= 48) shape.reg_slots = (int)n_slots_;
-      }
-      shape.wave_tables = fixed_order;
-      shape.uniform_fold = !knobs_.no_uniform_fold;
-      if (same) {
-        // ($FDB_JIT_ASYNC=1: a shape whose kernel still has to be built is scanned by the interpreting kernel meanwhile — when that one can)
-        JitDeferScope defer(interp_ok && !fixed_order);
-        if (jit_block != 0) { jit_fn = jit_get(shape); if (jit_fn != nullptr) per_cu = jit_blocks_per_cu(jit_fn, jit_block, lds_bytes); }
-        else {
-          int row_bytes = 0;
-          for (int k = 0; k < shape.n_c4; k++) row_bytes += shape.c4[k].has_values ? shape.c4[k].width : 0;
-          for (int k = 0; k < shape.n_l4; k++) row_bytes += shape.l4[k].has_values ? shape.l4[k].width : 0;
-          for (int k = 0; k < shape.n_c8; k++) row_bytes += shape.c8[k].has_values ? 8 : 0;
-          for (int k = 0; k < shape.n_l8; k++) row_bytes += shape.l8[k].has_values ? 8 : 0;
-          jit_fn = jit_select(shape, lds_bytes, row_bytes, ordered_, &jit_block, &per_cu);
-        }
-        quad_unit = shape.quad;
-      }
-    }
-    // a launch only the specialised kernel could serve (more leaves / aggregates than the interpreting kernel's register-resident
-    // plan holds, computed columns) falls back to the sequential kernel when specialisation is unavailable
-    if (jit_fn == nullptr) {  // the interpreting kernels read the uint32 columns
-      for (const Narrowed& nw : narrowed) {
-        Resolved& R = Rs[(size_t)nw.part];
-        (nw.late ? R.args.l4 : R.args.c4)[nw.k].values = nw.wide;
-        (nw.late ? R.args.wl4 : R.args.w4)[nw.k] = 0;
-        R.bytes += nw.saved;
-      }
-      narrowed.clear();
-    }
-    if (jit_fn == nullptr && !interp_ok) slots_ok = false;
-  }
-  if (fixed_order && jit_fn == nullptr) throw Error(FDB_ERR_UNSUPPORTED, "deterministic float sums need the run-time specialised dense kernel (records of one shape, hiprtc available)");
-
-  pt.mark("kernel select");
-  if (slots_ok) {
-    // ---- one launch of the slot kernel (specialised or interpreting) over every record -------------------------------------
-    if (jit_fn != nullptr) {
-      tile_rows_i = jit_block * (quad_unit ? 16 : 4);
-    } else {
-      fdb_slot_geometry(two_phase, sub, lds_acc, lds_bytes, device_, &tile_rows_i, &per_cu);
-    }
-    int grid = grid_override > 0 ? grid_override : (fdb_scan_default_grid(device_) / 2) * per_cu;
-    const int64_t tile_rows = tile_rows_i;
-    int64_t total_tiles = 0;
-    std::vector<FdbScanArgs> parts;
-    parts.reserve(live.size());  // (3 KB apiece: no re-growing copies)
-    for (int i : live) {
-      FdbScanArgs& a = Rs[(size_t)i].args;
-      a.tile_begin = total_tiles;
-      total_tiles += (a.n_rows + tile_rows - 1) / tile_rows;
-      a.tile_end = total_tiles;
-      parts.push_back(a);
-    }
-    if (grid > total_tiles) grid = (int)total_tiles;
-    unsigned long long* partials = alloc_partials(grid);
-    for (FdbScanArgs& a : parts) a.partials = partials;
-    bool fill_rides = false;
-    if (state_virgin_ && jit_fn != nullptr && partials != nullptr && (uint64_t)slots_alloc_ * (1 + aggs_.size()) < (1ull << 32)) {
-      // nothing accumulates into the table before reduce_partials (the next kernel on the stream): the scan fills it on its way in
-      FdbScanArgs& a0 = parts[0];
-      a0.fill_state = d_state_;
-      a0.fill_words = (uint32_t)(slots_alloc_ * (1 + aggs_.size()));
-      a0.fill_alloc = (uint32_t)slots_alloc_;
-      state_idents(a0.fill_idents);
-      fill_rides = true;
-    } else {
-      materialize_state();
-    }
-    trace("before scan");
-    pt.mark("parts build");
-    const FdbScanArgs* d_parts = (const FdbScanArgs*)upload(parts.data(), parts.size() * sizeof(FdbScanArgs));
-    ctx_->flush_staging();
-    pt.mark("parts upload");
-    trace("after upload");
-    timed([&] {
-      if (jit_fn != nullptr) hip_check(jit_launch(jit_fn, d_parts, (int)parts.size(), total_tiles, parts[0], grid, jit_block, lds_bytes, stream_), "scan launch");
-      else hip_check(fdb_launch_scan_slots(d_parts, (int)parts.size(), parts[0], total_tiles, grid, lds_bytes, two_phase, sub, stream_), "scan launch");
-    });
-    if (fill_rides) state_virgin_ = false;  // (only once the launch that carries the fill was accepted: a throw above leaves the table marked unfilled)
-    last_kernel_ = jit_fn != nullptr ? "fdb_plan_kernel" : "scan_slots_kernel";
-    pt.mark("scan launch");
-    trace("after scan");
-    if (partials != nullptr) {
-      unsigned long long* host_out = mirror_target();
-      hip_check(fdb_launch_reduce_partials(partials, grid, (int)(1 + aggs_.size()), n_slots_, d_state_, slots_alloc_, funcs, host_out, stream_), "reduce partials");
-      mirror_valid_ = host_out != nullptr;
-    }
-    trace("after reduce");
-    stat_launches += 1;
-  } else {
-    // ---- sequential kernel, one launch per record ----------------------------------------------------------------
-    const int rpt = rows_per_thread == 8 ? 8 : 4;
-    materialize_state();
-    ctx_->flush_staging();
-    for (int i : live) {
-      FdbScanArgs& a = Rs[(size_t)i].args;
-      if (a.n_expr > 0) throw Error(FDB_ERR_UNSUPPORTED, "computed (projected) columns are not supported by the sequential kernel (too many referenced columns)");
-      a.n_c4 = a.n_c8 = 0;
-      const int grid = fdb_scan_grid(a, base_grid, rpt);
-      a.partials = alloc_partials(grid);
-      timed([&] { hip_check(fdb_launch_scan_dense(a, grid, lds_bytes, rpt, stream_), "scan launch"); });
-      last_kernel_ = "scan_dense_kernel";
-      mirror_valid_ = false;  // (a launch that flushes with atomics leaves the host copy behind)
-      if (a.partials != nullptr) {
-        unsigned long long* host_out = mirror_target();
-        hip_check(fdb_launch_reduce_partials(a.partials, grid, (int)(1 + aggs_.size()), n_slots_, d_state_, slots_alloc_, funcs, host_out, stream_), "reduce partials");
-        mirror_valid_ = host_out != nullptr;
-      }
-      stat_launches += 1;
-    }
-  }
-  pt.mark("reduce launch");
+  if (!push_dense(bs, Rs, part_gcols, live, fixed_order, pt)) return;  // (split by shape: every part was pushed, and counted, on its own)
   state_dirty_ = true;
   for (int i : live) { stat_bytes += Rs[(size_t)i].bytes; stat_rows += bs[i]->rows; }
 }

@@ -195,6 +195,8 @@ struct GroupSchemaCol {
 };
 struct GroupSchema { std::vector<GroupSchemaCol> cols; std::vector<int32_t> agg_types; };
 
+struct PhaseTimer;  // fdb_plan_internal.h
+
 class Plan {
  public:
   Plan(const fdb_plan_desc* desc, int device, bool explain_only = false);
@@ -320,6 +322,7 @@ class Plan {
   std::unique_ptr<DeviceBatch> filter_batch_interp(const DeviceBatch& in, int64_t* n_selected);
   struct SelectStall {};  // the one-pass select kernel ran into its poll bound: filter_batches retries through the three-launch path
   struct FilterRun;       // launch state of filter_batches_impl
+  struct DenseLaunch;     // launch state of push_dense (fdb_dense.cpp)
   std::vector<std::unique_ptr<DeviceBatch>> filter_batches_impl(const DeviceBatch* const* in, int n, int64_t* n_selected, bool force_two_pass);
   // `launch` between two timing events on the plan's stream when `timing` is on; the next sync adds their interval to stat_ms
   // (`merge`: to stat_merge_ms). Defined in fdb_plan_internal.h.
@@ -335,6 +338,8 @@ class Plan {
   void switch_to_hash();
   void hash_layout();                                   // (re)assign key-tuple words; widen the key store if columns were added
   void hash_reserve(uint64_t extra_groups, uint64_t expected_groups = 0);  // capacity ≥ 2 × (max(groups, expected) + extra): grow + rehash on the device
+  // the dense table's scan (fdb_dense.cpp): bind_group_columns → stage_luts → assign_all_slots → plan_lds → narrow_slots → choose_kernel → launch
+  bool push_dense(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, std::vector<std::vector<int>>& part_gcols, const std::vector<int>& live, bool fixed_order, PhaseTimer& pt);
   void push_hash(const DeviceBatch* const* bs, std::vector<Resolved>& Rs, const std::vector<int>& live, bool runs = false);
   // Table-free OrderedAggregate (ordered_aggregate.go:163-551; fdb_kernels.h "run store"): while an ordered plan's records keep
   // the shape the run kernel needs, their runs of equal keys are collected instead of probing a table. Finish merges what wave /
@@ -422,7 +427,7 @@ class Plan {
   unsigned long long* d_cnt_ = nullptr;
   bool state_dirty_ = false;        // any kernel has accumulated into the table
   bool state_virgin_ = false;       // d_state_ is allocated but NOT identity-filled yet: the first specialised scan launch fills it in its
-                                    // prologue (push_batches); anything else that reads or accumulates into it calls materialize_state() first
+                                    // prologue (DenseLaunch::launch_slots); anything else that reads or accumulates into it calls materialize_state() first
   void materialize_state();
   // Host copy of a small dense table, written by reduce_partials_kernel itself (pinned memory): valid from a push whose fold wrote
   // it until anything else changes the table (another push, a merge, an all-reduce, a raw write, a re-layout). Finish reads it

@@ -1,4 +1,6 @@
-// fdb_plan_internal.h — per-record resolution state shared by fdb_plan.cpp, fdb_filter.cpp and fdb_hash.cpp (not part of any API).
+// fdb_plan_internal.h — per-record resolution state shared by fdb_plan.cpp, fdb_dense.cpp, fdb_filter.cpp, fdb_project.cpp and fdb_hash.cpp (not part of
+// any API): Resolved, the LUT blob and its classes (LutClasses), staging scope, phase timer. The stages of a dense scan launch that use them
+// — bind_group_columns, stage_luts, assign_all_slots, plan_lds, narrow_slots, choose_kernel, launch — are Plan::DenseLaunch in fdb_dense.cpp.
 #pragma once
 
 #include <algorithm>
@@ -9,6 +11,7 @@
 #include <exception>
 #include <functional>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "fdb_context.h"
@@ -29,6 +32,22 @@ struct PhaseTimer {  // FDB_PROFILE=1: per-phase host microseconds on stderr (tu
     t = n;
   }
 };
+
+// FDB_PROFILE=1: one line per dense scan launch with every decision behind it (tuning aid) — no pointers and no times, so that two
+// builds that decide alike print alike. `shape_key`: JitShape::key(true) of a specialised kernel, empty otherwise.
+inline void print_dense_launch(const char* kernel, const std::string& shape_key, const FdbScanArgs* parts, size_t n_parts, int64_t total_tiles, int grid, int block,
+                               size_t lds_bytes, int two_phase, int lds_acc, int cache_slots, size_t lut_lds_max, int per_cu, int tile_rows, bool fill_rides, bool partials) {
+  std::string s;
+  for (size_t p = 0; p < n_parts; p++) {
+    s += " " + std::to_string(parts[p].lut_class) + ":";
+    for (int k = 0; k < parts[p].n_c4; k++) s += std::to_string((int)parts[p].w4[k]);
+    s += "/";
+    for (int k = 0; k < parts[p].n_l4; k++) s += std::to_string((int)parts[p].wl4[k]);
+  }
+  std::fprintf(stderr, "[fdb] dense launch %s shape=%s parts=%zu total_tiles=%lld grid=%d block=%d lds_bytes=%zu two_phase=%d lds_acc=%d cache_slots=%d lut_lds_max=%zu "
+               "per_cu=%d tile_rows=%d fill=%d partials=%d class:w4/wl4=%s\n", kernel, shape_key.empty() ? "-" : shape_key.c_str(), n_parts, (long long)total_tiles, grid, block,
+               lds_bytes, two_phase, lds_acc, cache_slots, lut_lds_max, per_cu, tile_rows, (int)fill_rides, (int)partials, s.c_str());
+}
 
 struct Blob {  // LUTs of one batch, shipped with one copy
   std::vector<uint8_t> bytes;
@@ -124,6 +143,27 @@ inline bool same_lut_set(const Plan::Resolved& q, const Plan::Resolved& r) {
       return false;
   return true;
 }
+
+// The LUT sets of the records of ONE launch: add() every record in launch order, upload `blob` once, then place() every record.
+struct LutClasses {
+  Blob blob;                      // one copy of each distinct set, 16-byte aligned
+  std::vector<size_t> blob_base;  // [record] where its set starts in `blob`
+  std::vector<int> cls;           // [record] class, numbered in first-seen order
+  void add(const Plan::Resolved& R) {
+    size_t found = 0;
+    while (found < reps_.size() && !same_lut_set(*reps_[found].first, R)) found++;
+    if (found == reps_.size()) reps_.emplace_back(&R, R.blob.bytes.empty() ? 0 : blob.add(R.blob.bytes.data(), R.blob.bytes.size()));  // (no LUT: nothing to ship)
+    blob_base.push_back(reps_[found].second);
+    cls.push_back((int)found);
+  }
+  // record k of the launch (`d_blob`: the device copy of `blob`): lut / lut_lds of its leaves and group columns, its class; returns the end of its LDS region
+  size_t place(size_t k, unsigned char* d_blob, Plan::Resolved& R) const {
+    R.args.lut_class = cls[k];
+    return place_luts(R.luts, d_blob + blob_base[k], 0, &R.args);
+  }
+ private:
+  std::vector<std::pair<const Plan::Resolved*, size_t>> reps_;  // first record of each class (the caller keeps its records where they are until the last add), its blob_base
+};
 
 // Column slots of the load-hoisting kernel for a record (fdb_plan.cpp); 0 when they do not fit.
 int assign_slots(const DeviceBatch& b, Plan::Resolved& R, int first_layout = 1, bool relaxed = false, bool* interp_ok = nullptr);

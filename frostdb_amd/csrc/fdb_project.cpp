@@ -153,17 +153,8 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
   if (!live.empty()) {
     std::vector<FdbScanArgs> parts;
     std::vector<FdbProjectPart> oparts;
-    Blob blob;
-    std::vector<size_t> blob_base(live.size(), 0);
-    std::vector<int> lut_class(live.size(), 0);
-    std::vector<size_t> reps;
-    for (size_t k = 0; k < live.size(); k++) {  // (same_lut_set: one device copy and one class per LUT set)
-      const Resolved& R = recs[(size_t)live[k]].R;
-      size_t found = reps.size();
-      for (size_t q = 0; q < reps.size(); q++) if (same_lut_set(recs[(size_t)live[reps[q]]].R, R)) { found = q; break; }
-      if (found < reps.size()) { lut_class[k] = (int)found; blob_base[k] = blob_base[reps[found]]; }
-      else { lut_class[k] = (int)reps.size(); blob_base[k] = blob.add(R.blob.bytes.data(), R.blob.bytes.size()); reps.push_back(k); }
-    }
+    LutClasses luts;
+    for (int i : live) luts.add(recs[(size_t)i].R);
     JitShape shape;
     size_t lut_lds_max = 0;
     int64_t total_tiles = 0;
@@ -171,13 +162,12 @@ std::vector<std::unique_ptr<DeviceBatch>> Plan::project_batches(const fdb_projec
     const FdbProjectPart* d_oparts = nullptr;
     {
       StageScope stage_scope(ctx_);
-      unsigned char* d_blob = blob.bytes.empty() ? nullptr : (unsigned char*)upload(blob.bytes.data(), blob.bytes.size());
+      unsigned char* d_blob = luts.blob.bytes.empty() ? nullptr : (unsigned char*)upload(luts.blob.bytes.data(), luts.blob.bytes.size());
       for (size_t k = 0; k < live.size(); k++) {
         const DeviceBatch& b = *in[live[k]];
         Rec& r = recs[(size_t)live[k]];
         FdbScanArgs& a = r.R.args;
-        lut_lds_max = std::max(lut_lds_max, place_luts(r.R.luts, d_blob + blob_base[k], 0, &a));
-        a.lut_class = lut_class[k];
+        lut_lds_max = std::max(lut_lds_max, luts.place(k, d_blob, r.R));
         // leaves of string comparisons in the early pools, the expressions' columns in the late 8-byte pool: a column several
         // expressions reference has ONE slot and is loaded once
         if (assign_slots(b, r.R, 2, /*relaxed=*/true) != 2) throw Error(FDB_ERR_UNSUPPORTED, "projection: the expressions reference more columns than the kernel has slots");

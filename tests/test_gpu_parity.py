@@ -1604,6 +1604,63 @@ def test_a_new_shape_is_interpreted_while_its_kernel_is_built(pp, monkeypatch, t
         rb.close()
 
 
+def test_slots_narrowed_for_a_kernel_that_is_still_being_built_are_widened_again(pp, monkeypatch, tmp_path):
+    """A record of 2^20 rows (from there on a record holds narrow-index caches) whose dictionaries have at most 255 entries: the launch
+    narrows its dictionary slots for the specialised kernel — the caches are built — and then, under $FDB_JIT_ASYNC=1 with an empty
+    cache directory, finds that kernel still missing: the interpreting kernel runs, the slots read the uint32 columns again, and the
+    algorithmic bytes are those of the same query under FDB_NO_JIT (which narrows nothing). Once the kernel is there the same query
+    scans both dictionary columns at 1 byte: 3 bytes per row and column less."""
+    import os
+    import time
+    os.chmod(tmp_path, 0o700)
+    rows = 1 << 20
+    rng = np.random.default_rng(4097)
+    rec = make_prometheus_batch(rng, rows, n_path=37)
+    # (a shape no other test of the process uses)
+    filt = Or(Col("labels.code") == "404", Col("labels.code") == "200")
+    aggs, groups = [Min(Col("value")), Sum(Col("timestamp")), Count(Col("value")), Max(Col("value"))], [Col("labels.path")]
+    want = run_oracle([rec], filt, aggs, groups)
+    cols = ["labels.path"] + [a.Name() for a in aggs]
+    rb = pp.ResidentBatch(rec)
+
+    def query():
+        plan = pp.HashAggregatePlan(filt, aggs, groups)
+        try:
+            plan.CallbackResident([rb])
+            kernel, nbytes = plan.last_kernel(), plan.stats()["algorithmic_bytes"]
+            return arrow_to_pydict(plan.Finish()), kernel, nbytes
+        finally:
+            plan.Close()
+
+    try:
+        monkeypatch.setenv("FDB_NO_JIT", "1")
+        got, kernel, wide_bytes = query()
+        assert kernel == "scan_slots_kernel" and rb.scan_cache_bytes == 0
+        assert_same_result(got, want, cols)
+        monkeypatch.delenv("FDB_NO_JIT")
+        monkeypatch.setenv("FDB_JIT_CACHE", str(tmp_path))
+        monkeypatch.setenv("FDB_JIT_ASYNC", "1")
+        before = pp.jit_stats()["compiled"]
+        got, kernel, nbytes = query()
+        assert kernel == "scan_slots_kernel", kernel
+        assert rb.scan_cache_bytes > 0  # narrowed: the caches of labels.code and labels.path exist …
+        assert nbytes == wide_bytes     # … and widened again: the launch read, and counts, the uint32 columns
+        assert_same_result(got, want, cols)
+        deadline = time.time() + 60
+        while pp.jit_stats()["compiled"] == before and time.time() < deadline:
+            time.sleep(0.02)
+        for _ in range(200):  # (compiled, then loaded: the entry is published a moment later)
+            got, kernel, nbytes = query()
+            if kernel == "fdb_plan_kernel":
+                break
+            time.sleep(0.02)
+        assert kernel == "fdb_plan_kernel", kernel
+        assert nbytes == wide_bytes - 2 * 3 * rows
+        assert_same_result(got, want, cols)
+    finally:
+        rb.close()
+
+
 def test_projection_needs_specialised_kernel(pp, monkeypatch):
     monkeypatch.setenv("FDB_NO_JIT", "1")
     rng = np.random.default_rng(92)
@@ -1621,6 +1678,31 @@ def test_projection_needs_specialised_kernel(pp, monkeypatch):
             plan.Callback(b)
     finally:
         plan.Close()
+
+
+def test_a_computed_input_whose_kernel_cannot_be_had_is_refused_by_the_sequential_kernel(pp, monkeypatch):
+    """A dense plan with a computed aggregate input, created while the run-time compiler counts as available: at the launch the kernel
+    cannot be had (FDB_NO_JIT is read again there), the interpreting slot kernel has no expressions, and the sequential kernel, the last
+    resort, refuses the computed column. Nothing was accumulated: with the compiler back, the same plan gives the oracle's result."""
+    rng = np.random.default_rng(93)
+    b = many_label_batch(rng, 1000, 2, 3, int_key=True)
+    aggs, groups = [Sum(Col("value") * Col("bucket")), Count(Col("value"))], [DynCol("labels")]
+    monkeypatch.delenv("FDB_NO_JIT", raising=False)
+    plan = pp.HashAggregatePlan(None, aggs, groups)
+    rb = pp.ResidentBatch(b)
+    try:
+        monkeypatch.setenv("FDB_NO_JIT", "1")
+        with pytest.raises(pp.UnsupportedError, match="sequential kernel"):
+            plan.CallbackResident([rb])
+        monkeypatch.delenv("FDB_NO_JIT")
+        plan.CallbackResident([rb])
+        assert plan.last_kernel() == "fdb_plan_kernel"
+        got = arrow_to_pydict(plan.Finish())
+    finally:
+        plan.Close()
+        rb.close()
+    want = run_oracle([b], None, aggs, groups)
+    assert_same_result(got, want, ["labels.l00", "labels.l01"] + [a.Name() for a in aggs])
 
 
 def test_config1_simple_schema(pp, variant):
