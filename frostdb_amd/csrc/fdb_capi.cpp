@@ -163,6 +163,24 @@ int fdb_selftest_scan_cache(const uint32_t* indices, int64_t rows, int32_t width
   });
 }
 
+int fdb_selftest_scan_cache_nulls(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t width, int device, uint8_t* out, int64_t out_bytes) {
+  return guard(nullptr, [&] {
+    if (indices == nullptr || validity == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || (width != 1 && width != 2) ||
+        entries < 0 || entries > (width == 1 ? 255 : 65535) || out_bytes != (rows * width + 15) / 16 * 16)
+      throw fdb::Error(FDB_ERR_INVALID, "scan cache: 1 to 2^28 rows, width 1 or 2, entries <= 255 / 65 535, out_bytes = rows * width rounded up to 16");
+    // the null-folded builder as scan_cache_get runs it: a uint32 column and its bitmap in their slots, the cache in a slot of its own width
+    fdb::CallScope call(device);
+    void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
+    uint8_t* d_bits = (uint8_t*)call.alloc(fdb::bitmap_slot((size_t)rows));
+    void* d_dst = call.alloc(fdb::values_slot((size_t)rows, (size_t)width));
+    fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), "scan cache: copy in");
+    fdb::hip_check(hipMemcpyAsync(d_bits, validity, (size_t)(rows + 7) / 8, hipMemcpyHostToDevice, call.ctx->stream), "scan cache: copy in");
+    fdb::hip_check(fdb_launch_narrow_indices((const uint32_t*)d_src, d_bits, (uint32_t)entries, d_dst, rows, width, call.ctx->stream), "scan cache: builder");
+    fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), "scan cache: copy out");
+    fdb::hip_check(hipStreamSynchronize(call.ctx->stream), "scan cache: wait");
+  });
+}
+
 int fdb_selftest_exact_sum(const double* x, int64_t n, double* out) {
   return guard(nullptr, [&] {
     if (n < 0 || out == nullptr || (n > 0 && x == nullptr)) throw fdb::Error(FDB_ERR_INVALID, "exact sum: n >= 0 and non-null buffers");

@@ -42,7 +42,8 @@ struct Plan::DenseLaunch {
   FoldFuncs funcs;
 
   // narrow_slots() / widen_slots()
-  struct Narrowed { int part, k, col; bool late; const void* wide; int64_t saved; };  // a slot switched to its record's narrow-index cache
+  // a slot switched to its record's narrow-index cache; `validity`: the bitmap it read before a null-folded buffer made it needless
+  struct Narrowed { int part, k, col; bool late; const void* wide; int64_t saved; const uint8_t* validity; bool folded; };
   std::vector<Narrowed> narrowed;
 
   // choose_kernel()
@@ -73,7 +74,10 @@ struct Plan::DenseLaunch {
   void fold_partials(unsigned long long* partials, int grid);
 };
 
-// group columns → mixed-radix digits through per-dictionary LUTs; the table re-laid for the dictionaries as they are now
+// group columns → mixed-radix digits through per-dictionary LUTs; the table re-laid for the dictionaries as they are now. A column whose
+// narrow-index cache is null-folded gets one more entry, lut[entries] = 0, the digit of NULL: narrow_pool may take the slot's bitmap away,
+// and then a NULL row arrives as that index. (Here, in front of stage_luts and plan_lds, which size the LUTs' copies; the 4 bytes are
+// never read by a launch that keeps the bitmap.)
 void Plan::DenseLaunch::bind_group_columns() {
   for (int i : live) {
     Resolved& R = Rs[(size_t)i];
@@ -83,12 +87,15 @@ void Plan::DenseLaunch::bind_group_columns() {
       const DevColumn& c = bs[i]->cols[(size_t)gr.ci];
       G.idx = (const uint32_t*)c.d_values;
       G.validity = c.d_validity;
-      G.lut_len = (uint32_t)gr.lut->size();
+      // (an empty dictionary's LUT is the one entry 0 already)
+      const size_t null_entry = scan_cache_folded(*bs[i], (size_t)gr.ci) && gr.lut->size() <= c.dict->values.size() ? 1 : 0;
+      G.lut_len = (uint32_t)(gr.lut->size() + null_entry);
       G.lut_lds = FDB_NO_LDS;
       G.slot = -1;
       R.gcol_col[a.n_gcols] = gr.ci;
       const size_t off = R.blob.add(gr.lut->data(), gr.lut->size() * 4);
-      R.luts.push_back(PendingLut{1, a.n_gcols, off, gr.lut->size() * 4});
+      R.blob.bytes.resize(R.blob.bytes.size() + null_entry * 4, 0);
+      R.luts.push_back(PendingLut{1, a.n_gcols, off, (gr.lut->size() + null_entry) * 4});
       part_gcols[(size_t)i].push_back(gr.gi);
       a.n_gcols++;
     }
@@ -154,10 +161,22 @@ void Plan::DenseLaunch::plan_lds() {
 // cache of that one width for the slot's column — built here, by the first scan that wants it; otherwise the whole launch reads
 // the slot's uint32 columns, which every record has. Slots without values (IS NULL leaves) have nothing to narrow. The
 // algorithmic bytes count the width that is scanned. (Before the shape is taken: jit_shape reads the widths.)
+// A slot narrowed to a null-folded buffer (scan_cache_folded) also loses its bitmap pointer: the buffer holds NULL as the index one past
+// the dictionary, which a leaf's truth table answers last and the group LUT maps to digit 0 (bind_group_columns), so the shape is that of
+// a column without NULLs (has_validity 0, or 2 when another record of the launch keeps a bitmap). The exception is a slot an IS (NOT) NULL
+// leaf reads: FDB_LEAF_VALIDITY is the one consumer of a 4-byte slot's nibble (<reg>_m in fdb_jitgen.cpp) besides leaf_bits / leaf_lut
+// and the group digit, which the folded index serves. The algorithmic bytes keep counting the bitmap: they are what the query reads
+// of the record, not what this launch fetches.
 void Plan::DenseLaunch::narrow_slots() {
   if (!specialisable() || !jit_possible) return;
   narrow_pool(false);
   if (two_phase) narrow_pool(true);
+}
+// whether an IS (NOT) NULL leaf reads early 4-byte slot `k` (leaves sit in the early pools only, assign_slots)
+static bool validity_leaf_reads(const FdbScanArgs& a, int k) {
+  for (int l = 0; l < a.n_leaves; l++)
+    if (a.leaves[l].kind == FDB_LEAF_VALIDITY && !a.leaves[l].wide && a.leaves[l].slot == k) return true;
+  return false;
 }
 void Plan::DenseLaunch::narrow_pool(bool late) {
   const FdbScanArgs& a0 = args(live[0]);
@@ -180,8 +199,10 @@ void Plan::DenseLaunch::narrow_pool(bool late) {
       bool counted = false;  // (a column the filter and the group-by both read sits in two slots and counts once)
       for (const Narrowed& nw : narrowed) if (nw.part == i && nw.col == ci) counted = true;
       const int64_t saved = counted ? 0 : bs[i]->rows * (int64_t)(4 - w);
-      narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved});
+      const bool fold = sl.validity != nullptr && scan_cache_folded(*bs[i], (size_t)ci) && !(!late && validity_leaf_reads(R.args, k));
+      narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved, sl.validity, fold});
       sl.values = scan_cache_get(*bs[i], (size_t)ci, P.stream_);
+      if (fold) sl.validity = nullptr;
       (late ? R.args.wl4 : R.args.w4)[k] = (uint8_t)w;
       R.bytes -= saved;
     }
@@ -192,6 +213,7 @@ void Plan::DenseLaunch::widen_slots() {
   for (const Narrowed& nw : narrowed) {
     Resolved& R = Rs[(size_t)nw.part];
     (nw.late ? R.args.l4 : R.args.c4)[nw.k].values = nw.wide;
+    (nw.late ? R.args.l4 : R.args.c4)[nw.k].validity = nw.validity;
     (nw.late ? R.args.wl4 : R.args.w4)[nw.k] = 0;
     R.bytes += nw.saved;
   }
@@ -309,9 +331,13 @@ void Plan::DenseLaunch::launch_slots() {
   P.ctx_->flush_staging();
   pt.mark("parts upload");
   P.trace("after upload");
-  if (pt.on)
+  if (pt.on) {
+    std::vector<uint32_t> folded(parts.size(), 0u);
+    for (const Narrowed& nw : narrowed)
+      if (nw.folded) folded[(size_t)(std::find(live.begin(), live.end(), nw.part) - live.begin())] |= 1u << ((nw.late ? 16 : 0) + nw.k);
     print_dense_launch(jit_fn != nullptr ? "fdb_plan_kernel" : "scan_slots_kernel", shape_key, parts.data(), parts.size(), total_tiles, grid, jit_fn != nullptr ? jit_block : 0, lds.lds_bytes,
-                       two_phase, lds.lds_acc, lds.cache_slots, lut_lds_max, per_cu, tile_rows, fill_rides, partials != nullptr);
+                       two_phase, lds.lds_acc, lds.cache_slots, lut_lds_max, per_cu, tile_rows, fill_rides, partials != nullptr, folded);
+  }
   P.timed([&] {
     if (jit_fn != nullptr) hip_check(jit_launch(jit_fn, d_parts, (int)parts.size(), total_tiles, parts[0], grid, jit_block, lds.lds_bytes, P.stream_), "scan launch");
     else hip_check(fdb_launch_scan_slots(d_parts, (int)parts.size(), parts[0], total_tiles, grid, lds.lds_bytes, two_phase, sub, P.stream_), "scan launch");

@@ -736,6 +736,8 @@ hipError_t fdb_launch_reduce_partials(const unsigned long long* partials, int n_
 // the last, partial block in row order), zero up to the next multiple of 16 bytes (width: 1 or 2): the narrow-index cache of a resident
 // dictionary column. Both buffers are sized like a values slot (kTailPad past the payload), which the 16-byte accesses rely on.
 hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream);
+// The null-folded form: a row whose bit of `validity` (a bitmap slot, bit offset 0) is clear is written as `null_index`, which fits the width.
+hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream);
 // Measurement only: reads `bytes` (multiple of 16) once with the best streaming pattern of this box.
 hipError_t fdb_launch_stream_read(const void* src, int64_t bytes, unsigned long long* out, hipStream_t stream);
 hipError_t fdb_launch_scan_slots(const FdbScanArgs* d_parts, int n_parts, const FdbScanArgs& common, int64_t total_tiles, int grid_blocks,

@@ -2302,11 +2302,15 @@ namespace {
 // 16-byte vectors. The vectors of the record's full 1 024-row blocks are written in the wave-interleaved order fdb_plan_kernel loads them
 // in (scan_cache_position): vector l of a block (and of its half h, W = 2) holds lane l's rows 256 u + 4 l … + 3 of sub-steps u = 0 … 3
 // (W = 2: u = 2 h, 2 h + 1), gathered from 4 / 2 reads 1 KiB apart — each wave read instruction still contiguous. The vectors of the last,
-// partial block hold consecutive rows. Whatever sits under a NULL row is truncated (the scan masks it with the validity nibble anyway);
-// rows past the last one, up to the end of the thread's vector, are written as 0, so that a tail lane of the scan finds a legal index
-// there. The last thread reads ≤ 15 rows = 60 bytes and writes ≤ 15 bytes past the payloads: inside kTailPad of either slot.
-template <int W>
-__global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, int64_t rows, int64_t n_vec) {
+// partial block hold consecutive rows. FOLD (a null-folded buffer, fdb_record.h): a NULL row is written as `null_index`, the index one
+// past the dictionary; the validity nibble of source vector v (rows 4 v … 4 v + 3) is the (v & 1)-th nibble of bitmap byte v / 2, and
+// the thread's 4 / 2 nibbles are loaded with its source vectors, before the first is looked at. Otherwise whatever sits under a NULL row
+// is truncated (the scan masks it with the validity nibble anyway). Rows past the last one, up to the end of the thread's vector, are
+// written as 0, so that a tail lane of the scan finds a legal index there. The last thread reads ≤ 15 rows = 60 bytes (and 2 bitmap
+// bytes) and writes ≤ 15 bytes past the payloads: inside kTailPad of each slot.
+template <int W, bool FOLD>
+__global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __restrict__ src, const uint8_t* __restrict__ validity, uint32_t null_index, u32x4* __restrict__ dst,
+                                                             int64_t rows, int64_t n_vec) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_vec) return;
   constexpr int PER = 16 / W;  // rows per thread
@@ -2318,14 +2322,21 @@ __global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __rest
   const int64_t s0 = interleaved ? (i / VB) * (fdb::kScanCacheBlock / 4) + ((i % VB) / 64) * (64 * NV) + (i % 64) : i * NV;
   const int64_t sd = interleaved ? 64 : 1;
   uint32_t w[4] = {0u, 0u, 0u, 0u};
+  u32x4 in[NV];
+  uint32_t valid[NV];
 #pragma unroll
   for (int k = 0; k < NV; k++) {
-    const u32x4 v = __builtin_nontemporal_load(as_global(src + s0 + k * sd));
-    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+    in[k] = __builtin_nontemporal_load(as_global(src + s0 + k * sd));
+    valid[k] = FOLD ? (uint32_t)validity[(s0 + k * sd) >> 1] >> (4 * (int)((s0 + k * sd) & 1)) : 0xFu;
+  }
+#pragma unroll
+  for (int k = 0; k < NV; k++) {
+    const uint32_t e[4] = {in[k].x, in[k].y, in[k].z, in[k].w};
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const int r = k * 4 + q;  // element of the thread's vector; W bytes at byte r * W of its output
-      const uint32_t x = interleaved || r0 + r < rows ? (e[q] & (W == 1 ? 0xFFu : 0xFFFFu)) : 0u;
+      const uint32_t idx = (valid[k] >> q) & 1u ? (e[q] & (W == 1 ? 0xFFu : 0xFFFFu)) : null_index;
+      const uint32_t x = interleaved || r0 + r < rows ? idx : 0u;
       w[(r * W) / 4] |= x << (8 * ((r * W) % 4));
     }
   }
@@ -2334,14 +2345,26 @@ __global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __rest
 }
 }  // namespace
 
-hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream) {
+namespace {
+template <bool FOLD>
+hipError_t launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream) {
   if (rows <= 0) return hipSuccess;
   if (width != 1 && width != 2) return hipErrorInvalidValue;
   const int64_t per = 16 / width, n_vec = (rows + per - 1) / per;
   const unsigned grid = (unsigned)((n_vec + 255) / 256);
-  if (width == 1) hipLaunchKernelGGL(narrow_indices_kernel<1>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), reinterpret_cast<u32x4*>(dst), rows, n_vec);
-  else hipLaunchKernelGGL(narrow_indices_kernel<2>, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), reinterpret_cast<u32x4*>(dst), rows, n_vec);
+  if (width == 1) hipLaunchKernelGGL((narrow_indices_kernel<1, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<u32x4*>(dst), rows, n_vec);
+  else hipLaunchKernelGGL((narrow_indices_kernel<2, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<u32x4*>(dst), rows, n_vec);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream) {
+  return launch_narrow_indices<false>(src, nullptr, 0u, dst, rows, width, stream);
+}
+
+hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream) {
+  if (validity == nullptr || null_index > (width == 1 ? 0xFFu : 0xFFFFu)) return hipErrorInvalidValue;
+  return launch_narrow_indices<true>(src, validity, null_index, dst, rows, width, stream);
 }
 
 namespace {

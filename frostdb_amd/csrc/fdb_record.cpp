@@ -31,6 +31,12 @@ int scan_cache_width(const DeviceBatch& b, size_t c) {
   return narrow_width(col.dict->values.size());
 }
 
+bool scan_cache_folded(const DeviceBatch& b, size_t c) {
+  if (scan_cache_width(b, c) >= 4) return false;
+  const DevColumn& col = b.cols[c];
+  return col.d_validity != nullptr && scan_cache_folds(col.dict->values.size(), col.null_count, b.rows);
+}
+
 const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
   const int width = scan_cache_width(b, c);
   if (width >= 4) throw Error(FDB_ERR_INVALID, "internal: no narrow-index cache for column " + b.cols[c].name);
@@ -41,10 +47,12 @@ const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
   if (e.d != nullptr) return e.d;
   const size_t bytes = values_slot((size_t)b.rows, (size_t)width);
   void* d = device_pool_alloc(b.device, bytes);
-  hipError_t err = fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, d, b.rows, width, stream);
+  const bool folded = scan_cache_folded(b, c);
+  hipError_t err = folded ? fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, b.cols[c].d_validity, (uint32_t)b.cols[c].dict->values.size(), d, b.rows, width, stream)
+                          : fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, d, b.rows, width, stream);
   if (err == hipSuccess) err = hipStreamSynchronize(stream);
   if (err != hipSuccess) { device_pool_free(b.device, d); hip_check(err, "narrow-index cache"); }
-  e.d = d; e.width = width; e.bytes = bytes;
+  e.d = d; e.width = width; e.bytes = bytes; e.folded = folded;
   sc.bytes += (int64_t)bytes;
   return d;
 }

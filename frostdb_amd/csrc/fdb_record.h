@@ -48,6 +48,20 @@ FDB_RECORD_HD inline int64_t scan_cache_position(int64_t i, int64_t rows, int wi
   return width == 1 ? kScanCacheBlock * b + 16 * l + 4 * u + r : kScanCacheBlock * b + 512 * (u / 2) + 8 * l + 4 * (u % 2) + r;
 }
 
+// What the cache holds for a dictionary column, from numbers alone (tools/scan_cache_dump.cpp prints them for a test to hold to a table).
+constexpr int64_t kScanCacheMinRows = (int64_t)1 << 20;  // below it 3 B/row and column save less than a microsecond of a scan
+// Bytes per index the cache can hold for a dictionary of `entries` entries; 4: none (the column itself).
+inline int narrow_width(size_t entries) { return entries <= 256 ? 1 : entries <= 65536 ? 2 : 4; }
+// … of a resident record of `rows` rows
+inline int scan_cache_width_of(size_t entries, int64_t rows) { return rows < kScanCacheMinRows ? 4 : narrow_width(entries); }
+// Null-folded: the buffer holds the index S = `entries`, one past the dictionary, under every NULL row, so that its reader needs no
+// bitmap. The column has a bitmap (`nulls` > 0) and S fits the width: at most 255 entries at 1 byte, 65 535 at 2. Dictionaries of
+// exactly 256 and 65 536 entries keep their width, are not folded, and are scanned with their bitmap.
+inline bool scan_cache_folds(size_t entries, int64_t nulls, int64_t rows) {
+  const int w = scan_cache_width_of(entries, rows);
+  return nulls > 0 && w < 4 && entries < ((size_t)1 << (8 * w));
+}
+
 // Offsets of the slots of one record, in column order: [values | bitmap] per column.
 struct RecordLayout {
   struct Col { size_t val_off, bit_off; };  // bit_off == kNoSlot: no bitmap slot
@@ -125,17 +139,19 @@ struct CallScope {
 // it: the cache is extra memory, up to 3 bytes per row and scanned dictionary column, reported by fdb_batch_scan_cache_bytes.
 // A buffer is sized like a values slot and comes from the device pool, so fdb_live_allocations counts it. Its bytes are a private layout
 // (scan_cache_position, above): no other operator, and nothing outside the library, reads them.
-constexpr int64_t kScanCacheMinRows = (int64_t)1 << 20;  // below it 3 B/row and column save less than a microsecond of a scan
-// Bytes per index the cache can hold for a dictionary of `entries` entries; 4: none (the column itself).
-inline int narrow_width(size_t entries) { return entries <= 256 ? 1 : entries <= 65536 ? 2 : 4; }
+// NULL is an index of its own where it fits (scan_cache_folds, above): a null-folded buffer holds S = the dictionary's entry count
+// under every NULL row, the answer a filter leaf's truth table keeps last and the entry a group LUT gets appended (digit 0), so the scan
+// of such a column loads no bitmap. A buffer that is not folded holds the truncated uint32 of every row, a NULL row's included.
 struct ScanCache {
-  struct Col { void* d = nullptr; int width = 0; size_t bytes = 0; };
+  struct Col { void* d = nullptr; int width = 0; size_t bytes = 0; bool folded = false; };
   std::vector<Col> cols;  // by column of the record; empty until the first buffer
   int64_t bytes = 0;      // Σ values_slot(rows, width) of the buffers
 };
 // Width at which a dense generated scan may read column `c` of `b` — 1, 2, or 4 when the column gets no buffer: no dictionary column,
 // a dictionary too large, a record below kScanCacheMinRows or a transient one (a host record is scanned once). Builds nothing.
 int scan_cache_width(const DeviceBatch& b, size_t c);
+// Whether that buffer is (or, once built, will be) null-folded: scan_cache_folds of the column's dictionary, NULL count and rows. Builds nothing.
+bool scan_cache_folded(const DeviceBatch& b, size_t c);
 // The buffer of column `c` (scan_cache_width(b, c) < 4), built on `stream` if it is not there yet. Two plans on two threads and two
 // streams may meet the same fresh record: the record's mutex is held from the look-up to the publication, and a buffer is published
 // only after the stream that built it has been synchronised — exactly one survives and nobody reads it early.

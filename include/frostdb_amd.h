@@ -249,6 +249,11 @@ FDB_API int fdb_selftest_widen(const void* src, int32_t width, uint32_t* dst, in
  * bytes and copies the buffer's first `out_bytes` = rows x width rounded up to 16 bytes to `out` — the indices in the cache's order and
  * zeros behind the last row. FDB_ERR_INVALID also when a row is not where the library's own position formula puts it. */
 FDB_API int fdb_selftest_scan_cache(const uint32_t* indices, int64_t rows, int32_t width, int device, uint8_t* out, int64_t out_bytes);
+/* … of its null-folded form, which a column with NULLs gets when its dictionary of `entries` entries leaves room for one more index at
+ * `width` (entries <= 255 at 1 byte, <= 65 535 at 2): `validity` is the column's Arrow bitmap at bit offset 0, (rows + 7) / 8 bytes, and
+ * the buffer holds `entries` under every NULL row, whatever `indices` holds there. `out` as above; nothing is checked beyond the arguments. */
+FDB_API int fdb_selftest_scan_cache_nulls(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t width, int device, uint8_t* out,
+                                          int64_t out_bytes);
 
 /* ---- plan life cycle (≙ physicalplan.Build for one chain, physicalplan.go:417-474) -------------- */
 /* `desc` and everything it points at (expression nodes, names, literals, patterns) is copied: the caller may free it as soon

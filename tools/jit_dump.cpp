@@ -99,9 +99,10 @@ static void replace_sum(std::vector<fdb::JitAgg>& aggs, fdb::JitAgg a, int root)
 
 int main(int argc0, char** argv0) {
   // keyword arguments, anywhere on the line: agg=<func><type>:<expression> (a computed aggregate input in the place of the shape's first SUM),
-  // key=<expression> (hash modes: the last key column computed), nopred (flags / select: no predicate), fuse4 (select: the 4-byte slot fused too)
+  // key=<expression> (hash modes: the last key column computed), nopred (flags / select: no predicate), fuse4 (select: the 4-byte slot fused too),
+  // nonull (plan: the dictionary slots without bitmaps)
   std::string agg_arg, key_arg;
-  bool nopred = false, fuse4 = false;
+  bool nopred = false, fuse4 = false, nonull = false;
   std::vector<char*> pos;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
@@ -109,6 +110,7 @@ int main(int argc0, char** argv0) {
     else if (i > 0 && a.rfind("key=", 0) == 0) key_arg = a.substr(4);
     else if (i > 0 && a == "nopred") nopred = true;
     else if (i > 0 && a == "fuse4") fuse4 = true;
+    else if (i > 0 && a == "nonull") nonull = true;
     else pos.push_back(argv0[i]);
   }
   const int argc = (int)pos.size();
@@ -176,6 +178,10 @@ int main(int argc0, char** argv0) {
     }
     if (argc > 4) s.block = std::atoi(argv[4]);  // plan <variant> narrow <threads per workgroup>
     if (argc > 5 && std::string(argv[5]) == "sum" && !s.two_phase) s.aggs.resize(1);  // plan <variant> narrow <threads> sum: SUM(float64) alone, bench.py's headline query
+    if (nonull) {  // plan … nonull: no 4-byte slot has a bitmap — columns without NULLs, or null-folded caches (fdb_record.h), the headline's launch
+      for (int i = 0; i < s.n_c4; i++) s.c4[i].has_validity = 0;
+      for (int i = 0; i < s.n_l4; i++) s.l4[i].has_validity = 0;
+    }
     if (!agg_arg.empty()) { std::string spec; const fdb::JitAgg A = computed_agg(agg_arg, &spec); replace_sum(s.aggs, A, parse_into(s, spec).at(0)); }
     std::fputs(fdb::jit_source(s).c_str(), stdout);
     return 0;
