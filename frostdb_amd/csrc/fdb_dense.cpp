@@ -43,8 +43,10 @@ struct Plan::DenseLaunch {
 
   // narrow_slots() / widen_slots()
   // a slot switched to its record's narrow-index cache; `validity`: the bitmap it read before a null-folded buffer made it needless
-  struct Narrowed { int part, k, col; bool late; const void* wide; int64_t saved; const uint8_t* validity; bool folded; };
+  // (prev_of_part: the record's previous entry, SIZE_MAX: none — a record's few slots are found without a walk over the launch's)
+  struct Narrowed { int part, k, col; bool late; const void* wide; int64_t saved; const uint8_t* validity; bool folded; size_t prev_of_part; };
   std::vector<Narrowed> narrowed;
+  std::vector<size_t> narrowed_by_part;  // [record] its last entry in `narrowed`
 
   // choose_kernel()
   hipFunction_t jit_fn = nullptr;
@@ -53,6 +55,11 @@ struct Plan::DenseLaunch {
   bool slot_kernel = false;  // a slot kernel (specialised or interpreting) serves the launch; otherwise the sequential kernel
   int per_cu = 1;            // slot kernels: workgroups per CU …
   int tile_rows = 0;         // … and rows per tile (specialised: jit_block × 4, × 16 for a quad shape, JitShape::quad)
+  // The packed part table (JitShape::part_table): a specialised quad launch whose records' fields — ptab_words per record — fit the cap
+  // ships and reads those words only. 0 words: the argument blocks.
+  JitShape shape;
+  int ptab_words = 0;
+  std::vector<PartField> part_fields;  // jit_part_fields(shape), made once per launch
 
   DenseLaunch(Plan& p, const DeviceBatch* const* b, std::vector<Resolved>& rs, std::vector<std::vector<int>>& gc, const std::vector<int>& lv, bool fixed, PhaseTimer& t)
       : P(p), bs(b), Rs(rs), part_gcols(gc), live(lv), fixed_order(fixed), pt(t), jit_possible(p.jit_possible()), sub(p.sub_tiles == 4 ? 0 : p.sub_tiles) {}
@@ -78,27 +85,56 @@ struct Plan::DenseLaunch {
 // narrow-index cache is null-folded gets one more entry, lut[entries] = 0, the digit of NULL: narrow_pool may take the slot's bitmap away,
 // and then a NULL row arrives as that index. (Here, in front of stage_luts and plan_lds, which size the LUTs' copies; the 4 bytes are
 // never read by a launch that keeps the bitmap.)
+// The parts of a table mostly share their dictionaries, so their LUTs are the same objects (GroupColState::lut_for, the truth cache): a record
+// whose sources are those of an earlier one (`firsts`) takes that record's LUT list and copies nothing into its blob.
 void Plan::DenseLaunch::bind_group_columns() {
+  struct Src {  // one LUT's source: the object, and for a group LUT whether the entry for NULL follows it (part of the set)
+    const void* lut; bool null_entry;
+    bool operator==(const Src& o) const { return lut == o.lut && null_entry == o.null_entry; }
+  };
+  struct First { int rec; size_t n_leaf_luts; std::vector<Src> src; };
+  std::vector<First> firsts;
+  std::vector<Src> src;
   for (int i : live) {
     Resolved& R = Rs[(size_t)i];
     FdbScanArgs& a = R.args;
+    src.clear();
+    for (const auto& p : R.lut_src) src.push_back(Src{p.get(), false});
+    // whether a group column's LUT gets the entry for NULL (an empty dictionary's LUT is the one entry 0 already)
+    auto null_entry_of = [&](const GroupRes& gr) {
+      return scan_cache_folded(*bs[i], (size_t)gr.ci) && gr.lut->size() <= bs[i]->cols[(size_t)gr.ci].dict->values.size();
+    };
+    for (const GroupRes& gr : R.groups) src.push_back(Src{gr.lut.get(), null_entry_of(gr)});
+    const First* like = nullptr;
+    for (const First& f : firsts) {
+      const Resolved& Q = Rs[(size_t)f.rec];
+      if (f.src != src || f.n_leaf_luts != R.luts.size()) continue;
+      bool same = true;
+      for (size_t k = 0; same && k < R.luts.size(); k++)
+        same = Q.luts[k].kind == R.luts[k].kind && Q.luts[k].index == R.luts[k].index && Q.luts[k].blob_off == R.luts[k].blob_off && Q.luts[k].len_bytes == R.luts[k].len_bytes;
+      if (same) { like = &f; break; }
+    }
+    if (like == nullptr) firsts.push_back(First{i, R.luts.size(), src});
     for (const GroupRes& gr : R.groups) {
       FdbGroupCol& G = a.gcols[a.n_gcols];
       const DevColumn& c = bs[i]->cols[(size_t)gr.ci];
       G.idx = (const uint32_t*)c.d_values;
       G.validity = c.d_validity;
-      // (an empty dictionary's LUT is the one entry 0 already)
-      const size_t null_entry = scan_cache_folded(*bs[i], (size_t)gr.ci) && gr.lut->size() <= c.dict->values.size() ? 1 : 0;
+      const size_t null_entry = null_entry_of(gr) ? 1 : 0;
       G.lut_len = (uint32_t)(gr.lut->size() + null_entry);
       G.lut_lds = FDB_NO_LDS;
       G.slot = -1;
       R.gcol_col[a.n_gcols] = gr.ci;
-      const size_t off = R.blob.add(gr.lut->data(), gr.lut->size() * 4);
-      R.blob.bytes.resize(R.blob.bytes.size() + null_entry * 4, 0);
-      R.luts.push_back(PendingLut{1, a.n_gcols, off, (gr.lut->size() + null_entry) * 4});
+      if (like == nullptr) {
+        const size_t off = R.blob.add(gr.lut->data(), gr.lut->size() * 4);
+        R.blob.bytes.resize(R.blob.bytes.size() + null_entry * 4, 0);
+        R.luts.push_back(PendingLut{1, a.n_gcols, off, (gr.lut->size() + null_entry) * 4});
+        R.lut_src.push_back(gr.lut);
+      }
       part_gcols[(size_t)i].push_back(gr.gi);
       a.n_gcols++;
     }
+    if (like != nullptr) { R.lut_like = like->rec; R.luts = Rs[(size_t)like->rec].luts; }
   }
   std::vector<uint32_t> caps;
   for (const GroupColState& g : P.gcols_) caps.push_back((uint32_t)g.values.size() + 1);
@@ -107,7 +143,13 @@ void Plan::DenseLaunch::bind_group_columns() {
 }
 
 void Plan::DenseLaunch::stage_luts() {
-  for (int i : live) luts.add(Rs[(size_t)i]);
+  std::vector<size_t> at(Rs.size(), 0);  // [record] its place among the launch's
+  size_t n_added = 0;
+  for (int i : live) {
+    const Resolved& R = Rs[(size_t)i];
+    if (R.lut_like >= 0) luts.add_like(at[(size_t)R.lut_like]); else luts.add(R);
+    at[(size_t)i] = n_added++;
+  }
   stage_scope.emplace(P.ctx_);
   unsigned char* d_blob = luts.blob.bytes.empty() ? nullptr : (unsigned char*)P.upload(luts.blob.bytes.data(), luts.blob.bytes.size());
   size_t k = 0;
@@ -169,6 +211,7 @@ void Plan::DenseLaunch::plan_lds() {
 // of the record, not what this launch fetches.
 void Plan::DenseLaunch::narrow_slots() {
   if (!specialisable() || !jit_possible) return;
+  narrowed_by_part.assign(Rs.size(), SIZE_MAX);
   narrow_pool(false);
   if (two_phase) narrow_pool(true);
 }
@@ -197,10 +240,11 @@ void Plan::DenseLaunch::narrow_pool(bool late) {
       const int ci = late ? R.l4_col[k] : R.c4_col[k];
       FdbColSlot& sl = late ? R.args.l4[k] : R.args.c4[k];
       bool counted = false;  // (a column the filter and the group-by both read sits in two slots and counts once)
-      for (const Narrowed& nw : narrowed) if (nw.part == i && nw.col == ci) counted = true;
+      for (size_t at = narrowed_by_part[(size_t)i]; at != SIZE_MAX; at = narrowed[at].prev_of_part) if (narrowed[at].col == ci) counted = true;
       const int64_t saved = counted ? 0 : bs[i]->rows * (int64_t)(4 - w);
       const bool fold = sl.validity != nullptr && scan_cache_folded(*bs[i], (size_t)ci) && !(!late && validity_leaf_reads(R.args, k));
-      narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved, sl.validity, fold});
+      narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved, sl.validity, fold, narrowed_by_part[(size_t)i]});
+      narrowed_by_part[(size_t)i] = narrowed.size() - 1;
       sl.values = scan_cache_get(*bs[i], (size_t)ci, P.stream_);
       if (fold) sl.validity = nullptr;
       (late ? R.args.wl4 : R.args.w4)[k] = (uint8_t)w;
@@ -226,7 +270,6 @@ void Plan::DenseLaunch::widen_slots() {
 bool Plan::DenseLaunch::choose_kernel() {
   jit_block = fixed_order ? 256 : sub == 1 ? 512 : sub == 2 ? 256 : sub == 3 ? 1024 : 0;
   if (specialisable()) {
-    JitShape shape;
     bool same = true, first = true;
     const FdbScanArgs& args0 = args(live[0]);
     for (int i : live) {
@@ -242,6 +285,13 @@ bool Plan::DenseLaunch::choose_kernel() {
     }
     shape.wave_tables = fixed_order;
     shape.uniform_fold = !P.knobs_.no_uniform_fold;
+    // (a launch over ONE record has no boundary to cross and its one argument block is the by-value copy already: the table would only
+    // add its packing — one 25 M-row record measured 2 µs per step slower with it, profiles/part_table_ab.json)
+    if (same && shape.quad && live.size() > 1) {
+      part_fields = jit_part_fields(shape);
+      const int words = jit_part_words(part_fields);
+      if (live.size() * (size_t)words * 8 <= (size_t)P.knobs_.part_table_cap) { shape.part_table = true; ptab_words = words; }
+    }
     if (same) {
       // ($FDB_JIT_ASYNC=1: a shape whose kernel still has to be built is scanned by the interpreting kernel meanwhile — when that one can)
       JitDeferScope defer(interp_ok && !fixed_order);
@@ -251,6 +301,7 @@ bool Plan::DenseLaunch::choose_kernel() {
       if (pt.on && jit_fn != nullptr) shape_key = shape.key(true);
     }
   }
+  if (jit_fn == nullptr) ptab_words = 0;
   if (slots_ok && jit_fn == nullptr) widen_slots();
   // a launch only the specialised kernel could serve (more leaves / aggregates than the interpreting kernel's register-resident
   // plan holds, computed columns) falls back to the sequential kernel when specialisation is unavailable
@@ -306,17 +357,29 @@ void Plan::DenseLaunch::launch() {
 // one launch of the slot kernel (specialised or interpreting) over every record
 void Plan::DenseLaunch::launch_slots() {
   int grid = P.grid_override > 0 ? P.grid_override : (fdb_scan_default_grid(P.device_) / 2) * per_cu;
+  // the records' argument blocks (3 KB apiece) go to the device as they are — or, for a part-table launch, stay where they are: the
+  // table is packed straight from them, a few words per record
+  const bool ptab = ptab_words > 0;
   std::vector<FdbScanArgs> parts;
-  parts.reserve(live.size());  // (3 KB apiece: no re-growing copies)
-  for (int i : live) parts.push_back(args(i));
-  const int64_t total_tiles = assign_tiles(parts.data(), parts.size(), tile_rows);
+  std::vector<FdbScanArgs*> recs;
+  int64_t total_tiles = 0;
+  if (ptab) {
+    for (int i : live) recs.push_back(&args(i));
+    total_tiles = assign_tiles(recs.data(), recs.size(), tile_rows);
+  } else {
+    parts.reserve(live.size());  // (no re-growing copies)
+    for (int i : live) parts.push_back(args(i));
+    total_tiles = assign_tiles(parts.data(), parts.size(), tile_rows);
+  }
+  const int n_parts = (int)live.size();
   if (grid > total_tiles) grid = (int)total_tiles;
   unsigned long long* partials = alloc_partials(grid);
-  for (FdbScanArgs& a : parts) a.partials = partials;
+  if (ptab) recs[0]->partials = partials;  // (the kernel reads the by-value copy's)
+  else for (FdbScanArgs& a : parts) a.partials = partials;
+  FdbScanArgs& a0 = ptab ? *recs[0] : parts[0];
   bool fill_rides = false;
   if (P.state_virgin_ && jit_fn != nullptr && partials != nullptr && (uint64_t)P.slots_alloc_ * (1 + P.aggs_.size()) < (1ull << 32)) {
     // nothing accumulates into the table before reduce_partials (the next kernel on the stream): the scan fills it on its way in
-    FdbScanArgs& a0 = parts[0];
     a0.fill_state = P.d_state_;
     a0.fill_words = (uint32_t)(P.slots_alloc_ * (1 + P.aggs_.size()));
     a0.fill_alloc = (uint32_t)P.slots_alloc_;
@@ -327,20 +390,29 @@ void Plan::DenseLaunch::launch_slots() {
   }
   P.trace("before scan");
   pt.mark("parts build");
-  const FdbScanArgs* d_parts = (const FdbScanArgs*)P.upload(parts.data(), parts.size() * sizeof(FdbScanArgs));
+  const void* d_parts = nullptr;
+  if (ptab) {
+    std::vector<unsigned long long> table((size_t)n_parts * (size_t)ptab_words);
+    jit_pack_parts(part_fields, ptab_words, recs.data(), recs.size(), table.data());
+    d_parts = P.upload(table.data(), table.size() * 8);
+  } else {
+    d_parts = P.upload(parts.data(), parts.size() * sizeof(FdbScanArgs));
+  }
   P.ctx_->flush_staging();
   pt.mark("parts upload");
   P.trace("after upload");
   if (pt.on) {
-    std::vector<uint32_t> folded(parts.size(), 0u);
+    if (!ptab) for (FdbScanArgs& a : parts) recs.push_back(&a);  // (printed through pointers: no copy of the blocks inside a timed phase)
+    std::vector<uint32_t> folded(recs.size(), 0u);
     for (const Narrowed& nw : narrowed)
       if (nw.folded) folded[(size_t)(std::find(live.begin(), live.end(), nw.part) - live.begin())] |= 1u << ((nw.late ? 16 : 0) + nw.k);
-    print_dense_launch(jit_fn != nullptr ? "fdb_plan_kernel" : "scan_slots_kernel", shape_key, parts.data(), parts.size(), total_tiles, grid, jit_fn != nullptr ? jit_block : 0, lds.lds_bytes,
-                       two_phase, lds.lds_acc, lds.cache_slots, lut_lds_max, per_cu, tile_rows, fill_rides, partials != nullptr, folded);
+    print_dense_launch(jit_fn != nullptr ? "fdb_plan_kernel" : "scan_slots_kernel", shape_key, recs.data(), recs.size(), total_tiles, grid, jit_fn != nullptr ? jit_block : 0, lds.lds_bytes,
+                       two_phase, lds.lds_acc, lds.cache_slots, lut_lds_max, per_cu, tile_rows, fill_rides, partials != nullptr, folded, ptab_words);
   }
   P.timed([&] {
-    if (jit_fn != nullptr) hip_check(jit_launch(jit_fn, d_parts, (int)parts.size(), total_tiles, parts[0], grid, jit_block, lds.lds_bytes, P.stream_), "scan launch");
-    else hip_check(fdb_launch_scan_slots(d_parts, (int)parts.size(), parts[0], total_tiles, grid, lds.lds_bytes, two_phase, sub, P.stream_), "scan launch");
+    if (ptab) hip_check(jit_launch_ptab(jit_fn, (const unsigned long long*)d_parts, n_parts, total_tiles, a0, grid, jit_block, lds.lds_bytes, P.stream_), "scan launch");
+    else if (jit_fn != nullptr) hip_check(jit_launch(jit_fn, (const FdbScanArgs*)d_parts, n_parts, total_tiles, a0, grid, jit_block, lds.lds_bytes, P.stream_), "scan launch");
+    else hip_check(fdb_launch_scan_slots((const FdbScanArgs*)d_parts, n_parts, a0, total_tiles, grid, lds.lds_bytes, two_phase, sub, P.stream_), "scan launch");
   });
   if (fill_rides) P.state_virgin_ = false;  // (only once the launch that carries the fill was accepted: a throw above leaves the table marked unfilled)
   P.last_kernel_ = jit_fn != nullptr ? "fdb_plan_kernel" : "scan_slots_kernel";
@@ -362,7 +434,8 @@ void Plan::DenseLaunch::launch_sequential() {
     a.n_c4 = a.n_c8 = 0;
     const int grid = fdb_scan_grid(a, lds.base_grid, rpt);
     a.partials = alloc_partials(grid);
-    if (pt.on) print_dense_launch("scan_dense_kernel", "", &a, 1, 0, grid, 0, lds.lds_bytes, 0, lds.lds_acc, lds.cache_slots, lut_lds_max, 0, rpt, false, a.partials != nullptr);
+    const FdbScanArgs* one = &a;
+    if (pt.on) print_dense_launch("scan_dense_kernel", "", &one, 1, 0, grid, 0, lds.lds_bytes, 0, lds.lds_acc, lds.cache_slots, lut_lds_max, 0, rpt, false, a.partials != nullptr);
     P.timed([&] { hip_check(fdb_launch_scan_dense(a, grid, lds.lds_bytes, rpt, P.stream_), "scan launch"); });
     P.last_kernel_ = "scan_dense_kernel";
     P.mirror_valid_ = false;  // (a launch that flushes with atomics leaves the host copy behind)

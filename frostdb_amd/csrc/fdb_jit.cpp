@@ -326,4 +326,11 @@ hipError_t jit_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_parts,
   return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, (unsigned)lds_bytes, stream, args, nullptr);
 }
 
+hipError_t jit_launch_ptab(hipFunction_t fn, const unsigned long long* d_ptab, int n_parts, int64_t total_tiles, const FdbScanArgs& common, int grid, int block,
+                           size_t lds_bytes, hipStream_t stream) {
+  long long tt = total_tiles;
+  void* args[] = {(void*)&d_ptab, (void*)&n_parts, (void*)&tt, (void*)&common};
+  return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, (unsigned)lds_bytes, stream, args, nullptr);
+}
+
 }  // namespace fdb

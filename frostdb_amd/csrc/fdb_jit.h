@@ -52,6 +52,10 @@ struct JitShape {
   // total_tiles) is block × 16 rows instead of block × 4 — each wave takes one block of 1 024 rows as four sub-steps of 64 lanes × 4 rows
   // and reads the narrow slots of a full block with 16-byte loads, in the order the records' caches keep them (scan_cache_position).
   bool quad = false;
+  // fdb_plan_kernel: the per-record fields come from a packed table (jit_part_fields: W words per record), not from the array of 3 KB
+  // FdbScanArgs — a record switch reads W adjacent words, and the host ships those words only. The kernel takes
+  // `const unsigned long long* ptab` in the place of `parts` (jit_launch_ptab). Set by the launch (fdb_dense.cpp).
+  bool part_table = false;
   // fdb_select_kernel only (not part of key()): early slots whose values the kernel compacts itself, bit i = slot i of c4 / c8
   int fuse4 = 0, fuse8 = 0;
   // fdb_project_kernel only (not part of key()): root node of every computed field, in output order
@@ -136,6 +140,27 @@ hipError_t jit_project_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int 
                               unsigned long long* d_nulls, hipStream_t stream);
 
 std::string jit_source(const JitShape& shape);
+
+// The packed part table (JitShape::part_table). A shape's kernel reads a handful of values per record; jit_part_fields lists them, in
+// the order the record-entry emitter takes them, and BOTH the emitted reads and the host's packer walk that one list, so that field order
+// and words per record cannot drift apart. A 64-bit field owns a word; 32-bit fields share words in pairs, low half first, in list order.
+struct PartField {
+  enum What { TILE_END, TILE_BEGIN, N_ROWS, SLOT_VALUES, SLOT_VALIDITY, LEAF_LIT, LEAF_LUT, LEAF_LEN, LEAF_LDS, LEAF_OP, G_LUT, G_LDS, G_STRIDE, G_LEN, EXPR_LIT, LUT_CLASS };
+  What what;
+  int pool;    // SLOT_*: 0 c4, 1 c8, 2 l4, 3 l8
+  int index;   // slot, leaf, group column or expression node
+  int bits;    // 64 or 32
+  int word;    // where it sits in the record's W words …
+  int shift;   // … 0 or 32
+};
+std::vector<PartField> jit_part_fields(const JitShape& shape);
+int jit_part_words(const JitShape& shape);  // W
+int jit_part_words(const std::vector<PartField>& fields);
+const char* jit_part_field_name(PartField::What what);
+// `out`: n × W words, record k's at out + k × W; tile ranges and everything else as the argument blocks hold them at the call.
+void jit_pack_parts(const JitShape& shape, const FdbScanArgs* const* args, size_t n, unsigned long long* out);
+// … with the shape's list and W at hand (a launch makes the list once)
+void jit_pack_parts(const std::vector<PartField>& fields, int W, const FdbScanArgs* const* args, size_t n, unsigned long long* out);
 // The compiled kernel for `shape` (cached in the process and on disk), or nullptr if specialisation is unavailable.
 // While one of these with may_defer = true is alive on a thread, a jit_*get of a kernel that is not built yet may return nullptr at once
 // and leave the build to a background thread ($FDB_JIT_ASYNC=1 only): set by callers whose launch the interpreting kernels can serve.
@@ -155,5 +180,8 @@ hipFunction_t jit_get(const JitShape& shape);
 hipFunction_t jit_select(JitShape shape, size_t lds_bytes, int row_bytes, bool sorted_input, int* block_out, int* blocks_per_cu_out);
 hipError_t jit_launch(hipFunction_t fn, const FdbScanArgs* d_parts, int n_parts, int64_t total_tiles, const FdbScanArgs& common, int grid, int block,
                       size_t lds_bytes, hipStream_t stream);
+// A part_table kernel: `d_ptab` = the packed table (n_parts × W words, jit_pack_parts).
+hipError_t jit_launch_ptab(hipFunction_t fn, const unsigned long long* d_ptab, int n_parts, int64_t total_tiles, const FdbScanArgs& common, int grid, int block,
+                           size_t lds_bytes, hipStream_t stream);
 
 }  // namespace fdb

@@ -127,6 +127,14 @@ __device__ __forceinline__ u32x4 idx2x4(uint32_t lo, uint32_t hi) {
 }
 )HIP";
 
+// Part-table shapes only (JitShape::part_table). A word of the table, in scalar registers whichever load brought it: every lane reads the
+// same address, and what is decoded from the word — column pointers above all — must stay wave-uniform for the block loads to keep scalar bases.
+const char* kPartTablePreamble = R"HIP(
+__device__ __forceinline__ unsigned long long ptw(unsigned long long v) {
+  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+)HIP";
+
 // ---- code generation ---------------------------------------------------------------------------------------------------
 // C expression of node `ni` (typed: long long or double); `col(node)` gives the unsigned 64-bit raw value of a column node,
 // literals are the run-time variables K_elit<i>.
@@ -409,7 +417,32 @@ struct Gen {
     const char* var;  // the loop variable that counts the work units
     int block;        // threads per workgroup
     bool out_tile;    // the record's first output tile (out_tile_base) is read
+    bool ptab = false;  // fdb_plan_kernel of a part_table shape: the fields come from the packed table `ptab` (jit_part_fields), W words per record
   };
+  // where a field of the part table goes: the register of entry_decls it sets, and the cast from the word's bits
+  std::string part_target(const PartField& f, std::string* cast) const {
+    static const char* pools[4][2] = {{"4", "e"}, {"8", "e"}, {"4", "l"}, {"8", "l"}};
+    const std::string i = std::to_string(f.index);
+    switch (f.what) {
+      case PartField::TILE_END: *cast = "(long long)"; return "tile_end";
+      case PartField::TILE_BEGIN: *cast = "(long long)"; return "tile_begin";
+      case PartField::N_ROWS: *cast = "(long long)"; return "n_rows";
+      case PartField::SLOT_VALUES: *cast = "(const char*)"; return std::string("P_") + pools[f.pool][1] + pools[f.pool][0] + "_" + i + "_v";
+      case PartField::SLOT_VALIDITY: *cast = "(const uint8_t*)"; return std::string("P_") + pools[f.pool][1] + pools[f.pool][0] + "_" + i + "_b";
+      case PartField::LEAF_LIT: *cast = "(long long)"; return "K_lit" + i;
+      case PartField::LEAF_LUT: *cast = "(const uint8_t*)"; return "K_lut" + i;
+      case PartField::LEAF_LEN: *cast = "(uint32_t)"; return "K_len" + i;
+      case PartField::LEAF_LDS: *cast = "(uint32_t)"; return "K_lds" + i;
+      case PartField::LEAF_OP: *cast = "(int)(uint32_t)"; return "K_op" + i;
+      case PartField::G_LUT: *cast = "(const uint32_t*)"; return "G_lut" + i;
+      case PartField::G_LDS: *cast = "(uint32_t)"; return "G_lds" + i;
+      case PartField::G_STRIDE: *cast = "(uint32_t)"; return "G_stride" + i;
+      case PartField::G_LEN: *cast = "(uint32_t)"; return "G_len" + i;
+      case PartField::EXPR_LIT: *cast = "(long long)"; return "K_elit" + i;
+      case PartField::LUT_CLASS: *cast = "(int)(uint32_t)"; return "const int p_class";
+    }
+    return "";
+  }
   template <typename F> void each_slot(const Entry& e, F f) const {  // f(register, pool, index)
     for (bool late : {false, true}) {
       if (late && !e.late_pools) break;
@@ -430,6 +463,29 @@ struct Gen {
   // `luts`: the kernel's own assignments and LUTs, `leaving`: what it does about the record it leaves.
   void enter_record(const Entry& e, const std::function<void()>& per_record = nullptr, const std::function<void()>& luts = nullptr, const std::string& leaving = "") {
     o << "    if (part < 0 || " << e.var << " >= tile_end) {\n" << leaving;
+    if (e.ptab) {
+      // the walk over words W apart (40 records' ends share a few cache lines), then all W words of the record at once: no load waits for another
+      const std::vector<PartField> fields = jit_part_fields(s);
+      const int W = jit_part_words(fields);
+      o << "      int np = part < 0 ? 0 : part;\n      while (np + 1 < n_parts && " << e.var << " >= (long long)ptw(as_global(ptab)[(size_t)np * " << W << "])) np++;\n      part = np;\n";
+      o << "      const G1 unsigned long long* pw = as_global(ptab) + (size_t)part * " << W << ";\n";
+      for (int w = 0; w < W; w++) o << (w == 0 ? "      const unsigned long long " : ", ") << "w" << w << " = pw[" << w << "]";
+      o << ";\n";
+      for (int w = 0; w < W; w++) o << (w == 0 ? "      const unsigned long long " : ", ") << "s" << w << " = ptw(w" << w << ")";
+      o << ";\n";
+      for (const PartField& f : fields) {
+        std::string cast;
+        const std::string dst = part_target(f, &cast);
+        o << "      " << dst << " = " << cast << "(s" << f.word << (f.bits == 32 && f.shift ? " >> 32" : "") << ");\n";
+      }
+      o << "      if (p_class != lut_class) {\n        lut_class = p_class;\n        __syncthreads();\n";
+      for (size_t l = 0; l < s.leaves.size(); l++)
+        if (s.leaves[l].kind == FDB_LEAF_DICT_LUT && s.leaves[l].lut_in_lds)
+          o << "        for (uint32_t i = tid; i < K_len" << l << "; i += " << e.block << ") smem[K_lds" << l << " + i] = as_global(K_lut" << l << ")[i];\n";
+      if (luts) luts();
+      o << "        __syncthreads();\n      }\n    }\n";
+      return;
+    }
     o << "      int np = part < 0 ? 0 : part;\n      while (np + 1 < n_parts && " << e.var << " >= parts[np].tile_end) np++;\n      part = np;\n";
     o << "      const FdbScanArgs& pa = parts[part];\n      n_rows = pa.n_rows; tile_begin = pa.tile_begin; tile_end = pa.tile_end;" << (e.out_tile ? " out_tile = pa.out_tile_base;" : "") << "\n";
     each_slot(e, [&](const std::string& r, const char* pool, int i) {
@@ -450,10 +506,12 @@ struct Gen {
   // ---- fdb_plan_kernel -----------------------------------------------------------------------------------------------------------------
   std::string source() {
     const int BLK = s.block;
-    const Entry entry{true, "tile", BLK, false};
+    const Entry entry{true, "tile", BLK, false, s.part_table};
     o << "#include \"fdb_kernels.h\"\n" << kPreamble;
     if (s.quad) o << kQuadPreamble;
-    o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_plan_kernel(const FdbScanArgs* __restrict__ parts, const int n_parts, const long long total_tiles, const FdbScanArgs c) {\n";
+    if (s.part_table) o << kPartTablePreamble;
+    if (s.part_table) o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_plan_kernel(const unsigned long long* __restrict__ ptab, const int n_parts, const long long total_tiles, const FdbScanArgs c) {\n";
+    else o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_plan_kernel(const FdbScanArgs* __restrict__ parts, const int n_parts, const long long total_tiles, const FdbScanArgs c) {\n";
     o << "  extern __shared__ __align__(16) unsigned char smem[];\n  const uint32_t tid = threadIdx.x;\n  const uint32_t n_slots = c.n_slots;\n";
     o << "  if (c.fill_state != nullptr)  // (a fresh table: its identity fill rides on this launch, see FdbScanArgs)\n";
     o << "    for (uint32_t i = blockIdx.x * " << BLK << "u + tid; i < c.fill_words; i += gridDim.x * " << BLK << "u) c.fill_state[i] = c.fill_idents[i / c.fill_alloc];\n";
@@ -461,6 +519,7 @@ struct Gen {
     // per-record values, decoded when the workgroup enters a record
     entry_decls(entry, [&] {
       for (size_t g = 0; g < s.gcols.size(); g++) o << "  uint32_t G_lds" << g << " = 0, G_stride" << g << " = 0; const uint32_t* G_lut" << g << " = nullptr;\n";
+      if (s.part_table) for (size_t g = 0; g < s.gcols.size(); g++) if (s.gcols[g].lut_in_lds) o << "  uint32_t G_len" << g << " = 0;\n";
       for (size_t i = 0; i < s.exprs.size(); i++) if (s.exprs[i].kind == 1) o << "  long long K_elit" << i << " = 0;\n";
       for (int t = 0; t < s.reg_slots; t++) {  // the lane-private table
         o << "  unsigned long long R_cnt" << t << " = 0ull;\n";
@@ -483,7 +542,7 @@ struct Gen {
     }, [&] {
       for (size_t g = 0; g < s.gcols.size(); g++)
         if (s.gcols[g].lut_in_lds)
-          o << "        for (uint32_t i = tid; i < pa.gcols[" << g << "].lut_len; i += " << BLK << ") reinterpret_cast<uint32_t*>(smem + G_lds" << g << ")[i] = as_global(G_lut" << g << ")[i];\n";
+          o << "        for (uint32_t i = tid; i < " << (s.part_table ? "G_len" + std::to_string(g) : "pa.gcols[" + std::to_string(g) + "].lut_len") << "; i += " << BLK << ") reinterpret_cast<uint32_t*>(smem + G_lds" << g << ")[i] = as_global(G_lut" << g << ")[i];\n";
     });
     if (!s.quad) {
       tile_header("(tile - tile_begin) * " + std::to_string(BLK * 4) + "LL", "tid");
@@ -1518,7 +1577,7 @@ struct HashGen {
 
 std::string JitShape::key(bool with_validity) const {
   std::ostringstream k;
-  k << "b" << block << "l" << lds_acc << "c" << need_count << "t" << two_phase << "r" << reg_slots << "h" << cache << (wave_tables ? "w" : "") << (uniform_fold ? "u" : "") << (quad ? "q" : "") << "|";
+  k << "b" << block << "l" << lds_acc << "c" << need_count << "t" << two_phase << "r" << reg_slots << "h" << cache << (wave_tables ? "w" : "") << (uniform_fold ? "u" : "") << (quad ? "q" : "") << (part_table ? "p" : "") << "|";
   auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) { k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); if (p[i].width != 4) k << 'w' << p[i].width; } k << '|'; };
   slots(c4, n_c4); slots(c8, n_c8); slots(l4, n_l4); slots(l8, n_l8);
   for (const JitLeaf& L : leaves) k << L.kind << ',' << L.slot << ',' << L.wide << ',' << (L.kind >= FDB_LEAF_CMP_I64 && L.kind <= FDB_LEAF_CMP_I64_F64 ? L.op : 0) << ',' << L.lut_in_lds << ';';
@@ -1534,6 +1593,83 @@ std::string JitShape::key(bool with_validity) const {
 }
 
 std::string jit_source(const JitShape& shape) { return Gen(shape).source(); }
+
+// What fdb_plan_kernel's record entry takes per record for this shape, in its order: the tile range (tile_end first — the walk reads word 0),
+// every slot's pointers, what each leaf's kind reads (Gen::leaf_expr_of), the group columns, the expressions' literals, the LUT class.
+std::vector<PartField> jit_part_fields(const JitShape& s) {
+  std::vector<PartField> f;
+  auto add = [&](PartField::What what, int bits, int pool, int index) { f.push_back(PartField{what, pool, index, bits, 0, 0}); };
+  add(PartField::TILE_END, 64, 0, 0); add(PartField::TILE_BEGIN, 64, 0, 0); add(PartField::N_ROWS, 64, 0, 0);
+  const JitSlot* pools[4] = {s.c4, s.c8, s.l4, s.l8};
+  const int counts[4] = {s.n_c4, s.n_c8, s.n_l4, s.n_l8};
+  for (int p = 0; p < 4; p++)
+    for (int i = 0; i < counts[p]; i++) {
+      if (pools[p][i].has_values) add(PartField::SLOT_VALUES, 64, p, i);
+      if (pools[p][i].has_validity != 0) add(PartField::SLOT_VALIDITY, 64, p, i);
+    }
+  for (int l = 0; l < (int)s.leaves.size(); l++) {
+    const JitLeaf& L = s.leaves[(size_t)l];
+    if (L.kind == FDB_LEAF_CONST || L.kind == FDB_LEAF_VALIDITY) add(PartField::LEAF_OP, 32, 0, l);
+    else if (L.kind == FDB_LEAF_DICT_BITS) { add(PartField::LEAF_LIT, 64, 0, l); add(PartField::LEAF_LEN, 32, 0, l); }
+    else if (L.kind == FDB_LEAF_DICT_LUT) { add(PartField::LEAF_LUT, 64, 0, l); add(PartField::LEAF_LEN, 32, 0, l); if (L.lut_in_lds) add(PartField::LEAF_LDS, 32, 0, l); }
+    else add(PartField::LEAF_LIT, 64, 0, l);
+  }
+  for (int g = 0; g < (int)s.gcols.size(); g++) {
+    add(PartField::G_LUT, 64, 0, g); add(PartField::G_STRIDE, 32, 0, g);
+    if (s.gcols[(size_t)g].lut_in_lds) { add(PartField::G_LDS, 32, 0, g); add(PartField::G_LEN, 32, 0, g); }
+  }
+  for (int i = 0; i < (int)s.exprs.size(); i++) if (s.exprs[(size_t)i].kind == 1) add(PartField::EXPR_LIT, 64, 0, i);
+  add(PartField::LUT_CLASS, 32, 0, 0);
+  int words = 0, half = -1;  // `half`: a word whose high half is still free
+  for (PartField& x : f) {
+    if (x.bits == 64) { x.word = words++; x.shift = 0; }
+    else if (half >= 0) { x.word = half; x.shift = 32; half = -1; }
+    else { x.word = half = words++; x.shift = 0; }
+  }
+  return f;
+}
+int jit_part_words(const std::vector<PartField>& fields) {
+  int w = 0;
+  for (const PartField& x : fields) w = std::max(w, x.word + 1);
+  return w;
+}
+int jit_part_words(const JitShape& s) { return jit_part_words(jit_part_fields(s)); }
+const char* jit_part_field_name(PartField::What what) {
+  static const char* names[] = {"tile_end", "tile_begin", "n_rows", "values", "validity", "leaf.lit", "leaf.lut", "leaf.lut_len", "leaf.lut_lds", "leaf.op",
+                                "gcol.lut", "gcol.lut_lds", "gcol.stride", "gcol.lut_len", "expr.lit", "lut_class"};
+  return names[(int)what];
+}
+static unsigned long long part_field_value(const FdbScanArgs& a, const PartField& f) {
+  const FdbColSlot* pools[4] = {a.c4, a.c8, a.l4, a.l8};
+  switch (f.what) {
+    case PartField::TILE_END: return (unsigned long long)a.tile_end;
+    case PartField::TILE_BEGIN: return (unsigned long long)a.tile_begin;
+    case PartField::N_ROWS: return (unsigned long long)a.n_rows;
+    case PartField::SLOT_VALUES: return (unsigned long long)(uintptr_t)pools[f.pool][f.index].values;
+    case PartField::SLOT_VALIDITY: return (unsigned long long)(uintptr_t)pools[f.pool][f.index].validity;
+    case PartField::LEAF_LIT: return (unsigned long long)a.leaves[f.index].lit;
+    case PartField::LEAF_LUT: return (unsigned long long)(uintptr_t)a.leaves[f.index].lut;
+    case PartField::LEAF_LEN: return a.leaves[f.index].lut_len;
+    case PartField::LEAF_LDS: return a.leaves[f.index].lut_lds;
+    case PartField::LEAF_OP: return (uint32_t)a.leaves[f.index].op;
+    case PartField::G_LUT: return (unsigned long long)(uintptr_t)a.gcols[f.index].lut;
+    case PartField::G_LDS: return a.gcols[f.index].lut_lds;
+    case PartField::G_STRIDE: return a.gcols[f.index].stride;
+    case PartField::G_LEN: return a.gcols[f.index].lut_len;
+    case PartField::EXPR_LIT: return (unsigned long long)a.expr[f.index].lit;
+    case PartField::LUT_CLASS: return (uint32_t)a.lut_class;
+  }
+  return 0;
+}
+void jit_pack_parts(const JitShape& shape, const FdbScanArgs* const* args, size_t n, unsigned long long* out) {
+  const std::vector<PartField> fields = jit_part_fields(shape);
+  jit_pack_parts(fields, jit_part_words(fields), args, n, out);
+}
+void jit_pack_parts(const std::vector<PartField>& fields, int W, const FdbScanArgs* const* args, size_t n, unsigned long long* out) {
+  std::fill(out, out + n * (size_t)W, 0ull);
+  for (size_t k = 0; k < n; k++)
+    for (const PartField& f : fields) out[k * (size_t)W + (size_t)f.word] |= (f.bits == 32 ? part_field_value(*args[k], f) & 0xFFFFFFFFull : part_field_value(*args[k], f)) << f.shift;
+}
 
 JitShape jit_shape(const FdbScanArgs& a, bool two_phase, int block) {
   JitShape s;

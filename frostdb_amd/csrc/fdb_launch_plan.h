@@ -54,6 +54,17 @@ inline int64_t assign_tiles(FdbScanArgs* parts, size_t n, int64_t tile_rows) {
   return total_tiles;
 }
 
+// The same on the records' own argument blocks, in place (a launch that ships the packed part table makes no copy of them).
+inline int64_t assign_tiles(FdbScanArgs* const* parts, size_t n, int64_t tile_rows) {
+  int64_t total_tiles = 0;
+  for (size_t k = 0; k < n; k++) {
+    parts[k]->tile_begin = total_tiles;
+    total_tiles += (parts[k]->n_rows + tile_rows - 1) / tile_rows;
+    parts[k]->tile_end = total_tiles;
+  }
+  return total_tiles;
+}
+
 // How fdb_launch_reduce_partials folds each table array: [0] the row counts, [1 + j] aggregation j — 0 none (COUNT reads the counts), 1 integer
 // sum, 2 float64 sum, 3 min, 4 max. `func`: the aggregation's function in the argument block, `type`: the plan's accumulator type.
 struct FoldFuncs { int32_t f[1 + FDB_MAX_AGGS]; };

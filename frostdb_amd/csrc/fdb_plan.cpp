@@ -785,7 +785,8 @@ static std::shared_ptr<const Truth> cached_truth(Plan::Resolved* R, int node, co
 
 // Turns a truth table over dictionary column `ci` into a leaf: ≤ 64 answers ride in a 64-bit immediate (no LDS,
 // no memory access at all), larger tables become a byte LUT staged in LDS.
-static void emit_truth_leaf(const Truth& t, const DeviceBatch& b, int ci, Plan::Resolved* R, FdbLeaf* L) {
+static void emit_truth_leaf(const std::shared_ptr<const Truth>& tp, const DeviceBatch& b, int ci, Plan::Resolved* R, FdbLeaf* L) {
+  const Truth& t = *tp;
   const int li = (int)(L - R->args.leaves);
   const DevColumn& c = b.cols[(size_t)ci];
   L->values = c.d_values;
@@ -804,6 +805,7 @@ static void emit_truth_leaf(const Truth& t, const DeviceBatch& b, int ci, Plan::
   L->kind = FDB_LEAF_DICT_LUT;
   const size_t off = R->blob.add(t.data(), t.size());
   R->luts.push_back(PendingLut{0, li, off, t.size()});
+  R->lut_src.push_back(tp);
 }
 
 static void emit_filter(const std::vector<ExprNode>& nodes, int idx, const DeviceBatch& b, Plan::Resolved* R, int depth, int* max_depth) {
@@ -821,7 +823,7 @@ static void emit_filter(const std::vector<ExprNode>& nodes, int idx, const Devic
       L.lut_lds = FDB_NO_LDS;
       L.slot = -1;
       const std::shared_ptr<HostDict>& dict = b.cols[(size_t)col].dict;
-      emit_truth_leaf(*cached_truth(R, idx, dict, [&] { return subtree_truth(nodes, idx, *dict); }), b, col, R, &L);
+      emit_truth_leaf(cached_truth(R, idx, dict, [&] { return subtree_truth(nodes, idx, *dict); }), b, col, R, &L);
       a.code[a.n_code++] = (uint8_t)li;
       return;
     }
@@ -904,7 +906,7 @@ static void resolve_leaf(const ExprNode& e, const DeviceBatch& b, Plan::Resolved
       if (e.lit.type != FDB_LIT_STRING && e.lit.type != FDB_LIT_BINARY)
         throw Error(FDB_ERR_UNSUPPORTED, "unsupported binary operation (column/literal type combination) on " + c.name);
     }
-    emit_truth_leaf(*cached_truth(R, R->cur_node, c.dict, [&] { return leaf_truth(e, *c.dict); }), b, ci, R, L);
+    emit_truth_leaf(cached_truth(R, R->cur_node, c.dict, [&] { return leaf_truth(e, *c.dict); }), b, ci, R, L);
     return;
   }
   if (c.kind == ColKind::DICT) {
@@ -925,7 +927,7 @@ static void resolve_leaf(const ExprNode& e, const DeviceBatch& b, Plan::Resolved
       R->count(b, ci, /*values=*/false);  // the index buffer is not read by this leaf: only the bitmap counts
       return;
     }
-    emit_truth_leaf(*cached_truth(R, R->cur_node, c.dict, [&] { return leaf_truth(e, *c.dict); }), b, ci, R, L);
+    emit_truth_leaf(cached_truth(R, R->cur_node, c.dict, [&] { return leaf_truth(e, *c.dict); }), b, ci, R, L);
     return;
   }
   if (is_regex) throw Error(FDB_ERR_UNSUPPORTED, "ArrayScalarRegexMatch: unsupported type on the device path: " + c.format);
@@ -1082,6 +1084,8 @@ Plan::Knobs::Knobs() {
   max_key_bytes = mk != nullptr ? std::max<long long>(1, std::atoll(mk)) : 0x7FFFFFFFll;
   const char* fs = std::getenv("FDB_FINISH_SLICE_SHIFT");
   finish_slice_shift = fs != nullptr ? std::max(6, std::min(20, std::atoi(fs))) : 20;
+  const char* pc = std::getenv("FDB_PART_TABLE_CAP");
+  part_table_cap = pc != nullptr ? std::max<long long>(0, std::min<long long>(std::atoll(pc), 16384)) : 16384;
   // (a limb holds < 2^32 after a normalize and takes one digit < 2^32 per add: 2^31 − 1 adds keep it below 2^63)
   const char* en = std::getenv("FDB_TEST_EXACT_NORMALIZE_ROWS");
   exact_normalize_rows = en != nullptr ? std::max<long long>(1024, std::min<long long>(std::atoll(en), (1ll << 31) - (1ll << 24))) : (1ll << 31) - (1ll << 24);

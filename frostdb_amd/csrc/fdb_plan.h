@@ -388,6 +388,7 @@ class Plan {
     long long present_ids_min_bytes;  // index bytes a Finish must stand to save before it ranks the ids present ($FDB_PRESENT_IDS_MIN_BYTES), 32 MiB
     long long max_key_bytes;    // bytes one plain string / binary key column of ONE output record may hold ($FDB_TEST_MAX_KEY_BYTES; math.MaxInt32 like optbuilders.go:221-224)
     int finish_slice_shift;     // log2 of the rows per Finish slice ($FDB_FINISH_SLICE_SHIFT: tests reach several slices with a small result), 20
+    long long part_table_cap;   // bytes the packed part table of a dense quad launch may have ($FDB_PART_TABLE_CAP lowers it: tests reach the fallback with 3 records), 16 KiB
     long long exact_normalize_rows;  // adds a limb may take between two normalizes ($FDB_TEST_EXACT_NORMALIZE_ROWS: tests reach the normalize with few rows), 2^31 − 2^24
     Knobs();
   } knobs_;

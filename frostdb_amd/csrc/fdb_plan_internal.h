@@ -37,20 +37,22 @@ struct PhaseTimer {  // FDB_PROFILE=1: per-phase host microseconds on stderr (tu
 // builds that decide alike print alike. `shape_key`: JitShape::key(true) of a specialised kernel, empty otherwise. `folded`: per part
 // (empty: none) the slots that read a null-folded narrow-index cache without their bitmap, early slot k as bit k, late slot k as bit
 // 16 + k; such a slot's width is followed by `n`. A narrow slot without the mark whose shape has no bitmap is a column without NULLs.
-inline void print_dense_launch(const char* kernel, const std::string& shape_key, const FdbScanArgs* parts, size_t n_parts, int64_t total_tiles, int grid, int block,
+// `ptab_words`: words per record of the packed part table the kernel reads (JitShape::part_table), 0: it reads the argument blocks.
+inline void print_dense_launch(const char* kernel, const std::string& shape_key, const FdbScanArgs* const* parts, size_t n_parts, int64_t total_tiles, int grid, int block,
                                size_t lds_bytes, int two_phase, int lds_acc, int cache_slots, size_t lut_lds_max, int per_cu, int tile_rows, bool fill_rides, bool partials,
-                               const std::vector<uint32_t>& folded = std::vector<uint32_t>()) {
+                               const std::vector<uint32_t>& folded = std::vector<uint32_t>(), int ptab_words = 0) {
   std::string s;
   for (size_t p = 0; p < n_parts; p++) {
-    s += " " + std::to_string(parts[p].lut_class) + ":";
+    const FdbScanArgs& a = *parts[p];
+    s += " " + std::to_string(a.lut_class) + ":";
     const uint32_t f = p < folded.size() ? folded[p] : 0u;
-    for (int k = 0; k < parts[p].n_c4; k++) s += std::to_string((int)parts[p].w4[k]) + ((f >> k) & 1u ? "n" : "");
+    for (int k = 0; k < a.n_c4; k++) s += std::to_string((int)a.w4[k]) + ((f >> k) & 1u ? "n" : "");
     s += "/";
-    for (int k = 0; k < parts[p].n_l4; k++) s += std::to_string((int)parts[p].wl4[k]) + ((f >> (16 + k)) & 1u ? "n" : "");
+    for (int k = 0; k < a.n_l4; k++) s += std::to_string((int)a.wl4[k]) + ((f >> (16 + k)) & 1u ? "n" : "");
   }
   std::fprintf(stderr, "[fdb] dense launch %s shape=%s parts=%zu total_tiles=%lld grid=%d block=%d lds_bytes=%zu two_phase=%d lds_acc=%d cache_slots=%d lut_lds_max=%zu "
-               "per_cu=%d tile_rows=%d fill=%d partials=%d class:w4/wl4=%s\n", kernel, shape_key.empty() ? "-" : shape_key.c_str(), n_parts, (long long)total_tiles, grid, block,
-               lds_bytes, two_phase, lds_acc, cache_slots, lut_lds_max, per_cu, tile_rows, (int)fill_rides, (int)partials, s.c_str());
+               "per_cu=%d tile_rows=%d fill=%d partials=%d ptab=%d class:w4/wl4=%s\n", kernel, shape_key.empty() ? "-" : shape_key.c_str(), n_parts, (long long)total_tiles, grid, block,
+               lds_bytes, two_phase, lds_acc, cache_slots, lut_lds_max, per_cu, tile_rows, (int)fill_rides, (int)partials, ptab_words, s.c_str());
 }
 
 struct Blob {  // LUTs of one batch, shipped with one copy
@@ -108,6 +110,10 @@ struct Plan::Resolved {
   FdbScanArgs args;
   Blob blob;
   std::vector<PendingLut> luts;
+  // Where each entry of `luts` came from — the truth cache's table, a group column's key-id LUT — held for the length of the push, so that
+  // equal addresses mean one object: records whose LUTs have the same sources share a LUT set without a byte copied or compared.
+  std::vector<std::shared_ptr<const void>> lut_src;
+  int lut_like = -1;          // dense launch: the earlier record of the push whose LUT set this one shares (its own blob lacks the group LUTs then)
   std::vector<char> counted;  // per batch column: bit 0 values, bit 1 validity already counted in algorithmic bytes
   int64_t bytes = 0;
   int leaf_col[FDB_MAX_LEAVES];           // batch column behind each leaf (-1: constant leaf)
@@ -153,6 +159,8 @@ struct LutClasses {
   Blob blob;                      // one copy of each distinct set, 16-byte aligned
   std::vector<size_t> blob_base;  // [record] where its set starts in `blob`
   std::vector<int> cls;           // [record] class, numbered in first-seen order
+  // record `k` of the launch is known to carry the LUT set of the earlier record `like` (by the identity of its sources)
+  void add_like(size_t like) { blob_base.push_back(blob_base[like]); cls.push_back(cls[like]); }
   void add(const Plan::Resolved& R) {
     size_t found = 0;
     while (found < reps_.size() && !same_lut_set(*reps_[found].first, R)) found++;

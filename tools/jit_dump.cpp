@@ -100,9 +100,10 @@ static void replace_sum(std::vector<fdb::JitAgg>& aggs, fdb::JitAgg a, int root)
 int main(int argc0, char** argv0) {
   // keyword arguments, anywhere on the line: agg=<func><type>:<expression> (a computed aggregate input in the place of the shape's first SUM),
   // key=<expression> (hash modes: the last key column computed), nopred (flags / select: no predicate), fuse4 (select: the 4-byte slot fused too),
-  // nonull (plan: the dictionary slots without bitmaps)
+  // nonull (plan: the dictionary slots without bitmaps), ptab (plan: per-record fields from the packed part table, read from global memory; JitShape::part_table),
+  // cfg3 (plan two: bench.py's cfg 3 — three filter columns, `code` and `method` through truth tables, `instance` IS NOT NULL from its bitmap alone)
   std::string agg_arg, key_arg;
-  bool nopred = false, fuse4 = false, nonull = false;
+  bool nopred = false, fuse4 = false, nonull = false, ptab = false, cfg3 = false;
   std::vector<char*> pos;
   for (int i = 0; i < argc0; i++) {
     const std::string a = argv0[i];
@@ -111,6 +112,8 @@ int main(int argc0, char** argv0) {
     else if (i > 0 && a == "nopred") nopred = true;
     else if (i > 0 && a == "fuse4") fuse4 = true;
     else if (i > 0 && a == "nonull") nonull = true;
+    else if (i > 0 && a == "ptab") ptab = true;
+    else if (i > 0 && a == "cfg3") cfg3 = true;
     else pos.push_back(argv0[i]);
   }
   const int argc = (int)pos.size();
@@ -176,6 +179,15 @@ int main(int argc0, char** argv0) {
       (s.two_phase ? s.l4[0] : s.c4[1]).width = 2;
       s.quad = true;  // (what jit_shape sets for a launch with a narrow slot)
     }
+    if (cfg3 && s.two_phase) {  // plan two [narrow …] cfg3: two more early slots and leaves, AND-ed
+      s.n_c4 = 3;
+      s.c4[1].has_values = true; s.c4[1].has_validity = 1; s.c4[1].width = s.c4[0].width;
+      s.c4[2].has_values = false; s.c4[2].has_validity = 1;
+      fdb::JitLeaf b; b.kind = FDB_LEAF_DICT_BITS; b.slot = 1; b.wide = 0;
+      fdb::JitLeaf c; c.kind = FDB_LEAF_VALIDITY; c.slot = 2; c.wide = 0;
+      s.leaves = {a, b, c};
+      s.code = {0, 1, FDB_CODE_AND, 2, FDB_CODE_AND};
+    }
     if (argc > 4) s.block = std::atoi(argv[4]);  // plan <variant> narrow <threads per workgroup>
     if (argc > 5 && std::string(argv[5]) == "sum" && !s.two_phase) s.aggs.resize(1);  // plan <variant> narrow <threads> sum: SUM(float64) alone, bench.py's headline query
     if (nonull) {  // plan … nonull: no 4-byte slot has a bitmap — columns without NULLs, or null-folded caches (fdb_record.h), the headline's launch
@@ -183,6 +195,7 @@ int main(int argc0, char** argv0) {
       for (int i = 0; i < s.n_l4; i++) s.l4[i].has_validity = 0;
     }
     if (!agg_arg.empty()) { std::string spec; const fdb::JitAgg A = computed_agg(agg_arg, &spec); replace_sum(s.aggs, A, parse_into(s, spec).at(0)); }
+    s.part_table = ptab;
     std::fputs(fdb::jit_source(s).c_str(), stdout);
     return 0;
   }
