@@ -181,6 +181,26 @@ int fdb_selftest_scan_cache_nulls(const uint32_t* indices, const uint8_t* validi
   });
 }
 
+int fdb_selftest_scan_cache_packed(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t form, int device, uint8_t* out, int64_t out_bytes) {
+  return guard(nullptr, [&] {
+    const bool h = form == fdb::kScanFormH, t = form == fdb::kScanFormT;
+    if (indices == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || (!h && !t) || entries < 0 || entries + (validity != nullptr ? 1 : 0) > (h ? 16 : 4096) ||
+        out_bytes != (rows + 1023) / 1024 * fdb::scan_form_frame(form))
+      throw fdb::Error(FDB_ERR_INVALID, "packed scan cache: 1 to 2^28 rows, form H (5) or T (6), entries (+ 1 with a bitmap) <= 16 / 4 096, out_bytes = whole frames");
+    // the builder as scan_cache_get_packed runs it: a uint32 column (and its bitmap) in their slots, the cache in a slot of whole frames
+    fdb::CallScope call(device);
+    void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
+    uint8_t* d_bits = validity != nullptr ? (uint8_t*)call.alloc(fdb::bitmap_slot((size_t)rows)) : nullptr;
+    void* d_dst = call.alloc(fdb::packed_slot((size_t)rows, form));
+    fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), "packed scan cache: copy in");
+    if (validity != nullptr) fdb::hip_check(hipMemcpyAsync(d_bits, validity, (size_t)(rows + 7) / 8, hipMemcpyHostToDevice, call.ctx->stream), "packed scan cache: copy in");
+    fdb::hip_check(validity != nullptr ? fdb_launch_narrow_indices((const uint32_t*)d_src, d_bits, (uint32_t)entries, d_dst, rows, form, call.ctx->stream)
+                                       : fdb_launch_narrow_indices((const uint32_t*)d_src, d_dst, rows, form, call.ctx->stream), "packed scan cache: builder");
+    fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), "packed scan cache: copy out");
+    fdb::hip_check(hipStreamSynchronize(call.ctx->stream), "packed scan cache: wait");
+  });
+}
+
 int fdb_selftest_exact_sum(const double* x, int64_t n, double* out) {
   return guard(nullptr, [&] {
     if (n < 0 || out == nullptr || (n > 0 && x == nullptr)) throw fdb::Error(FDB_ERR_INVALID, "exact sum: n >= 0 and non-null buffers");

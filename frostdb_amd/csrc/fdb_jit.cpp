@@ -305,7 +305,11 @@ hipFunction_t jit_select(JitShape shape, size_t lds_bytes, int row_bytes, bool s
   // An ordered plan's input is sorted by its group columns: every wave takes the uniform fold, whose butterflies are a long dependent
   // chain behind each sub-step, and wants the third workgroup to load meanwhile (cfg 2 sorted: 0.197 ms per 100 M rows at 3 per CU,
   // 0.238 at 2).
-  if (shape.quad) waves = std::max(8, std::min(16, row_bytes > 0 ? (sorted_input ? 144 : 96) / row_bytes : 8));
+  // The packed index forms (fdb_record.h) take the headline's row from 11 to 10 B: unordered it stays at 2 per CU (3 again slower, 1.749
+  // against 1.605 ms per step in three pairs), but 144 / 10 would give the ordered plan 4 per CU, which loses what the saved byte wins
+  // (cfg 2 sorted at 10 B per row: 0.257 ms per step at 3 per CU, 0.271 at 4, every one of three pairs; profiles/packed_index_ab.json) —
+  // so an ordered quad launch takes at most 12 waves, 3 per CU, the one count measured best on both sides.
+  if (shape.quad) waves = std::max(8, std::min(sorted_input ? 12 : 16, row_bytes > 0 ? (sorted_input ? 144 : 96) / row_bytes : 8));
   const int block = shape.quad ? 256 : waves % 8 == 0 ? 512 : 256;
   shape.block = block;
   hipFunction_t fn = jit_get(shape);

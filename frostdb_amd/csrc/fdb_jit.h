@@ -20,6 +20,11 @@ struct JitGroup { int slot = -1; bool lut_in_lds = false; };
 struct JitAgg { int func = 0, type = 0, slot = -1; int expr = 0; };  // expr: 1 + root node of a computed input, 0 = stored column
 struct JitExprNode { int kind = 0, op = 0, left = -1, right = -1, slot = -1, type = 0; };  // literal values stay run-time arguments
 
+// JitSlot::width of a 4-byte slot read from a packed index cache (fdb_record.h: kScanFormH, 4 bits per index; kScanFormT, 12 bits as a
+// byte plane and a nibble plane), beside 1, 2 (bytes of the narrow-index cache) and 4 (the record's uint32 column).
+constexpr int kJitWidthH = 5, kJitWidthT = 6;
+inline bool jit_width_packed(int w) { return w == kJitWidthH || w == kJitWidthT; }
+
 // Everything that changes the generated CODE. Pointers, literals, truth-table bits, LUT offsets, strides and row counts
 // are run-time arguments and deliberately absent, so that queries of the same shape share one compiled kernel.
 struct JitShape {
@@ -63,11 +68,13 @@ struct JitShape {
   std::string key(bool with_validity = true) const;
   int row_bytes() const {  // bytes of column data a scan of this shape reads per row (slots with values, 4-byte slots at their width)
     int b = 0;
-    for (int k = 0; k < n_c4; k++) b += c4[k].has_values ? c4[k].width : 0;
-    for (int k = 0; k < n_l4; k++) b += l4[k].has_values ? l4[k].width : 0;
+    int packed_bits = 0;  // (the packed forms: whole bytes per row, rounded up over the shape's packed slots together)
+    auto w4 = [&](const JitSlot& c) { if (!c.has_values) return; if (jit_width_packed(c.width)) packed_bits += c.width == kJitWidthH ? 4 : 12; else b += c.width; };
+    for (int k = 0; k < n_c4; k++) w4(c4[k]);
+    for (int k = 0; k < n_l4; k++) w4(l4[k]);
     for (int k = 0; k < n_c8; k++) b += c8[k].has_values ? 8 : 0;
     for (int k = 0; k < n_l8; k++) b += l8[k].has_values ? 8 : 0;
-    return b;
+    return b + (packed_bits + 7) / 8;
   }
 };
 

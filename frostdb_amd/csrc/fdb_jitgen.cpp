@@ -127,6 +127,35 @@ __device__ __forceinline__ u32x4 idx2x4(uint32_t lo, uint32_t hi) {
 }
 )HIP";
 
+// Quad shapes with a packed slot only (JitSlot::width kJitWidthH / kJitWidthT; fdb_record.h, scan_cache_packed_position). A full block:
+// the lane's 16 nibbles are one 8-byte load, sub-step u bits 16 u … 16 u + 15 of it; form T's low bytes are one 16-byte load laid out as
+// the 1-byte cache. The record's last, partial block keeps its frame in row order: 2 bytes of nibbles (and 4 of low bytes) per lane and sub-step.
+const char* kPackedPreamble = R"HIP(
+__device__ __forceinline__ u32x2 ldblock8(const void* base, uint32_t byte_off) {
+#ifdef FDB_LD_TEMPORAL
+  return *as_global(reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(base) + byte_off));
+#else
+  return __builtin_nontemporal_load(as_global(reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(base) + byte_off)));
+#endif
+}
+__device__ __forceinline__ uint32_t ldnib4(const void* base, uint32_t byte_off) {
+#ifdef FDB_LD_TEMPORAL
+  return *as_global(reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(base) + byte_off));
+#else
+  return __builtin_nontemporal_load(as_global(reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(base) + byte_off)));
+#endif
+}
+__device__ __forceinline__ uint32_t nib_of(u32x2 n, int u) { return (u < 2 ? n.x : n.y) >> (16 * (u & 1)); }  // sub-step u's four nibbles in bits 0 … 15
+__device__ __forceinline__ u32x4 idxHx4(uint32_t h) {
+  u32x4 r; r.x = h & 0xFu; r.y = (h >> 4) & 0xFu; r.z = (h >> 8) & 0xFu; r.w = (h >> 12) & 0xFu;
+  return r;
+}
+__device__ __forceinline__ u32x4 idxTx4(uint32_t lo, uint32_t h) {
+  u32x4 r; r.x = (lo & 0xFFu) | ((h & 0xFu) << 8); r.y = ((lo >> 8) & 0xFFu) | ((h & 0xF0u) << 4); r.z = ((lo >> 16) & 0xFFu) | (h & 0xF00u); r.w = (lo >> 24) | ((h >> 4) & 0xF00u);
+  return r;
+}
+)HIP";
+
 // Part-table shapes only (JitShape::part_table). A word of the table, in scalar registers whichever load brought it: every lane reads the
 // same address, and what is decoded from the word — column pointers above all — must stay wave-uniform for the block loads to keep scalar bases.
 const char* kPartTablePreamble = R"HIP(
@@ -252,17 +281,25 @@ struct Gen {
   // Quad shapes (JitShape::quad), a wave whose 1 024-row block is full: every load that does not wait for `sel` has left before the first
   // sub-step is folded (block_loads), and the sub-step body takes its registers from there.
   bool full_block = false;
+  bool has_packed() const {
+    for (int i = 0; i < s.n_c4; i++) if (s.c4[i].has_values && jit_width_packed(s.c4[i].width)) return true;
+    for (int i = 0; i < s.n_l4; i++) if (s.l4[i].has_values && jit_width_packed(s.l4[i].width)) return true;
+    return false;
+  }
   void block_loads() {
     auto narrow = [&](const JitSlot& c, const std::string& r) {
-      if (!c.has_values || c.width >= 4) return;
-      if (c.width == 1) o << "      const u32x4 Q_" << r << " = ldblock(P_" << r << "_v + (size_t)wb, lane * 16u);\n";
+      if (!c.has_values || c.width == 4) return;
+      if (c.width == kJitWidthH) o << "      const u32x2 N_" << r << " = ldblock8(P_" << r << "_v + (size_t)(wb >> 1), lane * 8u);\n";
+      else if (c.width == kJitWidthT)
+        o << "      const u32x4 Q_" << r << " = ldblock(P_" << r << "_v + (size_t)(wb >> 10) * 1536, lane * 16u); const u32x2 N_" << r << " = ldblock8(P_" << r << "_v + (size_t)(wb >> 10) * 1536 + 1024, lane * 8u);\n";
+      else if (c.width == 1) o << "      const u32x4 Q_" << r << " = ldblock(P_" << r << "_v + (size_t)wb, lane * 16u);\n";
       else o << "      const u32x4 Q_" << r << "a = ldblock(P_" << r << "_v + (size_t)wb * 2, lane * 16u), Q_" << r << "b = ldblock(P_" << r << "_v + (size_t)wb * 2 + 1024, lane * 16u);\n";
     };
     for (int i = 0; i < s.n_c4; i++) narrow(s.c4[i], reg(false, false, i));
     for (int i = 0; i < s.n_l4; i++) narrow(s.l4[i], reg(false, true, i));
     for (int i = 0; i < s.n_c4; i++) {
       const std::string r = reg(false, false, i);
-      if (s.c4[i].has_values && s.c4[i].width >= 4) o << "      u32x4 A_" << r << "[4];\n";
+      if (s.c4[i].has_values && s.c4[i].width == 4) o << "      u32x4 A_" << r << "[4];\n";
       if (s.c4[i].has_validity != 0) o << "      uint32_t M_" << r << "[4];\n";
     }
     for (int i = 0; i < s.n_c8; i++) {
@@ -277,7 +314,7 @@ struct Gen {
     };
     for (int i = 0; i < s.n_c4; i++) {
       const std::string r = reg(false, false, i);
-      if (s.c4[i].has_values && s.c4[i].width >= 4) o << "        A_" << r << "[u] = ld4(P_" << r << "_v + o0 * 4, lane_off4);\n";
+      if (s.c4[i].has_values && s.c4[i].width == 4) o << "        A_" << r << "[u] = ld4(P_" << r << "_v + o0 * 4, lane_off4);\n";
       valid(s.c4[i], r);
     }
     for (int i = 0; i < s.n_c8; i++) {
@@ -294,7 +331,7 @@ struct Gen {
     auto use = [&](const std::string& v) { keep += (keep.empty() ? "\"v\"(" : ", \"v\"(") + v + ")"; };
     for (int i = 0; i < s.n_c4; i++) {
       const std::string r = reg(false, false, i);
-      if (s.c4[i].has_values && s.c4[i].width >= 4) use("A_" + r + "[0]");
+      if (s.c4[i].has_values && s.c4[i].width == 4) use("A_" + r + "[0]");
       if (s.c4[i].has_validity != 0) use("M_" + r + "[0]");
     }
     for (int i = 0; i < s.n_c8; i++) {
@@ -310,7 +347,12 @@ struct Gen {
     for (int i = 0; i < n4; i++) {
       const JitSlot& c = late ? s.l4[i] : s.c4[i];
       const std::string r = reg(false, late, i);
-      if (full_block && c.has_values && c.width == 1) o << "    const u32x4 " << r << " = idx1x4(dword_of(Q_" << r << ", u));\n";
+      if (full_block && c.has_values && c.width == kJitWidthH) o << "    const u32x4 " << r << " = idxHx4(nib_of(N_" << r << ", u));\n";
+      else if (full_block && c.has_values && c.width == kJitWidthT) o << "    const u32x4 " << r << " = idxTx4(dword_of(Q_" << r << ", u), nib_of(N_" << r << ", u));\n";
+      else if (c.has_values && c.width == kJitWidthH) o << "    const u32x4 " << r << " = idxHx4(ldnib4(P_" << r << "_v + (size_t)(r0 >> 10) * 512 + (size_t)(r0 & 1023) / 2, lane * 2u));\n";
+      else if (c.has_values && c.width == kJitWidthT)
+        o << "    const u32x4 " << r << " = idxTx4(ld1raw(P_" << r << "_v + (size_t)(r0 >> 10) * 1536 + (size_t)(r0 & 1023), lane_off1), ldnib4(P_" << r << "_v + (size_t)(r0 >> 10) * 1536 + 1024 + (size_t)(r0 & 1023) / 2, lane * 2u));\n";
+      else if (full_block && c.has_values && c.width == 1) o << "    const u32x4 " << r << " = idx1x4(dword_of(Q_" << r << ", u));\n";
       else if (full_block && c.has_values && c.width == 2)
         o << "    const u32x4 " << r << " = idx2x4(dword_of(u < 2 ? Q_" << r << "a : Q_" << r << "b, 2 * (u & 1)), dword_of(u < 2 ? Q_" << r << "a : Q_" << r << "b, 2 * (u & 1) + 1));\n";
       else if (full_block && !late && c.has_values) o << "    const u32x4 " << r << " = A_" << r << "[u];\n";
@@ -509,6 +551,7 @@ struct Gen {
     const Entry entry{true, "tile", BLK, false, s.part_table};
     o << "#include \"fdb_kernels.h\"\n" << kPreamble;
     if (s.quad) o << kQuadPreamble;
+    if (has_packed()) o << kPackedPreamble;
     if (s.part_table) o << kPartTablePreamble;
     if (s.part_table) o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_plan_kernel(const unsigned long long* __restrict__ ptab, const int n_parts, const long long total_tiles, const FdbScanArgs c) {\n";
     else o << "extern \"C\" __global__ __launch_bounds__(" << BLK << ") void fdb_plan_kernel(const FdbScanArgs* __restrict__ parts, const int n_parts, const long long total_tiles, const FdbScanArgs c) {\n";
@@ -1578,7 +1621,7 @@ struct HashGen {
 std::string JitShape::key(bool with_validity) const {
   std::ostringstream k;
   k << "b" << block << "l" << lds_acc << "c" << need_count << "t" << two_phase << "r" << reg_slots << "h" << cache << (wave_tables ? "w" : "") << (uniform_fold ? "u" : "") << (quad ? "q" : "") << (part_table ? "p" : "") << "|";
-  auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) { k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); if (p[i].width != 4) k << 'w' << p[i].width; } k << '|'; };
+  auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) { k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); if (jit_width_packed(p[i].width)) k << 'w' << (p[i].width == kJitWidthH ? 'H' : 'T'); else if (p[i].width != 4) k << 'w' << p[i].width; } k << '|'; };
   slots(c4, n_c4); slots(c8, n_c8); slots(l4, n_l4); slots(l8, n_l8);
   for (const JitLeaf& L : leaves) k << L.kind << ',' << L.slot << ',' << L.wide << ',' << (L.kind >= FDB_LEAF_CMP_I64 && L.kind <= FDB_LEAF_CMP_I64_F64 ? L.op : 0) << ',' << L.lut_in_lds << ';';
   k << '|';
@@ -1683,10 +1726,10 @@ JitShape jit_shape(const FdbScanArgs& a, bool two_phase, int block) {
     for (int i = 0; i < n; i++) { dst[i].has_values = src[i].values != nullptr; dst[i].has_validity = src[i].validity != nullptr ? 1 : 0; }
   };
   slots(s.c4, a.c4, s.n_c4); slots(s.c8, a.c8, s.n_c8); slots(s.l4, a.l4, s.n_l4); slots(s.l8, a.l8, s.n_l8);
-  for (int i = 0; i < s.n_c4; i++) s.c4[i].width = a.w4[i] == 1 || a.w4[i] == 2 ? a.w4[i] : 4;
-  for (int i = 0; i < s.n_l4; i++) s.l4[i].width = a.wl4[i] == 1 || a.wl4[i] == 2 ? a.wl4[i] : 4;
-  for (int i = 0; i < s.n_c4; i++) s.quad |= s.c4[i].has_values && s.c4[i].width < 4;
-  for (int i = 0; i < s.n_l4; i++) s.quad |= s.l4[i].has_values && s.l4[i].width < 4;
+  for (int i = 0; i < s.n_c4; i++) s.c4[i].width = a.w4[i] == 1 || a.w4[i] == 2 || jit_width_packed(a.w4[i]) ? a.w4[i] : 4;
+  for (int i = 0; i < s.n_l4; i++) s.l4[i].width = a.wl4[i] == 1 || a.wl4[i] == 2 || jit_width_packed(a.wl4[i]) ? a.wl4[i] : 4;
+  for (int i = 0; i < s.n_c4; i++) s.quad |= s.c4[i].has_values && s.c4[i].width != 4;
+  for (int i = 0; i < s.n_l4; i++) s.quad |= s.l4[i].has_values && s.l4[i].width != 4;
   for (int l = 0; l < a.n_leaves; l++) {
     const FdbLeaf& L = a.leaves[l];
     s.leaves.push_back({L.kind, L.slot, L.wide, L.op, L.kind == FDB_LEAF_DICT_LUT && L.lut_lds != FDB_NO_LDS});

@@ -135,6 +135,7 @@ struct FdbScanArgs {
   int32_t lut_class;        // records with the same class carry byte-identical LUT sets at the same LDS offsets
   // fdb_plan_kernel only: bytes per index that c4[k] / l4[k].values holds — 0 (what every other builder of these blocks leaves) or 4: the
   // record's own uint32 column; 1 / 2: the record's narrow-index cache (fdb_record.h, ScanCache), the same width in every part of a launch.
+  // 5 / 6: its packed forms, 4 bits per index (H) and 12 bits as a byte plane and a nibble plane (T; fdb_record.h, kScanFormH / kScanFormT).
   // A launch with such a slot is a quad launch (fdb_jit.h, JitShape::quad): tile_begin / tile_end count units of block × 16 rows.
   uint8_t w4[FDB_ARG_C4];
   uint8_t wl4[FDB_ARG_L4];

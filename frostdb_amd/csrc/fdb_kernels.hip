@@ -2346,9 +2346,69 @@ __global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __rest
 }  // namespace
 
 namespace {
+// The packed forms of that cache (fdb_record.h, scan_cache_packed_position): frames of 512 B (H: 4 bits per index) or 1 024 + 512 B (T: the
+// low bytes laid out as the 1-byte form, then the high nibbles laid out as H) per 1 024-row block. One 16-byte store per thread: vector t < 64
+// of T's byte plane is lane t's rows of the four sub-steps (4 source vectors, 64 apart), vector t of a nibble plane holds lanes 2 t and
+// 2 t + 1 (8 source vectors: the k-th is lane 2 t + k / 4, sub-step k % 4); in the record's last, partial block both hold consecutive rows.
+// Either way element q of the k-th source vector lands at element 4 k + q of the output. A thread loads all its source vectors and their
+// validity nibbles before the first is looked at; a source vector that begins at or past `rows` is not loaded (a frame runs up to 1 023
+// rows past the record, beyond any pad), and rows past the end are written as 0.
+template <bool T12, bool FOLD>
+__global__ __launch_bounds__(256) void pack_indices_kernel(const u32x4* __restrict__ src, const uint8_t* __restrict__ validity, uint32_t null_index, unsigned char* __restrict__ dst,
+                                                           int64_t rows, int64_t n_vec) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_vec) return;
+  constexpr int64_t VB = T12 ? 96 : 32, FRAME = T12 ? 1536 : 512;  // output vectors and bytes per block
+  const int64_t blk = i / VB;
+  int t = (int)(i % VB);
+  const bool bytes = T12 && t < 64;  // a vector of the byte plane
+  if (T12 && !bytes) t -= 64;
+  const bool interleaved = (blk + 1) * fdb::kScanCacheBlock <= rows;
+  const int nv = bytes ? 4 : 8;
+  u32x4 in[8];
+  uint32_t valid[8];
+  int have[8];  // rows of the k-th source vector that exist: 0 … 4
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int64_t v = blk * 256 + (bytes ? (interleaved ? 64 * k + t : 4 * t + k) : (interleaved ? 64 * (k & 3) + 2 * t + (k >> 2) : 8 * t + k));
+    const int64_t left = rows - v * 4;
+    have[k] = k < nv && left > 0 ? (left < 4 ? (int)left : 4) : 0;
+    in[k] = u32x4{0u, 0u, 0u, 0u};
+    valid[k] = 0xFu;
+    if (have[k] > 0) {
+      in[k] = __builtin_nontemporal_load(as_global(src + v));
+      if (FOLD) valid[k] = (uint32_t)validity[v >> 1] >> (4 * (int)(v & 1));
+    }
+  }
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const uint32_t e[4] = {in[k].x, in[k].y, in[k].z, in[k].w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const uint32_t idx = q >= have[k] ? 0u : (valid[k] >> q) & 1u ? (e[q] & (T12 ? 0xFFFu : 0xFu)) : null_index;
+      const int r = 4 * k + q;  // element of the thread's vector
+      if (bytes) { if (k < 4) w[r / 4] |= (idx & 0xFFu) << (8 * (r % 4)); }
+      else w[r / 8] |= ((T12 ? idx >> 8 : idx) & 0xFu) << (4 * (r % 8));
+    }
+  }
+  u32x4 out; out.x = w[0]; out.y = w[1]; out.z = w[2]; out.w = w[3];
+  *reinterpret_cast<u32x4*>(dst + blk * FRAME + (T12 && !bytes ? 1024 : 0) + 16 * t) = out;
+}
+}  // namespace
+
+namespace {
 template <bool FOLD>
 hipError_t launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream) {
   if (rows <= 0) return hipSuccess;
+  if (fdb::scan_form_packed(width)) {
+    const bool t12 = width == fdb::kScanFormT;
+    const int64_t n_vec = (rows + fdb::kScanCacheBlock - 1) / fdb::kScanCacheBlock * (t12 ? 96 : 32);
+    const unsigned grid = (unsigned)((n_vec + 255) / 256);
+    if (t12) hipLaunchKernelGGL((pack_indices_kernel<true, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<unsigned char*>(dst), rows, n_vec);
+    else hipLaunchKernelGGL((pack_indices_kernel<false, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<unsigned char*>(dst), rows, n_vec);
+    return hipGetLastError();
+  }
   if (width != 1 && width != 2) return hipErrorInvalidValue;
   const int64_t per = 16 / width, n_vec = (rows + per - 1) / per;
   const unsigned grid = (unsigned)((n_vec + 255) / 256);
@@ -2363,7 +2423,7 @@ hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t row
 }
 
 hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream) {
-  if (validity == nullptr || null_index > (width == 1 ? 0xFFu : 0xFFFFu)) return hipErrorInvalidValue;
+  if (validity == nullptr || null_index > (width == fdb::kScanFormH ? 0xFu : width == fdb::kScanFormT ? 0xFFFu : width == 1 ? 0xFFu : 0xFFFFu)) return hipErrorInvalidValue;
   return launch_narrow_indices<true>(src, validity, null_index, dst, rows, width, stream);
 }
 

@@ -36,19 +36,20 @@ struct PhaseTimer {  // FDB_PROFILE=1: per-phase host microseconds on stderr (tu
 // FDB_PROFILE=1: one line per dense scan launch with every decision behind it (tuning aid) — no pointers and no times, so that two
 // builds that decide alike print alike. `shape_key`: JitShape::key(true) of a specialised kernel, empty otherwise. `folded`: per part
 // (empty: none) the slots that read a null-folded narrow-index cache without their bitmap, early slot k as bit k, late slot k as bit
-// 16 + k; such a slot's width is followed by `n`. A narrow slot without the mark whose shape has no bitmap is a column without NULLs.
+// 16 + k; such a slot's width (H / T: the packed forms of 4 / 12 bits) is followed by `n`. A narrow slot without the mark whose shape has no bitmap is a column without NULLs.
 // `ptab_words`: words per record of the packed part table the kernel reads (JitShape::part_table), 0: it reads the argument blocks.
 inline void print_dense_launch(const char* kernel, const std::string& shape_key, const FdbScanArgs* const* parts, size_t n_parts, int64_t total_tiles, int grid, int block,
                                size_t lds_bytes, int two_phase, int lds_acc, int cache_slots, size_t lut_lds_max, int per_cu, int tile_rows, bool fill_rides, bool partials,
                                const std::vector<uint32_t>& folded = std::vector<uint32_t>(), int ptab_words = 0) {
   std::string s;
+  auto form = [](int w) { return w == 5 ? std::string("H") : w == 6 ? std::string("T") : std::to_string(w); };  // (fdb_record.h: kScanFormH, kScanFormT)
   for (size_t p = 0; p < n_parts; p++) {
     const FdbScanArgs& a = *parts[p];
     s += " " + std::to_string(a.lut_class) + ":";
     const uint32_t f = p < folded.size() ? folded[p] : 0u;
-    for (int k = 0; k < a.n_c4; k++) s += std::to_string((int)a.w4[k]) + ((f >> k) & 1u ? "n" : "");
+    for (int k = 0; k < a.n_c4; k++) s += form((int)a.w4[k]) + ((f >> k) & 1u ? "n" : "");
     s += "/";
-    for (int k = 0; k < a.n_l4; k++) s += std::to_string((int)a.wl4[k]) + ((f >> (16 + k)) & 1u ? "n" : "");
+    for (int k = 0; k < a.n_l4; k++) s += form((int)a.wl4[k]) + ((f >> (16 + k)) & 1u ? "n" : "");
   }
   std::fprintf(stderr, "[fdb] dense launch %s shape=%s parts=%zu total_tiles=%lld grid=%d block=%d lds_bytes=%zu two_phase=%d lds_acc=%d cache_slots=%d lut_lds_max=%zu "
                "per_cu=%d tile_rows=%d fill=%d partials=%d ptab=%d class:w4/wl4=%s\n", kernel, shape_key.empty() ? "-" : shape_key.c_str(), n_parts, (long long)total_tiles, grid, block,

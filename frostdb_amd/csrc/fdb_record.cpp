@@ -37,15 +37,20 @@ bool scan_cache_folded(const DeviceBatch& b, size_t c) {
   return col.d_validity != nullptr && scan_cache_folds(col.dict->values.size(), col.null_count, b.rows);
 }
 
-const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
-  const int width = scan_cache_width(b, c);
-  if (width >= 4) throw Error(FDB_ERR_INVALID, "internal: no narrow-index cache for column " + b.cols[c].name);
+int scan_cache_packed(const DeviceBatch& b, size_t c) {
+  if (scan_cache_width(b, c) >= 4) return 0;  // (transient, below the byte forms' threshold, no dictionary column, or a dictionary too large for any form)
+  const DevColumn& col = b.cols[c];
+  return scan_cache_packed_of(col.dict->values.size(), col.d_validity != nullptr ? col.null_count : 0, b.rows);
+}
+
+static const void* scan_cache_build(const DeviceBatch& b, size_t c, int width, hipStream_t stream) {
+  const bool packed = scan_form_packed(width);
   std::lock_guard<std::mutex> lk(b.scan_cache_mu);
   ScanCache& sc = b.scan_cache;
-  if (sc.cols.empty()) sc.cols.resize(b.cols.size());
-  ScanCache::Col& e = sc.cols[c];
+  if (sc.cols.empty()) sc.cols.resize(2 * b.cols.size());
+  ScanCache::Col& e = sc.cols[2 * c + (packed ? 1 : 0)];
   if (e.d != nullptr) return e.d;
-  const size_t bytes = values_slot((size_t)b.rows, (size_t)width);
+  const size_t bytes = packed ? packed_slot((size_t)b.rows, width) : values_slot((size_t)b.rows, (size_t)width);
   void* d = device_pool_alloc(b.device, bytes);
   const bool folded = scan_cache_folded(b, c);
   hipError_t err = folded ? fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, b.cols[c].d_validity, (uint32_t)b.cols[c].dict->values.size(), d, b.rows, width, stream)
@@ -55,6 +60,18 @@ const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
   e.d = d; e.width = width; e.bytes = bytes; e.folded = folded;
   sc.bytes += (int64_t)bytes;
   return d;
+}
+
+const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
+  const int width = scan_cache_width(b, c);
+  if (width >= 4) throw Error(FDB_ERR_INVALID, "internal: no narrow-index cache for column " + b.cols[c].name);
+  return scan_cache_build(b, c, width, stream);
+}
+
+const void* scan_cache_get_packed(const DeviceBatch& b, size_t c, hipStream_t stream) {
+  const int form = scan_cache_packed(b, c);
+  if (form == 0) throw Error(FDB_ERR_INVALID, "internal: no packed index cache for column " + b.cols[c].name);
+  return scan_cache_build(b, c, form, stream);
 }
 
 void require_values(const DeviceBatch& in, const char* what) {

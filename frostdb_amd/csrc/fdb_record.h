@@ -62,6 +62,43 @@ inline bool scan_cache_folds(size_t entries, int64_t nulls, int64_t rows) {
   return nulls > 0 && w < 4 && entries < ((size_t)1 << (8 * w));
 }
 
+// ---- the packed forms: 4 and 12 bits per index ----------------------------------------------------------------------------------------
+// Form H holds an index in 4 bits (a column whose entries plus one NULL value number at most 16), form T in 12 (at most 4 096) as two
+// planes: the low byte of every index, laid out exactly as the 1-byte form, and the high nibble, laid out as form H. Unpacking T is
+// lo | hi << 8: no bit field crosses a word. A buffer is a run of whole frames, one per 1 024-row block: 512 B for H; for T 1 024 B of
+// bytes, then 512 B of nibbles. In a full block lane l's 16 nibbles (rows 256 u + 4 l + r, nibble 4 u + r, low nibble first) are the 8
+// bytes at 8 l of the nibble plane, so sub-step u is bits 16 u … 16 u + 15 of the lane's 64-bit word. The record's last, partial block
+// keeps the same frame in row order: row j of the block at byte j and nibble j, zeros behind the last row to the frame's end.
+// A packed buffer of a column with NULLs is always null-folded (the rule below leaves S = entries room), so it needs no bitmap.
+constexpr int kScanFormH = 5, kScanFormT = 6;  // as JitSlot::width / FdbScanArgs::w4 carry them, beside the byte widths 1, 2 and 4
+constexpr int64_t kScanCachePackedMinRows = (int64_t)4 << 20;  // below it the 1 B a row the packed forms save on top of the byte forms is under a microsecond of a scan
+inline bool scan_form_packed(int form) { return form == kScanFormH || form == kScanFormT; }
+inline int scan_form_bits(int form) { return form == kScanFormH ? 4 : form == kScanFormT ? 12 : form == 1 ? 8 : form == 2 ? 16 : 32; }
+inline int64_t scan_form_frame(int form) { return form == kScanFormH ? 512 : 1536; }  // bytes of a packed form's frame
+inline size_t packed_slot(size_t rows, int form) { return align_up((rows + 1023) / 1024 * (size_t)scan_form_frame(form) + kTailPad, 256); }
+// Bytes a scan of `rows` rows reads of an index column at `form` (any of the five): the algorithmic bytes of that slot.
+inline int64_t scan_form_bytes(int64_t rows, int form) { return (rows * scan_form_bits(form) + 7) / 8; }
+// The width rule. H where entries + (nulls > 0) ≤ 16; else nothing where the 1-byte form applies; else T where entries + (nulls > 0)
+// ≤ 4 096; else nothing. 0: the column gets no packed buffer (it may get a byte one: scan_cache_width_of). A column of exactly 16 or
+// 4 096 entries with NULLs falls to the byte forms, which fold it.
+inline int scan_cache_packed_of(size_t entries, int64_t nulls, int64_t rows) {
+  if (rows < kScanCachePackedMinRows) return 0;
+  const size_t need = entries + (nulls > 0 ? 1 : 0);
+  return need <= 16 ? kScanFormH : entries <= 256 ? 0 : need <= 4096 ? kScanFormT : 0;
+}
+// Where row `i` of a packed buffer of `rows` rows sits: the byte of its low 8 bits (T; −1 for H) and the byte and shift of its nibble.
+struct PackedAt { int64_t byte; int64_t nibble_byte; int nibble_shift; };
+FDB_RECORD_HD inline PackedAt scan_cache_packed_position(int64_t i, int64_t rows, int form) {
+  const int64_t frame = form == kScanFormH ? 512 : 1536, plane = form == kScanFormH ? 0 : 1024;
+  const int64_t b = i / kScanCacheBlock, j = i % kScanCacheBlock, u = j / 256, l = (j % 256) / 4, r = j % 4;
+  const int64_t e = i >= rows / kScanCacheBlock * kScanCacheBlock ? j : 16 * l + 4 * u + r;  // element of the block: byte e, nibble e
+  PackedAt at;
+  at.byte = form == kScanFormH ? -1 : b * frame + e;
+  at.nibble_byte = b * frame + plane + e / 2;
+  at.nibble_shift = (int)(e % 2) * 4;
+  return at;
+}
+
 // Offsets of the slots of one record, in column order: [values | bitmap] per column.
 struct RecordLayout {
   struct Col { size_t val_off, bit_off; };  // bit_off == kNoSlot: no bitmap slot
@@ -144,18 +181,23 @@ struct CallScope {
 // of such a column loads no bitmap. A buffer that is not folded holds the truncated uint32 of every row, a NULL row's included.
 struct ScanCache {
   struct Col { void* d = nullptr; int width = 0; size_t bytes = 0; bool folded = false; };
-  std::vector<Col> cols;  // by column of the record; empty until the first buffer
-  int64_t bytes = 0;      // Σ values_slot(rows, width) of the buffers
+  std::vector<Col> cols;  // column c's byte form at 2 c, its packed form (kScanFormH / kScanFormT in `width`) at 2 c + 1; empty until the first buffer
+  int64_t bytes = 0;      // Σ values_slot(rows, width) / packed_slot(rows, form) of the buffers
 };
 // Width at which a dense generated scan may read column `c` of `b` — 1, 2, or 4 when the column gets no buffer: no dictionary column,
 // a dictionary too large, a record below kScanCacheMinRows or a transient one (a host record is scanned once). Builds nothing.
 int scan_cache_width(const DeviceBatch& b, size_t c);
+// The packed form a dense generated scan may read column `c` at — kScanFormH, kScanFormT, or 0: none (scan_cache_packed_of; never for a
+// transient record). A record scanned in different company may come to hold both forms of a column; both are counted and freed with it.
+int scan_cache_packed(const DeviceBatch& b, size_t c);
 // Whether that buffer is (or, once built, will be) null-folded: scan_cache_folds of the column's dictionary, NULL count and rows. Builds nothing.
 bool scan_cache_folded(const DeviceBatch& b, size_t c);
 // The buffer of column `c` (scan_cache_width(b, c) < 4), built on `stream` if it is not there yet. Two plans on two threads and two
 // streams may meet the same fresh record: the record's mutex is held from the look-up to the publication, and a buffer is published
 // only after the stream that built it has been synchronised — exactly one survives and nobody reads it early.
 const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream);
+// The same for the column's packed buffer (scan_cache_packed(b, c) != 0).
+const void* scan_cache_get_packed(const DeviceBatch& b, size_t c, hipStream_t stream);
 
 // FDB_ERR_UNSUPPORTED, naming `what`, if a column of `in` (rows > 0) is of a type the resident record cannot hold.
 void require_values(const DeviceBatch& in, const char* what);

@@ -111,6 +111,7 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_widen.argtypes = [vp, i32, vp, i64]
     L.fdb_selftest_scan_cache.argtypes = [vp, i64, i32, ctypes.c_int, vp, i64]
     L.fdb_selftest_scan_cache_nulls.argtypes = [vp, vp, i64, i64, i32, ctypes.c_int, vp, i64]
+    L.fdb_selftest_scan_cache_packed.argtypes = [vp, vp, i64, i64, i32, ctypes.c_int, vp, i64]
     L.fdb_plan_explain.argtypes = [vp, ctypes.c_char_p, i64, P(i64)]
     L.fdb_plan_last_kernel.restype = ctypes.c_char_p
     L.fdb_comm_unique_id.argtypes = [vp]

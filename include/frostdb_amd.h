@@ -254,6 +254,11 @@ FDB_API int fdb_selftest_scan_cache(const uint32_t* indices, int64_t rows, int32
  * the buffer holds `entries` under every NULL row, whatever `indices` holds there. `out` as above; nothing is checked beyond the arguments. */
 FDB_API int fdb_selftest_scan_cache_nulls(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t width, int device, uint8_t* out,
                                           int64_t out_bytes);
+/* … of its packed forms (4 bits per index: form 5, 12 bits: form 6; frostdb_amd/csrc/fdb_record.h): builds the buffer of `rows` rows
+ * for a dictionary of `entries` entries exactly as a dense scan's first launch would — null-folded (`entries` under every row whose bit
+ * of `validity` is clear) when `validity` is given — and copies its whole frames, ceil(rows / 1024) x 512 or 1 536 bytes, to `out`. */
+FDB_API int fdb_selftest_scan_cache_packed(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t form, int device, uint8_t* out,
+                                           int64_t out_bytes);
 
 /* ---- plan life cycle (≙ physicalplan.Build for one chain, physicalplan.go:417-474) -------------- */
 /* `desc` and everything it points at (expression nodes, names, literals, patterns) is copied: the caller may free it as soon

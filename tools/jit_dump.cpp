@@ -149,6 +149,7 @@ int main(int argc0, char** argv0) {
     // the dense scan kernel of a cfg 2-like shape (`labels.code == X` + SUM(float64) [+ MIN / COUNT] GROUP BY labels.path):
     //   plan [variant] [narrow [threads]]   narrow: the dictionary slots read from narrow-index caches (1-byte filter column, 2-byte group column),
     //                                       the quad shape of such a launch; threads: per workgroup (256 / 512 / 1024)
+    //   plan [variant] packed [threads]     the same with the slots read from packed index caches: the filter column at 4 bits, the group column at 12
     //   plan [variant] narrow threads sum   the same with SUM(float64) as the only aggregate: the shape bench.py's headline runs
     //   plan … agg=sumf:ci0n,ci1n,/         the shape's SUM over a computed input
     //   plan [variant]   variant: lds (default) | wave (per-wave tables: fdb_plan_set_deterministic) | reg (≤ 8 slots in registers) | cache (table too big for LDS) | two (two-phase layout, 4 aggregates)
@@ -178,6 +179,11 @@ int main(int argc0, char** argv0) {
       s.c4[0].width = 1;
       (s.two_phase ? s.l4[0] : s.c4[1]).width = 2;
       s.quad = true;  // (what jit_shape sets for a launch with a narrow slot)
+    }
+    if (argc > 3 && std::string(argv[3]) == "packed") {  // packed index caches in the place of `narrow`: the filter column at 4 bits (form H), the group column at 12 (form T)
+      s.c4[0].width = fdb::kJitWidthH;
+      (s.two_phase ? s.l4[0] : s.c4[1]).width = fdb::kJitWidthT;
+      s.quad = true;
     }
     if (cfg3 && s.two_phase) {  // plan two [narrow …] cfg3: two more early slots and leaves, AND-ed
       s.n_c4 = 3;
