@@ -142,62 +142,50 @@ int fdb_selftest_widen(const void* src, int32_t width, uint32_t* dst, int64_t n)
   });
 }
 
+// The three scan-cache selftests behind their fronts' argument rules: the builder as scan_cache_get runs it — a uint32 column (and its bitmap:
+// the null-folded builder) in their slots, the cache in a slot of its form —, `out_bytes` of it copied out, every row read back where scan_cache_at says.
+static void selftest_scan_cache(const char* what, const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, fdb::ScanForm form, int device, uint8_t* out, int64_t out_bytes) {
+  const std::string w = what;
+  fdb::CallScope call(device);
+  void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
+  uint8_t* d_bits = validity != nullptr ? (uint8_t*)call.alloc(fdb::bitmap_slot((size_t)rows)) : nullptr;
+  void* d_dst = call.alloc(fdb::scan_form_slot((size_t)rows, form));
+  fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), (w + ": copy in").c_str());
+  if (validity != nullptr) fdb::hip_check(hipMemcpyAsync(d_bits, validity, (size_t)(rows + 7) / 8, hipMemcpyHostToDevice, call.ctx->stream), (w + ": copy in").c_str());
+  fdb::hip_check(fdb_launch_narrow_indices((const uint32_t*)d_src, d_bits, (uint32_t)entries, d_dst, rows, form, call.ctx->stream), (w + ": builder").c_str());
+  fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), (w + ": copy out").c_str());
+  fdb::hip_check(hipStreamSynchronize(call.ctx->stream), (w + ": wait").c_str());
+  for (int64_t i = 0; i < rows; i++) {
+    const bool null = validity != nullptr && ((validity[i >> 3] >> (i & 7)) & 1) == 0;
+    const uint32_t want = null ? (uint32_t)entries : indices[i] & fdb::scan_form(form).max_index;
+    if (fdb::scan_cache_read(out, i, rows, form) != want) throw fdb::Error(FDB_ERR_INVALID, w + ": row " + std::to_string(i) + " is not at its position");
+  }
+}
+
 int fdb_selftest_scan_cache(const uint32_t* indices, int64_t rows, int32_t width, int device, uint8_t* out, int64_t out_bytes) {
   return guard(nullptr, [&] {
     if (indices == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || (width != 1 && width != 2) || out_bytes != (rows * width + 15) / 16 * 16)
       throw fdb::Error(FDB_ERR_INVALID, "scan cache: 1 to 2^28 rows, width 1 or 2, out_bytes = rows * width rounded up to 16");
-    // the builder as scan_cache_get runs it: a uint32 column in a values slot, the cache in a slot of its own width
-    fdb::CallScope call(device);
-    void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
-    void* d_dst = call.alloc(fdb::values_slot((size_t)rows, (size_t)width));
-    fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), "scan cache: copy in");
-    fdb::hip_check(fdb_launch_narrow_indices((const uint32_t*)d_src, d_dst, rows, width, call.ctx->stream), "scan cache: builder");
-    fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), "scan cache: copy out");
-    fdb::hip_check(hipStreamSynchronize(call.ctx->stream), "scan cache: wait");
-    // every row where scan_cache_position says, which is also where fdb_plan_kernel looks for it
-    for (int64_t i = 0; i < rows; i++) {
-      const int64_t at = fdb::scan_cache_position(i, rows, width);
-      const uint32_t got = width == 1 ? out[at] : (uint32_t)out[2 * at] | ((uint32_t)out[2 * at + 1] << 8);
-      if (got != (indices[i] & (width == 1 ? 0xFFu : 0xFFFFu))) throw fdb::Error(FDB_ERR_INVALID, "scan cache: row " + std::to_string(i) + " is not at its position");
-    }
+    selftest_scan_cache("scan cache", indices, nullptr, rows, 0, (fdb::ScanForm)width, device, out, out_bytes);
   });
 }
 
 int fdb_selftest_scan_cache_nulls(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t width, int device, uint8_t* out, int64_t out_bytes) {
   return guard(nullptr, [&] {
     if (indices == nullptr || validity == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || (width != 1 && width != 2) ||
-        entries < 0 || entries > (width == 1 ? 255 : 65535) || out_bytes != (rows * width + 15) / 16 * 16)
+        entries < 0 || entries > (int64_t)fdb::scan_form((fdb::ScanForm)width).max_index || out_bytes != (rows * width + 15) / 16 * 16)
       throw fdb::Error(FDB_ERR_INVALID, "scan cache: 1 to 2^28 rows, width 1 or 2, entries <= 255 / 65 535, out_bytes = rows * width rounded up to 16");
-    // the null-folded builder as scan_cache_get runs it: a uint32 column and its bitmap in their slots, the cache in a slot of its own width
-    fdb::CallScope call(device);
-    void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
-    uint8_t* d_bits = (uint8_t*)call.alloc(fdb::bitmap_slot((size_t)rows));
-    void* d_dst = call.alloc(fdb::values_slot((size_t)rows, (size_t)width));
-    fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), "scan cache: copy in");
-    fdb::hip_check(hipMemcpyAsync(d_bits, validity, (size_t)(rows + 7) / 8, hipMemcpyHostToDevice, call.ctx->stream), "scan cache: copy in");
-    fdb::hip_check(fdb_launch_narrow_indices((const uint32_t*)d_src, d_bits, (uint32_t)entries, d_dst, rows, width, call.ctx->stream), "scan cache: builder");
-    fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), "scan cache: copy out");
-    fdb::hip_check(hipStreamSynchronize(call.ctx->stream), "scan cache: wait");
+    selftest_scan_cache("scan cache", indices, validity, rows, entries, (fdb::ScanForm)width, device, out, out_bytes);
   });
 }
 
 int fdb_selftest_scan_cache_packed(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t form, int device, uint8_t* out, int64_t out_bytes) {
   return guard(nullptr, [&] {
-    const bool h = form == fdb::kScanFormH, t = form == fdb::kScanFormT;
-    if (indices == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || (!h && !t) || entries < 0 || entries + (validity != nullptr ? 1 : 0) > (h ? 16 : 4096) ||
-        out_bytes != (rows + 1023) / 1024 * fdb::scan_form_frame(form))
+    const fdb::ScanFormRow* f = fdb::scan_form_row(form);
+    if (indices == nullptr || out == nullptr || rows <= 0 || rows > ((int64_t)1 << 28) || f == nullptr || !f->framed || entries < 0 ||
+        entries + (validity != nullptr ? 1 : 0) > (int64_t)f->max_index + 1 || out_bytes != (rows + fdb::kScanCacheBlock - 1) / fdb::kScanCacheBlock * f->block_bytes)
       throw fdb::Error(FDB_ERR_INVALID, "packed scan cache: 1 to 2^28 rows, form H (5) or T (6), entries (+ 1 with a bitmap) <= 16 / 4 096, out_bytes = whole frames");
-    // the builder as scan_cache_get_packed runs it: a uint32 column (and its bitmap) in their slots, the cache in a slot of whole frames
-    fdb::CallScope call(device);
-    void* d_src = call.alloc(fdb::values_slot((size_t)rows, 4));
-    uint8_t* d_bits = validity != nullptr ? (uint8_t*)call.alloc(fdb::bitmap_slot((size_t)rows)) : nullptr;
-    void* d_dst = call.alloc(fdb::packed_slot((size_t)rows, form));
-    fdb::hip_check(hipMemcpyAsync(d_src, indices, (size_t)rows * 4, hipMemcpyHostToDevice, call.ctx->stream), "packed scan cache: copy in");
-    if (validity != nullptr) fdb::hip_check(hipMemcpyAsync(d_bits, validity, (size_t)(rows + 7) / 8, hipMemcpyHostToDevice, call.ctx->stream), "packed scan cache: copy in");
-    fdb::hip_check(validity != nullptr ? fdb_launch_narrow_indices((const uint32_t*)d_src, d_bits, (uint32_t)entries, d_dst, rows, form, call.ctx->stream)
-                                       : fdb_launch_narrow_indices((const uint32_t*)d_src, d_dst, rows, form, call.ctx->stream), "packed scan cache: builder");
-    fdb::hip_check(hipMemcpyAsync(out, d_dst, (size_t)out_bytes, hipMemcpyDeviceToHost, call.ctx->stream), "packed scan cache: copy out");
-    fdb::hip_check(hipStreamSynchronize(call.ctx->stream), "packed scan cache: wait");
+    selftest_scan_cache("packed scan cache", indices, validity, rows, entries, f->form, device, out, out_bytes);
   });
 }
 

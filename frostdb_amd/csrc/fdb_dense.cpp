@@ -102,7 +102,7 @@ void Plan::DenseLaunch::bind_group_columns() {
     for (const auto& p : R.lut_src) src.push_back(Src{p.get(), false});
     // whether a group column's LUT gets the entry for NULL (an empty dictionary's LUT is the one entry 0 already)
     auto null_entry_of = [&](const GroupRes& gr) {
-      return scan_cache_folded(*bs[i], (size_t)gr.ci) && gr.lut->size() <= bs[i]->cols[(size_t)gr.ci].dict->values.size();
+      return scan_cache_may_fold(*bs[i], (size_t)gr.ci) && gr.lut->size() <= bs[i]->cols[(size_t)gr.ci].dict->values.size();
     };
     for (const GroupRes& gr : R.groups) src.push_back(Src{gr.lut.get(), null_entry_of(gr)});
     const First* like = nullptr;
@@ -199,17 +199,16 @@ void Plan::DenseLaunch::plan_lds() {
   pt.mark("lut upload");
 }
 
-// Narrow index reads (fdb_record.h, ScanCache): a 4-byte slot is scanned at 4 or 12 bits, else at 1 or 2 bytes, when EVERY part of the
-// launch can hold a cache of that one form for the slot's column — built here, by the first scan that wants it; otherwise the whole launch reads
-// the slot's uint32 columns, which every record has. Slots without values (IS NULL leaves) have nothing to narrow. The
-// algorithmic bytes count the width that is scanned. (Before the shape is taken: jit_shape reads the widths.)
+// Narrow index reads (fdb_record.h, ScanForm): a 4-byte slot is scanned at the narrowest form that EVERY part of the launch offers for the
+// slot's column (scan_form_common) — its buffers built here, by the first scan that wants them; failing a common narrow form the whole
+// launch reads the slot's uint32 columns, which every record has. Slots without values (IS NULL leaves) have nothing to narrow. The
+// algorithmic bytes count the form that is scanned. (Before the shape is taken: jit_shape reads the forms.)
 // A slot narrowed to a null-folded buffer (scan_cache_folded) also loses its bitmap pointer: the buffer holds NULL as the index one past
 // the dictionary, which a leaf's truth table answers last and the group LUT maps to digit 0 (bind_group_columns), so the shape is that of
 // a column without NULLs (has_validity 0, or 2 when another record of the launch keeps a bitmap). The exception is a slot an IS (NOT) NULL
 // leaf reads: FDB_LEAF_VALIDITY is the one consumer of a 4-byte slot's nibble (<reg>_m in fdb_jitgen.cpp) besides leaf_bits / leaf_lut
 // and the group digit, which the folded index serves. The algorithmic bytes keep counting the bitmap: they are what the query reads
 // of the record, not what this launch fetches.
-static_assert(kScanFormH == kJitWidthH && kScanFormT == kJitWidthT, "the record's form codes are what JitSlot::width carries");
 void Plan::DenseLaunch::narrow_slots() {
   if (!specialisable() || !jit_possible) return;
   narrowed_by_part.assign(Rs.size(), SIZE_MAX);
@@ -226,22 +225,17 @@ void Plan::DenseLaunch::narrow_pool(bool late) {
   const FdbScanArgs& a0 = args(live[0]);
   const int n4 = late ? a0.n_l4 : a0.n_c4;
   for (int i : live) if ((late ? args(i).n_l4 : args(i).n_c4) != n4) return;  // (records of different shapes: the launch is split, choose_kernel)
+  std::vector<ScanForms> offers;
   for (int k = 0; k < n4; k++) {
-    // the narrowest form every part can hold for the slot's column: packed (kScanFormH / kScanFormT, one form in every part), then the
-    // byte form (one width in every part), then the uint32 column
-    int w = 0, pk = -1;
+    offers.clear();
     for (int i : live) {
       const Resolved& R = Rs[(size_t)i];
       const int ci = late ? R.l4_col[k] : R.c4_col[k];
       const bool none = (late ? R.args.l4[k] : R.args.c4[k]).values == nullptr || ci < 0;
-      const int wi = none ? 4 : scan_cache_width(*bs[i], (size_t)ci), pi = none ? 0 : scan_cache_packed(*bs[i], (size_t)ci);
-      w = w == 0 || w == wi ? wi : 4;
-      pk = pk < 0 || pk == pi ? pi : 0;
-      if (w == 4 && pk == 0) break;
+      offers.push_back(none ? ScanForms() : scan_cache_forms(*bs[i], (size_t)ci));
     }
-    const bool packed = pk > 0;
-    if (packed) w = pk;
-    if (w == 4) continue;
+    const ScanForm w = scan_form_common(offers.data(), offers.size());
+    if (w == kScanForm4) continue;
     for (int i : live) {
       Resolved& R = Rs[(size_t)i];
       const int ci = late ? R.l4_col[k] : R.c4_col[k];
@@ -249,10 +243,10 @@ void Plan::DenseLaunch::narrow_pool(bool late) {
       bool counted = false;  // (a column the filter and the group-by both read sits in two slots and counts once)
       for (size_t at = narrowed_by_part[(size_t)i]; at != SIZE_MAX; at = narrowed[at].prev_of_part) if (narrowed[at].col == ci) counted = true;
       const int64_t saved = counted ? 0 : bs[i]->rows * 4 - scan_form_bytes(bs[i]->rows, w);
-      const bool fold = sl.validity != nullptr && scan_cache_folded(*bs[i], (size_t)ci) && !(!late && validity_leaf_reads(R.args, k));
+      const bool fold = sl.validity != nullptr && scan_cache_folded(*bs[i], (size_t)ci, w) && !(!late && validity_leaf_reads(R.args, k));
       narrowed.push_back(Narrowed{i, k, ci, late, sl.values, saved, sl.validity, fold, narrowed_by_part[(size_t)i]});
       narrowed_by_part[(size_t)i] = narrowed.size() - 1;
-      sl.values = packed ? scan_cache_get_packed(*bs[i], (size_t)ci, P.stream_) : scan_cache_get(*bs[i], (size_t)ci, P.stream_);
+      sl.values = scan_cache_get(*bs[i], (size_t)ci, w, P.stream_);
       if (fold) sl.validity = nullptr;
       (late ? R.args.wl4 : R.args.w4)[k] = (uint8_t)w;
       R.bytes -= saved;

@@ -9,21 +9,18 @@
 #include <vector>
 
 #include "fdb_kernels.h"
+#include "fdb_record.h"
 
 namespace fdb {
 
-// has_validity: 0 no record has a bitmap, 1 every record, 2 some (checked per record). width (4-byte slots of fdb_plan_kernel only): bytes
-// per index behind `values` — 4: the uint32 column, 1 / 2: the records' narrow-index caches (FdbScanArgs.w4 / wl4), unpacked after the load
-struct JitSlot { bool has_values = false; int has_validity = 0; int width = 4; };
+// has_validity: 0 no record has a bitmap, 1 every record, 2 some (checked per record). form (4-byte slots of fdb_plan_kernel only): what
+// sits behind `values` — 4: the uint32 column, else a form of the records' narrow-index caches (fdb_record.h, ScanForm; FdbScanArgs.w4 /
+// wl4), unpacked after the load
+struct JitSlot { bool has_values = false; int has_validity = 0; ScanForm form = kScanForm4; };
 struct JitLeaf { int kind = 0, slot = -1, wide = 0, op = 0; bool lut_in_lds = false; };
 struct JitGroup { int slot = -1; bool lut_in_lds = false; };
 struct JitAgg { int func = 0, type = 0, slot = -1; int expr = 0; };  // expr: 1 + root node of a computed input, 0 = stored column
 struct JitExprNode { int kind = 0, op = 0, left = -1, right = -1, slot = -1, type = 0; };  // literal values stay run-time arguments
-
-// JitSlot::width of a 4-byte slot read from a packed index cache (fdb_record.h: kScanFormH, 4 bits per index; kScanFormT, 12 bits as a
-// byte plane and a nibble plane), beside 1, 2 (bytes of the narrow-index cache) and 4 (the record's uint32 column).
-constexpr int kJitWidthH = 5, kJitWidthT = 6;
-inline bool jit_width_packed(int w) { return w == kJitWidthH || w == kJitWidthT; }
 
 // Everything that changes the generated CODE. Pointers, literals, truth-table bits, LUT offsets, strides and row counts
 // are run-time arguments and deliberately absent, so that queries of the same shape share one compiled kernel.
@@ -53,9 +50,9 @@ struct JitShape {
   // LDS tables: when the slots of a wave's selected rows agree (sorted input) the updates go to a wave-uniform address, so that the compiler
   // folds them across the lanes (fdb_jitgen.cpp, "Sorted input")
   bool uniform_fold = true;  // ($FDB_NO_UNIFORM_FOLD, A/B aid: a plan reads it at create, Plan::Knobs)
-  // fdb_plan_kernel, set when a slot of the launch is narrow (JitSlot::width < 4): the unit of work (FdbScanArgs tile_begin / tile_end,
+  // fdb_plan_kernel, set when a slot of the launch is narrow (JitSlot::form != 4): the unit of work (FdbScanArgs tile_begin / tile_end,
   // total_tiles) is block × 16 rows instead of block × 4 — each wave takes one block of 1 024 rows as four sub-steps of 64 lanes × 4 rows
-  // and reads the narrow slots of a full block with 16-byte loads, in the order the records' caches keep them (scan_cache_position).
+  // and reads the narrow slots of a full block with 16-byte loads, in the order the records' caches keep them (scan_cache_at).
   bool quad = false;
   // fdb_plan_kernel: the per-record fields come from a packed table (jit_part_fields: W words per record), not from the array of 3 KB
   // FdbScanArgs — a record switch reads W adjacent words, and the host ships those words only. The kernel takes
@@ -66,15 +63,13 @@ struct JitShape {
   // fdb_project_kernel only (not part of key()): root node of every computed field, in output order
   std::vector<int> proj_roots;
   std::string key(bool with_validity = true) const;
-  int row_bytes() const {  // bytes of column data a scan of this shape reads per row (slots with values, 4-byte slots at their width)
-    int b = 0;
-    int packed_bits = 0;  // (the packed forms: whole bytes per row, rounded up over the shape's packed slots together)
-    auto w4 = [&](const JitSlot& c) { if (!c.has_values) return; if (jit_width_packed(c.width)) packed_bits += c.width == kJitWidthH ? 4 : 12; else b += c.width; };
-    for (int k = 0; k < n_c4; k++) w4(c4[k]);
-    for (int k = 0; k < n_l4; k++) w4(l4[k]);
-    for (int k = 0; k < n_c8; k++) b += c8[k].has_values ? 8 : 0;
-    for (int k = 0; k < n_l8; k++) b += l8[k].has_values ? 8 : 0;
-    return b + (packed_bits + 7) / 8;
+  int row_bytes() const {  // bytes of column data a scan of this shape reads per row (slots with values, 4-byte slots at their form), rounded up once
+    int bits = 0;
+    for (int k = 0; k < n_c4; k++) bits += c4[k].has_values ? scan_form_bits(c4[k].form) : 0;
+    for (int k = 0; k < n_l4; k++) bits += l4[k].has_values ? scan_form_bits(l4[k].form) : 0;
+    for (int k = 0; k < n_c8; k++) bits += c8[k].has_values ? 64 : 0;
+    for (int k = 0; k < n_l8; k++) bits += l8[k].has_values ? 64 : 0;
+    return (bits + 7) / 8;
   }
 };
 

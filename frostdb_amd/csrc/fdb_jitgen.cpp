@@ -106,7 +106,7 @@ template <int OP, typename T> __device__ __forceinline__ uint32_t cmp4(T a, T b,
 )HIP";
 
 // Quad shapes only (JitShape::quad; every other shape keeps the source it had). A full 1 024-row block of a narrow-index cache is
-// wave-interleaved (scan_cache_position, fdb_record.h): one 16-byte load per lane holds its four indices of sub-steps 0 … 3 in dwords
+// wave-interleaved (scan_cache_at, fdb_record.h): one 16-byte load per lane holds its four indices of sub-steps 0 … 3 in dwords
 // 0 … 3 (1 byte each), or those of two sub-steps in dwords 0, 1 and 2, 3 (2 bytes each) — unpacked as ld1x4 / ld2x4 unpack theirs.
 const char* kQuadPreamble = R"HIP(
 __device__ __forceinline__ u32x4 ldblock(const void* base, uint32_t byte_off) {
@@ -127,7 +127,7 @@ __device__ __forceinline__ u32x4 idx2x4(uint32_t lo, uint32_t hi) {
 }
 )HIP";
 
-// Quad shapes with a packed slot only (JitSlot::width kJitWidthH / kJitWidthT; fdb_record.h, scan_cache_packed_position). A full block:
+// Quad shapes with a packed slot only (JitSlot::form kScanFormH / kScanFormT; fdb_record.h, scan_cache_at). A full block:
 // the lane's 16 nibbles are one 8-byte load, sub-step u bits 16 u … 16 u + 15 of it; form T's low bytes are one 16-byte load laid out as
 // the 1-byte cache. The record's last, partial block keeps its frame in row order: 2 bytes of nibbles (and 4 of low bytes) per lane and sub-step.
 const char* kPackedPreamble = R"HIP(
@@ -281,25 +281,46 @@ struct Gen {
   // Quad shapes (JitShape::quad), a wave whose 1 024-row block is full: every load that does not wait for `sel` has left before the first
   // sub-step is folded (block_loads), and the sub-step body takes its registers from there.
   bool full_block = false;
-  bool has_packed() const {
-    for (int i = 0; i < s.n_c4; i++) if (s.c4[i].has_values && jit_width_packed(s.c4[i].width)) return true;
-    for (int i = 0; i < s.n_l4; i++) if (s.l4[i].has_values && jit_width_packed(s.l4[i].width)) return true;
+  // The three fragments of 4-byte slot `c` with values (registers named after `r`) at its form (the frame sizes from fdb_record.h's table):
+  // `block_decl` loads the wave's share of a full block at its head ("": form 4, loaded in block_loads' sub-step loop); `from_block` is
+  // sub-step u out of those registers ("": a late slot at form 4 has none); `direct` the load of a sub-step of a partial block or a shape that is not quad.
+  struct Slot4 { std::string block_decl, from_block, direct; };
+  static Slot4 slot4(const JitSlot& c, const std::string& r, bool late) {
+    const std::string P = "P_" + r + "_v", Q = "Q_" + r, N = "N_" + r;
+    const std::string frame = std::to_string(scan_form(c.form).block_bytes), plane = std::to_string(kScanCacheBlock);  // (T: the nibbles sit behind a plane of low bytes)
+    const std::string half = "u < 2 ? " + Q + "a : " + Q + "b";
+    switch (c.form) {
+      case kScanFormH:
+        return {"const u32x2 " + N + " = ldblock8(" + P + " + (size_t)(wb >> 1), lane * 8u);", "idxHx4(nib_of(" + N + ", u))",
+                "idxHx4(ldnib4(" + P + " + (size_t)(r0 >> 10) * " + frame + " + (size_t)(r0 & 1023) / 2, lane * 2u))"};
+      case kScanFormT:
+        return {"const u32x4 " + Q + " = ldblock(" + P + " + (size_t)(wb >> 10) * " + frame + ", lane * 16u); const u32x2 " + N + " = ldblock8(" + P + " + (size_t)(wb >> 10) * " + frame + " + " + plane + ", lane * 8u);",
+                "idxTx4(dword_of(" + Q + ", u), nib_of(" + N + ", u))",
+                "idxTx4(ld1raw(" + P + " + (size_t)(r0 >> 10) * " + frame + " + (size_t)(r0 & 1023), lane_off1), ldnib4(" + P + " + (size_t)(r0 >> 10) * " + frame + " + " + plane + " + (size_t)(r0 & 1023) / 2, lane * 2u))"};
+      case kScanForm1:
+        return {"const u32x4 " + Q + " = ldblock(" + P + " + (size_t)wb, lane * 16u);", "idx1x4(dword_of(" + Q + ", u))", "ld1x4(" + P + " + tile_off1, lane_off1)"};
+      case kScanForm2:
+        return {"const u32x4 " + Q + "a = ldblock(" + P + " + (size_t)wb * 2, lane * 16u), " + Q + "b = ldblock(" + P + " + (size_t)wb * 2 + " + std::to_string(scan_form(c.form).block_bytes / 2) + ", lane * 16u);",
+                "idx2x4(dword_of(" + half + ", 2 * (u & 1)), dword_of(" + half + ", 2 * (u & 1) + 1))", "ld2x4(" + P + " + tile_off2, lane_off2)"};
+      case kScanForm4: break;
+    }
+    return {"", late ? "" : "A_" + r + "[u]", "ld4(" + P + " + tile_off4, lane_off4)"};
+  }
+  bool has_packed() const {  // (which asks for kPackedPreamble)
+    for (int i = 0; i < s.n_c4; i++) if (s.c4[i].has_values && scan_form(s.c4[i].form).framed) return true;
+    for (int i = 0; i < s.n_l4; i++) if (s.l4[i].has_values && scan_form(s.l4[i].form).framed) return true;
     return false;
   }
   void block_loads() {
-    auto narrow = [&](const JitSlot& c, const std::string& r) {
-      if (!c.has_values || c.width == 4) return;
-      if (c.width == kJitWidthH) o << "      const u32x2 N_" << r << " = ldblock8(P_" << r << "_v + (size_t)(wb >> 1), lane * 8u);\n";
-      else if (c.width == kJitWidthT)
-        o << "      const u32x4 Q_" << r << " = ldblock(P_" << r << "_v + (size_t)(wb >> 10) * 1536, lane * 16u); const u32x2 N_" << r << " = ldblock8(P_" << r << "_v + (size_t)(wb >> 10) * 1536 + 1024, lane * 8u);\n";
-      else if (c.width == 1) o << "      const u32x4 Q_" << r << " = ldblock(P_" << r << "_v + (size_t)wb, lane * 16u);\n";
-      else o << "      const u32x4 Q_" << r << "a = ldblock(P_" << r << "_v + (size_t)wb * 2, lane * 16u), Q_" << r << "b = ldblock(P_" << r << "_v + (size_t)wb * 2 + 1024, lane * 16u);\n";
+    auto narrow = [&](const JitSlot& c, const std::string& r, bool late) {
+      const std::string decl = c.has_values ? slot4(c, r, late).block_decl : "";
+      if (!decl.empty()) o << "      " << decl << "\n";
     };
-    for (int i = 0; i < s.n_c4; i++) narrow(s.c4[i], reg(false, false, i));
-    for (int i = 0; i < s.n_l4; i++) narrow(s.l4[i], reg(false, true, i));
+    for (int i = 0; i < s.n_c4; i++) narrow(s.c4[i], reg(false, false, i), false);
+    for (int i = 0; i < s.n_l4; i++) narrow(s.l4[i], reg(false, true, i), true);
     for (int i = 0; i < s.n_c4; i++) {
       const std::string r = reg(false, false, i);
-      if (s.c4[i].has_values && s.c4[i].width == 4) o << "      u32x4 A_" << r << "[4];\n";
+      if (s.c4[i].has_values && s.c4[i].form == kScanForm4) o << "      u32x4 A_" << r << "[4];\n";
       if (s.c4[i].has_validity != 0) o << "      uint32_t M_" << r << "[4];\n";
     }
     for (int i = 0; i < s.n_c8; i++) {
@@ -314,7 +335,7 @@ struct Gen {
     };
     for (int i = 0; i < s.n_c4; i++) {
       const std::string r = reg(false, false, i);
-      if (s.c4[i].has_values && s.c4[i].width == 4) o << "        A_" << r << "[u] = ld4(P_" << r << "_v + o0 * 4, lane_off4);\n";
+      if (s.c4[i].has_values && s.c4[i].form == kScanForm4) o << "        A_" << r << "[u] = ld4(P_" << r << "_v + o0 * 4, lane_off4);\n";
       valid(s.c4[i], r);
     }
     for (int i = 0; i < s.n_c8; i++) {
@@ -331,7 +352,7 @@ struct Gen {
     auto use = [&](const std::string& v) { keep += (keep.empty() ? "\"v\"(" : ", \"v\"(") + v + ")"; };
     for (int i = 0; i < s.n_c4; i++) {
       const std::string r = reg(false, false, i);
-      if (s.c4[i].has_values && s.c4[i].width == 4) use("A_" + r + "[0]");
+      if (s.c4[i].has_values && s.c4[i].form == kScanForm4) use("A_" + r + "[0]");
       if (s.c4[i].has_validity != 0) use("M_" + r + "[0]");
     }
     for (int i = 0; i < s.n_c8; i++) {
@@ -347,18 +368,10 @@ struct Gen {
     for (int i = 0; i < n4; i++) {
       const JitSlot& c = late ? s.l4[i] : s.c4[i];
       const std::string r = reg(false, late, i);
-      if (full_block && c.has_values && c.width == kJitWidthH) o << "    const u32x4 " << r << " = idxHx4(nib_of(N_" << r << ", u));\n";
-      else if (full_block && c.has_values && c.width == kJitWidthT) o << "    const u32x4 " << r << " = idxTx4(dword_of(Q_" << r << ", u), nib_of(N_" << r << ", u));\n";
-      else if (c.has_values && c.width == kJitWidthH) o << "    const u32x4 " << r << " = idxHx4(ldnib4(P_" << r << "_v + (size_t)(r0 >> 10) * 512 + (size_t)(r0 & 1023) / 2, lane * 2u));\n";
-      else if (c.has_values && c.width == kJitWidthT)
-        o << "    const u32x4 " << r << " = idxTx4(ld1raw(P_" << r << "_v + (size_t)(r0 >> 10) * 1536 + (size_t)(r0 & 1023), lane_off1), ldnib4(P_" << r << "_v + (size_t)(r0 >> 10) * 1536 + 1024 + (size_t)(r0 & 1023) / 2, lane * 2u));\n";
-      else if (full_block && c.has_values && c.width == 1) o << "    const u32x4 " << r << " = idx1x4(dword_of(Q_" << r << ", u));\n";
-      else if (full_block && c.has_values && c.width == 2)
-        o << "    const u32x4 " << r << " = idx2x4(dword_of(u < 2 ? Q_" << r << "a : Q_" << r << "b, 2 * (u & 1)), dword_of(u < 2 ? Q_" << r << "a : Q_" << r << "b, 2 * (u & 1) + 1));\n";
-      else if (full_block && !late && c.has_values) o << "    const u32x4 " << r << " = A_" << r << "[u];\n";
-      else if (c.has_values && c.width == 1) o << "    const u32x4 " << r << " = ld1x4(P_" << r << "_v + tile_off1, lane_off1);\n";
-      else if (c.has_values && c.width == 2) o << "    const u32x4 " << r << " = ld2x4(P_" << r << "_v + tile_off2, lane_off2);\n";
-      else if (c.has_values) o << "    const u32x4 " << r << " = ld4(P_" << r << "_v + tile_off4, lane_off4);\n";
+      if (c.has_values) {
+        const Slot4 f = slot4(c, r, late);
+        o << "    const u32x4 " << r << " = " << (full_block && !f.from_block.empty() ? f.from_block : f.direct) << ";\n";
+      }
       mask(c, r, late);
     }
     for (int i = 0; i < n8; i++) {
@@ -1621,7 +1634,7 @@ struct HashGen {
 std::string JitShape::key(bool with_validity) const {
   std::ostringstream k;
   k << "b" << block << "l" << lds_acc << "c" << need_count << "t" << two_phase << "r" << reg_slots << "h" << cache << (wave_tables ? "w" : "") << (uniform_fold ? "u" : "") << (quad ? "q" : "") << (part_table ? "p" : "") << "|";
-  auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) { k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); if (jit_width_packed(p[i].width)) k << 'w' << (p[i].width == kJitWidthH ? 'H' : 'T'); else if (p[i].width != 4) k << 'w' << p[i].width; } k << '|'; };
+  auto slots = [&](const JitSlot* p, int n) { for (int i = 0; i < n; i++) { k << (p[i].has_values ? 'v' : '-') << (with_validity ? p[i].has_validity : 0); if (p[i].form != kScanForm4) k << 'w' << scan_form_name(p[i].form); } k << '|'; };
   slots(c4, n_c4); slots(c8, n_c8); slots(l4, n_l4); slots(l8, n_l8);
   for (const JitLeaf& L : leaves) k << L.kind << ',' << L.slot << ',' << L.wide << ',' << (L.kind >= FDB_LEAF_CMP_I64 && L.kind <= FDB_LEAF_CMP_I64_F64 ? L.op : 0) << ',' << L.lut_in_lds << ';';
   k << '|';
@@ -1726,10 +1739,11 @@ JitShape jit_shape(const FdbScanArgs& a, bool two_phase, int block) {
     for (int i = 0; i < n; i++) { dst[i].has_values = src[i].values != nullptr; dst[i].has_validity = src[i].validity != nullptr ? 1 : 0; }
   };
   slots(s.c4, a.c4, s.n_c4); slots(s.c8, a.c8, s.n_c8); slots(s.l4, a.l4, s.n_l4); slots(s.l8, a.l8, s.n_l8);
-  for (int i = 0; i < s.n_c4; i++) s.c4[i].width = a.w4[i] == 1 || a.w4[i] == 2 || jit_width_packed(a.w4[i]) ? a.w4[i] : 4;
-  for (int i = 0; i < s.n_l4; i++) s.l4[i].width = a.wl4[i] == 1 || a.wl4[i] == 2 || jit_width_packed(a.wl4[i]) ? a.wl4[i] : 4;
-  for (int i = 0; i < s.n_c4; i++) s.quad |= s.c4[i].has_values && s.c4[i].width != 4;
-  for (int i = 0; i < s.n_l4; i++) s.quad |= s.l4[i].has_values && s.l4[i].width != 4;
+  auto form_of = [](uint8_t w) { const ScanFormRow* f = scan_form_row(w); return f != nullptr ? f->form : kScanForm4; };  // (0, what the argument blocks write for 4)
+  for (int i = 0; i < s.n_c4; i++) s.c4[i].form = form_of(a.w4[i]);
+  for (int i = 0; i < s.n_l4; i++) s.l4[i].form = form_of(a.wl4[i]);
+  for (int i = 0; i < s.n_c4; i++) s.quad |= s.c4[i].has_values && s.c4[i].form != kScanForm4;
+  for (int i = 0; i < s.n_l4; i++) s.quad |= s.l4[i].has_values && s.l4[i].form != kScanForm4;
   for (int l = 0; l < a.n_leaves; l++) {
     const FdbLeaf& L = a.leaves[l];
     s.leaves.push_back({L.kind, L.slot, L.wide, L.op, L.kind == FDB_LEAF_DICT_LUT && L.lut_lds != FDB_NO_LDS});

@@ -133,9 +133,9 @@ struct FdbScanArgs {
   unsigned long long* partials;  // LDS mode: per-workgroup partial tables [grid][1 + n_aggs][n_slots], written with plain
                                  // coalesced stores and folded by fdb_launch_reduce_partials (nullptr: flush with atomics)
   int32_t lut_class;        // records with the same class carry byte-identical LUT sets at the same LDS offsets
-  // fdb_plan_kernel only: bytes per index that c4[k] / l4[k].values holds — 0 (what every other builder of these blocks leaves) or 4: the
-  // record's own uint32 column; 1 / 2: the record's narrow-index cache (fdb_record.h, ScanCache), the same width in every part of a launch.
-  // 5 / 6: its packed forms, 4 bits per index (H) and 12 bits as a byte plane and a nibble plane (T; fdb_record.h, kScanFormH / kScanFormT).
+  // fdb_plan_kernel only: the form (fdb_record.h, ScanForm) of what c4[k] / l4[k].values holds — 0 (what every other builder of these
+  // blocks leaves) or 4: the record's own uint32 column; 1, 2, 5 (H) or 6 (T): a buffer of the record's narrow-index cache, the same
+  // form in every part of a launch.
   // A launch with such a slot is a quad launch (fdb_jit.h, JitShape::quad): tile_begin / tile_end count units of block × 16 rows.
   uint8_t w4[FDB_ARG_C4];
   uint8_t wl4[FDB_ARG_L4];
@@ -733,12 +733,12 @@ hipError_t fdb_launch_reduce_partials(const unsigned long long* partials, int n_
 // The slot kernel over `n_parts` records in ONE launch. `d_parts` is the device copy of the per-record argument
 // blocks (global tile ranges filled in, in units of fdb_slot_geometry's tile_rows); `common` = any of them (table
 // pointers, aggregation functions, LDS layout are identical across records). sub_tiles: 1 or 2.
-// dst[scan_cache_position(i, rows, width)] = (uint8 / uint16) src[i] for i < rows (fdb_record.h: the full 1 024-row blocks wave-interleaved,
-// the last, partial block in row order), zero up to the next multiple of 16 bytes (width: 1 or 2): the narrow-index cache of a resident
-// dictionary column. Both buffers are sized like a values slot (kTailPad past the payload), which the 16-byte accesses rely on.
-hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream);
-// The null-folded form: a row whose bit of `validity` (a bitmap slot, bit offset 0) is clear is written as `null_index`, which fits the width.
-hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream);
+// The narrow-index cache of a resident dictionary column at `form` (fdb_record.h, ScanForm: 1, 2, H or T): row i's index src[i], truncated
+// to the form, where scan_cache_at(i, rows, form) says — the full 1 024-row blocks wave-interleaved, the last, partial block in row order —
+// and zero behind the last row up to the next multiple of 16 bytes, or the frame's end. `src` is a values slot and `dst` a
+// scan_form_slot (kTailPad past the payload), which the 16-byte accesses rely on. `validity` != nullptr (a bitmap slot, bit offset 0):
+// the buffer is null-folded, a row whose bit is clear is written as `null_index`, which must fit the form; nullptr: not folded.
+hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int form, hipStream_t stream);
 // Measurement only: reads `bytes` (multiple of 16) once with the best streaming pattern of this box.
 hipError_t fdb_launch_stream_read(const void* src, int64_t bytes, unsigned long long* out, hipStream_t stream);
 hipError_t fdb_launch_scan_slots(const FdbScanArgs* d_parts, int n_parts, const FdbScanArgs& common, int64_t total_tiles, int grid_blocks,

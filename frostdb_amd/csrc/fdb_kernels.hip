@@ -2300,7 +2300,7 @@ hipError_t fdb_launch_stream_read(const void* src, int64_t bytes, unsigned long 
 namespace {
 // The narrow-index cache of a resident dictionary column (fdb_record.h, ScanCache): one 16-byte store per thread = 16 / W rows, read as
 // 16-byte vectors. The vectors of the record's full 1 024-row blocks are written in the wave-interleaved order fdb_plan_kernel loads them
-// in (scan_cache_position): vector l of a block (and of its half h, W = 2) holds lane l's rows 256 u + 4 l … + 3 of sub-steps u = 0 … 3
+// in (scan_cache_at): vector l of a block (and of its half h, W = 2) holds lane l's rows 256 u + 4 l … + 3 of sub-steps u = 0 … 3
 // (W = 2: u = 2 h, 2 h + 1), gathered from 4 / 2 reads 1 KiB apart — each wave read instruction still contiguous. The vectors of the last,
 // partial block hold consecutive rows. FOLD (a null-folded buffer, fdb_record.h): a NULL row is written as `null_index`, the index one
 // past the dictionary; the validity nibble of source vector v (rows 4 v … 4 v + 3) is the (v & 1)-th nibble of bitmap byte v / 2, and
@@ -2346,7 +2346,7 @@ __global__ __launch_bounds__(256) void narrow_indices_kernel(const u32x4* __rest
 }  // namespace
 
 namespace {
-// The packed forms of that cache (fdb_record.h, scan_cache_packed_position): frames of 512 B (H: 4 bits per index) or 1 024 + 512 B (T: the
+// The packed forms of that cache (fdb_record.h, scan_cache_at): frames of 512 B (H: 4 bits per index) or 1 024 + 512 B (T: the
 // low bytes laid out as the 1-byte form, then the high nibbles laid out as H) per 1 024-row block. One 16-byte store per thread: vector t < 64
 // of T's byte plane is lane t's rows of the four sub-steps (4 source vectors, 64 apart), vector t of a nibble plane holds lanes 2 t and
 // 2 t + 1 (8 source vectors: the k-th is lane 2 t + k / 4, sub-step k % 4); in the record's last, partial block both hold consecutive rows.
@@ -2399,32 +2399,24 @@ __global__ __launch_bounds__(256) void pack_indices_kernel(const u32x4* __restri
 
 namespace {
 template <bool FOLD>
-hipError_t launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream) {
-  if (rows <= 0) return hipSuccess;
-  if (fdb::scan_form_packed(width)) {
-    const bool t12 = width == fdb::kScanFormT;
-    const int64_t n_vec = (rows + fdb::kScanCacheBlock - 1) / fdb::kScanCacheBlock * (t12 ? 96 : 32);
-    const unsigned grid = (unsigned)((n_vec + 255) / 256);
-    if (t12) hipLaunchKernelGGL((pack_indices_kernel<true, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<unsigned char*>(dst), rows, n_vec);
-    else hipLaunchKernelGGL((pack_indices_kernel<false, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<unsigned char*>(dst), rows, n_vec);
-    return hipGetLastError();
-  }
-  if (width != 1 && width != 2) return hipErrorInvalidValue;
-  const int64_t per = 16 / width, n_vec = (rows + per - 1) / per;
+hipError_t launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, const fdb::ScanFormRow& f, hipStream_t stream) {
+  const int64_t blocks = (rows + fdb::kScanCacheBlock - 1) / fdb::kScanCacheBlock;
+  const int64_t n_vec = f.framed ? blocks * (f.block_bytes / 16) : (rows * (f.bits / 8) + 15) / 16;  // 16-byte vectors of the buffer, one per thread
   const unsigned grid = (unsigned)((n_vec + 255) / 256);
-  if (width == 1) hipLaunchKernelGGL((narrow_indices_kernel<1, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<u32x4*>(dst), rows, n_vec);
-  else hipLaunchKernelGGL((narrow_indices_kernel<2, FOLD>), dim3(grid), dim3(256), 0, stream, reinterpret_cast<const u32x4*>(src), validity, null_index, reinterpret_cast<u32x4*>(dst), rows, n_vec);
+  const u32x4* s = reinterpret_cast<const u32x4*>(src);
+  if (f.form == fdb::kScanFormT) hipLaunchKernelGGL((pack_indices_kernel<true, FOLD>), dim3(grid), dim3(256), 0, stream, s, validity, null_index, reinterpret_cast<unsigned char*>(dst), rows, n_vec);
+  else if (f.form == fdb::kScanFormH) hipLaunchKernelGGL((pack_indices_kernel<false, FOLD>), dim3(grid), dim3(256), 0, stream, s, validity, null_index, reinterpret_cast<unsigned char*>(dst), rows, n_vec);
+  else if (f.form == fdb::kScanForm1) hipLaunchKernelGGL((narrow_indices_kernel<1, FOLD>), dim3(grid), dim3(256), 0, stream, s, validity, null_index, reinterpret_cast<u32x4*>(dst), rows, n_vec);
+  else hipLaunchKernelGGL((narrow_indices_kernel<2, FOLD>), dim3(grid), dim3(256), 0, stream, s, validity, null_index, reinterpret_cast<u32x4*>(dst), rows, n_vec);
   return hipGetLastError();
 }
 }  // namespace
 
-hipError_t fdb_launch_narrow_indices(const uint32_t* src, void* dst, int64_t rows, int width, hipStream_t stream) {
-  return launch_narrow_indices<false>(src, nullptr, 0u, dst, rows, width, stream);
-}
-
-hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int width, hipStream_t stream) {
-  if (validity == nullptr || null_index > (width == fdb::kScanFormH ? 0xFu : width == fdb::kScanFormT ? 0xFFFu : width == 1 ? 0xFFu : 0xFFFFu)) return hipErrorInvalidValue;
-  return launch_narrow_indices<true>(src, validity, null_index, dst, rows, width, stream);
+hipError_t fdb_launch_narrow_indices(const uint32_t* src, const uint8_t* validity, uint32_t null_index, void* dst, int64_t rows, int form, hipStream_t stream) {
+  const fdb::ScanFormRow* f = fdb::scan_form_row(form);
+  if (f == nullptr || f->form == fdb::kScanForm4 || (validity != nullptr && null_index > f->max_index)) return hipErrorInvalidValue;
+  if (rows <= 0) return hipSuccess;
+  return validity != nullptr ? launch_narrow_indices<true>(src, validity, null_index, dst, rows, *f, stream) : launch_narrow_indices<false>(src, nullptr, 0u, dst, rows, *f, stream);
 }
 
 namespace {

@@ -83,7 +83,7 @@ DeviceBatch::~DeviceBatch() {
   }
   if (arena != nullptr) device_pool_free(device, arena);
   for (void* p : extra_arenas) device_pool_free(device, p);
-  for (const ScanCache::Col& c : scan_cache.cols) device_pool_free(device, c.d);  // (only resident records get one: the scans that read it were waited for above)
+  for (const ScanCache::Entry& e : scan_cache.entries) device_pool_free(device, e.d);  // (only resident records get one: the scans that read it were waited for above)
 }
 
 int DeviceBatch::find(const std::string& name) const {

@@ -42,7 +42,7 @@ inline void print_dense_launch(const char* kernel, const std::string& shape_key,
                                size_t lds_bytes, int two_phase, int lds_acc, int cache_slots, size_t lut_lds_max, int per_cu, int tile_rows, bool fill_rides, bool partials,
                                const std::vector<uint32_t>& folded = std::vector<uint32_t>(), int ptab_words = 0) {
   std::string s;
-  auto form = [](int w) { return w == 5 ? std::string("H") : w == 6 ? std::string("T") : std::to_string(w); };  // (fdb_record.h: kScanFormH, kScanFormT)
+  auto form = [](int w) { const ScanFormRow* f = scan_form_row(w); return f != nullptr ? std::string(f->name) : std::to_string(w); };  // (0: the argument blocks' 4)
   for (size_t p = 0; p < n_parts; p++) {
     const FdbScanArgs& a = *parts[p];
     s += " " + std::to_string(a.lut_class) + ":";

@@ -24,54 +24,40 @@ void* CallScope::alloc(size_t bytes) {
   return p;
 }
 
-int scan_cache_width(const DeviceBatch& b, size_t c) {
-  if (b.arena_ctx != nullptr || b.arena_borrowed || b.rows < kScanCacheMinRows) return 4;
+// NULLs as the cache sees them: a column without a bitmap has none
+static int64_t cached_nulls(const DevColumn& col) { return col.d_validity != nullptr ? col.null_count : 0; }
+
+ScanForms scan_cache_forms(const DeviceBatch& b, size_t c) {
   const DevColumn& col = b.cols[c];
-  if (col.kind != ColKind::DICT || col.dict == nullptr || col.d_values == nullptr) return 4;
-  return narrow_width(col.dict->values.size());
+  if (b.arena_ctx != nullptr || b.arena_borrowed || col.kind != ColKind::DICT || col.dict == nullptr || col.d_values == nullptr) return ScanForms();
+  return scan_forms_of(col.dict->values.size(), cached_nulls(col), b.rows);
 }
 
-bool scan_cache_folded(const DeviceBatch& b, size_t c) {
-  if (scan_cache_width(b, c) >= 4) return false;
-  const DevColumn& col = b.cols[c];
-  return col.d_validity != nullptr && scan_cache_folds(col.dict->values.size(), col.null_count, b.rows);
+bool scan_cache_folded(const DeviceBatch& b, size_t c, ScanForm form) {
+  return form != kScanForm4 && scan_cache_forms(b, c).has(form) && scan_form_folds(form, b.cols[c].dict->values.size(), cached_nulls(b.cols[c]));
 }
 
-int scan_cache_packed(const DeviceBatch& b, size_t c) {
-  if (scan_cache_width(b, c) >= 4) return 0;  // (transient, below the byte forms' threshold, no dictionary column, or a dictionary too large for any form)
-  const DevColumn& col = b.cols[c];
-  return scan_cache_packed_of(col.dict->values.size(), col.d_validity != nullptr ? col.null_count : 0, b.rows);
+bool scan_cache_may_fold(const DeviceBatch& b, size_t c) {
+  const ScanForms f = scan_cache_forms(b, c);
+  for (int k = 0; k + 1 < f.n; k++) if (scan_form_folds(f.form[k], b.cols[c].dict->values.size(), cached_nulls(b.cols[c]))) return true;  // (the closing 4 never folds)
+  return false;
 }
 
-static const void* scan_cache_build(const DeviceBatch& b, size_t c, int width, hipStream_t stream) {
-  const bool packed = scan_form_packed(width);
+const void* scan_cache_get(const DeviceBatch& b, size_t c, ScanForm form, hipStream_t stream) {
+  if (form == kScanForm4 || !scan_cache_forms(b, c).has(form)) throw Error(FDB_ERR_INVALID, "internal: no narrow-index cache at form " + std::string(scan_form_name(form)) + " for column " + b.cols[c].name);
   std::lock_guard<std::mutex> lk(b.scan_cache_mu);
   ScanCache& sc = b.scan_cache;
-  if (sc.cols.empty()) sc.cols.resize(2 * b.cols.size());
-  ScanCache::Col& e = sc.cols[2 * c + (packed ? 1 : 0)];
-  if (e.d != nullptr) return e.d;
-  const size_t bytes = packed ? packed_slot((size_t)b.rows, width) : values_slot((size_t)b.rows, (size_t)width);
+  for (const ScanCache::Entry& e : sc.entries) if (e.column == c && e.form == form) return e.d;
+  sc.entries.reserve(sc.entries.size() + 1);  // (nothing may throw between the build and the publication)
+  const size_t bytes = scan_form_slot((size_t)b.rows, form);
   void* d = device_pool_alloc(b.device, bytes);
-  const bool folded = scan_cache_folded(b, c);
-  hipError_t err = folded ? fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, b.cols[c].d_validity, (uint32_t)b.cols[c].dict->values.size(), d, b.rows, width, stream)
-                          : fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, d, b.rows, width, stream);
+  const bool folded = scan_form_folds(form, b.cols[c].dict->values.size(), cached_nulls(b.cols[c]));
+  hipError_t err = fdb_launch_narrow_indices((const uint32_t*)b.cols[c].d_values, folded ? b.cols[c].d_validity : nullptr, (uint32_t)b.cols[c].dict->values.size(), d, b.rows, form, stream);
   if (err == hipSuccess) err = hipStreamSynchronize(stream);
   if (err != hipSuccess) { device_pool_free(b.device, d); hip_check(err, "narrow-index cache"); }
-  e.d = d; e.width = width; e.bytes = bytes; e.folded = folded;
+  sc.entries.push_back(ScanCache::Entry{c, form, d, bytes, folded});
   sc.bytes += (int64_t)bytes;
   return d;
-}
-
-const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream) {
-  const int width = scan_cache_width(b, c);
-  if (width >= 4) throw Error(FDB_ERR_INVALID, "internal: no narrow-index cache for column " + b.cols[c].name);
-  return scan_cache_build(b, c, width, stream);
-}
-
-const void* scan_cache_get_packed(const DeviceBatch& b, size_t c, hipStream_t stream) {
-  const int form = scan_cache_packed(b, c);
-  if (form == 0) throw Error(FDB_ERR_INVALID, "internal: no packed index cache for column " + b.cols[c].name);
-  return scan_cache_build(b, c, form, stream);
 }
 
 void require_values(const DeviceBatch& in, const char* what) {

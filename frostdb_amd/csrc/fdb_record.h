@@ -30,73 +30,103 @@ inline size_t values_slot(size_t rows, size_t width) { return align_up(rows * wi
 // byte count is itself such a multiple, so the rounding never passes it.
 inline size_t bitmap_slot(size_t rows) { return align_up((rows + 63) / 64 * 8 + kTailPad, 256); }
 
-// Element position of row `i` in a narrow-index cache (ScanCache, below) of `rows` rows at `width` 1 or 2 bytes per index. The cache has one
-// reader, fdb_plan_kernel, whose wave owns a block of 1 024 consecutive rows as four sub-steps of 256 rows; in sub-step u lane l owns rows
-// 256 u + 4 l … + 3. The indices of a full block sit in the order the wave's 16-byte loads want them: lane l's load at byte 16 l of the
-// block's 1 024 bytes (width 1), or its two loads at bytes 1 024 h + 16 l of the block's 2 048 (width 2), hold its rows of sub-steps
-// 0 … 3, or 2 h and 2 h + 1. The rows of the record's last, partial block stay in row order. The layout follows from the wave
-// (64 lanes × 4 rows) alone: not from a workgroup size, a query or a launch.
-#if defined(__HIPCC__)
-#define FDB_RECORD_HD __host__ __device__
-#else
-#define FDB_RECORD_HD
-#endif
+// ---- the forms of the narrow-index cache ----------------------------------------------------------------------------------------------
+// A resident dictionary column is scanned (fdb_plan_kernel, the cache's one reader) at one of five forms: its own uint32 indices (4), or
+// a buffer of the record's cache (ScanCache, below) that holds them at 1 or 2 bytes, or packed at 4 bits (H) or 12 bits (T: the low byte
+// of every index, laid out exactly as form 1, then the high nibble, laid out as H — unpacking is lo | hi << 8, no bit field crosses a
+// word). The codes are what FdbScanArgs::w4 / wl4, JitSlot::form and the launch description carry (an argument block writes 0 for 4).
+//
+// Layout. The reader's wave owns a block of 1 024 consecutive rows as four sub-steps of 256 rows; in sub-step u lane l owns rows
+// 256 u + 4 l … + 3. The indices of a full block sit in the order the wave's loads want them: lane l's 16-byte load at byte 16 l of the
+// block (forms 1 and T's byte plane), or its two loads at bytes 1 024 h + 16 l (form 2), hold its rows of sub-steps 0 … 3, or 2 h and
+// 2 h + 1; its 16 nibbles (rows 256 u + 4 l + r, nibble 4 u + r, low nibble first) are the 8 bytes at 8 l of the nibble plane, so
+// sub-step u is bits 16 u … 16 u + 15 of the lane's 64-bit word. The rows of the record's last, partial block stay in row order; a framed
+// form (H, T) still gives that block a whole frame, zeros behind the last row. The layout follows from the wave (64 lanes × 4 rows) alone.
+//
+enum ScanForm : int { kScanForm1 = 1, kScanForm2 = 2, kScanForm4 = 4, kScanFormH = 5, kScanFormT = 6 };
 constexpr int64_t kScanCacheBlock = 1024;  // rows of a wave's block
-FDB_RECORD_HD inline int64_t scan_cache_position(int64_t i, int64_t rows, int width) {
-  if (i >= rows / kScanCacheBlock * kScanCacheBlock) return i;
-  const int64_t b = i / kScanCacheBlock, j = i % kScanCacheBlock, u = j / 256, l = (j % 256) / 4, r = j % 4;
-  return width == 1 ? kScanCacheBlock * b + 16 * l + 4 * u + r : kScanCacheBlock * b + 512 * (u / 2) + 8 * l + 4 * (u % 2) + r;
+// Per form: bits per index; the largest index it holds; the bytes of a full block's indices; framed (the packed forms): a partial block
+// occupies a whole frame too; the rows a record must have (below them the bytes the form saves are under a microsecond of a scan).
+struct ScanFormRow { ScanForm form; const char* name; int bits; uint32_t max_index; int64_t block_bytes; bool framed; int64_t min_rows; };
+constexpr ScanFormRow kScanForms[] = {
+    {kScanForm1, "1", 8, 0xFFu, 1024, false, (int64_t)1 << 20},
+    {kScanForm2, "2", 16, 0xFFFFu, 2048, false, (int64_t)1 << 20},
+    {kScanForm4, "4", 32, 0xFFFFFFFFu, 4096, false, 0},
+    {kScanFormH, "H", 4, 0xFu, 512, true, (int64_t)4 << 20},
+    {kScanFormT, "T", 12, 0xFFFu, 1536, true, (int64_t)4 << 20},
+};
+constexpr const ScanFormRow* scan_form_row(int form) {  // nullptr: not a form's code
+  for (const ScanFormRow& r : kScanForms) if (r.form == form) return &r;
+  return nullptr;
+}
+inline const ScanFormRow& scan_form(ScanForm form) { return *scan_form_row(form); }
+inline const char* scan_form_name(ScanForm form) { return scan_form(form).name; }
+inline int scan_form_bits(ScanForm form) { return scan_form(form).bits; }
+inline int64_t scan_form_bytes(int64_t rows, ScanForm form) { return (rows * scan_form_bits(form) + 7) / 8; }  // the algorithmic bytes a scan reads of such a slot
+// Bytes of a buffer of `rows` rows: sized like a values slot, a framed form in whole frames.
+inline size_t scan_form_slot(size_t rows, ScanForm form) {
+  const ScanFormRow& f = scan_form(form);
+  return align_up((f.framed ? (rows + kScanCacheBlock - 1) / kScanCacheBlock * (size_t)f.block_bytes : rows * (size_t)f.bits / 8) + kTailPad, 256);
+}
+// Null-folded: the buffer of a column with NULLs holds S = `entries`, the index one past the dictionary, under every NULL row where S fits
+// the form, and its reader needs no bitmap. Dictionaries of exactly 256 and 65 536 entries keep their byte form and their bitmap.
+inline bool scan_form_folds(ScanForm form, size_t entries, int64_t nulls) { return nulls > 0 && form != kScanForm4 && entries <= scan_form(form).max_index; }
+
+// The rule: the forms a column of a record of `rows` rows may be scanned at, narrowest first, always ending in 4 (the column itself) —
+// at most its packed form, its byte form and 4. A form applies from its minimum rows on where the dictionary fits it; a packed form must
+// also leave room for S when the column has NULLs (so a packed buffer of such a column is always folded: 16 or 4 096 entries with NULLs
+// fall to the byte forms, which fold them), and is offered only where it is narrower than the byte form (T never beside form 1).
+struct ScanForms {  // (as constructed: the column itself only)
+  int n = 1; ScanForm form[3] = {kScanForm4, kScanForm4, kScanForm4};
+  bool has(ScanForm f) const { return (n > 0 && form[0] == f) || (n > 1 && form[1] == f) || (n > 2 && form[2] == f); }
+};
+inline ScanForms scan_forms_of(size_t entries, int64_t nulls, int64_t rows) {
+  const ScanFormRow *packed = nullptr, *bytes = nullptr;
+  for (const ScanFormRow& f : kScanForms) {
+    if (f.form == kScanForm4 || rows < f.min_rows || entries + (f.framed && nulls > 0 ? 1 : 0) > (size_t)f.max_index + 1) continue;
+    const ScanFormRow*& best = f.framed ? packed : bytes;
+    if (best == nullptr || f.bits < best->bits) best = &f;
+  }
+  ScanForms out; out.n = 0;
+  if (packed != nullptr && (bytes == nullptr || packed->bits < bytes->bits)) out.form[out.n++] = packed->form;
+  if (bytes != nullptr) out.form[out.n++] = bytes->form;
+  out.form[out.n++] = kScanForm4;
+  return out;
+}
+// The form a launch over `n` > 0 parts reads a slot at: the first candidate of parts[0] that every part offers (4 always survives) —
+// the same packed form in all parts, else the same byte form in all parts, else the uint32 columns.
+inline ScanForm scan_form_common(const ScanForms* parts, size_t n) {
+  for (int k = 0; k < parts[0].n; k++) {
+    bool all = true;
+    for (size_t p = 1; all && p < n; p++) all = parts[p].has(parts[0].form[k]);
+    if (all) return parts[0].form[k];
+  }
+  return kScanForm4;
 }
 
-// What the cache holds for a dictionary column, from numbers alone (tools/scan_cache_dump.cpp prints them for a test to hold to a table).
-constexpr int64_t kScanCacheMinRows = (int64_t)1 << 20;  // below it 3 B/row and column save less than a microsecond of a scan
-// Bytes per index the cache can hold for a dictionary of `entries` entries; 4: none (the column itself).
-inline int narrow_width(size_t entries) { return entries <= 256 ? 1 : entries <= 65536 ? 2 : 4; }
-// … of a resident record of `rows` rows
-inline int scan_cache_width_of(size_t entries, int64_t rows) { return rows < kScanCacheMinRows ? 4 : narrow_width(entries); }
-// Null-folded: the buffer holds the index S = `entries`, one past the dictionary, under every NULL row, so that its reader needs no
-// bitmap. The column has a bitmap (`nulls` > 0) and S fits the width: at most 255 entries at 1 byte, 65 535 at 2. Dictionaries of
-// exactly 256 and 65 536 entries keep their width, are not folded, and are scanned with their bitmap.
-inline bool scan_cache_folds(size_t entries, int64_t nulls, int64_t rows) {
-  const int w = scan_cache_width_of(entries, rows);
-  return nulls > 0 && w < 4 && entries < ((size_t)1 << (8 * w));
-}
-
-// ---- the packed forms: 4 and 12 bits per index ----------------------------------------------------------------------------------------
-// Form H holds an index in 4 bits (a column whose entries plus one NULL value number at most 16), form T in 12 (at most 4 096) as two
-// planes: the low byte of every index, laid out exactly as the 1-byte form, and the high nibble, laid out as form H. Unpacking T is
-// lo | hi << 8: no bit field crosses a word. A buffer is a run of whole frames, one per 1 024-row block: 512 B for H; for T 1 024 B of
-// bytes, then 512 B of nibbles. In a full block lane l's 16 nibbles (rows 256 u + 4 l + r, nibble 4 u + r, low nibble first) are the 8
-// bytes at 8 l of the nibble plane, so sub-step u is bits 16 u … 16 u + 15 of the lane's 64-bit word. The record's last, partial block
-// keeps the same frame in row order: row j of the block at byte j and nibble j, zeros behind the last row to the frame's end.
-// A packed buffer of a column with NULLs is always null-folded (the rule below leaves S = entries room), so it needs no bitmap.
-constexpr int kScanFormH = 5, kScanFormT = 6;  // as JitSlot::width / FdbScanArgs::w4 carry them, beside the byte widths 1, 2 and 4
-constexpr int64_t kScanCachePackedMinRows = (int64_t)4 << 20;  // below it the 1 B a row the packed forms save on top of the byte forms is under a microsecond of a scan
-inline bool scan_form_packed(int form) { return form == kScanFormH || form == kScanFormT; }
-inline int scan_form_bits(int form) { return form == kScanFormH ? 4 : form == kScanFormT ? 12 : form == 1 ? 8 : form == 2 ? 16 : 32; }
-inline int64_t scan_form_frame(int form) { return form == kScanFormH ? 512 : 1536; }  // bytes of a packed form's frame
-inline size_t packed_slot(size_t rows, int form) { return align_up((rows + 1023) / 1024 * (size_t)scan_form_frame(form) + kTailPad, 256); }
-// Bytes a scan of `rows` rows reads of an index column at `form` (any of the five): the algorithmic bytes of that slot.
-inline int64_t scan_form_bytes(int64_t rows, int form) { return (rows * scan_form_bits(form) + 7) / 8; }
-// The width rule. H where entries + (nulls > 0) ≤ 16; else nothing where the 1-byte form applies; else T where entries + (nulls > 0)
-// ≤ 4 096; else nothing. 0: the column gets no packed buffer (it may get a byte one: scan_cache_width_of). A column of exactly 16 or
-// 4 096 entries with NULLs falls to the byte forms, which fold it.
-inline int scan_cache_packed_of(size_t entries, int64_t nulls, int64_t rows) {
-  if (rows < kScanCachePackedMinRows) return 0;
-  const size_t need = entries + (nulls > 0 ? 1 : 0);
-  return need <= 16 ? kScanFormH : entries <= 256 ? 0 : need <= 4096 ? kScanFormT : 0;
-}
-// Where row `i` of a packed buffer of `rows` rows sits: the byte of its low 8 bits (T; −1 for H) and the byte and shift of its nibble.
-struct PackedAt { int64_t byte; int64_t nibble_byte; int nibble_shift; };
-FDB_RECORD_HD inline PackedAt scan_cache_packed_position(int64_t i, int64_t rows, int form) {
-  const int64_t frame = form == kScanFormH ? 512 : 1536, plane = form == kScanFormH ? 0 : 1024;
+// Where row `i` of a buffer of `rows` rows at `form` sits: `n_bytes` bytes (little-endian; 0: none, form H) at `byte` hold the index's
+// low bits, and the nibble at `nibble_byte` >> `nibble_shift` (nibble_byte < 0: none, the unpacked forms) the 4 bits above them.
+struct ScanCacheAt { int64_t byte; int n_bytes; int64_t nibble_byte; int nibble_shift; };
+inline ScanCacheAt scan_cache_at(int64_t i, int64_t rows, ScanForm form) {
+  const ScanFormRow& f = scan_form(form);
   const int64_t b = i / kScanCacheBlock, j = i % kScanCacheBlock, u = j / 256, l = (j % 256) / 4, r = j % 4;
-  const int64_t e = i >= rows / kScanCacheBlock * kScanCacheBlock ? j : 16 * l + 4 * u + r;  // element of the block: byte e, nibble e
-  PackedAt at;
-  at.byte = form == kScanFormH ? -1 : b * frame + e;
-  at.nibble_byte = b * frame + plane + e / 2;
-  at.nibble_shift = (int)(e % 2) * 4;
+  const bool full = i < rows / kScanCacheBlock * kScanCacheBlock;
+  const int64_t e = full ? 16 * l + 4 * u + r : j;                            // element of the block at one byte (and one nibble) each
+  const int64_t e2 = full ? 512 * (u / 2) + 8 * l + 4 * (u % 2) + r : j;      // … at two bytes each
+  ScanCacheAt at;
+  at.n_bytes = f.bits / 8;  // the whole bytes of an index; a framed form keeps the nibble above them in a plane behind theirs
+  at.byte = b * f.block_bytes + (at.n_bytes == 2 ? 2 * e2 : at.n_bytes == 4 ? 4 * j : e);
+  at.nibble_byte = f.framed ? b * f.block_bytes + at.n_bytes * kScanCacheBlock + e / 2 : -1;
+  at.nibble_shift = f.framed ? (int)(e % 2) * 4 : 0;
   return at;
+}
+// The index a buffer holds for row `i`.
+inline uint32_t scan_cache_read(const uint8_t* buf, int64_t i, int64_t rows, ScanForm form) {
+  const ScanCacheAt at = scan_cache_at(i, rows, form);
+  uint32_t v = 0;
+  for (int k = 0; k < at.n_bytes; k++) v |= (uint32_t)buf[at.byte + k] << (8 * k);
+  if (at.nibble_byte >= 0) v |= (uint32_t)((buf[at.nibble_byte] >> at.nibble_shift) & 0xFu) << (8 * at.n_bytes);
+  return v;
 }
 
 // Offsets of the slots of one record, in column order: [values | bitmap] per column.
@@ -169,35 +199,30 @@ struct CallScope {
 };
 
 // ---- the narrow-index cache of a resident record -------------------------------------------------------------------------------------
-// Beside the record, never part of it: per dictionary column at most one device buffer of the column's indices at 1 byte (dictionaries
-// of ≤ 256 entries) or 2 bytes (≤ 65 536), which the dense generated scan (fdb_plan_kernel) reads instead of the uint32 column. It
-// depends on the immutable record alone, so it is built once — by the first such scan that references the column — and freed with the
-// record. The record's layout, arena_bytes (fdb_batch_device_bytes: the record's OWN columns) and every other operator are untouched by
-// it: the cache is extra memory, up to 3 bytes per row and scanned dictionary column, reported by fdb_batch_scan_cache_bytes.
-// A buffer is sized like a values slot and comes from the device pool, so fdb_live_allocations counts it. Its bytes are a private layout
-// (scan_cache_position, above): no other operator, and nothing outside the library, reads them.
-// NULL is an index of its own where it fits (scan_cache_folds, above): a null-folded buffer holds S = the dictionary's entry count
-// under every NULL row, the answer a filter leaf's truth table keeps last and the entry a group LUT gets appended (digit 0), so the scan
-// of such a column loads no bitmap. A buffer that is not folded holds the truncated uint32 of every row, a NULL row's included.
+// Beside the record, never part of it: per dictionary column and form (ScanForm, above) at most one device buffer of the column's
+// indices, which the dense generated scan (fdb_plan_kernel) reads instead of the uint32 column. It depends on the immutable record
+// alone, so it is built once — by the first such scan that wants the column at that form — and freed with the record; a record scanned
+// in different company may come to hold two forms of a column. The record's layout, arena_bytes (fdb_batch_device_bytes: the record's
+// OWN columns) and every other operator are untouched by it: the cache is extra memory from the device pool (fdb_live_allocations
+// counts it), reported by fdb_batch_scan_cache_bytes, in a private layout (scan_cache_at) that nothing else reads.
+// A null-folded buffer (scan_form_folds) holds S under every NULL row, the answer a filter leaf's truth table keeps last and the entry
+// a group LUT gets appended (digit 0); a buffer that is not folded holds the truncated uint32 of every row, a NULL row's included.
 struct ScanCache {
-  struct Col { void* d = nullptr; int width = 0; size_t bytes = 0; bool folded = false; };
-  std::vector<Col> cols;  // column c's byte form at 2 c, its packed form (kScanFormH / kScanFormT in `width`) at 2 c + 1; empty until the first buffer
-  int64_t bytes = 0;      // Σ values_slot(rows, width) / packed_slot(rows, form) of the buffers
+  struct Entry { size_t column; ScanForm form; void* d; size_t bytes; bool folded; };
+  std::vector<Entry> entries;  // looked up by (column, form)
+  int64_t bytes = 0;           // Σ scan_form_slot(rows, form) of the buffers
 };
-// Width at which a dense generated scan may read column `c` of `b` — 1, 2, or 4 when the column gets no buffer: no dictionary column,
-// a dictionary too large, a record below kScanCacheMinRows or a transient one (a host record is scanned once). Builds nothing.
-int scan_cache_width(const DeviceBatch& b, size_t c);
-// The packed form a dense generated scan may read column `c` at — kScanFormH, kScanFormT, or 0: none (scan_cache_packed_of; never for a
-// transient record). A record scanned in different company may come to hold both forms of a column; both are counted and freed with it.
-int scan_cache_packed(const DeviceBatch& b, size_t c);
-// Whether that buffer is (or, once built, will be) null-folded: scan_cache_folds of the column's dictionary, NULL count and rows. Builds nothing.
-bool scan_cache_folded(const DeviceBatch& b, size_t c);
-// The buffer of column `c` (scan_cache_width(b, c) < 4), built on `stream` if it is not there yet. Two plans on two threads and two
-// streams may meet the same fresh record: the record's mutex is held from the look-up to the publication, and a buffer is published
-// only after the stream that built it has been synchronised — exactly one survives and nobody reads it early.
-const void* scan_cache_get(const DeviceBatch& b, size_t c, hipStream_t stream);
-// The same for the column's packed buffer (scan_cache_packed(b, c) != 0).
-const void* scan_cache_get_packed(const DeviceBatch& b, size_t c, hipStream_t stream);
+// The forms a dense generated scan may read column `c` of `b` at (scan_forms_of) — just 4 when the column gets no buffer: no dictionary
+// column, no values, or a transient or borrowed record (a host record is scanned once). Builds nothing.
+ScanForms scan_cache_forms(const DeviceBatch& b, size_t c);
+// Whether the column's buffer at `form` is (or, once built, will be) null-folded. Builds nothing.
+bool scan_cache_folded(const DeviceBatch& b, size_t c, ScanForm form);
+// … whether any candidate folds, for what is decided before a launch has chosen (a packed form folds whenever the byte form does).
+bool scan_cache_may_fold(const DeviceBatch& b, size_t c);
+// The buffer of column `c` at `form`, one of scan_cache_forms(b, c) below 4, built on `stream` if it is not there yet. Two plans on two
+// threads and two streams may meet the same fresh record: the record's mutex is held from the look-up to the publication, and a buffer
+// is published only after the stream that built it has been synchronised — exactly one survives and nobody reads it early.
+const void* scan_cache_get(const DeviceBatch& b, size_t c, ScanForm form, hipStream_t stream);
 
 // FDB_ERR_UNSUPPORTED, naming `what`, if a column of `in` (rows > 0) is of a type the resident record cannot hold.
 void require_values(const DeviceBatch& in, const char* what);

@@ -176,18 +176,18 @@ int main(int argc0, char** argv0) {
       s.aggs = {{FDB_AGG_SUM, FDB_T_F64, 0, 0}, {FDB_AGG_MIN, FDB_T_F64, 0, 0}};
     }
     if (argc > 3 && std::string(argv[3]) == "narrow") {  // narrow-index caches: the filter column read at 1 byte, the group column at 2
-      s.c4[0].width = 1;
-      (s.two_phase ? s.l4[0] : s.c4[1]).width = 2;
+      s.c4[0].form = fdb::kScanForm1;
+      (s.two_phase ? s.l4[0] : s.c4[1]).form = fdb::kScanForm2;
       s.quad = true;  // (what jit_shape sets for a launch with a narrow slot)
     }
     if (argc > 3 && std::string(argv[3]) == "packed") {  // packed index caches in the place of `narrow`: the filter column at 4 bits (form H), the group column at 12 (form T)
-      s.c4[0].width = fdb::kJitWidthH;
-      (s.two_phase ? s.l4[0] : s.c4[1]).width = fdb::kJitWidthT;
+      s.c4[0].form = fdb::kScanFormH;
+      (s.two_phase ? s.l4[0] : s.c4[1]).form = fdb::kScanFormT;
       s.quad = true;
     }
     if (cfg3 && s.two_phase) {  // plan two [narrow …] cfg3: two more early slots and leaves, AND-ed
       s.n_c4 = 3;
-      s.c4[1].has_values = true; s.c4[1].has_validity = 1; s.c4[1].width = s.c4[0].width;
+      s.c4[1].has_values = true; s.c4[1].has_validity = 1; s.c4[1].form = s.c4[0].form;
       s.c4[2].has_values = false; s.c4[2].has_validity = 1;
       fdb::JitLeaf b; b.kind = FDB_LEAF_DICT_BITS; b.slot = 1; b.wide = 0;
       fdb::JitLeaf c; c.kind = FDB_LEAF_VALIDITY; c.slot = 2; c.wide = 0;
