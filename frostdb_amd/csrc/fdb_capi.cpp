@@ -189,6 +189,69 @@ int fdb_selftest_scan_cache_packed(const uint32_t* indices, const uint8_t* valid
   });
 }
 
+// The device prefix sums, each launch sequence as the library runs it (scratch at the sizes fdb_kernels.h documents), over a caller's array.
+int fdb_selftest_prefix_sums(int32_t kind, int device, const uint32_t* in, int64_t n, int32_t option, const int64_t* recs, int32_t n_recs, uint32_t* out,
+                             uint64_t* totals) {
+  return guard(nullptr, [&] {
+    const int64_t max_n = (int64_t)1 << 28;
+    const int64_t stride = kind == 2 ? option : 1;
+    if (kind < 0 || kind > 2 || n < 0 || n > max_n || totals == nullptr || (n > 0 && (in == nullptr || out == nullptr)))
+      throw fdb::Error(FDB_ERR_INVALID, "prefix sums: kind 0, 1 or 2, 0 to 2^28 entries, non-null buffers");
+    if (kind == 0 && option != 0 && option != 1) throw fdb::Error(FDB_ERR_INVALID, "prefix sums: exclusive scan takes option 0 (block sums) or 1 (none)");
+    if (kind == 2 && (stride < 1 || stride > 16 || n * stride > max_n)) throw fdb::Error(FDB_ERR_INVALID, "prefix sums: strided scan takes a stride of 1 to 16, 2^28 words in all");
+    if (kind != 1 && (recs != nullptr || n_recs != 0)) throw fdb::Error(FDB_ERR_INVALID, "prefix sums: a record table goes with kind 1 only");
+    if (kind == 1) {
+      if (option < 0 || option > 2 || n < 1 || recs == nullptr || n_recs < 1 || n_recs > n)
+        throw fdb::Error(FDB_ERR_INVALID, "prefix sums: filter scan takes option 0 (as filter() chooses), 1 (one level) or 2 (two levels), tiles and their records");
+      // the table as filter() builds it: records with rows only, each owning the tiles of its rows, end to end from tile 0
+      for (int32_t r = 0; r < n_recs; r++) {
+        const int64_t begin = recs[2 * r], rows = recs[2 * r + 1], end = r + 1 < n_recs ? recs[2 * r + 2] : n;
+        if (begin < 0 || begin >= n || (r == 0 && begin != 0) || rows < 1 || rows > max_n * FDB_COMPACT_TILE || begin + (rows + FDB_COMPACT_TILE - 1) / FDB_COMPACT_TILE != end)
+          throw fdb::Error(FDB_ERR_INVALID, "prefix sums: record " + std::to_string(r) + " does not own the tiles of its rows, after its predecessor's");
+      }
+    }
+    fdb::CallScope call(device);
+    const hipStream_t stream = call.ctx->stream;
+    const int64_t n_blocks = (n + 1023) / 1024;
+    const size_t n_totals = kind == 1 ? (size_t)n_recs + 1 : 1;
+    unsigned long long* d_totals = (unsigned long long*)call.alloc(n_totals * 8 + 64);
+    // (what a launch leaves unwritten reads 0xA5… afterwards)
+    fdb::hip_check(hipMemsetAsync(d_totals, 0xA5, n_totals * 8, stream), "prefix sums: fill");
+    uint32_t* d_out = nullptr;
+    if (kind == 0) {
+      uint32_t* d_counts = (uint32_t*)call.alloc((size_t)n * 4 + 256);
+      uint32_t* d_block_sums = option == 0 ? (uint32_t*)call.alloc(((size_t)n_blocks + 1) * 4) : nullptr;
+      if (n > 0) fdb::hip_check(hipMemcpyAsync(d_counts, in, (size_t)n * 4, hipMemcpyHostToDevice, stream), "prefix sums: copy in");
+      fdb::hip_check(fdb_launch_exclusive_scan(d_counts, n, d_block_sums, d_totals, stream), "prefix sums: exclusive scan");
+      d_out = d_counts;
+    } else if (kind == 1) {
+      // block sums in front of the tile counts, as count_rows_two_pass lays them out
+      unsigned char* d_counts = (unsigned char*)call.alloc((size_t)n_blocks * 8 + (size_t)n * 4 + 256);
+      unsigned long long* d_block_sums = (unsigned long long*)d_counts;
+      uint32_t* d_tile_counts = (uint32_t*)(d_counts + (size_t)n_blocks * 8);
+      d_out = (uint32_t*)call.alloc((size_t)n * 4 + 256);
+      FdbCompactRec* d_recs = (FdbCompactRec*)call.alloc((size_t)n_recs * sizeof(FdbCompactRec));
+      static_assert(sizeof(FdbCompactRec) == 16, "the record table crosses the C ABI as pairs of int64");
+      fdb::hip_check(hipMemcpyAsync(d_tile_counts, in, (size_t)n * 4, hipMemcpyHostToDevice, stream), "prefix sums: copy in");
+      fdb::hip_check(hipMemcpyAsync(d_recs, recs, (size_t)n_recs * sizeof(FdbCompactRec), hipMemcpyHostToDevice, stream), "prefix sums: copy in");
+      fdb::hip_check(hipMemsetAsync(d_out, 0xA5, (size_t)n * 4, stream), "prefix sums: fill");
+      const bool two_level = option == 0 ? fdb_sel_scan_two_level(n) : option == 2;
+      if (two_level) fdb::hip_check(fdb_launch_sel_block_sums(d_tile_counts, n, d_block_sums, stream), "prefix sums: block sums");
+      fdb::hip_check(fdb_launch_sel_scan(d_tile_counts, two_level ? d_block_sums : nullptr, n, d_out, d_recs, n_recs, d_totals, stream), "prefix sums: filter scan");
+    } else {
+      uint32_t* d_in = (uint32_t*)call.alloc((size_t)(n * stride) * 4 + 256);
+      d_out = (uint32_t*)call.alloc((size_t)n * 4 + 256);
+      unsigned long long* d_scratch = (unsigned long long*)call.alloc(((size_t)n / 1024 + 2) * 8);
+      if (n > 0) fdb::hip_check(hipMemcpyAsync(d_in, in, (size_t)(n * stride) * 4, hipMemcpyHostToDevice, stream), "prefix sums: copy in");
+      if (n > 0) fdb::hip_check(hipMemsetAsync(d_out, 0xA5, (size_t)n * 4, stream), "prefix sums: fill");
+      fdb::hip_check(fdb_launch_scan_u32(d_in, (int)stride, d_out, n, d_scratch, d_totals, stream), "prefix sums: strided scan");
+    }
+    if (n > 0) fdb::hip_check(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, stream), "prefix sums: copy out");
+    fdb::hip_check(hipMemcpyAsync(totals, d_totals, n_totals * 8, hipMemcpyDeviceToHost, stream), "prefix sums: copy out");
+    fdb::hip_check(hipStreamSynchronize(stream), "prefix sums: wait");
+  });
+}
+
 int fdb_selftest_exact_sum(const double* x, int64_t n, double* out) {
   return guard(nullptr, [&] {
     if (n < 0 || out == nullptr || (n > 0 && x == nullptr)) throw fdb::Error(FDB_ERR_INVALID, "exact sum: n >= 0 and non-null buffers");

@@ -492,7 +492,7 @@ void Plan::FilterRun::count_rows_two_pass(int64_t grid, unsigned long long* h_ba
   P.scratch_.push_back(d_counts); P.scratch_.push_back(d_rec_base);
   unsigned long long* d_block_sums = (unsigned long long*)d_counts;
   uint32_t* d_tile_counts = (uint32_t*)(d_counts + (size_t)n_blocks * 8);
-  const bool two_level = n_blocks > 64;  // (below that every scan workgroup adds up the counts in front of its block itself)
+  const bool two_level = fdb_sel_scan_two_level(total_tiles);  // (below that every scan workgroup adds up the counts in front of its block itself)
   P.timed([&] {
     hip_check(jit_flags_launch(flags_fn, d_parts, (int)parts.size(), total_super, parts[0], (int)grid, lut_lds_max, d_masks, d_tile_counts, stream), "flags launch");
     if (two_level) hip_check(fdb_launch_sel_block_sums(d_tile_counts, total_tiles, d_block_sums, stream), "block sums launch");

@@ -796,6 +796,8 @@ struct FdbZeroRegion { void* ptr; int64_t bytes; };  // 16-byte aligned, a multi
 // offsets[t] = Σ tile_counts[< t] (mod 2^32), rec_base[r] = the same sum in full at record r's first tile, rec_base[n_recs] = the
 // grand total. block_sums[b] = Σ tile_counts[1024 b …) (fdb_launch_sel_block_sums; nullptr: every workgroup adds up the counts in
 // front of its block itself — cheaper than a launch while there are only a few dozen blocks).
+// fdb_sel_scan_two_level: whether filter() runs fdb_launch_sel_block_sums first — beyond 64 scan workgroups (65 536 tiles).
+static inline bool fdb_sel_scan_two_level(int64_t total_tiles) { return (total_tiles + 1023) / 1024 > 64; }
 hipError_t fdb_launch_sel_scan(const uint32_t* tile_counts, const unsigned long long* block_sums, int64_t total_tiles, uint32_t* offsets, const FdbCompactRec* recs,
                                int n_recs, unsigned long long* rec_base, hipStream_t stream);
 hipError_t fdb_launch_sel_block_sums(const uint32_t* tile_counts, int64_t total_tiles, unsigned long long* block_sums, hipStream_t stream);

@@ -1306,18 +1306,30 @@ __global__ __launch_bounds__(256) void scan_block_sums_kernel(const uint32_t* __
   __syncthreads();
   if (threadIdx.x == 0) sums[blockIdx.x] = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
 }
-__global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ counts, int64_t n, const uint32_t* __restrict__ block_offsets) {
+// The block sums are 32-bit, so the `total` step 2 added up from them lacks what a block's own counts carried past bit 32: this
+// launch adds it. (Counts below 2^22 — selected rows of a tile, entries of a chunk, bits of a word — cannot carry: nothing extra runs.)
+__global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ counts, int64_t n, const uint32_t* __restrict__ block_offsets,
+                                                         unsigned long long* __restrict__ total) {
   __shared__ unsigned int wave_sum[4];
+  __shared__ unsigned long long wide_sum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t i0 = (int64_t)blockIdx.x * 1024 + (int64_t)threadIdx.x * 4;
-  uint32_t v[4], s = 0;
+  uint32_t v[4], s = 0, big = 0;
 #pragma unroll
-  for (int k = 0; k < 4; k++) { v[k] = i0 + k < n ? counts[i0 + k] : 0u; s += v[k]; }
+  for (int k = 0; k < 4; k++) { v[k] = i0 + k < n ? counts[i0 + k] : 0u; s += v[k]; big |= v[k]; }
   uint32_t incl = s;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
   if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
+  if (__syncthreads_or((int)(big >> 22))) {  // (1 024 counts below 2^22 stay below 2^32)
+    unsigned long long wide = (unsigned long long)v[0] + v[1] + v[2] + v[3];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wide += (unsigned long long)__shfl_xor((long long)wide, o, 64);
+    if (lane == 0) wide_sum[wave] = wide;
+    __syncthreads();
+    const unsigned long long carried = (wide_sum[0] + wide_sum[1] + wide_sum[2] + wide_sum[3]) >> 32;
+    if (threadIdx.x == 0 && carried != 0ull) atomicAdd(total, carried << 32);
+  }
   uint32_t run = block_offsets[blockIdx.x] + incl - s;
   for (int w = 0; w < wave; w++) run += wave_sum[w];
 #pragma unroll
@@ -2559,7 +2571,7 @@ hipError_t fdb_launch_exclusive_scan(uint32_t* counts, int64_t n, uint32_t* bloc
   const int64_t n_blocks = (n + 1023) / 1024;
   hipLaunchKernelGGL(scan_block_sums_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, counts, n, block_sums);
   hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(FDB_BLOCK), 0, stream, block_sums, n_blocks, total);
-  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, counts, n, block_sums);
+  hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, counts, n, block_sums, total);
   return hipGetLastError();
 }
 

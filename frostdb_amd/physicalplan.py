@@ -112,6 +112,7 @@ def lib() -> ctypes.CDLL:
     L.fdb_selftest_scan_cache.argtypes = [vp, i64, i32, ctypes.c_int, vp, i64]
     L.fdb_selftest_scan_cache_nulls.argtypes = [vp, vp, i64, i64, i32, ctypes.c_int, vp, i64]
     L.fdb_selftest_scan_cache_packed.argtypes = [vp, vp, i64, i64, i32, ctypes.c_int, vp, i64]
+    L.fdb_selftest_prefix_sums.argtypes = [i32, ctypes.c_int, vp, i64, i32, vp, i32, vp, vp]
     L.fdb_plan_explain.argtypes = [vp, ctypes.c_char_p, i64, P(i64)]
     L.fdb_plan_last_kernel.restype = ctypes.c_char_p
     L.fdb_comm_unique_id.argtypes = [vp]
@@ -260,6 +261,28 @@ def selftest_exact_sum(values) -> float:
     if rc != FDB_OK:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
     return out.value
+
+
+PREFIX_EXCLUSIVE_SCAN, PREFIX_FILTER_SCAN, PREFIX_STRIDED_SCAN = 0, 1, 2
+
+
+def selftest_prefix_sums(kind: int, counts, option: int = 0, recs=None, device: int = 0):
+    """One of the library's device prefix sums over `counts` (uint32), run as the library runs it (fdb_selftest_prefix_sums).
+    PREFIX_EXCLUSIVE_SCAN: `option` 1 withholds the block-sum scratch; PREFIX_FILTER_SCAN: `recs` is the record table, (first tile,
+    rows) per record, `option` 0 / 1 / 2 = levels as filter() chooses / one / two; PREFIX_STRIDED_SCAN: `option` is the stride and
+    `counts` holds n x stride words. Returns (uint32 prefix array, uint64 totals: [sum], or rec_base[n_recs + 1] for the filter scan)."""
+    import numpy as np
+    a = np.ascontiguousarray(counts, dtype=np.uint32)
+    n = len(a) // int(option) if kind == PREFIX_STRIDED_SCAN and int(option) >= 1 else len(a)
+    table = np.ascontiguousarray(recs, dtype=np.int64).reshape(-1, 2) if recs is not None else None
+    out = np.empty(max(n, 1), dtype=np.uint32)
+    totals = np.empty(len(table) + 1 if table is not None else 1, dtype=np.uint64)
+    rc = lib().fdb_selftest_prefix_sums(int(kind), int(device), a.ctypes.data if len(a) else None, n, int(option),
+                                        table.ctypes.data if table is not None and len(table) else None, len(table) if table is not None else 0,
+                                        out.ctypes.data, totals.ctypes.data)
+    if rc != FDB_OK:
+        _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
+    return out[:n], totals
 
 
 def selftest_reservoir(seed: int, size: int, record_rows: Sequence[int]) -> List[int]:

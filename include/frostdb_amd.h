@@ -259,6 +259,20 @@ FDB_API int fdb_selftest_scan_cache_nulls(const uint32_t* indices, const uint8_t
  * of `validity` is clear) when `validity` is given — and copies its whole frames, ceil(rows / 1024) x 512 or 1 536 bytes, to `out`. */
 FDB_API int fdb_selftest_scan_cache_packed(const uint32_t* indices, const uint8_t* validity, int64_t rows, int64_t entries, int32_t form, int device, uint8_t* out,
                                            int64_t out_bytes);
+/* Self-check of the device prefix sums: uploads `in`, runs ONE of the library's three launch sequences on `device` exactly as the
+ * library runs it (scratch buffers at the sizes the launchers document) and copies the results out. Exclusive prefix sums of 32-bit
+ * counts, modulo 2^32 in `out`, in full in `totals`. 0 <= n <= 2^28.
+ *   kind 0: the in-place exclusive scan (interpreting filter(), hash Finish, Parquet rank scan) of in[n]. `option` 0: with its block-sum
+ *           scratch (one workgroup up to n = 4 096, three launches beyond); 1: without (one workgroup at any n). out[n], totals[0] = the sum.
+ *   kind 1: filter()'s step over in[n] selected-row counts per tile (n >= 1) and the record table `recs` — n_recs pairs {first tile,
+ *           rows}, records with rows only, each owning the tiles of its rows, end to end from tile 0. `option` 0: one or two levels as
+ *           filter() chooses; 1: one level; 2: two levels (block sums first). out[n] = every tile's offset, totals[n_recs + 1] = the sum
+ *           in front of every record's first tile, then the grand total.
+ *   kind 2: the strided scan (run-store Finish) of in[i x stride], i < n; `option` = stride, 1 to 16, `in` holds n x stride words.
+ *           out[n], totals[0] = the sum.
+ * `recs` NULL and n_recs 0 for kinds 0 and 2. FDB_ERR_INVALID, before anything is launched, for arguments outside these rules. */
+FDB_API int fdb_selftest_prefix_sums(int32_t kind, int device, const uint32_t* in, int64_t n, int32_t option, const int64_t* recs, int32_t n_recs, uint32_t* out,
+                                     uint64_t* totals);
 
 /* ---- plan life cycle (≙ physicalplan.Build for one chain, physicalplan.go:417-474) -------------- */
 /* `desc` and everything it points at (expression nodes, names, literals, patterns) is copied: the caller may free it as soon

@@ -397,6 +397,36 @@ def test_every_entry_point_has_a_typed_binding(built_lib):
             assert fn.restype is not ctypes.c_int, name
 
 
+def test_prefix_sum_selftest_checks_its_arguments_before_any_device_call(built_lib):
+    """fdb_selftest_prefix_sums is declared, exported and bound, and answers arguments outside its rules with FDB_ERR_INVALID before it
+    touches a device: on a machine without one a valid call gets as far as the device and says so, an invalid one never does."""
+    import numpy as np
+    from frostdb_amd import physicalplan as pp
+    assert "fdb_selftest_prefix_sums" in declared_functions()
+    assert hasattr(built_lib, "fdb_selftest_prefix_sums") and pp.lib().fdb_selftest_prefix_sums.argtypes is not None
+    counts = np.ones(4096, dtype=np.uint32)
+
+    def code(*args):
+        try:
+            pp.selftest_prefix_sums(*args)
+        except pp.FdbError as e:
+            return e.code
+        return pp.FDB_OK
+
+    tile = 2048
+    for args in [(3, counts), (-1, counts), (pp.PREFIX_EXCLUSIVE_SCAN, counts, 2), (pp.PREFIX_EXCLUSIVE_SCAN, counts, 0, [(0, 1)]),
+                 (pp.PREFIX_STRIDED_SCAN, counts, 0), (pp.PREFIX_STRIDED_SCAN, counts, 17),
+                 (pp.PREFIX_FILTER_SCAN, counts, 3, [(0, 4096 * tile)]), (pp.PREFIX_FILTER_SCAN, counts, 0),
+                 (pp.PREFIX_FILTER_SCAN, counts, 0, [(1, 4095 * tile)]), (pp.PREFIX_FILTER_SCAN, counts, 0, [(0, 4095 * tile)]),
+                 (pp.PREFIX_FILTER_SCAN, counts, 0, [(0, tile), (2, 4094 * tile)]), (pp.PREFIX_FILTER_SCAN, counts, 0, [(0, 4096 * tile), (4096, 0)]),
+                 (pp.PREFIX_FILTER_SCAN, counts, 0, [(0, tile), (2**62, 2**62)]), (pp.PREFIX_FILTER_SCAN, counts[:0], 0, [(0, 1)])]:
+        assert code(*args) == pp.FDB_ERR_INVALID, args
+    if pp.device_count() == 0:
+        for args in [(pp.PREFIX_EXCLUSIVE_SCAN, counts), (pp.PREFIX_STRIDED_SCAN, counts, 2),
+                     (pp.PREFIX_FILTER_SCAN, counts, 0, [(0, 4095 * tile + 1)]), (pp.PREFIX_FILTER_SCAN, counts, 2, [(0, tile), (1, 4095 * tile)])]:
+            assert code(*args) == pp.FDB_ERR_DEVICE, args
+
+
 def test_arrow_roundtrip_random_shapes(built_lib):
     """Randomised: column types, lengths 0 … 300, NULL densities 0 … 1, arbitrary slices (bit-unaligned validity and bool
     offsets, dictionary and string offsets), dictionaries with unused and duplicate entries."""
