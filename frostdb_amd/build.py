@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfrostdb_amd.so")
-SOURCES = ["fdb_kernels.hip", "fdb_codec.hip", "fdb_merge.hip", "fdb_sort.hip", "fdb_take.hip", "fdb_sortkeys.hip", "fdb_mergepath.hip", "fdb_pqwrite.hip", "fdb_pqdelta.hip", "fdb_pqruns.hip", "fdb_pqsnappy.hip", "fdb_pqlz4.hip", "fdb_pqstats.hip", "fdb_pqbloom.hip", "fdb_pqdict.hip", "fdb_arrow.cpp", "fdb_context.cpp", "fdb_plan.cpp", "fdb_dense.cpp", "fdb_record.cpp", "fdb_filter.cpp", "fdb_project.cpp", "fdb_take.cpp", "fdb_sort.cpp", "fdb_mergerec.cpp", "fdb_hash.cpp", "fdb_jit.cpp", "fdb_jitgen.cpp", "fdb_dynamic.cpp", "fdb_comm.cpp", "fdb_parquet.cpp", "fdb_pqwrite.cpp", "fdb_codec.cpp", "fdb_widen.cc", "fdb_regex.cpp", "fdb_capi.cpp"]
-HEADERS = ["fdb_kernels.h", "fdb_arrow.h", "fdb_context.h", "fdb_plan.h", "fdb_plan_internal.h", "fdb_launch_plan.h", "fdb_record.h", "fdb_codec.h", "fdb_jit.h", "fdb_comm.h", "fdb_dynamic.h", "fdb_regex.h", "fdb_take.h", "fdb_sort.h", "fdb_sortkey.h", "fdb_sortplan.h", "fdb_mergepath.h", "fdb_mergerec.h", "fdb_reservoir.h", "fdb_pqwrite.h", "fdb_pqdelta.h", "fdb_pqruns.h", "fdb_pqsnappy.h", "fdb_pqlz4.h", "fdb_pqstats.h", "fdb_pqbloom.h", "fdb_pqdict.h", "fdb_pqwrite_host.h", "fdb_hostpool.h", "fdb_unicode_tables.inc", "exports.map", "../../include/frostdb_amd.h", "../../include/arrow_c_data.h"]
+SOURCES = ["fdb_kernels.hip", "fdb_codec.hip", "fdb_merge.hip", "fdb_sort.hip", "fdb_take.hip", "fdb_sortkeys.hip", "fdb_mergepath.hip", "fdb_pqwrite.hip", "fdb_pqdelta.hip", "fdb_pqruns.hip", "fdb_pqsnappy.hip", "fdb_pqlz4.hip", "fdb_pqstats.hip", "fdb_pqbloom.hip", "fdb_pqdict.hip", "fdb_pqbytes.hip", "fdb_arrow.cpp", "fdb_context.cpp", "fdb_plan.cpp", "fdb_dense.cpp", "fdb_record.cpp", "fdb_filter.cpp", "fdb_project.cpp", "fdb_take.cpp", "fdb_sort.cpp", "fdb_mergerec.cpp", "fdb_hash.cpp", "fdb_jit.cpp", "fdb_jitgen.cpp", "fdb_dynamic.cpp", "fdb_comm.cpp", "fdb_parquet.cpp", "fdb_pqwrite.cpp", "fdb_codec.cpp", "fdb_widen.cc", "fdb_regex.cpp", "fdb_capi.cpp"]
+HEADERS = ["fdb_kernels.h", "fdb_arrow.h", "fdb_context.h", "fdb_plan.h", "fdb_plan_internal.h", "fdb_launch_plan.h", "fdb_record.h", "fdb_codec.h", "fdb_jit.h", "fdb_comm.h", "fdb_dynamic.h", "fdb_regex.h", "fdb_take.h", "fdb_sort.h", "fdb_sortkey.h", "fdb_sortplan.h", "fdb_mergepath.h", "fdb_mergerec.h", "fdb_reservoir.h", "fdb_pqwrite.h", "fdb_pqdelta.h", "fdb_pqruns.h", "fdb_pqsnappy.h", "fdb_pqlz4.h", "fdb_pqstats.h", "fdb_pqbloom.h", "fdb_pqdict.h", "fdb_pqbytes.h", "fdb_pqwrite_host.h", "fdb_hostpool.h", "fdb_unicode_tables.inc", "exports.map", "../../include/frostdb_amd.h", "../../include/arrow_c_data.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-result",
          "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 

@@ -345,6 +345,15 @@ const std::vector<int32_t>& HostDict::arrow_offsets() const {
   return arrow_offsets_;
 }
 
+const std::string& HostDict::joined() const {
+  if (lens.size() == values.size() && (size_t)(uint32_t)arrow_offsets().back() == concat.size()) return concat;
+  std::call_once(joined_once_, [this] {
+    joined_.reserve((size_t)(uint32_t)arrow_offsets().back());
+    for (const std::string& v : values) joined_ += v;
+  });
+  return joined_;
+}
+
 const std::vector<uint32_t>& HostDict::sorted_ranks() const {
   std::call_once(ranks_once_, [this] {
     std::vector<uint32_t> order(values.size());

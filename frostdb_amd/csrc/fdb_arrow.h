@@ -44,11 +44,16 @@ struct HostDict {
   // group columns: ≈ 4 ms of every Finish before.
   const std::vector<int32_t>& arrow_offsets() const;
   const std::vector<uint32_t>& sorted_ranks() const;
+  // … and the entries' bytes laid end to end, for arrow_offsets() to point into: `concat` where the dictionary keeps it, else — the
+  // dictionary of a plain string / binary column (encode_plain, make_plain_dictionary), which keeps neither `lens` nor `concat` — joined
+  // on first use and kept with the dictionary (the Parquet writer's entry tables, fdb_pqbytes.h).
+  const std::string& joined() const;
   bool utf8() const { return value_format == "u" || value_format == "U"; }
   bool same_content(const HostDict& o) const { return hash == o.hash && plain == o.plain && values == o.values; }
 
  private:
-  mutable std::once_flag offsets_once_, ranks_once_;
+  mutable std::once_flag offsets_once_, ranks_once_, joined_once_;
+  mutable std::string joined_;
   mutable std::vector<int32_t> arrow_offsets_;
   mutable std::vector<uint32_t> sorted_ranks_;
 };

@@ -908,6 +908,19 @@ int fdb_selftest_parquet_write_grouped(struct ArrowArray* batch, struct ArrowSch
   return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs, groups}, bytes, n_bytes);
 }
 
+int fdb_batch_to_parquet_strings(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs,
+                                 const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom, const fdb_parquet_run_options* runs,
+                                 const fdb_parquet_group_options* groups, const fdb_parquet_string_options* strings, uint8_t** bytes, int64_t* n_bytes) {
+  return write_resident(batch, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs, groups, strings}, bytes, n_bytes);
+}
+
+int fdb_selftest_parquet_write_strings(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings,
+                                       const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index, const fdb_parquet_bloom_options* bloom,
+                                       const fdb_parquet_run_options* runs, const fdb_parquet_group_options* groups, const fdb_parquet_string_options* strings, uint8_t** bytes,
+                                       int64_t* n_bytes) {
+  return write_selftest(batch, schema, fdb::PqwSpec{options, encodings, n_encodings, codecs, n_codecs, index, bloom, runs, groups, strings}, bytes, n_bytes);
+}
+
 int fdb_batches_from_parquet(const fdb_parquet_row_group* groups, int32_t n_groups, int device, fdb_batch** out) {
   return guard(nullptr, [&] {
     if (out == nullptr || n_groups <= 0) throw fdb::Error(FDB_ERR_INVALID, "null output");

@@ -6,7 +6,7 @@
 // payload. Every entry point fills a PqwSpec with the arguments it has (null / 0: not asked) and runs ONE pipeline; a pass in
 // [brackets] runs only when asked for, and without it launches, allocations and copies are those of the narrower call.
 //   plan     pqw_plan: options and columns checked, every refusal made — in the parameters' order: write options and columns, index,
-//            bloom, runs, groups — before anything is launched; the columns' modes and ranks (statistics) and the entry hashes of the filtered
+//            bloom, runs, groups, strings — before anything is launched; the columns' modes and ranks (statistics) and the entry hashes of the filtered
 //            index columns (entry_hashes, fdb_sortplan.h) prepared. A record without rows or columns ends here, on the host.
 //   survey   pqw_survey_kernel: per (column, page) the non-NULL rows and, of index columns, the smallest and largest index; per tile
 //            the rank of its first value. Only the per-page table comes back. Behind it, their tables back in the SAME wait:
@@ -22,6 +22,11 @@
 //                        (pqg_resolve) and a remap pass writes a re-keyed copy of every pruned index column, which IS the column for
 //                        every later pass but the bloom insert; the run passes, which need the new width, then follow it and are
 //                        waited for once more.
+//            [strings]   a dictionary / string / binary column written with a FORM (fdb_parquet_string_options; rule: fdb_pqbytes.h) has no
+//                        dictionary page: its pages hold the non-NULL values themselves, PLAIN or DELTA_LENGTH_BYTE_ARRAY. fdb_pqbytes.hip
+//                        sums the entry lengths of every tile's non-NULL rows (the host scans the sums into page sizes and per-tile byte
+//                        bases) and writes a DELTA_LENGTH column's lengths in rank order as one more column of the DELTA passes. After the
+//                        layout a byte encode pass gathers the values from the entry tables, by output position.
 //   layout   pqw_layout (host): with these tables every page's size is known, so every payload's file offset is; every DELTA and run
 //            size is held to its rule's bounds first. The survey's table sizes the bloom filters (pqb_size). Pages are folded into
 //            chunk bounds, keys mapped back (a rank to an entry), the zero rule, the cut of BYTE_ARRAY bounds, the boundary order, the
@@ -106,7 +111,7 @@ struct Thrift {
 };
 
 enum { PT_BOOLEAN = 0, PT_INT64 = 2, PT_DOUBLE = 5, PT_BYTE_ARRAY = 6 };
-enum { ENC_PLAIN = 0, ENC_RLE = 3, ENC_DELTA_BINARY_PACKED = 5, ENC_RLE_DICTIONARY = 8 };
+enum { ENC_PLAIN = 0, ENC_RLE = 3, ENC_DELTA_BINARY_PACKED = 5, ENC_DELTA_LENGTH_BYTE_ARRAY = 6, ENC_RLE_DICTIONARY = 8 };
 enum { PAGE_DATA = 0, PAGE_DICTIONARY = 2 };
 
 std::string page_header(int type, int64_t body, int64_t compressed, int64_t num_values, int encoding) {
@@ -174,9 +179,9 @@ std::string footer(const std::vector<ChunkMeta>& chunks, size_t n_cols, const st
     t.i64(2, m.dict_off >= 0 ? m.dict_off : m.data_off);
     t.open(3);  // ColumnMetaData
     t.i32(1, c.physical);
-    const bool dict = c.pq_kind == FDB_PQW_INDEX;
+    const bool dict = c.pq_kind == FDB_PQW_INDEX && c.form == 0;  // (a form: the values are in the pages, PLAIN or DELTA_LENGTH_BYTE_ARRAY)
     t.list(2, Thrift::T_I32, 1 + (c.optional ? 1 : 0) + (dict ? 1 : 0));  // (RLE: the definition levels, which a required column does not have)
-    t.zigzag(c.delta_slot >= 0 ? ENC_DELTA_BINARY_PACKED : ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
+    t.zigzag(c.form == FDB_PQY_DELTA_LENGTH ? ENC_DELTA_LENGTH_BYTE_ARRAY : c.delta_slot >= 0 ? ENC_DELTA_BINARY_PACKED : ENC_PLAIN); if (c.optional) t.zigzag(ENC_RLE); if (dict) t.zigzag(ENC_RLE_DICTIONARY);
     t.list(3, Thrift::T_BINARY, 1); t.str(c.name);
     t.i32(4, c.codec);  // 0 UNCOMPRESSED, 1 SNAPPY, 7 LZ4_RAW
     t.i64(5, rows);
@@ -674,9 +679,8 @@ static void pqb_prepare(const std::vector<PqwColumn>& cols, PqbPlan* b) {
 }
 
 // ---- used-entry dictionaries: the host's half of the present and remap passes (fdb_pqdict.h) ---------------------------------------------
-PqgPlan pqg_plan(const fdb_parquet_group_options* groups, int64_t rows, std::vector<PqwColumn>* cols) {
-  PqgPlan d;
-  if (groups == nullptr) return d;
+void pqg_check(const fdb_parquet_group_options* groups, int64_t rows) {
+  if (groups == nullptr) return;
   const int64_t R = groups->row_group_rows;
   if (R < 0 || R % 64 != 0) throw Error(FDB_ERR_INVALID, "parquet write: row_group_rows must be a multiple of 64 (0: one row group), got " + std::to_string(R));
   const int64_t n_groups = R > 0 && rows > 0 ? (rows - 1) / R + 1 : 1;
@@ -685,10 +689,16 @@ PqgPlan pqg_plan(const fdb_parquet_group_options* groups, int64_t rows, std::vec
   if (groups->dictionaries < 0 || groups->dictionaries > 1)
     throw Error(FDB_ERR_INVALID, "parquet write: dictionaries is " + std::to_string(groups->dictionaries) + " (0 the whole dictionary, 1 the used entries only)");
   if (groups->pad != 0) throw Error(FDB_ERR_INVALID, "parquet write: the group options' pad is " + std::to_string(groups->pad) + " (0)");
+}
+
+PqgPlan pqg_plan(const fdb_parquet_group_options* groups, int64_t rows, std::vector<PqwColumn>* cols) {
+  PqgPlan d;
+  pqg_check(groups, rows);
+  if (groups == nullptr) return d;
   uint64_t words = 0;
   for (size_t k = 0; k < cols->size() && groups->dictionaries == 1; k++) {
     PqwColumn& c = (*cols)[k];
-    if (c.pq_kind != FDB_PQW_INDEX) continue;  // (an empty dictionary has nothing to prune)
+    if (c.pq_kind != FDB_PQW_INDEX || c.form != 0) continue;  // (an empty dictionary has nothing to prune, a column with a form no dictionary page)
     c.used_slot = (int)d.cols.size();
     PqgPlan::Col o;
     o.col = k; o.entries = c.entries; o.word_off = words; o.words = fdb_pqg_words(c.entries);
@@ -756,6 +766,118 @@ void pqg_remap_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, con
   }
 }
 
+// ---- value pages of BYTE_ARRAY columns: the host's half of the byte passes (fdb_pqbytes.h) ------------------------------------------------
+size_t pqy_plan(const fdb_parquet_string_options* strings, const fdb_parquet_run_options* runs, std::vector<PqwColumn>* cols, PqyPlan* y) {
+  if (strings == nullptr) return 0;
+  if (strings->n_columns != 0 && (strings->n_columns != (int32_t)cols->size() || strings->forms == nullptr))
+    throw Error(FDB_ERR_INVALID, "parquet write: the string options' `forms` has " + std::to_string(strings->n_columns) + " entries, the record " + std::to_string(cols->size()) + " columns");
+  for (int32_t k = 0; k < strings->n_columns; k++) {
+    const int e = (int)strings->forms[k];
+    if (e < 0 || e > 2) throw Error(FDB_ERR_INVALID, "parquet write: string options forms[" + std::to_string(k) + "] is " + std::to_string(e) + " (0 as ever, 1 PLAIN, 2 DELTA_LENGTH_BYTE_ARRAY)");
+  }
+  if (strings->pad != 0) throw Error(FDB_ERR_INVALID, "parquet write: the string options' pad is " + std::to_string(strings->pad) + " (0)");
+  for (int32_t k = 0; k < strings->n_columns; k++) {
+    const PqwColumn& c = (*cols)[(size_t)k];
+    if (strings->forms[k] == 0) continue;
+    const char* form = strings->forms[k] == FDB_PQY_PLAIN ? "PLAIN" : "DELTA_LENGTH_BYTE_ARRAY";
+    if (c.pq_kind != FDB_PQW_INDEX && c.pq_kind != PQW_NO_VALUES)
+      throw Error(FDB_ERR_UNSUPPORTED, std::string("parquet write: ") + form + " value pages are for dictionary and string / binary columns; column " + c.name + " is not one");
+    if (runs != nullptr && k < runs->n_columns && (runs->columns[k] & 1) != 0)
+      throw Error(FDB_ERR_UNSUPPORTED, "parquet write: runs of dictionary indices are asked for column " + c.name + ", which is written " + form + " and has no index pages");
+  }
+  size_t next = 0, deltas = pqw_delta_columns(*cols);
+  y->tables.assign(cols->size(), nullptr);
+  for (int32_t k = 0; k < strings->n_columns; k++) {
+    PqwColumn& c = (*cols)[(size_t)k];
+    c.form = (int)strings->forms[k];
+    if (c.form == 0) continue;
+    if (c.pq_kind == PQW_NO_VALUES) {  // all NULL over an empty dictionary: PLAIN pages of zero values are its form already; pages of zero lengths are the host's
+      if (c.form == FDB_PQY_PLAIN) c.form = 0;
+      continue;
+    }
+    c.bytes_slot = (int)next++;
+    if (c.form == FDB_PQY_DELTA_LENGTH) c.delta_slot = (int)deltas++;  // the lengths: one more column of the DELTA passes
+    auto t = std::make_shared<PqyTables>();
+    const std::vector<int32_t>& offsets = c.dict->arrow_offsets();  // (entries + 1; below 2^31: pqw_columns has held the dictionary to it)
+    const std::string& bytes = c.dict->joined();                    // (both computed once per dictionary and kept with it: nothing is copied per call)
+    t->off = (const uint32_t*)offsets.data(); t->bytes = (const unsigned char*)bytes.data(); t->n_bytes = bytes.size();
+    y->tables[(size_t)k] = std::move(t);
+  }
+  return next;
+}
+
+void pqy_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, size_t n_bytes_cols, PqyPlan* y) {
+  y->tile_bytes.assign(n_bytes_cols * (size_t)g.n_pages * (size_t)g.tiles_per_page, 0);
+  for (const PqwColumn& c : cols) {
+    if (c.bytes_slot < 0) continue;
+    const PqyTables& tb = *y->tables[c.real];
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      for (int32_t t = 0; t < g.tiles_per_page; t++) {
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        uint64_t sum = 0;
+        for (int wi = 0; wi < FDB_PQW_TILE_WORDS && first < end; wi++) {
+          const uint64_t w = fdb_pqw_valid_word(c.validity, first, wi, end);
+          for (int b = 0; b < 64; b++)
+            if ((w >> b) & 1) sum += fdb_pqy_value_bytes(fdb_pqy_entry_len(tb.off, (uint32_t)c.entries, ((const uint32_t*)c.values)[first + wi * 64 + b]), c.form == FDB_PQY_PLAIN);
+        }
+        y->tile_bytes[((size_t)c.bytes_slot * (size_t)g.n_pages + (size_t)p) * (size_t)g.tiles_per_page + (size_t)t] = sum;
+      }
+    }
+  }
+}
+
+void pqy_scan(const FdbPqwGeom& g, size_t n_bytes_cols, PqyPlan* y) {
+  const size_t pages = n_bytes_cols * (size_t)g.n_pages, tpp = (size_t)g.tiles_per_page;
+  if (y->tile_bytes.size() != pages * tpp) throw Error(FDB_ERR_STATE, "parquet write: the byte survey's table does not match the record");
+  y->page_bytes.assign(pages, 0);
+  y->byte_base.assign(pages * tpp, 0);
+  for (size_t cp = 0; cp < pages; cp++) {
+    uint64_t run = 0;
+    for (size_t t = 0; t < tpp; t++) { y->byte_base[cp * tpp + t] = run; run += y->tile_bytes[cp * tpp + t]; }
+    y->page_bytes[cp] = run;
+  }
+}
+
+void pqy_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqyPlan& y, const std::vector<uint64_t>& bytes_out, unsigned char* image) {
+  std::vector<uint32_t> off(FDB_PQW_TILE + 1), idx(FDB_PQW_TILE);
+  for (const PqwColumn& c : cols) {
+    if (c.bytes_slot < 0) continue;
+    const PqyTables& tb = *y.tables[c.real];
+    const bool plain = c.form == FDB_PQY_PLAIN;
+    for (int64_t p = 0; p < g.n_pages; p++) {
+      const size_t cp = (size_t)c.bytes_slot * (size_t)g.n_pages + (size_t)p;
+      if (bytes_out[cp] == FDB_PQW_NONE) continue;
+      for (int32_t t = 0; t < g.tiles_per_page; t++) {
+        int64_t first, end;
+        fdb_pqw_tile_rows(g, p, t, &first, &end);
+        if (first >= end) continue;
+        uint32_t count = 0, total = 0;  // the tile's values by rank: entry and exclusive byte offset
+        for (int wi = 0; wi < FDB_PQW_TILE_WORDS; wi++) {
+          const uint64_t w = fdb_pqw_valid_word(c.validity, first, wi, end);
+          for (int b = 0; b < 64; b++) {
+            if (!((w >> b) & 1)) continue;
+            const uint32_t e = ((const uint32_t*)c.values)[first + wi * 64 + b];
+            idx[count] = e < c.entries ? e : 0u;
+            off[count++] = total;
+            total += fdb_pqy_value_bytes(fdb_pqy_entry_len(tb.off, (uint32_t)c.entries, e), plain);
+          }
+        }
+        off[count] = total;
+        if (total == 0) continue;
+        const uint64_t dst = bytes_out[cp] + y.byte_base[cp * (size_t)g.tiles_per_page + (size_t)t];
+        for (uint64_t k = fdb_pqy_first_word(dst); k <= fdb_pqy_last_word(dst, total); k++) {
+          uint32_t mask, cur;
+          const uint32_t word = fdb_pqy_word(off.data(), idx.data(), count, plain, tb.off, tb.bytes, dst, total, k, &mask);
+          std::memcpy(&cur, image + k * 4, 4);
+          cur = mask == 0xFFFFFFFFu ? word : cur | word;  // (stored, or OR-ed into the zeroed image: the kernel's two ways)
+          std::memcpy(image + k * 4, &cur, 4);
+        }
+      }
+    }
+  }
+}
+
 PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec) {
   PqwPlan P;
   int32_t page_rows = 0;
@@ -763,6 +885,8 @@ PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& s
   P.x = pqx_plan(spec.index, P.cols.size());
   P.bloom = pqb_plan(spec.bloom, P.cols);
   P.n_runs = pqr_plan(spec.runs, &P.cols);
+  pqg_check(spec.groups, rows);  // (the group options' refusals come before the string options'; the plan below leaves a column with a form out)
+  P.n_bytes = pqy_plan(spec.strings, spec.runs, &P.cols, &P.strings);
   P.dict = pqg_plan(spec.groups, rows, &P.cols);
   P.grouped = spec.groups != nullptr && (spec.groups->row_group_rows != 0 || spec.groups->dictionaries != 0);
   if (P.x.statistics > 0) pqx_prepare(P.cols, &P.x);
@@ -780,7 +904,8 @@ static PqwPlan pqw_part(const PqwPlan& P, const fdb_parquet_group_options* group
   A.x = P.x; A.x.modes.clear();
   A.bloom = P.bloom; A.bloom.on.clear();
   A.grouped = true; A.first_group = first; A.n_groups = n; A.n_real = P.n_real; A.file_rows = P.file_rows;
-  int deltas = 0, runs = 0;
+  A.strings.tables = P.strings.tables;
+  int deltas = 0, runs = 0, streams = 0;
   for (int64_t gi = 0; gi < n; gi++) {
     const size_t at = (size_t)((first + gi) * R);
     for (size_t k = 0; k < P.cols.size(); k++) {
@@ -791,6 +916,7 @@ static PqwPlan pqw_part(const PqwPlan& P, const fdb_parquet_group_options* group
       if (c.delta_slot >= 0) c.delta_slot = deltas++;
       if (c.run_values >= 0) c.run_values = runs++;
       if (c.run_levels >= 0) c.run_levels = runs++;
+      if (c.bytes_slot >= 0) c.bytes_slot = streams++;
       A.cols.push_back(std::move(c));
       if (!P.x.modes.empty()) A.x.modes.push_back(P.x.modes[k]);
       if (P.bloom.any()) A.bloom.on.push_back(P.bloom.on[k]);
@@ -798,7 +924,7 @@ static PqwPlan pqw_part(const PqwPlan& P, const fdb_parquet_group_options* group
   }
   A.dict = pqg_plan(groups, rows, &A.cols);
   A.g = pqw_geometry(rows, P.g.page_rows, A.cols.size());
-  A.n_delta = (size_t)deltas; A.n_runs = (size_t)runs; A.n_compressed = pqw_compressed_columns(A.cols);
+  A.n_delta = (size_t)deltas; A.n_runs = (size_t)runs; A.n_bytes = (size_t)streams; A.n_compressed = pqw_compressed_columns(A.cols);
   return A;
 }
 
@@ -914,6 +1040,7 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
   if (bounds && (x->table.size() != 2 * stats.size() || x->modes.size() != cols.size())) throw Error(FDB_ERR_STATE, "parquet write: the min / max table does not match the record");
   if (stats.size() != cols.size() * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the survey table does not match the record");
   if (delta_bytes.size() != plan.n_delta * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of DELTA page sizes does not match the record");
+  if ((sizes.stream_bytes != nullptr ? sizes.stream_bytes->size() : 0) != plan.n_bytes * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of byte stream sizes does not match the record");
   const size_t n_run_streams = plan.n_runs;
   if ((run_bytes != nullptr ? run_bytes->size() : 0) != n_run_streams * (size_t)g.n_pages) throw Error(FDB_ERR_STATE, "parquet write: the table of run-encoded sizes does not match the record");
   // The bytes of a page's stream cut into runs, held to the rule's bounds: no more than its one bit-packed run, no less than a run.
@@ -926,6 +1053,7 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
   LP.delta_out.assign(delta_bytes.size(), FDB_PQW_NONE);
   LP.out.assign(stats.size(), FdbPqwPageOut{FDB_PQW_NONE, FDB_PQW_NONE});
   LP.run_out.assign(n_run_streams * (size_t)g.n_pages, FDB_PQW_NONE);
+  LP.bytes_out.assign(plan.n_bytes * (size_t)g.n_pages, FDB_PQW_NONE);
   for (size_t k = 0; k < cols.size(); k++) {
     const PqwColumn& c = cols[k];
     ChunkMeta& m = chunks[chunk_base[pi] + k];
@@ -935,7 +1063,7 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
     const bool lz4 = c.codec == PQW_LZ4_RAW;
     const unsigned long long* used = c.used_slot >= 0 ? plan.dict.bits.data() + plan.dict.cols[(size_t)c.used_slot].word_off : nullptr;  // the chunk's presence bitmap
     if (used != nullptr && plan.dict.before.size() != plan.dict.bits.size()) throw Error(FDB_ERR_STATE, "parquet write: the used entries of " + c.name + " have not been counted");
-    if (c.pq_kind == FDB_PQW_INDEX) {
+    if (c.pq_kind == FDB_PQW_INDEX && c.form == 0) {
       const std::string body = used != nullptr ? dictionary_body(*c.dict, used) : dictionary_body(*c.dict);
       const std::string stored = !squeeze ? std::string() : lz4 ? pql_block_host((const unsigned char*)body.data(), body.size()) : pqs_block_host((const unsigned char*)body.data(), body.size());  // (host bytes already: the header's walk)
       const std::string hdr = page_header(PAGE_DICTIONARY, (int64_t)body.size(), (int64_t)(squeeze ? stored.size() : body.size()), (int64_t)c.entries, ENC_PLAIN);
@@ -969,7 +1097,24 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
         }
       }
       int encoding = ENC_PLAIN;
-      if (c.delta_slot >= 0) {
+      uint64_t stream_payload = 0;  // a column with a form: the page's byte stream, which follows the DELTA lengths, if any
+      if (c.form != 0) {  // the values themselves: PLAIN, or their lengths as a DELTA page and then their bytes (fdb_pqbytes.h)
+        encoding = c.form == FDB_PQY_DELTA_LENGTH ? ENC_DELTA_LENGTH_BYTE_ARRAY : ENC_PLAIN;
+        if (c.bytes_slot < 0) vpre = std::string("\x80\x01\x04\x00\x00", 5);  // (all NULL over an empty dictionary: the header of zero lengths)
+        else {
+          if (cnt > 0 && (s.mn > s.mx || s.mx >= c.entries)) throw Error(FDB_ERR_INVALID, index_out_of_range(c, s.mx, c.entries));
+          stream_payload = (*sizes.stream_bytes)[(size_t)c.bytes_slot * (size_t)g.n_pages + (size_t)p];
+          if (c.form == FDB_PQY_DELTA_LENGTH) {
+            value_payload = delta_bytes[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p];
+            if (value_payload < 5 || value_payload > fdb_pqd_max_page_bytes(cnt) || (cnt <= 1 && value_payload > FDB_PQD_MAX_HEADER))
+              throw Error(FDB_ERR_STATE, "parquet write: the block survey sizes the lengths of " + std::to_string(cnt) + " values at " + std::to_string(value_payload) + " bytes (" + c.name + ")");
+          }
+          // (a value is at most 2^31 - 1 bytes and a page 2^24 rows: no sum here wraps)
+          if (stream_payload < (c.form == FDB_PQY_PLAIN ? 4ull * cnt : 0ull) || pre.size() + level_payload + value_payload + stream_payload > 0x7FFFFFFFull)
+            throw Error(FDB_ERR_INVALID, "parquet write: page " + std::to_string(p) + " of column " + c.name + " would hold " + std::to_string(pre.size() + level_payload + value_payload + stream_payload) +
+                        " bytes, more than the 2^31 - 1 a page header can say; write fewer rows a page (page_rows)");
+        }
+      } else if (c.delta_slot >= 0) {
         encoding = ENC_DELTA_BINARY_PACKED;
         value_payload = delta_bytes[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p];
         // (the smallest page is 80 01 04 + a count byte + a first-value byte; the first value's length is the device's to know)
@@ -995,7 +1140,7 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
           }
         }
       }
-      const uint64_t body = pre.size() + level_payload + vpre.size() + value_payload;
+      const uint64_t body = pre.size() + level_payload + vpre.size() + value_payload + stream_payload;
       if (squeeze) {  // header, the block's preamble (SNAPPY; an LZ4_RAW block is bare), then what the compressor made of the body
         const uint64_t elements = (*page_elements)[next_compressed++];
         if (lz4 ? elements < 1 || elements > fdb_pql_bound(body) : elements > (uint64_t)fdb_pqs_fragments(body) * fdb_pqs_bound(FDB_PQS_FRAGMENT) || (body > 0) != (elements > 0))
@@ -1026,6 +1171,7 @@ PqwLayout pqw_layout(const std::vector<const PqwPlan*>& parts, const std::vector
       if (value_runs && c.pq_kind == FDB_PQW_INDEX) { LP.run_out[(size_t)c.run_values * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }
       else if (c.delta_slot >= 0) { LP.delta_out[(size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += value_payload; }  // (the encode pass leaves the values alone)
       else if (value_payload > 0) { o.values_off = cur; cur += value_payload; }
+      if (stream_payload > 0) { LP.bytes_out[(size_t)c.bytes_slot * (size_t)g.n_pages + (size_t)p] = cur; cur += stream_payload; }  // (behind the lengths, if any)
     }
     m.bytes = (int64_t)(cur - chunk_start);
     m.nulls = g.rows - valid;
@@ -1172,7 +1318,7 @@ void pqw_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
 }
 
 // ---- the DELTA passes over host arrays: compaction, block survey and page walk, then the encoder, block by block -------------------------
-void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& tile_base, PqdHost* d) {
+void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& tile_base, PqdHost* d, const PqyPlan* y) {
   const size_t n_d = pqw_delta_columns(cols), bpp = (size_t)fdb_pqd_blocks_per_page(g.page_rows);
   d->dense.assign(n_d, std::vector<uint64_t>());
   d->blocks.assign(n_d * (size_t)g.n_pages * bpp, FdbPqdBlock{0, 0, 0, 0, 0});
@@ -1181,7 +1327,8 @@ void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
     const PqwColumn& c = cols[k];
     if (c.delta_slot < 0) continue;
     const size_t slot = (size_t)c.delta_slot;
-    if (c.validity != nullptr) {  // compaction, tile by tile: a value goes to the survey's rank of its tile + its rank inside the tile
+    const PqyTables* lengths_of = c.form != 0 ? y->tables[c.real].get() : nullptr;
+    if (c.validity != nullptr || c.form != 0) {  // compaction, tile by tile: a value goes to the survey's rank of its tile + its rank inside the tile
       std::vector<uint64_t>& dense = d->dense[slot];
       dense.assign((size_t)g.rows, 0);
       for (int64_t p = 0; p < g.n_pages; p++) {
@@ -1194,7 +1341,10 @@ void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, co
           for (int wi = 0; wi < FDB_PQW_TILE_WORDS; wi++) {
             const uint64_t w = fdb_pqw_valid_word(c.validity, first, wi, end);
             for (int b = 0; b < 64; b++)
-              if ((w >> b) & 1) std::memcpy(dst + before + (uint32_t)fdb_pqw_popc(w & ((1ull << b) - 1)), (const unsigned char*)c.values + (size_t)(first + wi * 64 + b) * 8, 8);
+              if (!((w >> b) & 1)) continue;
+              else if (c.form == 0) std::memcpy(dst + before + (uint32_t)fdb_pqw_popc(w & ((1ull << b) - 1)), (const unsigned char*)c.values + (size_t)(first + wi * 64 + b) * 8, 8);
+              else  // DELTA_LENGTH: the value's length (the byte survey's other product) — in [0, 2^31), so the 64-bit rule packs what a 32-bit encoder would
+                dst[before + (uint32_t)fdb_pqw_popc(w & ((1ull << b) - 1))] = fdb_pqy_entry_len(lengths_of->off, (uint32_t)c.entries, ((const uint32_t*)c.values)[first + wi * 64 + b]);
             before += (uint32_t)fdb_pqw_popc(w);
           }
         }
@@ -1326,10 +1476,11 @@ static void pqw_write_host(std::vector<PqwPlan>& plans, uint8_t** bytes, int64_t
       for (size_t slot = 0; slot < P.dict.cols.size(); slot++) { PqwColumn& c = P.cols[P.dict.cols[slot].col]; c.raw_values = c.values; c.values = h.rekeyed[slot].data(); }
     }
     if (P.bloom.any()) pqb_size(cols, g, h.stats, &P.bloom);
-    pqd_survey_host(cols, g, h.stats, h.tile_base, &h.delta);
+    if (P.n_bytes > 0) { pqy_survey_host(cols, g, P.n_bytes, &P.strings); pqy_scan(g, P.n_bytes, &P.strings); }  // the byte survey, and the host's scan of its table
+    pqd_survey_host(cols, g, h.stats, h.tile_base, &h.delta, &P.strings);
     if (P.n_runs > 0) pqr_survey_host(cols, g, h.stats, &h.rn);
     parts.push_back(&P);
-    sizes.push_back(PqwSizes{h.stats, &h.delta.page_bytes, P.n_runs > 0 ? &h.rn.page_bytes : nullptr, nullptr});
+    sizes.push_back(PqwSizes{h.stats, &h.delta.page_bytes, P.n_runs > 0 ? &h.rn.page_bytes : nullptr, nullptr, P.n_bytes > 0 ? &P.strings.page_bytes : nullptr});
     n_compressed += P.n_compressed;
   }
   // layout, and the encode passes
@@ -1340,6 +1491,7 @@ static void pqw_write_host(std::vector<PqwPlan>& plans, uint8_t** bytes, int64_t
     pqw_encode_host(P.cols, P.g, L.parts[pi].out, h.tile_base, image.data());
     pqd_encode_host(P.cols, P.g, h.stats, h.delta, L.parts[pi].delta_out, image.data());
     if (P.n_runs > 0) pqr_encode_host(h.rn, L.parts[pi].run_out, image.data());
+    if (P.n_bytes > 0) pqy_encode_host(P.cols, P.g, P.strings, L.parts[pi].bytes_out, image.data());
   }
   // the file's body: the image, or — `image` being the staging image — what the compressor made of it, laid out again and gathered
   PqwLayout F; uint8_t* file = nullptr;
@@ -1355,7 +1507,7 @@ static void pqw_write_host(std::vector<PqwPlan>& plans, uint8_t** bytes, int64_t
       page_elements.push_back((uint32_t)elements.back().size());
     }
     std::vector<PqwSizes> final_sizes;
-    for (const PqwSizes& z : sizes) final_sizes.push_back(PqwSizes{z.stats, z.delta_bytes, z.run_bytes, &page_elements});
+    for (const PqwSizes& z : sizes) final_sizes.push_back(PqwSizes{z.stats, z.delta_bytes, z.run_bytes, &page_elements, z.stream_bytes});
     F = pqw_layout(parts, final_sizes);
     file = pqw_alloc_bytes(F.file_bytes(), false);
     for (size_t i = 0; i < F.pages.size(); i++) std::memcpy(file + F.pages[i].off, elements[i].data(), elements[i].size());
@@ -1393,7 +1545,10 @@ struct PoolBlock {  // an image of the file body in HBM
 
 // What the parts of one call share beside scope, stream and images: the pass queued last, and the device copies of the rank and hash
 // tables, which belong to the record's columns — every group of a column reads the same one.
-struct PqwShared { const char* queued = nullptr; std::vector<const uint32_t*> d_ranks; std::vector<const uint64_t*> d_hashes; };
+struct PqwShared {
+  const char* queued = nullptr; std::vector<const uint32_t*> d_ranks; std::vector<const uint64_t*> d_hashes;
+  std::vector<const uint32_t*> d_entry_off; std::vector<const unsigned char*> d_entry_bytes;  // the entry tables of the columns with a form (fdb_pqbytes.h)
+};
 
 // One part's side of the device (a call without row groups has one): the plan, its scope, stream and timer, its images (with a compressed column: staging image,
 // scratch, final image), the tables of the survey and of the optional passes (the call's arena) and the host tables its wait fills.
@@ -1410,6 +1565,7 @@ struct PqwCall {
   const FdbPqdCol* d_dcols = nullptr; FdbPqdBlock* d_blocks = nullptr; uint32_t* d_page_bytes = nullptr;
   const FdbPqrStream* d_streams = nullptr; uint32_t* d_run_bytes = nullptr; unsigned char* d_bitsets = nullptr;
   unsigned long long* d_present = nullptr;  // used-entry dictionaries: the table of presence bitmaps
+  const FdbPqyCol* d_ycols = nullptr; uint64_t* d_tile_bytes = nullptr; std::vector<uint64_t*> d_lengths;  // columns with a form: the byte survey's table; per DELTA slot the scratch column of lengths (null: not one)
   bool compact = false, run_compact = false;  // a DELTA column / a column whose indices are cut into runs has a bitmap
   std::vector<FdbPqwPageStat> stats; std::vector<uint32_t> delta_bytes, run_bytes;  // what the survey's wait fills
   void wait() { hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
@@ -1454,7 +1610,13 @@ static void pqd_tables(PqwCall* c) {
     if (cols[k].delta_slot < 0) continue;
     FdbPqdCol& o = dc[(size_t)cols[k].delta_slot];
     std::memset(&o, 0, sizeof(FdbPqdCol));
-    o.values = (const uint64_t*)cols[k].values; o.validity = cols[k].validity; o.col = (int32_t)k;
+    o.col = (int32_t)k;
+    if (cols[k].form != 0) {  // DELTA_LENGTH: the values' lengths, a dense column of the call's arena that the byte survey fills in rank order
+      o.dense = (uint64_t*)c->cs.alloc(((size_t)g.rows + 1) * 8); o.values = o.dense;
+      c->d_lengths.resize(c->P.n_delta, nullptr); c->d_lengths[(size_t)cols[k].delta_slot] = o.dense;
+      continue;
+    }
+    o.values = (const uint64_t*)cols[k].values; o.validity = cols[k].validity;
     o.dense = cols[k].validity != nullptr ? (uint64_t*)c->cs.alloc(((size_t)g.rows + 1) * 8) : (uint64_t*)const_cast<void*>(cols[k].values);  // (only ever read when it is the column)
     c->compact = c->compact || cols[k].validity != nullptr;
   }
@@ -1487,6 +1649,42 @@ static void pqr_tables(PqwCall* c) {
   }
   c->d_streams = (const FdbPqrStream*)c->cs.ctx->stage(rs.data(), rs.size() * sizeof(FdbPqrStream));
   c->d_run_bytes = (uint32_t*)c->cs.alloc(c->r_items * 4);
+}
+
+// The columns with a form as fdb_pqbytes.hip sees them — their entry tables uploaded once per call, every group of a column reads the
+// same ones — and the byte survey's table. After pqd_tables: a DELTA_LENGTH column's lengths are that pass's scratch.
+static void pqy_tables(PqwCall* c) {
+  const std::vector<PqwColumn>& cols = c->P.cols;
+  std::vector<FdbPqyCol> yc(c->P.n_bytes);
+  for (size_t k = 0; k < cols.size(); k++) {
+    const PqwColumn& col = cols[k];
+    if (col.bytes_slot < 0) continue;
+    const PqyTables& tb = *c->P.strings.tables[col.real];
+    const uint32_t*& d_off = c->shared.d_entry_off[col.real];
+    if (d_off == nullptr) {  // (the plan outlives the wait)
+      d_off = (const uint32_t*)c->upload(tb.off, ((size_t)col.entries + 1) * 4, "hipMemcpyAsync(entry offsets)");
+      c->shared.d_entry_bytes[col.real] = (const unsigned char*)c->upload(tb.bytes, tb.n_bytes, "hipMemcpyAsync(entry bytes)");
+    }
+    FdbPqyCol& o = yc[(size_t)col.bytes_slot];
+    std::memset(&o, 0, sizeof(FdbPqyCol));
+    o.values = (const uint32_t*)col.values; o.validity = col.validity; o.entry_off = d_off; o.entry_bytes = c->shared.d_entry_bytes[col.real];
+    o.lengths = col.delta_slot >= 0 ? c->d_lengths[(size_t)col.delta_slot] : nullptr;
+    o.entries = (uint32_t)col.entries; o.col = (int32_t)k; o.plain = col.form == FDB_PQY_PLAIN;
+  }
+  c->d_ycols = (const FdbPqyCol*)c->cs.ctx->stage(yc.data(), yc.size() * sizeof(FdbPqyCol));
+  const size_t tiles = c->P.n_bytes * (size_t)c->P.g.n_pages * (size_t)c->P.g.tiles_per_page;
+  c->d_tile_bytes = (uint64_t*)c->cs.alloc(tiles * 8);
+  c->P.strings.tile_bytes.resize(tiles);
+}
+
+// The byte survey (fdb_pqbytes.hip): behind the survey, whose tile ranks it reads, and in front of the DELTA passes, whose lengths it
+// writes; its table back in the same wait.
+static void pqy_survey_pass(PqwCall* c) {
+  if (c->queued != nullptr) c->settle();
+  std::vector<uint64_t>& tile_bytes = c->P.strings.tile_bytes;
+  hip_check(fdb_launch_pqy_survey(c->d_ycols, (int32_t)c->P.n_bytes, c->P.g, c->d_tile_base, c->d_tile_bytes, c->stream), "parquet write: byte survey launch");
+  hip_check(hipMemcpyAsync(tile_bytes.data(), c->d_tile_bytes, tile_bytes.size() * 8, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(byte survey table)");
+  c->queued = "pqwrite bytes survey";
 }
 
 // The min / max pass (fdb_pqstats.hip): behind the survey, its table back in the same wait.
@@ -1637,6 +1835,13 @@ static void pqw_encode_passes(PqwCall* c, const PqwLayout::Part& L) {
     hip_check(fdb_launch_pqr_encode(c->d_streams, (int32_t)c->P.n_runs, g, c->d_stats, c->d_run_bytes, d_run_out, image, c->stream), "parquet write: run encode launch");
     c->timed("pqwrite run encode");
   }
+  if (c->P.n_bytes > 0) {  // (behind the DELTA encoder: a word the lengths and the bytes share is stored by the one, OR-ed by the other)
+    const PqyPlan& y = c->P.strings;
+    const uint64_t* d_bytes_out = (const uint64_t*)c->upload(L.bytes_out.data(), L.bytes_out.size() * 8, "hipMemcpyAsync(byte stream offsets)");
+    const uint64_t* d_byte_base = (const uint64_t*)c->upload(y.byte_base.data(), y.byte_base.size() * 8, "hipMemcpyAsync(tile byte bases)");  // (the plan outlives the wait)
+    hip_check(fdb_launch_pqy_encode(c->d_ycols, (int32_t)c->P.n_bytes, g, d_bytes_out, d_byte_base, image, c->stream), "parquet write: byte encode launch");
+    c->timed("pqwrite bytes encode");
+  }
 }
 
 // SNAPPY (fdb_pqsnappy.hip) and LZ4_RAW (fdb_pqlz4.hip): the host tables of the compress and gather passes — they outlive the waits of
@@ -1780,13 +1985,14 @@ void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes
   CallScope cs(b.device);
   DrainOnUnwind drain{cs.ctx->stream};
   PqwShared shared;
-  shared.d_ranks.assign(n_real, nullptr); shared.d_hashes.assign(n_real, nullptr);
+  shared.d_ranks.assign(n_real, nullptr); shared.d_hashes.assign(n_real, nullptr); shared.d_entry_off.assign(n_real, nullptr); shared.d_entry_bytes.assign(n_real, nullptr);
   std::vector<PqwCall> calls;
   for (PqwPlan& P : plans) calls.push_back(PqwCall{P, cs, cs.ctx->stream, image, scratch, final_image, pt, shared, shared.queued});
   hipStream_t stream = cs.ctx->stream;
   for (PqwCall& c : calls) {
     pqw_tables(&c);
     if (c.P.n_delta > 0) pqd_tables(&c);
+    if (c.P.n_bytes > 0) pqy_tables(&c);
     if (c.P.n_runs > 0 && !pruned) pqr_tables(&c);
   }
   // the survey passes, their tables back in ONE wait
@@ -1797,6 +2003,7 @@ void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes
     hip_check(hipMemcpyAsync(c.stats.data(), c.d_stats, c.items * sizeof(FdbPqwPageStat), hipMemcpyDeviceToHost, c.stream), "hipMemcpyAsync(page table)");
     c.queued = "pqwrite survey";
     if (bounds) pqx_minmax_pass(&c);
+    if (c.P.n_bytes > 0) pqy_survey_pass(&c);
     if (c.P.n_delta > 0) pqd_survey_pass(&c);
     if (pruned) pqg_present_pass(&c);
     if (c.P.n_runs > 0 && !pruned) pqr_survey_pass(&c);
@@ -1820,8 +2027,9 @@ void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes
   std::vector<PqwSizes> sizes;
   for (PqwCall& c : calls) {
     if (blooms) pqb_size(c.P.cols, c.P.g, c.stats, &c.P.bloom);
+    if (c.P.n_bytes > 0) pqy_scan(c.P.g, c.P.n_bytes, &c.P.strings);
     parts.push_back(&c.P);
-    sizes.push_back(PqwSizes{c.stats, &c.delta_bytes, c.P.n_runs > 0 ? &c.run_bytes : nullptr, nullptr});
+    sizes.push_back(PqwSizes{c.stats, &c.delta_bytes, c.P.n_runs > 0 ? &c.run_bytes : nullptr, nullptr, c.P.n_bytes > 0 ? &c.P.strings.page_bytes : nullptr});
   }
   const PqwLayout L = pqw_layout(parts, sizes);
   pt.mark("pqwrite layout");
@@ -1835,7 +2043,7 @@ void batch_to_parquet(const DeviceBatch& b, const PqwSpec& spec, uint8_t** bytes
   if (squeezed) {
     pqs_compress_pass(&calls[0], L, &t);
     std::vector<PqwSizes> final_sizes;
-    for (const PqwSizes& z : sizes) final_sizes.push_back(PqwSizes{z.stats, z.delta_bytes, z.run_bytes, &t.page_elements});
+    for (const PqwSizes& z : sizes) final_sizes.push_back(PqwSizes{z.stats, z.delta_bytes, z.run_bytes, &t.page_elements, z.stream_bytes});
     F = pqw_layout(parts, final_sizes);
     pt.mark("pqwrite final layout");
     pqs_gather_pass(&calls[0], L, F, &t);

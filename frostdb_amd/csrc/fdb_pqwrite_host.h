@@ -9,6 +9,7 @@
 
 #include "fdb_arrow.h"
 #include "fdb_pqbloom.h"
+#include "fdb_pqbytes.h"
 #include "fdb_pqdelta.h"
 #include "fdb_pqdict.h"
 #include "fdb_pqruns.h"
@@ -49,6 +50,9 @@ struct PqwColumn {
   int used_slot = -1;             // >= 0: the chunk's dictionary keeps the used entries only (fdb_pqdict.h), and the column's place in PqgPlan. Once
                                   // pqg_resolve has run, `entries` counts the used ones, `width` is theirs and `values` the re-keyed copy
   const void* raw_values = nullptr;  // … and the indices as the record holds them, which the bloom pass keeps reading
+  int form = 0;                   // FDB_PQY_*: 1 / 2 = no dictionary page, the values themselves in PLAIN / DELTA_LENGTH_BYTE_ARRAY pages (fdb_pqbytes.h)
+  int bytes_slot = -1;            // >= 0: … whose byte streams the byte passes size and write, and the column's place in their tables. (A DELTA_LENGTH
+                                  // column has a delta_slot too: its lengths. All NULL over an empty dictionary: neither — the host writes its pages)
   const HostDict* dict = nullptr;
   const void* values = nullptr;
   const unsigned char* validity = nullptr;  // nullptr: every row counts
@@ -65,6 +69,7 @@ struct PqwLayout {
     std::vector<FdbPqwPageOut> out;
     std::vector<uint64_t> delta_out;  // [delta_slot × n_pages + page]: where a DELTA page's value bytes start (its `out` says FDB_PQW_NONE for the values)
     std::vector<uint64_t> run_out;    // [run stream × n_pages + page]: where a stream cut into runs starts (FDB_PQW_NONE: the page's is not; then `out` says where it goes)
+    std::vector<uint64_t> bytes_out;  // [bytes_slot × n_pages + page]: where a page's byte stream starts (FDB_PQW_NONE: the page has no value)
   };
   std::vector<Part> parts;
   uint64_t body_bytes = 0;       // PAR1 + column chunks: what the image holds; the footer starts here
@@ -141,6 +146,7 @@ struct PqwSpec {
   const fdb_parquet_bloom_options* bloom = nullptr;
   const fdb_parquet_run_options* runs = nullptr;
   const fdb_parquet_group_options* groups = nullptr;
+  const fdb_parquet_string_options* strings = nullptr;
 };
 // The write options, encodings and codecs of `spec` and the columns checked, every refusal of theirs made (FDB_ERR_INVALID /
 // FDB_ERR_UNSUPPORTED): nothing has been launched yet.
@@ -172,6 +178,8 @@ struct PqgPlan {
 // Every refusal of the group options (FDB_ERR_INVALID): nothing has been launched yet. `groups` == nullptr or all zero: nothing asked.
 // Returns the pruned columns of `cols` — the record's, or one part's virtual columns — their used_slot set.
 PqgPlan pqg_plan(const fdb_parquet_group_options* groups, int64_t rows, std::vector<PqwColumn>* cols);
+// … the refusals alone (pqg_plan makes them too): pqw_plan checks the group options, then the string options — whose columns the plan leaves out.
+void pqg_check(const fdb_parquet_group_options* groups, int64_t rows);
 // The pass over host arrays: every non-NULL row's index into its column's bitmap of d->bits (zeroed).
 void pqg_present_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, PqgPlan* d);
 // After the wait: an index out of range refused (as the layout would), the used entries counted, d->before made; the columns' `entries`
@@ -180,14 +188,37 @@ void pqg_resolve(const std::vector<FdbPqwPageStat>& stats, const FdbPqwGeom& g, 
 // The pass over host arrays: `out`[slot] = the column's re-keyed indices (rows + 8 of them).
 void pqg_remap_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqgPlan& d, std::vector<std::vector<uint32_t>>* out);
 
+// Value pages of BYTE_ARRAY columns (fdb_parquet_string_options; fdb_pqbytes.h): the entry tables of the record's columns with a form —
+// the call's parts share them, as they share ranks and entry hashes — and, per part, what the byte survey found, scanned.
+struct PqyTables {  // entries + 1 offsets into the entries' bytes laid end to end: the dictionary's own (HostDict::arrow_offsets / joined), made once per dictionary, borrowed here
+  const uint32_t* off = nullptr; const unsigned char* bytes = nullptr; size_t n_bytes = 0;
+};
+struct PqyPlan {
+  std::vector<std::shared_ptr<const PqyTables>> tables;  // per column of the RECORD (PqwColumn::real); null: the column has no byte stream
+  std::vector<uint64_t> tile_bytes;   // [(bytes_slot × n_pages + page) × tiles_per_page + tile]: the byte survey's table …
+  std::vector<uint64_t> page_bytes;   // [bytes_slot × n_pages + page]: … summed per page: the page's byte stream (pqy_scan)
+  std::vector<uint64_t> byte_base;    // … and per tile the bytes of its page's tiles before it
+};
+// Every refusal of the string options: FDB_ERR_INVALID — n_columns neither 0 nor the column count, an entry outside 0 … 2, pad != 0;
+// FDB_ERR_UNSUPPORTED, naming the column — a form on a column that is not a dictionary / string / binary column, `runs` bit 0 on a column
+// with a form. Nothing has been launched yet. Sets the columns' form, bytes_slot and — DELTA_LENGTH: the lengths are one more DELTA
+// column — delta_slot, and makes the entry tables; returns the columns with a byte stream. `strings` == nullptr or all zero: nothing.
+size_t pqy_plan(const fdb_parquet_string_options* strings, const fdb_parquet_run_options* runs, std::vector<PqwColumn>* cols, PqyPlan* y);
+// The pass over host arrays: y->tile_bytes, tile by tile.
+void pqy_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, size_t n_bytes_cols, PqyPlan* y);
+// After the wait: the table summed into y->page_bytes and y->byte_base.
+void pqy_scan(const FdbPqwGeom& g, size_t n_bytes_cols, PqyPlan* y);
+// The pass over host arrays: every tile's share of its page's byte stream, word by word (fdb_pqy_word) as the kernel writes it.
+void pqy_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const PqyPlan& y, const std::vector<uint64_t>& bytes_out, unsigned char* image);
+
 // Everything a call decides before anything is launched: the columns, the geometry, the index and bloom options checked and prepared
 // (modes and ranks; entry hashes), how many columns are DELTA, how many compressed, how many streams are cut into runs. What the
 // passes find later goes into it: x.table (the min / max pass), the filters' sizes (pqb_size).
 struct PqwPlan {
   std::vector<PqwColumn> cols;
   FdbPqwGeom g;
-  PqxIndex x; PqbPlan bloom; PqgPlan dict;
-  size_t n_delta = 0, n_compressed = 0, n_runs = 0;
+  PqxIndex x; PqbPlan bloom; PqgPlan dict; PqyPlan strings;
+  size_t n_delta = 0, n_compressed = 0, n_runs = 0, n_bytes = 0;  // (n_bytes: the columns with a byte stream)
   bool grouped = false;  // group options that are not all zero: a row group says its ordinal
   // Several row groups (row_group_rows = R cuts the record): the plan is one PART of the call, over VIRTUAL columns — (group, column),
   // group after group: the record's column with its buffers starting (first_group + group) · R rows in, a column of a record of g.rows
@@ -196,7 +227,7 @@ struct PqwPlan {
   size_t n_real = 0;     // the record's columns: cols.size() == n_groups × n_real
 };
 // THE place that checks a call's options and makes every refusal, in the parameters' order: write options and columns (pqw_columns),
-// index (pqx_plan), bloom (pqb_plan), runs (pqr_plan), groups (pqg_plan). Nothing has been launched yet. `in` outlives the plan (its dictionaries).
+// index (pqx_plan), bloom (pqb_plan), runs (pqr_plan), groups (pqg_plan), strings (pqy_plan). Nothing has been launched yet. `in` outlives the plan (its dictionaries).
 PqwPlan pqw_plan(const std::vector<PqwInput>& in, int64_t rows, const PqwSpec& spec);
 // The call's parts: the plan itself when the record is one row group, else the full groups' part and, if the last group is shorter, its.
 std::vector<PqwPlan> pqw_parts(PqwPlan&& plan, const PqwSpec& spec);
@@ -209,6 +240,7 @@ std::vector<PqwPlan> pqw_parts(PqwPlan&& plan, const PqwSpec& spec);
 struct PqwSizes {
   const std::vector<FdbPqwPageStat>& stats;  // the survey's
   const std::vector<uint32_t>*delta_bytes = nullptr, *run_bytes = nullptr, *page_elements = nullptr;
+  const std::vector<uint64_t>* stream_bytes = nullptr;  // [bytes_slot × n_pages + page]: PqyPlan::page_bytes, as the byte survey found them
 };
 // The page index, sorting_columns and the bloom filters of the plan are laid out when the layout is the file's own — no compressed
 // column, or `page_elements` given: a staging image has neither.
@@ -229,9 +261,10 @@ struct PqdHost {
   std::vector<std::vector<uint64_t>> dense;
   std::vector<FdbPqdBlock> blocks;
   std::vector<uint32_t> page_bytes;
-  const uint64_t* values(const PqwColumn& c) const { return c.validity != nullptr ? dense[(size_t)c.delta_slot].data() : (const uint64_t*)c.values; }
+  const uint64_t* values(const PqwColumn& c) const { return c.validity != nullptr || c.form != 0 ? dense[(size_t)c.delta_slot].data() : (const uint64_t*)c.values; }  // (a form: its lengths)
 };
-void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& tile_base, PqdHost* d);
+void pqd_survey_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const std::vector<uint32_t>& tile_base, PqdHost* d,
+                     const PqyPlan* y = nullptr);  // (`y`: the entry tables, with a DELTA_LENGTH column)
 void pqd_encode_host(const std::vector<PqwColumn>& cols, const FdbPqwGeom& g, const std::vector<FdbPqwPageStat>& stats, const PqdHost& d, const std::vector<uint64_t>& delta_out,
                      unsigned char* image);
 

@@ -174,8 +174,8 @@ def lib() -> ctypes.CDLL:
     L.fdb_batch_column_name.restype = ctypes.c_char_p
     L.fdb_batch_column_format.argtypes = [vp, i32]
     L.fdb_batch_column_format.restype = ctypes.c_char_p
-    for suffix, takes in PARQUET_WRITE_ENTRIES:
-        optional_args = [vp, i32, vp, i32, vp, vp, vp, vp][:takes + min(takes, 2)]  # (encodings and codecs: an array and its length)
+    for suffix, takes in PARQUET_WRITE_ENTRIES + [PARQUET_WRITE_STRINGS]:
+        optional_args = [vp, i32, vp, i32, vp, vp, vp, vp, vp][:takes + min(takes, 2)]  # (encodings and codecs: an array and its length)
         getattr(L, "fdb_batch_to_parquet" + suffix).argtypes = [vp, vp] + optional_args + [P(vp), P(i64)]
         getattr(L, "fdb_selftest_parquet_write" + suffix).argtypes = [vp, vp, vp] + optional_args + [P(vp), P(i64)]
     L.fdb_bytes_free.argtypes = [vp]
@@ -504,15 +504,15 @@ class ParquetRunOptions(ctypes.Structure):
 PARQUET_RUN_STREAMS = {None: 0, False: 0, "values": 1, "levels": 2, True: 3}
 
 
-def _parquet_run_options(runs, names, is_index):
+def _parquet_run_options(runs, names, is_index, forms=None):
     """`runs`: None; True — every column, its definition levels and, of a dictionary / string / binary column (`is_index`: per
-    column), its indices; a sequence of column names (both streams of each); or a dict of name → True (both) / "values" (the
+    column) that is not written with a string form (`forms`: per column, 0 = none), its indices; a sequence of column names (both streams of each); or a dict of name → True (both) / "values" (the
     dictionary indices) / "levels" (the definition levels) / None. Returns the struct and what it points at, or (None, None) when
     nothing is asked: the caller then calls what it called without this argument."""
     if runs is None or runs is False:
         return None, None
     if runs is True:
-        wanted = [2 | (1 if ix else 0) for ix in is_index]
+        wanted = [2 | (1 if ix and not (forms and forms[k]) else 0) for k, ix in enumerate(is_index)]
     elif isinstance(runs, str):
         _raise(FDB_ERR_INVALID, "parquet write: `runs` is True, a sequence of column names or a dict of name → True / 'values' / 'levels', got %r" % (runs,))
     else:
@@ -551,6 +551,47 @@ def _parquet_group_options(row_group_rows, dictionaries):
     return ParquetGroupOptions(row_group_rows, PARQUET_DICTIONARIES[dictionaries], 0)
 
 
+class ParquetStringOptions(ctypes.Structure):
+    """fdb_parquet_string_options."""
+    _fields_ = [("forms", ctypes.c_void_p), ("n_columns", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+PARQUET_STRING_FORMS = {None: 0, "dictionary": 0, "plain": 1, "delta_length": 2}
+
+
+def _parquet_string_forms(strings, names, is_index, runs):
+    """`strings`: None; "plain" or "delta_length" — every dictionary / string / binary column (`is_index`: per column) whose
+    dictionary indices `runs` does not ask by name to be cut into runs; a sequence with one entry per column or a dict by column name
+    of None / "dictionary" (a dictionary page and RLE_DICTIONARY pages, as without it), "plain" or "delta_length". Returns the form
+    per column, or None when nothing is asked: the caller then calls what it called without this argument."""
+    if strings is None:
+        return None
+    if isinstance(strings, str):
+        if strings not in ("plain", "delta_length"):
+            _raise(FDB_ERR_INVALID, "parquet write: `strings` is None, 'plain', 'delta_length', a sequence per column or a dict by name, got %r" % (strings,))
+        indexed = set()   # the columns whose indices are asked for by name (anything else about `runs` is the run options' to refuse)
+        if runs is not None and not isinstance(runs, (bool, str)):
+            for n in runs:
+                e = runs[n] if isinstance(runs, dict) else True
+                if e is True or (isinstance(e, str) and e == "values"):
+                    indexed.add(n)
+        wanted = [strings if ix and n not in indexed else None for n, ix in zip(names, is_index)]
+    elif isinstance(strings, dict):
+        unknown = [n for n in strings if n not in names]
+        if unknown:
+            _raise(FDB_ERR_INVALID, "parquet write: `strings` names no column of the record: %s" % (unknown[0],))
+        wanted = [strings.get(n) for n in names]
+    else:
+        wanted = list(strings)
+        if len(wanted) != len(names):
+            _raise(FDB_ERR_INVALID, "parquet write: `strings` has %d entries, the record %d columns" % (len(wanted), len(names)))
+    for e in wanted:
+        if not (e is None or isinstance(e, str)) or e not in PARQUET_STRING_FORMS:
+            _raise(FDB_ERR_INVALID, "parquet write: unknown string form %r (None, 'dictionary', 'plain' or 'delta_length')" % (e,))
+    forms = [PARQUET_STRING_FORMS[e] for e in wanted]
+    return forms if any(forms) else None
+
+
 def _take_bytes(rc, out, n) -> bytes:
     if rc != 0:
         _raise(rc, lib().fdb_last_error().decode("utf-8", "replace"))
@@ -563,42 +604,47 @@ def _take_bytes(rc, out, n) -> bytes:
 # The writer's entry points, narrowest first: the suffix of the name, and how many of the optional arguments — encodings, codecs, index
 # options, bloom options, run options, group options, in this order — it takes.
 PARQUET_WRITE_ENTRIES = [("", 0), ("_encoded", 1), ("_compressed", 2), ("_indexed", 3), ("_filtered", 4), ("_runs", 5), ("_grouped", 6)]
+PARQUET_WRITE_STRINGS = ("_strings", 7)  # … and the widest, which takes the string options behind them
 
 
 def _parquet_write(entry, head, names, is_bool, is_index, asked) -> bytes:
     """`asked`, the options of ResidentBatch.to_parquet / selftest_parquet_write in their order, as the C structures, and the call
     through the NARROWEST of `entry`'s entry points that carries what was asked (`head`: its arguments in front of the options)."""
-    page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries = asked
+    page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries, strings = asked
     opts, _keep = _parquet_write_options(page_rows, optional, names)
     enc, n_enc = _parquet_encodings(encodings, names) if encodings is not None else (None, 0)
     codecs, n_codecs = _parquet_codecs(compression, names) if compression is not None else (None, 0)
     index, _keep_index = _parquet_index_options(statistics, index_size_limit, sorting_columns, names)
     bloom, _keep_bloom = _parquet_bloom_options(bloom_filters, bloom_bits_per_value, names, is_bool, sorting_columns)
-    run_opts, _keep_runs = _parquet_run_options(runs, names, is_index)
+    forms = _parquet_string_forms(strings, names, is_index, runs)
+    run_opts, _keep_runs = _parquet_run_options(runs, names, is_index, forms)
     group_opts = _parquet_group_options(row_group_rows, dictionaries)
+    _keep_forms = (ctypes.c_int8 * max(1, len(names)))(*forms) if forms is not None else None
+    string_opts = ParquetStringOptions(ctypes.cast(_keep_forms, ctypes.c_void_p), len(forms), 0) if forms is not None else None
     optional_args = [(ctypes.cast(enc, ctypes.c_void_p) if n_enc else None, n_enc), (ctypes.cast(codecs, ctypes.c_void_p) if n_codecs else None, n_codecs)]
-    optional_args += [(ctypes.byref(struct) if struct is not None else None,) for struct in (index, bloom, run_opts, group_opts)]
-    is_asked = [encodings is not None, compression is not None, index is not None, bloom is not None, run_opts is not None, group_opts is not None]
+    optional_args += [(ctypes.byref(struct) if struct is not None else None,) for struct in (index, bloom, run_opts, group_opts, string_opts)]
+    is_asked = [encodings is not None, compression is not None, index is not None, bloom is not None, run_opts is not None, group_opts is not None, string_opts is not None]
     need = max([i + 1 for i, on in enumerate(is_asked) if on], default=0)
-    suffix, takes = next(e for e in PARQUET_WRITE_ENTRIES if e[1] >= need)
+    suffix, takes = next(e for e in PARQUET_WRITE_ENTRIES + [PARQUET_WRITE_STRINGS] if e[1] >= need)
     out, n = ctypes.c_void_p(), ctypes.c_int64()
     rc = getattr(lib(), entry + suffix)(*head, ctypes.byref(opts), *[a for group in optional_args[:takes] for a in group], ctypes.byref(out), ctypes.byref(n))
     return _take_bytes(rc, out, n)
 
 
 def selftest_parquet_write(record: pa.RecordBatch, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0,
-                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None) -> bytes:
+                           sorting_columns=None, bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None, strings=None) -> bytes:
     """The Parquet file ``ResidentBatch(record).to_parquet(page_rows, optional, encodings, compression, ...)`` writes, byte for byte,
     made without a device (fdb_selftest_parquet_write, with `encodings` fdb_selftest_parquet_write_encoded, with `compression`
     fdb_selftest_parquet_write_compressed — "snappy" by the host walk of fdb_pqsnappy.h, "lz4" by that of fdb_pqlz4.h —, with `statistics`, `index_size_limit` or `sorting_columns`
     fdb_selftest_parquet_write_indexed, with `bloom_filters` or `bloom_bits_per_value` fdb_selftest_parquet_write_filtered): the same
     layout, headers and footer, the kernels replaced by a host walk of the code they compile. With `runs`
     fdb_selftest_parquet_write_runs: the run passes walked as well; with `row_group_rows` or `dictionaries`
-    fdb_selftest_parquet_write_grouped: the present and remap passes too."""
+    fdb_selftest_parquet_write_grouped: the present and remap passes too; with `strings` fdb_selftest_parquet_write_strings: the
+    byte survey and the byte encode pass, the by-position lookup included."""
     def is_index(t):
         t = t.value_type if pa.types.is_dictionary(t) else t
         return pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t)
-    asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries)
+    asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries, strings)
     with ExportedBatch(record) as ex:
         return _parquet_write("fdb_selftest_parquet_write", [ctypes.addressof(ex.array), ctypes.addressof(ex.schema)], list(record.schema.names),
                               [pa.types.is_boolean(f.type) for f in record.schema], [is_index(f.type) for f in record.schema], asked)
@@ -939,7 +985,7 @@ class ResidentBatch:
         return {"merge_ms": a.value, "gather_ms": b.value, "round_ms": [rounds[i] for i in range(min(k.value, 32))], "words": w.value}
 
     def to_parquet(self, page_rows: int = 0, optional=None, encodings=None, compression=None, statistics=None, index_size_limit: int = 0, sorting_columns=None,
-                   bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None) -> bytes:
+                   bloom_filters=None, bloom_bits_per_value: int = 0, runs=None, row_group_rows: int = 0, dictionaries=None, strings=None) -> bytes:
         """≙ pqarrow.RecordsToFile for one record: this resident record as one complete Parquet file (one row group, data pages V1 of
         `page_rows` rows, 0 = 65 536), its payloads encoded on the device (fdb_batch_to_parquet). `optional`: None, a
         sequence per column or a dict by name of None (auto: optional iff the column holds NULLs or is a dictionary / string column),
@@ -974,8 +1020,16 @@ class ResidentBatch:
         found and re-keyed on the device by two more passes (fdb_batch_to_parquet_grouped). `row_group_rows` (≙ WithRowGroupSize;
         here a multiple of 64): 0 (one row group), or the rows per row group — the last one shorter —, each group with its own pages,
         statistics, page index, bloom filters and (with "used") dictionaries; from_parquet_many reads them back in one call.
-        Without these two the call is what it was."""
-        asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries)
+        Without these two the call is what it was. `strings`: None; "plain" or "delta_length" — every dictionary / string / binary
+        column; a sequence per column or a dict by name of None / "dictionary" / "plain" / "delta_length": such a column's chunk has
+        no dictionary page, its pages hold the non-NULL values themselves — PLAIN (length and bytes per value: FrostDB's own default
+        for a string column) or DELTA_LENGTH_BYTE_ARRAY (the lengths DELTA_BINARY_PACKED, then the bytes) — what a column of mostly
+        distinct values asks for; sized by a byte survey and gathered from the entries by a byte encode pass on the device
+        (fdb_batch_to_parquet_strings). The bare string skips the columns that cannot take it — other kinds, and those whose
+        dictionary indices `runs` asks for by name — and `runs=True` leaves the indices of a column with a form alone; an explicit
+        entry that cannot be honoured is refused. `dictionaries="used"` has no effect on such a column. Without it the call is what
+        it was."""
+        asked = (page_rows, optional, encodings, compression, statistics, index_size_limit, sorting_columns, bloom_filters, bloom_bits_per_value, runs, row_group_rows, dictionaries, strings)
         return _parquet_write("fdb_batch_to_parquet", [self.handle], self.column_names, [f == "b" for f in self.column_formats],
                               [f not in ("l", "L", "g", "b") for f in self.column_formats], asked)
 

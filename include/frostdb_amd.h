@@ -803,6 +803,41 @@ typedef struct fdb_parquet_group_options {
 FDB_API int fdb_batch_to_parquet_grouped(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, const fdb_parquet_group_options* groups /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 FDB_API int fdb_selftest_parquet_write_grouped(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, const fdb_parquet_group_options* groups /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
 
+/* … and with the VALUES of a dictionary / string / binary column in its pages instead of a dictionary page and indices: what FrostDB's
+ * own default is for a string column without the `rle_dict` tag (PLAIN; dynparquet/schema.go:531-563) and what its schemas can name
+ * (`delta_length_byte_array`), and what a column of mostly distinct values — ids, stack traces, whatever filter() or take has thinned
+ * out — asks for, where a dictionary page repeats every value and the indices come on top. `forms`[k] = 1 or 2 on such a column: its
+ * chunk has no dictionary page and no dictionary_page_offset, data_page_offset is the first data page, ColumnMetaData.encodings is
+ * [PLAIN] or [DELTA_LENGTH_BYTE_ARRAY] (+ RLE when the column is optional) and every DataPageHeader.encoding 0 or 6. A page's body is its
+ * definition levels exactly as before (cut into runs when `runs` bit 1 asks) and then its non-NULL values in row order — PLAIN: per
+ * value the 4-byte little-endian length and the entry's bytes; DELTA_LENGTH_BYTE_ARRAY: the lengths as DELTA_BINARY_PACKED (blocks of
+ * 128, 4 miniblocks, the rule of the int64 columns: lengths lie in [0, 2^31), so its bytes are a 32-bit encoder's), then all the bytes
+ * back to back; a page without a value holds the header of zero lengths, 80 01 04 00 00. Entries of equal bytes write the same bytes, an
+ * unused entry never shows. A column that is all NULL over an empty dictionary keeps its present form (PLAIN pages of zero values) under
+ * form 1 and gets pages of zero lengths under form 2. Statistics, the page index, bloom filters, sorting_columns and row groups are over
+ * the record's indices and entries and do not change, PageLocations and sizes follow the new bodies; SNAPPY / LZ4_RAW columns go through
+ * the staging image as ever; `dictionaries` = 1 has no effect on such a column (no present or remap pass runs for it).
+ *
+ * Two more passes (fdb_pqbytes.hip; the rule: fdb_pqbytes.h) over tables of the entries' offsets and bytes, uploaded once per call and
+ * shared by its row groups: behind the survey a byte survey sums the entry lengths of every tile's non-NULL rows (its table comes back
+ * in the survey's wait; the host scans it into page sizes and per-tile byte bases) and, of a DELTA_LENGTH column, writes the rows'
+ * lengths as one more 64-bit column for the DELTA passes; after the layout a byte encode pass writes every tile's output range by OUTPUT
+ * position — each lane owns consecutive output bytes and finds the value they belong to in the tile's byte offsets — so stores are
+ * contiguous whatever the lengths are.
+ *
+ * `strings` == NULL, n_columns == 0 or every entry 0: fdb_batch_to_parquet_grouped's path and bytes, no launch, allocation, upload or
+ * wait more. Refused before anything is launched, after everything the calls above refuse: FDB_ERR_INVALID — n_columns neither 0 nor the
+ * column count, an entry outside 0 … 2, pad != 0; FDB_ERR_UNSUPPORTED, naming the column — a form on a column that is not a dictionary
+ * / string / binary column, `runs` bit 0 on a column with a form (it has no index pages). After the survey, before the image is
+ * allocated: FDB_ERR_INVALID, naming column and page — a page whose uncompressed body would not fit the i32 of its header. */
+typedef struct fdb_parquet_string_options {
+  const int8_t* forms;     /* per column: 0 = as ever (dictionary page + RLE_DICTIONARY), 1 = PLAIN, 2 = DELTA_LENGTH_BYTE_ARRAY */
+  int32_t n_columns;       /* 0 (all 0) or the record's column count */
+  int32_t pad;             /* 0 */
+} fdb_parquet_string_options;
+FDB_API int fdb_batch_to_parquet_strings(const fdb_batch* batch, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, const fdb_parquet_group_options* groups /* NULL: none */, const fdb_parquet_string_options* strings /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+FDB_API int fdb_selftest_parquet_write_strings(struct ArrowArray* batch, struct ArrowSchema* schema, const fdb_parquet_write_options* options, const int8_t* encodings, int32_t n_encodings, const int8_t* codecs, int32_t n_codecs, const fdb_parquet_index_options* index /* NULL: none */, const fdb_parquet_bloom_options* bloom /* NULL: none */, const fdb_parquet_run_options* runs /* NULL: none */, const fdb_parquet_group_options* groups /* NULL: none */, const fdb_parquet_string_options* strings /* NULL: none */, uint8_t** bytes, int64_t* n_bytes);
+
 /* Snappy pages inflated on the device (one wave per page, fdb_kernels.h snappy_decode_kernel) — the building block for pages that cross
  * PCIe compressed (pqarrow/arrow.go:711-823 inflates them on the host; so does fdb_batch_from_parquet today). This entry
  * point takes HOST buffers, for tests and measurement: `src` holds the compressed pages (pages[i] = {src_off, dst_off, src_len,

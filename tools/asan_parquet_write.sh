@@ -16,6 +16,9 @@
 # … and with group options at random — a row_group_rows that leaves one row group, dictionaries of used entries only: the present and
 # remap passes' host walk (fdb_pqdict.h), every re-keyed index checked, and a dictionary reader of the program's own finds in every
 # pruned chunk exactly the used entries.
+# … and with a string form drawn per byte-array column — dictionary, PLAIN or DELTA_LENGTH_BYTE_ARRAY: the byte survey's and the byte
+# encode pass's host walk (fdb_pqbytes.h), the lengths through the DELTA walk, and a PLAIN reader and a DELTA_LENGTH reader of the
+# program's own find every page's values in exactly the bytes the layout gave it.
 # No GPU, no HIP runtime (fdb_codec.h takes its types from the HIP headers), no python: a stand-alone program (tools/asan_parquet_write_main.cpp) is compiled with g++ and run. Prints "asan parquet write ok".
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -703,6 +703,74 @@ static void one_record(uint64_t* seed, int round) {
     }
     pqw_free_bytes(ufile);
   }
+  // … and with a string form drawn per byte-array column (fdb_pqbytes.h), beside runs on levels at random: the byte survey's walk and the
+  // host's scan of its table, the lengths as one more column of the DELTA walk, the byte encode walk word by word — and a PLAIN reader and
+  // a DELTA_LENGTH reader of the program's own find in every page the values of its non-NULL rows, in exactly the bytes the layout gave it
+  {
+    std::vector<int8_t> forms, level_flags;
+    for (size_t k = 0; k < n_cols; k++) forms.push_back((int8_t)(cols[k].kind == ColKind::DICT ? rnd(seed) % 3 : 0));
+    for (size_t k = 0; k < n_cols; k++) level_flags.push_back((int8_t)((rnd(seed) & 1) * 2));
+    const fdb_parquet_string_options sopt{forms.data(), (int32_t)n_cols, 0};
+    const fdb_parquet_run_options lopt{level_flags.data(), (int32_t)n_cols, 0};
+    spec.runs = (rnd(seed) & 1) ? &lopt : nullptr; spec.strings = &sopt;
+    PqwPlan sp = pqw_plan(in, rows, spec);
+    spec.runs = nullptr; spec.strings = nullptr;
+    size_t want_streams = 0;
+    for (size_t k = 0; k < n_cols; k++) want_streams += forms[k] != 0 && !cols[k].dict->values.empty();
+    CHECK(sp.n_bytes == want_streams && !sp.dict.any());
+    PqyPlan& y = sp.strings;
+    if (sp.n_bytes > 0) { pqy_survey_host(sp.cols, g, sp.n_bytes, &y); pqy_scan(g, sp.n_bytes, &y); }
+    PqdHost sdh;
+    pqd_survey_host(sp.cols, g, stats, tile_base, &sdh, &y);
+    PqrHost srh;
+    if (sp.n_runs > 0) pqr_survey_host(sp.cols, g, stats, &srh);
+    const PqwLayout S = pqw_layout(sp, PqwSizes{stats, &sdh.page_bytes, sp.n_runs > 0 ? &srh.page_bytes : nullptr, nullptr, sp.n_bytes > 0 ? &y.page_bytes : nullptr});
+    CHECK(S.parts[0].bytes_out.size() == sp.n_bytes * (size_t)g.n_pages);
+    std::vector<unsigned char> simage(((size_t)S.body_bytes + 8 + 3) / 4 * 4, 0);
+    pqw_encode_host(sp.cols, g, S.parts[0].out, tile_base, simage.data());
+    pqd_encode_host(sp.cols, g, stats, sdh, S.parts[0].delta_out, simage.data());
+    if (sp.n_runs > 0) pqr_encode_host(srh, S.parts[0].run_out, simage.data());
+    if (sp.n_bytes > 0) pqy_encode_host(sp.cols, g, y, S.parts[0].bytes_out, simage.data());
+    for (size_t b = (size_t)S.body_bytes; b < simage.size(); b++) CHECK(simage[b] == 0);
+    std::vector<uint8_t> own(S.body_bytes, 0);  // no byte of a stream is the host's
+    for (const PqwLayout::Piece& p : S.pieces) for (size_t b = 0; b < p.len; b++) { CHECK(p.off + b < S.body_bytes && own[p.off + b] == 0); own[p.off + b] = 1; }
+    for (size_t k = 0; k < n_cols; k++) {
+      const PqwColumn& c = sp.cols[k];
+      CHECK((c.bytes_slot >= 0) == (forms[k] != 0 && !cols[k].dict->values.empty()) && (c.bytes_slot < 0 || c.form == forms[k]));
+      CHECK((c.form == FDB_PQY_DELTA_LENGTH && c.bytes_slot >= 0) == (cols[k].kind == ColKind::DICT && c.delta_slot >= 0));
+      if (c.bytes_slot < 0) continue;
+      for (int64_t p = 0; p < g.n_pages; p++) {
+        const size_t at = (size_t)c.bytes_slot * (size_t)g.n_pages + (size_t)p;
+        std::vector<const std::string*> want;
+        std::vector<uint64_t> lens;
+        uint64_t total = 0;
+        for (int64_t r = fdb_pqw_page_first(g, p); r < fdb_pqw_page_end(g, p); r++)
+          if (cols[k].valid(r)) { want.push_back(&cols[k].dict->values[cols[k].idx[(size_t)r]]); lens.push_back(want.back()->size()); total += want.back()->size(); }
+        const uint64_t stream = total + (c.form == FDB_PQY_PLAIN ? 4 * want.size() : 0), off = S.parts[0].bytes_out[at];
+        CHECK(y.page_bytes[at] == stream && (off != FDB_PQW_NONE) == (stream > 0));
+        if (c.form == FDB_PQY_DELTA_LENGTH) {  // the lengths: a DELTA page of exactly the surveyed bytes, the byte stream right behind it
+          const size_t dat = (size_t)c.delta_slot * (size_t)g.n_pages + (size_t)p;
+          const uint64_t doff = S.parts[0].delta_out[dat], dbytes = sdh.page_bytes[dat];
+          CHECK(doff != FDB_PQW_NONE && doff + dbytes <= S.body_bytes && (stream == 0 || off == doff + dbytes));
+          const std::vector<uint8_t> exact(simage.begin() + (size_t)doff, simage.begin() + (size_t)(doff + dbytes));  // (sized exactly)
+          check_delta_page(exact.data(), exact.size(), lens);
+          if (want.empty()) CHECK(dbytes == 5 && std::memcmp(exact.data(), "\x80\x01\x04\x00\x00", 5) == 0);
+          for (uint64_t b = 0; b < dbytes; b++) { CHECK(own[doff + b] == 0); own[doff + b] = 6; }
+        }
+        if (stream == 0) continue;
+        CHECK(off + stream <= S.body_bytes);
+        for (uint64_t b = 0; b < stream; b++) { CHECK(own[off + b] == 0); own[off + b] = 7; }
+        const std::vector<uint8_t> exact(simage.begin() + (size_t)off, simage.begin() + (size_t)(off + stream));  // (sized exactly: a reader that runs past the stream is caught)
+        size_t rd = 0;
+        for (const std::string* v : want) {
+          if (c.form == FDB_PQY_PLAIN) { uint32_t len; std::memcpy(&len, exact.data() + rd, 4); CHECK(len == v->size()); rd += 4; }
+          CHECK(rd + v->size() <= exact.size() && std::memcmp(exact.data() + rd, v->data(), v->size()) == 0);
+          rd += v->size();
+        }
+        CHECK(rd == exact.size());
+      }
+    }
+  }
   // … and cut into several row groups — row_group_rows a multiple of 64 below the rows, the dictionaries whole or of used entries, runs at
   // random: the plan's parts (pqw_parts: the full groups as virtual columns, the shorter last group) walked pass by pass as the self-test
   // walks them, into ONE layout. Every group is then read back: its chunks follow each other from where the group before ended, every
@@ -908,6 +976,13 @@ static void refusals() {
   CHECK(group_code(fdb_parquet_group_options{-64, 0, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{63, 0, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{64, 0, 0}, 64 * 32767 + 1) == FDB_ERR_INVALID);
   CHECK(group_code(fdb_parquet_group_options{0, 2, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{0, -1, 0}, 8) == FDB_ERR_INVALID && group_code(fdb_parquet_group_options{0, 1, 1}, 8) == FDB_ERR_INVALID);
   CHECK(group_code(fdb_parquet_group_options{64, 0, 0}, 65) == FDB_OK && group_code(fdb_parquet_group_options{64, 1, 0}, 64 * 32767) == FDB_OK);  // several row groups, as many as an ordinal can say
+  const auto string_code = [&](const fdb_parquet_string_options& o, const fdb_parquet_run_options* r) {
+    try { std::vector<PqwColumn> c = pqw_columns(in, 8, PqwSpec{&plain_opt}, &pr); PqyPlan y; pqy_plan(&o, r, &c, &y); } catch (const Error& e2) { return e2.code; } return (int)FDB_OK;
+  };
+  CHECK(string_code(fdb_parquet_string_options{&none, 1, 0}, nullptr) == FDB_OK && string_code(fdb_parquet_string_options{nullptr, 0, 0}, nullptr) == FDB_OK);
+  CHECK(string_code(fdb_parquet_string_options{&delta, 1, 0}, nullptr) == FDB_ERR_UNSUPPORTED && string_code(fdb_parquet_string_options{&two, 1, 0}, nullptr) == FDB_ERR_UNSUPPORTED);  // a form on an int64 column
+  CHECK(string_code(fdb_parquet_string_options{&bad, 1, 0}, nullptr) == FDB_ERR_INVALID && string_code(fdb_parquet_string_options{&minus, 1, 0}, nullptr) == FDB_ERR_INVALID);
+  CHECK(string_code(fdb_parquet_string_options{both, 2, 0}, nullptr) == FDB_ERR_INVALID && string_code(fdb_parquet_string_options{nullptr, 1, 0}, nullptr) == FDB_ERR_INVALID && string_code(fdb_parquet_string_options{&none, 1, 1}, nullptr) == FDB_ERR_INVALID);
   in[0].kind = ColKind::F64;
   CHECK(enc_code(&delta, 1) == FDB_ERR_UNSUPPORTED && bloom_code(fdb_parquet_bloom_options{&delta, 1, 0}) == FDB_OK);
   in[0].kind = ColKind::BOOL;

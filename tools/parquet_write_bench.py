@@ -57,9 +57,17 @@ With --groups R the record is written in row groups of R rows (fdb_batch_to_parq
 with --used): ⌈rows / R⌉ row groups, every pass launched once for the full groups and once more for a shorter last one. The line's own
 figures are the grouped call's — its phases are the SUM of a call's marks, both launches — with row_groups, and the ungrouped call of the
 parent path on the same record in the same process goes into the line as with --delta, with its spread and plain_floor_ms.
+With --strings the record gets one more column, `id`: an all-distinct 16-byte binary value per row — what an id column is — and is written
+three times (fdb_batch_to_parquet_strings): `id` in the dictionary form (the call without the option: a dictionary page of every value
+plus indices), as "plain" and as "delta_length". Per form file_bytes, to_parquet_ms with its spread, the phases — among them
+bytes_survey_ms (the byte survey of fdb_pqbytes.hip with the wait for the survey's tables) and bytes_encode_ms — copy_ms and floor_ms, the
+bare device→host copy of that file's bytes; bytes_encode_gbs is the byte encode pass's rate over what it reads and writes (the value
+bytes twice, 4 B of index a row, with "plain" 4 B of length a value), beside copy_probe_gbs, the best `1 read : 1 written` line of
+--copy-probe (tools/copy_probe, built with hipcc first) run by the same command. The record WITHOUT `id`, written by this build without
+the option, goes into the same line as base_to_parquet_ms with its spread: what the parent commit's call is compared with.
 One JSON line on stdout, appended to --out (profiles/parquet_write_bench.jsonl) when given.
 
-    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --lz4 | --stats | --bloom | --runs | [--used [--fraction F]] [--groups R]] [--out FILE]
+    python tools/parquet_write_bench.py [--rows N] [--page-rows N] [--delta | --snappy | --lz4 | --stats | --bloom | --runs | [--used [--fraction F]] [--groups R] | --strings [--copy-probe FILE]] [--out FILE]
 """
 import argparse
 import io
@@ -90,6 +98,8 @@ BLOOM_PHASES = ["bloom insert", "bloom copy"]
 BLOOM_COLUMNS = ["timestamp", "labels.l4"]
 RUN_PHASES = ["run survey", "run encode"]
 DICT_PHASES = ["dict present", "dict remap"]
+BYTES_PHASES = ["bytes survey", "bytes encode"]
+ID_BYTES = 16
 
 
 def make_record(rows: int, seed: int = 1, fraction: float = 1.0) -> pa.RecordBatch:
@@ -120,7 +130,7 @@ def median_ms(fn, reps, warmup):
     return statistics.median(times), times
 
 
-def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None, runs=None, dictionaries=None, groups=0):
+def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats=None, bloom=None, runs=None, dictionaries=None, groups=0, strings=None):
     """The library's FDB_PROFILE lines of `reps` to_parquet() calls: {phase: median ms} — with `groups`, where a call marks a pass once
     per launch, the marks' sum per call."""
     os.environ["FDB_PROFILE"] = "1"
@@ -130,7 +140,7 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         os.dup2(tmp.fileno(), 2)
         try:
             for _ in range(reps):
-                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs, dictionaries=dictionaries, row_group_rows=groups)
+                rb.to_parquet(page_rows=page_rows, encodings=encodings, compression=compression, statistics=stats, bloom_filters=bloom, runs=runs, dictionaries=dictionaries, row_group_rows=groups, strings=strings)
         finally:
             os.dup2(saved, 2)
             os.close(saved)
@@ -138,10 +148,103 @@ def profiled_phases(rb, page_rows, reps, encodings=None, compression=None, stats
         tmp.seek(0)
         text = tmp.read().decode("utf-8", "replace")
     out = {}
-    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + LZ4_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES + DICT_PHASES:
+    for phase in PHASES + DELTA_PHASES + SNAPPY_PHASES + LZ4_PHASES + STATS_PHASES + BLOOM_PHASES + RUN_PHASES + DICT_PHASES + BYTES_PHASES:
         us = [float(m) for m in re.findall(r"\[fdb\] pqwrite %s\s+([0-9.]+) us" % re.escape(phase), text)]
         out[phase] = (sum(us) / reps if groups else statistics.median(us)) / 1e3 if us else None
     return out
+
+
+def id_column(rows: int) -> pa.Array:
+    """`rows` distinct binary values of ID_BYTES bytes: the hex digits of a bijection of the row number."""
+    v = np.arange(rows, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    digits = np.empty((rows, ID_BYTES), dtype=np.uint8)
+    for k in range(ID_BYTES):
+        nib = ((v >> np.uint64(4 * k)) & np.uint64(15)).astype(np.uint8)
+        digits[:, ID_BYTES - 1 - k] = np.where(nib < 10, nib + 48, nib + 87)
+    offsets = (np.arange(rows + 1, dtype=np.int64) * ID_BYTES).astype(np.int32 if rows * ID_BYTES < 2**31 else np.int64)
+    typ = pa.binary() if offsets.dtype == np.int32 else pa.large_binary()
+    return pa.Array.from_buffers(typ, rows, [None, pa.py_buffer(offsets.tobytes()), pa.py_buffer(digits.tobytes())])
+
+
+def copy_probe_gbs(path):
+    """The best GB/s among copy_probe's `1 read : 1 written` lines, or None without the probe."""
+    import subprocess
+    if not path or not os.path.exists(path):
+        return None
+    out = subprocess.run([path], check=True, capture_output=True, text=True, timeout=120).stdout
+    rates = [float(m.group(1)) for ln in out.splitlines() if "(1 read : 1 written)" in ln for m in [re.search(r"([0-9.]+) GB/s", ln)] if m]
+    return max(rates) if rates else None
+
+
+def strings_main(args):
+    import ctypes
+    base = make_record(args.rows)
+    record = base.append_column("id", id_column(args.rows))
+    r3 = lambda v: None if v is None else round(v, 3)  # noqa: E731
+    line = {"tool": "parquet_write_bench", "strings": "id", "rows": args.rows, "page_rows": args.page_rows or 65536, "columns": record.num_columns, "id_bytes": ID_BYTES,
+            "reps": args.reps, "warmup": args.warmup, "date": time.strftime("%Y-%m-%d")}
+
+    def bare_copy_ms(n_bytes):
+        dev = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+        host = torch.empty(n_bytes, dtype=torch.uint8).pin_memory()
+
+        def bare_copy():
+            host.copy_(dev, non_blocking=True)
+            torch.cuda.synchronize()
+        return median_ms(bare_copy, args.reps, args.warmup)[0]
+
+    def measure(rb, form, prefix):
+        names = rb.column_names
+        data = rb.to_parquet(page_rows=args.page_rows, strings={"id": form} if form else None)
+        want = len(data)
+        md = pq.ParquetFile(io.BytesIO(data)).metadata
+        assert md.num_rows == args.rows
+        if form:
+            col = md.row_group(0).column(names.index("id"))
+            assert not col.has_dictionary_page and col.encodings[0] == ("PLAIN" if form == "plain" else "DELTA_LENGTH_BYTE_ARRAY"), col.encodings
+        del data
+        opts = pp.ParquetWriteOptions(args.page_rows, 0, None)
+        forms = (ctypes.c_int8 * len(names))(*[pp.PARQUET_STRING_FORMS[form] if n == "id" else 0 for n in names])
+        sopt = pp.ParquetStringOptions(ctypes.cast(forms, ctypes.c_void_p), len(names), 0)
+
+        def c_call():
+            out, n = ctypes.c_void_p(), ctypes.c_int64()
+            if form:
+                rc = pp.lib().fdb_batch_to_parquet_strings(rb.handle, ctypes.byref(opts), None, 0, None, 0, None, None, None, None, ctypes.byref(sopt), ctypes.byref(out), ctypes.byref(n))
+            else:
+                rc = pp.lib().fdb_batch_to_parquet(rb.handle, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n))
+            assert rc == 0 and n.value == want, pp.lib().fdb_last_error()
+            pp.lib().fdb_bytes_free(out.value)
+        ms, every = median_ms(c_call, args.reps, args.warmup)
+        ph = profiled_phases(rb, args.page_rows, args.reps, strings={"id": form} if form else None)
+        line.update({prefix + "file_bytes": want, prefix + "to_parquet_ms": r3(ms), prefix + "to_parquet_min_ms": r3(min(every)), prefix + "to_parquet_max_ms": r3(max(every)),
+                     prefix + "floor_ms": r3(bare_copy_ms(want))})
+        line.update({prefix + k.replace(" ", "_") + "_ms": r3(ph[k]) for k in PHASES + (BYTES_PHASES if form else [])})
+        if form and ph["bytes encode"]:
+            moved = args.rows * (2 * ID_BYTES + 4 + (4 if form == "plain" else 0))
+            line[prefix + "bytes_encode_gbs"] = round(moved / (ph["bytes encode"] * 1e-3) / 1e9, 1)
+
+    rb = pp.ResidentBatch(base)
+    try:
+        measure(rb, None, "base_")
+    finally:
+        rb.close()
+    del base
+    rb = pp.ResidentBatch(record)
+    del record
+    try:
+        for form, prefix in ((None, "dictionary_"), ("plain", "plain_"), ("delta_length", "delta_length_")):
+            measure(rb, form, prefix)
+    finally:
+        rb.close()
+    probe = copy_probe_gbs(args.copy_probe)
+    line["copy_probe_gbs"] = None if probe is None else round(probe, 1)
+    text = json.dumps(line)
+    print(text, flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+    assert pp.live_allocations()["device_blocks"] == 0
 
 
 def main():
@@ -160,8 +263,13 @@ def main():
     ap.add_argument("--used", action="store_true", help="write dictionaries of used entries only (uncompressed); the call with the whole dictionaries goes into the same line")
     ap.add_argument("--fraction", type=float, default=1.0, help="with --used: the label columns name only every ceil(1/F)-th entry of their dictionaries")
     ap.add_argument("--groups", type=int, default=0, help="write row groups of this many rows (a multiple of 64; alone or with --used); the ungrouped call goes into the same line")
+    ap.add_argument("--strings", action="store_true", help="add an all-distinct 16-byte `id` column and write it as a dictionary, PLAIN and DELTA_LENGTH_BYTE_ARRAY; the record without it goes into the same line")
+    ap.add_argument("--copy-probe", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "copy_probe"), help="with --strings: tools/copy_probe, built with hipcc (its best copy line goes into the line)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.strings:
+        assert args.delta + args.snappy + args.lz4 + args.stats + args.bloom + args.runs + args.used == 0 and args.groups == 0, "--strings stands alone"
+        return strings_main(args)
     assert args.delta + args.snappy + args.lz4 + args.stats + args.bloom + args.runs + args.used <= 1, "--delta, --snappy, --lz4, --stats, --bloom, --runs or --used"
     assert 0.0 < args.fraction <= 1.0 and (args.used or args.fraction == 1.0), "--fraction goes with --used"
     assert args.groups == 0 or (args.groups > 0 and args.groups % 64 == 0 and args.delta + args.snappy + args.lz4 + args.stats + args.bloom + args.runs == 0), "--groups R: a multiple of 64, alone or with --used"
